@@ -55,8 +55,11 @@ def make_variant(tag, seed, gain, n=64):
     logits = model(xf, True).numpy()
     enc, _ = model.encoder(xf[:2])
     dec, _ = model.decoder(enc)
+    # the same forward in float64: what a port must reproduce whatever CPU runs it (float32 results move with the CPU's
+    # thread count and vector width, by up to a few 1e-6 at gain 3)
+    probs64 = model.double()(xf.double(), False).numpy()
     np.savez_compressed(os.path.join(OUT, f"variant_{tag}.npz"), seed=seed, gain=gain, images=x,
-                        probs=probs, logits=logits, enc2=enc.numpy(), dec2=dec.numpy())
+                        probs=probs, logits=logits, enc2=enc.numpy(), dec2=dec.numpy(), probs64=probs64)
     print(tag, "probs[4:7]", probs[4:7])
 
 

@@ -18,8 +18,11 @@ def _bench():
 
 def test_help_and_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, check=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--model", "--resident-only", "--full-line", "--legs", "--no-image-legs"):
+    for flag in ("--gpus", "--steps", "--warmup", "--model", "--resident-only", "--full-line", "--legs", "--no-image-legs",
+                 "--dump-outputs"):
         assert flag in out
+    bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True)
+    assert bad.returncode == 2 and "--steps" in bad.stderr                  # a run always times the steps it was asked for
 
 
 def test_traffic_comes_from_the_committed_pmc_passes():
@@ -137,3 +140,32 @@ def test_counters_know_when_they_are_older_than_the_kernel():
     assert b.counters_stale(99, "inflate.hip", "realign.hip") is False
     path, rnd = b.newest_profile("variant_pmc.json")
     assert path.startswith("profiles/r") and rnd >= 5 and b.newest_profile("no_such_profile.txt") == (None, 0)
+
+
+def test_dump_outputs_writes_what_the_caller_receives(tmp_path):
+    """--dump-outputs: the last timed step's results as float32 .npy files, every value as the caller received it; outputs past
+    64 MB (the polish step's labels and phred) as the same fixed, seeded sample of units from each, the units' indices beside them."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(0)
+    probs = rng.random((1 << 18, 3), dtype=np.float32)
+    assert b.dump_outputs(str(tmp_path / "v"), {"probabilities": probs}) == {"probabilities.npy": [1 << 18, 3]}
+    assert np.array_equal(np.load(tmp_path / "v" / "probabilities.npy"), probs)
+    labels = rng.integers(0, 5, (32768, 1000), dtype=np.uint8)
+    phred = rng.integers(0, 256, (32768, 1000), dtype=np.uint8)
+    for rank, world in ((0, 1), (3, 8)):
+        d = tmp_path / ("p%d" % world)
+        sfx = "_rank%d" % rank if world > 1 else ""
+        written = b.dump_outputs(str(d), {"labels": labels, "phred": phred}, rank, world)
+        assert sorted(written) == sorted(n + sfx + ".npy" for n in ("labels", "phred", "units"))
+        assert sum(f.stat().st_size for f in d.iterdir()) <= b.DUMP_LIMIT_BYTES // world
+        units = np.load(d / ("units%s.npy" % sfx))
+        assert units.dtype == np.float64 and len(units) > 0.9 * (b.DUMP_LIMIT_BYTES // world) / 8000
+        idx = units.astype(np.int64)
+        assert np.array_equal(idx, units) and np.all(np.diff(idx) > 0) and idx[-1] < 32768
+        for name, full in (("labels", labels), ("phred", phred)):
+            got = np.load(d / ("%s%s.npy" % (name, sfx)))
+            assert got.dtype == np.float32 and np.array_equal(got, full[idx].astype(np.float32))
+    again = b.dump_outputs(str(tmp_path / "again"), {"labels": labels, "phred": phred})
+    assert again == b.dump_outputs(str(tmp_path / "p1"), {"labels": labels, "phred": phred})
+    assert np.array_equal(np.load(tmp_path / "again" / "units.npy"), np.load(tmp_path / "p1" / "units.npy"))     # the same sample
