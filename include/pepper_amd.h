@@ -68,6 +68,15 @@ int pa_variant_overflow_rows(pa_variant_model* m, int64_t* rows);
  * return when their results are in the output buffers. */
 int pa_variant_split_fallbacks(pa_variant_model* m, int64_t* calls);
 
+/* Batch-invariant mode (off at creation; PEPPER_AMD_BATCH_INVARIANT=1 in the environment turns it on for every handle the
+ * Python wrappers make).  On: every output element of the int8 entry points (pa_variant_forward_device / _host) is a pure
+ * function of the weights and its own window -- the same bits whatever the call size, max_chunk, the window's position and
+ * neighbours in the call, and the handle's earlier calls.  Small calls then run the arithmetic of a full 16 384-window
+ * pass (up to 3 072 windows in 32-row step loops that give the same bits; slower than the default small-call schedule).  It may be switched between calls; the f32-input entry point is not covered.
+ * on: 0 / 1.  Null or foreign handles fail with PA_ERR_INVALID. */
+int pa_variant_set_batch_invariant(pa_variant_model* m, int32_t on);
+int pa_variant_get_batch_invariant(pa_variant_model* m, int32_t* on);
+
 /* forward(x, train_mode=False): images int8 [n, window, image_features] (the dtype the images
  * HDF5 stores: pepper_variant/modules/python/DataStore.py:68) -> probs float32 [n, classes].
  * logits (pre-softmax, = forward(x, train_mode=True)) may be NULL.  All pointers are DEVICE
@@ -135,6 +144,14 @@ int pa_polish_predict_host(pa_polish_model* m, const uint8_t* images, int64_t n,
  * reference's DataLoader(num_workers) (predict_distributed_gpu.py:40-47) -- hand them over together. */
 int pa_polish_predict_host_parts(pa_polish_model* m, int32_t n_parts, const uint8_t* const* images, const int64_t* counts,
                                  uint8_t* const* labels, uint8_t* const* phred);
+
+/* Batch-invariant mode of the polish handle (see pa_variant_set_batch_invariant): with it on, the labels, phred and acc of
+ * pa_polish_predict_device / _host / _host_parts for a chunk depend on that chunk alone, however the chunks are cut into
+ * calls and parts.  Calls of at most 4 096 chunks then run the big-call schedule.  pa_polish_forward_device is not covered.
+ * A handle on the exact-f32 GRU kernels (a weight >= 64, hidden size 256, PA_SPLIT_GEMM=0 / PA_SPLIT_REC=0 at creation)
+ * cannot take the mode: turning it on fails with PA_ERR_UNSUPPORTED and the handle stays as it was. */
+int pa_polish_set_batch_invariant(pa_polish_model* m, int32_t on);
+int pa_polish_get_batch_invariant(pa_polish_model* m, int32_t* on);
 
 /* ------------------------------------------------------------------------------------------
  * Per-kernel timing with HIP events recorded on the handle's own stream (what bench.py's

@@ -39,6 +39,8 @@ SYMBOLS = [
     ("pa_variant_destroy", None, [c_void_p]),
     ("pa_variant_overflow_rows", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64)]),
     ("pa_variant_split_fallbacks", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64)]),
+    ("pa_variant_set_batch_invariant", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_variant_get_batch_invariant", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int32)]),
     ("pa_variant_forward_device", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     ("pa_variant_forward_device_f32", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     ("pa_variant_forward_host", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
@@ -51,6 +53,8 @@ SYMBOLS = [
     ("pa_polish_predict_device", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     ("pa_polish_predict_host", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     ("pa_polish_predict_host_parts", ctypes.c_int, [c_void_p, ctypes.c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("pa_polish_set_batch_invariant", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_polish_get_batch_invariant", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int32)]),
     ("pa_profile_enable", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_profile_count", ctypes.c_int, [c_void_p]),
     ("pa_profile_get", ctypes.c_int, [c_void_p, c_int32, c_char_p, c_int32, ctypes.POINTER(c_double),
@@ -148,6 +152,33 @@ PA_ERR_INVALID = 1
 PA_ERR_HIP = 2
 PA_ERR_NO_DEVICE = 3
 PA_ERR_UNSUPPORTED = 4
+
+
+BATCH_INVARIANT_ENV = "PEPPER_AMD_BATCH_INVARIANT"
+
+
+def parse_batch_invariant(value):
+    """A batch_invariant option or the value of PEPPER_AMD_BATCH_INVARIANT -> bool.  None / "" -> False; accepts bools,
+    0 / 1 and the words true / false, yes / no, on / off (any case); anything else is a ValueError."""
+    if value is None or isinstance(value, bool):
+        return bool(value)
+    if isinstance(value, int):
+        if value in (0, 1):
+            return bool(value)
+        raise ValueError(f"batch_invariant must be 0 or 1, got {value!r}")
+    v = str(value).strip().lower()
+    if v in ("", "0", "false", "no", "off"):
+        return False
+    if v in ("1", "true", "yes", "on"):
+        return True
+    raise ValueError(f"batch_invariant: cannot read {value!r} as on / off")
+
+
+def batch_invariant_default(value=None):
+    """What a new handle uses: `value` when given (not None), else the process-wide PEPPER_AMD_BATCH_INVARIANT."""
+    if value is not None:
+        return parse_batch_invariant(value)
+    return parse_batch_invariant(os.environ.get(BATCH_INVARIANT_ENV))
 
 
 def check(rc):

@@ -512,6 +512,11 @@ struct pa_variant_model : ModelBase {
     int split_sabotage = 0;           // PA_UNIT_SPLIT_SABOTAGE=n (tests): in the next n split launches one member never arrives
     DevBuf *us_exch = nullptr, *us_cnt = nullptr, *us_failed = nullptr;
     int* us_host = nullptr;           // page-locked: [0] the kernel's failure flag, [1] the out-of-range row counter before the call
+    // Batch-invariant mode (pa_variant_set_batch_invariant): every call runs the arithmetic of a full 16 384-window
+    // pass -- fused decoder, no unit split; up to `small_rows` windows the same step loops in 32-row workgroups -- with linear_1
+    // on the fixed K partition below and the MLP tail re-running only the rows that left the f16 range; a window's bits are
+    // then a function of that window alone.
+    bool batch_invariant = false;
     ~pa_variant_model() override {
         if (us_host) (void)hipHostFree(us_host);
     }
@@ -625,6 +630,10 @@ void pa_variant_destroy(pa_variant_model* m) {
 }
 
 constexpr int US_HOLDOFF = 256;
+// linear_1's K slices in batch-invariant mode: what a full 16 384-window pass picks by itself (128 output tiles x 2 slices
+// fill the 256 CUs), fixed so that the k ranges, and the order in which splitk_finish_kernel adds the slices and then the
+// bias, never depend on the call size or on the workspace a handle happens to hold.
+constexpr int kCanonicalL1Splits = 2;
 
 static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* images, int64_t n,
                                  float* probs, float* logits, bool allow_split = true) {
@@ -639,12 +648,16 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     // decoder's input projection runs as one GEMM over all T steps on the whole chip instead (0.13 ms at 512 windows) and the
     // step loop contracts K = 256 only (14.7 us per step): 512 windows 2.16 -> 1.42 ms, 1024: 2.17 -> 1.59, 2048: 2.18 -> 1.83;
     // at 4096 the fused loop wins again (profiles/r03_small_batch_kernels.json).  PA_SMALL_BATCH=0: always fused.
-    const bool fuse_dec = m->fuse_dec && n > m->small_batch;
+    const bool bi = m->batch_invariant;
+    const bool fuse_dec = m->fuse_dec && (bi || n > m->small_batch);
     // ... and, up to `small_rows` windows, both step loops run with 32-row workgroups (rnn_h2.hip MTILES = 1): a step is one
     // CU's affair, half the rows are half the MFMAs and half the gate phase per step (PA_SMALL_ROWS, 0 = never)
+    // (batch-invariant mode too: the 32-row workgroups issue every row's MFMA chain and gate arithmetic exactly as the 64-row
+    // ones do -- tests/test_gpu_batch_invariant.py holds them to the bits of a full pass -- and there the fused decoder takes
+    // them as well)
     const bool small_rows = n <= m->small_rows;
     // up to 1024 windows: every layer as projection GEMM + the unit-split step loop (see pa_variant_model::unit_split)
-    bool unit_split = allow_split && m->unit_split && n <= m->unit_split_max && H == 256 && m->split_rec && !fuse_dec && m->mlp_w32 != nullptr &&
+    bool unit_split = allow_split && !bi && m->unit_split && n <= m->unit_split_max && H == 256 && m->split_rec && !fuse_dec && m->mlp_w32 != nullptr &&
                       m->mlp_w != nullptr && C <= 8;
     for (const RecLayer& r : m->rec) unit_split = unit_split && r.w_hh_h2 != nullptr && r.prescaled;
     // the members of a group wait for each other: every workgroup of the launch must be on the device at once (a CPX
@@ -704,7 +717,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
             // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
             LAUNCH_TRY(m, "lstm_dec_h2_fused", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
                        pa::launch_lstm_dec_h2(H, cur, cur_ld, bias_l, r.w_cat_dec_h2->p, y, 2 * H, (int)n, T, m->stream,
-                                              r.prescaled));
+                                              r.prescaled, bi && small_rows));
         } else {
             if (li > 0 && m->split_gemm && r.w_ih_h2 != nullptr) {
                 // the previous layer's y is only read by this projection: if it is still f32, split it
@@ -751,8 +764,9 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     // (up to 32 slices: a call of 512 windows has 4 output tiles, 0.137 ms with 8 slices, 0.078 with 32; big calls have tiles
     // enough and stay at 2 slices.  PA_L1_SPLITS overrides the cap)
     static const int max_splits = getenv("PA_L1_SPLITS") ? atoi(getenv("PA_L1_SPLITS")) : 32;
-    while (splits < max_splits && tiles1 * splits * 2 <= 256 && (size_t)(splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
+    while (!bi && splits < max_splits && tiles1 * splits * 2 <= 256 && (size_t)(splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
         splits *= 2;
+    if (bi) splits = kCanonicalL1Splits;   // (the workspace holds 8 x n x L1 floats: room for them at any n)
     if (m->split_gemm && m->lin[0].w_h2 != nullptr && cur_kind == pa::A_F32) {
         if (!cur_h2)
             LAUNCH_TRY(m, "cvt_h2", 0.0,
@@ -770,7 +784,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         LAUNCH_TRY(m, "mlp_tail_h2", 2.0 * n * m->L1 * (4.0 * m->L1 + C),
                    pa::launch_mlp_tail_h2(m->l1->f(), m->L1, m->mlp_w->p, m->mlp_b->f(), 4, m->out.w->f(), m->out.b->f(), C,
                                           probs, logits, (int)n, m->stream, static_cast<const float* const*>(m->mlp_w32->p),
-                                          reinterpret_cast<int*>(static_cast<char*>(m->mlp_w32->p) + 4 * sizeof(float*))));
+                                          reinterpret_cast<int*>(static_cast<char*>(m->mlp_w32->p) + 4 * sizeof(float*)), bi));
         if (unit_split) {
             // did every group of the split step loops meet?  (one synchronise per small call: 10-20 us beside its 0.65 ms)
             HIP_TRY(hipMemcpyAsync(&m->us_host[0], m->us_failed->p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
@@ -818,6 +832,19 @@ static int variant_forward(pa_variant_model* m, int a_kind, const void* images, 
 int pa_variant_split_fallbacks(pa_variant_model* m, int64_t* calls) {
     if (!m || m->magic != 0x50414d44 || !calls) return fail(PA_ERR_INVALID, "bad argument");
     *calls = m->split_fallbacks;
+    return PA_OK;
+}
+
+int pa_variant_set_batch_invariant(pa_variant_model* m, int32_t on) {
+    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (on != 0 && on != 1) return fail(PA_ERR_INVALID, "pa_variant_set_batch_invariant: on must be 0 or 1");
+    m->batch_invariant = on != 0;
+    return PA_OK;
+}
+
+int pa_variant_get_batch_invariant(pa_variant_model* m, int32_t* on) {
+    if (!m || m->magic != 0x50414d44 || !on) return fail(PA_ERR_INVALID, "bad model handle");
+    *on = m->batch_invariant ? 1 : 0;
     return PA_OK;
 }
 
@@ -903,6 +930,7 @@ struct pa_polish_model : ModelBase {
     bool y_h2 = false;           // format of the last polish_window output
     bool fuse_head = true;       // PA_FUSE_HEAD=0: last decoder layer writes y, dense1 + softmax + overlap-add as their own kernel
     int small_max = 4096;        // calls of at most this many chunks take the small-call schedule (PA_POLISH_SMALL_MAX; 0: never)
+    bool batch_invariant = false; // pa_polish_set_batch_invariant: every call takes the big-call schedule
     std::vector<RecLayer> enc, dec;
     Linear dense;
     DevBuf *dense_h2 = nullptr;  // dense1 as h2 fragments of the 16x16x32 tile (rnn_h2.hip pack_dense_head_h2)
@@ -945,7 +973,7 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
                                      (r.K <= 16 || ((xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(cur) & 3) == 0));
             // Small calls: a step's latency is what counts (19 windows x 200 dependent steps whatever n is), so the projections
             // run as GEMMs over all T steps and the step loops as 16-row workgroups with their weights in registers
-            const bool small = m->small_max > 0 && n <= m->small_max && rec_h2 && r.w_hh_small_h2 != nullptr && H == 128 &&
+            const bool small = !m->batch_invariant && m->small_max > 0 && n <= m->small_max && rec_h2 && r.w_hh_small_h2 != nullptr && H == 128 &&
                                (cur_h2 ? (r.w_ih_h2 != nullptr && m->split_gemm) : (stage == 0 && l == 0));
             if (small) {
                 if (cur_h2)
@@ -1279,6 +1307,26 @@ int pa_polish_predict_host_parts(pa_polish_model* m, int32_t n_parts, const uint
     if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
     if (n_parts < 0 || (n_parts > 0 && (!images || !counts || !labels || !phred))) return fail(PA_ERR_INVALID, "bad argument");
     return polish_predict_host_impl(m, n_parts, images, counts, labels, phred, nullptr);
+}
+
+int pa_polish_set_batch_invariant(pa_polish_model* m, int32_t on) {
+    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (on != 0 && on != 1) return fail(PA_ERR_INVALID, "pa_polish_set_batch_invariant: on must be 0 or 1");
+    // The f32 recurrences (a checkpoint with a weight >= kSplitMaxWeight, PA_SPLIT_GEMM=0 / PA_SPLIT_REC=0, hidden size 256)
+    // were measured NOT to give a chunk the same bits at every call size (tests/test_gpu_batch_invariant.py): the mode is
+    // refused there rather than promised.
+    if (on && !m->split_rec)
+        return fail(PA_ERR_UNSUPPORTED, "pa_polish_set_batch_invariant: this handle runs the exact-f32 GRU kernels (largest weight >= " +
+                                            std::to_string((int)kSplitMaxWeight) + ", hidden size 256, or PA_SPLIT_GEMM=0 / PA_SPLIT_REC=0), "
+                                            "whose results depend on the call size; batch-invariant mode needs the split-f16 kernels");
+    m->batch_invariant = on != 0;
+    return PA_OK;
+}
+
+int pa_polish_get_batch_invariant(pa_polish_model* m, int32_t* on) {
+    if (!m || m->magic != 0x50414d44 || !on) return fail(PA_ERR_INVALID, "bad model handle");
+    *on = m->batch_invariant ? 1 : 0;
+    return PA_OK;
 }
 
 // ---- profiler / sync -----------------------------------------------------------------------------

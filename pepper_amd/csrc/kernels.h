@@ -76,7 +76,7 @@ hipError_t launch_lstm_rec_h2_split(int H, const float* Xp, int ldx, const void*
 // LSTM layer fed by an h2 layer output Xh [B*T, 2H]: projection contracted inside the step loop (weights packed
 // with pack_rec_weights_h2(..., F = 2H, KX = 2H); bias = b_ih + b_hh).
 hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias, const void* Wp, void* Y, int ldy, int B,
-                              int T, hipStream_t stream, bool prescaled);
+                              int T, hipStream_t stream, bool prescaled, bool small = false);   // small: 32-row workgroups
 // GRU (H = 128) counterpart; arguments as launch_gru_rec / launch_gru_rec_fused, Y in h2 format.
 hipError_t launch_gru_rec_h2(int H, const float* Xp, int ldx, const uint8_t* X, int F, int64_t x_bstride,
                              const float* bias, const void* Wp, const float* bhn, const float* h0, int ldh0, float* hn,
@@ -113,9 +113,11 @@ void pack_mlp_weights_h2(const float* const* W, int NL, uint32_t* out, float* sc
 size_t mlp_weights_h2_words(int NL);
 // W32: DEVICE array of the NL f32 weight matrices [512][512] (the exact re-run of a 64-row tile in which an activation left the
 // f16 range: >= 65504 or NaN); overflow_rows (device counter, may be null) counts the rows that took it.
+// per_row (batch-invariant mode): only the rows that left the range take the f32 result, the others keep their split-f16
+// bits, so no row's result depends on its neighbours in the tile.
 hipError_t launch_mlp_tail_h2(const float* X, int ldx, const void* Wp, const float* bias, int NL, const float* Wout,
                               const float* bout, int C, float* probs, float* logits, int n, hipStream_t stream,
-                              const float* const* W32, int* overflow_rows);
+                              const float* const* W32, int* overflow_rows, bool per_row = false);
 
 // head.hip
 hipError_t launch_dense_small(int mode, const float* X, int ldx, const float* W, const float* bias,

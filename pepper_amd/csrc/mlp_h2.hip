@@ -23,7 +23,10 @@ constexpr int ROWB = D * 4 + 16, ROWD = ROWB / 4;      // 2064-byte rows: odd nu
 
 PA_DEV f32x16 mfma_h(h8 a, h8 b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
 
-template <int NL>
+// PERROW (batch-invariant mode): a flag per row in LDS behind the rows records which rows saw an out-of-range activation;
+// only those rows take the f32 re-run's result, every other row keeps its split-f16 bits (written before the re-run
+// overwrites the LDS rows), so a row's result never depends on the other 63 rows of its tile.
+template <int NL, bool PERROW = false>
 __global__ __launch_bounds__(512, 1) void mlp_tail_h2_kernel(const float* __restrict__ X, int ldx,
                                                              const uint32_t* __restrict__ Wp,      // [NL][16][32][2][64][4] dwords
                                                              const float* __restrict__ bias,       // [NL][512] x scale | [NL] 1 / scale | [NL][512] as given
@@ -43,6 +46,7 @@ __global__ __launch_bounds__(512, 1) void mlp_tail_h2_kernel(const float* __rest
     // value, and a workgroup that saw one re-runs its 64 rows with plain f32 arithmetic at the end (simple_model.py:60-78 is
     // f32 throughout): never a silent inf / NaN.
     bool bad = false;
+    uint32_t* rowbad = lds + MT * ROWD;                // PERROW: [MT] flags
     // ---- stage the f32 input rows as h2: thread = (row, eight groups of 8 columns) ----
     {
         const int row = tid >> 3, gsel = tid & 7;              // 64 rows x 8 threads
@@ -64,6 +68,13 @@ __global__ __launch_bounds__(512, 1) void mlp_tail_h2_kernel(const float* __rest
             }
             *reinterpret_cast<h8*>(lds + row * ROWD + g * 8) = hi;
             *reinterpret_cast<h8*>(lds + row * ROWD + g * 8 + 4) = lo;
+        }
+        if (PERROW) {      // the row's 8 threads are neighbouring lanes: their OR, written by the first (sets every flag)
+            int b8 = bad ? 1 : 0;
+            b8 |= __shfl_xor(b8, 1, 64);
+            b8 |= __shfl_xor(b8, 2, 64);
+            b8 |= __shfl_xor(b8, 4, 64);
+            if (gsel == 0) rowbad[row] = (uint32_t)b8;
         }
     }
     __syncthreads();
@@ -140,17 +151,74 @@ __global__ __launch_bounds__(512, 1) void mlp_tail_h2_kernel(const float* __rest
                 for (int r = 0; r < 16; ++r) {
                     const float v = selu_f(acc[m][nn][r] * unscale);
                     bad |= !(fabsf(v) < 65504.0f);
+                    if (PERROW && !(fabsf(v) < 65504.0f)) rowbad[4 * hf + 32 * m + (r & 3) + 8 * (r >> 2)] = 1u;
                     dst[(32 * m + (r & 3) + 8 * (r >> 2)) * ROWD] = h2_word_of(v, h2_select(odd));
                 }
         }
         lds_barrier();                      // next layer's input visible
     }
 
+    // ---- output layer + softmax: wave w takes rows 8w .. 8w+7, lane = one group of 8 columns ----
+    // from_f32: the rows' activations are the f32 re-run's (below), else the h2 rows of the last layer
+    float* frow = reinterpret_cast<float*>(lds);       // the same 2064-byte rows, now [64][516] f32
+    auto head = [&](bool from_f32, bool select) {
+        float wo[8][8];
+#pragma unroll
+        for (int c = 0; c < 8; ++c)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) wo[c][e] = c < C ? Wout[(size_t)c * D + lane * 8 + e] : 0.0f;
+        for (int rr = 0; rr < 8; ++rr) {
+            const int row = 8 * w + rr;
+            if (PERROW && select && (rowbad[row] != 0) != from_f32) continue;     // (uniform over the wave)
+            const h8 hi = *reinterpret_cast<const h8*>(lds + row * ROWD + lane * 8);
+            const h8 lo = *reinterpret_cast<const h8*>(lds + row * ROWD + lane * 8 + 4);
+            float x[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) x[e] = from_f32 ? frow[row * ROWD + lane * 8 + e] : (float)hi[e] + (float)lo[e];
+            float logit[8], mx = -INFINITY;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                float p = 0.0f;
+#pragma unroll
+                for (int e = 0; e < 8; ++e) p += x[e] * wo[c][e];
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
+                logit[c] = c < C ? p + bout[c < C ? c : 0] : -INFINITY;
+                mx = fmaxf(mx, logit[c]);
+            }
+            float e[8], den = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c) {
+                e[c] = c < C ? expf(logit[c] - mx) : 0.0f;
+                den += e[c];
+            }
+            float my_logit = 0.0f, my_e = 0.0f;
+#pragma unroll
+            for (int c = 0; c < 8; ++c)
+                if (lane == c) { my_logit = logit[c]; my_e = e[c]; }
+            const int grow = b0 + row;
+            if (grow < n && lane < C) {
+                probs[(size_t)grow * C + lane] = my_e / den;
+                if (logits != nullptr) logits[(size_t)grow * C + lane] = my_logit;
+            }
+        }
+    };
+
     // ---- out-of-range activations somewhere in these 64 rows: the layers again, in f32, from the f32 input ----
     const bool rerun = __syncthreads_or(bad ? 1 : 0) != 0;
-    float* frow = reinterpret_cast<float*>(lds);       // the same 2064-byte rows, now [64][516] f32
+    if (PERROW) {
+        head(false, rerun);                 // the rows that stayed in range, from their h2 rows, before the re-run overwrites them
+        if (rerun) __syncthreads();
+    }
     if (rerun) {
-        if (tid == 0 && overflow_rows != nullptr) atomicAdd(overflow_rows, n - b0 < MT ? n - b0 : MT);
+        if (tid == 0 && overflow_rows != nullptr) {
+            int cnt = n - b0 < MT ? n - b0 : MT;
+            if (PERROW) {
+                cnt = 0;
+                for (int r = 0; r < MT && b0 + r < n; ++r) cnt += rowbad[r] != 0 ? 1 : 0;
+            }
+            atomicAdd(overflow_rows, cnt);
+        }
         for (int i = tid; i < MT * D; i += 512) {
             const int row = i / D, col = i - row * D;
             const int grow = b0 + row < n ? b0 + row : n - 1;
@@ -183,45 +251,10 @@ __global__ __launch_bounds__(512, 1) void mlp_tail_h2_kernel(const float* __rest
         }
     }
 
-    // ---- output layer + softmax: wave w takes rows 8w .. 8w+7, lane = one group of 8 columns ----
-    float wo[8][8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c)
-#pragma unroll
-        for (int e = 0; e < 8; ++e) wo[c][e] = c < C ? Wout[(size_t)c * D + lane * 8 + e] : 0.0f;
-    for (int rr = 0; rr < 8; ++rr) {
-        const int row = 8 * w + rr;
-        const h8 hi = *reinterpret_cast<const h8*>(lds + row * ROWD + lane * 8);
-        const h8 lo = *reinterpret_cast<const h8*>(lds + row * ROWD + lane * 8 + 4);
-        float x[8];
-#pragma unroll
-        for (int e = 0; e < 8; ++e) x[e] = rerun ? frow[row * ROWD + lane * 8 + e] : (float)hi[e] + (float)lo[e];
-        float logit[8], mx = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            float p = 0.0f;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) p += x[e] * wo[c][e];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) p += __shfl_xor(p, o, 64);
-            logit[c] = c < C ? p + bout[c < C ? c : 0] : -INFINITY;
-            mx = fmaxf(mx, logit[c]);
-        }
-        float e[8], den = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            e[c] = c < C ? expf(logit[c] - mx) : 0.0f;
-            den += e[c];
-        }
-        float my_logit = 0.0f, my_e = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 8; ++c)
-            if (lane == c) { my_logit = logit[c]; my_e = e[c]; }
-        const int grow = b0 + row;
-        if (grow < n && lane < C) {
-            probs[(size_t)grow * C + lane] = my_e / den;
-            if (logits != nullptr) logits[(size_t)grow * C + lane] = my_logit;
-        }
+    if (PERROW) {
+        if (rerun) head(true, true);        // the rows that left the range, from the f32 re-run
+    } else {
+        head(rerun, false);
     }
 }
 
@@ -264,9 +297,15 @@ size_t mlp_weights_h2_words(int NL) { return (size_t)NL * NTILES * KS * 2 * 256;
 
 hipError_t launch_mlp_tail_h2(const float* X, int ldx, const void* Wp, const float* bias, int NL, const float* Wout,
                               const float* bout, int C, float* probs, float* logits, int n, hipStream_t stream,
-                              const float* const* W32, int* overflow_rows) {
+                              const float* const* W32, int* overflow_rows, bool per_row) {
     if (n <= 0) return hipSuccess;
     if (NL != 4 || C > 8 || C <= 0 || (ldx & 3) || W32 == nullptr) return hipErrorInvalidValue;
+    if (per_row) {
+        const size_t lds = (size_t)MT * ROWB + (size_t)MT * sizeof(uint32_t);      // + the row flags
+        hipLaunchKernelGGL((mlp_tail_h2_kernel<4, true>), dim3((n + MT - 1) / MT), dim3(512), lds, stream, X, ldx,
+                           static_cast<const uint32_t*>(Wp), bias, Wout, bout, C, probs, logits, n, W32, overflow_rows);
+        return hipGetLastError();
+    }
     const size_t lds = (size_t)MT * ROWB;
     hipLaunchKernelGGL((mlp_tail_h2_kernel<4>), dim3((n + MT - 1) / MT), dim3(512), lds, stream, X, ldx,
                        static_cast<const uint32_t*>(Wp), bias, Wout, bout, C, probs, logits, n, W32, overflow_rows);

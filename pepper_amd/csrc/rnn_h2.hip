@@ -77,7 +77,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                                                                      const uint32_t* __restrict__ Xh = nullptr, int ldxh = 0) {
     constexpr int KT = H + KX, KS = KT / 16, KSH = H / 16, NT = H / 32, NW = H / 32;
     constexpr int MTL = 32 * MTILES;             // rows of this workgroup
-    static_assert(MTILES == 2 || (MTILES == 1 && !XG), "the x ring of the XG form is laid out for 64 rows");
+    static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
     constexpr int KL = XG ? H : KT;              // columns kept in the LDS rows
     constexpr int ROWB = KL * 4 + 16;            // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
     constexpr int ROWD = ROWB / 4;               // in dwords
@@ -167,16 +167,21 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
             }
         }
     };
-    // XG staging: thread -> (row = tid / 8, 16-byte chunk c = tid % 8) of an iteration's 64 x 128 B slab
+    // XG staging: thread -> (row = tid / 8, 16-byte chunk c = tid % 8) of an iteration's MTL x 128 B slab.  With 32 rows
+    // (MTILES = 1) only waves 0-3 stage (a wave covers 8 rows: the test is uniform over the wave); every wave reads the ring.
+    const bool xg_stager = XG && tid < MTL * 8;
     const __amdgpu_buffer_rsrc_t xgrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t*>(XG ? Xh + (size_t)b0 * T * ldxh : Wp), 0, 0x7fffffff, 0x00020000);
     const unsigned xg_off = XG ? ((unsigned)((tid >> 3) * T) * ldxh) * 4u + (tid & 7) * 16u : 0u;
     uint32_t* xst_dst = xring + (tid >> 3) * XRD + (tid & 7) * 4;
     u32x4 xstage[2];
     auto xg_load = [&](int j, int t) {      // iteration j of step t -> staging register j & 1
-        xstage[j & 1] = __builtin_amdgcn_raw_buffer_load_b128(xgrs, xg_off, ((unsigned)t * ldxh) * 4u + (unsigned)j * 128u, SAUX);
+        if (MTILES == 2 || xg_stager)
+            xstage[j & 1] = __builtin_amdgcn_raw_buffer_load_b128(xgrs, xg_off, ((unsigned)t * ldxh) * 4u + (unsigned)j * 128u, SAUX);
     };
-    auto xg_store = [&](int j) { *reinterpret_cast<u32x4*>(xst_dst + (j & 1) * XSLOT) = xstage[j & 1]; };
+    auto xg_store = [&](int j) {
+        if (MTILES == 2 || xg_stager) *reinterpret_cast<u32x4*>(xst_dst + (j & 1) * XSLOT) = xstage[j & 1];
+    };
 
     struct Frag { h8 b[4][2], a[MTILES][2]; };     // [gate][hi, lo], [row tile][hi, lo]
     const uint32_t* arow = lds + li * ROWD + hf * 8;
@@ -1557,9 +1562,23 @@ int gru_fused_input_kx(int H, int F) {
 size_t rec_weights_h2_words(int G, int H, int KX) { return (size_t)2 * (G * H / 32) * ((H + KX) / 16) * 2 * 256; }
 
 hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias, const void* Wp, void* Y, int ldy, int B,
-                              int T, hipStream_t stream, bool prescaled) {
+                              int T, hipStream_t stream, bool prescaled, bool small) {
     if (B <= 0) return hipSuccess;
     if (H != 256 || (ldy & 7) || (ldxh & 7) || ldxh < 512) return hipErrorInvalidValue;
+    if (small) {
+        // 32-row workgroups (MTILES = 1): a row's MFMA chain and gate arithmetic are those of the 64-row workgroup, the tile
+        // just holds half the rows.  Xh / Y must hold the rows up to the next multiple of 32 (the workspace pads to 64).
+        const int nbt = (B + 31) / 32, grid1 = 2 * ((nbt + 3) / 4) * 4;
+        const size_t lds1 = (size_t)32 * (256 * 4 + 16) + (size_t)8 * 16 * 64 * 4 + (size_t)2 * 32 * 36 * 4;   // h + c + x ring
+#define PA_DEC1(PRE_, AUX_)                                                                                            \
+        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, PRE_, true, AUX_, false, 1>), dim3(grid1), dim3(512), lds1, stream, \
+                           (const float*)nullptr, 0, (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp),    \
+                           static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr, static_cast<const uint32_t*>(Xh), ldxh)
+        if (stream_nt()) { if (prescaled) PA_DEC1(true, 2); else PA_DEC1(false, 2); }
+        else { if (prescaled) PA_DEC1(true, 0); else PA_DEC1(false, 0); }
+#undef PA_DEC1
+        return hipGetLastError();
+    }
     const size_t lds = (size_t)MT * (256 * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4 + (size_t)2 * MT * 36 * 4;   // h + c + x ring
     const int grid = rec_grid(B);
 #define PA_DEC(PRE_, AUX_)                                                                                             \

@@ -33,7 +33,7 @@ def handle_output_directory(output_dir):
     return output_dir
 
 
-def polish_genome_distributed_gpu(image_dir, model_path, batch_size, num_workers, output_dir, device_ids):
+def polish_genome_distributed_gpu(image_dir, model_path, batch_size, num_workers, output_dir, device_ids, batch_invariant=None):
     _log("INFO: DISTRIBUTED GPU SETUP")
     if device_ids is None:
         device_ids = list(range(torch.cuda.device_count()))
@@ -50,11 +50,16 @@ def polish_genome_distributed_gpu(image_dir, model_path, batch_size, num_workers
                               sizes=[os.path.getsize(f) for f in input_files] if total_callers > 1 else None)
     device_ids = device_ids[:max(1, len(file_chunks))]
     _log("INFO: TOTAL THREADS: " + str(len(device_ids)))
-    predict_distributed_gpu(image_dir, file_chunks, output_dir, model_path, batch_size, device_ids, num_workers)
+    predict_distributed_gpu(image_dir, file_chunks, output_dir, model_path, batch_size, device_ids, num_workers,
+                            batch_invariant=batch_invariant)
     _log("INFO: PREDICTION GENERATED SUCCESSFULLY.")
 
 
-def call_consensus(image_dir, model_path, batch_size, num_workers, output_dir, device_ids, gpu, threads):
+def call_consensus(image_dir, model_path, batch_size, num_workers, output_dir, device_ids, gpu, threads, batch_invariant=None):
+    """The reference's arguments; batch_invariant (default: PEPPER_AMD_BATCH_INVARIANT): a chunk's predictions are the same
+    bits however the chunks are cut into device passes (pa_polish_set_batch_invariant)."""
+    from pepper_amd import _lib
+    batch_invariant = _lib.batch_invariant_default(batch_invariant)
     if not os.path.isfile(model_path):
         raise FileNotFoundError("ERROR: CAN NOT LOCATE MODEL FILE.")
     if not os.path.isdir(image_dir):
@@ -70,4 +75,4 @@ def call_consensus(image_dir, model_path, batch_size, num_workers, output_dir, d
         raise RuntimeError("pepper_amd is the MI355X drop-in for the GPU inference path and has no CPU fallback")
     if not torch.cuda.is_available():
         raise RuntimeError("ERROR: TORCH IS NOT BUILT WITH CUDA/HIP OR NO GPU IS VISIBLE.")
-    polish_genome_distributed_gpu(image_dir, model_path, batch_size, num_workers, output_dir, device_ids)
+    polish_genome_distributed_gpu(image_dir, model_path, batch_size, num_workers, output_dir, device_ids, batch_invariant)

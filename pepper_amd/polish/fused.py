@@ -165,8 +165,9 @@ class FusedConsensus(object):
     PASS_CHUNKS = int(os.environ.get("PEPPER_AMD_FUSED_PASS_CHUNKS", 16384))      # a pass that fills the chip
     HANDLES = 2          # passes in flight per device (own stream and workspace each)
 
-    def __init__(self, model_path, output_directory):
+    def __init__(self, model_path, output_directory, batch_invariant=None):
         self.model_path = model_path
+        self.batch_invariant = batch_invariant       # (None: PEPPER_AMD_BATCH_INVARIANT decides, per handle)
         self.output_directory = output_directory
         self.models, self.models_lock = {}, threading.Lock()
         self.chunks = 0
@@ -238,7 +239,8 @@ class FusedConsensus(object):
                 loaded = ModelHandler.load_simple_model_for_training(self.model_path, input_channels=ImageSizeOptions.IMAGE_CHANNELS,
                                                                      image_features=ImageSizeOptions.IMAGE_HEIGHT,
                                                                      seq_len=ImageSizeOptions.SEQ_LENGTH,
-                                                                     num_classes=ImageSizeOptions.TOTAL_LABELS)[0]
+                                                                     num_classes=ImageSizeOptions.TOTAL_LABELS,
+                                                                     batch_invariant=self.batch_invariant)[0]
                 # PEPPER_AMD_FUSED_STREAM_PRIORITY=-1 puts the passes' stream on the device's high-priority queues.  Measured with
                 # full-sized passes: no gain (7.8 s either way on the 64 Mb job), and the extra hardware queues push a process that
                 # already drives sixteen past what the device keeps resident (docs/LEDGER_r05.md, "Late finding") -- inside

@@ -36,7 +36,7 @@ LANE_PASS_BLOCKS = int(os.environ.get("PEPPER_AMD_POLISH_PASS_BLOCKS", max(1, DE
 LANE_PASSES_IN_FLIGHT = int(os.environ.get("PEPPER_AMD_POLISH_IN_FLIGHT", 2))
 
 def predict(input_filepath, file_chunks, output_filepath, model_path, batch_size, num_workers, rank, device_id,
-            model=None):
+            model=None, batch_invariant=None):
     torch.cuda.set_device(device_id)
     holder = {"model": model}
 
@@ -45,7 +45,8 @@ def predict(input_filepath, file_chunks, output_filepath, model_path, batch_size
             torch.cuda.set_device(device_id)                # also reached from a lanes call's preparing thread
             holder["model"] = ModelHandler.load_simple_model_for_training(
                 model_path, input_channels=ImageSizeOptions.IMAGE_CHANNELS, image_features=ImageSizeOptions.IMAGE_HEIGHT,
-                seq_len=ImageSizeOptions.SEQ_LENGTH, num_classes=ImageSizeOptions.TOTAL_LABELS)[0]
+                seq_len=ImageSizeOptions.SEQ_LENGTH, num_classes=ImageSizeOptions.TOTAL_LABELS,
+                batch_invariant=batch_invariant)[0]
             holder["model"].eval()
         return holder["model"]
     # big jobs (or num_workers > 0, the reference's DataLoader(num_workers=...)): reader and writer processes per lane of
@@ -126,7 +127,7 @@ def predict(input_filepath, file_chunks, output_filepath, model_path, batch_size
 def _setup(rank, device_ids, args, all_input_files, port, backend):
     import torch.distributed as dist
     from pepper_amd.parallel import broadcast_checkpoint
-    filepath, output_filepath, model_path, batch_size, num_workers = args
+    filepath, output_filepath, model_path, batch_size, num_workers, batch_invariant = args
     device = device_ids[rank]
     torch.cuda.set_device(device)
     os.environ.setdefault('MASTER_ADDR', '127.0.0.1')
@@ -139,18 +140,22 @@ def _setup(rank, device_ids, args, all_input_files, port, backend):
         state, meta = broadcast_checkpoint(model_path if rank == 0 else None, src=0,
                                            device=torch.device("cuda", device) if backend == "nccl" else None)
         model = ModelHandler.get_new_gru_model(ImageSizeOptions.IMAGE_CHANNELS, ImageSizeOptions.IMAGE_HEIGHT,
-                                               meta["gru_layers"], meta["hidden_size"], ImageSizeOptions.TOTAL_LABELS)
+                                               meta["gru_layers"], meta["hidden_size"], ImageSizeOptions.TOTAL_LABELS,
+                                               batch_invariant=batch_invariant)
         model.load_state_dict(state)
         predict(filepath, all_input_files[rank] if rank < len(all_input_files) else [], output_filepath, model_path,
-                batch_size, num_workers, rank, device, model=model)
+                batch_size, num_workers, rank, device, model=model, batch_invariant=batch_invariant)
         dist.barrier()
     finally:
         dist.destroy_process_group()
 
 
-def predict_distributed_gpu(filepath, file_chunks, output_filepath, model_path, batch_size, device_ids, num_workers):
+def predict_distributed_gpu(filepath, file_chunks, output_filepath, model_path, batch_size, device_ids, num_workers,
+                            batch_invariant=None):
     """One model per entry of device_ids over the given file chunks (reference signature).  An ordinal listed twice
-    gets two callers on that GPU (the weight broadcast then runs over gloo: RCCL refuses two ranks per device)."""
+    gets two callers on that GPU (the weight broadcast then runs over gloo: RCCL refuses two ranks per device).
+    batch_invariant: every caller's handles run in batch-invariant mode (pa_polish_set_batch_invariant); None: as
+    PEPPER_AMD_BATCH_INVARIANT says."""
     from pepper_amd.variant.RunInference import dist_backend, free_port, remove_stale_predictions
     if len(file_chunks) > len(device_ids) and len(device_ids) > 1:
         raise ValueError("predict_distributed_gpu: %d file chunks for %d devices" % (len(file_chunks), len(device_ids)))
@@ -158,8 +163,8 @@ def predict_distributed_gpu(filepath, file_chunks, output_filepath, model_path, 
     if len(device_ids) == 1:
         # every file goes to the one device, whatever the caller's chunking was
         return predict(filepath, [f for chunk in file_chunks for f in chunk], output_filepath, model_path, batch_size,
-                       num_workers, 0, device_ids[0])
+                       num_workers, 0, device_ids[0], batch_invariant=batch_invariant)
     import torch.multiprocessing as mp
-    args = (filepath, output_filepath, model_path, batch_size, num_workers)
+    args = (filepath, output_filepath, model_path, batch_size, num_workers, batch_invariant)
     mp.spawn(_setup, args=(device_ids, args, file_chunks, free_port(), dist_backend(device_ids)), nprocs=len(device_ids),
              join=True)

@@ -16,7 +16,7 @@ from pepper_amd.polish.Options import ImageSizeOptions, TrainOptions
 
 class TransducerGRU(object):
     def __init__(self, image_channels, image_features, gru_layers, hidden_size, num_classes,
-                 bidirectional=True, device=None, max_chunk=0):
+                 bidirectional=True, device=None, max_chunk=0, batch_invariant=None):
         if not bidirectional:
             raise ValueError("the reference inference path only instantiates bidirectional=True")
         self.image_features = image_features
@@ -24,6 +24,10 @@ class TransducerGRU(object):
         self.num_layers = gru_layers
         self.num_classes = num_classes
         self.max_chunk = max_chunk
+        # batch-invariant mode (include/pepper_amd.h pa_polish_set_batch_invariant): on when asked for here, or when the process
+        # has PEPPER_AMD_BATCH_INVARIANT=1
+        # and the argument is left at None (an explicit True / False wins over the environment)
+        self.batch_invariant = _lib.batch_invariant_default(batch_invariant)
         self.device = torch.cuda.current_device() if device is None and torch.cuda.is_available() else (device or 0)
         self._handle = None
         self._stream = None
@@ -45,14 +49,32 @@ class TransducerGRU(object):
                                         ctypes.c_void_p(self._stream.cuda_stream), ctypes.byref(handle)))
         self._handle = handle
         self._state = state_dict
+        if self.batch_invariant:
+            try:
+                _lib.check(lib.pa_polish_set_batch_invariant(handle, 1))
+            except _lib.PepperAmdError:
+                self.close()             # (the exact-f32 kernels refuse the mode: no handle without the guarantee asked for)
+                raise
         return self
+
+    def set_batch_invariant(self, on=True):
+        """Switch the handle's batch-invariant mode between calls (it applies from the next prediction)."""
+        on = _lib.parse_batch_invariant(on)
+        _lib.check(_lib.load().pa_polish_set_batch_invariant(self.handle, int(on)))
+        self.batch_invariant = on
+        return self
+
+    def get_batch_invariant(self):
+        v = ctypes.c_int32()
+        _lib.check(_lib.load().pa_polish_get_batch_invariant(self.handle, ctypes.byref(v)))
+        return bool(v.value)
 
     def clone(self, stream_priority=None):
         """A second, independent handle on the same weights (own stream, own staging buffers): what runs a second block on
         the device while this one's pass is under way (pepper_amd/hostpipe.py polish_lanes).  stream_priority: 0 / -1 (high) for
         the clone's stream; None: this object's."""
         other = TransducerGRU(1, self.image_features, self.num_layers, self.hidden_size, self.num_classes, device=self.device,
-                              max_chunk=self.max_chunk)
+                              max_chunk=self.max_chunk, batch_invariant=self.batch_invariant)
         other.stream_priority = int(getattr(self, "stream_priority", 0) if stream_priority is None else stream_priority)
         return other.load_state_dict(self._state)
 

@@ -18,10 +18,14 @@ def _log(message):
 
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
-           num_workers, stage_walls=None, fused_inference=None):
+           num_workers, stage_walls=None, fused_inference=None, batch_invariant=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
-    the image files back (pepper_amd/polish/fused.py); both stores are still written."""
+    the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
+    PEPPER_AMD_BATCH_INVARIANT=1): the model handles of either form run in batch-invariant mode, so both forms, and any
+    device_ids, give the same predictions bit for bit."""
+    from pepper_amd import _lib
+    batch_invariant = _lib.batch_invariant_default(batch_invariant)
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
         if not os.path.isfile(path):
             raise FileNotFoundError("CAN NOT LOCATE " + what + " FILE: " + str(path))
@@ -47,7 +51,7 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         from pepper_amd.polish.fused import FusedConsensus
         UserInterfaceSupport.handle_output_directory(prediction_output_directory)
         _log("STEP 1+2: GENERATING IMAGES AND RUNNING INFERENCE (FUSED) -> " + prediction_output_directory)
-        sink = FusedConsensus(model_path, prediction_output_directory)
+        sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant)
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
                         stats=image_stats)
@@ -59,7 +63,7 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         t1 = time.perf_counter()
         _log("STEP 2: RUNNING INFERENCE -> " + prediction_output_directory)
         call_consensus(image_output_directory, model_path, batch_size, num_workers, prediction_output_directory, device_ids,
-                       gpu_mode, threads)
+                       gpu_mode, threads, batch_invariant=batch_invariant)
         t2 = time.perf_counter()
     _log("STEP 3: RUNNING STITCH -> " + output_dir)
     perform_stitch(prediction_output_directory, output_dir, threads)

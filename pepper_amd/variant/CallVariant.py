@@ -37,6 +37,10 @@ def call_variant(options):
         raise ValueError("ERROR: num_workers NEEDS TO BE >=0.")
 
     timestr = time.strftime("%m%d%Y_%H%M%S")
+    # batch-invariant mode (options.batch_invariant, default PEPPER_AMD_BATCH_INVARIANT): resolved once here, the options object
+    # carries it to every handle of the run -- three-step or fused, the lanes' second handle, every process of device_ids
+    from pepper_amd import _lib
+    options.batch_invariant = _lib.batch_invariant_default(getattr(options, "batch_invariant", None))
     output_dir = ImageGenerationUtils.handle_output_directory(options.output_dir)
     image_output_directory = output_dir + "images_" + str(timestr) + "/"
     prediction_output_directory = output_dir + "predictions_" + str(timestr) + "/"

@@ -127,7 +127,8 @@ def _worker(rank, world, device_ids, options, image_dir, file_chunks, output_dir
                                            device=torch.device("cuda", device) if backend == "nccl" else None)
         model = ModelHandler.get_new_gru_model(ImageSizeOptions.IMAGE_HEIGHT, meta["gru_layers"],
                                                meta["hidden_size"], ImageSizeOptions.TOTAL_LABELS,
-                                               ImageSizeOptions.TOTAL_TYPE_LABELS)
+                                               ImageSizeOptions.TOTAL_TYPE_LABELS,
+                                               batch_invariant=getattr(options, "batch_invariant", None))
         model.load_state_dict(state)
         threads = max(1, int(options.threads / world))
         predict(options, image_dir, file_chunks[rank] if rank < len(file_chunks) else [], output_dir, threads,
@@ -170,6 +171,9 @@ def distributed_gpu(options, image_dir, output_dir):
 
 
 def run_inference(options, image_dir, output_dir):
+    from pepper_amd import _lib
+    # options.batch_invariant (default PEPPER_AMD_BATCH_INVARIANT): every handle of every caller process in batch-invariant mode
+    options.batch_invariant = _lib.batch_invariant_default(getattr(options, "batch_invariant", None))
     output_dir = handle_output_directory(output_dir)
     if getattr(options, "dry", False):
         raise NotImplementedError("--dry (fake one-hot predictor over train-mode labels, "

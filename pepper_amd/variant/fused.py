@@ -80,7 +80,8 @@ class FusedPredictor(object):
                 try:
                     model = ModelHandler.load_simple_model_for_training(
                         self.options.model_path, image_features=ImageSizeOptions.IMAGE_HEIGHT, num_classes=ImageSizeOptions.TOTAL_LABELS,
-                        num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS)[0]
+                        num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS,
+                        batch_invariant=getattr(self.options, "batch_invariant", None))[0]
                 finally:
                     simple_model.NEW_HANDLES.stream_priority = 0
                 model.eval()

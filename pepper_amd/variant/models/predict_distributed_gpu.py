@@ -68,13 +68,15 @@ def predict(options, input_filepath, input_files, output_filepath, threads, rank
         device = torch.cuda.current_device()
     torch.cuda.set_device(device)
     holder = {"model": model}
+    batch_invariant = getattr(options, "batch_invariant", None)      # (None: PEPPER_AMD_BATCH_INVARIANT decides)
 
     def get_model():
         if holder["model"] is None:
             torch.cuda.set_device(device)                   # also reached from a lanes call's preparing thread
             holder["model"] = ModelHandler.load_simple_model_for_training(
                 options.model_path, image_features=ImageSizeOptions.IMAGE_HEIGHT,
-                num_classes=ImageSizeOptions.TOTAL_LABELS, num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS)[0]
+                num_classes=ImageSizeOptions.TOTAL_LABELS, num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS,
+                batch_invariant=batch_invariant)[0]
             holder["model"].eval()
         return holder["model"]
     suffix = "" if rank is None else "_" + str(rank)
@@ -99,7 +101,8 @@ def predict(options, input_filepath, input_files, output_filepath, threads, rank
             torch.cuda.set_device(device)
             other = ModelHandler.load_simple_model_for_training(
                 options.model_path, image_features=ImageSizeOptions.IMAGE_HEIGHT,
-                num_classes=ImageSizeOptions.TOTAL_LABELS, num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS)[0]
+                num_classes=ImageSizeOptions.TOTAL_LABELS, num_type_classes=ImageSizeOptions.TOTAL_TYPE_LABELS,
+                batch_invariant=batch_invariant)[0]
             other.eval()
             return forward_with(lambda: other)
         try:

@@ -30,7 +30,7 @@ NEW_HANDLES = _threading.local()
 
 class TransducerGRU(object):
     def __init__(self, image_features, gru_layers, hidden_size, num_classes, num_classes_type,
-                 bidirectional=True, device=None, max_chunk=0):
+                 bidirectional=True, device=None, max_chunk=0, batch_invariant=None):
         if not bidirectional:
             raise ValueError("the reference inference path only instantiates bidirectional=True")
         self.image_features = image_features
@@ -41,6 +41,10 @@ class TransducerGRU(object):
         self.num_classes_type = num_classes_type
         self.window = ImageSizeOptions.CANDIDATE_WINDOW_SIZE + 1
         self.max_chunk = max_chunk
+        # batch-invariant mode (include/pepper_amd.h pa_variant_set_batch_invariant): on when asked for here, or when the process
+        # has PEPPER_AMD_BATCH_INVARIANT=1
+        # and the argument is left at None (an explicit True / False wins over the environment)
+        self.batch_invariant = _lib.batch_invariant_default(batch_invariant)
         self.device = torch.cuda.current_device() if device is None and torch.cuda.is_available() else (device or 0)
         self._handle = None
         self._stream = None
@@ -58,7 +62,25 @@ class TransducerGRU(object):
         _lib.check(lib.pa_variant_create(ctypes.byref(cfg), names, data, numel, n,
                                          ctypes.c_void_p(self._stream.cuda_stream), ctypes.byref(handle)))
         self._handle = handle
+        if self.batch_invariant:
+            try:
+                _lib.check(lib.pa_variant_set_batch_invariant(handle, 1))
+            except _lib.PepperAmdError:
+                self.close()
+                raise
         return self
+
+    def set_batch_invariant(self, on=True):
+        """Switch the handle's batch-invariant mode between calls (it applies from the next forward)."""
+        on = _lib.parse_batch_invariant(on)
+        _lib.check(_lib.load().pa_variant_set_batch_invariant(self.handle, int(on)))
+        self.batch_invariant = on
+        return self
+
+    def get_batch_invariant(self):
+        v = ctypes.c_int32()
+        _lib.check(_lib.load().pa_variant_get_batch_invariant(self.handle, ctypes.byref(v)))
+        return bool(v.value)
 
     def eval(self):
         self.training = False
