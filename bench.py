@@ -19,6 +19,11 @@ line.
 
 `--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (dump_outputs): the inputs are seeded, so two
 builds run with the same arguments can be compared output for output.
+
+A plain run does only what its headline needs: set-up, warm-up, the timed steps, the dump if asked for, the line (the roofline
+and per-kernel figures in it come from the timed steps' own HIP events and the committed counter passes).  Everything that takes
+runs of its own -- CPU baselines, the device-resident and default-batch legs, the `secondary` block, the per-rank image legs of
+an N-rank run, the other models' extra legs -- runs only with `--full`, which also writes the whole record to FULL_RECORD.
 """
 import argparse
 import ctypes
@@ -100,17 +105,21 @@ def parse():
     ap.add_argument("--pool", type=int, default=0, help="distinct windows / chunks in the page-locked host pool per GPU")
     ap.add_argument("--resident-only", action="store_true",
                     help="time the device-resident pass instead of the host-buffer path (kernel profiling under rocprofv3)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the device-resident and batch-512 legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: CPU baselines, the device-resident and default-batch legs, the "
+                         "variant's `secondary` block, the per-rank image legs of N > 1, the other models' extra legs; and write the "
+                         "whole record to the file the line's `full_record` names.  Off: set-up, warm-up, the timed steps, the dump, the line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the device-resident and batch-512 legs")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="variant only: skip the `secondary` block (polish, encoder and the two HDF5 -> HDF5 pipelines)")
+                    help="with --full, variant only: skip the `secondary` block (polish, encoder and the two HDF5 -> HDF5 pipelines)")
     ap.add_argument("--no-image-legs", action="store_true",
-                    help="N > 1: skip the per-rank image generation legs (variant generate_images and the polish chain on each rank's own "
-                         "synthetic BAM) that follow the timed model steps")
-    ap.add_argument("--legs", default="", help="secondary block: only these legs (comma separated names of the `secondary` keys)")
+                    help="with --full, N > 1: skip the per-rank image generation legs (variant generate_images and the polish chain on "
+                         "each rank's own synthetic BAM) that follow the timed model steps")
+    ap.add_argument("--legs", default="",
+                    help="with --full: only these legs of the secondary block (comma separated names of the `secondary` keys)")
     ap.add_argument("--full-line", action="store_true",
-                    help="print the whole record (tens of KB) as the stdout line instead of the compact one; the whole record is "
-                         "always written to gpurun_out/bench_full.json")
+                    help="print the whole record (tens of KB with --full) as the stdout line instead of the compact one")
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="variant / polish / ns-literal: after the timed steps, write what the last timed step returned to its caller "
                          "(variant: probabilities; polish: labels, phred) as DIR/<name>.npy in float32; past 64 MB a fixed seeded "
@@ -123,6 +132,8 @@ def parse():
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.dump_outputs and (args.model not in ("variant", "polish", "ns-literal") or args.workload != "v-syn"):
         ap.error("--dump-outputs: only the variant (v-syn), polish and ns-literal models")
+    if args.legs and not args.full:
+        ap.error("--legs selects legs of the secondary block, which only --full runs")
     return args
 
 
@@ -435,9 +446,7 @@ def realign_bench(args):
     over (the image chain hands over ~8 600 per call).  The one-region call (1 500 reads) and the 60-read region are reported
     beside it.  Not the headline metric."""
     import ctypes
-    from oracle import ssw
     from pepper_amd.polish import PEPPER
-    from pepper_amd.polish.PEPPER import ReadAligner
     rng = np.random.default_rng(5)
     n_windows = 8
     per_window = args.per_gpu or 1500
@@ -474,52 +483,6 @@ def realign_bench(args):
     dt = time.perf_counter() - t0
     cells = c.value
     n = len(seqs_all)
-    # one region per call: the reference's cap of 1 500 reads
-    aligner = ReadAligner(0, len(reference), reference)
-    aligner.align_arrays(pos, off, seq)
-    t1r = time.perf_counter()
-    for _ in range(args.steps):
-        aligner.align_arrays(pos, off, seq)
-    dt1 = time.perf_counter() - t1r
-    # a region at ordinary coverage: 60 reads (latency of one call)
-    n60 = min(60, len(seqs))
-    off60 = off[:n60 + 1].copy()
-    seq60 = seq[:int(off60[-1])]
-    aligner.align_arrays(pos[:n60], off60, seq60)
-    t60 = time.perf_counter()
-    for _ in range(args.steps):
-        aligner.align_arrays(pos[:n60], off60, seq60)
-    ms60 = (time.perf_counter() - t60) / args.steps * 1e3
-    # the image generator runs its regions on worker threads (one handle and stream each): aggregate over 4 of them
-    import threading
-
-    def worker():
-        PEPPER.align_windows(windows, which, pos_all, off_all, seq_all)
-        barrier.wait()
-        for _ in range(args.steps):
-            PEPPER.align_windows(windows, which, pos_all, off_all, seq_all)
-        barrier.wait()
-    barrier = threading.Barrier(5)
-    threads = [threading.Thread(target=worker) for _ in range(4)]
-    for th in threads:
-        th.start()
-    barrier.wait()
-    t2 = time.perf_counter()
-    barrier.wait()
-    dt4 = time.perf_counter() - t2
-    for th in threads:
-        th.join()
-    # CPU: the reference's own SSW build where it travelled with the snapshot, else the scalar restatement
-    kind = "reference" if ssw.have_reference() else "port"
-    fn = ssw.align_reference if kind == "reference" else ssw.align
-    t1 = time.perf_counter()
-    done = 0
-    for p, q in zip(pos, seqs):
-        fn(reference[p:], q)
-        done += 1
-        if time.perf_counter() - t1 > args.cpu_seconds:
-            break
-    cpu_dt = time.perf_counter() - t1
     # the roof is vector instruction issue: 1 024 SIMDs x 2.4 GHz / 4 cycles per wave instruction; the two kernels' instructions
     # per read come from the committed counter pass of this very workload (profiles/r05_realign_pmc.txt, SQ_INSTS_VALU)
     roof = {"bound": "valu issue", "kernel": "sw_ends_pair_kernel + band_kernel", "unit": "G wave-instructions/s", "peak": 1024 * 2.4 / 4,
@@ -542,20 +505,71 @@ def realign_bench(args):
                          "pass of this workload) over their HIP-event time; frac = the share of the chip's issue slots they fill")
     except (OSError, KeyError, ValueError):
         pass
-    print(json.dumps({
+    line = {
         "metric": "polish read re-alignment, reads/s (secondary workload)", "value": n * args.steps / dt, "unit": "reads/s",
         "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
         "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int16 pairs (two reads per 32-bit lane register)", "data": "synthetic",
-        "reads_per_s_4_worker_threads": 4 * n * args.steps / dt4, "reads_per_s_one_region_call": len(seqs) * args.steps / dt1,
-        "ms_per_60_read_region": ms60,
         "config": {"workload": f"{n} region-clipped reads (mean {int(off_all[-1]) // n} bases) of {n_windows} draft windows of 1020 bases in one call, "
                                "SSW scoring 4/6/8/2, host buffers in, CIGARs out"},
         "kernels": {"score_kernels": {"avg_ms": ends / args.steps, "gcups_one_pass_equiv": cells / (ends / args.steps * 1e-3) / 1e9},
                     "band_kernel": {"avg_ms": band / args.steps}},
-        "roofline": roof,
-        "cpu_baseline": {"value": done / cpu_dt, "unit": "reads/s", "cores": 1, "kind": kind,
-                         "sample": f"{done} of the same reads through {'the reference SSW build (oracle/_ref)' if kind == 'reference' else 'oracle/ssw_oracle.cpp'}, one thread, {cpu_dt:.1f} s"},
-        "speedup_vs_cpu_baseline": (n * args.steps / dt) / (done / cpu_dt)}))
+        "roofline": roof}
+    if args.full:
+        from oracle import ssw
+        from pepper_amd.polish.PEPPER import ReadAligner
+        # one region per call: the reference's cap of 1 500 reads
+        aligner = ReadAligner(0, len(reference), reference)
+        aligner.align_arrays(pos, off, seq)
+        t1r = time.perf_counter()
+        for _ in range(args.steps):
+            aligner.align_arrays(pos, off, seq)
+        dt1 = time.perf_counter() - t1r
+        # a region at ordinary coverage: 60 reads (latency of one call)
+        n60 = min(60, len(seqs))
+        off60 = off[:n60 + 1].copy()
+        seq60 = seq[:int(off60[-1])]
+        aligner.align_arrays(pos[:n60], off60, seq60)
+        t60 = time.perf_counter()
+        for _ in range(args.steps):
+            aligner.align_arrays(pos[:n60], off60, seq60)
+        ms60 = (time.perf_counter() - t60) / args.steps * 1e3
+        # the image generator runs its regions on worker threads (one handle and stream each): aggregate over 4 of them
+        import threading
+
+        def worker():
+            PEPPER.align_windows(windows, which, pos_all, off_all, seq_all)
+            barrier.wait()
+            for _ in range(args.steps):
+                PEPPER.align_windows(windows, which, pos_all, off_all, seq_all)
+            barrier.wait()
+        barrier = threading.Barrier(5)
+        threads = [threading.Thread(target=worker) for _ in range(4)]
+        for th in threads:
+            th.start()
+        barrier.wait()
+        t2 = time.perf_counter()
+        barrier.wait()
+        dt4 = time.perf_counter() - t2
+        for th in threads:
+            th.join()
+        # CPU: the reference's own SSW build where it travelled with the snapshot, else the scalar restatement
+        kind = "reference" if ssw.have_reference() else "port"
+        fn = ssw.align_reference if kind == "reference" else ssw.align
+        t1 = time.perf_counter()
+        done = 0
+        for p, q in zip(pos, seqs):
+            fn(reference[p:], q)
+            done += 1
+            if time.perf_counter() - t1 > args.cpu_seconds:
+                break
+        cpu_dt = time.perf_counter() - t1
+        line.update({
+            "reads_per_s_4_worker_threads": 4 * n * args.steps / dt4, "reads_per_s_one_region_call": len(seqs) * args.steps / dt1,
+            "ms_per_60_read_region": ms60,
+            "cpu_baseline": {"value": done / cpu_dt, "unit": "reads/s", "cores": 1, "kind": kind,
+                             "sample": f"{done} of the same reads through {'the reference SSW build (oracle/_ref)' if kind == 'reference' else 'oracle/ssw_oracle.cpp'}, one thread, {cpu_dt:.1f} s"},
+            "speedup_vs_cpu_baseline": (n * args.steps / dt) / (done / cpu_dt)})
+    print(json.dumps(line))
 
 
 ENCODER_BYTES_PER_BASE = 2          # one base + one quality byte per aligned base
@@ -719,75 +733,6 @@ def encoder_bench(args):
     alg_bytes = ENCODER_BYTES_PER_BASE * stats["bases"] + ENCODER_BYTES_PER_ROW * stats["rows"]
     achieved = alg_bytes / (avg["tile_count_ms"] * 1e-3) / 1e9
     traffic = encoder_traffic()
-    # PCIe-inclusive form (never `value`): stage + run of the same batch through one call
-    t0 = time.perf_counter()
-    b2 = StagedBatch(gens, flats, ont, cand)
-    b2.run()
-    t_one = time.perf_counter() - t0
-    out = b2.results()
-    # several handles on as many host threads, as image generation runs its workers (one encoder per thread): the candidate
-    # enumeration of one handle's batch overlaps the kernels of the others'.  The batch is dealt over the handles.
-    two = []
-    for n_handles in ((2, 4) if (n_regions >= 16 and world == 1) else ()):
-        import threading
-        share = n_regions // n_handles
-        done_bases = [0] * n_handles
-        start_gate = threading.Barrier(n_handles + 1)
-
-        def worker(k):
-            sl = slice(k * share, (k + 1) * share)
-            mine = StagedBatch(gens[sl], flats[sl], ont, cand[sl])        # its own handle: _encoder is per thread
-            mine.run()
-            start_gate.wait()
-            for _ in range(2 * args.steps):
-                mine.run()
-            done_bases[k] = 2 * args.steps * mine.stats()["bases"]
-            start_gate.wait()
-        threads = [threading.Thread(target=worker, args=(k,)) for k in range(n_handles)]
-        for th in threads:
-            th.start()
-        start_gate.wait()
-        t0 = time.perf_counter()
-        start_gate.wait()
-        t_two = time.perf_counter() - t0
-        for th in threads:
-            th.join()
-        two.append({"value": sum(done_bases) / t_two, "unit": "aligned bases/s", "handles": n_handles, "regions_per_handle": share})
-    # the packed host-fed form (what image generation drives): reads as BAM stores them in the handle's page-locked arena ->
-    # one H2D of the arena + one of the tables -> unpack_clip_kernel -> the step above.  PCIe-inclusive; never `value`.
-    packed = None
-    try:
-        from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
-        arena, table, pair_read, region_pairs, used = packed_arena_of(regions)
-        enc = PackedEncoder(device, arena_bytes=int(used) + (1 << 20), max_reads=len(table) + 16, max_pairs=len(pair_read) + 16,
-                            host_threads=0)
-        enc.arena[:len(arena)] = arena
-        enc.reads[:len(table)] = table
-        enc.pair_read[:len(pair_read)] = pair_read
-        spans = [(rs, re_) for _, _, rs, re_ in regions]
-        refs = [ref for ref, _, _, _ in regions]
-        counts3 = (len(table), len(pair_read), int(used))
-        outs, live = enc.encode(spans, refs, region_pairs, counts3, ont, cand)
-        same = all(np.array_equal(a["images"], b["images"]) and a["candidates"] == b["candidates"] for a, b in zip(outs, out))
-        reps = max(3, args.steps // 2)
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            enc.encode(spans, refs, region_pairs, counts3, ont, cand)
-        t_packed = (time.perf_counter() - t0) / reps
-        tm = enc.last.timing()
-        shipped = int(used) + sum(len(r) for r in refs)
-        packed = {"value": stats["bases"] / t_packed, "unit": "aligned bases/s", "ms": t_packed * 1e3,
-                  "bytes_over_pcie": shipped, "bytes_per_aligned_base": shipped / stats["bases"],
-                  "upload_ms": tm["upload_ms"], "unpack_clip_ms": tm["unpack_clip_ms"],
-                  "pcie_roof": {"peak_GBps": 63.0, "bases_per_s_at_peak": 63.0e9 / (shipped / stats["bases"]),
-                                "achieved_GBps_during_upload": shipped / (tm["upload_ms"] * 1e-3) / 1e9 if tm["upload_ms"] else None,
-                                "note": "PCIe Gen5 x16 (MI355X_MICROARCH.md: 63 GB/s): the packed form ships ~1.65 B per aligned base "
-                                        "(4-bit bases, qualities, CIGAR words), the host-clipped form 2 B + 8 B per operation"},
-                  "identical_to_resident_form": bool(same),
-                  "note": "pa_encoder_stage_packed + pa_encoder_run_staged + result copy per call, arena and tables page-locked"}
-        enc.close()
-    except Exception as e:      # noqa: BLE001 -- the leg is extra
-        packed = {"error": repr(e)[:300]}
     line = {
         "metric": "variant summary encoder, aligned bases/s (pileup -> candidate summary images)",
         "value": value, "unit": "aligned bases/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -811,15 +756,87 @@ def encoder_bench(args):
                              "SURVEY.md 8(d); launch duration from HIP events on the encoder's stream around the kernel, averaged "
                              "over the timed steps"},
         "kernels_ms": avg,
-        "concurrent_handles": two,
-        "concurrent_handles_note": "N encoder handles on N host threads (image generation's worker scheme), each running its share of "
-                                   "the regions back to back: one handle's host enumeration beside the others' kernels",
-        "host_buffers_one_call": {"value": stats["bases"] / t_one, "unit": "aligned bases/s", "ms": t_one * 1e3,
-                                  "note": "pa_encoder_generate_summary_batch from pageable numpy arrays: validate + H2D of 0.75 GB + the "
-                                          "step above (PCIe-inclusive; never `value`)"},
-        "packed_host_fed": packed,
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        # PCIe-inclusive form (never `value`): stage + run of the same batch through one call
+        t0 = time.perf_counter()
+        b2 = StagedBatch(gens, flats, ont, cand)
+        b2.run()
+        t_one = time.perf_counter() - t0
+        out = b2.results()
+        # several handles on as many host threads, as image generation runs its workers (one encoder per thread): the candidate
+        # enumeration of one handle's batch overlaps the kernels of the others'.  The batch is dealt over the handles.
+        two = []
+        for n_handles in ((2, 4) if (n_regions >= 16 and world == 1) else ()):
+            import threading
+            share = n_regions // n_handles
+            done_bases = [0] * n_handles
+            start_gate = threading.Barrier(n_handles + 1)
+
+            def worker(k):
+                sl = slice(k * share, (k + 1) * share)
+                mine = StagedBatch(gens[sl], flats[sl], ont, cand[sl])        # its own handle: _encoder is per thread
+                mine.run()
+                start_gate.wait()
+                for _ in range(2 * args.steps):
+                    mine.run()
+                done_bases[k] = 2 * args.steps * mine.stats()["bases"]
+                start_gate.wait()
+            threads = [threading.Thread(target=worker, args=(k,)) for k in range(n_handles)]
+            for th in threads:
+                th.start()
+            start_gate.wait()
+            t0 = time.perf_counter()
+            start_gate.wait()
+            t_two = time.perf_counter() - t0
+            for th in threads:
+                th.join()
+            two.append({"value": sum(done_bases) / t_two, "unit": "aligned bases/s", "handles": n_handles, "regions_per_handle": share})
+        # the packed host-fed form (what image generation drives): reads as BAM stores them in the handle's page-locked arena ->
+        # one H2D of the arena + one of the tables -> unpack_clip_kernel -> the step above.  PCIe-inclusive; never `value`.
+        packed = None
+        try:
+            from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
+            arena, table, pair_read, region_pairs, used = packed_arena_of(regions)
+            enc = PackedEncoder(device, arena_bytes=int(used) + (1 << 20), max_reads=len(table) + 16, max_pairs=len(pair_read) + 16,
+                                host_threads=0)
+            enc.arena[:len(arena)] = arena
+            enc.reads[:len(table)] = table
+            enc.pair_read[:len(pair_read)] = pair_read
+            spans = [(rs, re_) for _, _, rs, re_ in regions]
+            refs = [ref for ref, _, _, _ in regions]
+            counts3 = (len(table), len(pair_read), int(used))
+            outs, live = enc.encode(spans, refs, region_pairs, counts3, ont, cand)
+            same = all(np.array_equal(a["images"], b["images"]) and a["candidates"] == b["candidates"] for a, b in zip(outs, out))
+            reps = max(3, args.steps // 2)
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                enc.encode(spans, refs, region_pairs, counts3, ont, cand)
+            t_packed = (time.perf_counter() - t0) / reps
+            tm = enc.last.timing()
+            shipped = int(used) + sum(len(r) for r in refs)
+            packed = {"value": stats["bases"] / t_packed, "unit": "aligned bases/s", "ms": t_packed * 1e3,
+                      "bytes_over_pcie": shipped, "bytes_per_aligned_base": shipped / stats["bases"],
+                      "upload_ms": tm["upload_ms"], "unpack_clip_ms": tm["unpack_clip_ms"],
+                      "pcie_roof": {"peak_GBps": 63.0, "bases_per_s_at_peak": 63.0e9 / (shipped / stats["bases"]),
+                                    "achieved_GBps_during_upload": shipped / (tm["upload_ms"] * 1e-3) / 1e9 if tm["upload_ms"] else None,
+                                    "note": "PCIe Gen5 x16, 63 GB/s peak: the packed form ships ~1.65 B per aligned base "
+                                            "(4-bit bases, qualities, CIGAR words), the host-clipped form 2 B + 8 B per operation"},
+                      "identical_to_resident_form": bool(same),
+                      "note": "pa_encoder_stage_packed + pa_encoder_run_staged + result copy per call, arena and tables page-locked"}
+            enc.close()
+        except Exception as e:      # noqa: BLE001 -- the leg is extra
+            packed = {"error": repr(e)[:300]}
+        line.update({
+            "concurrent_handles": two,
+            "concurrent_handles_note": "N encoder handles on N host threads (image generation's worker scheme), each running its share of "
+                                       "the regions back to back: one handle's host enumeration beside the others' kernels",
+            "host_buffers_one_call": {"value": stats["bases"] / t_one, "unit": "aligned bases/s", "ms": t_one * 1e3,
+                                      "note": "pa_encoder_generate_summary_batch from pageable numpy arrays: validate + H2D of 0.75 GB + the "
+                                              "step above (PCIe-inclusive; never `value`)"},
+            "packed_host_fed": packed,
+        })
+    if args.full and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         from oracle import encoder_cpu
         one = encoder_cpu.time_regions(regions[:8], args.cpu_seconds)
@@ -896,14 +913,6 @@ def polish_encoder_bench(args):
     value = args.steps * stats["bases"] / dt
     alg_bytes = POLISH_ENCODER_BYTES_PER_BASE * stats["bases"] + POLISH_ENCODER_BYTES_PER_ROW * stats["rows"]
     achieved = alg_bytes / (avg["tile_ms"] * 1e-3) / 1e9
-    # host buffers in, host arrays out, one call (what AlignmentSummarizer.create_summaries makes per batch of regions)
-    reps = max(3, args.steps // 2)
-    t0 = time.perf_counter()
-    for _ in range(reps):
-        b2 = StagedSummaries(gens, flats, spans)
-        b2.run()
-        image, pos = b2.results()
-    t_one = (time.perf_counter() - t0) / reps
     line = {
         "metric": "polish summary encoder, aligned bases/s (pileup -> summary rows)",
         "value": value, "unit": "aligned bases/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
@@ -923,10 +932,6 @@ def polish_encoder_bench(args):
                              "pixels + the (position, index) int64 pair); 512-position tiles of 1.2 kb regions: 768 workgroups for 256 "
                              "regions, the launch is latency- not bandwidth-bound at this size"},
         "kernels_ms": avg,
-        "host_buffers_one_call": {"value": stats["bases"] / t_one, "unit": "aligned bases/s", "ms": t_one * 1e3,
-                                  "regions_per_s": n_regions / t_one,
-                                  "note": "pa_polish_encoder_stage_batch + run + result copy per batch: gather into page-locked blocks, one "
-                                          "H2D per array, kernels, one wait, D2H of the rows"},
     }
     # The roof that binds polish_tile_kernel: 768 workgroups are ONE round of wavefronts (6 per SIMD), so the launch is as long as its
     # slowest wavefront's dependent chain -- the issue share and the share of their cycles the wavefronts spend waiting say so
@@ -944,7 +949,20 @@ def polish_encoder_bench(args):
             "source": src, "stale": counters_stale(src_round, "encoder_polish.hip", "encoder_common.h")}
     except Exception:       # noqa: BLE001
         pass
-    if not args.no_cpu_baseline:
+    if args.full:
+        # host buffers in, host arrays out, one call (what AlignmentSummarizer.create_summaries makes per batch of regions)
+        reps = max(3, args.steps // 2)
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            b2 = StagedSummaries(gens, flats, spans)
+            b2.run()
+            image, pos = b2.results()
+        t_one = (time.perf_counter() - t0) / reps
+        line["host_buffers_one_call"] = {"value": stats["bases"] / t_one, "unit": "aligned bases/s", "ms": t_one * 1e3,
+                                         "regions_per_s": n_regions / t_one,
+                                         "note": "pa_polish_encoder_stage_batch + run + result copy per batch: gather into page-locked blocks, one "
+                                                 "H2D per array, kernels, one wait, D2H of the rows"}
+    if args.full and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(REPO, "oracle"))
         from oracle import encoder_cpu
         one = encoder_cpu.time_polish_regions(regions[:16], args.cpu_seconds)
@@ -1134,7 +1152,7 @@ def secondary_block(args):
         mid = good[len(good) // 2]
         mid["_runs"] = [round(g[key], 1) for g in good]
         return mid
-    d = median_of([sys.executable, me, "--model", "polish", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--full-line"], 300) if want("polish") else SKIP
+    d = median_of([sys.executable, me, "--model", "polish", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline", "--full-line"], 300) if want("polish") else SKIP
     out["polish"] = d if "error" in d else {
         "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "workload": d["config"]["workload"],
         "h2d_d2h": d["config"]["h2d_d2h"], "roofline": {k: d["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac",
@@ -1142,7 +1160,7 @@ def secondary_block(args):
                                                                                       "hbm_GBps") if k in d["roofline"]},
         "batch128": d.get("batch128"), "device_resident": (d.get("device_resident") or {}).get("value"),
         "runs": d["_runs"], "seconds": d["_seconds"]}
-    d = median_of([sys.executable, me, "--model", "encoder", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"], 300) if want("encoder") else SKIP
+    d = median_of([sys.executable, me, "--model", "encoder", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline"], 300) if want("encoder") else SKIP
     out["encoder"] = d if "error" in d else {
         "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "regions_per_step": d["config"]["regions_per_gpu_per_step"],
         "aligned_bases_per_step": d["config"]["aligned_bases_per_step"], "candidates_per_step": d["config"]["candidates_per_step"],
@@ -1150,14 +1168,14 @@ def secondary_block(args):
                                                    "issue") if k in d["roofline"]},
         "host_buffers_one_call": d["host_buffers_one_call"]["value"], "packed_host_fed": d.get("packed_host_fed"),
         "runs": d["_runs"], "seconds": d["_seconds"]}
-    d = median_of([sys.executable, me, "--model", "polish-encoder", "--steps", "10", "--warmup", "2", "--no-cpu-baseline"], 300) if want("polish_encoder") else SKIP
+    d = median_of([sys.executable, me, "--model", "polish-encoder", "--steps", "10", "--warmup", "2", "--full", "--no-cpu-baseline"], 300) if want("polish_encoder") else SKIP
     out["polish_encoder"] = d if "error" in d else {
         "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "regions_per_step": d["config"]["regions_per_step"],
         "aligned_bases_per_step": d["config"]["aligned_bases_per_step"], "rows_per_step": d["config"]["rows_per_step"],
         "roofline": {k: d["roofline"][k] for k in ("bound", "kernel", "achieved", "peak", "unit", "frac", "algorithmic_bytes_per_launch", "issue")
                      if k in d["roofline"]},
         "host_buffers_one_call": d["host_buffers_one_call"]["value"], "runs": d["_runs"], "seconds": d["_seconds"]}
-    d = median_of([sys.executable, me, "--model", "realign", "--steps", "10", "--warmup", "2", "--cpu-seconds", "3"], 300) if want("realign") else SKIP
+    d = median_of([sys.executable, me, "--model", "realign", "--steps", "10", "--warmup", "2", "--full", "--cpu-seconds", "3"], 300) if want("realign") else SKIP
     out["realign"] = d if "error" in d else {
         "value": d["value"], "unit": d["unit"], "ms_per_step": d["ms_per_step"], "workload": d["config"]["workload"],
         "reads_per_s_4_worker_threads": d.get("reads_per_s_4_worker_threads"), "reads_per_s_one_region_call": d.get("reads_per_s_one_region_call"),
@@ -1414,8 +1432,9 @@ def final_line(full, limit=LINE_LIMIT, full_record=FULL_RECORD):
     """The ONE stdout line the driver parses, assembled from the full record: the contract's headline keys, `config`, `dtype`,
     `roofline` (with `traffic` and the algorithmic fraction of the dtype's dense peak), `cpu_baseline`, the default-batch call and one
     tuple per secondary leg -- numbers to four figures, prose cut to what names the thing.  Everything else (stage times, notes,
-    per-run figures, the whole `secondary` block) is in `full_record`, written next to the profiles by the same run.  Optional
-    blocks are dropped, least important first, until the line is under `limit` bytes; the required ones never are."""
+    per-run figures, the whole `secondary` block) is in `full_record`, written next to the profiles by the same --full run (None:
+    no record was written, and the line does not name one).  Optional blocks are dropped, least important first, until the line is
+    under `limit` bytes; the required ones never are."""
     def short(s, n):
         return s if not isinstance(s, str) or len(s) <= n else s[:n - 1].rstrip() + "…"
     cfg = full.get("config", {})
@@ -1462,7 +1481,8 @@ def final_line(full, limit=LINE_LIMIT, full_record=FULL_RECORD):
     for k, v in optional:
         if v:
             line[k] = v
-    line["full_record"] = full_record
+    if full_record:
+        line["full_record"] = full_record
     drop = ["cpu_baseline_single_process", "hbm_view", "kernels", "end_to_end_tflops", "device_resident"]
     while len(json.dumps(line)) >= limit and drop:
         line.pop(drop.pop(0), None)
@@ -1715,7 +1735,7 @@ def main():
         sys.stderr.write("[bench] rank %d: last timed step's outputs in %s: %s\n" % (rank, args.dump_outputs, dumped))
 
     image_legs = None
-    if world > 1 and variant and not args.no_image_legs and not args.resident_only:
+    if args.full and world > 1 and variant and not args.no_image_legs and not args.resident_only:
         import torch.distributed as dist
         mine = rank_image_legs(rank, world, device)
         gathered = [None] * world
@@ -1734,7 +1754,7 @@ def main():
             image_legs["errors"] = errs[:2]
 
     extras = {}
-    if world == 1 and not args.no_extras and not args.resident_only:
+    if args.full and world == 1 and not args.no_extras and not args.resident_only:
         # (a) the same kernels on inputs already in HBM (round 1's figure): one device pass of `chunk` units, repeated
         xr = pool_dev[:chunk].contiguous()
         outs_d = [torch.empty((chunk,) + sh, dtype=out_dtype, device=dev) for sh in out_shapes]
@@ -1835,7 +1855,7 @@ def main():
         line.update(extras)
         if "device_resident" in extras:
             line["host_path_over_device_resident"] = value / extras["device_resident"]["value"]
-        if world == 1 and not args.no_cpu_baseline and args.model != "ns-literal":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.model != "ns-literal":
             # whole-box CPU number = the reference's own scheme (single-thread workers, one per physical core); the
             # single-process multi-thread figure is kept beside it
             single = cpu_baseline(args.model, args.cpu_seconds)
@@ -1845,15 +1865,18 @@ def main():
             line["speedup_vs_cpu_baseline"] = value / line["cpu_baseline"]["value"]
             # BASELINE.md holds no published number for this metric: vs_baseline stays null; the ratio north_star targets (>= 50 x
             # the reference CPU run_inference on the same box's host cores) is speedup_vs_cpu_baseline
-        if variant and world == 1 and not args.no_secondary and not args.resident_only and not args.no_extras:
+        if args.full and variant and world == 1 and not args.no_secondary and not args.resident_only and not args.no_extras:
             sync()
             line["secondary"] = secondary_block(args)
-        # the whole record goes to a file; the stdout line is the part the driver parses, under LINE_LIMIT bytes (final_line)
+        # the stdout line is the part the driver parses, under LINE_LIMIT bytes (final_line); a --full run writes the whole record
+        # to a file as well
         if args.full_line:
             print(json.dumps(line))
-        else:
+        elif args.full:
             write_full_record(line)
             print(json.dumps(final_line(line)))
+        else:
+            print(json.dumps(final_line(line, full_record=None)))
 
     if variant:
         lib.pa_variant_destroy(handle)

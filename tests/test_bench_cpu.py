@@ -18,11 +18,44 @@ def _bench():
 
 def test_help_and_contract_flags():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], capture_output=True, text=True, check=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup", "--model", "--resident-only", "--full-line", "--legs", "--no-image-legs",
+    for flag in ("--gpus", "--steps", "--warmup", "--model", "--resident-only", "--full", "--full-line", "--legs", "--no-image-legs",
                  "--dump-outputs"):
         assert flag in out
     bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0"], capture_output=True, text=True)
     assert bad.returncode == 2 and "--steps" in bad.stderr                  # a run always times the steps it was asked for
+
+
+def test_extra_legs_wait_for_full():
+    """A plain run times the headline and prints its line; the secondary block, the CPU baselines and the other extra legs run
+    only under --full.  --legs picks secondary legs, so without --full it is refused rather than ignored; a line with no record
+    file behind it names none."""
+    bad = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--legs", "polish"], capture_output=True, text=True)
+    assert bad.returncode == 2 and "--full" in bad.stderr
+    b = _bench()
+    record = {"metric": "m", "value": 1.0, "unit": "u", "config": {"workload": "w"}, "roofline": {"bound": "mfma"}}
+    assert "full_record" not in b.final_line(record, full_record=None)
+    assert b.final_line(record)["full_record"] == b.FULL_RECORD
+
+
+def test_secondary_block_asks_its_model_runs_for_full(monkeypatch):
+    """The --full record reads the model legs' extra keys (polish: batch128 / device_resident; encoder and polish-encoder:
+    host_buffers_one_call; realign: cpu_baseline and the worker-thread figures), which a model run prints only under --full: every
+    child run of those legs passes it."""
+    import argparse
+    import types
+    b = _bench()
+    seen = []
+
+    def fake_run(cmd, **kw):
+        seen.append(list(cmd))
+        return types.SimpleNamespace(stdout="", stderr="", returncode=1)
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    out = b.secondary_block(argparse.Namespace(legs="polish,encoder,polish_encoder,realign"))
+    assert set(out) == {"polish", "encoder", "polish_encoder", "realign"}
+    models = [c[c.index("--model") + 1] for c in seen]
+    assert sorted(set(models)) == ["encoder", "polish", "polish-encoder", "realign"] and len(seen) == 12      # three runs each
+    for cmd in seen:
+        assert "--full" in cmd, cmd
 
 
 def test_traffic_comes_from_the_committed_pmc_passes():

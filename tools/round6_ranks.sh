@@ -1,7 +1,7 @@
 # Round 6: the N-rank code path of bench.py on the one-GPU box (ranks share the device, gloo: plumbing only, never a scaling number).
 O=gpurun_out/r06; mkdir -p $O
 for n in 2 8; do
-  PEPPER_AMD_BENCH_SHARE_GPU=1 timeout 900 python bench.py --gpus $n --steps 3 --warmup 1 --per-gpu 65536 --pool 131072 --no-cpu-baseline --no-extras > $O/bench_${n}rank_shared.json 2> $O/bench_${n}rank_shared.err
+  PEPPER_AMD_BENCH_SHARE_GPU=1 timeout 900 python bench.py --full --gpus $n --steps 3 --warmup 1 --per-gpu 65536 --pool 131072 --no-cpu-baseline --no-extras > $O/bench_${n}rank_shared.json 2> $O/bench_${n}rank_shared.err
   echo "rc=$?"; tail -n 1 $O/bench_${n}rank_shared.json | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print(d['n_gpus'], d['value'], d['config']['ranks_seen'], d['config']['collective_backend'], d['config'].get('per_rank_image_legs'))"
