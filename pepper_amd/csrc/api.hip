@@ -488,10 +488,8 @@ int init_base(ModelBase* m, int device, void* hip_stream) {
 struct pa_variant_model : ModelBase {
     pa_variant_config cfg{};
     int H = 256, L1 = 512;
-    bool fuse_input = true;      // PA_FUSE_INPUT=0 falls back to GEMM + Xp for A/B measurements
     bool split_gemm = true;      // PA_SPLIT_GEMM=0 keeps the big GEMMs on the f32 matrix instructions
     bool split_rec = true;       // PA_SPLIT_REC=0 keeps the recurrences on the f32 matrix instructions
-    bool fuse_dec = true;        // PA_FUSE_DEC=0: decoder projection as a GEMM + Xp instead of inside the step loop
     int64_t small_batch = 3072;  // calls of at most this many windows take the GEMM + Xp decoder (PA_SMALL_BATCH)
     int64_t small_rows = 3072;   // ... and 32-row workgroups in both step loops (PA_SMALL_ROWS); at 4096 windows both schedules take 2.25 ms
     std::vector<RecLayer> rec;   // encoder layers then decoder layers
@@ -506,7 +504,6 @@ struct pa_variant_model : ModelBase {
     // ordinary small-call schedule (same results, the caller sees nothing but the time) and the handle leaves the split
     // alone for its next `US_HOLDOFF` small calls.  PA_UNIT_SPLIT=0: never.
     bool unit_split = true;
-    int64_t unit_split_max = 1024;    // PA_UNIT_SPLIT_MAX: 512 = only the eight-member form (513-1024 windows: four members of 64 units)
     int split_holdoff = 0;            // small calls still to run without the split after a group did not meet
     int64_t split_fallbacks = 0;      // calls that were run again (pa_variant_split_fallbacks)
     int split_sabotage = 0;           // PA_UNIT_SPLIT_SABOTAGE=n (tests): in the next n split launches one member never arrives
@@ -543,18 +540,15 @@ int pa_variant_create(const pa_variant_config* cfg, const char* const* names, co
     if (m->cfg.max_chunk <= 0) m->cfg.max_chunk = 16384;
     // the h2 GEMM addresses its A operand through a 32-bit buffer descriptor: [n*T, 2H] h2 rows must stay < 4 GiB
     m->cfg.max_chunk = std::min<int32_t>(m->cfg.max_chunk, (int32_t)((int64_t)0xf0000000 / ((int64_t)cfg->window * 2 * 256 * 4)));
-    if (const char* e = getenv("PA_FUSE_INPUT")) m->fuse_input = e[0] != '0';
     if (const char* e = getenv("PA_SPLIT_GEMM")) m->split_gemm = e[0] != '0';
     if (const char* e = getenv("PA_SPLIT_REC")) m->split_rec = e[0] != '0';
     StateDict sd(names, data, numel, n_tensors);
     if (!(state_dict_max_abs_weight(sd) < kSplitMaxWeight)) m->split_gemm = false;   // see kSplitMaxWeight
     m->split_rec = m->split_rec && m->split_gemm;   // the h2 layer output needs the h2 consumers
-    if (const char* e = getenv("PA_FUSE_DEC")) m->fuse_dec = e[0] != '0';
     if (const char* e = getenv("PA_SMALL_BATCH")) m->small_batch = atoll(e);
     if (const char* e = getenv("PA_SMALL_ROWS")) m->small_rows = atoll(e);
     if (const char* e = getenv("PA_UNIT_SPLIT")) m->unit_split = e[0] != '0';
     if (const char* e = getenv("PA_UNIT_SPLIT_SABOTAGE")) m->split_sabotage = atoi(e);
-    if (const char* e = getenv("PA_UNIT_SPLIT_MAX")) m->unit_split_max = std::min<int64_t>(1024, atoll(e));
     int rc = init_base(m, cfg->device, hip_stream);
     const int H = m->H;
     for (int mod = 0; mod < 2 && rc == PA_OK; ++mod)
@@ -649,7 +643,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     // step loop contracts K = 256 only (14.7 us per step): 512 windows 2.16 -> 1.42 ms, 1024: 2.17 -> 1.59, 2048: 2.18 -> 1.83;
     // at 4096 the fused loop wins again (profiles/r03_small_batch_kernels.json).  PA_SMALL_BATCH=0: always fused.
     const bool bi = m->batch_invariant;
-    const bool fuse_dec = m->fuse_dec && (bi || n > m->small_batch);
+    const bool fuse_dec = bi || n > m->small_batch;
     // ... and, up to `small_rows` windows, both step loops run with 32-row workgroups (rnn_h2.hip MTILES = 1): a step is one
     // CU's affair, half the rows are half the MFMAs and half the gate phase per step (PA_SMALL_ROWS, 0 = never)
     // (batch-invariant mode too: the 32-row workgroups issue every row's MFMA chain and gate arithmetic exactly as the 64-row
@@ -657,7 +651,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     // them as well)
     const bool small_rows = n <= m->small_rows;
     // up to 1024 windows: every layer as projection GEMM + the unit-split step loop (see pa_variant_model::unit_split)
-    bool unit_split = allow_split && !bi && m->unit_split && n <= m->unit_split_max && H == 256 && m->split_rec && !fuse_dec && m->mlp_w32 != nullptr &&
+    bool unit_split = allow_split && !bi && m->unit_split && n <= 1024 && H == 256 && m->split_rec && !fuse_dec && m->mlp_w32 != nullptr &&
                       m->mlp_w != nullptr && C <= 8;
     for (const RecLayer& r : m->rec) unit_split = unit_split && r.w_hh_h2 != nullptr && r.prescaled;
     // the members of a group wait for each other: every workgroup of the launch must be on the device at once (a CPX
@@ -677,7 +671,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         // (the out-of-range counter as it is before this call: a pass that gave up feeds garbage to the MLP kernel)
         HIP_TRY(hipMemcpyAsync(&m->us_host[1], ovf_counter, sizeof(int), hipMemcpyDeviceToHost, m->stream));
     }
-    const bool fuse_in = m->fuse_input && !unit_split;
+    const bool fuse_in = !unit_split;
     bool need_xp = !(a_kind == pa::A_I8 && fuse_in && !m->rec.empty() && m->rec[0].w_cat != nullptr);
     for (size_t li = 1; li < m->rec.size(); ++li)
         need_xp = need_xp || !(m->split_rec && fuse_dec && m->rec[li].w_cat_dec_h2 != nullptr);
@@ -708,7 +702,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
             if (rec_h2 && r.w_cat_h2 != nullptr)
                 LAUNCH_TRY(m, "lstm_rec_h2_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
                            pa::launch_lstm_rec_h2(H, nullptr, 0, static_cast<const int8_t*>(cur), r.K, bias_l,
-                                                  r.w_cat_h2->p, y, 2 * H, (int)n, T, m->stream, r.prescaled, small_rows));
+                                                  r.w_cat_h2->p, y, 2 * H, (int)n, T, m->stream, small_rows));
             else
                 LAUNCH_TRY(m, "lstm_rec_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
                            pa::launch_lstm_rec_fused(H, static_cast<const int8_t*>(cur), r.K, r.b_in->f(),
@@ -717,7 +711,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
             // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
             LAUNCH_TRY(m, "lstm_dec_h2_fused", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
                        pa::launch_lstm_dec_h2(H, cur, cur_ld, bias_l, r.w_cat_dec_h2->p, y, 2 * H, (int)n, T, m->stream,
-                                              r.prescaled, bi && small_rows));
+                                              bi && small_rows));
         } else {
             if (li > 0 && m->split_gemm && r.w_ih_h2 != nullptr) {
                 // the previous layer's y is only read by this projection: if it is still f32, split it
@@ -744,7 +738,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
             } else if (rec_h2)
                 LAUNCH_TRY(m, "lstm_rec_h2", 2.0 * n * T * (4.0 * H) * H * 2,
                            pa::launch_lstm_rec_h2(H, m->xp->f(), NX, nullptr, 0, nullptr, r.w_hh_h2->p, y, 2 * H, (int)n,
-                                                  T, m->stream, r.prescaled, small_rows));
+                                                  T, m->stream, small_rows));
             else
                 LAUNCH_TRY(m, "lstm_rec", 2.0 * n * T * (4.0 * H) * H * 2,
                            pa::launch_lstm_rec(H, m->xp->f(), NX, r.w_hh->f(), y, 2 * H, (int)n, T, m->stream));
@@ -762,9 +756,8 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     const int tiles1 = (int)((n + 255) / 256) * ((m->L1 + 255) / 256);
     int splits = 1;
     // (up to 32 slices: a call of 512 windows has 4 output tiles, 0.137 ms with 8 slices, 0.078 with 32; big calls have tiles
-    // enough and stay at 2 slices.  PA_L1_SPLITS overrides the cap)
-    static const int max_splits = getenv("PA_L1_SPLITS") ? atoi(getenv("PA_L1_SPLITS")) : 32;
-    while (!bi && splits < max_splits && tiles1 * splits * 2 <= 256 && (size_t)(splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
+    // enough and stay at 2 slices)
+    while (!bi && splits < 32 && tiles1 * splits * 2 <= 256 && (size_t)(splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
         splits *= 2;
     if (bi) splits = kCanonicalL1Splits;   // (the workspace holds 8 x n x L1 floats: room for them at any n)
     if (m->split_gemm && m->lin[0].w_h2 != nullptr && cur_kind == pa::A_F32) {
@@ -923,10 +916,8 @@ int pa_variant_forward_host(pa_variant_model* m, const int8_t* images, int64_t n
 // ================================================================================================
 struct pa_polish_model : ModelBase {
     pa_polish_config cfg{};
-    bool fuse_input = true;      // PA_FUSE_INPUT=0 falls back to GEMM + Xp
     bool split_gemm = true;      // PA_SPLIT_GEMM=0 keeps the projections on the f32 matrix instructions
     bool split_rec = true;       // PA_SPLIT_REC=0 keeps the recurrences on the f32 matrix instructions
-    bool fuse_dec = true;        // PA_FUSE_DEC=0: decoder projection as a GEMM + Xp instead of inside the step loop
     bool y_h2 = false;           // format of the last polish_window output
     bool fuse_head = true;       // PA_FUSE_HEAD=0: last decoder layer writes y, dense1 + softmax + overlap-add as their own kernel
     int small_max = 4096;        // calls of at most this many chunks take the small-call schedule (PA_POLISH_SMALL_MAX; 0: never)
@@ -989,7 +980,7 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
                            pa::launch_gru_small_h2(H, m->xp->f(), NX, r.w_hh_small_h2->p, r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H,
                                                    (int)n, T, m->stream));
                 cur_h2 = true;
-            } else if (stage == 0 && l == 0 && cur_kind == pa::A_U8 && (r.w_cat != nullptr || fused_h2_ok) && m->fuse_input) {
+            } else if (stage == 0 && l == 0 && cur_kind == pa::A_U8 && (r.w_cat != nullptr || fused_h2_ok)) {
                 if (fused_h2_ok)
                     LAUNCH_TRY(m, "gru_rec_h2_fused_in", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
                                pa::launch_gru_rec_h2(H, nullptr, 0, static_cast<const uint8_t*>(cur), r.K, xbs, r.b_in->f(),
@@ -1002,7 +993,7 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
                                                         m->stream));
                 cur_h2 = fused_h2_ok;
             } else if (want_head && stage == 1 && l == L - 1 && rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 &&
-                       cur_bs == 0 && m->fuse_dec && m->fuse_head && m->dense_h2 != nullptr && H == 128) {
+                       cur_bs == 0 && m->fuse_head && m->dense_h2 != nullptr && H == 128) {
                 // last layer: projection AND dense1 contracted inside the step loop; no layer output at all
                 if (int rc = m->part->ensure(pa::dense_partials_floats((int)n, T) * sizeof(float))) return rc;
                 LAUNCH_TRY(m, "gru_dec_h2_fused_dense", 2.0 * n * T * ((3.0 * H) * (H + r.K) + m->cfg.num_classes * H) * 2,
@@ -1010,7 +1001,7 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
                                                        ldh, m->dense_h2->p, m->part->f(), (int)n, T, m->stream));
                 *head_fused = true;
                 cur_h2 = true;
-            } else if (rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 && cur_bs == 0 && m->fuse_dec) {
+            } else if (rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 && cur_bs == 0) {
                 // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
                 LAUNCH_TRY(m, "gru_dec_h2_fused", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
                            pa::launch_gru_dec_h2(H, cur, cur_ld, r.b_in->f(), r.w_cat_dec_h2->p, r.b_hn->f(), h0l, ldh, hnl,
@@ -1080,13 +1071,11 @@ int pa_polish_create(const pa_polish_config* cfg, const char* const* names, cons
     m->cfg = *cfg;
     if (m->cfg.max_chunk <= 0) m->cfg.max_chunk = 16384;   // 128 chunks per workgroup and direction: 256 workgroups
     m->cfg.max_chunk = std::min<int32_t>(m->cfg.max_chunk, (int32_t)((int64_t)0xf0000000 / ((int64_t)cfg->window * 2 * cfg->hidden_size * 4)));
-    if (const char* e = getenv("PA_FUSE_INPUT")) m->fuse_input = e[0] != '0';
     if (const char* e = getenv("PA_SPLIT_GEMM")) m->split_gemm = e[0] != '0';
     if (const char* e = getenv("PA_SPLIT_REC")) m->split_rec = e[0] != '0';
     StateDict sd(names, data, numel, n_tensors);
     if (!(state_dict_max_abs_weight(sd) < kSplitMaxWeight)) m->split_gemm = false;   // see kSplitMaxWeight
     m->split_rec = m->split_rec && m->split_gemm && cfg->hidden_size == 128;
-    if (const char* e = getenv("PA_FUSE_DEC")) m->fuse_dec = e[0] != '0';
     int rc = init_base(m, cfg->device, hip_stream);
     const int H = cfg->hidden_size;
     for (int stage = 0; stage < 2 && rc == PA_OK; ++stage)

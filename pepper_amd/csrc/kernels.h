@@ -57,10 +57,10 @@ void pack_rec_weights_h2(const float* const whh[2], const float* const wih[2], i
                          uint32_t* out, const float* const* bias = nullptr);   // bias: column H + F (fused layers, F < KX)
 size_t rec_weights_h2_words(int G, int H, int KX);
 int gru_fused_input_kx(int H, int F);   // 16 / 128: padded width of the uint8-input step loop; 0: projection as a GEMM
-// prescaled: weights / bias / Xp were multiplied per gate row by the exp2 constants (see rnn_h2.hip).
+// The weights, the bias and Xp are multiplied per gate row by the exp2 constants (see rnn_h2.hip).
 hipError_t launch_lstm_rec_h2(int H, const float* Xp, int ldx, const int8_t* X, int F, const float* bias,
                               const void* Wp, void* Y, int ldy, int B, int T, hipStream_t stream,
-                              bool prescaled = false, bool small = false);   // small: 32-row workgroups (small calls)
+                              bool small = false);   // small: 32-row workgroups (small calls)
 
 // The step loop of a call of at most 512 windows with a tile's hidden units split over eight workgroups that exchange h_t
 // through `exch` every step (rnn_h2.hip lstm_rec_h2_split_kernel); prescaled weights only.  *failed is set when a group
@@ -76,7 +76,7 @@ hipError_t launch_lstm_rec_h2_split(int H, const float* Xp, int ldx, const void*
 // LSTM layer fed by an h2 layer output Xh [B*T, 2H]: projection contracted inside the step loop (weights packed
 // with pack_rec_weights_h2(..., F = 2H, KX = 2H); bias = b_ih + b_hh).
 hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias, const void* Wp, void* Y, int ldy, int B,
-                              int T, hipStream_t stream, bool prescaled, bool small = false);   // small: 32-row workgroups
+                              int T, hipStream_t stream, bool small = false);   // small: 32-row workgroups
 // GRU (H = 128) counterpart; arguments as launch_gru_rec / launch_gru_rec_fused, Y in h2 format.
 hipError_t launch_gru_rec_h2(int H, const float* Xp, int ldx, const uint8_t* X, int F, int64_t x_bstride,
                              const float* bias, const void* Wp, const float* bhn, const float* h0, int ldh0, float* hn,

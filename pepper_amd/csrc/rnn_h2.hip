@@ -23,11 +23,6 @@
 #include "common.h"
 #include "kernels.h"
 
-// measured r02 (16384 windows, device-resident pass): 2.566 -> 2.596 M windows/s with nt on the once-through streams
-#ifndef PA_NT_DEFAULT
-#define PA_NT_DEFAULT true
-#endif
-
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -45,7 +40,7 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 // value of lane ^ 1 (quad_perm [1,0,3,2])
 
 
-// PRE: the packed weights, the bias and Xp arrive pre-multiplied per gate row by -log2(e) (i, f, o) or
+// The packed weights, the bias and Xp arrive pre-multiplied per gate row by -log2(e) (i, f, o) or
 // +2 log2(e) (g), so the accumulators ARE the exp2 arguments of sigmoid / tanh (api.hip build_rec_layer).
 // XG (decoder layers): the layer input x_t is the previous layer's output, an h2 tensor Xh [B*T, KX]; its
 // projection is contracted inside the step loop (K = H + KX).  No projection GEMM, no Xp round trip (4.4 GB
@@ -58,7 +53,8 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 // weights out of L2.)
 // SAUX: cache policy of the streams that pass through once -- the x slab loads of the XG form and the y stores (2 = nt:
 // the lines are not kept in the XCD's L2, which has to hold this direction's 3 MB of weight fragments that every
-// workgroup re-reads every step; 0 = default policy).
+// workgroup re-reads every step; 0 = default policy, what the forms seeded from Xp are launched with).  Measured r02
+// (16384 windows, device-resident pass): 2.566 -> 2.596 M windows/s with nt on the once-through streams.
 // BC (fused int8 first layer with F < KX): the bias lives in column H + F of the packed weights and x carries a constant
 // 1.0 there, so the first MFMA of a step starts every accumulator from the inline constant 0: no bias loads and no 128
 // register moves per step in the gate phase, which is bound by VALU issue (two waves per SIMD, ~1300 instructions each).
@@ -67,7 +63,7 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 // 16 MTILES elements per lane -- whatever the number of workgroups, so a call of a few hundred windows, which fills a small
 // part of the chip either way, takes half the time per step with 32-row workgroups (twice as many of them, each still
 // streaming the direction's weight fragments from L2).  Big calls keep 64 rows: half the weight stream per window.
-template <int H, int KX, bool PRE, bool XG = false, int SAUX = 0, bool BC = false, int MTILES = 2>
+template <int H, int KX, bool XG = false, int SAUX = 0, bool BC = false, int MTILES = 2>
 __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float* __restrict__ Xp, int ldx,
                                                                      const int8_t* __restrict__ Xi, int F,
                                                                      const float* __restrict__ bias,
@@ -185,11 +181,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 
     struct Frag { h8 b[4][2], a[MTILES][2]; };     // [gate][hi, lo], [row tile][hi, lo]
     const uint32_t* arow = lds + li * ROWD + hf * 8;
-    bool exp_loads = true;       // PA_EXP_NO_BLOAD (energy experiment, wrong results): weight fragments loaded once, not per step
     auto load_b = [&](int s, Frag& fr) {
-#ifdef PA_EXP_NO_BLOAD
-        if (!exp_loads) return;
-#endif
 #pragma unroll
         for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -248,10 +240,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
         x_load(t0);
         x_store();
         load_b(0, ring[0]);
-#ifdef PA_EXP_NO_BLOAD
-        load_b(1, ring[1]);
-        exp_loads = false;
-#endif
     }
     __syncthreads();
 
@@ -400,10 +388,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                     f32x2 ai = {acc[m][0][r], acc[m][0][r + 1]}, af = {acc[m][1][r], acc[m][1][r + 1]},
                           ag = {acc[m][2][r], acc[m][2][r + 1]}, ao = {acc[m][3][r], acc[m][3][r + 1]};
                     if (KX && !BC) { ai += cb[0]; af += cb[1]; ag += cb[2]; ao += cb[3]; }
-                    if (!PRE) {
-                        ai *= -1.4426950408889634f; af *= -1.4426950408889634f;
-                        ag *= 2.8853900817779268f;  ao *= -1.4426950408889634f;
-                    }
                     auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
                     auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
                     const f32x2 ig = rcp(one + ex2(ai));
@@ -449,7 +433,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 // what this kernel does.  All eight members of a group must be resident at once: the launcher takes at most 256 workgroups
 // (two fit a CU), the spin is bounded (~25 ms), and a group that does not meet sets *failed and returns instead of hanging:
 // the host then runs the call again with the ordinary small-call schedule (api.hip variant_forward_chunk).
-// PRE form only (weights, Xp and bias pre-multiplied by the exp2 factors; Xp = x W_ih^T + b from the projection GEMM).
+// Weights, Xp and bias pre-multiplied by the exp2 factors as above; Xp = x W_ih^T + b from the projection GEMM.
 constexpr int US_AUX_SC1 = 16;                // cache policy bit sc1 of the gfx940+ buffer instructions
 
 // NTW: unit tiles of 32 per member.  1: eight members (calls of at most 512 windows: 256 workgroups); 2: four members of 64
@@ -1278,229 +1262,6 @@ __global__ __launch_bounds__(256, 1) void gru_small_h2_kernel(const float* __res
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// GRU decoder layer with its input projection fused (polish model): the layer input x_t is the previous
-// layer's output, already an h2 tensor [B*T, KX] with KX = 2H, so the step contracts [h_{t-1} | x_t]
-// (K = H + KX = 384) against [W_hh | W_ih] and neither the projection GEMM nor its 2.5 GB-per-window Xp
-// round trip exist.  What makes it fit: 64 batch rows per workgroup (LDS rows of 1552 B = 97 KB), four
-// waves = one per SIMD with both row tiles each (so every weight fragment is fetched once per workgroup:
-// 590 KB per step, ~43 B/clk/CU), a 3-deep fragment ring instead of a second wave to cover L2 latency,
-// and the next step's x slab (64 KB) prefetched into registers during the MFMA phase.
-//   /root/reference/pepper/modules/python/models/simple_model.py:32
-template <int H, int KX>
-__global__ __launch_bounds__(256, 1) void gru_dec_h2_kernel(const uint32_t* __restrict__ Xh, int ldxh,
-                                                            const float* __restrict__ bias,
-                                                            const uint32_t* __restrict__ Wp,
-                                                            const float* __restrict__ bhn,
-                                                            const float* __restrict__ h0, int ldh0,
-                                                            float* __restrict__ hn, int ldhn,
-                                                            uint32_t* __restrict__ Y, int ldy, int B, int T) {
-    constexpr int KT = H + KX, KS = KT / 16, KSH = H / 16, NT = H / 32, MTG = MT, NTHR = NT * 64;
-    constexpr int ROWB = KT * 4 + 16, ROWD = ROWB / 4;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTG][ROWD] h2 rows of [h | x]
-    static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
-    static_assert(NT == 4, "one wave per SIMD");
-
-    int dir, btile;
-    decode_block(blockIdx.x, dir, btile);
-    const int b0 = btile * MTG;
-    if (b0 >= B) return;
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int li = lane & 31, hf = lane >> 5;
-    const int col = u * 32 + li;
-
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(Wp + ((size_t)dir * (3 * NT) + u) * KS * 512), 0, 0x7fffffff, 0x00020000);
-    const unsigned woff = lane * 16u;
-    const size_t lb = (size_t)(b0 + 4 * hf);
-    const bool odd = li & 1;
-    uint32_t* hl_dst = lds + 4 * hf * ROWD + (col >> 3) * 8 + (odd ? 4 : 0) + ((col & 7) >> 1);
-    const uint32_t* arow = lds + li * ROWD + hf * 8;
-
-    for (int idx = tid; idx < MTG * ROWD; idx += NTHR) lds[idx] = 0u;
-    __syncthreads();
-
-    const unsigned h2sel = h2_select(odd);
-    auto h2_word = [&](float hv) { return h2_word_of(hv, h2sel); };
-
-    f32x16 hreg[2], acc[2][4];     // r, z, n(hidden half), n(input half)
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int dr = 32 * m + (r & 3) + 8 * (r >> 2);
-            const float hv = h0 != nullptr ? h0[(lb + dr) * ldh0 + dir * H + col] : 0.0f;
-            hreg[m][r] = hv;
-            hl_dst[dr * ROWD] = h2_word(hv);
-        }
-    const float bn = bhn[dir * H + col];
-    const float b_r = bias[dir * 3 * H + col], b_z = bias[dir * 3 * H + H + col], b_nx = bias[dir * 3 * H + 2 * H + col];
-    auto seed_chunk = [&](int m, int qd) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            acc[m][0][4 * qd + e] = b_r;
-            acc[m][1][4 * qd + e] = b_z;
-            acc[m][2][4 * qd + e] = bn;
-            acc[m][3][4 * qd + e] = b_nx;
-        }
-    };
-
-    // x slab of one step: MTG rows x KX*4 bytes, 16 bytes per thread per pass
-    constexpr int XCPR = KX / 4;                       // 16-byte chunks per row (64)
-    constexpr int XROWS = NTHR / XCPR;                 // rows per pass (4)
-    constexpr int XN = MTG / XROWS;                    // passes (16)
-    const int xr = tid / XCPR, xc = tid % XCPR;
-    const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(Xh + (size_t)b0 * T * ldxh), 0, 0x7fffffff, 0x00020000);
-    const unsigned x_off = ((unsigned)(xr * T) * ldxh + xc * 4) * 4u;
-    uint32_t* x_dst = lds + xr * ROWD + H + xc * 4;
-    u32x4 xq[XN];
-    auto x_load_one = [&](int j, int t) {
-        // rows beyond B read the workspace padding (finite garbage in rows nobody reads back)
-        xq[j] = __builtin_amdgcn_raw_buffer_load_b128(xrs, x_off, ((unsigned)(j * XROWS * T + t) * ldxh) * 4u, 0);
-    };
-    auto x_store = [&]() {
-#pragma unroll
-        for (int j = 0; j < XN; ++j) *reinterpret_cast<u32x4*>(x_dst + j * XROWS * ROWD) = xq[j];
-    };
-    {
-        const int t0 = dir ? T - 1 : 0;
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) seed_chunk(m, qd);
-#pragma unroll
-        for (int j = 0; j < XN; ++j) x_load_one(j, t0);
-        x_store();
-    }
-    __syncthreads();
-
-    constexpr int CPR = H / 4, YROWS = NTHR / CPR, YC = MTG / YROWS;   // 32 chunks/row, 8 rows/pass, 8 passes
-    const int yc_row = tid / CPR, yc_c = tid % CPR;
-    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
-    const __amdgpu_buffer_rsrc_t ycrs =
-        __builtin_amdgcn_make_buffer_rsrc(Y + (size_t)b0 * T * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
-    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
-    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
-    auto yc_write = [&](int j, int tp, u32x4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, 0);
-    };
-
-    struct Frag { h8 b[3][2], a[2][2]; };
-    auto load_step = [&](int s, Frag& fr) {
-#pragma unroll
-        for (int g = 0; g < 3; ++g)
-#pragma unroll
-            for (int hl = 0; hl < 2; ++hl)
-                fr.b[g][hl] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(
-                                                         wrs, woff, (unsigned)((g * NT * KS + s) * 2 + hl) * 1024u, 0));
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            fr.a[m][0] = *reinterpret_cast<const h8*>(arow + m * 32 * ROWD + s * 16);
-            fr.a[m][1] = *reinterpret_cast<const h8*>(arow + m * 32 * ROWD + s * 16 + 4);
-        }
-    };
-
-    for (int step = 0; step < T; ++step) {
-        const int t = dir ? T - 1 - step : step;
-        const int tp = step > 0 ? (dir ? t + 1 : t - 1) : t;
-        const int tn = (step + 1 < T) ? (dir ? t - 1 : t + 1) : t;     // last step re-reads its own slab (unused)
-        // ---------------- MFMA phase ----------------
-        {
-            Frag ring[3];
-            load_step(0, ring[0]);
-            load_step(1, ring[1]);
-            u32x4 ycv = {0, 0, 0, 0};
-#pragma unroll
-            for (int s = 0; s < KS; ++s) {
-                const int p = s % 3;
-                if (s + 2 < KS) load_step(s + 2, ring[(p + 2) % 3]);
-                if (s < XN) x_load_one(s, tn);
-                if (s >= 1 && s <= YC) yc_write(s - 1, tp, ycv);
-                if (s < YC) ycv = yc_read(s);
-#pragma unroll
-                for (int term = 0; term < 3; ++term)
-#pragma unroll
-                    for (int g = 0; g < 3; ++g)
-#pragma unroll
-                        for (int m = 0; m < 2; ++m) {
-                            const int ai = (g == 2 && s >= KSH) ? 3 : g;
-                            acc[m][ai] = mfma_h(ring[p].a[m][term == 0 ? 1 : 0], ring[p].b[g][term == 1 ? 1 : 0], acc[m][ai]);
-                        }
-                if (s + 2 < KS) {
-#pragma unroll
-                    for (int q = 0; q < 6; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // B fragment
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // A fragment
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);       // x slab prefetch
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x040, 1, 0);       // y copy store
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);       // y copy read
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        lds_barrier();
-
-        // ---------------- gate phase ----------------
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * qd + e;
-                    const int dr = 32 * m + (r & 3) + 8 * (r >> 2);
-                    const float rgate = fast_sigmoid(acc[m][0][r]);
-                    const float zgate = fast_sigmoid(acc[m][1][r]);
-                    const float ngate = fast_tanh(acc[m][3][r] + rgate * acc[m][2][r]);
-                    const float hv = (1.0f - zgate) * ngate + zgate * hreg[m][r];
-                    hreg[m][r] = hv;
-                    hl_dst[dr * ROWD] = h2_word(hv);
-                }
-                seed_chunk(m, qd);
-            }
-        x_store();
-        lds_barrier();
-    }
-
-    {
-        const int tl = dir ? 0 : T - 1;
-#pragma unroll
-        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
-    }
-    if (hn != nullptr) {
-#pragma unroll
-        for (int m = 0; m < 2; ++m)
-#pragma unroll
-            for (int r = 0; r < 16; ++r)
-                hn[(lb + 32 * m + (r & 3) + 8 * (r >> 2)) * ldhn + dir * H + col] = hreg[m][r];
-    }
-}
-
-// PA_NT=1: nt cache policy on the once-through streams of the step loops (see SAUX)
-inline bool stream_nt() {
-    static const bool on = [] { const char* e = getenv("PA_NT"); return e ? e[0] != '0' : PA_NT_DEFAULT; }();
-    return on;
-}
-
-// PA_BIAS_COLUMN=0: the fused first layers take their biases in the gate phase instead of from the bias column
-inline bool bias_column() {
-    static const bool on = [] { const char* e = getenv("PA_BIAS_COLUMN"); return !e || e[0] != '0'; }();
-    return on;
-}
-
 inline int rec_grid(int B) {
     const int nbt = (B + MT - 1) / MT;
     return 2 * ((nbt + 3) / 4) * 4;
@@ -1562,7 +1323,7 @@ int gru_fused_input_kx(int H, int F) {
 size_t rec_weights_h2_words(int G, int H, int KX) { return (size_t)2 * (G * H / 32) * ((H + KX) / 16) * 2 * 256; }
 
 hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias, const void* Wp, void* Y, int ldy, int B,
-                              int T, hipStream_t stream, bool prescaled, bool small) {
+                              int T, hipStream_t stream, bool small) {
     if (B <= 0) return hipSuccess;
     if (H != 256 || (ldy & 7) || (ldxh & 7) || ldxh < 512) return hipErrorInvalidValue;
     if (small) {
@@ -1570,28 +1331,20 @@ hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias
         // just holds half the rows.  Xh / Y must hold the rows up to the next multiple of 32 (the workspace pads to 64).
         const int nbt = (B + 31) / 32, grid1 = 2 * ((nbt + 3) / 4) * 4;
         const size_t lds1 = (size_t)32 * (256 * 4 + 16) + (size_t)8 * 16 * 64 * 4 + (size_t)2 * 32 * 36 * 4;   // h + c + x ring
-#define PA_DEC1(PRE_, AUX_)                                                                                            \
-        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, PRE_, true, AUX_, false, 1>), dim3(grid1), dim3(512), lds1, stream, \
-                           (const float*)nullptr, 0, (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp),    \
-                           static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr, static_cast<const uint32_t*>(Xh), ldxh)
-        if (stream_nt()) { if (prescaled) PA_DEC1(true, 2); else PA_DEC1(false, 2); }
-        else { if (prescaled) PA_DEC1(true, 0); else PA_DEC1(false, 0); }
-#undef PA_DEC1
+        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, true, 2, false, 1>), dim3(grid1), dim3(512), lds1, stream,
+                           (const float*)nullptr, 0, (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp),
+                           static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr, static_cast<const uint32_t*>(Xh), ldxh);
         return hipGetLastError();
     }
     const size_t lds = (size_t)MT * (256 * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4 + (size_t)2 * MT * 36 * 4;   // h + c + x ring
     const int grid = rec_grid(B);
-#define PA_DEC(PRE_, AUX_)                                                                                             \
-    hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, PRE_, true, AUX_>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, \
-                       (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T, \
-                       debug_buffer(), static_cast<const uint32_t*>(Xh), ldxh)
-    if (stream_nt()) { if (prescaled) PA_DEC(true, 2); else PA_DEC(false, 2); }
-    else { if (prescaled) PA_DEC(true, 0); else PA_DEC(false, 0); }
-#undef PA_DEC
+    hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, true, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
+                       (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
+                       debug_buffer(), static_cast<const uint32_t*>(Xh), ldxh);
     return hipGetLastError();
 }
 
-// Unit-split step loop (lstm_rec_h2_split_kernel): B <= 1024, prescaled weights, Xp from the projection GEMM.
+// Unit-split step loop (lstm_rec_h2_split_kernel): B <= 1024, Xp from the projection GEMM.
 // exch: 2 * tiles4 groups x 64 KB; counters: 2 * tiles4 x 128 B (zeroed here); failed: one int the kernel sets when a group
 // did not meet.  tiles4 = row tiles of 32 rounded up to a multiple of four.  Eight members of 32 units up to 512 windows,
 // four of 64 units above: at most 256 workgroups either way.
@@ -1644,23 +1397,23 @@ hipError_t launch_lstm_rec_h2_split(int H, const float* Xp, int ldx, const void*
 }
 
 hipError_t launch_lstm_rec_h2(int H, const float* Xp, int ldx, const int8_t* X, int F, const float* bias,
-                              const void* Wp, void* Y, int ldy, int B, int T, hipStream_t stream, bool prescaled, bool small) {
+                              const void* Wp, void* Y, int ldy, int B, int T, hipStream_t stream, bool small) {
     if (B <= 0) return hipSuccess;
     if (H != 256 || (ldy & 7)) return hipErrorInvalidValue;
     const int grid = rec_grid(B);
-    if (small && prescaled) {
+    if (small) {
         // 32-row workgroups for small calls (see the kernel's MTILES): twice the workgroups, half the time per step
         const int nbt = (B + 31) / 32, grid1 = 2 * ((nbt + 3) / 4) * 4;
-        if (X != nullptr && F > 0 && F < 32 && stream_nt() && bias_column()) {
+        if (X != nullptr && F > 0 && F < 32) {
             const size_t lds = (size_t)32 * ((256 + 32) * 4 + 16) + (size_t)8 * 16 * 64 * 4;
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, true, false, 2, true, 1>), dim3(grid1), dim3(512), lds, stream,
+            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2, true, 1>), dim3(grid1), dim3(512), lds, stream,
                                (const float*)nullptr, 0, X, F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y),
                                ldy, B, T, (unsigned long long*)nullptr);
             return hipGetLastError();
         }
         if (X == nullptr) {
             const size_t lds = (size_t)32 * (256 * 4 + 16) + (size_t)8 * 16 * 64 * 4;
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0, true, false, 0, false, 1>), dim3(grid1), dim3(512), lds, stream, Xp, ldx,
+            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0, false, 0, false, 1>), dim3(grid1), dim3(512), lds, stream, Xp, ldx,
                                (const int8_t*)nullptr, 0, (const float*)nullptr, static_cast<const uint32_t*>(Wp),
                                static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr);
             return hipGetLastError();
@@ -1669,26 +1422,17 @@ hipError_t launch_lstm_rec_h2(int H, const float* Xp, int ldx, const int8_t* X, 
     if (X != nullptr) {
         if (F <= 0 || F > 32) return hipErrorInvalidValue;
         const size_t lds = (size_t)MT * ((256 + 32) * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4;
-        if (prescaled && stream_nt() && F < 32 && bias_column())
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, true, false, 2, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
+        if (F < 32)
+            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
                                F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
                                debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
-        else if (prescaled && stream_nt())
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, true, false, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
+        else
+            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
                                F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
                                debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
-        else if (prescaled) hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
-                           F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
-                           debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
-        else hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
-                           F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
-                           debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
     } else {
         const size_t lds = (size_t)MT * (256 * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4;
-        if (prescaled) hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0, true>), dim3(grid), dim3(512), lds, stream, Xp, ldx,
-                           (const int8_t*)nullptr, 0, (const float*)nullptr, static_cast<const uint32_t*>(Wp),
-                           static_cast<uint32_t*>(Y), ldy, B, T, debug_buffer());
-        else hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0, false>), dim3(grid), dim3(512), lds, stream, Xp, ldx,
+        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0>), dim3(grid), dim3(512), lds, stream, Xp, ldx,
                            (const int8_t*)nullptr, 0, (const float*)nullptr, static_cast<const uint32_t*>(Wp),
                            static_cast<uint32_t*>(Y), ldy, B, T, debug_buffer());
     }
@@ -1706,20 +1450,16 @@ hipError_t launch_gru_rec_h2(int H, const float* Xp, int ldx, const uint8_t* X, 
         const int KX = gru_fused_input_kx(H, F);
         if (KX == 16) {
             const size_t lds = (size_t)2 * MT * ((128 + 16) * 4 + 16);
-            if (stream_nt() && F < 16 && bias_column())
+            if (F < 16)
                 hipLaunchKernelGGL((gru_rec_h2_kernel<128, 16, false, 2, false, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
                                    F, x_bstride, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn, ldhn,
                                    static_cast<uint32_t*>(Y), ldy, B, T, (const uint32_t*)nullptr, 0, (const uint32_t*)nullptr,
                                    (float*)nullptr, gru_debug_buffer() ? gru_debug_buffer() + 64 : nullptr);
-            else if (stream_nt())
+            else
                 hipLaunchKernelGGL((gru_rec_h2_kernel<128, 16, false, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
                                    F, x_bstride, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn, ldhn,
                                    static_cast<uint32_t*>(Y), ldy, B, T, (const uint32_t*)nullptr, 0, (const uint32_t*)nullptr,
                                    (float*)nullptr, gru_debug_buffer() ? gru_debug_buffer() + 64 : nullptr);
-            else
-                hipLaunchKernelGGL((gru_rec_h2_kernel<128, 16>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
-                                   F, x_bstride, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn, ldhn,
-                                   static_cast<uint32_t*>(Y), ldy, B, T);
         } else if (KX == 128) {
             if ((x_bstride & 3) || (reinterpret_cast<uintptr_t>(X) & 3)) return hipErrorInvalidValue;
             const size_t lds = (size_t)2 * MT * ((128 + 128) * 4 + 16) + (size_t)8 * 15 * 64 * 4;   // + f32 h strip (160 KB in all)
@@ -1803,13 +1543,10 @@ hipError_t launch_gru_dec_h2_dense(int H, const void* Xh, int ldxh, const float*
     const int grid = 2 * ((nbt + 3) / 4) * 4;
     const size_t lds = (size_t)2 * MT * (128 * 4 + 16) + (size_t)2 * 2 * MT * 36 * 4 + (size_t)4 * 2 * 1024 + (size_t)4 * 5 * 2 * MT * 4 +
                        (size_t)8 * 16 * 64 * 4;   // h rows + x ring + dense1 fragments + partial-logit scratch + f32 h strip
-#define PA_GDD(AUX_)                                                                                                   \
-    hipLaunchKernelGGL((gru_rec_h2_kernel<128, 256, true, AUX_, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, \
-                       (const uint8_t*)nullptr, 0, (int64_t)0, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn, ldhn, \
-                       (uint32_t*)nullptr, 8, B, T, static_cast<const uint32_t*>(Xh), ldxh, static_cast<const uint32_t*>(Wd), P, \
-                       gru_debug_buffer())
-    if (stream_nt()) PA_GDD(2); else PA_GDD(0);
-#undef PA_GDD
+    hipLaunchKernelGGL((gru_rec_h2_kernel<128, 256, true, 2, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
+                       (const uint8_t*)nullptr, 0, (int64_t)0, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn, ldhn,
+                       (uint32_t*)nullptr, 8, B, T, static_cast<const uint32_t*>(Xh), ldxh, static_cast<const uint32_t*>(Wd), P,
+                       gru_debug_buffer());
     return hipGetLastError();
 }
 
@@ -1818,27 +1555,13 @@ hipError_t launch_gru_dec_h2(int H, const void* Xh, int ldxh, const float* bias,
                              hipStream_t stream) {
     if (B <= 0) return hipSuccess;
     if (H != 128 || (ldy & 7) || (ldxh & 7)) return hipErrorInvalidValue;
-    // default: the 8-wave / 128-row step loop with the x slab streamed through the LDS ring (half the weight
-    // stream per row of gru_dec_h2_kernel's 64-row form, which PA_GRU_DEC_RING=0 selects)
-    static const bool ring = [] { const char* e = getenv("PA_GRU_DEC_RING"); return !e || e[0] != '0'; }();
-    if (ring) {
-        const int nbt = (B + 2 * MT - 1) / (2 * MT);
-        const int grid = 2 * ((nbt + 3) / 4) * 4;
-        const size_t lds = (size_t)2 * MT * (128 * 4 + 16) + (size_t)2 * 2 * MT * 36 * 4 + (size_t)8 * 16 * 64 * 4;
-        if (stream_nt())
-            hipLaunchKernelGGL((gru_rec_h2_kernel<128, 256, true, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
-                               (const uint8_t*)nullptr, 0, (int64_t)0, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn,
-                               ldhn, static_cast<uint32_t*>(Y), ldy, B, T, static_cast<const uint32_t*>(Xh), ldxh);
-        else
-            hipLaunchKernelGGL((gru_rec_h2_kernel<128, 256, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
-                               (const uint8_t*)nullptr, 0, (int64_t)0, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn,
-                               ldhn, static_cast<uint32_t*>(Y), ldy, B, T, static_cast<const uint32_t*>(Xh), ldxh);
-        return hipGetLastError();
-    }
-    const size_t lds = (size_t)MT * ((128 + 256) * 4 + 16);
-    hipLaunchKernelGGL((gru_dec_h2_kernel<128, 256>), dim3(rec_grid(B)), dim3(256), lds, stream,
-                       static_cast<const uint32_t*>(Xh), ldxh, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn,
-                       ldhn, static_cast<uint32_t*>(Y), ldy, B, T);
+    // the 8-wave / 128-row step loop with the x slab streamed through the LDS ring
+    const int nbt = (B + 2 * MT - 1) / (2 * MT);
+    const int grid = 2 * ((nbt + 3) / 4) * 4;
+    const size_t lds = (size_t)2 * MT * (128 * 4 + 16) + (size_t)2 * 2 * MT * 36 * 4 + (size_t)8 * 16 * 64 * 4;
+    hipLaunchKernelGGL((gru_rec_h2_kernel<128, 256, true, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
+                       (const uint8_t*)nullptr, 0, (int64_t)0, bias, static_cast<const uint32_t*>(Wp), bhn, h0, ldh0, hn,
+                       ldhn, static_cast<uint32_t*>(Y), ldy, B, T, static_cast<const uint32_t*>(Xh), ldxh);
     return hipGetLastError();
 }
 
