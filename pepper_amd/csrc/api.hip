@@ -1,6 +1,6 @@
 // C ABI of pepper_amd (see include/pepper_amd.h): model handles, weight packing, workspace,
-// the two forward pipelines and the HIP-event profiler.  Host-side C++ only; kernels live in
-// gemm.hip / rnn.hip / head.hip.
+// the two forward pipelines and the HIP-event profiler.  Host-side C++ only; the kernels and their launchers
+// (kernels.h) live in gemm.hip / gemm_h2.hip / rnn.hip / rnn_h2.hip / mlp_h2.hip / head.hip.
 #include "../../include/pepper_amd.h"
 
 #include <hip/hip_runtime.h>
@@ -71,8 +71,10 @@ struct ProfSample {
     double flops;
 };
 
+constexpr uint32_t kHandleMagic = 0x50414d44;  // 'PAMD'
+
 struct ModelBase {
-    uint32_t magic = 0x50414d44;  // 'PAMD'
+    uint32_t magic = kHandleMagic;
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -123,6 +125,9 @@ struct ModelBase {
         owned.push_back(new DevBuf());
         return owned.back();
     }
+    void new_bufs(std::initializer_list<DevBuf**> slots) {
+        for (DevBuf** s : slots) *s = new_buf();
+    }
 
     // Host-buffer entry points (pa_*_host): device passes of max_chunk units with the H2D copy of pass i+1 and the D2H
     // copy of pass i-1 on their own streams beside the kernels of pass i (two staging slots each way).  With page-locked
@@ -163,6 +168,40 @@ struct ModelBase {
         (void)hipStreamDestroy(pipe.h2d);
         (void)hipStreamDestroy(pipe.d2h);
         pipe.ready = false;
+    }
+    // The one copy of the two-slot loop: n units in passes of `chunk`, pass i in slot i & 1.  The model supplies
+    //   copy_in(k, off, c):  size slot k's staging buffers, issue the H2D copies of units [off, off + c) on pipe.h2d
+    //   run(k, c):           the device pass over slot k on `stream`
+    //   copy_out(k, off, c): issue the D2H copies of the pass's results on pipe.d2h
+    // (the staging buffers only grow in the first pass of a slot, so sizing them behind the wait for in_free queues nothing)
+    template <class CopyIn, class Run, class CopyOut>
+    int host_passes(int64_t n, int64_t chunk, CopyIn&& copy_in, Run&& run, CopyOut&& copy_out) {
+        auto passes = [&]() -> int {
+            HIP_TRY(hipSetDevice(device));
+            if (int rc = pipe_init()) return rc;
+            int64_t i = 0;
+            for (int64_t off = 0; off < n; off += chunk, ++i) {
+                const int64_t c = std::min<int64_t>(chunk, n - off);
+                const int k = (int)(i & 1);
+                if (i >= 2) HIP_TRY(hipStreamWaitEvent(pipe.h2d, pipe.in_free[k], 0));   // pass i-2 has consumed this slot
+                if (int rc = copy_in(k, off, c)) return rc;
+                HIP_TRY(hipEventRecord(pipe.in_ready[k], pipe.h2d));
+                HIP_TRY(hipStreamWaitEvent(stream, pipe.in_ready[k], 0));
+                if (i >= 2) HIP_TRY(hipStreamWaitEvent(stream, pipe.out_free[k], 0));    // results of pass i-2 have left the slot
+                if (int rc = run(k, c)) return rc;
+                HIP_TRY(hipEventRecord(pipe.in_free[k], stream));
+                HIP_TRY(hipEventRecord(pipe.out_ready[k], stream));
+                HIP_TRY(hipStreamWaitEvent(pipe.d2h, pipe.out_ready[k], 0));
+                if (int rc = copy_out(k, off, c)) return rc;
+                HIP_TRY(hipEventRecord(pipe.out_free[k], pipe.d2h));
+            }
+            HIP_TRY(hipStreamSynchronize(pipe.d2h));
+            HIP_TRY(hipStreamSynchronize(stream));
+            return PA_OK;
+        };
+        const int rc = passes();
+        if (rc != PA_OK) quiesce();
+        return rc;
     }
 };
 
@@ -239,40 +278,33 @@ float state_dict_max_abs_weight(const StateDict& sd) {
     return m;
 }
 
-int upload(DevBuf* b, const std::vector<float>& host) {
-    if (int rc = b->ensure(host.size() * sizeof(float))) return rc;
-    HIP_TRY(hipMemcpy(b->p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+// host vector (floats, packed h2 words, pointers) -> a device buffer sized to hold it
+template <class T>
+int upload(DevBuf* b, const std::vector<T>& host) {
+    if (int rc = b->ensure(host.size() * sizeof(T))) return rc;
+    HIP_TRY(hipMemcpy(b->p, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
     return PA_OK;
+}
+
+// every value is a finite f16 magnitude (NaN fails)
+bool fits_f16(const float* v, int64_t count) {
+    for (int64_t i = 0; i < count; ++i)
+        if (!(std::fabs(v[i]) < 65504.0f)) return false;
+    return true;
 }
 
 // f32 [rows, K] (dense) -> h2 split format on the device (K % 8 == 0); values must fit f16 range
 int upload_h2(DevBuf* b, const float* host, int64_t rows, int K) {
-    for (int64_t i = 0; i < rows * K; ++i)
-        if (!(std::fabs(host[i]) < 65504.0f))
-            return fail(PA_ERR_INVALID, "weight magnitude >= 65504 (or NaN): not representable in the split-f16 GEMM path");
+    if (!fits_f16(host, rows * K))
+        return fail(PA_ERR_INVALID, "weight magnitude >= 65504 (or NaN): not representable in the split-f16 GEMM path");
     std::vector<uint32_t> h((size_t)rows * K);
     pa::split_h2_host(host, h.data(), rows, K, K, K);
-    if (int rc = b->ensure(h.size() * sizeof(uint32_t))) return rc;
-    HIP_TRY(hipMemcpy(b->p, h.data(), h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-    return PA_OK;
+    return upload(b, h);
 }
 
-// W_hh [G*H, H] of both directions -> fragment order [dir][G*H/32][H/8][64][4] (rnn.hip):
+// Fused first layer (rnn.hip lstm_rec_pp_kernel<H, 32>): per direction [W_hh | W_ih | 0] with K = H + KX columns (F of them
+// taken from W_ih) in fragment order [dir][G*H/32][K/8][64][4] (rnn.hip):
 // lane l of n-tile nt, k-block kb holds W[nt*32 + (l&31)][kb*8 + 4*(l>>5) + e], e = 0..3.
-void pack_rec_weights(const float* const w[2], int G, int H, std::vector<float>& out) {
-    const int NTt = G * H / 32, KB = H / 8;
-    out.resize((size_t)2 * NTt * KB * 64 * 4);
-    for (int d = 0; d < 2; ++d)
-        for (int nt = 0; nt < NTt; ++nt)
-            for (int kb = 0; kb < KB; ++kb)
-                for (int l = 0; l < 64; ++l)
-                    for (int e = 0; e < 4; ++e)
-                        out[((((size_t)d * NTt + nt) * KB + kb) * 64 + l) * 4 + e] =
-                            w[d][(size_t)(nt * 32 + (l & 31)) * H + kb * 8 + 4 * (l >> 5) + e];
-}
-
-// Fused first layer (rnn.hip lstm_rec_pp_kernel<H, 32>): per direction [W_hh | W_ih | 0] with
-// K = H + 32 columns, in the same fragment order as pack_rec_weights.
 void pack_fused_weights(const float* const whh[2], const float* const wih[2], int G, int H, int F, int KX,
                         std::vector<float>& out) {
     const int KT = H + KX, NTt = G * H / 32, KB = KT / 8;
@@ -288,6 +320,11 @@ void pack_fused_weights(const float* const whh[2], const float* const wih[2], in
                         else if (k - H < F) v = wih[d][(size_t)n * F + (k - H)];
                         out[((((size_t)d * NTt + nt) * KB + kb) * 64 + l) * 4 + e] = v;
                     }
+}
+
+// W_hh [G*H, H] of both directions alone, in the same order: [dir][G*H/32][H/8][64][4]
+void pack_rec_weights(const float* const w[2], int G, int H, std::vector<float>& out) {
+    pack_fused_weights(w, w, G, H, 0, 0, out);
 }
 
 // One bidirectional recurrent layer's device weights.
@@ -385,21 +422,14 @@ int build_rec_layer(ModelBase* m, const StateDict& sd, const std::string& prefix
         const float* const bias_x[2] = {bs.data(), bs.data() + (size_t)G * H};
         auto pack_upload = [&](DevBuf*& dst, const float* const wx[2], int KX, bool with_bias = false) -> int {
             for (int d = 0; d < 2; ++d) {
-                for (int64_t i = 0; i < (int64_t)G * H * H; ++i)
-                    if (!(std::fabs(whh_x[d][i]) < 65504.0f)) return fail(PA_ERR_INVALID, "recurrent weight not representable in f16 range");
-                if (wx[0])
-                    for (int64_t i = 0; i < (int64_t)G * H * K; ++i)
-                        if (!(std::fabs(wx[d][i]) < 65504.0f)) return fail(PA_ERR_INVALID, "input weight not representable in f16 range");
+                if (!fits_f16(whh_x[d], (int64_t)G * H * H)) return fail(PA_ERR_INVALID, "recurrent weight not representable in f16 range");
+                if (wx[0] && !fits_f16(wx[d], (int64_t)G * H * K)) return fail(PA_ERR_INVALID, "input weight not representable in f16 range");
             }
-            if (with_bias)
-                for (int64_t i = 0; i < (int64_t)2 * G * H; ++i)
-                    if (!(std::fabs(bs[(size_t)i]) < 65504.0f)) return fail(PA_ERR_INVALID, "bias not representable in f16 range");
+            if (with_bias && !fits_f16(bs.data(), (int64_t)2 * G * H)) return fail(PA_ERR_INVALID, "bias not representable in f16 range");
             std::vector<uint32_t> hp(pa::rec_weights_h2_words(G, H, KX));
             pa::pack_rec_weights_h2(whh_x, wx, G, H, K, KX, hp.data(), with_bias ? bias_x : nullptr);
             dst = m->new_buf();
-            if (int rc = dst->ensure(hp.size() * sizeof(uint32_t))) return rc;
-            HIP_TRY(hipMemcpy(dst->p, hp.data(), hp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-            return PA_OK;
+            return upload(dst, hp);
         };
         const float* const none[2] = {nullptr, nullptr};
         if (int rc = pack_upload(out.w_hh_h2, none, 0)) return rc;
@@ -411,8 +441,7 @@ int build_rec_layer(ModelBase* m, const StateDict& sd, const std::string& prefix
             std::vector<uint32_t> hp(pa::gru_small_weights_h2_words(H));
             pa::pack_gru_small_weights_h2(whh_x, H, hp.data());
             out.w_hh_small_h2 = m->new_buf();
-            if (int rc = out.w_hh_small_h2->ensure(hp.size() * sizeof(uint32_t))) return rc;
-            HIP_TRY(hipMemcpy(out.w_hh_small_h2->p, hp.data(), hp.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            if (int rc = upload(out.w_hh_small_h2, hp)) return rc;
         }
     }
     if ((G == 4 && H == 256 && K <= 32) || (G == 3 && H == 128 && K <= 16)) {
@@ -480,6 +509,61 @@ int init_base(ModelBase* m, int device, void* hip_stream) {
             return fail(PA_ERR_HIP, std::string(label) + ": " + hipGetErrorString(e_));        \
     } while (0)
 
+// The one handle check, for the typed entry points and the void* ones of the profiler alike: both handle structs derive
+// from ModelBase as their only (polymorphic) base, so a handle's address is its ModelBase address; the magic word
+// guards against foreign pointers.
+ModelBase* as_base(void* model) {
+    auto* b = reinterpret_cast<ModelBase*>(model);
+    if (!model || b->magic != kHandleMagic) return nullptr;
+    return b;
+}
+
+// What pa_variant_create and pa_polish_create share ahead of their weights: the pass size, the arithmetic switches, the device.
+template <class M>
+int create_common(M* m, const StateDict& sd, int window, int H, void* hip_stream) {
+    if (m->cfg.max_chunk <= 0) m->cfg.max_chunk = 16384;   // (polish: 128 chunks per workgroup and direction: 256 workgroups)
+    // the h2 GEMM addresses its A operand through a 32-bit buffer descriptor: [n*T, 2H] h2 rows must stay < 4 GiB
+    m->cfg.max_chunk = std::min<int32_t>(m->cfg.max_chunk, (int32_t)((int64_t)0xf0000000 / ((int64_t)window * 2 * H * 4)));
+    if (const char* e = getenv("PA_SPLIT_GEMM")) m->split_gemm = e[0] != '0';
+    if (const char* e = getenv("PA_SPLIT_REC")) m->split_rec = e[0] != '0';
+    if (!(state_dict_max_abs_weight(sd) < kSplitMaxWeight)) m->split_gemm = false;   // see kSplitMaxWeight
+    m->split_rec = m->split_rec && m->split_gemm;   // the h2 layer output needs the h2 consumers
+    return init_base(m, m->cfg.device, hip_stream);
+}
+
+void destroy_model(ModelBase* m) {
+    if (!m) return;
+    (void)hipSetDevice(m->device);
+    if (m->stream) (void)hipStreamSynchronize(m->stream);
+    delete m;
+}
+
+template <class M>
+int set_batch_invariant(M* m, int32_t on, const char* entry) {
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
+    if (on != 0 && on != 1) return fail(PA_ERR_INVALID, std::string(entry) + ": on must be 0 or 1");
+    m->batch_invariant = on != 0;
+    return PA_OK;
+}
+
+template <class M>
+int get_batch_invariant(M* m, int32_t* on) {
+    if (!as_base(m) || !on) return fail(PA_ERR_INVALID, "bad model handle");
+    *on = m->batch_invariant ? 1 : 0;
+    return PA_OK;
+}
+
+// Where a recurrent layer's gate pre-activations come from: contracted inside its own step loop, or a projection GEMM
+// over all T steps into the Xp workspace (the three-MFMA f16 product of gemm_h2.hip, or gemm.hip's f32 one)
+enum Proj { IN_LOOP, XP_GEMM_H2, XP_GEMM_F32 };
+// ... and, with the step loop that consumes them (Rec: the model's own list), the form one recurrent layer runs in
+template <class Rec>
+struct LayerForm {
+    Proj proj;
+    Rec rec;
+    bool y_h2;   // the layer's output is in the h2 split format
+};
+
 }  // namespace
 
 // ================================================================================================
@@ -496,6 +580,9 @@ struct pa_variant_model : ModelBase {
     Linear lin[5], out;
     DevBuf *mlp_w = nullptr, *mlp_b = nullptr;   // linear_2..5 as h2 fragments + their biases (mlp_h2.hip)
     DevBuf *mlp_w32 = nullptr;   // device array of the four f32 weight pointers + the out-of-range row counter behind them
+    int* ovf_counter() const {
+        return mlp_w32 ? reinterpret_cast<int*>(static_cast<char*>(mlp_w32->p) + 4 * sizeof(float*)) : nullptr;
+    }
     DevBuf *xp, *ya, *yb, *l1, *l2, *stage_in[2], *stage_p[2], *stage_l[2];
     // Calls of at most 1024 windows (the reference's DataLoader batch is 512) run their step loops with the hidden units of a
     // 32-row tile split over eight (above 512 windows: four) workgroups that exchange h_t through memory every step (rnn_h2.hip lstm_rec_h2_split_kernel;
@@ -537,20 +624,13 @@ int pa_variant_create(const pa_variant_config* cfg, const char* const* names, co
         return fail(PA_ERR_INVALID, "bad pa_variant_config");
     auto* m = new pa_variant_model();
     m->cfg = *cfg;
-    if (m->cfg.max_chunk <= 0) m->cfg.max_chunk = 16384;
-    // the h2 GEMM addresses its A operand through a 32-bit buffer descriptor: [n*T, 2H] h2 rows must stay < 4 GiB
-    m->cfg.max_chunk = std::min<int32_t>(m->cfg.max_chunk, (int32_t)((int64_t)0xf0000000 / ((int64_t)cfg->window * 2 * 256 * 4)));
-    if (const char* e = getenv("PA_SPLIT_GEMM")) m->split_gemm = e[0] != '0';
-    if (const char* e = getenv("PA_SPLIT_REC")) m->split_rec = e[0] != '0';
+    const int H = m->H;
     StateDict sd(names, data, numel, n_tensors);
-    if (!(state_dict_max_abs_weight(sd) < kSplitMaxWeight)) m->split_gemm = false;   // see kSplitMaxWeight
-    m->split_rec = m->split_rec && m->split_gemm;   // the h2 layer output needs the h2 consumers
+    int rc = create_common(m, sd, cfg->window, H, hip_stream);
     if (const char* e = getenv("PA_SMALL_BATCH")) m->small_batch = atoll(e);
     if (const char* e = getenv("PA_SMALL_ROWS")) m->small_rows = atoll(e);
     if (const char* e = getenv("PA_UNIT_SPLIT")) m->unit_split = e[0] != '0';
     if (const char* e = getenv("PA_UNIT_SPLIT_SABOTAGE")) m->split_sabotage = atoi(e);
-    int rc = init_base(m, cfg->device, hip_stream);
-    const int H = m->H;
     for (int mod = 0; mod < 2 && rc == PA_OK; ++mod)
         for (int layer = 0; layer < cfg->gru_layers && rc == PA_OK; ++layer) {
             const int K = (mod == 0 && layer == 0) ? cfg->image_features : 2 * H;
@@ -571,7 +651,7 @@ int pa_variant_create(const pa_variant_config* cfg, const char* const* names, co
         for (int i = 0; i < 4 && ok; ++i) {
             w4[i] = sd.get(std::string(lin_names[i + 1]) + ".weight", (int64_t)m->L1 * m->L1, err);
             const float* b = sd.get(std::string(lin_names[i + 1]) + ".bias", m->L1, err);
-            for (int64_t k = 0; k < (int64_t)m->L1 * m->L1; ++k) ok = ok && std::fabs(w4[i][k]) < 65504.0f;
+            ok = fits_f16(w4[i], (int64_t)m->L1 * m->L1);
             std::memcpy(&b4[(size_t)i * m->L1], b, m->L1 * sizeof(float));
         }
         if (ok) {   // (weights outside the f16 range keep the f32 GEMM chain)
@@ -589,16 +669,13 @@ int pa_variant_create(const pa_variant_config* cfg, const char* const* names, co
             b4.swap(table);
             m->mlp_w = m->new_buf();
             m->mlp_b = m->new_buf();
-            rc = m->mlp_w->ensure(packed.size() * sizeof(uint32_t));
-            if (rc == PA_OK && hipMemcpy(m->mlp_w->p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-                rc = fail(PA_ERR_HIP, "upload of the packed MLP weights failed");
+            rc = upload(m->mlp_w, packed);
             if (rc == PA_OK) rc = upload(m->mlp_b, b4);
             if (rc == PA_OK) {      // the f32 matrices the kernel re-runs a tile on when an activation leaves the f16 range
-                const float* ptrs[5] = {m->lin[1].w->f(), m->lin[2].w->f(), m->lin[3].w->f(), m->lin[4].w->f(), nullptr};
+                // (the fifth word is the out-of-range row counter, zero to begin with: pa_variant_model::ovf_counter)
+                const std::vector<const float*> ptrs = {m->lin[1].w->f(), m->lin[2].w->f(), m->lin[3].w->f(), m->lin[4].w->f(), nullptr};
                 m->mlp_w32 = m->new_buf();
-                rc = m->mlp_w32->ensure(sizeof(ptrs));
-                if (rc == PA_OK && hipMemcpy(m->mlp_w32->p, ptrs, sizeof(ptrs), hipMemcpyHostToDevice) != hipSuccess)
-                    rc = fail(PA_ERR_HIP, "upload of the MLP weight table failed");
+                rc = upload(m->mlp_w32, ptrs);
             }
         }
     }
@@ -606,22 +683,13 @@ int pa_variant_create(const pa_variant_config* cfg, const char* const* names, co
         delete m;
         return rc;
     }
-    m->xp = m->new_buf(); m->ya = m->new_buf(); m->yb = m->new_buf();
-    m->l1 = m->new_buf(); m->l2 = m->new_buf();
-    m->us_exch = m->new_buf(); m->us_cnt = m->new_buf(); m->us_failed = m->new_buf();
-    for (int k = 0; k < 2; ++k) {
-        m->stage_in[k] = m->new_buf(); m->stage_p[k] = m->new_buf(); m->stage_l[k] = m->new_buf();
-    }
+    m->new_bufs({&m->xp, &m->ya, &m->yb, &m->l1, &m->l2, &m->us_exch, &m->us_cnt, &m->us_failed, &m->stage_in[0], &m->stage_p[0],
+                 &m->stage_l[0], &m->stage_in[1], &m->stage_p[1], &m->stage_l[1]});
     *out = m;
     return PA_OK;
 }
 
-void pa_variant_destroy(pa_variant_model* m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    delete m;
-}
+void pa_variant_destroy(pa_variant_model* m) { destroy_model(m); }
 
 constexpr int US_HOLDOFF = 256;
 // linear_1's K slices in batch-invariant mode: what a full 16 384-window pass picks by itself (128 output tiles x 2 slices
@@ -634,35 +702,68 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     const int T = m->cfg.window, F = m->cfg.image_features, H = m->H, C = m->cfg.num_classes_type;
     const int64_t np = round_up(n, MT);
     const int NX = 2 * 4 * H;  // both directions' gate pre-activations
-    // Xp (gate pre-activations, 4.4 GB at 16384 windows) is only materialised when some layer's projection is
-    // NOT contracted inside its step loop; otherwise the workspace just holds linear_1's split-K partials
-    // Small calls (the reference's DataLoader batch is 512 windows, predict_distributed_gpu.py:58-67): a step of the fused
-    // decoder loop costs 41 us whatever the number of 64-row tiles -- 8 waves on one CU issue the K = 768 contraction of their
-    // tile, 3 MB of weight fragments per step -- so a call of 128 ... 2048 windows took 2.15 ms.  Below `small_batch` windows the
-    // decoder's input projection runs as one GEMM over all T steps on the whole chip instead (0.13 ms at 512 windows) and the
-    // step loop contracts K = 256 only (14.7 us per step): 512 windows 2.16 -> 1.42 ms, 1024: 2.17 -> 1.59, 2048: 2.18 -> 1.83;
-    // at 4096 the fused loop wins again (profiles/r03_small_batch_kernels.json).  PA_SMALL_BATCH=0: always fused.
     const bool bi = m->batch_invariant;
-    const bool fuse_dec = bi || n > m->small_batch;
-    // ... and, up to `small_rows` windows, both step loops run with 32-row workgroups (rnn_h2.hip MTILES = 1): a step is one
-    // CU's affair, half the rows are half the MFMAs and half the gate phase per step (PA_SMALL_ROWS, 0 = never)
-    // (batch-invariant mode too: the 32-row workgroups issue every row's MFMA chain and gate arithmetic exactly as the 64-row
-    // ones do -- tests/test_gpu_batch_invariant.py holds them to the bits of a full pass -- and there the fused decoder takes
-    // them as well)
-    const bool small_rows = n <= m->small_rows;
-    // up to 1024 windows: every layer as projection GEMM + the unit-split step loop (see pa_variant_model::unit_split)
-    bool unit_split = allow_split && !bi && m->unit_split && n <= 1024 && H == 256 && m->split_rec && !fuse_dec && m->mlp_w32 != nullptr &&
-                      m->mlp_w != nullptr && C <= 8;
-    for (const RecLayer& r : m->rec) unit_split = unit_split && r.w_hh_h2 != nullptr && r.prescaled;
+
+    // ---- decide: the call's schedule, fixed here before the first launch ----
+    struct Schedule {
+        // Small calls (the reference's DataLoader batch is 512 windows, predict_distributed_gpu.py:58-67): a step of the fused
+        // decoder loop costs 41 us whatever the number of 64-row tiles -- 8 waves on one CU issue the K = 768 contraction of their
+        // tile, 3 MB of weight fragments per step -- so a call of 128 ... 2048 windows took 2.15 ms.  Below `small_batch` windows the
+        // decoder's input projection runs as one GEMM over all T steps on the whole chip instead (0.13 ms at 512 windows) and the
+        // step loop contracts K = 256 only (14.7 us per step): 512 windows 2.16 -> 1.42 ms, 1024: 2.17 -> 1.59, 2048: 2.18 -> 1.83;
+        // at 4096 the fused loop wins again (profiles/r03_small_batch_kernels.json).  PA_SMALL_BATCH=0: always fused.
+        bool fuse_dec;
+        // ... and, up to `small_rows` windows, both step loops run with 32-row workgroups (rnn_h2.hip MTILES = 1): a step is one
+        // CU's affair, half the rows are half the MFMAs and half the gate phase per step (PA_SMALL_ROWS, 0 = never)
+        // (batch-invariant mode too: the 32-row workgroups issue every row's MFMA chain and gate arithmetic exactly as the 64-row
+        // ones do -- tests/test_gpu_batch_invariant.py holds them to the bits of a full pass -- and there the fused decoder takes
+        // them as well)
+        bool small_rows;
+        // up to 1024 windows: every layer as projection GEMM + the unit-split step loop (see pa_variant_model::unit_split)
+        bool unit_split;
+        // Xp (gate pre-activations, 4.4 GB at 16384 windows) is only materialised when some layer's projection is
+        // NOT contracted inside its step loop; otherwise the workspace just holds linear_1's split-K partials
+        bool need_xp = false;
+        // linear_1 has few output tiles (n/256 x 2) and a long K: slice K so that every CU gets a tile; the
+        // partial sums reuse the Xp workspace (dead after the last recurrent layer), so this is set once that is sized
+        int l1_splits = 1;
+    } s;
+    s.fuse_dec = bi || n > m->small_batch;
+    s.small_rows = n <= m->small_rows;
+    s.unit_split = allow_split && !bi && m->unit_split && n <= 1024 && H == 256 && m->split_rec && !s.fuse_dec && m->mlp_w32 != nullptr &&
+                   m->mlp_w != nullptr && C <= 8;
+    for (const RecLayer& r : m->rec) s.unit_split = s.unit_split && r.w_hh_h2 != nullptr && r.prescaled;
     // the members of a group wait for each other: every workgroup of the launch must be on the device at once (a CPX
     // partition of 32 CUs, or a device that reports fewer CUs, never holds 256 of them -- no split there, no spin, no re-run)
-    if (unit_split && pa::lstm_split_grid((int)n) > pa::lstm_split_resident_workgroups(n <= 512 ? 1 : 2)) unit_split = false;
-    if (unit_split && m->split_holdoff > 0) {
+    if (s.unit_split && pa::lstm_split_grid((int)n) > pa::lstm_split_resident_workgroups(n <= 512 ? 1 : 2)) s.unit_split = false;
+    if (s.unit_split && m->split_holdoff > 0) {
         --m->split_holdoff;
-        unit_split = false;
+        s.unit_split = false;
     }
-    int* const ovf_counter = m->mlp_w32 ? reinterpret_cast<int*>(static_cast<char*>(m->mlp_w32->p) + 4 * sizeof(float*)) : nullptr;
-    if (unit_split) {
+
+    // the step loop of each recurrent layer, and with it where its gate pre-activations come from
+    enum Rec { FUSED_IN_H2, FUSED_IN_F32, FUSED_DEC_H2, SPLIT_H2, PLAIN_H2, PLAIN_F32 };
+    auto form_of = [&](size_t li, bool in_h2) -> LayerForm<Rec> {
+        const RecLayer& r = m->rec[li];
+        const bool rec_h2 = m->split_rec && r.w_hh_h2 != nullptr;
+        // int8 summaries straight into the recurrent kernel: no Xp round trip
+        if (li == 0 && a_kind == pa::A_I8 && r.w_cat != nullptr && !s.unit_split)
+            return {IN_LOOP, rec_h2 && r.w_cat_h2 != nullptr ? FUSED_IN_H2 : FUSED_IN_F32, rec_h2};
+        // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
+        if (li > 0 && rec_h2 && in_h2 && r.w_cat_dec_h2 != nullptr && s.fuse_dec) return {IN_LOOP, FUSED_DEC_H2, rec_h2};
+        // the previous layer's y is only read by this projection: if it is still f32, split it
+        // in place; then the three-MFMA f16 product (gemm_h2.hip)
+        const Proj proj = li > 0 && m->split_gemm && r.w_ih_h2 != nullptr ? XP_GEMM_H2 : XP_GEMM_F32;
+        return {proj, !rec_h2 ? PLAIN_F32 : s.unit_split ? SPLIT_H2 : PLAIN_H2, rec_h2};
+    };
+    std::vector<LayerForm<Rec>> forms;
+    for (size_t li = 0; li < m->rec.size(); ++li) {
+        forms.push_back(form_of(li, li > 0 && forms.back().y_h2));
+        s.need_xp = s.need_xp || forms.back().proj != IN_LOOP;
+    }
+
+    int* const ovf_counter = m->ovf_counter();
+    if (s.unit_split) {
         if (int rc = m->us_exch->ensure(pa::lstm_split_exchange_bytes(1024))) return rc;
         if (int rc = m->us_cnt->ensure(pa::lstm_split_counter_bytes(1024))) return rc;
         if (int rc = m->us_failed->ensure(sizeof(int))) return rc;
@@ -671,11 +772,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         // (the out-of-range counter as it is before this call: a pass that gave up feeds garbage to the MLP kernel)
         HIP_TRY(hipMemcpyAsync(&m->us_host[1], ovf_counter, sizeof(int), hipMemcpyDeviceToHost, m->stream));
     }
-    const bool fuse_in = !unit_split;
-    bool need_xp = !(a_kind == pa::A_I8 && fuse_in && !m->rec.empty() && m->rec[0].w_cat != nullptr);
-    for (size_t li = 1; li < m->rec.size(); ++li)
-        need_xp = need_xp || !(m->split_rec && fuse_dec && m->rec[li].w_cat_dec_h2 != nullptr);
-    const size_t xp_bytes = std::max(need_xp ? (size_t)np * T * NX * sizeof(float) : (size_t)0,
+    const size_t xp_bytes = std::max(s.need_xp ? (size_t)np * T * NX * sizeof(float) : (size_t)0,
                                      (size_t)8 * n * m->L1 * sizeof(float));
     if (int rc = m->xp->ensure(xp_bytes)) return rc;
     if (int rc = m->ya->ensure((size_t)np * T * 2 * H * sizeof(float))) return rc;
@@ -683,7 +780,15 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         if (int rc = m->yb->ensure((size_t)np * T * 2 * H * sizeof(float))) return rc;
     if (int rc = m->l1->ensure((size_t)n * m->L1 * sizeof(float))) return rc;
     if (int rc = m->l2->ensure((size_t)n * m->L1 * sizeof(float))) return rc;
+    const int tiles1 = (int)((n + 255) / 256) * ((m->L1 + 255) / 256);
+    // (up to 32 slices: a call of 512 windows has 4 output tiles, 0.137 ms with 8 slices, 0.078 with 32; big calls have tiles
+    // enough and stay at 2 slices)
+    while (!bi && s.l1_splits < 32 && tiles1 * s.l1_splits * 2 <= 256 &&
+           (size_t)(s.l1_splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
+        s.l1_splits *= 2;
+    if (bi) s.l1_splits = kCanonicalL1Splits;   // (the workspace holds 8 x n x L1 floats: room for them at any n)
 
+    // ---- launch ----
     const void* cur = images;
     int cur_kind = a_kind, cur_ld = F;
     bool cur_h2 = false;         // cur is a layer output already in the h2 split format
@@ -692,74 +797,67 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
     const int M = (int)(n * T);
     for (size_t li = 0; li < m->rec.size(); ++li) {
         const RecLayer& r = m->rec[li];
+        const LayerForm<Rec>& f = forms[li];
         float* y = ybuf[which];
-        const bool rec_h2 = m->split_rec && r.w_hh_h2 != nullptr;
         // bias / f32 projection weights matching what the recurrent kernel of this layer expects
-        const float* bias_l = (rec_h2 && r.prescaled) ? r.b_in_s->f() : r.b_in->f();
-        const float* wih_l = (rec_h2 && r.prescaled) ? r.w_ih_s->f() : r.w_ih->f();
-        if (li == 0 && cur_kind == pa::A_I8 && r.w_cat != nullptr && fuse_in) {
-            // int8 summaries straight into the recurrent kernel: no Xp round trip
-            if (rec_h2 && r.w_cat_h2 != nullptr)
-                LAUNCH_TRY(m, "lstm_rec_h2_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
-                           pa::launch_lstm_rec_h2(H, nullptr, 0, static_cast<const int8_t*>(cur), r.K, bias_l,
-                                                  r.w_cat_h2->p, y, 2 * H, (int)n, T, m->stream, small_rows));
-            else
-                LAUNCH_TRY(m, "lstm_rec_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
-                           pa::launch_lstm_rec_fused(H, static_cast<const int8_t*>(cur), r.K, r.b_in->f(),
-                                                     r.w_cat->f(), y, 2 * H, (int)n, T, m->stream));
-        } else if (li > 0 && rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && fuse_dec) {
-            // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
+        const float* bias_l = (f.y_h2 && r.prescaled) ? r.b_in_s->f() : r.b_in->f();
+        const float* wih_l = (f.y_h2 && r.prescaled) ? r.w_ih_s->f() : r.w_ih->f();
+        if (f.proj == XP_GEMM_H2) {
+            const size_t a_bytes = (size_t)M * cur_ld * sizeof(float);
+            if (!cur_h2)
+                LAUNCH_TRY(m, "cvt_h2", 0.0,
+                           pa::launch_f32_to_h2(static_cast<const float*>(cur), const_cast<void*>(cur), M, r.K,
+                                                cur_ld, m->stream));
+            LAUNCH_TRY(m, "gemm_h2_inproj", 2.0 * M * NX * r.K,
+                       pa::launch_gemm_h2(cur, cur_ld, a_bytes, r.w_ih_h2->p, r.K, (size_t)NX * r.K * 4, bias_l,
+                                          m->xp->f(), NX, (int)(np * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
+        } else if (f.proj == XP_GEMM_F32) {
+            LAUNCH_TRY(m, li == 0 ? "gemm_inproj_in" : "gemm_inproj", 2.0 * M * NX * r.K,
+                       pa::launch_gemm_nt(cur_kind, cur, cur_ld, wih_l, r.Kp, bias_l, m->xp->f(),
+                                          NX, (int)(np * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
+        }
+        switch (f.rec) {
+        case FUSED_IN_H2:
+            LAUNCH_TRY(m, "lstm_rec_h2_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
+                       pa::launch_lstm_rec_h2(H, nullptr, 0, static_cast<const int8_t*>(cur), r.K, bias_l,
+                                              r.w_cat_h2->p, y, 2 * H, (int)n, T, m->stream, s.small_rows));
+            break;
+        case FUSED_IN_F32:
+            LAUNCH_TRY(m, "lstm_rec_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
+                       pa::launch_lstm_rec_fused(H, static_cast<const int8_t*>(cur), r.K, r.b_in->f(),
+                                                 r.w_cat->f(), y, 2 * H, (int)n, T, m->stream));
+            break;
+        case FUSED_DEC_H2:
             LAUNCH_TRY(m, "lstm_dec_h2_fused", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
                        pa::launch_lstm_dec_h2(H, cur, cur_ld, bias_l, r.w_cat_dec_h2->p, y, 2 * H, (int)n, T, m->stream,
-                                              bi && small_rows));
-        } else {
-            if (li > 0 && m->split_gemm && r.w_ih_h2 != nullptr) {
-                // the previous layer's y is only read by this projection: if it is still f32, split it
-                // in place; then the three-MFMA f16 product (gemm_h2.hip)
-                const size_t a_bytes = (size_t)M * cur_ld * sizeof(float);
-                if (!cur_h2)
-                    LAUNCH_TRY(m, "cvt_h2", 0.0,
-                               pa::launch_f32_to_h2(static_cast<const float*>(cur), const_cast<void*>(cur), M, r.K,
-                                                    cur_ld, m->stream));
-                LAUNCH_TRY(m, "gemm_h2_inproj", 2.0 * M * NX * r.K,
-                           pa::launch_gemm_h2(cur, cur_ld, a_bytes, r.w_ih_h2->p, r.K, (size_t)NX * r.K * 4, bias_l,
-                                              m->xp->f(), NX, (int)(np * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
-            } else {
-                LAUNCH_TRY(m, li == 0 ? "gemm_inproj_in" : "gemm_inproj", 2.0 * M * NX * r.K,
-                           pa::launch_gemm_nt(cur_kind, cur, cur_ld, wih_l, r.Kp, bias_l, m->xp->f(),
-                                              NX, (int)(np * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
-            }
-            if (rec_h2 && unit_split) {
-                const int sabotage = m->split_sabotage > 0 ? 1 : 0;
-                m->split_sabotage -= sabotage;
-                LAUNCH_TRY(m, "lstm_rec_h2_split", 2.0 * n * T * (4.0 * H) * H * 2,
-                           pa::launch_lstm_rec_h2_split(H, m->xp->f(), NX, r.w_hh_h2->p, y, 2 * H, (int)n, T, m->us_exch->p,
-                                                        m->us_cnt->p, static_cast<int*>(m->us_failed->p), m->stream, sabotage));
-            } else if (rec_h2)
-                LAUNCH_TRY(m, "lstm_rec_h2", 2.0 * n * T * (4.0 * H) * H * 2,
-                           pa::launch_lstm_rec_h2(H, m->xp->f(), NX, nullptr, 0, nullptr, r.w_hh_h2->p, y, 2 * H, (int)n,
-                                                  T, m->stream, small_rows));
-            else
-                LAUNCH_TRY(m, "lstm_rec", 2.0 * n * T * (4.0 * H) * H * 2,
-                           pa::launch_lstm_rec(H, m->xp->f(), NX, r.w_hh->f(), y, 2 * H, (int)n, T, m->stream));
+                                              bi && s.small_rows));
+            break;
+        case SPLIT_H2: {
+            const int sabotage = m->split_sabotage > 0 ? 1 : 0;
+            m->split_sabotage -= sabotage;
+            LAUNCH_TRY(m, "lstm_rec_h2_split", 2.0 * n * T * (4.0 * H) * H * 2,
+                       pa::launch_lstm_rec_h2_split(H, m->xp->f(), NX, r.w_hh_h2->p, y, 2 * H, (int)n, T, m->us_exch->p,
+                                                    m->us_cnt->p, static_cast<int*>(m->us_failed->p), m->stream, sabotage));
+            break;
+        }
+        case PLAIN_H2:
+            LAUNCH_TRY(m, "lstm_rec_h2", 2.0 * n * T * (4.0 * H) * H * 2,
+                       pa::launch_lstm_rec_h2(H, m->xp->f(), NX, nullptr, 0, nullptr, r.w_hh_h2->p, y, 2 * H, (int)n,
+                                              T, m->stream, s.small_rows));
+            break;
+        case PLAIN_F32:
+            LAUNCH_TRY(m, "lstm_rec", 2.0 * n * T * (4.0 * H) * H * 2,
+                       pa::launch_lstm_rec(H, m->xp->f(), NX, r.w_hh->f(), y, 2 * H, (int)n, T, m->stream));
+            break;
         }
         cur = y;
         cur_kind = pa::A_F32;
         cur_ld = 2 * H;
-        cur_h2 = rec_h2;
+        cur_h2 = f.y_h2;
         which ^= 1;
     }
     // flatten(start_dim=1, end_dim=2): [n, T, 2H] rows are already contiguous -> [n, T*2H]
     const int K1 = T * 2 * H;
-    // linear_1 has few output tiles (n/256 x 2) and a long K: slice K so that every CU gets a tile; the
-    // partial sums reuse the Xp workspace (dead after the last recurrent layer)
-    const int tiles1 = (int)((n + 255) / 256) * ((m->L1 + 255) / 256);
-    int splits = 1;
-    // (up to 32 slices: a call of 512 windows has 4 output tiles, 0.137 ms with 8 slices, 0.078 with 32; big calls have tiles
-    // enough and stay at 2 slices)
-    while (!bi && splits < 32 && tiles1 * splits * 2 <= 256 && (size_t)(splits * 2) * n * m->L1 * sizeof(float) <= m->xp->bytes)
-        splits *= 2;
-    if (bi) splits = kCanonicalL1Splits;   // (the workspace holds 8 x n x L1 floats: room for them at any n)
     if (m->split_gemm && m->lin[0].w_h2 != nullptr && cur_kind == pa::A_F32) {
         if (!cur_h2)
             LAUNCH_TRY(m, "cvt_h2", 0.0,
@@ -767,7 +865,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         LAUNCH_TRY(m, "gemm_h2_linear_1", 2.0 * n * m->L1 * K1,
                    pa::launch_gemm_h2(cur, K1, (size_t)n * K1 * 4, m->lin[0].w_h2->p, K1, (size_t)m->L1 * K1 * 4,
                                       m->lin[0].b->f(), m->l1->f(), m->L1, (int)n, m->L1, K1, 1, 0, 0, 0, 0, m->stream,
-                                      splits > 1 ? m->xp->f() : nullptr, splits));
+                                      s.l1_splits > 1 ? m->xp->f() : nullptr, s.l1_splits));
     } else {
         LAUNCH_TRY(m, "gemm_linear_1", 2.0 * n * m->L1 * K1,
                    pa::launch_gemm_nt(pa::A_F32, cur, K1, m->lin[0].w->f(), K1, m->lin[0].b->f(), m->l1->f(),
@@ -777,8 +875,8 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         LAUNCH_TRY(m, "mlp_tail_h2", 2.0 * n * m->L1 * (4.0 * m->L1 + C),
                    pa::launch_mlp_tail_h2(m->l1->f(), m->L1, m->mlp_w->p, m->mlp_b->f(), 4, m->out.w->f(), m->out.b->f(), C,
                                           probs, logits, (int)n, m->stream, static_cast<const float* const*>(m->mlp_w32->p),
-                                          reinterpret_cast<int*>(static_cast<char*>(m->mlp_w32->p) + 4 * sizeof(float*)), bi));
-        if (unit_split) {
+                                          ovf_counter, bi));
+        if (s.unit_split) {
             // did every group of the split step loops meet?  (one synchronise per small call: 10-20 us beside its 0.65 ms)
             HIP_TRY(hipMemcpyAsync(&m->us_host[0], m->us_failed->p, sizeof(int), hipMemcpyDeviceToHost, m->stream));
             HIP_TRY(hipStreamSynchronize(m->stream));
@@ -807,7 +905,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
 
 static int variant_forward(pa_variant_model* m, int a_kind, const void* images, size_t elem, int64_t n,
                            float* probs, float* logits) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n < 0 || (n > 0 && (!images || !probs))) return fail(PA_ERR_INVALID, "null buffer");
     HIP_TRY(hipSetDevice(m->device));
     const int64_t per = (int64_t)m->cfg.window * m->cfg.image_features;
@@ -823,31 +921,24 @@ static int variant_forward(pa_variant_model* m, int a_kind, const void* images, 
 }
 
 int pa_variant_split_fallbacks(pa_variant_model* m, int64_t* calls) {
-    if (!m || m->magic != 0x50414d44 || !calls) return fail(PA_ERR_INVALID, "bad argument");
+    if (!as_base(m) || !calls) return fail(PA_ERR_INVALID, "bad argument");
     *calls = m->split_fallbacks;
     return PA_OK;
 }
 
 int pa_variant_set_batch_invariant(pa_variant_model* m, int32_t on) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
-    if (on != 0 && on != 1) return fail(PA_ERR_INVALID, "pa_variant_set_batch_invariant: on must be 0 or 1");
-    m->batch_invariant = on != 0;
-    return PA_OK;
+    return set_batch_invariant(m, on, "pa_variant_set_batch_invariant");
 }
 
-int pa_variant_get_batch_invariant(pa_variant_model* m, int32_t* on) {
-    if (!m || m->magic != 0x50414d44 || !on) return fail(PA_ERR_INVALID, "bad model handle");
-    *on = m->batch_invariant ? 1 : 0;
-    return PA_OK;
-}
+int pa_variant_get_batch_invariant(pa_variant_model* m, int32_t* on) { return get_batch_invariant(m, on); }
 
 int pa_variant_overflow_rows(pa_variant_model* m, int64_t* rows) {
-    if (!m || m->magic != 0x50414d44 || !rows) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m) || !rows) return fail(PA_ERR_INVALID, "bad model handle");
     HIP_TRY(hipSetDevice(m->device));
     int v = 0;
     if (m->mlp_w32 != nullptr) {
         HIP_TRY(hipStreamSynchronize(m->stream));
-        HIP_TRY(hipMemcpy(&v, static_cast<char*>(m->mlp_w32->p) + 4 * sizeof(float*), sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&v, m->ovf_counter(), sizeof(int), hipMemcpyDeviceToHost));
     }
     *rows = v;
     return PA_OK;
@@ -863,50 +954,33 @@ int pa_variant_forward_device_f32(pa_variant_model* m, const float* images, int6
     return variant_forward(m, pa::A_F32_SCALAR, images, 4, n, probs, logits);
 }
 
-static int variant_forward_host_run(pa_variant_model* m, const int8_t* images, int64_t n, float* probs, float* logits) {
-    HIP_TRY(hipSetDevice(m->device));
-    if (int rc = m->pipe_init()) return rc;
-    const size_t per = (size_t)m->cfg.window * m->cfg.image_features;
-    const int C = m->cfg.num_classes_type;
-    const int64_t chunk = m->cfg.max_chunk;
-    auto& pp = m->pipe;
-    int64_t i = 0;
-    for (int64_t off = 0; off < n; off += chunk, ++i) {
-        const int64_t c = std::min<int64_t>(chunk, n - off);
-        const int k = (int)(i & 1);
-        if (int rc = m->stage_in[k]->ensure((size_t)std::min<int64_t>(chunk, n) * per)) return rc;
-        if (int rc = m->stage_p[k]->ensure((size_t)std::min<int64_t>(chunk, n) * C * sizeof(float))) return rc;
-        if (logits)
-            if (int rc = m->stage_l[k]->ensure((size_t)std::min<int64_t>(chunk, n) * C * sizeof(float))) return rc;
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(pp.h2d, pp.in_free[k], 0));      // pass i-2 has consumed this slot
-        HIP_TRY(hipMemcpyAsync(m->stage_in[k]->p, images + (size_t)off * per, (size_t)c * per, hipMemcpyHostToDevice, pp.h2d));
-        HIP_TRY(hipEventRecord(pp.in_ready[k], pp.h2d));
-        HIP_TRY(hipStreamWaitEvent(m->stream, pp.in_ready[k], 0));
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->stream, pp.out_free[k], 0));  // results of pass i-2 have left the slot
-        if (int rc = variant_forward_chunk(m, pa::A_I8, m->stage_in[k]->p, c, m->stage_p[k]->f(),
-                                           logits ? m->stage_l[k]->f() : nullptr))
-            return rc;
-        HIP_TRY(hipEventRecord(pp.in_free[k], m->stream));
-        HIP_TRY(hipEventRecord(pp.out_ready[k], m->stream));
-        HIP_TRY(hipStreamWaitEvent(pp.d2h, pp.out_ready[k], 0));
-        HIP_TRY(hipMemcpyAsync(probs + off * C, m->stage_p[k]->p, (size_t)c * C * sizeof(float), hipMemcpyDeviceToHost, pp.d2h));
-        if (logits)
-            HIP_TRY(hipMemcpyAsync(logits + off * C, m->stage_l[k]->p, (size_t)c * C * sizeof(float), hipMemcpyDeviceToHost, pp.d2h));
-        HIP_TRY(hipEventRecord(pp.out_free[k], pp.d2h));
-    }
-    HIP_TRY(hipStreamSynchronize(pp.d2h));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return PA_OK;
-}
-
 int pa_variant_forward_host(pa_variant_model* m, const int8_t* images, int64_t n, float* probs,
                             float* logits) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n < 0 || (n > 0 && (!images || !probs))) return fail(PA_ERR_INVALID, "null buffer");
     if (n == 0) return PA_OK;
-    const int rc = variant_forward_host_run(m, images, n, probs, logits);
-    if (rc != PA_OK) m->quiesce();
-    return rc;
+    const size_t per = (size_t)m->cfg.window * m->cfg.image_features;
+    const int C = m->cfg.num_classes_type;
+    const size_t cap = (size_t)std::min<int64_t>(m->cfg.max_chunk, n);
+    return m->host_passes(
+        n, m->cfg.max_chunk,
+        [&](int k, int64_t off, int64_t c) -> int {
+            if (int rc = m->stage_in[k]->ensure(cap * per)) return rc;
+            if (int rc = m->stage_p[k]->ensure(cap * C * sizeof(float))) return rc;
+            if (logits)
+                if (int rc = m->stage_l[k]->ensure(cap * C * sizeof(float))) return rc;
+            HIP_TRY(hipMemcpyAsync(m->stage_in[k]->p, images + (size_t)off * per, (size_t)c * per, hipMemcpyHostToDevice, m->pipe.h2d));
+            return PA_OK;
+        },
+        [&](int k, int64_t c) -> int {
+            return variant_forward_chunk(m, pa::A_I8, m->stage_in[k]->p, c, m->stage_p[k]->f(), logits ? m->stage_l[k]->f() : nullptr);
+        },
+        [&](int k, int64_t off, int64_t c) -> int {
+            HIP_TRY(hipMemcpyAsync(probs + off * C, m->stage_p[k]->p, (size_t)c * C * sizeof(float), hipMemcpyDeviceToHost, m->pipe.d2h));
+            if (logits)
+                HIP_TRY(hipMemcpyAsync(logits + off * C, m->stage_l[k]->p, (size_t)c * C * sizeof(float), hipMemcpyDeviceToHost, m->pipe.d2h));
+            return PA_OK;
+        });
 }
 
 }  // extern "C"
@@ -947,6 +1021,32 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
     bool cur_h2 = false;         // cur is a layer output in the h2 split format
     float* ybuf[2] = {m->y1->f(), m->y2->f()};
     int which = 0;
+
+    // the step loop of a layer, and with it where its gate pre-activations come from: decided from the layer's buffers and
+    // its input (cur*) before anything of the layer is launched
+    enum Rec { SMALL_H2, FUSED_IN_H2, FUSED_IN_F32, FUSED_DEC_DENSE_H2, FUSED_DEC_H2, PLAIN_H2, PLAIN_F32 };
+    auto form_of = [&](const RecLayer& r, bool first, bool last, int64_t xbs) -> LayerForm<Rec> {
+        const bool rec_h2 = m->split_rec && r.w_hh_h2 != nullptr;
+        // Small calls: a step's latency is what counts (19 windows x 200 dependent steps whatever n is), so the projections
+        // run as GEMMs over all T steps and the step loops as 16-row workgroups with their weights in registers
+        const bool small = !m->batch_invariant && m->small_max > 0 && n <= m->small_max && rec_h2 && r.w_hh_small_h2 != nullptr && H == 128 &&
+                           (cur_h2 ? (r.w_ih_h2 != nullptr && m->split_gemm) : first);
+        if (small) return {cur_h2 ? XP_GEMM_H2 : XP_GEMM_F32, SMALL_H2, true};
+        // wide uint8 inputs (16 < F <= 128) are read as dwords by the step loop: rows must be 4-byte aligned
+        const bool fused_h2_ok = rec_h2 && r.w_cat_h2 != nullptr &&
+                                 (r.K <= 16 || ((xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(cur) & 3) == 0));
+        if (first && cur_kind == pa::A_U8 && (r.w_cat != nullptr || fused_h2_ok))
+            return {IN_LOOP, fused_h2_ok ? FUSED_IN_H2 : FUSED_IN_F32, fused_h2_ok};
+        const bool fused_dec_ok = rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 && cur_bs == 0;
+        // last layer: projection AND dense1 contracted inside the step loop; no layer output at all
+        if (fused_dec_ok && want_head && last && m->fuse_head && m->dense_h2 != nullptr && H == 128)
+            return {IN_LOOP, FUSED_DEC_DENSE_H2, true};
+        // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
+        if (fused_dec_ok) return {IN_LOOP, FUSED_DEC_H2, true};
+        // the previous layer's y (workspace, read only here): split in place if needed, f16-pipe GEMM
+        return {!first && m->split_gemm && r.w_ih_h2 != nullptr ? XP_GEMM_H2 : XP_GEMM_F32, rec_h2 ? PLAIN_H2 : PLAIN_F32, rec_h2};
+    };
+
     // encoder: h0 = hidden_in, h_n -> hid_a ; decoder: h0 = hid_a, h_n -> hidden_out
     for (int stage = 0; stage < 2; ++stage) {
         std::vector<RecLayer>& layers = stage == 0 ? m->enc : m->dec;
@@ -954,95 +1054,78 @@ static int polish_window(pa_polish_model* m, int x_kind, const void* x, int x_ld
         float* hn = stage == 0 ? m->hid_a->f() : hidden_out;
         for (int l = 0; l < L; ++l) {
             const RecLayer& r = layers[l];
-            const bool rec_h2 = m->split_rec && r.w_hh_h2 != nullptr;
             const float* h0l = h0 ? h0 + (size_t)l * 2 * H : nullptr;
             float* hnl = hn ? hn + (size_t)l * 2 * H : nullptr;
             float* y = ybuf[which];
             const int64_t xbs = cur_bs > 0 ? cur_bs : (int64_t)T * r.K;
-            // wide uint8 inputs (16 < F <= 128) are read as dwords by the step loop: rows must be 4-byte aligned
-            const bool fused_h2_ok = rec_h2 && r.w_cat_h2 != nullptr &&
-                                     (r.K <= 16 || ((xbs & 3) == 0 && (reinterpret_cast<uintptr_t>(cur) & 3) == 0));
-            // Small calls: a step's latency is what counts (19 windows x 200 dependent steps whatever n is), so the projections
-            // run as GEMMs over all T steps and the step loops as 16-row workgroups with their weights in registers
-            const bool small = !m->batch_invariant && m->small_max > 0 && n <= m->small_max && rec_h2 && r.w_hh_small_h2 != nullptr && H == 128 &&
-                               (cur_h2 ? (r.w_ih_h2 != nullptr && m->split_gemm) : (stage == 0 && l == 0));
-            if (small) {
-                if (cur_h2)
-                    LAUNCH_TRY(m, "gemm_h2_inproj_small", 2.0 * M * NX * r.K,
-                               pa::launch_gemm_h2(cur, cur_ld, (size_t)M * cur_ld * 4, r.w_ih_h2->p, r.K,
-                                                  (size_t)NX * r.K * 4, r.b_in->f(), m->xp->f(), NX,
-                                                  (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
-                else
-                    LAUNCH_TRY(m, "gemm_inproj_in_small", 2.0 * M * NX * r.K,
-                               pa::launch_gemm_nt(cur_kind, cur, cur_ld, r.w_ih->f(), r.Kp, r.b_in->f(), m->xp->f(), NX,
-                                                  (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, cur_bs, T, (int)n, m->stream));
+            const bool first = stage == 0 && l == 0;
+            const LayerForm<Rec> f = form_of(r, first, stage == 1 && l == L - 1, xbs);
+            const bool small = f.rec == SMALL_H2;
+            if (f.proj == XP_GEMM_H2) {
+                if (!cur_h2)
+                    LAUNCH_TRY(m, "cvt_h2", 0.0,
+                               pa::launch_f32_to_h2(static_cast<const float*>(cur), const_cast<void*>(cur), M, r.K,
+                                                    cur_ld, m->stream));
+                LAUNCH_TRY(m, small ? "gemm_h2_inproj_small" : "gemm_h2_inproj", 2.0 * M * NX * r.K,
+                           pa::launch_gemm_h2(cur, cur_ld, (size_t)M * cur_ld * 4, r.w_ih_h2->p, r.K,
+                                              (size_t)NX * r.K * 4, r.b_in->f(), m->xp->f(), NX,
+                                              (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
+            } else if (f.proj == XP_GEMM_F32) {
+                LAUNCH_TRY(m, small ? "gemm_inproj_in_small" : first ? "gemm_inproj_in" : "gemm_inproj", 2.0 * M * NX * r.K,
+                           pa::launch_gemm_nt(cur_kind, cur, cur_ld, r.w_ih->f(), r.Kp, r.b_in->f(), m->xp->f(), NX,
+                                              (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, cur_bs, T, (int)n, m->stream));
+            }
+            switch (f.rec) {
+            case SMALL_H2:
                 LAUNCH_TRY(m, "gru_small_h2", 2.0 * n * T * (3.0 * H) * H * 2,
                            pa::launch_gru_small_h2(H, m->xp->f(), NX, r.w_hh_small_h2->p, r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H,
                                                    (int)n, T, m->stream));
-                cur_h2 = true;
-            } else if (stage == 0 && l == 0 && cur_kind == pa::A_U8 && (r.w_cat != nullptr || fused_h2_ok)) {
-                if (fused_h2_ok)
-                    LAUNCH_TRY(m, "gru_rec_h2_fused_in", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
-                               pa::launch_gru_rec_h2(H, nullptr, 0, static_cast<const uint8_t*>(cur), r.K, xbs, r.b_in->f(),
-                                                     r.w_cat_h2->p, r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T,
-                                                     m->stream));
-                else
-                    LAUNCH_TRY(m, "gru_rec_fused_in", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
-                               pa::launch_gru_rec_fused(H, static_cast<const uint8_t*>(cur), r.K, xbs, r.b_in->f(),
-                                                        r.w_cat->f(), r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T,
-                                                        m->stream));
-                cur_h2 = fused_h2_ok;
-            } else if (want_head && stage == 1 && l == L - 1 && rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 &&
-                       cur_bs == 0 && m->fuse_head && m->dense_h2 != nullptr && H == 128) {
-                // last layer: projection AND dense1 contracted inside the step loop; no layer output at all
+                break;
+            case FUSED_IN_H2:
+                LAUNCH_TRY(m, "gru_rec_h2_fused_in", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
+                           pa::launch_gru_rec_h2(H, nullptr, 0, static_cast<const uint8_t*>(cur), r.K, xbs, r.b_in->f(),
+                                                 r.w_cat_h2->p, r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T,
+                                                 m->stream));
+                break;
+            case FUSED_IN_F32:
+                LAUNCH_TRY(m, "gru_rec_fused_in", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
+                           pa::launch_gru_rec_fused(H, static_cast<const uint8_t*>(cur), r.K, xbs, r.b_in->f(),
+                                                    r.w_cat->f(), r.b_hn->f(), h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T,
+                                                    m->stream));
+                break;
+            case FUSED_DEC_DENSE_H2:
                 if (int rc = m->part->ensure(pa::dense_partials_floats((int)n, T) * sizeof(float))) return rc;
                 LAUNCH_TRY(m, "gru_dec_h2_fused_dense", 2.0 * n * T * ((3.0 * H) * (H + r.K) + m->cfg.num_classes * H) * 2,
                            pa::launch_gru_dec_h2_dense(H, cur, cur_ld, r.b_in->f(), r.w_cat_dec_h2->p, r.b_hn->f(), h0l, ldh, hnl,
                                                        ldh, m->dense_h2->p, m->part->f(), (int)n, T, m->stream));
                 *head_fused = true;
-                cur_h2 = true;
-            } else if (rec_h2 && cur_h2 && r.w_cat_dec_h2 != nullptr && cur_rpb == 0 && cur_bs == 0) {
-                // h2 layer output -> this layer: projection contracted inside the step loop (no GEMM, no Xp)
+                break;
+            case FUSED_DEC_H2:
                 LAUNCH_TRY(m, "gru_dec_h2_fused", 2.0 * n * T * (3.0 * H) * (H + r.K) * 2,
                            pa::launch_gru_dec_h2(H, cur, cur_ld, r.b_in->f(), r.w_cat_dec_h2->p, r.b_hn->f(), h0l, ldh, hnl,
                                                  ldh, y, 2 * H, (int)n, T, m->stream));
-                cur_h2 = true;
-            } else {
-                if (!(stage == 0 && l == 0) && m->split_gemm && r.w_ih_h2 != nullptr) {
-                    // the previous layer's y (workspace, read only here): split in place if needed, f16-pipe GEMM
-                    if (!cur_h2)
-                        LAUNCH_TRY(m, "cvt_h2", 0.0,
-                                   pa::launch_f32_to_h2(static_cast<const float*>(cur), const_cast<void*>(cur), M, r.K,
-                                                        cur_ld, m->stream));
-                    LAUNCH_TRY(m, "gemm_h2_inproj", 2.0 * M * NX * r.K,
-                               pa::launch_gemm_h2(cur, cur_ld, (size_t)M * cur_ld * 4, r.w_ih_h2->p, r.K,
-                                                  (size_t)NX * r.K * 4, r.b_in->f(), m->xp->f(), NX,
-                                                  (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, 0, T, (int)n, m->stream));
-                } else {
-                    LAUNCH_TRY(m, (stage == 0 && l == 0) ? "gemm_inproj_in" : "gemm_inproj", 2.0 * M * NX * r.K,
-                               pa::launch_gemm_nt(cur_kind, cur, cur_ld, r.w_ih->f(), r.Kp, r.b_in->f(), m->xp->f(), NX,
-                                                  (int)(round_up(n, MTP) * T), NX, r.K, 0, 0, cur_bs, T, (int)n, m->stream));
-                }
-                if (rec_h2)
-                    LAUNCH_TRY(m, "gru_rec_h2", 2.0 * n * T * (3.0 * H) * H * 2,
-                               pa::launch_gru_rec_h2(H, m->xp->f(), NX, nullptr, 0, 0, nullptr, r.w_hh_h2->p, r.b_hn->f(),
-                                                     h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T, m->stream));
-                else
-                    LAUNCH_TRY(m, "gru_rec", 2.0 * n * T * (3.0 * H) * H * 2,
-                               pa::launch_gru_rec(H, m->xp->f(), NX, r.w_hh->f(), r.b_hn->f(), h0l, ldh, hnl, ldh, y,
-                                                  2 * H, (int)n, T, m->stream));
-                cur_h2 = rec_h2;
+                break;
+            case PLAIN_H2:
+                LAUNCH_TRY(m, "gru_rec_h2", 2.0 * n * T * (3.0 * H) * H * 2,
+                           pa::launch_gru_rec_h2(H, m->xp->f(), NX, nullptr, 0, 0, nullptr, r.w_hh_h2->p, r.b_hn->f(),
+                                                 h0l, ldh, hnl, ldh, y, 2 * H, (int)n, T, m->stream));
+                break;
+            case PLAIN_F32:
+                LAUNCH_TRY(m, "gru_rec", 2.0 * n * T * (3.0 * H) * H * 2,
+                           pa::launch_gru_rec(H, m->xp->f(), NX, r.w_hh->f(), r.b_hn->f(), h0l, ldh, hnl, ldh, y,
+                                              2 * H, (int)n, T, m->stream));
+                break;
             }
             cur = y;
             cur_kind = pa::A_F32;
             cur_ld = 2 * H;
             cur_rpb = 0;
             cur_bs = 0;
+            cur_h2 = f.y_h2;
             which ^= 1;
         }
     }
     m->y_h2 = cur_h2;
-    (void)cur_rpb;
     *y_last = const_cast<float*>(static_cast<const float*>(cur));
     return PA_OK;
 }
@@ -1069,15 +1152,10 @@ int pa_polish_create(const pa_polish_config* cfg, const char* const* names, cons
         return fail(PA_ERR_INVALID, "bad pa_polish_config (hidden_size must be 128 or 256)");
     auto* m = new pa_polish_model();
     m->cfg = *cfg;
-    if (m->cfg.max_chunk <= 0) m->cfg.max_chunk = 16384;   // 128 chunks per workgroup and direction: 256 workgroups
-    m->cfg.max_chunk = std::min<int32_t>(m->cfg.max_chunk, (int32_t)((int64_t)0xf0000000 / ((int64_t)cfg->window * 2 * cfg->hidden_size * 4)));
-    if (const char* e = getenv("PA_SPLIT_GEMM")) m->split_gemm = e[0] != '0';
-    if (const char* e = getenv("PA_SPLIT_REC")) m->split_rec = e[0] != '0';
-    StateDict sd(names, data, numel, n_tensors);
-    if (!(state_dict_max_abs_weight(sd) < kSplitMaxWeight)) m->split_gemm = false;   // see kSplitMaxWeight
-    m->split_rec = m->split_rec && m->split_gemm && cfg->hidden_size == 128;
-    int rc = init_base(m, cfg->device, hip_stream);
     const int H = cfg->hidden_size;
+    StateDict sd(names, data, numel, n_tensors);
+    int rc = create_common(m, sd, cfg->window, H, hip_stream);
+    m->split_rec = m->split_rec && H == 128;   // the split GRU step loops exist for hidden size 128 only
     for (int stage = 0; stage < 2 && rc == PA_OK; ++stage)
         for (int l = 0; l < cfg->gru_layers && rc == PA_OK; ++l) {
             auto& vec = stage == 0 ? m->enc : m->dec;
@@ -1095,35 +1173,23 @@ int pa_polish_create(const pa_polish_config* cfg, const char* const* names, cons
         std::vector<uint32_t> packed(pa::dense_head_h2_words(H));
         pa::pack_dense_head_h2(w, cfg->num_classes, H, packed.data());
         m->dense_h2 = m->new_buf();
-        rc = m->dense_h2->ensure(packed.size() * sizeof(uint32_t));
-        if (rc == PA_OK && hipMemcpy(m->dense_h2->p, packed.data(), packed.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-            rc = fail(PA_ERR_HIP, "upload of the packed dense1 fragments failed");
+        rc = upload(m->dense_h2, packed);
     }
     if (rc != PA_OK) {
         delete m;
         return rc;
     }
-    m->part = m->new_buf();
-    m->xp = m->new_buf(); m->y1 = m->new_buf(); m->y2 = m->new_buf();
-    m->hid_a = m->new_buf(); m->hid_b = m->new_buf(); m->acc = m->new_buf();
-    for (int k = 0; k < 2; ++k) {
-        m->stage_in[k] = m->new_buf(); m->stage_lab[k] = m->new_buf(); m->stage_ph[k] = m->new_buf();
-        m->stage_acc[k] = m->new_buf();
-    }
+    m->new_bufs({&m->part, &m->xp, &m->y1, &m->y2, &m->hid_a, &m->hid_b, &m->acc, &m->stage_in[0], &m->stage_lab[0], &m->stage_ph[0],
+                 &m->stage_acc[0], &m->stage_in[1], &m->stage_lab[1], &m->stage_ph[1], &m->stage_acc[1]});
     *out = m;
     return PA_OK;
 }
 
-void pa_polish_destroy(pa_polish_model* m) {
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    if (m->stream) (void)hipStreamSynchronize(m->stream);
-    delete m;
-}
+void pa_polish_destroy(pa_polish_model* m) { destroy_model(m); }
 
 int pa_polish_forward_device(pa_polish_model* m, const float* x, const float* hidden, int64_t n, int32_t T,
                              float* logits, float* hidden_out) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n < 0 || T <= 0 || (n > 0 && (!x || !logits))) return fail(PA_ERR_INVALID, "bad argument");
     if (n == 0) return PA_OK;
     HIP_TRY(hipSetDevice(m->device));
@@ -1158,7 +1224,7 @@ int pa_polish_forward_device(pa_polish_model* m, const float* x, const float* hi
 
 int pa_polish_predict_device(pa_polish_model* m, const uint8_t* images, int64_t n, uint8_t* labels,
                              uint8_t* phred, float* acc_out) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n < 0 || (n > 0 && (!images || !labels || !phred))) return fail(PA_ERR_INVALID, "null buffer");
     if (n == 0) return PA_OK;
     HIP_TRY(hipSetDevice(m->device));
@@ -1208,20 +1274,16 @@ int pa_polish_predict_device(pa_polish_model* m, const uint8_t* images, int64_t 
 // One or several host blocks as ONE sequence of device passes: the polish kernels give a workgroup 128 chunks of one
 // direction and walk their time steps in sequence, so a pass costs about the same for 2 048 chunks as for 16 384 -- callers
 // that hold their chunks in several buffers (the reader lanes' slots, pepper_amd/hostpipe.py) hand them over together.
-static int polish_predict_host_run(pa_polish_model* m, int32_t n_parts, const uint8_t* const* images, const int64_t* counts,
-                                   uint8_t* const* labels, uint8_t* const* phred, float* acc) {
+static int polish_predict_host_blocks(pa_polish_model* m, int32_t n_parts, const uint8_t* const* images, const int64_t* counts,
+                                      uint8_t* const* labels, uint8_t* const* phred, float* acc) {
     int64_t n = 0;
     for (int32_t p = 0; p < n_parts; ++p) {
         if (counts[p] < 0 || (counts[p] > 0 && (!images[p] || !labels[p] || !phred[p]))) return fail(PA_ERR_INVALID, "null buffer");
         n += counts[p];
     }
     if (n == 0) return PA_OK;
-    HIP_TRY(hipSetDevice(m->device));
-    if (int rc = m->pipe_init()) return rc;
     const size_t S = m->cfg.seq_length, F = m->cfg.image_features, C = m->cfg.num_classes;
-    const int64_t chunk = m->cfg.max_chunk;
-    const size_t cap = (size_t)std::min<int64_t>(chunk, n);
-    auto& pp = m->pipe;
+    const size_t cap = (size_t)std::min<int64_t>(m->cfg.max_chunk, n);
     // the pieces of the parts that make up units [off, off + c): f(part, first unit within the part, first unit within the pass, units)
     auto pieces = [&](int64_t off, int64_t c, auto&& f) -> int {
         int64_t start = 0;
@@ -1233,100 +1295,69 @@ static int polish_predict_host_run(pa_polish_model* m, int32_t n_parts, const ui
         }
         return PA_OK;
     };
-    int64_t i = 0;
-    for (int64_t off = 0; off < n; off += chunk, ++i) {
-        const int64_t c = std::min<int64_t>(chunk, n - off);
-        const int k = (int)(i & 1);
-        if (int rc = m->stage_in[k]->ensure(cap * S * F)) return rc;
-        if (int rc = m->stage_lab[k]->ensure(cap * S)) return rc;
-        if (int rc = m->stage_ph[k]->ensure(cap * S)) return rc;
-        if (acc)
-            if (int rc = m->stage_acc[k]->ensure(cap * S * C * sizeof(float))) return rc;
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(pp.h2d, pp.in_free[k], 0));
-        if (int rc = pieces(off, c, [&](int32_t p, int64_t in_part, int64_t in_pass, int64_t units) -> int {
-                HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(m->stage_in[k]->p) + (size_t)in_pass * S * F,
-                                       images[p] + (size_t)in_part * S * F, (size_t)units * S * F, hipMemcpyHostToDevice, pp.h2d));
+    auto slot = [](DevBuf* b, int64_t in_pass, size_t row) { return static_cast<uint8_t*>(b->p) + (size_t)in_pass * row; };
+    return m->host_passes(
+        n, m->cfg.max_chunk,
+        [&](int k, int64_t off, int64_t c) -> int {
+            if (int rc = m->stage_in[k]->ensure(cap * S * F)) return rc;
+            if (int rc = m->stage_lab[k]->ensure(cap * S)) return rc;
+            if (int rc = m->stage_ph[k]->ensure(cap * S)) return rc;
+            if (acc)
+                if (int rc = m->stage_acc[k]->ensure(cap * S * C * sizeof(float))) return rc;
+            return pieces(off, c, [&](int32_t p, int64_t in_part, int64_t in_pass, int64_t units) -> int {
+                HIP_TRY(hipMemcpyAsync(slot(m->stage_in[k], in_pass, S * F), images[p] + (size_t)in_part * S * F, (size_t)units * S * F,
+                                       hipMemcpyHostToDevice, m->pipe.h2d));
                 return PA_OK;
-            }))
-            return rc;
-        HIP_TRY(hipEventRecord(pp.in_ready[k], pp.h2d));
-        HIP_TRY(hipStreamWaitEvent(m->stream, pp.in_ready[k], 0));
-        if (i >= 2) HIP_TRY(hipStreamWaitEvent(m->stream, pp.out_free[k], 0));
-        if (int rc = pa_polish_predict_device(m, static_cast<const uint8_t*>(m->stage_in[k]->p), c,
-                                              static_cast<uint8_t*>(m->stage_lab[k]->p),
-                                              static_cast<uint8_t*>(m->stage_ph[k]->p), acc ? m->stage_acc[k]->f() : nullptr))
-            return rc;
-        HIP_TRY(hipEventRecord(pp.in_free[k], m->stream));
-        HIP_TRY(hipEventRecord(pp.out_ready[k], m->stream));
-        HIP_TRY(hipStreamWaitEvent(pp.d2h, pp.out_ready[k], 0));
-        if (int rc = pieces(off, c, [&](int32_t p, int64_t in_part, int64_t in_pass, int64_t units) -> int {
-                HIP_TRY(hipMemcpyAsync(labels[p] + (size_t)in_part * S, static_cast<uint8_t*>(m->stage_lab[k]->p) + (size_t)in_pass * S,
-                                       (size_t)units * S, hipMemcpyDeviceToHost, pp.d2h));
-                HIP_TRY(hipMemcpyAsync(phred[p] + (size_t)in_part * S, static_cast<uint8_t*>(m->stage_ph[k]->p) + (size_t)in_pass * S,
-                                       (size_t)units * S, hipMemcpyDeviceToHost, pp.d2h));
-                return PA_OK;
-            }))
-            return rc;
-        if (acc)     // single-part callers only (pa_polish_predict_host)
-            HIP_TRY(hipMemcpyAsync(acc + (size_t)off * S * C, m->stage_acc[k]->p, (size_t)c * S * C * sizeof(float),
-                                   hipMemcpyDeviceToHost, pp.d2h));
-        HIP_TRY(hipEventRecord(pp.out_free[k], pp.d2h));
-    }
-    HIP_TRY(hipStreamSynchronize(pp.d2h));
-    HIP_TRY(hipStreamSynchronize(m->stream));
-    return PA_OK;
-}
-
-static int polish_predict_host_impl(pa_polish_model* m, int32_t n_parts, const uint8_t* const* images, const int64_t* counts,
-                                    uint8_t* const* labels, uint8_t* const* phred, float* acc) {
-    const int rc = polish_predict_host_run(m, n_parts, images, counts, labels, phred, acc);
-    if (rc != PA_OK) m->quiesce();
-    return rc;
+            });
+        },
+        [&](int k, int64_t c) -> int {
+            return pa_polish_predict_device(m, static_cast<const uint8_t*>(m->stage_in[k]->p), c, static_cast<uint8_t*>(m->stage_lab[k]->p),
+                                            static_cast<uint8_t*>(m->stage_ph[k]->p), acc ? m->stage_acc[k]->f() : nullptr);
+        },
+        [&](int k, int64_t off, int64_t c) -> int {
+            if (int rc = pieces(off, c, [&](int32_t p, int64_t in_part, int64_t in_pass, int64_t units) -> int {
+                    HIP_TRY(hipMemcpyAsync(labels[p] + (size_t)in_part * S, slot(m->stage_lab[k], in_pass, S), (size_t)units * S,
+                                           hipMemcpyDeviceToHost, m->pipe.d2h));
+                    HIP_TRY(hipMemcpyAsync(phred[p] + (size_t)in_part * S, slot(m->stage_ph[k], in_pass, S), (size_t)units * S,
+                                           hipMemcpyDeviceToHost, m->pipe.d2h));
+                    return PA_OK;
+                }))
+                return rc;
+            if (acc)     // single-part callers only (pa_polish_predict_host)
+                HIP_TRY(hipMemcpyAsync(acc + (size_t)off * S * C, m->stage_acc[k]->p, (size_t)c * S * C * sizeof(float),
+                                       hipMemcpyDeviceToHost, m->pipe.d2h));
+            return PA_OK;
+        });
 }
 
 int pa_polish_predict_host(pa_polish_model* m, const uint8_t* images, int64_t n, uint8_t* labels,
                            uint8_t* phred, float* acc) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n < 0 || (n > 0 && (!images || !labels || !phred))) return fail(PA_ERR_INVALID, "null buffer");
-    return polish_predict_host_impl(m, 1, &images, &n, &labels, &phred, acc);
+    return polish_predict_host_blocks(m, 1, &images, &n, &labels, &phred, acc);
 }
 
 int pa_polish_predict_host_parts(pa_polish_model* m, int32_t n_parts, const uint8_t* const* images, const int64_t* counts,
                                  uint8_t* const* labels, uint8_t* const* phred) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
+    if (!as_base(m)) return fail(PA_ERR_INVALID, "bad model handle");
     if (n_parts < 0 || (n_parts > 0 && (!images || !counts || !labels || !phred))) return fail(PA_ERR_INVALID, "bad argument");
-    return polish_predict_host_impl(m, n_parts, images, counts, labels, phred, nullptr);
+    return polish_predict_host_blocks(m, n_parts, images, counts, labels, phred, nullptr);
 }
 
 int pa_polish_set_batch_invariant(pa_polish_model* m, int32_t on) {
-    if (!m || m->magic != 0x50414d44) return fail(PA_ERR_INVALID, "bad model handle");
-    if (on != 0 && on != 1) return fail(PA_ERR_INVALID, "pa_polish_set_batch_invariant: on must be 0 or 1");
     // The f32 recurrences (a checkpoint with a weight >= kSplitMaxWeight, PA_SPLIT_GEMM=0 / PA_SPLIT_REC=0, hidden size 256)
     // were measured NOT to give a chunk the same bits at every call size (tests/test_gpu_batch_invariant.py): the mode is
     // refused there rather than promised.
-    if (on && !m->split_rec)
+    if (as_base(m) && on == 1 && !m->split_rec)
         return fail(PA_ERR_UNSUPPORTED, "pa_polish_set_batch_invariant: this handle runs the exact-f32 GRU kernels (largest weight >= " +
                                             std::to_string((int)kSplitMaxWeight) + ", hidden size 256, or PA_SPLIT_GEMM=0 / PA_SPLIT_REC=0), "
                                             "whose results depend on the call size; batch-invariant mode needs the split-f16 kernels");
-    m->batch_invariant = on != 0;
-    return PA_OK;
+    return set_batch_invariant(m, on, "pa_polish_set_batch_invariant");
 }
 
-int pa_polish_get_batch_invariant(pa_polish_model* m, int32_t* on) {
-    if (!m || m->magic != 0x50414d44 || !on) return fail(PA_ERR_INVALID, "bad model handle");
-    *on = m->batch_invariant ? 1 : 0;
-    return PA_OK;
-}
+int pa_polish_get_batch_invariant(pa_polish_model* m, int32_t* on) { return get_batch_invariant(m, on); }
 
 // ---- profiler / sync -----------------------------------------------------------------------------
-static ModelBase* as_base(void* model) {
-    // Both handle structs derive from ModelBase as their only (polymorphic) base, so a handle's
-    // address is its ModelBase address; the magic word guards against foreign pointers.
-    auto* b = reinterpret_cast<ModelBase*>(model);
-    if (!model || b->magic != 0x50414d44) return nullptr;
-    return b;
-}
-
 int pa_profile_enable(void* model, int32_t on) {
     ModelBase* b = as_base(model);
     if (!b) return fail(PA_ERR_INVALID, "bad model handle");

@@ -6,68 +6,35 @@ hidden hand-off, plus ``predict_chunks`` = the whole sliding-window loop of
 /root/reference/pepper/modules/python/models/predict_distributed_cpu.py:43-90 on the device.
 """
 import ctypes
-import os
 
 import torch
 
 from pepper_amd import _lib
+from pepper_amd._handle import NEW_HANDLES, HandleModel, _pinned_empty
 from pepper_amd.polish.Options import ImageSizeOptions, TrainOptions
 
 
-class TransducerGRU(object):
+class TransducerGRU(HandleModel):
+    KIND = "polish"
+
     def __init__(self, image_channels, image_features, gru_layers, hidden_size, num_classes,
                  bidirectional=True, device=None, max_chunk=0, batch_invariant=None):
         if not bidirectional:
             raise ValueError("the reference inference path only instantiates bidirectional=True")
+        HandleModel.__init__(self, device, max_chunk, batch_invariant)
         self.image_features = image_features
         self.hidden_size = hidden_size
         self.num_layers = gru_layers
         self.num_classes = num_classes
-        self.max_chunk = max_chunk
-        # batch-invariant mode (include/pepper_amd.h pa_polish_set_batch_invariant): on when asked for here, or when the process
-        # has PEPPER_AMD_BATCH_INVARIANT=1
-        # and the argument is left at None (an explicit True / False wins over the environment)
-        self.batch_invariant = _lib.batch_invariant_default(batch_invariant)
-        self.device = torch.cuda.current_device() if device is None and torch.cuda.is_available() else (device or 0)
-        self._handle = None
-        self._stream = None
         self._state = None
 
     def load_state_dict(self, state_dict, strict=True):
-        lib = _lib.load()
-        self.close()
-        cfg = _lib.PolishConfig(self.image_features, self.hidden_size, self.num_layers, self.num_classes,
-                                ImageSizeOptions.SEQ_LENGTH, TrainOptions.TRAIN_WINDOW,
-                                TrainOptions.WINDOW_JUMP, ImageSizeOptions.SEQ_OVERLAP, self.device,
-                                self.max_chunk)
-        names, data, numel, n, keep = _lib.marshal_state_dict(state_dict)
-        # (priority -1: a stream of the device's high-priority queues -- a caller whose passes must not queue behind other
-        # streams' long kernels in a shared hardware queue, polish/fused.py)
-        self._stream = torch.cuda.Stream(device=self.device, priority=int(getattr(self, "stream_priority", 0)))
-        handle = ctypes.c_void_p()
-        _lib.check(lib.pa_polish_create(ctypes.byref(cfg), names, data, numel, n,
-                                        ctypes.c_void_p(self._stream.cuda_stream), ctypes.byref(handle)))
-        self._handle = handle
+        self._create(_lib.PolishConfig(self.image_features, self.hidden_size, self.num_layers, self.num_classes,
+                                       ImageSizeOptions.SEQ_LENGTH, TrainOptions.TRAIN_WINDOW,
+                                       TrainOptions.WINDOW_JUMP, ImageSizeOptions.SEQ_OVERLAP, self.device,
+                                       self.max_chunk), state_dict)
         self._state = state_dict
-        if self.batch_invariant:
-            try:
-                _lib.check(lib.pa_polish_set_batch_invariant(handle, 1))
-            except _lib.PepperAmdError:
-                self.close()             # (the exact-f32 kernels refuse the mode: no handle without the guarantee asked for)
-                raise
         return self
-
-    def set_batch_invariant(self, on=True):
-        """Switch the handle's batch-invariant mode between calls (it applies from the next prediction)."""
-        on = _lib.parse_batch_invariant(on)
-        _lib.check(_lib.load().pa_polish_set_batch_invariant(self.handle, int(on)))
-        self.batch_invariant = on
-        return self
-
-    def get_batch_invariant(self):
-        v = ctypes.c_int32()
-        _lib.check(_lib.load().pa_polish_get_batch_invariant(self.handle, ctypes.byref(v)))
-        return bool(v.value)
 
     def clone(self, stream_priority=None):
         """A second, independent handle on the same weights (own stream, own staging buffers): what runs a second block on
@@ -75,51 +42,20 @@ class TransducerGRU(object):
         the clone's stream; None: this object's."""
         other = TransducerGRU(1, self.image_features, self.num_layers, self.hidden_size, self.num_classes, device=self.device,
                               max_chunk=self.max_chunk, batch_invariant=self.batch_invariant)
-        other.stream_priority = int(getattr(self, "stream_priority", 0) if stream_priority is None else stream_priority)
-        return other.load_state_dict(self._state)
-
-    def eval(self):
-        return self
-
-    def cuda(self, device=None):
-        return self
-
-    def cpu(self):
-        return self
-
-    def close(self):
-        if self._handle is not None:
-            _lib.load().pa_polish_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
+        # (priority -1: a stream of the device's high-priority queues -- a caller whose passes must not queue behind other
+        # streams' long kernels in a shared hardware queue, polish/fused.py)
+        before = getattr(NEW_HANDLES, "stream_priority", 0)
+        NEW_HANDLES.stream_priority = int(self._stream.priority if stream_priority is None else stream_priority)
         try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        if self._handle is None:
-            raise _lib.PepperAmdError("TransducerGRU has no weights: call load_state_dict first")
-        return self._handle
+            return other.load_state_dict(self._state)
+        finally:
+            NEW_HANDLES.stream_priority = before
 
     def init_hidden(self, batch_size, num_layers, bidirectional=True):
         return torch.zeros(batch_size, (2 if bidirectional else 1) * num_layers, self.hidden_size)
 
     def __call__(self, x, hidden):
         return self.forward(x, hidden)
-
-    def _enter(self, dev):
-        cur = torch.cuda.current_stream(dev)
-        self._stream.wait_stream(cur)
-        return cur
-
-    def _leave(self, cur, tensors):
-        for t in tensors:
-            if t is not None:
-                t.record_stream(self._stream)
-        cur.wait_stream(self._stream)
 
     def forward(self, x, hidden):
         lib = _lib.load()
@@ -133,10 +69,9 @@ class TransducerGRU(object):
             raise ValueError("bad x / hidden shape")
         logits = torch.empty((n, T, self.num_classes), dtype=torch.float32, device=dev)
         hidden_out = torch.empty_like(hidden)
-        cur = self._enter(dev)
-        _lib.check(lib.pa_polish_forward_device(self.handle, x.data_ptr(), hidden.data_ptr(), n, T,
-                                                logits.data_ptr(), hidden_out.data_ptr()))
-        self._leave(cur, (x, hidden, logits, hidden_out))
+        with self._on_stream(x, hidden, logits, hidden_out):
+            _lib.check(lib.pa_polish_forward_device(self.handle, x.data_ptr(), hidden.data_ptr(), n, T,
+                                                    logits.data_ptr(), hidden_out.data_ptr()))
         return (logits.cpu(), hidden_out.cpu()) if on_cpu else (logits, hidden_out)
 
     def predict_chunks_into(self, images, labels, phred):
@@ -179,7 +114,6 @@ class TransducerGRU(object):
             raise ValueError("polish images are uint8 (pepper DataStore.py:60)")
         if on_cpu:
             # host buffers: device passes with the copies of the neighbouring passes beside the kernels
-            from pepper_amd.variant.models.simple_model import _pinned_empty
             images = images.contiguous()
             n, S = images.shape[0], images.shape[1]
             labels = _pinned_empty((n, S), torch.uint8)
@@ -193,9 +127,8 @@ class TransducerGRU(object):
         labels = torch.empty((n, S), dtype=torch.uint8, device=dev)
         phred = torch.empty((n, S), dtype=torch.uint8, device=dev)
         acc = torch.empty((n, S, self.num_classes), dtype=torch.float32, device=dev) if return_acc else None
-        cur = self._enter(dev)
-        _lib.check(lib.pa_polish_predict_device(self.handle, images.data_ptr(), n, labels.data_ptr(),
-                                                phred.data_ptr(), acc.data_ptr() if acc is not None else None))
-        self._leave(cur, (images, labels, phred, acc))
+        with self._on_stream(images, labels, phred, acc):
+            _lib.check(lib.pa_polish_predict_device(self.handle, images.data_ptr(), n, labels.data_ptr(),
+                                                    phred.data_ptr(), acc.data_ptr() if acc is not None else None))
         out = (labels, phred) + ((acc,) if return_acc else ())
         return tuple(t.cpu() for t in out) if on_cpu else out

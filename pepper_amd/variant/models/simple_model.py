@@ -5,34 +5,21 @@ constructor arguments, same state_dict keys/shapes, ``forward(x, train_mode=Fals
 softmax probabilities [B,3] (logits when ``train_mode``).  All arithmetic runs in
 libpepper_amd.so on the GPU; torch is used only for device memory and stream ordering.
 """
-import ctypes
-
 import torch
 
 from pepper_amd import _lib
+from pepper_amd._handle import NEW_HANDLES, HandleModel, _pinned_empty  # noqa: F401  (NEW_HANDLES: set by variant/fused.py)
 from pepper_amd.variant.Options import ImageSizeOptions
 
 
-def _pinned_empty(shape, dtype):
-    """Page-locked result buffer (the D2H copies of the host entry points are asynchronous only into pinned memory);
-    falls back to pageable memory where pinning is refused."""
-    try:
-        return torch.empty(shape, dtype=dtype, pin_memory=True)
-    except RuntimeError:
-        return torch.empty(shape, dtype=dtype)
+class TransducerGRU(HandleModel):
+    KIND = "variant"
 
-
-# Per thread: the priority of the stream a handle made on this thread gets (0; -1 = one of the device's high-priority queues).  The
-# loaders keep the reference's signatures, so a caller that wants its forwards not to queue behind other streams' long kernels in a
-# shared hardware queue (variant/fused.py) sets NEW_HANDLES.stream_priority around its load.
-import threading as _threading
-NEW_HANDLES = _threading.local()
-
-class TransducerGRU(object):
     def __init__(self, image_features, gru_layers, hidden_size, num_classes, num_classes_type,
                  bidirectional=True, device=None, max_chunk=0, batch_invariant=None):
         if not bidirectional:
             raise ValueError("the reference inference path only instantiates bidirectional=True")
+        HandleModel.__init__(self, device, max_chunk, batch_invariant)
         self.image_features = image_features
         self.hidden_size = hidden_size          # kept for parity; layer widths are fixed at 256/512
         self.bidirectional = bidirectional
@@ -40,74 +27,11 @@ class TransducerGRU(object):
         self.num_classes = num_classes
         self.num_classes_type = num_classes_type
         self.window = ImageSizeOptions.CANDIDATE_WINDOW_SIZE + 1
-        self.max_chunk = max_chunk
-        # batch-invariant mode (include/pepper_amd.h pa_variant_set_batch_invariant): on when asked for here, or when the process
-        # has PEPPER_AMD_BATCH_INVARIANT=1
-        # and the argument is left at None (an explicit True / False wins over the environment)
-        self.batch_invariant = _lib.batch_invariant_default(batch_invariant)
-        self.device = torch.cuda.current_device() if device is None and torch.cuda.is_available() else (device or 0)
-        self._handle = None
-        self._stream = None
-        self.training = False
 
-    # ---- nn.Module-like surface used by predict() ------------------------------------------
+    # ---- nn.Module-like surface used by predict() (the rest of it: HandleModel) ------------------
     def load_state_dict(self, state_dict, strict=True):
-        lib = _lib.load()
-        self.close()
-        cfg = _lib.VariantConfig(self.image_features, self.window, self.num_layers,
-                                 self.num_classes_type, self.device, self.max_chunk)
-        names, data, numel, n, keep = _lib.marshal_state_dict(state_dict)
-        self._stream = torch.cuda.Stream(device=self.device, priority=int(getattr(NEW_HANDLES, "stream_priority", 0)))
-        handle = ctypes.c_void_p()
-        _lib.check(lib.pa_variant_create(ctypes.byref(cfg), names, data, numel, n,
-                                         ctypes.c_void_p(self._stream.cuda_stream), ctypes.byref(handle)))
-        self._handle = handle
-        if self.batch_invariant:
-            try:
-                _lib.check(lib.pa_variant_set_batch_invariant(handle, 1))
-            except _lib.PepperAmdError:
-                self.close()
-                raise
-        return self
-
-    def set_batch_invariant(self, on=True):
-        """Switch the handle's batch-invariant mode between calls (it applies from the next forward)."""
-        on = _lib.parse_batch_invariant(on)
-        _lib.check(_lib.load().pa_variant_set_batch_invariant(self.handle, int(on)))
-        self.batch_invariant = on
-        return self
-
-    def get_batch_invariant(self):
-        v = ctypes.c_int32()
-        _lib.check(_lib.load().pa_variant_get_batch_invariant(self.handle, ctypes.byref(v)))
-        return bool(v.value)
-
-    def eval(self):
-        self.training = False
-        return self
-
-    def cuda(self, device=None):
-        return self
-
-    def cpu(self):
-        return self
-
-    def close(self):
-        if self._handle is not None:
-            _lib.load().pa_variant_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    @property
-    def handle(self):
-        if self._handle is None:
-            raise _lib.PepperAmdError("TransducerGRU has no weights: call load_state_dict first")
-        return self._handle
+        return self._create(_lib.VariantConfig(self.image_features, self.window, self.num_layers,
+                                               self.num_classes_type, self.device, self.max_chunk), state_dict)
 
     def __call__(self, x, train_mode=False):
         return self.forward(x, train_mode)
@@ -136,14 +60,9 @@ class TransducerGRU(object):
         n = x.shape[0]
         probs = torch.empty((n, self.num_classes_type), dtype=torch.float32, device=dev)
         logits = torch.empty_like(probs) if train_mode else None
-        cur = torch.cuda.current_stream(dev)
-        self._stream.wait_stream(cur)
         fn = lib.pa_variant_forward_device if x.dtype == torch.int8 else lib.pa_variant_forward_device_f32
-        _lib.check(fn(self.handle, x.data_ptr(), n, probs.data_ptr(),
-                      logits.data_ptr() if logits is not None else None))
-        for t in (x, probs, logits):
-            if t is not None:
-                t.record_stream(self._stream)
-        cur.wait_stream(self._stream)
+        with self._on_stream(x, probs, logits):
+            _lib.check(fn(self.handle, x.data_ptr(), n, probs.data_ptr(),
+                          logits.data_ptr() if logits is not None else None))
         out = logits if train_mode else probs
         return out.cpu() if on_cpu else out
