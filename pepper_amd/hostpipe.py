@@ -15,14 +15,21 @@ numbering (variant) never span lanes because an image file never does; the next 
 directory (FindCandidates.py:151-166, perform_stitch.py:44-72), exactly as it does for the per-GPU / per-thread files the
 reference writes.
 
-Worker processes are spawned (the parent holds a HIP context) and import only numpy + the libhdf5 binding.
+Worker processes are spawned (the parent holds a HIP context) and import only numpy + the libhdf5 binding.  Both models go
+through one harness (_lanes: slots, queues, workers, clean-up) and one GPU loop (_device_loop); polish_lanes and
+variant_lanes supply their sizes, their worker functions, how blocks become a device pass and what a retired block does.
 """
 import collections
+import contextlib
 import os
+import queue
 import sys
+import threading
 import time
 import traceback
+from concurrent.futures import ThreadPoolExecutor
 from multiprocessing import get_context, shared_memory
+from types import SimpleNamespace
 
 import numpy as np
 
@@ -64,7 +71,6 @@ class Slots(object):
     order given, while the workers start and read; ready(i) waits for segment i."""
 
     def __init__(self, count, nbytes, pin_bytes=None):
-        import threading
         self.nbytes = int(nbytes)
         self.pin_bytes = self.nbytes if pin_bytes is None else min(int(pin_bytes), self.nbytes)   # leading bytes the GPU touches
         self.segments = []
@@ -133,7 +139,6 @@ class Slots(object):
 def register_async(slot_sets, use_gpu=True):
     """Page-lock every segment of every Slots object on one background thread: slot 0 of each lane first, then slot 1 ...
     (the order the lanes will need them).  Without a GPU (CPU tests) the segments are just marked ready."""
-    import threading
     order = [(sl, i) for i in range(max(len(sl.segments) for sl in slot_sets)) for sl in slot_sets if i < len(sl.segments)]
 
     def work():
@@ -212,7 +217,6 @@ def _start_all(procs):
             if had_file:
                 del main.__file__
         # a spawned interpreter takes ~20 ms of this process's time to start; four threads start them side by side
-        from concurrent.futures import ThreadPoolExecutor
         with ThreadPoolExecutor(max_workers=4) as starters:
             list(starters.map(lambda p: p.start(), procs))
     finally:
@@ -231,7 +235,6 @@ class _Preparing(object):
         self.error = None
         self.thread = None
         if prepare is not None:
-            import threading
             self.thread = threading.Thread(target=self._run, args=(prepare,), daemon=True)
             self.thread.start()
 
@@ -258,7 +261,6 @@ def _next_message(result_q, procs, poll=None):
     caller's script without the `if __name__ == "__main__":` guard that spawned children need) must not leave the GPU
     loop waiting forever.  poll: seconds after which to return None instead of waiting on (the caller has device passes
     in flight to look after)."""
-    import queue
     if poll is not None:
         try:
             return result_q.get(timeout=poll)
@@ -290,6 +292,164 @@ def _guarded(fn, lane, result_q, args):
         fn(lane, result_q, *args)
     except BaseException:
         result_q.put(("error", lane, traceback.format_exc()))
+
+
+@contextlib.contextmanager
+def _lanes(files, lanes, output_stem, slots_per_lane, slot_bytes, pin_bytes, pin, reader, writer, prepare, depth):
+    """What a lanes call owns, set up in the order that matters and taken down whatever happens inside the `with`: the image
+    files dealt over the lanes (groups, outputs: lane k's files and prediction file), prepare() on a thread from the first
+    moment, the shared-memory slots (slots[k], made beside it; the leading pin_bytes of each are page-locked when `pin`),
+    the queues (result_q: workers -> this process; free_qs[k]: slot numbers a reader may fill; write_qs[k]: -> the writer),
+    the reader and writer processes (procs; reader(h, k) / writer(h, k) -> the worker function and its arguments after
+    (lane, result_q)) and, for depth > 1 device passes at once, the thread pool they and their predictors run on."""
+    h = SimpleNamespace(t_begin=time.perf_counter(), groups=deal_files(files, max(1, lanes)), depth=depth)
+    h.lanes = len(h.groups)
+    h.outputs = [output_stem + ".hdf" if h.lanes == 1 else "%s_%d.hdf" % (output_stem, k) for k in range(h.lanes)]
+    ctx = get_context("spawn")
+    preparing = _Preparing(prepare)
+    try:
+        h.slots = make_slots(h.lanes, slots_per_lane, slot_bytes, pin_bytes)
+    except BaseException:
+        preparing.wait()
+        raise
+    h.result_q = ctx.Queue()
+    h.free_qs = [ctx.Queue() for _ in range(h.lanes)]
+    h.write_qs = [ctx.Queue() for _ in range(h.lanes)]
+    h.procs = []
+    h.pool = ThreadPoolExecutor(max_workers=depth) if depth > 1 else None
+    locker = None                 # bound before the try: the finally reads it when prepare() or a worker start raises
+    try:
+        for k in range(h.lanes):
+            for s in range(slots_per_lane):
+                h.free_qs[k].put(s)
+        for role in (reader, writer):            # the readers first: a process takes ~25 ms to start, the writers have time
+            for k in range(h.lanes):
+                fn, args = role(h, k)
+                h.procs.append(ctx.Process(target=_guarded, args=(fn, k, h.result_q, args), daemon=True))
+        _start_all(h.procs)
+        _trace(h.t_begin, "workers started")
+        preparing.join()           # e.g. the checkpoint loaded and the model built while the slots were made and the readers started
+        _trace(h.t_begin, "caller prepared")
+        # page-locking after prepare(): hipHostRegister holds the process's mm lock, and a model creation (hipMalloc,
+        # uploads) running beside it took 0.4 s instead of 0.07 s
+        locker = register_async(h.slots, pin and _have_gpu())
+        yield h
+        locker.join()
+        for p in h.procs:
+            p.join(timeout=60)
+        _trace(h.t_begin, "workers joined")
+    finally:
+        preparing.wait()
+        if h.pool is not None:
+            h.pool.shutdown(wait=True)
+        for p in h.procs:
+            if p.is_alive():
+                p.terminate()
+        for p in h.procs:
+            p.join(timeout=5)            # (terminated workers are reaped here: none outlives the call)
+        if locker is not None:
+            locker.join()
+        for s in h.slots:
+            s.close()
+
+
+def _device_loop(h, first, more, per_pass, call, retired, unit, rate=False):
+    """The GPU side of the lanes `h`: blocks (lane, slot, n, meta) arrive from the readers; up to h.depth device passes are
+    under way, each call(predictor, blocks) on up to per_pass of the oldest blocks (with h.depth == 1 on this thread,
+    otherwise on the pool, the passes going round over `first` and the predictors that more() builds beside the first pass);
+    passes retire oldest first -- retired(blocks, what call returned) hands the blocks on to their writers -- and a lane's
+    end marker follows that lane's last retired block.  A block of n == 0 (a reader's empty end-of-file block) keeps its
+    turn and runs nothing.  Returns the sum of what the writers reported with "write_done"."""
+    pool, depth = h.pool, h.depth
+    predictors = [first]
+    extra = [pool.submit(more) for _ in range(depth - 1)] if pool is not None else []    # built beside the first pass
+    pending = collections.deque()           # blocks received and not yet on the device, oldest first
+    inflight = collections.deque()          # (future or None, result when there is no future, [blocks]) passes under way, oldest first
+    read_done = set()                       # lanes whose end marker waits for their last blocks to retire
+    spans = []                              # (start, end, chunks or windows) of every device pass, for the trace
+    launched = written = 0
+    reading = writing = h.lanes
+
+    def run(predict, take):
+        t0 = time.perf_counter()
+        try:
+            return call(predict, take)
+        finally:
+            spans.append((t0, time.perf_counter(), sum(item[2] for item in take)))
+
+    def launch():
+        nonlocal launched
+        take = [pending.popleft() for _ in range(min(per_pass, len(pending)))]
+        if not any(item[2] for item in take):
+            inflight.append((None, None, take))
+            return
+        for lane, slot, _, _ in take:
+            h.slots[lane].ready(slot)
+        if launched == 0:
+            _trace(h.t_begin, "first block on the GPU")
+        if pool is None:
+            inflight.append((None, run(first, take), take))
+        else:
+            while len(predictors) < min(depth, launched + 1):
+                predictors.append(extra[len(predictors) - 1].result())
+            inflight.append((pool.submit(run, predictors[launched % len(predictors)], take), None, take))
+        launched += 1
+
+    def owed(lane):
+        return any(item[0] == lane for item in pending) or any(item[0] == lane for _, _, take in inflight for item in take)
+
+    def retire_finished():
+        while inflight and (inflight[0][0] is None or inflight[0][0].done()):
+            fut, result, take = inflight.popleft()
+            retired(take, result if fut is None else fut.result())
+            for lane in {item[0] for item in take} & read_done:
+                if not owed(lane):
+                    read_done.discard(lane)
+                    h.write_qs[lane].put(None)           # the end marker follows the lane's last block
+
+    def handle(msg):
+        nonlocal reading, writing, written
+        kind, lane = msg[0], msg[1]
+        if kind == "error":
+            raise (SlotTooSmall if "SlotTooSmall" in msg[2] else LaneError)("lane %d failed:\n%s" % (lane, msg[2]))
+        if kind == "block":
+            pending.append(msg[1:])
+        elif kind == "read_done":
+            reading -= 1
+            if owed(lane):
+                read_done.add(lane)
+            else:
+                h.write_qs[lane].put(None)
+        elif kind == "write_done":
+            writing -= 1
+            written += sum(msg[2:])                      # (the variant writers report their batch_<n> groups)
+
+    while writing:
+        # a pass costs about the same whatever it holds: the first of the passes under way takes what there is (an idle
+        # device is worse than a small pass), a further one starts only full -- or when nothing more is coming
+        while pending and len(inflight) < depth and (not inflight or len(pending) >= per_pass or reading == 0):
+            launch()
+            retire_finished()                             # (a pass on this thread is over when launch() returns)
+        # with passes under way, do not sleep on the queue past the moment the oldest one is done: its slots (freed when it
+        # retires, or by the writers) may be what the readers are waiting for
+        msg = _next_message(h.result_q, h.procs, poll=0.002 if inflight else None)
+        if msg is not None:
+            handle(msg)
+            while True:                                   # whatever else has arrived by now travels with it
+                try:
+                    handle(h.result_q.get_nowait())
+                except queue.Empty:
+                    break
+        # (after a message as well as after a quiet poll: a steady trickle of blocks must not keep a finished pass waiting)
+        retire_finished()
+    _trace(h.t_begin, "all lanes written")
+    if spans and os.environ.get("PEPPER_AMD_LANE_TRACE"):
+        busy, total = sum(b - a for a, b, _ in spans), sum(c for _, _, c in spans)
+        window = max(b for _, b, _ in spans) - spans[0][0]
+        sys.stderr.write("[lanes] %d device passes of %.0f %s and %.1f ms on average, %.2f of them at once over %.2f s%s\n"
+                         % (len(spans), total / len(spans), unit, 1e3 * busy / len(spans), busy / max(1e-9, window), window,
+                            " (%.2f M %s/s inside)" % (1e-6 * total / max(1e-9, window), unit) if rate else ""))
+    return written
 
 
 # ============================================================================================================
@@ -396,14 +556,6 @@ def _polish_writer(lane, result_q, output_filename, slot_names, layout_args, wri
         _close_all(segs)
 
 
-def polish_reader(lane, result_q, *args):
-    _guarded(_polish_reader, lane, result_q, args)
-
-
-def polish_writer(lane, result_q, *args):
-    _guarded(_polish_writer, lane, result_q, args)
-
-
 def polish_lanes(files, output_stem, predict_block, lanes, block=8192, seq_len=1000, features=10, slots_per_lane=3, log=None,
                  prepare=None, predict_parts=None, more_predict=None, in_flight=1, pass_blocks=1):
     """Run the polish predict loop over `files` with `lanes` reader/writer process pairs.
@@ -422,170 +574,37 @@ def polish_lanes(files, output_stem, predict_block, lanes, block=8192, seq_len=1
     buffers) -- that many passes are under way at once, each on its own thread (the library call releases the GIL), so
     that the copies of one lie beside the kernels of the other.  The first block does not wait for company.  Blocks reach
     a lane's writer in the order its reader produced them."""
-    t_begin = time.perf_counter()
-    groups = deal_files(files, max(1, lanes))
-    lanes = len(groups)
-    if lanes == 0:
+    if not files:
         return 0
     layout = PolishLayout(block, seq_len, features)
     largs = (block, seq_len, features)
-    ctx = get_context("spawn")
-    preparing = _Preparing(prepare)
-    try:
-        slots = make_slots(lanes, slots_per_lane, layout.nbytes, layout.pin_bytes)
-    except BaseException:
-        preparing.wait()
-        raise
-    result_q = ctx.Queue()
-    free_qs = [ctx.Queue() for _ in range(lanes)]
-    write_qs = [ctx.Queue() for _ in range(lanes)]
-    procs = []
     done = 0
-    locker = pool = None          # bound before the try: the finally reads them when prepare() or a worker start raises
-    try:
-        for k in range(lanes):
-            for s in range(slots_per_lane):
-                free_qs[k].put(s)
-            out = output_stem + ".hdf" if lanes == 1 else "%s_%d.hdf" % (output_stem, k)
-            procs.append(ctx.Process(target=polish_reader, args=(k, result_q, groups[k], slots[k].names, largs, free_qs[k]),
-                                     daemon=True))
-            procs.append(ctx.Process(target=polish_writer, args=(k, result_q, out, slots[k].names, largs, write_qs[k], free_qs[k]),
-                                     daemon=True))
-        _start_all(procs[0::2] + procs[1::2])    # the readers first: a process takes ~25 ms to start, the writers have time
-        _trace(t_begin, "workers started")
-        preparing.join()           # e.g. the checkpoint loaded and the model built while the slots were made and the readers started
-        _trace(t_begin, "caller prepared")
-        # page-locking after prepare(): hipHostRegister holds the process's mm lock, and a model creation (hipMalloc,
-        # uploads) running beside it took 0.4 s instead of 0.07 s
-        # PEPPER_AMD_POLISH_PIN=0: leave the slots pageable (the copies are then staged by the runtime; the path needs ~1 GB/s)
-        locker = register_async(slots, _have_gpu() and os.environ.get("PEPPER_AMD_POLISH_PIN", "1") != "0")
 
-        def one_by_one(parts):
-            for part in parts:
-                predict_block(*part)
-        depth = max(1, int(in_flight)) if more_predict is not None else 1
-        per_pass = max(1, int(pass_blocks))
-        predictors = [predict_parts if predict_parts is not None else one_by_one]
-        extra = []
-        if depth > 1:
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=depth)
-            extra = [pool.submit(more_predict) for _ in range(depth - 1)]    # built beside the first pass
-        pending = collections.deque()           # (lane, slot, n, meta) received and not yet on the device, oldest first
-        inflight = collections.deque()          # (future or None, [blocks]) passes under way, oldest first
-        read_done = set()                       # lanes whose end marker waits for their last blocks to retire
-        spans = []                              # (start, end, chunks) of every device pass, for the trace
-        launched = 0
-        writing = lanes
-
-        def run(predict, take):
-            views = [layout.views(slots[lane].segments[slot].buf, n) for lane, slot, n, _ in take]
-            t0 = time.perf_counter()
+    def one_by_one(predict_block):
+        return lambda parts: [predict_block(*part) for part in parts]
+    first = predict_parts if predict_parts is not None else one_by_one(predict_block)
+    more = more_predict if predict_parts is not None or more_predict is None else (lambda: one_by_one(more_predict()))
+    # PEPPER_AMD_POLISH_PIN=0: leave the slots pageable (the copies are then staged by the runtime; the path needs ~1 GB/s)
+    with _lanes(files, lanes, output_stem, slots_per_lane, layout.nbytes, layout.pin_bytes,
+                os.environ.get("PEPPER_AMD_POLISH_PIN", "1") != "0",
+                lambda h, k: (_polish_reader, (h.groups[k], h.slots[k].names, largs, h.free_qs[k])),
+                lambda h, k: (_polish_writer, (h.outputs[k], h.slots[k].names, largs, h.write_qs[k], h.free_qs[k])),
+                prepare, max(1, int(in_flight)) if more is not None else 1) as h:
+        def call(predict, take):
+            views = [layout.views(h.slots[lane].segments[slot].buf, n) for lane, slot, n, _ in take]
             try:
                 predict([(v[0], v[3], v[4]) for v in views])
             finally:
                 del views
-                spans.append((t0, time.perf_counter(), sum(item[2] for item in take)))
 
-        def launch():
-            nonlocal launched
-            take = [pending.popleft() for _ in range(min(per_pass, len(pending)))]
-            for lane, slot, _, _ in take:
-                slots[lane].ready(slot)
-            if launched == 0:
-                _trace(t_begin, "first block on the GPU")
-            if pool is None:
-                run(predictors[0], take)
-                inflight.append((None, take))
-            else:
-                while len(predictors) < min(depth, launched + 1):
-                    more = extra[len(predictors) - 1].result()
-                    predictors.append(more if predict_parts is not None else
-                                      (lambda parts, one=more: [one(*part) for part in parts]))
-                inflight.append((pool.submit(run, predictors[launched % len(predictors)], take), take))
-            launched += 1
-
-        def retire():
+        def retired(take, _):
             nonlocal done
-            fut, take = inflight.popleft()
-            if fut is not None:
-                fut.result()
             for lane, slot, n, meta in take:
-                write_qs[lane].put((slot, n, meta))
+                h.write_qs[lane].put((slot, n, meta))      # (the writer frees the slot)
                 done += n
             if log is not None:
                 log(done)
-            for lane in {item[0] for item in take} & read_done:
-                if all(item[0] != lane for item in pending) and all(item[0] != lane for _, blocks in inflight for item in blocks):
-                    read_done.discard(lane)
-                    write_qs[lane].put(None)             # the end marker follows the lane's last block
-
-        reading = lanes
-
-        def handle(msg):
-            nonlocal reading, writing
-            kind, lane = msg[0], msg[1]
-            if kind == "error":
-                raise (SlotTooSmall if "SlotTooSmall" in msg[2] else LaneError)("lane %d failed:\n%s" % (lane, msg[2]))
-            if kind == "block":
-                _, _, slot, n, meta = msg
-                pending.append((lane, slot, n, meta))
-            elif kind == "read_done":
-                reading -= 1
-                if any(item[0] == lane for item in pending) or any(item[0] == lane for _, blocks in inflight for item in blocks):
-                    read_done.add(lane)
-                else:
-                    write_qs[lane].put(None)
-            elif kind == "write_done":
-                writing -= 1
-
-        import queue
-        while writing:
-            # a pass costs about the same whatever it holds: the first of the passes under way takes what there is (an idle
-            # device is worse than a small pass), a further one starts only full -- or when nothing more is coming
-            while pending and len(inflight) < depth and (not inflight or len(pending) >= per_pass or reading == 0):
-                launch()
-                if pool is None:
-                    retire()
-            if not writing:
-                break
-            # with passes under way, do not sleep on the queue past the moment the oldest one is done: its slots (freed by
-            # the writers) may be what the readers are waiting for
-            msg = _next_message(result_q, procs, poll=0.002 if inflight else None)
-            if msg is not None:
-                handle(msg)
-                while True:                               # whatever else has arrived by now travels with it
-                    try:
-                        handle(result_q.get_nowait())
-                    except queue.Empty:
-                        break
-            # (after a message as well as after a quiet poll: a steady trickle of blocks must not keep a finished pass waiting)
-            while inflight and inflight[0][0].done():
-                retire()
-        _trace(t_begin, "all lanes written")
-        if spans and os.environ.get("PEPPER_AMD_LANE_TRACE"):
-            busy = sum(b - a for a, b, _ in spans)
-            sys.stderr.write("[lanes] %d device passes of %.0f chunks and %.1f ms on average, %.2f of them at once over %.2f s\n"
-                             % (len(spans), sum(c for _, _, c in spans) / len(spans), 1e3 * busy / len(spans),
-                                busy / max(1e-9, max(b for _, b, _ in spans) - spans[0][0]),
-                                max(b for _, b, _ in spans) - spans[0][0]))
-        locker.join()
-        for p in procs:
-            p.join(timeout=60)
-        _trace(t_begin, "workers joined")
-    finally:
-        preparing.wait()
-        if pool is not None:
-            pool.shutdown(wait=True)
-        for p in procs:
-            if p.is_alive():
-                p.terminate()
-        for p in procs:
-            p.join(timeout=5)            # (terminated workers are reaped here: none outlives the call)
-        if locker is not None:
-            locker.join()
-        for s in slots:
-            s.close()
+        _device_loop(h, first, more, max(1, int(pass_blocks)), call, retired, "chunks")
     return done
 
 
@@ -596,7 +615,7 @@ VARIANT_BLOCK_WINDOWS = 65536       # a reader hands over about this many window
 VARIANT_SLOT_BYTES = 3 * VARIANT_BLOCK_WINDOWS * 33 * 26 // 2      # a block plus the group that crosses the mark: 84 MB
 
 
-def _variant_reader(lane, result_q, image_directory, files, slot_names, slot_bytes, free_q, block_windows=VARIANT_BLOCK_WINDOWS):
+def _variant_reader(lane, result_q, files, slot_names, slot_bytes, free_q, block_windows=VARIANT_BLOCK_WINDOWS):
     """Files of the lane, in order; each file's summaries groups in name order (as SequenceDataset reads them), handed over
     in blocks of whole groups of about VARIANT_BLOCK_WINDOWS windows: the GPU starts after the first block, not after the
     first file, and a slot is a block, not a file."""
@@ -614,7 +633,7 @@ def _variant_reader(lane, result_q, image_directory, files, slot_names, slot_byt
                     blob, offsets, np.concatenate(freqs), (rows,) + tuple(shape))
         else:
             meta = None
-        result_q.put(("block", lane, slot, meta, file_end))
+        result_q.put(("block", lane, slot, rows, (meta, file_end)))
 
     try:
         for path in files:
@@ -710,14 +729,6 @@ def _variant_writer(lane, result_q, output_filename, batch_size, write_q):
         store.close()
 
 
-def variant_reader(lane, result_q, *args):
-    _guarded(_variant_reader, lane, result_q, args)
-
-
-def variant_writer(lane, result_q, *args):
-    _guarded(_variant_writer, lane, result_q, args)
-
-
 def variant_lanes(image_directory, files, output_stem, forward_block, batch_size, lanes, slots_per_lane=0, log=None,
                   block_windows=VARIANT_BLOCK_WINDOWS, prepare=None, second_forward=None):
     """Run the variant predict loop over `files` with `lanes` reader/writer process pairs.
@@ -729,145 +740,36 @@ def variant_lanes(image_directory, files, output_stem, forward_block, batch_size
     own bookkeeping no longer sit between device passes; results still reach a lane's writer in block order.  Output: `<output_stem>.hdf` for one lane, `<output_stem>_<lane>.hdf`
     otherwise; batch_<n> numbering runs over the files of a lane, as it runs over the files of a caller in the reference
     (predict_distributed_gpu.py:40-67).  Returns (batches written, windows processed)."""
-    t_begin = time.perf_counter()
-    groups = deal_files(files, max(1, lanes))
-    lanes = len(groups)
-    if lanes == 0:
+    if not files:
         return 0, 0
     # a slot holds one block of whole groups: block_windows windows plus room for the group that crosses the mark (a file
     # smaller than that needs only its own size; a single group larger than a slot raises SlotTooSmall).  Small slots
     # matter: page-locking holds the process's mm lock, and 4 GB of it slowed the concurrent checkpoint load by 0.5 s
     slot_bytes = min(max(os.path.getsize(f) for f in files), max(VARIANT_SLOT_BYTES, 3 * block_windows * 33 * 26 // 2))
-    if slots_per_lane <= 0:
-        slots_per_lane = 2
-    ctx = get_context("spawn")
-    preparing = _Preparing(prepare)
-    try:
-        slots = make_slots(lanes, slots_per_lane, slot_bytes)
-    except BaseException:
-        preparing.wait()
-        raise
-    result_q = ctx.Queue()
-    free_qs = [ctx.Queue() for _ in range(lanes)]
-    write_qs = [ctx.Queue() for _ in range(lanes)]
-    procs = []
-    windows = batches = 0
-    locker = None
-    pool = second = None          # bound before the try: the finally reads them when prepare() or a worker start raises
-    try:
-        for k in range(lanes):
-            for s in range(slots_per_lane):
-                free_qs[k].put(s)
-            out = output_stem + ".hdf" if lanes == 1 else "%s_%d.hdf" % (output_stem, k)
-            procs.append(ctx.Process(target=variant_reader, args=(k, result_q, image_directory, groups[k], slots[k].names,
-                                                                   slot_bytes, free_qs[k], block_windows), daemon=True))
-            procs.append(ctx.Process(target=variant_writer, args=(k, result_q, out, batch_size, write_qs[k]), daemon=True))
-        _start_all(procs)
-        _trace(t_begin, "workers started")
-        preparing.join()           # e.g. the checkpoint loaded and the model built while the slots were made and the readers started
-        _trace(t_begin, "caller prepared")
-        # page-locking after prepare(): hipHostRegister holds the process's mm lock, and a model creation (hipMalloc,
-        # uploads) running beside it took 0.4 s instead of 0.07 s
-        locker = register_async(slots, _have_gpu())
-        writing = lanes
-        files_done = 0
-        forwards = [forward_block]
-        if second_forward is not None:
-            from concurrent.futures import ThreadPoolExecutor
-            pool = ThreadPoolExecutor(max_workers=2)
-            second = pool.submit(second_forward)        # built beside the first block's device pass
-        inflight = collections.deque()                  # (future or None, lane, slot, meta, file_end), oldest first
-        submitted = 0
-
-        spans = []                                       # (start, end, windows) of every device pass, for the trace
-
-        def run(forward, lane, slot, shape):
-            images = slots[lane].view(slot, 0, shape, np.int8)
-            t0 = time.perf_counter()
+    windows = files_done = 0
+    with _lanes(files, lanes, output_stem, slots_per_lane if slots_per_lane > 0 else 2, slot_bytes, None, True,
+                lambda h, k: (_variant_reader, (h.groups[k], h.slots[k].names, slot_bytes, h.free_qs[k], block_windows)),
+                lambda h, k: (_variant_writer, (h.outputs[k], batch_size, h.write_qs[k])),
+                prepare, 2 if second_forward is not None else 1) as h:
+        def call(forward, take):                  # one block per pass; its meta: (the reader's arrays or None, file_end)
+            (lane, slot, _, (meta, _)), = take
+            images = h.slots[lane].view(slot, 0, meta[6], np.int8)
             try:
                 return np.asarray(forward(images))
             finally:
                 del images
-                spans.append((t0, time.perf_counter(), shape[0]))
 
-        def retire():
+        def retired(take, probs):
             nonlocal windows, files_done
-            fut, lane, slot, meta, file_end = inflight.popleft()
-            if meta is not None:
-                contigs, positions, depths, blob, offsets, freqs, shape = meta
-                probs = fut.result() if pool is not None else fut
-                write_qs[lane].put(((contigs, positions, depths, blob, offsets, freqs, probs), file_end))
-                windows += shape[0]
-            else:
-                write_qs[lane].put((None, file_end))
-            free_qs[lane].put(slot)                       # the forward has consumed the images
+            (lane, slot, n, (meta, file_end)), = take
+            h.write_qs[lane].put((meta[:6] + (probs,) if n else None, file_end))
+            h.free_qs[lane].put(slot)             # the forward has consumed the images
+            windows += n
             if file_end:
                 files_done += 1
                 if log is not None:
                     log(files_done)
-
-        depth = 2 if pool is not None else 1
-        while writing:
-            # with passes in flight, do not sleep on the queue past the moment the oldest one is done: its slot may be what
-            # the only reader still running is waiting for
-            msg = _next_message(result_q, procs, poll=0.002 if inflight else None)
-            if msg is None:
-                while inflight and (inflight[0][0] is None or pool is None or inflight[0][0].done()):
-                    retire()
-                continue
-            kind, lane = msg[0], msg[1]
-            if kind == "error":
-                raise (SlotTooSmall if "SlotTooSmall" in msg[2] else LaneError)("lane %d failed:\n%s" % (lane, msg[2]))
-            if kind == "block":
-                _, _, slot, meta, file_end = msg
-                while len(inflight) >= depth:
-                    retire()
-                fut = None
-                if meta is not None:
-                    slots[lane].ready(slot)
-                    if submitted == 0:
-                        _trace(t_begin, "first block on the GPU")
-                    if pool is None:
-                        fut = run(forward_block, lane, slot, meta[6])
-                    else:
-                        if submitted == 1:
-                            forwards.append(second.result())
-                        fut = pool.submit(run, forwards[submitted % len(forwards)], lane, slot, meta[6])
-                    submitted += 1
-                inflight.append((fut, lane, slot, meta, file_end))
-                if pool is None:
-                    retire()
-            elif kind == "read_done":
-                while inflight:                          # the end marker follows the lane's last block
-                    retire()
-                write_qs[lane].put(None)
-            elif kind == "write_done":
-                writing -= 1
-                batches += msg[2]
-        _trace(t_begin, "all lanes written")
-        if spans and os.environ.get("PEPPER_AMD_LANE_TRACE"):
-            busy = sum(b - a for a, b, _ in spans)
-            window = max(b for _, b, _ in spans) - spans[0][0]
-            sys.stderr.write("[lanes] %d device passes of %.0f windows and %.1f ms on average, %.2f of them at once over %.2f s "
-                             "(%.2f M windows/s inside)\n" % (len(spans), sum(c for _, _, c in spans) / len(spans), 1e3 * busy / len(spans),
-                                                              busy / max(1e-9, window), window, 1e-6 * sum(c for _, _, c in spans) / max(1e-9, window)))
-        locker.join()
-        for p in procs:
-            p.join(timeout=60)
-        _trace(t_begin, "workers joined")
-    finally:
-        preparing.wait()
-        if pool is not None:
-            pool.shutdown(wait=True)
-        for p in procs:
-            if p.is_alive():
-                p.terminate()
-        for p in procs:
-            p.join(timeout=5)            # (terminated workers are reaped here: none outlives the call)
-        if locker is not None:
-            locker.join()
-        for s in slots:
-            s.close()
+        batches = _device_loop(h, forward_block, second_forward, 1, call, retired, "windows", rate=True)
     return batches, windows
 
 

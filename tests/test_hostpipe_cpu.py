@@ -66,6 +66,7 @@ def test_variant_lanes_write_what_the_in_process_loop_writes(tmp_path, in_flight
     # writers must still cut batches of 256 per FILE exactly like the in-process loop (345 -> 256 + 89, 700 -> 256 + 256 + 188).
     # in_flight = 2: two blocks on the device path at once (two handles on two threads); a lane's writer must still see its
     # blocks in order
+    before = {n for n in os.listdir("/dev/shm") if n.startswith("psm_")}
     batches, windows = hostpipe.variant_lanes(str(tmp_path), files, str(out / "pepper_prediction"), _fake_forward, 256, lanes=2,
                                               block_windows=100,
                                               second_forward=(lambda: _slow_fake_forward) if in_flight == 2 else None)
@@ -98,7 +99,8 @@ def test_variant_lanes_write_what_the_in_process_loop_writes(tmp_path, in_flight
     assert sorted(got_comp) == sorted(want_comp) and sorted(len(c) for c in want_comp) == [17, 89, 124, 188, 256, 256, 256, 256]
     assert set(want) == set(got) and len(want) == windows
     assert all(np.array_equal(want[k], got[k]) for k in want)
-    assert not [n for n in os.listdir("/dev/shm") if n.startswith("psm_")] or True     # segments are unlinked by Slots.close
+    assert {n for n in os.listdir("/dev/shm") if n.startswith("psm_")} == before      # segments are unlinked by Slots.close
+    assert not [p for p in __import__("multiprocessing").active_children() if p.is_alive()]
 
 
 @pytest.mark.parametrize("mode", ["one block per pass", "gathered passes, two under way", "gathered passes, one under way"])
@@ -139,6 +141,7 @@ def test_polish_lanes_write_what_the_in_process_loop_writes(tmp_path, mode):
     def more_predict():
         made.append(len(made) + 1)
         return parts_predictor("extra%d" % len(made))
+    before = {n for n in os.listdir("/dev/shm") if n.startswith("psm_")}
     if mode == "one block per pass":
         done = hostpipe.polish_lanes(files, str(out / "pepper_prediction_0"), fake_predict, lanes=3, block=4, slots_per_lane=2)
     else:
@@ -150,6 +153,8 @@ def test_polish_lanes_write_what_the_in_process_loop_writes(tmp_path, mode):
         assert any(len(sizes) > 1 for _, sizes in passes)                  # blocks did travel together
         assert len(made) == depth - 1 and ({t for t, _ in passes} == {"first", "extra1"} if depth > 1 else True)
     assert done == 23
+    assert {n for n in os.listdir("/dev/shm") if n.startswith("psm_")} == before
+    assert not [p for p in __import__("multiprocessing").active_children() if p.is_alive()]
     produced = sorted(os.listdir(out))
     assert produced == ["pepper_prediction_0_%d.hdf" % k for k in range(3)]
 
