@@ -137,6 +137,20 @@ int pa_encoder_set_host_threads(pa_encoder* e, int32_t n);
 /* Reads with at least one base inside each region of the last run -- the reference's len(all_reads) after get_reads (an
  * interval without any writes no summary group, AlignmentSummarizer.py:200-204); host-clipped form: the pileup's n_reads. */
 int pa_encoder_region_reads(pa_encoder* e, int32_t* n_reads, int32_t n);
+/* The reference's reservoir sample of deep intervals, drawn ON THE DEVICE for the packed forms (pa_encoder_run_staged after
+ * pa_encoder_stage_packed, pa_polish_chain_run): an interval whose n reads with a base inside exceed
+ * k = int(min(max_reads, rate * n)) keeps the k reads numpy.random.RandomState(seed) picks in read order
+ * (AlignmentSummarizer.py: 192-199 variant, 314-326 polish; csrc/reservoir.h), between the clip and everything that reads the
+ * pairs (reservoir_keep_kernel: one workgroup per such interval).  The region-read counts are then those AFTER sampling; an
+ * interval with k == 0 keeps nothing.  Off at creation; takes effect from the handle's next run; max_reads == 0 switches it
+ * off again, 1 <= max_reads <= 5000 (the slots live in LDS), rate >= 0 (the polish caller gives 1.0: k = max_reads).  The
+ * kernel is not launched for a call in which no interval can need it (rate >= 1 and no interval with more than max_reads pairs).
+ * pa_encoder_sampled_regions: intervals sampled and reads dropped by this handle since it was created (either may be NULL).
+ * pa_encoder_pair_live: keep[p] = 1 where (read, region) pair p of the last packed batch still counts as a read of its interval
+ * (a base inside and, if the interval was sampled, kept), for the first n pairs. */
+int pa_encoder_set_sampling(pa_encoder* e, uint32_t seed, int32_t max_reads, double rate);
+int pa_encoder_sampled_regions(pa_encoder* e, int64_t* regions, int64_t* reads_dropped);
+int pa_encoder_pair_live(pa_encoder* e, uint8_t* keep, int64_t n);
 
 /* Times of the last run in milliseconds, HIP events on the encoder's stream: [0] record kernels (segment_reads x 2 +
  * tile_offsets), [1] tile_count_kernel, [2] compact_votes_kernel + pack_results_kernel, [3] gather_windows_kernel; host clock:
@@ -204,7 +218,8 @@ int pa_polish_encoder_last_timing(pa_encoder* e, double* ms, int32_t n);
  *   realign      realignment_flag of create_summary
  * Outputs (any may be NULL): n_rows[r] summary rows, region_reads[r] = the reference's len(all_reads), n_chunks[r] (0 for a
  * region without reads: it writes nothing), *total_chunks.  The reservoir sample of a region with more than
- * MAX_READS_IN_REGION reads is the caller's business (such a region goes through the per-region entry points).
+ * MAX_READS_IN_REGION reads is drawn on the device when pa_encoder_set_sampling has switched it on (region_reads[r] is then
+ * the count after sampling); without it such a region is the caller's business (the per-region entry points).
  * PA_ERR_UNSUPPORTED: a batch this form does not take (an operation of 2^24 bases, a read that keeps more than 2 L + 64 bases
  * of a region of L positions): nothing was produced, take the host-clipped form.
  * ------------------------------------------------------------------------------------------ */

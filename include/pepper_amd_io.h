@@ -336,6 +336,12 @@ int pa_bam_pack_inflated(pa_bam* b, const uint8_t* data, int64_t data_bytes, int
                          int32_t include_supplementary, int32_t min_mapq, pa_packed_read* reads, int32_t reads_cap,
                          int32_t* pair_read, int32_t pairs_cap, int32_t* region_pairs, int32_t* n_done, int64_t* counts);
 
+/* The reservoir sample the reference draws over an interval's reads (AlignmentSummarizer.py: numpy.random.RandomState(seed),
+ * randint(0, i + 1) per read i >= k, in read order): slots[0 .. min(n, k)) = the read kept in each slot.  The same inline
+ * functions (csrc/reservoir.h) run in reservoir_keep_kernel on the device; this entry point is their host build, what the
+ * tests compare both with.  k > n keeps every read; returns 0, or -1 for a negative count or a NULL slots with k > 0. */
+int pa_reservoir_sample(uint32_t seed, int64_t n, int64_t k, int32_t* slots);
+
 #ifdef __cplusplus
 }
 #endif

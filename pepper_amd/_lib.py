@@ -80,6 +80,9 @@ SYMBOLS = [
                                                ctypes.POINTER(c_int64), c_void_p]),
     ("pa_encoder_region_reads", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_set_host_threads", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_encoder_set_sampling", ctypes.c_int, [c_void_p, ctypes.c_uint32, c_int32, c_double]),
+    ("pa_encoder_sampled_regions", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    ("pa_encoder_pair_live", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_encoder_last_timing", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_batch_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_get_results", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -179,6 +182,21 @@ def batch_invariant_default(value=None):
     if value is not None:
         return parse_batch_invariant(value)
     return parse_batch_invariant(os.environ.get(BATCH_INVARIANT_ENV))
+
+
+def reservoir_sample(seed, n, k):
+    """pa_reservoir_sample (include/pepper_amd_io.h; exported by the I/O library, bound in pepper_amd/variant/bam.py): the
+    slots of the reference's reservoir sample of n reads down to k, as the device draws it."""
+    from pepper_amd.variant import bam
+    return bam.reservoir_sample(seed, n, k)
+
+
+DEVICE_SAMPLING_ENV = "PEPPER_AMD_DEVICE_SAMPLING"
+
+
+def device_sampling():
+    """PEPPER_AMD_DEVICE_SAMPLING=0: the image-generation drivers send sampled intervals through their host forms again."""
+    return os.environ.get(DEVICE_SAMPLING_ENV, "1") != "0"
 
 
 def check(rc):

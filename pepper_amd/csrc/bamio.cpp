@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/pepper_amd_io.h"
+#include "reservoir.h"
 
 namespace {
 
@@ -1201,6 +1202,13 @@ int pa_bam_copy_reads(pa_bam* b, int64_t* pos, int64_t* pos_end, uint8_t* revers
     cp(cigar_op, rs.cigar_op.data(), rs.cigar_op.size() * 4);
     cp(cigar_len, rs.cigar_len.data(), rs.cigar_len.size() * 4);
     cp(names, rs.names.data(), rs.names.size());
+    return 0;
+}
+
+// the host build of the sampler reservoir_keep_kernel runs on the device (reservoir.h)
+int pa_reservoir_sample(uint32_t seed, int64_t n, int64_t k, int32_t* slots) {
+    if (n < 0 || k < 0 || n > 0x7fffffff || (!slots && k > 0 && n > 0)) return -1;
+    pa_reservoir_sample_serial(seed, n, k, slots);
     return 0;
 }
 

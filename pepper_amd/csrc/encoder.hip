@@ -41,6 +41,7 @@
 
 #include "../../include/pepper_amd_realign.h"
 #include "encoder_common.h"
+#include "reservoir.h"
 
 using namespace pa_enc;
 
@@ -293,6 +294,100 @@ __global__ __launch_bounds__(256) void unpack_clip_kernel(UnpackArgs a) {
         const uint8_t* q = quals + bidx;
         qual_out[j] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24);
     }
+}
+
+// ---- the reservoir sample of a deep interval (include/pepper_amd_encoder.h, pa_encoder_set_sampling) ------------------------
+// The reference samples an interval's reads down to k = int(min(cap, rate * n)) with numpy.random.RandomState(seed) over the
+// reads in read order (AlignmentSummarizer.py); n = the reads with a base inside, which only the clip kernel above knows.
+// One workgroup per interval that can need it, between the clip and everything that reads the pairs: count the live pairs,
+// run the sampler of reservoir.h (the generator's 624 words and the k <= 5000 slots in LDS; the whole workgroup regenerates
+// and tempers the state -- three data-parallel stretches and the last word -- and ONE lane draws: n - k reads, 1 to 2 words
+// each, in order; DESIGN.md 4.11 has what that costs), then clear every live pair whose rank is in no slot exactly as the
+// clip kernel leaves a pair that keeps nothing.  The kept SET is what the later stages see (every count downstream is a sum
+// over reads).
+struct SampRec { int32_t region, pair0, pair1, pad; };
+constexpr int RS_T = 256;            // threads of a workgroup: a stretch of the regeneration (227 words) fits one pass
+constexpr int RS_CAP = 5000;         // slots in LDS: the largest max_reads pa_encoder_set_sampling takes
+static_assert(PA_MT_S1 <= RS_T && PA_MT_S3 - PA_MT_S2 <= RS_T, "one regeneration stretch per pass of the workgroup");
+
+__global__ __launch_bounds__(RS_T) void reservoir_keep_kernel(const SampRec* __restrict__ tab, ReadRec* __restrict__ reads,
+                                                              int* __restrict__ live, uint8_t* __restrict__ keep,
+                                                              int2* __restrict__ out, uint32_t seed, int cap, double rate) {
+    __shared__ uint32_t mt[PA_MT_N], words[PA_MT_N];
+    __shared__ int32_t slots[RS_CAP];
+    __shared__ int wsum[RS_T / 64];
+    __shared__ int s_n;
+    __shared__ long long s_i;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const SampRec rec = tab[blockIdx.x];
+    // n = the interval's reads: pairs that kept a base (ReadRec.slen = written > 0)
+    if (tid == 0) s_n = 0;
+    __syncthreads();
+    int c = 0;
+    for (int p = rec.pair0 + tid; p < rec.pair1; p += RS_T) c += reads[p].slen > 0 ? 1 : 0;
+    c = wave_sum(c);
+    if (lane == 0) atomicAdd(&s_n, c);
+    __syncthreads();
+    const int n = s_n;
+    const int k = (int)pa_reservoir_allowed(cap, rate, n);      // (<= cap <= RS_CAP)
+    if (tid == 0) out[blockIdx.x] = make_int2(n, n > k ? k : n);
+    if (n <= k) return;                                          // nothing to do: the interval stays as the clip left it
+    if (k > 0) {
+        for (int i = tid; i < k; i += RS_T) slots[i] = i;
+        if (tid == 0) {
+            pa_mt_seed(mt, seed);
+            s_i = k;
+        }
+        __syncthreads();
+        for (;;) {
+            for (int s = 0; s < 3; ++s) {
+                const int lo = s == 0 ? 0 : (s == 1 ? PA_MT_S1 : PA_MT_S2), hi = s == 0 ? PA_MT_S1 : (s == 1 ? PA_MT_S2 : PA_MT_S3);
+                const int kk = lo + tid;
+                uint32_t word = 0;
+                if (kk < hi) word = pa_mt_twist_word(mt[kk], mt[kk + 1], mt[pa_mt_far(kk)]);
+                __syncthreads();                                 // (word kk + 1 is read before its owner replaces it)
+                if (kk < hi) mt[kk] = word;
+                __syncthreads();
+            }
+            if (tid == 0) mt[PA_MT_N - 1] = pa_mt_twist_word(mt[PA_MT_N - 1], mt[0], mt[PA_MT_M - 1]);
+            __syncthreads();
+            for (int p = tid; p < PA_MT_N; p += RS_T) words[p] = pa_mt_temper(mt[p]);
+            __syncthreads();
+            if (tid == 0) {
+                int at = 0;
+                s_i = pa_reservoir_draw(words, PA_MT_N, &at, s_i, n, k, slots);
+            }
+            __syncthreads();
+            if (s_i >= n) break;
+        }
+    }
+    // ranks in a slot, then the pairs in pair order again: a live pair whose rank is in none is cleared
+    uint8_t* kp = keep + rec.pair0;
+    for (int i = tid; i < n; i += RS_T) kp[i] = 0;
+    __syncthreads();
+    for (int i = tid; i < k; i += RS_T) kp[slots[i]] = 1;
+    __syncthreads();
+    int carry = 0;
+    for (int base = rec.pair0; base < rec.pair1; base += RS_T) {
+        const int p = base + tid;
+        const int v = (p < rec.pair1 && reads[p].slen > 0) ? 1 : 0;
+        const int inc = wave_inclusive_sum(v);
+        if (lane == 63) wsum[w] = inc;
+        __syncthreads();
+        int before = carry, total = 0;
+        for (int q = 0; q < RS_T / 64; ++q) {
+            if (q < w) before += wsum[q];
+            total += wsum[q];
+        }
+        if (v && !kp[before + inc - 1]) {
+            reads[p].ncig = 0;
+            reads[p].slen = 0;
+            reads[p].flags &= READ_REV;
+        }
+        carry += total;
+        __syncthreads();
+    }
+    if (tid == 0) live[rec.region] = k;
 }
 
 // exclusive scan of the per-tile record counts (one workgroup; tiles per batch: 12.5 k for 64 regions of 100 kb)
@@ -1016,6 +1111,8 @@ struct pa_variant_batch {
     int n_tiles = 0, W = 33, F = 26, mid = 16;
     int rec_cap = 0, ovf_cap = 0, pool_cap = 0;
     bool staged = false, packed = false;
+    bool sampled = false;             // the staged packed batch has been through pa_enc::sample_pairs
+    int64_t last_pairs = 0;           // (read, region) pairs of the last packed batch / chain run (in d_reads)
     DBuf d_seq, d_qual, d_ref, d_cig_op, d_cig_len, d_reads, d_regions, d_tile_region;
     // the tables of the staged batch as the kernels get them: the buffers above (pa_encoder_stage_batch) or slices of d_meta
     // (pa_encoder_stage_packed, one upload for all of them)
@@ -1492,6 +1589,8 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
     b.pool_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(4096, b.total_ops / 64));
     b.live.assign((size_t)n_regions, 0);
     b.packed = true;
+    b.sampled = false;
+    b.last_pairs = n_pairs;
     b.staged = true;
     return PA_OK;
 }
@@ -1525,6 +1624,14 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     if (!b.h_counts.ensure(((size_t)CT_N + 2 * (size_t)n_regions + 1) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
     int* host_counters = b.h_counts.as<int>();                  // [CT_N] | per-region counts | records
     const int* host_rc = host_counters + CT_N;
+    if (b.packed && !b.sampled) {     // deep intervals sampled down before anything reads the pairs (once per staged batch)
+        std::vector<int32_t> region_pairs((size_t)n_regions + 1);
+        for (int r = 0; r < n_regions; ++r) region_pairs[(size_t)r] = (int32_t)b.regs[(size_t)r].read_base;
+        region_pairs[(size_t)n_regions] = (int32_t)b.total_reads;
+        const int rc = pa_enc::sample_pairs(e, n_regions, region_pairs.data(), b.d_reads.as<ReadRec>(), b.d_live.as<int>(), b.h_live.as<int>());
+        if (rc != PA_OK) return rc;
+        b.sampled = true;
+    }
     for (int attempt = 0;; ++attempt) {
         ENC_ALLOC(b.d_sorted, (size_t)b.rec_cap * sizeof(TileRec));
         ENC_ALLOC(b.d_ovf, (size_t)b.ovf_cap * sizeof(int4));
@@ -1602,6 +1709,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         (void)hipEventElapsedTime(&ms, e->ev[7], e->ev[8]); b.ms[9] = ms;   // unpack_clip_kernel
     }
     if (b.packed) {               // what unpack_clip_kernel reported while the batch was staged (the copy is long done)
+        pa_enc::sample_collect(e);
         const int* hl = b.h_live.as<int>();
         if (hl[n_regions] > 0)
             return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(hl[n_regions] - 1) + ": its CIGAR walks over more bases than the record holds");
@@ -1712,6 +1820,45 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
 
 }  // namespace
 
+int pa_enc::sample_pairs(pa_encoder* e, int32_t n_regions, const int32_t* region_pairs, ReadRec* d_reads, int* d_live, int* h_live) {
+    pa_sampler& s = e->sampler;
+    s.pending = 0;
+    if (!s.on || n_regions <= 0) return PA_OK;
+    // an interval can need the sample when rate * n < n for some n it may have, or when it has more pairs than the cap
+    std::vector<SampRec> tab;
+    for (int r = 0; r < n_regions; ++r) {
+        const int32_t pairs = region_pairs[r + 1] - region_pairs[r];
+        if (pairs > 0 && (s.rate < 1.0 || pairs > s.cap)) tab.push_back(SampRec{r, region_pairs[r], region_pairs[r + 1], 0});
+    }
+    if (tab.empty()) return PA_OK;
+    const size_t c = tab.size(), o_out = c * sizeof(SampRec), bytes = o_out + c * sizeof(int2);
+    if (!s.h_tab.ensure(bytes)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_ALLOC(s.d_tab, bytes);
+    ENC_ALLOC(s.d_keep, (size_t)region_pairs[n_regions] + 64);
+    std::memcpy(s.h_tab.p, tab.data(), o_out);
+    hipStream_t st = e->stream;
+    char* dt = s.d_tab.as<char>();
+    ENC_HIP(hipMemcpyAsync(dt, s.h_tab.p, o_out, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(reservoir_keep_kernel, dim3((unsigned)c), dim3(RS_T), 0, st, reinterpret_cast<const SampRec*>(dt), d_reads, d_live,
+                       s.d_keep.as<uint8_t>(), reinterpret_cast<int2*>(dt + o_out), s.seed, (int)s.cap, s.rate);
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipMemcpyAsync(s.h_tab.as<char>() + o_out, dt + o_out, c * sizeof(int2), hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipMemcpyAsync(h_live, d_live, ((size_t)n_regions + 2) * 4, hipMemcpyDeviceToHost, st));
+    s.pending = (int)c;
+    return PA_OK;
+}
+
+void pa_enc::sample_collect(pa_encoder* e) {
+    pa_sampler& s = e->sampler;
+    const int2* out = reinterpret_cast<const int2*>(s.h_tab.as<char>() + (size_t)s.pending * sizeof(SampRec));
+    for (int k = 0; k < s.pending; ++k)
+        if (out[k].y < out[k].x) {
+            s.regions += 1;
+            s.dropped += out[k].x - out[k].y;
+        }
+    s.pending = 0;
+}
+
 // The packed reads of a batch of regions clipped and decoded on the device WITHOUT the variant encoder's tables: what the polish
 // image chain (encoder_polish.hip) starts from.  Same arena / read / pair tables as stage_packed, same kernel; the regions are
 // given by their bounds alone.  Nothing here waits for the device.
@@ -1805,10 +1952,12 @@ int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_
     out->cigar_op = b.d_cig_op.as<int32_t>();
     out->cigar_len = b.d_cig_len.as<int32_t>();
     out->seq = b.d_seq.as<char>();
+    b.last_pairs = n_pairs;
     out->n_pairs = n_pairs;
     out->total_bases = total_bases;
     out->total_ops = total_ops;
     out->extra_ops = extra_ops;
+    out->d_live = b.d_live.as<int>();
     out->h_live = b.h_live.as<int>();
     return PA_OK;
 }
@@ -2020,6 +2169,36 @@ int pa_encoder_set_host_threads(pa_encoder* e, int32_t n) {
 int pa_encoder_region_reads(pa_encoder* e, int32_t* n_reads, int32_t n) {
     if (!e || !n_reads || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
     for (int i = 0; i < n; ++i) n_reads[i] = (e->variant && i < (int)e->variant->live.size()) ? e->variant->live[(size_t)i] : 0;
+    return PA_OK;
+}
+
+int pa_encoder_set_sampling(pa_encoder* e, uint32_t seed, int32_t max_reads, double rate) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (max_reads < 0 || max_reads > RS_CAP || !(rate >= 0.0))
+        return pa::set_error(PA_ERR_INVALID, "sampling: 0 <= max_reads <= 5000 (0 switches it off) and rate >= 0");
+    e->sampler.on = max_reads > 0;
+    e->sampler.seed = seed;
+    e->sampler.cap = max_reads;
+    e->sampler.rate = rate;
+    return PA_OK;
+}
+
+int pa_encoder_sampled_regions(pa_encoder* e, int64_t* regions, int64_t* reads_dropped) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (regions) *regions = e->sampler.regions;
+    if (reads_dropped) *reads_dropped = e->sampler.dropped;
+    return PA_OK;
+}
+
+int pa_encoder_pair_live(pa_encoder* e, uint8_t* keep, int64_t n) {
+    if (!e || n < 0 || (n > 0 && !keep)) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!e->variant || n > e->variant->last_pairs) return pa::set_error(PA_ERR_INVALID, "no packed batch with that many pairs");
+    if (n == 0) return PA_OK;
+    ENC_HIP(hipSetDevice(e->device));
+    std::vector<ReadRec> reads((size_t)n);
+    ENC_HIP(hipMemcpyAsync(reads.data(), e->variant->d_reads.p, (size_t)n * sizeof(ReadRec), hipMemcpyDeviceToHost, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    for (int64_t p = 0; p < n; ++p) keep[p] = reads[(size_t)p].slen > 0 ? 1 : 0;
     return PA_OK;
 }
 

@@ -139,6 +139,19 @@ constexpr int READ_REV = 1, READ_MAPQ_OK = 2;
         if (!(buf).ensure(bytes_)) return pa::set_error(PA_ERR_HIP, "hipMalloc failed in encoder workspace"); \
     } while (0)
 
+// The reservoir sample of deep intervals (pa_encoder_set_sampling; reservoir_keep_kernel in encoder.hip): the handle's
+// setting, its counters and the small tables of a launch.
+struct pa_sampler {
+    bool on = false;
+    uint32_t seed = 0;
+    int32_t cap = 0;                 // MAX_READS_IN_REGION of the caller
+    double rate = 1.0;               // downsample_rate (polish: 1.0)
+    int64_t regions = 0, dropped = 0;     // intervals sampled / reads dropped since the handle was created
+    int pending = 0;                 // intervals of the last launch whose {n, kept} have not been added to the counters yet
+    pa_enc::DBuf d_tab, d_keep;      // [SampRec x c][int2 x c] | one byte per (interval, rank): in a slot
+    pa_enc::HBuf h_tab;
+};
+
 struct pa_variant_batch;     // encoder.hip
 struct pa_polish_batch;      // encoder_polish.hip
 
@@ -150,6 +163,7 @@ struct pa_encoder {
     pa_variant_batch* variant = nullptr;
     pa_polish_batch* polish = nullptr;
     struct pa_realigner* realigner = nullptr;      // the polish image chain's re-aligner on this encoder's stream (made on first use)
+    pa_sampler sampler;
 };
 
 // ---- the polish image chain (encoder_polish.hip: pa_polish_chain_*) crosses the three files; the pieces it calls --------------
@@ -164,12 +178,20 @@ struct UnpackedReads {
     int32_t* cigar_len = nullptr;
     const char* seq = nullptr;
     int64_t n_pairs = 0, total_bases = 0, total_ops = 0, extra_ops = 0;      // slots the pairs were given (bounds of what they use)
+    int* d_live = nullptr;           // the same three on the device
     const int* h_live = nullptr;     // page-locked [n_regions + 2], valid once the stream has been waited for: reads with a base
                                      // inside each region | first inconsistent read + 1 | first unsupported read + 1
 };
 int unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_t* region_start, const int64_t* region_end,
                           const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads,
                           const int32_t* pair_read, const int32_t* region_pairs, int32_t extra_ops_per_pair, UnpackedReads* out);
+// The reservoir sample over the pairs unpack_clip_kernel has just clipped (same stream, nothing waits): one workgroup of
+// reservoir_keep_kernel per interval that can need it -- none, and no launch, when sampling is off or (rate >= 1 and every
+// interval has at most `cap` pairs).  It clears the pairs that fall out of the sample the way the clip kernel marks a pair
+// without a base inside, sets d_live[r] to the kept count and copies d_live to h_live again.  sample_collect: once the stream
+// has been waited for, the launch's counts into the handle's counters.
+int sample_pairs(pa_encoder* e, int32_t n_regions, const int32_t* region_pairs, ReadRec* d_reads, int* d_live, int* h_live);
+void sample_collect(pa_encoder* e);
 }  // namespace pa_enc
 
 namespace pa_ra {

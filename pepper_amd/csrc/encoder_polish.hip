@@ -873,6 +873,9 @@ int pa_polish_chain_run(pa_encoder* e, int32_t n_regions, const pa_packed_region
     int rc = unpack_packed_regions(e, n_regions, rs.data(), re.data(), arena, arena_bytes, reads, n_reads, pair_read, region_pairs,
                                    realign ? max_wl + 4 : -1, &u);
     if (rc != PA_OK) return rc;
+    // 1b. piles beyond the cap sampled down as the reference does (pa_encoder_set_sampling), before the re-aligner sees the pairs
+    rc = pa_enc::sample_pairs(e, n_regions, region_pairs, u.reads, u.d_live, const_cast<int*>(u.h_live));
+    if (rc != PA_OK) return rc;
     b.chain_counts[0] = u.n_pairs;
     b.chain_ms[0] = since(t0);
     t0 = now();
@@ -914,6 +917,7 @@ int pa_polish_chain_run(pa_encoder* e, int32_t n_regions, const pa_packed_region
     rc = polish_run(e, rows.data());
     if (rc != PA_OK) return rc;
     // (the stream has been waited for: what unpack_clip_kernel reported is here)
+    pa_enc::sample_collect(e);
     if (u.h_live[n_regions] > 0)
         return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(u.h_live[n_regions] - 1) + ": its CIGAR walks over more bases than the record holds");
     if (u.h_live[n_regions + 1] > 0)

@@ -153,8 +153,9 @@ class UserInterfaceSupport:
         """image_generator through the device-resident chain (PEPPER.PolishChain): per run of consecutive intervals ONE call of
         the BAM reader's packed form (the file's BGZF members inflated and walked on the device) and ONE of the chain (clip,
         re-align, summarise, cut into chunks on the device), then one call of the image writer.  Intervals the chain does not
-        take -- more than MAX_READS_IN_REGION reads (the reservoir sample is drawn in read order on the host), a record with
-        its CIGAR in the CG tag, a read that keeps more bases than a pair's slot -- go through parse_regions as before."""
+        take -- a record with its CIGAR in the CG tag, a read that keeps more bases than a pair's slot -- go through
+        parse_regions as before.  An interval with more than MAX_READS_IN_REGION reads is sampled down on the device
+        (reservoir_keep_kernel, between the clip and the re-aligner); PEPPER_AMD_DEVICE_SAMPLING=0 sends it to parse_regions."""
         import numpy as np
         from pepper_amd import _lib
         from pepper_amd.polish import PEPPER
@@ -170,7 +171,8 @@ class UserInterfaceSupport:
         if thread_id == 0:
             _log("INFO: STARTING THREAD: " + str(thread_id) + " FOR " + str(len(intervals)) + " INTERVALS")
         start_time = time.time()
-        mine = {}
+        # (two counts among the stage times: intervals the device sampled down, intervals that took parse_regions for any reason)
+        mine = {"sampled_on_device": 0, "host_form_intervals": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -191,6 +193,9 @@ class UserInterfaceSupport:
         chain = PEPPER.PolishChain(enc)
         consensus = fused.worker(thread_id, device, stream=enc.stream) if fused is not None else None      # polish(fused_inference=True): fused.py
         device_inflate = os.environ.get("PEPPER_AMD_DEVICE_INFLATE", "1") != "0"
+        device_sampling = _lib.device_sampling()
+        sampling = (AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION) if device_sampling else None
+        sampled_before = enc.sampled()[0]
         safe = AlingerOptions.ALIGNMENT_SAFE_BASES
         seq_len, features = ImageSizeOptions.SEQ_LENGTH, ImageSizeOptions.IMAGE_HEIGHT
         views = {}
@@ -200,6 +205,7 @@ class UserInterfaceSupport:
                 def host_form(chr_name, block):
                     """parse_regions (host-clipped reads, host arrays between the stages) for the intervals of `block`."""
                     key = (chr_name, bam_file, draft_file)
+                    mine["host_form_intervals"] += len(block)
                     if key not in views:
                         views.clear()
                         views[key] = UserInterfaceView(chr_name, bam_file, draft_file, truth_bam, train_mode)
@@ -247,10 +253,11 @@ class UserInterfaceSupport:
                     block, starts, stops = block[:n_done], starts[:n_done], stops[:n_done]
                     region_pairs = np.asarray(region_pairs[:n_done + 1], np.int32)
                     per_region = np.diff(region_pairs)
-                    deep = np.flatnonzero(per_region > AlingerOptions.MAX_READS_IN_REGION)
+                    deep = [] if device_sampling else np.flatnonzero(per_region > AlingerOptions.MAX_READS_IN_REGION)
                     if len(deep):
-                        # a pile beyond the reference's cap is sampled down in read order (AlignmentSummarizer.py:314-326): on the
-                        # host; the chain sees those intervals without reads and their chunks come from host_form below
+                        # PEPPER_AMD_DEVICE_SAMPLING=0: a pile beyond the reference's cap is sampled down in read order
+                        # (AlignmentSummarizer.py:314-326) on the host; the chain sees those intervals without reads and their
+                        # chunks come from host_form below
                         keep = np.ones(int(region_pairs[-1]), bool)
                         for r in deep:
                             keep[region_pairs[r]:region_pairs[r + 1]] = False
@@ -273,7 +280,7 @@ class UserInterfaceSupport:
                         try:
                             _rows, _live, chunks = chain.run(list(zip(starts[r0:r1], stops[r0:r1])), windows[r0:r1], region_pairs[r0:r1 + 1],
                                                              counts, realign=True, resident=resident, chunk_size=seq_len,
-                                                             chunk_overlap=ImageSizeOptions.SEQ_OVERLAP)
+                                                             chunk_overlap=ImageSizeOptions.SEQ_OVERLAP, sampling=sampling)
                         except _lib.PepperAmdError as err:
                             if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
                                 raise
@@ -318,6 +325,8 @@ class UserInterfaceSupport:
             raise
         finally:
             enc.inflate_ms, enc.inflated_bytes = 0.0, 0
+            mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
+            enc.set_sampling(None)
             enc.release()
         if stats is not None:
             with _STATS_LOCK:
@@ -403,7 +412,11 @@ class UserInterfaceSupport:
         args = (output_path, bam_file, draft_file, truth_bam, train_mode, downsample_rate)
         # the device-resident chain is the default; PEPPER_AMD_POLISH_CHAIN=0: host arrays between the stages (round 4's form,
         # device 0 only)
-        chain = os.environ.get("PEPPER_AMD_POLISH_CHAIN", "1") != "0" and downsample_rate >= 1.0
+        # downsample_rate: the reference's inference branch never reads it (AlignmentSummarizer.py:296-358; its one use is in the
+        # train branch) and neither does parse_regions here, so it does not choose the form; PEPPER_AMD_DEVICE_SAMPLING=0
+        # restores the earlier routing, in which a rate below 1 switched the chain off
+        from pepper_amd import _lib
+        chain = os.environ.get("PEPPER_AMD_POLISH_CHAIN", "1") != "0" and (downsample_rate >= 1.0 or _lib.device_sampling())
 
         def work(thread_id, n):
             if chain:

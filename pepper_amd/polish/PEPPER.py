@@ -153,13 +153,17 @@ class PolishChain(object):
         self.n_chunks = 0
         self.chunk_size = 0
 
-    def run(self, regions, windows, region_pairs, counts, realign=True, resident=False, chunk_size=1000, chunk_overlap=50):
+    def run(self, regions, windows, region_pairs, counts, realign=True, resident=False, chunk_size=1000, chunk_overlap=50,
+            sampling=None):
         """regions: [(start, end)] of the packed run -- or of a stretch of it: region_pairs[0] may be > 0, the pairs of the
         regions given are then pair_read[region_pairs[0] .. region_pairs[n]) (one pack_device() span serves several chain calls);
         windows[r]: the draft from start to end + 20 (bytes; shorter at the contig's end); region_pairs / counts: what
-        pack_device() / pack() returned.  -> (rows per region, reads per region, chunks per region)."""
+        pack_device() / pack() returned.  sampling: (seed, max_reads) -- a region with more reads is sampled down on the device as
+        the reference does on the host (pa_encoder_set_sampling); None: not.  -> (rows per region, reads per region -- after
+        sampling, chunks per region)."""
         from pepper_amd.variant.PEPPER_VARIANT import _PackedRegion
         pe = self.packed
+        pe.set_sampling(sampling)
         n = len(regions)
         refs = [w if isinstance(w, bytes) else bytes(w) for w in windows]
         regs = (_PackedRegion * max(1, n))(*[_PackedRegion(int(a), int(b), ref, len(ref)) for (a, b), ref in zip(regions, refs)])

@@ -18,12 +18,12 @@ def _log(message):
 
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
-           num_workers, stage_walls=None, fused_inference=None, batch_invariant=None):
+           num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
     PEPPER_AMD_BATCH_INVARIANT=1): the model handles of either form run in batch-invariant mode, so both forms, and any
-    device_ids, give the same predictions bit for bit."""
+    device_ids, give the same predictions bit for bit.  downsample_rate: make_images' (no effect on the output)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
@@ -54,12 +54,13 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant)
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
-                        stats=image_stats)
+                        stats=image_stats, downsample_rate=downsample_rate)
         finally:
             sink.close()
         t1 = t2 = time.perf_counter()
     else:
-        make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, stats=image_stats)
+        make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, stats=image_stats,
+                    downsample_rate=downsample_rate)
         t1 = time.perf_counter()
         _log("STEP 2: RUNNING INFERENCE -> " + prediction_output_directory)
         call_consensus(image_output_directory, model_path, batch_size, num_workers, prediction_output_directory, device_ids,

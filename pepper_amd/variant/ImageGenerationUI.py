@@ -178,7 +178,8 @@ class ImageGenerationUtils:
         from pepper_amd.variant.AlignmentSummarizer import create_summaries
         generators = {}
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
-        mine = {}
+        # ... and two counts: intervals the device sampled down, intervals that took the host-clipped form for any reason
+        mine = {"sampled_on_device": 0, "host_form_intervals": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -207,8 +208,10 @@ class ImageGenerationUtils:
 
         def host_clipped(output_hdf_file, group):
             """The form in which the host clips every read to its interval (BAM_handler.get_reads): injected handlers,
-            intervals whose reads are sampled down, operations the device-side clip refuses."""
+            operations the device-side clip refuses, intervals whose reads outgrow the arena (and, under
+            PEPPER_AMD_DEVICE_SAMPLING=0, intervals whose reads are sampled down)."""
             prepared = []
+            mine["host_form_intervals"] += len(group)
             for chr_name, _start, _end in group:
                 if chr_name not in generators:
                     generators.clear()               # one contig's handles at a time per worker
@@ -252,6 +255,13 @@ class ImageGenerationUtils:
                       options.delete_frequency, options.min_coverage_threshold, options.snp_candidate_frequency_threshold,
                       options.indel_candidate_frequency_threshold, options.candidate_support_threshold, options.skip_indels)
             device_inflate = os.environ.get("PEPPER_AMD_DEVICE_INFLATE", "1") != "0"
+            # the reference samples an interval's reads down to min(MAX_READS_IN_REGION, downsample_rate * n)
+            # (AlignmentSummarizer.py:192-199) in read order: drawn on the device between the clip and the summary
+            # (reservoir_keep_kernel); PEPPER_AMD_DEVICE_SAMPLING=0: such intervals take the host-clipped form
+            device_sampling = _lib.device_sampling()
+            sampling = ((AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION, float(options.downsample_rate))
+                        if device_sampling else None)
+            sampled_before = enc.sampled()[0]
             g0 = 0
             while g0 < len(intervals):
                 # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last
@@ -288,9 +298,8 @@ class ImageGenerationUtils:
                     continue
                 group, regions = group[:n_done], regions[:n_done]
                 per_region = np.diff(region_pairs[:n_done + 1])
-                # the reference samples an interval's reads down to min(MAX_READS_IN_REGION, downsample_rate * n)
-                # (AlignmentSummarizer.py:192-199) in read order: such intervals take the host-clipped form
-                if options.downsample_rate < 1.0 or int(per_region.max(initial=0)) > AlingerOptions.MAX_READS_IN_REGION:
+                if not device_sampling and (options.downsample_rate < 1.0
+                                            or int(per_region.max(initial=0)) > AlingerOptions.MAX_READS_IN_REGION):
                     host_clipped(output_hdf_file, group)
                     g0 += n_done
                     continue
@@ -301,7 +310,8 @@ class ImageGenerationUtils:
                 t0 = lap("fasta", t0)
                 try:
                     outs, live = enc.encode(regions, references, region_pairs, counts, params, [(s, e) for _, s, e in group],
-                                            ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident)
+                                            ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident,
+                                            sampling=sampling)
                 except _lib.PepperAmdError as err:
                     if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
                         raise
@@ -317,7 +327,7 @@ class ImageGenerationUtils:
                     t0 = lap("fused_forward", t0)
                 for (chr_name, _start, _end), out, n_reads in zip(group, outs, live):
                     k = len(out["positions"])
-                    if n_reads > 0:                  # (no read with a base inside: create_summary returns None, nothing is written)
+                    if n_reads > 0:                  # (no read with a base inside, or an empty sample: create_summary returns None, nothing is written)
                         write(output_hdf_file, chr_name, _start, _end, out, None if probs is None else probs[at:at + k])
                     at += k
                 lap("hdf5", t0)
@@ -326,6 +336,8 @@ class ImageGenerationUtils:
                 mine["inflate_kernel"] = mine.get("inflate_kernel", 0.0) + enc.inflate_ms / 1e3
                 mine["inflated_bytes"] = mine.get("inflated_bytes", 0.0) + enc.inflated_bytes
             enc.inflate_ms, enc.inflated_bytes = 0.0, 0
+            mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
+            enc.set_sampling(None)
             enc.release()
             t_close = time.perf_counter()
         lap("close", t_close)

@@ -331,6 +331,27 @@ class PackedEncoder(object):
         except Exception:
             pass
 
+    def set_sampling(self, sampling):
+        """(seed, max_reads[, rate]) for this handle's next runs, None: off (pa_encoder_set_sampling)."""
+        if sampling is None:
+            seed, cap, rate = 0, 0, 1.0
+        else:
+            seed, cap = int(sampling[0]), int(sampling[1])
+            rate = float(sampling[2]) if len(sampling) > 2 else 1.0
+        _lib.check(self.lib.pa_encoder_set_sampling(self.enc, seed, cap, rate))
+
+    def sampled(self):
+        """-> (intervals the device sampled down, reads it dropped) since this handle was created."""
+        regions, dropped = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self.lib.pa_encoder_sampled_regions(self.enc, ctypes.byref(regions), ctypes.byref(dropped)))
+        return regions.value, dropped.value
+
+    def pair_live(self, n_pairs):
+        """uint8 [n_pairs]: 1 where the pair of the last packed batch is a read of its interval (pa_encoder_pair_live)."""
+        keep = np.zeros(max(1, int(n_pairs)), np.uint8)
+        _lib.check(self.lib.pa_encoder_pair_live(self.enc, keep.ctypes.data, int(n_pairs)))
+        return keep[:int(n_pairs)]
+
     def pack(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq):
         """-> (n_done, region_pairs, (n_reads, n_pairs, arena_bytes)): BAM_handler.pack_regions into this object's buffers."""
         return bam_handler.pack_regions(contig, starts, stops, include_supplementary, min_mapq, self.arena, self.reads, self.pair_read)
@@ -429,11 +450,15 @@ class PackedEncoder(object):
         return n_done, region_pairs, (counts[0], counts[1], int(out_bytes))
 
     def encode(self, regions, references, region_pairs, counts, params, candidate_regions, candidate_window_size=32, feature_size=26,
-               want_int32=False, resident=False):
+               want_int32=False, resident=False, sampling=None):
         """regions: [(ref_start, ref_end)] of the packed run (the fetch ranges), references: their sequences (bytes / str),
         region_pairs / counts: what pack() returned, params: the ten thresholds of generate_summary in order,
-        candidate_regions: [(start, end)].  -> (one dict of arrays per region as generate_summary_arrays, reads per region)."""
+        candidate_regions: [(start, end)].  sampling: (seed, max_reads, downsample_rate) -- intervals with more reads than
+        int(min(max_reads, rate * n)) are sampled down on the device as the reference does on the host
+        (pa_encoder_set_sampling); None: not.  -> (one dict of arrays per region as generate_summary_arrays, reads per
+        region -- after sampling)."""
         n = len(regions)
+        self.set_sampling(sampling)
         refs = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in references]
         regs = (_PackedRegion * max(1, n))(*[_PackedRegion(int(a), int(b), ref, len(ref)) for (a, b), ref in zip(regions, refs)])
         (min_snp_baseq, min_indel_baseq, snp_freq_threshold, insert_freq_threshold, delete_freq_threshold,

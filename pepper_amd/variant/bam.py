@@ -42,6 +42,7 @@ SYMBOLS = [
     ("pa_bam_pack_inflated", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_char_p, c_int32, c_void_p, c_void_p,
                                             c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                             ctypes.POINTER(c_int32), c_void_p]),
+    ("pa_reservoir_sample", ctypes.c_int, [ctypes.c_uint32, c_int64, c_int64, c_void_p]),
 ]
 _bound = False
 
@@ -59,6 +60,15 @@ def _lib():
             fn.restype, fn.argtypes = restype, argtypes
         _bound = True
     return lib
+
+
+def reservoir_sample(seed, n, k):
+    """slots of the reference's reservoir sample of n reads down to k (pa_reservoir_sample: the host build of the sampler the
+    device runs) -> int32 [min(n, k)], the read kept in each slot."""
+    slots = np.zeros(max(0, min(int(n), int(k))), np.int32)
+    if _lib().pa_reservoir_sample(int(seed), int(n), int(k), slots.ctypes.data) != 0:
+        raise ValueError("reservoir_sample: bad n = %r / k = %r" % (n, k))
+    return slots
 
 
 def _check(rc):

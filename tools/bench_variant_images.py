@@ -2,7 +2,7 @@
 through pepper_amd.variant.ImageGenerationUI.generate_images, the entry point of pepper_variant make_images / call_variant.
 
   python tools/bench_variant_images.py make_fast <dir> [genome_bases=64000000] [coverage=60] [seed] [level=1] [tags=0] [quals=0]    synthetic data set
-  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000]     GPU; one JSON line
+  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000] [downsample_rate=1.0]     GPU; one JSON line
 
 `run` reports, per thread count, the wall time, Mb of reference per second, aligned bases per second and the stage times
 summed over the workers (bam_pack: inflate + header walk + slice copies; fasta; encode: upload + clip/decode + kernels +
@@ -46,12 +46,13 @@ def make_fast(out, bases=64000000, coverage=60, seed=2027, level=1, tags=0, qual
     return info
 
 
-def run(data, thread_counts=(16,), region_size=100000, warm=True):
+def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rate=1.0):
     from pepper_amd.variant.ImageGenerationUI import ImageGenerationUtils
     info = json.load(open(os.path.join(data, "synth.json")))
     mb = info["genome_bases"] / 1e6
     if warm:      # library load, the workers' buffers grown to the size of the job's groups, the file in the page cache -- not part of the rate
-        ImageGenerationUtils.generate_images(options(data, os.path.join(data, "vimages_warm"), thread_counts[0], region_size))
+        ImageGenerationUtils.generate_images(options(data, os.path.join(data, "vimages_warm"), thread_counts[0], region_size,
+                                                     downsample_rate=downsample_rate))
         shutil.rmtree(os.path.join(data, "vimages_warm"), ignore_errors=True)
     runs = []
     for threads in thread_counts:
@@ -59,7 +60,8 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True):
         shutil.rmtree(tmp, ignore_errors=True)
         stages = {}
         t0 = time.perf_counter()
-        ImageGenerationUtils.generate_images(options(data, tmp, threads, region_size, stage_seconds=stages))
+        ImageGenerationUtils.generate_images(options(data, tmp, threads, region_size, stage_seconds=stages,
+                                                     downsample_rate=downsample_rate))
         dt = time.perf_counter() - t0
         size = sum(os.path.getsize(os.path.join(tmp, f)) for f in os.listdir(tmp))
         runs.append({"threads": threads, "seconds": round(dt, 3), "mb_reference_per_s": round(mb / dt, 2),
@@ -72,7 +74,7 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True):
                 mb, info["coverage"], info["records"], info["bam_bytes"] / 1e9, info.get("deflate", "level 1"),
                 (", NM/MD/RG tags" if info.get("aux_tags") else "") + (", run-length qualities" if "run-length" in info.get("quals", "") else ""),
                 region_size),
-            "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0", "runs": runs}
+            "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0", "downsample_rate": downsample_rate, "runs": runs}
 
 
 if __name__ == "__main__":
@@ -80,4 +82,5 @@ if __name__ == "__main__":
         print(json.dumps(make_fast(sys.argv[2], *(float(a) for a in sys.argv[3:9]))))
     else:
         counts = tuple(int(t) for t in sys.argv[3].split(",")) if len(sys.argv) > 3 else (16,)
-        print(json.dumps(run(sys.argv[2], counts, int(sys.argv[4]) if len(sys.argv) > 4 else 100000)))
+        print(json.dumps(run(sys.argv[2], counts, int(sys.argv[4]) if len(sys.argv) > 4 else 100000,
+                             downsample_rate=float(sys.argv[5]) if len(sys.argv) > 5 else 1.0)))
