@@ -84,6 +84,7 @@ int pa_encoder_run_staged(pa_encoder* e, int64_t* n_candidates);
  *                the upload is then asynchronous; any host memory works); NULL: the span pa_encoder_inflate_bgzf left on
  *                the device (data_off then need not be aligned)
  *   reads        n_reads table entries; pair_read[region_pairs[r] .. region_pairs[r + 1]) = the reads of region r
+ *                (a read whose bases do not follow its operations: pa_encoder_set_seq_offsets before this call)
  *   regions      per region the generator's ref_start / ref_end (= the fetch range given to the packer) and its reference
  * The `reference` buffers must stay valid until the run returns (deleted bases of candidate alleles are cut from them).
  * An operation of 2^24 bases or more fails the run with PA_ERR_UNSUPPORTED: take the host-clipped form for that batch.
@@ -130,6 +131,17 @@ int pa_encoder_inflate_bgzf(pa_encoder* e, const uint8_t* comp, int64_t comp_byt
  * pa_bam_pack_inflated treats as a cut).  The caller then takes the span to the host after all. */
 int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry,
                             void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags);
+/* Reads whose CIGAR travels in the CG tag, kept on the device path (both off / empty on a new handle).
+ * pa_encoder_set_split_slices  on != 0: pa_encoder_walk_records looks the tag up in the record's auxiliary fields (one wavefront
+ *                     per record; every byte read lies inside the record and the span) and reports state 3 as
+ *                     include/pepper_amd_io.h describes instead of state 1; a malformed field gives state 2.
+ * pa_encoder_set_seq_offsets  seq_off[k] for each of the n_reads packed reads of the NEXT pa_encoder_stage_packed /
+ *                     pa_polish_chain_run: where read k's `bases | qualities` lie in the arena when they do not follow its
+ *                     operations, -1 when they do (pa_bam_split_offsets fills it).  The table is copied, serves that one call
+ *                     (which checks both slices against the arena and fails when n_reads differs from its own) and is then
+ *                     forgotten, whether the call succeeded or was refused; NULL with n_reads = 0 clears it. */
+int pa_encoder_set_split_slices(pa_encoder* e, int32_t on);
+int pa_encoder_set_seq_offsets(pa_encoder* e, const int64_t* seq_off, int32_t n_reads);
 /* Host threads of a run's candidate enumeration (one short task per region): 0 = the default (the CPUs the process may use),
  * 1 = the calling thread alone -- what image generation sets, whose workers each drive their own encoder while the other
  * CPUs inflate BGZF blocks. */

@@ -299,10 +299,15 @@ int pa_bam_pack_regions(pa_bam* b, const char* contig, int32_t n_regions, const 
  *                     the last stop (or the end of a span that data_is_final says holds the contig's last record); when the
  *                     span ends earlier the regions closed by then are done (*n_done) and the caller takes a later span for the
  *                     rest -- none closed: -9.  A record whose CIGAR lives in the CG tag is no single slice: -8, take
- *                     pa_bam_pack_regions for that batch. */
+ *                     pa_bam_pack_regions for that batch -- unless pa_bam_set_split_slices has switched the handle to the
+ *                     two-slice form below. */
 /* One record of an inflated span as the device's walk reads it out (pa_encoder_walk_records, include/pepper_amd_encoder.h):
  * data_off = where the record's `CIGAR words | bases | qualities` start in the span, ref_len = the reference bases its
- * operations cover, state = 0, 1 (the placeholder of a CIGAR kept in the CG tag) or 2 (fields that overrun the record). */
+ * operations cover, state = 0, 1 (the placeholder of a CIGAR kept in the CG tag) or 2 (fields that overrun the record).
+ * After pa_encoder_set_split_slices the walk looks the CG tag up itself: state = 3, data_off = where the tag's operations
+ * start, n_cigar / ref_len = their number / reference bases, and block_size = the distance from data_off BACK to the record's
+ * bases (bases | qualities stay in the core: at data_off - block_size).  block_size of a state-3 header is therefore NOT the
+ * record's size: it is the record's size in every other state.  State 2 then also covers a malformed auxiliary field. */
 #ifndef PA_RECORD_HEADER_DEFINED
 #define PA_RECORD_HEADER_DEFINED
 typedef struct {
@@ -322,6 +327,16 @@ int pa_bam_pack_headers(pa_bam* b, const pa_record_header* headers, int64_t n_he
                         int32_t n_regions, const int64_t* start, const int64_t* stop, int32_t include_supplementary, int32_t min_mapq,
                         pa_packed_read* reads, int32_t reads_cap, int32_t* pair_read, int32_t pairs_cap, int32_t* region_pairs,
                         int32_t* n_done, int64_t* counts);
+/* Reads whose operations and bases lie apart (SAM specification 4.2.2: more than 65 535 operations travel in the CG:B,I tag,
+ * the core keeps <l_seq>S<ref_len>N, bases and qualities).  Off on a new handle: pa_bam_pack_inflated / pa_bam_pack_headers fail
+ * with -8 at such a record.  on != 0: they keep it in place like any other -- data_off / n_cigar are the tag's operations, and
+ * a table parallel to `reads` says where the bases start: pa_bam_split_offsets copies seq_off[k] of the first n_reads reads of
+ * the handle's last packed walk (-1: `bases | qualities` follow the operations, as ever) and counts the others in *n_split
+ * (may be NULL).  pa_encoder_set_seq_offsets (include/pepper_amd_encoder.h) hands the table to the clip kernel.  A placeholder
+ * without a usable tag (htslib's rules: B,I or B,i, at least as many operations as the core, fewer than 2^29) keeps its core
+ * CIGAR, as pa_bam_pack_regions does.  pa_bam_pack_regions and pa_bam_get_reads do not look at the switch. */
+int pa_bam_set_split_slices(pa_bam* b, int32_t on);
+int pa_bam_split_offsets(pa_bam* b, int64_t* seq_off, int32_t n_reads, int32_t* n_split);
 /* The host's counterpart of the device inflate (include/pepper_amd_io_device.h) over the same member tables: libdeflate where
  * it is installed (htslib's choice), zlib otherwise, on n_threads threads -- the CPU baseline of the inflate bench. */
 int pa_bgzf_inflate_host(const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* comp_off, const int32_t* comp_len,

@@ -78,6 +78,8 @@ SYMBOLS = [
                                                c_void_p]),
     ("pa_encoder_walk_records", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                                ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_encoder_set_split_slices", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_encoder_set_seq_offsets", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_region_reads", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_set_host_threads", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_encoder_set_sampling", ctypes.c_int, [c_void_p, ctypes.c_uint32, c_int32, c_double]),
@@ -197,6 +199,15 @@ DEVICE_SAMPLING_ENV = "PEPPER_AMD_DEVICE_SAMPLING"
 def device_sampling():
     """PEPPER_AMD_DEVICE_SAMPLING=0: the image-generation drivers send sampled intervals through their host forms again."""
     return os.environ.get(DEVICE_SAMPLING_ENV, "1") != "0"
+
+
+DEVICE_LONG_CIGARS_ENV = "PEPPER_AMD_DEVICE_LONG_CIGARS"
+
+
+def device_long_cigars():
+    """PEPPER_AMD_DEVICE_LONG_CIGARS=0: the image-generation drivers send a batch with a CIGAR kept in the CG tag through the
+    host packer again."""
+    return os.environ.get(DEVICE_LONG_CIGARS_ENV, "1") != "0"
 
 
 def check(rc):

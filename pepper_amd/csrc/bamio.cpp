@@ -231,6 +231,8 @@ struct pa_bam {
     std::vector<uint8_t> scratch_qual;
     std::vector<std::pair<int32_t, int32_t>> pack_pairs;       // pa_bam_pack_regions: (region, read) as the walk finds them
     std::vector<int64_t> pack_closed;
+    bool split_slices = false;                                 // pa_bam_set_split_slices: pack_inflated / pack_headers keep CG records
+    std::vector<int64_t> pack_seq_off;                         // per read of the last packed walk: where its bases start, -1 = behind its operations
     std::string path;
     int span_fd = -1;                                          // pa_bam_read_span: its own descriptor (pread, no shared position)
     std::vector<int64_t> span_members;                         // file offsets of the members of the last pa_bam_read_span
@@ -725,6 +727,8 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         }
     };
     int64_t hk = 0;
+    std::vector<int64_t>& seq_offs = b->pack_seq_off;
+    seq_offs.clear();
     while (!nothing) {
         uint32_t block_size = 0;
         const uint8_t* R = nullptr;
@@ -828,9 +832,16 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         if (full) break;
         if (first_pair < 0) continue;
         const int64_t bytes = 4ll * n_cig + (l_seq + 1) / 2 + l_seq;
-        int64_t at;
+        int64_t at, seq_at = -1;
         if (H) {
-            if (H->state == 1) return bam_fail(-8, "pack_headers: a record keeps its CIGAR in the CG tag (take pack_regions)");
+            // state 3: the device's walk found the operations in the tag (data_off, n_cigar, ref_len are theirs) and left the
+            // distance back to the record's bases in block_size -- two slices, kept only on a handle that was asked to
+            if (H->state == 1 || (H->state == 3 && !b->split_slices))
+                return bam_fail(-8, "pack_headers: a record keeps its CIGAR in the CG tag (take pack_regions)");
+            if (H->state == 3) {
+                seq_at = H->data_off - (int64_t)H->block_size;
+                if (H->block_size <= 0 || seq_at < 0) return bam_fail(-6, "corrupt BAM record");
+            }
             if (n_reads >= reads_cap) {
                 pairs.resize((size_t)first_pair);
                 full = true;
@@ -839,7 +850,10 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
             at = H->data_off;
         } else if (mem) {
             // in place: the slice is the record's own bytes (any alignment); a CIGAR kept in the CG tag is not one slice
-            if (cig != R + o_cigar) return bam_fail(-8, "pack_inflated: a record keeps its CIGAR in the CG tag (take pack_regions)");
+            if (cig != R + o_cigar) {
+                if (!b->split_slices) return bam_fail(-8, "pack_inflated: a record keeps its CIGAR in the CG tag (take pack_regions)");
+                seq_at = (int64_t)(R + o_seq - mem);          // (two slices: the operations inside the tag, the bases in the core)
+            }
             if (n_reads >= reads_cap) {
                 pairs.resize((size_t)first_pair);
                 full = true;
@@ -866,6 +880,7 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         pr.n_cigar = (int32_t)n_cig;
         pr.l_seq = (int32_t)l_seq;
         pr.flags = (int32_t)(flag | ((uint32_t)mapq << 16));
+        seq_offs.push_back(seq_at);
         used = (mem || H) ? used + bytes : at + bytes;
     }
     if (!full && !cut) close_up_to(0x7fffffffffffffffll);        // the walk ended: every region is complete
@@ -1180,6 +1195,24 @@ int pa_bam_pack_inflated(pa_bam* b, const uint8_t* data, int64_t data_bytes, int
     static const uint8_t none = 0;
     return pack_walk(b, tid, false, data ? data : &none, data_bytes, first_record, data_is_final != 0, nullptr, 0, n_regions, start, stop,
                      include_supplementary, min_mapq, nullptr, 0, reads, reads_cap, pair_read, pairs_cap, region_pairs, n_done, counts);
+}
+
+int pa_bam_set_split_slices(pa_bam* b, int32_t on) {
+    if (!b) return bam_fail(-1, "null handle");
+    b->split_slices = on != 0;
+    return 0;
+}
+
+int pa_bam_split_offsets(pa_bam* b, int64_t* seq_off, int32_t n_reads, int32_t* n_split) {
+    if (!b || n_reads < 0 || (n_reads > 0 && !seq_off)) return bam_fail(-1, "null argument");
+    if ((size_t)n_reads > b->pack_seq_off.size()) return bam_fail(-1, "split_offsets: the handle's last packed walk kept fewer reads");
+    int32_t n = 0;
+    for (int32_t k = 0; k < n_reads; ++k) {
+        seq_off[k] = b->pack_seq_off[(size_t)k];
+        n += seq_off[k] >= 0 ? 1 : 0;
+    }
+    if (n_split) *n_split = n;
+    return 0;
 }
 
 int pa_bam_copy_reads(pa_bam* b, int64_t* pos, int64_t* pos_end, uint8_t* reverse, int32_t* mapq, int32_t* flags,

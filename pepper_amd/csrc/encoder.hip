@@ -196,6 +196,7 @@ static_assert(sizeof(PackedRead) == sizeof(pa_packed_read) && sizeof(PackedRead)
 struct UnpackArgs {
     const PairRec* pairs; int n_pairs;
     const PackedRead* preads; const RegRec* regions; const int64_t* region_start; const uint8_t* arena;
+    const int64_t* seq_off;      // per packed read: where its bases and qualities lie when not behind its operations (-1), or null: none does
     ReadRec* reads; int32_t* cigar_op; int32_t* cigar_len; char* seq; uint8_t* qual;
     int* live;        // [n_regions] reads with a base inside | [n_regions] first inconsistent read + 1 | [n_regions + 1] first unsupported + 1
     int n_regions;
@@ -273,7 +274,8 @@ __global__ __launch_bounds__(256) void unpack_clip_kernel(UnpackArgs a) {
     }
     if (written <= 0) return;
     // the kept stretch: bases first_idx .. first_idx + written - 1 of the record, four per lane and step
-    const uint8_t* packed = a.arena + rd.data_off + 4ll * rd.n_cigar;
+    const int64_t apart = a.seq_off ? a.seq_off[pr.read] : -1;      // (a CIGAR kept in the CG tag: the bases stay in the record's core)
+    const uint8_t* packed = a.arena + (apart >= 0 ? apart : rd.data_off + 4ll * rd.n_cigar);
     const uint8_t* quals = packed + (rd.l_seq + 1) / 2;
     const unsigned long long lut_lo = 0x565352474d43413dull;                // "=ACMGRSV", first letter in the low byte
     const unsigned long long lut_hi = 0x4e42444b48595754ull;                // "TWYHKDBN"
@@ -1429,14 +1431,32 @@ int stage_batch(pa_encoder* e, int32_t n_regions, const pa_pileup* pileups, cons
 }
 
 
+// a packed read's slice(s) lie inside the arena: `CIGAR words | bases | qualities` from data_off, or the words there and
+// `bases | qualities` from seq_off (pa_encoder_set_seq_offsets)
+static bool packed_read_inside(const pa_packed_read& rd, int64_t seq_off, int64_t arena_bytes) {
+    if (rd.n_cigar < 0 || rd.l_seq < 0 || rd.data_off < 0) return false;
+    const int64_t ops_end = rd.data_off + 4ll * rd.n_cigar, bases = ((int64_t)rd.l_seq + 1) / 2 + rd.l_seq;
+    if (seq_off < 0) return ops_end + bases <= arena_bytes;
+    return ops_end <= arena_bytes && seq_off + bases <= arena_bytes;
+}
+// the table of pa_encoder_set_seq_offsets serves ONE staging call, accepted or refused: taken before anything else is checked
+static std::vector<int64_t> take_seq_offsets(pa_encoder* e) {
+    std::vector<int64_t> out;
+    if (e) out.swap(e->seq_off);
+    return out;
+}
+
 // The packed form of a batch (include/pepper_amd_encoder.h): tables built in ONE page-locked block and uploaded with one copy,
 // the arena with another, then unpack_clip_kernel -- nothing here waits for the device.
 int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
                  const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads, const int32_t* pair_read,
                  const int32_t* region_pairs) {
+    const std::vector<int64_t> soff = take_seq_offsets(e);
     if (!e || n_regions < 0 || (n_regions > 0 && (!regions || !params || !region_pairs)) || arena_bytes < 0 || n_reads < 0 ||
         (n_reads > 0 && (!reads || !pair_read)))
         return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!soff.empty() && (int64_t)soff.size() != n_reads)
+        return pa::set_error(PA_ERR_INVALID, "the base offsets set for this call are not one per packed read");
     if (n_regions >= (1 << 22)) return pa::set_error(PA_ERR_INVALID, "more than 4194303 regions in one batch");
     ENC_HIP(hipSetDevice(e->device));
     if (!e->variant) e->variant = new pa_variant_batch();
@@ -1471,7 +1491,8 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_reg = 0, o_start = up16(o_reg + (size_t)n_regions * sizeof(RegRec)), o_tile = up16(o_start + (size_t)n_regions * 8),
                  o_reads = up16(o_tile + (size_t)b.n_tiles * 4), o_pairs = up16(o_reads + (size_t)n_reads * sizeof(PackedRead)),
-                 o_ref = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)), meta_bytes = up16(o_ref + (size_t)b.total_ref + 64);
+                 o_soff = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)), o_ref = up16(o_soff + soff.size() * 8),
+                 meta_bytes = up16(o_ref + (size_t)b.total_ref + 64);
     if (!b.h_meta.ensure(meta_bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
     char* hm = b.h_meta.as<char>();
     RegRec* regrecs = reinterpret_cast<RegRec*>(hm + o_reg);
@@ -1479,6 +1500,7 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
     int32_t* tile_region = reinterpret_cast<int32_t*>(hm + o_tile);
     PairRec* pairs = reinterpret_cast<PairRec*>(hm + o_pairs);
     if (n_reads) std::memcpy(hm + o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
+    if (!soff.empty()) std::memcpy(hm + o_soff, soff.data(), soff.size() * 8);
     b.total_rows = 0;
     b.total_ref = 0;
     b.n_tiles = 0;
@@ -1525,8 +1547,7 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
             const int32_t ri = pair_read[k];
             if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
             const pa_packed_read& rd = reads[ri];
-            if (rd.n_cigar < 0 || rd.l_seq < 0 || rd.data_off < 0 ||
-                rd.data_off + 4ll * rd.n_cigar + (rd.l_seq + 1) / 2 + rd.l_seq > arena_bytes)
+            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
                 return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
             pairs[k] = PairRec{b.total_bases, ri, r, (int32_t)b.total_ops, 0};
             b.total_bases += ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
@@ -1572,6 +1593,7 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
         ua.regions = b.p_regions;
         ua.region_start = reinterpret_cast<const int64_t*>(dm + o_start);
         ua.arena = b.d_arena.as<uint8_t>();
+        ua.seq_off = soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + o_soff);
         ua.reads = b.d_reads.as<ReadRec>();
         ua.cigar_op = b.d_cig_op.as<int32_t>();
         ua.cigar_len = b.d_cig_len.as<int32_t>();
@@ -1865,6 +1887,9 @@ void pa_enc::sample_collect(pa_encoder* e) {
 int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_t* region_start, const int64_t* region_end,
                                   const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads,
                                   const int32_t* pair_read, const int32_t* region_pairs, int32_t extra_ops_per_pair, UnpackedReads* out) {
+    const std::vector<int64_t> soff = take_seq_offsets(e);
+    if (!soff.empty() && (int64_t)soff.size() != n_reads)
+        return pa::set_error(PA_ERR_INVALID, "the base offsets set for this call are not one per packed read");
     if (!e || !out || n_regions < 0 || (n_regions > 0 && (!region_start || !region_end || !region_pairs)) || arena_bytes < 0 || n_reads < 0 ||
         (n_reads > 0 && (!reads || !pair_read)))
         return pa::set_error(PA_ERR_INVALID, "null argument");
@@ -1879,13 +1904,15 @@ int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_
     if (n_pairs < 0 || (n_regions && region_pairs[0] != 0)) return pa::set_error(PA_ERR_INVALID, "region_pairs must start at 0 and ascend");
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t o_reg = 0, o_start = up16(o_reg + (size_t)n_regions * sizeof(RegRec)), o_reads = up16(o_start + (size_t)n_regions * 8),
-                 o_pairs = up16(o_reads + (size_t)n_reads * sizeof(PackedRead)), meta_bytes = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)) + 64;
+                 o_pairs = up16(o_reads + (size_t)n_reads * sizeof(PackedRead)), o_soff = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)),
+                 meta_bytes = up16(o_soff + soff.size() * 8) + 64;
     if (!b.h_meta.ensure(meta_bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
     char* hm = b.h_meta.as<char>();
     RegRec* regrecs = reinterpret_cast<RegRec*>(hm + o_reg);
     int64_t* rstart = reinterpret_cast<int64_t*>(hm + o_start);
     PairRec* pairs = reinterpret_cast<PairRec*>(hm + o_pairs);
     if (n_reads) std::memcpy(hm + o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
+    if (!soff.empty()) std::memcpy(hm + o_soff, soff.data(), soff.size() * 8);
     int64_t total_bases = 0, total_ops = 0;
     for (int r = 0; r < n_regions; ++r) {
         if (region_end[r] < region_start[r] || region_end[r] - region_start[r] > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
@@ -1898,8 +1925,7 @@ int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_
             const int32_t ri = pair_read[k];
             if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
             const pa_packed_read& rd = reads[ri];
-            if (rd.n_cigar < 0 || rd.l_seq < 0 || rd.data_off < 0 ||
-                rd.data_off + 4ll * rd.n_cigar + (rd.l_seq + 1) / 2 + rd.l_seq > arena_bytes)
+            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
                 return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
             // the clipped stretch of a read holds its aligned bases inside the region and the inserts between them: room for the
             // whole read would be 10-50 kb per pair of a 1 kb region, so a pair gets min(l_seq, 2 L + 64) bases; a pair that
@@ -1937,6 +1963,7 @@ int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_
         ua.regions = reinterpret_cast<const RegRec*>(dm + o_reg);
         ua.region_start = reinterpret_cast<const int64_t*>(dm + o_start);
         ua.arena = b.d_arena.as<uint8_t>();
+        ua.seq_off = soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + o_soff);
         ua.reads = b.d_reads.as<ReadRec>();
         ua.cigar_op = b.d_cig_op.as<int32_t>();
         ua.cigar_len = b.d_cig_len.as<int32_t>();
@@ -2132,7 +2159,7 @@ int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* en
     pa::launch_record_walk(st, b.d_arena.as<uint8_t>(), data_bytes, reinterpret_cast<const int64_t*>(mapped ? mw : dw), n_entries,
                            cap_per_entry, dw + o_slots, reinterpret_cast<int32_t*>(dw + o_counts), reinterpret_cast<int32_t*>(dw + o_base),
                            reinterpret_cast<int32_t*>(dw + o_flags), dw + o_out, (int64_t)slots,
-                           mapped ? reinterpret_cast<int32_t*>(mw + h_tail) : nullptr);
+                           mapped ? reinterpret_cast<int32_t*>(mw + h_tail) : nullptr, e->split_walk ? 1 : 0);
     ENC_HIP(hipGetLastError());
     if (!mapped) {
         ENC_HIP(hipMemcpyAsync(tail, dw + o_base + n * 4, 4, hipMemcpyDeviceToHost, st));
@@ -2156,6 +2183,18 @@ int pa_encoder_stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_re
                             const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads,
                             const int32_t* pair_read, const int32_t* region_pairs) {
     return stage_packed(e, n_regions, regions, params, arena, arena_bytes, reads, n_reads, pair_read, region_pairs);
+}
+
+int pa_encoder_set_split_slices(pa_encoder* e, int32_t on) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    e->split_walk = on != 0;
+    return PA_OK;
+}
+
+int pa_encoder_set_seq_offsets(pa_encoder* e, const int64_t* seq_off, int32_t n_reads) {
+    if (!e || n_reads < 0 || (n_reads > 0 && !seq_off)) return pa::set_error(PA_ERR_INVALID, "null argument");
+    e->seq_off.assign(seq_off, seq_off + n_reads);
+    return PA_OK;
 }
 
 int pa_encoder_set_host_threads(pa_encoder* e, int32_t n) {

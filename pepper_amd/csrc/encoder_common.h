@@ -164,6 +164,8 @@ struct pa_encoder {
     pa_polish_batch* polish = nullptr;
     struct pa_realigner* realigner = nullptr;      // the polish image chain's re-aligner on this encoder's stream (made on first use)
     pa_sampler sampler;
+    bool split_walk = false;                       // pa_encoder_set_split_slices: the record walk resolves CIGARs kept in the CG tag
+    std::vector<int64_t> seq_off;                  // pa_encoder_set_seq_offsets: per packed read of the NEXT staging where its bases lie (-1: behind its operations)
 };
 
 // ---- the polish image chain (encoder_polish.hip: pa_polish_chain_*) crosses the three files; the pieces it calls --------------

@@ -837,6 +837,8 @@ int pa_polish_chain_run(pa_encoder* e, int32_t n_regions, const pa_packed_region
                         const pa_packed_read* reads, int32_t n_reads, const int32_t* pair_read, const int32_t* region_pairs,
                         int32_t realign, int32_t chunk_size, int32_t chunk_overlap, int64_t* n_rows, int32_t* region_reads,
                         int32_t* n_chunks, int64_t* total_chunks) {
+    // (the base offsets of pa_encoder_set_seq_offsets serve this call alone, refused or not: unpack_packed_regions takes them)
+    struct Once { pa_encoder* e; ~Once() { if (e) e->seq_off.clear(); } } once{e};
     if (!e || n_regions < 0 || (n_regions > 0 && (!regions || !region_pairs)) || chunk_size <= 0 || chunk_overlap < 0 || chunk_overlap >= chunk_size)
         return pa::set_error(PA_ERR_INVALID, "null argument");
     ENC_HIP(hipSetDevice(e->device));

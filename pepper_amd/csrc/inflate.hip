@@ -990,7 +990,7 @@ __global__ __launch_bounds__(64) void record_chase_kernel(const uint8_t* __restr
         h.flags = (int32_t)((w3 >> 16) | (((w2 >> 8) & 0xffu) << 16));
         const int64_t o_cigar = 32 + (int64_t)(w2 & 0xffu);
         h.data_off = at + 4 + o_cigar;
-        h.ref_len = 0;
+        h.ref_len = (int32_t)(w2 & 0xffu);       // (the name's length, for record_finish_kernel to find the record's end; it writes the sum)
         h.block_size = (int32_t)bs;
         const int64_t o_aux = o_cigar + 4ll * h.n_cigar + ((int64_t)(uint32_t)h.l_seq + 1) / 2 + (int64_t)(uint32_t)h.l_seq;
         h.state = (h.l_seq < 0 || o_aux > (int64_t)bs) ? 2 : 0;
@@ -1024,30 +1024,111 @@ __global__ __launch_bounds__(64) void record_base_kernel(const int32_t* __restri
     }
 }
 
-// one wavefront per slot: the reference bases of the record's operations; the placeholder of a CIGAR kept in the CG tag
-// (kSmN, SAM specification 4.2.2: first operation S over all bases) marks the record for the host path
-__global__ __launch_bounds__(256) void record_finish_kernel(const uint8_t* __restrict__ data, const RecHdr* __restrict__ slots,
+// bytes of one value of an auxiliary field's type letter (SAM specification 4.2.4), -1: no fixed-size type
+__device__ __forceinline__ int aux_value_bytes(uint32_t t) {
+    switch (t) {
+        case 'A': case 'c': case 'C': return 1;
+        case 's': case 'S': return 2;
+        case 'i': case 'I': case 'f': return 4;
+        case 'd': return 8;
+    }
+    return -1;
+}
+
+// The CG:B,I tag among the auxiliary fields data[p, end) of one record, looked for by a whole wavefront with the rules of
+// bamio.cpp's find_cg: the typed walk is the same in every lane (one field after the other: nothing to share out), the NUL
+// of a Z / H field -- methylation strings run to hundreds of kilobytes -- is found 64 bytes at a time.  Every byte read lies
+// in [p, end).  -> 1: found, *ops = where its operations start and *count how many; 0: the record has none (or fewer than
+// four bytes are left, where find_cg stops too); -1: a field that overruns the record or an unknown type letter.
+__device__ int wave_find_cg(const uint8_t* __restrict__ data, int64_t p, int64_t end, int lane, int64_t* ops, uint32_t* count) {
+    while (end - p >= 4) {
+        const bool is_cg = data[p] == 'C' && data[p + 1] == 'G';
+        const uint32_t type = data[p + 2];
+        p += 3;
+        if (type == 'Z' || type == 'H') {
+            int64_t nul = -1;
+            for (int64_t q = p; q < end && nul < 0; q += 64) {
+                const int64_t at = q + lane;
+                const unsigned long long m = __ballot(at < end && data[at] == 0);
+                if (m) nul = q + (__ffsll((long long)m) - 1);
+            }
+            if (nul < 0) return -1;
+            p = nul + 1;
+        } else if (type == 'B') {
+            if (end - p < 5) return -1;
+            const uint32_t sub = data[p];
+            const int esz = aux_value_bytes(sub);
+            if (esz < 0) return -1;
+            const uint32_t cnt = load32(data + p + 1);
+            if ((uint64_t)(end - p - 5) < (uint64_t)cnt * (uint64_t)esz) return -1;
+            if (is_cg && (sub == 'I' || sub == 'i')) {
+                *ops = p + 5;
+                *count = cnt;
+                return 1;
+            }
+            p += 5 + (int64_t)cnt * esz;
+        } else {
+            const int sz = aux_value_bytes(type);
+            if (sz < 0 || end - p < sz) return -1;
+            p += sz;
+        }
+    }
+    return 0;
+}
+
+// one wavefront per slot: the reference bases of the record's operations.  The placeholder of a CIGAR kept in the CG tag
+// (kSmN, SAM specification 4.2.2: first operation S over all bases) marks the record for the host path (state 1) -- or, with
+// split != 0, its operations are looked up in the tag: state 3, data_off / n_cigar / ref_len those of the real operations and
+// block_size the distance from them back to the record's bases (which stay where the core has them); a tag that does not
+// qualify (find_cg's rules) leaves the core CIGAR standing as the host does, a malformed field gives state 2.
+__global__ __launch_bounds__(256) void record_finish_kernel(const uint8_t* __restrict__ data, int64_t data_bytes, const RecHdr* __restrict__ slots,
                                                            const int32_t* __restrict__ counts, const int32_t* __restrict__ base,
-                                                           int cap, int n_entries, RecHdr* __restrict__ out, long long out_cap) {
+                                                           int cap, int n_entries, RecHdr* __restrict__ out, long long out_cap, int split) {
     // sixteen workgroups = 64 wavefronts per entry, striding over its records (a wavefront per SLOT would be mostly empty ones)
     const int i = blockIdx.x >> 4, lane = threadIdx.x & 63;
     if (i >= n_entries) return;
     const int n = counts[i];
     for (int j = (blockIdx.x & 15) * 4 + ((int)threadIdx.x >> 6); j < n; j += 64) {
     RecHdr h = slots[(size_t)i * cap + j];
+    const int l_name = h.ref_len;
     int ref = 0;
     if (h.state == 0) {
         const uint8_t* cig = data + h.data_off;
-        for (int k0 = 0; k0 < h.n_cigar; k0 += 64) {
-            const int k = k0 + lane;
-            const uint32_t c = k < h.n_cigar ? load32(cig + 4ll * k) : 5u;
-            const int op = (int)(c & 15u);
-            ref += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (int)(c >> 4) : 0;
-        }
-        for (int o = 32; o > 0; o >>= 1) ref += __shfl_xor(ref, o, 64);
-        if (h.n_cigar >= 1) {
+        int n_ops = h.n_cigar;
+        if (n_ops >= 1) {
             const uint32_t c0 = load32(cig);
-            if ((c0 & 15u) == 4u && (int)(c0 >> 4) == h.l_seq) h.state = 1;
+            if ((c0 & 15u) == 4u && (int)(c0 >> 4) == h.l_seq) {
+                if (!split) h.state = 1;
+                else {
+                    // the record's bytes are [data_off - 32 - l_name, + block_size) (the chase kernel checked them against
+                    // the span); its auxiliary fields follow the qualities
+                    const int64_t seq_off = h.data_off + 4ll * h.n_cigar;
+                    const int64_t aux = seq_off + ((int64_t)h.l_seq + 1) / 2 + (int64_t)h.l_seq;
+                    int64_t end = h.data_off - 32 - (int64_t)l_name + (int64_t)h.block_size;
+                    if (end > data_bytes) end = data_bytes;
+                    int64_t ops = 0;
+                    uint32_t cnt = 0;
+                    const int found = aux <= end ? wave_find_cg(data, aux, end, lane, &ops, &cnt) : -1;
+                    if (found < 0) h.state = 2;
+                    else if (found == 1 && cnt >= (uint32_t)h.n_cigar && cnt < (1u << 29)) {
+                        h.state = 3;
+                        h.data_off = ops;
+                        h.n_cigar = (int32_t)cnt;
+                        h.block_size = (int32_t)(ops - seq_off);
+                        cig = data + ops;
+                        n_ops = (int)cnt;
+                    }
+                }
+            }
+        }
+        if (h.state != 2) {
+            for (int k0 = 0; k0 < n_ops; k0 += 64) {
+                const int k = k0 + lane;
+                const uint32_t c = k < n_ops ? load32(cig + 4ll * k) : 5u;
+                const int op = (int)(c & 15u);
+                ref += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (int)(c >> 4) : 0;
+            }
+            for (int o = 32; o > 0; o >>= 1) ref += __shfl_xor(ref, o, 64);
         }
     }
     if (lane == 0 && (long long)base[i] + j < out_cap) {
@@ -1060,13 +1141,13 @@ __global__ __launch_bounds__(256) void record_finish_kernel(const uint8_t* __res
 }  // namespace
 
 void launch_record_walk(hipStream_t stream, const uint8_t* data, int64_t data_bytes, const int64_t* entries, int n_entries, int cap,
-                        void* slots, int32_t* counts, int32_t* base, int32_t* flags, void* out, int64_t out_cap, int32_t* tail) {
+                        void* slots, int32_t* counts, int32_t* base, int32_t* flags, void* out, int64_t out_cap, int32_t* tail, int split) {
     if (n_entries <= 0) return;
     hipLaunchKernelGGL(record_chase_kernel, dim3((unsigned)((n_entries + 63) / 64)), dim3(64), 0, stream, data, data_bytes, entries,
                        n_entries, cap, static_cast<RecHdr*>(slots), counts, flags);
     hipLaunchKernelGGL(record_base_kernel, dim3(1), dim3(64), 0, stream, counts, n_entries, base, flags, tail);
-    hipLaunchKernelGGL(record_finish_kernel, dim3((unsigned)n_entries * 16u), dim3(256), 0, stream, data,
-                       static_cast<const RecHdr*>(slots), counts, base, cap, n_entries, static_cast<RecHdr*>(out), (long long)out_cap);
+    hipLaunchKernelGGL(record_finish_kernel, dim3((unsigned)n_entries * 16u), dim3(256), 0, stream, data, data_bytes,
+                       static_cast<const RecHdr*>(slots), counts, base, cap, n_entries, static_cast<RecHdr*>(out), (long long)out_cap, split);
 }
 
 void launch_bgzf_inflate(hipStream_t stream, const uint8_t* comp, const int64_t* comp_off, const int32_t* comp_len,

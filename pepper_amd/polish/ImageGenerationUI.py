@@ -153,8 +153,9 @@ class UserInterfaceSupport:
         """image_generator through the device-resident chain (PEPPER.PolishChain): per run of consecutive intervals ONE call of
         the BAM reader's packed form (the file's BGZF members inflated and walked on the device) and ONE of the chain (clip,
         re-align, summarise, cut into chunks on the device), then one call of the image writer.  Intervals the chain does not
-        take -- a record with its CIGAR in the CG tag, a read that keeps more bases than a pair's slot -- go through
-        parse_regions as before.  An interval with more than MAX_READS_IN_REGION reads is sampled down on the device
+        take -- a read that keeps more bases than a pair's slot -- go through parse_regions as before.  A record with its
+        CIGAR in the CG tag stays in the span on the device (PEPPER_AMD_DEVICE_LONG_CIGARS=0: its run of intervals is packed on
+        the host instead).  An interval with more than MAX_READS_IN_REGION reads is sampled down on the device
         (reservoir_keep_kernel, between the clip and the re-aligner); PEPPER_AMD_DEVICE_SAMPLING=0 sends it to parse_regions."""
         import numpy as np
         from pepper_amd import _lib
@@ -172,7 +173,7 @@ class UserInterfaceSupport:
             _log("INFO: STARTING THREAD: " + str(thread_id) + " FOR " + str(len(intervals)) + " INTERVALS")
         start_time = time.time()
         # (two counts among the stage times: intervals the device sampled down, intervals that took parse_regions for any reason)
-        mine = {"sampled_on_device": 0, "host_form_intervals": 0}
+        mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -196,6 +197,8 @@ class UserInterfaceSupport:
         device_sampling = _lib.device_sampling()
         sampling = (AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION) if device_sampling else None
         sampled_before = enc.sampled()[0]
+        long_cigars = _lib.device_long_cigars()
+        long_before = enc.long_cigar_reads
         safe = AlingerOptions.ALIGNMENT_SAFE_BASES
         seq_len, features = ImageSizeOptions.SEQ_LENGTH, ImageSizeOptions.IMAGE_HEIGHT
         views = {}
@@ -234,7 +237,8 @@ class UserInterfaceSupport:
                     bam_handler, fasta_handler = handles[chr_name]
                     starts, stops = [a for _, a, _ in block], [b for _, _, b in block]
                     t0 = time.perf_counter()
-                    on_device = enc.pack_device(bam_handler, chr_name, starts, stops, False, 0, laps=mine) if device_inflate else None
+                    on_device = (enc.pack_device(bam_handler, chr_name, starts, stops, False, 0, laps=mine, long_cigars=long_cigars)
+                                 if device_inflate else None)
                     resident = on_device is not None
                     n_done = 0
                     if resident:
@@ -326,6 +330,7 @@ class UserInterfaceSupport:
         finally:
             enc.inflate_ms, enc.inflated_bytes = 0.0, 0
             mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
+            mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
             enc.set_sampling(None)
             enc.release()
         if stats is not None:

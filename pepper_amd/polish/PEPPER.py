@@ -172,6 +172,7 @@ class PolishChain(object):
         n_reads, _n_pairs, arena_bytes = counts
         rows, live, chunks = np.zeros(max(1, n), np.int64), np.zeros(max(1, n), np.int32), np.zeros(max(1, n), np.int32)
         total = ctypes.c_int64()
+        pe.send_seq_offsets(n_reads, resident)
         _lib.check(self.lib.pa_polish_chain_run(
             pe.enc, n, ctypes.cast(regs, ctypes.c_void_p), None if (resident and n_reads > 0) else pe.arena.ctypes.data,
             int(arena_bytes), pe.reads.ctypes.data, int(n_reads), pe.pair_read.ctypes.data + 4 * first_pair, region_pairs.ctypes.data,

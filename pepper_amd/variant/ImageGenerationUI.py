@@ -179,7 +179,7 @@ class ImageGenerationUtils:
         generators = {}
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
         # ... and two counts: intervals the device sampled down, intervals that took the host-clipped form for any reason
-        mine = {"sampled_on_device": 0, "host_form_intervals": 0}
+        mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -262,6 +262,10 @@ class ImageGenerationUtils:
             sampling = ((AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION, float(options.downsample_rate))
                         if device_sampling else None)
             sampled_before = enc.sampled()[0]
+            # a read whose CIGAR travels in the CG tag stays in the span inflated on the device (operations from the tag, bases
+            # from the core); PEPPER_AMD_DEVICE_LONG_CIGARS=0: its group of intervals takes the host packer
+            long_cigars = _lib.device_long_cigars()
+            long_before = enc.long_cigar_reads
             g0 = 0
             while g0 < len(intervals):
                 # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last
@@ -278,7 +282,8 @@ class ImageGenerationUtils:
                 # the BGZF members inflated on the device where the BAM has an index (PEPPER_AMD_DEVICE_INFLATE=0: on the host);
                 # a batch the device form cannot take (pack_device's docstring) goes through the host packer
                 on_device = enc.pack_device(bam_handler, chr_name, [r[0] for r in regions], [r[1] for r in regions],
-                                            options.include_supplementary, options.min_mapq, laps=mine) if device_inflate else None
+                                            options.include_supplementary, options.min_mapq, laps=mine,
+                                            long_cigars=long_cigars) if device_inflate else None
                 resident = on_device is not None
                 if resident:
                     n_done, region_pairs, counts = on_device
@@ -337,6 +342,7 @@ class ImageGenerationUtils:
                 mine["inflated_bytes"] = mine.get("inflated_bytes", 0.0) + enc.inflated_bytes
             enc.inflate_ms, enc.inflated_bytes = 0.0, 0
             mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
+            mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
             enc.set_sampling(None)
             enc.release()
             t_close = time.perf_counter()

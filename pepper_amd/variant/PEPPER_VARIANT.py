@@ -264,6 +264,8 @@ class PackedEncoder(object):
     in this object's page-locked arena -- CIGAR words, 4-bit bases, qualities, once per read -- clipped to each region and
     decoded by the device.  One object per worker thread: it owns its encoder handle (stream, workspace, arena)."""
 
+    _split_walk = False             # what pa_encoder_set_split_slices was last told (off on a new handle)
+    host_walk_spans = 0             # pack_device calls that asked for the device's record walk and walked the span on the host after all
     _idle = []                      # encoders returned by release(): a later job's workers take them instead of pinning new arenas
     _idle_lock = __import__("threading").Lock()
 
@@ -318,6 +320,10 @@ class PackedEncoder(object):
         self.entries = None
         self.inflate_ms = 0.0           # device time of the inflate kernels of this object's pack_device calls
         self.inflated_bytes = 0
+        self.seq_off = None             # pack_device(long_cigars=True): where the reads with a CIGAR in the CG tag keep their bases
+        self.long_cigar_reads = 0       # such reads kept on the device path, counted once per pack_device call that kept them
+        self._split_walk = False
+        self.host_walk_spans = 0
 
     def close(self):
         if self.enc:
@@ -354,17 +360,32 @@ class PackedEncoder(object):
 
     def pack(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq):
         """-> (n_done, region_pairs, (n_reads, n_pairs, arena_bytes)): BAM_handler.pack_regions into this object's buffers."""
+        self.seq_off = None
         return bam_handler.pack_regions(contig, starts, stops, include_supplementary, min_mapq, self.arena, self.reads, self.pair_read)
 
-    def pack_device(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq, lookahead_windows=4, laps=None):
+    def send_seq_offsets(self, n_reads, resident):
+        """Before a staging call: the base offsets of the packed reads pack_device(long_cigars=True) left, if any (they describe
+        the span resident on the device, so nothing is sent for the host arena)."""
+        if resident and self.seq_off is not None and n_reads > 0:
+            _lib.check(self.lib.pa_encoder_set_seq_offsets(self.enc, self.seq_off.ctypes.data, int(n_reads)))
+        else:
+            _lib.check(self.lib.pa_encoder_set_seq_offsets(self.enc, None, 0))
+
+    def pack_device(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq, lookahead_windows=4, laps=None,
+                    long_cigars=False):
         """The same tables with the BGZF members inflated ON THE DEVICE (pa_encoder_inflate_bgzf) into the encoder's arena and
         the records left in place there: the file span of the regions' reads (BAM index) is read as it is, uploaded, inflated
         one wavefront per member, and walked on the host in a downloaded copy (headers, filters, region test -- no inflate, no
         copy).  -> (n_done, region_pairs, counts) for encode(..., resident=True), or None when the batch has to take pack():
         no index, a span larger than the arena even for one region, a record with its CIGAR in the CG tag, reads longer than
-        the span's lookahead."""
+        the span's lookahead.  long_cigars: CG records stay in the span too -- operations read from the tag, bases from the
+        core (self.seq_off, which encode(..., resident=True) and PolishChain.run pass on).  self.long_cigar_reads adds up the
+        CG reads each call kept: a read that reaches two calls' runs of regions is counted in both.  self.host_walk_spans
+        counts the calls that asked for the device's record walk and walked a downloaded copy of the span on the host instead
+        (slot overflow, an auxiliary field the device's tag walk could not follow)."""
         import time
         from pepper_amd.variant.bam import BamError
+        self.seq_off = None
         if not bam_handler.has_index():
             return None
         if self.span is None:
@@ -418,6 +439,9 @@ class PackedEncoder(object):
             # slots per entry: 2 048 records of one 16 kb window, fewer when a span has very many windows (low coverage): the
             # device keeps two 40-byte tables of entries x slots; a window that overflows its slots takes the host walk
             slots = max(64, min(2048, (32 << 20) // (40 * max(1, n_entries))))
+            if bool(long_cigars) != self._split_walk:
+                _lib.check(self.lib.pa_encoder_set_split_slices(self.enc, 1 if long_cigars else 0))
+                self._split_walk = bool(long_cigars)
             try:
                 _lib.check(self.lib.pa_encoder_walk_records(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots,
                                                             self.headers.ctypes.data, len(self.headers), ctypes.byref(n_headers),
@@ -430,16 +454,28 @@ class PackedEncoder(object):
                 headers = n_headers.value
             else:
                 inflate(True)                        # (a window with more records than a lane's slots, ...: the span to the host after all)
+                self.host_walk_spans += 1
             if laps is not None:
                 laps["bam_walk_device"] = laps.get("bam_walk_device", 0.0) + time.perf_counter() - t0
                 t0 = time.perf_counter()
         try:
             if headers is not None:
-                n_done, region_pairs, counts = bam_handler.pack_headers(self.headers, headers, final, contig, starts[:n], stops[:n],
-                                                                        include_supplementary, min_mapq, self.reads, self.pair_read)
-            else:
+                try:
+                    n_done, region_pairs, counts = bam_handler.pack_headers(self.headers, headers, final, contig, starts[:n], stops[:n],
+                                                                            include_supplementary, min_mapq, self.reads, self.pair_read,
+                                                                            long_cigars=long_cigars)
+                except BamError as err:
+                    if not (long_cigars and getattr(err, "code", 0) == -6):
+                        raise
+                    # (state 2 may be an auxiliary field the device's tag walk could not follow: the host's walk of the
+                    # span decides -- it keeps such a record with its core CIGAR, and fails on a corrupt one as before)
+                    inflate(True)
+                    headers = None
+                    self.host_walk_spans += 1
+            if headers is None:
                 n_done, region_pairs, counts = bam_handler.pack_inflated(self.arena, out_bytes, first, final, contig, starts[:n], stops[:n],
-                                                                         include_supplementary, min_mapq, self.reads, self.pair_read)
+                                                                         include_supplementary, min_mapq, self.reads, self.pair_read,
+                                                                         long_cigars=long_cigars)
         except BamError as err:
             if getattr(err, "code", 0) in (-7, -8, -9):
                 return None
@@ -447,6 +483,11 @@ class PackedEncoder(object):
         finally:
             if laps is not None:
                 laps["bam_walk"] = laps.get("bam_walk", 0.0) + time.perf_counter() - t0
+        if long_cigars and counts[0] > 0:
+            seq_off, n_split = bam_handler.split_offsets(counts[0])
+            if n_split:
+                self.seq_off = seq_off
+                self.long_cigar_reads += n_split
         return n_done, region_pairs, (counts[0], counts[1], int(out_bytes))
 
     def encode(self, regions, references, region_pairs, counts, params, candidate_regions, candidate_window_size=32, feature_size=26,
@@ -472,6 +513,7 @@ class PackedEncoder(object):
         region_pairs = np.ascontiguousarray(region_pairs[:n + 1], np.int32)
         n_reads, _n_pairs, arena_bytes = counts
         # resident: the arena is the inflated span pack_device left on the device
+        self.send_seq_offsets(n_reads, resident)
         _lib.check(self.lib.pa_encoder_stage_packed(self.enc, n, ctypes.cast(regs, ctypes.c_void_p), ctypes.cast(pars, ctypes.c_void_p),
                                                     None if (resident and n_reads > 0) else self.arena.ctypes.data,
                                                     int(arena_bytes), self.reads.ctypes.data, int(n_reads),

@@ -42,6 +42,8 @@ SYMBOLS = [
     ("pa_bam_pack_inflated", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_char_p, c_int32, c_void_p, c_void_p,
                                             c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                             ctypes.POINTER(c_int32), c_void_p]),
+    ("pa_bam_set_split_slices", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_bam_split_offsets", ctypes.c_int, [c_void_p, c_void_p, c_int32, ctypes.POINTER(c_int32)]),
     ("pa_reservoir_sample", ctypes.c_int, [ctypes.c_uint32, c_int64, c_int64, c_void_p]),
 ]
 _bound = False
@@ -254,9 +256,23 @@ class BAM_handler(object):
                                           entries.ctypes.data, len(entries), ctypes.byref(n)))
         return n.value
 
+    def set_split_slices(self, on):
+        """pa_bam_set_split_slices: pack_inflated / pack_headers keep a record whose CIGAR travels in the CG tag (off: -8)."""
+        _check(_lib().pa_bam_set_split_slices(self._h, 1 if on else 0))
+
+    def split_offsets(self, n_reads):
+        """pa_bam_split_offsets -> (int64 [n_reads]: where each read of the last packed walk keeps its bases, -1 = behind its
+        operations; how many are not -1)."""
+        seq_off = np.full(max(1, int(n_reads)), -1, np.int64)
+        n_split = c_int32()
+        _check(_lib().pa_bam_split_offsets(self._h, seq_off.ctypes.data, int(n_reads), ctypes.byref(n_split)))
+        return seq_off[:int(n_reads)], n_split.value
+
     def pack_headers(self, headers, n_headers, data_is_final, chromosome, starts, stops, include_supplementary, min_mapq, reads,
-                     pair_read):
-        """pa_bam_pack_headers: pack_inflated's tables from the record headers the device read out (array of RECORD_HEADER)."""
+                     pair_read, long_cigars=False):
+        """pa_bam_pack_headers: pack_inflated's tables from the record headers the device read out (array of RECORD_HEADER).
+        long_cigars: records with their CIGAR in the CG tag are kept (split_offsets() then says where their bases lie)."""
+        self.set_split_slices(long_cigars)
         starts = np.ascontiguousarray(starts, np.int64)
         stops = np.ascontiguousarray(stops, np.int64)
         n = len(starts)
@@ -270,8 +286,10 @@ class BAM_handler(object):
         return n_done.value, region_pairs, (int(counts[0]), int(counts[1]), int(counts[2]))
 
     def pack_inflated(self, data, data_bytes, first_record, data_is_final, chromosome, starts, stops, include_supplementary,
-                      min_mapq, reads, pair_read):
-        """pa_bam_pack_inflated: pack_regions' tables over an inflated span (`data`: uint8 array), records left in place."""
+                      min_mapq, reads, pair_read, long_cigars=False):
+        """pa_bam_pack_inflated: pack_regions' tables over an inflated span (`data`: uint8 array), records left in place.
+        long_cigars: as for pack_headers."""
+        self.set_split_slices(long_cigars)
         starts = np.ascontiguousarray(starts, np.int64)
         stops = np.ascontiguousarray(stops, np.int64)
         n = len(starts)

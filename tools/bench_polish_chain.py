@@ -1,7 +1,7 @@
 """Polish image generation rate through the device-resident chain: BAM + draft -> image HDF5 files through
 pepper_amd.polish.make_images.make_images (pepper polish's first step, /root/reference/pepper/modules/python/make_images.py).
 
-  python tools/bench_polish_chain.py make_fast <dir> [draft_bases=16000000] [coverage=60]     synthetic data set (tools/synth_bam)
+  python tools/bench_polish_chain.py make_fast <dir> [draft_bases=16000000] [coverage=60] [seed=2027] [cg_ppm=0]     synthetic data set (tools/synth_bam)
   python tools/bench_polish_chain.py run <dir> [threads,threads,...] [regions_per_call]       GPU; one JSON line
 
 `run` reports, per thread count, wall time, Mb of draft per second, intervals per second, reads re-aligned per second and the stage
@@ -18,9 +18,9 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
 
-def make_fast(out, bases=16000000, coverage=60, seed=2027):
+def make_fast(out, bases=16000000, coverage=60, seed=2027, cg_ppm=0):
     from bench_variant_images import make_fast as mk
-    return mk(out, bases, coverage, seed)
+    return mk(out, bases, coverage, seed, cg_ppm=cg_ppm)
 
 
 def run(data, thread_counts=(8,), regions_per_call=None, warm=True):
@@ -60,7 +60,7 @@ def run(data, thread_counts=(8,), regions_per_call=None, warm=True):
 if __name__ == "__main__":
     sys.path.insert(0, os.path.join(REPO, "tools"))
     if sys.argv[1] == "make_fast":
-        print(json.dumps(make_fast(sys.argv[2], *(float(a) for a in sys.argv[3:5]))))
+        print(json.dumps(make_fast(sys.argv[2], *(float(a) for a in sys.argv[3:7]))))
     else:
         counts = tuple(int(t) for t in sys.argv[3].split(",")) if len(sys.argv) > 3 else (8,)
         print(json.dumps(run(sys.argv[2], counts, int(sys.argv[4]) if len(sys.argv) > 4 else None)))

@@ -74,7 +74,7 @@ struct Piece {
     int64_t n_bases = 0;
 };
 
-int g_level = 1, g_tags = 0, g_quals = 0;
+int g_level = 1, g_tags = 0, g_quals = 0, g_cg_ppm = 0;
 
 struct Deflater {
 #ifdef PA_HAVE_LIBDEFLATE
@@ -250,10 +250,15 @@ void make_piece(const Genome& g, int tid, int64_t lo, int64_t hi, double coverag
         const uint32_t mapq = rng.below(100) < 2 ? 0 : 60;
         const int l_name = snprintf(name, sizeof name, "r%d_%lld_%lld", tid, (long long)lo, (long long)k) + 1;
         const uint32_t n_cig = (uint32_t)cigar.size();
-        // aux data as aligners write it: NM:i (uint16), MD:Z, RG:Z
-        const uint32_t aux_bytes = g_tags ? (3 + 2) + (3 + (uint32_t)md.size() + 1) + (3 + 4) : 0;
-        const uint32_t body = 32 + (uint32_t)l_name + 4 * std::min<uint32_t>(n_cig, 65535u) + (l_seq + 1) / 2 + l_seq + aux_bytes;
         if (n_cig > 65535) continue;                 // (never with these lengths)
+        // cg_ppm: this share of the reads is written the way a writer stores more than 65535 operations (SAM specification
+        // 4.2.2): <l_seq>S<ref_len>N in the core, the operations in a CG:B,I tag behind the other aux data (chosen by a hash
+        // of the read's place, not by a draw: the reads are those of the file without the option)
+        const bool cg_form = g_cg_ppm > 0 && site_hash((uint64_t)tid, (uint64_t)pos * 8191u + (uint64_t)k, seed ^ 0x4347u) % 1000000u < (uint64_t)g_cg_ppm;
+        const uint32_t n_core = cg_form ? 2u : n_cig;
+        // aux data as aligners write it: NM:i (uint16), MD:Z, RG:Z
+        const uint32_t aux_bytes = (g_tags ? (3 + 2) + (3 + (uint32_t)md.size() + 1) + (3 + 4) : 0) + (cg_form ? 8 + 4 * n_cig : 0);
+        const uint32_t body = 32 + (uint32_t)l_name + 4 * n_core + (l_seq + 1) / 2 + l_seq + aux_bytes;
         rec.resize(4 + body);
         uint8_t* p = rec.data();
         auto w32 = [&](uint32_t v) { std::memcpy(p, &v, 4); p += 4; };
@@ -261,15 +266,20 @@ void make_piece(const Genome& g, int tid, int64_t lo, int64_t hi, double coverag
         w32((uint32_t)tid);
         w32((uint32_t)pos);
         w32((uint32_t)l_name | (mapq << 8) | ((uint32_t)reg2bin(pos, end) << 16));
-        w32(n_cig | (flag << 16));
+        w32(n_core | (flag << 16));
         w32(l_seq);
         w32(0xffffffffu);
         w32(0xffffffffu);
         w32(0);
         std::memcpy(p, name, (size_t)l_name);
         p += l_name;
-        std::memcpy(p, cigar.data(), 4ull * n_cig);
-        p += 4ull * n_cig;
+        if (cg_form) {
+            w32((l_seq << 4) | 4u);
+            w32(((uint32_t)(end - pos) << 4) | 3u);
+        } else {
+            std::memcpy(p, cigar.data(), 4ull * n_cig);
+            p += 4ull * n_cig;
+        }
         for (uint32_t i = 0; i + 1 < l_seq; i += 2) *p++ = (uint8_t)((kCode[bases[i]] << 4) | kCode[bases[i + 1]]);
         if (l_seq & 1) *p++ = (uint8_t)(kCode[bases[l_seq - 1]] << 4);
         std::memcpy(p, quals.data(), l_seq);
@@ -283,6 +293,12 @@ void make_piece(const Genome& g, int tid, int64_t lo, int64_t hi, double coverag
             *p++ = 0;
             std::memcpy(p, "RGZ", 3); p += 3;
             std::memcpy(p, "rg1", 4); p += 4;
+        }
+        if (cg_form) {
+            std::memcpy(p, "CGBI", 4); p += 4;
+            w32(n_cig);
+            std::memcpy(p, cigar.data(), 4ull * n_cig);
+            p += 4ull * n_cig;
         }
         // the record starts in block n_blocks + (bytes waiting) / 0xff00 of this piece
         const uint64_t waiting = raw.size();
@@ -298,7 +314,7 @@ void make_piece(const Genome& g, int tid, int64_t lo, int64_t hi, double coverag
 
 int main(int argc, char** argv) {
     if (argc < 3) {
-        fprintf(stderr, "usage: synth_bam <out_dir> <genome_bases> [coverage=60] [seed=2027] [threads=0] [contigs=1]\n");
+        fprintf(stderr, "usage: synth_bam <out_dir> <genome_bases> [coverage=60] [seed=2027] [threads=0] [contigs=1] [level=1] [tags=0] [quals=0] [cg_ppm=0]\n");
         return 2;
     }
     const std::string dir = argv[1];
@@ -310,6 +326,7 @@ int main(int argc, char** argv) {
     g_level = argc > 7 ? std::max(1, std::min(9, atoi(argv[7]))) : 1;
     g_tags = argc > 8 ? atoi(argv[8]) != 0 : 0;
     g_quals = argc > 9 ? atoi(argv[9]) : 0;
+    g_cg_ppm = argc > 10 ? std::max(0, atoi(argv[10])) : 0;
     if (threads <= 0) threads = std::max(1u, std::thread::hardware_concurrency());
     if (FILE* fh = fopen("/sys/fs/cgroup/cpu.max", "r")) {       // a cgroup quota below the hardware's thread count
         char quota[32] = {0};
