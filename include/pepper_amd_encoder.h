@@ -164,10 +164,25 @@ int pa_encoder_set_sampling(pa_encoder* e, uint32_t seed, int32_t max_reads, dou
 int pa_encoder_sampled_regions(pa_encoder* e, int64_t* regions, int64_t* reads_dropped);
 int pa_encoder_pair_live(pa_encoder* e, uint8_t* keep, int64_t n);
 
+/* The candidates of a run enumerated ON THE DEVICE (off on a new handle; callable between calls; holds for every variant form:
+ * pa_encoder_generate_summary[_batch], pa_encoder_run_staged after pa_encoder_stage_batch or pa_encoder_stage_packed).  Off, a run
+ * waits for its counts, copies sites, votes, the rare-alphabet list and the allele pool to the host, orders and enumerates them
+ * there, uploads the candidate table and waits again for the windows.  On, group_votes_kernel and enumerate_sites_kernel
+ * (csrc/encoder.hip; order and rule from csrc/candidates.h, the text the host enumeration is compiled from) produce the same
+ * table, positions, depths, frequencies and names in device memory and the window gather follows in the same submission: one
+ * wait per run, results byte for byte those of the host enumeration.  pa_encoder_get_results fetches the lists from the device
+ * when asked.  A run the kernels do not take -- a site with more than 1024 indel votes, or with more than twelve distinct read
+ * letters outside ACGT -- is enumerated on the host exactly as with the switch off, after the one wait.
+ * pa_encoder_candidate_calls: runs of this handle (switch on) enumerated on the device / handed back to the host; either may be
+ * NULL. */
+int pa_encoder_set_device_candidates(pa_encoder* e, int32_t on);
+int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host);
+
 /* Times of the last run in milliseconds, HIP events on the encoder's stream: [0] record kernels (segment_reads x 2 +
  * tile_offsets), [1] tile_count_kernel, [2] compact_votes_kernel + pack_results_kernel, [3] gather_windows_kernel; host clock:
  * [4] candidate enumeration, [5] the whole run, [6], [7] parts of [4]; packed form: [8] upload of arena + tables,
- * [9] unpack_clip_kernel.  Sizes of the staged batch: [0] read bases, [1] matrix rows,
+ * [9] unpack_clip_kernel; [12] the device enumeration (group_votes_kernel, enumerate_sites_kernel and the scans between them;
+ * [4], [6], [7] are 0 for a run it served, [12] is 0 for every other run).  Sizes of the staged batch: [0] read bases, [1] matrix rows,
  * [2] reads, [3] CIGAR operations, [4] tiles, [5] regions. */
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n);
 int pa_encoder_batch_stats(pa_encoder* e, int64_t* out, int32_t n);

@@ -85,6 +85,8 @@ SYMBOLS = [
     ("pa_encoder_set_sampling", ctypes.c_int, [c_void_p, ctypes.c_uint32, c_int32, c_double]),
     ("pa_encoder_sampled_regions", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     ("pa_encoder_pair_live", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
+    ("pa_encoder_set_device_candidates", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_encoder_candidate_calls", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     ("pa_encoder_last_timing", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_batch_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_get_results", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -208,6 +210,15 @@ def device_long_cigars():
     """PEPPER_AMD_DEVICE_LONG_CIGARS=0: the image-generation drivers send a batch with a CIGAR kept in the CG tag through the
     host packer again."""
     return os.environ.get(DEVICE_LONG_CIGARS_ENV, "1") != "0"
+
+
+DEVICE_CANDIDATES_ENV = "PEPPER_AMD_DEVICE_CANDIDATES"
+
+
+def device_candidates():
+    """PEPPER_AMD_DEVICE_CANDIDATES=1: the image-generation drivers have their encoders enumerate candidates on the device
+    (pa_encoder_set_device_candidates).  Unset or any other value: on the host."""
+    return os.environ.get(DEVICE_CANDIDATES_ENV, "0") == "1"
 
 
 def check(rc):

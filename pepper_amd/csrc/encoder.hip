@@ -41,13 +41,16 @@
 
 #include "../../include/pepper_amd_realign.h"
 #include "encoder_common.h"
+#include "candidates.h"
 #include "reservoir.h"
 
 using namespace pa_enc;
+using pa_cand::SiteRec; using pa_cand::Vote; using pa_cand::CandDesc; using pa_cand::Tally; using pa_cand::AlleleSrc;
+using pa_cand::is_acgt; using pa_cand::up; using pa_cand::symbol_column; using pa_cand::base_code;
 
 namespace {
 
-constexpr int MAXC = 125;
+constexpr int MAXC = pa_cand::MAXC;
 constexpr int TP = 512;             // rows per tile = threads of a tile_count_kernel workgroup
 constexpr int MATF = 26;            // int32 per matrix row in HBM (the image columns)
 constexpr int NCNT = 28;            // privatised counters per row
@@ -63,7 +66,7 @@ static_assert(VCAP == NT, "the flush takes one buffered vote per thread");
 enum { K_COV = 0, K_SNP = 1, K_INS = 2, K_DEL = 3, K_FWD = 4, K_REV = 12, K_TAB = 20 };
 // counters of a run
 enum { CT_OVF = 0, CT_VOTES = 2, CT_ERR = 3, CT_POOL = 4, CT_N = 8 };
-constexpr int POOL_SLOT = 64;       // bytes per pooled allele (an allele is at most 61 bytes, region_summary.cpp:455)
+constexpr int POOL_SLOT = pa_cand::POOL_SLOT;
 // per region, behind them: [2 r] passing sites, [2 r + 1] votes of passing sites -- both lists are written region by region
 // (sites of region r from row_base, votes from vote_base), so the host never has to sort a batch's records by region
 
@@ -79,50 +82,9 @@ struct RegRec {                      // one region of the batch, as the kernels 
     double min_snp_q, min_indel_q, snp_thr, ins_thr, del_thr, min_cov;
 };
 struct TileRec { int32_t read, op, row, ri; };   // walk of `read` enters the tile at operation `op`, whose first row / read index are given
-struct SiteRec { int32_t region, idx, cov, flags, fwd[4], rev[4]; };
-// meta = type (1 insert, 2 delete) | reverse << 2 | from_ref << 3 | len << 4 | region << 10; prefix = the first 8 bytes of the allele,
-// first byte in the top bits (compares like the string), filled for the votes of passing rows: the host orders alleles without touching
-// the reads unless two of them agree on 8 bytes
-struct Vote { uint32_t idx, meta; int64_t off; uint64_t prefix; };
-struct CandDesc {
-    int32_t idx, type;        // row of the candidate site; 1 SNP, 2 insert, 3 delete
-    int32_t vcol, vval;       // columns 1/2/3 <- alt base code / allele length
-    int32_t fwd, rev;         // strand allele depths (<= 125) for columns 5..7 / 16..18
-    int32_t neg_f, neg_r;     // columns negated on the centre row (-1: none)
-    int32_t last;             // delete: last spill row of the window (else -1)
-    int32_t star_f, star_r;   // delete: '*' columns negated on spill rows
-    int32_t region;
-};
+// SiteRec, Vote, CandDesc: candidates.h
 
-__host__ __device__ inline bool is_acgt(char c) {
-    c &= ~0x20;
-    return c == 'A' || c == 'C' || c == 'G' || c == 'T';
-}
-__host__ __device__ inline int up(char c) { return (c >= 'a' && c <= 'z') ? c - 32 : c; }
-// column of `symbol` for a strand, -1 if the reference base is not A/C/G/T (region_summary.cpp:201-230)
-__host__ __device__ inline int symbol_column(char ref_base, char symbol, bool reverse) {
-    if (!is_acgt(ref_base)) return -1;
-    const int first = reverse ? 19 : 8;
-    switch (up(symbol)) {
-        case 'A': return first;
-        case 'C': return first + 1;
-        case 'G': return first + 2;
-        case 'T': return first + 3;
-        case 'I': return first + 4;
-        case 'D': return first + 5;
-        default: return first + 6;
-    }
-}
 __device__ __forceinline__ int column_slot(int col) { return col < 15 ? col - 3 : col - 6; }   // columns 8..14 / 19..25
-__host__ __device__ inline int base_code(char c) {
-    switch (up(c)) {
-        case 'A': return 1;
-        case 'C': return 2;
-        case 'G': return 3;
-        case 'T': return 4;
-        default: return 5;
-    }
-}
 
 // ---- records: where the walk of each (read, tile) starts -----------------------------------------------------------
 // Two passes of the same walk: FILL = false counts the records of every tile (atomics spread over the tiles), an exclusive
@@ -985,13 +947,13 @@ __global__ __launch_bounds__(256) void pack_results_kernel(const RegRec* __restr
 }
 
 // one 64-lane workgroup per candidate: 33 x 26 = 858 cells
-__global__ __launch_bounds__(64) void gather_windows_kernel(const int* __restrict__ mat, const RegRec* __restrict__ regions,
-                                                            const CandDesc* __restrict__ cands, int W, int F, int mid,
-                                                            int* __restrict__ out32, int8_t* __restrict__ out8) {
-    const CandDesc cd = cands[blockIdx.x];
+__device__ __forceinline__ void gather_window(const int* __restrict__ mat, const RegRec* __restrict__ regions,
+                                              const CandDesc* __restrict__ cands, int c, int W, int F, int mid,
+                                              int* __restrict__ out32, int8_t* __restrict__ out8) {
+    const CandDesc cd = cands[c];
     const int L = regions[cd.region].L;
     const int* m = mat + regions[cd.region].row_base * MATF;
-    const size_t base = (size_t)blockIdx.x * W * F;
+    const size_t base = (size_t)c * W * F;
     for (int e = threadIdx.x; e < W * F; e += 64) {
         const int r = e / F, f = e - r * F;
         const int row = cd.idx - mid + r;
@@ -1011,8 +973,246 @@ __global__ __launch_bounds__(64) void gather_windows_kernel(const int* __restric
         out8[base + e] = (int8_t)v;                        // two's-complement wrap, as numpy 1.22's int8 cast
     }
 }
+__global__ __launch_bounds__(64) void gather_windows_kernel(const int* __restrict__ mat, const RegRec* __restrict__ regions,
+                                                            const CandDesc* __restrict__ cands, int W, int F, int mid,
+                                                            int* __restrict__ out32, int8_t* __restrict__ out8) {
+    gather_window(mat, regions, cands, (int)blockIdx.x, W, F, mid, out32, out8);
+}
 
-struct Tally { int total = 0, fwd = 0, rev = 0; };
+// ---- candidates enumerated on the device (pa_encoder_set_device_candidates) -------------------------------------------------
+// What enumerate_region does on the host, between pack_results_kernel and the window gather, without a copy or a wait:
+//   group_votes_kernel       one workgroup per region: every passing row learns its slot in the dense site list, the region's
+//                            votes are counted per site and moved into one slice per site (a counting sort by site; the order
+//                            of the slices and inside them is whatever the atomics give -- nothing below depends on it), the
+//                            rare-alphabet entries are chained to their sites
+//   enumerate_sites_kernel   one wavefront per site.  COUNT form: the site's votes into LDS, a bitonic sort under vote_less
+//                            (candidates.h: the full order, tails in the reference / the pool included), written back sorted;
+//                            runs of same_allele are tallied, the rule (candidates.h: accepted) decides, and the site's number of
+//                            candidates and name bytes are added to its 512-row tile's totals.  WRITE form, after an exclusive scan
+//                            of the tile totals (tile_offsets_kernel): the same walk over the sorted slice, each accepted allele
+//                            written at tile offset + candidates of the tile's earlier rows + its rank in the site -- ascending
+//                            rows of ascending regions, the host's order.  Two instances of each form: sites of at most 64
+//                            votes (1.5 kB of LDS, nearly all of them), striding over the dense site list, and of 65 ..
+//                            CAND_SITE_MAX votes (24 kB), striding over the list of such sites that group_votes_kernel
+//                            leaves (a batch without one: its workgroups return at once).
+//   gather_windows_n_kernel  gather_windows_kernel over a count that is only known on the device
+// A call the kernels cannot take -- a site with more than CAND_SITE_MAX votes, or more than twelve rare letters -- raises
+// CI_REFUSED: nothing is written and the host enumerates that call.  More candidates than the buffers hold: nothing is written,
+// the host grows them and runs the call again.
+constexpr int CAND_SITE_MAX = 1024;
+enum { CI_SITES = 0, CI_REFUSED = 1, CI_LARGE = 2, CI_N = 4 };   // cinfo: passing sites of the batch | the call is refused | sites of more than 64 votes
+struct SiteAux { int32_t v0, nv, fill, rare, nc, nb, pad0, pad1; };   // slice of the grouped votes, cursor, head of the rare chain (-1: none), candidates, name bytes
+struct CandArgs {
+    const RegRec* regions; const pa_cand::Rule* rules; int n_regions, n_tiles;
+    const int* counters; const int* region_counts; const int* n_recs; int rec_cap, ovf_cap, pool_cap, vote_cap;
+    const SiteRec* sites; const Vote* votes; Vote* grouped; const int4* ovf; int* rare_next;
+    const char* ref; const char* pool; const uint8_t* pass; int* row_slot; SiteAux* aux; int* large;
+    int* cinfo; int* tile_nc; int* tile_nb; const int* tile_c0; const int* tile_b0;
+    int cand_cap, mid;
+    CandDesc* cands; int64_t* positions; int32_t* depths; int32_t* freqs; char* names;
+};
+// the call will be run again with larger buffers, or fails: its lists are not complete (pool slots past pool_cap were never
+// written), so nothing here reads them
+__device__ __forceinline__ bool cand_call_void(const CandArgs& a) {
+    return a.counters[CT_OVF] > a.ovf_cap || a.counters[CT_POOL] > a.pool_cap || *a.n_recs > a.rec_cap || a.counters[CT_ERR] > 0 ||
+           a.counters[CT_VOTES] > a.vote_cap;
+}
+// ... or the device enumeration of it has nothing to write
+__device__ __forceinline__ bool cand_no_output(const CandArgs& a) {
+    return cand_call_void(a) || a.cinfo[CI_REFUSED] != 0 || a.tile_c0[a.n_tiles] > a.cand_cap;
+}
+
+__global__ __launch_bounds__(1024) void group_votes_kernel(CandArgs a) {
+    if (cand_call_void(a)) return;
+    __shared__ int off[3];
+    const int r = blockIdx.x, tid = threadIdx.x;
+    if (tid < 3) off[tid] = 0;
+    __syncthreads();
+    int s = 0, v = 0;
+    for (int q = tid; q < r; q += 1024) {
+        s += a.region_counts[2 * q];
+        v += a.region_counts[2 * q + 1];
+    }
+    if (s) atomicAdd(&off[0], s);
+    if (v) atomicAdd(&off[1], v);
+    __syncthreads();
+    const int s_off = off[0], v_off = off[1];
+    const int ns = a.region_counts[2 * r], nv = a.region_counts[2 * r + 1];
+    const RegRec reg = a.regions[r];
+    for (int i = tid; i < ns; i += 1024) {
+        a.row_slot[reg.row_base + a.sites[s_off + i].idx] = s_off + i;
+        a.aux[s_off + i] = SiteAux{0, 0, 0, -1, 0, 0, 0, 0};
+    }
+    __syncthreads();
+    for (int j = tid; j < nv; j += 1024) atomicAdd(&a.aux[a.row_slot[reg.row_base + a.votes[v_off + j].idx]].nv, 1);
+    // every region's workgroup reads the whole rare-alphabet list of the batch for its own entries: regions x entries, with a
+    // handful of entries per batch (read letters outside ACGT on passing rows).  Piles rich in N would want a bucket per region.
+    const int n_ovf = a.counters[CT_OVF];
+    for (int k = tid; k < n_ovf; k += 1024) {
+        const int4 o = a.ovf[k];
+        if (o.w == r && o.x >= 0 && o.x < reg.L && a.pass[reg.row_base + o.x])
+            a.rare_next[k] = atomicExch(&a.aux[a.row_slot[reg.row_base + o.x]].rare, k);
+    }
+    __syncthreads();
+    for (int i = tid; i < ns; i += 1024) {
+        const int n = atomicAdd(&a.aux[s_off + i].nv, 0);
+        a.aux[s_off + i].v0 = v_off + atomicAdd(&off[2], n);      // (off[2] ends at nv: every vote of a region lies on a passing row)
+        if (n > 64) a.large[atomicAdd(&a.cinfo[CI_LARGE], 1)] = s_off + i;   // (in no fixed order: a site's place in the output comes from its row)
+    }
+    __syncthreads();
+    for (int j = tid; j < nv; j += 1024) {
+        const Vote vt = a.votes[v_off + j];
+        SiteAux* x = &a.aux[a.row_slot[reg.row_base + vt.idx]];
+        a.grouped[x->v0 + atomicAdd(&x->fill, 1)] = vt;
+    }
+    if (r == (int)gridDim.x - 1 && tid == 0) a.cinfo[CI_SITES] = s_off + ns;
+}
+
+template <int CAP, bool WRITE>
+__global__ __launch_bounds__(64) void enumerate_sites_kernel(CandArgs a) {
+    if (WRITE ? cand_no_output(a) : cand_call_void(a)) return;
+    __shared__ Vote sv[CAP];
+    __shared__ pa_cand::SnpAllele s_snp[pa_cand::SNP_MAX];
+    __shared__ int s_nsnp;
+    const int lane = threadIdx.x;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int n_sites = a.cinfo[CAP == 64 ? CI_SITES : CI_LARGE];
+    for (int q = blockIdx.x; q < n_sites; q += gridDim.x) {
+        __syncthreads();                                   // the LDS of the previous site is free
+        const int s = CAP == 64 ? q : a.large[q];
+        const SiteAux aux = a.aux[s];
+        const int nv = aux.nv;
+        if (CAP == 64 && nv > 64) continue;                // the other instance's site
+        if (nv > CAP) {
+            if (!WRITE && lane == 0) a.cinfo[CI_REFUSED] = 1;
+            continue;
+        }
+        if (WRITE && aux.nc == 0) continue;
+        const SiteRec site = a.sites[s];
+        const RegRec reg = a.regions[site.region];
+        const pa_cand::Rule rule = a.rules[site.region];
+        const AlleleSrc src{a.ref + reg.ref_off, a.pool};
+        const int depth = pa_cand::clamp_count(site.cov);
+        const char rb = site.idx < reg.ref_len ? src.reference[site.idx] : 'N';
+        const int tile = reg.tile0 + site.idx / TP;
+        // where the site's candidates and names go: the tile's offset + what the tile's earlier rows hold
+        int c_at = 0, b_at = 0;
+        if (WRITE) {
+            for (int row = (site.idx / TP) * TP + lane; row < site.idx; row += 64)
+                if (a.pass[reg.row_base + row]) {
+                    const SiteAux& x = a.aux[a.row_slot[reg.row_base + row]];
+                    c_at += x.nc;
+                    b_at += x.nb;
+                }
+            c_at = a.tile_c0[tile] + wave_sum(c_at);
+            b_at = a.tile_b0[tile] + wave_sum(b_at);
+        }
+        if (lane == 0) {
+            int n = pa_cand::snp_from_site(site, s_snp);
+            if (aux.rare >= 0) {
+                bool full = false;
+                for (int k = aux.rare; k >= 0; k = a.rare_next[k]) {
+                    const int4 o = a.ovf[k];
+                    if (!pa_cand::snp_merge(s_snp, n, (char)o.y, 1, o.z ? 0 : 1, o.z ? 1 : 0)) full = true;
+                }
+                pa_cand::snp_sort(s_snp, n);
+                if (full && !WRITE) a.cinfo[CI_REFUSED] = 1;      // (which letters the host drops depends on its own order)
+            }
+            s_nsnp = n;
+        }
+        int P = 1;
+        while (P < nv) P <<= 1;
+        for (int k = lane; k < P; k += 64) sv[k] = k < nv ? a.grouped[aux.v0 + k] : Vote{0xffffffffu, 0u, 0, 0ull};   // (a row no site has: sorts last)
+        __syncthreads();
+        if (!WRITE && nv > 1) {
+            for (int k2 = 2; k2 <= P; k2 <<= 1)
+                for (int j = k2 >> 1; j > 0; j >>= 1) {
+                    for (int i = lane; i < P; i += 64) {
+                        const int m = i ^ j;
+                        if (m > i) {
+                            const Vote x = sv[i], y = sv[m];
+                            if ((i & k2) == 0 ? vote_less(y, x, src) : vote_less(x, y, src)) {
+                                sv[i] = y;
+                                sv[m] = x;
+                            }
+                        }
+                    }
+                    __syncthreads();
+                }
+            for (int k = lane; k < nv; k += 64) a.grouped[aux.v0 + k] = sv[k];
+        }
+        // SNP alleles first, one per lane
+        int n_c = 0, n_b = 0;
+        {
+            const bool acc = lane < s_nsnp && pa_cand::accepted(1, s_snp[lane < s_nsnp ? lane : 0].t, depth, site.flags, rule);
+            const unsigned long long m = __ballot(acc);
+            if (WRITE && acc) {
+                const pa_cand::SnpAllele al = s_snp[lane];
+                const int c = c_at + __popcll(m & below);
+                char* name = a.names + b_at + 3 * __popcll(m & below);
+                a.cands[c] = pa_cand::snp_desc(site.region, site.idx, rb, al.base, al.t);
+                a.positions[c] = rule.region_start + site.idx;
+                a.depths[c] = depth;
+                a.freqs[c] = pa_cand::clamp_count(al.t.total);
+                name[0] = '1';
+                name[1] = al.base;
+                name[2] = 0;
+            }
+            n_c = __popcll(m);
+            n_b = 3 * n_c;
+        }
+        // then the runs of equal alleles in the sorted votes: the lane at a run's first vote tallies it
+        for (int k0 = 0; k0 < nv; k0 += 64) {
+            const int k = k0 + lane;
+            Tally t{0, 0, 0};
+            bool acc = false;
+            int type = 0, alen = 0;
+            if (k < nv && (k == 0 || !same_allele(sv[k], sv[k - 1], src))) {
+                const Vote v = sv[k];
+                for (int k1 = k; k1 < nv && (k1 == k || same_allele(sv[k1], v, src)); ++k1) {
+                    t.total += 1;
+                    ((sv[k1].meta & 4u) ? t.rev : t.fwd) += 1;
+                }
+                type = (v.meta & 3u) == 1u ? 2 : 3;
+                alen = (int)pa_cand::allele_len(v);
+                acc = pa_cand::accepted(type, t, depth, site.flags, rule);
+            }
+            const unsigned long long m = __ballot(acc);
+            const int bytes = acc ? alen + 2 : 0;
+            const int inc = wave_inclusive_sum(bytes);
+            if (WRITE && acc) {
+                const Vote v = sv[k];
+                const int c = c_at + n_c + __popcll(m & below);
+                char* name = a.names + b_at + n_b + inc - bytes;
+                a.cands[c] = pa_cand::indel_desc(site.region, site.idx, rb, type, alen, t, a.mid, rule);
+                a.positions[c] = rule.region_start + site.idx;
+                a.depths[c] = depth;
+                a.freqs[c] = pa_cand::clamp_count(t.total);
+                name[0] = (char)('0' + type);
+                pa_cand::copy_allele(name + 1, v, src);
+                name[1 + alen] = 0;
+            }
+            n_c += __popcll(m);
+            n_b += wave_total(inc);
+        }
+        if (!WRITE && lane == 0) {
+            a.aux[s].nc = n_c;
+            a.aux[s].nb = n_b;
+            if (n_c) {
+                atomicAdd(&a.tile_nc[tile], n_c);
+                atomicAdd(&a.tile_nb[tile], n_b);
+            }
+        }
+    }
+}
+
+// gather_windows_kernel for a count on the device: a fixed grid strides over the candidates
+__global__ __launch_bounds__(64) void gather_windows_n_kernel(CandArgs a, const int* __restrict__ mat, int W, int F,
+                                                              int* __restrict__ out32, int8_t* __restrict__ out8) {
+    if (cand_no_output(a)) return;
+    const int n = a.tile_c0[a.n_tiles];
+    for (int c = blockIdx.x; c < n; c += gridDim.x) gather_window(mat, a.regions, a.cands, c, W, F, a.mid, out32, out8);
+}
 
 struct RegHost {
     pa_pileup p;
@@ -1129,6 +1329,15 @@ struct pa_variant_batch {
     DBuf d_zero;                      // counters [CT_N] | per-region counts [2 n_regions] | tile_count [n_tiles] | tile_fill [n_tiles]: cleared per run
     DBuf d_tile_off, d_sorted, d_mat, d_pass, d_sites, d_votes, d_votes_out, d_sites_dense, d_votes_dense, d_ovf, d_cands, d_img32, d_img8;
     HBuf h_counts, h_sites, h_votes;
+    // candidates enumerated on the device (pa_encoder_set_device_candidates): the rules of the staged regions, the per-site and
+    // per-row tables of group_votes_kernel, the tile totals and their scans, the results
+    bool dev_cands = false;           // the switch
+    bool dev_results = false;         // positions / depths / frequencies / names of the last run are still on the device
+    int cand_cap = 1024;              // candidates the result buffers hold (grown when a call has more)
+    int64_t dev_calls = 0, host_calls = 0;     // calls enumerated on the device / on the host since the handle was created
+    int64_t name_bytes = 0;
+    DBuf d_rules, d_row_slot, d_aux, d_large, d_grouped, d_rare_next, d_czero, d_cscan, d_pos, d_depths, d_freqs, d_names;
+    HBuf h_rules, h_cscan;
     std::unique_ptr<RegionPool> pool;
     int host_threads = 0;             // threads of the candidate enumeration: 0 = the default below, 1 = the calling thread alone
     // results of the last run
@@ -1137,7 +1346,7 @@ struct pa_variant_batch {
     std::vector<int64_t> positions;
     std::vector<int32_t> depths, freqs;
     std::string names;
-    double ms[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void pa_variant_batch_free(pa_variant_batch* b) { delete b; }
@@ -1152,42 +1361,26 @@ struct RegionOut {
     std::string names;
 };
 
-// where the bytes of a vote's allele past the first eight live: deleted bases in the region's reference, inserted ones in the
-// pool slot pack_results_kernel filled (the first eight are the vote's prefix)
-struct AlleleSrc { const char* reference; const char* pool; };
-inline const char* allele_tail(const Vote& v, const AlleleSrc& p) {
-    return ((v.meta & 8u) ? p.reference + v.off : p.pool + (size_t)v.off * POOL_SLOT) + 8;
-}
-inline void append_allele(std::string& key, const Vote& v, const AlleleSrc& p) {
-    const uint32_t len = (v.meta >> 4) & 63u;
-    for (uint32_t k = 0; k < std::min(len, 8u); ++k) key.push_back((char)(v.prefix >> (56 - 8 * k)));
-    if (len > 8) key.append(allele_tail(v, p), (size_t)len - 8);
-}
-// order of the votes of one region: site, then the allele key as std::map<std::string> orders "2..." / "3..." strings
-// (type character, bytes as unsigned chars, the shorter of two that agree first).  The 8-byte prefix decides nearly always.
-inline bool vote_less(const Vote& x, const Vote& y, const AlleleSrc& p) {
-    if (x.idx != y.idx) return x.idx < y.idx;
-    const uint32_t tx = x.meta & 3u, ty = y.meta & 3u;
-    if (tx != ty) return tx < ty;
-    if (x.prefix != y.prefix) return x.prefix < y.prefix;
-    const uint32_t lx = (x.meta >> 4) & 63u, ly = (y.meta >> 4) & 63u;
-    if (lx > 8 && ly > 8) {
-        const int c = std::memcmp(allele_tail(x, p), allele_tail(y, p), std::min(lx, ly) - 8);
-        if (c != 0) return c < 0;
-    }
-    return lx < ly;
-}
-inline bool same_allele(const Vote& x, const Vote& y, const AlleleSrc& p) {
-    if (x.idx != y.idx || ((x.meta ^ y.meta) & 3u) || x.prefix != y.prefix) return false;
-    const uint32_t lx = (x.meta >> 4) & 63u, ly = (y.meta >> 4) & 63u;
-    return lx == ly && (lx <= 8 || std::memcmp(allele_tail(x, p), allele_tail(y, p), lx - 8) == 0);
+// the order of the votes (vote_less, same_allele) and the rule (accepted, snp_desc, indel_desc): candidates.h, shared with
+// enumerate_sites_kernel
+using pa_cand::vote_less; using pa_cand::same_allele;
+
+pa_cand::Rule region_rule(const RegHost& rh) {
+    pa_cand::Rule q;
+    q.support = rh.q.candidate_support_threshold;
+    q.snp_freq = rh.q.snp_candidate_freq_threshold;
+    q.indel_freq = rh.q.indel_candidate_freq_threshold;
+    q.region_start = rh.p.region_start;
+    q.skip_indels = rh.q.skip_indels;
+    q.last_cap = rh.q.candidate_window_size - 1;
+    return q;
 }
 
 void enumerate_region(const RegHost& rh, int region, int mid, const SiteRec* sites, size_t n_sites, const Vote* votes,
                       size_t n_votes, const int4* ovf, size_t n_ovf, const char* pool, RegionOut& out) {
     const pa_pileup& p = rh.p;
     const AlleleSrc src{p.reference, pool};
-    const pa_summary_params& q = rh.q;
+    const pa_cand::Rule rule = region_rule(rh);
     auto refc = [&](int64_t idx) { return idx >= 0 && idx < p.reference_len ? p.reference[idx] : 'N'; };
     std::map<int32_t, std::map<char, Tally>> rare;       // SNP alleles outside ACGT
     for (size_t k = 0; k < n_ovf; ++k) {
@@ -1205,58 +1398,29 @@ void enumerate_region(const RegHost& rh, int region, int mid, const SiteRec* sit
         const SiteRec& s = sites[si];
         const int depth = std::min(s.cov, MAXC);
         const char rb = refc(s.idx);
-        auto accept = [&](char type, const Tally& t) {
-            const double freq = (double)t.total / std::max(1.0, (double)depth);
-            if ((double)t.total < q.candidate_support_threshold) return false;
-            if (type != '1' && freq < q.indel_candidate_freq_threshold) return false;
-            if (type == '1' && freq < q.snp_candidate_freq_threshold) return false;
-            if (type != '1' && q.skip_indels) return false;
-            if ((type == '1' && !(s.flags & 1)) || (type == '2' && !(s.flags & 2)) || (type == '3' && !(s.flags & 4)))
-                return false;
-            return true;
-        };
-        auto emit = [&](const std::string& key, const Tally& t, CandDesc d) {
-            d.region = region;
+        auto emit = [&](const std::string& key, const Tally& t, const CandDesc& d) {
             out.cands.push_back(d);
-            out.positions.push_back(p.region_start + s.idx);
+            out.positions.push_back(rule.region_start + s.idx);
             out.depths.push_back(depth);
-            out.freqs.push_back(std::min(t.total, MAXC));
+            out.freqs.push_back(pa_cand::clamp_count(t.total));
             out.names += key;
             out.names.push_back('\0');
         };
         // SNP alleles: "1" + base, ordered by the raw base character (A C G T from the device's tallies are already in that
         // order; the rare alphabet, if any at this site, is merged in)
-        struct SnpAllele { char base; Tally t; };
-        SnpAllele snp[4 + 12];
-        int n_snp = 0;
-        const char acgt[4] = {'A', 'C', 'G', 'T'};
-        for (int k = 0; k < 4; ++k)
-            if (s.fwd[k] + s.rev[k] > 0) snp[n_snp++] = SnpAllele{acgt[k], Tally{s.fwd[k] + s.rev[k], s.fwd[k], s.rev[k]}};
+        pa_cand::SnpAllele snp[pa_cand::SNP_MAX];
+        int n_snp = pa_cand::snp_from_site(s, snp);
         if (!rare.empty()) {
             const auto rit = rare.find(s.idx);
             if (rit != rare.end())
-                for (const auto& kv : rit->second) {
-                    int at = 0;
-                    while (at < n_snp && snp[at].base != kv.first) ++at;
-                    if (at == n_snp) {
-                        if (n_snp == 16) continue;           // (more than 12 distinct non-ACGT read letters at one site: not a pileup)
-                        snp[n_snp++] = SnpAllele{kv.first, Tally{}};
-                    }
-                    snp[at].t.total += kv.second.total;
-                    snp[at].t.fwd += kv.second.fwd;
-                    snp[at].t.rev += kv.second.rev;
-                }
-            std::sort(snp, snp + n_snp, [](const SnpAllele& x, const SnpAllele& y) { return x.base < y.base; });
+                for (const auto& kv : rit->second)      // (a letter the full site cannot take is dropped)
+                    (void)pa_cand::snp_merge(snp, n_snp, kv.first, kv.second.total, kv.second.fwd, kv.second.rev);
+            pa_cand::snp_sort(snp, n_snp);
         }
         for (int k = 0; k < n_snp; ++k) {
-            if (!accept('1', snp[k].t)) continue;
-            CandDesc d{};
-            d.idx = s.idx; d.type = 1; d.vcol = 1; d.vval = base_code(snp[k].base);
-            d.fwd = std::min(snp[k].t.fwd, MAXC); d.rev = std::min(snp[k].t.rev, MAXC);
-            d.neg_f = symbol_column(rb, snp[k].base, false); d.neg_r = symbol_column(rb, snp[k].base, true);
-            d.last = -1; d.star_f = d.star_r = -1;
+            if (!pa_cand::accepted(1, snp[k].t, depth, s.flags, rule)) continue;
             const char key[3] = {'1', snp[k].base, 0};
-            emit(std::string(key, 2), snp[k].t, d);
+            emit(std::string(key, 2), snp[k].t, pa_cand::snp_desc(region, s.idx, rb, snp[k].base, snp[k].t));
         }
         while (vk < n_votes && (int32_t)votes[vk].idx < s.idx) ++vk;
         if (vk >= n_votes || (int32_t)votes[vk].idx != s.idx) continue;
@@ -1264,32 +1428,19 @@ void enumerate_region(const RegHost& rh, int region, int mid, const SiteRec* sit
         // votes arrive ordered by (site, type, allele bytes) -- see vote_less -- so equal keys are runs
         for (size_t k0 = vk; k0 < n_votes && (int32_t)votes[k0].idx == s.idx;) {
             size_t k1 = k0;
-            Tally t;
+            Tally t{0, 0, 0};
             while (k1 < n_votes && same_allele(votes[k1], votes[k0], src)) {
                 t.total += 1;
                 ((votes[k1].meta & 4u) ? t.rev : t.fwd) += 1;
                 ++k1;
             }
             const Vote& v = votes[k0];
-            const char type = (v.meta & 3u) == 1u ? '2' : '3';
-            const int alen = (int)((v.meta >> 4) & 63u);
-            if (accept(type, t)) {
-                CandDesc d{};
-                d.idx = s.idx; d.type = type - '0';
-                d.fwd = std::min(t.fwd, MAXC); d.rev = std::min(t.rev, MAXC);
-                d.vval = std::min(alen, MAXC);
-                d.star_f = d.star_r = -1;
-                if (type == '2') {
-                    d.vcol = 2; d.last = -1;
-                    d.neg_f = symbol_column(rb, 'I', false); d.neg_r = symbol_column(rb, 'I', true);
-                } else {
-                    d.vcol = 3; d.last = std::min(mid + alen - 1, q.candidate_window_size - 1);
-                    d.neg_f = symbol_column(rb, 'D', false); d.neg_r = symbol_column(rb, 'D', true);
-                    d.star_f = symbol_column(rb, '*', false); d.star_r = symbol_column(rb, '*', true);
-                }
-                std::string key(1, type);
-                append_allele(key, v, src);
-                emit(key, t, d);
+            const int type = (v.meta & 3u) == 1u ? 2 : 3;
+            const int alen = (int)pa_cand::allele_len(v);
+            if (pa_cand::accepted(type, t, depth, s.flags, rule)) {
+                std::string key(1 + (size_t)alen, (char)('0' + type));
+                pa_cand::copy_allele(&key[1], v, src);
+                emit(key, t, pa_cand::indel_desc(region, s.idx, rb, type, alen, t, mid, rule));
             }
             k0 = k1;
         }
@@ -1654,6 +1805,24 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         if (rc != PA_OK) return rc;
         b.sampled = true;
     }
+    const bool dev = b.dev_cands;
+    b.dev_results = false;
+    b.ms[12] = 0;
+    const size_t n_czero = (size_t)CI_N + 2 * (size_t)b.n_tiles, n_cscan = 2 * ((size_t)b.n_tiles + 1);
+    if (dev) {                        // the rule of every region, and the tables sized by the batch
+        if (!b.h_rules.ensure((size_t)n_regions * sizeof(pa_cand::Rule)) || !b.h_cscan.ensure((n_cscan + CI_N) * 4))
+            return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+        for (int r = 0; r < n_regions; ++r) b.h_rules.as<pa_cand::Rule>()[r] = region_rule(b.regs[(size_t)r]);
+        ENC_ALLOC(b.d_rules, (size_t)n_regions * sizeof(pa_cand::Rule));
+        ENC_ALLOC(b.d_row_slot, (size_t)b.total_rows * 4 + 64);
+        ENC_ALLOC(b.d_aux, (size_t)b.total_rows * sizeof(SiteAux) + 64);
+        ENC_ALLOC(b.d_large, (size_t)b.total_rows * 4 + 64);         // (a row holds at most one site)
+        ENC_ALLOC(b.d_grouped, (size_t)vote_cap * sizeof(Vote));
+        ENC_ALLOC(b.d_czero, n_czero * 4);
+        ENC_ALLOC(b.d_cscan, n_cscan * 4);
+        ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
+    }
+    bool on_device = false;           // this call's candidates were enumerated by the kernels
     for (int attempt = 0;; ++attempt) {
         ENC_ALLOC(b.d_sorted, (size_t)b.rec_cap * sizeof(TileRec));
         ENC_ALLOC(b.d_ovf, (size_t)b.ovf_cap * sizeof(int4));
@@ -1709,6 +1878,45 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
                            b.d_seq.as<char>(), b.d_pool.as<char>(), b.pool_cap, counters);
         ENC_HIP(hipEventRecord(e->ev[3], st));
         ENC_HIP(hipGetLastError());
+        if (dev) {                    // candidates and windows behind the counts, in the same submission
+            ENC_ALLOC(b.d_rare_next, (size_t)b.ovf_cap * 4);
+            ENC_ALLOC(b.d_cands, (size_t)b.cand_cap * sizeof(CandDesc));
+            ENC_ALLOC(b.d_pos, (size_t)b.cand_cap * 8);
+            ENC_ALLOC(b.d_depths, (size_t)b.cand_cap * 4);
+            ENC_ALLOC(b.d_freqs, (size_t)b.cand_cap * 4);
+            ENC_ALLOC(b.d_names, (size_t)b.cand_cap * 72);           // a name is a type character, at most 63 allele bytes and a NUL
+            ENC_ALLOC(b.d_img32, (size_t)b.cand_cap * b.W * b.F * sizeof(int));
+            ENC_ALLOC(b.d_img8, (size_t)b.cand_cap * b.W * b.F);
+            CandArgs ca;
+            ca.regions = b.p_regions; ca.rules = b.d_rules.as<pa_cand::Rule>(); ca.n_regions = n_regions; ca.n_tiles = b.n_tiles;
+            ca.counters = counters; ca.region_counts = region_counts; ca.n_recs = b.d_tile_off.as<int>() + b.n_tiles;
+            ca.rec_cap = b.rec_cap; ca.ovf_cap = b.ovf_cap; ca.pool_cap = b.pool_cap; ca.vote_cap = vote_cap;
+            ca.sites = b.d_sites_dense.as<SiteRec>(); ca.votes = b.d_votes_dense.as<Vote>(); ca.grouped = b.d_grouped.as<Vote>();
+            ca.ovf = b.d_ovf.as<int4>(); ca.rare_next = b.d_rare_next.as<int>();
+            ca.ref = b.p_ref; ca.pool = b.d_pool.as<char>(); ca.pass = b.d_pass.as<uint8_t>();
+            ca.row_slot = b.d_row_slot.as<int>(); ca.aux = b.d_aux.as<SiteAux>(); ca.large = b.d_large.as<int>();
+            ca.cinfo = b.d_czero.as<int>(); ca.tile_nc = ca.cinfo + CI_N; ca.tile_nb = ca.tile_nc + b.n_tiles;
+            ca.tile_c0 = b.d_cscan.as<int>(); ca.tile_b0 = ca.tile_c0 + b.n_tiles + 1;
+            ca.cand_cap = b.cand_cap; ca.mid = b.mid;
+            ca.cands = b.d_cands.as<CandDesc>(); ca.positions = b.d_pos.as<int64_t>(); ca.depths = b.d_depths.as<int32_t>();
+            ca.freqs = b.d_freqs.as<int32_t>(); ca.names = b.d_names.as<char>();
+            const dim3 g_small((unsigned)std::min<int64_t>(b.total_rows, 8192)), g_large((unsigned)std::min<int64_t>(b.total_rows, 1536));
+            ENC_HIP(hipMemsetAsync(b.d_czero.p, 0, n_czero * 4, st));
+            hipLaunchKernelGGL(group_votes_kernel, dim3((unsigned)n_regions), dim3(1024), 0, st, ca);
+            hipLaunchKernelGGL((enumerate_sites_kernel<64, false>), g_small, dim3(64), 0, st, ca);
+            hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, false>), g_large, dim3(64), 0, st, ca);
+            hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nc, b.n_tiles, b.d_cscan.as<int>());
+            hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nb, b.n_tiles, b.d_cscan.as<int>() + b.n_tiles + 1);
+            hipLaunchKernelGGL((enumerate_sites_kernel<64, true>), g_small, dim3(64), 0, st, ca);
+            hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, true>), g_large, dim3(64), 0, st, ca);
+            ENC_HIP(hipEventRecord(e->ev[4], st));
+            hipLaunchKernelGGL(gather_windows_n_kernel, dim3((unsigned)std::min(b.cand_cap, 16384)), dim3(64), 0, st, ca, b.d_mat.as<int>(),
+                               b.W, b.F, b.d_img32.as<int>(), b.d_img8.as<int8_t>());
+            ENC_HIP(hipEventRecord(e->ev[5], st));
+            ENC_HIP(hipGetLastError());
+            ENC_HIP(hipMemcpyAsync(b.h_cscan.p, b.d_cscan.p, n_cscan * 4, hipMemcpyDeviceToHost, st));
+            ENC_HIP(hipMemcpyAsync(b.h_cscan.as<int>() + n_cscan, b.d_czero.p, CI_N * 4, hipMemcpyDeviceToHost, st));
+        }
         ENC_HIP(hipMemcpyAsync(host_counters, counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
         ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
         ENC_HIP(hipStreamSynchronize(st));
@@ -1719,6 +1927,15 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
             b.ovf_cap = std::max(b.ovf_cap, host_counters[CT_OVF] + 1024);
             b.pool_cap = std::max(b.pool_cap, host_counters[CT_POOL] + 1024);
             continue;
+        }
+        if (dev && host_counters[CT_ERR] <= 0 && host_counters[CT_VOTES] <= vote_cap && b.h_cscan.as<int>()[n_cscan + CI_REFUSED] == 0) {
+            const int found = b.h_cscan.as<int>()[b.n_tiles];
+            if (found > b.cand_cap) {                            // more candidates than the buffers hold: nothing was written
+                if (attempt >= 3) return pa::set_error(PA_ERR_HIP, "encoder candidate buffers could not be sized");
+                b.cand_cap = (int)std::min<int64_t>(0x7ffffff0, (int64_t)found + found / 4 + 1024);
+                continue;
+            }
+            on_device = true;
         }
         break;
     }
@@ -1748,6 +1965,26 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
                                                  " runs past its sequence");
     }
     if (host_counters[CT_VOTES] > vote_cap) return pa::set_error(PA_ERR_INVALID, "more indel votes than CIGAR operations (corrupt pileup)");
+    if (on_device) {                  // nothing left for the host: the counts per region are differences of the tile offsets
+        const int* c0 = b.h_cscan.as<int>();
+        int tile = 0;
+        for (int r = 0; r < n_regions; ++r) {
+            const int nt = (b.regs[(size_t)r].L + 1 + TP - 1) / TP;
+            b.region_n[(size_t)r] = c0[tile + nt] - c0[tile];
+            tile += nt;
+        }
+        b.n = c0[b.n_tiles];
+        b.name_bytes = c0[n_cscan - 1];
+        b.dev_results = true;
+        b.dev_calls += 1;
+        if (n_candidates)
+            for (int r = 0; r < n_regions; ++r) n_candidates[r] = b.region_n[(size_t)r];
+        (void)hipEventElapsedTime(&ms, e->ev[3], e->ev[4]); b.ms[12] = ms;  // group_votes_kernel ... enumerate_sites_kernel (both forms)
+        (void)hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); b.ms[3] = ms;   // gather_windows_n_kernel
+        b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+        return PA_OK;
+    }
+    if (dev) b.host_calls += 1;       // refused by the kernels (CI_REFUSED): enumerated below, as with the switch off
     // region r's sites / votes are [s0[r], s0[r + 1]) / [v0[r], v0[r + 1]) of the dense lists
     std::vector<size_t> s0((size_t)n_regions + 1, 0), v0((size_t)n_regions + 1, 0), o0((size_t)n_regions + 1, 0);
     for (int r = 0; r < n_regions; ++r) {
@@ -2205,6 +2442,20 @@ int pa_encoder_set_host_threads(pa_encoder* e, int32_t n) {
     return PA_OK;
 }
 
+int pa_encoder_set_device_candidates(pa_encoder* e, int32_t on) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (!e->variant) e->variant = new pa_variant_batch();
+    e->variant->dev_cands = on != 0;
+    return PA_OK;
+}
+
+int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (on_device) *on_device = e->variant ? e->variant->dev_calls : 0;
+    if (on_host) *on_host = e->variant ? e->variant->host_calls : 0;
+    return PA_OK;
+}
+
 int pa_encoder_region_reads(pa_encoder* e, int32_t* n_reads, int32_t n) {
     if (!e || !n_reads || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
     for (int i = 0; i < n; ++i) n_reads[i] = (e->variant && i < (int)e->variant->live.size()) ? e->variant->live[(size_t)i] : 0;
@@ -2261,8 +2512,22 @@ int pa_encoder_get_results(pa_encoder* e, int64_t* positions, int32_t* depths, i
         if (candidates_needed) *candidates_needed = 0;
         return PA_OK;
     }
-    const pa_variant_batch& b = *e->variant;
+    pa_variant_batch& b = *e->variant;
     const size_t n = (size_t)b.n;
+    if (b.dev_results) {              // enumerated on the device: the lists are fetched when somebody asks for them
+        b.positions.assign(n, 0);
+        b.depths.assign(n, 0);
+        b.freqs.assign(n, 0);
+        b.names.assign((size_t)b.name_bytes, '\0');
+        if (n > 0) {
+            ENC_HIP(hipMemcpyAsync(b.positions.data(), b.d_pos.p, n * 8, hipMemcpyDeviceToHost, e->stream));
+            ENC_HIP(hipMemcpyAsync(b.depths.data(), b.d_depths.p, n * 4, hipMemcpyDeviceToHost, e->stream));
+            ENC_HIP(hipMemcpyAsync(b.freqs.data(), b.d_freqs.p, n * 4, hipMemcpyDeviceToHost, e->stream));
+            ENC_HIP(hipMemcpyAsync(&b.names[0], b.d_names.p, (size_t)b.name_bytes, hipMemcpyDeviceToHost, e->stream));
+            ENC_HIP(hipStreamSynchronize(e->stream));
+        }
+        b.dev_results = false;
+    }
     if (positions) std::copy(b.positions.begin(), b.positions.end(), positions);
     if (depths) std::copy(b.depths.begin(), b.depths.end(), depths);
     if (candidate_frequency) std::copy(b.freqs.begin(), b.freqs.end(), candidate_frequency);
@@ -2282,7 +2547,7 @@ const int8_t* pa_encoder_device_images(pa_encoder* e) {
 
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n) {
     if (!e || !ms || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 12) ? e->variant->ms[i] : 0.0;
+    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 13) ? e->variant->ms[i] : 0.0;
     return PA_OK;
 }
 

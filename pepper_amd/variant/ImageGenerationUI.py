@@ -179,7 +179,10 @@ class ImageGenerationUtils:
         generators = {}
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
         # ... and two counts: intervals the device sampled down, intervals that took the host-clipped form for any reason
-        mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0}
+        # ... and the encoder calls of the packed form (one per group of intervals), with those whose candidates were enumerated
+        # on the device / handed back to the host (both 0 unless PEPPER_AMD_DEVICE_CANDIDATES=1)
+        mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0,
+                "encoder_calls": 0, "device_enumerated_calls": 0, "host_enumerated_calls": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -266,6 +269,10 @@ class ImageGenerationUtils:
             # from the core); PEPPER_AMD_DEVICE_LONG_CIGARS=0: its group of intervals takes the host packer
             long_cigars = _lib.device_long_cigars()
             long_before = enc.long_cigar_reads
+            # candidates enumerated between the count kernels and the window gather, without the host pass in the middle of
+            # every call (pa_encoder_set_device_candidates)
+            enc.set_device_candidates(_lib.device_candidates())
+            calls_before = enc.candidate_calls()
             g0 = 0
             while g0 < len(intervals):
                 # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last
@@ -324,6 +331,7 @@ class ImageGenerationUtils:
                     g0 += n_done
                     continue
                 t0 = lap("encode", t0)
+                mine["encoder_calls"] += 1
                 probs, at = None, 0
                 if sink is not None:
                     # the group's windows are still where the encoder left them on the device: the model reads them there
@@ -343,7 +351,11 @@ class ImageGenerationUtils:
             enc.inflate_ms, enc.inflated_bytes = 0.0, 0
             mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
             mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
+            calls = enc.candidate_calls()
+            mine["device_enumerated_calls"] += calls[0] - calls_before[0]
+            mine["host_enumerated_calls"] += calls[1] - calls_before[1]
             enc.set_sampling(None)
+            enc.set_device_candidates(False)
             enc.release()
             t_close = time.perf_counter()
         lap("close", t_close)

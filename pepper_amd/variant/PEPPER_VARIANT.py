@@ -111,6 +111,21 @@ def _encoder(device):
     return lib, _encoders[key]
 
 
+def set_device_candidates(on, device=0):
+    """Candidates of this thread's encoder on `device` enumerated on the device (pa_encoder_set_device_candidates) from its
+    next call on: what RegionalSummaryGenerator, StagedBatch and generate_summary_arrays_batch run on."""
+    lib, enc = _encoder(device)
+    _lib.check(lib.pa_encoder_set_device_candidates(enc, 1 if on else 0))
+
+
+def candidate_calls(device=0):
+    """-> (calls enumerated on the device, calls handed back to the host) of this thread's encoder on `device`."""
+    lib, enc = _encoder(device)
+    dev, host = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(lib.pa_encoder_candidate_calls(enc, ctypes.byref(dev), ctypes.byref(host)))
+    return dev.value, host.value
+
+
 def flatten_reads(reads):
     """type_read-like objects -> the flat arrays of pa_pileup."""
     n = len(reads)
@@ -141,6 +156,10 @@ class RegionalSummaryGenerator(object):
         self.device = device
         # GENERATE_INDELS == false in the reference (region_summary.h:50): no insert columns
         self.total_observered_insert_bases = 0
+
+    def set_device_candidates(self, on):
+        """The switch of the encoder this generator's calls run on (this thread's, on its device)."""
+        set_device_candidates(on, self.device)
 
     def generate_max_insert_summary(self, reads):
         """Axes of the region.  With GENERATE_INDELS false every max_observed_insert entry is 0, so
@@ -210,11 +229,11 @@ class StagedBatch(object):
         return self.counts[:self.n_regions]
 
     def timing(self):
-        ms = np.zeros(12, np.float64)
-        _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 12))
+        ms = np.zeros(13, np.float64)
+        _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 13))
         return dict(records_ms=ms[0], tile_count_ms=ms[1], compact_votes_ms=ms[2], gather_windows_ms=ms[3],
                     host_enumeration_ms=ms[4], run_ms=ms[5], host_bucket_ms=ms[6], host_bucket_and_threads_ms=ms[7],
-                    upload_ms=ms[8], unpack_clip_ms=ms[9])
+                    upload_ms=ms[8], unpack_clip_ms=ms[9], device_enumeration_ms=ms[12])
 
     def stats(self):
         v = np.zeros(6, np.int64)
@@ -345,6 +364,16 @@ class PackedEncoder(object):
             seed, cap = int(sampling[0]), int(sampling[1])
             rate = float(sampling[2]) if len(sampling) > 2 else 1.0
         _lib.check(self.lib.pa_encoder_set_sampling(self.enc, seed, cap, rate))
+
+    def set_device_candidates(self, on):
+        """Candidates of this handle's next runs enumerated on the device (pa_encoder_set_device_candidates)."""
+        _lib.check(self.lib.pa_encoder_set_device_candidates(self.enc, 1 if on else 0))
+
+    def candidate_calls(self):
+        """-> (runs enumerated on the device, runs handed back to the host) since this handle was created."""
+        dev, host = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self.lib.pa_encoder_candidate_calls(self.enc, ctypes.byref(dev), ctypes.byref(host)))
+        return dev.value, host.value
 
     def sampled(self):
         """-> (intervals the device sampled down, reads it dropped) since this handle was created."""

@@ -1,6 +1,6 @@
 """Throughput of the variant summary encoder on a batch of synthetic ONT-like regions (E-syn, pepper_amd.synthetic:
 100 kb + 2 x 100 flank, ~60x, ~8 kb reads, 2 % indel events, 4 % substitutions, planted SNP / indel sites).
-    python tools/bench_encoder.py [--regions 64] [--reps 5] [--check 2]
+    python tools/bench_encoder.py [--regions 64] [--reps 5] [--check 2] [--device-candidates]
 Prints one JSON line: aligned bases/s of pa_encoder_run_staged (inputs resident in HBM: kernels + host candidate
 enumeration + window gather), per-kernel HIP-event times, the rate of the one-call form (H2D included), and the first
 `--check` regions compared with the oracle restatement.  bench.py --model encoder is the line of record."""
@@ -26,9 +26,13 @@ def main():
     ap.add_argument("--check", type=int, default=2)
     ap.add_argument("--region-size", type=int, default=100_000)
     ap.add_argument("--cache", default="", help="pickle of the generated regions: written if absent, read if present (profiling passes)")
+    ap.add_argument("--device-candidates", action="store_true",
+                    help="enumerate the candidates on the device (pa_encoder_set_device_candidates) instead of on the host")
     args = ap.parse_args()
     from pepper_amd import synthetic
+    from pepper_amd.variant import PEPPER_VARIANT
     from pepper_amd.variant.PEPPER_VARIANT import RegionalSummaryGenerator, StagedBatch
+    PEPPER_VARIANT.set_device_candidates(args.device_candidates)
     t0 = time.perf_counter()
     if args.cache and os.path.exists(args.cache):
         import pickle
@@ -76,6 +80,7 @@ def main():
     avg = {k: float(np.mean([t[k] for t in times])) for k in times[0]}
     alg_bytes = 2 * stats["bases"] + 104 * stats["rows"]
     print(json.dumps({"metric": "variant summary encoder, aligned bases/s (inputs resident in HBM)", "regions": args.regions,
+                      "device_candidates": bool(args.device_candidates), "candidate_calls": list(PEPPER_VARIANT.candidate_calls()),
                       "stats": stats, "candidates": int(counts.sum()), "run_ms": dt * 1e3, "bases_per_s": stats["bases"] / dt,
                       "timing_ms": avg, "tile_count_GBps": alg_bytes / (avg["tile_count_ms"] * 1e-3) / 1e9,
                       "tile_count_bases_per_s": stats["bases"] / (avg["tile_count_ms"] * 1e-3),

@@ -6,7 +6,8 @@ through pepper_amd.variant.ImageGenerationUI.generate_images, the entry point of
 
 `run` reports, per thread count, the wall time, Mb of reference per second, aligned bases per second and the stage times
 summed over the workers (bam_pack: inflate + header walk + slice copies; fasta; encode: upload + clip/decode + kernels +
-candidate enumeration + result copy; hdf5).  PEPPER_AMD_PACKED_READS=0 times the host-clipped form."""
+candidate enumeration + result copy; hdf5).  PEPPER_AMD_PACKED_READS=0 times the host-clipped form;
+PEPPER_AMD_DEVICE_CANDIDATES=1 the form whose candidates are enumerated on the device (the line says which it was)."""
 import json
 import os
 import shutil
@@ -75,7 +76,8 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rat
                 mb, info["coverage"], info["records"], info["bam_bytes"] / 1e9, info.get("deflate", "level 1"),
                 (", NM/MD/RG tags" if info.get("aux_tags") else "") + (", run-length qualities" if "run-length" in info.get("quals", "") else ""),
                 region_size),
-            "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0", "downsample_rate": downsample_rate, "runs": runs}
+            "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0",
+            "device_candidates": os.environ.get("PEPPER_AMD_DEVICE_CANDIDATES", "0") == "1", "downsample_rate": downsample_rate, "runs": runs}
 
 
 if __name__ == "__main__":
