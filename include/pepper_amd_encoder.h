@@ -131,6 +131,61 @@ int pa_encoder_inflate_bgzf(pa_encoder* e, const uint8_t* comp, int64_t comp_byt
  * pa_bam_pack_inflated treats as a cut).  The caller then takes the span to the host after all. */
 int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry,
                             void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags);
+/* The read and pair tables of a run of regions built ON THE DEVICE from those headers: what pa_bam_pack_headers (include/
+ * pepper_amd_io.h) does on the host after a download of 40 bytes per record, and the per-pair offsets pa_encoder_stage_packed
+ * sums on the host, by two kernels over the header table where the walk left it (csrc/encoder.hip: pack_scan_kernel,
+ * pack_fill_kernel; the per-record rules are csrc/pack_rule.h, the text pa_bam_pack_headers is compiled from).  A summary of a
+ * few hundred bytes comes back; the clip kernel reads the device-built tables.
+ * pa_encoder_submit_walk   pa_encoder_walk_records without its wait and without the download of the headers: the walk is
+ *                     queued, nothing is returned.  pa_encoder_pack_records (headers = NULL) follows in the same submission
+ *                     and waits ONCE for both; out->walk_flags are the walk's flags, out->n_headers its record count.
+ * pa_encoder_walk_headers  the headers and flags of the handle's last walk after all (the caller's way back to
+ *                     pa_bam_pack_headers when the pack hands a span back).
+ * pa_encoder_pack_records  headers == NULL: the table the handle's last walk left on the device; otherwise n_headers host
+ *                     entries (pa_record_header) are uploaded first (tests, callers with their own walk).  ref_id = the
+ *                     contig's index in the BAM header, start / stop / include_supplementary / min_mapq as for
+ *                     pa_bam_pack_headers, reads_cap / pairs_cap = the table sizes the host walk would be given.  Every kept
+ *                     read's slice(s) are checked against the resident span here, before any kernel dereferences them (both
+ *                     slices of a state-3 record; pa_encoder_set_split_slices says whether those are kept at all).
+ *                     out->status == 0: region_pairs [n_regions + 1], n_done, the counts and the tables
+ *                     pa_encoder_packed_tables returns equal byte for byte what pa_bam_pack_headers returns with rc 0 on the
+ *                     same headers and arguments; a cut that closed at least one region is status 0 with n_done < n_regions.
+ *                     out->status != 0: nothing usable, and the verdict is the host walk's (the device may report a case the
+ *                     host walk would have stopped in front of).  Two such cases are known and deliberate.  The slice, CG
+ *                     and cap checks (statuses 5, 3, 1) cover every kept read up to the walk's end, also the reads behind
+ *                     the header that closed the last closed region of a cut span, which the host walk does not keep.  And a
+ *                     state-2 header of an earlier contig gives status 2, where the host walk skips it with the rest of that
+ *                     contig.  In both the host walk may return 0 for a span the device handed back; pa_encoder_pack_calls
+ *                     (the driver's host_packed_calls) shows how often that happens on real spans.
+ *                     Device memory: the first call allocates the handle's tables for reads_cap reads (24 + 8 + 8 bytes
+ *                     each) and pairs_cap pairs (24 + 4 bytes each), sized by the caps and not by the span, and they stay
+ *                     with the handle.
+ * pa_encoder_stage_packed_device  pa_encoder_stage_packed of the out->n_done regions over the tables the last
+ *                     pa_encoder_pack_records left (the span still resident): the same uploads and launches, without the
+ *                     read, pair and offset tables.  pa_encoder_run_staged follows.
+ * pa_encoder_packed_tables  the device-built tables copied out (any pointer may be NULL): n_reads reads and base offsets,
+ *                     n_pairs pair_read entries.
+ * pa_encoder_pack_calls  calls of this handle packed on the device / handed back with status != 0 (either may be NULL). */
+typedef struct {
+    int32_t status;        /* 0: tables complete.  != 0: nothing usable, the caller takes pa_bam_pack_headers:
+                              1 reads_cap / pairs_cap exceeded, 2 a header in state 2 before the walk's end,
+                              3 a kept header in state 1 (or state 3 with split slices off), 4 cut before the first region closed,
+                              5 a kept read's slice outside the span / a size limit, 6 the walk left no table (walk_flags[0]) */
+    int32_t n_done, n_reads, n_pairs, n_split;
+    int32_t walk_flags[2]; /* headers == NULL: flags[0..1] of pa_encoder_walk_records */
+    int32_t reserved;
+    int64_t n_headers;     /* headers the pack looked at */
+    int64_t slice_bytes;   /* counts[2] of pa_bam_pack_headers */
+    int64_t total_bases, total_ops;      /* room the clipped pairs of the closed regions are given */
+} pa_device_pack;
+int pa_encoder_submit_walk(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry);
+int pa_encoder_walk_headers(pa_encoder* e, void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags);
+int pa_encoder_pack_records(pa_encoder* e, const void* headers, int64_t n_headers, int32_t data_is_final, int32_t ref_id,
+                            int32_t n_regions, const int64_t* start, const int64_t* stop, int32_t include_supplementary,
+                            int32_t min_mapq, int32_t reads_cap, int32_t pairs_cap, int32_t* region_pairs, pa_device_pack* out);
+int pa_encoder_stage_packed_device(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params);
+int pa_encoder_packed_tables(pa_encoder* e, pa_packed_read* reads, int32_t* pair_read, int64_t* seq_off);
+int pa_encoder_pack_calls(pa_encoder* e, int64_t* on_device, int64_t* handed_back);
 /* Reads whose CIGAR travels in the CG tag, kept on the device path (both off / empty on a new handle).
  * pa_encoder_set_split_slices  on != 0: pa_encoder_walk_records looks the tag up in the record's auxiliary fields (one wavefront
  *                     per record; every byte read lies inside the record and the span) and reports state 3 as

@@ -327,6 +327,13 @@ int pa_bam_pack_headers(pa_bam* b, const pa_record_header* headers, int64_t n_he
                         int32_t n_regions, const int64_t* start, const int64_t* stop, int32_t include_supplementary, int32_t min_mapq,
                         pa_packed_read* reads, int32_t reads_cap, int32_t* pair_read, int32_t pairs_cap, int32_t* region_pairs,
                         int32_t* n_done, int64_t* counts);
+/* The per-record rules pa_bam_pack_headers and the device's pack (pa_encoder_pack_records) are both compiled from
+ * (csrc/pack_rule.h), header by header and without a walk's memory -- what a test compares with a restatement.  out[4 * k ..]:
+ * [0] 0 the walk skips the header (an earlier contig) / 1 it ends the walk / 2 a header of contig ref_id in front of the last stop,
+ * [1] 1 when the filters drop the record, [2] r_lo = the first region with stop > pos, [3] one past the last region r >= r_lo with
+ * start < pos + max(1, ref_len): the record's regions are [r_lo, [3]).  Regions as pa_bam_pack_headers takes them, at least one. */
+int pa_bam_pack_rule(const pa_record_header* headers, int64_t n_headers, int32_t ref_id, int32_t n_regions, const int64_t* start,
+                     const int64_t* stop, int32_t include_supplementary, int32_t min_mapq, int32_t* out);
 /* Reads whose operations and bases lie apart (SAM specification 4.2.2: more than 65 535 operations travel in the CG:B,I tag,
  * the core keeps <l_seq>S<ref_len>N, bases and qualities).  Off on a new handle: pa_bam_pack_inflated / pa_bam_pack_headers fail
  * with -8 at such a record.  on != 0: they keep it in place like any other -- data_off / n_cigar are the tag's operations, and

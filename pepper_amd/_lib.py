@@ -22,6 +22,13 @@ class VariantConfig(ctypes.Structure):
                 ("num_classes_type", c_int32), ("device", c_int32), ("max_chunk", c_int32)]
 
 
+class DevicePack(ctypes.Structure):
+    """pa_device_pack (include/pepper_amd_encoder.h): the summary of pa_encoder_pack_records."""
+    _fields_ = [("status", c_int32), ("n_done", c_int32), ("n_reads", c_int32), ("n_pairs", c_int32), ("n_split", c_int32),
+                ("walk_flags", c_int32 * 2), ("reserved", c_int32), ("n_headers", c_int64), ("slice_bytes", c_int64),
+                ("total_bases", c_int64), ("total_ops", c_int64)]
+
+
 class PolishConfig(ctypes.Structure):
     _fields_ = [("image_features", c_int32), ("hidden_size", c_int32), ("gru_layers", c_int32),
                 ("num_classes", c_int32), ("seq_length", c_int32), ("window", c_int32),
@@ -78,6 +85,13 @@ SYMBOLS = [
                                                c_void_p]),
     ("pa_encoder_walk_records", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64,
                                                ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_encoder_submit_walk", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32]),
+    ("pa_encoder_walk_headers", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_encoder_pack_records", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32,
+                                               c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    ("pa_encoder_stage_packed_device", ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
+    ("pa_encoder_packed_tables", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    ("pa_encoder_pack_calls", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     ("pa_encoder_set_split_slices", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_encoder_set_seq_offsets", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_region_reads", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
@@ -219,6 +233,15 @@ def device_candidates():
     """PEPPER_AMD_DEVICE_CANDIDATES=1: the image-generation drivers have their encoders enumerate candidates on the device
     (pa_encoder_set_device_candidates).  Unset or any other value: on the host."""
     return os.environ.get(DEVICE_CANDIDATES_ENV, "0") == "1"
+
+
+DEVICE_PACK_ENV = "PEPPER_AMD_DEVICE_PACK"
+
+
+def device_pack():
+    """PEPPER_AMD_DEVICE_PACK=1: the variant image-generation driver has its encoders build the packed read and pair tables
+    on the device (pa_encoder_pack_records).  Unset or any other value: on the host."""
+    return os.environ.get(DEVICE_PACK_ENV, "0") == "1"
 
 
 def check(rc):

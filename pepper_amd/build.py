@@ -11,7 +11,7 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpepper_amd.so")
 SOURCES = ["api.hip", "inflate.hip", "gemm.hip", "gemm_h2.hip", "rnn.hip", "rnn_h2.hip", "mlp_h2.hip", "head.hip", "encoder.hip", "encoder_polish.hip", "realign.hip"]
-HEADERS = ["common.h", "kernels.h", "encoder_common.h", "reservoir.h", "candidates.h", os.path.join("..", "..", "include", "pepper_amd.h"),
+HEADERS = ["common.h", "kernels.h", "encoder_common.h", "reservoir.h", "candidates.h", "pack_rule.h", os.path.join("..", "..", "include", "pepper_amd.h"),
            os.path.join("..", "..", "include", "pepper_amd_encoder.h"),
            os.path.join("..", "..", "include", "pepper_amd_realign.h")]
 
@@ -45,10 +45,11 @@ def build_io(force=False, verbose=False):
     cnd = os.path.join(CSRC, "candidates.cpp") # candidate selection + VCF record text of a prediction batch
     hdr = os.path.join(CSRC, "..", "..", "include", "pepper_amd_io.h")
     rsv = os.path.join(CSRC, "reservoir.h")    # the reservoir sampler bamio.cpp exports (shared with encoder.hip)
-    have_src = all(os.path.exists(f) for f in (src, bam, bld, cnd, hdr, rsv))
+    pkr = os.path.join(CSRC, "pack_rule.h")    # the packed walk's per-record rules (shared with encoder.hip)
+    have_src = all(os.path.exists(f) for f in (src, bam, bld, cnd, hdr, rsv, pkr))
     if os.path.exists(IO_LIB) and (not have_src or (not force and os.path.getmtime(IO_LIB) >= max(
             os.path.getmtime(src), os.path.getmtime(bam), os.path.getmtime(bld), os.path.getmtime(cnd), os.path.getmtime(hdr),
-            os.path.getmtime(rsv)))):
+            os.path.getmtime(rsv), os.path.getmtime(pkr)))):
         return IO_LIB
     inc, lib = os.path.join(HDF5_PREFIX, "include"), os.path.join(HDF5_PREFIX, "lib")
     if not os.path.exists(os.path.join(inc, "hdf5.h")):

@@ -36,6 +36,7 @@
 #include <vector>
 
 #include "../../include/pepper_amd_io.h"
+#include "pack_rule.h"
 #include "reservoir.h"
 
 namespace {
@@ -778,11 +779,11 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         flag = R[14] | (R[15] << 8);
         l_seq = le32(R + 16);
         }
-        if (ref_id != tid) {
-            if (ref_id > tid || ref_id < 0) break;
-            continue;
+        {   // (the walk's rules -- pack_rule.h, the text the device's pack is compiled from)
+            const int cls = pa_pack::header_class(ref_id, pos, tid, last_stop);
+            if (cls == pa_pack::HDR_STOP) break;
+            if (cls == pa_pack::HDR_SKIP) continue;
         }
-        if (pos >= last_stop) break;
         if (!H) {
             o_cigar = 32 + (size_t)R[8];
             o_seq = o_cigar + 4ull * n_cigar_op;
@@ -790,12 +791,10 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
             if (o_aux > block_size) return bam_fail(-6, "corrupt BAM record");
         }
         close_up_to(pos);
-        while (r_lo < n_regions && stop[r_lo] <= pos) ++r_lo;
+        if (H) r_lo = std::max(r_lo, (int)pa_pack::first_open_region(stop, n_regions, pos));
+        else while (r_lo < n_regions && stop[r_lo] <= pos) ++r_lo;
         // ---- filters of get_reads (:138-151); a record without bases has nothing to pile up ----
-        if (flag & (0x200 | 0x400 | 0x100 | 0x4)) continue;
-        if (!include_supplementary && (flag & 0x800)) continue;
-        if (mapq < min_mapq) continue;
-        if (l_seq == 0) continue;
+        if (pa_pack::record_dropped(flag, mapq, l_seq, 1, include_supplementary, min_mapq)) continue;
         const uint8_t* cig = H ? nullptr : R + o_cigar;
         uint32_t n_cig = n_cigar_op;
         if (!H && n_cigar_op >= 1 && (le32(cig) & 15) == 4 && (le32(cig) >> 4) == l_seq) {      // long CIGAR in the CG tag (as above)
@@ -809,9 +808,10 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         if (n_cig == 0) continue;                            // no alignment to walk: get_reads keeps nothing of it
         // the region test of the iterator: pos < stop and end > start, end = pos + reference length (at least pos + 1); only a
         // read that starts in front of a region needs its end
-        int64_t end = H ? (int64_t)pos + std::max<int64_t>(1, H->ref_len) : -1;     // (the device's walk summed the operations)
+        int64_t end = H ? pa_pack::read_end(pos, H->ref_len) : -1;     // (the device's walk summed the operations)
         int first_pair = -1;
-        for (int r = r_lo; r < n_regions && start[r] < (end < 0 ? (int64_t)0x7fffffffffffll : end); ++r) {
+        const int r_hi = H ? (int)pa_pack::region_range_end(start, n_regions, r_lo, end) : n_regions;
+        for (int r = r_lo; r < r_hi && start[r] < (end < 0 ? (int64_t)0x7fffffffffffll : end); ++r) {
             if (pos >= stop[r]) continue;
             if (pos < start[r]) {
                 if (end < 0) {
@@ -831,7 +831,7 @@ int pack_walk(pa_bam* b, int tid, bool nothing, const uint8_t* mem, int64_t mem_
         }
         if (full) break;
         if (first_pair < 0) continue;
-        const int64_t bytes = 4ll * n_cig + (l_seq + 1) / 2 + l_seq;
+        const int64_t bytes = pa_pack::slice_bytes(n_cig, l_seq);
         int64_t at, seq_at = -1;
         if (H) {
             // state 3: the device's walk found the operations in the tag (data_off, n_cigar, ref_len are theirs) and left the
@@ -1174,6 +1174,21 @@ int pa_bam_pack_headers(pa_bam* b, const pa_record_header* headers, int64_t n_he
     static const pa_record_header none{};
     return pack_walk(b, tid, false, nullptr, 0, 0, data_is_final != 0, headers ? headers : &none, n_headers, n_regions, start, stop,
                      include_supplementary, min_mapq, nullptr, 0, reads, reads_cap, pair_read, pairs_cap, region_pairs, n_done, counts);
+}
+
+int pa_bam_pack_rule(const pa_record_header* headers, int64_t n_headers, int32_t ref_id, int32_t n_regions, const int64_t* start,
+                     const int64_t* stop, int32_t include_supplementary, int32_t min_mapq, int32_t* out) {
+    if (n_headers < 0 || (n_headers > 0 && (!headers || !out)) || n_regions < 1 || !start || !stop) return bam_fail(-1, "null argument");
+    for (int64_t k = 0; k < n_headers; ++k) {
+        const pa_record_header& h = headers[k];
+        int32_t* o = out + 4 * k;
+        o[0] = pa_pack::header_class(h.ref_id, h.pos, ref_id, stop[n_regions - 1]);
+        o[1] = pa_pack::record_dropped((uint32_t)h.flags & 0xffffu, (h.flags >> 16) & 0xff, (uint32_t)h.l_seq, (uint32_t)h.n_cigar,
+                                       include_supplementary, min_mapq) ? 1 : 0;
+        o[2] = pa_pack::first_open_region(stop, n_regions, h.pos);
+        o[3] = pa_pack::region_range_end(start, n_regions, o[2], pa_pack::read_end(h.pos, h.ref_len));
+    }
+    return 0;
 }
 
 int pa_bam_pack_inflated(pa_bam* b, const uint8_t* data, int64_t data_bytes, int64_t first_record, int32_t data_is_final,

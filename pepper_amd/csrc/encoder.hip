@@ -25,6 +25,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +44,7 @@
 #include "encoder_common.h"
 #include "candidates.h"
 #include "reservoir.h"
+#include "pack_rule.h"
 
 using namespace pa_enc;
 using pa_cand::SiteRec; using pa_cand::Vote; using pa_cand::CandDesc; using pa_cand::Tally; using pa_cand::AlleleSrc;
@@ -352,6 +354,286 @@ __global__ __launch_bounds__(RS_T) void reservoir_keep_kernel(const SampRec* __r
         __syncthreads();
     }
     if (tid == 0) live[rec.region] = k;
+}
+
+// ---- packed form: the read and pair tables built on the device ------------------------------------------------------------
+// What pa_bam_pack_headers does on the host over the headers record_walk left in device memory (bamio.cpp: pack_walk's hdrs
+// branch; the per-record rules are pack_rule.h, the same text): pack_scan_kernel -- ONE workgroup, the headers in file order
+// PACK_BLOCK at a time with running carries, as tile_offsets_kernel scans -- finds the walk's end (a block minimum), the
+// prefix maximum of the positions (which regions are closed), every kept record's run of regions (two binary searches) and
+// its index in the read table (a prefix sum), writes the reads, snapshots what was complete when each region closed, adds up
+// pairs / bases / operations per region, and leaves the summary; pack_fill_kernel -- one workgroup per closed region, the
+// reads in file order PACK_BLOCK at a time -- gives the region's pairs their slots and their base / operation offsets.
+// Spans hold thousands of records (2^18 at most): the order is what matters here, not the bandwidth.
+constexpr int PACK_BLOCK = 1024;
+struct PackHdr { int64_t data_off; int32_t ref_id, pos, l_seq, n_cigar, flags, ref_len, state, block_size; };    // = pa_record_header
+static_assert(sizeof(PackHdr) == 40 && sizeof(pa_device_pack) == 64, "record header / pack summary");
+enum { PK_CAP = 1, PK_CORRUPT = 2, PK_CG = 4, PK_OUTSIDE = 8, PK_WALK = 16 };          // what the scan met (bits)
+
+struct PackArgs {
+    const PackHdr* hdr;
+    const int32_t* n_hdr_dev;        // the walk's record count and flags where the walk left them (null: n_hdr host entries uploaded)
+    const int32_t* walk_flags_dev;
+    int64_t n_hdr, hdr_cap;
+    const int64_t* bounds_src; int64_t* bounds;      // start [n_regions] | stop [n_regions]: as handed over (mapped host memory or `bounds` itself), in device memory
+    int32_t n_regions, tid, is_final, include_supplementary, min_mapq, split, reads_cap, pairs_cap;
+    int64_t span_bytes;
+    PackedRead* reads; int64_t* seq_off; int2* range;         // [reads_cap]: the table, the base offsets, each read's run of regions
+    PairRec* pairs; int32_t* pair_read;                       // [pairs_cap]
+    // [n_regions] each: pairs, bases, operations of a region; reads / slice bytes complete when it closed
+    int32_t* r_pairs; unsigned long long* r_bases; unsigned long long* r_ops; int32_t* closed_reads; int64_t* closed_bytes;
+    // the head: summary | region_pairs [n + 1] | op_base [n + 1] (pad to 8) | seq_base [n + 1] -- in device memory, and copied
+    // into the page-locked block where that is mapped
+    int32_t* head; int32_t* head_mapped; int32_t head_words;
+};
+__host__ __device__ inline size_t pack_head_ops(int n_regions) { return 64 + ((size_t)n_regions + 1) * 4; }
+__host__ __device__ inline size_t pack_head_bases(int n_regions) { return (pack_head_ops(n_regions) + ((size_t)n_regions + 1) * 4 + 7) & ~(size_t)7; }
+__host__ __device__ inline size_t pack_head_bytes(int n_regions) { return pack_head_bases(n_regions) + ((size_t)n_regions + 1) * 8; }
+
+// inclusive scans over the wave for 64-bit sums and 32-bit maxima (lane shuffles; the 32-bit sums take wave_inclusive_sum)
+__device__ __forceinline__ long long wave_inclusive_sum64(long long x) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const long long y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    return x;
+}
+__device__ __forceinline__ int wave_inclusive_max(int x) {
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int y = __shfl_up(x, d, 64);
+        if (lane >= d) x = max(x, y);
+    }
+    return x;
+}
+
+__global__ __launch_bounds__(PACK_BLOCK) void pack_scan_kernel(PackArgs a) {
+    __shared__ int w_min[16], w_max[16], w_cnt[16];
+    __shared__ long long w_bytes[16];
+    __shared__ int c_reads, c_max, c_met, c_split;
+    __shared__ long long c_bytes;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int nreg = a.n_regions;
+    int64_t n = a.n_hdr;
+    int met0 = 0;
+    if (a.n_hdr_dev) {
+        n = *a.n_hdr_dev;
+        if (n < 0 || n > a.hdr_cap || a.walk_flags_dev[0] != 0) { n = 0; met0 = PK_WALK; }
+    }
+    if (tid == 0) { c_reads = 0; c_max = INT_MIN; c_met = met0; c_split = 0; c_bytes = 0; }
+    if (a.bounds_src != a.bounds)                // (one trip over the bus instead of one per step of every binary search)
+        for (int k = tid; k < 2 * nreg; k += PACK_BLOCK) a.bounds[k] = a.bounds_src[k];
+    const int64_t* r_start = a.bounds;
+    const int64_t* r_stop = a.bounds + nreg;
+    for (int r = tid; r < nreg; r += PACK_BLOCK) {
+        a.r_pairs[r] = 0; a.r_bases[r] = 0; a.r_ops[r] = 0; a.closed_reads[r] = 0; a.closed_bytes[r] = 0;
+    }
+    __threadfence();
+    __syncthreads();
+    const int64_t last_stop = r_stop[nreg - 1];
+    bool ended = false;
+    for (int64_t base = 0; base < n && !ended; base += PACK_BLOCK) {
+        const int64_t i = base + tid;
+        PackHdr h{};
+        int cls = pa_pack::HDR_SKIP;
+        if (i < n) {
+            h = a.hdr[i];
+            cls = pa_pack::header_class(h.ref_id, h.pos, a.tid, last_stop);
+        }
+        // the first header of the block that ends the walk (a corrupt one ends it with an error)
+        const bool corrupt = i < n && h.state == 2;
+        const int wm = wave_min((cls == pa_pack::HDR_STOP || corrupt) ? tid : PACK_BLOCK);
+        if (lane == 0) w_min[w] = wm;
+        __syncthreads();
+        int first = PACK_BLOCK;
+        for (int k = 0; k < 16; ++k) first = min(first, w_min[k]);
+        ended = first < PACK_BLOCK;
+        if (tid == first && corrupt) atomicOr(&c_met, PK_CORRUPT);
+        const bool active = i < n && tid < first && cls == pa_pack::HDR_CONTIG;
+        // the furthest position seen up to each header: the regions whose stop it has reached are closed
+        const int pinc = wave_inclusive_max(active ? h.pos : INT_MIN);
+        if (lane == 63) w_max[w] = pinc;
+        __syncthreads();
+        int pm_before = c_max;
+        for (int k = 0; k < w; ++k) pm_before = max(pm_before, w_max[k]);
+        int p_prev = __shfl_up(pinc, 1, 64);
+        if (lane == 0) p_prev = INT_MIN;
+        const int pm_excl = max(pm_before, p_prev);
+        const int pm_incl = max(pm_before, pinc);
+        int lo = 0, hi = 0;
+        bool is_read = false;
+        int64_t bytes = 0, seq_at = -1;
+        if (active) {
+            lo = pa_pack::first_open_region(r_stop, nreg, pm_incl);
+            const uint32_t flag = (uint32_t)h.flags & 0xffffu;
+            const int mapq = (h.flags >> 16) & 0xff;
+            hi = lo;
+            if (!pa_pack::record_dropped(flag, mapq, (uint32_t)h.l_seq, (uint32_t)h.n_cigar, a.include_supplementary, a.min_mapq))
+                hi = pa_pack::region_range_end(r_start, nreg, lo, pa_pack::read_end(h.pos, h.ref_len));
+            is_read = hi > lo;
+        }
+        if (is_read) {
+            int met = 0;
+            if (h.state == 1 || (h.state == 3 && !a.split)) met |= PK_CG;
+            if (h.state == 3) {
+                seq_at = h.data_off - (int64_t)h.block_size;
+                if (h.block_size <= 0 || seq_at < 0) met |= PK_OUTSIDE;
+            }
+            // the arena test of the host's staging: both slices inside the resident span, before anything dereferences them
+            if (h.n_cigar < 0 || h.l_seq < 0 || h.data_off < 0) {
+                met |= PK_OUTSIDE;
+            } else {
+                const int64_t ops_end = h.data_off + 4ll * h.n_cigar, bases = ((int64_t)h.l_seq + 1) / 2 + h.l_seq;
+                if (seq_at < 0 ? ops_end + bases > a.span_bytes : (ops_end > a.span_bytes || seq_at + bases > a.span_bytes)) met |= PK_OUTSIDE;
+            }
+            if (met) atomicOr(&c_met, met);
+            bytes = pa_pack::slice_bytes((uint32_t)h.n_cigar, (uint32_t)h.l_seq);
+        }
+        const int rinc = wave_inclusive_sum(is_read ? 1 : 0);
+        const long long binc = wave_inclusive_sum64(bytes);
+        if (lane == 63) { w_cnt[w] = rinc; w_bytes[w] = binc; }
+        __syncthreads();
+        int r_before = c_reads;
+        long long b_before = c_bytes;
+        for (int k = 0; k < w; ++k) { r_before += w_cnt[k]; b_before += w_bytes[k]; }
+        const int ri = r_before + rinc - (is_read ? 1 : 0);
+        const long long b_excl = b_before + binc - bytes;
+        if (active) {
+            // what was complete when this header closed its regions: the reads and bytes in front of it
+            const int lo_prev = pa_pack::first_open_region(r_stop, nreg, pm_excl);
+            for (int k = lo_prev; k < lo; ++k) { a.closed_reads[k] = ri; a.closed_bytes[k] = b_excl; }
+        }
+        if (is_read && ri < a.reads_cap) {
+            a.reads[ri] = PackedRead{h.data_off, h.pos, h.n_cigar, h.l_seq, (int32_t)((uint32_t)h.flags & 0x00ffffffu)};
+            a.seq_off[ri] = seq_at;
+            a.range[ri] = make_int2(lo, hi);
+            const unsigned long long room = (unsigned long long)(((int64_t)h.l_seq + 3 & ~(int64_t)3) + 4);
+            for (int r = lo; r < hi; ++r) {
+                atomicAdd(&a.r_pairs[r], 1);
+                atomicAdd(&a.r_bases[r], room);
+                atomicAdd(&a.r_ops[r], (unsigned long long)(uint32_t)h.n_cigar);
+            }
+        }
+        __syncthreads();
+        if (tid == PACK_BLOCK - 1) { c_reads = r_before + rinc; c_bytes = b_before + binc; c_max = pm_incl; }
+        __syncthreads();
+    }
+    __threadfence();
+    __syncthreads();
+    // the summary (one lane: a few dozen regions)
+    pa_device_pack* sum = reinterpret_cast<pa_device_pack*>(a.head);
+    int32_t* region_pairs = a.head + 16;
+    int32_t* op_base = reinterpret_cast<int32_t*>(reinterpret_cast<char*>(a.head) + pack_head_ops(nreg));
+    int64_t* seq_base = reinterpret_cast<int64_t*>(reinterpret_cast<char*>(a.head) + pack_head_bases(nreg));
+    if (tid == 0) {
+        int met = c_met;
+        const bool cut = !ended && !a.is_final;
+        const int n_closed = cut ? pa_pack::first_open_region(r_stop, nreg, c_max) : nreg;
+        const int total_reads = c_reads;
+        if (total_reads > a.reads_cap) met |= PK_CAP;
+        long long all_pairs = 0, pairs = 0, bases = 0, ops = 0;
+        region_pairs[0] = 0; op_base[0] = 0; seq_base[0] = 0;
+        for (int r = 0; r < nreg; ++r) {
+            const long long np = __hip_atomic_load(&a.r_pairs[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            all_pairs += np;
+            if (r < n_closed) {
+                const long long rb = (long long)__hip_atomic_load(&a.r_bases[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                pairs += np;
+                bases += rb;
+                ops += (long long)__hip_atomic_load(&a.r_ops[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (rb > 0xffffff00ll || ops > 0x7ffffff0ll) met |= PK_OUTSIDE;        // (the staging's limits: 2^32 bases per region, 2^31 operations)
+            }
+            region_pairs[r + 1] = (int32_t)(pairs < 0x7fffffff ? pairs : 0x7fffffff);
+            op_base[r + 1] = (int32_t)(ops < 0x7fffffff ? ops : 0x7fffffff);
+            seq_base[r + 1] = bases;
+        }
+        if (all_pairs > a.pairs_cap) met |= PK_CAP;
+        int status = 0;
+        if (met & PK_WALK) status = 6;
+        else if (met & PK_CORRUPT) status = 2;
+        else if (met & PK_CG) status = 3;
+        else if (met & PK_CAP) status = 1;
+        else if (cut && n_closed == 0) status = 4;
+        else if (met & PK_OUTSIDE) status = 5;
+        sum->status = status;
+        sum->n_done = status ? 0 : n_closed;
+        sum->n_reads = status ? 0 : ((cut && n_closed > 0) ? a.closed_reads[n_closed - 1] : total_reads);
+        sum->n_pairs = status ? 0 : (int32_t)pairs;
+        sum->n_split = 0;
+        sum->walk_flags[0] = a.walk_flags_dev ? a.walk_flags_dev[0] : 0;
+        sum->walk_flags[1] = a.walk_flags_dev ? a.walk_flags_dev[1] : 0;
+        sum->reserved = 0;
+        sum->n_headers = n;
+        sum->slice_bytes = status ? 0 : ((cut && n_closed > 0) ? a.closed_bytes[n_closed - 1] : c_bytes);
+        sum->total_bases = status ? 0 : bases;
+        sum->total_ops = status ? 0 : ops;
+    }
+    __threadfence();
+    __syncthreads();
+    // reads of the kept table whose bases lie apart from their operations
+    {
+        const int kept = sum->n_reads;
+        int mine = 0;
+        for (int k = tid; k < kept; k += PACK_BLOCK) mine += a.seq_off[k] >= 0 ? 1 : 0;
+        mine = wave_sum(mine);
+        if (lane == 0 && mine) atomicAdd(&c_split, mine);
+        __syncthreads();
+        if (tid == 0) sum->n_split = c_split;
+        __threadfence();
+        __syncthreads();
+    }
+    if (a.head_mapped)
+        for (int k = tid; k < a.head_words; k += PACK_BLOCK) a.head_mapped[k] = a.head[k];
+}
+
+// one workgroup per closed region: its reads in file order, each pair's slot and where its clipped bases / operations go
+// (the running sums of the host's staging: ((l_seq + 3) & ~3) + 4 bases and n_cigar operations per pair)
+__global__ __launch_bounds__(PACK_BLOCK) void pack_fill_kernel(PackArgs a) {
+    __shared__ int w_cnt[16], w_ops[16];
+    __shared__ long long w_bases[16];
+    __shared__ int c_cnt, c_ops;
+    __shared__ long long c_bases;
+    const pa_device_pack* sum = reinterpret_cast<const pa_device_pack*>(a.head);
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (sum->status != 0 || r >= sum->n_done) return;
+    const int nreg = a.n_regions, n_reads = min(sum->n_reads, a.reads_cap);
+    const int32_t* region_pairs = a.head + 16;
+    const int slot0 = region_pairs[r], slot1 = region_pairs[r + 1];
+    const int ops0 = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(a.head) + pack_head_ops(nreg))[r];
+    const long long bases0 = reinterpret_cast<const int64_t*>(reinterpret_cast<const char*>(a.head) + pack_head_bases(nreg))[r];
+    if (tid == 0) { c_cnt = 0; c_ops = 0; c_bases = 0; }
+    __syncthreads();
+    for (int base = 0; base < n_reads; base += PACK_BLOCK) {
+        const int ri = base + tid;
+        bool in = false;
+        int ops = 0;
+        long long room = 0;
+        if (ri < n_reads) {
+            const int2 rg = a.range[ri];
+            in = rg.x <= r && r < rg.y;
+            if (in) {
+                const PackedRead rd = a.reads[ri];
+                ops = rd.n_cigar;
+                room = ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
+            }
+        }
+        const int cinc = wave_inclusive_sum(in ? 1 : 0), oinc = wave_inclusive_sum(ops);
+        const long long binc = wave_inclusive_sum64(room);
+        if (lane == 63) { w_cnt[w] = cinc; w_ops[w] = oinc; w_bases[w] = binc; }
+        __syncthreads();
+        int c_before = c_cnt, o_before = c_ops;
+        long long b_before = c_bases;
+        for (int k = 0; k < w; ++k) { c_before += w_cnt[k]; o_before += w_ops[k]; b_before += w_bases[k]; }
+        const int slot = slot0 + c_before + cinc - 1;
+        if (in && slot < slot1 && slot < a.pairs_cap) {
+            a.pair_read[slot] = ri;
+            a.pairs[slot] = PairRec{bases0 + b_before + binc - room, ri, r, ops0 + o_before + oinc - ops, 0};
+        }
+        __syncthreads();
+        if (tid == PACK_BLOCK - 1) { c_cnt = c_before + cinc; c_ops = o_before + oinc; c_bases = b_before + binc; }
+        __syncthreads();
+    }
 }
 
 // exclusive scan of the per-tile record counts (one workgroup; tiles per batch: 12.5 k for 64 regions of 100 kb)
@@ -1338,6 +1620,14 @@ struct pa_variant_batch {
     int64_t name_bytes = 0;
     DBuf d_rules, d_row_slot, d_aux, d_large, d_grouped, d_rare_next, d_czero, d_cscan, d_pos, d_depths, d_freqs, d_names;
     HBuf h_rules, h_cscan;
+    // tables built on the device (pa_encoder_pack_records): where the last walk left its headers, the tables, the summary of
+    // the last pack as the staging needs it
+    struct { bool valid = false; bool mapped = false; size_t slots = 0, o_count = 0, o_flags = 0, o_out = 0, h_tail = 0;
+             std::chrono::steady_clock::time_point t0; } walk;
+    struct { bool valid = false; pa_device_pack sum{}; std::vector<int32_t> region_pairs, op_base; std::vector<int64_t> seq_base;
+             int64_t on_device = 0, handed_back = 0; } pk;
+    DBuf d_pk_hdr, d_pk_reads, d_pk_soff, d_pk_range, d_pk_pairs, d_pk_pair_read, d_pk_state;
+    HBuf h_pk;
     std::unique_ptr<RegionPool> pool;
     int host_threads = 0;             // threads of the candidate enumeration: 0 = the default below, 1 = the calling thread alone
     // results of the last run
@@ -1597,17 +1887,22 @@ static std::vector<int64_t> take_seq_offsets(pa_encoder* e) {
     return out;
 }
 
-// The packed form of a batch (include/pepper_amd_encoder.h): tables built in ONE page-locked block and uploaded with one copy,
-// the arena with another, then unpack_clip_kernel -- nothing here waits for the device.
-int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
-                 const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads, const int32_t* pair_read,
-                 const int32_t* region_pairs) {
-    const std::vector<int64_t> soff = take_seq_offsets(e);
-    if (!e || n_regions < 0 || (n_regions > 0 && (!regions || !params || !region_pairs)) || arena_bytes < 0 || n_reads < 0 ||
-        (n_reads > 0 && (!reads || !pair_read)))
-        return pa::set_error(PA_ERR_INVALID, "null argument");
-    if (!soff.empty() && (int64_t)soff.size() != n_reads)
-        return pa::set_error(PA_ERR_INVALID, "the base offsets set for this call are not one per packed read");
+// Where a packed staging's page-locked block (and its copy on the device) keeps what it uploads:
+// [RegRec x R][region_start x R][tile_region x tiles][PackedRead x reads][PairRec x pairs][base offsets x reads][reference bytes]
+// -- the three tables are empty where pa_encoder_pack_records has built them on the device
+struct PackedBlock {
+    size_t o_reg, o_start, o_tile, o_reads, o_pairs, o_soff, o_ref, bytes;
+};
+// the tables unpack_clip_kernel reads, as device addresses (seq_off null: no read keeps its bases apart)
+struct PackedTables {
+    const PackedRead* reads; const PairRec* pairs; const int64_t* seq_off;
+};
+
+// The first half of a packed staging, whoever built the tables: the regions checked, the block laid out with
+// `reads_bytes | pairs_bytes | soff_bytes` of room for tables that travel in it, and both of its copies allocated
+static int packed_begin(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
+                        const int32_t* region_pairs, const uint8_t* arena, int64_t arena_bytes, int32_t n_reads, size_t reads_bytes,
+                        size_t pairs_bytes, size_t soff_bytes, PackedBlock& L) {
     if (n_regions >= (1 << 22)) return pa::set_error(PA_ERR_INVALID, "more than 4194303 regions in one batch");
     ENC_HIP(hipSetDevice(e->device));
     if (!e->variant) e->variant = new pa_variant_batch();
@@ -1638,20 +1933,33 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
         b.n_tiles += (int)((p.region_end - p.region_start + 1 + 1 + TP - 1) / TP);
         if (b.total_rows > ((int64_t)1 << 30)) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^30 rows");
     }
-    // one block: [RegRec x R][region_start x R][tile_region x tiles][PackedRead x reads][PairRec x pairs][reference bytes]
     auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_reg = 0, o_start = up16(o_reg + (size_t)n_regions * sizeof(RegRec)), o_tile = up16(o_start + (size_t)n_regions * 8),
-                 o_reads = up16(o_tile + (size_t)b.n_tiles * 4), o_pairs = up16(o_reads + (size_t)n_reads * sizeof(PackedRead)),
-                 o_soff = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)), o_ref = up16(o_soff + soff.size() * 8),
-                 meta_bytes = up16(o_ref + (size_t)b.total_ref + 64);
-    if (!b.h_meta.ensure(meta_bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    L.o_reg = 0;
+    L.o_start = up16(L.o_reg + (size_t)n_regions * sizeof(RegRec));
+    L.o_tile = up16(L.o_start + (size_t)n_regions * 8);
+    L.o_reads = up16(L.o_tile + (size_t)b.n_tiles * 4);
+    L.o_pairs = up16(L.o_reads + reads_bytes);
+    L.o_soff = up16(L.o_pairs + pairs_bytes);
+    L.o_ref = up16(L.o_soff + soff_bytes);
+    L.bytes = up16(L.o_ref + (size_t)b.total_ref + 64);
+    if (!b.h_meta.ensure(L.bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_ALLOC(b.d_meta, L.bytes);
+    return PA_OK;
+}
+
+// The second half, shared by both forms: the region records from the offsets summed per region (`seq_base`, `op_base`:
+// [n_regions + 1], every read already checked against the arena by whoever summed them), the block uploaded with one copy,
+// the arena with another, then unpack_clip_kernel over `t` -- nothing here waits for the device.
+static int packed_finish(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
+                         const int32_t* region_pairs, const uint8_t* arena, int64_t arena_bytes, int32_t n_reads, const PackedBlock& L,
+                         const int64_t* seq_base, const int32_t* op_base, const PackedTables& t) {
+    pa_variant_batch& b = *e->variant;
+    const bool resident = arena == nullptr && n_reads > 0;
+    const int64_t n_pairs = n_regions ? region_pairs[n_regions] : 0;
     char* hm = b.h_meta.as<char>();
-    RegRec* regrecs = reinterpret_cast<RegRec*>(hm + o_reg);
-    int64_t* rstart = reinterpret_cast<int64_t*>(hm + o_start);
-    int32_t* tile_region = reinterpret_cast<int32_t*>(hm + o_tile);
-    PairRec* pairs = reinterpret_cast<PairRec*>(hm + o_pairs);
-    if (n_reads) std::memcpy(hm + o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
-    if (!soff.empty()) std::memcpy(hm + o_soff, soff.data(), soff.size() * 8);
+    RegRec* regrecs = reinterpret_cast<RegRec*>(hm + L.o_reg);
+    int64_t* rstart = reinterpret_cast<int64_t*>(hm + L.o_start);
+    int32_t* tile_region = reinterpret_cast<int32_t*>(hm + L.o_tile);
     b.total_rows = 0;
     b.total_ref = 0;
     b.n_tiles = 0;
@@ -1668,8 +1976,8 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
         rh.q = q;
         rh.L = (int)(p.region_end - p.region_start + 1);
         rh.row_base = b.total_rows;
-        rh.seq_base = b.total_bases;
-        rh.op_base = b.total_ops;
+        rh.seq_base = seq_base[r];
+        rh.op_base = op_base[r];
         rh.read_base = region_pairs[r];
         RegRec& g = regrecs[r];
         g.ref_off = b.total_ref;
@@ -1691,25 +1999,17 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
         g.del_thr = q.delete_freq_threshold;
         g.min_cov = q.min_coverage_threshold;
         rstart[r] = p.region_start;
-        for (int t = 0; t < g.n_tiles; ++t) tile_region[g.tile0 + t] = r;
-        if (p.reference_len > 0) std::memcpy(hm + o_ref + b.total_ref, p.reference, (size_t)p.reference_len);
-        // where each pair's clipped bases and operations go: room for the whole read (what is kept is known on the device only)
-        for (int32_t k = region_pairs[r]; k < region_pairs[r + 1]; ++k) {
-            const int32_t ri = pair_read[k];
-            if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
-            const pa_packed_read& rd = reads[ri];
-            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
-                return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
-            pairs[k] = PairRec{b.total_bases, ri, r, (int32_t)b.total_ops, 0};
-            b.total_bases += ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
-            b.total_ops += rd.n_cigar;
-            if (b.total_ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
-        }
-        if (b.total_bases - rh.seq_base > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
+        for (int t2 = 0; t2 < g.n_tiles; ++t2) tile_region[g.tile0 + t2] = r;
+        if (p.reference_len > 0) std::memcpy(hm + L.o_ref + b.total_ref, p.reference, (size_t)p.reference_len);
+        if (seq_base[r + 1] < seq_base[r] || op_base[r + 1] < op_base[r] || op_base[r + 1] > 0x7ffffff0)
+            return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
+        if (seq_base[r + 1] - seq_base[r] > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
         b.total_rows += (rh.L + 1 + 15) & ~(int64_t)15;
         b.total_ref += p.reference_len;
         b.n_tiles += g.n_tiles;
     }
+    b.total_bases = seq_base[n_regions];
+    b.total_ops = op_base[n_regions];
     b.total_reads = n_pairs;
     b.W = n_regions ? params[0].candidate_window_size + 1 : 33;
     b.F = n_regions ? params[0].feature_size : 26;
@@ -1720,7 +2020,6 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
         ENC_ALLOC(b.d_arena, (size_t)arena_bytes + 256);
         b.resident_bytes = 0;
     }
-    ENC_ALLOC(b.d_meta, meta_bytes);
     ENC_ALLOC(b.d_live, ((size_t)n_regions + 2) * 4);
     ENC_ALLOC(b.d_seq, (size_t)b.total_bases + 64);
     ENC_ALLOC(b.d_qual, (size_t)b.total_bases + 64);
@@ -1729,22 +2028,22 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
     ENC_ALLOC(b.d_reads, (size_t)n_pairs * sizeof(ReadRec) + 64);
     ENC_HIP(hipEventRecord(e->ev[6], st));
     if (arena_bytes > 0 && !resident) ENC_HIP(hipMemcpyAsync(b.d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
-    ENC_HIP(hipMemcpyAsync(b.d_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, st));
+    ENC_HIP(hipMemcpyAsync(b.d_meta.p, hm, L.bytes, hipMemcpyHostToDevice, st));
     ENC_HIP(hipMemsetAsync(b.d_live.p, 0, ((size_t)n_regions + 2) * 4, st));
     ENC_HIP(hipEventRecord(e->ev[7], st));
     const char* dm = b.d_meta.as<char>();
-    b.p_regions = reinterpret_cast<const RegRec*>(dm + o_reg);
-    b.p_tile_region = reinterpret_cast<const int32_t*>(dm + o_tile);
-    b.p_ref = dm + o_ref;
+    b.p_regions = reinterpret_cast<const RegRec*>(dm + L.o_reg);
+    b.p_tile_region = reinterpret_cast<const int32_t*>(dm + L.o_tile);
+    b.p_ref = dm + L.o_ref;
     if (n_pairs > 0) {
         UnpackArgs ua;
-        ua.pairs = reinterpret_cast<const PairRec*>(dm + o_pairs);
+        ua.pairs = t.pairs;
         ua.n_pairs = (int)n_pairs;
-        ua.preads = reinterpret_cast<const PackedRead*>(dm + o_reads);
+        ua.preads = t.reads;
         ua.regions = b.p_regions;
-        ua.region_start = reinterpret_cast<const int64_t*>(dm + o_start);
+        ua.region_start = reinterpret_cast<const int64_t*>(dm + L.o_start);
         ua.arena = b.d_arena.as<uint8_t>();
-        ua.seq_off = soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + o_soff);
+        ua.seq_off = t.seq_off;
         ua.reads = b.d_reads.as<ReadRec>();
         ua.cigar_op = b.d_cig_op.as<int32_t>();
         ua.cigar_len = b.d_cig_len.as<int32_t>();
@@ -1766,6 +2065,71 @@ int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regio
     b.last_pairs = n_pairs;
     b.staged = true;
     return PA_OK;
+}
+
+// The packed form of a batch (include/pepper_amd_encoder.h) from host tables: they travel in the block, and every pair is
+// walked here -- its read checked against the arena, its clipped bases and operations given room for the whole read (what is
+// kept is known on the device only)
+int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
+                 const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads, const int32_t* pair_read,
+                 const int32_t* region_pairs) {
+    const std::vector<int64_t> soff = take_seq_offsets(e);
+    if (!e || n_regions < 0 || (n_regions > 0 && (!regions || !params || !region_pairs)) || arena_bytes < 0 || n_reads < 0 ||
+        (n_reads > 0 && (!reads || !pair_read)))
+        return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!soff.empty() && (int64_t)soff.size() != n_reads)
+        return pa::set_error(PA_ERR_INVALID, "the base offsets set for this call are not one per packed read");
+    const int64_t n_pairs = n_regions ? std::max<int64_t>(0, region_pairs[n_regions]) : 0;      // (packed_begin refuses a negative one)
+    PackedBlock L;
+    const int rc = packed_begin(e, n_regions, regions, params, region_pairs, arena, arena_bytes, n_reads, (size_t)n_reads * sizeof(PackedRead),
+                                (size_t)n_pairs * sizeof(PairRec), soff.size() * 8, L);
+    if (rc != PA_OK) return rc;
+    pa_variant_batch& b = *e->variant;
+    char* hm = b.h_meta.as<char>();
+    PairRec* pairs = reinterpret_cast<PairRec*>(hm + L.o_pairs);
+    if (n_reads) std::memcpy(hm + L.o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
+    if (!soff.empty()) std::memcpy(hm + L.o_soff, soff.data(), soff.size() * 8);
+    std::vector<int64_t> seq_base((size_t)n_regions + 1, 0);
+    std::vector<int32_t> op_base((size_t)n_regions + 1, 0);
+    int64_t bases = 0, ops = 0;
+    for (int r = 0; r < n_regions; ++r) {
+        for (int32_t k = region_pairs[r]; k < region_pairs[r + 1]; ++k) {
+            const int32_t ri = pair_read[k];
+            if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
+            const pa_packed_read& rd = reads[ri];
+            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
+                return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
+            pairs[k] = PairRec{bases, ri, r, (int32_t)ops, 0};
+            bases += ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
+            ops += rd.n_cigar;
+            if (ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
+        }
+        if (bases - seq_base[(size_t)r] > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
+        seq_base[(size_t)r + 1] = bases;
+        op_base[(size_t)r + 1] = (int32_t)ops;
+    }
+    const char* dm = b.d_meta.as<char>();
+    const PackedTables t{reinterpret_cast<const PackedRead*>(dm + L.o_reads), reinterpret_cast<const PairRec*>(dm + L.o_pairs),
+                         soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + L.o_soff)};
+    return packed_finish(e, n_regions, regions, params, region_pairs, arena, arena_bytes, n_reads, L, seq_base.data(), op_base.data(), t);
+}
+
+// The same batch over the tables pa_encoder_pack_records left on the device: it has placed the pairs, checked every read
+// against the span and summed the same offsets, so the block carries the regions and the reference only
+static int stage_packed_device(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params) {
+    take_seq_offsets(e);                      // (a table set for this call has nothing to say about the device's reads)
+    pa_variant_batch& b = *e->variant;
+    const int32_t n_reads = b.pk.sum.n_reads;
+    const int32_t* region_pairs = b.pk.region_pairs.data();
+    if (n_regions < 0 || (n_regions > 0 && (!regions || !params))) return pa::set_error(PA_ERR_INVALID, "null argument");
+    // (no read: nothing is dereferenced, and the staging takes no arena -- as the host-table form is called for such a run)
+    const int64_t arena_bytes = n_reads > 0 ? b.resident_bytes : 0;
+    PackedBlock L;
+    const int rc = packed_begin(e, n_regions, regions, params, region_pairs, nullptr, arena_bytes, n_reads, 0, 0, 0, L);
+    if (rc != PA_OK) return rc;
+    const PackedTables t{b.d_pk_reads.as<PackedRead>(), b.d_pk_pairs.as<PairRec>(), b.pk.sum.n_split > 0 ? b.d_pk_soff.as<int64_t>() : nullptr};
+    return packed_finish(e, n_regions, regions, params, region_pairs, nullptr, arena_bytes, n_reads, L, b.pk.seq_base.data(),
+                         b.pk.op_base.data(), t);
 }
 
 int run_staged(pa_encoder* e, int64_t* n_candidates) {
@@ -2317,6 +2681,7 @@ int pa_encoder_inflate_bgzf(pa_encoder* e, const uint8_t* comp, int64_t comp_byt
     if (!e->variant) e->variant = new pa_variant_batch();
     pa_variant_batch& b = *e->variant;
     b.resident_bytes = 0;
+    b.walk.valid = b.pk.valid = false;            // (headers and tables describe the span that was resident)
     b.ms[10] = b.ms[11] = 0;
     if (n_blocks == 0) return PA_OK;
     hipStream_t st = e->stream;
@@ -2360,13 +2725,10 @@ int pa_encoder_inflate_bgzf(pa_encoder* e, const uint8_t* comp, int64_t comp_byt
     return PA_OK;
 }
 
-// The record headers of the span pa_encoder_inflate_bgzf left on the device (inflate.hip: record_chase_kernel and friends)
-int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry,
-                            void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags) {
-    if (!e || !entries || n_entries < 1 || cap_per_entry < 1 || !headers || headers_cap < 0 || !n_headers || !flags || data_bytes < 0)
-        return pa::set_error(PA_ERR_INVALID, "null or invalid argument");
-    *n_headers = 0;
-    flags[0] = flags[1] = 0;
+// The record headers of the span pa_encoder_inflate_bgzf left on the device (inflate.hip: record_chase_kernel and friends):
+// everything up to the wait -- the walk's launches and, where the page-locked block is not mapped, the copies of its tail words
+static int walk_submit(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry) {
+    if (!e || !entries || n_entries < 1 || cap_per_entry < 1 || data_bytes < 0) return pa::set_error(PA_ERR_INVALID, "null or invalid argument");
     if (!e->variant || e->variant->resident_bytes <= 0 || data_bytes > e->variant->resident_bytes)
         return pa::set_error(PA_ERR_INVALID, "no inflated span of that size resident on the device");
     for (int32_t k = 0; k < n_entries; ++k)
@@ -2374,6 +2736,7 @@ int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* en
             return pa::set_error(PA_ERR_INVALID, "record entries must ascend inside the span");
     ENC_HIP(hipSetDevice(e->device));
     pa_variant_batch& b = *e->variant;
+    b.walk.valid = b.pk.valid = false;
     hipStream_t st = e->stream;
     const size_t n = (size_t)n_entries, slots = n * (size_t)cap_per_entry;
     const size_t o_counts = n * 8, o_base = o_counts + n * 4, o_flags = o_base + (n + 1) * 4, o_slots = (o_flags + 8 + 63) & ~(size_t)63,
@@ -2390,7 +2753,7 @@ int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* en
     void* mapped = nullptr;
     if (hipHostGetDevicePointer(&mapped, hw, 0) != hipSuccess || !mapped) mapped = nullptr;
     char* mw = static_cast<char*>(mapped);
-    const auto t0 = std::chrono::steady_clock::now();
+    b.walk.t0 = std::chrono::steady_clock::now();
     if (!mapped) ENC_HIP(hipMemcpyAsync(dw, hw, n * 8, hipMemcpyHostToDevice, st));
     ENC_HIP(hipMemsetAsync(dw + o_flags, 0, 8, st));
     pa::launch_record_walk(st, b.d_arena.as<uint8_t>(), data_bytes, reinterpret_cast<const int64_t*>(mapped ? mw : dw), n_entries,
@@ -2402,17 +2765,187 @@ int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* en
         ENC_HIP(hipMemcpyAsync(tail, dw + o_base + n * 4, 4, hipMemcpyDeviceToHost, st));
         ENC_HIP(hipMemcpyAsync(tail + 1, dw + o_flags, 8, hipMemcpyDeviceToHost, st));
     }
+    b.walk.mapped = mapped != nullptr;
+    b.walk.slots = slots;
+    b.walk.o_count = o_base + n * 4;
+    b.walk.o_flags = o_flags;
+    b.walk.o_out = o_out;
+    b.walk.h_tail = h_tail;
+    b.walk.valid = true;
+    return PA_OK;
+}
+
+int pa_encoder_submit_walk(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry) {
+    return walk_submit(e, data_bytes, entries, n_entries, cap_per_entry);
+}
+
+// the wait, the walk's tail words and, where they are clean, the headers themselves
+int pa_encoder_walk_headers(pa_encoder* e, void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags) {
+    if (!e || !headers || headers_cap < 0 || !n_headers || !flags) return pa::set_error(PA_ERR_INVALID, "null or invalid argument");
+    *n_headers = 0;
+    flags[0] = flags[1] = 0;
+    if (!e->variant || !e->variant->walk.valid) return pa::set_error(PA_ERR_INVALID, "no record walk of the resident span on this handle");
+    ENC_HIP(hipSetDevice(e->device));
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    const int32_t* tail = reinterpret_cast<const int32_t*>(b.h_walk.as<char>() + b.walk.h_tail);
     ENC_HIP(hipStreamSynchronize(st));
     flags[0] = tail[1];
     flags[1] = tail[2];
     const int64_t found = tail[0];
     if (flags[0] == 0 && found > headers_cap) flags[0] |= 4;            // the caller's table is too small
     if (flags[0] == 0 && found > 0) {                                   // (the headers themselves: one copy out of device memory --
-        ENC_HIP(hipMemcpyAsync(headers, dw + o_out, (size_t)found * 40, hipMemcpyDeviceToHost, st));      // 40-byte stores of single
+        ENC_HIP(hipMemcpyAsync(headers, b.d_walk.as<char>() + b.walk.o_out, (size_t)found * 40, hipMemcpyDeviceToHost, st));      // 40-byte stores of single
         ENC_HIP(hipStreamSynchronize(st));                                                              // lanes across PCIe are slower)
     }
     *n_headers = flags[0] == 0 ? found : 0;
-    b.ms[11] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return PA_OK;
+}
+
+int pa_encoder_walk_records(pa_encoder* e, int64_t data_bytes, const int64_t* entries, int32_t n_entries, int32_t cap_per_entry,
+                            void* headers, int64_t headers_cap, int64_t* n_headers, int32_t* flags) {
+    if (!e || !entries || n_entries < 1 || cap_per_entry < 1 || !headers || headers_cap < 0 || !n_headers || !flags || data_bytes < 0)
+        return pa::set_error(PA_ERR_INVALID, "null or invalid argument");
+    *n_headers = 0;
+    flags[0] = flags[1] = 0;
+    int rc = walk_submit(e, data_bytes, entries, n_entries, cap_per_entry);
+    if (rc == PA_OK) rc = pa_encoder_walk_headers(e, headers, headers_cap, n_headers, flags);
+    if (rc != PA_OK) return rc;
+    pa_variant_batch& b = *e->variant;
+    b.ms[11] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.walk.t0).count();
+    return PA_OK;
+}
+
+// The read and pair tables of a run of regions built where the headers lie (pack_scan_kernel, pack_fill_kernel): one
+// submission -- behind the walk's, when pa_encoder_submit_walk has just queued it -- and one wait; the summary comes back
+// through the page-locked block (mapped where possible, else one small copy)
+int pa_encoder_pack_records(pa_encoder* e, const void* headers, int64_t n_headers, int32_t data_is_final, int32_t ref_id,
+                            int32_t n_regions, const int64_t* start, const int64_t* stop, int32_t include_supplementary,
+                            int32_t min_mapq, int32_t reads_cap, int32_t pairs_cap, int32_t* region_pairs, pa_device_pack* out) {
+    if (!e || !out || !region_pairs || n_regions < 0 || (n_regions > 0 && (!start || !stop)) || n_headers < 0 || reads_cap < 0 ||
+        pairs_cap < 0 || ref_id < 0)
+        return pa::set_error(PA_ERR_INVALID, "null or invalid argument");
+    *out = pa_device_pack{};
+    for (int r = 0; r <= n_regions; ++r) region_pairs[r] = 0;
+    for (int r = 0; r < n_regions; ++r)
+        if (stop[r] < start[r] || (r > 0 && (start[r] < start[r - 1] || stop[r] < stop[r - 1])))
+            return pa::set_error(PA_ERR_INVALID, "pack_records: regions must be ascending in start and stop");
+    ENC_HIP(hipSetDevice(e->device));
+    if (!e->variant) e->variant = new pa_variant_batch();
+    pa_variant_batch& b = *e->variant;
+    b.pk.valid = false;
+    if (!headers && !b.walk.valid) return pa::set_error(PA_ERR_INVALID, "no headers given and no record walk of the resident span on this handle");
+    if (n_regions == 0) return PA_OK;
+    hipStream_t st = e->stream;
+    const size_t nr = (size_t)n_regions, head_bytes = (pack_head_bytes(n_regions) + 15) & ~(size_t)15;
+    // device state: head | start, stop | bases, operations, closed bytes [n] x 8 | pairs, closed reads [n] x 4
+    const size_t o_bounds = head_bytes, o_rb = o_bounds + nr * 16, o_ro = o_rb + nr * 8, o_cb = o_ro + nr * 8, o_rp = o_cb + nr * 8,
+                 o_cr = o_rp + nr * 4, state_bytes = o_cr + nr * 4;
+    ENC_ALLOC(b.d_pk_state, state_bytes + 64);
+    ENC_ALLOC(b.d_pk_reads, (size_t)reads_cap * sizeof(PackedRead) + 64);
+    ENC_ALLOC(b.d_pk_soff, (size_t)reads_cap * 8 + 64);
+    ENC_ALLOC(b.d_pk_range, (size_t)reads_cap * 8 + 64);
+    ENC_ALLOC(b.d_pk_pairs, (size_t)pairs_cap * sizeof(PairRec) + 64);
+    ENC_ALLOC(b.d_pk_pair_read, (size_t)pairs_cap * 4 + 64);
+    if (headers) ENC_ALLOC(b.d_pk_hdr, (size_t)n_headers * sizeof(PackHdr) + 64);
+    // page-locked: start, stop | head
+    if (!b.h_pk.ensure(nr * 16 + head_bytes)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed in the device pack");
+    char* hp = b.h_pk.as<char>();
+    std::memcpy(hp, start, nr * 8);
+    std::memcpy(hp + nr * 8, stop, nr * 8);
+    pa_device_pack* hsum = reinterpret_cast<pa_device_pack*>(hp + nr * 16);
+    *hsum = pa_device_pack{};
+    hsum->status = -1;                              // (a kernel that never ran leaves no usable summary)
+    void* mapped = nullptr;
+    if (hipHostGetDevicePointer(&mapped, hp, 0) != hipSuccess || !mapped) mapped = nullptr;
+    char* ds = b.d_pk_state.as<char>();
+    if (headers && n_headers > 0)
+        ENC_HIP(hipMemcpyAsync(b.d_pk_hdr.p, headers, (size_t)n_headers * sizeof(PackHdr), hipMemcpyHostToDevice, st));
+    if (!mapped) ENC_HIP(hipMemcpyAsync(ds + o_bounds, hp, nr * 16, hipMemcpyHostToDevice, st));
+    PackArgs a{};
+    if (headers) {
+        a.hdr = b.d_pk_hdr.as<PackHdr>();
+        a.n_hdr = n_headers;
+    } else {
+        const char* dw = b.d_walk.as<char>();
+        a.hdr = reinterpret_cast<const PackHdr*>(dw + b.walk.o_out);
+        a.n_hdr_dev = reinterpret_cast<const int32_t*>(dw + b.walk.o_count);
+        a.walk_flags_dev = reinterpret_cast<const int32_t*>(dw + b.walk.o_flags);
+        a.hdr_cap = (int64_t)b.walk.slots;
+    }
+    a.bounds = reinterpret_cast<int64_t*>(ds + o_bounds);
+    a.bounds_src = mapped ? static_cast<const int64_t*>(mapped) : a.bounds;
+    a.n_regions = n_regions;
+    a.tid = ref_id;
+    a.is_final = data_is_final != 0;
+    a.include_supplementary = include_supplementary;
+    a.min_mapq = min_mapq;
+    a.split = e->split_walk ? 1 : 0;
+    a.reads_cap = reads_cap;
+    a.pairs_cap = pairs_cap;
+    a.span_bytes = b.resident_bytes;
+    a.reads = b.d_pk_reads.as<PackedRead>();
+    a.seq_off = b.d_pk_soff.as<int64_t>();
+    a.range = b.d_pk_range.as<int2>();
+    a.pairs = b.d_pk_pairs.as<PairRec>();
+    a.pair_read = b.d_pk_pair_read.as<int32_t>();
+    a.r_bases = reinterpret_cast<unsigned long long*>(ds + o_rb);
+    a.r_ops = reinterpret_cast<unsigned long long*>(ds + o_ro);
+    a.closed_bytes = reinterpret_cast<int64_t*>(ds + o_cb);
+    a.r_pairs = reinterpret_cast<int32_t*>(ds + o_rp);
+    a.closed_reads = reinterpret_cast<int32_t*>(ds + o_cr);
+    a.head = reinterpret_cast<int32_t*>(ds);
+    a.head_mapped = mapped ? reinterpret_cast<int32_t*>(static_cast<char*>(mapped) + nr * 16) : nullptr;
+    a.head_words = (int32_t)(pack_head_bytes(n_regions) / 4);
+    hipLaunchKernelGGL(pack_scan_kernel, dim3(1), dim3(PACK_BLOCK), 0, st, a);
+    ENC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(pack_fill_kernel, dim3((unsigned)n_regions), dim3(PACK_BLOCK), 0, st, a);
+    ENC_HIP(hipGetLastError());
+    if (!mapped) ENC_HIP(hipMemcpyAsync(hp + nr * 16, ds, pack_head_bytes(n_regions), hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipStreamSynchronize(st));
+    if (hsum->status < 0) return pa::set_error(PA_ERR_HIP, "the device pack left no summary");
+    *out = *hsum;
+    const int32_t* h_pairs = reinterpret_cast<const int32_t*>(hp + nr * 16 + 64);
+    const int32_t* h_ops = reinterpret_cast<const int32_t*>(hp + nr * 16 + pack_head_ops(n_regions));
+    const int64_t* h_bases = reinterpret_cast<const int64_t*>(hp + nr * 16 + pack_head_bases(n_regions));
+    if (out->status == 0) {
+        std::copy(h_pairs, h_pairs + nr + 1, region_pairs);
+        b.pk.sum = *out;
+        b.pk.region_pairs.assign(h_pairs, h_pairs + nr + 1);
+        b.pk.op_base.assign(h_ops, h_ops + nr + 1);
+        b.pk.seq_base.assign(h_bases, h_bases + nr + 1);
+        b.pk.valid = true;
+        b.pk.on_device += 1;
+    } else {
+        b.pk.handed_back += 1;
+    }
+    if (!headers) b.ms[11] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - b.walk.t0).count();
+    return PA_OK;
+}
+
+int pa_encoder_stage_packed_device(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params) {
+    if (!e || !e->variant || !e->variant->pk.valid) return pa::set_error(PA_ERR_INVALID, "no tables packed on the device for the resident span");
+    pa_variant_batch& b = *e->variant;
+    if (n_regions != b.pk.sum.n_done) return pa::set_error(PA_ERR_INVALID, "the device pack closed another number of regions");
+    return stage_packed_device(e, n_regions, regions, params);
+}
+
+int pa_encoder_packed_tables(pa_encoder* e, pa_packed_read* reads, int32_t* pair_read, int64_t* seq_off) {
+    if (!e || !e->variant || !e->variant->pk.valid) return pa::set_error(PA_ERR_INVALID, "no tables packed on the device");
+    ENC_HIP(hipSetDevice(e->device));
+    pa_variant_batch& b = *e->variant;
+    const size_t n_reads = (size_t)b.pk.sum.n_reads, n_pairs = (size_t)b.pk.sum.n_pairs;
+    if (reads && n_reads) ENC_HIP(hipMemcpyAsync(reads, b.d_pk_reads.p, n_reads * sizeof(PackedRead), hipMemcpyDeviceToHost, e->stream));
+    if (seq_off && n_reads) ENC_HIP(hipMemcpyAsync(seq_off, b.d_pk_soff.p, n_reads * 8, hipMemcpyDeviceToHost, e->stream));
+    if (pair_read && n_pairs) ENC_HIP(hipMemcpyAsync(pair_read, b.d_pk_pair_read.p, n_pairs * 4, hipMemcpyDeviceToHost, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    return PA_OK;
+}
+
+int pa_encoder_pack_calls(pa_encoder* e, int64_t* on_device, int64_t* handed_back) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (on_device) *on_device = e->variant ? e->variant->pk.on_device : 0;
+    if (handed_back) *handed_back = e->variant ? e->variant->pk.handed_back : 0;
     return PA_OK;
 }
 

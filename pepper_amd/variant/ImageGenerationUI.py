@@ -180,9 +180,11 @@ class ImageGenerationUtils:
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
         # ... and two counts: intervals the device sampled down, intervals that took the host-clipped form for any reason
         # ... and the encoder calls of the packed form (one per group of intervals), with those whose candidates were enumerated
-        # on the device / handed back to the host (both 0 unless PEPPER_AMD_DEVICE_CANDIDATES=1)
+        # on the device / handed back to the host (both 0 unless PEPPER_AMD_DEVICE_CANDIDATES=1), and those whose read and pair
+        # tables were built on the device (PEPPER_AMD_DEVICE_PACK=1) / on the host
         mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0,
-                "encoder_calls": 0, "device_enumerated_calls": 0, "host_enumerated_calls": 0}
+                "encoder_calls": 0, "device_enumerated_calls": 0, "host_enumerated_calls": 0,
+                "device_packed_calls": 0, "host_packed_calls": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -273,6 +275,9 @@ class ImageGenerationUtils:
             # every call (pa_encoder_set_device_candidates)
             enc.set_device_candidates(_lib.device_candidates())
             calls_before = enc.candidate_calls()
+            # the read and pair tables built behind the device's record walk (pa_encoder_pack_records): the lap bam_walk_device
+            # is then walk + pack with their one wait, and bam_walk only the spans the device handed back
+            device_pack = _lib.device_pack()
             g0 = 0
             while g0 < len(intervals):
                 # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last
@@ -290,7 +295,7 @@ class ImageGenerationUtils:
                 # a batch the device form cannot take (pack_device's docstring) goes through the host packer
                 on_device = enc.pack_device(bam_handler, chr_name, [r[0] for r in regions], [r[1] for r in regions],
                                             options.include_supplementary, options.min_mapq, laps=mine,
-                                            long_cigars=long_cigars) if device_inflate else None
+                                            long_cigars=long_cigars, device_pack=device_pack) if device_inflate else None
                 resident = on_device is not None
                 if resident:
                     n_done, region_pairs, counts = on_device
@@ -332,6 +337,7 @@ class ImageGenerationUtils:
                     continue
                 t0 = lap("encode", t0)
                 mine["encoder_calls"] += 1
+                mine["device_packed_calls" if (resident and enc.device_packed) else "host_packed_calls"] += 1
                 probs, at = None, 0
                 if sink is not None:
                     # the group's windows are still where the encoder left them on the device: the model reads them there

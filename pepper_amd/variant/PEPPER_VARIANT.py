@@ -285,6 +285,8 @@ class PackedEncoder(object):
 
     _split_walk = False             # what pa_encoder_set_split_slices was last told (off on a new handle)
     host_walk_spans = 0             # pack_device calls that asked for the device's record walk and walked the span on the host after all
+    _device_packed = False          # the last pack / pack_device left its tables on the device (pa_encoder_pack_records): encode stages from there
+    pack_handbacks = 0              # pack_device(device_pack=True) calls whose span the device handed back to the host's pack_headers
     _idle = []                      # encoders returned by release(): a later job's workers take them instead of pinning new arenas
     _idle_lock = __import__("threading").Lock()
 
@@ -343,6 +345,8 @@ class PackedEncoder(object):
         self.long_cigar_reads = 0       # such reads kept on the device path, counted once per pack_device call that kept them
         self._split_walk = False
         self.host_walk_spans = 0
+        self._device_packed = False
+        self.pack_handbacks = 0
 
     def close(self):
         if self.enc:
@@ -375,6 +379,21 @@ class PackedEncoder(object):
         _lib.check(self.lib.pa_encoder_candidate_calls(self.enc, ctypes.byref(dev), ctypes.byref(host)))
         return dev.value, host.value
 
+    def pack_calls(self):
+        """-> (calls packed on the device, calls the device handed back) since this handle was created (pa_encoder_pack_calls)."""
+        dev, back = ctypes.c_int64(), ctypes.c_int64()
+        _lib.check(self.lib.pa_encoder_pack_calls(self.enc, ctypes.byref(dev), ctypes.byref(back)))
+        return dev.value, back.value
+
+    def packed_tables(self, n_reads, n_pairs):
+        """-> (reads, pair_read, seq_off): the tables the last device pack built, copied out (pa_encoder_packed_tables)."""
+        from pepper_amd.variant.bam import PACKED_READ
+        reads = np.zeros(max(1, int(n_reads)), PACKED_READ)
+        pair_read = np.zeros(max(1, int(n_pairs)), np.int32)
+        seq_off = np.zeros(max(1, int(n_reads)), np.int64)
+        _lib.check(self.lib.pa_encoder_packed_tables(self.enc, reads.ctypes.data, pair_read.ctypes.data, seq_off.ctypes.data))
+        return reads[:int(n_reads)], pair_read[:int(n_pairs)], seq_off[:int(n_reads)]
+
     def sampled(self):
         """-> (intervals the device sampled down, reads it dropped) since this handle was created."""
         regions, dropped = ctypes.c_int64(), ctypes.c_int64()
@@ -387,9 +406,16 @@ class PackedEncoder(object):
         _lib.check(self.lib.pa_encoder_pair_live(self.enc, keep.ctypes.data, int(n_pairs)))
         return keep[:int(n_pairs)]
 
+    @property
+    def device_packed(self):
+        """True when the last pack / pack_device left its tables on the device (pack_device(device_pack=True), not handed
+        back): encode(..., resident=True) stages from there, and the driver counts the call as device-packed."""
+        return self._device_packed
+
     def pack(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq):
         """-> (n_done, region_pairs, (n_reads, n_pairs, arena_bytes)): BAM_handler.pack_regions into this object's buffers."""
         self.seq_off = None
+        self._device_packed = False
         return bam_handler.pack_regions(contig, starts, stops, include_supplementary, min_mapq, self.arena, self.reads, self.pair_read)
 
     def send_seq_offsets(self, n_reads, resident):
@@ -401,7 +427,7 @@ class PackedEncoder(object):
             _lib.check(self.lib.pa_encoder_set_seq_offsets(self.enc, None, 0))
 
     def pack_device(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq, lookahead_windows=4, laps=None,
-                    long_cigars=False):
+                    long_cigars=False, device_pack=False):
         """The same tables with the BGZF members inflated ON THE DEVICE (pa_encoder_inflate_bgzf) into the encoder's arena and
         the records left in place there: the file span of the regions' reads (BAM index) is read as it is, uploaded, inflated
         one wavefront per member, and walked on the host in a downloaded copy (headers, filters, region test -- no inflate, no
@@ -411,10 +437,15 @@ class PackedEncoder(object):
         core (self.seq_off, which encode(..., resident=True) and PolishChain.run pass on).  self.long_cigar_reads adds up the
         CG reads each call kept: a read that reaches two calls' runs of regions is counted in both.  self.host_walk_spans
         counts the calls that asked for the device's record walk and walked a downloaded copy of the span on the host instead
-        (slot overflow, an auxiliary field the device's tag walk could not follow)."""
+        (slot overflow, an auxiliary field the device's tag walk could not follow).
+        device_pack (with the device's record walk): the tables are built where the headers lie (pa_encoder_pack_records, queued
+        behind the walk: one wait for both) and stay there -- self.reads / self.pair_read are not filled, self.seq_off stays
+        None, and encode(..., resident=True) stages from the device tables.  A span the device hands back (status != 0) has
+        its headers downloaded and goes through pack_headers as without the switch; self.pack_handbacks counts those."""
         import time
         from pepper_amd.variant.bam import BamError
         self.seq_off = None
+        self._device_packed = False
         if not bam_handler.has_index():
             return None
         if self.span is None:
@@ -471,14 +502,41 @@ class PackedEncoder(object):
             if bool(long_cigars) != self._split_walk:
                 _lib.check(self.lib.pa_encoder_set_split_slices(self.enc, 1 if long_cigars else 0))
                 self._split_walk = bool(long_cigars)
+            tid = bam_handler.contig_index(contig) if device_pack else None
+            summary = None
             try:
-                _lib.check(self.lib.pa_encoder_walk_records(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots,
-                                                            self.headers.ctypes.data, len(self.headers), ctypes.byref(n_headers),
-                                                            flags.ctypes.data))
+                if tid is not None and tid >= 0:
+                    # walk and pack in one submission, one wait; the walk's flags and the pack's summary are read after it
+                    summary = _lib.DevicePack()
+                    d_starts = np.ascontiguousarray(starts[:n], np.int64)
+                    d_stops = np.ascontiguousarray(stops[:n], np.int64)
+                    d_pairs = np.zeros(n + 1, np.int32)
+                    _lib.check(self.lib.pa_encoder_submit_walk(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots))
+                    _lib.check(self.lib.pa_encoder_pack_records(self.enc, None, 0, int(bool(final)), int(tid), n, d_starts.ctypes.data,
+                                                                d_stops.ctypes.data, int(bool(include_supplementary)), int(min_mapq),
+                                                                len(self.reads), len(self.pair_read), d_pairs.ctypes.data,
+                                                                ctypes.byref(summary)))
+                    flags[0], flags[1] = summary.walk_flags[0], summary.walk_flags[1]
+                    if flags[0] == 0 and summary.status != 0:
+                        # handed back: the headers come down after all and the host's walk decides
+                        self.pack_handbacks += 1
+                        _lib.check(self.lib.pa_encoder_walk_headers(self.enc, self.headers.ctypes.data, len(self.headers),
+                                                                    ctypes.byref(n_headers), flags.ctypes.data))
+                else:
+                    _lib.check(self.lib.pa_encoder_walk_records(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots,
+                                                                self.headers.ctypes.data, len(self.headers), ctypes.byref(n_headers),
+                                                                flags.ctypes.data))
             except _lib.PepperAmdError as err:
                 if getattr(err, "code", 0) != _lib.PA_ERR_INVALID:
                     raise
                 return None                              # (entries outside the span: a stale index -- the host packer reads the file itself)
+            if flags[0] == 0 and summary is not None and summary.status == 0:
+                if laps is not None:
+                    laps["bam_walk_device"] = laps.get("bam_walk_device", 0.0) + time.perf_counter() - t0
+                self._device_packed = True
+                if long_cigars and summary.n_split:
+                    self.long_cigar_reads += summary.n_split
+                return summary.n_done, d_pairs, (summary.n_reads, summary.n_pairs, int(out_bytes))
             if flags[0] == 0:
                 headers = n_headers.value
             else:
@@ -542,11 +600,17 @@ class PackedEncoder(object):
         region_pairs = np.ascontiguousarray(region_pairs[:n + 1], np.int32)
         n_reads, _n_pairs, arena_bytes = counts
         # resident: the arena is the inflated span pack_device left on the device
-        self.send_seq_offsets(n_reads, resident)
-        _lib.check(self.lib.pa_encoder_stage_packed(self.enc, n, ctypes.cast(regs, ctypes.c_void_p), ctypes.cast(pars, ctypes.c_void_p),
-                                                    None if (resident and n_reads > 0) else self.arena.ctypes.data,
-                                                    int(arena_bytes), self.reads.ctypes.data, int(n_reads),
-                                                    self.pair_read.ctypes.data, region_pairs.ctypes.data))
+        if resident and self._device_packed:
+            # the tables the last pack_device(device_pack=True) built are on the device, beside the span
+            self.send_seq_offsets(0, False)
+            _lib.check(self.lib.pa_encoder_stage_packed_device(self.enc, n, ctypes.cast(regs, ctypes.c_void_p),
+                                                               ctypes.cast(pars, ctypes.c_void_p)))
+        else:
+            self.send_seq_offsets(n_reads, resident)
+            _lib.check(self.lib.pa_encoder_stage_packed(self.enc, n, ctypes.cast(regs, ctypes.c_void_p), ctypes.cast(pars, ctypes.c_void_p),
+                                                        None if (resident and n_reads > 0) else self.arena.ctypes.data,
+                                                        int(arena_bytes), self.reads.ctypes.data, int(n_reads),
+                                                        self.pair_read.ctypes.data, region_pairs.ctypes.data))
         batch = StagedBatch.__new__(StagedBatch)
         batch.lib, batch.enc, batch.n_regions = self.lib, self.enc, n
         batch.window, batch.features = candidate_window_size + 1, feature_size

@@ -39,6 +39,7 @@ SYMBOLS = [
     ("pa_bam_span_entries", ctypes.c_int, [c_void_p, c_char_p, c_int64, c_void_p, c_int32, c_void_p, c_int32, ctypes.POINTER(c_int32)]),
     ("pa_bam_pack_headers", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_char_p, c_int32, c_void_p, c_void_p, c_int32, c_int32,
                                            c_void_p, c_int32, c_void_p, c_int32, c_void_p, ctypes.POINTER(c_int32), c_void_p]),
+    ("pa_bam_pack_rule", ctypes.c_int, [c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     ("pa_bam_pack_inflated", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_char_p, c_int32, c_void_p, c_void_p,
                                             c_int32, c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
                                             ctypes.POINTER(c_int32), c_void_p]),
@@ -182,6 +183,13 @@ class BAM_handler(object):
             _check(lib.pa_bam_target(self._h, i, buf, n + 1, None))
             out.append(buf.value.decode())
         return out
+
+    def contig_index(self, chromosome):
+        """The contig's index in the BAM header (the ref_id of its records), -1 when the header does not name it."""
+        names = getattr(self, "_contig_names", None)
+        if names is None:
+            names = self._contig_names = {name: i for i, name in enumerate(self.get_chromosome_sequence_names())}
+        return names.get(str(chromosome), -1)
 
     def get_chromosome_sequence_names_with_length(self):
         lib = _lib()
