@@ -508,7 +508,7 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_scan_kernel(PackArgs a) {
             a.reads[ri] = PackedRead{h.data_off, h.pos, h.n_cigar, h.l_seq, (int32_t)((uint32_t)h.flags & 0x00ffffffu)};
             a.seq_off[ri] = seq_at;
             a.range[ri] = make_int2(lo, hi);
-            const unsigned long long room = (unsigned long long)(((int64_t)h.l_seq + 3 & ~(int64_t)3) + 4);
+            const unsigned long long room = (unsigned long long)pa_pack::base_room(h.l_seq);
             for (int r = lo; r < hi; ++r) {
                 atomicAdd(&a.r_pairs[r], 1);
                 atomicAdd(&a.r_bases[r], room);
@@ -588,7 +588,7 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_scan_kernel(PackArgs a) {
 }
 
 // one workgroup per closed region: its reads in file order, each pair's slot and where its clipped bases / operations go
-// (the running sums of the host's staging: ((l_seq + 3) & ~3) + 4 bases and n_cigar operations per pair)
+// (the running sums of the host's staging: pa_pack::base_room(l_seq) bases and n_cigar operations per pair)
 __global__ __launch_bounds__(PACK_BLOCK) void pack_fill_kernel(PackArgs a) {
     __shared__ int w_cnt[16], w_ops[16];
     __shared__ long long w_bases[16];
@@ -615,7 +615,7 @@ __global__ __launch_bounds__(PACK_BLOCK) void pack_fill_kernel(PackArgs a) {
             if (in) {
                 const PackedRead rd = a.reads[ri];
                 ops = rd.n_cigar;
-                room = ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
+                room = pa_pack::base_room(rd.l_seq);
             }
         }
         const int cinc = wave_inclusive_sum(in ? 1 : 0), oinc = wave_inclusive_sum(ops);
@@ -1738,69 +1738,91 @@ void enumerate_region(const RegHost& rh, int region, int mid, const SiteRec* sit
     }
 }
 
+// ---- staging: what the three entry points (stage_batch, the packed forms, pa_enc::unpack_packed_regions) share ----------------
+const char* const BATCH_TOO_LARGE = "batch too large: more than 2^30 rows or 2^31 CIGAR operations / reads";
+
+// a staging call, accepted or refused, leaves no earlier batch staged: first thing in each of them
+void unstage(pa_encoder* e) {
+    if (e && e->variant) e->variant->staged = false;
+}
+
+struct RegionSums { int64_t rows = 0, ref = 0; int tiles = 0; };      // matrix rows, reference bytes and tiles of the regions so far
+
+// One region of a batch, from its bounds, its reference length and its parameters: checked (the bounds; the parameters, which
+// every region shares with q0, the batch's first), turned into its RegHost and its RegRec, and added to the sums.  seq_base /
+// op_base / read_base: where its reads' bases, operations and read records start.  q == null (the polish chain, which brings no
+// parameters and has matrices of its own): the record is zero but for L, and nothing else is written.
+int region_pass(const pa_pileup& p, const pa_summary_params* q, const pa_summary_params* q0, int64_t seq_base, int64_t op_base,
+                int64_t read_base, RegionSums& sums, RegHost* rh, RegRec& g) {
+    if (p.region_end < p.region_start || p.region_end - p.region_start > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
+    std::memset(&g, 0, sizeof(g));
+    g.L = (int32_t)(p.region_end - p.region_start + 1);
+    if (!q) return PA_OK;
+    if (q->feature_size < 26 || q->candidate_window_size < 2 || q->candidate_window_size > 254)
+        return pa::set_error(PA_ERR_INVALID, "feature_size must be >= 26 and 2 <= candidate_window_size <= 254");
+    if (q->feature_size != q0->feature_size || q->candidate_window_size != q0->candidate_window_size)
+        return pa::set_error(PA_ERR_INVALID, "one batch has one window size and one feature size");
+    if (p.n_reads < 0 || p.reference_len < 0) return pa::set_error(PA_ERR_INVALID, "negative count");
+    g.ref_off = sums.ref; g.row_base = sums.rows; g.seq_base = seq_base;
+    g.ref_len = (int32_t)std::min<int64_t>(p.reference_len, 0x7fffffff);
+    g.tile0 = sums.tiles; g.n_tiles = (g.L + 1 + TP - 1) / TP;
+    auto row_of = [&](int64_t pos) { return (int32_t)std::max<int64_t>(-2, std::min<int64_t>(pos - p.region_start, 0x7ffffff0)); };
+    g.cand_lo = row_of(q->candidate_region_start);
+    g.cand_hi = row_of(q->candidate_region_end);
+    // integer base quality Q passes `(double)Q >= min_snp_baseq` iff Q >= qmin
+    g.qmin = std::isnan(q->min_snp_baseq) ? 256 : (q->min_snp_baseq <= 0 ? 0 : (q->min_snp_baseq > 255 ? 256 : (int)std::ceil(q->min_snp_baseq)));
+    g.vote_base = (int32_t)op_base;
+    g.min_snp_q = q->min_snp_baseq; g.min_indel_q = q->min_indel_baseq; g.min_cov = q->min_coverage_threshold;
+    g.snp_thr = q->snp_freq_threshold; g.ins_thr = q->insert_freq_threshold; g.del_thr = q->delete_freq_threshold;
+    rh->p = p; rh->q = *q; rh->L = g.L;
+    rh->row_base = g.row_base; rh->seq_base = seq_base; rh->op_base = op_base; rh->read_base = read_base;
+    sums.rows += (g.L + 1 + 15) & ~(int64_t)15;      // 16 rows x 104 B = 13 x 128 B: every tile store starts on a line
+    sums.ref += p.reference_len;
+    sums.tiles += g.n_tiles;
+    if (sums.rows > ((int64_t)1 << 30)) return pa::set_error(PA_ERR_INVALID, BATCH_TOO_LARGE);
+    return PA_OK;
+}
+
+// the sums of a finished region pass and the window of its regions' (shared) parameters
+void set_geometry(pa_variant_batch& b, const RegionSums& sums, int32_t n_regions, const pa_summary_params* params) {
+    b.total_rows = sums.rows; b.total_ref = sums.ref; b.n_tiles = sums.tiles;
+    b.W = n_regions ? params[0].candidate_window_size + 1 : 33;
+    b.F = n_regions ? params[0].feature_size : 26;
+    b.mid = n_regions ? params[0].candidate_window_size / 2 : 16;
+}
+
+// records: a read enters a tile once per TP rows it spans, plus its first tile; reads with long deletions / skips span more
+// rows than they have bases, so the kernels count what they could not store and the run is repeated with room
+void set_record_caps(pa_variant_batch& b) {
+    b.rec_cap = (int)std::min<int64_t>(0x7ffffff0, b.total_bases / TP + 2 * b.total_reads + 1024);
+    b.ovf_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(1 << 16, b.total_bases / 64));
+    b.pool_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(4096, b.total_ops / 64));
+}
+
 int stage_batch(pa_encoder* e, int32_t n_regions, const pa_pileup* pileups, const pa_summary_params* params) {
+    unstage(e);
     if (!e || n_regions < 0 || (n_regions > 0 && (!pileups || !params))) return pa::set_error(PA_ERR_INVALID, "null argument");
     if (n_regions >= (1 << 22)) return pa::set_error(PA_ERR_INVALID, "more than 4194303 regions in one batch");
     ENC_HIP(hipSetDevice(e->device));
     if (!e->variant) e->variant = new pa_variant_batch();
     pa_variant_batch& b = *e->variant;
-    b.staged = false;
     b.ms[8] = b.ms[9] = 0;
     b.regs.assign((size_t)n_regions, RegHost());
-    b.total_bases = b.total_ops = b.total_reads = b.total_rows = b.total_ref = 0;
-    b.n_tiles = 0;
+    b.total_bases = b.total_ops = b.total_reads = 0;
+    RegionSums sums;
     std::vector<RegRec> regrecs((size_t)n_regions);
     for (int r = 0; r < n_regions; ++r) {
         const pa_pileup& p = pileups[r];
-        const pa_summary_params& q = params[r];
-        if (p.region_end < p.region_start || p.region_end - p.region_start > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
-        if (q.feature_size < 26 || q.candidate_window_size < 2 || q.candidate_window_size > 254)
-            return pa::set_error(PA_ERR_INVALID, "feature_size must be >= 26 and 2 <= candidate_window_size <= 254");
-        if (r > 0 && (q.feature_size != params[0].feature_size || q.candidate_window_size != params[0].candidate_window_size))
-            return pa::set_error(PA_ERR_INVALID, "one batch has one window size and one feature size");
-        if (p.n_reads < 0 || p.reference_len < 0) return pa::set_error(PA_ERR_INVALID, "negative count");
         if (p.reference_len > 0x7fffffff || (p.n_reads > 0 && p.seq_offset[p.n_reads] > 0xffffffffll))
             return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases and 2^31 reference bases");
-        RegHost& rh = b.regs[(size_t)r];
-        rh.p = p;
-        rh.q = q;
-        rh.L = (int)(p.region_end - p.region_start + 1);
-        rh.row_base = b.total_rows;
-        rh.seq_base = b.total_bases;
-        rh.op_base = b.total_ops;
-        rh.read_base = b.total_reads;
-        RegRec& g = regrecs[(size_t)r];
-        g.ref_off = b.total_ref;
-        g.row_base = rh.row_base;
-        g.seq_base = rh.seq_base;
-        g.ref_len = (int32_t)std::min<int64_t>(p.reference_len, 0x7fffffff);
-        g.L = rh.L;
-        g.tile0 = b.n_tiles;
-        g.n_tiles = (rh.L + 1 + TP - 1) / TP;
-        auto row_of = [&](int64_t pos) { return (int32_t)std::max<int64_t>(-2, std::min<int64_t>(pos - p.region_start, 0x7ffffff0)); };
-        g.cand_lo = row_of(q.candidate_region_start);
-        g.cand_hi = row_of(q.candidate_region_end);
-        // integer base quality Q passes `(double)Q >= min_snp_baseq` iff Q >= qmin
-        g.qmin = std::isnan(q.min_snp_baseq) ? 256 : (q.min_snp_baseq <= 0 ? 0 : (q.min_snp_baseq > 255 ? 256 : (int)std::ceil(q.min_snp_baseq)));
-        g.vote_base = (int32_t)rh.op_base;
-        g.min_snp_q = q.min_snp_baseq;
-        g.min_indel_q = q.min_indel_baseq;
-        g.snp_thr = q.snp_freq_threshold;
-        g.ins_thr = q.insert_freq_threshold;
-        g.del_thr = q.delete_freq_threshold;
-        g.min_cov = q.min_coverage_threshold;
-        b.total_rows += (rh.L + 1 + 15) & ~(int64_t)15;      // 16 rows x 104 B = 13 x 128 B: every tile store starts on a line
-        b.total_ref += p.reference_len;
+        const int rc = region_pass(p, &params[r], params, b.total_bases, b.total_ops, b.total_reads, sums, &b.regs[(size_t)r], regrecs[(size_t)r]);
+        if (rc != PA_OK) return rc;
         b.total_reads += p.n_reads;
         b.total_bases += p.n_reads > 0 ? p.seq_offset[p.n_reads] : 0;
         b.total_ops += p.n_reads > 0 ? p.cigar_offset[p.n_reads] : 0;
-        b.n_tiles += g.n_tiles;
-        if (b.total_rows > ((int64_t)1 << 30) || b.total_ops > 0x7ffffff0 || b.total_reads > 0x7ffffff0)
-            return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^30 rows or 2^31 CIGAR operations / reads");
+        if (b.total_ops > 0x7ffffff0 || b.total_reads > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, BATCH_TOO_LARGE);
     }
-    b.W = n_regions ? params[0].candidate_window_size + 1 : 33;
-    b.F = n_regions ? params[0].feature_size : 26;
-    b.mid = n_regions ? params[0].candidate_window_size / 2 : 16;
+    set_geometry(b, sums, n_regions, params);
 
     // read table
     std::vector<ReadRec> reads((size_t)b.total_reads);
@@ -1856,11 +1878,7 @@ int stage_batch(pa_encoder* e, int32_t n_regions, const pa_pileup* pileups, cons
         ENC_HIP(hipMemcpyAsync(b.d_tile_region.p, tile_region.data(), tile_region.size() * 4, hipMemcpyHostToDevice, st));
     }
     ENC_HIP(hipStreamSynchronize(st));            // the tables above are locals
-    // records: a read enters a tile once per TP rows it spans, plus its first tile; reads with long deletions / skips span
-    // more rows than they have bases, so the kernels count what they could not store and the run is repeated with room
-    b.rec_cap = (int)std::min<int64_t>(0x7ffffff0, b.total_bases / TP + 2 * b.total_reads + 1024);
-    b.ovf_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(1 << 16, b.total_bases / 64));
-    b.pool_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(4096, b.total_ops / 64));
+    set_record_caps(b);
     b.p_regions = b.d_regions.as<RegRec>();
     b.p_tile_region = b.d_tile_region.as<int32_t>();
     b.p_ref = b.d_ref.as<char>();
@@ -1870,7 +1888,6 @@ int stage_batch(pa_encoder* e, int32_t n_regions, const pa_pileup* pileups, cons
     b.staged = true;
     return PA_OK;
 }
-
 
 // a packed read's slice(s) lie inside the arena: `CIGAR words | bases | qualities` from data_off, or the words there and
 // `bases | qualities` from seq_off (pa_encoder_set_seq_offsets)
@@ -1889,146 +1906,97 @@ static std::vector<int64_t> take_seq_offsets(pa_encoder* e) {
 
 // Where a packed staging's page-locked block (and its copy on the device) keeps what it uploads:
 // [RegRec x R][region_start x R][tile_region x tiles][PackedRead x reads][PairRec x pairs][base offsets x reads][reference bytes]
-// -- the three tables are empty where pa_encoder_pack_records has built them on the device
+// -- the three tables are empty where pa_encoder_pack_records has built them on the device, tile_region and the reference for
+// the polish chain
 struct PackedBlock {
     size_t o_reg, o_start, o_tile, o_reads, o_pairs, o_soff, o_ref, bytes;
 };
+static PackedBlock lay_out_block(int32_t n_regions, int n_tiles, size_t reads_bytes, size_t pairs_bytes, size_t soff_bytes, int64_t ref_bytes) {
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    PackedBlock L{};
+    L.o_start = up16(L.o_reg + (size_t)n_regions * sizeof(RegRec));
+    L.o_tile = up16(L.o_start + (size_t)n_regions * 8);
+    L.o_reads = up16(L.o_tile + (size_t)n_tiles * 4);
+    L.o_pairs = up16(L.o_reads + reads_bytes);
+    L.o_soff = up16(L.o_pairs + pairs_bytes);
+    L.o_ref = up16(L.o_soff + soff_bytes);
+    L.bytes = up16(L.o_ref + (size_t)ref_bytes + 64);
+    return L;
+}
 // the tables unpack_clip_kernel reads, as device addresses (seq_off null: no read keeps its bases apart)
 struct PackedTables {
     const PackedRead* reads; const PairRec* pairs; const int64_t* seq_off;
 };
+static PackedTables block_tables(const pa_variant_batch& b, const PackedBlock& L, bool with_seq_off) {
+    const char* dm = b.d_meta.as<char>();
+    return PackedTables{reinterpret_cast<const PackedRead*>(dm + L.o_reads), reinterpret_cast<const PairRec*>(dm + L.o_pairs),
+                        with_seq_off ? reinterpret_cast<const int64_t*>(dm + L.o_soff) : nullptr};
+}
 
-// The first half of a packed staging, whoever built the tables: the regions checked, the block laid out with
-// `reads_bytes | pairs_bytes | soff_bytes` of room for tables that travel in it, and both of its copies allocated
-static int packed_begin(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
-                        const int32_t* region_pairs, const uint8_t* arena, int64_t arena_bytes, int32_t n_reads, size_t reads_bytes,
-                        size_t pairs_bytes, size_t soff_bytes, PackedBlock& L) {
-    if (n_regions >= (1 << 22)) return pa::set_error(PA_ERR_INVALID, "more than 4194303 regions in one batch");
-    ENC_HIP(hipSetDevice(e->device));
-    if (!e->variant) e->variant = new pa_variant_batch();
-    pa_variant_batch& b = *e->variant;
-    // arena == NULL: the bytes pa_encoder_inflate_bgzf left on the device
-    const bool resident = arena == nullptr && n_reads > 0;
-    if (resident && (b.resident_bytes <= 0 || arena_bytes > b.resident_bytes))
+// arena == NULL: the bytes pa_encoder_inflate_bgzf left on the device
+static bool arena_is_resident(const uint8_t* arena, int32_t n_reads) { return arena == nullptr && n_reads > 0; }
+static int check_resident(const pa_variant_batch& b, const uint8_t* arena, int32_t n_reads, int64_t arena_bytes) {
+    if (arena_is_resident(arena, n_reads) && (b.resident_bytes <= 0 || arena_bytes > b.resident_bytes))
         return pa::set_error(PA_ERR_INVALID, "no arena given and no inflated span of that size resident on the device");
-    b.staged = false;
-    b.ms[8] = b.ms[9] = 0;
-    b.regs.assign((size_t)n_regions, RegHost());
-    b.total_bases = b.total_ops = b.total_reads = b.total_rows = b.total_ref = 0;
-    b.n_tiles = 0;
-    const int64_t n_pairs = n_regions ? region_pairs[n_regions] : 0;
-    if (n_pairs < 0 || (n_regions && region_pairs[0] != 0)) return pa::set_error(PA_ERR_INVALID, "region_pairs must start at 0 and ascend");
-    for (int r = 0; r < n_regions; ++r) {
-        const pa_packed_region& p = regions[r];
-        const pa_summary_params& q = params[r];
-        if (p.region_end < p.region_start || p.region_end - p.region_start > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
-        if (q.feature_size < 26 || q.candidate_window_size < 2 || q.candidate_window_size > 254)
-            return pa::set_error(PA_ERR_INVALID, "feature_size must be >= 26 and 2 <= candidate_window_size <= 254");
-        if (r > 0 && (q.feature_size != params[0].feature_size || q.candidate_window_size != params[0].candidate_window_size))
-            return pa::set_error(PA_ERR_INVALID, "one batch has one window size and one feature size");
-        if (p.reference_len < 0 || p.reference_len > 0x7fffffff || region_pairs[r + 1] < region_pairs[r])
-            return pa::set_error(PA_ERR_INVALID, "negative count");
-        b.total_ref += p.reference_len;
-        b.total_rows += ((p.region_end - p.region_start + 1) + 1 + 15) & ~(int64_t)15;
-        b.n_tiles += (int)((p.region_end - p.region_start + 1 + 1 + TP - 1) / TP);
-        if (b.total_rows > ((int64_t)1 << 30)) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^30 rows");
-    }
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    L.o_reg = 0;
-    L.o_start = up16(L.o_reg + (size_t)n_regions * sizeof(RegRec));
-    L.o_tile = up16(L.o_start + (size_t)n_regions * 8);
-    L.o_reads = up16(L.o_tile + (size_t)b.n_tiles * 4);
-    L.o_pairs = up16(L.o_reads + reads_bytes);
-    L.o_soff = up16(L.o_pairs + pairs_bytes);
-    L.o_ref = up16(L.o_soff + soff_bytes);
-    L.bytes = up16(L.o_ref + (size_t)b.total_ref + 64);
-    if (!b.h_meta.ensure(L.bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
-    ENC_ALLOC(b.d_meta, L.bytes);
     return PA_OK;
 }
 
-// The second half, shared by both forms: the region records from the offsets summed per region (`seq_base`, `op_base`:
-// [n_regions + 1], every read already checked against the arena by whoever summed them), the block uploaded with one copy,
-// the arena with another, then unpack_clip_kernel over `t` -- nothing here waits for the device.
-static int packed_finish(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
-                         const int32_t* region_pairs, const uint8_t* arena, int64_t arena_bytes, int32_t n_reads, const PackedBlock& L,
-                         const int64_t* seq_base, const int32_t* op_base, const PackedTables& t) {
-    pa_variant_batch& b = *e->variant;
-    const bool resident = arena == nullptr && n_reads > 0;
-    const int64_t n_pairs = n_regions ? region_pairs[n_regions] : 0;
-    char* hm = b.h_meta.as<char>();
-    RegRec* regrecs = reinterpret_cast<RegRec*>(hm + L.o_reg);
-    int64_t* rstart = reinterpret_cast<int64_t*>(hm + L.o_start);
-    int32_t* tile_region = reinterpret_cast<int32_t*>(hm + L.o_tile);
-    b.total_rows = 0;
-    b.total_ref = 0;
-    b.n_tiles = 0;
+// The (read, region) pairs of a packed batch, region by region: every pair's read checked (its index, its slices against the
+// arena) and given its place -- the PairRec says where its clipped bases and operations go -- with the running sums per region
+// left in seq_base / op_base [n_regions + 1].  Room: for the whole read (capped_by null: what is kept is known on the device
+// only), or for what region r of capped_by[r].L rows can keep.  The clipped stretch of a read holds its aligned bases inside
+// the region and the inserts between them: room for the whole read would be 10-50 kb per pair of a 1 kb region, so such a pair
+// gets min(l_seq, 2 L + 64) bases and min(n_cigar, L + that + 2) operations (kept M / D / N operations each cover a row of the
+// region, kept I / S ones a kept base); a pair that keeps more is reported as unsupported (h_live[n_regions + 1]) and the
+// caller takes the host-clipped form.
+static int walk_pairs(int32_t n_regions, const int32_t* region_pairs, const int32_t* pair_read, const pa_packed_read* reads, int32_t n_reads,
+                      const std::vector<int64_t>& soff, int64_t arena_bytes, const RegRec* capped_by, PairRec* pairs, int64_t* seq_base,
+                      int32_t* op_base) {
+    int64_t bases = 0, ops = 0;
+    seq_base[0] = 0;
+    op_base[0] = 0;
     for (int r = 0; r < n_regions; ++r) {
-        const pa_packed_region& p = regions[r];
-        const pa_summary_params& q = params[r];
-        RegHost& rh = b.regs[(size_t)r];
-        rh.p = pa_pileup{};
-        rh.p.region_start = p.region_start;
-        rh.p.region_end = p.region_end;
-        rh.p.reference = p.reference;
-        rh.p.reference_len = p.reference_len;
-        rh.p.n_reads = region_pairs[r + 1] - region_pairs[r];
-        rh.q = q;
-        rh.L = (int)(p.region_end - p.region_start + 1);
-        rh.row_base = b.total_rows;
-        rh.seq_base = seq_base[r];
-        rh.op_base = op_base[r];
-        rh.read_base = region_pairs[r];
-        RegRec& g = regrecs[r];
-        g.ref_off = b.total_ref;
-        g.row_base = rh.row_base;
-        g.seq_base = rh.seq_base;
-        g.ref_len = (int32_t)p.reference_len;
-        g.L = rh.L;
-        g.tile0 = b.n_tiles;
-        g.n_tiles = (rh.L + 1 + TP - 1) / TP;
-        auto row_of = [&](int64_t pos) { return (int32_t)std::max<int64_t>(-2, std::min<int64_t>(pos - p.region_start, 0x7ffffff0)); };
-        g.cand_lo = row_of(q.candidate_region_start);
-        g.cand_hi = row_of(q.candidate_region_end);
-        g.qmin = std::isnan(q.min_snp_baseq) ? 256 : (q.min_snp_baseq <= 0 ? 0 : (q.min_snp_baseq > 255 ? 256 : (int)std::ceil(q.min_snp_baseq)));
-        g.vote_base = (int32_t)rh.op_base;
-        g.min_snp_q = q.min_snp_baseq;
-        g.min_indel_q = q.min_indel_baseq;
-        g.snp_thr = q.snp_freq_threshold;
-        g.ins_thr = q.insert_freq_threshold;
-        g.del_thr = q.delete_freq_threshold;
-        g.min_cov = q.min_coverage_threshold;
-        rstart[r] = p.region_start;
-        for (int t2 = 0; t2 < g.n_tiles; ++t2) tile_region[g.tile0 + t2] = r;
-        if (p.reference_len > 0) std::memcpy(hm + L.o_ref + b.total_ref, p.reference, (size_t)p.reference_len);
-        if (seq_base[r + 1] < seq_base[r] || op_base[r + 1] < op_base[r] || op_base[r + 1] > 0x7ffffff0)
-            return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
-        if (seq_base[r + 1] - seq_base[r] > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
-        b.total_rows += (rh.L + 1 + 15) & ~(int64_t)15;
-        b.total_ref += p.reference_len;
-        b.n_tiles += g.n_tiles;
+        for (int32_t k = region_pairs[r]; k < region_pairs[r + 1]; ++k) {
+            const int32_t ri = pair_read[k];
+            if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
+            const pa_packed_read& rd = reads[ri];
+            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
+                return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
+            const int64_t cap = capped_by ? std::min<int64_t>(rd.l_seq, 2ll * capped_by[r].L + 64) : 0;
+            pairs[k] = PairRec{bases, ri, r, (int32_t)ops, (int32_t)cap};
+            bases += pa_pack::base_room(capped_by ? cap : rd.l_seq);
+            ops += capped_by ? std::min<int64_t>(rd.n_cigar, (int64_t)capped_by[r].L + cap + 2) : rd.n_cigar;
+            if (ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, BATCH_TOO_LARGE);
+        }
+        seq_base[r + 1] = bases;
+        op_base[r + 1] = (int32_t)ops;
     }
-    b.total_bases = seq_base[n_regions];
-    b.total_ops = op_base[n_regions];
-    b.total_reads = n_pairs;
-    b.W = n_regions ? params[0].candidate_window_size + 1 : 33;
-    b.F = n_regions ? params[0].feature_size : 26;
-    b.mid = n_regions ? params[0].candidate_window_size / 2 : 16;
+    return PA_OK;
+}
 
+// The block and the arena uploaded (one copy each; a resident arena stays where it is) and unpack_clip_kernel run over the
+// tables `t`: the pairs' clipped reads in d_reads / d_seq / d_qual / d_cig_* (total_bases, total_ops: the room the pairs were
+// given; extra_ops: more operation slots behind them, the polish chain's), what the kernel reports on its way to h_live.
+// Nothing here waits for the device.  ev[6..8] bracket the uploads and the kernel for run_staged's ms[8] / ms[9]; the polish
+// chain records them too, where nothing reads them (its call leaves no staged batch).
+static int submit_unpack(pa_encoder* e, int32_t n_regions, int64_t n_pairs, const uint8_t* arena, int64_t arena_bytes, int32_t n_reads,
+                         const PackedBlock& L, const PackedTables& t, int64_t total_bases, int64_t total_ops, int64_t extra_ops) {
+    pa_variant_batch& b = *e->variant;
+    const bool resident = arena_is_resident(arena, n_reads);
     hipStream_t st = e->stream;
     if (!resident) {
         ENC_ALLOC(b.d_arena, (size_t)arena_bytes + 256);
         b.resident_bytes = 0;
     }
     ENC_ALLOC(b.d_live, ((size_t)n_regions + 2) * 4);
-    ENC_ALLOC(b.d_seq, (size_t)b.total_bases + 64);
-    ENC_ALLOC(b.d_qual, (size_t)b.total_bases + 64);
-    ENC_ALLOC(b.d_cig_op, (size_t)b.total_ops * 4 + 1024);
-    ENC_ALLOC(b.d_cig_len, (size_t)b.total_ops * 4 + 1024);
+    ENC_ALLOC(b.d_seq, (size_t)total_bases + 64);
+    ENC_ALLOC(b.d_qual, (size_t)total_bases + 64);
+    ENC_ALLOC(b.d_cig_op, (size_t)(total_ops + extra_ops) * 4 + 1024);
+    ENC_ALLOC(b.d_cig_len, (size_t)(total_ops + extra_ops) * 4 + 1024);
     ENC_ALLOC(b.d_reads, (size_t)n_pairs * sizeof(ReadRec) + 64);
     ENC_HIP(hipEventRecord(e->ev[6], st));
     if (arena_bytes > 0 && !resident) ENC_HIP(hipMemcpyAsync(b.d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
-    ENC_HIP(hipMemcpyAsync(b.d_meta.p, hm, L.bytes, hipMemcpyHostToDevice, st));
+    ENC_HIP(hipMemcpyAsync(b.d_meta.p, b.h_meta.p, L.bytes, hipMemcpyHostToDevice, st));
     ENC_HIP(hipMemsetAsync(b.d_live.p, 0, ((size_t)n_regions + 2) * 4, st));
     ENC_HIP(hipEventRecord(e->ev[7], st));
     const char* dm = b.d_meta.as<char>();
@@ -2037,281 +2005,272 @@ static int packed_finish(pa_encoder* e, int32_t n_regions, const pa_packed_regio
     b.p_ref = dm + L.o_ref;
     if (n_pairs > 0) {
         UnpackArgs ua;
-        ua.pairs = t.pairs;
-        ua.n_pairs = (int)n_pairs;
-        ua.preads = t.reads;
-        ua.regions = b.p_regions;
-        ua.region_start = reinterpret_cast<const int64_t*>(dm + L.o_start);
+        ua.pairs = t.pairs; ua.n_pairs = (int)n_pairs; ua.preads = t.reads; ua.seq_off = t.seq_off;
+        ua.regions = b.p_regions; ua.region_start = reinterpret_cast<const int64_t*>(dm + L.o_start); ua.n_regions = n_regions;
         ua.arena = b.d_arena.as<uint8_t>();
-        ua.seq_off = t.seq_off;
-        ua.reads = b.d_reads.as<ReadRec>();
-        ua.cigar_op = b.d_cig_op.as<int32_t>();
-        ua.cigar_len = b.d_cig_len.as<int32_t>();
-        ua.seq = b.d_seq.as<char>();
-        ua.qual = b.d_qual.as<uint8_t>();
-        ua.live = b.d_live.as<int>();
-        ua.n_regions = n_regions;
+        ua.reads = b.d_reads.as<ReadRec>(); ua.cigar_op = b.d_cig_op.as<int32_t>(); ua.cigar_len = b.d_cig_len.as<int32_t>();
+        ua.seq = b.d_seq.as<char>(); ua.qual = b.d_qual.as<uint8_t>(); ua.live = b.d_live.as<int>();
         hipLaunchKernelGGL(unpack_clip_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, st, ua);
         ENC_HIP(hipGetLastError());
     }
     ENC_HIP(hipEventRecord(e->ev[8], st));
     ENC_HIP(hipMemcpyAsync(b.h_live.p, b.d_live.p, ((size_t)n_regions + 2) * 4, hipMemcpyDeviceToHost, st));
-    b.rec_cap = (int)std::min<int64_t>(0x7ffffff0, b.total_bases / TP + 2 * b.total_reads + 1024);
-    b.ovf_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(1 << 16, b.total_bases / 64));
-    b.pool_cap = (int)std::min<int64_t>(0x7ffffff0, std::max<int64_t>(4096, b.total_ops / 64));
+    b.last_pairs = n_pairs;
+    return PA_OK;
+}
+
+// A packed staging, whoever built the tables.  Host tables (reads, pair_read; soff: the base offsets set for the call) travel
+// in the block, and every pair is walked here.  device_tables: those pa_encoder_pack_records left on the device -- it has
+// placed the pairs, checked every read against the span and summed the same offsets (b.pk), so the block carries the regions
+// and the reference only.  One pass over the regions, the block laid out from its sums, the pairs placed, the region records
+// put into the block with where their reads' bases and operations start, then the submission: nothing here waits for the device.
+static int stage_packed_tables(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
+                               const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads,
+                               const int32_t* pair_read, const int32_t* region_pairs, const std::vector<int64_t>& soff,
+                               bool device_tables) {
+    if (n_regions >= (1 << 22)) return pa::set_error(PA_ERR_INVALID, "more than 4194303 regions in one batch");
+    ENC_HIP(hipSetDevice(e->device));
+    if (!e->variant) e->variant = new pa_variant_batch();
+    pa_variant_batch& b = *e->variant;
+    int rc = check_resident(b, arena, n_reads, arena_bytes);
+    if (rc != PA_OK) return rc;
+    b.ms[8] = b.ms[9] = 0;
+    b.regs.assign((size_t)n_regions, RegHost());
+    b.total_bases = b.total_ops = b.total_reads = 0;
+    const int64_t n_pairs = n_regions ? region_pairs[n_regions] : 0;
+    if (n_pairs < 0 || (n_regions && region_pairs[0] != 0)) return pa::set_error(PA_ERR_INVALID, "region_pairs must start at 0 and ascend");
+    RegionSums sums;
+    std::vector<RegRec> regrecs((size_t)n_regions);      // (kept here until the block exists: its layout needs the sums)
+    for (int r = 0; r < n_regions; ++r) {
+        if (regions[r].reference_len > 0x7fffffff) return pa::set_error(PA_ERR_INVALID, "negative count");      // (this form's words for it)
+        pa_pileup p{};
+        p.region_start = regions[r].region_start; p.region_end = regions[r].region_end;
+        p.reference = regions[r].reference; p.reference_len = regions[r].reference_len;
+        p.n_reads = region_pairs[r + 1] < region_pairs[r] ? -1 : region_pairs[r + 1] - region_pairs[r];      // (descending: a negative count)
+        rc = region_pass(p, &params[r], params, 0, 0, region_pairs[r], sums, &b.regs[(size_t)r], regrecs[(size_t)r]);
+        if (rc != PA_OK) return rc;
+    }
+    set_geometry(b, sums, n_regions, params);
+    const PackedBlock L = lay_out_block(n_regions, b.n_tiles, device_tables ? 0 : (size_t)n_reads * sizeof(PackedRead),
+                                        device_tables ? 0 : (size_t)n_pairs * sizeof(PairRec), soff.size() * 8, b.total_ref);
+    if (!b.h_meta.ensure(L.bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_ALLOC(b.d_meta, L.bytes);
+    char* hm = b.h_meta.as<char>();
+    std::vector<int64_t> walked_bases;
+    std::vector<int32_t> walked_ops;
+    const int64_t* seq_base = b.pk.seq_base.data();
+    const int32_t* op_base = b.pk.op_base.data();
+    PackedTables t{b.d_pk_reads.as<PackedRead>(), b.d_pk_pairs.as<PairRec>(), b.pk.sum.n_split > 0 ? b.d_pk_soff.as<int64_t>() : nullptr};
+    if (!device_tables) {
+        if (n_reads) std::memcpy(hm + L.o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
+        if (!soff.empty()) std::memcpy(hm + L.o_soff, soff.data(), soff.size() * 8);
+        walked_bases.resize((size_t)n_regions + 1);
+        walked_ops.resize((size_t)n_regions + 1);
+        rc = walk_pairs(n_regions, region_pairs, pair_read, reads, n_reads, soff, arena_bytes, nullptr, reinterpret_cast<PairRec*>(hm + L.o_pairs),
+                        walked_bases.data(), walked_ops.data());
+        if (rc != PA_OK) return rc;
+        seq_base = walked_bases.data();
+        op_base = walked_ops.data();
+        t = block_tables(b, L, !soff.empty());
+    }
+    int64_t* rstart = reinterpret_cast<int64_t*>(hm + L.o_start);
+    int32_t* tile_region = reinterpret_cast<int32_t*>(hm + L.o_tile);
+    for (int r = 0; r < n_regions; ++r) {
+        if (seq_base[r + 1] < seq_base[r] || op_base[r + 1] < op_base[r] || op_base[r + 1] > 0x7ffffff0)
+            return pa::set_error(PA_ERR_INVALID, BATCH_TOO_LARGE);
+        if (seq_base[r + 1] - seq_base[r] > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
+        RegHost& rh = b.regs[(size_t)r];
+        RegRec& g = regrecs[(size_t)r];
+        g.seq_base = rh.seq_base = seq_base[r];
+        g.vote_base = op_base[r];
+        rh.op_base = op_base[r];
+        rstart[r] = rh.p.region_start;
+        for (int t2 = 0; t2 < g.n_tiles; ++t2) tile_region[g.tile0 + t2] = r;
+        if (rh.p.reference_len > 0) std::memcpy(hm + L.o_ref + g.ref_off, rh.p.reference, (size_t)rh.p.reference_len);
+    }
+    if (n_regions) std::memcpy(hm + L.o_reg, regrecs.data(), (size_t)n_regions * sizeof(RegRec));
+    b.total_bases = seq_base[n_regions];
+    b.total_ops = op_base[n_regions];
+    b.total_reads = n_pairs;
+    rc = submit_unpack(e, n_regions, n_pairs, arena, arena_bytes, n_reads, L, t, b.total_bases, b.total_ops, 0);
+    if (rc != PA_OK) return rc;
+    set_record_caps(b);
     b.live.assign((size_t)n_regions, 0);
     b.packed = true;
     b.sampled = false;
-    b.last_pairs = n_pairs;
     b.staged = true;
     return PA_OK;
 }
 
-// The packed form of a batch (include/pepper_amd_encoder.h) from host tables: they travel in the block, and every pair is
-// walked here -- its read checked against the arena, its clipped bases and operations given room for the whole read (what is
-// kept is known on the device only)
+// The packed form of a batch (include/pepper_amd_encoder.h) from host tables
 int stage_packed(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params,
                  const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads, const int32_t* pair_read,
                  const int32_t* region_pairs) {
     const std::vector<int64_t> soff = take_seq_offsets(e);
+    unstage(e);
     if (!e || n_regions < 0 || (n_regions > 0 && (!regions || !params || !region_pairs)) || arena_bytes < 0 || n_reads < 0 ||
         (n_reads > 0 && (!reads || !pair_read)))
         return pa::set_error(PA_ERR_INVALID, "null argument");
     if (!soff.empty() && (int64_t)soff.size() != n_reads)
         return pa::set_error(PA_ERR_INVALID, "the base offsets set for this call are not one per packed read");
-    const int64_t n_pairs = n_regions ? std::max<int64_t>(0, region_pairs[n_regions]) : 0;      // (packed_begin refuses a negative one)
-    PackedBlock L;
-    const int rc = packed_begin(e, n_regions, regions, params, region_pairs, arena, arena_bytes, n_reads, (size_t)n_reads * sizeof(PackedRead),
-                                (size_t)n_pairs * sizeof(PairRec), soff.size() * 8, L);
-    if (rc != PA_OK) return rc;
-    pa_variant_batch& b = *e->variant;
-    char* hm = b.h_meta.as<char>();
-    PairRec* pairs = reinterpret_cast<PairRec*>(hm + L.o_pairs);
-    if (n_reads) std::memcpy(hm + L.o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
-    if (!soff.empty()) std::memcpy(hm + L.o_soff, soff.data(), soff.size() * 8);
-    std::vector<int64_t> seq_base((size_t)n_regions + 1, 0);
-    std::vector<int32_t> op_base((size_t)n_regions + 1, 0);
-    int64_t bases = 0, ops = 0;
-    for (int r = 0; r < n_regions; ++r) {
-        for (int32_t k = region_pairs[r]; k < region_pairs[r + 1]; ++k) {
-            const int32_t ri = pair_read[k];
-            if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
-            const pa_packed_read& rd = reads[ri];
-            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
-                return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
-            pairs[k] = PairRec{bases, ri, r, (int32_t)ops, 0};
-            bases += ((int64_t)rd.l_seq + 3 & ~(int64_t)3) + 4;
-            ops += rd.n_cigar;
-            if (ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
-        }
-        if (bases - seq_base[(size_t)r] > 0xffffff00ll) return pa::set_error(PA_ERR_INVALID, "a region is limited to 2^32 read bases");
-        seq_base[(size_t)r + 1] = bases;
-        op_base[(size_t)r + 1] = (int32_t)ops;
-    }
-    const char* dm = b.d_meta.as<char>();
-    const PackedTables t{reinterpret_cast<const PackedRead*>(dm + L.o_reads), reinterpret_cast<const PairRec*>(dm + L.o_pairs),
-                         soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + L.o_soff)};
-    return packed_finish(e, n_regions, regions, params, region_pairs, arena, arena_bytes, n_reads, L, seq_base.data(), op_base.data(), t);
+    return stage_packed_tables(e, n_regions, regions, params, arena, arena_bytes, reads, n_reads, pair_read, region_pairs, soff, false);
 }
 
-// The same batch over the tables pa_encoder_pack_records left on the device: it has placed the pairs, checked every read
-// against the span and summed the same offsets, so the block carries the regions and the reference only
+// The same batch over the tables pa_encoder_pack_records left on the device
 static int stage_packed_device(pa_encoder* e, int32_t n_regions, const pa_packed_region* regions, const pa_summary_params* params) {
     take_seq_offsets(e);                      // (a table set for this call has nothing to say about the device's reads)
+    unstage(e);
     pa_variant_batch& b = *e->variant;
-    const int32_t n_reads = b.pk.sum.n_reads;
-    const int32_t* region_pairs = b.pk.region_pairs.data();
     if (n_regions < 0 || (n_regions > 0 && (!regions || !params))) return pa::set_error(PA_ERR_INVALID, "null argument");
     // (no read: nothing is dereferenced, and the staging takes no arena -- as the host-table form is called for such a run)
-    const int64_t arena_bytes = n_reads > 0 ? b.resident_bytes : 0;
-    PackedBlock L;
-    const int rc = packed_begin(e, n_regions, regions, params, region_pairs, nullptr, arena_bytes, n_reads, 0, 0, 0, L);
-    if (rc != PA_OK) return rc;
-    const PackedTables t{b.d_pk_reads.as<PackedRead>(), b.d_pk_pairs.as<PairRec>(), b.pk.sum.n_split > 0 ? b.d_pk_soff.as<int64_t>() : nullptr};
-    return packed_finish(e, n_regions, regions, params, region_pairs, nullptr, arena_bytes, n_reads, L, b.pk.seq_base.data(),
-                         b.pk.op_base.data(), t);
+    const int32_t n_reads = b.pk.sum.n_reads;
+    return stage_packed_tables(e, n_regions, regions, params, nullptr, n_reads > 0 ? b.resident_bytes : 0, nullptr, n_reads, nullptr,
+                               b.pk.region_pairs.data(), std::vector<int64_t>(), true);
 }
 
-int run_staged(pa_encoder* e, int64_t* n_candidates) {
-    if (!e || !e->variant || !e->variant->staged) return pa::set_error(PA_ERR_INVALID, "no staged batch");
-    ENC_HIP(hipSetDevice(e->device));
+// ---- a run of the staged batch, in steps (run_staged below calls them in this order) ----------------------------------------
+// what the steps share: the sizes the staged batch fixes, the slices of d_zero and the page-locked copy of the counters
+struct RunShape {
+    int n_regions = 0, vote_cap = 0;
+    size_t n_zero = 0, n_czero = 0, n_cscan = 0;
+    bool dev = false;                                           // candidates enumerated by the kernels (the handle's switch)
+    int *counters = nullptr, *region_counts = nullptr, *tile_count = nullptr, *tile_fill = nullptr;
+    int* host_counters = nullptr;                               // [CT_N] | per-region counts | records
+};
+
+// the workspaces sized by the batch (those sized by the record caps belong to the attempts); with the switch on, the rule of
+// every region and the tables of the candidate kernels too
+int size_workspaces(pa_encoder* e, RunShape& w) {
     pa_variant_batch& b = *e->variant;
-    hipStream_t st = e->stream;
-    const int n_regions = (int)b.regs.size();
-    b.n = 0;
-    b.region_n.assign((size_t)n_regions, 0);
-    b.positions.clear();
-    b.depths.clear();
-    b.freqs.clear();
-    b.names.clear();
-    for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
-    if (n_regions == 0) return PA_OK;
-    const auto t_begin = std::chrono::steady_clock::now();
-    const int vote_cap = (int)std::min<int64_t>(b.total_ops + 1, 0x7ffffff0);
-    const size_t n_zero = (size_t)CT_N + 2 * (size_t)n_regions + 2 * (size_t)b.n_tiles;
-    ENC_ALLOC(b.d_zero, n_zero * 4);
+    const int n_regions = w.n_regions = (int)b.regs.size();
+    w.vote_cap = (int)std::min<int64_t>(b.total_ops + 1, 0x7ffffff0);
+    w.n_zero = (size_t)CT_N + 2 * (size_t)n_regions + 2 * (size_t)b.n_tiles;
+    w.n_czero = (size_t)CI_N + 2 * (size_t)b.n_tiles;
+    w.n_cscan = 2 * ((size_t)b.n_tiles + 1);
+    w.dev = b.dev_cands;
+    ENC_ALLOC(b.d_zero, w.n_zero * 4);
     ENC_ALLOC(b.d_tile_off, ((size_t)b.n_tiles + 1) * 4);
     ENC_ALLOC(b.d_mat, (size_t)b.total_rows * MATF * 4 + 64);
     ENC_ALLOC(b.d_pass, (size_t)b.total_rows + 64);
     ENC_ALLOC(b.d_sites, (size_t)b.total_rows * sizeof(SiteRec));
-    ENC_ALLOC(b.d_votes, (size_t)vote_cap * sizeof(Vote));
-    ENC_ALLOC(b.d_votes_out, (size_t)vote_cap * sizeof(Vote));
+    ENC_ALLOC(b.d_votes, (size_t)w.vote_cap * sizeof(Vote));
+    ENC_ALLOC(b.d_votes_out, (size_t)w.vote_cap * sizeof(Vote));
     ENC_ALLOC(b.d_sites_dense, (size_t)b.total_rows * sizeof(SiteRec));
-    ENC_ALLOC(b.d_votes_dense, (size_t)vote_cap * sizeof(Vote));
+    ENC_ALLOC(b.d_votes_dense, (size_t)w.vote_cap * sizeof(Vote));
     if (!b.h_counts.ensure(((size_t)CT_N + 2 * (size_t)n_regions + 1) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
-    int* host_counters = b.h_counts.as<int>();                  // [CT_N] | per-region counts | records
-    const int* host_rc = host_counters + CT_N;
-    if (b.packed && !b.sampled) {     // deep intervals sampled down before anything reads the pairs (once per staged batch)
-        std::vector<int32_t> region_pairs((size_t)n_regions + 1);
-        for (int r = 0; r < n_regions; ++r) region_pairs[(size_t)r] = (int32_t)b.regs[(size_t)r].read_base;
-        region_pairs[(size_t)n_regions] = (int32_t)b.total_reads;
-        const int rc = pa_enc::sample_pairs(e, n_regions, region_pairs.data(), b.d_reads.as<ReadRec>(), b.d_live.as<int>(), b.h_live.as<int>());
-        if (rc != PA_OK) return rc;
-        b.sampled = true;
-    }
-    const bool dev = b.dev_cands;
-    b.dev_results = false;
-    b.ms[12] = 0;
-    const size_t n_czero = (size_t)CI_N + 2 * (size_t)b.n_tiles, n_cscan = 2 * ((size_t)b.n_tiles + 1);
-    if (dev) {                        // the rule of every region, and the tables sized by the batch
-        if (!b.h_rules.ensure((size_t)n_regions * sizeof(pa_cand::Rule)) || !b.h_cscan.ensure((n_cscan + CI_N) * 4))
-            return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
-        for (int r = 0; r < n_regions; ++r) b.h_rules.as<pa_cand::Rule>()[r] = region_rule(b.regs[(size_t)r]);
-        ENC_ALLOC(b.d_rules, (size_t)n_regions * sizeof(pa_cand::Rule));
-        ENC_ALLOC(b.d_row_slot, (size_t)b.total_rows * 4 + 64);
-        ENC_ALLOC(b.d_aux, (size_t)b.total_rows * sizeof(SiteAux) + 64);
-        ENC_ALLOC(b.d_large, (size_t)b.total_rows * 4 + 64);         // (a row holds at most one site)
-        ENC_ALLOC(b.d_grouped, (size_t)vote_cap * sizeof(Vote));
-        ENC_ALLOC(b.d_czero, n_czero * 4);
-        ENC_ALLOC(b.d_cscan, n_cscan * 4);
-        ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
-    }
-    bool on_device = false;           // this call's candidates were enumerated by the kernels
-    for (int attempt = 0;; ++attempt) {
-        ENC_ALLOC(b.d_sorted, (size_t)b.rec_cap * sizeof(TileRec));
-        ENC_ALLOC(b.d_ovf, (size_t)b.ovf_cap * sizeof(int4));
-        ENC_ALLOC(b.d_pool, (size_t)b.pool_cap * POOL_SLOT);
-        int* counters = b.d_zero.as<int>();
-        int* region_counts = counters + CT_N;
-        int* tile_count = region_counts + 2 * n_regions;
-        int* tile_fill = tile_count + b.n_tiles;
-        ENC_HIP(hipMemsetAsync(b.d_zero.p, 0, n_zero * 4, st));
-        ENC_HIP(hipEventRecord(e->ev[0], st));
-        const dim3 seg_grid((unsigned)((b.total_reads + 3) / 4));
-        if (b.total_reads > 0)
-            hipLaunchKernelGGL(segment_reads_kernel<false>, seg_grid, dim3(256), 0, st, b.d_reads.as<ReadRec>(), (int)b.total_reads,
-                               b.p_regions, b.d_cig_op.as<int32_t>(), b.d_cig_len.as<int32_t>(), tile_count,
-                               (const int*)nullptr, (int*)nullptr, (TileRec*)nullptr, 0);
-        hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, tile_count, b.n_tiles, b.d_tile_off.as<int>());
-        if (b.total_reads > 0)
-            hipLaunchKernelGGL(segment_reads_kernel<true>, seg_grid, dim3(256), 0, st, b.d_reads.as<ReadRec>(), (int)b.total_reads,
-                               b.p_regions, b.d_cig_op.as<int32_t>(), b.d_cig_len.as<int32_t>(), tile_count,
-                               b.d_tile_off.as<int>(), tile_fill, b.d_sorted.as<TileRec>(), b.rec_cap);
-        ENC_HIP(hipEventRecord(e->ev[1], st));
-        TileArgs ta;
-        ta.reads = b.d_reads.as<ReadRec>();
-        ta.regions = b.p_regions;
-        ta.tile_region = b.p_tile_region;
-        ta.cigar_op = b.d_cig_op.as<int32_t>();
-        ta.cigar_len = b.d_cig_len.as<int32_t>();
-        ta.seq = b.d_seq.as<char>();
-        ta.qual = b.d_qual.as<uint8_t>();
-        ta.ref = b.p_ref;
-        ta.recs = b.d_sorted.as<TileRec>();
-        ta.tile_off = b.d_tile_off.as<int>();
-        ta.rec_cap = b.rec_cap;
-        ta.mat = b.d_mat.as<int>();
-        ta.pass = b.d_pass.as<uint8_t>();
-        ta.sites = b.d_sites.as<SiteRec>();
-        ta.votes = b.d_votes.as<Vote>();
-        ta.votes_out = b.d_votes_out.as<Vote>();
-        ta.vote_cap = vote_cap;
-        ta.ovf = b.d_ovf.as<int4>();
-        ta.ovf_cap = b.ovf_cap;
-        ta.counters = counters;
-        ta.region_counts = region_counts;
-        static const int tile_debug = [] { const char* e = getenv("PA_TILE_DEBUG"); return e ? atoi(e) : 0; }();
-        ta.debug = tile_debug;
-        hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
-        ENC_HIP(hipEventRecord(e->ev[2], st));
-        hipLaunchKernelGGL(compact_votes_kernel, dim3((unsigned)std::min(2048, (vote_cap + 255) / 256)), dim3(256), 0, st, b.d_votes.as<Vote>(), counters,
-                           vote_cap, b.p_regions, b.d_pass.as<uint8_t>(), b.d_seq.as<char>(), b.p_ref, region_counts,
-                           b.d_votes_out.as<Vote>());
-        hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)n_regions), dim3(256), 0, st, b.p_regions, region_counts,
-                           b.d_sites.as<SiteRec>(), b.d_votes_out.as<Vote>(), b.d_sites_dense.as<SiteRec>(), b.d_votes_dense.as<Vote>(),
-                           b.d_seq.as<char>(), b.d_pool.as<char>(), b.pool_cap, counters);
-        ENC_HIP(hipEventRecord(e->ev[3], st));
-        ENC_HIP(hipGetLastError());
-        if (dev) {                    // candidates and windows behind the counts, in the same submission
-            ENC_ALLOC(b.d_rare_next, (size_t)b.ovf_cap * 4);
-            ENC_ALLOC(b.d_cands, (size_t)b.cand_cap * sizeof(CandDesc));
-            ENC_ALLOC(b.d_pos, (size_t)b.cand_cap * 8);
-            ENC_ALLOC(b.d_depths, (size_t)b.cand_cap * 4);
-            ENC_ALLOC(b.d_freqs, (size_t)b.cand_cap * 4);
-            ENC_ALLOC(b.d_names, (size_t)b.cand_cap * 72);           // a name is a type character, at most 63 allele bytes and a NUL
-            ENC_ALLOC(b.d_img32, (size_t)b.cand_cap * b.W * b.F * sizeof(int));
-            ENC_ALLOC(b.d_img8, (size_t)b.cand_cap * b.W * b.F);
-            CandArgs ca;
-            ca.regions = b.p_regions; ca.rules = b.d_rules.as<pa_cand::Rule>(); ca.n_regions = n_regions; ca.n_tiles = b.n_tiles;
-            ca.counters = counters; ca.region_counts = region_counts; ca.n_recs = b.d_tile_off.as<int>() + b.n_tiles;
-            ca.rec_cap = b.rec_cap; ca.ovf_cap = b.ovf_cap; ca.pool_cap = b.pool_cap; ca.vote_cap = vote_cap;
-            ca.sites = b.d_sites_dense.as<SiteRec>(); ca.votes = b.d_votes_dense.as<Vote>(); ca.grouped = b.d_grouped.as<Vote>();
-            ca.ovf = b.d_ovf.as<int4>(); ca.rare_next = b.d_rare_next.as<int>();
-            ca.ref = b.p_ref; ca.pool = b.d_pool.as<char>(); ca.pass = b.d_pass.as<uint8_t>();
-            ca.row_slot = b.d_row_slot.as<int>(); ca.aux = b.d_aux.as<SiteAux>(); ca.large = b.d_large.as<int>();
-            ca.cinfo = b.d_czero.as<int>(); ca.tile_nc = ca.cinfo + CI_N; ca.tile_nb = ca.tile_nc + b.n_tiles;
-            ca.tile_c0 = b.d_cscan.as<int>(); ca.tile_b0 = ca.tile_c0 + b.n_tiles + 1;
-            ca.cand_cap = b.cand_cap; ca.mid = b.mid;
-            ca.cands = b.d_cands.as<CandDesc>(); ca.positions = b.d_pos.as<int64_t>(); ca.depths = b.d_depths.as<int32_t>();
-            ca.freqs = b.d_freqs.as<int32_t>(); ca.names = b.d_names.as<char>();
-            const dim3 g_small((unsigned)std::min<int64_t>(b.total_rows, 8192)), g_large((unsigned)std::min<int64_t>(b.total_rows, 1536));
-            ENC_HIP(hipMemsetAsync(b.d_czero.p, 0, n_czero * 4, st));
-            hipLaunchKernelGGL(group_votes_kernel, dim3((unsigned)n_regions), dim3(1024), 0, st, ca);
-            hipLaunchKernelGGL((enumerate_sites_kernel<64, false>), g_small, dim3(64), 0, st, ca);
-            hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, false>), g_large, dim3(64), 0, st, ca);
-            hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nc, b.n_tiles, b.d_cscan.as<int>());
-            hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nb, b.n_tiles, b.d_cscan.as<int>() + b.n_tiles + 1);
-            hipLaunchKernelGGL((enumerate_sites_kernel<64, true>), g_small, dim3(64), 0, st, ca);
-            hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, true>), g_large, dim3(64), 0, st, ca);
-            ENC_HIP(hipEventRecord(e->ev[4], st));
-            hipLaunchKernelGGL(gather_windows_n_kernel, dim3((unsigned)std::min(b.cand_cap, 16384)), dim3(64), 0, st, ca, b.d_mat.as<int>(),
-                               b.W, b.F, b.d_img32.as<int>(), b.d_img8.as<int8_t>());
-            ENC_HIP(hipEventRecord(e->ev[5], st));
-            ENC_HIP(hipGetLastError());
-            ENC_HIP(hipMemcpyAsync(b.h_cscan.p, b.d_cscan.p, n_cscan * 4, hipMemcpyDeviceToHost, st));
-            ENC_HIP(hipMemcpyAsync(b.h_cscan.as<int>() + n_cscan, b.d_czero.p, CI_N * 4, hipMemcpyDeviceToHost, st));
-        }
-        ENC_HIP(hipMemcpyAsync(host_counters, counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
-        ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
-        ENC_HIP(hipStreamSynchronize(st));
-        const int n_recs = host_counters[CT_N + 2 * n_regions];
-        if (n_recs > b.rec_cap || host_counters[CT_OVF] > b.ovf_cap || host_counters[CT_POOL] > b.pool_cap) {
-            if (attempt >= 2) return pa::set_error(PA_ERR_HIP, "encoder record buffers could not be sized");
-            b.rec_cap = std::max(b.rec_cap, n_recs + 1024);
-            b.ovf_cap = std::max(b.ovf_cap, host_counters[CT_OVF] + 1024);
-            b.pool_cap = std::max(b.pool_cap, host_counters[CT_POOL] + 1024);
-            continue;
-        }
-        if (dev && host_counters[CT_ERR] <= 0 && host_counters[CT_VOTES] <= vote_cap && b.h_cscan.as<int>()[n_cscan + CI_REFUSED] == 0) {
-            const int found = b.h_cscan.as<int>()[b.n_tiles];
-            if (found > b.cand_cap) {                            // more candidates than the buffers hold: nothing was written
-                if (attempt >= 3) return pa::set_error(PA_ERR_HIP, "encoder candidate buffers could not be sized");
-                b.cand_cap = (int)std::min<int64_t>(0x7ffffff0, (int64_t)found + found / 4 + 1024);
-                continue;
-            }
-            on_device = true;
-        }
-        break;
-    }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); b.ms[0] = ms;       // records: count pass + offsets + fill pass
-    (void)hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); b.ms[1] = ms;       // tile_count_kernel
-    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); b.ms[2] = ms;       // compact_votes_kernel + pack_results_kernel
-    if (b.packed && b.ms[8] == 0 && b.ms[9] == 0) {
-        (void)hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); b.ms[8] = ms;   // upload of the arena and the tables
-        (void)hipEventElapsedTime(&ms, e->ev[7], e->ev[8]); b.ms[9] = ms;   // unpack_clip_kernel
-    }
-    if (b.packed) {               // what unpack_clip_kernel reported while the batch was staged (the copy is long done)
+    w.host_counters = b.h_counts.as<int>();
+    w.counters = b.d_zero.as<int>();
+    w.region_counts = w.counters + CT_N;
+    w.tile_count = w.region_counts + 2 * n_regions;
+    w.tile_fill = w.tile_count + b.n_tiles;
+    if (!w.dev) return PA_OK;
+    if (!b.h_rules.ensure((size_t)n_regions * sizeof(pa_cand::Rule)) || !b.h_cscan.ensure((w.n_cscan + CI_N) * 4))
+        return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    for (int r = 0; r < n_regions; ++r) b.h_rules.as<pa_cand::Rule>()[r] = region_rule(b.regs[(size_t)r]);
+    ENC_ALLOC(b.d_rules, (size_t)n_regions * sizeof(pa_cand::Rule));
+    ENC_ALLOC(b.d_row_slot, (size_t)b.total_rows * 4 + 64);
+    ENC_ALLOC(b.d_aux, (size_t)b.total_rows * sizeof(SiteAux) + 64);
+    ENC_ALLOC(b.d_large, (size_t)b.total_rows * 4 + 64);         // (a row holds at most one site)
+    ENC_ALLOC(b.d_grouped, (size_t)w.vote_cap * sizeof(Vote));
+    ENC_ALLOC(b.d_czero, w.n_czero * 4);
+    ENC_ALLOC(b.d_cscan, w.n_cscan * 4);
+    return PA_OK;
+}
+
+// one attempt's count kernels: the records of every tile, tile_count_kernel, the votes compacted and the lists packed
+int submit_counts(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    ENC_ALLOC(b.d_sorted, (size_t)b.rec_cap * sizeof(TileRec));
+    ENC_ALLOC(b.d_ovf, (size_t)b.ovf_cap * sizeof(int4));
+    ENC_ALLOC(b.d_pool, (size_t)b.pool_cap * POOL_SLOT);
+    ENC_HIP(hipMemsetAsync(b.d_zero.p, 0, w.n_zero * 4, st));
+    ENC_HIP(hipEventRecord(e->ev[0], st));
+    const dim3 seg_grid((unsigned)((b.total_reads + 3) / 4));
+    if (b.total_reads > 0)
+        hipLaunchKernelGGL(segment_reads_kernel<false>, seg_grid, dim3(256), 0, st, b.d_reads.as<ReadRec>(), (int)b.total_reads,
+                           b.p_regions, b.d_cig_op.as<int32_t>(), b.d_cig_len.as<int32_t>(), w.tile_count,
+                           (const int*)nullptr, (int*)nullptr, (TileRec*)nullptr, 0);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, w.tile_count, b.n_tiles, b.d_tile_off.as<int>());
+    if (b.total_reads > 0)
+        hipLaunchKernelGGL(segment_reads_kernel<true>, seg_grid, dim3(256), 0, st, b.d_reads.as<ReadRec>(), (int)b.total_reads,
+                           b.p_regions, b.d_cig_op.as<int32_t>(), b.d_cig_len.as<int32_t>(), w.tile_count,
+                           b.d_tile_off.as<int>(), w.tile_fill, b.d_sorted.as<TileRec>(), b.rec_cap);
+    ENC_HIP(hipEventRecord(e->ev[1], st));
+    TileArgs ta;
+    ta.reads = b.d_reads.as<ReadRec>(); ta.regions = b.p_regions; ta.tile_region = b.p_tile_region;
+    ta.cigar_op = b.d_cig_op.as<int32_t>(); ta.cigar_len = b.d_cig_len.as<int32_t>();
+    ta.seq = b.d_seq.as<char>(); ta.qual = b.d_qual.as<uint8_t>(); ta.ref = b.p_ref;
+    ta.recs = b.d_sorted.as<TileRec>(); ta.tile_off = b.d_tile_off.as<int>(); ta.rec_cap = b.rec_cap;
+    ta.mat = b.d_mat.as<int>(); ta.pass = b.d_pass.as<uint8_t>(); ta.sites = b.d_sites.as<SiteRec>();
+    ta.votes = b.d_votes.as<Vote>(); ta.votes_out = b.d_votes_out.as<Vote>(); ta.vote_cap = w.vote_cap;
+    ta.ovf = b.d_ovf.as<int4>(); ta.ovf_cap = b.ovf_cap; ta.counters = w.counters; ta.region_counts = w.region_counts;
+    static const int tile_debug = [] { const char* e = getenv("PA_TILE_DEBUG"); return e ? atoi(e) : 0; }();
+    ta.debug = tile_debug;
+    hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    ENC_HIP(hipEventRecord(e->ev[2], st));
+    hipLaunchKernelGGL(compact_votes_kernel, dim3((unsigned)std::min(2048, (w.vote_cap + 255) / 256)), dim3(256), 0, st, b.d_votes.as<Vote>(),
+                       w.counters, w.vote_cap, b.p_regions, b.d_pass.as<uint8_t>(), b.d_seq.as<char>(), b.p_ref, w.region_counts,
+                       b.d_votes_out.as<Vote>());
+    hipLaunchKernelGGL(pack_results_kernel, dim3((unsigned)w.n_regions), dim3(256), 0, st, b.p_regions, w.region_counts,
+                       b.d_sites.as<SiteRec>(), b.d_votes_out.as<Vote>(), b.d_sites_dense.as<SiteRec>(), b.d_votes_dense.as<Vote>(),
+                       b.d_seq.as<char>(), b.d_pool.as<char>(), b.pool_cap, w.counters);
+    ENC_HIP(hipEventRecord(e->ev[3], st));
+    ENC_HIP(hipGetLastError());
+    return PA_OK;
+}
+
+// candidates and windows behind the counts, in the same submission: the votes grouped per site, the sites enumerated twice
+// (counted, then written behind the scans of the tile totals), the windows gathered, the scans on their way to the host
+int submit_candidates(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    ENC_ALLOC(b.d_rare_next, (size_t)b.ovf_cap * 4);
+    ENC_ALLOC(b.d_cands, (size_t)b.cand_cap * sizeof(CandDesc));
+    ENC_ALLOC(b.d_pos, (size_t)b.cand_cap * 8);
+    ENC_ALLOC(b.d_depths, (size_t)b.cand_cap * 4);
+    ENC_ALLOC(b.d_freqs, (size_t)b.cand_cap * 4);
+    ENC_ALLOC(b.d_names, (size_t)b.cand_cap * 72);           // a name is a type character, at most 63 allele bytes and a NUL
+    ENC_ALLOC(b.d_img32, (size_t)b.cand_cap * b.W * b.F * sizeof(int));
+    ENC_ALLOC(b.d_img8, (size_t)b.cand_cap * b.W * b.F);
+    CandArgs ca;
+    ca.regions = b.p_regions; ca.rules = b.d_rules.as<pa_cand::Rule>(); ca.n_regions = w.n_regions; ca.n_tiles = b.n_tiles;
+    ca.counters = w.counters; ca.region_counts = w.region_counts; ca.n_recs = b.d_tile_off.as<int>() + b.n_tiles;
+    ca.rec_cap = b.rec_cap; ca.ovf_cap = b.ovf_cap; ca.pool_cap = b.pool_cap; ca.vote_cap = w.vote_cap;
+    ca.sites = b.d_sites_dense.as<SiteRec>(); ca.votes = b.d_votes_dense.as<Vote>(); ca.grouped = b.d_grouped.as<Vote>();
+    ca.ovf = b.d_ovf.as<int4>(); ca.rare_next = b.d_rare_next.as<int>();
+    ca.ref = b.p_ref; ca.pool = b.d_pool.as<char>(); ca.pass = b.d_pass.as<uint8_t>();
+    ca.row_slot = b.d_row_slot.as<int>(); ca.aux = b.d_aux.as<SiteAux>(); ca.large = b.d_large.as<int>();
+    ca.cinfo = b.d_czero.as<int>(); ca.tile_nc = ca.cinfo + CI_N; ca.tile_nb = ca.tile_nc + b.n_tiles;
+    ca.tile_c0 = b.d_cscan.as<int>(); ca.tile_b0 = ca.tile_c0 + b.n_tiles + 1;
+    ca.cand_cap = b.cand_cap; ca.mid = b.mid;
+    ca.cands = b.d_cands.as<CandDesc>(); ca.positions = b.d_pos.as<int64_t>(); ca.depths = b.d_depths.as<int32_t>();
+    ca.freqs = b.d_freqs.as<int32_t>(); ca.names = b.d_names.as<char>();
+    const dim3 g_small((unsigned)std::min<int64_t>(b.total_rows, 8192)), g_large((unsigned)std::min<int64_t>(b.total_rows, 1536));
+    ENC_HIP(hipMemsetAsync(b.d_czero.p, 0, w.n_czero * 4, st));
+    hipLaunchKernelGGL(group_votes_kernel, dim3((unsigned)w.n_regions), dim3(1024), 0, st, ca);
+    hipLaunchKernelGGL((enumerate_sites_kernel<64, false>), g_small, dim3(64), 0, st, ca);
+    hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, false>), g_large, dim3(64), 0, st, ca);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nc, b.n_tiles, b.d_cscan.as<int>());
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, ca.tile_nb, b.n_tiles, b.d_cscan.as<int>() + b.n_tiles + 1);
+    hipLaunchKernelGGL((enumerate_sites_kernel<64, true>), g_small, dim3(64), 0, st, ca);
+    hipLaunchKernelGGL((enumerate_sites_kernel<CAND_SITE_MAX, true>), g_large, dim3(64), 0, st, ca);
+    ENC_HIP(hipEventRecord(e->ev[4], st));
+    hipLaunchKernelGGL(gather_windows_n_kernel, dim3((unsigned)std::min(b.cand_cap, 16384)), dim3(64), 0, st, ca, b.d_mat.as<int>(),
+                       b.W, b.F, b.d_img32.as<int>(), b.d_img8.as<int8_t>());
+    ENC_HIP(hipEventRecord(e->ev[5], st));
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipMemcpyAsync(b.h_cscan.p, b.d_cscan.p, w.n_cscan * 4, hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipMemcpyAsync(b.h_cscan.as<int>() + w.n_cscan, b.d_czero.p, CI_N * 4, hipMemcpyDeviceToHost, st));
+    return PA_OK;
+}
+
+// what the device reported about the input: unpack_clip_kernel while the batch was staged (the copy is long done; with it the
+// reads per region and the sample's counts), then the counters of the run
+int check_reports(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    const int n_regions = w.n_regions;
+    if (b.packed) {
         pa_enc::sample_collect(e);
         const int* hl = b.h_live.as<int>();
         if (hl[n_regions] > 0)
@@ -2321,34 +2280,47 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
                                                          ": a CIGAR operation of 2^24 bases or more (take the host-clipped form for this batch)");
         for (int r = 0; r < n_regions; ++r) b.live[(size_t)r] = hl[r];
     }
-    if (host_counters[CT_ERR] > 0) {
-        const int64_t g = host_counters[CT_ERR] - 1;
+    if (w.host_counters[CT_ERR] > 0) {
+        const int64_t g = w.host_counters[CT_ERR] - 1;
         size_t r = 0;
         while (r + 1 < b.regs.size() && b.regs[r + 1].read_base <= g) ++r;
         return pa::set_error(PA_ERR_INVALID, "CIGAR of read " + std::to_string(g - b.regs[r].read_base) + (n_regions > 1 ? " of region " + std::to_string(r) : "") +
                                                  " runs past its sequence");
     }
-    if (host_counters[CT_VOTES] > vote_cap) return pa::set_error(PA_ERR_INVALID, "more indel votes than CIGAR operations (corrupt pileup)");
-    if (on_device) {                  // nothing left for the host: the counts per region are differences of the tile offsets
-        const int* c0 = b.h_cscan.as<int>();
-        int tile = 0;
-        for (int r = 0; r < n_regions; ++r) {
-            const int nt = (b.regs[(size_t)r].L + 1 + TP - 1) / TP;
-            b.region_n[(size_t)r] = c0[tile + nt] - c0[tile];
-            tile += nt;
-        }
-        b.n = c0[b.n_tiles];
-        b.name_bytes = c0[n_cscan - 1];
-        b.dev_results = true;
-        b.dev_calls += 1;
-        if (n_candidates)
-            for (int r = 0; r < n_regions; ++r) n_candidates[r] = b.region_n[(size_t)r];
-        (void)hipEventElapsedTime(&ms, e->ev[3], e->ev[4]); b.ms[12] = ms;  // group_votes_kernel ... enumerate_sites_kernel (both forms)
-        (void)hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); b.ms[3] = ms;   // gather_windows_n_kernel
-        b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        return PA_OK;
+    if (w.host_counters[CT_VOTES] > w.vote_cap) return pa::set_error(PA_ERR_INVALID, "more indel votes than CIGAR operations (corrupt pileup)");
+    return PA_OK;
+}
+
+// the kernels enumerated this run: nothing left for the host -- the counts per region are differences of the tile offsets
+int take_device_results(pa_encoder* e, const RunShape& w, int64_t* n_candidates) {
+    pa_variant_batch& b = *e->variant;
+    const int* c0 = b.h_cscan.as<int>();
+    int tile = 0;
+    for (int r = 0; r < w.n_regions; ++r) {
+        const int nt = (b.regs[(size_t)r].L + 1 + TP - 1) / TP;
+        b.region_n[(size_t)r] = c0[tile + nt] - c0[tile];
+        tile += nt;
     }
-    if (dev) b.host_calls += 1;       // refused by the kernels (CI_REFUSED): enumerated below, as with the switch off
+    b.n = c0[b.n_tiles];
+    b.name_bytes = c0[w.n_cscan - 1];
+    b.dev_results = true;
+    b.dev_calls += 1;
+    if (n_candidates)
+        for (int r = 0; r < w.n_regions; ++r) n_candidates[r] = b.region_n[(size_t)r];
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e->ev[3], e->ev[4]); b.ms[12] = ms;  // group_votes_kernel ... enumerate_sites_kernel (both forms)
+    (void)hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); b.ms[3] = ms;   // gather_windows_n_kernel
+    return PA_OK;
+}
+
+// the host's enumeration: the dense lists downloaded, sorted and enumerated region by region on the pool, the candidates sent
+// back and their windows gathered
+int enumerate_on_host(pa_encoder* e, const RunShape& w, int64_t* n_candidates) {
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    const int n_regions = w.n_regions;
+    const int* host_rc = w.host_counters + CT_N;
+    if (w.dev) b.host_calls += 1;     // refused by the kernels (CI_REFUSED): enumerated here, as with the switch off
     // region r's sites / votes are [s0[r], s0[r + 1]) / [v0[r], v0[r + 1]) of the dense lists
     std::vector<size_t> s0((size_t)n_regions + 1, 0), v0((size_t)n_regions + 1, 0), o0((size_t)n_regions + 1, 0);
     for (int r = 0; r < n_regions; ++r) {
@@ -2356,7 +2328,8 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         v0[(size_t)r + 1] = v0[(size_t)r] + (size_t)host_rc[2 * r + 1];
     }
     const size_t n_sites = s0[(size_t)n_regions], n_votes = v0[(size_t)n_regions];
-    const int n_ovf = host_counters[CT_OVF], n_pool = host_counters[CT_POOL];
+    const int n_ovf = w.host_counters[CT_OVF], n_pool = w.host_counters[CT_POOL];
+    float ms = 0;
     if (!b.h_sites.ensure(n_sites * sizeof(SiteRec) + 64) || !b.h_votes.ensure(n_votes * sizeof(Vote) + 64) ||
         !b.h_pool.ensure((size_t)n_pool * POOL_SLOT + 64))
         return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
@@ -2437,6 +2410,74 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         ENC_HIP(hipStreamSynchronize(st));
         (void)hipEventElapsedTime(&ms, e->ev[4], e->ev[5]); b.ms[3] = ms;   // gather_windows_kernel
     }
+    return PA_OK;
+}
+
+int run_staged(pa_encoder* e, int64_t* n_candidates) {
+    if (!e || !e->variant || !e->variant->staged) return pa::set_error(PA_ERR_INVALID, "no staged batch");
+    ENC_HIP(hipSetDevice(e->device));
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    const int n_regions = (int)b.regs.size();
+    b.n = 0;
+    b.region_n.assign((size_t)n_regions, 0);
+    b.positions.clear(); b.depths.clear(); b.freqs.clear(); b.names.clear();
+    for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
+    if (n_regions == 0) return PA_OK;
+    const auto t_begin = std::chrono::steady_clock::now();
+    RunShape w;
+    int rc = size_workspaces(e, w);
+    if (rc != PA_OK) return rc;
+    if (b.packed && !b.sampled) {     // deep intervals sampled down before anything reads the pairs (once per staged batch)
+        std::vector<int32_t> region_pairs((size_t)n_regions + 1);
+        for (int r = 0; r < n_regions; ++r) region_pairs[(size_t)r] = (int32_t)b.regs[(size_t)r].read_base;
+        region_pairs[(size_t)n_regions] = (int32_t)b.total_reads;
+        rc = pa_enc::sample_pairs(e, n_regions, region_pairs.data(), b.d_reads.as<ReadRec>(), b.d_live.as<int>(), b.h_live.as<int>());
+        if (rc != PA_OK) return rc;
+        b.sampled = true;
+    }
+    b.dev_results = false;
+    b.ms[12] = 0;
+    if (w.dev) ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
+    int* host_counters = w.host_counters;
+    bool on_device = false;           // this call's candidates were enumerated by the kernels
+    for (int attempt = 0;; ++attempt) {       // one submission and one wait each; repeated with room when a buffer was too small
+        rc = submit_counts(e, w);
+        if (rc == PA_OK && w.dev) rc = submit_candidates(e, w);
+        if (rc != PA_OK) return rc;
+        ENC_HIP(hipMemcpyAsync(host_counters, w.counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
+        ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
+        ENC_HIP(hipStreamSynchronize(st));
+        const int n_recs = host_counters[CT_N + 2 * n_regions];
+        if (n_recs > b.rec_cap || host_counters[CT_OVF] > b.ovf_cap || host_counters[CT_POOL] > b.pool_cap) {
+            if (attempt >= 2) return pa::set_error(PA_ERR_HIP, "encoder record buffers could not be sized");
+            b.rec_cap = std::max(b.rec_cap, n_recs + 1024);
+            b.ovf_cap = std::max(b.ovf_cap, host_counters[CT_OVF] + 1024);
+            b.pool_cap = std::max(b.pool_cap, host_counters[CT_POOL] + 1024);
+            continue;
+        }
+        if (w.dev && host_counters[CT_ERR] <= 0 && host_counters[CT_VOTES] <= w.vote_cap && b.h_cscan.as<int>()[w.n_cscan + CI_REFUSED] == 0) {
+            const int found = b.h_cscan.as<int>()[b.n_tiles];
+            if (found > b.cand_cap) {                            // more candidates than the buffers hold: nothing was written
+                if (attempt >= 3) return pa::set_error(PA_ERR_HIP, "encoder candidate buffers could not be sized");
+                b.cand_cap = (int)std::min<int64_t>(0x7ffffff0, (int64_t)found + found / 4 + 1024);
+                continue;
+            }
+            on_device = true;
+        }
+        break;
+    }
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e->ev[0], e->ev[1]); b.ms[0] = ms;       // records: count pass + offsets + fill pass
+    (void)hipEventElapsedTime(&ms, e->ev[1], e->ev[2]); b.ms[1] = ms;       // tile_count_kernel
+    (void)hipEventElapsedTime(&ms, e->ev[2], e->ev[3]); b.ms[2] = ms;       // compact_votes_kernel + pack_results_kernel
+    if (b.packed && b.ms[8] == 0 && b.ms[9] == 0) {
+        (void)hipEventElapsedTime(&ms, e->ev[6], e->ev[7]); b.ms[8] = ms;   // upload of the arena and the tables
+        (void)hipEventElapsedTime(&ms, e->ev[7], e->ev[8]); b.ms[9] = ms;   // unpack_clip_kernel
+    }
+    rc = check_reports(e, w);
+    if (rc == PA_OK) rc = on_device ? take_device_results(e, w, n_candidates) : enumerate_on_host(e, w, n_candidates);
+    if (rc != PA_OK) return rc;
     b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();  // whole run, host clock
     return PA_OK;
 }
@@ -2483,8 +2524,9 @@ void pa_enc::sample_collect(pa_encoder* e) {
 }
 
 // The packed reads of a batch of regions clipped and decoded on the device WITHOUT the variant encoder's tables: what the polish
-// image chain (encoder_polish.hip) starts from.  Same arena / read / pair tables as stage_packed, same kernel; the regions are
-// given by their bounds alone.  Nothing here waits for the device.
+// image chain (encoder_polish.hip) starts from.  Same arena / read / pair tables as stage_packed, same block, same pair walk (with
+// the room a region can fill) and the same submission; the regions are given by their bounds alone.  Nothing here waits for
+// the device.
 int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_t* region_start, const int64_t* region_end,
                                   const uint8_t* arena, int64_t arena_bytes, const pa_packed_read* reads, int32_t n_reads,
                                   const int32_t* pair_read, const int32_t* region_pairs, int32_t extra_ops_per_pair, UnpackedReads* out) {
@@ -2497,96 +2539,41 @@ int pa_enc::unpack_packed_regions(pa_encoder* e, int32_t n_regions, const int64_
     ENC_HIP(hipSetDevice(e->device));
     if (!e->variant) e->variant = new pa_variant_batch();
     pa_variant_batch& b = *e->variant;
-    const bool resident = arena == nullptr && n_reads > 0;
-    if (resident && (b.resident_bytes <= 0 || arena_bytes > b.resident_bytes))
-        return pa::set_error(PA_ERR_INVALID, "no arena given and no inflated span of that size resident on the device");
+    int rc = check_resident(b, arena, n_reads, arena_bytes);
+    if (rc != PA_OK) return rc;
     b.staged = false;               // (the variant encoder's staged batch, if any, shares these buffers)
     const int64_t n_pairs = n_regions ? region_pairs[n_regions] : 0;
     if (n_pairs < 0 || (n_regions && region_pairs[0] != 0)) return pa::set_error(PA_ERR_INVALID, "region_pairs must start at 0 and ascend");
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_reg = 0, o_start = up16(o_reg + (size_t)n_regions * sizeof(RegRec)), o_reads = up16(o_start + (size_t)n_regions * 8),
-                 o_pairs = up16(o_reads + (size_t)n_reads * sizeof(PackedRead)), o_soff = up16(o_pairs + (size_t)n_pairs * sizeof(PairRec)),
-                 meta_bytes = up16(o_soff + soff.size() * 8) + 64;
-    if (!b.h_meta.ensure(meta_bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    const PackedBlock L = lay_out_block(n_regions, 0, (size_t)n_reads * sizeof(PackedRead), (size_t)n_pairs * sizeof(PairRec), soff.size() * 8, 0);
+    if (!b.h_meta.ensure(L.bytes) || !b.h_live.ensure(((size_t)n_regions + 2) * 4)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_ALLOC(b.d_meta, L.bytes);
     char* hm = b.h_meta.as<char>();
-    RegRec* regrecs = reinterpret_cast<RegRec*>(hm + o_reg);
-    int64_t* rstart = reinterpret_cast<int64_t*>(hm + o_start);
-    PairRec* pairs = reinterpret_cast<PairRec*>(hm + o_pairs);
-    if (n_reads) std::memcpy(hm + o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
-    if (!soff.empty()) std::memcpy(hm + o_soff, soff.data(), soff.size() * 8);
-    int64_t total_bases = 0, total_ops = 0;
+    RegRec* regrecs = reinterpret_cast<RegRec*>(hm + L.o_reg);
+    int64_t* rstart = reinterpret_cast<int64_t*>(hm + L.o_start);
+    RegionSums sums;
     for (int r = 0; r < n_regions; ++r) {
-        if (region_end[r] < region_start[r] || region_end[r] - region_start[r] > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
+        pa_pileup p{};
+        p.region_start = rstart[r] = region_start[r];
+        p.region_end = region_end[r];
+        rc = region_pass(p, nullptr, nullptr, 0, 0, 0, sums, nullptr, regrecs[r]);
+        if (rc != PA_OK) return rc;
         if (region_pairs[r + 1] < region_pairs[r]) return pa::set_error(PA_ERR_INVALID, "region_pairs must ascend");
-        RegRec& g = regrecs[r];
-        std::memset(&g, 0, sizeof(g));
-        g.L = (int32_t)(region_end[r] - region_start[r] + 1);
-        rstart[r] = region_start[r];
-        for (int32_t k = region_pairs[r]; k < region_pairs[r + 1]; ++k) {
-            const int32_t ri = pair_read[k];
-            if (ri < 0 || ri >= n_reads) return pa::set_error(PA_ERR_INVALID, "pair_read out of range");
-            const pa_packed_read& rd = reads[ri];
-            if (!packed_read_inside(rd, soff.empty() ? -1 : soff[(size_t)ri], arena_bytes))
-                return pa::set_error(PA_ERR_INVALID, "packed read " + std::to_string(ri) + " lies outside the arena");
-            // the clipped stretch of a read holds its aligned bases inside the region and the inserts between them: room for the
-            // whole read would be 10-50 kb per pair of a 1 kb region, so a pair gets min(l_seq, 2 L + 64) bases; a pair that
-            // keeps more is reported as unsupported (h_live[n_regions + 1]) and the caller takes the host-clipped form
-            const int64_t cap = std::min<int64_t>(rd.l_seq, 2ll * g.L + 64);
-            pairs[k] = PairRec{total_bases, ri, r, (int32_t)total_ops, (int32_t)cap};
-            total_bases += ((cap + 3) & ~(int64_t)3) + 4;
-            // (kept M / D / N operations each cover a row of the region, kept I / S ones a kept base)
-            total_ops += std::min<int64_t>(rd.n_cigar, (int64_t)g.L + cap + 2);
-        }
     }
+    if (n_reads) std::memcpy(hm + L.o_reads, reads, (size_t)n_reads * sizeof(PackedRead));
+    if (!soff.empty()) std::memcpy(hm + L.o_soff, soff.data(), soff.size() * 8);
+    std::vector<int64_t> seq_base((size_t)n_regions + 1);
+    std::vector<int32_t> op_base((size_t)n_regions + 1);
+    rc = walk_pairs(n_regions, region_pairs, pair_read, reads, n_reads, soff, arena_bytes, regrecs, reinterpret_cast<PairRec*>(hm + L.o_pairs),
+                    seq_base.data(), op_base.data());
+    if (rc != PA_OK) return rc;
+    const int64_t total_bases = seq_base[(size_t)n_regions], total_ops = op_base[(size_t)n_regions];
     const int64_t extra_ops = extra_ops_per_pair < 0 ? 0 : total_bases + n_pairs * (int64_t)extra_ops_per_pair;
-    if (total_ops + extra_ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, "batch too large: more than 2^31 CIGAR operations");
-    hipStream_t st = e->stream;
-    if (!resident) {
-        ENC_ALLOC(b.d_arena, (size_t)arena_bytes + 256);
-        b.resident_bytes = 0;
-    }
-    ENC_ALLOC(b.d_meta, meta_bytes);
-    ENC_ALLOC(b.d_live, ((size_t)n_regions + 2) * 4);
-    ENC_ALLOC(b.d_seq, (size_t)total_bases + 64);
-    ENC_ALLOC(b.d_qual, (size_t)total_bases + 64);
-    ENC_ALLOC(b.d_cig_op, (size_t)(total_ops + extra_ops) * 4 + 1024);
-    ENC_ALLOC(b.d_cig_len, (size_t)(total_ops + extra_ops) * 4 + 1024);
-    ENC_ALLOC(b.d_reads, (size_t)n_pairs * sizeof(ReadRec) + 64);
-    if (arena_bytes > 0 && !resident) ENC_HIP(hipMemcpyAsync(b.d_arena.p, arena, (size_t)arena_bytes, hipMemcpyHostToDevice, st));
-    ENC_HIP(hipMemcpyAsync(b.d_meta.p, hm, meta_bytes, hipMemcpyHostToDevice, st));
-    ENC_HIP(hipMemsetAsync(b.d_live.p, 0, ((size_t)n_regions + 2) * 4, st));
-    const char* dm = b.d_meta.as<char>();
-    if (n_pairs > 0) {
-        UnpackArgs ua;
-        ua.pairs = reinterpret_cast<const PairRec*>(dm + o_pairs);
-        ua.n_pairs = (int)n_pairs;
-        ua.preads = reinterpret_cast<const PackedRead*>(dm + o_reads);
-        ua.regions = reinterpret_cast<const RegRec*>(dm + o_reg);
-        ua.region_start = reinterpret_cast<const int64_t*>(dm + o_start);
-        ua.arena = b.d_arena.as<uint8_t>();
-        ua.seq_off = soff.empty() ? nullptr : reinterpret_cast<const int64_t*>(dm + o_soff);
-        ua.reads = b.d_reads.as<ReadRec>();
-        ua.cigar_op = b.d_cig_op.as<int32_t>();
-        ua.cigar_len = b.d_cig_len.as<int32_t>();
-        ua.seq = b.d_seq.as<char>();
-        ua.qual = b.d_qual.as<uint8_t>();
-        ua.live = b.d_live.as<int>();
-        ua.n_regions = n_regions;
-        hipLaunchKernelGGL(unpack_clip_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(256), 0, st, ua);
-        ENC_HIP(hipGetLastError());
-    }
-    ENC_HIP(hipMemcpyAsync(b.h_live.p, b.d_live.p, ((size_t)n_regions + 2) * 4, hipMemcpyDeviceToHost, st));
-    out->reads = b.d_reads.as<ReadRec>();
-    out->cigar_op = b.d_cig_op.as<int32_t>();
-    out->cigar_len = b.d_cig_len.as<int32_t>();
-    out->seq = b.d_seq.as<char>();
-    b.last_pairs = n_pairs;
-    out->n_pairs = n_pairs;
-    out->total_bases = total_bases;
-    out->total_ops = total_ops;
-    out->extra_ops = extra_ops;
-    out->d_live = b.d_live.as<int>();
-    out->h_live = b.h_live.as<int>();
+    if (total_ops + extra_ops > 0x7ffffff0) return pa::set_error(PA_ERR_INVALID, BATCH_TOO_LARGE);
+    rc = submit_unpack(e, n_regions, n_pairs, arena, arena_bytes, n_reads, L, block_tables(b, L, !soff.empty()), total_bases, total_ops, extra_ops);
+    if (rc != PA_OK) return rc;
+    out->reads = b.d_reads.as<ReadRec>(); out->cigar_op = b.d_cig_op.as<int32_t>(); out->cigar_len = b.d_cig_len.as<int32_t>();
+    out->seq = b.d_seq.as<char>(); out->d_live = b.d_live.as<int>(); out->h_live = b.h_live.as<int>();
+    out->n_pairs = n_pairs; out->total_bases = total_bases; out->total_ops = total_ops; out->extra_ops = extra_ops;
     return PA_OK;
 }
 

@@ -61,4 +61,8 @@ PA_PK_FN int32_t region_range_end(const int64_t* start, int32_t n_regions, int32
 // bytes of a kept record's slice(s): operations, 4-bit bases, qualities
 PA_PK_FN int64_t slice_bytes(uint32_t n_cigar, uint32_t l_seq) { return 4ll * n_cigar + (l_seq + 1) / 2 + l_seq; }
 
+// bytes a (read, region) pair gets for n clipped bases in the byte-per-base arrays: unpack_clip_kernel decodes four bases per
+// store, and a pair's first base sits on a multiple of 4
+PA_PK_FN int64_t base_room(int64_t n_bases) { return ((n_bases + 3) & ~(int64_t)3) + 4; }
+
 }  // namespace pa_pack
