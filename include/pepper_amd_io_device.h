@@ -30,7 +30,8 @@ typedef struct pa_inflater pa_inflater;
 int pa_inflater_create(int32_t device, pa_inflater** out);
 void pa_inflater_destroy(pa_inflater* h);
 /* Host buffers in, host buffer out: upload, `repeats` runs of the kernel (>= 1; the runs write the same bytes -- for timing),
- * download.  Returns PA_ERR_INVALID with the first failing block's reason when a stream is malformed. */
+ * download.  Returns PA_ERR_INVALID with the first failing block's reason when a stream is malformed: what zlib's inflate
+ * refuses is refused (an over-subscribed or incomplete Huffman code, a distance beyond the output, output that is not ISIZE, ...). */
 int pa_inflater_inflate(pa_inflater* h, const uint8_t* comp, int64_t comp_bytes, int32_t n_blocks, const int64_t* comp_off,
                         const int32_t* comp_len, const int64_t* out_off, const int32_t* out_len, uint8_t* out, int64_t out_bytes,
                         int32_t repeats);

@@ -35,9 +35,13 @@
 // masks is scalar work), and the register budget is six wavefronts per SIMD (79 VGPRs; at eight, spills cost more than
 // the two wavefronts bring).
 //
-// Checks: over-subscribed code sets, codes without a symbol, distances beyond the produced output, output beyond the
-// block's ISIZE, a stored block's LEN/NLEN complement, input consumed beyond the block -> a non-zero status word per
-// block (the host call fails with the first one).  The member's CRC-32 is verified in the kernel's epilogue (wave_crc32).
+// Checks, as zlib's inflate makes them: a reserved block type, a stored block's LEN/NLEN complement, HLIT / HDIST out of range,
+// over-subscribed and incomplete code sets (the code length code always; a literal/length or distance set may be empty or one
+// code of length 1), a repeat without a previous length or past HLIT + HDIST, a set without the end-of-block code, bits that
+// are no code of a set, the length symbols 286 / 287, distances beyond the produced output, output that is not the block's
+// ISIZE, input consumed beyond the block -> a non-zero status word per block (the host call fails with the first one;
+// tests/test_gpu_inflate_crafted.py reaches every one of them).  The member's CRC-32 is verified in the kernel's epilogue
+// (wave_crc32).
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_io_device.h"
 
@@ -67,7 +71,7 @@ constexpr int RING_MIRROR = 8;                   // ... and its first words once
 
 enum InflateStatus : int32_t {
     INF_OK = 0, INF_BAD_BLOCK_TYPE = 1, INF_STORED_LEN = 2, INF_OVERSUBSCRIBED = 3, INF_NO_END_CODE = 4, INF_BAD_CODE = 5,
-    INF_BAD_REPEAT = 6, INF_DISTANCE = 7, INF_OUTPUT = 8, INF_LENGTH = 9, INF_INPUT = 10, INF_BAD_COUNTS = 11, INF_CRC = 12
+    INF_BAD_REPEAT = 6, INF_DISTANCE = 7, INF_OUTPUT = 8, INF_LENGTH = 9, INF_INPUT = 10, INF_BAD_COUNTS = 11, INF_CRC = 12, INF_INCOMPLETE = 13
 };
 
 struct Tables {
@@ -183,7 +187,8 @@ struct Stream {
 };
 
 // Canonical code of `n` symbols from their lengths (RFC 1951 3.2.2): count[], the symbols in (length, symbol) order and
-// the primary table of 2^tbits entries.  Returns false for an over-subscribed set.  All lanes call it.
+// the primary table of 2^tbits entries.  Returns what the set leaves of the code space in units of 2^-15 (RFC 1951's Kraft sum:
+// 0 = complete, > 0 = incomplete, the table is built all the same), -1 for an over-subscribed set.  All lanes call it.
 // What a primary-table entry holds (0 = no code of at most `tbits` bits starts like this index):
 //   PLAIN   uint16  length | symbol << 4                                              (the code length code)
 //   LITLEN  uint16  length | extra bits << 4 | is-length << 7 | value << 8            value = the literal, or a length
@@ -211,7 +216,7 @@ PA_DEV uint32_t table_entry(TableFormat format, int sym, int len) {
 }
 
 template <TableFormat FORMAT, typename Entry>
-PA_DEV bool build_table(const uint8_t* lens, int n, int* count, uint16_t* syms, Entry* table, int tbits, int* first_of = nullptr,
+PA_DEV int build_table(const uint8_t* lens, int n, int* count, uint16_t* syms, Entry* table, int tbits, int* first_of = nullptr,
                         int* index_of = nullptr) {
     const int lane = threadIdx.x;
     if (lane < 16) count[lane] = 0;
@@ -237,7 +242,7 @@ PA_DEV bool build_table(const uint8_t* lens, int n, int* count, uint16_t* syms, 
     }
     wave_order();
     if (lane == 0) count[0] = 0;
-    if (!ok) return false;
+    if (!ok) return -1;
     for (int base = 0; base < n; base += 64) {
         const int s = base + lane;
         const int l = s < n ? lens[s] : 0;
@@ -274,8 +279,11 @@ PA_DEV bool build_table(const uint8_t* lens, int n, int* count, uint16_t* syms, 
         table[t] = where >= 0 ? (Entry)table_entry(FORMAT, syms[where], hit_len) : (Entry)0;
     }
     wave_order();
-    return true;
+    return left;
 }
+
+// The incomplete sets zlib's inflate_table lets a literal/length or distance set be: no code at all, or a single code of length 1.
+PA_DEV bool empty_or_one_bit_code(int left, const int* count) { return left == 1 << 15 || (left == 1 << 14 && uni(count[1]) == 1); }
 
 // One symbol from uniform bits: the primary table, or bit by bit for a longer code.  -1: the bits are no code of the set.
 // *used: the code's length.
@@ -576,7 +584,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
                 in.p += 3 * hclen;
             }
             wave_order();
-            if (!build_table<PLAIN>(T.cl_lens, 19, T.cl_count, T.cl_sym, T.cl_table, CL_BITS)) { err = INF_OVERSUBSCRIBED; break; }
+            // (the code length code must be complete: zlib's "invalid code lengths set")
+            const int cl_left = build_table<PLAIN>(T.cl_lens, 19, T.cl_count, T.cl_sym, T.cl_table, CL_BITS);
+            if (cl_left != 0) { err = cl_left < 0 ? INF_OVERSUBSCRIBED : INF_INCOMPLETE; break; }
             const int total = hlit + hdist;
             int i = 0, prev = 0;
             while (i < total) {
@@ -622,11 +632,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(WAVES, WAVES
             for (int s = hlit + lane; s < 288; s += 64) T.lens[s] = 0;
         }
         wave_order();
-        if (!build_table<LITLEN>(T.lens, 288, T.lit_count, T.lit_sym, T.lit_table, LIT_BITS, T.lit_first, T.lit_index) ||
-            !build_table<DIST>(T.lens + 288, 32, T.dist_count, T.dist_sym, T.dist_table, DIST_BITS, T.dist_first, T.dist_index)) {
-            err = INF_OVERSUBSCRIBED;
-            break;
-        }
+        // (zlib's "invalid literal/lengths set" / "invalid distances set")
+        const int lit_left = build_table<LITLEN>(T.lens, 288, T.lit_count, T.lit_sym, T.lit_table, LIT_BITS, T.lit_first, T.lit_index);
+        if (lit_left != 0 && !empty_or_one_bit_code(lit_left, T.lit_count)) { err = lit_left < 0 ? INF_OVERSUBSCRIBED : INF_INCOMPLETE; break; }
+        const int dist_left = build_table<DIST>(T.lens + 288, 32, T.dist_count, T.dist_sym, T.dist_table, DIST_BITS, T.dist_first, T.dist_index);
+        if (dist_left != 0 && !empty_or_one_bit_code(dist_left, T.dist_count)) { err = dist_left < 0 ? INF_OVERSUBSCRIBED : INF_INCOMPLETE; break; }
         // ---- the symbols of the block: 64 bit offsets at a time ----
         // Lane k decodes whatever starts at bit p + k (most offsets are inside a symbol: their result is never looked at);
         // the symbols that do start in the window are found by following the lengths from offset 0.
@@ -1186,6 +1196,7 @@ const char* inflate_status_text(int32_t s) {
         case INF_INPUT: return "stream runs beyond the block's compressed bytes";
         case INF_BAD_COUNTS: return "HLIT or HDIST out of range";
         case INF_CRC: return "CRC32 of the inflated bytes differs from the member's trailer";
+        case INF_INCOMPLETE: return "incomplete Huffman code";
     }
     return "?";
 }
