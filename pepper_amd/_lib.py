@@ -244,6 +244,24 @@ def device_pack():
     return os.environ.get(DEVICE_PACK_ENV, "0") == "1"
 
 
+DEVICE_INFLATE_ENV = "PEPPER_AMD_DEVICE_INFLATE"
+
+
+def device_inflate():
+    """PEPPER_AMD_DEVICE_INFLATE=0: the image-generation drivers have the host packer inflate the BGZF members again
+    (PackedEncoder.fetch goes straight to pack)."""
+    return os.environ.get(DEVICE_INFLATE_ENV, "1") != "0"
+
+
+DEVICE_WALK_ENV = "PEPPER_AMD_DEVICE_WALK"
+
+
+def device_walk():
+    """PEPPER_AMD_DEVICE_WALK=0: PackedEncoder.pack_device walks a downloaded copy of every inflated span on the host again.
+    Read per call."""
+    return os.environ.get(DEVICE_WALK_ENV, "1") != "0"
+
+
 def check(rc):
     if rc != PA_OK:
         msg = load().pa_last_error()

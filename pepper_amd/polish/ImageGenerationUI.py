@@ -11,7 +11,6 @@ import os
 import re
 import sys
 import time
-import threading
 from concurrent.futures import ThreadPoolExecutor
 from datetime import datetime
 
@@ -20,9 +19,6 @@ from pepper_amd.polish.DataStore import DataStore
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.variant.bam import BAM_handler
 from pepper_amd.variant.fasta import FASTA_handler
-
-
-_STATS_LOCK = threading.Lock()
 
 
 def _log(message):
@@ -161,7 +157,7 @@ class UserInterfaceSupport:
         from pepper_amd import _lib
         from pepper_amd.polish import PEPPER
         from pepper_amd.polish.AlignmentSummarizer import AlingerOptions
-        from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
+        from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder, adjacent_run, merge_stats, worker_counters
         output_path, bam_file, draft_file, truth_bam, train_mode, downsample_rate = args
         timestr = time.strftime("%m%d%Y_%H%M%S")
         file_name = output_path + "pepper_hp_images_thread_" + str(thread_id) + "_" + str(timestr) + ".hdf"
@@ -193,150 +189,126 @@ class UserInterfaceSupport:
             return UserInterfaceSupport.image_generator(args, all_intervals, total_threads, thread_id)
         chain = PEPPER.PolishChain(enc)
         consensus = fused.worker(thread_id, device, stream=enc.stream) if fused is not None else None      # polish(fused_inference=True): fused.py
-        device_inflate = os.environ.get("PEPPER_AMD_DEVICE_INFLATE", "1") != "0"
+        device_inflate = _lib.device_inflate()
         device_sampling = _lib.device_sampling()
         sampling = (AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION) if device_sampling else None
-        sampled_before = enc.sampled()[0]
         long_cigars = _lib.device_long_cigars()
-        long_before = enc.long_cigar_reads
         safe = AlingerOptions.ALIGNMENT_SAFE_BASES
         seq_len, features = ImageSizeOptions.SEQ_LENGTH, ImageSizeOptions.IMAGE_HEIGHT
         views = {}
         handles = {}
-        try:
-            with DataStore(file_name, 'w') as output_hdf_file:
-                def host_form(chr_name, block):
-                    """parse_regions (host-clipped reads, host arrays between the stages) for the intervals of `block`."""
-                    key = (chr_name, bam_file, draft_file)
-                    mine["host_form_intervals"] += len(block)
-                    if key not in views:
-                        views.clear()
-                        views[key] = UserInterfaceView(chr_name, bam_file, draft_file, truth_bam, train_mode)
-                    for g0 in range(0, len(block), UserInterfaceSupport.REGIONS_PER_CALL):
-                        part = block[g0:g0 + UserInterfaceSupport.REGIONS_PER_CALL]
-                        results = views[key].parse_regions([(a, b) for _, a, b in part], downsample_rate)
-                        for region, (images, labels, positions, chunk_ids) in zip(part, results):
-                            if len(images):
-                                output_hdf_file.write_summaries(region, images, labels, positions, chunk_ids)
-                                if consensus is not None:
-                                    consensus.add_host(region, images, positions, chunk_ids)
+        # what the encoder counts while this worker runs goes into `mine` and the handle goes back to the pool, whether the
+        # loop ends or raises
+        with worker_counters(enc, mine, release_on_error=True):
+            try:
+                with DataStore(file_name, 'w') as output_hdf_file:
+                    def host_form(chr_name, block):
+                        """parse_regions (host-clipped reads, host arrays between the stages) for the intervals of `block`."""
+                        key = (chr_name, bam_file, draft_file)
+                        mine["host_form_intervals"] += len(block)
+                        if key not in views:
+                            views.clear()
+                            views[key] = UserInterfaceView(chr_name, bam_file, draft_file, truth_bam, train_mode)
+                        for g0 in range(0, len(block), UserInterfaceSupport.REGIONS_PER_CALL):
+                            part = block[g0:g0 + UserInterfaceSupport.REGIONS_PER_CALL]
+                            results = views[key].parse_regions([(a, b) for _, a, b in part], downsample_rate)
+                            for region, (images, labels, positions, chunk_ids) in zip(part, results):
+                                if len(images):
+                                    output_hdf_file.write_summaries(region, images, labels, positions, chunk_ids)
+                                    if consensus is not None:
+                                        consensus.add_host(region, images, positions, chunk_ids)
 
-                counter = 0
-                while counter < len(intervals):
-                    chr_name = intervals[counter][0]
-                    g1 = counter + 1
-                    # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last one)
-                    while (g1 < len(intervals) and g1 - counter < batch and intervals[g1][0] == chr_name
-                           and intervals[g1 - 1][1] <= intervals[g1][1] <= intervals[g1 - 1][2] + 1
-                           and intervals[g1][2] >= intervals[g1 - 1][2]):
-                        g1 += 1
-                    block = intervals[counter:g1]
-                    if chr_name not in handles:
-                        handles.clear()
-                        handles[chr_name] = (BAM_handler(bam_file), FASTA_handler(draft_file))
-                    bam_handler, fasta_handler = handles[chr_name]
-                    starts, stops = [a for _, a, _ in block], [b for _, _, b in block]
+                    counter = 0
+                    while counter < len(intervals):
+                        chr_name = intervals[counter][0]
+                        block = intervals[counter:adjacent_run(intervals, counter, batch, 1)]
+                        if chr_name not in handles:
+                            handles.clear()
+                            handles[chr_name] = (BAM_handler(bam_file), FASTA_handler(draft_file))
+                        bam_handler, fasta_handler = handles[chr_name]
+                        starts, stops = [a for _, a, _ in block], [b for _, _, b in block]
+                        # bam_pack is the whole fetch, on the device or through the host packer (lap_resident=True)
+                        resident, n_done, region_pairs, counts = enc.fetch(bam_handler, chr_name, starts, stops, False, 0, device_inflate,
+                                                                           mine, lap_resident=True, long_cigars=long_cigars)
+                        t0 = time.perf_counter()
+                        if n_done == 0:
+                            host_form(chr_name, block[:1])
+                            counter += 1
+                            continue
+                        block, starts, stops = block[:n_done], starts[:n_done], stops[:n_done]
+                        region_pairs = np.asarray(region_pairs[:n_done + 1], np.int32)
+                        per_region = np.diff(region_pairs)
+                        deep = [] if device_sampling else np.flatnonzero(per_region > AlingerOptions.MAX_READS_IN_REGION)
+                        if len(deep):
+                            # PEPPER_AMD_DEVICE_SAMPLING=0: a pile beyond the reference's cap is sampled down in read order
+                            # (AlignmentSummarizer.py:314-326) on the host; the chain sees those intervals without reads and their
+                            # chunks come from host_form below
+                            keep = np.ones(int(region_pairs[-1]), bool)
+                            for r in deep:
+                                keep[region_pairs[r]:region_pairs[r + 1]] = False
+                            kept = enc.pair_read[:int(region_pairs[-1])][keep]
+                            enc.pair_read[:len(kept)] = kept
+                            per_region = per_region.copy()
+                            per_region[deep] = 0
+                            region_pairs = np.concatenate([[0], np.cumsum(per_region)]).astype(np.int32)
+                            counts = (counts[0], int(region_pairs[-1]), counts[2])
+                        lo = starts[0]
+                        whole = fasta_handler.get_reference_bytes(chr_name, lo, max(stops) + safe + 1)
+                        windows = [whole[a - lo:b + safe + 1 - lo] for a, b in zip(starts, stops)]
+                        t0 = lap("fasta", t0)
+                        refused_at = None
+                        for r0 in range(0, n_done, per_call):           # the chain over stretches of the resident span
+                            r1 = min(n_done, r0 + per_call)
+                            if consensus is not None:
+                                consensus.settle()                       # (the copies of the last run's chunks: this run overwrites them)
+                                t0 = lap("fused_consensus", t0)
+                            try:
+                                _rows, _live, chunks = chain.run(list(zip(starts[r0:r1], stops[r0:r1])), windows[r0:r1], region_pairs[r0:r1 + 1],
+                                                                 counts, realign=True, resident=resident, chunk_size=seq_len,
+                                                                 chunk_overlap=ImageSizeOptions.SEQ_OVERLAP, sampling=sampling)
+                            except _lib.PepperAmdError as err:
+                                if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
+                                    raise
+                                host_form(chr_name, block[r0:])          # (this stretch and what follows it in the span)
+                                refused_at = r0
+                                break
+                            t0 = lap("chain", t0)
+                            for key, v in chain.timing().items():
+                                if key.endswith("_ms"):
+                                    mine["chain_" + key[:-3]] = mine.get("chain_" + key[:-3], 0.0) + v / 1e3
+                                else:
+                                    mine[key] = mine.get(key, 0) + v
+                            if consensus is not None and chain.n_chunks:
+                                # (first: the gather copy then runs on the device while this thread writes the image file)
+                                _img, pos_v, idx_v = chain.chunk_arrays()
+                                consensus.add(chr_name, starts[r0:r1], stops[r0:r1], chunks, chain.device_chunks(), pos_v, idx_v)
+                                t0 = lap("fused_consensus", t0)
+                            img, pos, idx = chain.chunk_pointers()
+                            output_hdf_file.write_regions(chr_name, starts[r0:r1], stops[r0:r1], chunks, seq_len, features, img, pos, idx)
+                            t0 = lap("hdf5", t0)
+                        if refused_at is not None:
+                            deep = [r for r in deep if r < refused_at]
+                        if len(deep):
+                            host_form(chr_name, [block[r] for r in deep])
+                            lap("deep_host_form", t0)
+                        before = counter
+                        counter += n_done
+                        if thread_id == 0 and counter // 1000 > before // 1000:
+                            elapsed = int(time.time() - start_time)
+                            _log("INFO: [THREAD " + "{:02d}".format(thread_id) + "] " + str(counter) + "/" + str(len(intervals))
+                                 + " COMPLETE (" + str(int(100 * counter / len(intervals))) + "%) [ELAPSED TIME: "
+                                 + str(elapsed // 60) + " Min " + str(elapsed % 60) + " Sec]")
+                    t_close = time.perf_counter()
+                lap("close", t_close)
+                if consensus is not None:
                     t0 = time.perf_counter()
-                    on_device = (enc.pack_device(bam_handler, chr_name, starts, stops, False, 0, laps=mine, long_cigars=long_cigars)
-                                 if device_inflate else None)
-                    resident = on_device is not None
-                    n_done = 0
-                    if resident:
-                        n_done, region_pairs, counts = on_device
-                    else:
-                        try:
-                            n_done, region_pairs, counts = enc.pack(bam_handler, chr_name, starts, stops, False, 0)
-                        except Exception as err:
-                            if getattr(err, "code", 0) != -7:      # (-7: one interval's reads outgrow the arena)
-                                raise
-                    t0 = lap("bam_pack", t0)
-                    if n_done == 0:
-                        host_form(chr_name, block[:1])
-                        counter += 1
-                        continue
-                    block, starts, stops = block[:n_done], starts[:n_done], stops[:n_done]
-                    region_pairs = np.asarray(region_pairs[:n_done + 1], np.int32)
-                    per_region = np.diff(region_pairs)
-                    deep = [] if device_sampling else np.flatnonzero(per_region > AlingerOptions.MAX_READS_IN_REGION)
-                    if len(deep):
-                        # PEPPER_AMD_DEVICE_SAMPLING=0: a pile beyond the reference's cap is sampled down in read order
-                        # (AlignmentSummarizer.py:314-326) on the host; the chain sees those intervals without reads and their
-                        # chunks come from host_form below
-                        keep = np.ones(int(region_pairs[-1]), bool)
-                        for r in deep:
-                            keep[region_pairs[r]:region_pairs[r + 1]] = False
-                        kept = enc.pair_read[:int(region_pairs[-1])][keep]
-                        enc.pair_read[:len(kept)] = kept
-                        per_region = per_region.copy()
-                        per_region[deep] = 0
-                        region_pairs = np.concatenate([[0], np.cumsum(per_region)]).astype(np.int32)
-                        counts = (counts[0], int(region_pairs[-1]), counts[2])
-                    lo = starts[0]
-                    whole = fasta_handler.get_reference_bytes(chr_name, lo, max(stops) + safe + 1)
-                    windows = [whole[a - lo:b + safe + 1 - lo] for a, b in zip(starts, stops)]
-                    t0 = lap("fasta", t0)
-                    refused_at = None
-                    for r0 in range(0, n_done, per_call):           # the chain over stretches of the resident span
-                        r1 = min(n_done, r0 + per_call)
-                        if consensus is not None:
-                            consensus.settle()                       # (the copies of the last run's chunks: this run overwrites them)
-                            t0 = lap("fused_consensus", t0)
-                        try:
-                            _rows, _live, chunks = chain.run(list(zip(starts[r0:r1], stops[r0:r1])), windows[r0:r1], region_pairs[r0:r1 + 1],
-                                                             counts, realign=True, resident=resident, chunk_size=seq_len,
-                                                             chunk_overlap=ImageSizeOptions.SEQ_OVERLAP, sampling=sampling)
-                        except _lib.PepperAmdError as err:
-                            if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
-                                raise
-                            host_form(chr_name, block[r0:])          # (this stretch and what follows it in the span)
-                            refused_at = r0
-                            break
-                        t0 = lap("chain", t0)
-                        for key, v in chain.timing().items():
-                            if key.endswith("_ms"):
-                                mine["chain_" + key[:-3]] = mine.get("chain_" + key[:-3], 0.0) + v / 1e3
-                            else:
-                                mine[key] = mine.get(key, 0) + v
-                        if consensus is not None and chain.n_chunks:
-                            # (first: the gather copy then runs on the device while this thread writes the image file)
-                            _img, pos_v, idx_v = chain.chunk_arrays()
-                            consensus.add(chr_name, starts[r0:r1], stops[r0:r1], chunks, chain.device_chunks(), pos_v, idx_v)
-                            t0 = lap("fused_consensus", t0)
-                        img, pos, idx = chain.chunk_pointers()
-                        output_hdf_file.write_regions(chr_name, starts[r0:r1], stops[r0:r1], chunks, seq_len, features, img, pos, idx)
-                        t0 = lap("hdf5", t0)
-                    if refused_at is not None:
-                        deep = [r for r in deep if r < refused_at]
-                    if len(deep):
-                        host_form(chr_name, [block[r] for r in deep])
-                        lap("deep_host_form", t0)
-                    before = counter
-                    counter += n_done
-                    if thread_id == 0 and counter // 1000 > before // 1000:
-                        elapsed = int(time.time() - start_time)
-                        _log("INFO: [THREAD " + "{:02d}".format(thread_id) + "] " + str(counter) + "/" + str(len(intervals))
-                             + " COMPLETE (" + str(int(100 * counter / len(intervals))) + "%) [ELAPSED TIME: "
-                             + str(elapsed // 60) + " Min " + str(elapsed % 60) + " Sec]")
-                t_close = time.perf_counter()
-            lap("close", t_close)
-            if consensus is not None:
-                t0 = time.perf_counter()
-                consensus.close()
-                lap("fused_consensus", t0)
-        except BaseException:
-            if consensus is not None:
-                consensus.close(failed=True)
-            raise
-        finally:
-            enc.inflate_ms, enc.inflated_bytes = 0.0, 0
-            mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
-            mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
-            enc.set_sampling(None)
-            enc.release()
-        if stats is not None:
-            with _STATS_LOCK:
-                for key, v in mine.items():
-                    stats[key] = stats.get(key, 0.0) + v
+                    consensus.close()
+                    lap("fused_consensus", t0)
+            except BaseException:
+                if consensus is not None:
+                    consensus.close(failed=True)
+                raise
+        merge_stats(stats, mine)
         return thread_id
 
     @staticmethod

@@ -22,9 +22,6 @@ from pepper_amd.variant.AlignmentSummarizer import AlignmentSummarizer
 from pepper_amd.variant.DataStore import DataStore
 
 
-_STATS_LOCK = __import__("threading").Lock()
-
-
 def _log(msg):
     sys.stderr.write("[" + datetime.now().strftime('%m-%d-%Y %H:%M:%S') + "] " + msg + "\n")
     sys.stderr.flush()
@@ -176,6 +173,7 @@ class ImageGenerationUtils:
         if process_id == 0:
             _log("INFO: STARTING PROCESS: " + str(process_id) + " FOR " + str(len(intervals)) + " INTERVALS")
         from pepper_amd.variant.AlignmentSummarizer import create_summaries
+        from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder, adjacent_run, merge_stats, worker_counters
         generators = {}
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
         # ... and two counts: intervals the device sampled down, intervals that took the host-clipped form for any reason
@@ -190,12 +188,6 @@ class ImageGenerationUtils:
             now = time.perf_counter()
             mine[key] = mine.get(key, 0.0) + now - t0
             return now
-
-        def report():
-            if stats is not None:
-                with _STATS_LOCK:
-                    for key, v in mine.items():
-                        stats[key] = stats.get(key, 0.0) + v
 
         sink = getattr(options, "fused_sink", None)         # call_variant's fused form: predictions straight from the encoder's windows
 
@@ -234,7 +226,7 @@ class ImageGenerationUtils:
             if not packed:
                 for g0 in range(0, len(intervals), batch):
                     host_clipped(output_hdf_file, intervals[g0:g0 + batch])
-                report()
+                merge_stats(stats, mine)
                 return process_id
             # The packed form: per group of consecutive intervals ONE call of the BAM reader (inflate, header walk, filters; no
             # clipping, no decoding: the reads cross PCIe as BAM stores them, once per group) and ONE of the encoder (clip +
@@ -242,7 +234,6 @@ class ImageGenerationUtils:
             from pepper_amd import _lib
             from pepper_amd.variant.AlignmentSummarizer import AlingerOptions, ConsensCandidateFinder
             from pepper_amd.variant.Options import ImageSizeOptions
-            from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
             t_setup = time.perf_counter()
             # (every CPU the process has is inflating BGZF blocks in some worker: the encoder's host part runs on this thread)
             try:
@@ -251,7 +242,7 @@ class ImageGenerationUtils:
                 # no page-locked arena to be had (memlock / cgroup limit): the host-clipped form needs none
                 for g0 in range(0, len(intervals), batch):
                     host_clipped(output_hdf_file, intervals[g0:g0 + batch])
-                report()
+                merge_stats(stats, mine)
                 return process_id
             bam_handler, fasta_handler = _handlers(options, options.bam, options.fasta)
             lap("setup", t_setup)
@@ -259,113 +250,80 @@ class ImageGenerationUtils:
             params = (options.min_snp_baseq, options.min_indel_baseq, options.snp_frequency, options.insert_frequency,
                       options.delete_frequency, options.min_coverage_threshold, options.snp_candidate_frequency_threshold,
                       options.indel_candidate_frequency_threshold, options.candidate_support_threshold, options.skip_indels)
-            device_inflate = os.environ.get("PEPPER_AMD_DEVICE_INFLATE", "1") != "0"
+            # the BGZF members inflated on the device where the BAM has an index (PEPPER_AMD_DEVICE_INFLATE=0: on the host)
+            device_inflate = _lib.device_inflate()
             # the reference samples an interval's reads down to min(MAX_READS_IN_REGION, downsample_rate * n)
             # (AlignmentSummarizer.py:192-199) in read order: drawn on the device between the clip and the summary
             # (reservoir_keep_kernel); PEPPER_AMD_DEVICE_SAMPLING=0: such intervals take the host-clipped form
             device_sampling = _lib.device_sampling()
             sampling = ((AlingerOptions.RANDOM_SEED, AlingerOptions.MAX_READS_IN_REGION, float(options.downsample_rate))
                         if device_sampling else None)
-            sampled_before = enc.sampled()[0]
             # a read whose CIGAR travels in the CG tag stays in the span inflated on the device (operations from the tag, bases
             # from the core); PEPPER_AMD_DEVICE_LONG_CIGARS=0: its group of intervals takes the host packer
             long_cigars = _lib.device_long_cigars()
-            long_before = enc.long_cigar_reads
-            # candidates enumerated between the count kernels and the window gather, without the host pass in the middle of
-            # every call (pa_encoder_set_device_candidates)
-            enc.set_device_candidates(_lib.device_candidates())
-            calls_before = enc.candidate_calls()
             # the read and pair tables built behind the device's record walk (pa_encoder_pack_records): the lap bam_walk_device
             # is then walk + pack with their one wait, and bam_walk only the spans the device handed back
             device_pack = _lib.device_pack()
-            g0 = 0
-            while g0 < len(intervals):
-                # ADJACENT intervals of one contig, ascending (the packer walks every record between the first and the last
-                # region of a call: a group must not bridge the gap to this worker's next run of intervals)
-                g1 = g0 + 1
-                while (g1 < len(intervals) and g1 - g0 < batch and intervals[g1][0] == intervals[g0][0]
-                       and intervals[g1 - 1][1] <= intervals[g1][1] <= intervals[g1 - 1][2] + 2 * safe
-                       and intervals[g1][2] >= intervals[g1 - 1][2]):
-                    g1 += 1
-                group = intervals[g0:g1]
-                chr_name = group[0][0]
-                regions = [(max(0, s - safe), e + safe) for _, s, e in group]
-                t0 = time.perf_counter()
-                # the BGZF members inflated on the device where the BAM has an index (PEPPER_AMD_DEVICE_INFLATE=0: on the host);
-                # a batch the device form cannot take (pack_device's docstring) goes through the host packer
-                on_device = enc.pack_device(bam_handler, chr_name, [r[0] for r in regions], [r[1] for r in regions],
-                                            options.include_supplementary, options.min_mapq, laps=mine,
-                                            long_cigars=long_cigars, device_pack=device_pack) if device_inflate else None
-                resident = on_device is not None
-                if resident:
-                    n_done, region_pairs, counts = on_device
+            # what the encoder counts while this worker runs goes into `mine`; candidates enumerated between the count kernels
+            # and the window gather where PEPPER_AMD_DEVICE_CANDIDATES=1 (pa_encoder_set_device_candidates).  A worker that
+            # raises leaves its handle out of the pool
+            with worker_counters(enc, mine, release_on_error=False, inflate_figures=True, candidates=True):
+                g0 = 0
+                while g0 < len(intervals):
+                    group = intervals[g0:adjacent_run(intervals, g0, batch, 2 * safe)]
+                    chr_name = group[0][0]
+                    regions = [(max(0, s - safe), e + safe) for _, s, e in group]
+                    # a batch the device form cannot take (pack_device's docstring) goes through the host packer; bam_pack is the
+                    # host packer's time alone (lap_resident=False: what the device form takes is in its own laps)
+                    resident, n_done, region_pairs, counts = enc.fetch(
+                        bam_handler, chr_name, [r[0] for r in regions], [r[1] for r in regions], options.include_supplementary,
+                        options.min_mapq, device_inflate, mine, lap_resident=False, long_cigars=long_cigars, device_pack=device_pack)
                     t0 = time.perf_counter()
-                else:
+                    if n_done == 0:
+                        host_clipped(output_hdf_file, group[:1])
+                        g0 += 1
+                        continue
+                    group, regions = group[:n_done], regions[:n_done]
+                    per_region = np.diff(region_pairs[:n_done + 1])
+                    if not device_sampling and (options.downsample_rate < 1.0
+                                                or int(per_region.max(initial=0)) > AlingerOptions.MAX_READS_IN_REGION):
+                        host_clipped(output_hdf_file, group)
+                        g0 += n_done
+                        continue
+                    # one fetch for the group's whole stretch of the contig (adjacent intervals), sliced per interval
+                    lo, hi = regions[0][0], max(b for _, b in regions) + 1
+                    whole = fasta_handler.get_reference_bytes(chr_name, lo, hi)
+                    references = [whole[a - lo:b + 1 - lo] for a, b in regions]
+                    t0 = lap("fasta", t0)
                     try:
-                        n_done, region_pairs, counts = enc.pack(bam_handler, chr_name, [r[0] for r in regions], [r[1] for r in regions],
-                                                                options.include_supplementary, options.min_mapq)
-                    except Exception as err:
-                        if getattr(err, "code", 0) != -7:
+                        outs, live = enc.encode(regions, references, region_pairs, counts, params, [(s, e) for _, s, e in group],
+                                                ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident,
+                                                sampling=sampling)
+                    except _lib.PepperAmdError as err:
+                        if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
                             raise
-                        n_done = 0                       # (-7: one interval's reads outgrow the arena)
-                    t0 = lap("bam_pack", t0)
-                if n_done == 0:
-                    host_clipped(output_hdf_file, group[:1])
-                    g0 += 1
-                    continue
-                group, regions = group[:n_done], regions[:n_done]
-                per_region = np.diff(region_pairs[:n_done + 1])
-                if not device_sampling and (options.downsample_rate < 1.0
-                                            or int(per_region.max(initial=0)) > AlingerOptions.MAX_READS_IN_REGION):
-                    host_clipped(output_hdf_file, group)
+                        host_clipped(output_hdf_file, group)
+                        g0 += n_done
+                        continue
+                    t0 = lap("encode", t0)
+                    mine["encoder_calls"] += 1
+                    mine["device_packed_calls" if (resident and enc.device_packed) else "host_packed_calls"] += 1
+                    probs, at = None, 0
+                    if sink is not None:
+                        # the group's windows are still where the encoder left them on the device: the model reads them there
+                        total = sum(len(o["positions"]) for o in outs)
+                        probs = sink.forward_device(device, enc.lib.pa_encoder_device_images(enc.enc), total)
+                        t0 = lap("fused_forward", t0)
+                    for (chr_name, _start, _end), out, n_reads in zip(group, outs, live):
+                        k = len(out["positions"])
+                        if n_reads > 0:                  # (no read with a base inside, or an empty sample: create_summary returns None, nothing is written)
+                            write(output_hdf_file, chr_name, _start, _end, out, None if probs is None else probs[at:at + k])
+                        at += k
+                    lap("hdf5", t0)
                     g0 += n_done
-                    continue
-                # one fetch for the group's whole stretch of the contig (adjacent intervals), sliced per interval
-                lo, hi = regions[0][0], max(b for _, b in regions) + 1
-                whole = fasta_handler.get_reference_bytes(chr_name, lo, hi)
-                references = [whole[a - lo:b + 1 - lo] for a, b in regions]
-                t0 = lap("fasta", t0)
-                try:
-                    outs, live = enc.encode(regions, references, region_pairs, counts, params, [(s, e) for _, s, e in group],
-                                            ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident,
-                                            sampling=sampling)
-                except _lib.PepperAmdError as err:
-                    if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
-                        raise
-                    host_clipped(output_hdf_file, group)
-                    g0 += n_done
-                    continue
-                t0 = lap("encode", t0)
-                mine["encoder_calls"] += 1
-                mine["device_packed_calls" if (resident and enc.device_packed) else "host_packed_calls"] += 1
-                probs, at = None, 0
-                if sink is not None:
-                    # the group's windows are still where the encoder left them on the device: the model reads them there
-                    total = sum(len(o["positions"]) for o in outs)
-                    probs = sink.forward_device(device, enc.lib.pa_encoder_device_images(enc.enc), total)
-                    t0 = lap("fused_forward", t0)
-                for (chr_name, _start, _end), out, n_reads in zip(group, outs, live):
-                    k = len(out["positions"])
-                    if n_reads > 0:                  # (no read with a base inside, or an empty sample: create_summary returns None, nothing is written)
-                        write(output_hdf_file, chr_name, _start, _end, out, None if probs is None else probs[at:at + k])
-                    at += k
-                lap("hdf5", t0)
-                g0 += n_done
-            if enc.inflated_bytes:
-                mine["inflate_kernel"] = mine.get("inflate_kernel", 0.0) + enc.inflate_ms / 1e3
-                mine["inflated_bytes"] = mine.get("inflated_bytes", 0.0) + enc.inflated_bytes
-            enc.inflate_ms, enc.inflated_bytes = 0.0, 0
-            mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
-            mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
-            calls = enc.candidate_calls()
-            mine["device_enumerated_calls"] += calls[0] - calls_before[0]
-            mine["host_enumerated_calls"] += calls[1] - calls_before[1]
-            enc.set_sampling(None)
-            enc.set_device_candidates(False)
-            enc.release()
             t_close = time.perf_counter()
         lap("close", t_close)
-        report()
+        merge_stats(stats, mine)
         return process_id
 
     @staticmethod

@@ -10,12 +10,16 @@ libpepper_amd.so (include/pepper_amd_encoder.h).  `generate_summary_arrays` retu
 struct-of-arrays form (images already int8-packed on the device) for callers that do not need
 per-candidate Python objects.
 """
+import collections
+import contextlib
 import ctypes
-import os
+import threading
+import time
 
 import numpy as np
 
 from pepper_amd import _lib
+from pepper_amd.variant.bam import RECORD_HEADER, BamError
 
 
 class CigarOp(object):
@@ -278,6 +282,22 @@ class _PackedRegion(ctypes.Structure):
                 ("reference_len", ctypes.c_int64)]
 
 
+# PackedEncoder._fit_span: the n regions whose file span was read (first: where its first record starts, final: none of the
+# contig behind it) or holds no record; _walk_on_device: one of four outcomes, what comes with it, whether the pack came back
+_Span = collections.namedtuple("_Span", "n first final n_blocks comp_bytes out_bytes")
+_EmptySpan = collections.namedtuple("_EmptySpan", "n")
+_Walked = collections.namedtuple("_Walked", "outcome detail handed_back")
+PACKED_ON_DEVICE, HEADERS_ON_HOST, HOST_MUST_WALK, STALE_INDEX = "packed on device", "headers on host", "host must walk", "stale index"
+
+
+def _lap(laps, key, t0):
+    """laps[key] += the time since t0 (laps None: nobody asked) -> now"""
+    now = time.perf_counter()
+    if laps is not None:
+        laps[key] = laps.get(key, 0.0) + now - t0
+    return now
+
+
 class PackedEncoder(object):
     """The packed form of a batch (pa_encoder_stage_packed): the reads of a run of regions as pa_bam_pack_regions leaves them
     in this object's page-locked arena -- CIGAR words, 4-bit bases, qualities, once per read -- clipped to each region and
@@ -288,7 +308,7 @@ class PackedEncoder(object):
     _device_packed = False          # the last pack / pack_device left its tables on the device (pa_encoder_pack_records): encode stages from there
     pack_handbacks = 0              # pack_device(device_pack=True) calls whose span the device handed back to the host's pack_headers
     _idle = []                      # encoders returned by release(): a later job's workers take them instead of pinning new arenas
-    _idle_lock = __import__("threading").Lock()
+    _idle_lock = threading.Lock()
 
     @classmethod
     def acquire(cls, device=0, arena_bytes=192 << 20, host_threads=1, torch_stream=False):
@@ -428,31 +448,65 @@ class PackedEncoder(object):
 
     def pack_device(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq, lookahead_windows=4, laps=None,
                     long_cigars=False, device_pack=False):
-        """The same tables with the BGZF members inflated ON THE DEVICE (pa_encoder_inflate_bgzf) into the encoder's arena and
-        the records left in place there: the file span of the regions' reads (BAM index) is read as it is, uploaded, inflated
-        one wavefront per member, and walked on the host in a downloaded copy (headers, filters, region test -- no inflate, no
-        copy).  -> (n_done, region_pairs, counts) for encode(..., resident=True), or None when the batch has to take pack():
-        no index, a span larger than the arena even for one region, a record with its CIGAR in the CG tag, reads longer than
-        the span's lookahead.  long_cigars: CG records stay in the span too -- operations read from the tag, bases from the
-        core (self.seq_off, which encode(..., resident=True) and PolishChain.run pass on).  self.long_cigar_reads adds up the
-        CG reads each call kept: a read that reaches two calls' runs of regions is counted in both.  self.host_walk_spans
-        counts the calls that asked for the device's record walk and walked a downloaded copy of the span on the host instead
-        (slot overflow, an auxiliary field the device's tag walk could not follow).
-        device_pack (with the device's record walk): the tables are built where the headers lie (pa_encoder_pack_records, queued
-        behind the walk: one wait for both) and stay there -- self.reads / self.pair_read are not filled, self.seq_off stays
-        None, and encode(..., resident=True) stages from the device tables.  A span the device hands back (status != 0) has
-        its headers downloaded and goes through pack_headers as without the switch; self.pack_handbacks counts those."""
-        import time
-        from pepper_amd.variant.bam import BamError
-        self.seq_off = None
-        self._device_packed = False
-        if not bam_handler.has_index():
+        """The same tables with the BGZF members inflated ON THE DEVICE into the encoder's arena and the records left in place
+        there -> (n_done, region_pairs, counts) for encode(..., resident=True), or None when the batch has to take pack().
+        One step per rung: _fit_span, _inflate, _walk_on_device (PEPPER_AMD_DEVICE_WALK=0: skipped), _pack_on_host.
+        long_cigars: records with their CIGAR in the CG tag stay in the span too -- operations read from the tag, bases from the
+        core (self.seq_off); self.long_cigar_reads adds them up per call, so a read that reaches two calls counts twice.
+        device_pack (with the device's walk): the tables are built where the headers lie and stay there; self.reads /
+        self.pair_read are not filled, self.seq_off stays None, encode(..., resident=True) stages from the device tables."""
+        self.seq_off, self._device_packed = None, False
+        span = self._fit_span(bam_handler, contig, starts, stops, lookahead_windows, laps) if bam_handler.has_index() else None
+        if span is None:
             return None
+        if isinstance(span, _EmptySpan):             # no record of the contig: every region is done, with nothing in it
+            return span.n, np.zeros(span.n + 1, np.int32), (0, 0, 0)
+        batch = (contig, starts[:span.n], stops[:span.n], include_supplementary, min_mapq)
+        t0 = time.perf_counter()
+        device_walk = _lib.device_walk()
+        self._inflate(span, host_copy=not device_walk)
+        t0 = _lap(laps, "bam_inflate_device", t0)
+        n_headers = None                             # (None: the host walks the span in self.arena)
+        if device_walk:
+            walked = self._walk_on_device(bam_handler, span, batch, long_cigars, device_pack)
+            self.pack_handbacks += int(walked.handed_back)
+            if walked.outcome == STALE_INDEX:
+                return None                          # (the host packer reads the file itself)
+            if walked.outcome == PACKED_ON_DEVICE:
+                _lap(laps, "bam_walk_device", t0)
+                summary, region_pairs = walked.detail
+                self._device_packed = True
+                self.long_cigar_reads += summary.n_split if long_cigars else 0
+                return summary.n_done, region_pairs, (summary.n_reads, summary.n_pairs, int(span.out_bytes))
+            if walked.outcome == HOST_MUST_WALK:
+                self._inflate(span, host_copy=True)
+                self.host_walk_spans += 1
+            else:
+                n_headers = walked.detail
+            t0 = _lap(laps, "bam_walk_device", t0)
+        try:
+            packed = self._pack_on_host(bam_handler, span, batch, n_headers, long_cigars)
+        finally:
+            _lap(laps, "bam_walk", t0)
+        if packed is None:
+            return None
+        n_done, region_pairs, counts = packed
+        if long_cigars and counts[0] > 0:
+            seq_off, n_split = bam_handler.split_offsets(counts[0])
+            if n_split:
+                self.seq_off = seq_off
+                self.long_cigar_reads += n_split
+        return n_done, region_pairs, (counts[0], counts[1], int(span.out_bytes))
+
+    def _fit_span(self, bam_handler, contig, starts, stops, lookahead_windows, laps):
+        """The largest run of regions -- all, half, a quarter, ... -- whose file span (BAM index) is complete and fits the arena,
+        read into the page-locked span block (allocated on first use) -> _Span (bam_span_read is lapped), _EmptySpan, or None:
+        no such block under this memlock limit, or no fit even for one region."""
         if self.span is None:
             cap = self.arena.nbytes + (1 << 20)
             ptr = self.lib.pa_encoder_host_span(self.enc, cap)
             if not ptr:
-                return None                              # (no second page-locked block under this memlock limit: the host packer's form)
+                return None
             self.span = np.ctypeslib.as_array(ctypes.cast(ptr, ctypes.POINTER(ctypes.c_uint8)), shape=(cap,))
             nb = max(4096, self.arena.nbytes // 4096)
             self.tables = (np.zeros(nb, np.int64), np.zeros(nb, np.int32), np.zeros(nb, np.int64), np.zeros(nb, np.int32))
@@ -460,122 +514,112 @@ class PackedEncoder(object):
         n = len(starts)
         while n >= 1:
             begin, first, end, final = bam_handler.region_span(contig, int(starts[0]), int(stops[n - 1]), lookahead_windows)
-            if end <= begin:                         # no record of the contig: every region is done, with nothing in it
-                return n, np.zeros(n + 1, np.int32), (0, 0, 0)
+            if end <= begin:
+                return _EmptySpan(n)
             n_blocks, comp_bytes, out_bytes, complete, at_eof = bam_handler.read_span(begin, end, self.span, self.tables, 1)
-            final = final or at_eof
             if complete and out_bytes + 256 <= self.arena.nbytes:
-                break
+                _lap(laps, "bam_span_read", t0)
+                return _Span(n, first, final or at_eof, n_blocks, comp_bytes, out_bytes)
             n //= 2
-        else:
-            return None
-        if laps is not None:
-            laps["bam_span_read"] = laps.get("bam_span_read", 0.0) + time.perf_counter() - t0
-            t0 = time.perf_counter()
-        comp_off, comp_len, out_off, out_len = self.tables
-        device_walk = os.environ.get("PEPPER_AMD_DEVICE_WALK", "1") != "0"
+        return None
 
-        def inflate(host_copy):
-            _lib.check(self.lib.pa_encoder_inflate_bgzf(self.enc, self.span.ctypes.data, comp_bytes, n_blocks, comp_off.ctypes.data,
-                                                        comp_len.ctypes.data, out_off.ctypes.data, out_len.ctypes.data, out_bytes,
-                                                        self.arena.ctypes.data if host_copy else None))
-            ms = np.zeros(12, np.float64)
-            _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 12))
-            self.inflate_ms += float(ms[10])
-            self.inflated_bytes += int(out_bytes)
-        inflate(not device_walk)
-        if laps is not None:
-            laps["bam_inflate_device"] = laps.get("bam_inflate_device", 0.0) + time.perf_counter() - t0
-            t0 = time.perf_counter()
-        headers = None
-        if device_walk:
-            # the record headers read out on the device (40 bytes per record come back instead of the span)
-            if self.headers is None:
-                from pepper_amd.variant.bam import RECORD_HEADER
-                self.headers = np.zeros(max(1 << 16, self.arena.nbytes // 512), RECORD_HEADER)
-                self.entries = np.zeros(8192, np.int64)
-            n_entries = bam_handler.span_entries(contig, first, out_off, n_blocks, self.entries)
-            n_headers, flags = ctypes.c_int64(), np.zeros(2, np.int32)
-            # slots per entry: 2 048 records of one 16 kb window, fewer when a span has very many windows (low coverage): the
-            # device keeps two 40-byte tables of entries x slots; a window that overflows its slots takes the host walk
-            slots = max(64, min(2048, (32 << 20) // (40 * max(1, n_entries))))
-            if bool(long_cigars) != self._split_walk:
-                _lib.check(self.lib.pa_encoder_set_split_slices(self.enc, 1 if long_cigars else 0))
-                self._split_walk = bool(long_cigars)
-            tid = bam_handler.contig_index(contig) if device_pack else None
-            summary = None
-            try:
-                if tid is not None and tid >= 0:
-                    # walk and pack in one submission, one wait; the walk's flags and the pack's summary are read after it
-                    summary = _lib.DevicePack()
-                    d_starts = np.ascontiguousarray(starts[:n], np.int64)
-                    d_stops = np.ascontiguousarray(stops[:n], np.int64)
-                    d_pairs = np.zeros(n + 1, np.int32)
-                    _lib.check(self.lib.pa_encoder_submit_walk(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots))
-                    _lib.check(self.lib.pa_encoder_pack_records(self.enc, None, 0, int(bool(final)), int(tid), n, d_starts.ctypes.data,
-                                                                d_stops.ctypes.data, int(bool(include_supplementary)), int(min_mapq),
-                                                                len(self.reads), len(self.pair_read), d_pairs.ctypes.data,
-                                                                ctypes.byref(summary)))
-                    flags[0], flags[1] = summary.walk_flags[0], summary.walk_flags[1]
-                    if flags[0] == 0 and summary.status != 0:
-                        # handed back: the headers come down after all and the host's walk decides
-                        self.pack_handbacks += 1
-                        _lib.check(self.lib.pa_encoder_walk_headers(self.enc, self.headers.ctypes.data, len(self.headers),
-                                                                    ctypes.byref(n_headers), flags.ctypes.data))
-                else:
-                    _lib.check(self.lib.pa_encoder_walk_records(self.enc, out_bytes, self.entries.ctypes.data, n_entries, slots,
-                                                                self.headers.ctypes.data, len(self.headers), ctypes.byref(n_headers),
-                                                                flags.ctypes.data))
-            except _lib.PepperAmdError as err:
-                if getattr(err, "code", 0) != _lib.PA_ERR_INVALID:
-                    raise
-                return None                              # (entries outside the span: a stale index -- the host packer reads the file itself)
-            if flags[0] == 0 and summary is not None and summary.status == 0:
-                if laps is not None:
-                    laps["bam_walk_device"] = laps.get("bam_walk_device", 0.0) + time.perf_counter() - t0
-                self._device_packed = True
-                if long_cigars and summary.n_split:
-                    self.long_cigar_reads += summary.n_split
-                return summary.n_done, d_pairs, (summary.n_reads, summary.n_pairs, int(out_bytes))
-            if flags[0] == 0:
-                headers = n_headers.value
-            else:
-                inflate(True)                        # (a window with more records than a lane's slots, ...: the span to the host after all)
-                self.host_walk_spans += 1
-            if laps is not None:
-                laps["bam_walk_device"] = laps.get("bam_walk_device", 0.0) + time.perf_counter() - t0
-                t0 = time.perf_counter()
+    def _inflate(self, span, host_copy):
+        """pa_encoder_inflate_bgzf: the span's members into the device arena, one wavefront per member; host_copy: and down into
+        self.arena for a walk on the host.  Kernel time and bytes add to inflate_ms / inflated_bytes, twice for a span inflated twice."""
+        _lib.check(self.lib.pa_encoder_inflate_bgzf(self.enc, self.span.ctypes.data, span.comp_bytes, span.n_blocks,
+                                                    *(table.ctypes.data for table in self.tables), span.out_bytes,
+                                                    self.arena.ctypes.data if host_copy else None))
+        ms = np.zeros(12, np.float64)
+        _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 12))
+        self.inflate_ms += float(ms[10])
+        self.inflated_bytes += int(span.out_bytes)
+
+    def _walk_on_device(self, bam_handler, span, batch, long_cigars, device_pack):
+        """The record headers of the inflated span read out on the device -> _Walked: PACKED_ON_DEVICE (device_pack and a contig
+        the header names: walk and pa_encoder_pack_records in one submission, one wait; detail = (summary, region_pairs)),
+        HEADERS_ON_HOST (40 bytes per record came back instead of the span; detail = their number), HOST_MUST_WALK (a window of
+        more records than a lane's slots, a tag walk that lost its way) or STALE_INDEX (entries outside the span)."""
+        contig, starts, stops, include_supplementary, min_mapq = batch
+        if self.headers is None:
+            self.headers = np.zeros(max(1 << 16, self.arena.nbytes // 512), RECORD_HEADER)
+            self.entries = np.zeros(8192, np.int64)
+        n_entries = bam_handler.span_entries(contig, span.first, self.tables[2], span.n_blocks, self.entries)
+        n_headers, flags = ctypes.c_int64(), np.zeros(2, np.int32)
+        # slots per entry: 2 048 records of one 16 kb window, fewer when a span has very many windows (low coverage): the
+        # device keeps two 40-byte tables of entries x slots; a window that overflows its slots takes the host walk
+        walk = (self.enc, span.out_bytes, self.entries.ctypes.data, n_entries, max(64, min(2048, (32 << 20) // (40 * max(1, n_entries)))))
+        download = (self.headers.ctypes.data, len(self.headers), ctypes.byref(n_headers), flags.ctypes.data)
+        if bool(long_cigars) != self._split_walk:
+            _lib.check(self.lib.pa_encoder_set_split_slices(self.enc, 1 if long_cigars else 0))
+            self._split_walk = bool(long_cigars)
+        tid = bam_handler.contig_index(contig) if device_pack else None
+        summary, handed_back = None, False
         try:
-            if headers is not None:
-                try:
-                    n_done, region_pairs, counts = bam_handler.pack_headers(self.headers, headers, final, contig, starts[:n], stops[:n],
-                                                                            include_supplementary, min_mapq, self.reads, self.pair_read,
-                                                                            long_cigars=long_cigars)
-                except BamError as err:
-                    if not (long_cigars and getattr(err, "code", 0) == -6):
-                        raise
-                    # (state 2 may be an auxiliary field the device's tag walk could not follow: the host's walk of the
-                    # span decides -- it keeps such a record with its core CIGAR, and fails on a corrupt one as before)
-                    inflate(True)
-                    headers = None
-                    self.host_walk_spans += 1
-            if headers is None:
-                n_done, region_pairs, counts = bam_handler.pack_inflated(self.arena, out_bytes, first, final, contig, starts[:n], stops[:n],
-                                                                         include_supplementary, min_mapq, self.reads, self.pair_read,
-                                                                         long_cigars=long_cigars)
+            if tid is not None and tid >= 0:
+                summary, region_pairs = _lib.DevicePack(), np.zeros(span.n + 1, np.int32)
+                d_starts, d_stops = np.ascontiguousarray(starts, np.int64), np.ascontiguousarray(stops, np.int64)
+                _lib.check(self.lib.pa_encoder_submit_walk(*walk))
+                _lib.check(self.lib.pa_encoder_pack_records(self.enc, None, 0, int(bool(span.final)), int(tid), span.n, d_starts.ctypes.data,
+                                                            d_stops.ctypes.data, int(bool(include_supplementary)), int(min_mapq),
+                                                            len(self.reads), len(self.pair_read), region_pairs.ctypes.data,
+                                                            ctypes.byref(summary)))
+                flags[0], flags[1] = summary.walk_flags[0], summary.walk_flags[1]
+                handed_back = flags[0] == 0 and summary.status != 0
+                if handed_back:                      # the headers come down after all and the host's pack_headers decides
+                    _lib.check(self.lib.pa_encoder_walk_headers(self.enc, *download))
+            else:
+                _lib.check(self.lib.pa_encoder_walk_records(*walk, *download))
+        except _lib.PepperAmdError as err:
+            if getattr(err, "code", 0) != _lib.PA_ERR_INVALID:
+                raise
+            return _Walked(STALE_INDEX, None, handed_back)
+        if flags[0] != 0:
+            return _Walked(HOST_MUST_WALK, None, handed_back)
+        if summary is not None and not handed_back:
+            return _Walked(PACKED_ON_DEVICE, (summary, region_pairs), False)
+        return _Walked(HEADERS_ON_HOST, n_headers.value, handed_back)
+
+    def _pack_on_host(self, bam_handler, span, batch, n_headers, long_cigars):
+        """pack_headers over the n_headers the device read out, or -- None -- pack_inflated over the span in self.arena ->
+        (n_done, region_pairs, counts).  What a BamError means: -7 / -8 / -9 (the reads outgrow the tables or the span's
+        lookahead): None, the batch takes pack(); -6 from the headers under long_cigars (state 2 may be an auxiliary field the
+        device's tag walk could not follow): the host's walk decides, which keeps such a record with its core CIGAR; else raised."""
+        try:
+            if n_headers is not None:
+                return bam_handler.pack_headers(self.headers, n_headers, span.final, *batch, self.reads, self.pair_read, long_cigars=long_cigars)
+            return bam_handler.pack_inflated(self.arena, span.out_bytes, span.first, span.final, *batch, self.reads, self.pair_read,
+                                             long_cigars=long_cigars)
         except BamError as err:
-            if getattr(err, "code", 0) in (-7, -8, -9):
+            code = getattr(err, "code", 0)
+            if code in (-7, -8, -9):
                 return None
-            raise
-        finally:
-            if laps is not None:
-                laps["bam_walk"] = laps.get("bam_walk", 0.0) + time.perf_counter() - t0
-        if long_cigars and counts[0] > 0:
-            seq_off, n_split = bam_handler.split_offsets(counts[0])
-            if n_split:
-                self.seq_off = seq_off
-                self.long_cigar_reads += n_split
-        return n_done, region_pairs, (counts[0], counts[1], int(out_bytes))
+            if not (code == -6 and long_cigars and n_headers is not None):
+                raise
+        self._inflate(span, host_copy=True)
+        self.host_walk_spans += 1
+        return self._pack_on_host(bam_handler, span, batch, None, long_cigars)
+
+    def fetch(self, bam_handler, contig, starts, stops, include_supplementary, min_mapq, device_inflate, laps, lap_resident,
+              long_cigars=False, device_pack=False):
+        """A group's reads for the image drivers: pack_device where the device inflate is on and takes the batch, else pack
+        -> (resident, n_done, region_pairs, counts); resident: for encode(..., resident=True) / PolishChain.run.  n_done 0:
+        the first region's reads outgrow the arena (pack's -7) and it has to take the driver's host form.  laps["bam_pack"]
+        gets the time of a fetch that ended in pack, and with lap_resident that of one that stayed on the device too."""
+        t0 = time.perf_counter()
+        on_device = self.pack_device(bam_handler, contig, starts, stops, include_supplementary, min_mapq, laps=laps,
+                                     long_cigars=long_cigars, device_pack=device_pack) if device_inflate else None
+        if on_device is not None:
+            if lap_resident:
+                _lap(laps, "bam_pack", t0)
+            return (True,) + on_device
+        n_done, region_pairs, counts = 0, None, None
+        try:
+            n_done, region_pairs, counts = self.pack(bam_handler, contig, starts, stops, include_supplementary, min_mapq)
+        except Exception as err:
+            if getattr(err, "code", 0) != -7:
+                raise
+        _lap(laps, "bam_pack", t0)
+        return False, n_done, region_pairs, counts
 
     def encode(self, regions, references, region_pairs, counts, params, candidate_regions, candidate_window_size=32, feature_size=26,
                want_int32=False, resident=False, sampling=None):
@@ -621,6 +665,64 @@ class PackedEncoder(object):
         _lib.check(self.lib.pa_encoder_region_reads(self.enc, live.ctypes.data, n))
         self.last = batch
         return batch.results(want_int32), live[:n]
+
+
+def adjacent_run(intervals, g0, batch, slack):
+    """-> g1: intervals[g0:g1] is what one fetch of an image driver takes -- at most `batch` ADJACENT intervals (contig, start,
+    end) of one contig, ascending: each starts no earlier than the one before it and at most `slack` bases behind its end, and
+    ends no earlier.  (The packer walks every record between the first and the last region of a call: a group must not bridge
+    the gap to the worker's next run of intervals.)"""
+    g1 = g0 + 1
+    while (g1 < len(intervals) and g1 - g0 < batch and intervals[g1][0] == intervals[g0][0]
+           and intervals[g1 - 1][1] <= intervals[g1][1] <= intervals[g1 - 1][2] + slack
+           and intervals[g1][2] >= intervals[g1 - 1][2]):
+        g1 += 1
+    return g1
+
+
+_STATS_LOCK = threading.Lock()
+
+
+def merge_stats(stats, mine):
+    """A worker's stage times and counts added to the dict its caller shares among the workers (None: nobody asked)."""
+    if stats is not None:
+        with _STATS_LOCK:
+            for key, v in mine.items():
+                stats[key] = stats.get(key, 0.0) + v
+
+
+@contextlib.contextmanager
+def worker_counters(enc, mine, release_on_error, inflate_figures=False, candidates=False):
+    """Around an image worker's loop over its groups: what the worker's PackedEncoder counted meanwhile -- intervals sampled
+    down on the device, reads kept with their CIGAR in the CG tag -- is added to `mine`, the handle's switches are cleared and
+    it goes back to the pool.  release_on_error: also when the loop raises (the polish driver; the variant driver leaves a
+    handle that failed out of the pool).  inflate_figures: the inflate kernels' time and bytes go into `mine` as well (the
+    variant driver's stage times have the two keys, the polish driver's do not); they are reset either way.  candidates: the
+    handle enumerates candidates where PEPPER_AMD_DEVICE_CANDIDATES says, and its calls are counted by where they ran."""
+    sampled_before, long_before = enc.sampled()[0], enc.long_cigar_reads
+    if candidates:
+        enc.set_device_candidates(_lib.device_candidates())
+        calls_before = enc.candidate_calls()
+    failed = True
+    try:
+        yield
+        failed = False
+    finally:
+        if not failed or release_on_error:
+            if inflate_figures and enc.inflated_bytes:
+                mine["inflate_kernel"] = mine.get("inflate_kernel", 0.0) + enc.inflate_ms / 1e3
+                mine["inflated_bytes"] = mine.get("inflated_bytes", 0.0) + enc.inflated_bytes
+            enc.inflate_ms, enc.inflated_bytes = 0.0, 0
+            mine["sampled_on_device"] += enc.sampled()[0] - sampled_before
+            mine["long_cigar_reads_on_device"] += enc.long_cigar_reads - long_before
+            if candidates:
+                calls = enc.candidate_calls()
+                mine["device_enumerated_calls"] += calls[0] - calls_before[0]
+                mine["host_enumerated_calls"] += calls[1] - calls_before[1]
+            enc.set_sampling(None)
+            if candidates:
+                enc.set_device_candidates(False)
+            enc.release()
 
 
 def generate_summary_arrays_batch(generators, reads_list, min_snp_baseq, min_indel_baseq, snp_freq_threshold,
