@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "dec_frag16.h"
 #include "kernels.h"
 
 namespace {
@@ -435,8 +436,18 @@ int build_rec_layer(ModelBase* m, const StateDict& sd, const std::string& prefix
         if (int rc = pack_upload(out.w_hh_h2, none, 0)) return rc;
         if (K <= KXh2)
             if (int rc = pack_upload(out.w_cat_h2, wih_x, KXh2, true)) return rc;
-        if (K == 2 * H)
+        if (K == 2 * H && G == 4) {
+            // the fused LSTM decoder contracts on 16x16x32 tiles: its own fragment order (dec_frag16.h)
+            for (int d = 0; d < 2; ++d)
+                if (!fits_f16(whh_x[d], (int64_t)G * H * H) || !fits_f16(wih_x[d], (int64_t)G * H * K))
+                    return fail(PA_ERR_INVALID, "decoder weight not representable in f16 range");
+            std::vector<uint32_t> hp(pa_dec16::words(H, K));
+            pa_dec16::pack(whh_x, wih_x, H, K, hp.data());
+            out.w_cat_dec_h2 = m->new_buf();
+            if (int rc = upload(out.w_cat_dec_h2, hp)) return rc;
+        } else if (K == 2 * H) {
             if (int rc = pack_upload(out.w_cat_dec_h2, wih_x, K)) return rc;
+        }
         if (G == 3 && H == 128) {
             std::vector<uint32_t> hp(pa::gru_small_weights_h2_words(H));
             pa::pack_gru_small_weights_h2(whh_x, H, hp.data());

@@ -73,8 +73,8 @@ int lstm_split_resident_workgroups(int ntw);
 hipError_t launch_lstm_rec_h2_split(int H, const float* Xp, int ldx, const void* Wp, void* Y, int ldy, int B, int T, void* exch,
                                     void* counters, int* failed, hipStream_t stream, int sabotage = 0);
 
-// LSTM layer fed by an h2 layer output Xh [B*T, 2H]: projection contracted inside the step loop (weights packed
-// with pack_rec_weights_h2(..., F = 2H, KX = 2H); bias = b_ih + b_hh).
+// LSTM layer fed by an h2 layer output Xh [B*T, 2H]: projection contracted inside the step loop on 16x16x32 tiles (weights
+// packed with pa_dec16::pack(whh, wih, H, 2H, ...) of dec_frag16.h; bias = b_ih + b_hh).
 hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias, const void* Wp, void* Y, int ldy, int B,
                               int T, hipStream_t stream, bool small = false);   // small: 32-row workgroups
 // GRU (H = 128) counterpart; arguments as launch_gru_rec / launch_gru_rec_fused, Y in h2 format.

@@ -42,19 +42,12 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 
 // The packed weights, the bias and Xp arrive pre-multiplied per gate row by -log2(e) (i, f, o) or
 // +2 log2(e) (g), so the accumulators ARE the exp2 arguments of sigmoid / tanh (api.hip build_rec_layer).
-// XG (decoder layers): the layer input x_t is the previous layer's output, an h2 tensor Xh [B*T, KX]; its
-// projection is contracted inside the step loop (K = H + KX).  No projection GEMM, no Xp round trip (4.4 GB
-// written + read per 16384 windows).  The x slab of a step (64 rows x 2 KB = 128 KB) does not fit in LDS next to
-// h and c, so it streams through a two-slot LDS ring, two k steps (64 rows x 128 B) per slot: every thread
-// loads one 16-byte chunk of iteration j+2 into a staging register while iteration j is contracted, writes it
-// to the free slot, and one LDS barrier per iteration publishes it; all waves then read their x fragments from
-// LDS like they read h.  (First form of this kernel: every wave fetched its x fragments straight from global
-// memory -- 8x redundant through L1, +0.7 ms per 16384 windows, and 4 MB of x per step per XCD pushed the
-// weights out of L2.)
-// SAUX: cache policy of the streams that pass through once -- the x slab loads of the XG form and the y stores (2 = nt:
-// the lines are not kept in the XCD's L2, which has to hold this direction's 3 MB of weight fragments that every
-// workgroup re-reads every step; 0 = default policy, what the forms seeded from Xp are launched with).  Measured r02
-// (16384 windows, device-resident pass): 2.566 -> 2.596 M windows/s with nt on the once-through streams.
+// XG (decoder layers, whose input x_t is the previous layer's h2 output Xh [B*T, KX]): a step loop of its own,
+// lstm_dec_h2_body below; this kernel is only its entry.
+// SAUX: cache policy of the stream that passes through once -- the y stores (2 = nt: the lines are not kept in the XCD's
+// L2, which has to hold this direction's weight fragments that every workgroup re-reads every step; 0 = default policy,
+// what the forms seeded from Xp are launched with).  Measured r02 (16384 windows, device-resident pass): 2.566 -> 2.596 M
+// windows/s with nt on the once-through streams.
 // BC (fused int8 first layer with F < KX): the bias lives in column H + F of the packed weights and x carries a constant
 // 1.0 there, so the first MFMA of a step starts every accumulator from the inline constant 0: no bias loads and no 128
 // register moves per step in the gate phase, which is bound by VALU issue (two waves per SIMD, ~1300 instructions each).
@@ -63,6 +56,10 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 // 16 MTILES elements per lane -- whatever the number of workgroups, so a call of a few hundred windows, which fills a small
 // part of the chip either way, takes half the time per step with 32-row workgroups (twice as many of them, each still
 // streaming the direction's weight fragments from L2).  Big calls keep 64 rows: half the weight stream per window.
+template <int MTILES>
+PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
+                             int B, int T, unsigned long long* __restrict__ dbg, const uint32_t* __restrict__ Xh, int ldxh);
+
 template <int H, int KX, bool XG = false, int SAUX = 0, bool BC = false, int MTILES = 2>
 __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float* __restrict__ Xp, int ldx,
                                                                      const int8_t* __restrict__ Xi, int F,
@@ -71,11 +68,15 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                                                                      uint32_t* __restrict__ Y, int ldy, int B, int T,
                                                                      unsigned long long* __restrict__ dbg,
                                                                      const uint32_t* __restrict__ Xh = nullptr, int ldxh = 0) {
+    if constexpr (XG) {
+        static_assert(H == 256 && KX == 512 && SAUX == 2 && !BC, "the fused decoder has one shape");
+        lstm_dec_h2_body<MTILES>(bias, Wp, Y, ldy, B, T, dbg, Xh, ldxh);
+        return;
+    }
     constexpr int KT = H + KX, KS = KT / 16, KSH = H / 16, NT = H / 32, NW = H / 32;
     constexpr int MTL = 32 * MTILES;             // rows of this workgroup
     static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
-    constexpr int KL = XG ? H : KT;              // columns kept in the LDS rows
-    constexpr int ROWB = KL * 4 + 16;            // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
+    constexpr int ROWB = KT * 4 + 16;            // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
     constexpr int ROWD = ROWB / 4;               // in dwords
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, then c (f32)
     static_assert(KS % 2 == 0, "the weight prefetch assumes an even number of k steps");
@@ -92,9 +93,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 
     float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][r][lane]
     for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
-    // XG: x ring after the cell state: 2 slots x [MTL rows][XRD dwords] (128 B of x + 16 B pad per row)
-    constexpr int XRD = 36, XSLOT = MTL * XRD, NXI = XG ? KX / 32 : 0;   // NXI iterations of two k steps
-    uint32_t* xring = lds + MTL * ROWD + NW * MTILES * 16 * 64;
 
     f32x16 acc[MTILES][4];   // [row tile][gate]
 
@@ -133,7 +131,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 
     // fused only: x_t (int8, exact in f16) -> hi halves of LDS columns [H, H+KX); lo halves stay 0.
     // One thread per pair of features: 64 rows x KX/2 pairs over 512 threads.
-    constexpr bool XI8 = KX > 0 && !XG;
+    constexpr bool XI8 = KX > 0;
     constexpr int XN = XI8 ? (MTL * KX / 2) / (NW * 64) : 1;
     unsigned xv[XN];
     auto x_load = [&](int t) {
@@ -163,22 +161,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
             }
         }
     };
-    // XG staging: thread -> (row = tid / 8, 16-byte chunk c = tid % 8) of an iteration's MTL x 128 B slab.  With 32 rows
-    // (MTILES = 1) only waves 0-3 stage (a wave covers 8 rows: the test is uniform over the wave); every wave reads the ring.
-    const bool xg_stager = XG && tid < MTL * 8;
-    const __amdgpu_buffer_rsrc_t xgrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(XG ? Xh + (size_t)b0 * T * ldxh : Wp), 0, 0x7fffffff, 0x00020000);
-    const unsigned xg_off = XG ? ((unsigned)((tid >> 3) * T) * ldxh) * 4u + (tid & 7) * 16u : 0u;
-    uint32_t* xst_dst = xring + (tid >> 3) * XRD + (tid & 7) * 4;
-    u32x4 xstage[2];
-    auto xg_load = [&](int j, int t) {      // iteration j of step t -> staging register j & 1
-        if (MTILES == 2 || xg_stager)
-            xstage[j & 1] = __builtin_amdgcn_raw_buffer_load_b128(xgrs, xg_off, ((unsigned)t * ldxh) * 4u + (unsigned)j * 128u, SAUX);
-    };
-    auto xg_store = [&](int j) {
-        if (MTILES == 2 || xg_stager) *reinterpret_cast<u32x4*>(xst_dst + (j & 1) * XSLOT) = xstage[j & 1];
-    };
-
     struct Frag { h8 b[4][2], a[MTILES][2]; };     // [gate][hi, lo], [row tile][hi, lo]
     const uint32_t* arow = lds + li * ROWD + hf * 8;
     auto load_b = [&](int s, Frag& fr) {
@@ -190,16 +172,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                                                          wrs, woff, (unsigned)((g * NT * KS + s) * 2 + hl) * 1024u, 0));
     };
     auto load_a = [&](int s, Frag& fr, int) {
-        if (XG && s >= KSH) {
-            const int xs = s - KSH;
-            const uint32_t* src = xring + ((xs >> 1) & 1) * XSLOT + li * XRD + ((xs & 1) * 2 + hf) * 8;
-#pragma unroll
-            for (int m = 0; m < MTILES; ++m) {
-                fr.a[m][0] = *reinterpret_cast<const h8*>(src + m * 32 * XRD);
-                fr.a[m][1] = *reinterpret_cast<const h8*>(src + m * 32 * XRD + 4);
-            }
-            return;
-        }
 #pragma unroll
         for (int m = 0; m < MTILES; ++m) {
             fr.a[m][0] = *reinterpret_cast<const h8*>(arow + m * 32 * ROWD + s * 16);
@@ -255,17 +227,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const int p = s & 1;
-                if (XG) {
-                    // iteration j = k steps (KSH + 2j, KSH + 2j + 1); its slab is loaded at step 2j + 9 (j = 0, 1: steps
-                    // 0, 1), written to slot j & 1 at step 2j + 13 (j = 0: step 8) and published by the barrier at the
-                    // start of step 2j + 15, the step that pre-reads its first fragments
-                    if (s == 0) xg_load(0, t);
-                    if (s == 1) xg_load(1, t);
-                    if (s >= KSH - 1 && ((s - (KSH - 1)) & 1) == 0 && (s - (KSH - 1)) / 2 < NXI) lds_barrier();
-                    if (s == 8) xg_store(0);
-                    if (s >= 15 && ((s - 13) & 1) == 0 && (s - 13) / 2 < NXI) xg_store((s - 13) / 2);
-                    if (s >= 13 && ((s - 9) & 1) == 0 && (s - 9) / 2 < NXI) xg_load((s - 9) / 2, t);
-                }
                 if (s + 1 < KS) { load_b(s + 1, ring[p ^ 1]); load_a(s + 1, ring[p ^ 1], t); }
                 else load_b(0, ring[p ^ 1]);            // KS is even: ring[p ^ 1] == ring[0]
                 if (s >= 1 && s <= YC) yc_write(s - 1, tp, ycv);
@@ -282,23 +243,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                             acc[m][g] = mfma_h(ring[p].a[m][term == 0 ? 1 : 0], ring[p].b[g][term == 1 ? 1 : 0],
                                                fresh ? f32x16{} : acc[m][g]);
                 }
-                if (XG && s + 1 < KS && s > YC) {
-#pragma unroll
-                    for (int q = 0; q < 8; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);   // 2 MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);   // 1 VMEM read (B fragment)
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // 1 DS read (A fragment: h rows or x ring)
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);       // x slab chunk -> ring
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);       // x slab chunk of a later iteration
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                } else if (MTILES == 1 && s + 1 < KS) {
+                if (MTILES == 1 && s + 1 < KS) {
                     // 12 MFMAs per k step: 8 weight fragments, 2 A fragments, the y copy's read / write in the first steps
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
@@ -410,6 +355,253 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
         if (step + 1 < T) x_store();
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
         lds_barrier();                    // h_t (and x_{t+1}) visible
+    }
+    {
+        const int tl = dir ? 0 : T - 1;
+#pragma unroll
+        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The fused decoder's step loop: lstm_rec_h2_kernel's decomposition (workgroup = 64 or 32 batch rows x one direction, wave u
+// owns hidden units [32u, 32u+32) of all four gates, MFMA phase | barrier | gate phase | barrier), the same h2 row image in
+// LDS (so the same y), the same three-term product (lo.hi, hi.lo, hi.hi per k step, k ascending per accumulator) -- on
+// v_mfma_f32_16x16x32_f16.  The chip holds a higher clock on that shape (tools/microbench/mfma_shape.hip,
+// profiles/mfma_shape_probe.txt: 1.08 x the 32x32x16 loop by wall with this kernel's operand traffic, random data).
+//
+// The layer input x_t is the previous layer's output, an h2 tensor Xh [B*T, KX]; its projection is contracted inside the
+// step loop (K = H + KX = 768): no projection GEMM, no Xp round trip.  The x slab of a step (64 rows x 2 KB) does not fit in
+// LDS next to h and c, so it streams through a two-slot LDS ring, ONE k step (rows x 128 B) per slot: every staging thread
+// loads one 16-byte chunk of iteration j into a staging register a k step before it writes it to the free slot, and one
+// LDS barrier per iteration publishes it; all waves then read their x fragments from LDS like they read h.  The once-through
+// streams (x slab loads, y stores) carry the nt cache policy: the XCD's L2 has to keep this direction's 3 MB of weight
+// fragments, which every workgroup re-reads every step.
+//
+// Tiles: a wave's 64 x 128 outputs are acc[row tile of 16][gate][column tile of 16] (f32x4: lane l holds column l & 15, rows
+// 4 (l >> 4) + r); i, f, g, o of one (row, unit) share lane and register index, so the gate phase stays lane-local.
+// k steps: 32 wide, 8 for h and 16 for x.  A lane's A chunk is the 16-byte hi (then lo) slot at s * 128 + (l >> 4) * 32 of
+// its row; sixteen rows at odd 16-byte strides (65 slots per h row, 9 per ring row) keep ds_read_b128 conflict-free.
+// Registers: 128 accumulators, the A fragments of one k step (single-buffered: a row tile's are re-read for the next k step
+// right after their last use, 36 MFMAs before they are needed), and a B ring of two stages of one GATE PAIR each (8
+// fragments, dec_frag16.h); the stage of (i, f) is refilled while (g, o) is contracted and the other way round.  A k step is
+// two phases of 12 MFMAs per row tile in the order [row tile][column tile][term][gate of the pair]; every memory
+// instruction sits alone in an MFMA gap.  The k loop stays a LOOP over bodies of one k step (one body per kind of step:
+// unrolled over all 24, the compiler renames the accumulators from MFMA to MFMA and spills).
+// Ring schedule (iteration j = k step 8 + j): loaded into the one staging register early in the second phase of step j + 6
+// (93 MFMAs before it is needed), written to slot j & 1 at the end of the first phase of step j + 7, published by the barrier
+// that opens the second phase of that step, whose A re-reads are the first to touch it.  16 barriers per time step.
+// MTILES = 1 is the small-call schedule (32-row workgroups, lstm_rec_h2_kernel explains why); both come from this one
+// template, so a row's chain of products and sums is the same in both.
+// what a k step does beside its MFMAs and its B loads: FRESH the first products start the accumulators; Y (Y2) a y copy pass
+// (and the last pass); XR the ring work: 0 nothing, 1 load the first iteration, 2 write the staged iteration, which this
+// step's barrier publishes, and load the next; AN the next k step's A fragments come from 0 nowhere, 1 the h rows, 2 the ring
+template <bool FRESH_, bool Y_, bool Y2_, int XR_, int AN_>
+struct DecStep {
+    static constexpr bool FRESH = FRESH_, Y = Y_, Y2 = Y2_;
+    static constexpr int XR = XR_, AN = AN_;
+};
+
+template <int MTILES>
+PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
+                             int B, int T, unsigned long long* __restrict__ dbg, const uint32_t* __restrict__ Xh, int ldxh) {
+    constexpr int H = 256, KX = 512, KS = (H + KX) / 32, KSH = H / 32, NW = H / 32, SAUX = 2;
+    constexpr int MTL = 32 * MTILES, RT = 2 * MTILES;   // rows, row tiles of 16
+    static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
+    constexpr int ROWB = H * 4 + 16, ROWD = ROWB / 4;   // bytes per LDS row: h2 image of h + 16 pad (odd 16-B count)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, c (f32), x ring
+    static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
+
+    int dir, btile;
+    decode_block(blockIdx.x, dir, btile);
+    const int b0 = btile * MTL;
+    if (b0 >= B) return;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lq = lane >> 4;
+
+    float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][column tile][r][lane]
+    for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
+    constexpr int XRD = 36, XSLOT = MTL * XRD;           // ring: 2 slots x [MTL rows][128 B of x + 16 B pad]
+    uint32_t* xring = lds + MTL * ROWD + NW * MTILES * 16 * 64;
+
+    f32x4 acc[RT][4][2];   // [row tile][gate][column tile]
+
+    const size_t urow = (size_t)b0 * T;
+    const __amdgpu_buffer_rsrc_t brs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias + dir * 4 * H + 32 * u), 0, 0x7fffffff, 0x00020000);
+    // fragment (g, column tile c, k step s, hi/lo) of this wave: byte ((((g * 16 + 2u + c) * KS + s) * 2 + hl) * 1024 + lane * 16
+    // of the direction's block (dec_frag16.h); the wave's own term is part of the descriptor's base
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * 16) + 2 * u) * KS * 512), 0, 0x7fffffff, 0x00020000);
+    const unsigned woff = lane * 16u;
+
+    // x staging: thread -> (row = tid / 8, 16-byte chunk tid % 8) of an iteration's MTL x 128 B slab.  With 32 rows only
+    // waves 0-3 stage (a wave covers 8 rows: the test is uniform over the wave); every wave reads the ring.
+    const bool xg_stager = tid < MTL * 8;
+    const __amdgpu_buffer_rsrc_t xgrs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(Xh + (size_t)b0 * T * ldxh), 0, 0x7fffffff, 0x00020000);
+    const unsigned xg_off = ((unsigned)((tid >> 3) * T) * ldxh) * 4u + (tid & 7) * 16u;
+    uint32_t* xst_dst = xring + (tid >> 3) * XRD + (tid & 7) * 4;
+    u32x4 xstage = {0, 0, 0, 0};
+    auto xg_load = [&](int j, int t) {               // iteration j of step t -> the staging register
+        if (MTILES == 2 || xg_stager)
+            xstage = __builtin_amdgcn_raw_buffer_load_b128(xgrs, xg_off, ((unsigned)t * ldxh) * 4u + (unsigned)j * 128u, SAUX);
+    };
+    auto xg_store = [&](int slot) {                  // the staging register -> ring slot
+        if (MTILES == 2 || xg_stager) *reinterpret_cast<u32x4*>(xst_dst + slot * XSLOT) = xstage;
+    };
+
+    int once = 1;
+    asm volatile("" : "+s"(once));
+    h8 a[RT][2];            // [row tile][hi, lo] of the current k step
+    h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
+    const uint32_t* arow = lds + lr * ROWD + lq * 8;
+    const uint32_t* xrow = xring + lr * XRD + lq * 8;
+    auto load_b = [&](int s, int gp, int idx) {      // idx: in the order the MFMAs first need them
+        const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
+        b[gp][g2][c][hl] = __builtin_bit_cast(
+            h8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * KS + s) * 2 + hl) * 1024u, 0));
+    };
+    auto load_a_h = [&](int s, int m, int hl) { a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * ROWD + s * 32 + hl * 4); };
+    auto load_a_x = [&](int slot, int m, int hl) {
+        a[m][hl] = *reinterpret_cast<const h8*>(xrow + slot * XSLOT + m * 16 * XRD + hl * 4);
+    };
+
+    // y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is
+    constexpr int CPR = H / 4;                                // 16-byte chunks per row
+    constexpr int YROWS = (NW * 64) / CPR;                    // rows per pass (8)
+    constexpr int YC = MTL / YROWS;                           // passes (8 or 4): one per k step from step 0
+    const int yc_row = tid / CPR, yc_c = tid % CPR;
+    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
+    const __amdgpu_buffer_rsrc_t ycrs =
+        __builtin_amdgcn_make_buffer_rsrc(Y + urow * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
+    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
+    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
+    auto yc_write = [&](int j, int tp, u32x4 v) {
+        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, SAUX);
+    };
+
+    // gate-phase h write: element (row, col) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2, lo half 16 bytes later
+    // (h2_store16); the lane's element (m, c, r) is row 16m + 4 lq + r, col 32u + 16c + lr
+    const int hcol = 32 * u + lr;
+    unsigned short* hl_dst = reinterpret_cast<unsigned short*>(lds + 4 * lq * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
+
+    // The weights do not depend on the step: the first stage of k step 0 is requested during the last k step of the
+    // previous time step and flies under the gate phase (b[0] stays live across it).
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < 8; ++i) load_b(0, 0, i);
+    __syncthreads();
+
+    for (int step = 0; step < T; ++step) {
+        const int t = dir ? T - 1 - step : step;
+        const bool stamp = dbg != nullptr && blockIdx.x == 8 && lane == 0;
+        if (stamp) dbg[(u * 80 + 2 * step) * 2] = __builtin_amdgcn_s_memtime();
+        // ---------------- MFMA phase ----------------
+        {
+            const int tp = step > 0 ? (dir ? t + 1 : t - 1) : t;   // time index of h_{s-1} (step 0: zeros, rewritten later)
+            u32x4 ycv = {0, 0, 0, 0}, ycv2 = {0, 0, 0, 0};
+            constexpr int NM = RT * 12;                            // MFMAs of a phase (one gate pair of one k step)
+            auto kstep = [&](int s, auto cfg) {
+                using C = decltype(cfg);
+                const int sn = C::AN == 0 ? 0 : s + 1, slot = (s - KSH + 1) & 1;     // slot of iteration s + 1 - KSH
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) {
+                    if (gp == 1 && C::XR == 2) lds_barrier();
+#pragma unroll
+                    for (int i = 0; i < NM; ++i) {
+                        const int m = i / 12, c = (i % 12) / 6, term = (i % 6) >> 1, g2 = i & 1, g = 2 * gp + g2;
+                        // the first product into every accumulator of a time step starts from the inline constant 0; the
+                        // biases of the lane's columns are added in the gate phase
+                        acc[m][g][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m][term == 0 ? 1 : 0], b[gp][g2][c][term == 1 ? 1 : 0],
+                                                                              C::FRESH && term == 0 ? f32x4{} : acc[m][g][c], 0, 0, 0);
+                        // next stage's 8 B fragments (the other gate pair of this k step, or the first of the next) early in
+                        // the phase: with 48 MFMAs the last of them has 26 to arrive
+                        if (MTILES == 2 ? (i < 24 && i % 3 == 1) : i < 8) load_b(gp == 0 ? s : sn, gp ^ 1, MTILES == 2 ? i / 3 : i);
+                        // second gate pair: a row tile's A fragments of the next k step, right after their last use
+                        if (gp == 1 && C::AN != 0 && (i % 12 == 9 || i % 12 == 11)) {
+                            if (C::AN == 1) load_a_h(sn, m, i % 12 == 9 ? 1 : 0);
+                            else load_a_x(slot, m, i % 12 == 9 ? 1 : 0);
+                        }
+                        if (C::Y && i == NM / 2 + 1) {
+                            if (gp == 0) ycv = yc_read(s);
+                            else yc_write(s, tp, ycv);
+                        }
+                        if (C::Y2 && i == NM / 2 + 4) {
+                            if (gp == 0) ycv2 = yc_read(YC - 1);
+                            else yc_write(YC - 1, tp, ycv2);
+                        }
+                        if (C::XR == 2 && gp == 0 && i == NM - 1) xg_store(slot);
+                        // (the last step of the ring has nothing left to load: it loads the last iteration again)
+                        if (C::XR != 0 && gp == 1 && i == (MTILES == 2 ? 2 : 10)) xg_load(s - 6 < KS - KSH ? s - 6 : KS - KSH - 1, t);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            };
+            // y copy passes: one per k step from step 0; step 0 also takes the eighth of the 64-row workgroup
+            constexpr bool Y2 = YC > 7;
+            constexpr int YL = YC < 6 ? YC : 6;
+#pragma unroll
+            for (int i = 0; i < 2 * RT; ++i) load_a_h(0, i >> 1, i & 1);
+            __builtin_amdgcn_sched_barrier(0);
+            // (`once` is 1: a body that stands alone is wrapped in a loop of one trip the compiler cannot see through.  As
+            // straight-line code its accumulators are renamed from MFMA to MFMA and spill; as a loop body they stay in place.)
+#pragma unroll 1
+            for (int r = 0; r < once; ++r) kstep(0, DecStep<true, true, Y2, 0, 1>{});
+#pragma unroll 1
+            for (int s = 1; s < YL; ++s) kstep(s, DecStep<false, true, false, 0, 1>{});
+#pragma unroll 1
+            for (int s = YL; s < 6; ++s) kstep(s, DecStep<false, false, false, 0, 1>{});
+#pragma unroll 1
+            for (int r = 0; r < once; ++r) kstep(6, DecStep<false, (YC > 6), false, 1, 1>{});
+#pragma unroll 1
+            for (int s = 7; s < KS - 1; ++s) kstep(s, DecStep<false, false, false, 2, 2>{});
+#pragma unroll 1
+            for (int r = 0; r < once; ++r) kstep(KS - 1, DecStep<false, false, false, 0, 0>{});
+        }
+        // the lane's eight biases, re-read every step (in flight across the barrier) rather than held through the MFMA phase
+        float cb[4][2];
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+                cb[g][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, lr * 4u, (unsigned)(g * H + 16 * c) * 4u, 0));
+        if (stamp) dbg[(u * 80 + 2 * step) * 2 + 1] = __builtin_amdgcn_s_memtime();
+
+        lds_barrier();                    // every wave has finished reading h_{t-1}
+        if (stamp) dbg[(u * 80 + 2 * step + 1) * 2] = __builtin_amdgcn_s_memtime();
+
+        // ---------------- gate phase (lstm_rec_h2_kernel's, on this kernel's (row, column) <-> (lane, register) map) ----------------
+#pragma unroll
+        for (int m = 0; m < RT; ++m)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    typedef float f32x2 __attribute__((ext_vector_type(2)));
+                    const f32x2 one = {1.0f, 1.0f};
+                    f32x2 ai = {acc[m][0][c][e], acc[m][0][c][e + 1]}, af = {acc[m][1][c][e], acc[m][1][c][e + 1]},
+                          ag = {acc[m][2][c][e], acc[m][2][c][e + 1]}, ao = {acc[m][3][c][e], acc[m][3][c][e + 1]};
+                    ai += cb[0][c]; af += cb[1][c]; ag += cb[2][c]; ao += cb[3][c];
+                    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
+                    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
+                    const f32x2 ig = rcp(one + ex2(ai));
+                    const f32x2 fg = rcp(one + ex2(af));
+                    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
+                    const f32x2 og = rcp(one + ex2(ao));
+                    const int ci = (m * 8 + c * 4 + e) * 64;
+                    const f32x2 cold = {cs[ci], cs[ci + 64]};
+                    const f32x2 cn = fg * cold + ig * gg;
+                    cs[ci] = cn.x;
+                    cs[ci + 64] = cn.y;
+                    const f32x2 hv2 = og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) h2_store16(hl_dst + (16 * m + e + k) * ROWD * 2 + c * 32, k ? hv2.y : hv2.x);
+                }
+        if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
+        lds_barrier();                    // h_t visible
     }
     {
         const int tl = dir ? 0 : T - 1;

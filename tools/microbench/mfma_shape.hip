@@ -1,0 +1,303 @@
+// Debug aid (not product): does the chip hold a higher clock on v_mfma_f32_16x16x32_f16 than on v_mfma_f32_32x32x16_f16
+// in the fused LSTM decoder's step loop (rnn_h2.hip: lstm_rec_h2_kernel<256, 512, XG>)?
+//   hipcc --offload-arch=gfx950 -O3 -o tools/microbench/mfma_shape tools/microbench/mfma_shape.hip && tools/microbench/mfma_shape
+// One workgroup per CU, 8 waves (two per SIMD), each with the decoder's wave tile: 64 rows x 128 columns (32 units of four
+// gates), 128 accumulator registers.  A k loop of three-term split-f16 products (lo.hi, hi.lo, hi.hi) in two bodies with the
+// same MFMA work:
+//   S32: 24 x v_mfma_f32_32x32x16_f16 per 16-wide k step   (acc[row tile 0..1][gate] of f32x16)
+//   S16: 96 x v_mfma_f32_16x16x32_f16 per 32-wide k step   (acc[row tile 0..3][gate][column tile 0..1] of f32x4)
+// each in two variants:
+//   reg: operands loaded once and held in registers;
+//   mem: as in the decoder -- A fragments by ds_read_b128 from h2 rows in LDS (1040-byte stride), B fragments by
+//        raw_buffer_load_b128 from a 3 MB block that every workgroup re-reads every 48 k16 (24 k32) steps, one memory
+//        instruction per MFMA gap.  S32 keeps the decoder's 2-deep ring of whole k steps, with the 48 k steps unrolled as the
+//        decoder has them ("mem-u") and as a loop of two ("mem"); S16 keeps a B ring of two stages of one gate pair each (8
+//        fragments) and single-buffered A fragments that are re-read right after their last use, its k loop a loop of one
+//        k32 step (unrolled over the 24 steps the compiler renames the accumulators from MFMA to MFMA, needs s_nops before
+//        the loads that land in registers of MFMAs in flight, and spills).
+// On random finite data and on zeros.  Reports wall TFLOP/s (hipEvents around back-to-back launches) and the in-kernel clock
+// = delta s_memtime / delta s_memrealtime x 100 MHz, stamped once around the loop (median over workgroups), after at least
+// 2 s of back-to-back launches of the same kernel on the same data.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <chrono>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+
+#define CHECK(x)                                                                                              \
+    do {                                                                                                      \
+        hipError_t e_ = (x);                                                                                  \
+        if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(1); }           \
+    } while (0)
+
+constexpr int ROWB = 1040, ROWD = ROWB / 4;        // h2 row of 256 units: 32 slots of (16 B hi, 16 B lo) + 16 B pad
+constexpr int LDS_BYTES = 64 * ROWB;
+constexpr int K16 = 48;                            // k16 steps of one decoder time step (K = 256 + 512)
+constexpr unsigned W_BYTES = 4u * 8u * K16 * 2u * 1024u;   // one direction's weight fragments: 3 MB
+
+#define GAP() __builtin_amdgcn_sched_barrier(0)
+
+template <int SHAPE, bool MEM, bool ROLLED = false>
+__global__ __launch_bounds__(512, 1) void k(int nrep, const uint32_t* __restrict__ Aimg, const uint32_t* __restrict__ Wp,
+                                            float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < LDS_BYTES / 16; i += 512)
+        reinterpret_cast<u32x4*>(lds)[i] = reinterpret_cast<const u32x4*>(Aimg)[i];
+    __syncthreads();
+    const unsigned woff = lane * 16u;
+    unsigned long long t0, t1, r0, r1;
+    float sum = 0.0f;
+
+    if (SHAPE == 32) {
+        // fragment (g, s, hi/lo) of wave u: byte (((g * 8 + u) * 48 + s) * 2 + hl) * 1024 + lane * 16
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint32_t*>(Wp + (size_t)u * K16 * 512), 0, (int)(W_BYTES - (unsigned)u * K16 * 2048u), 0x00020000);
+        const uint32_t* arow = lds + (lane & 31) * ROWD + (lane >> 5) * 8;
+        struct Frag { h8 b[4][2], a[2][2]; };
+        Frag ring[2];
+        auto load_b = [&](int s, Frag& fr, int g, int hl) {
+            fr.b[g][hl] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                     wrs, woff, (unsigned)((g * 8 * K16 + s) * 2 + hl) * 1024u, 0));
+        };
+        auto load_a = [&](int s, Frag& fr, int m, int hl) {
+            fr.a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 32 * ROWD + (s & 15) * 16 + hl * 4);
+        };
+        f32x16 acc[2][4] = {};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_b(0, ring[0], i >> 1, i & 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) load_a(0, ring[0], i >> 1, i & 1);
+        GAP();
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+        auto kstep = [&](int s, int sn, int p) {
+#pragma unroll
+            for (int i = 0; i < 24; ++i) {
+                const int term = i >> 3, g = (i & 7) >> 1, m = i & 1;
+                acc[m][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring[p].a[m][term == 0 ? 1 : 0],
+                                                                   ring[p].b[g][term == 1 ? 1 : 0], acc[m][g], 0, 0, 0);
+                if (i < 16 && (i & 1)) load_b(sn, ring[p ^ 1], (i >> 1) >> 1, (i >> 1) & 1);
+                if (i >= 16 && i < 20) load_a(sn, ring[p ^ 1], (i - 16) >> 1, (i - 16) & 1);
+                GAP();
+            }
+        };
+        if (MEM && ROLLED) {
+            // the same stream with the k loop left as a loop of two k steps (the ring's two slots)
+            for (int it = 0; it < nrep; ++it) {
+#pragma unroll 1
+                for (int s = 0; s < K16; s += 2) {
+                    kstep(s, s + 1, 0);
+                    kstep(s + 1, s + 2 < K16 ? s + 2 : 0, 1);
+                }
+            }
+        } else if (MEM) {
+            // the decoder's form: all 48 k steps of a time step unrolled
+            for (int it = 0; it < nrep; ++it) {
+#pragma unroll
+                for (int s = 0; s < K16; ++s) kstep(s, s + 1 < K16 ? s + 1 : 0, s & 1);
+            }
+        } else {
+            for (int it = 0; it < nrep * (K16 / 2); ++it) {
+#pragma unroll
+                for (int i = 0; i < 48; ++i) {
+                    const int term = (i % 24) >> 3, g = (i & 7) >> 1, m = i & 1;
+                    acc[m][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring[0].a[m][term == 0 ? 1 : 0],
+                                                                       ring[0].b[g][term == 1 ? 1 : 0], acc[m][g], 0, 0, 0);
+                    GAP();
+                }
+            }
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        r1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sum += acc[m][g][r];
+    } else {
+        // fragment (g, column tile c, k32 step s, hi/lo) of wave u: byte ((((g * 16 + 2u + c) * 24 + s) * 2 + hl) * 1024 + lane * 16
+        constexpr int K32 = K16 / 2;
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint32_t*>(Wp + (size_t)u * 2 * K32 * 512), 0, (int)(W_BYTES - (unsigned)u * 2u * K32 * 2048u), 0x00020000);
+        // lane l: row l & 15 of a row tile, 16-byte hi (then lo) slot at s * 128 + (l >> 4) * 32 of the row
+        const uint32_t* arow = lds + (lane & 15) * ROWD + (lane >> 4) * 8;
+        h8 a[4][2];             // [row tile][hi, lo]
+        h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
+        auto load_b = [&](int s, int gp, int idx) {
+            const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;     // in the order the MFMAs first need them
+            b[gp][g2][c][hl] = __builtin_bit_cast(
+                h8, __builtin_amdgcn_raw_buffer_load_b128(
+                        wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * K32 + s) * 2 + hl) * 1024u, 0));
+        };
+        auto load_a = [&](int s, int m, int hl) {
+            a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * ROWD + (s & 7) * 32 + hl * 4);
+        };
+        f32x4 acc[4][4][2] = {};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_b(0, 0, i);
+        if (!MEM) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) load_b(0, 1, i);
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_a(0, i >> 1, i & 1);
+        GAP();
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+        if (MEM) {
+            for (int it = 0; it < nrep; ++it) {
+#pragma unroll 1
+                for (int s = 0; s < K32; ++s) {
+#pragma unroll
+                    for (int gp = 0; gp < 2; ++gp) {
+                        const int sn = s + 1 < K32 ? s + 1 : 0;
+#pragma unroll
+                        for (int i = 0; i < 48; ++i) {
+                            const int m = i / 12, c = (i % 12) / 6, term = (i % 6) >> 1, g2 = i & 1;
+                            acc[m][2 * gp + g2][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                                a[m][term == 0 ? 1 : 0], b[gp][g2][c][term == 1 ? 1 : 0], acc[m][2 * gp + g2][c], 0, 0, 0);
+                            // next stage's 8 B fragments (the other gate pair of this k step, or the first of the next) in
+                            // the first half of the phase: the last of them has 26 MFMAs to arrive
+                            if (i < 24 && i % 3 == 1) load_b(gp == 0 ? s : sn, gp ^ 1, i / 3);
+                            // second gate pair: a row tile's A fragments of the next k step, right after their last use
+                            if (gp == 1 && i % 12 == 9) load_a(sn, m, 1);
+                            if (gp == 1 && i % 12 == 11) load_a(sn, m, 0);
+                            GAP();
+                        }
+                    }
+                }
+            }
+        } else {
+            for (int it = 0; it < nrep * K32; ++it) {
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp)
+#pragma unroll
+                    for (int i = 0; i < 48; ++i) {
+                        const int m = i / 12, c = (i % 12) / 6, term = (i % 6) >> 1, g2 = i & 1;
+                        acc[m][2 * gp + g2][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                            a[m][term == 0 ? 1 : 0], b[gp][g2][c][term == 1 ? 1 : 0], acc[m][2 * gp + g2][c], 0, 0, 0);
+                        GAP();
+                    }
+            }
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        r1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) sum += acc[m][g][c][0] + acc[m][g][c][1] + acc[m][g][c][2] + acc[m][g][c][3];
+    }
+    out[blockIdx.x * 512 + tid] = sum;
+    if (tid == 0) {
+        stamps[blockIdx.x * 2] = t1 - t0;
+        stamps[blockIdx.x * 2 + 1] = r1 - r0;
+    }
+}
+
+static uint16_t f16_bits(_Float16 h) { uint16_t b; memcpy(&b, &h, 2); return b; }
+
+// nwords 32-byte h2 slots (8 values: 16 B hi, 16 B lo) of uniform values in [-scale, scale), or zeros
+static void fill_h2(uint16_t* dst, size_t nslots, bool random, float scale, unsigned& seed) {
+    for (size_t s = 0; s < nslots; ++s)
+        for (int e = 0; e < 8; ++e) {
+            seed = seed * 1664525u + 1013904223u;
+            const float v = random ? scale * ((float)(seed >> 8) * (2.0f / 16777216.0f) - 1.0f) : 0.0f;
+            const _Float16 hi = (_Float16)v, lo = (_Float16)(v - (float)hi);
+            dst[s * 16 + e] = f16_bits(hi);
+            dst[s * 16 + 8 + e] = f16_bits(lo);
+        }
+}
+
+struct Bufs { uint32_t *aimg, *w; float* out; unsigned long long* stamps; int ncu; };
+
+template <int SHAPE, bool MEM, bool ROLLED = false>
+void run(const Bufs& d, const char* data, int nrep) {
+    auto fn = k<SHAPE, MEM, ROLLED>;
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+    auto launch = [&]() { hipLaunchKernelGGL(fn, dim3(d.ncu), dim3(512), LDS_BYTES, 0, nrep, d.aimg, d.w, d.out, d.stamps); };
+    // at least 2 s of back-to-back launches before anything is read
+    const auto w0 = std::chrono::steady_clock::now();
+    int warm = 0;
+    do {
+        for (int i = 0; i < 8; ++i) launch();
+        CHECK(hipDeviceSynchronize());
+        warm += 8;
+    } while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 2.0);
+    constexpr int L = 40;
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    CHECK(hipEventRecord(e0, 0));
+    for (int i = 0; i < L; ++i) launch();
+    CHECK(hipEventRecord(e1, 0));
+    CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    std::vector<unsigned long long> st(2 * d.ncu);
+    CHECK(hipMemcpy(st.data(), d.stamps, st.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<double> ghz(d.ncu);
+    for (int i = 0; i < d.ncu; ++i) ghz[i] = 0.1 * (double)st[2 * i] / (double)st[2 * i + 1];
+    std::sort(ghz.begin(), ghz.end());
+    // per wave and k16 step: 24 MFMAs of 2 * 32 * 32 * 16 FLOP (= 96 of 2 * 16 * 16 * 32 per two of them)
+    const double flop = (double)L * d.ncu * 8.0 * nrep * K16 * 24.0 * 32768.0;
+    // two waves share a SIMD: cycles of the launch (wall x in-kernel clock, so launch overhead and the LDS fill included) per
+    // 32x32x16-equivalent MFMA of the pair; the pipe's own figure is 32
+    const double cpm = (double)ms / L * 1e6 * ghz[d.ncu / 2] / ((double)nrep * K16 * 24.0 * 2.0);
+    printf("%-9s %-5s %-6s  %8.3f ms/launch  %8.1f TFLOP/s  clock %.3f GHz  %6.2f SIMD cycles per 32x32x16-equivalent MFMA  (%d warm launches)\n",
+           SHAPE == 32 ? "32x32x16" : "16x16x32", !MEM ? "reg" : SHAPE == 32 && !ROLLED ? "mem-u" : "mem", data, ms / L, flop / (ms * 1e-3) * 1e-12, ghz[d.ncu / 2], cpm, warm);
+    fflush(stdout);
+    CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
+}
+
+int main(int argc, char** argv) {
+    const int nrep = argc > 1 ? atoi(argv[1]) : 200, passes = argc > 2 ? atoi(argv[2]) : 2;
+    hipDeviceProp_t prop;
+    CHECK(hipGetDeviceProperties(&prop, 0));
+    Bufs d;
+    d.ncu = prop.multiProcessorCount;
+    CHECK(hipMalloc(&d.aimg, LDS_BYTES)); CHECK(hipMalloc(&d.w, W_BYTES));
+    CHECK(hipMalloc(&d.out, (size_t)d.ncu * 512 * 4)); CHECK(hipMalloc(&d.stamps, (size_t)d.ncu * 16));
+    printf("%s, %d CUs, %d x %d k16 steps per launch\n", prop.name, d.ncu, nrep, K16);
+    std::vector<uint16_t> ha(LDS_BYTES / 2, 0), hw(W_BYTES / 2);
+    for (int pass = 0; pass < passes; ++pass)
+        for (int rnd = 1; rnd >= 0; --rnd) {
+            unsigned seed = 12345u;
+            for (int r = 0; r < 64; ++r) fill_h2(ha.data() + (size_t)r * (ROWB / 2), 32, rnd, 1.0f, seed);   // h in (-1, 1)
+            // a weight fragment pair is 1024 B hi then 1024 B lo; which value sits where does not matter to the probe
+            for (size_t f = 0; f < W_BYTES / 2048; ++f) {
+                std::vector<uint16_t> tmp(1024);
+                fill_h2(tmp.data(), 64, rnd, 0.5f, seed);
+                for (int s = 0; s < 64; ++s) {
+                    memcpy(&hw[f * 1024 + s * 8], &tmp[s * 16], 16);
+                    memcpy(&hw[f * 1024 + 512 + s * 8], &tmp[s * 16 + 8], 16);
+                }
+            }
+            CHECK(hipMemcpy(d.aimg, ha.data(), LDS_BYTES, hipMemcpyHostToDevice));
+            CHECK(hipMemcpy(d.w, hw.data(), W_BYTES, hipMemcpyHostToDevice));
+            const char* data = rnd ? "random" : "zeros";
+            run<32, false>(d, data, nrep);
+            run<16, false>(d, data, nrep);
+            run<32, true>(d, data, nrep);
+            run<32, true, true>(d, data, nrep);
+            run<16, true>(d, data, nrep);
+        }
+    CHECK(hipFree(d.aimg)); CHECK(hipFree(d.w)); CHECK(hipFree(d.out)); CHECK(hipFree(d.stamps));
+    return 0;
+}
