@@ -338,7 +338,7 @@ struct RecLayer {
     DevBuf *w_ih_s = nullptr;   // [2*G*H, Kp] f32, gate-scaled (feeds the f32 GEMM of float / unfused first layers)
     DevBuf *b_in_s = nullptr;   // [2*G*H] gate-scaled bias
     DevBuf *w_hh_h2 = nullptr;  // LSTM H=256: W_hh as h2 fragments (rnn_h2.hip)
-    DevBuf *w_cat_h2 = nullptr; // LSTM first layer: [W_hh | W_ih] as h2 fragments
+    DevBuf *w_cat_h2 = nullptr; // first layer: [W_hh | W_ih] as h2 fragments (LSTM: dec_frag16.h order, GRU: pack_rec_weights_h2)
     DevBuf *w_cat_dec_h2 = nullptr; // layer fed by an h2 layer output (K = 2H): [W_hh | W_ih] fragments
     DevBuf *w_hh_small_h2 = nullptr; // GRU H=128: W_hh as 16x16x32 fragments for the small-call step loop (gru_small_h2_kernel)
     DevBuf *b_in = nullptr;    // [2*G*H]       LSTM: b_ih + b_hh; GRU: b_ih + (b_hr, b_hz, 0)
@@ -434,8 +434,19 @@ int build_rec_layer(ModelBase* m, const StateDict& sd, const std::string& prefix
         };
         const float* const none[2] = {nullptr, nullptr};
         if (int rc = pack_upload(out.w_hh_h2, none, 0)) return rc;
-        if (K <= KXh2)
+        if (K <= KXh2 && G == 4) {
+            // the fused int8 LSTM encoder contracts on 16x16x32 tiles: dec_frag16.h's fragment order, with the bias column
+            for (int d = 0; d < 2; ++d)
+                if (!fits_f16(whh_x[d], (int64_t)G * H * H) || !fits_f16(wih_x[d], (int64_t)G * H * K))
+                    return fail(PA_ERR_INVALID, "encoder weight not representable in f16 range");
+            if (!fits_f16(bs.data(), (int64_t)2 * G * H)) return fail(PA_ERR_INVALID, "bias not representable in f16 range");
+            std::vector<uint32_t> hp(pa_dec16::words(H, KXh2));
+            pa_dec16::pack(whh_x, wih_x, H, KXh2, hp.data(), K, bias_x);
+            out.w_cat_h2 = m->new_buf();
+            if (int rc = upload(out.w_cat_h2, hp)) return rc;
+        } else if (K <= KXh2) {
             if (int rc = pack_upload(out.w_cat_h2, wih_x, KXh2, true)) return rc;
+        }
         if (K == 2 * H && G == 4) {
             // the fused LSTM decoder contracts on 16x16x32 tiles: its own fragment order (dec_frag16.h)
             for (int d = 0; d < 2; ++d)

@@ -1,14 +1,18 @@
-// The weight layout of the fused LSTM decoder's step loop (rnn_h2.hip: lstm_dec_h2_body), which contracts [h | x] with
-// [W_hh | W_ih] on v_mfma_f32_16x16x32_f16: where a weight's f16 hi and lo halves live, and the host packer that puts them
-// there (api.hip build_rec_layer, for this layer only: every other step loop keeps pack_rec_weights_h2).  Plain inline
-// functions, no HIP types and no _Float16: g++ and hipcc both compile this file.
+// The weight layout of the fused LSTM step loops on v_mfma_f32_16x16x32_f16 (rnn_h2.hip: lstm_dec_h2_body, KX = 2H, and
+// lstm_enc_h2_body, the int8 first layer, KX = 32), which contract [h | x] with [W_hh | W_ih]: where a weight's f16 hi and
+// lo halves live, and the host packer that puts them there (api.hip build_rec_layer, for these layers only: every other
+// step loop keeps pack_rec_weights_h2).  Plain inline functions, no HIP types and no _Float16: g++ and hipcc both compile
+// this file.
 //
 //     [dir][gate][column tile of 16][k step of 32][hi, lo][64 lanes][16 B]
 //     lane l of (gate g, column tile c, k step s) holds W[g*H + 16c + (l & 15)][32s + 8(l >> 4) + e], e = 0..7
 //
 // W = [W_hh | W_ih] is [4H, K] per direction, K = H + KX; the B operand of the instruction wants, per lane, eight consecutive
 // k of one output column (gru_small_h2_kernel and the DENSE head use the same operand layout).  Same bytes as
-// pack_rec_weights_h2.
+// pack_rec_weights_h2.  Any number of k steps: K = H + KX must be a multiple of 32.
+// A first layer with F < KX input features keeps W_ih in columns [H, H + F), zeros beyond, and -- when a bias is given --
+// bias[d][n] in column H + F: the step loop feeds a constant 1.0 in that input column, so the matrix pipe adds the bias
+// (pack_rec_weights_h2's bias column).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -64,8 +68,11 @@ inline size_t half_index(int H, int KX, int d, int g, int c, int s, int hl, int 
     return ((((((size_t)d * 4 + g) * (H / 16) + c) * ((H + KX) / 32) + s) * 2 + hl) * 64 + l) * 8 + e;
 }
 
-// whh[d]: [4H, H], wih[d]: [4H, KX] (row n = g*H + unit), both row-major f32 -> out[words(H, KX)]
-inline void pack(const float* const whh[2], const float* const wih[2], int H, int KX, uint32_t* out) {
+// whh[d]: [4H, H], wih[d]: [4H, F] (row n = g*H + unit), both row-major f32 -> out[words(H, KX)].  F < 0: F = KX.
+// bias (may be null): bias[d][4H], placed in column H + F when F < KX.
+inline void pack(const float* const whh[2], const float* const wih[2], int H, int KX, uint32_t* out, int F = -1,
+                 const float* const* bias = nullptr) {
+    if (F < 0) F = KX;
     uint16_t* o = reinterpret_cast<uint16_t*>(out);
     const int KS = (H + KX) / 32, CT = H / 16;
     for (int d = 0; d < 2; ++d)
@@ -75,7 +82,10 @@ inline void pack(const float* const whh[2], const float* const wih[2], int H, in
                     for (int l = 0; l < 64; ++l)
                         for (int e = 0; e < 8; ++e) {
                             const int n = g * H + 16 * c + (l & 15), k = 32 * s + 8 * (l >> 4) + e;
-                            const float v = k < H ? whh[d][(size_t)n * H + k] : wih[d][(size_t)n * KX + (k - H)];
+                            float v = 0.0f;
+                            if (k < H) v = whh[d][(size_t)n * H + k];
+                            else if (k - H < F) v = wih[d][(size_t)n * F + (k - H)];
+                            else if (bias != nullptr && k - H == F && F < KX) v = bias[d][n];
                             const uint16_t hi = f16_bits(v);
                             o[half_index(H, KX, d, g, c, s, 0, l, e)] = hi;
                             o[half_index(H, KX, d, g, c, s, 1, l, e)] = f16_bits(v - f16_value(hi));

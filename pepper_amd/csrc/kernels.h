@@ -49,10 +49,11 @@ hipError_t launch_gru_rec_fused(int H, const uint8_t* X, int F, int64_t x_bstrid
                                 const float* Wcat, const float* bhn, const float* h0, int ldh0, float* hn, int ldhn,
                                 float* Y, int ldy, int B, int T, hipStream_t stream);
 
-// rnn_h2.hip: the LSTM step loop on the f16 matrix pipe.  Weights packed by pack_rec_weights_h2
-// (wih = {nullptr, nullptr}, KX = 0 for W_hh alone; KX = 32 for the fused first layer).  X != nullptr
-// selects the fused form (int8 rows [B, T, F], bias [2*4H]); otherwise Xp seeds the accumulators as in
-// launch_lstm_rec.  Y receives the layer output in the h2 split format (ldy in 4-byte elements).
+// rnn_h2.hip: the LSTM step loop on the f16 matrix pipe.  X == nullptr: Xp seeds the accumulators as in
+// launch_lstm_rec, weights packed by pack_rec_weights_h2 (wih = {nullptr, nullptr}, KX = 0: W_hh alone).  X != nullptr
+// selects the fused first layer (int8 rows [B, T, F], F <= 32, bias [2*4H]) on 16x16x32 tiles: weights packed with
+// pa_dec16::pack(whh, wih, H, 32, out, F, bias) of dec_frag16.h (the bias in column H + F when F < 32).
+// Y receives the layer output in the h2 split format (ldy in 4-byte elements).
 void pack_rec_weights_h2(const float* const whh[2], const float* const wih[2], int G, int H, int F, int KX,
                          uint32_t* out, const float* const* bias = nullptr);   // bias: column H + F (fused layers, F < KX)
 size_t rec_weights_h2_words(int G, int H, int KX);

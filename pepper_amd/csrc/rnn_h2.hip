@@ -44,6 +44,9 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 // +2 log2(e) (g), so the accumulators ARE the exp2 arguments of sigmoid / tanh (api.hip build_rec_layer).
 // XG (decoder layers, whose input x_t is the previous layer's h2 output Xh [B*T, KX]): a step loop of its own,
 // lstm_dec_h2_body below; this kernel is only its entry.
+// KX = 32 (the fused int8 first layer) likewise: lstm_enc_h2_body below, on v_mfma_f32_16x16x32_f16 like the decoder's.  What
+// this kernel's own body still runs is the form seeded from Xp (KX = 0, whose Xp arrives in 32x32 C-fragment order); the
+// fused parts of it (x_load / x_store, BC, the two-term x steps) are what the encoder body restates on its own tiles.
 // SAUX: cache policy of the stream that passes through once -- the y stores (2 = nt: the lines are not kept in the XCD's
 // L2, which has to hold this direction's weight fragments that every workgroup re-reads every step; 0 = default policy,
 // what the forms seeded from Xp are launched with).  Measured r02 (16384 windows, device-resident pass): 2.566 -> 2.596 M
@@ -59,6 +62,10 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
 template <int MTILES>
 PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
                              int B, int T, unsigned long long* __restrict__ dbg, const uint32_t* __restrict__ Xh, int ldxh);
+// The fused int8 first layer (KX = 32) has a step loop of its own as well, lstm_enc_h2_body below.
+template <int MTILES, bool BC>
+PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* __restrict__ bias, const uint32_t* __restrict__ Wp,
+                             uint32_t* __restrict__ Y, int ldy, int B, int T, unsigned long long* __restrict__ dbg);
 
 template <int H, int KX, bool XG = false, int SAUX = 0, bool BC = false, int MTILES = 2>
 __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float* __restrict__ Xp, int ldx,
@@ -71,6 +78,11 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
     if constexpr (XG) {
         static_assert(H == 256 && KX == 512 && SAUX == 2 && !BC, "the fused decoder has one shape");
         lstm_dec_h2_body<MTILES>(bias, Wp, Y, ldy, B, T, dbg, Xh, ldxh);
+        return;
+    }
+    if constexpr (!XG && KX == 32) {
+        static_assert(H == 256 && SAUX == 2, "the fused int8 encoder has one shape");
+        lstm_enc_h2_body<MTILES, BC>(Xi, F, bias, Wp, Y, ldy, B, T, dbg);
         return;
     }
     constexpr int KT = H + KX, KS = KT / 16, KSH = H / 16, NT = H / 32, NW = H / 32;
@@ -602,6 +614,264 @@ PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __r
                 }
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
         lds_barrier();                    // h_t visible
+    }
+    {
+        const int tl = dir ? 0 : T - 1;
+#pragma unroll
+        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The fused int8 encoder's step loop (KX = 32: the first layer, whose input x_t is int8 features Xi [B*T, F], F <= 32), the
+// sibling of lstm_dec_h2_body on v_mfma_f32_16x16x32_f16: same decomposition, same tiles (acc[row tile of 16][gate][column
+// tile of 16], lane l = column l & 15, rows 4 (l >> 4) + r), same B ring of two gate-pair stages, same single-buffered A
+// fragments re-read right after their last use, same lane-local gate phase, every memory instruction alone in an MFMA gap,
+// the k loop a loop over one-k-step bodies (profiles/mfma_shape_probe.txt, the `enc` rows, is the probe that preceded it).
+// What differs: x is no ring.  The LDS row is the h2 image of [h | x] (288 units + 16 B pad = 1168 B, 73 16-byte slots: odd);
+// the gate phase converts the next step's int8 row and stores it beside h (hi halves; the lo halves stay zero; with BC the
+// constant 1.0 in column H + F, where the packed weights hold the bias), so the x columns are the ninth k step of the same
+// row.  That step issues two terms per product (x_hi.w_lo, x_hi.w_hi): the lo half of an int8 value is identically zero.
+// Nine k steps of 32 per time step, k ascending per accumulator: eight over h (three terms), one over x (the first time
+// step: the x step alone, PA_ENC_SKIP0 below).  The first stage of k step 0 is requested during the x step of the previous time
+// step and flies under the gate phase.
+// Weights: dec_frag16.h's order with nine k steps (pa_dec16::pack with the bias column).
+// what a k step does beside its MFMAs and its B loads: FRESH the first products start the accumulators; Y a y copy pass;
+// X the two-term x step; AN the next k step's A fragments: 0 none, 1 hi and lo of the h columns, 2 the hi half of the x columns
+// PA_ENC_SKIP0 (build switch, 1 unless a build defines it 0): at the first time step h is all zeros -- the eight h k steps
+// would add exact zeros to accumulators that start from +0 -- so that step runs the x step alone, with fresh accumulators,
+// and no y copy (what the copy would write there, zeros, is rewritten one step later anyway).  Same bits either way.
+#ifndef PA_ENC_SKIP0
+#define PA_ENC_SKIP0 1
+#endif
+template <bool FRESH_, bool Y_, bool X_, int AN_>
+struct EncStep {
+    static constexpr bool FRESH = FRESH_, Y = Y_, X = X_;
+    static constexpr int AN = AN_;
+};
+
+template <int MTILES, bool BC>
+PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* __restrict__ bias, const uint32_t* __restrict__ Wp,
+                             uint32_t* __restrict__ Y, int ldy, int B, int T, unsigned long long* __restrict__ dbg) {
+    constexpr int H = 256, KX = 32, KS = (H + KX) / 32, KSH = H / 32, NW = H / 32, SAUX = 2;
+    constexpr int MTL = 32 * MTILES, RT = 2 * MTILES;   // rows, row tiles of 16
+    static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
+    constexpr int ROWB = (H + KX) * 4 + 16, ROWD = ROWB / 4;   // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, then c (f32)
+    static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
+
+    int dir, btile;
+    decode_block(blockIdx.x, dir, btile);
+    const int b0 = btile * MTL;
+    if (b0 >= B) return;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lr = lane & 15, lq = lane >> 4;
+
+    float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][column tile][r][lane]
+    for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
+
+    f32x4 acc[RT][4][2];   // [row tile][gate][column tile]
+
+    const size_t urow = (size_t)b0 * T;
+    const __amdgpu_buffer_rsrc_t brs =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias + dir * 4 * H + 32 * u), 0, 0x7fffffff, 0x00020000);
+    // fragment (g, column tile c, k step s, hi/lo) of this wave: byte ((((g * 16 + 2u + c) * KS + s) * 2 + hl) * 1024 + lane * 16
+    // of the direction's block (dec_frag16.h); the wave's own term is part of the descriptor's base
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * 16) + 2 * u) * KS * 512), 0, 0x7fffffff, 0x00020000);
+    const unsigned woff = lane * 16u;
+
+    // x_t (int8, exact in f16) -> hi halves of LDS columns [H, H+KX); lo halves stay 0.
+    // One thread per pair of features: MTL rows x KX/2 pairs over 512 threads.
+    constexpr int XN = (MTL * KX / 2) / (NW * 64);
+    unsigned xv[XN];
+    auto x_load = [&](int t) {
+#pragma unroll
+        for (int k = 0; k < XN; ++k) {
+            const int e = tid + k * (NW * 64);
+            const int row = e / (KX / 2), f = (e % (KX / 2)) * 2;
+            int brow = b0 + row;
+            brow = brow < B ? brow : B - 1;
+            const int8_t* src = Xi + ((size_t)brow * T + t) * F;
+            const _Float16 one = BC ? (_Float16)1.0f : (_Float16)0.0f;     // the bias column's input
+            const _Float16 h0 = f < F ? (_Float16)(float)src[f] : (f == F ? one : (_Float16)0.0f);
+            const _Float16 h1 = f + 1 < F ? (_Float16)(float)src[f + 1] : (f + 1 == F ? one : (_Float16)0.0f);
+            xv[k] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
+        }
+    };
+    auto x_store = [&]() {
+#pragma unroll
+        for (int k = 0; k < XN; ++k) {
+            const int e = tid + k * (NW * 64);
+            const int row = e / (KX / 2), f = (e % (KX / 2)) * 2;
+            lds[row * ROWD + ((H + f) >> 3) * 8 + ((f & 7) >> 1)] = xv[k];
+        }
+    };
+
+    int once = 1;
+    asm volatile("" : "+s"(once));
+    h8 a[RT][2];            // [row tile][hi, lo] of the current k step
+    h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
+    const uint32_t* arow = lds + lr * ROWD + lq * 8;
+    auto load_b = [&](int s, int gp, int idx) {      // idx: in the order the MFMAs first need them
+        const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
+        b[gp][g2][c][hl] = __builtin_bit_cast(
+            h8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * KS + s) * 2 + hl) * 1024u, 0));
+    };
+    auto load_a = [&](int s, int m, int hl) { a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * ROWD + s * 32 + hl * 4); };
+
+    // y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is
+    constexpr int CPR = H / 4;                                // 16-byte chunks per row
+    constexpr int YROWS = (NW * 64) / CPR;                    // rows per pass (8)
+    constexpr int YC = MTL / YROWS;                           // passes (8 or 4): one per k step from step 0
+    static_assert(YC <= KSH, "one y copy pass per h k step");
+    const int yc_row = tid / CPR, yc_c = tid % CPR;
+    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
+    const __amdgpu_buffer_rsrc_t ycrs =
+        __builtin_amdgcn_make_buffer_rsrc(Y + urow * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
+    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
+    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
+    auto yc_write = [&](int j, int tp, u32x4 v) {
+        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, SAUX);
+    };
+
+    // gate-phase h write: element (row, col) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2, lo half 16 bytes later
+    // (h2_store16); the lane's element (m, c, r) is row 16m + 4 lq + r, col 32u + 16c + lr
+    const int hcol = 32 * u + lr;
+    unsigned short* hl_dst = reinterpret_cast<unsigned short*>(lds + 4 * lq * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
+
+    // The weights do not depend on the step: the first stage of k step 0 is requested during the x step of the previous time
+    // step and flies under the gate phase (b[0] stays live across it).
+    __syncthreads();
+    {
+        x_load(dir ? T - 1 : 0);
+        x_store();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_b(PA_ENC_SKIP0 ? KS - 1 : 0, 0, i);   // the first time step starts at the x step
+    }
+    __syncthreads();
+
+    for (int step = 0; step < T; ++step) {
+        const int t = dir ? T - 1 - step : step;
+        const bool stamp = dbg != nullptr && blockIdx.x == 8 && lane == 0;
+        if (stamp) dbg[(u * 80 + 2 * step) * 2] = __builtin_amdgcn_s_memtime();
+        // ---------------- MFMA phase ----------------
+        {
+            const int tp = step > 0 ? (dir ? t + 1 : t - 1) : t;   // time index of h_{s-1} (step 0: zeros, rewritten later)
+            u32x4 ycv = {0, 0, 0, 0};
+            auto kstep = [&](int s, auto cfg) {
+                using C = decltype(cfg);
+                constexpr int PT = C::X ? 4 : 6;                   // MFMAs per (row tile, column tile) of a phase
+                constexpr int NM = RT * 2 * PT;                    // MFMAs of a phase (one gate pair of one k step)
+                const int sn = C::X ? 0 : s + 1;
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp) {
+#pragma unroll
+                    for (int i = 0; i < NM; ++i) {
+                        const int m = i / (2 * PT), c = (i % (2 * PT)) / PT, term = ((i % PT) >> 1) + (C::X ? 1 : 0), g2 = i & 1,
+                                  g = 2 * gp + g2;
+                        // the first product into every accumulator of a time step starts from the inline constant 0
+                        acc[m][g][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m][term == 0 ? 1 : 0], b[gp][g2][c][term == 1 ? 1 : 0],
+                                                                              C::FRESH && i % PT < 2 ? f32x4{} : acc[m][g][c], 0, 0, 0);
+                        // next stage's 8 B fragments (the other gate pair of this k step, or the first of the next) early in
+                        // the phase
+                        if (C::X) {
+                            if (MTILES == 2 ? (i < 16 && (i & 1)) : i < 8) load_b(gp == 0 ? s : sn, gp ^ 1, MTILES == 2 ? i >> 1 : i);
+                        } else {
+                            if (MTILES == 2 ? (i < 24 && i % 3 == 1) : i < 8) load_b(gp == 0 ? s : sn, gp ^ 1, MTILES == 2 ? i / 3 : i);
+                        }
+                        // second gate pair: a row tile's A fragments of the next k step, right after their last use (the x
+                        // step wants no lo half)
+                        if (!C::X && gp == 1 && C::AN == 1 && i % 12 == 9) load_a(sn, m, 1);
+                        if (!C::X && gp == 1 && C::AN != 0 && i % 12 == 11) load_a(sn, m, 0);
+                        if (C::Y && i == NM / 2 + 1) {
+                            if (gp == 0) ycv = yc_read(s);
+                            else yc_write(s, tp, ycv);
+                        }
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            };
+            // (`once` is 1: a body that stands alone is wrapped in a loop of one trip the compiler cannot see through.  As
+            // straight-line code its accumulators are renamed from MFMA to MFMA and spill; as a loop body they stay in place.)
+            // One straight sequence of loops whatever the step (a branch around the bodies makes the compiler rename the
+            // accumulators between its arms, and spill): at the first time step the h bodies make no trip and the x step is
+            // the fresh one.
+            const int hrun = PA_ENC_SKIP0 && step == 0 ? 0 : once;
+#pragma unroll
+            for (int i = 0; i < 2 * RT; ++i) load_a(0, i >> 1, i & 1);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+            for (int r = 0; r < hrun; ++r) kstep(0, EncStep<true, true, false, 1>{});
+#pragma unroll 1
+            for (int s = 1; s < (YC < KSH - 1 ? YC : KSH - 1) * hrun; ++s) kstep(s, EncStep<false, true, false, 1>{});
+            if constexpr (YC < KSH - 1) {
+#pragma unroll 1
+                for (int s = YC; s < (KSH - 1) * hrun; ++s) kstep(s, EncStep<false, false, false, 1>{});
+            }
+#pragma unroll 1
+            for (int r = 0; r < hrun; ++r) kstep(KSH - 1, EncStep<false, (YC >= KSH), false, 2>{});
+#pragma unroll 1
+            for (int r = 0; r < hrun; ++r) kstep(KS - 1, EncStep<false, false, true, 0>{});
+            if (PA_ENC_SKIP0) {
+#pragma unroll 1
+                for (int r = hrun; r < once; ++r) {
+                    // h_{-1} = 0: only the x step, on fresh accumulators
+#pragma unroll
+                    for (int m = 0; m < RT; ++m) load_a(KSH, m, 0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    kstep(KS - 1, EncStep<true, false, true, 0>{});
+                }
+            }
+        }
+        // !BC: the lane's eight biases, re-read every step (in flight across the barrier) rather than held through the MFMA phase
+        float cb[4][2] = {};
+        if (!BC) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c)
+                    cb[g][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, lr * 4u, (unsigned)(g * H + 16 * c) * 4u, 0));
+        }
+        if (stamp) dbg[(u * 80 + 2 * step) * 2 + 1] = __builtin_amdgcn_s_memtime();
+
+        lds_barrier();                    // every wave has finished reading h_{t-1} and x_t
+        if (stamp) dbg[(u * 80 + 2 * step + 1) * 2] = __builtin_amdgcn_s_memtime();
+
+        // ---------------- gate phase (lstm_dec_h2_body's) ----------------
+        const int tn = dir ? t - 1 : t + 1;
+        if (step + 1 < T) x_load(tn);
+#pragma unroll
+        for (int m = 0; m < RT; ++m)
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int e = 0; e < 4; e += 2) {
+                    typedef float f32x2 __attribute__((ext_vector_type(2)));
+                    const f32x2 one = {1.0f, 1.0f};
+                    f32x2 ai = {acc[m][0][c][e], acc[m][0][c][e + 1]}, af = {acc[m][1][c][e], acc[m][1][c][e + 1]},
+                          ag = {acc[m][2][c][e], acc[m][2][c][e + 1]}, ao = {acc[m][3][c][e], acc[m][3][c][e + 1]};
+                    if (!BC) { ai += cb[0][c]; af += cb[1][c]; ag += cb[2][c]; ao += cb[3][c]; }
+                    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
+                    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
+                    const f32x2 ig = rcp(one + ex2(ai));
+                    const f32x2 fg = rcp(one + ex2(af));
+                    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
+                    const f32x2 og = rcp(one + ex2(ao));
+                    const int ci = (m * 8 + c * 4 + e) * 64;
+                    const f32x2 cold = {cs[ci], cs[ci + 64]};
+                    const f32x2 cn = fg * cold + ig * gg;
+                    cs[ci] = cn.x;
+                    cs[ci + 64] = cn.y;
+                    const f32x2 hv2 = og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) h2_store16(hl_dst + (16 * m + e + k) * ROWD * 2 + c * 32, k ? hv2.y : hv2.x);
+                }
+        if (step + 1 < T) x_store();
+        if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
+        lds_barrier();                    // h_t (and x_{t+1}) visible
     }
     {
         const int tl = dir ? 0 : T - 1;

@@ -1,6 +1,7 @@
 // Debug aid (not product): does the chip hold a higher clock on v_mfma_f32_16x16x32_f16 than on v_mfma_f32_32x32x16_f16
 // in the fused LSTM decoder's step loop (rnn_h2.hip: lstm_rec_h2_kernel<256, 512, XG>)?
 //   hipcc --offload-arch=gfx950 -O3 -o tools/microbench/mfma_shape tools/microbench/mfma_shape.hip && tools/microbench/mfma_shape
+//   (arguments: repetitions per launch [200], passes over the table [2], rows all | dec | enc; the encoder's rows are below)
 // One workgroup per CU, 8 waves (two per SIMD), each with the decoder's wave tile: 64 rows x 128 columns (32 units of four
 // gates), 128 accumulator registers.  A k loop of three-term split-f16 products (lo.hi, hi.lo, hi.hi) in two bodies with the
 // same MFMA work:
@@ -212,6 +213,164 @@ __global__ __launch_bounds__(512, 1) void k(int nrep, const uint32_t* __restrict
     }
 }
 
+// ---- the fused int8 ENCODER's traffic (lstm_rec_h2_kernel<256, 32, false, 2, true, 2>): K = 256 + 32, 18 k16 = 9 k32 steps,
+// one direction's fragments 1.125 MB re-read every time step, h2 rows of 1168 B ([h | x] + 16 pad).  The x steps (the last
+// two k16 steps / the last k32 step) are two-term: x is int8, exact in its hi half, so lo(x).hi(w) is not issued.
+//   S32: the form the encoder has today -- the 18 k16 steps of a time step unrolled, a 2-deep ring of whole k steps;
+//   S16: the body it would get -- a loop over eight one-k-step bodies for h and one two-term body for x, B ring of two gate-pair
+//        stages, single-buffered A re-read after its last use; the A fragments of k step 0 are read at the head of the time
+//        step (in the kernel they are the h the gate phase has just written).
+constexpr int EROWB = 1168, EROWD = EROWB / 4;
+constexpr int ELDS_BYTES = 64 * EROWB;
+constexpr int EK16 = 18, EKH16 = 16;
+constexpr unsigned EW_BYTES = 4u * 8u * EK16 * 2u * 1024u;   // 1.125 MB
+constexpr int EMFMA = EKH16 * 24 + (EK16 - EKH16) * 16;      // 32x32x16-equivalent MFMAs per wave and time step: 416
+
+template <int SHAPE>
+__global__ __launch_bounds__(512, 1) void ke(int nrep, const uint32_t* __restrict__ Aimg, const uint32_t* __restrict__ Wp,
+                                             float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int i = tid; i < ELDS_BYTES / 16; i += 512)
+        reinterpret_cast<u32x4*>(lds)[i] = reinterpret_cast<const u32x4*>(Aimg)[i];
+    __syncthreads();
+    const unsigned woff = lane * 16u;
+    unsigned long long t0, t1, r0, r1;
+    float sum = 0.0f;
+
+    if (SHAPE == 32) {
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint32_t*>(Wp + (size_t)u * EK16 * 512), 0, (int)(EW_BYTES - (unsigned)u * EK16 * 2048u), 0x00020000);
+        const uint32_t* arow = lds + (lane & 31) * EROWD + (lane >> 5) * 8;
+        struct Frag { h8 b[4][2], a[2][2]; };
+        Frag ring[2];
+        auto load_b = [&](int s, Frag& fr, int g, int hl) {
+            fr.b[g][hl] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(
+                                                     wrs, woff, (unsigned)((g * 8 * EK16 + s) * 2 + hl) * 1024u, 0));
+        };
+        auto load_a = [&](int s, Frag& fr, int m, int hl) {
+            fr.a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 32 * EROWD + s * 16 + hl * 4);
+        };
+        f32x16 acc[2][4] = {};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_b(0, ring[0], i >> 1, i & 1);
+        GAP();
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+        for (int it = 0; it < nrep; ++it) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) load_a(0, ring[0], i >> 1, i & 1);
+            GAP();
+#pragma unroll
+            for (int s = 0; s < EK16; ++s) {
+                const int p = s & 1, sn = s + 1 < EK16 ? s + 1 : 0;
+                const bool two = s >= EKH16;                     // x step: hi.lo and hi.hi only
+                const int n = two ? 16 : 24;
+#pragma unroll
+                for (int i = 0; i < n; ++i) {
+                    const int term = (i >> 3) + (two ? 1 : 0), g = (i & 7) >> 1, m = i & 1;
+                    acc[m][g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ring[p].a[m][term == 0 ? 1 : 0],
+                                                                       ring[p].b[g][term == 1 ? 1 : 0], acc[m][g], 0, 0, 0);
+                    if (!two) {
+                        if (i < 16 && (i & 1)) load_b(sn, ring[p ^ 1], (i >> 1) >> 1, (i >> 1) & 1);
+                        if (i >= 16 && i < 20) load_a(sn, ring[p ^ 1], (i - 16) >> 1, (i - 16) & 1);
+                    } else {
+                        if (i < 8) load_b(sn, ring[p ^ 1], i >> 1, i & 1);
+                        if (sn != 0 && i >= 8 && i < 12) load_a(sn, ring[p ^ 1], (i - 8) >> 1, (i - 8) & 1);
+                    }
+                    GAP();
+                }
+            }
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        r1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sum += acc[m][g][r];
+    } else {
+        constexpr int K32 = EK16 / 2, KH32 = EKH16 / 2;
+        const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
+            const_cast<uint32_t*>(Wp + (size_t)u * 2 * K32 * 512), 0, (int)(EW_BYTES - (unsigned)u * 2u * K32 * 2048u), 0x00020000);
+        const uint32_t* arow = lds + (lane & 15) * EROWD + (lane >> 4) * 8;
+        h8 a[4][2];             // [row tile][hi, lo]
+        h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
+        auto load_b = [&](int s, int gp, int idx) {
+            const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
+            b[gp][g2][c][hl] = __builtin_bit_cast(
+                h8, __builtin_amdgcn_raw_buffer_load_b128(
+                        wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * K32 + s) * 2 + hl) * 1024u, 0));
+        };
+        auto load_a = [&](int s, int m, int hl) {
+            a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * EROWD + s * 32 + hl * 4);
+        };
+        f32x4 acc[4][4][2] = {};
+        int once = 1;
+        asm volatile("" : "+s"(once));
+#pragma unroll
+        for (int i = 0; i < 8; ++i) load_b(0, 0, i);
+        GAP();
+        t0 = __builtin_amdgcn_s_memtime();
+        r0 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+        for (int it = 0; it < nrep; ++it) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) load_a(0, i >> 1, i & 1);
+            GAP();
+#pragma unroll 1
+            for (int s = 0; s < KH32; ++s) {
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp)
+#pragma unroll
+                    for (int i = 0; i < 48; ++i) {
+                        const int m = i / 12, c = (i % 12) / 6, term = (i % 6) >> 1, g2 = i & 1;
+                        acc[m][2 * gp + g2][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                            a[m][term == 0 ? 1 : 0], b[gp][g2][c][term == 1 ? 1 : 0], acc[m][2 * gp + g2][c], 0, 0, 0);
+                        if (i < 24 && i % 3 == 1) load_b(gp == 0 ? s : s + 1, gp ^ 1, i / 3);
+                        // the x step wants no lo half of A
+                        if (gp == 1 && i % 12 == 9 && s + 1 < KH32) load_a(s + 1, m, 1);
+                        if (gp == 1 && i % 12 == 11) load_a(s + 1, m, 0);
+                        GAP();
+                    }
+            }
+#pragma unroll 1
+            for (int r = 0; r < once; ++r) {
+#pragma unroll
+                for (int gp = 0; gp < 2; ++gp)
+#pragma unroll
+                    for (int i = 0; i < 32; ++i) {
+                        const int m = i / 8, c = (i % 8) / 4, term = 1 + ((i % 4) >> 1), g2 = i & 1;
+                        acc[m][2 * gp + g2][c] = __builtin_amdgcn_mfma_f32_16x16x32_f16(
+                            a[m][0], b[gp][g2][c][term == 1 ? 1 : 0], acc[m][2 * gp + g2][c], 0, 0, 0);
+                        if (i < 16 && (i & 1)) load_b(gp == 0 ? KH32 : 0, gp ^ 1, i >> 1);
+                        GAP();
+                    }
+            }
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        r1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int g = 0; g < 4; ++g)
+#pragma unroll
+                for (int c = 0; c < 2; ++c) sum += acc[m][g][c][0] + acc[m][g][c][1] + acc[m][g][c][2] + acc[m][g][c][3];
+    }
+    out[blockIdx.x * 512 + tid] = sum;
+    if (tid == 0) {
+        stamps[blockIdx.x * 2] = t1 - t0;
+        stamps[blockIdx.x * 2 + 1] = r1 - r0;
+    }
+}
+
 static uint16_t f16_bits(_Float16 h) { uint16_t b; memcpy(&b, &h, 2); return b; }
 
 // nwords 32-byte h2 slots (8 values: 16 B hi, 16 B lo) of uniform values in [-scale, scale), or zeros
@@ -266,17 +425,86 @@ void run(const Bufs& d, const char* data, int nrep) {
     CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
 }
 
+template <int SHAPE>
+void run_enc(const Bufs& d, const char* data, int nrep) {
+    auto fn = ke<SHAPE>;
+    CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, ELDS_BYTES));
+    auto launch = [&]() { hipLaunchKernelGGL(fn, dim3(d.ncu), dim3(512), ELDS_BYTES, 0, nrep, d.aimg, d.w, d.out, d.stamps); };
+    const auto w0 = std::chrono::steady_clock::now();
+    int warm = 0;
+    do {
+        for (int i = 0; i < 8; ++i) launch();
+        CHECK(hipDeviceSynchronize());
+        warm += 8;
+    } while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 2.0);
+    constexpr int L = 40;
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    CHECK(hipEventRecord(e0, 0));
+    for (int i = 0; i < L; ++i) launch();
+    CHECK(hipEventRecord(e1, 0));
+    CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    std::vector<unsigned long long> st(2 * d.ncu);
+    CHECK(hipMemcpy(st.data(), d.stamps, st.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<double> ghz(d.ncu);
+    for (int i = 0; i < d.ncu; ++i) ghz[i] = 0.1 * (double)st[2 * i] / (double)st[2 * i + 1];
+    std::sort(ghz.begin(), ghz.end());
+    const double flop = (double)L * d.ncu * 8.0 * nrep * EMFMA * 32768.0;
+    const double cpm = (double)ms / L * 1e6 * ghz[d.ncu / 2] / ((double)nrep * EMFMA * 2.0);
+    printf("%-9s %-5s %-6s  %8.3f ms/launch  %8.1f TFLOP/s  clock %.3f GHz  %6.2f SIMD cycles per 32x32x16-equivalent MFMA  (%d warm launches)\n",
+           SHAPE == 32 ? "32x32x16" : "16x16x32", "enc", data, ms / L, flop / (ms * 1e-3) * 1e-12, ghz[d.ncu / 2], cpm, warm);
+    fflush(stdout);
+    CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
+}
+
+// the encoder rows: its own LDS image ([h | x] rows of 1168 B, x = int8 values in the hi half) and weight block (1.125 MB)
+static void enc_rows(const Bufs& d, int nrep, int passes) {
+    printf("encoder traffic: %d x %d k16 steps per launch\n", nrep, EK16);
+    std::vector<uint16_t> ha(ELDS_BYTES / 2, 0), hw(EW_BYTES / 2);
+    for (int pass = 0; pass < passes; ++pass)
+        for (int rnd = 1; rnd >= 0; --rnd) {
+            unsigned seed = 12345u;
+            for (int r = 0; r < 64; ++r) {
+                uint16_t* row = ha.data() + (size_t)r * (EROWB / 2);
+                fill_h2(row, 32, rnd, 1.0f, seed);                        // h in (-1, 1)
+                for (int sl = 32; sl < 36; ++sl)
+                    for (int e = 0; e < 8; ++e) {                         // x: an int8 value, lo half zero
+                        seed = seed * 1664525u + 1013904223u;
+                        row[sl * 16 + e] = f16_bits((_Float16)(rnd ? (float)((int)(seed >> 24) - 128) : 0.0f));
+                        row[sl * 16 + 8 + e] = 0;
+                    }
+            }
+            for (size_t f = 0; f < EW_BYTES / 2048; ++f) {
+                std::vector<uint16_t> tmp(1024);
+                fill_h2(tmp.data(), 64, rnd, 0.5f, seed);
+                for (int s = 0; s < 64; ++s) {
+                    memcpy(&hw[f * 1024 + s * 8], &tmp[s * 16], 16);
+                    memcpy(&hw[f * 1024 + 512 + s * 8], &tmp[s * 16 + 8], 16);
+                }
+            }
+            CHECK(hipMemcpy(d.aimg, ha.data(), ELDS_BYTES, hipMemcpyHostToDevice));
+            CHECK(hipMemcpy(d.w, hw.data(), EW_BYTES, hipMemcpyHostToDevice));
+            const char* data = rnd ? "random" : "zeros";
+            run_enc<32>(d, data, nrep);
+            run_enc<16>(d, data, nrep);
+        }
+}
+
 int main(int argc, char** argv) {
     const int nrep = argc > 1 ? atoi(argv[1]) : 200, passes = argc > 2 ? atoi(argv[2]) : 2;
+    const char* rows = argc > 3 ? argv[3] : "all";      // all | dec | enc
+    const bool dec = strcmp(rows, "enc") != 0, enc = strcmp(rows, "dec") != 0;
     hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     Bufs d;
     d.ncu = prop.multiProcessorCount;
-    CHECK(hipMalloc(&d.aimg, LDS_BYTES)); CHECK(hipMalloc(&d.w, W_BYTES));
+    CHECK(hipMalloc(&d.aimg, ELDS_BYTES)); CHECK(hipMalloc(&d.w, W_BYTES));
     CHECK(hipMalloc(&d.out, (size_t)d.ncu * 512 * 4)); CHECK(hipMalloc(&d.stamps, (size_t)d.ncu * 16));
     printf("%s, %d CUs, %d x %d k16 steps per launch\n", prop.name, d.ncu, nrep, K16);
     std::vector<uint16_t> ha(LDS_BYTES / 2, 0), hw(W_BYTES / 2);
-    for (int pass = 0; pass < passes; ++pass)
+    for (int pass = 0; dec && pass < passes; ++pass)
         for (int rnd = 1; rnd >= 0; --rnd) {
             unsigned seed = 12345u;
             for (int r = 0; r < 64; ++r) fill_h2(ha.data() + (size_t)r * (ROWB / 2), 32, rnd, 1.0f, seed);   // h in (-1, 1)
@@ -298,6 +526,7 @@ int main(int argc, char** argv) {
             run<32, true, true>(d, data, nrep);
             run<16, true>(d, data, nrep);
         }
+    if (enc) enc_rows(d, nrep * K16 / EK16, passes);
     CHECK(hipFree(d.aimg)); CHECK(hipFree(d.w)); CHECK(hipFree(d.out)); CHECK(hipFree(d.stamps));
     return 0;
 }
