@@ -322,6 +322,47 @@ int pa_polish_chain_device_chunks(pa_encoder* e, const uint8_t** images);
  * score pass was proven to overflow from their BAM alignment and skipped (ssw.c:819-824 discards that pass's results). */
 int pa_polish_chain_last_timing(pa_encoder* e, double* ms, int32_t n_ms, int64_t* counts, int32_t n_counts);
 
+/* ------------------------------------------------------------------------------------------
+ * The polish stitch ON THE DEVICE (opt-in: polish(..., device_stitch=True); pepper_amd/csrc/stitch.hip).
+ * replaces, for such a run: Stitch.py small_chunk_stitch (:36-94) -- per piece a dictionary keyed (position, insert index),
+ * written in loop order, the last write wins, keys in order, gaps dropped.  The piece and loop order of every region
+ * (create_consensus_sequence :97-128) stay the caller's: pepper_amd/polish/DeviceStitch.py plan().
+ *
+ * A handle collects prediction rows while a run goes on (add) and merges one contig at a time at its end (finish, take).
+ * Calls on one handle exclude each other; all of them return when their device work is done.
+ * ------------------------------------------------------------------------------------------ */
+typedef struct pa_stitcher pa_stitcher;
+
+int pa_stitcher_create(int32_t device, void* hip_stream, pa_stitcher** out);
+void pa_stitcher_destroy(pa_stitcher* s);
+/* out[0] largest position, [1] largest insert index a kept row may have, [2] elements one workgroup of the scans takes,
+ * [3] packed rows per slab (the most one chunk may keep). */
+int pa_stitcher_limits(int64_t* out, int32_t n);
+/* n_chunks chunks of chunk_len rows each of contig `contig` (an id of the caller's): position / index host int64
+ * [n_chunks, chunk_len]; labels uint8 [n_chunks, chunk_len], in the memory of the handle's device and complete
+ * (labels_on_device != 0) or on the host; per chunk the caller's region id, a value that orders the chunks of a region as the
+ * reference iterates them (its ids as strings; equal values keep the order they arrive in) and drop_below: rows with
+ * position <= drop_below are the region's overlap and dropped (start + 2 * MIN_IMAGE_OVERLAP for a region with start > 0,
+ * else -1).  Rows with a negative position or index are dropped.  Kept rows are packed (8 bytes) behind those of earlier calls.
+ * PA_ERR_UNSUPPORTED: a kept row lies beyond the limits, or a chunk keeps more rows than a slab holds; PA_ERR_HIP: no memory
+ * for another slab.  A call that fails has added nothing and leaves the handle as it was. */
+int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
+                    const uint8_t* labels, int32_t labels_on_device, const int32_t* region, const int64_t* chunk_order,
+                    const int64_t* drop_below);
+/* Merge what the handle holds of `contig`: per region id its piece (0 .. n_pieces - 1) and its rank in the loop order.
+ * piece_first / piece_last / piece_length [n_pieces]: first and last kept position (-1, -1 for a piece without kept rows) and
+ * letters of every piece; *sequence_length letters in all, the pieces ordered by (first, last) as take() copies them.
+ * *bad_label != 0: a surviving label that is no base (the reference's label_decoder raises KeyError); no sequence then.
+ * The handle keeps the rows: a contig may be finished again, with another plan. */
+int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const int32_t* region, const int32_t* piece, const int64_t* rank,
+                       int32_t n_pieces, int64_t* piece_first, int64_t* piece_last, int64_t* piece_length, int64_t* sequence_length,
+                       int32_t* bad_label);
+/* The sequence of the last finish (capacity >= its length; no terminator). */
+int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity);
+/* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
+ * its tables. */
+int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
+
 #ifdef __cplusplus
 }
 #endif

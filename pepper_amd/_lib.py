@@ -119,6 +119,15 @@ SYMBOLS = [
     ("pa_polish_chain_chunks", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("pa_polish_chain_device_chunks", ctypes.c_int, [c_void_p, c_void_p]),
     ("pa_polish_chain_last_timing", ctypes.c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_int32]),
+    ("pa_stitcher_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
+    ("pa_stitcher_destroy", None, [c_void_p]),
+    ("pa_stitcher_limits", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_stitcher_add", ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
+                                       c_void_p]),
+    ("pa_stitcher_finish", ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                          ctypes.POINTER(c_int64), ctypes.POINTER(c_int32)]),
+    ("pa_stitcher_take", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
+    ("pa_stitcher_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     # include/pepper_amd_realign.h
     ("pa_realigner_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_realigner_destroy", None, [c_void_p]),
@@ -260,6 +269,15 @@ def device_walk():
     """PEPPER_AMD_DEVICE_WALK=0: PackedEncoder.pack_device walks a downloaded copy of every inflated span on the host again.
     Read per call."""
     return os.environ.get(DEVICE_WALK_ENV, "1") != "0"
+
+
+DEVICE_STITCH_ENV = "PEPPER_AMD_DEVICE_STITCH"
+
+
+def device_stitch():
+    """PEPPER_AMD_DEVICE_STITCH=1: polish() merges the predictions on the device (pa_stitcher_*; pepper_amd/polish/DeviceStitch.py)
+    instead of perform_stitch on the host.  Unset or any other value: on the host."""
+    return os.environ.get(DEVICE_STITCH_ENV, "0") == "1"
 
 
 def check(rc):

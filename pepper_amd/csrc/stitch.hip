@@ -1,0 +1,691 @@
+// Polish stitch on the device (include/pepper_amd_encoder.h, pa_stitcher_*).
+//
+// replaces, for a run that opts in: the merge of pepper/modules/python/Stitch.py small_chunk_stitch (:36-94) -- per piece a
+// dictionary keyed (position, insert index), written in loop order, the last write of a key wins, keys come out sorted, gaps
+// are dropped -- which pa_h5_stitch_polish_regions runs on CPU cores from the prediction files.
+//
+// The merge needs no sort.  A piece's keys are dense: positions span [first, last] and a position holds max(index) + 1 keys, so
+//   width[piece, position] = max(index) + 1              (atomicMax)
+//   base                   = exclusive scan of the widths  (the slot of key (position, 0))
+//   slot[base + index]     = max over its writers of ((rank + 1) << 8 | label)    (64-bit atomicMax)
+// where rank numbers the kept rows of the contig in the reference's loop order.  An integer maximum does not depend on the
+// order the rows arrive in, so the winner is the dictionary's last write whatever the schedule.  A second scan over "the winner is
+// a base" gives every letter its place.  Both scans are reduce-then-scan over separate launches (block sums, scan of the sums,
+// add back): no workgroup ever waits for another one.
+//
+// add() is the streaming half: a count kernel and a compaction kernel per call keep the rows the dictionary would take (stored
+// order), 8 bytes each, in fixed-size slabs that are never moved.
+#include "../../include/pepper_amd.h"
+#include "../../include/pepper_amd_encoder.h"
+
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "common.h"
+#include "kernels.h"
+
+namespace {
+
+constexpr int ST_THREADS = 256;                         // 4 waves
+constexpr int ST_ITEMS = 4;                             // consecutive scan elements per thread
+constexpr int ST_B = ST_THREADS * ST_ITEMS;             // scan elements per workgroup (pa_stitcher_limits [2])
+constexpr int64_t ST_SLAB_ROWS = 1 << 20;               // packed rows per slab: 8 MiB (pa_stitcher_limits [3])
+constexpr int64_t ST_MAX_POSITION = 0xFFFFFFFFll;
+constexpr int64_t ST_MAX_INDEX = 0xFFFFll;
+
+// packed row: position << 24 | index << 8 | label
+PA_DEV uint64_t pack_row(int64_t p, int64_t x, uint8_t label) { return ((uint64_t)p << 24) | ((uint64_t)x << 8) | label; }
+PA_DEV uint32_t row_position(uint64_t v) { return (uint32_t)(v >> 24); }
+PA_DEV uint32_t row_index(uint64_t v) { return (uint32_t)(v >> 8) & 0xFFFFu; }
+PA_DEV uint32_t row_label(uint64_t v) { return (uint32_t)v & 0xFFu; }
+
+// the rows small_chunk_stitch keeps: position >= 0, index >= 0, and past the overlap of a region that does not start at 0
+// (drop_below = start + 2 * MIN_IMAGE_OVERLAP there, -1 elsewhere)
+PA_DEV bool keeps(int64_t p, int64_t x, int64_t drop_below) { return p >= 0 && x >= 0 && p > drop_below; }
+
+// ---------------------------------------------------------------- add: count, then compact ----
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_count(const int64_t* __restrict__ pos, const int64_t* __restrict__ idx,
+                                                             const int64_t* __restrict__ drop_below, int chunk_len,
+                                                             int32_t* __restrict__ kept, int32_t* __restrict__ refused) {
+    __shared__ int s_kept, s_bad;
+    const int c = blockIdx.x;
+    if (threadIdx.x == 0) s_kept = s_bad = 0;
+    __syncthreads();
+    const int64_t thr = drop_below[c];
+    const size_t at = (size_t)c * chunk_len;
+    int mine = 0, bad = 0;
+    for (int i = threadIdx.x; i < chunk_len; i += ST_THREADS) {
+        const int64_t p = pos[at + i], x = idx[at + i];
+        if (keeps(p, x, thr)) {
+            ++mine;
+            bad |= (p > ST_MAX_POSITION || x > ST_MAX_INDEX);
+        }
+    }
+    for (int d = 32; d; d >>= 1) {
+        mine += __shfl_xor(mine, d);
+        bad |= __shfl_xor(bad, d);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        atomicAdd(&s_kept, mine);
+        if (bad) atomicOr(&s_bad, 1);
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        kept[c] = s_kept;
+        refused[c] = s_bad;
+    }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_compact(const int64_t* __restrict__ pos, const int64_t* __restrict__ idx,
+                                                               const uint8_t* __restrict__ labels, const int64_t* __restrict__ drop_below,
+                                                               int chunk_len, const int32_t* __restrict__ kept,
+                                                               uint64_t* const* __restrict__ dst_of) {
+    __shared__ int s_wave[ST_THREADS / 64];
+    const int c = blockIdx.x;
+    const int room = kept[c];
+    if (room == 0) return;                               // (uniform for the workgroup)
+    uint64_t* dst = dst_of[c];
+    const int64_t thr = drop_below[c];
+    const size_t at = (size_t)c * chunk_len;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int t = 0; t < chunk_len; t += ST_THREADS) {
+        const int i = t + threadIdx.x;
+        int64_t p = -1, x = -1;
+        if (i < chunk_len) {
+            p = pos[at + i];
+            x = idx[at + i];
+        }
+        const bool keep = i < chunk_len && keeps(p, x, thr);
+        const unsigned long long mask = __ballot(keep);
+        const int before = __popcll(mask & ((1ull << lane) - 1ull));
+        if (lane == 0) s_wave[wave] = __popcll(mask);
+        __syncthreads();
+        int wave_base = 0, total = 0;
+        for (int w = 0; w < ST_THREADS / 64; ++w) {
+            if (w < wave) wave_base += s_wave[w];
+            total += s_wave[w];
+        }
+        const int o = base + wave_base + before;
+        if (keep && o < room) dst[o] = pack_row(p, x, labels[at + i]);
+        base += total;
+        __syncthreads();
+    }
+}
+
+// ---------------------------------------------------------------- finish ----
+struct ChunkDesc {                                      // one chunk of the contig, in loop order
+    const uint64_t* rows;
+    uint32_t count, piece;
+    uint64_t rank_base;                                 // rank of its first kept row
+};
+
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_range(const ChunkDesc* __restrict__ desc, uint32_t* __restrict__ pmin,
+                                                             uint32_t* __restrict__ pmax) {
+    const ChunkDesc d = desc[blockIdx.x];
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (uint32_t r = threadIdx.x; r < d.count; r += ST_THREADS) {
+        const uint32_t p = row_position(d.rows[r]);
+        lo = min(lo, p);
+        hi = max(hi, p);
+    }
+    for (int s = 32; s; s >>= 1) {
+        lo = min(lo, (uint32_t)__shfl_xor((int)lo, s));
+        hi = max(hi, (uint32_t)__shfl_xor((int)hi, s));
+    }
+    if ((threadIdx.x & 63) == 0 && lo <= hi) {          // one pair of atomics per wave that saw a row
+        atomicMin(&pmin[d.piece], lo);
+        atomicMax(&pmax[d.piece], hi);
+    }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_width(const ChunkDesc* __restrict__ desc, const uint32_t* __restrict__ pmin,
+                                                             const uint64_t* __restrict__ pbase, uint32_t* __restrict__ width,
+                                                             uint64_t n_positions, uint32_t* __restrict__ fault) {
+    const ChunkDesc d = desc[blockIdx.x];
+    const uint64_t base = pbase[d.piece];
+    const uint32_t first = pmin[d.piece];
+    for (uint32_t r = threadIdx.x; r < d.count; r += ST_THREADS) {
+        const uint64_t v = d.rows[r];
+        const uint64_t at = base + (row_position(v) - first);
+        if (at < n_positions) atomicMax(&width[at], row_index(v) + 1u);
+        else atomicOr(fault, 1u);
+    }
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_scatter(const ChunkDesc* __restrict__ desc, const uint32_t* __restrict__ pmin,
+                                                               const uint64_t* __restrict__ pbase, const uint32_t* __restrict__ slot_base,
+                                                               unsigned long long* __restrict__ slots, uint64_t n_positions,
+                                                               uint64_t n_slots, uint32_t* __restrict__ fault) {
+    const ChunkDesc d = desc[blockIdx.x];
+    const uint64_t base = pbase[d.piece];
+    const uint32_t first = pmin[d.piece];
+    for (uint32_t r = threadIdx.x; r < d.count; r += ST_THREADS) {
+        const uint64_t v = d.rows[r];
+        const uint64_t at = base + (row_position(v) - first);
+        uint64_t slot = n_slots;
+        if (at < n_positions) slot = (uint64_t)slot_base[at] + row_index(v);
+        if (slot < n_slots) atomicMax(&slots[slot], (unsigned long long)(((d.rank_base + r + 1) << 8) | row_label(v)));
+        else atomicOr(fault, 2u);
+    }
+}
+
+// the winner of every slot: its letter (0: a gap, an empty slot or a label that is no base), the largest label above 4
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_check(const unsigned long long* __restrict__ slots, uint64_t n_slots,
+                                                             uint8_t* __restrict__ letters, uint32_t* __restrict__ bad_label) {
+    const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= n_slots) return;
+    const uint32_t label = (uint32_t)slots[i] & 0xFFu;
+    uint8_t letter = 0;
+    if (label >= 1 && label <= 4) letter = (uint8_t)((0x54474341u >> (8 * (label - 1))) & 0xFFu);      // "ACGT"
+    else if (label > 4) atomicMax(bad_label, label);
+    letters[i] = letter;
+}
+
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_emit(const uint8_t* __restrict__ letters, const uint32_t* __restrict__ place,
+                                                            uint64_t n_slots, uint64_t n_letters, uint8_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= n_slots) return;
+    const uint8_t letter = letters[i];
+    if (letter && place[i] < n_letters) out[place[i]] = letter;
+}
+
+// where every piece's slots and letters begin (pieces lie one after the other in both)
+__global__ void k_stitch_bounds(const uint64_t* __restrict__ pbase, int n_pieces, const uint32_t* __restrict__ slot_base,
+                                const uint32_t* __restrict__ place, uint64_t n_positions, uint64_t n_slots, uint64_t n_letters,
+                                uint64_t* __restrict__ letter_start) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_pieces) return;
+    const uint64_t at = pbase[p];
+    const uint64_t slot = at < n_positions ? slot_base[at] : n_slots;
+    letter_start[p] = slot < n_slots ? place[slot] : n_letters;
+}
+
+// ---------------------------------------------------------------- exclusive scan: reduce, scan the sums, add back ----
+struct LoadU32 {
+    const uint32_t* p;
+    PA_DEV uint64_t operator()(uint64_t i) const { return p[i]; }
+};
+struct LoadU64 {
+    const uint64_t* p;
+    PA_DEV uint64_t operator()(uint64_t i) const { return p[i]; }
+};
+struct LoadLetter {
+    const uint8_t* p;
+    PA_DEV uint64_t operator()(uint64_t i) const { return p[i] != 0; }
+};
+
+PA_DEV uint64_t shfl_up64(uint64_t v, int d) {
+    const int lo = __shfl_up((int)(uint32_t)v, d), hi = __shfl_up((int)(uint32_t)(v >> 32), d);
+    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
+}
+
+// inclusive scan of one value per thread over the workgroup -> (inclusive prefix, workgroup total)
+PA_DEV uint64_t block_scan(uint64_t v, uint64_t* s_wave, uint64_t* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t u = shfl_up64(v, d);
+        if (lane >= d) v += u;
+    }
+    if (lane == 63) s_wave[wave] = v;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (int w = 0; w < ST_THREADS / 64; ++w) {
+        if (w < wave) before += s_wave[w];
+        all += s_wave[w];
+    }
+    *total = all;
+    return v + before;
+}
+
+// sums[b] = sum of in[b * B .. min(n, (b + 1) * B))  (a workgroup past the end writes 0)
+template <class L>
+__global__ __launch_bounds__(ST_THREADS) void k_scan_reduce(L in, uint64_t n, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    uint64_t v = 0;
+    for (int k = 0; k < ST_ITEMS; ++k)
+        if (i0 + k < n) v += in(i0 + k);
+    uint64_t total;
+    (void)block_scan(v, s_wave, &total);
+    if (threadIdx.x == 0) sums[blockIdx.x] = total;
+}
+
+// out[i] = offset[b] + sum of in[b * B .. i)   (offset == nullptr: one workgroup, offset 0).  in and out may be the same array:
+// a thread reads its own elements before it writes them and touches no others.
+template <class L, class TO>
+__global__ __launch_bounds__(ST_THREADS) void k_scan_down(L in, uint64_t n, const uint64_t* __restrict__ offset, TO* out) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    uint64_t item[ST_ITEMS], v = 0;
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        item[k] = i0 + k < n ? in(i0 + k) : 0;
+        v += item[k];
+    }
+    uint64_t total;
+    uint64_t run = block_scan(v, s_wave, &total) - v + (offset ? offset[blockIdx.x] : 0);
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        if (i0 + k < n) out[i0 + k] = (TO)run;
+        run += item[k];
+    }
+}
+
+inline uint64_t scan_blocks(uint64_t n) { return (n + ST_B - 1) / ST_B; }
+
+// 64-bit words of scratch scan_exclusive needs for n elements
+inline uint64_t scan_scratch_words(uint64_t n) {
+    uint64_t words = 0, m = scan_blocks(n) + 1;
+    for (;;) {
+        words += m;
+        if (m <= (uint64_t)ST_B) return words;
+        m = scan_blocks(m);
+    }
+}
+
+// in place over m 64-bit sums; `next` = scratch behind them
+void scan_sums(hipStream_t stream, uint64_t* sums, uint64_t m, uint64_t* next) {
+    if (m <= (uint64_t)ST_B) {
+        k_scan_down<LoadU64, uint64_t><<<1, ST_THREADS, 0, stream>>>(LoadU64{sums}, m, nullptr, sums);
+        return;
+    }
+    const uint64_t blocks = scan_blocks(m);
+    k_scan_reduce<LoadU64><<<(unsigned)blocks, ST_THREADS, 0, stream>>>(LoadU64{sums}, m, next);
+    scan_sums(stream, next, blocks, next + blocks);
+    k_scan_down<LoadU64, uint64_t><<<(unsigned)blocks, ST_THREADS, 0, stream>>>(LoadU64{sums}, m, next, sums);
+}
+
+// out[i] = sum of in[0 .. i) for i < n; returns where the total of all n lies (device memory, in `scratch`)
+template <class L, class TO>
+const uint64_t* scan_exclusive(hipStream_t stream, L in, uint64_t n, TO* out, uint64_t* scratch) {
+    const uint64_t blocks = scan_blocks(n);
+    // one workgroup more than the input needs: it sums nothing, and after the scan of the sums its entry is the total
+    k_scan_reduce<L><<<(unsigned)(blocks + 1), ST_THREADS, 0, stream>>>(in, n, scratch);
+    scan_sums(stream, scratch, blocks + 1, scratch + blocks + 1);
+    if (blocks) k_scan_down<L, TO><<<(unsigned)blocks, ST_THREADS, 0, stream>>>(in, n, scratch, out);
+    return scratch + blocks;
+}
+
+struct Buffer {
+    void* p = nullptr;
+    size_t cap = 0;
+    bool grow(size_t need) {
+        if (need <= cap) return true;
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+        const size_t want = need + need / 8 + 4096;
+        if (hipMalloc(&p, want) != hipSuccess) return false;
+        cap = want;
+        return true;
+    }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        cap = 0;
+    }
+    template <class T> T* as() const { return (T*)p; }
+};
+
+struct ChunkRec {
+    int32_t region;
+    int64_t order;
+    uint64_t arrival;
+    uint64_t* rows;
+    uint32_t count;
+};
+
+struct PieceOut {
+    int64_t first, last, offset, length;
+    int piece;
+};
+
+}  // namespace
+
+struct pa_stitcher {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::mutex lock;
+    std::vector<uint64_t*> slabs;
+    size_t slab_at = 0;                                 // slabs in use: the last of them is being filled
+    int64_t slab_used = ST_SLAB_ROWS;                   // rows taken of it (no slab yet: "full")
+    std::unordered_map<int32_t, std::vector<ChunkRec>> contigs;
+    uint64_t arrivals = 0;
+    int64_t rows_held = 0;
+    // add's staging
+    Buffer a_pos, a_idx, a_lab, a_drop, a_kept, a_refused, a_dst;
+    // finish's tables
+    Buffer f_desc, f_piece, f_width, f_base, f_slots, f_letters, f_place, f_out, f_scan, f_words;
+    std::vector<PieceOut> pieces;                       // of the last finish, in output order
+    int64_t sequence_length = 0;
+    int64_t last_slots = 0, last_pieces = 0, last_positions = 0, last_scratch_bytes = 0;
+};
+
+namespace {
+
+#define ST_HIP(expr)                                                                                                 \
+    do {                                                                                                             \
+        hipError_t e_ = (expr);                                                                                      \
+        if (e_ != hipSuccess) return pa::set_error(PA_ERR_HIP, std::string("stitcher: " #expr ": ") + hipGetErrorString(e_)); \
+    } while (0)
+
+int no_memory(const char* what, uint64_t bytes) {
+    (void)hipGetLastError();
+    return pa::set_error(PA_ERR_HIP, std::string("stitcher: no device memory for ") + what + " (" + std::to_string(bytes) + " bytes)");
+}
+
+std::vector<Buffer*> buffers_of(pa_stitcher* s) {
+    return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece, &s->f_width,
+            &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_scan, &s->f_words};
+}
+
+}  // namespace
+
+extern "C" {
+
+int pa_stitcher_limits(int64_t* out, int32_t n) {
+    if (!out || n < 0) return pa::set_error(PA_ERR_INVALID, "stitcher limits: null or negative argument");
+    const int64_t v[4] = {ST_MAX_POSITION, ST_MAX_INDEX, ST_B, ST_SLAB_ROWS};
+    for (int32_t i = 0; i < n; ++i) out[i] = i < 4 ? v[i] : 0;
+    return PA_OK;
+}
+
+int pa_stitcher_create(int32_t device, void* hip_stream, pa_stitcher** out) {
+    if (!out) return pa::set_error(PA_ERR_INVALID, "stitcher: null argument");
+    *out = nullptr;
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+        return pa::set_error(PA_ERR_NO_DEVICE, "no HIP device visible: the device stitch has no CPU fallback (perform_stitch is the host form)");
+    if (device < 0 || device >= count) return pa::set_error(PA_ERR_INVALID, "stitcher: device ordinal out of range");
+    ST_HIP(hipSetDevice(device));
+    auto* s = new pa_stitcher();
+    s->device = device;
+    s->stream = (hipStream_t)hip_stream;
+    if (!hip_stream) {
+        if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) {
+            delete s;
+            return pa::set_error(PA_ERR_HIP, "stitcher: stream creation failed");
+        }
+        s->own_stream = true;
+    }
+    *out = s;
+    return PA_OK;
+}
+
+void pa_stitcher_destroy(pa_stitcher* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    (void)hipStreamSynchronize(s->stream);
+    for (Buffer* b : buffers_of(s)) b->release();
+    for (uint64_t* slab : s->slabs) (void)hipFree(slab);
+    if (s->own_stream) (void)hipStreamDestroy(s->stream);
+    delete s;
+}
+
+int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
+                    const uint8_t* labels, int32_t labels_on_device, const int32_t* region, const int64_t* chunk_order,
+                    const int64_t* drop_below) {
+    if (!s || n_chunks < 0 || chunk_len < 0) return pa::set_error(PA_ERR_INVALID, "stitcher add: null handle or negative size");
+    if (n_chunks == 0 || chunk_len == 0) return PA_OK;
+    if (!position || !index || !labels || !region || !chunk_order || !drop_below)
+        return pa::set_error(PA_ERR_INVALID, "stitcher add: null array");
+    std::lock_guard<std::mutex> guard(s->lock);
+    ST_HIP(hipSetDevice(s->device));
+    const size_t n = (size_t)n_chunks, rows = n * (size_t)chunk_len;
+    if (!s->a_pos.grow(rows * 8) || !s->a_idx.grow(rows * 8) || !s->a_drop.grow(n * 8) || !s->a_kept.grow(n * 4) ||
+        !s->a_refused.grow(n * 4) || !s->a_dst.grow(n * 8) || (!labels_on_device && !s->a_lab.grow(rows)))
+        return no_memory("the staged chunks", rows * 17);
+    ST_HIP(hipMemcpyAsync(s->a_pos.p, position, rows * 8, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(s->a_idx.p, index, rows * 8, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(s->a_drop.p, drop_below, n * 8, hipMemcpyHostToDevice, s->stream));
+    const uint8_t* d_labels = labels;
+    if (!labels_on_device) {
+        ST_HIP(hipMemcpyAsync(s->a_lab.p, labels, rows, hipMemcpyHostToDevice, s->stream));
+        d_labels = s->a_lab.as<uint8_t>();
+    }
+    k_stitch_count<<<(unsigned)n, ST_THREADS, 0, s->stream>>>(s->a_pos.as<int64_t>(), s->a_idx.as<int64_t>(), s->a_drop.as<int64_t>(),
+                                                               chunk_len, s->a_kept.as<int32_t>(), s->a_refused.as<int32_t>());
+    ST_HIP(hipGetLastError());
+    std::vector<int32_t> kept(n), refused(n);
+    ST_HIP(hipMemcpyAsync(kept.data(), s->a_kept.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(refused.data(), s->a_refused.p, n * 4, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    for (size_t c = 0; c < n; ++c) {
+        if (refused[c])
+            return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher add: chunk " + std::to_string(c) + " of the call holds a kept row with a position above " +
+                                                         std::to_string(ST_MAX_POSITION) + " or an insert index above " +
+                                                         std::to_string(ST_MAX_INDEX) + "; nothing of the call was taken");
+        if (kept[c] > ST_SLAB_ROWS)
+            return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher add: chunk " + std::to_string(c) + " keeps " + std::to_string(kept[c]) +
+                                                         " rows, a slab holds " + std::to_string(ST_SLAB_ROWS) + "; nothing of the call was taken");
+    }
+    // every chunk's place: behind the last one while the slab has room, else at the head of a new slab
+    std::vector<uint64_t*> dst(n, nullptr);
+    size_t slab = s->slab_at;
+    int64_t used = s->slab_used;
+    for (size_t c = 0; c < n; ++c) {
+        if (kept[c] == 0) continue;
+        if (used + kept[c] > ST_SLAB_ROWS) {
+            if (slab == s->slabs.size()) {
+                uint64_t* fresh = nullptr;
+                if (hipMalloc((void**)&fresh, (size_t)ST_SLAB_ROWS * 8) != hipSuccess) return no_memory("a slab", (uint64_t)ST_SLAB_ROWS * 8);
+                s->slabs.push_back(fresh);              // (kept if the call fails later: the cursor has not moved, the next call fills it)
+            }
+            ++slab;
+            used = 0;
+        }
+        dst[c] = s->slabs[slab - 1] + used;
+        used += kept[c];
+    }
+    ST_HIP(hipMemcpyAsync(s->a_dst.p, dst.data(), n * 8, hipMemcpyHostToDevice, s->stream));
+    k_stitch_compact<<<(unsigned)n, ST_THREADS, 0, s->stream>>>(s->a_pos.as<int64_t>(), s->a_idx.as<int64_t>(), d_labels,
+                                                                 s->a_drop.as<int64_t>(), chunk_len, s->a_kept.as<int32_t>(),
+                                                                 s->a_dst.as<uint64_t*>());
+    ST_HIP(hipGetLastError());
+    ST_HIP(hipStreamSynchronize(s->stream));            // the caller's arrays and labels are free again; dst is read
+    auto& list = s->contigs[contig];
+    for (size_t c = 0; c < n; ++c) {
+        if (kept[c] == 0) continue;
+        list.push_back(ChunkRec{region[c], chunk_order[c], s->arrivals++, dst[c], (uint32_t)kept[c]});
+        s->rows_held += kept[c];
+    }
+    s->slab_at = slab;
+    s->slab_used = used;
+    return PA_OK;
+}
+
+int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const int32_t* region, const int32_t* piece, const int64_t* rank,
+                       int32_t n_pieces, int64_t* piece_first, int64_t* piece_last, int64_t* piece_length, int64_t* sequence_length,
+                       int32_t* bad_label) {
+    if (!s || n_regions < 0 || n_pieces < 0 || !sequence_length || !bad_label ||
+        (n_regions > 0 && (!region || !piece || !rank)) || (n_pieces > 0 && (!piece_first || !piece_last || !piece_length)))
+        return pa::set_error(PA_ERR_INVALID, "stitcher finish: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    ST_HIP(hipSetDevice(s->device));
+    *sequence_length = 0;
+    *bad_label = 0;
+    s->pieces.clear();
+    s->sequence_length = 0;
+    s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
+    s->last_pieces = n_pieces;
+    for (int32_t p = 0; p < n_pieces; ++p) {
+        piece_first[p] = piece_last[p] = -1;
+        piece_length[p] = 0;
+    }
+    std::unordered_map<int32_t, std::pair<int32_t, int64_t>> where;      // region id -> (piece, rank)
+    for (int32_t r = 0; r < n_regions; ++r) {
+        if (piece[r] < 0 || piece[r] >= n_pieces) return pa::set_error(PA_ERR_INVALID, "stitcher finish: a region's piece is out of range");
+        where[region[r]] = {piece[r], rank[r]};
+    }
+    auto found = s->contigs.find(contig);
+    if (found == s->contigs.end() || found->second.empty() || n_pieces == 0) {
+        if (found != s->contigs.end() && !found->second.empty())
+            return pa::set_error(PA_ERR_INVALID, "stitcher finish: the contig holds chunks and the plan has no piece");
+        return PA_OK;
+    }
+    // loop order: regions as ranked, a region's chunks by their order value, equal ones as they arrived
+    struct Ordered { int64_t rank; const ChunkRec* rec; int32_t piece; };
+    std::vector<Ordered> order;
+    order.reserve(found->second.size());
+    for (const ChunkRec& rec : found->second) {
+        auto w = where.find(rec.region);
+        if (w == where.end())
+            return pa::set_error(PA_ERR_INVALID, "stitcher finish: region " + std::to_string(rec.region) + " holds chunks and is not in the plan");
+        order.push_back(Ordered{w->second.second, &rec, w->second.first});
+    }
+    std::sort(order.begin(), order.end(), [](const Ordered& a, const Ordered& b) {
+        if (a.rank != b.rank) return a.rank < b.rank;
+        if (a.rec->order != b.rec->order) return a.rec->order < b.rec->order;
+        return a.rec->arrival < b.rec->arrival;
+    });
+    const size_t n_desc = order.size();
+    std::vector<ChunkDesc> desc(n_desc);
+    std::vector<int64_t> piece_rows((size_t)n_pieces, 0);
+    uint64_t rank_base = 0;
+    for (size_t i = 0; i < n_desc; ++i) {
+        desc[i] = ChunkDesc{order[i].rec->rows, order[i].rec->count, (uint32_t)order[i].piece, rank_base};
+        rank_base += order[i].rec->count;
+        piece_rows[(size_t)order[i].piece] += order[i].rec->count;
+    }
+    // piece words on the device: [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces, then fault, bad label
+    const size_t np = (size_t)n_pieces;
+    const size_t off_pmax = np * 4, off_pbase = (np * 8 + 7) / 8 * 8, off_start = off_pbase + np * 8, off_flags = off_start + np * 8;
+    if (!s->f_desc.grow(n_desc * sizeof(ChunkDesc)) || !s->f_piece.grow(off_flags + 16))
+        return no_memory("the chunk table", n_desc * sizeof(ChunkDesc));
+    uint8_t* pw = s->f_piece.as<uint8_t>();
+    uint32_t* d_pmin = (uint32_t*)pw;
+    uint32_t* d_pmax = (uint32_t*)(pw + off_pmax);
+    uint64_t* d_pbase = (uint64_t*)(pw + off_pbase);
+    uint64_t* d_start = (uint64_t*)(pw + off_start);
+    uint32_t* d_fault = (uint32_t*)(pw + off_flags);
+    uint32_t* d_bad = d_fault + 1;
+    ST_HIP(hipMemcpyAsync(s->f_desc.p, desc.data(), n_desc * sizeof(ChunkDesc), hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(d_pmin, 0xFF, np * 4, s->stream));
+    ST_HIP(hipMemsetAsync(d_pmax, 0, np * 4, s->stream));
+    ST_HIP(hipMemsetAsync(d_fault, 0, 8, s->stream));
+    // 1. range
+    k_stitch_range<<<(unsigned)n_desc, ST_THREADS, 0, s->stream>>>(s->f_desc.as<ChunkDesc>(), d_pmin, d_pmax);
+    ST_HIP(hipGetLastError());
+    std::vector<uint32_t> pmin(np), pmax(np);
+    ST_HIP(hipMemcpyAsync(pmin.data(), d_pmin, np * 4, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(pmax.data(), d_pmax, np * 4, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    std::vector<uint64_t> pbase(np);
+    uint64_t n_positions = 0;
+    for (size_t p = 0; p < np; ++p) {
+        pbase[p] = n_positions;
+        if (piece_rows[p] > 0) {
+            if (pmin[p] > pmax[p]) return pa::set_error(PA_ERR_HIP, "stitcher finish: a piece with rows has no position range");
+            n_positions += (uint64_t)pmax[p] - pmin[p] + 1;
+            piece_first[p] = pmin[p];
+            piece_last[p] = pmax[p];
+        }
+    }
+    s->last_positions = (int64_t)n_positions;
+    // 2. widths, 3. their scan
+    const uint64_t scan_words = std::max(scan_scratch_words(n_positions), (uint64_t)1);
+    if (!s->f_width.grow(n_positions * 4) || !s->f_base.grow(n_positions * 4) || !s->f_scan.grow(scan_words * 8))
+        return no_memory("the width table", n_positions * 8);
+    ST_HIP(hipMemcpyAsync(d_pbase, pbase.data(), np * 8, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(s->f_width.p, 0, n_positions * 4, s->stream));
+    k_stitch_width<<<(unsigned)n_desc, ST_THREADS, 0, s->stream>>>(s->f_desc.as<ChunkDesc>(), d_pmin, d_pbase, s->f_width.as<uint32_t>(),
+                                                                    n_positions, d_fault);
+    ST_HIP(hipGetLastError());
+    const uint64_t* d_total = scan_exclusive<LoadU32, uint32_t>(s->stream, LoadU32{s->f_width.as<uint32_t>()}, n_positions,
+                                                                s->f_base.as<uint32_t>(), s->f_scan.as<uint64_t>());
+    ST_HIP(hipGetLastError());
+    uint64_t n_slots = 0;
+    ST_HIP(hipMemcpyAsync(&n_slots, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    if (n_slots > 0xFFFFFFFFull)
+        return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher finish: the contig needs " + std::to_string(n_slots) + " slots, the tables index 2^32 - 1");
+    s->last_slots = (int64_t)n_slots;
+    // 4. scatter, 5. check and count
+    const uint64_t letter_words = std::max(scan_scratch_words(n_slots), (uint64_t)1);
+    if (!s->f_slots.grow(n_slots * 8) || !s->f_letters.grow(n_slots) || !s->f_place.grow(n_slots * 4) || !s->f_words.grow(letter_words * 8))
+        return no_memory("the slot table", n_slots * 13);
+    s->last_scratch_bytes = (int64_t)(n_positions * 8 + n_slots * 13 + (scan_words + letter_words) * 8 + n_desc * sizeof(ChunkDesc));
+    ST_HIP(hipMemsetAsync(s->f_slots.p, 0, n_slots * 8, s->stream));
+    k_stitch_scatter<<<(unsigned)n_desc, ST_THREADS, 0, s->stream>>>(s->f_desc.as<ChunkDesc>(), d_pmin, d_pbase, s->f_base.as<uint32_t>(),
+                                                                      s->f_slots.as<unsigned long long>(), n_positions, n_slots, d_fault);
+    ST_HIP(hipGetLastError());
+    const unsigned slot_blocks = (unsigned)((n_slots + ST_THREADS - 1) / ST_THREADS);
+    if (slot_blocks) {
+        k_stitch_check<<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_slots.as<unsigned long long>(), n_slots, s->f_letters.as<uint8_t>(), d_bad);
+        ST_HIP(hipGetLastError());
+    }
+    const uint64_t* d_letters_total = scan_exclusive<LoadLetter, uint32_t>(s->stream, LoadLetter{s->f_letters.as<uint8_t>()}, n_slots,
+                                                                           s->f_place.as<uint32_t>(), s->f_words.as<uint64_t>());
+    ST_HIP(hipGetLastError());
+    uint64_t n_letters = 0;
+    uint32_t flags[2] = {0, 0};
+    ST_HIP(hipMemcpyAsync(&n_letters, d_letters_total, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(flags, d_fault, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    if (flags[0]) return pa::set_error(PA_ERR_HIP, "stitcher finish: a row fell outside its piece's tables (flags " + std::to_string(flags[0]) + ")");
+    if (flags[1]) {                                     // label_decoder[...] raises KeyError in the reference
+        *bad_label = (int32_t)flags[1];
+        return PA_OK;
+    }
+    // 6. the letters, piece after piece
+    if (!s->f_out.grow(n_letters + 1)) return no_memory("the sequence", n_letters);
+    if (slot_blocks) {
+        k_stitch_emit<<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(), n_slots, n_letters,
+                                                                 s->f_out.as<uint8_t>());
+        ST_HIP(hipGetLastError());
+    }
+    k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(d_pbase, n_pieces, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
+                                                                     n_positions, n_slots, n_letters, d_start);
+    ST_HIP(hipGetLastError());
+    std::vector<uint64_t> start(np + 1);
+    ST_HIP(hipMemcpyAsync(start.data(), d_start, np * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    start[np] = n_letters;
+    for (size_t p = 0; p < np; ++p) {
+        if (piece_rows[p] == 0) continue;               // a piece without kept rows is skipped: (-1, -1, '')
+        const int64_t length = (int64_t)(start[p + 1] - start[p]);
+        piece_length[p] = length;
+        s->pieces.push_back(PieceOut{piece_first[p], piece_last[p], (int64_t)start[p], length, (int)p});
+    }
+    std::stable_sort(s->pieces.begin(), s->pieces.end(), [](const PieceOut& a, const PieceOut& b) {
+        return a.first != b.first ? a.first < b.first : a.last < b.last;
+    });
+    s->sequence_length = (int64_t)n_letters;
+    *sequence_length = (int64_t)n_letters;
+    return PA_OK;
+}
+
+int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity) {
+    if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (capacity < s->sequence_length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take: the sequence has " + std::to_string(s->sequence_length) + " letters, room for " +
+                                                 std::to_string(capacity));
+    ST_HIP(hipSetDevice(s->device));
+    int64_t at = 0;
+    for (const PieceOut& piece : s->pieces) {
+        if (piece.length == 0) continue;
+        ST_HIP(hipMemcpyAsync(dst + at, s->f_out.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
+        at += piece.length;
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
+}
+
+int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n) {
+    if (!s || !out || n < 0) return pa::set_error(PA_ERR_INVALID, "stitcher stats: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    const int64_t v[6] = {s->rows_held, (int64_t)s->slabs.size() * ST_SLAB_ROWS * 8, s->last_slots, s->last_pieces, s->last_positions,
+                          s->last_scratch_bytes};
+    for (int32_t i = 0; i < n; ++i) out[i] = i < 6 ? v[i] : 0;
+    return PA_OK;
+}
+
+}  // extern "C"

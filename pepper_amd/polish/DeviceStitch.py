@@ -1,0 +1,301 @@
+"""The polish stitch on the device (opt-in: polish(..., device_stitch=True) / PEPPER_AMD_DEVICE_STITCH=1).
+
+replaces, for a run that opts in: pepper/modules/python/Stitch.py of the reference
+    small_chunk_stitch        :36-94    the {(position, insert index): label} merge -> pa_stitcher_* (pepper_amd/csrc/stitch.hip)
+    create_consensus_sequence :97-128   region order and pieces -> plan() below, pure host code
+perform_stitch (the host form) is untouched and stays the default; what this module writes is byte for byte its FASTA.
+
+plan() restates the loop order of the reference: regions sorted by name, then stably by (start, end), cut into pieces of
+max(2, int(n / threads) + 1) consecutive regions; inside a region the chunk ids in STRING order.  The device only needs, per
+row, its piece and a rank that grows along that loop: the last write of a key is the one with the largest rank.
+"""
+import collections
+import ctypes
+import threading
+from pathlib import Path
+
+import numpy as np
+
+from pepper_amd import _lib, h5
+from pepper_amd.polish.Options import ImageSizeOptions
+from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
+from pepper_amd.polish.perform_stitch import _log, get_file_paths_from_directory, natural_key
+
+Plan = collections.namedtuple("Plan", "order piece rank n_pieces chunk_order")
+
+
+def string_order(chunk_ids):
+    """The place of every chunk id in sorted(ids as strings): ("0", "1", "10", "11", "2", ...) -> [0, 1, 4, ...]."""
+    ids = [str(c) for c in chunk_ids]
+    place = [0] * len(ids)
+    for k, i in enumerate(sorted(range(len(ids)), key=lambda i: ids[i])):
+        place[i] = k
+    return place
+
+
+def string_order_key(chunk_id):
+    """An integer that orders decimal chunk ids as their strings order (for a caller that does not know a region's other ids
+    yet): the digits, each plus one, as an 18-digit number in base 11."""
+    text = str(int(chunk_id))
+    if int(chunk_id) < 0 or len(text) > 18:
+        raise ValueError("chunk id %r has no string-order key" % (chunk_id,))
+    key = 0
+    for k in range(18):
+        key = key * 11 + (int(text[k]) + 1 if k < len(text) else 0)
+    return key
+
+
+def plan(region_keys, threads, chunk_ids=None):
+    """region_keys: [(file name, region name, start, end)] as perform_stitch collects them (files in listing order, a file's
+    regions by name).  -> Plan: order = indices into region_keys in the order create_consensus_sequence iterates them; piece[i] /
+    rank[i] = the piece small_chunk_stitch gets region i in and its place in `order`; n_pieces; chunk_order[i] = the place of every
+    id of chunk_ids[i] in the string order small_chunk_stitch reads them in (None without chunk_ids)."""
+    n = len(region_keys)
+    order = sorted(range(n), key=lambda i: region_keys[i][1])
+    order = sorted(order, key=lambda i: (int(region_keys[i][2]), int(region_keys[i][3])))
+    size = max(MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING, int(n / max(1, threads)) + 1)
+    piece, rank = [0] * n, [0] * n
+    for k, i in enumerate(order):
+        rank[i] = k
+        piece[i] = k // size
+    n_pieces = (n + size - 1) // size
+    chunk_order = None if chunk_ids is None else [string_order(ids) for ids in chunk_ids]
+    return Plan(order, piece, rank, n_pieces, chunk_order)
+
+
+def _labels_u8(labels):
+    """Host labels of any integer type as uint8; what does not fit is 255 (no base either: KeyError if it survives)."""
+    labels = np.asarray(labels)
+    if labels.dtype == np.uint8:
+        return np.ascontiguousarray(labels)
+    return np.ascontiguousarray(np.where((labels < 0) | (labels > 255), 255, labels).astype(np.uint8))
+
+
+class DeviceStitcher(object):
+    """One pa_stitcher handle: add() while a run goes on, finish() per contig at its end.  Regions are named by the keys plan()
+    takes -- (file name, region name, start, end) -- and kept per contig in the order they first arrive."""
+
+    def __init__(self, device=0, stream=None):
+        self._lib = _lib.load()
+        self.device = int(device)
+        self._lock = threading.Lock()
+        self._contigs = {}                   # contig -> (id, {region key: id}, [region keys])
+        handle = ctypes.c_void_p()
+        _lib.check(self._lib.pa_stitcher_create(self.device, ctypes.c_void_p(stream) if stream else None, ctypes.byref(handle)))
+        self._handle = handle
+
+    @staticmethod
+    def limits():
+        """{'max_position', 'max_index', 'scan_block' (elements per workgroup of the scans), 'slab_rows'}"""
+        out = (ctypes.c_int64 * 4)()
+        _lib.check(_lib.load().pa_stitcher_limits(out, 4))
+        return dict(zip(("max_position", "max_index", "scan_block", "slab_rows"), (int(v) for v in out)))
+
+    @property
+    def handle(self):
+        if self._handle is None:
+            raise _lib.PepperAmdError("the stitcher is closed")
+        return self._handle
+
+    def contigs(self):
+        return list(self._contigs)
+
+    def regions(self, contig):
+        return list(self._contigs[contig][2]) if contig in self._contigs else []
+
+    def add(self, contig, region_keys, chunk_order, position, index, labels):
+        """Chunks of one contig: region_keys[k] = (file name, region name, start, end) of chunk k, chunk_order[k] = what orders it
+        among its region's chunks (string_order / string_order_key), position / index [n, length] integers, labels [n, length]:
+        a numpy array, or a uint8 torch tensor on this stitcher's device whose values are complete (the caller has waited for
+        the stream that wrote them)."""
+        n = len(region_keys)
+        if n == 0:
+            return
+        position = np.ascontiguousarray(position, dtype=np.int64).reshape(n, -1)
+        index = np.ascontiguousarray(index, dtype=np.int64).reshape(n, -1)
+        length = position.shape[1]
+        if index.shape != position.shape:
+            raise ValueError("position and index differ in shape")
+        on_device = hasattr(labels, "is_cuda") and labels.is_cuda and labels.device.index == self.device
+        if on_device:
+            import torch
+            if labels.dtype != torch.uint8 or labels.numel() != n * length:
+                raise ValueError("device labels must be uint8 [n, length]")
+            labels = labels.contiguous()
+            labels_ptr = labels.data_ptr()
+        else:
+            if hasattr(labels, "detach"):
+                labels = labels.detach().cpu().numpy()
+            labels = _labels_u8(labels).reshape(n, -1)
+            if labels.shape != position.shape:
+                raise ValueError("labels and position differ in shape")
+            labels_ptr = labels.ctypes.data
+        buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
+        with self._lock:
+            entry = self._contigs.get(contig)
+            if entry is None:
+                entry = (len(self._contigs), {}, [])
+            ids, new_keys = entry[1], []
+            for k in region_keys:
+                if k not in ids:
+                    ids[k] = len(ids)
+                    new_keys.append(k)
+            try:
+                region = np.array([ids[k] for k in region_keys], dtype=np.int32)
+                drop = np.array([int(k[2]) + buffer_positions if int(k[2]) > 0 else -1 for k in region_keys], dtype=np.int64)
+                order = np.ascontiguousarray(chunk_order, dtype=np.int64)
+                if order.shape != (n,):
+                    raise ValueError("chunk_order must have one value per chunk")
+                _lib.check(self._lib.pa_stitcher_add(self.handle, entry[0], n, length, position.ctypes.data, index.ctypes.data,
+                                                     labels_ptr, 1 if on_device else 0, region.ctypes.data, order.ctypes.data,
+                                                     drop.ctypes.data))
+            except BaseException:
+                for k in new_keys:           # a refused call has added nothing: its new regions are not recorded either
+                    del ids[k]
+                raise
+            entry[2].extend(new_keys)
+            self._contigs[contig] = entry
+
+    def finish(self, contig, threads, region_keys=None):
+        """The consensus of one contig as create_consensus_sequence(contig, region_keys, threads) returns it; region_keys
+        default to the contig's regions in the order they first arrived.  KeyError(label): a surviving label that is no base."""
+        with self._lock:
+            entry = self._contigs.get(contig)
+            if entry is None:
+                return ""
+            keys = list(region_keys) if region_keys is not None else list(entry[2])
+            p = plan(keys, threads)
+            known = [i for i, k in enumerate(keys) if k in entry[1]]
+            region = np.array([entry[1][keys[i]] for i in known], dtype=np.int32)
+            piece = np.array([p.piece[i] for i in known], dtype=np.int32)
+            rank = np.array([p.rank[i] for i in known], dtype=np.int64)
+            n_pieces = max(1, p.n_pieces)
+            first, last, length = (np.empty(n_pieces, np.int64) for _ in range(3))
+            total, bad = ctypes.c_int64(), ctypes.c_int32()
+            _lib.check(self._lib.pa_stitcher_finish(self.handle, entry[0], len(known), region.ctypes.data, piece.ctypes.data,
+                                                    rank.ctypes.data, n_pieces, first.ctypes.data, last.ctypes.data,
+                                                    length.ctypes.data, ctypes.byref(total), ctypes.byref(bad)))
+            if bad.value:
+                raise KeyError(int(bad.value))
+            self.last_pieces = list(zip(first.tolist(), last.tolist(), length.tolist()))
+            buf = ctypes.create_string_buffer(max(1, total.value))
+            _lib.check(self._lib.pa_stitcher_take(self.handle, buf, total.value))
+            return buf.raw[:total.value].decode()
+
+    def stats(self):
+        """{'rows', 'slab_bytes'} held, and of the last finish {'slots', 'pieces', 'positions', 'table_bytes'}"""
+        out = (ctypes.c_int64 * 6)()
+        _lib.check(self._lib.pa_stitcher_stats(self.handle, out, 6))
+        return dict(zip(("rows", "slab_bytes", "slots", "pieces", "positions", "table_bytes"), (int(v) for v in out)))
+
+    def write_fasta(self, output_prefix, threads):
+        """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file)."""
+        output_path = output_prefix + '_pepper_polished.fa'
+        Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
+        with open(output_path, 'w') as fasta:
+            for contig in sorted(self.contigs(), key=natural_key):
+                sequence = self.finish(contig, threads)
+                _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
+                if len(sequence) > 0:
+                    fasta.write('>' + contig + "\n")
+                    fasta.write(sequence + "\n")
+        return output_path
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.pa_stitcher_destroy(self._handle)
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *args):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _read_region(hdf5_file, prefix):
+    """The chunks of one region group in string order of their ids -> [(position, index, labels)] blocks of [n, length] rows
+    (one block of all chunks where they have the pipeline's length, else one block per chunk)."""
+    try:
+        positions, indices, bases = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH)
+        return [(positions, indices, bases)] if len(positions) else []
+    except h5.H5Error:                  # chunks of another length, or more of them than one call takes: one by one
+        blocks = []
+        for chunk in sorted(set(hdf5_file.keys(prefix)) - {'contig_start', 'contig_end'}):
+            row = [np.asarray(hdf5_file[prefix + '/' + chunk + '/' + name], dtype=np.int64).reshape(1, -1)
+                   for name in ('position', 'index', 'bases')]
+            if row[0].size:
+                blocks.append(tuple(row))
+        return blocks
+
+
+class _Held(object):
+    """Chunks of one contig read from the files, handed to the stitcher a few thousand at a time (an add() is two launches and
+    two waits whatever its size)."""
+    CHUNKS = 8192
+
+    def __init__(self, stitcher, contig):
+        self.stitcher, self.contig = stitcher, contig
+        self.keys, self.order, self.blocks = [], [], []
+
+    def take(self, key, first_order, positions, indices, bases):
+        n = len(positions)
+        if self.blocks and self.blocks[0][0].shape[1] != positions.shape[1]:
+            self.flush()
+        self.keys.extend([key] * n)
+        self.order.extend(range(first_order, first_order + n))
+        self.blocks.append((positions, indices, bases))
+        if len(self.keys) >= self.CHUNKS:
+            self.flush()
+
+    def flush(self):
+        if self.keys:
+            position, index, labels = (np.concatenate([b[k] for b in self.blocks]) for k in range(3))
+            self.stitcher.add(self.contig, self.keys, self.order, position, index, labels)
+        self.keys, self.order, self.blocks = [], [], []
+
+
+def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None):
+    """perform_stitch(hdf_file_path, output_path, threads) with the merge on the device: the same files read, the same FASTA
+    written.  stats: a dict that receives the handle's stats() after the last contig."""
+    all_prediction_files = get_file_paths_from_directory(hdf_file_path)
+    all_contigs = set()
+    for prediction_file in all_prediction_files:
+        with h5.File(prediction_file, 'r') as hdf5_file:
+            if 'predictions' in hdf5_file.keys():
+                all_contigs.update(hdf5_file.keys('predictions'))
+    output_path = output_path + '_pepper_polished.fa'
+    Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
+    with DeviceStitcher(device) as stitcher, open(output_path, 'w') as fasta:
+        for contig in sorted(all_contigs, key=natural_key):
+            _log("PROCESSING CONTIG: " + contig)
+            all_chunk_keys = []
+            held = _Held(stitcher, contig)
+            for prediction_file in all_prediction_files:
+                with h5.File(prediction_file, 'r') as hdf5_file:
+                    if 'predictions' not in hdf5_file.keys() or contig not in hdf5_file.keys('predictions'):
+                        continue
+                    regions = hdf5_file.list_polish_regions(contig)
+                    all_chunk_keys.extend((prediction_file, name, start, end) for name, start, end in regions)
+                    for name, start, end in regions:
+                        key, at = (prediction_file, name, start, end), 0
+                        # (the group is read by the name small_chunk_stitch rebuilds: contig-start-end)
+                        for positions, indices, bases in _read_region(hdf5_file, 'predictions/' + contig + '/' + contig + '-' +
+                                                                      str(start) + '-' + str(end)):
+                            held.take(key, at, positions, indices, bases)
+                            at += len(positions)
+            held.flush()
+            sequence = stitcher.finish(contig, threads, all_chunk_keys)
+            _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
+            if len(sequence) > 0:
+                fasta.write('>' + contig + "\n")
+                fasta.write(sequence + "\n")
+        if stats is not None:
+            stats.update(stitcher.stats())
+    return output_path

@@ -119,14 +119,28 @@ class _Gather(object):
 
     def _predict_and_write(self, st, n):
         entry, model = self.owner._model(self.device)
+        owner = self.owner
+        feed = None
         try:
             torch.cuda.set_device(self.device)
             with torch.cuda.stream(model._stream):          # (this thread's "current stream": not the process-wide default one)
                 labels, phred = model.predict_chunks(st.buffer[:n])
-                labels, phred = labels.cpu().numpy(), phred.cpu().numpy()
+                if owner.device_stitch:
+                    # the labels stay where the model left them (a pass on another device hands them over through the host)
+                    if self.device == owner.stitch_device(self.device):
+                        model._stream.synchronize()
+                        feed = labels
+                    else:
+                        feed = labels.cpu().numpy()
+                if owner.keep_predictions:
+                    labels, phred = labels.cpu().numpy(), phred.cpu().numpy()
         finally:
             entry["free"].put(model)
         meta = st.meta[:n]
+        if feed is not None:
+            owner.stitch_add(meta, st.position[:n], st.index[:n], feed)
+        if not owner.keep_predictions:
+            return
         contigs = np.array([m[0] for m in meta], dtype='S')
         self.owner.store().write_predictions_block(contigs, np.array([m[1] for m in meta], np.int64), np.array([m[2] for m in meta], np.int64),
                                                    np.array([m[3] for m in meta], np.int64), st.position[:n], st.index[:n], labels, phred)
@@ -165,8 +179,16 @@ class FusedConsensus(object):
     PASS_CHUNKS = int(os.environ.get("PEPPER_AMD_FUSED_PASS_CHUNKS", 16384))      # a pass that fills the chip
     HANDLES = 2          # passes in flight per device (own stream and workspace each)
 
-    def __init__(self, model_path, output_directory, batch_invariant=None):
+    def __init__(self, model_path, output_directory, batch_invariant=None, device_stitch=False, keep_predictions=True,
+                 stitch_device=None):
+        """device_stitch: the passes hand their labels to one DeviceStitcher (pepper_amd/polish/DeviceStitch.py) on stitch_device
+        (default: the device of the first pass) and polish() writes the FASTA from it; the prediction files are then written only
+        with keep_predictions."""
         self.model_path = model_path
+        self.device_stitch = bool(device_stitch)
+        self.keep_predictions = bool(keep_predictions) or not self.device_stitch
+        self._stitch_device = stitch_device
+        self.stitcher = None
         self.batch_invariant = batch_invariant       # (None: PEPPER_AMD_BATCH_INVARIANT decides, per handle)
         self.output_directory = output_directory
         self.models, self.models_lock = {}, threading.Lock()
@@ -191,6 +213,29 @@ class FusedConsensus(object):
     def check(self):
         if self.error is not None:
             raise RuntimeError("fused consensus: a model pass failed") from self.error
+
+    # ---- the device stitch: one handle for the run ----
+    def stitch_device(self, default):
+        with self.models_lock:
+            if self._stitch_device is None:
+                self._stitch_device = default
+            return self._stitch_device
+
+    def stitch_add(self, meta, position, index, labels):
+        """The chunks of one pass: runs of one contig go to the stitcher in one call each.  Regions are keyed as perform_stitch
+        would find them in a prediction file; a chunk's order is its id's place among decimal strings."""
+        from pepper_amd.polish.DeviceStitch import DeviceStitcher, string_order_key
+        with self.models_lock:
+            if self.stitcher is None:
+                self.stitcher = DeviceStitcher(self._stitch_device)
+        a, n = 0, len(meta)
+        while a < n:
+            b = a + 1
+            while b < n and meta[b][0] == meta[a][0]:
+                b += 1
+            keys = [("", m[0] + "-" + str(m[1]) + "-" + str(m[2]), m[1], m[2]) for m in meta[a:b]]
+            self.stitcher.add(meta[a][0], keys, [string_order_key(m[3]) for m in meta[a:b]], position[a:b], index[a:b], labels[a:b])
+            a = b
 
     # ---- the prediction files: one per pass thread ----
     def store(self):
@@ -286,6 +331,9 @@ class FusedConsensus(object):
                 model.close()
         self.models.clear()
         self.gathers.clear()
+        if failed and self.stitcher is not None:
+            self.stitcher.close()
+            self.stitcher = None
         if err is not None:
             raise RuntimeError("fused consensus failed") from err
 

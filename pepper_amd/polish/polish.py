@@ -6,7 +6,7 @@ import sys
 import time
 from datetime import datetime
 
-from pepper_amd.polish.ImageGenerationUI import UserInterfaceSupport
+from pepper_amd.polish.ImageGenerationUI import UserInterfaceSupport, parse_device_ids
 from pepper_amd.polish.call_consensus import call_consensus
 from pepper_amd.polish.make_images import make_images
 from pepper_amd.polish.perform_stitch import perform_stitch
@@ -18,12 +18,16 @@ def _log(message):
 
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
-           num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0):
+           num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0, device_stitch=None,
+           keep_predictions=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
     PEPPER_AMD_BATCH_INVARIANT=1): the model handles of either form run in batch-invariant mode, so both forms, and any
-    device_ids, give the same predictions bit for bit.  downsample_rate: make_images' (no effect on the output)."""
+    device_ids, give the same predictions bit for bit.  downsample_rate: make_images' (no effect on the output).
+    device_stitch (default: PEPPER_AMD_DEVICE_STITCH=1): step 3 merges the predictions on the device
+    (pepper_amd/polish/DeviceStitch.py) and writes the FASTA perform_stitch would; in the fused form the labels go from the model
+    to the stitcher without leaving the device, and the prediction files are written only with keep_predictions (default: not)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
@@ -47,16 +51,22 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     t0 = time.perf_counter()
     if fused_inference is None:
         fused_inference = os.environ.get("PEPPER_AMD_FUSED_POLISH") == "1"
+    if device_stitch is None:
+        device_stitch = _lib.device_stitch()
+    stitcher = None
     if fused_inference:
         from pepper_amd.polish.fused import FusedConsensus
         UserInterfaceSupport.handle_output_directory(prediction_output_directory)
         _log("STEP 1+2: GENERATING IMAGES AND RUNNING INFERENCE (FUSED) -> " + prediction_output_directory)
-        sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant)
+        sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant, device_stitch=device_stitch,
+                              keep_predictions=bool(keep_predictions) or not device_stitch,
+                              stitch_device=parse_device_ids(device_ids)[0])
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
                         stats=image_stats, downsample_rate=downsample_rate)
         finally:
             sink.close()
+        stitcher = sink.stitcher
         t1 = t2 = time.perf_counter()
     else:
         make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, stats=image_stats,
@@ -67,7 +77,20 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
                        gpu_mode, threads, batch_invariant=batch_invariant)
         t2 = time.perf_counter()
     _log("STEP 3: RUNNING STITCH -> " + output_dir)
-    perform_stitch(prediction_output_directory, output_dir, threads)
+    if not device_stitch:
+        perform_stitch(prediction_output_directory, output_dir, threads)
+    elif not fused_inference:
+        from pepper_amd.polish.DeviceStitch import stitch_directory
+        stitch_directory(prediction_output_directory, output_dir, threads, device=parse_device_ids(device_ids)[0])
+    elif stitcher is None:                   # (no chunk was predicted: perform_stitch over no files writes an empty FASTA)
+        open(output_dir + '_pepper_polished.fa', 'w').close()
+    else:
+        try:
+            stitcher.write_fasta(output_dir, threads)
+            if stage_walls is not None:
+                stage_walls["device_stitch_stats"] = stitcher.stats()
+        finally:
+            stitcher.close()
     if stage_walls is not None:
         stage_walls.update(make_images=t1 - t0, call_consensus=t2 - t1, perform_stitch=time.perf_counter() - t2)
         stage_walls["image_stage_seconds_summed_over_workers"] = image_stats

@@ -7,6 +7,8 @@
   python tools/bench_e2e.py polish <dir> [draft_bases=64000000] [coverage=60] [runs=3]
   python tools/bench_e2e.py polish_fused <dir> ...           the same with fused_inference=True (pepper_amd/polish/fused.py)
       pepper_amd.polish.polish.polish (pepper polish, polish.py:94-117): BAM + draft + checkpoint -> images -> predictions -> FASTA
+  python tools/bench_e2e.py polish_device_stitch <dir> ... / polish_fused_device_stitch <dir> ...
+      either form with device_stitch=True (pepper_amd/polish/DeviceStitch.py; without the suffix PEPPER_AMD_DEVICE_STITCH decides)
 
 Each prints one JSON line: the run with the median wall of `runs` (after one untimed run that loads the libraries, grows the
 workspaces and leaves the input files in the page cache), every run's wall, the stage walls and the units per second."""
@@ -129,7 +131,7 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False):
                 info["genome_bases"] / 1e6, info["coverage"], info["records"], info["bam_bytes"] / 1e9), "synth_seconds": info["seconds"]}
 
 
-def polish_job(work, bases, coverage, n_runs, fused=False):
+def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None):
     from pepper_amd.hostinfo import usable_cpus
     from pepper_amd.polish.polish import polish
     info = synth(work, bases, coverage)
@@ -143,8 +145,9 @@ def polish_job(work, bases, coverage, n_runs, fused=False):
         walls = {}
         t0 = time.perf_counter()
         polish(os.path.join(work, "reads.bam"), os.path.join(work, "draft.fa"), out, threads, None, model, 512, True, "0", 0, stage_walls=walls,
-               fused_inference=fused)
+               fused_inference=fused, device_stitch=device_stitch)
         dt = time.perf_counter() - t0
+        stitch_stats = walls.pop("device_stitch_stats", None)
         fasta = glob.glob(out + "*.fa")
         size = os.path.getsize(fasta[0]) if fasta else 0
         images = sum(os.path.getsize(p) for p in glob.glob(out + "images_*/*.hdf"))
@@ -152,16 +155,20 @@ def polish_job(work, bases, coverage, n_runs, fused=False):
             stages = walls.pop("image_stage_seconds_summed_over_workers", None) or {}
             runs.append({"seconds": round(dt, 3), "stage_walls": {n: round(v, 3) for n, v in walls.items()}, "polished_fasta_bytes": size,
                          "image_stage_seconds_summed_over_workers": {n: round(v, 2) for n, v in sorted(stages.items()) if isinstance(v, float)},
-                         "image_file_mb": round(images / 1e6, 1)})
+                         "image_file_mb": round(images / 1e6, 1),
+                         "prediction_file_mb": round(sum(os.path.getsize(p) for p in glob.glob(out + "predictions_*/*.hdf")) / 1e6, 1),
+                         "device_stitch_stats": stitch_stats})
         shutil.rmtree(out, ignore_errors=True)
     mid = median_run(runs)
     longest = max(mid["stage_walls"].values())
-    return {"metric": "polish end to end (BAM + draft + checkpoint -> polished FASTA)" + (", images and inference fused" if fused else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
+    return {"metric": "polish end to end (BAM + draft + checkpoint -> polished FASTA)" + (", images and inference fused" if fused else "") +
+                      (", device stitch" if device_stitch else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
             "unit": "Mb of draft/s", "seconds": mid["seconds"], "runs_seconds": [r["seconds"] for r in runs], "stage_walls": mid["stage_walls"],
             "wall_over_longest_stage": round(mid["seconds"] / longest, 3), "polished_fasta_bytes": mid["polished_fasta_bytes"],
             "image_stage_seconds_summed_over_workers": mid["image_stage_seconds_summed_over_workers"],
             "runs_stage_walls": [r["stage_walls"] for r in runs],
-            "image_file_mb": mid["image_file_mb"], "threads": threads,
+            "image_file_mb": mid["image_file_mb"], "prediction_file_mb": mid["prediction_file_mb"],
+            "device_stitch_stats": mid["device_stitch_stats"], "threads": threads,
             "data": "synthetic BAM %.0f Mb at %.0fx, %d records, %.2f GB (tools/synth_bam), seeded random-init checkpoint" % (
                 info["genome_bases"] / 1e6, info["coverage"], info["records"], info["bam_bytes"] / 1e9), "synth_seconds": info["seconds"]}
 
@@ -173,7 +180,8 @@ if __name__ == "__main__":
     n_runs = int(sys.argv[5]) if len(sys.argv) > 5 else 3
     if kind == "call_variant_fused":
         print(json.dumps(call_variant_job(work, bases, coverage, n_runs, fused=True)))
-    elif kind == "polish_fused":
-        print(json.dumps(polish_job(work, bases, coverage, n_runs, fused=True)))
+    elif kind.startswith("polish"):
+        print(json.dumps(polish_job(work, bases, coverage, n_runs, fused="fused" in kind,
+                                    device_stitch=True if kind.endswith("device_stitch") else None)))
     else:
         print(json.dumps((call_variant_job if kind == "call_variant" else polish_job)(work, bases, coverage, n_runs)))

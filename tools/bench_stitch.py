@@ -1,6 +1,8 @@
-"""Stitch rate (prediction HDF5 files -> polished FASTA; host only): perform_stitch with the merge inside the I/O library
-(default) and with the numpy form (PEPPER_AMD_STITCH_NUMPY=1), one and eight workers.
-    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm]"""
+"""Stitch rate (prediction HDF5 files -> polished FASTA): perform_stitch with the merge inside the I/O library (default) and with
+the numpy form (PEPPER_AMD_STITCH_NUMPY=1), one and eight workers; --device adds the same set through the device stitch
+(pepper_amd/polish/DeviceStitch.py stitch_directory: the files read on the host, the merge on the GPU) and checks its FASTA
+against the host's.
+    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device]"""
 import argparse
 import json
 import os
@@ -22,6 +24,7 @@ def main():
     ap.add_argument("--chunks", type=int, default=65536)
     ap.add_argument("--files", type=int, default=4)
     ap.add_argument("--dir", default=None)
+    ap.add_argument("--device", action="store_true", help="also run the set through the device stitch")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
@@ -54,8 +57,20 @@ def main():
                 dt = time.perf_counter() - t0
                 runs.append({"merge": "numpy" if numpy_form else "library", "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out)})
+        if args.device:
+            from pepper_amd.polish.DeviceStitch import stitch_directory
+            host = {threads: open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read() for threads in (1, 8)}
+            for threads in (1, 8):
+                for repeat in range(2):                    # (the first run loads the library and grows the handle's tables)
+                    stats = {}
+                    t0 = time.perf_counter()
+                    out = stitch_directory(pred, os.path.join(tmp, "dev%d%d" % (threads, repeat)), threads, stats=stats)
+                    dt = time.perf_counter() - t0
+                    runs.append({"merge": "device", "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
+                                 "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                                 "equals_host": open(out, "rb").read() == host[threads], "stats": stats})
         from pepper_amd.hostinfo import usable_cpus
-        print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host)", "chunks": 2 * regions, "files": args.files,
+        print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
     finally:
         shutil.rmtree(tmp)
