@@ -349,18 +349,32 @@ int pa_stitcher_limits(int64_t* out, int32_t n);
 int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
                     const uint8_t* labels, int32_t labels_on_device, const int32_t* region, const int64_t* chunk_order,
                     const int64_t* drop_below);
+/* pa_stitcher_add with the rows' qualities: phred uint8 [n_chunks, chunk_len] lies where labels lies (labels_on_device governs
+ * both).  A kept row carries its phred in the top byte of its packed word (rows added through pa_stitcher_add carry 0 there);
+ * the row that supplies a letter's label supplies its quality.  Qualities are not switched on anywhere: a finish produces them
+ * whenever EVERY chunk it merges was added through this entry point (a contig without chunks has them, empty). */
+int pa_stitcher_add_qual(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position,
+                         const int64_t* index, const uint8_t* labels, const uint8_t* phred, int32_t labels_on_device,
+                         const int32_t* region, const int64_t* chunk_order, const int64_t* drop_below);
 /* Merge what the handle holds of `contig`: per region id its piece (0 .. n_pieces - 1) and its rank in the loop order.
  * piece_first / piece_last / piece_length [n_pieces]: first and last kept position (-1, -1 for a piece without kept rows) and
  * letters of every piece; *sequence_length letters in all, the pieces ordered by (first, last) as take() copies them.
  * *bad_label != 0: a surviving label that is no base (the reference's label_decoder raises KeyError); no sequence then.
- * The handle keeps the rows: a contig may be finished again, with another plan. */
+ * The handle keeps the rows: a contig may be finished again, with another plan.
+ * PA_ERR_UNSUPPORTED, before any launch: the contig keeps more than 2^48 - 1 rows (the rank's share of the 64-bit word
+ * (rank + 1) << 16 | phred << 8 | label that decides a key's last write). */
 int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const int32_t* region, const int32_t* piece, const int64_t* rank,
                        int32_t n_pieces, int64_t* piece_first, int64_t* piece_last, int64_t* piece_length, int64_t* sequence_length,
                        int32_t* bad_label);
 /* The sequence of the last finish (capacity >= its length; no terminator). */
 int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity);
+/* The qualities of the last finish, one per letter of pa_stitcher_take and in its order: Sanger text, '!' + min(phred, 93) of
+ * the row whose label the letter is (capacity >= the sequence length; no terminator).  PA_ERR_INVALID: no finish yet; the last
+ * finish produced no sequence (a bad label, a failure); a chunk of its contig was added without qualities; capacity is short.
+ * The handle stays usable. */
+int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
 /* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
- * its tables. */
+ * its tables (the quality buffer among them when the finish produced qualities). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
 
 #ifdef __cplusplus

@@ -212,6 +212,9 @@ int pa_h5_write_polish_predictions(pa_h5* f, int32_t n, int32_t seq_len, const c
  * caller's arrays (max_chunks rows); *n_chunks = number of chunks found (Stitch.py:36-62 reads them one dataset at a time). */
 int pa_h5_read_polish_prediction_region(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks,
                                         int64_t* position, int64_t* index, uint8_t* bases, int32_t* n_chunks);
+/* The same with every chunk's phred_score (uint8 [seq]) beside its bases, for a stitch that writes qualities. */
+int pa_h5_read_polish_prediction_region_qual(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks,
+                                             int64_t* position, int64_t* index, uint8_t* bases, uint8_t* phred, int32_t* n_chunks);
 
 /* The chunks of one polish region into the image file in one call: summaries/<name>/{image u8 [seq,features], label u8
  * [seq], position, index int64 [seq], contig (vlen string), region_start, region_end, chunk_id int64}

@@ -124,9 +124,12 @@ SYMBOLS = [
     ("pa_stitcher_limits", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_stitcher_add", ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p,
                                        c_void_p]),
+    ("pa_stitcher_add_qual", ctypes.c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                            c_void_p, c_void_p]),
     ("pa_stitcher_finish", ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
                                           ctypes.POINTER(c_int64), ctypes.POINTER(c_int32)]),
     ("pa_stitcher_take", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
+    ("pa_stitcher_take_qualities", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     # include/pepper_amd_realign.h
     ("pa_realigner_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
@@ -278,6 +281,15 @@ def device_stitch():
     """PEPPER_AMD_DEVICE_STITCH=1: polish() merges the predictions on the device (pa_stitcher_*; pepper_amd/polish/DeviceStitch.py)
     instead of perform_stitch on the host.  Unset or any other value: on the host."""
     return os.environ.get(DEVICE_STITCH_ENV, "0") == "1"
+
+
+POLISH_QUALITIES_ENV = "PEPPER_AMD_POLISH_QUALITIES"
+
+
+def polish_qualities():
+    """PEPPER_AMD_POLISH_QUALITIES=1: polish() writes <prefix>_pepper_polished.fastq beside the FASTA, every base with the phred of
+    the prediction row that supplied it.  Unset or any other value: the FASTA alone."""
+    return os.environ.get(POLISH_QUALITIES_ENV, "0") == "1"
 
 
 def check(rc):

@@ -999,10 +999,9 @@ static herr_t collect_names(hid_t, const char* name, const H5L_info_t*, void* p)
     return 0;
 }
 
-int pa_h5_read_polish_prediction_region(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks,
-                                        int64_t* position, int64_t* index, uint8_t* bases, int32_t* n_chunks) {
-    if (!f || !region_path || seq_len <= 0 || max_chunks <= 0 || !position || !index || !bases || !n_chunks)
-        return fail("bad argument");
+// phred == nullptr: pa_h5_read_polish_prediction_region, else ..._qual
+static int read_prediction_region(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks, int64_t* position,
+                                  int64_t* index, uint8_t* bases, uint8_t* phred, int32_t* n_chunks) {
     Quiet q;
     hid_t g = H5Gopen2(f->file, region_path, H5P_DEFAULT);
     if (g < 0) return fail(std::string("no group '") + region_path + "'");
@@ -1021,10 +1020,25 @@ int pa_h5_read_polish_prediction_region(pa_h5* f, const char* region_path, int32
         rc = read_numeric(c, "position", H5T_NATIVE_INT64, seq_len, position + i * (size_t)seq_len, where);
         if (!rc) rc = read_numeric(c, "index", H5T_NATIVE_INT64, seq_len, index + i * (size_t)seq_len, where);
         if (!rc) rc = read_numeric(c, "bases", H5T_NATIVE_UINT8, seq_len, bases + i * (size_t)seq_len, where);
+        if (!rc && phred) rc = read_numeric(c, "phred_score", H5T_NATIVE_UINT8, seq_len, phred + i * (size_t)seq_len, where);
         H5Gclose(c);
     }
     H5Gclose(g);
     return rc;
+}
+
+int pa_h5_read_polish_prediction_region(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks,
+                                        int64_t* position, int64_t* index, uint8_t* bases, int32_t* n_chunks) {
+    if (!f || !region_path || seq_len <= 0 || max_chunks <= 0 || !position || !index || !bases || !n_chunks)
+        return fail("bad argument");
+    return read_prediction_region(f, region_path, seq_len, max_chunks, position, index, bases, nullptr, n_chunks);
+}
+
+int pa_h5_read_polish_prediction_region_qual(pa_h5* f, const char* region_path, int32_t seq_len, int32_t max_chunks,
+                                             int64_t* position, int64_t* index, uint8_t* bases, uint8_t* phred, int32_t* n_chunks) {
+    if (!f || !region_path || seq_len <= 0 || max_chunks <= 0 || !position || !index || !bases || !phred || !n_chunks)
+        return fail("bad argument");
+    return read_prediction_region(f, region_path, seq_len, max_chunks, position, index, bases, phred, n_chunks);
 }
 
 int pa_h5_write_polish_image_chunks(pa_h5* f, const char* names, int32_t n, int32_t seq_len, int32_t features,

@@ -7,14 +7,19 @@
 // The merge needs no sort.  A piece's keys are dense: positions span [first, last] and a position holds max(index) + 1 keys, so
 //   width[piece, position] = max(index) + 1              (atomicMax)
 //   base                   = exclusive scan of the widths  (the slot of key (position, 0))
-//   slot[base + index]     = max over its writers of ((rank + 1) << 8 | label)    (64-bit atomicMax)
-// where rank numbers the kept rows of the contig in the reference's loop order.  An integer maximum does not depend on the
+//   slot[base + index]     = max over its writers of ((rank + 1) << 16 | phred << 8 | label)    (64-bit atomicMax)
+// where rank numbers the kept rows of the contig in the reference's loop order.  Ranks are distinct, so the rank alone decides
+// the maximum and the phred and the label of the winner ride along.  An integer maximum does not depend on the
 // order the rows arrive in, so the winner is the dictionary's last write whatever the schedule.  A second scan over "the winner is
 // a base" gives every letter its place.  Both scans are reduce-then-scan over separate launches (block sums, scan of the sums,
 // add back): no workgroup ever waits for another one.
 //
 // add() is the streaming half: a count kernel and a compaction kernel per call keep the rows the dictionary would take (stored
 // order), 8 bytes each, in fixed-size slabs that are never moved.
+//
+// Qualities (pa_stitcher_add_qual, pa_stitcher_take_qualities): a row added with its phred carries it above the position, the
+// scatter word carries it between the rank and the label, and the emit that places the letters places, from the same winner,
+// chr(33 + min(phred, 93)) into a second buffer -- no further scan, no further wait.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -39,12 +44,17 @@ constexpr int ST_B = ST_THREADS * ST_ITEMS;             // scan elements per wor
 constexpr int64_t ST_SLAB_ROWS = 1 << 20;               // packed rows per slab: 8 MiB (pa_stitcher_limits [3])
 constexpr int64_t ST_MAX_POSITION = 0xFFFFFFFFll;
 constexpr int64_t ST_MAX_INDEX = 0xFFFFll;
+constexpr uint64_t ST_MAX_ROWS = (1ull << 48) - 1;      // rank + 1 has 48 bits of the scatter word
+constexpr uint32_t ST_MAX_QUALITY = 93;                 // Sanger: '!' + 93 = '~'
 
-// packed row: position << 24 | index << 8 | label
-PA_DEV uint64_t pack_row(int64_t p, int64_t x, uint8_t label) { return ((uint64_t)p << 24) | ((uint64_t)x << 8) | label; }
+// packed row: phred << 56 | position << 24 | index << 8 | label
+PA_DEV uint64_t pack_row(int64_t p, int64_t x, uint8_t label, uint8_t phred) {
+    return ((uint64_t)phred << 56) | ((uint64_t)p << 24) | ((uint64_t)x << 8) | label;
+}
 PA_DEV uint32_t row_position(uint64_t v) { return (uint32_t)(v >> 24); }
 PA_DEV uint32_t row_index(uint64_t v) { return (uint32_t)(v >> 8) & 0xFFFFu; }
 PA_DEV uint32_t row_label(uint64_t v) { return (uint32_t)v & 0xFFu; }
+PA_DEV uint32_t row_phred(uint64_t v) { return (uint32_t)(v >> 56); }
 
 // the rows small_chunk_stitch keeps: position >= 0, index >= 0, and past the overlap of a region that does not start at 0
 // (drop_below = start + 2 * MIN_IMAGE_OVERLAP there, -1 elsewhere)
@@ -84,8 +94,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_count(const int64_t* __re
 }
 
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_compact(const int64_t* __restrict__ pos, const int64_t* __restrict__ idx,
-                                                               const uint8_t* __restrict__ labels, const int64_t* __restrict__ drop_below,
-                                                               int chunk_len, const int32_t* __restrict__ kept,
+                                                               const uint8_t* __restrict__ labels, const uint8_t* __restrict__ phred,
+                                                               const int64_t* __restrict__ drop_below, int chunk_len,
+                                                               const int32_t* __restrict__ kept,
                                                                uint64_t* const* __restrict__ dst_of) {
     __shared__ int s_wave[ST_THREADS / 64];
     const int c = blockIdx.x;
@@ -114,7 +125,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_compact(const int64_t* __
             total += s_wave[w];
         }
         const int o = base + wave_base + before;
-        if (keep && o < room) dst[o] = pack_row(p, x, labels[at + i]);
+        if (keep && o < room) dst[o] = pack_row(p, x, labels[at + i], phred ? phred[at + i] : (uint8_t)0);      // (phred: uniform)
         base += total;
         __syncthreads();
     }
@@ -172,7 +183,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_scatter(const ChunkDesc* 
         const uint64_t at = base + (row_position(v) - first);
         uint64_t slot = n_slots;
         if (at < n_positions) slot = (uint64_t)slot_base[at] + row_index(v);
-        if (slot < n_slots) atomicMax(&slots[slot], (unsigned long long)(((d.rank_base + r + 1) << 8) | row_label(v)));
+        if (slot < n_slots)
+            atomicMax(&slots[slot], (unsigned long long)(((d.rank_base + r + 1) << 16) | ((uint64_t)row_phred(v) << 8) | row_label(v)));
         else atomicOr(fault, 2u);
     }
 }
@@ -189,12 +201,18 @@ __global__ __launch_bounds__(ST_THREADS) void k_stitch_check(const unsigned long
     letters[i] = letter;
 }
 
+// QUAL: the winner's phred, clamped and offset, goes to the letter's place in `qual` as well
+template <bool QUAL>
 __global__ __launch_bounds__(ST_THREADS) void k_stitch_emit(const uint8_t* __restrict__ letters, const uint32_t* __restrict__ place,
-                                                            uint64_t n_slots, uint64_t n_letters, uint8_t* __restrict__ out) {
+                                                            const unsigned long long* __restrict__ slots, uint64_t n_slots,
+                                                            uint64_t n_letters, uint8_t* __restrict__ out, uint8_t* __restrict__ qual) {
     const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
     if (i >= n_slots) return;
     const uint8_t letter = letters[i];
-    if (letter && place[i] < n_letters) out[place[i]] = letter;
+    if (letter && place[i] < n_letters) {
+        out[place[i]] = letter;
+        if (QUAL) qual[place[i]] = (uint8_t)(33u + min(((uint32_t)slots[i] >> 8) & 0xFFu, ST_MAX_QUALITY));
+    }
 }
 
 // where every piece's slots and letters begin (pieces lie one after the other in both)
@@ -339,6 +357,7 @@ struct ChunkRec {
     uint64_t arrival;
     uint64_t* rows;
     uint32_t count;
+    bool qualities;                                     // added through pa_stitcher_add_qual: its rows carry their phred
 };
 
 struct PieceOut {
@@ -360,11 +379,14 @@ struct pa_stitcher {
     uint64_t arrivals = 0;
     int64_t rows_held = 0;
     // add's staging
-    Buffer a_pos, a_idx, a_lab, a_drop, a_kept, a_refused, a_dst;
-    // finish's tables
-    Buffer f_desc, f_piece, f_width, f_base, f_slots, f_letters, f_place, f_out, f_scan, f_words;
+    Buffer a_pos, a_idx, a_lab, a_phr, a_drop, a_kept, a_refused, a_dst;
+    // finish's tables (f_qual: only once a contig came with qualities)
+    Buffer f_desc, f_piece, f_width, f_base, f_slots, f_letters, f_place, f_out, f_qual, f_scan, f_words;
     std::vector<PieceOut> pieces;                       // of the last finish, in output order
     int64_t sequence_length = 0;
+    bool finished = false;                              // a finish has run: the three below speak of it
+    bool contig_qualities = false;                      // every chunk of its contig came with qualities
+    bool have_qualities = false;                        // ... and it got as far as the emit: f_qual holds them
     int64_t last_slots = 0, last_pieces = 0, last_positions = 0, last_scratch_bytes = 0;
 };
 
@@ -382,8 +404,8 @@ int no_memory(const char* what, uint64_t bytes) {
 }
 
 std::vector<Buffer*> buffers_of(pa_stitcher* s) {
-    return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece, &s->f_width,
-            &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_scan, &s->f_words};
+    return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
+            &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words};
 }
 
 }  // namespace
@@ -429,19 +451,25 @@ void pa_stitcher_destroy(pa_stitcher* s) {
     delete s;
 }
 
-int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
-                    const uint8_t* labels, int32_t labels_on_device, const int32_t* region, const int64_t* chunk_order,
-                    const int64_t* drop_below) {
+}  // extern "C"
+
+namespace {
+
+// pa_stitcher_add (with_phred false, phred unused) and pa_stitcher_add_qual
+int stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
+                 const uint8_t* labels, const uint8_t* phred, bool with_phred, int32_t labels_on_device, const int32_t* region,
+                 const int64_t* chunk_order, const int64_t* drop_below) {
     if (!s || n_chunks < 0 || chunk_len < 0) return pa::set_error(PA_ERR_INVALID, "stitcher add: null handle or negative size");
     if (n_chunks == 0 || chunk_len == 0) return PA_OK;
-    if (!position || !index || !labels || !region || !chunk_order || !drop_below)
+    if (!position || !index || !labels || (with_phred && !phred) || !region || !chunk_order || !drop_below)
         return pa::set_error(PA_ERR_INVALID, "stitcher add: null array");
     std::lock_guard<std::mutex> guard(s->lock);
     ST_HIP(hipSetDevice(s->device));
     const size_t n = (size_t)n_chunks, rows = n * (size_t)chunk_len;
     if (!s->a_pos.grow(rows * 8) || !s->a_idx.grow(rows * 8) || !s->a_drop.grow(n * 8) || !s->a_kept.grow(n * 4) ||
-        !s->a_refused.grow(n * 4) || !s->a_dst.grow(n * 8) || (!labels_on_device && !s->a_lab.grow(rows)))
-        return no_memory("the staged chunks", rows * 17);
+        !s->a_refused.grow(n * 4) || !s->a_dst.grow(n * 8) || (!labels_on_device && !s->a_lab.grow(rows)) ||
+        (with_phred && !labels_on_device && !s->a_phr.grow(rows)))
+        return no_memory("the staged chunks", rows * (with_phred ? 18 : 17));
     ST_HIP(hipMemcpyAsync(s->a_pos.p, position, rows * 8, hipMemcpyHostToDevice, s->stream));
     ST_HIP(hipMemcpyAsync(s->a_idx.p, index, rows * 8, hipMemcpyHostToDevice, s->stream));
     ST_HIP(hipMemcpyAsync(s->a_drop.p, drop_below, n * 8, hipMemcpyHostToDevice, s->stream));
@@ -449,6 +477,11 @@ int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t ch
     if (!labels_on_device) {
         ST_HIP(hipMemcpyAsync(s->a_lab.p, labels, rows, hipMemcpyHostToDevice, s->stream));
         d_labels = s->a_lab.as<uint8_t>();
+    }
+    const uint8_t* d_phred = with_phred ? phred : nullptr;
+    if (with_phred && !labels_on_device) {
+        ST_HIP(hipMemcpyAsync(s->a_phr.p, phred, rows, hipMemcpyHostToDevice, s->stream));
+        d_phred = s->a_phr.as<uint8_t>();
     }
     k_stitch_count<<<(unsigned)n, ST_THREADS, 0, s->stream>>>(s->a_pos.as<int64_t>(), s->a_idx.as<int64_t>(), s->a_drop.as<int64_t>(),
                                                                chunk_len, s->a_kept.as<int32_t>(), s->a_refused.as<int32_t>());
@@ -485,20 +518,38 @@ int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t ch
         used += kept[c];
     }
     ST_HIP(hipMemcpyAsync(s->a_dst.p, dst.data(), n * 8, hipMemcpyHostToDevice, s->stream));
-    k_stitch_compact<<<(unsigned)n, ST_THREADS, 0, s->stream>>>(s->a_pos.as<int64_t>(), s->a_idx.as<int64_t>(), d_labels,
+    k_stitch_compact<<<(unsigned)n, ST_THREADS, 0, s->stream>>>(s->a_pos.as<int64_t>(), s->a_idx.as<int64_t>(), d_labels, d_phred,
                                                                  s->a_drop.as<int64_t>(), chunk_len, s->a_kept.as<int32_t>(),
                                                                  s->a_dst.as<uint64_t*>());
     ST_HIP(hipGetLastError());
-    ST_HIP(hipStreamSynchronize(s->stream));            // the caller's arrays and labels are free again; dst is read
+    ST_HIP(hipStreamSynchronize(s->stream));            // the caller's arrays, labels and phred are free again; dst is read
     auto& list = s->contigs[contig];
     for (size_t c = 0; c < n; ++c) {
         if (kept[c] == 0) continue;
-        list.push_back(ChunkRec{region[c], chunk_order[c], s->arrivals++, dst[c], (uint32_t)kept[c]});
+        list.push_back(ChunkRec{region[c], chunk_order[c], s->arrivals++, dst[c], (uint32_t)kept[c], with_phred});
         s->rows_held += kept[c];
     }
     s->slab_at = slab;
     s->slab_used = used;
     return PA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pa_stitcher_add(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position, const int64_t* index,
+                    const uint8_t* labels, int32_t labels_on_device, const int32_t* region, const int64_t* chunk_order,
+                    const int64_t* drop_below) {
+    return stitcher_add(s, contig, n_chunks, chunk_len, position, index, labels, nullptr, false, labels_on_device, region, chunk_order,
+                        drop_below);
+}
+
+int pa_stitcher_add_qual(pa_stitcher* s, int32_t contig, int32_t n_chunks, int32_t chunk_len, const int64_t* position,
+                         const int64_t* index, const uint8_t* labels, const uint8_t* phred, int32_t labels_on_device,
+                         const int32_t* region, const int64_t* chunk_order, const int64_t* drop_below) {
+    return stitcher_add(s, contig, n_chunks, chunk_len, position, index, labels, phred, true, labels_on_device, region, chunk_order,
+                        drop_below);
 }
 
 int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const int32_t* region, const int32_t* piece, const int64_t* rank,
@@ -513,6 +564,8 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     *bad_label = 0;
     s->pieces.clear();
     s->sequence_length = 0;
+    s->finished = true;
+    s->contig_qualities = s->have_qualities = false;
     s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
@@ -528,6 +581,7 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     if (found == s->contigs.end() || found->second.empty() || n_pieces == 0) {
         if (found != s->contigs.end() && !found->second.empty())
             return pa::set_error(PA_ERR_INVALID, "stitcher finish: the contig holds chunks and the plan has no piece");
+        s->contig_qualities = s->have_qualities = true;  // no chunk came without them: the empty sequence has empty qualities
         return PA_OK;
     }
     // loop order: regions as ranked, a region's chunks by their order value, equal ones as they arrived
@@ -549,11 +603,17 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     std::vector<ChunkDesc> desc(n_desc);
     std::vector<int64_t> piece_rows((size_t)n_pieces, 0);
     uint64_t rank_base = 0;
+    bool qualities = true;                              // on when every chunk of the contig came with them
     for (size_t i = 0; i < n_desc; ++i) {
         desc[i] = ChunkDesc{order[i].rec->rows, order[i].rec->count, (uint32_t)order[i].piece, rank_base};
         rank_base += order[i].rec->count;
         piece_rows[(size_t)order[i].piece] += order[i].rec->count;
+        qualities = qualities && order[i].rec->qualities;
     }
+    if (rank_base > ST_MAX_ROWS)                        // (rank + 1 of the last row = rank_base)
+        return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher finish: the contig keeps " + std::to_string(rank_base) +
+                                                     " rows, the scatter word ranks 2^48 - 1");
+    s->contig_qualities = qualities;
     // piece words on the device: [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces, then fault, bad label
     const size_t np = (size_t)n_pieces;
     const size_t off_pmax = np * 4, off_pbase = (np * 8 + 7) / 8 * 8, off_start = off_pbase + np * 8, off_flags = off_start + np * 8;
@@ -636,9 +696,19 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     }
     // 6. the letters, piece after piece
     if (!s->f_out.grow(n_letters + 1)) return no_memory("the sequence", n_letters);
+    if (qualities) {
+        if (!s->f_qual.grow(n_letters + 1)) return no_memory("the qualities", n_letters);
+        s->last_scratch_bytes += (int64_t)n_letters;
+    }
     if (slot_blocks) {
-        k_stitch_emit<<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(), n_slots, n_letters,
-                                                                 s->f_out.as<uint8_t>());
+        if (qualities)
+            k_stitch_emit<true><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
+                                                                           s->f_slots.as<unsigned long long>(), n_slots, n_letters,
+                                                                           s->f_out.as<uint8_t>(), s->f_qual.as<uint8_t>());
+        else
+            k_stitch_emit<false><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
+                                                                            s->f_slots.as<unsigned long long>(), n_slots, n_letters,
+                                                                            s->f_out.as<uint8_t>(), nullptr);
         ST_HIP(hipGetLastError());
     }
     k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(d_pbase, n_pieces, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
@@ -658,6 +728,7 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
         return a.first != b.first ? a.first < b.first : a.last < b.last;
     });
     s->sequence_length = (int64_t)n_letters;
+    s->have_qualities = qualities;
     *sequence_length = (int64_t)n_letters;
     return PA_OK;
 }
@@ -673,6 +744,29 @@ int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity) {
     for (const PieceOut& piece : s->pieces) {
         if (piece.length == 0) continue;
         ST_HIP(hipMemcpyAsync(dst + at, s->f_out.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
+        at += piece.length;
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
+}
+
+int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
+    if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: no contig has been finished");
+    if (!s->have_qualities)
+        return pa::set_error(PA_ERR_INVALID, s->contig_qualities
+                                                 ? "stitcher take qualities: the last finish gave no sequence (a label that is no base, or it failed)"
+                                                 : "stitcher take qualities: the last finish produced none: a chunk of its contig was added "
+                                                   "without qualities (pa_stitcher_add_qual on every chunk asks for them), or it failed early");
+    if (capacity < s->sequence_length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: the sequence has " + std::to_string(s->sequence_length) +
+                                                 " letters, room for " + std::to_string(capacity));
+    ST_HIP(hipSetDevice(s->device));
+    int64_t at = 0;
+    for (const PieceOut& piece : s->pieces) {
+        if (piece.length == 0) continue;
+        ST_HIP(hipMemcpyAsync(dst + at, s->f_qual.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
         at += piece.length;
     }
     ST_HIP(hipStreamSynchronize(s->stream));

@@ -42,6 +42,8 @@ SYMBOLS = [
     ("pa_h5_prediction_batch_take", ctypes.c_int, [c_void_p] * 6),
     ("pa_h5_read_polish_prediction_region", ctypes.c_int, [c_void_p, c_char_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
                                                            ctypes.POINTER(c_int32)]),
+    ("pa_h5_read_polish_prediction_region_qual", ctypes.c_int, [c_void_p, c_char_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                                                c_void_p, ctypes.POINTER(c_int32)]),
     ("pa_h5_write_polish_image_chunks", ctypes.c_int, [c_void_p, c_char_p, c_int32, c_int32, c_int32, c_char_p, c_int64, c_int64] +
                                                        [c_void_p] * 5),
     ("pa_h5_write_polish_predictions", ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 9),
@@ -379,11 +381,18 @@ class File(object):
         return [(n.decode(), int(s), int(e)) for n, s, e in zip(names, starts.tolist(), ends.tolist())]
 
     @_locked
-    def read_polish_prediction_region(self, region_path, seq_len, max_chunks=64):
-        """(position, index, bases) rows of every chunk under one predictions region group, chunk ids in string order."""
+    def read_polish_prediction_region(self, region_path, seq_len, max_chunks=64, qualities=False):
+        """(position, index, bases) rows of every chunk under one predictions region group, chunk ids in string order;
+        qualities: (position, index, bases, phred_score)."""
         position, index = np.empty((max_chunks, seq_len), np.int64), np.empty((max_chunks, seq_len), np.int64)
         bases = np.empty((max_chunks, seq_len), np.uint8)
         n = c_int32()
+        if qualities:
+            phred = np.empty((max_chunks, seq_len), np.uint8)
+            _check(self._lib.pa_h5_read_polish_prediction_region_qual(self._h, region_path.encode(), seq_len, max_chunks,
+                                                                      position.ctypes.data, index.ctypes.data, bases.ctypes.data,
+                                                                      phred.ctypes.data, ctypes.byref(n)))
+            return position[:n.value], index[:n.value], bases[:n.value], phred[:n.value]
         _check(self._lib.pa_h5_read_polish_prediction_region(self._h, region_path.encode(), seq_len, max_chunks,
                                                              position.ctypes.data, index.ctypes.data, bases.ctypes.data,
                                                              ctypes.byref(n)))

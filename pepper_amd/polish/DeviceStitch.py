@@ -3,13 +3,15 @@
 replaces, for a run that opts in: pepper/modules/python/Stitch.py of the reference
     small_chunk_stitch        :36-94    the {(position, insert index): label} merge -> pa_stitcher_* (pepper_amd/csrc/stitch.hip)
     create_consensus_sequence :97-128   region order and pieces -> plan() below, pure host code
-perform_stitch (the host form) is untouched and stays the default; what this module writes is byte for byte its FASTA.
+perform_stitch (the host form) is untouched and stays the default; what this module writes is byte for byte its FASTA, and with
+qualities on (opt-in, not in the reference) byte for byte its FASTQ: the phred of a row travels through the merge with its label.
 
 plan() restates the loop order of the reference: regions sorted by name, then stably by (start, end), cut into pieces of
 max(2, int(n / threads) + 1) consecutive regions; inside a region the chunk ids in STRING order.  The device only needs, per
 row, its piece and a rank that grows along that loop: the last write of a key is the one with the largest rank.
 """
 import collections
+import contextlib
 import ctypes
 import threading
 from pathlib import Path
@@ -19,7 +21,7 @@ import numpy as np
 from pepper_amd import _lib, h5
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
-from pepper_amd.polish.perform_stitch import _log, get_file_paths_from_directory, natural_key
+from pepper_amd.polish.perform_stitch import _log, fastq_path, get_file_paths_from_directory, natural_key, write_fastq_record
 
 Plan = collections.namedtuple("Plan", "order piece rank n_pieces chunk_order")
 
@@ -103,11 +105,12 @@ class DeviceStitcher(object):
     def regions(self, contig):
         return list(self._contigs[contig][2]) if contig in self._contigs else []
 
-    def add(self, contig, region_keys, chunk_order, position, index, labels):
+    def add(self, contig, region_keys, chunk_order, position, index, labels, phred=None):
         """Chunks of one contig: region_keys[k] = (file name, region name, start, end) of chunk k, chunk_order[k] = what orders it
         among its region's chunks (string_order / string_order_key), position / index [n, length] integers, labels [n, length]:
         a numpy array, or a uint8 torch tensor on this stitcher's device whose values are complete (the caller has waited for
-        the stream that wrote them)."""
+        the stream that wrote them).  phred [n, length]: the rows' qualities, where and what labels is (a numpy array beside a
+        numpy array, a uint8 device tensor beside a device tensor); a contig has qualities when every add of it had them."""
         n = len(region_keys)
         if n == 0:
             return
@@ -117,12 +120,20 @@ class DeviceStitcher(object):
         if index.shape != position.shape:
             raise ValueError("position and index differ in shape")
         on_device = hasattr(labels, "is_cuda") and labels.is_cuda and labels.device.index == self.device
+        phred_ptr = None
+        if phred is not None and (hasattr(phred, "is_cuda") and phred.is_cuda and phred.device.index == self.device) != on_device:
+            raise ValueError("labels and phred must both be device tensors of this stitcher's device or both host arrays")
         if on_device:
             import torch
             if labels.dtype != torch.uint8 or labels.numel() != n * length:
                 raise ValueError("device labels must be uint8 [n, length]")
             labels = labels.contiguous()
             labels_ptr = labels.data_ptr()
+            if phred is not None:
+                if phred.dtype != torch.uint8 or phred.numel() != n * length:
+                    raise ValueError("device phred must be uint8 [n, length]")
+                phred = phred.contiguous()
+                phred_ptr = phred.data_ptr()
         else:
             if hasattr(labels, "detach"):
                 labels = labels.detach().cpu().numpy()
@@ -130,6 +141,13 @@ class DeviceStitcher(object):
             if labels.shape != position.shape:
                 raise ValueError("labels and position differ in shape")
             labels_ptr = labels.ctypes.data
+            if phred is not None:
+                if hasattr(phred, "detach"):
+                    phred = phred.detach().cpu().numpy()
+                phred = np.ascontiguousarray(np.asarray(phred).astype(np.uint8, copy=False)).reshape(n, -1)
+                if phred.shape != position.shape:
+                    raise ValueError("phred and position differ in shape")
+                phred_ptr = phred.ctypes.data
         buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
         with self._lock:
             entry = self._contigs.get(contig)
@@ -146,9 +164,14 @@ class DeviceStitcher(object):
                 order = np.ascontiguousarray(chunk_order, dtype=np.int64)
                 if order.shape != (n,):
                     raise ValueError("chunk_order must have one value per chunk")
-                _lib.check(self._lib.pa_stitcher_add(self.handle, entry[0], n, length, position.ctypes.data, index.ctypes.data,
-                                                     labels_ptr, 1 if on_device else 0, region.ctypes.data, order.ctypes.data,
-                                                     drop.ctypes.data))
+                if phred_ptr is None:
+                    _lib.check(self._lib.pa_stitcher_add(self.handle, entry[0], n, length, position.ctypes.data, index.ctypes.data,
+                                                         labels_ptr, 1 if on_device else 0, region.ctypes.data, order.ctypes.data,
+                                                         drop.ctypes.data))
+                else:
+                    _lib.check(self._lib.pa_stitcher_add_qual(self.handle, entry[0], n, length, position.ctypes.data,
+                                                              index.ctypes.data, labels_ptr, phred_ptr, 1 if on_device else 0,
+                                                              region.ctypes.data, order.ctypes.data, drop.ctypes.data))
             except BaseException:
                 for k in new_keys:           # a refused call has added nothing: its new regions are not recorded either
                     del ids[k]
@@ -156,13 +179,15 @@ class DeviceStitcher(object):
             entry[2].extend(new_keys)
             self._contigs[contig] = entry
 
-    def finish(self, contig, threads, region_keys=None):
+    def finish(self, contig, threads, region_keys=None, qualities=False):
         """The consensus of one contig as create_consensus_sequence(contig, region_keys, threads) returns it; region_keys
-        default to the contig's regions in the order they first arrived.  KeyError(label): a surviving label that is no base."""
+        default to the contig's regions in the order they first arrived.  KeyError(label): a surviving label that is no base.
+        qualities: (sequence, quality) as create_consensus_sequence(..., qualities=True) returns them; PepperAmdError where an
+        add of the contig came without phred."""
         with self._lock:
             entry = self._contigs.get(contig)
             if entry is None:
-                return ""
+                return ("", "") if qualities else ""
             keys = list(region_keys) if region_keys is not None else list(entry[2])
             p = plan(keys, threads)
             known = [i for i, k in enumerate(keys) if k in entry[1]]
@@ -180,7 +205,11 @@ class DeviceStitcher(object):
             self.last_pieces = list(zip(first.tolist(), last.tolist(), length.tolist()))
             buf = ctypes.create_string_buffer(max(1, total.value))
             _lib.check(self._lib.pa_stitcher_take(self.handle, buf, total.value))
-            return buf.raw[:total.value].decode()
+            sequence = buf.raw[:total.value].decode()
+            if not qualities:
+                return sequence
+            _lib.check(self._lib.pa_stitcher_take_qualities(self.handle, buf, total.value))
+            return sequence, buf.raw[:total.value].decode()
 
     def stats(self):
         """{'rows', 'slab_bytes'} held, and of the last finish {'slots', 'pieces', 'positions', 'table_bytes'}"""
@@ -201,6 +230,21 @@ class DeviceStitcher(object):
                     fasta.write(sequence + "\n")
         return output_path
 
+    def write_fastq(self, output_prefix, threads):
+        """write_fasta's file, and beside it <output_prefix>_pepper_polished.fastq with the same records and their qualities
+        (perform_stitch(..., qualities=True)'s two files), from one finish per contig.  -> the FASTQ's path."""
+        output_path = output_prefix + '_pepper_polished.fa'
+        Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
+        with open(output_path, 'w') as fasta, open(fastq_path(output_prefix), 'w') as fastq:
+            for contig in sorted(self.contigs(), key=natural_key):
+                sequence, quality = self.finish(contig, threads, qualities=True)
+                _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
+                if len(sequence) > 0:
+                    fasta.write('>' + contig + "\n")
+                    fasta.write(sequence + "\n")
+                    write_fastq_record(fastq, contig, sequence, quality)
+        return fastq_path(output_prefix)
+
     def close(self):
         if self._handle is not None:
             self._lib.pa_stitcher_destroy(self._handle)
@@ -219,17 +263,20 @@ class DeviceStitcher(object):
             pass
 
 
-def _read_region(hdf5_file, prefix):
+def _read_region(hdf5_file, prefix, qualities=False):
     """The chunks of one region group in string order of their ids -> [(position, index, labels)] blocks of [n, length] rows
-    (one block of all chunks where they have the pipeline's length, else one block per chunk)."""
+    (one block of all chunks where they have the pipeline's length, else one block per chunk); qualities: (position, index,
+    labels, phred) blocks -- the region read's sibling that takes phred_score beside bases, one dataset more per chunk."""
+    names = ('position', 'index', 'bases', 'phred_score') if qualities else ('position', 'index', 'bases')
     try:
-        positions, indices, bases = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH)
-        return [(positions, indices, bases)] if len(positions) else []
+        block = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH, qualities=True) if qualities else \
+            hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH)
+        return [tuple(block)] if len(block[0]) else []
     except h5.H5Error:                  # chunks of another length, or more of them than one call takes: one by one
         blocks = []
         for chunk in sorted(set(hdf5_file.keys(prefix)) - {'contig_start', 'contig_end'}):
             row = [np.asarray(hdf5_file[prefix + '/' + chunk + '/' + name], dtype=np.int64).reshape(1, -1)
-                   for name in ('position', 'index', 'bases')]
+                   for name in names]
             if row[0].size:
                 blocks.append(tuple(row))
         return blocks
@@ -244,35 +291,39 @@ class _Held(object):
         self.stitcher, self.contig = stitcher, contig
         self.keys, self.order, self.blocks = [], [], []
 
-    def take(self, key, first_order, positions, indices, bases):
+    def take(self, key, first_order, positions, indices, bases, phred=None):
         n = len(positions)
         if self.blocks and self.blocks[0][0].shape[1] != positions.shape[1]:
             self.flush()
         self.keys.extend([key] * n)
         self.order.extend(range(first_order, first_order + n))
-        self.blocks.append((positions, indices, bases))
+        self.blocks.append((positions, indices, bases) if phred is None else (positions, indices, bases, phred))
         if len(self.keys) >= self.CHUNKS:
             self.flush()
 
     def flush(self):
         if self.keys:
-            position, index, labels = (np.concatenate([b[k] for b in self.blocks]) for k in range(3))
-            self.stitcher.add(self.contig, self.keys, self.order, position, index, labels)
+            columns = [np.concatenate([b[k] for b in self.blocks]) for k in range(len(self.blocks[0]))]
+            self.stitcher.add(self.contig, self.keys, self.order, *columns)
         self.keys, self.order, self.blocks = [], [], []
 
 
-def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None):
-    """perform_stitch(hdf_file_path, output_path, threads) with the merge on the device: the same files read, the same FASTA
-    written.  stats: a dict that receives the handle's stats() after the last contig."""
+def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False):
+    """perform_stitch(hdf_file_path, output_path, threads, qualities) with the merge on the device: the same files read, the
+    same FASTA (and FASTQ) written.  stats: a dict that receives the handle's stats() after the last contig."""
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
         with h5.File(prediction_file, 'r') as hdf5_file:
             if 'predictions' in hdf5_file.keys():
                 all_contigs.update(hdf5_file.keys('predictions'))
+    output_prefix = output_path
     output_path = output_path + '_pepper_polished.fa'
     Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
-    with DeviceStitcher(device) as stitcher, open(output_path, 'w') as fasta:
+    with contextlib.ExitStack() as files:
+        stitcher = files.enter_context(DeviceStitcher(device))
+        fasta = files.enter_context(open(output_path, 'w'))
+        fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
         for contig in sorted(all_contigs, key=natural_key):
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -286,16 +337,21 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None):
                     for name, start, end in regions:
                         key, at = (prediction_file, name, start, end), 0
                         # (the group is read by the name small_chunk_stitch rebuilds: contig-start-end)
-                        for positions, indices, bases in _read_region(hdf5_file, 'predictions/' + contig + '/' + contig + '-' +
-                                                                      str(start) + '-' + str(end)):
-                            held.take(key, at, positions, indices, bases)
-                            at += len(positions)
+                        for block in _read_region(hdf5_file, 'predictions/' + contig + '/' + contig + '-' + str(start) + '-' +
+                                                  str(end), qualities):
+                            held.take(key, at, *block)
+                            at += len(block[0])
             held.flush()
-            sequence = stitcher.finish(contig, threads, all_chunk_keys)
+            if qualities:
+                sequence, quality = stitcher.finish(contig, threads, all_chunk_keys, qualities=True)
+            else:
+                sequence = stitcher.finish(contig, threads, all_chunk_keys)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
             if len(sequence) > 0:
                 fasta.write('>' + contig + "\n")
                 fasta.write(sequence + "\n")
+                if qualities:
+                    write_fastq_record(fastq, contig, sequence, quality)
         if stats is not None:
             stats.update(stitcher.stats())
     return output_path

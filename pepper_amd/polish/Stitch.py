@@ -7,6 +7,8 @@ Vectorised with numpy: per piece the (position, index, label) triples of all its
 are concatenated in the reference's iteration order (chunk ids sorted as strings), filtered
 (position/index >= 0; for regions not starting at 0 positions <= start + 2 * MIN_IMAGE_OVERLAP are
 overlap and dropped), then the last write of every key wins and keys come out sorted.
+qualities=True (opt-in, not in the reference): the phred_score of the row that supplied a letter's label travels with it and
+comes out as Sanger text, chr(33 + min(phred, 93)); a winning gap gives neither a letter nor a quality.
 Pinned: tests/golden/polish_stitch_ref.fa is the reference's own output on the same prediction arrays.
 """
 import concurrent.futures
@@ -20,16 +22,20 @@ from pepper_amd.polish.Options import ImageSizeOptions
 label_decoder = {1: 'A', 2: 'C', 3: 'G', 4: 'T', 0: ''}
 _DECODE = np.frombuffer(b"\0ACGT", dtype=np.uint8)
 MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING = 2
+MAX_QUALITY = 93                          # Sanger: '!' + 93 = '~' (the model writes 100 for "certain", a file may hold 255)
 
 
 def chunks(file_names, threads):
     return [file_names[i:i + threads] for i in range(0, len(file_names), threads)]
 
 
-def small_chunk_stitch(contig, small_chunk_keys):
+def small_chunk_stitch(contig, small_chunk_keys, qualities=False):
     """One piece of the consensus.  The merge runs inside the I/O library (pa_h5_stitch_polish_regions: chunk rows straight
     from the mapped prediction files, each chunk merged into the tail of the piece; 3 k -> see DESIGN.md chunks/s);
-    PEPPER_AMD_STITCH_NUMPY=1 keeps the numpy form below, which tests hold it to."""
+    PEPPER_AMD_STITCH_NUMPY=1 keeps the numpy form below, which tests hold it to.  qualities: (first, last, sequence, quality),
+    always through the numpy form (the library's merge carries no phred)."""
+    if qualities:
+        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=True)
     if os.environ.get("PEPPER_AMD_STITCH_NUMPY") == "1":
         return small_chunk_stitch_numpy(contig, small_chunk_keys)
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
@@ -49,9 +55,11 @@ def small_chunk_stitch(contig, small_chunk_keys):
             f.close()
 
 
-def small_chunk_stitch_numpy(contig, small_chunk_keys):
+def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False):
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
-    pos_parts, idx_parts, base_parts = [], [], []
+    nothing = (-1, -1, '', '') if qualities else (-1, -1, '')
+    names = ('position', 'index', 'bases', 'phred_score') if qualities else ('position', 'index', 'bases')
+    pos_parts, idx_parts, base_parts, phred_parts = [], [], [], []
     open_files = {}                       # each prediction file is opened once per call, not once per region
     try:
         for file_name, contig_name, _st, _end in small_chunk_keys:
@@ -61,29 +69,39 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys):
             if hdf5_file is None:
                 hdf5_file = open_files[file_name] = h5.File(file_name, 'r')
             # every chunk of the region in one library call (chunk ids in string order, as sorted() gives them)
+            phred = None
             try:
-                positions, indices, bases = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH)
+                if qualities:
+                    positions, indices, bases, phred = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH,
+                                                                                               qualities=True)
+                    phred = phred.reshape(-1).astype(np.int64)
+                else:
+                    positions, indices, bases = hdf5_file.read_polish_prediction_region(prefix, ImageSizeOptions.SEQ_LENGTH)
                 positions, indices, bases = positions.reshape(-1), indices.reshape(-1), bases.reshape(-1).astype(np.int64)
             except h5.H5Error:                  # chunks of another length (not written by this pipeline): one by one
-                parts = [[], [], []]
+                parts = [[] for _ in names]
                 for chunk in sorted(set(hdf5_file.keys(prefix)) - {'contig_start', 'contig_end'}):
-                    for k, name in enumerate(('position', 'index', 'bases')):
+                    for k, name in enumerate(names):
                         parts[k].append(np.asarray(hdf5_file[prefix + '/' + chunk + '/' + name], dtype=np.int64).reshape(-1))
-                positions, indices, bases = (np.concatenate(p) if p else np.zeros(0, np.int64) for p in parts)
+                positions, indices, bases = (np.concatenate(p) if p else np.zeros(0, np.int64) for p in parts[:3])
+                if qualities:
+                    phred = np.concatenate(parts[3]) if parts[3] else np.zeros(0, np.int64)
             keep = (indices >= 0) & (positions >= 0)
             if _st > 0:
                 keep &= positions > _st + buffer_positions
             pos_parts.append(positions[keep])
             idx_parts.append(indices[keep])
             base_parts.append(bases[keep])
+            if qualities:
+                phred_parts.append(phred[keep])
     finally:
         for f in open_files.values():
             f.close()
     if not pos_parts:
-        return -1, -1, ''
+        return nothing
     positions = np.concatenate(pos_parts)
     if positions.size == 0:
-        return -1, -1, ''
+        return nothing
     indices = np.concatenate(idx_parts)
     bases = np.concatenate(base_parts)
     # stable sort on (position, index): the last element of every run is the last write
@@ -96,18 +114,26 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys):
         raise KeyError(int(labels[(labels < 0) | (labels > 4)][0]))      # label_decoder[...] in the reference
     letters = _DECODE[labels]
     sequence = letters[letters != 0].tobytes().decode()
+    if qualities:                         # the phred the winning write carried, for the winners that are bases
+        phred = np.concatenate(phred_parts)[order][last]
+        quality = (33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8).tobytes().decode()
+        return int(positions[0]), int(positions[-1]), sequence, quality
     return int(positions[0]), int(positions[-1]), sequence
 
 
-def create_consensus_sequence(contig, sequence_chunk_keys, threads):
+def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False):
+    """The consensus of one contig; qualities: (sequence, quality), the pieces' qualities concatenated as their letters are."""
+    extra = (True,) if qualities else ()
     key_list = sorted(((file_name, contig, int(contig_start), int(contig_end))
                        for file_name, _, contig_start, contig_end in sorted(sequence_chunk_keys, key=lambda e: e[1])),
                       key=lambda e: (e[2], e[3]))
     file_chunks = chunks(key_list, max(MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING, int(len(key_list) / max(1, threads)) + 1))
     if threads <= 1 or len(file_chunks) <= 1:
-        results = [small_chunk_stitch(contig, chunk) for chunk in file_chunks]
+        results = [small_chunk_stitch(contig, chunk, *extra) for chunk in file_chunks]
     else:
         with concurrent.futures.ProcessPoolExecutor(max_workers=threads) as executor:
-            results = [f.result() for f in [executor.submit(small_chunk_stitch, contig, chunk) for chunk in file_chunks]]
+            results = [f.result() for f in [executor.submit(small_chunk_stitch, contig, chunk, *extra) for chunk in file_chunks]]
     pieces = sorted((r for r in results if r[0] != -1 and r[1] != -1), key=lambda e: (e[0], e[1]))
+    if qualities:
+        return ''.join(piece[2] for piece in pieces), ''.join(piece[3] for piece in pieces)
     return ''.join(sequence for _, _, sequence in pieces)

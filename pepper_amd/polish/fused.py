@@ -120,25 +120,28 @@ class _Gather(object):
     def _predict_and_write(self, st, n):
         entry, model = self.owner._model(self.device)
         owner = self.owner
-        feed = None
+        feed = feed_phred = None
         try:
             torch.cuda.set_device(self.device)
             with torch.cuda.stream(model._stream):          # (this thread's "current stream": not the process-wide default one)
                 labels, phred = model.predict_chunks(st.buffer[:n])
                 if owner.device_stitch:
                     # the labels stay where the model left them (a pass on another device hands them over through the host)
+                    # (and with qualities on the phred beside them, the same way)
                     if self.device == owner.stitch_device(self.device):
                         model._stream.synchronize()
                         feed = labels
+                        feed_phred = phred if owner.qualities else None
                     else:
                         feed = labels.cpu().numpy()
+                        feed_phred = phred.cpu().numpy() if owner.qualities else None
                 if owner.keep_predictions:
                     labels, phred = labels.cpu().numpy(), phred.cpu().numpy()
         finally:
             entry["free"].put(model)
         meta = st.meta[:n]
         if feed is not None:
-            owner.stitch_add(meta, st.position[:n], st.index[:n], feed)
+            owner.stitch_add(meta, st.position[:n], st.index[:n], feed, feed_phred)
         if not owner.keep_predictions:
             return
         contigs = np.array([m[0] for m in meta], dtype='S')
@@ -180,12 +183,13 @@ class FusedConsensus(object):
     HANDLES = 2          # passes in flight per device (own stream and workspace each)
 
     def __init__(self, model_path, output_directory, batch_invariant=None, device_stitch=False, keep_predictions=True,
-                 stitch_device=None):
+                 stitch_device=None, qualities=False):
         """device_stitch: the passes hand their labels to one DeviceStitcher (pepper_amd/polish/DeviceStitch.py) on stitch_device
         (default: the device of the first pass) and polish() writes the FASTA from it; the prediction files are then written only
-        with keep_predictions."""
+        with keep_predictions.  qualities: the passes hand their phred to the stitcher as well (polish() writes the FASTQ)."""
         self.model_path = model_path
         self.device_stitch = bool(device_stitch)
+        self.qualities = bool(qualities)
         self.keep_predictions = bool(keep_predictions) or not self.device_stitch
         self._stitch_device = stitch_device
         self.stitcher = None
@@ -221,9 +225,10 @@ class FusedConsensus(object):
                 self._stitch_device = default
             return self._stitch_device
 
-    def stitch_add(self, meta, position, index, labels):
+    def stitch_add(self, meta, position, index, labels, phred=None):
         """The chunks of one pass: runs of one contig go to the stitcher in one call each.  Regions are keyed as perform_stitch
-        would find them in a prediction file; a chunk's order is its id's place among decimal strings."""
+        would find them in a prediction file; a chunk's order is its id's place among decimal strings.  phred: the rows'
+        qualities, where labels is (device tensor or host array)."""
         from pepper_amd.polish.DeviceStitch import DeviceStitcher, string_order_key
         with self.models_lock:
             if self.stitcher is None:
@@ -234,7 +239,8 @@ class FusedConsensus(object):
             while b < n and meta[b][0] == meta[a][0]:
                 b += 1
             keys = [("", m[0] + "-" + str(m[1]) + "-" + str(m[2]), m[1], m[2]) for m in meta[a:b]]
-            self.stitcher.add(meta[a][0], keys, [string_order_key(m[3]) for m in meta[a:b]], position[a:b], index[a:b], labels[a:b])
+            self.stitcher.add(meta[a][0], keys, [string_order_key(m[3]) for m in meta[a:b]], position[a:b], index[a:b], labels[a:b],
+                              None if phred is None else phred[a:b])
             a = b
 
     # ---- the prediction files: one per pass thread ----

@@ -3,7 +3,10 @@
 replaces: /root/reference/pepper/modules/python/perform_stitch.py:44-84 (`perform_stitch`): every
 `*hdf` of the directory, contigs in natural order, one `>contig` record per non-empty consensus,
 written to `<output_path>_pepper_polished.fa`.  (The reference's 5 s sleep is not reproduced.)
+qualities=True (opt-in, not in the reference) also writes `<output_path>_pepper_polished.fastq`: the same records with the
+phred of the prediction row that supplied each base, as Sanger text.
 """
+import contextlib
 import re
 import sys
 from datetime import datetime
@@ -28,7 +31,19 @@ def _log(message):
     sys.stderr.write("[" + str(datetime.now().strftime('%m-%d-%Y %H:%M:%S')) + "] INFO: " + message + "\n")
 
 
-def perform_stitch(hdf_file_path, output_path, threads):
+def fastq_path(output_prefix):
+    return output_prefix + '_pepper_polished.fastq'
+
+
+def write_fastq_record(fastq, contig, sequence, quality):
+    # (four writes: the record of a whole contig is not put together in memory first)
+    fastq.write('@' + contig + "\n")
+    fastq.write(sequence)
+    fastq.write("\n+\n")
+    fastq.write(quality + "\n")
+
+
+def perform_stitch(hdf_file_path, output_path, threads, qualities=False):
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -36,9 +51,12 @@ def perform_stitch(hdf_file_path, output_path, threads):
             if 'predictions' in hdf5_file.keys():
                 all_contigs.update(hdf5_file.keys('predictions'))
 
+    output_prefix = output_path
     output_path = output_path + '_pepper_polished.fa'
     Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
-    with open(output_path, 'w') as consensus_fasta_file:
+    with contextlib.ExitStack() as files:
+        consensus_fasta_file = files.enter_context(open(output_path, 'w'))
+        fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
         for contig in sorted(all_contigs, key=natural_key):
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -48,9 +66,14 @@ def perform_stitch(hdf_file_path, output_path, threads):
                         continue
                     # every region group with its contig_start / contig_end in one library call (names in sorted order)
                     all_chunk_keys.extend((prediction_file, name, start, end) for name, start, end in hdf5_file.list_polish_regions(contig))
-            consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads)
+            if qualities:
+                consensus_sequence, quality = create_consensus_sequence(contig, all_chunk_keys, threads, qualities=True)
+            else:
+                consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(consensus_sequence)) + ".")
             if consensus_sequence is not None and len(consensus_sequence) > 0:
                 consensus_fasta_file.write('>' + contig + "\n")
                 consensus_fasta_file.write(consensus_sequence + "\n")
+                if qualities:
+                    write_fastq_record(fastq, contig, consensus_sequence, quality)
     return output_path

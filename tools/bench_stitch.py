@@ -1,8 +1,9 @@
 """Stitch rate (prediction HDF5 files -> polished FASTA): perform_stitch with the merge inside the I/O library (default) and with
 the numpy form (PEPPER_AMD_STITCH_NUMPY=1), one and eight workers; --device adds the same set through the device stitch
 (pepper_amd/polish/DeviceStitch.py stitch_directory: the files read on the host, the merge on the GPU) and checks its FASTA
-against the host's.
-    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device]"""
+against the host's.  --qualities runs the set with qualities on as well -- perform_stitch(..., qualities=True) on the host (the
+numpy merge with a phred column) and, with --device, stitch_directory(..., qualities=True) -- and checks the two FASTQ files equal.
+    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities]"""
 import argparse
 import json
 import os
@@ -25,12 +26,14 @@ def main():
     ap.add_argument("--files", type=int, default=4)
     ap.add_argument("--dir", default=None)
     ap.add_argument("--device", action="store_true", help="also run the set through the device stitch")
+    ap.add_argument("--qualities", action="store_true", help="also run the set with qualities on (FASTQ beside the FASTA)")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
         pred = os.path.join(tmp, "pred")
         os.makedirs(pred)
         rng = np.random.default_rng(3)
+        rng_phred = np.random.default_rng(4)               # (a stream of its own: the labels are the ones of every earlier run)
         stores = [DataStore(os.path.join(pred, "pepper_prediction_%d.hdf" % k), "w") for k in range(args.files)]
         regions = args.chunks // 2
         block = 256                                        # regions per write call
@@ -45,7 +48,7 @@ def main():
             bases = rng.integers(0, 5, (2 * m, 1000)).astype(np.uint8)
             contigs = np.array([b"ctg0"] * (2 * m), dtype="S256")
             stores[(r0 // block) % args.files].write_predictions_block(contigs, start2, start2 + 1200, chunk, position, idx[:2 * m],
-                                                                        bases, bases)
+                                                                        bases, rng_phred.integers(0, 101, (2 * m, 1000)).astype(np.uint8))
         for s in stores:
             s.close()
         runs = []
@@ -57,6 +60,15 @@ def main():
                 dt = time.perf_counter() - t0
                 runs.append({"merge": "numpy" if numpy_form else "library", "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out)})
+        if args.qualities:
+            os.environ["PEPPER_AMD_STITCH_NUMPY"] = "0"
+            for threads in (1, 8):
+                t0 = time.perf_counter()
+                out = perform_stitch(pred, os.path.join(tmp, "outq%d" % threads), threads, qualities=True)
+                dt = time.perf_counter() - t0
+                runs.append({"merge": "numpy", "qualities": True, "threads": threads, "seconds": round(dt, 2),
+                             "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                             "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
         if args.device:
             from pepper_amd.polish.DeviceStitch import stitch_directory
             host = {threads: open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read() for threads in (1, 8)}
@@ -69,6 +81,18 @@ def main():
                     runs.append({"merge": "device", "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
                                  "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                                  "equals_host": open(out, "rb").read() == host[threads], "stats": stats})
+            for threads in (1, 8) if args.qualities else ():
+                host_fastq = open(os.path.join(tmp, "outq%d" % threads) + "_pepper_polished.fastq", "rb").read()
+                for repeat in range(2):
+                    stats = {}
+                    t0 = time.perf_counter()
+                    out = stitch_directory(pred, os.path.join(tmp, "devq%d%d" % (threads, repeat)), threads, stats=stats, qualities=True)
+                    dt = time.perf_counter() - t0
+                    fastq = open(out[:-len(".fa")] + ".fastq", "rb").read()
+                    runs.append({"merge": "device", "qualities": True, "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
+                                 "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                                 "equals_host": open(out, "rb").read() == host[threads], "fastq_equals_host": fastq == host_fastq,
+                                 "fastq_bytes": len(fastq), "stats": stats})
         from pepper_amd.hostinfo import usable_cpus
         print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
