@@ -377,6 +377,77 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
  * its tables (the quality buffer among them when the finish produced qualities). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
 
+/* ------------------------------------------------------------------------------------------
+ * The candidate finder's selection ON THE DEVICE (opt-in: call_variant(..., fused_inference=True, device_selection=True);
+ * pepper_amd/csrc/select.hip).
+ * replaces, for such a run: which rows of a prediction batch pa_candidates_reference_flags + pa_candidates_select_format
+ * (include/pepper_amd_io.h; CandidateFinder.py:356-581) keep, decided where the encoder left the lists and the model the
+ * probabilities.  Only the kept rows come back, compacted in row order; their record TEXT (%g, round(x, 3),
+ * int(-10 log10(..)), the QUAL cutoff of flags bit 1) stays with pa_candidates_select_format on the host, which is handed
+ * the compacted arrays and keeps all of them.
+ *
+ * A row is kept exactly when the host pair keeps it: the reference letter ref[p] upper-cased is one of ACGT; the name is a
+ * type character followed by letters of ACGT only, and the type is '1'..'3'; non_alt = max(p1, p2) widened to double is
+ * >= p_value[kind] (p_value_in_lc[kind] where the low-complexity flag is set), or 0 < report_above_freq[kind] <=
+ * (double)support / (double)depth.  The low-complexity flag: a run of at least 5 equal upper-cased letters inside
+ * ref[max(0, p - 10), p + 10), cut at the end of the reference given, that shares an index with [p - 5, p + 4).
+ * flags: bit 0 SNP (from the swapped lengths), bit 2 REF / ALT swapped (a deletion admitted by probability), bits 4-5 the
+ * genotype (first maximum of the three probabilities); bit 1 is not computed here.
+ *
+ * Handed back instead of decided (summary.status != 0, nothing can be taken; the caller does that call on the host):
+ *   PA_SELECT_ZERO_DEPTH   a row with a valid letter and a valid allele has depth 0 (the host path returns -2)
+ *   PA_SELECT_NAN          a row that reaches the rules has a NaN probability (the host path returns -2)
+ *   PA_SELECT_NAME         a name is empty, longer than pa_selector_limits [2] bytes or holds one of " ,'\"[]\n"
+ *   PA_SELECT_CONTEXT      a row inside its reference whose context starts in front of reference[0] while reference_start > 0
+ *   PA_SELECT_NAME_COUNT   `names` does not hold exactly n NULs
+ * Two runs over the same input leave the same bytes: nothing depends on the order workgroups or atomics run in.
+ * ------------------------------------------------------------------------------------------ */
+#ifndef PA_CANDIDATE_RULES_DEFINED
+#define PA_CANDIDATE_RULES_DEFINED
+typedef struct {
+    double p_value[3], p_value_in_lc[3], report_above_freq[3];
+    double snp_q_cutoff, snp_q_cutoff_in_lc, indel_q_cutoff, indel_q_cutoff_in_lc;
+} pa_candidate_rules;
+#endif
+typedef struct pa_selector pa_selector;
+typedef struct {
+    int64_t first_row;         /* rows [first_row, next region's first_row) lie in this region; regions[0].first_row = 0 */
+    int64_t reference_start;   /* contig coordinate of reference[0] */
+    const char* reference;
+    int64_t reference_len;
+} pa_selector_region;
+enum { PA_SELECT_ZERO_DEPTH = 1, PA_SELECT_NAN = 2, PA_SELECT_NAME = 4, PA_SELECT_CONTEXT = 8, PA_SELECT_NAME_COUNT = 16 };
+typedef struct {
+    int64_t kept_rows;         /* m */
+    int64_t kept_name_bytes;   /* bytes of the m kept names, their NULs included */
+    int32_t status;            /* 0, or the PA_SELECT_* bits of the cases found */
+    int32_t reserved;
+} pa_selection;
+
+/* One selector per (thread, stream): owns its workspace; hip_stream NULL: a stream of its own. */
+int pa_selector_create(int32_t device, void* hip_stream, pa_selector** out);
+void pa_selector_destroy(pa_selector* s);
+/* out[0] rows per workgroup, [1] elements one workgroup of the scans takes, [2] longest name taken (bytes without the NUL),
+ * [3] the most elements a scan takes without a further level, [4] the most rows of a call. */
+int pa_selector_limits(int64_t* out, int32_t n);
+/* One call's rows: position int64 [n], depth / support int32 [n], prediction float32 [n, 3], names = n NUL-terminated strings
+ * back to back (name_bytes of them, as the encoder leaves them), regions ascending by first_row.  on_device 0: every array
+ * (the regions' references too) is host memory and is uploaded; 1: device memory of the selector's device, complete.  One
+ * submission on the selector's stream and one wait, for *summary. */
+int pa_selector_run(pa_selector* s, const pa_candidate_rules* rules, int64_t n, const int64_t* position, const int32_t* depth,
+                    const int32_t* support, const float* prediction, const char* names, int64_t name_bytes, int32_t n_regions,
+                    const pa_selector_region* regions, int32_t on_device, pa_selection* summary);
+/* The m kept rows of the last run in row order (HOST pointers, any may be NULL): their row numbers, flags, reference letters
+ * and low-complexity flags, the compacted fields, the kept names back to back and where each begins (name_offsets[m] = the
+ * kept name bytes).  One wait.  PA_ERR_INVALID: no run, or its status was not 0. */
+int pa_selector_take(pa_selector* s, int32_t* row, uint8_t* flags, uint8_t* letter, uint8_t* in_repeat, int64_t* position,
+                     int64_t* depth, int64_t* support, float* prediction, char* names, int64_t* name_offsets);
+/* pa_selector_run over the encoder's last variant run: the lists are read where the device enumeration left them (a
+ * host-enumerated run uploads its lists first), the references in the staged batch, a row's region from the run's counts;
+ * prediction float32 [n, 3] in device memory, complete.  Nothing is downloaded to set the call up. */
+int pa_encoder_select_candidates(pa_encoder* e, pa_selector* s, const float* prediction, const pa_candidate_rules* rules,
+                                 pa_selection* summary);
+
 #ifdef __cplusplus
 }
 #endif

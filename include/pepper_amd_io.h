@@ -102,10 +102,13 @@ int pa_h5_read_polish_chunks(pa_h5* f, const char* names, int32_t n, int32_t seq
  * re-genotyping, bit 2 REF/ALT swapped (a deletion called by probability), bits 4-5 genotype) and its VCF line
  * lines[line_offsets[k] .. line_offsets[k+1]) ('\n'-terminated).  -1: error; -2: a row only the reference-shaped Python path
  * reproduces (NaN probabilities, the reference's division by a zero depth): the caller takes that path for the batch. */
+#ifndef PA_CANDIDATE_RULES_DEFINED      /* (shared with include/pepper_amd_encoder.h: pa_selector_run) */
+#define PA_CANDIDATE_RULES_DEFINED
 typedef struct {
     double p_value[3], p_value_in_lc[3], report_above_freq[3];
     double snp_q_cutoff, snp_q_cutoff_in_lc, indel_q_cutoff, indel_q_cutoff_in_lc;
 } pa_candidate_rules;
+#endif
 /* The upper-cased reference base (0 outside the window) and the low-complexity flag of the reference's candidate finder
  * (CandidateFinder.py:397-418: a homopolymer run >= 5 touching [p - 5, p + 4) inside the context ref[p - 10, p + 10)) for n
  * positions, out of the text of ONE fetch ref[window_lo, window_lo + text_len) that covers them with 16 bases to spare. */

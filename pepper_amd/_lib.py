@@ -29,6 +29,16 @@ class DevicePack(ctypes.Structure):
                 ("total_bases", c_int64), ("total_ops", c_int64)]
 
 
+class SelectorRegion(ctypes.Structure):
+    """pa_selector_region (include/pepper_amd_encoder.h)."""
+    _fields_ = [("first_row", c_int64), ("reference_start", c_int64), ("reference", c_void_p), ("reference_len", c_int64)]
+
+
+class Selection(ctypes.Structure):
+    """pa_selection: the summary of pa_selector_run / pa_encoder_select_candidates."""
+    _fields_ = [("kept_rows", c_int64), ("kept_name_bytes", c_int64), ("status", c_int32), ("reserved", c_int32)]
+
+
 class PolishConfig(ctypes.Structure):
     _fields_ = [("image_features", c_int32), ("hidden_size", c_int32), ("gru_layers", c_int32),
                 ("num_classes", c_int32), ("seq_length", c_int32), ("window", c_int32),
@@ -131,6 +141,13 @@ SYMBOLS = [
     ("pa_stitcher_take", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_take_qualities", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
+    ("pa_selector_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
+    ("pa_selector_destroy", None, [c_void_p]),
+    ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
+    ("pa_selector_run", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                       c_void_p, c_int32, c_void_p]),
+    ("pa_selector_take", ctypes.c_int, [c_void_p] * 11),
+    ("pa_encoder_select_candidates", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/pepper_amd_realign.h
     ("pa_realigner_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_realigner_destroy", None, [c_void_p]),
@@ -281,6 +298,16 @@ def device_stitch():
     """PEPPER_AMD_DEVICE_STITCH=1: polish() merges the predictions on the device (pa_stitcher_*; pepper_amd/polish/DeviceStitch.py)
     instead of perform_stitch on the host.  Unset or any other value: on the host."""
     return os.environ.get(DEVICE_STITCH_ENV, "0") == "1"
+
+
+DEVICE_SELECTION_ENV = "PEPPER_AMD_DEVICE_SELECTION"
+
+
+def device_selection():
+    """PEPPER_AMD_DEVICE_SELECTION=1: the fused call_variant selects its candidates on the device (pa_selector_*;
+    pepper_amd/variant/DeviceSelect.py) behind the model, and hands the host only the rows that end up in a VCF.  Unset or any
+    other value: on the host (FastCandidates.native_batch_arrays over every row).  Needs fused_inference."""
+    return os.environ.get(DEVICE_SELECTION_ENV, "0") == "1"
 
 
 POLISH_QUALITIES_ENV = "PEPPER_AMD_POLISH_QUALITIES"

@@ -10,8 +10,8 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libpepper_amd.so")
-SOURCES = ["api.hip", "inflate.hip", "gemm.hip", "gemm_h2.hip", "rnn.hip", "rnn_h2.hip", "mlp_h2.hip", "head.hip", "encoder.hip", "encoder_polish.hip", "realign.hip", "stitch.hip"]
-HEADERS = ["common.h", "kernels.h", "encoder_common.h", "reservoir.h", "candidates.h", "pack_rule.h", "dec_frag16.h", os.path.join("..", "..", "include", "pepper_amd.h"),
+SOURCES = ["api.hip", "inflate.hip", "gemm.hip", "gemm_h2.hip", "rnn.hip", "rnn_h2.hip", "mlp_h2.hip", "head.hip", "encoder.hip", "encoder_polish.hip", "realign.hip", "stitch.hip", "select.hip"]
+HEADERS = ["common.h", "kernels.h", "encoder_common.h", "reservoir.h", "candidates.h", "pack_rule.h", "dec_frag16.h", "scan.h", os.path.join("..", "..", "include", "pepper_amd.h"),
            os.path.join("..", "..", "include", "pepper_amd_encoder.h"),
            os.path.join("..", "..", "include", "pepper_amd_realign.h")]
 

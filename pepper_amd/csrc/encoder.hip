@@ -1615,6 +1615,7 @@ struct pa_variant_batch {
     // per-row tables of group_votes_kernel, the tile totals and their scans, the results
     bool dev_cands = false;           // the switch
     bool dev_results = false;         // positions / depths / frequencies / names of the last run are still on the device
+    bool dev_lists = false;           // d_pos / d_depths / d_freqs / d_names hold the last run's lists (enumerated there, or uploaded by selection_view)
     int cand_cap = 1024;              // candidates the result buffers hold (grown when a call has more)
     int64_t dev_calls = 0, host_calls = 0;     // calls enumerated on the device / on the host since the handle was created
     int64_t name_bytes = 0;
@@ -2304,6 +2305,7 @@ int take_device_results(pa_encoder* e, const RunShape& w, int64_t* n_candidates)
     b.n = c0[b.n_tiles];
     b.name_bytes = c0[w.n_cscan - 1];
     b.dev_results = true;
+    b.dev_lists = true;
     b.dev_calls += 1;
     if (n_candidates)
         for (int r = 0; r < w.n_regions; ++r) n_candidates[r] = b.region_n[(size_t)r];
@@ -2422,6 +2424,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.n = 0;
     b.region_n.assign((size_t)n_regions, 0);
     b.positions.clear(); b.depths.clear(); b.freqs.clear(); b.names.clear();
+    b.dev_results = b.dev_lists = false;
     for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
     if (n_regions == 0) return PA_OK;
     const auto t_begin = std::chrono::steady_clock::now();
@@ -2437,6 +2440,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         b.sampled = true;
     }
     b.dev_results = false;
+    b.dev_lists = false;
     b.ms[12] = 0;
     if (w.dev) ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
     int* host_counters = w.host_counters;
@@ -2509,6 +2513,45 @@ int pa_enc::sample_pairs(pa_encoder* e, int32_t n_regions, const int32_t* region
     ENC_HIP(hipMemcpyAsync(s.h_tab.as<char>() + o_out, dt + o_out, c * sizeof(int2), hipMemcpyDeviceToHost, st));
     ENC_HIP(hipMemcpyAsync(h_live, d_live, ((size_t)n_regions + 2) * 4, hipMemcpyDeviceToHost, st));
     s.pending = (int)c;
+    return PA_OK;
+}
+
+int pa_enc::selection_view(pa_encoder* e, int device, hipStream_t stream, SelectionView* out) {
+    if (!e || !out) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!e->variant || !e->variant->staged) return pa::set_error(PA_ERR_INVALID, "select candidates: the encoder has no variant run");
+    if (e->device != device) return pa::set_error(PA_ERR_INVALID, "select candidates: the encoder and the selector are on different devices");
+    pa_variant_batch& b = *e->variant;
+    const size_t n = (size_t)b.n;
+    if (!b.dev_lists) {               // enumerated on the host: its lists go where the device enumeration would have left them
+        if (b.positions.size() != n || b.depths.size() != n || b.freqs.size() != n)
+            return pa::set_error(PA_ERR_INVALID, "select candidates: the last run left no lists");
+        b.name_bytes = (int64_t)b.names.size();
+        ENC_ALLOC(b.d_pos, n * 8 + 8);
+        ENC_ALLOC(b.d_depths, n * 4 + 8);
+        ENC_ALLOC(b.d_freqs, n * 4 + 8);
+        ENC_ALLOC(b.d_names, b.names.size() + 8);
+        if (n) {
+            ENC_HIP(hipMemcpyAsync(b.d_pos.p, b.positions.data(), n * 8, hipMemcpyHostToDevice, stream));
+            ENC_HIP(hipMemcpyAsync(b.d_depths.p, b.depths.data(), n * 4, hipMemcpyHostToDevice, stream));
+            ENC_HIP(hipMemcpyAsync(b.d_freqs.p, b.freqs.data(), n * 4, hipMemcpyHostToDevice, stream));
+            ENC_HIP(hipMemcpyAsync(b.d_names.p, b.names.data(), b.names.size(), hipMemcpyHostToDevice, stream));
+        }
+        b.dev_lists = true;
+    }
+    out->n = b.n;
+    out->name_bytes = b.name_bytes;
+    out->positions = b.d_pos.as<int64_t>();
+    out->depths = b.d_depths.as<int32_t>();
+    out->supports = b.d_freqs.as<int32_t>();
+    out->names = b.d_names.as<char>();
+    out->regions.clear();
+    int64_t first = 0, ref_off = 0;
+    for (size_t r = 0; r < b.regs.size(); ++r) {
+        const pa_pileup& p = b.regs[r].p;
+        out->regions.push_back(SelectionRegion{first, p.region_start, p.reference_len, b.p_ref + ref_off});
+        first += r < b.region_n.size() ? b.region_n[r] : 0;
+        ref_off += p.reference_len;
+    }
     return PA_OK;
 }
 

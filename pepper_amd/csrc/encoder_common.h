@@ -196,6 +196,23 @@ int sample_pairs(pa_encoder* e, int32_t n_regions, const int32_t* region_pairs, 
 void sample_collect(pa_encoder* e);
 }  // namespace pa_enc
 
+namespace pa_enc {
+// What the candidate selection (select.hip: pa_encoder_select_candidates) reads of the encoder's last variant run, all of it in
+// device memory: the lists where the device enumeration left them -- a host-enumerated run's lists are uploaded on `stream`
+// first, once per run --, the references of the staged batch, and per region its first row (from the counts the run's one wait
+// brought back: nothing is downloaded here).
+struct SelectionRegion { int64_t first_row, reference_start, reference_len; const char* reference; };
+struct SelectionView {
+    int64_t n = 0, name_bytes = 0;
+    const int64_t* positions = nullptr;
+    const int32_t* depths = nullptr;
+    const int32_t* supports = nullptr;
+    const char* names = nullptr;
+    std::vector<SelectionRegion> regions;
+};
+int selection_view(pa_encoder* e, int device, hipStream_t stream, SelectionView* out);
+}  // namespace pa_enc
+
 namespace pa_ra {
 // The re-aligner over reads that are already on the device (realign.hip).  reads[k] (ReadRec of pair k: s0, slen, row0 = read
 // position - region start, region, flags) against window `region`: codes [window_off[region], + window_len[region]) of the

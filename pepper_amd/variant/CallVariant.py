@@ -54,6 +54,16 @@ def call_variant(options):
     precomputed = None
     t0 = time.perf_counter()
     fused = bool(getattr(options, "fused_inference", False)) or os.environ.get("PEPPER_AMD_FUSED_CALL_VARIANT") == "1"
+    # the candidate finder's selection on the device behind the model (options.device_selection / PEPPER_AMD_DEVICE_SELECTION=1;
+    # DESIGN.md 4.13).  Its forms: fused + device_selection = lean (no image file, no prediction file, step 3 from the workers'
+    # segments); + keep_images / keep_predictions = the files written as always beside it; without the fused run there is
+    # nothing on the device to select from, and the switch is refused
+    device_selection = bool(getattr(options, "device_selection", False)) or _lib.device_selection()
+    if device_selection and not fused:
+        raise ValueError("ERROR: device_selection (PEPPER_AMD_DEVICE_SELECTION=1) NEEDS fused_inference: THE THREE-STEP RUN SELECTS "
+                         "FROM ITS PREDICTION FILES ON THE HOST.")
+    options.device_selection = device_selection
+    segments = None
     if fused:
         # opt-in: the encoder's windows go to the model where they lie on the device; both HDF5 files are still written
         # (pepper_amd/variant/fused.py).  Steps 1 and 2 are then one step.
@@ -70,13 +80,18 @@ def call_variant(options):
             # (an image worker that raised: the predictions written so far are withdrawn, not published under the final name)
             sink.close(failed=sys.exc_info()[0] is not None)
             precomputed = sink.segments or None
+            if device_selection:
+                segments = sink.device_segments
             if walls is not None:
                 walls["fused_writer_drain"] = getattr(sink, "drain_seconds", 0.0)
                 walls["fused_forward_summed_over_handles"] = sink.forward_seconds
                 walls["fused_writer_busy_summed"], walls["fused_selection_busy_summed"] = sink.write_seconds, sink.select_seconds
             if sink.select_error is not None:
                 _log("INFO: THE FUSED RUN'S CANDIDATE SELECTION STOPPED (" + repr(sink.select_error) + "): STEP 3 DOES THE REST FROM THE FILE")
-            _log("INFO: FUSED: " + str(len(sink.segments)) + " OF " + str(sink.batch_no) + " BATCHES SELECTED AHEAD OF STEP 3")
+            if device_selection:
+                _log("INFO: FUSED: " + str(len(sink.device_segments)) + " SEGMENTS SELECTED BEHIND THE MODEL")
+            else:
+                _log("INFO: FUSED: " + str(len(sink.segments)) + " OF " + str(sink.batch_no) + " BATCHES SELECTED AHEAD OF STEP 3")
         t1 = t2 = time.perf_counter()
     else:
         ImageGenerationUtils.generate_images(options)
@@ -90,7 +105,7 @@ def call_variant(options):
     _log("STEP 3/3 FINDING CANDIDATES")
     _log("OUTPUT: " + str(candidate_output_directory))
     totals = process_candidates(options, prediction_output_directory, candidate_output_directory,
-                                precomputed=precomputed if fused else None)
+                                precomputed=precomputed if fused else None, segments=segments)
     if walls is not None:
         walls.update(make_images=t1 - t0, run_inference=t2 - t1, find_candidates=time.perf_counter() - t2)
 

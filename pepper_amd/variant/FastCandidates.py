@@ -469,15 +469,33 @@ def process(options, all_prediction_pair, vcf, precomputed=None):
                 segments.append(seg)
         if todo:
             flush()
-    plain = _plain_options(options)
-    sizes = np.fromiter(map(len, segments), np.int64, len(segments))
-    n = int(sizes.sum())
     if leftovers:
         # files this package did not write (several alleles in a row's candidate list): the whole job through the tuple path,
         # whose record order (batch by batch) decides which duplicate of a site survives
         from pepper_amd.variant.CandidateFinder import find_candidates
         contigs, _, sites = find_candidates(options, None, all_prediction_pair)
-        return contigs, vcf.write_vcf_records(sites, plain)
+        return contigs, vcf.write_vcf_records(sites, _plain_options(options))
+    return _write_segments(options, segments, vcf)
+
+
+def process_segments(options, segments, vcf):
+    """The segments of a run that has no prediction file (the fused call_variant with device_selection: one _Segment per encoder
+    call, pepper_amd/variant/DeviceSelect.py) -> (contigs, totals), as process() returns them.
+
+    The segments may come in ANY order.  Which record of a site survives is decided by the order of the site's rows after the
+    lexsort below.  All rows of a site come from ONE encoder call -- a call's intervals are disjoint stretches of one contig, and
+    a site lies in exactly one interval -- so they sit in one segment, in row order; the sort is stable, so whatever the order
+    of the segments, a site's rows come out in that row order.  (process() cannot say the same of a prediction FILE, whose
+    batches cut a call's rows wherever batch_size falls: there the listing's order is kept.)"""
+    return _write_segments(options, [seg for seg in segments if len(seg)], vcf)
+
+
+def _write_segments(options, segments, vcf):
+    """The collected segments -> the five files: one stable order by (contig, position), sites with several allele records through
+    the reference's merge, one bulk write per file."""
+    plain = _plain_options(options)
+    sizes = np.fromiter(map(len, segments), np.int64, len(segments))
+    n = int(sizes.sum())
     if n == 0:
         return [], (0, 0, 0, 0, 0)
     # one stable order by (contig name, position), as _by_site / write_vcf_records sort; sites = runs of equal keys

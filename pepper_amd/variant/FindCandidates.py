@@ -29,11 +29,13 @@ def _log(message):
     sys.stderr.write("[" + str(datetime.now().strftime('%m-%d-%Y %H:%M:%S')) + "] INFO: " + message + "\n")
 
 
-def candidate_finder(options, input_dir, output_path, precomputed=None):
+def candidate_finder(options, input_dir, output_path, precomputed=None, segments=None):
     """precomputed: {(prediction file, batch key): FastCandidates segment} of batches whose selection was done while they were
-    written (the fused call_variant); the others are read from the files as always."""
+    written (the fused call_variant); the others are read from the files as always.
+    segments: the FastCandidates segments of a run that has no prediction file to read (the fused call_variant with
+    device_selection): they ARE the job, input_dir is not listed, and the records go through FastCandidates.process_segments."""
     all_prediction_pair = []
-    for prediction_file in get_file_paths_from_directory(input_dir):
+    for prediction_file in (get_file_paths_from_directory(input_dir) if segments is None else []):
         with h5.File(prediction_file, 'r') as hdf5_file:
             if 'predictions' in hdf5_file.keys():
                 for batch in hdf5_file.keys('predictions'):
@@ -47,7 +49,12 @@ def candidate_finder(options, input_dir, output_path, precomputed=None):
         return VCFWriter([], options.fasta, options.sample_name, output_path, "PEPPER_VARIANT_FULL",
                          "PEPPER_VARIANT_OUTPUT_PEPPER", "PEPPER_VARIANT_OUTPUT_VARIANT_CALLING",
                          fasta_handler=factory(options.fasta) if factory is not None else None)
-    if os.environ.get("PEPPER_AMD_CANDIDATES_TUPLES") == "1":
+    if segments is not None:
+        from pepper_amd.variant import FastCandidates
+        vcf_file_full = writer()
+        contigs, totals = FastCandidates.process_segments(options, segments, vcf_file_full)
+        end_time = time.time()
+    elif os.environ.get("PEPPER_AMD_CANDIDATES_TUPLES") == "1":
         # the reference-shaped path: one tuple per selected allele, dictionaries of sites, one record at a time
         contigs, selected_candidates_phasing, selected_candidates_variant_calling = find_candidates(options, input_dir, all_prediction_pair)
         end_time = time.time()
@@ -71,6 +78,6 @@ def candidate_finder(options, input_dir, output_path, precomputed=None):
     return totals
 
 
-def process_candidates(options, input_dir, output_dir, precomputed=None):
+def process_candidates(options, input_dir, output_dir, precomputed=None, segments=None):
     output_dir = ImageGenerationUtils.handle_output_directory(output_dir)
-    return candidate_finder(options, input_dir, output_dir, precomputed=precomputed)
+    return candidate_finder(options, input_dir, output_dir, precomputed=precomputed, segments=segments)

@@ -10,6 +10,7 @@ group per interval that produced candidates.  BAM/FASTA access goes through `opt
 methods); reading BAM/FASTA files needs htslib and is the "next" row N3, so without factories this
 raises.  Workers run sequentially in-process (one GPU encoder), not in a ProcessPoolExecutor.
 """
+import contextlib
 import os
 import re
 import sys
@@ -65,6 +66,17 @@ def _handlers(options, bam_path, fasta_path):
     if ff is None:
         from pepper_amd.variant.fasta import FASTA_handler as ff
     return bf(bam_path), ff(fasta_path)
+
+
+def _live_rows(probs, outs, live):
+    """The probabilities of a call's rows without those of intervals that have no read (which write nothing)."""
+    keep, at = [], 0
+    for out, n_reads in zip(outs, live):
+        k = len(out["positions"])
+        if n_reads > 0:
+            keep.append(probs[at:at + k])
+        at += k
+    return np.concatenate(keep) if keep else probs[:0]
 
 
 class ImageGenerator:
@@ -180,9 +192,11 @@ class ImageGenerationUtils:
         # ... and the encoder calls of the packed form (one per group of intervals), with those whose candidates were enumerated
         # on the device / handed back to the host (both 0 unless PEPPER_AMD_DEVICE_CANDIDATES=1), and those whose read and pair
         # tables were built on the device (PEPPER_AMD_DEVICE_PACK=1) / on the host
+        # ... and, in a fused run with device_selection, the encoder calls whose candidates were selected on the device (one
+        # segment per call, pepper_amd/variant/fused.py: forward_select) / the calls and host-clipped groups selected the host way
         mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0,
                 "encoder_calls": 0, "device_enumerated_calls": 0, "host_enumerated_calls": 0,
-                "device_packed_calls": 0, "host_packed_calls": 0}
+                "device_packed_calls": 0, "host_packed_calls": 0, "device_selected_calls": 0, "host_selected_calls": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -190,11 +204,25 @@ class ImageGenerationUtils:
             return now
 
         sink = getattr(options, "fused_sink", None)         # call_variant's fused form: predictions straight from the encoder's windows
+        # ... with the selection on the device behind the model: segments instead of probabilities, and neither HDF5 file unless
+        # options.keep_images / options.keep_predictions ask for them
+        selecting = sink is not None and sink.device_selection
+        keep_images = not selecting or bool(getattr(options, "keep_images", False))
+        keep_predictions = sink is not None and sink.keep_predictions
 
-        def write(output_hdf_file, chr_name, _start, _end, out, probs=None):
+        def write(output_hdf_file, chr_name, _start, _end, out, probs=None, selected=False):
+            """selected: the interval's call has been through the model and the selection already (probs None: and nobody wants
+            its probabilities)."""
             n = len(out["candidates"])
             if sink is not None:
-                sink.submit(chr_name, out, probs if probs is not None else sink.forward_host(device, out["images"]))
+                if probs is None and not selected:
+                    probs = sink.forward_host(device, out["images"])
+                    if selecting:                        # a host-clipped interval: selected the present way
+                        sink.select_host(chr_name, [out], probs)
+                if probs is not None:
+                    sink.submit(chr_name, out, probs)
+            if output_hdf_file is None:
+                return
             summary_name = chr_name + "_" + str(_start) + "_" + str(_end)
             if output_hdf_file.write_summary_packed(summary_name, chr_name, out):
                 return
@@ -214,15 +242,19 @@ class ImageGenerationUtils:
                     generators.clear()               # one contig's handles at a time per worker
                     generators[chr_name] = ImageGenerator(chr_name, options.bam, options.fasta, wopts)
                 prepared.append(generators[chr_name].prepare(wopts, _start, _end))
+            t0 = time.perf_counter()
             for (chr_name, _start, _end), out in zip(group, create_summaries(prepared)):
                 if out is not None:
                     write(output_hdf_file, chr_name, _start, _end, out)
+            if selecting:
+                mine["host_selected_calls"] += 1
+                lap("fused_select", t0)
 
         packed = (getattr(options, "bam_handler_factory", None) is None and getattr(options, "fasta_handler_factory", None) is None
                   and os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0" and not getattr(options, "train_mode", False))
         if getattr(options, "use_hp_info", False):
             packed = False                           # (host_clipped raises the reference's message for it)
-        with DataStore(file_name, 'w') as output_hdf_file:
+        with (DataStore(file_name, 'w') if keep_images else contextlib.nullcontext()) as output_hdf_file:
             if not packed:
                 for g0 in range(0, len(intervals), batch):
                     host_clipped(output_hdf_file, intervals[g0:g0 + batch])
@@ -295,10 +327,12 @@ class ImageGenerationUtils:
                     whole = fasta_handler.get_reference_bytes(chr_name, lo, hi)
                     references = [whole[a - lo:b + 1 - lo] for a, b in regions]
                     t0 = lap("fasta", t0)
+                    # (the lean form of device_selection fetches no list and no image: outs are then the counts per interval)
+                    fetch = keep_images or keep_predictions
                     try:
                         outs, live = enc.encode(regions, references, region_pairs, counts, params, [(s, e) for _, s, e in group],
                                                 ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident,
-                                                sampling=sampling)
+                                                sampling=sampling, fetch=fetch)
                     except _lib.PepperAmdError as err:
                         if getattr(err, "code", 0) != _lib.PA_ERR_UNSUPPORTED:
                             raise
@@ -309,7 +343,30 @@ class ImageGenerationUtils:
                     mine["encoder_calls"] += 1
                     mine["device_packed_calls" if (resident and enc.device_packed) else "host_packed_calls"] += 1
                     probs, at = None, 0
-                    if sink is not None:
+                    if selecting:
+                        # model and selection back to back on the device; what comes back is the call's segment
+                        per_interval = [len(o["positions"]) for o in outs] if fetch else [int(k) for k in outs]
+                        total = sum(per_interval)
+                        if any(k > 0 and n_reads <= 0 for k, n_reads in zip(per_interval, live)):
+                            raise RuntimeError("fused device selection: candidates in an interval without reads")
+                        segment, probs = sink.forward_select(device, enc, total, chr_name, want_probs=keep_predictions)
+                        if segment is None:              # handed back: this call the present way
+                            if not fetch:
+                                outs = enc.last.results()
+                            sink.select_host(chr_name, [o for o, n_reads in zip(outs, live) if n_reads > 0], _live_rows(probs, outs, live))
+                            mine["host_selected_calls"] += 1
+                        else:
+                            sink.add_segment(segment)
+                            mine["device_selected_calls"] += 1
+                            # rows the device looked at / kept, and the bytes of the kept rows that came back
+                            mine["device_selection_rows"] = mine.get("device_selection_rows", 0) + total
+                            mine["device_selection_kept"] = mine.get("device_selection_kept", 0) + len(segment)
+                            mine["device_selection_bytes"] = mine.get("device_selection_bytes", 0) + getattr(segment, "downloaded_bytes", 0)
+                        t0 = lap("fused_select", t0)
+                        if not fetch:
+                            g0 += n_done
+                            continue
+                    elif sink is not None:
                         # the group's windows are still where the encoder left them on the device: the model reads them there
                         total = sum(len(o["positions"]) for o in outs)
                         probs = sink.forward_device(device, enc.lib.pa_encoder_device_images(enc.enc), total)
@@ -317,7 +374,7 @@ class ImageGenerationUtils:
                     for (chr_name, _start, _end), out, n_reads in zip(group, outs, live):
                         k = len(out["positions"])
                         if n_reads > 0:                  # (no read with a base inside, or an empty sample: create_summary returns None, nothing is written)
-                            write(output_hdf_file, chr_name, _start, _end, out, None if probs is None else probs[at:at + k])
+                            write(output_hdf_file, chr_name, _start, _end, out, None if probs is None else probs[at:at + k], selected=selecting)
                         at += k
                     lap("hdf5", t0)
                     g0 += n_done

@@ -622,13 +622,15 @@ class PackedEncoder(object):
         return False, n_done, region_pairs, counts
 
     def encode(self, regions, references, region_pairs, counts, params, candidate_regions, candidate_window_size=32, feature_size=26,
-               want_int32=False, resident=False, sampling=None):
+               want_int32=False, resident=False, sampling=None, fetch=True):
         """regions: [(ref_start, ref_end)] of the packed run (the fetch ranges), references: their sequences (bytes / str),
         region_pairs / counts: what pack() returned, params: the ten thresholds of generate_summary in order,
         candidate_regions: [(start, end)].  sampling: (seed, max_reads, downsample_rate) -- intervals with more reads than
         int(min(max_reads, rate * n)) are sampled down on the device as the reference does on the host
         (pa_encoder_set_sampling); None: not.  -> (one dict of arrays per region as generate_summary_arrays, reads per
-        region -- after sampling)."""
+        region -- after sampling).  fetch=False: no list and no image is downloaded -- the first value is then the candidates per
+        region (int64 [n]), and the results stay on the device for pa_variant_forward_device and pa_encoder_select_candidates
+        (self.last.results() still fetches them, e.g. for a call the device selection hands back)."""
         n = len(regions)
         self.set_sampling(sampling)
         refs = [r.encode("latin-1") if isinstance(r, str) else bytes(r) for r in references]
@@ -664,6 +666,8 @@ class PackedEncoder(object):
         live = np.zeros(max(1, n), np.int32)
         _lib.check(self.lib.pa_encoder_region_reads(self.enc, live.ctypes.data, n))
         self.last = batch
+        if not fetch:
+            return batch.counts[:n].copy(), live[:n]
         return batch.results(want_int32), live[:n]
 
 

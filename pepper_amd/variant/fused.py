@@ -7,6 +7,14 @@ H2D round trip for the model's input) and queues the predictions for one writer 
 the reference's layouts -- the image files by the workers as before, `pepper_prediction.hdf` (predictions/batch_<n> groups of
 options.batch_size candidates) by the writer in arrival order.  Which batch a candidate lands in differs from the unfused run (the
 candidate finder sorts sites itself, CandidateFinder.py:356-581); every candidate's record is the same.
+
+With options.device_selection (PEPPER_AMD_DEVICE_SELECTION=1) the candidate finder's selection follows the model ON
+THE DEVICE (forward_select: pa_variant_forward_device, then pa_encoder_select_candidates on the same stream, while the worker
+holds the model handle and its selector): the worker gets a FastCandidates segment per encoder call -- the rows that end up in
+a VCF -- instead of probabilities, and step 3 writes the VCFs from those segments (FastCandidates.process_segments).  The lean
+form writes neither HDF5 file and starts no writer and no selector thread; options.keep_images / options.keep_predictions ask
+for the files, which are then downloaded and written as always beside the device selection.  A call the kernels hand back, and
+every host-clipped group, is selected the host way (select_host) and its segment joins the same list.
 """
 import ctypes
 import os
@@ -32,8 +40,15 @@ class FusedPredictor(object):
         self.batch_size = int(options.batch_size)
         self.models = {}
         self.models_lock = threading.Lock()
+        # the selection on the device: the workers collect segments (device_segments), no batch is selected on a host thread
+        self.device_selection = bool(getattr(options, "device_selection", False))
+        self.keep_predictions = not self.device_selection or bool(getattr(options, "keep_predictions", False))
+        self.device_segments = []
+        self.rules = None
+        self.output_filepath = output_filepath
+        self.host_files = 0
         # (the append-only writer: ~9 000 batch groups per 256 Mb cost the writer thread 0.3 ms each through libhdf5)
-        self.store = DataStore(output_filepath + "pepper_prediction.hdf", mode='w', bulk=True)
+        self.store = DataStore(output_filepath + "pepper_prediction.hdf", mode='w', bulk=True) if self.keep_predictions else None
         self.queue = queue.Queue(maxsize=64)
         self.error = None
         self.batch_no = 0
@@ -49,14 +64,20 @@ class FusedPredictor(object):
         self.segments = {}
         self.select_queue = queue.Queue()
         self.selector = None
-        if not getattr(options, "fused_candidates_off", False):
+        if self.device_selection:
+            from pepper_amd.variant import FastCandidates
+            self.rules = FastCandidates._rules(options)      # (None: thresholds the library does not take -- every call the host way)
+            self.select_fasta = threading.local()
+        elif not getattr(options, "fused_candidates_off", False):
             # (two threads: a batch is ~0.4 ms here against ~0.3 ms in the writer, and the library calls release the interpreter)
             self.selector = [threading.Thread(target=self._select_loop, name="fused-candidate-selection-%d" % k, daemon=True)
                              for k in range(max(1, int(os.environ.get("PEPPER_AMD_FUSED_SELECTORS", 2))))]
             for t in self.selector:
                 t.start()
-        self.writer = threading.Thread(target=self._write_loop, name="fused-prediction-writer", daemon=True)
-        self.writer.start()
+        self.writer = None
+        if self.store is not None:
+            self.writer = threading.Thread(target=self._write_loop, name="fused-prediction-writer", daemon=True)
+            self.writer.start()
 
     # ---- model ----
     HANDLES = 2          # forwards in flight per device: while one handle's results come back, the other's kernels run
@@ -128,6 +149,88 @@ class FusedPredictor(object):
                 self.forward_seconds += time.perf_counter() - t0    # (summed over the handles: not a wall time)
             entry["free"].put(model)
 
+    def forward_select(self, device, enc, n, contig, want_probs=False):
+        """The encoder's last run (enc: the worker's PackedEncoder; n windows, all of `contig`) through the model and the device
+        selection, back to back on the model handle's stream while this worker holds the handle.
+        -> (segment, probabilities): segment None when the selection handed the call back (or the rules are not numbers); the
+        probabilities [n, 3] on the host when want_probs or when the call was handed back, else None."""
+        from pepper_amd.variant import DeviceSelect
+        if n == 0:
+            return DeviceSelect.segment(self.rules, contig, DeviceSelect.Taken.empty()), np.zeros((0, ImageSizeOptions.TOTAL_TYPE_LABELS), np.float32)
+        entry, model = self._model(device)
+        lib = _lib.load()
+        t0 = time.perf_counter()
+        try:
+            torch.cuda.set_device(device)
+            with torch.cuda.stream(model._stream):
+                probs = torch.empty((n, model.num_classes_type), dtype=torch.float32, device=torch.device("cuda", device))
+                _lib.check(lib.pa_variant_forward_device(model.handle, ctypes.c_void_p(lib.pa_encoder_device_images(enc.enc)), n,
+                                                         probs.data_ptr(), None))
+                taken = None
+                if self.rules is not None:
+                    selector = getattr(model, "_selector", None)
+                    if selector is None:                 # one selector per model handle, on the handle's stream
+                        selector = model._selector = DeviceSelect.DeviceSelector(device, model._stream)
+                    status, _, _ = selector.run_encoder(enc.enc, self.rules, probs)
+                    if status == 0:
+                        taken = selector.take()
+                host_probs = None
+                if want_probs or taken is None:
+                    model._stream.synchronize()
+                    host_probs = probs.cpu().numpy()
+        finally:
+            with self.timer_lock:
+                self.forward_seconds += time.perf_counter() - t0
+            entry["free"].put(model)
+        return (DeviceSelect.segment(self.rules, contig, taken) if taken is not None else None), host_probs
+
+    def select_host(self, contig, outs, probs):
+        """The present way for the calls the device does not select -- handed back, or host-clipped: the call's lists (outs: the
+        encoder's dicts of its intervals, all of `contig`) and probabilities through FastCandidates.native_batch_arrays; a call
+        even that does not take goes through the per-row Python path, by way of a prediction file of its own (withdrawn again
+        unless the run keeps its predictions).  The segment joins device_segments."""
+        from pepper_amd.variant import FastCandidates
+        outs = [o for o in outs if len(o["positions"])]
+        if not outs:
+            return
+        fasta_handler = getattr(self.select_fasta, "handler", None)
+        if fasta_handler is None:
+            fasta_handler = self.select_fasta.handler = FastCandidates._fasta(self.options)
+        first = contig.encode() if isinstance(contig, str) else bytes(contig)
+        positions = np.concatenate([np.asarray(o["positions"], np.int64) for o in outs])
+        depths = np.concatenate([np.asarray(o["depths"]) for o in outs])
+        freqs = np.concatenate([np.asarray(o["candidate_frequency"]) for o in outs]).reshape(-1, 1)
+        blob = b"".join(bytes(o["candidates_blob"]) if "candidates_blob" in o else
+                        b"".join(c.encode("latin-1") + b"\0" for c in o["candidates"]) for o in outs)
+        n = len(positions)
+        probs = np.ascontiguousarray(probs, np.float32).reshape(n, -1)
+        seg = None
+        if self.rules is not None:
+            seg = FastCandidates.native_batch_arrays(self.options, self.rules, fasta_handler, first, n, positions, depths, freqs, probs, blob)
+        if seg is None:
+            with self.timer_lock:
+                self.host_files += 1
+                name = self.output_filepath + "pepper_prediction_host_selected_%d.hdf" % self.host_files
+            store = DataStore(name, mode='w')
+            cands = np.array([[c.decode("latin-1")] for c in blob.split(b"\0")[:n]], dtype=object).reshape(n, 1)
+            store.write_prediction(0, [first.decode()] * n, positions.astype(np.int32), depths.astype(np.uint8), cands,
+                                   freqs.astype(np.uint8), probs)
+            store.close()
+            leftovers = []
+            try:
+                seg = FastCandidates._python_batch(self.options, fasta_handler, name, "batch_0", leftovers)
+            finally:
+                if not getattr(self.options, "keep_predictions", False):
+                    os.remove(name)
+            if leftovers:
+                raise RuntimeError("fused device selection: a call with several alleles in one candidate list")
+        self.add_segment(seg)
+
+    def add_segment(self, seg):
+        if seg is not None and len(seg):
+            with self.timer_lock:
+                self.device_segments.append(seg)
+
     def forward_host(self, device, images):
         """int8 windows on the host (the host-clipped form of image generation) -> probabilities."""
         if len(images) == 0:
@@ -145,6 +248,8 @@ class FusedPredictor(object):
         candidate_frequency); probs float32 [n, 3]."""
         if self.error is not None:
             raise self.error
+        if self.store is None:           # (the lean form of device_selection: no prediction file)
+            return
         if len(out["positions"]):
             self.queue.put((threading.get_ident(), contig, out, probs))
 
@@ -254,20 +359,26 @@ class FusedPredictor(object):
         """failed: the run is being abandoned (an image worker raised): whatever was written is withdrawn -- a partial
         pepper_prediction.hdf under its final name would be read by a re-run of step 3 as if it were complete."""
         t0 = time.perf_counter()
-        self.queue.put(None)
-        self.writer.join()
+        if self.writer is not None:
+            self.queue.put(None)
+            self.writer.join()
         if self.selector is not None:
             for _ in self.selector:
                 self.select_queue.put(None)
             for t in self.selector:
                 t.join()
         self.drain_seconds = time.perf_counter() - t0      # what the two threads still had to do when image generation was over
-        if self.error is not None or failed:
+        if self.store is None:
+            pass
+        elif self.error is not None or failed:
             self.store.abort()                             # (no partial predictions file for the next step's listing)
         else:
             self.store.close()
         for entry in self.models.values():
             for model in entry["all"]:
+                if getattr(model, "_selector", None) is not None:
+                    model._selector.close()
+                    model._selector = None
                 model.close()
         self.models.clear()
         if self.error is not None:

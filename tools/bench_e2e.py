@@ -4,6 +4,8 @@
       pepper_amd.variant.CallVariant.call_variant (pepper_variant call_variant, CallVariant.py:74-104):
       BAM + FASTA + checkpoint -> image HDF5 -> predictions HDF5 -> five VCFs
   python tools/bench_e2e.py call_variant_fused <dir> ...     the same with options.fused_inference (pepper_amd/variant/fused.py)
+      --device-selection (also on call_variant, which then runs fused: the selection needs it): with options.device_selection, the lean form (pepper_amd/variant/DeviceSelect.py: no image file, no
+      prediction file); --keep-files with it: keep_images and keep_predictions, the files written beside the device selection
   python tools/bench_e2e.py polish <dir> [draft_bases=64000000] [coverage=60] [runs=3]
   python tools/bench_e2e.py polish_fused <dir> ...           the same with fused_inference=True (pepper_amd/polish/fused.py)
       pepper_amd.polish.polish.polish (pepper polish, polish.py:94-117): BAM + draft + checkpoint -> images -> predictions -> FASTA
@@ -78,7 +80,7 @@ def median_run(runs, key="seconds"):
     return order[len(order) // 2]
 
 
-def call_variant_job(work, bases, coverage, n_runs, fused=False):
+def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selection=False, keep_files=False):
     from pepper_amd.hostinfo import usable_cpus
     from pepper_amd.variant.CallVariant import call_variant
     info = synth(work, bases, coverage)
@@ -100,7 +102,7 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False):
             sample_name="SYN", allowed_multiallelics=4, snp_p_value=0.1, insert_p_value=0.25, delete_p_value=0.25, snp_p_value_in_lc=0.1,
             insert_p_value_in_lc=0.3, delete_p_value_in_lc=0.3, snp_q_cutoff=20, indel_q_cutoff=15, snp_q_cutoff_in_lc=20,
             indel_q_cutoff_in_lc=10, report_snp_above_freq=0, report_indel_above_freq=0, stage_walls=walls, stage_seconds=stages,
-            fused_inference=fused)
+            fused_inference=fused, device_selection=device_selection, keep_images=keep_files, keep_predictions=keep_files)
         t0 = time.perf_counter()
         image_dir, pred_dir, totals = call_variant(options)
         dt = time.perf_counter() - t0
@@ -113,6 +115,8 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False):
             with h5.File(path) as f:
                 for g in f.keys("predictions"):
                     windows += f.info("predictions/" + g + "/positions")[0][0]
+        if device_selection and not keep_files:
+            windows = int(stages.get("device_selection_rows", 0))          # (no prediction file to count them in)
         if k > 0:
             runs.append({"seconds": round(dt, 3), "stage_walls": {n: round(v, 3) for n, v in walls.items()}, "windows": windows,
                          "image_stage_seconds_summed_over_workers": {n: round(v, 2) for n, v in sorted(stages.items()) if n != "inflated_bytes"},
@@ -120,7 +124,8 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False):
         shutil.rmtree(out, ignore_errors=True)
     mid = median_run(runs)
     longest = max(mid["stage_walls"].get(n, 0.0) for n in ("make_images", "run_inference", "find_candidates"))
-    return {"metric": "call_variant end to end (BAM + FASTA + checkpoint -> 5 VCFs)" + (", images and inference fused" if fused else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
+    return {"metric": "call_variant end to end (BAM + FASTA + checkpoint -> 5 VCFs)" + (", images and inference fused" if fused else "") +
+                      (", device selection" + (", files kept" if keep_files else ", lean") if device_selection else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
             "unit": "Mb of reference/s", "seconds": mid["seconds"], "runs_seconds": [r["seconds"] for r in runs], "stage_walls": mid["stage_walls"],
             "wall_over_longest_stage": round(mid["seconds"] / longest, 3), "windows": mid["windows"],
             "runs_stage_walls": [r["stage_walls"] for r in runs],
@@ -179,12 +184,17 @@ def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, q
 
 
 if __name__ == "__main__":
+    flags = {a for a in sys.argv[1:] if a.startswith("--")}
+    sys.argv = [a for a in sys.argv if not a.startswith("--")]
+    if flags - {"--device-selection", "--keep-files"}:
+        raise SystemExit("unknown flag: " + " ".join(sorted(flags - {"--device-selection", "--keep-files"})))
     kind, work = sys.argv[1], sys.argv[2]
     bases = float(sys.argv[3]) if len(sys.argv) > 3 else (256e6 if kind.startswith("call_variant") else 64e6)
     coverage = float(sys.argv[4]) if len(sys.argv) > 4 else (30 if kind.startswith("call_variant") else 60)
     n_runs = int(sys.argv[5]) if len(sys.argv) > 5 else 3
-    if kind == "call_variant_fused":
-        print(json.dumps(call_variant_job(work, bases, coverage, n_runs, fused=True)))
+    if kind == "call_variant_fused" or (kind == "call_variant" and "--device-selection" in flags):      # (the selection needs the fused run)
+        print(json.dumps(call_variant_job(work, bases, coverage, n_runs, fused=True, device_selection="--device-selection" in flags,
+                                          keep_files="--keep-files" in flags)))
     elif kind.startswith("polish"):
         qualities = True if kind.endswith("_qualities") else None
         form = kind[:-len("_qualities")] if qualities else kind
