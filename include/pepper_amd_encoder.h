@@ -374,8 +374,37 @@ int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity);
  * The handle stays usable. */
 int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
 /* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
- * its tables (the quality buffer among them when the finish produced qualities). */
+ * its tables (the quality buffer among them when the finish produced qualities, the edit records once pa_stitcher_edits ran). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
+
+/* What the last finish changed against the draft (opt-in, not in the reference; pepper_amd/polish/Edits.py is the host twin and
+ * writes the text).  Pieces in take() order, inside a piece the keys (position, insert index) in order; one record for
+ *   SUB        slot (p, 0)      the winner is a base and differs from upper(draft[p]) (a draft letter outside ACGT always does)
+ *   DEL        slot (p, 0)      the winner is a gap, or the slot has no writer
+ *   INS        slot (p, i > 0)  the winner is a base
+ *   GAP_OPEN   position p inside the piece without a slot, p - 1 has one
+ *   GAP_CLOSE  position p inside the piece without a slot, p + 1 has one (a run of one position: both, GAP_OPEN first)
+ * offset counts letters of pa_stitcher_take: the record's own letter for SUB and INS, the letters in front of it otherwise. */
+enum { PA_EDIT_SUB = 1, PA_EDIT_DEL = 2, PA_EDIT_INS = 3, PA_EDIT_GAP_OPEN = 4, PA_EDIT_GAP_CLOSE = 5 };
+typedef struct pa_stitch_edit {
+    uint32_t position;   /* of the draft */
+    uint32_t offset;     /* of the consensus */
+    uint16_t index;      /* insert index */
+    uint16_t piece;      /* the piece's place in take() order */
+    uint8_t kind;        /* PA_EDIT_* */
+    uint8_t draft;       /* the draft letter upper-cased; 0 for INS */
+    uint8_t letter;      /* A, C, G or T; 0 for DEL and the GAP kinds */
+    uint8_t phred;       /* the winner's raw phred; 0 without a winner, for the GAP kinds, and for a contig without qualities */
+} pa_stitch_edit;        /* 16 bytes */
+/* Compare the tables of the last finish with draft[0 .. draft_length): *n_edits records, counts[k] of kind k (counts[0] = 0).
+ * One wait; the records stay on the device until pa_stitcher_take_edits, in a buffer allocated on first use and counted in
+ * pa_stitcher_stats [5] from then on.  A later finish invalidates them.
+ * PA_ERR_INVALID before any launch: no finish yet; the last finish gave no sequence (a bad label, a failure); draft_length <=
+ * the largest piece_last; the finish had more than 65 535 pieces.  The handle stays usable. */
+int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts /* [6] */);
+/* The records of the last pa_stitcher_edits (capacity >= *n_edits records).  PA_ERR_INVALID: pa_stitcher_edits has not run since
+ * the last finish; capacity is short.  The handle stays usable. */
+int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity);
 
 /* ------------------------------------------------------------------------------------------
  * The candidate finder's selection ON THE DEVICE (opt-in: call_variant(..., fused_inference=True, device_selection=True);

@@ -141,6 +141,8 @@ SYMBOLS = [
     ("pa_stitcher_take", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_take_qualities", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
+    ("pa_stitcher_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_stitcher_take_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_selector_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_selector_destroy", None, [c_void_p]),
     ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
@@ -317,6 +319,15 @@ def polish_qualities():
     """PEPPER_AMD_POLISH_QUALITIES=1: polish() writes <prefix>_pepper_polished.fastq beside the FASTA, every base with the phred of
     the prediction row that supplied it.  Unset or any other value: the FASTA alone."""
     return os.environ.get(POLISH_QUALITIES_ENV, "0") == "1"
+
+
+POLISH_EDITS_ENV = "PEPPER_AMD_POLISH_EDITS"
+
+
+def polish_edits():
+    """PEPPER_AMD_POLISH_EDITS=1: polish() writes <prefix>_pepper_polished.edits.tsv beside the FASTA: what the consensus changed
+    against the draft (pepper_amd/polish/Edits.py).  Unset or any other value: the FASTA alone."""
+    return os.environ.get(POLISH_EDITS_ENV, "0") == "1"
 
 
 def check(rc):

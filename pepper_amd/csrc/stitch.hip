@@ -20,6 +20,13 @@
 // Qualities (pa_stitcher_add_qual, pa_stitcher_take_qualities): a row added with its phred carries it above the position, the
 // scatter word carries it between the rank and the label, and the emit that places the letters places, from the same winner,
 // chr(33 + min(phred, 93)) into a second buffer -- no further scan, no further wait.
+//
+// Edits (pa_stitcher_edits, pa_stitcher_take_edits; opt-in, not in the reference): what the consensus changed against the draft,
+// read off the tables the last finish left.  One lane per SLOT (not per position: a position with thousands of insert slots
+// spreads over as many lanes); a lane finds its position by bisecting the slot bases, so it needs no table of its own.  A slot
+// gives 0 or 1 record, and the slot (p, 0) behind a run of uncovered positions carries the run's two GAP records in front of
+// its own: every run is closed by exactly one such slot.  Count (block sums), scan of the sums, write: the write pass scans
+// its block again instead of reading a per-slot prefix, so the only table this adds is the records themselves.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -231,6 +238,161 @@ struct LoadLetter {
     PA_DEV uint64_t operator()(uint64_t i) const { return p[i] != 0; }
 };
 
+// ---------------------------------------------------------------- edits against the draft ----
+struct EditTables {                                     // the last finish's tables, as the edit passes read them
+    const uint32_t* slot_base;                          // [n_positions] slot of key (position, 0)
+    const uint32_t* width;                              // [n_positions]
+    const unsigned long long* slots;                    // [n_slots] winner words
+    const uint8_t* letters;                             // [n_slots]
+    const uint32_t* place;                              // [n_slots] letters in front of the slot, in table order
+    const uint64_t* pbase;                              // [n_pieces] first position row of a piece
+    const uint32_t* pmin;                               // [n_pieces] its first position
+    const int64_t* letter_shift;                        // [n_pieces] take() offset of the piece's first letter - its table offset
+    const uint16_t* take_index;                         // [n_pieces] the piece's place in take() order
+    const uint8_t* draft;                               // draft[draft_lo .. draft_lo + draft_span)
+    uint64_t n_positions, n_slots;
+    uint32_t n_pieces, draft_lo, draft_span, qualities;
+};
+
+struct SlotEdit {
+    uint32_t kind;                                      // 0: none, else PA_EDIT_SUB / DEL / INS
+    bool gap;                                           // the slot closes a run of uncovered positions
+    uint32_t position, index, piece, open_at;           // open_at: first position of that run
+    uint8_t draft, letter;
+};
+
+// the last i in [0, n) with v[i] <= key (v ascending, v[0] <= key)
+template <class T, class K> PA_DEV uint64_t last_at_most(const T* __restrict__ v, uint64_t n, K key) {
+    uint64_t lo = 0, hi = n;                             // v[lo] <= key < v[hi]
+    while (hi - lo > 1) {
+        const uint64_t mid = lo + (hi - lo) / 2;
+        if (v[mid] <= key) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) {
+    SlotEdit e;
+    // zero-width positions share the base of the next covered one: the LAST position whose base is <= s owns the slot
+    const uint64_t gp = last_at_most(t.slot_base, t.n_positions, (uint32_t)s);
+    e.piece = (uint32_t)last_at_most(t.pbase, (uint64_t)t.n_pieces, gp);      // (a piece without rows shares the next one's base)
+    const uint64_t row0 = t.pbase[e.piece];
+    e.position = t.pmin[e.piece] + (uint32_t)(gp - row0);
+    e.index = (uint32_t)s - t.slot_base[gp];
+    e.letter = t.letters[s];
+    e.draft = 0;
+    e.kind = 0;
+    e.gap = false;
+    e.open_at = 0;
+    if (e.index > 0) {
+        if (e.letter) e.kind = PA_EDIT_INS;
+        return e;
+    }
+    const uint32_t at = e.position - t.draft_lo;
+    uint8_t d = at < t.draft_span ? t.draft[at] : (uint8_t)0;
+    if (d >= 'a' && d <= 'z') d = (uint8_t)(d - 32);
+    e.draft = d;
+    if (!e.letter) e.kind = PA_EDIT_DEL;
+    else if (e.letter != d) e.kind = PA_EDIT_SUB;
+    if (gp > row0 && t.width[gp - 1] == 0) {            // the piece's first position has a slot, so slot s - 1 is the piece's too
+        const uint64_t before = last_at_most(t.slot_base, t.n_positions, (uint32_t)(s - 1));
+        e.gap = true;
+        e.open_at = e.position - (uint32_t)(gp - before) + 1;
+    }
+    return e;
+}
+
+// sums[b] = records of slots [b * B, (b + 1) * B) (a workgroup past the end writes 0); kinds[k] += records of kind k
+__global__ __launch_bounds__(ST_THREADS) void k_edit_count(EditTables t, uint64_t* __restrict__ sums,
+                                                           unsigned long long* __restrict__ kinds) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    __shared__ uint64_t s_kind[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    uint64_t v = 0, packed = 0;                         // packed: SUB | DEL << 16 | INS << 32 | gaps << 48 (a workgroup has <= 1024 each)
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        if (i0 + k >= t.n_slots) break;
+        const SlotEdit e = classify_slot(t, i0 + k);
+        v += (e.kind != 0) + (e.gap ? 2 : 0);
+        if (e.kind) packed += 1ull << (16 * (e.kind - 1));
+        if (e.gap) packed += 1ull << 48;
+    }
+    for (int d = 32; d; d >>= 1)
+        packed += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(packed >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)packed, d);
+    if ((threadIdx.x & 63) == 0) s_kind[threadIdx.x >> 6] = packed;
+    uint64_t total;
+    (void)block_scan(v, s_wave, &total);               // (its barrier also publishes s_kind)
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = total;
+        uint64_t all = 0;
+        for (int w = 0; w < ST_THREADS / 64; ++w) all += s_kind[w];
+        const unsigned long long sub = all & 0xFFFFu, del = (all >> 16) & 0xFFFFu, ins = (all >> 32) & 0xFFFFu, gaps = all >> 48;
+        if (sub) atomicAdd(&kinds[PA_EDIT_SUB], sub);     // one atomic per workgroup and kind; integer sums do not depend on the order
+        if (del) atomicAdd(&kinds[PA_EDIT_DEL], del);
+        if (ins) atomicAdd(&kinds[PA_EDIT_INS], ins);
+        if (gaps) {
+            atomicAdd(&kinds[PA_EDIT_GAP_OPEN], gaps);
+            atomicAdd(&kinds[PA_EDIT_GAP_CLOSE], gaps);
+        }
+    }
+}
+
+PA_DEV pa_stitch_edit make_edit(uint32_t position, uint32_t offset, uint32_t index, uint32_t piece, uint32_t kind, uint8_t draft,
+                                uint8_t letter, uint8_t phred) {
+    pa_stitch_edit r;
+    r.position = position;
+    r.offset = offset;
+    r.index = (uint16_t)index;
+    r.piece = (uint16_t)piece;
+    r.kind = (uint8_t)kind;
+    r.draft = draft;
+    r.letter = letter;
+    r.phred = phred;
+    return r;
+}
+
+// the records of slot i go to out[offset[b] + records of the block's slots in front of i ..): k_scan_down's walk with the
+// classification in place of a load.  piece_start[p] = where the records of piece p begin.
+__global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const uint64_t* __restrict__ offset, uint64_t n_edits,
+                                                           pa_stitch_edit* __restrict__ out, uint64_t* __restrict__ piece_start) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    SlotEdit item[ST_ITEMS];
+    uint64_t v = 0;
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        item[k].kind = 0;
+        item[k].gap = false;
+        if (i0 + k < t.n_slots) item[k] = classify_slot(t, i0 + k);
+        v += (item[k].kind != 0) + (item[k].gap ? 2 : 0);
+    }
+    uint64_t total;
+    uint64_t run = block_scan(v, s_wave, &total) - v + offset[blockIdx.x];
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        if (i0 + k >= t.n_slots) break;
+        const SlotEdit& e = item[k];
+        const uint32_t piece = t.take_index[e.piece];
+        const uint32_t letters_before = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[e.piece]);
+        if (e.index == 0 && (uint64_t)(e.position - t.pmin[e.piece]) == 0) piece_start[e.piece] = run;
+        if (e.gap) {
+            const uint32_t close_at = e.position - 1;
+            const uint32_t lo = e.open_at - t.draft_lo, hi = close_at - t.draft_lo;
+            uint8_t d_open = lo < t.draft_span ? t.draft[lo] : (uint8_t)0, d_close = hi < t.draft_span ? t.draft[hi] : (uint8_t)0;
+            if (d_open >= 'a' && d_open <= 'z') d_open = (uint8_t)(d_open - 32);
+            if (d_close >= 'a' && d_close <= 'z') d_close = (uint8_t)(d_close - 32);
+            if (run < n_edits) out[run] = make_edit(e.open_at, letters_before, 0, piece, PA_EDIT_GAP_OPEN, d_open, 0, 0);
+            if (run + 1 < n_edits) out[run + 1] = make_edit(close_at, letters_before, 0, piece, PA_EDIT_GAP_CLOSE, d_close, 0, 0);
+            run += 2;
+        }
+        if (e.kind) {
+            const uint8_t phred = t.qualities ? (uint8_t)(((uint32_t)t.slots[i0 + k] >> 8) & 0xFFu) : (uint8_t)0;
+            if (run < n_edits)
+                out[run] = make_edit(e.position, letters_before, e.index, piece, e.kind, e.draft, e.kind == PA_EDIT_DEL ? (uint8_t)0 : e.letter,
+                                     phred);
+            run += 1;
+        }
+    }
+}
+
 struct Buffer {
     void* p = nullptr;
     size_t cap = 0;
@@ -283,12 +445,17 @@ struct pa_stitcher {
     Buffer a_pos, a_idx, a_lab, a_phr, a_drop, a_kept, a_refused, a_dst;
     // finish's tables (f_qual: only once a contig came with qualities)
     Buffer f_desc, f_piece, f_width, f_base, f_slots, f_letters, f_place, f_out, f_qual, f_scan, f_words;
+    // edits' staging (the draft span, the pieces' take() order) and its one table: the records
+    Buffer e_draft, e_piece, e_records;
     std::vector<PieceOut> pieces;                       // of the last finish, in output order
     int64_t sequence_length = 0;
     bool finished = false;                              // a finish has run: the three below speak of it
     bool contig_qualities = false;                      // every chunk of its contig came with qualities
     bool have_qualities = false;                        // ... and it got as far as the emit: f_qual holds them
     int64_t last_slots = 0, last_pieces = 0, last_positions = 0, last_scratch_bytes = 0;
+    bool have_sequence = false;                         // the last finish ran to its end: its tables are whole
+    bool have_edits = false;                            // pa_stitcher_edits ran on them
+    int64_t n_edits = 0;
 };
 
 namespace {
@@ -306,7 +473,8 @@ int no_memory(const char* what, uint64_t bytes) {
 
 std::vector<Buffer*> buffers_of(pa_stitcher* s) {
     return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
-            &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words};
+            &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words,
+            &s->e_draft, &s->e_piece, &s->e_records};
 }
 
 }  // namespace
@@ -467,6 +635,8 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     s->sequence_length = 0;
     s->finished = true;
     s->contig_qualities = s->have_qualities = false;
+    s->have_sequence = s->have_edits = false;
+    s->n_edits = 0;
     s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
@@ -483,6 +653,7 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
         if (found != s->contigs.end() && !found->second.empty())
             return pa::set_error(PA_ERR_INVALID, "stitcher finish: the contig holds chunks and the plan has no piece");
         s->contig_qualities = s->have_qualities = true;  // no chunk came without them: the empty sequence has empty qualities
+        s->have_sequence = true;
         return PA_OK;
     }
     // loop order: regions as ranked, a region's chunks by their order value, equal ones as they arrived
@@ -630,6 +801,7 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     });
     s->sequence_length = (int64_t)n_letters;
     s->have_qualities = qualities;
+    s->have_sequence = true;
     *sequence_length = (int64_t)n_letters;
     return PA_OK;
 }
@@ -669,6 +841,137 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
         if (piece.length == 0) continue;
         ST_HIP(hipMemcpyAsync(dst + at, s->f_qual.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
         at += piece.length;
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
+}
+
+int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
+    if (!s || !n_edits || !counts || draft_length < 0 || (draft_length > 0 && !draft))
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    *n_edits = 0;
+    for (int k = 0; k < 6; ++k) counts[k] = 0;
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher edits: no contig has been finished");
+    if (!s->have_sequence)
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (s->last_pieces > 0xFFFF)
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish had " + std::to_string(s->last_pieces) +
+                                                 " pieces, a record names 65535");
+    int64_t lo = -1, hi = -1;
+    for (const PieceOut& piece : s->pieces) {
+        lo = lo < 0 ? piece.first : std::min(lo, piece.first);
+        hi = std::max(hi, piece.last);
+    }
+    if (draft_length <= hi)
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: the draft has " + std::to_string(draft_length) +
+                                                 " letters, a piece ends at position " + std::to_string(hi));
+    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);      // asked again: counted once
+    s->have_edits = false;
+    s->n_edits = 0;
+    const size_t np = (size_t)s->last_pieces;
+    const uint64_t n_slots = (uint64_t)s->last_slots;
+    if (s->pieces.empty() || n_slots == 0) {            // nothing was merged: no record
+        s->have_edits = true;
+        return PA_OK;
+    }
+    ST_HIP(hipSetDevice(s->device));
+    // per piece (table order): its place in take() order and what turns a table letter offset into a take() offset; then the
+    // device's answers: where a piece's records begin, the records per kind
+    std::vector<int64_t> shift(np, 0);
+    std::vector<uint16_t> take_index(np, 0);
+    int64_t at = 0;
+    for (size_t k = 0; k < s->pieces.size(); ++k) {
+        const PieceOut& piece = s->pieces[k];
+        shift[(size_t)piece.piece] = at - piece.offset;
+        take_index[(size_t)piece.piece] = (uint16_t)k;
+        at += piece.length;
+    }
+    const size_t off_start = np * 8, off_kinds = off_start + np * 8, off_index = off_kinds + 6 * 8, piece_bytes = off_index + np * 2;
+    const size_t span = (size_t)(hi - lo + 1);
+    if (!s->e_piece.grow(piece_bytes) || !s->e_draft.grow(span)) return no_memory("the draft", span);
+    uint8_t* ew = s->e_piece.as<uint8_t>();
+    int64_t* d_shift = (int64_t*)ew;
+    uint64_t* d_start = (uint64_t*)(ew + off_start);
+    unsigned long long* d_kinds = (unsigned long long*)(ew + off_kinds);
+    uint16_t* d_index = (uint16_t*)(ew + off_index);
+    ST_HIP(hipMemcpyAsync(d_shift, shift.data(), np * 8, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(d_index, take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(d_start, 0, np * 8 + 6 * 8, s->stream));
+    ST_HIP(hipMemcpyAsync(s->e_draft.p, draft + lo, span, hipMemcpyHostToDevice, s->stream));
+    // the piece words of the finish: [pmin u32 | pmax u32 | pbase u64 | ...] x n_pieces
+    const uint8_t* pw = s->f_piece.as<uint8_t>();
+    EditTables t;
+    t.slot_base = s->f_base.as<uint32_t>();
+    t.width = s->f_width.as<uint32_t>();
+    t.slots = s->f_slots.as<unsigned long long>();
+    t.letters = s->f_letters.as<uint8_t>();
+    t.place = s->f_place.as<uint32_t>();
+    t.pbase = (const uint64_t*)(pw + (np * 8 + 7) / 8 * 8);
+    t.pmin = (const uint32_t*)pw;
+    t.letter_shift = d_shift;
+    t.take_index = d_index;
+    t.draft = s->e_draft.as<uint8_t>();
+    t.n_positions = (uint64_t)s->last_positions;
+    t.n_slots = n_slots;
+    t.n_pieces = (uint32_t)np;
+    t.draft_lo = (uint32_t)lo;
+    t.draft_span = (uint32_t)span;
+    t.qualities = s->contig_qualities ? 1u : 0u;
+    // count per block (f_words is the letter scan's scratch: sized for n_slots elements, free since the finish), scan the sums
+    const uint64_t blocks = scan_blocks(n_slots);
+    uint64_t* sums = s->f_words.as<uint64_t>();
+    k_edit_count<<<(unsigned)(blocks + 1), ST_THREADS, 0, s->stream>>>(t, sums, d_kinds);
+    ST_HIP(hipGetLastError());
+    scan_sums(s->stream, sums, blocks + 1, sums + blocks + 1);
+    ST_HIP(hipGetLastError());
+    uint64_t total = 0, kinds[6] = {0, 0, 0, 0, 0, 0};
+    ST_HIP(hipMemcpyAsync(&total, sums + blocks, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(kinds, d_kinds, 6 * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));            // the one wait: the record buffer's size
+    if (total > 0) {
+        if (!s->e_records.grow(total * sizeof(pa_stitch_edit))) return no_memory("the edit records", total * sizeof(pa_stitch_edit));
+        // the write is left in flight: take_edits, a later finish and destroy are ordered behind it on the handle's stream
+        k_edit_write<<<(unsigned)blocks, ST_THREADS, 0, s->stream>>>(t, sums, total, s->e_records.as<pa_stitch_edit>(), d_start);
+        ST_HIP(hipGetLastError());
+    }
+    s->last_scratch_bytes += (int64_t)(total * sizeof(pa_stitch_edit));
+    s->n_edits = (int64_t)total;
+    s->have_edits = true;
+    *n_edits = (int64_t)total;
+    for (int k = 0; k < 6; ++k) counts[k] = (int64_t)kinds[k];
+    return PA_OK;
+}
+
+int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity) {
+    if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take edits: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (!s->have_edits) return pa::set_error(PA_ERR_INVALID, "stitcher take edits: pa_stitcher_edits has not run since the last finish");
+    if (capacity < s->n_edits)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take edits: there are " + std::to_string(s->n_edits) + " records, room for " +
+                                                 std::to_string(capacity));
+    if (s->n_edits == 0) return PA_OK;
+    ST_HIP(hipSetDevice(s->device));
+    // where every piece's records begin (table order; the write pass left them), then piece after piece as take() goes
+    const size_t np = (size_t)s->last_pieces;
+    std::vector<uint64_t> start(np);
+    ST_HIP(hipMemcpyAsync(start.data(), s->e_piece.as<uint8_t>() + np * 8, np * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    // in the buffer the pieces lie in table order: a piece's records end where those of the next piece with rows begin
+    std::vector<std::pair<int, uint64_t>> table;
+    for (const PieceOut& piece : s->pieces) table.push_back({piece.piece, start[(size_t)piece.piece]});
+    std::sort(table.begin(), table.end());
+    std::vector<uint64_t> end_of(np, 0);
+    for (size_t k = 0; k < table.size(); ++k) end_of[(size_t)table[k].first] = k + 1 < table.size() ? table[k + 1].second : (uint64_t)s->n_edits;
+    int64_t at = 0;
+    for (const PieceOut& piece : s->pieces) {
+        const uint64_t begin = start[(size_t)piece.piece], end = end_of[(size_t)piece.piece];
+        if (begin > end || end > (uint64_t)s->n_edits || at + (int64_t)(end - begin) > s->n_edits)
+            return pa::set_error(PA_ERR_HIP, "stitcher take edits: a piece's records lie outside the buffer");
+        if (end == begin) continue;
+        ST_HIP(hipMemcpyAsync(dst + at, s->e_records.as<pa_stitch_edit>() + begin, (size_t)(end - begin) * sizeof(pa_stitch_edit),
+                              hipMemcpyDeviceToHost, s->stream));
+        at += (int64_t)(end - begin);
     }
     ST_HIP(hipStreamSynchronize(s->stream));
     return PA_OK;

@@ -14,14 +14,17 @@ import collections
 import contextlib
 import ctypes
 import threading
+import time
 from pathlib import Path
 
 import numpy as np
 
 from pepper_amd import _lib, h5
+from pepper_amd.polish import Edits
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
-from pepper_amd.polish.perform_stitch import _log, fastq_path, get_file_paths_from_directory, natural_key, write_fastq_record
+from pepper_amd.polish.perform_stitch import (_log, draft_lengths, fastq_path, get_file_paths_from_directory, natural_key,
+                                              write_fastq_record)
 
 Plan = collections.namedtuple("Plan", "order piece rank n_pieces chunk_order")
 
@@ -82,6 +85,11 @@ class DeviceStitcher(object):
         self.device = int(device)
         self._lock = threading.Lock()
         self._contigs = {}                   # contig -> (id, {region key: id}, [region keys])
+        self._plain = set()                  # contigs that had an add without phred
+        self.last_pieces = []                # of the last finish: [(first, last, length)] by piece number
+        self.last_edit_counts = None         # of the last edits(): records per kind, [0..5]
+        # over every edits() of this handle; the seconds: the comparison with its copy back, and the text made of it
+        self.edit_totals = {"records": 0, "bytes_returned": 0, "seconds_compare": 0.0, "seconds_text": 0.0}
         handle = ctypes.c_void_p()
         _lib.check(self._lib.pa_stitcher_create(self.device, ctypes.c_void_p(stream) if stream else None, ctypes.byref(handle)))
         self._handle = handle
@@ -178,6 +186,8 @@ class DeviceStitcher(object):
                 raise
             entry[2].extend(new_keys)
             self._contigs[contig] = entry
+            if phred_ptr is None:
+                self._plain.add(contig)
 
     def finish(self, contig, threads, region_keys=None, qualities=False):
         """The consensus of one contig as create_consensus_sequence(contig, region_keys, threads) returns it; region_keys
@@ -211,39 +221,83 @@ class DeviceStitcher(object):
             _lib.check(self._lib.pa_stitcher_take_qualities(self.handle, buf, total.value))
             return sequence, buf.raw[:total.value].decode()
 
+    def has_qualities(self, contig):
+        """Every add of the contig came with phred."""
+        return contig not in self._plain
+
+    def pieces(self):
+        """The pieces of the last finish that hold rows, [(first, last, length)], in the order of the consensus."""
+        return sorted((p for p in self.last_pieces if p[0] != -1 and p[1] != -1), key=lambda e: (e[0], e[1]))
+
+    def edits(self, draft_sequence):
+        """After finish(): what the consensus changed against draft_sequence (str or bytes, the whole contig of the draft), as
+        Edits.EDIT_DTYPE records in the order and with the bytes of Edits.records_numpy -- compared on the device, only the
+        records come back.  Pieces go with them as pieces()."""
+        draft = draft_sequence.encode() if isinstance(draft_sequence, str) else bytes(draft_sequence)
+        with self._lock:
+            t0 = time.perf_counter()
+            n, counts = ctypes.c_int64(), (ctypes.c_int64 * 6)()
+            _lib.check(self._lib.pa_stitcher_edits(self.handle, draft, len(draft), ctypes.byref(n), counts))
+            records = np.zeros(n.value, Edits.EDIT_DTYPE)
+            _lib.check(self._lib.pa_stitcher_take_edits(self.handle, records.ctypes.data, n.value))
+            self.last_edit_counts = [int(v) for v in counts]
+            self.edit_totals["records"] += n.value
+            self.edit_totals["bytes_returned"] += n.value * Edits.EDIT_DTYPE.itemsize
+            self.edit_totals["seconds_compare"] += time.perf_counter() - t0
+        return records
+
+    def _write_edits(self, edits_file, draft, lengths, contig):
+        """One contig's lines of the .edits.tsv, after its finish."""
+        if contig not in lengths:
+            raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+        records = self.edits(draft.get_reference_bytes(contig, 0, lengths[contig]))
+        t0 = time.perf_counter()
+        Edits.write_contig(edits_file, contig, records, self.pieces(), lengths[contig], self.has_qualities(contig))
+        self.edit_totals["seconds_text"] += time.perf_counter() - t0
+
     def stats(self):
         """{'rows', 'slab_bytes'} held, and of the last finish {'slots', 'pieces', 'positions', 'table_bytes'}"""
         out = (ctypes.c_int64 * 6)()
         _lib.check(self._lib.pa_stitcher_stats(self.handle, out, 6))
         return dict(zip(("rows", "slab_bytes", "slots", "pieces", "positions", "table_bytes"), (int(v) for v in out)))
 
-    def write_fasta(self, output_prefix, threads):
-        """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file)."""
-        output_path = output_prefix + '_pepper_polished.fa'
-        Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as fasta:
-            for contig in sorted(self.contigs(), key=natural_key):
-                sequence = self.finish(contig, threads)
-                _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
-                if len(sequence) > 0:
-                    fasta.write('>' + contig + "\n")
-                    fasta.write(sequence + "\n")
-        return output_path
+    def write_fasta(self, output_prefix, threads, edits=None):
+        """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file).  edits: the
+        draft FASTA's path; <output_prefix>_pepper_polished.edits.tsv beside it (perform_stitch(..., edits=)'s file)."""
+        return self._write(output_prefix, threads, False, edits)
 
-    def write_fastq(self, output_prefix, threads):
+    def write_fastq(self, output_prefix, threads, edits=None):
         """write_fasta's file, and beside it <output_prefix>_pepper_polished.fastq with the same records and their qualities
         (perform_stitch(..., qualities=True)'s two files), from one finish per contig.  -> the FASTQ's path."""
+        return self._write(output_prefix, threads, True, edits)
+
+    def _write(self, output_prefix, threads, qualities, edits):
         output_path = output_prefix + '_pepper_polished.fa'
         Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
-        with open(output_path, 'w') as fasta, open(fastq_path(output_prefix), 'w') as fastq:
+        with contextlib.ExitStack() as files:
+            fasta = files.enter_context(open(output_path, 'w'))
+            fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
+            if edits is not None:
+                from pepper_amd.variant.fasta import FASTA_handler
+                lengths = draft_lengths(edits)
+                draft = FASTA_handler(edits)
+                files.callback(draft.close)
+                edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
+                edits_file.write(Edits.HEADER)
             for contig in sorted(self.contigs(), key=natural_key):
-                sequence, quality = self.finish(contig, threads, qualities=True)
+                if qualities:
+                    sequence, quality = self.finish(contig, threads, qualities=True)
+                else:
+                    sequence = self.finish(contig, threads)
+                if edits is not None:
+                    self._write_edits(edits_file, draft, lengths, contig)
                 _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
                 if len(sequence) > 0:
                     fasta.write('>' + contig + "\n")
                     fasta.write(sequence + "\n")
-                    write_fastq_record(fastq, contig, sequence, quality)
-        return fastq_path(output_prefix)
+                    if qualities:
+                        write_fastq_record(fastq, contig, sequence, quality)
+        return fastq_path(output_prefix) if qualities else output_path
 
     def close(self):
         if self._handle is not None:
@@ -308,9 +362,11 @@ class _Held(object):
         self.keys, self.order, self.blocks = [], [], []
 
 
-def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False):
-    """perform_stitch(hdf_file_path, output_path, threads, qualities) with the merge on the device: the same files read, the
-    same FASTA (and FASTQ) written.  stats: a dict that receives the handle's stats() after the last contig."""
+def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False, edits=None):
+    """perform_stitch(hdf_file_path, output_path, threads, qualities, edits) with the merge on the device: the same files read,
+    the same FASTA (and FASTQ, and .edits.tsv) written.  stats: a dict that receives the handle's stats() after the last
+    contig."""
+    read_phred = qualities or edits is not None         # the edit records carry the winners' phred
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -324,6 +380,13 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
         stitcher = files.enter_context(DeviceStitcher(device))
         fasta = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
+        if edits is not None:
+            from pepper_amd.variant.fasta import FASTA_handler
+            lengths = draft_lengths(edits)
+            draft = FASTA_handler(edits)
+            files.callback(draft.close)
+            edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
+            edits_file.write(Edits.HEADER)
         for contig in sorted(all_contigs, key=natural_key):
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -338,7 +401,7 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                         key, at = (prediction_file, name, start, end), 0
                         # (the group is read by the name small_chunk_stitch rebuilds: contig-start-end)
                         for block in _read_region(hdf5_file, 'predictions/' + contig + '/' + contig + '-' + str(start) + '-' +
-                                                  str(end), qualities):
+                                                  str(end), read_phred):
                             held.take(key, at, *block)
                             at += len(block[0])
             held.flush()
@@ -346,6 +409,8 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                 sequence, quality = stitcher.finish(contig, threads, all_chunk_keys, qualities=True)
             else:
                 sequence = stitcher.finish(contig, threads, all_chunk_keys)
+            if edits is not None:
+                stitcher._write_edits(edits_file, draft, lengths, contig)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
             if len(sequence) > 0:
                 fasta.write('>' + contig + "\n")

@@ -1,0 +1,241 @@
+"""What the stitch changed: draft-to-consensus edits (opt-in: polish(..., edits=True) / PEPPER_AMD_POLISH_EDITS=1; not in the
+reference).
+
+The stitch holds, for every key (position, insert index) of a piece, the winning label, the winner's phred and the letter's place
+in the consensus; the position is a coordinate of the draft.  A RECORD (EDIT_DTYPE, 16 bytes, `pa_stitch_edit` of
+include/pepper_amd_encoder.h) is one key that differs from the draft, or one end of a run of positions no row covered:
+
+    kind          where                          condition
+    1 SUB         slot (p, 0)                    the winner is a base and differs from upper(draft[p]) (a draft letter outside
+                                                 ACGT always differs)
+    2 DEL         slot (p, 0)                    the winner is a gap, or the slot has no writer
+    3 INS         slot (p, i > 0)                the winner is a base
+    4 GAP_OPEN    position p inside the piece    p has no slot and p - 1 has one
+    5 GAP_CLOSE   the same                       p has no slot and p + 1 has one (a run of one position: both, GAP_OPEN first)
+
+Pieces in the order the consensus concatenates them, inside a piece the keys in order.  `offset` counts letters of the contig's
+consensus: the record's own letter for SUB and INS, the letters in front of the record for the others.
+
+records_numpy() makes them from the numpy merge's sorted last-write arrays (Stitch.small_chunk_stitch_numpy); the device makes
+the same bytes from its tables (pa_stitcher_edits).  hunks() and write_edits() turn either into the text both forms write, and
+apply() replays the records over the draft: it gives back the consensus, which is the check that needs no twin.
+"""
+import numpy as np
+
+SUB, DEL, INS, GAP_OPEN, GAP_CLOSE = 1, 2, 3, 4, 5
+EDIT_DTYPE = np.dtype([("position", "<u4"), ("offset", "<u4"), ("index", "<u2"), ("piece", "<u2"), ("kind", "u1"), ("draft", "u1"),
+                       ("letter", "u1"), ("phred", "u1")])
+assert EDIT_DTYPE.itemsize == 16
+MAX_PIECES = 0xFFFF
+HEADER = "#contig\tdraft_start\tdraft_end\tpolished_start\tpolished_end\tkind\tdraft\tpolished\tmin_phred\n"
+HUNK_KINDS = ("sub", "ins", "del", "complex", "uncovered", "duplicated")
+_DECODE = np.frombuffer(b"\0ACGT", dtype=np.uint8)
+_UPPER = bytes(c - 32 if 97 <= c <= 122 else c for c in range(256))
+
+
+def edits_path(output_prefix):
+    return output_prefix + '_pepper_polished.edits.tsv'
+
+
+def upper_bytes(draft):
+    """A draft span (str or bytes) as upper-case uint8."""
+    if isinstance(draft, str):
+        draft = draft.encode()
+    return np.frombuffer(bytes(draft).translate(_UPPER), dtype=np.uint8)
+
+
+def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece=0, offset=0):
+    """The records of ONE piece.  positions / indices / labels: its keys after the merge -- sorted by (position, index), one
+    entry per key, labels 0..4 -- and phred the winners' (None: the contig has no qualities, every record gets 0).  draft: the
+    draft letters from draft_start on, covering [positions[0], positions[-1]].  piece / offset: the piece's place among the
+    contig's pieces and the letters in front of it."""
+    positions = np.asarray(positions, dtype=np.int64)
+    if positions.size == 0:
+        return np.zeros(0, EDIT_DTYPE)
+    indices = np.asarray(indices, dtype=np.int64)
+    letters = _DECODE[np.asarray(labels, dtype=np.int64)]
+    phred = np.zeros(positions.size, np.int64) if phred is None else np.asarray(phred, dtype=np.int64)
+    draft = upper_bytes(draft)
+    if int(positions[-1]) - draft_start >= draft.size or int(positions[0]) < draft_start:
+        raise ValueError("the draft span [%d, %d) does not cover the piece [%d, %d]" %
+                         (draft_start, draft_start + draft.size, positions[0], positions[-1]))
+    is_letter = letters != 0
+    before = offset + np.cumsum(is_letter) - is_letter               # letters in front of every key
+    at0, deeper = indices == 0, indices > 0
+    d = draft[positions - draft_start]
+    sub = at0 & is_letter & (letters != d)
+    dele = at0 & ~is_letter
+    ins = deeper & is_letter
+    keep = sub | dele | ins
+    kind = np.where(sub, SUB, np.where(dele, DEL, INS))
+    parts = [(positions[keep], before[keep], indices[keep], kind[keep], np.where(ins, 0, d)[keep], np.where(dele, 0, letters)[keep],
+              phred[keep])]
+    # the first key of every position: a position whose keys start above index 0 has an empty slot (p, 0)
+    first = np.ones(positions.size, dtype=bool)
+    first[1:] = positions[1:] != positions[:-1]
+    hole = first & deeper
+    zeros = np.zeros(int(hole.sum()), np.int64)
+    parts.append((positions[hole], before[hole], zeros, zeros + DEL, d[hole], zeros, zeros))
+    # runs of positions without a key, between two positions that have one
+    heads = np.flatnonzero(first)
+    run = np.flatnonzero(positions[heads][1:] - positions[heads][:-1] > 1)
+    zeros = np.zeros(run.size, np.int64)
+    open_at, close_at, lead = positions[heads][run] + 1, positions[heads][run + 1] - 1, before[heads][run + 1]
+    parts.append((open_at, lead, zeros, zeros + GAP_OPEN, draft[open_at - draft_start], zeros, zeros))
+    parts.append((close_at, lead, zeros, zeros + GAP_CLOSE, draft[close_at - draft_start], zeros, zeros))
+    columns = [np.concatenate([p[k] for p in parts]) for k in range(7)]
+    order = np.lexsort((columns[3], columns[2], columns[0]))       # position, index, then GAP_OPEN before GAP_CLOSE
+    if int(columns[2].max(initial=0)) > 0xFFFF or int(columns[0].max(initial=0)) > 0xFFFFFFFF:
+        raise ValueError("a record's position or insert index does not fit its field")
+    out = np.zeros(order.size, EDIT_DTYPE)
+    for name, column in zip(("position", "offset", "index", "kind", "draft", "letter", "phred"), columns):
+        out[name] = column[order]
+    out["piece"] = piece
+    return out
+
+
+def place(records, piece, offset):
+    """Records made with piece 0 / offset 0 (a worker does not know its piece's place) moved to where the piece lies."""
+    if piece > MAX_PIECES:
+        raise ValueError("a record names %d pieces at most" % MAX_PIECES)
+    records = records.copy()
+    records["piece"] = piece
+    records["offset"] += np.uint32(offset)
+    return records
+
+
+def _record_hunks(records, has_qualities):
+    """The hunks the records of ONE piece give, as columns: (draft_start, draft_end, polished_start, polished_end, kind, draft
+    text, polished text, min_phred), lists of equal length in record order."""
+    if records.size == 0:
+        return tuple([] for _ in range(8))
+    kind = records["kind"]
+    opens, closes = np.flatnonzero(kind == GAP_OPEN), np.flatnonzero(kind == GAP_CLOSE)
+    if opens.size != closes.size or np.any(closes != opens + 1):
+        raise ValueError("a GAP_OPEN record without its GAP_CLOSE behind it")
+    close_at = np.zeros(records.size, np.int64)
+    close_at[opens] = records["position"][closes]
+    unit = kind != GAP_CLOSE                                         # one unit per edit record and per GAP pair
+    kind, close_at = kind[unit].astype(np.int64), close_at[unit]
+    p, o = records["position"][unit].astype(np.int64), records["offset"][unit].astype(np.int64)
+    gap = kind == GAP_OPEN
+    d0 = p + (kind == INS)
+    d1 = np.where(gap, close_at + 1, p + 1)
+    o1 = o + ((kind == SUB) | (kind == INS))
+    join = np.zeros(p.size, dtype=bool)
+    join[1:] = ~gap[1:] & ~gap[:-1] & (d0[1:] == d1[:-1]) & (o[1:] == o1[:-1])
+    starts = np.flatnonzero(~join)
+    ends = np.append(starts[1:], p.size) - 1
+    h_d0, h_d1, h_o0, h_o1, h_gap = d0[starts], d1[ends], o[starts], o1[ends], gap[starts]
+    dn, on = h_d1 - h_d0, h_o1 - h_o0
+    names = np.array(HUNK_KINDS)[np.where(h_gap, 4, np.where(dn == on, 0, np.where(dn == 0, 1, np.where(on == 0, 2, 3))))]
+    # the letters: every SUB and DEL brings one draft letter, every SUB and INS one polished letter, so a hunk's texts are dn and
+    # on letters of the two streams
+    units = records[unit]
+    draft_text = units["draft"][(kind == SUB) | (kind == DEL)].tobytes().decode()
+    polished_text = units["letter"][(kind == SUB) | (kind == INS)].tobytes().decode()
+    da = np.cumsum(np.where(h_gap, 0, dn)) - np.where(h_gap, 0, dn)
+    oa = np.cumsum(np.where(h_gap, 0, on)) - np.where(h_gap, 0, on)
+    low = np.minimum.reduceat(units["phred"], starts)
+    texts_d = [draft_text[a:a + n] or "." for a, n in zip(da.tolist(), np.where(h_gap, 0, dn).tolist())]
+    texts_o = [polished_text[a:a + n] or "." for a, n in zip(oa.tolist(), np.where(h_gap, 0, on).tolist())]
+    phreds = [str(q) if has_qualities and not g else "." for q, g in zip(low.tolist(), h_gap.tolist())]
+    return (h_d0.tolist(), h_d1.tolist(), h_o0.tolist(), h_o1.tolist(), names.tolist(), texts_d, texts_o, phreds)
+
+
+def _hunk_blocks(records, pieces, draft_length, has_qualities):
+    """hunks(), one list per piece (a contig's hunks are never all in memory as tuples when they are only written)."""
+    records = np.asarray(records, dtype=EDIT_DTYPE)
+    piece_of = records["piece"].astype(np.int64)
+    if records.size and (np.any(np.diff(piece_of) < 0) or int(piece_of[-1]) >= len(pieces)):
+        raise ValueError("the records are not in the order of their pieces")
+    by_piece = np.searchsorted(piece_of, np.arange(len(pieces) + 1))
+    start = 0                                                        # letters in front of the piece
+    for k, (first, last, length) in enumerate(pieces):
+        out = []
+        if k == 0:
+            if first > 0:
+                out.append((0, first, 0, 0, "uncovered", ".", ".", "."))
+        else:
+            before = pieces[k - 1][1]
+            if first > before + 1:
+                out.append((before + 1, first, start, start, "uncovered", ".", ".", "."))
+            elif first < before + 1:
+                out.append((first, before + 1, start, start, "duplicated", ".", ".", "."))
+        out.extend(zip(*_record_hunks(records[by_piece[k]:by_piece[k + 1]], has_qualities)))
+        start += length
+        yield out
+    if pieces:
+        if pieces[-1][1] + 1 < draft_length:
+            yield [(pieces[-1][1] + 1, draft_length, start, start, "uncovered", ".", ".", ".")]
+    elif draft_length > 0:
+        yield [(0, draft_length, 0, 0, "uncovered", ".", ".", ".")]
+
+
+def hunks(records, pieces, draft_length, has_qualities):
+    """-> [(draft_start, draft_end, polished_start, polished_end, kind, draft, polished, min_phred)] in the consensus' order;
+    0-based half-open coordinates, '.' for an empty column.  pieces: [(first, last, length)] in the order of the consensus.
+
+    A record of kinds 1-3 occupies a draft and a polished interval -- SUB [p, p+1) [o, o+1); DEL [p, p+1) [o, o); INS
+    [p+1, p+1) [o, o+1) -- and joins its predecessor in the piece when both intervals start where the predecessor's end.  The
+    run's kind follows from its lengths: equal and positive `sub`, draft empty `ins`, polished empty `del`, else `complex`.
+    A GAP_OPEN / GAP_CLOSE pair is one `uncovered` hunk.  From the piece bounds come `uncovered` hunks for [0, first_0), between
+    two pieces and (last_n, draft_length), and a `duplicated` hunk for [first_k+1, last_k + 1) where consecutive pieces overlap
+    (its polished interval is empty, at the first letter of piece k + 1)."""
+    return [hunk for block in _hunk_blocks(records, pieces, draft_length, has_qualities) for hunk in block]
+
+
+def summary(hunk_list, total=None):
+    """Bases per hunk kind: draft bases for sub / del / uncovered / duplicated, polished bases for ins, both for complex
+    (total: a summary to add to)."""
+    if total is None:
+        total = dict.fromkeys(("sub", "ins", "del", "complex_draft", "complex_polished", "uncovered", "duplicated"), 0)
+    for d0, d1, o0, o1, kind, _, _, _ in hunk_list:
+        if kind == "complex":
+            total["complex_draft"] += d1 - d0
+            total["complex_polished"] += o1 - o0
+        elif kind == "ins":
+            total["ins"] += o1 - o0
+        else:
+            total[kind] += d1 - d0
+    return total
+
+
+def write_edits(file, contig, hunk_list, draft_length, polished_length, blocks=False):
+    """One line per hunk, then the contig's summary line (blocks: hunk_list is an iterable of lists of hunks)."""
+    total = None
+    for block in (hunk_list if blocks else [hunk_list]):
+        file.writelines(contig + "\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%s\n" % hunk for hunk in block)
+        total = summary(block, total)
+    file.write("##contig=" + contig + "\tdraft_length=" + str(draft_length) + "\tpolished_length=" + str(polished_length) +
+               "".join("\t%s=%d" % kv for kv in (total or summary([])).items()) + "\n")
+
+
+def write_contig(file, contig, records, pieces, draft_length, has_qualities):
+    """hunks() + write_edits(), piece by piece: what both stitch forms call per contig (pieces: [(first, last, length)])."""
+    write_edits(file, contig, _hunk_blocks(records, pieces, draft_length, has_qualities), draft_length, sum(p[2] for p in pieces),
+                blocks=True)
+
+
+def apply(draft_sequence, records, pieces):
+    """The consensus again: the records replayed over the draft, piece by piece.  A position of a piece gives its draft letter
+    (upper-cased) unless a DEL or a GAP run takes it or a SUB replaces it; INS letters follow their position by index."""
+    records = np.asarray(records, dtype=EDIT_DTYPE)
+    draft = upper_bytes(draft_sequence)
+    out = []
+    for k, (first, last, _length) in enumerate(pieces):
+        mine = records[records["piece"] == k]
+        position = mine["position"].astype(np.int64)
+        letters = draft[first:last + 1].copy()
+        keep = np.ones(letters.size, dtype=bool)
+        kind = mine["kind"]
+        keep[position[kind == DEL] - first] = False
+        for a, b in zip(position[kind == GAP_OPEN], position[kind == GAP_CLOSE]):
+            keep[a - first:b - first + 1] = False
+        letters[position[kind == SUB] - first] = mine["letter"][kind == SUB]
+        ins = kind == INS
+        key = np.concatenate([(np.arange(first, last + 1, dtype=np.int64) << 16)[keep],
+                              (position[ins] << 16) | mine["index"][ins].astype(np.int64)])
+        text = np.concatenate([letters[keep], mine["letter"][ins]])
+        out.append(text[np.argsort(key, kind="stable")].tobytes().decode())
+    return "".join(out)

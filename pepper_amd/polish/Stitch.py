@@ -9,6 +9,8 @@ are concatenated in the reference's iteration order (chunk ids sorted as strings
 overlap and dropped), then the last write of every key wins and keys come out sorted.
 qualities=True (opt-in, not in the reference): the phred_score of the row that supplied a letter's label travels with it and
 comes out as Sanger text, chr(33 + min(phred, 93)); a winning gap gives neither a letter nor a quality.
+edits=<draft FASTA> (opt-in, not in the reference): every piece also gives the records of what it changed against the draft
+(pepper_amd/polish/Edits.py); a worker reads the span of the draft its piece covers from the file itself.
 Pinned: tests/golden/polish_stitch_ref.fa is the reference's own output on the same prediction arrays.
 """
 import concurrent.futures
@@ -29,13 +31,14 @@ def chunks(file_names, threads):
     return [file_names[i:i + threads] for i in range(0, len(file_names), threads)]
 
 
-def small_chunk_stitch(contig, small_chunk_keys, qualities=False):
+def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None):
     """One piece of the consensus.  The merge runs inside the I/O library (pa_h5_stitch_polish_regions: chunk rows straight
     from the mapped prediction files, each chunk merged into the tail of the piece; 3 k -> see DESIGN.md chunks/s);
     PEPPER_AMD_STITCH_NUMPY=1 keeps the numpy form below, which tests hold it to.  qualities: (first, last, sequence, quality),
-    always through the numpy form (the library's merge carries no phred)."""
-    if qualities:
-        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=True)
+    always through the numpy form (the library's merge carries no phred).  edits: the draft FASTA's path; the piece's edit
+    records (piece 0, offsets from the piece's first letter) follow as one more element, through the numpy form as well."""
+    if qualities or edits is not None:
+        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=qualities, edits=edits)
     if os.environ.get("PEPPER_AMD_STITCH_NUMPY") == "1":
         return small_chunk_stitch_numpy(contig, small_chunk_keys)
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
@@ -55,9 +58,14 @@ def small_chunk_stitch(contig, small_chunk_keys, qualities=False):
             f.close()
 
 
-def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False):
+def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=None):
+    want_qualities = qualities
+    qualities = qualities or edits is not None          # the edit records carry the winners' phred
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
-    nothing = (-1, -1, '', '') if qualities else (-1, -1, '')
+    nothing = (-1, -1, '', '') if want_qualities else (-1, -1, '')
+    if edits is not None:
+        from pepper_amd.polish import Edits
+        nothing += (np.zeros(0, Edits.EDIT_DTYPE),)
     names = ('position', 'index', 'bases', 'phred_score') if qualities else ('position', 'index', 'bases')
     pos_parts, idx_parts, base_parts, phred_parts = [], [], [], []
     open_files = {}                       # each prediction file is opened once per call, not once per region
@@ -114,16 +122,29 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False):
         raise KeyError(int(labels[(labels < 0) | (labels > 4)][0]))      # label_decoder[...] in the reference
     letters = _DECODE[labels]
     sequence = letters[letters != 0].tobytes().decode()
+    result = (int(positions[0]), int(positions[-1]), sequence)
     if qualities:                         # the phred the winning write carried, for the winners that are bases
         phred = np.concatenate(phred_parts)[order][last]
-        quality = (33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8).tobytes().decode()
-        return int(positions[0]), int(positions[-1]), sequence, quality
-    return int(positions[0]), int(positions[-1]), sequence
+        if want_qualities:
+            result += ((33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8).tobytes().decode(),)
+    if edits is not None:                 # only the span the piece covers is read from the draft
+        from pepper_amd.variant.fasta import FASTA_handler
+        draft = FASTA_handler(edits)
+        try:
+            if draft.get_chromosome_sequence_length(contig) <= result[1]:
+                raise ValueError("the draft FASTA %s has no letter at position %d of %s" % (edits, result[1], contig))
+            span = draft.get_reference_bytes(contig, result[0], result[1] + 1)
+        finally:
+            draft.close()
+        result += (Edits.records_numpy(positions[last], indices[last], labels, np.minimum(phred, 255), span, result[0]),)
+    return result
 
 
-def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False):
-    """The consensus of one contig; qualities: (sequence, quality), the pieces' qualities concatenated as their letters are."""
-    extra = (True,) if qualities else ()
+def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False, edits=None):
+    """The consensus of one contig; qualities: (sequence, quality), the pieces' qualities concatenated as their letters are.
+    edits (the draft FASTA's path): (sequence, quality or None, records, pieces) -- the contig's edit records and its pieces
+    [(first, last, length)], both in the order of the consensus (pepper_amd/polish/Edits.py)."""
+    extra = (bool(qualities), edits) if edits is not None else (True,) if qualities else ()
     key_list = sorted(((file_name, contig, int(contig_start), int(contig_end))
                        for file_name, _, contig_start, contig_end in sorted(sequence_chunk_keys, key=lambda e: e[1])),
                       key=lambda e: (e[2], e[3]))
@@ -134,6 +155,14 @@ def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=Fa
         with concurrent.futures.ProcessPoolExecutor(max_workers=threads) as executor:
             results = [f.result() for f in [executor.submit(small_chunk_stitch, contig, chunk, *extra) for chunk in file_chunks]]
     pieces = sorted((r for r in results if r[0] != -1 and r[1] != -1), key=lambda e: (e[0], e[1]))
+    if edits is not None:
+        from pepper_amd.polish import Edits
+        records, at = [np.zeros(0, Edits.EDIT_DTYPE)], 0
+        for k, piece in enumerate(pieces):
+            records.append(Edits.place(piece[-1], k, at))
+            at += len(piece[2])
+        return (''.join(piece[2] for piece in pieces), ''.join(piece[3] for piece in pieces) if qualities else None,
+                np.concatenate(records), [(piece[0], piece[1], len(piece[2])) for piece in pieces])
     if qualities:
         return ''.join(piece[2] for piece in pieces), ''.join(piece[3] for piece in pieces)
     return ''.join(sequence for _, _, sequence in pieces)

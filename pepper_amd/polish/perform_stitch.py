@@ -5,6 +5,8 @@ replaces: /root/reference/pepper/modules/python/perform_stitch.py:44-84 (`perfor
 written to `<output_path>_pepper_polished.fa`.  (The reference's 5 s sleep is not reproduced.)
 qualities=True (opt-in, not in the reference) also writes `<output_path>_pepper_polished.fastq`: the same records with the
 phred of the prediction row that supplied each base, as Sanger text.
+edits=<draft FASTA> (opt-in, not in the reference) also writes `<output_path>_pepper_polished.edits.tsv`: what the consensus
+changed against the draft, hunk by hunk in both coordinate systems (pepper_amd/polish/Edits.py).
 """
 import contextlib
 import re
@@ -43,7 +45,17 @@ def write_fastq_record(fastq, contig, sequence, quality):
     fastq.write(quality + "\n")
 
 
-def perform_stitch(hdf_file_path, output_path, threads, qualities=False):
+def draft_lengths(draft_fasta):
+    """{contig: length} of the draft FASTA the edits are taken against."""
+    from pepper_amd.variant.fasta import FASTA_handler
+    handler = FASTA_handler(draft_fasta)
+    try:
+        return {name: handler.get_chromosome_sequence_length(name) for name in handler.get_chromosome_names()}
+    finally:
+        handler.close()
+
+
+def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None):
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -57,6 +69,11 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False):
     with contextlib.ExitStack() as files:
         consensus_fasta_file = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
+        if edits is not None:
+            from pepper_amd.polish import Edits
+            lengths = draft_lengths(edits)
+            edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
+            edits_file.write(Edits.HEADER)
         for contig in sorted(all_contigs, key=natural_key):
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -66,7 +83,13 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False):
                         continue
                     # every region group with its contig_start / contig_end in one library call (names in sorted order)
                     all_chunk_keys.extend((prediction_file, name, start, end) for name, start, end in hdf5_file.list_polish_regions(contig))
-            if qualities:
+            if edits is not None:
+                if contig not in lengths:
+                    raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+                consensus_sequence, quality, records, pieces = create_consensus_sequence(contig, all_chunk_keys, threads,
+                                                                                         qualities=qualities, edits=edits)
+                Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True)
+            elif qualities:
                 consensus_sequence, quality = create_consensus_sequence(contig, all_chunk_keys, threads, qualities=True)
             else:
                 consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads)

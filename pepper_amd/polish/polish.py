@@ -19,7 +19,7 @@ def _log(message):
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
            num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0, device_stitch=None,
-           keep_predictions=None, qualities=None):
+           keep_predictions=None, qualities=None, edits=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
@@ -29,12 +29,19 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     (pepper_amd/polish/DeviceStitch.py) and writes the FASTA perform_stitch would; in the fused form the labels go from the model
     to the stitcher without leaving the device, and the prediction files are written only with keep_predictions (default: not).
     qualities (default: PEPPER_AMD_POLISH_QUALITIES=1): step 3 also writes <output>_pepper_polished.fastq, every base with the
-    phred of the prediction row that supplied it as Sanger text, chr(33 + min(phred, 93)); the FASTA is the same either way."""
+    phred of the prediction row that supplied it as Sanger text, chr(33 + min(phred, 93)); the FASTA is the same either way.
+    edits (default: PEPPER_AMD_POLISH_EDITS=1): step 3 also writes <output>_pepper_polished.edits.tsv, what the consensus changed
+    against fasta_filepath hunk by hunk in both coordinate systems (pepper_amd/polish/Edits.py; not in the reference); in the
+    fused device-stitch form the comparison runs on the device and the phred goes to the stitcher as with qualities
+    (stage_walls["device_stitch_edits"]: the records, the bytes that came back, the seconds of the comparison and of the text)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     if qualities is None:
         qualities = _lib.polish_qualities()
     qualities = bool(qualities)
+    if edits is None:
+        edits = _lib.polish_edits()
+    draft_fasta = fasta_filepath if edits else None
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
         if not os.path.isfile(path):
             raise FileNotFoundError("CAN NOT LOCATE " + what + " FILE: " + str(path))
@@ -65,7 +72,7 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         _log("STEP 1+2: GENERATING IMAGES AND RUNNING INFERENCE (FUSED) -> " + prediction_output_directory)
         sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant, device_stitch=device_stitch,
                               keep_predictions=bool(keep_predictions) or not device_stitch,
-                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities)
+                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities or bool(edits))
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
                         stats=image_stats, downsample_rate=downsample_rate)
@@ -83,22 +90,29 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         t2 = time.perf_counter()
     _log("STEP 3: RUNNING STITCH -> " + output_dir)
     if not device_stitch:
-        perform_stitch(prediction_output_directory, output_dir, threads, qualities=qualities)
+        perform_stitch(prediction_output_directory, output_dir, threads, qualities=qualities, edits=draft_fasta)
     elif not fused_inference:
         from pepper_amd.polish.DeviceStitch import stitch_directory
-        stitch_directory(prediction_output_directory, output_dir, threads, device=parse_device_ids(device_ids)[0], qualities=qualities)
+        stitch_directory(prediction_output_directory, output_dir, threads, device=parse_device_ids(device_ids)[0], qualities=qualities,
+                         edits=draft_fasta)
     elif stitcher is None:                   # (no chunk was predicted: perform_stitch over no files writes an empty FASTA)
         open(output_dir + '_pepper_polished.fa', 'w').close()
         if qualities:
             open(output_dir + '_pepper_polished.fastq', 'w').close()
+        if edits:
+            from pepper_amd.polish import Edits
+            with open(Edits.edits_path(output_dir), 'w') as edits_file:
+                edits_file.write(Edits.HEADER)
     else:
         try:
             if qualities:
-                stitcher.write_fastq(output_dir, threads)
+                stitcher.write_fastq(output_dir, threads, edits=draft_fasta)
             else:
-                stitcher.write_fasta(output_dir, threads)
+                stitcher.write_fasta(output_dir, threads, edits=draft_fasta)
             if stage_walls is not None:
                 stage_walls["device_stitch_stats"] = stitcher.stats()
+                if edits:
+                    stage_walls["device_stitch_edits"] = dict(stitcher.edit_totals)
         finally:
             stitcher.close()
     if stage_walls is not None:

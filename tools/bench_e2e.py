@@ -13,6 +13,8 @@
       either form with device_stitch=True (pepper_amd/polish/DeviceStitch.py; without the suffix PEPPER_AMD_DEVICE_STITCH decides)
   python tools/bench_e2e.py polish..._qualities <dir> ...    any of the four with qualities=True: the FASTQ beside the FASTA
       (without the suffix PEPPER_AMD_POLISH_QUALITIES decides)
+  python tools/bench_e2e.py polish..._edits <dir> ...        any of the four with edits=True: the .edits.tsv beside the FASTA
+      (what the consensus changed against the draft; without the suffix PEPPER_AMD_POLISH_EDITS decides)
 
 Each prints one JSON line: the run with the median wall of `runs` (after one untimed run that loads the libraries, grows the
 workspaces and leaves the input files in the page cache), every run's wall, the stage walls and the units per second."""
@@ -138,7 +140,7 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selectio
                 info["genome_bases"] / 1e6, info["coverage"], info["records"], info["bam_bytes"] / 1e9), "synth_seconds": info["seconds"]}
 
 
-def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, qualities=None):
+def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, qualities=None, edits=None):
     from pepper_amd.hostinfo import usable_cpus
     from pepper_amd.polish.polish import polish
     info = synth(work, bases, coverage)
@@ -152,9 +154,11 @@ def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, q
         walls = {}
         t0 = time.perf_counter()
         polish(os.path.join(work, "reads.bam"), os.path.join(work, "draft.fa"), out, threads, None, model, 512, True, "0", 0, stage_walls=walls,
-               fused_inference=fused, device_stitch=device_stitch, qualities=qualities)
+               fused_inference=fused, device_stitch=device_stitch, qualities=qualities, **({"edits": True} if edits else {}))
         dt = time.perf_counter() - t0
         stitch_stats = walls.pop("device_stitch_stats", None)
+        edit_totals = walls.pop("device_stitch_edits", None)
+        tsv = glob.glob(out + "*.edits.tsv")
         fasta = glob.glob(out + "*.fa")
         size = os.path.getsize(fasta[0]) if fasta else 0
         fastq = glob.glob(out + "*.fastq")
@@ -163,6 +167,7 @@ def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, q
             stages = walls.pop("image_stage_seconds_summed_over_workers", None) or {}
             runs.append({"seconds": round(dt, 3), "stage_walls": {n: round(v, 3) for n, v in walls.items()}, "polished_fasta_bytes": size,
                          "polished_fastq_bytes": os.path.getsize(fastq[0]) if fastq else None,
+                         "edits_tsv_bytes": os.path.getsize(tsv[0]) if tsv else None, "device_stitch_edits": edit_totals,
                          "image_stage_seconds_summed_over_workers": {n: round(v, 2) for n, v in sorted(stages.items()) if isinstance(v, float)},
                          "image_file_mb": round(images / 1e6, 1),
                          "prediction_file_mb": round(sum(os.path.getsize(p) for p in glob.glob(out + "predictions_*/*.hdf")) / 1e6, 1),
@@ -171,10 +176,11 @@ def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, q
     mid = median_run(runs)
     longest = max(mid["stage_walls"].values())
     return {"metric": "polish end to end (BAM + draft + checkpoint -> polished FASTA)" + (", images and inference fused" if fused else "") +
-                      (", device stitch" if device_stitch else "") + (", qualities" if qualities else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
+                      (", device stitch" if device_stitch else "") + (", qualities" if qualities else "") + (", edits" if edits else ""), "value": round(info["genome_bases"] / 1e6 / mid["seconds"], 2),
             "unit": "Mb of draft/s", "seconds": mid["seconds"], "runs_seconds": [r["seconds"] for r in runs], "stage_walls": mid["stage_walls"],
             "wall_over_longest_stage": round(mid["seconds"] / longest, 3), "polished_fasta_bytes": mid["polished_fasta_bytes"],
             "polished_fastq_bytes": mid["polished_fastq_bytes"],
+            "edits_tsv_bytes": mid["edits_tsv_bytes"], "device_stitch_edits": mid["device_stitch_edits"],
             "image_stage_seconds_summed_over_workers": mid["image_stage_seconds_summed_over_workers"],
             "runs_stage_walls": [r["stage_walls"] for r in runs],
             "image_file_mb": mid["image_file_mb"], "prediction_file_mb": mid["prediction_file_mb"],
@@ -196,9 +202,11 @@ if __name__ == "__main__":
         print(json.dumps(call_variant_job(work, bases, coverage, n_runs, fused=True, device_selection="--device-selection" in flags,
                                           keep_files="--keep-files" in flags)))
     elif kind.startswith("polish"):
-        qualities = True if kind.endswith("_qualities") else None
-        form = kind[:-len("_qualities")] if qualities else kind
+        edits = True if kind.endswith("_edits") else None
+        form = kind[:-len("_edits")] if edits else kind
+        qualities = True if form.endswith("_qualities") else None
+        form = form[:-len("_qualities")] if qualities else form
         print(json.dumps(polish_job(work, bases, coverage, n_runs, fused="fused" in form,
-                                    device_stitch=True if form.endswith("device_stitch") else None, qualities=qualities)))
+                                    device_stitch=True if form.endswith("device_stitch") else None, qualities=qualities, edits=edits)))
     else:
         print(json.dumps((call_variant_job if kind == "call_variant" else polish_job)(work, bases, coverage, n_runs)))

@@ -3,7 +3,10 @@ the numpy form (PEPPER_AMD_STITCH_NUMPY=1), one and eight workers; --device adds
 (pepper_amd/polish/DeviceStitch.py stitch_directory: the files read on the host, the merge on the GPU) and checks its FASTA
 against the host's.  --qualities runs the set with qualities on as well -- perform_stitch(..., qualities=True) on the host (the
 numpy merge with a phred column) and, with --device, stitch_directory(..., qualities=True) -- and checks the two FASTQ files equal.
-    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities]"""
+--edits runs the set with the edits on as well, against a seeded random draft (the labels are random too, so four slots in five
+are an edit: the record buffer's worst case, not a polished assembly's share) -- perform_stitch(..., edits=draft) on the host and,
+with --device, stitch_directory(..., edits=draft) -- and checks the two .edits.tsv files equal.
+    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits]"""
 import argparse
 import json
 import os
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--dir", default=None)
     ap.add_argument("--device", action="store_true", help="also run the set through the device stitch")
     ap.add_argument("--qualities", action="store_true", help="also run the set with qualities on (FASTQ beside the FASTA)")
+    ap.add_argument("--edits", action="store_true", help="also run the set with the edits on (.edits.tsv beside the FASTA)")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
@@ -69,6 +73,20 @@ def main():
                 runs.append({"merge": "numpy", "qualities": True, "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                              "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
+        if args.edits:
+            os.environ["PEPPER_AMD_STITCH_NUMPY"] = "0"
+            draft_fa = os.path.join(tmp, "draft.fa")
+            with open(draft_fa, "w") as fh:                 # as long as the positions reach
+                fh.write(">ctg0\n" + np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(5).integers(0, 4, regions * 1000 + 2400)]
+                         .tobytes().decode() + "\n")
+            for threads in (1, 8):
+                t0 = time.perf_counter()
+                out = perform_stitch(pred, os.path.join(tmp, "oute%d" % threads), threads, edits=draft_fa)
+                dt = time.perf_counter() - t0
+                runs.append({"merge": "numpy", "edits": True, "threads": threads, "seconds": round(dt, 2),
+                             "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                             "edits_tsv_bytes": os.path.getsize(out[:-len(".fa")] + ".edits.tsv"),
+                             "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
         if args.device:
             from pepper_amd.polish.DeviceStitch import stitch_directory
             host = {threads: open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read() for threads in (1, 8)}
@@ -93,6 +111,18 @@ def main():
                                  "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                                  "equals_host": open(out, "rb").read() == host[threads], "fastq_equals_host": fastq == host_fastq,
                                  "fastq_bytes": len(fastq), "stats": stats})
+            for threads in (1, 8) if args.edits else ():
+                host_tsv = open(os.path.join(tmp, "oute%d" % threads) + "_pepper_polished.edits.tsv", "rb").read()
+                for repeat in range(2):
+                    stats = {}
+                    t0 = time.perf_counter()
+                    out = stitch_directory(pred, os.path.join(tmp, "deve%d%d" % (threads, repeat)), threads, stats=stats, edits=draft_fa)
+                    dt = time.perf_counter() - t0
+                    tsv = open(out[:-len(".fa")] + ".edits.tsv", "rb").read()
+                    runs.append({"merge": "device", "edits": True, "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
+                                 "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                                 "equals_host": open(out, "rb").read() == host[threads], "edits_tsv_equals_host": tsv == host_tsv,
+                                 "edits_tsv_bytes": len(tsv), "stats": stats})
         from pepper_amd.hostinfo import usable_cpus
         print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
