@@ -19,6 +19,11 @@ int pa_debug_dump_gru_timing(unsigned long long* host_out);
 void pa_debug_gemm_h2_experiment(int e);
 int pa_debug_gemm_h2(const float* A, const float* W, const float* bias, float* C, int a_rows, int M, int N, int K, int act,
                      int frag_T, int frag_nb, int iters, float* ms_out);
+/* The split-K path of the same GEMM twice on the same operands (tests/test_gpu_gemm_h2_k32.py): `splits` k slices by
+ * gemm_h2_k32_kernel into C_new and by gemm_h2_kernel<0> into C_parent, each through splitk_finish_kernel and timed as above.
+ * Needs splits >= 2, N % 4 == 0 and K / 32 >= splits. */
+int pa_debug_gemm_h2_split(const float* A, const float* W, const float* bias, float* C_new, float* C_parent, int a_rows, int M,
+                           int N, int K, int act, int splits, int iters, float* ms_new, float* ms_parent);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 // Debug aid (not product): does the chip hold a higher clock on v_mfma_f32_16x16x32_f16 than on v_mfma_f32_32x32x16_f16
 // in the fused LSTM decoder's step loop (rnn_h2.hip: lstm_rec_h2_kernel<256, 512, XG>)?
 //   hipcc --offload-arch=gfx950 -O3 -o tools/microbench/mfma_shape tools/microbench/mfma_shape.hip && tools/microbench/mfma_shape
-//   (arguments: repetitions per launch [200], passes over the table [2], rows all | dec | enc; the encoder's rows are below)
+//   (arguments: repetitions per launch [200], passes over the table [2], rows all | dec | enc | gemm; the encoder's rows and
+//   linear_1's GEMM rows are below -- the gemm rows run one pass over the k range per 50 repetitions)
 // One workgroup per CU, 8 waves (two per SIMD), each with the decoder's wave tile: 64 rows x 128 columns (32 units of four
 // gates), 128 accumulator registers.  A k loop of three-term split-f16 products (lo.hi, hi.lo, hi.hi) in two bodies with the
 // same MFMA work:
@@ -371,6 +372,298 @@ __global__ __launch_bounds__(512, 1) void ke(int nrep, const uint32_t* __restric
     }
 }
 
+// ---- linear_1's split-K GEMM (gemm_h2.hip: gemm_h2_kernel<0>, M = 16 384, N = 512, K = 16 896, two k slices): the real
+// grid (64 x 2 tiles of 256 x 256, two slices = 256 workgroups), the real operands (row-major h2, 1.1 GB of A), the real
+// staging: per k-tile of 32 and workgroup 16 buffer_load_b128 per 256 threads into staging registers, 16 ds_write_b128 into
+// two stages of 512 rows x 144 B, one barrier, every fragment by ds_read_b128.  Three bodies:
+//   a: the kernel as it is -- 4 waves, 128 x 128 wave tile, 96 x 32x32x16 per k-tile, two fragment sets, the k-tile body
+//      scheduled by sched_group_barrier;
+//   b: 4 waves, 128 x 128 wave tile as 8 x 8 tiles of 16 x 16 (256 accumulator registers), 192 x 16x16x32 per k-tile, one
+//      fragment set re-read right after its last use (row tile m after row m, the column tiles through the last row), the
+//      barrier after the first row, a loop over one-k-tile bodies;
+//   c: 8 waves (two per SIMD), 128 x 64 wave tile (128 accumulator registers), 96 x 16x16x32 per wave and k-tile, the same
+//      staging over 512 threads (8 loads each), A fragments as a ring of two row tiles (the whole set does not fit 256
+//      registers beside the staging), B fragments re-read through the last row; 1.5 x the fragment reads of a and b.
+// The accumulators are summed, not stored: the epilogue is not part of the question.
+constexpr int GT = 256, GK = 32, GROW = 36, GSTAGE = 2 * GT * GROW;     // tile, k-tile, LDS row (dwords), stage (dwords)
+constexpr int G_M = 16384, G_N = 512, G_K = 16896, G_SPLITS = 2;
+constexpr int G_TILES_N = G_N / GT, G_NWG = (G_M / GT) * G_TILES_N, G_NK = G_K / GK / G_SPLITS;
+
+__device__ __forceinline__ void lds_barrier() {      // s_waitcnt lgkmcnt(0) + s_barrier: global loads stay in flight
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    __builtin_amdgcn_s_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
+}
+
+template <int BODY>
+__global__ __launch_bounds__(BODY == 2 ? 512 : 256) void kg(int nrep, const uint32_t* __restrict__ A, const uint32_t* __restrict__ W,
+                                                            float* __restrict__ out, unsigned long long* __restrict__ stamps) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[2 * GSTAGE];
+    constexpr int NT = BODY == 2 ? 512 : 256, NP = BODY == 2 ? 4 : 8;     // threads, staged rows of A (and of W) per thread
+    // gemm_h2_kernel's tile order: XCD-contiguous runs, groups of 4 row panels, row panel fastest
+    int tile;
+    {
+        const int bid = blockIdx.x, q = G_NWG >> 3;
+        tile = (bid & 7) * q + (bid >> 3);
+    }
+    const int group = tile / (4 * G_TILES_N), within = tile - group * (4 * G_TILES_N);
+    const int m0 = (group * 4 + within % 4) * GT, n0 = (within / 4) * GT;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kq = tid & 7, r0 = tid >> 3;
+    const __amdgpu_buffer_rsrc_t arsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(A), 0, (int)((unsigned)G_M * G_K * 4u), 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrsrc =
+        __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(W), 0, (int)((unsigned)G_N * G_K * 4u), 0x00020000);
+    uint32_t aoff[NP], woff[NP];
+#pragma unroll
+    for (int i = 0; i < NP; ++i) {
+        aoff[i] = (uint32_t)(m0 + r0 + (NT / 8) * i) * (G_K * 4u) + kq * 16;
+        woff[i] = (uint32_t)(n0 + r0 + (NT / 8) * i) * (G_K * 4u) + kq * 16;
+    }
+    u32x4 ra[NP], rb[NP];
+    auto gload1 = [&](int kt, int i) {     // piece i < NP: A, else W
+        if (i < NP) ra[i] = __builtin_amdgcn_raw_buffer_load_b128(arsrc, aoff[i], kt * (GK * 4), 0);
+        else rb[i - NP] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, woff[i - NP], kt * (GK * 4), 0);
+    };
+    auto lstore1 = [&](int buf, int i) {
+        uint32_t* base = lds + buf * GSTAGE + r0 * GROW + kq * 4;
+        if (i < NP) *reinterpret_cast<u32x4*>(base + ((NT / 8) * i) * GROW) = ra[i];
+        else *reinterpret_cast<u32x4*>(base + (GT + (NT / 8) * (i - NP)) * GROW) = rb[i - NP];
+    };
+    const int kbeg = G_NK * (int)blockIdx.y, nk = G_NK;
+    unsigned long long t0, t1, c0, c1;
+    float sum = 0.0f;
+    GAP();
+    t0 = __builtin_amdgcn_s_memtime();
+    c0 = __builtin_amdgcn_s_memrealtime();
+    GAP();
+
+    if constexpr (BODY == 0) {
+        const int wm = wid >> 1, wn = wid & 1, li = lane & 31, hf = lane >> 5;
+        f32x16 acc[4][4] = {};
+        struct Frag { h8 a[4][2], b[4][2]; };
+        auto read_step = [&](int buf, int step, Frag& f) {
+            const uint32_t* Ab = lds + buf * GSTAGE + (wm * 128 + li) * GROW + (2 * step + hf) * 8;
+            const uint32_t* Bb = lds + buf * GSTAGE + (GT + wn * 128 + li) * GROW + (2 * step + hf) * 8;
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                f.a[m][0] = *reinterpret_cast<const h8*>(Ab + m * 32 * GROW);
+                f.a[m][1] = *reinterpret_cast<const h8*>(Ab + m * 32 * GROW + 4);
+            }
+#pragma unroll
+            for (int n = 0; n < 4; ++n) {
+                f.b[n][0] = *reinterpret_cast<const h8*>(Bb + n * 32 * GROW);
+                f.b[n][1] = *reinterpret_cast<const h8*>(Bb + n * 32 * GROW + 4);
+            }
+        };
+        auto mma_step = [&](const Frag& f) {
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+#pragma unroll
+                    for (int n = 0; n < 4; ++n)
+                        acc[m][n] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.a[m][t == 0 ? 1 : 0], f.b[n][t == 1 ? 1 : 0],
+                                                                           acc[m][n], 0, 0, 0);
+        };
+        Frag f0, f1;
+        for (int rep = 0; rep < nrep; ++rep) {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gload1(kbeg, i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) lstore1(0, i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gload1(kbeg + (nk > 1 ? 1 : 0), i);
+            __syncthreads();
+            read_step(0, 0, f0);
+            for (int kt = 0; kt < nk; ++kt) {
+                const int buf = kt & 1;
+                const int nxt2 = kbeg + (kt + 2 < nk ? kt + 2 : nk - 1);
+                read_step(buf, 1, f1);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) { lstore1(buf ^ 1, i); lstore1(buf ^ 1, 8 + i); }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) gload1(nxt2, i);
+                mma_step(f0);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                __syncthreads();
+                read_step(buf ^ 1, 0, f0);
+#pragma unroll
+                for (int i = 8; i < 16; ++i) gload1(nxt2, i);
+                mma_step(f1);
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                }
+#pragma unroll
+                for (int i = 0; i < 8; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+                }
+                __builtin_amdgcn_sched_group_barrier(0x008, 24, 0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            __syncthreads();     // the next repetition's prologue writes stage 0
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        c1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sum += acc[m][n][r];
+    } else if constexpr (BODY == 1) {
+        const int wm = wid >> 1, wn = wid & 1, l15 = lane & 15, qd = lane >> 4;
+        // lane l: row l & 15 of a 16-row tile, k 8 (l >> 4) .. + 7 of the k-tile: 16 B hi at byte 32 (l >> 4), lo 16 B on
+        const uint32_t* afr = lds + (wm * 128 + l15) * GROW + qd * 8;
+        const uint32_t* bfr = lds + (GT + wn * 128 + l15) * GROW + qd * 8;
+        h8 a[8][2], b[8][2];       // [tile][hi, lo], one set
+        f32x4 acc[8][8] = {};
+        auto rd_a = [&](int buf, int m, int hl) { a[m][hl] = *reinterpret_cast<const h8*>(afr + buf * GSTAGE + m * 16 * GROW + hl * 4); };
+        auto rd_b = [&](int buf, int n, int hl) { b[n][hl] = *reinterpret_cast<const h8*>(bfr + buf * GSTAGE + n * 16 * GROW + hl * 4); };
+        for (int rep = 0; rep < nrep; ++rep) {
+            // stage 0 <- tile 0, stage 1 <- tile 1, staging registers <- tile 2 (indices clamped to the slice)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gload1(kbeg, i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) lstore1(0, i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gload1(kbeg + (nk > 1 ? 1 : 0), i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) lstore1(1, i);
+#pragma unroll
+            for (int i = 0; i < 16; ++i) gload1(kbeg + (nk > 2 ? 2 : nk - 1), i);
+            __syncthreads();
+#pragma unroll
+            for (int n = 0; n < 8; ++n) { rd_b(0, n, 0); rd_b(0, n, 1); }
+#pragma unroll
+            for (int m = 0; m < 7; ++m) { rd_a(0, m, 0); rd_a(0, m, 1); }
+            GAP();
+            // Tile t: the registers hold its fragments but row tile 7's, which row 0 reads from stage t & 1.  The barrier
+            // after row 0 says: every wave has read all it wants of stage t & 1 (tile t+2 may be written there) and tile
+            // t+1 is whole in the other stage (written during tile t-1).  Rows 1 .. 6: tile t+2 from the staging registers
+            // to LDS, each piece's request for tile t+3 behind it.  Row m: row tile m-1 of tile t+1.  Row 7: the column
+            // tiles of tile t+1, each pair after its last MFMA.
+#pragma unroll 1
+            for (int t = 0; t < nk; ++t) {
+                const int cur = t & 1, nxt = cur ^ 1;
+                const int kt3 = kbeg + (t + 3 < nk ? t + 3 : nk - 1);
+#pragma unroll
+                for (int m = 0; m < 8; ++m)
+#pragma unroll
+                for (int r = 0; r < 24; ++r) {
+                    const int n = 2 * (r / 6) + (r & 1), term = (r % 6) >> 1;
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m][term == 0 ? 1 : 0], b[n][term == 1 ? 1 : 0],
+                                                                       acc[m][n], 0, 0, 0);
+                    if (m == 0) {
+                        if (r == 0) rd_a(cur, 7, 1);
+                        if (r == 1) rd_a(cur, 7, 0);
+                        if (r == 23) { GAP(); lds_barrier(); }
+                    } else {
+                        if (r == 2) rd_a(nxt, m - 1, 1);
+                        if (r == 8) rd_a(nxt, m - 1, 0);
+                        const int g = (m - 1) * 24 + r;      // rows 1 .. 6: a piece every 9 gaps (the slow LDS write port)
+                        if (m <= 6 && g % 9 == 0) lstore1(cur, g / 9);
+                        if (m <= 6 && g % 9 == 1) gload1(kt3, g / 9);
+                        if (m == 7 && r % 6 == 3) rd_b(nxt, n - 1, 1);
+                        if (m == 7 && r % 6 == 4) rd_b(nxt, n + 1, 1);
+                        if (m == 7 && r % 6 == 5) { rd_b(nxt, n - 1, 0); rd_b(nxt, n, 0); }
+                    }
+                    GAP();
+                }
+            }
+            __syncthreads();
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        c1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+#pragma unroll
+            for (int n = 0; n < 8; ++n) sum += acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3];
+    } else {
+        const int wm = wid >> 2, wn = wid & 3, l15 = lane & 15, qd = lane >> 4;
+        const uint32_t* afr = lds + (wm * 128 + l15) * GROW + qd * 8;
+        const uint32_t* bfr = lds + (GT + wn * 64 + l15) * GROW + qd * 8;
+        h8 a[2][2], b[4][2];       // A: ring of two row tiles; B: one set
+        f32x4 acc[8][4] = {};
+        auto rd_a = [&](int buf, int m, int hl) { a[m & 1][hl] = *reinterpret_cast<const h8*>(afr + buf * GSTAGE + m * 16 * GROW + hl * 4); };
+        auto rd_b = [&](int buf, int n, int hl) { b[n][hl] = *reinterpret_cast<const h8*>(bfr + buf * GSTAGE + n * 16 * GROW + hl * 4); };
+        for (int rep = 0; rep < nrep; ++rep) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) gload1(kbeg, i);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) lstore1(0, i);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) gload1(kbeg + (nk > 1 ? 1 : 0), i);
+            __syncthreads();
+#pragma unroll
+            for (int n = 0; n < 4; ++n) { rd_b(0, n, 0); rd_b(0, n, 1); }
+            rd_a(0, 0, 0); rd_a(0, 0, 1);
+            GAP();
+            // Tile t: row m reads row tile m+1 of stage t & 1 into the other ring slot.  Rows 0 .. 5: tile t+1 from the
+            // staging registers to the other stage, each piece's request for tile t+2 behind it.  The barrier before row 7
+            // says: stage t & 1 is read out and tile t+1 is whole.  Row 7: row tile 0 and the column tiles of tile t+1.
+#pragma unroll 1
+            for (int t = 0; t < nk; ++t) {
+                const int cur = t & 1, nxt = cur ^ 1;
+                const int kt2 = kbeg + (t + 2 < nk ? t + 2 : nk - 1);
+#pragma unroll
+                for (int m = 0; m < 8; ++m)
+#pragma unroll
+                for (int r = 0; r < 12; ++r) {
+                    const int n = 2 * (r / 6) + (r & 1), term = (r % 6) >> 1;
+                    if (m == 7 && r == 0) { lds_barrier(); GAP(); }
+                    acc[m][n] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[m & 1][term == 0 ? 1 : 0], b[n][term == 1 ? 1 : 0],
+                                                                       acc[m][n], 0, 0, 0);
+                    if (r == 0) rd_a(m < 7 ? cur : nxt, (m + 1) & 7, 1);
+                    if (r == 1) rd_a(m < 7 ? cur : nxt, (m + 1) & 7, 0);
+                    const int g = m * 12 + r;               // rows 0 .. 5: a piece every 9 gaps
+                    if (m <= 5 && g % 9 == 2) lstore1(nxt, g / 9);
+                    if (m <= 5 && g % 9 == 3) gload1(kt2, g / 9);
+                    if (m == 7 && r % 6 == 3) rd_b(nxt, n - 1, 1);
+                    if (m == 7 && r % 6 == 4) rd_b(nxt, n + 1, 1);
+                    if (m == 7 && r % 6 == 5) { rd_b(nxt, n - 1, 0); rd_b(nxt, n, 0); }
+                    GAP();
+                }
+            }
+            __syncthreads();
+        }
+        GAP();
+        t1 = __builtin_amdgcn_s_memtime();
+        c1 = __builtin_amdgcn_s_memrealtime();
+        GAP();
+#pragma unroll
+        for (int m = 0; m < 8; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) sum += acc[m][n][0] + acc[m][n][1] + acc[m][n][2] + acc[m][n][3];
+    }
+    out[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * NT + tid] = sum;
+    if (tid == 0) {
+        stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 2] = t1 - t0;
+        stamps[(blockIdx.y * gridDim.x + blockIdx.x) * 2 + 1] = c1 - c0;
+    }
+}
+
 static uint16_t f16_bits(_Float16 h) { uint16_t b; memcpy(&b, &h, 2); return b; }
 
 // nwords 32-byte h2 slots (8 values: 16 B hi, 16 B lo) of uniform values in [-scale, scale), or zeros
@@ -492,11 +785,80 @@ static void enc_rows(const Bufs& d, int nrep, int passes) {
         }
 }
 
+template <int BODY>
+void run_gemm(const uint32_t* A, const uint32_t* W, float* out, unsigned long long* stamps, const char* data, int nrep) {
+    constexpr int NT = BODY == 2 ? 512 : 256;
+    auto launch = [&]() { hipLaunchKernelGGL(kg<BODY>, dim3(G_NWG, G_SPLITS), dim3(NT), 0, 0, nrep, A, W, out, stamps); };
+    const auto w0 = std::chrono::steady_clock::now();
+    int warm = 0;
+    do {
+        for (int i = 0; i < 8; ++i) launch();
+        CHECK(hipDeviceSynchronize());
+        warm += 8;
+    } while (std::chrono::duration<double>(std::chrono::steady_clock::now() - w0).count() < 2.0);
+    constexpr int L = 40, NW = G_NWG * G_SPLITS;
+    hipEvent_t e0, e1;
+    CHECK(hipEventCreate(&e0)); CHECK(hipEventCreate(&e1));
+    CHECK(hipEventRecord(e0, 0));
+    for (int i = 0; i < L; ++i) launch();
+    CHECK(hipEventRecord(e1, 0));
+    CHECK(hipEventSynchronize(e1));
+    float ms = 0;
+    CHECK(hipEventElapsedTime(&ms, e0, e1));
+    std::vector<unsigned long long> st(2 * NW);
+    CHECK(hipMemcpy(st.data(), stamps, st.size() * 8, hipMemcpyDeviceToHost));
+    std::vector<double> ghz(NW);
+    for (int i = 0; i < NW; ++i) ghz[i] = 0.1 * (double)st[2 * i] / (double)st[2 * i + 1];
+    std::sort(ghz.begin(), ghz.end());
+    const double flop = (double)L * nrep * 3.0 * 2.0 * G_M * G_N * G_K;
+    // one workgroup per CU: per SIMD and k-tile 96 32x32x16-equivalent MFMAs (one wave's, or two waves' 48 each)
+    const double cpm = (double)ms / L * 1e6 * ghz[NW / 2] / ((double)nrep * G_NK * 96.0);
+    printf("%-9s %-5s %-6s  %8.3f ms/launch  %8.1f TFLOP/s  clock %.3f GHz  %6.2f SIMD cycles per 32x32x16-equivalent MFMA  (%d warm launches)\n",
+           BODY == 0 ? "32x32x16" : "16x16x32", BODY == 0 ? "gemm-a" : BODY == 1 ? "gemm-b" : "gemm-c", data, ms / L,
+           flop / (ms * 1e-3) * 1e-12, ghz[NW / 2], cpm, warm);
+    fflush(stdout);
+    CHECK(hipEventDestroy(e0)); CHECK(hipEventDestroy(e1));
+}
+
+// the gemm rows: linear_1's operands at full size, A as copies of one random 1024-row block
+static void gemm_rows(int nrep, int passes) {
+    printf("linear_1 GEMM traffic: M %d, N %d, K %d in %d slices, %d x %d k-tiles of 32 per workgroup and launch\n", G_M, G_N, G_K,
+           G_SPLITS, nrep, G_NK);
+    const size_t a_bytes = (size_t)G_M * G_K * 4, w_bytes = (size_t)G_N * G_K * 4, blk_rows = 1024, blk = blk_rows * G_K * 4;
+    uint32_t *A, *W;
+    float* out;
+    unsigned long long* stamps;
+    CHECK(hipMalloc(&A, a_bytes)); CHECK(hipMalloc(&W, w_bytes));
+    CHECK(hipMalloc(&out, (size_t)G_NWG * G_SPLITS * 512 * 4)); CHECK(hipMalloc(&stamps, (size_t)G_NWG * G_SPLITS * 16));
+    std::vector<uint16_t> ha(blk / 2), hw(w_bytes / 2);
+    for (int pass = 0; pass < passes; ++pass)
+        for (int rnd = 1; rnd >= 0; --rnd) {
+            if (rnd) {
+                unsigned seed = 12345u;
+                fill_h2(ha.data(), blk / 32, true, 1.0f, seed);      // the decoder's h in (-1, 1)
+                fill_h2(hw.data(), w_bytes / 32, true, 0.5f, seed);
+                CHECK(hipMemcpy(W, hw.data(), w_bytes, hipMemcpyHostToDevice));
+                CHECK(hipMemcpy(A, ha.data(), blk, hipMemcpyHostToDevice));
+                for (size_t r = blk_rows; r < (size_t)G_M; r += blk_rows)
+                    CHECK(hipMemcpy(reinterpret_cast<char*>(A) + r * G_K * 4, A, blk, hipMemcpyDeviceToDevice));
+            } else {
+                CHECK(hipMemset(A, 0, a_bytes));
+                CHECK(hipMemset(W, 0, w_bytes));
+            }
+            CHECK(hipDeviceSynchronize());
+            const char* data = rnd ? "random" : "zeros";
+            run_gemm<0>(A, W, out, stamps, data, nrep);
+            run_gemm<1>(A, W, out, stamps, data, nrep);
+            run_gemm<2>(A, W, out, stamps, data, nrep);
+        }
+    CHECK(hipFree(A)); CHECK(hipFree(W)); CHECK(hipFree(out)); CHECK(hipFree(stamps));
+}
+
 int main(int argc, char** argv) {
     const int nrep = argc > 1 ? atoi(argv[1]) : 200, passes = argc > 2 ? atoi(argv[2]) : 2;
-    const char* rows = argc > 3 ? argv[3] : "all";      // all | dec | enc
-    const bool dec = strcmp(rows, "enc") != 0, enc = strcmp(rows, "dec") != 0;
-    hipDeviceProp_t prop;
+    const char* rows = argc > 3 ? argv[3] : "all";      // all | dec | enc | gemm
+    const bool all = strcmp(rows, "all") == 0;
+    const bool dec = all || strcmp(rows, "dec") == 0, enc = all || strcmp(rows, "enc") == 0;    hipDeviceProp_t prop;
     CHECK(hipGetDeviceProperties(&prop, 0));
     Bufs d;
     d.ncu = prop.multiProcessorCount;
@@ -527,6 +889,7 @@ int main(int argc, char** argv) {
             run<16, true>(d, data, nrep);
         }
     if (enc) enc_rows(d, nrep * K16 / EK16, passes);
+    if (all || strcmp(rows, "gemm") == 0) gemm_rows(std::max(1, nrep / 50), passes);
     CHECK(hipFree(d.aimg)); CHECK(hipFree(d.w)); CHECK(hipFree(d.out)); CHECK(hipFree(d.stamps));
     return 0;
 }

@@ -24,6 +24,7 @@ LABELS = [
     ("lstm_rec_h2_kernel<256, 512, true", "lstm_dec_h2_fused"),
     ("lstm_rec_h2_kernel<256, 32, false", "lstm_rec_h2_fused_in"),
     ("gemm_h2_kernel", "gemm_h2_linear_1"),
+    ("gemm_h2_k32_kernel", "gemm_h2_linear_1"),
     ("mlp_tail_h2_kernel", "mlp_tail_h2"),
     ("splitk_finish_kernel", "splitk_finish"),
     ("gru_rec_h2_kernel<128, 16", "gru_rec_h2_fused_in"),
