@@ -216,3 +216,60 @@ def variant_forward_f64(sd, images, gru_layers=1):
     logits = a @ sd["output_layer_type.weight"].astype(f8).T + sd["output_layer_type.bias"].astype(f8)
     e = np.exp(logits - logits.max(axis=1, keepdims=True))
     return e / e.sum(axis=1, keepdims=True), logits
+
+
+# ---- float64 restatement of the polish predict loop ----------------------------------------------------------------
+# Same equations and citations as gru_direction, polish_forward and polish_predict_chunks above, in float64 throughout
+# (sigmoid arguments clipped as in variant_forward_f64).  Stress families of polish weights -- a confident head, mixed
+# row scales, large biases (tests/weight_families.py) -- are judged against this form: the float32 restatement is itself
+# a few 1e-6 away from exact arithmetic there.
+def polish_predict_chunks_f64(sd, images, hidden_size, window=100, jump=50, overlap=50, gru_layers=1):
+    """images uint8/float [B,S,F] -> (acc float64 [B,S,C], counts float64 [B,S])."""
+    f8 = np.float64
+    sig = lambda v: 1.0 / (1.0 + np.exp(-np.clip(v, -700.0, 700.0)))   # noqa: E731
+    H = hidden_size
+    w = {k: np.asarray(v).astype(f8) for k, v in sd.items()}
+
+    def direction(x, h, w_ih, w_hh, b_ih, b_hh, reverse):
+        T = x.shape[1]
+        y = np.zeros((x.shape[0], T, H), f8)
+        xp = x @ w_ih.T + b_ih
+        whh = w_hh.T
+        for t in (range(T - 1, -1, -1) if reverse else range(T)):
+            hp = h @ whh + b_hh
+            r = sig(xp[:, t, :H] + hp[:, :H])
+            z = sig(xp[:, t, H:2 * H] + hp[:, H:2 * H])
+            n = np.tanh(xp[:, t, 2 * H:] + r * hp[:, 2 * H:])
+            h = (1.0 - z) * n + z * h
+            y[:, t] = h
+        return y, h
+
+    def bi_gru(prefix, inp, h0):
+        hn = np.zeros_like(h0)
+        for layer in range(gru_layers):
+            outs = []
+            for d, (s, rev) in enumerate((("", False), ("_reverse", True))):
+                y, hn[:, 2 * layer + d] = direction(inp, h0[:, 2 * layer + d], w[f"{prefix}.weight_ih_l{layer}{s}"],
+                                                    w[f"{prefix}.weight_hh_l{layer}{s}"], w[f"{prefix}.bias_ih_l{layer}{s}"],
+                                                    w[f"{prefix}.bias_hh_l{layer}{s}"], rev)
+                outs.append(y)
+            inp = np.concatenate(outs, axis=2)
+        return inp, hn
+
+    x = np.asarray(images).astype(f8)
+    B, S, _ = x.shape
+    C = w["dense1.bias"].shape[0]
+    hidden = np.zeros((B, 2 * gru_layers, H), f8)
+    acc = np.zeros((B, S, C), f8)
+    for i in range(0, S, jump):
+        if i + window > S:
+            break
+        y1, h_enc = bi_gru("gru_encoder", x[:, i:i + window], hidden)
+        y2, hidden = bi_gru("gru_decoder", y1, h_enc)
+        logits = y2 @ w["dense1.weight"].T + w["dense1.bias"]
+        e = np.exp(logits - logits.max(axis=2, keepdims=True))
+        acc[:, i:i + window] += e / e.sum(axis=2, keepdims=True)
+    counts = np.full((B, S), 2.0, f8)
+    counts[:, :overlap] = 1.0
+    counts[:, S - overlap:] = 1.0
+    return acc, counts

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void polish_combine_kernel(const float* __rest
         const int tc = i >> 2, q = i & 3;
         const f32x4 a = *reinterpret_cast<const f32x4*>(p0 + (size_t)tc * CMB_TILE + 4 * q);
         const f32x4 b = *reinterpret_cast<const f32x4*>(p0 + dstride + (size_t)tc * CMB_TILE + 4 * q);
-        const float bv = bias[tc % CMB_C];
+        const float bv = tc % CMB_C < C ? bias[tc % CMB_C] : 0.0f;   // bias holds C floats; classes C..4 are masked below
         f32x4 v = {a.x + b.x + bv, a.y + b.y + bv, a.z + b.z + bv, a.w + b.w + bv};
         *reinterpret_cast<f32x4*>(lg + tc * CMB_ROWS + 4 * q) = v;
     }

@@ -78,10 +78,14 @@ def make_variant_two_layer(tag, seed, gain, n=8):
 
 
 @torch.no_grad()
-def make_polish(tag, seed, gain, n=4):
+def make_polish(tag, seed, gain, n=4, head_scale=1.0):
+    """head_scale: dense1 (weight and bias) multiplied by it -- 40 gives the confident head of a trained checkpoint
+    (tests/weight_families.py confident_head): phred up to 100, the inf -> 100 replacement and the uint8 cast act."""
     from pepper.modules.python.models.simple_model import TransducerGRU
     import torch.nn as nn
     sd = synthetic.polish_state_dict(seed=seed, gain=gain)
+    sd["dense1.weight"] *= np.float32(head_scale)
+    sd["dense1.bias"] *= np.float32(head_scale)
     model = TransducerGRU(1, 10, 1, 128, 5, bidirectional=True)
     model.load_state_dict(to_torch(sd))
     model.eval()
@@ -106,7 +110,7 @@ def make_polish(tag, seed, gain, n=4):
     counts = nn.ZeroPad2d((50, 50))(counts) + 1
     phred = -10 * torch.log10(1.0 - (values / counts))
     phred[phred == float("inf")] = 100
-    np.savez_compressed(os.path.join(OUT, f"polish_{tag}.npz"), seed=seed, gain=gain, images=imgs,
+    np.savez_compressed(os.path.join(OUT, f"polish_{tag}.npz"), seed=seed, gain=gain, head_scale=head_scale, images=imgs,
                         logits_w0=logits0, hiddens=np.stack(hiddens, 0), acc=acc.numpy(),
                         labels=labels.numpy().astype(np.uint8),
                         phred=phred.numpy().astype(np.uint8), phred_f32=phred.numpy())
@@ -134,6 +138,10 @@ if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "polish_l2":
         make_polish_two_layer("l2", seed=23, gain=2.0)
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "polish_confident":
+        torch.set_num_threads(8)
+        make_polish("confident", seed=24, gain=1.0, n=2, head_scale=40)
+        sys.exit(0)
     torch.set_num_threads(8)
     make_variant("g1", seed=11, gain=1.0)
     make_variant("g3", seed=12, gain=3.0)
@@ -141,3 +149,4 @@ if __name__ == "__main__":
     make_polish("g1", seed=21, gain=1.0)
     make_polish("g3", seed=22, gain=3.0)
     make_polish_two_layer("l2", seed=23, gain=2.0)
+    make_polish("confident", seed=24, gain=1.0, n=2, head_scale=40)

@@ -38,3 +38,79 @@ def test_why_large_weights_leave_the_split_path():
         pe, le = wf.variant_forward_emulated(sd, x)
     assert max(wf.errors(p32, inter["logits"], p64, l64)) < 2e-5
     assert max(wf.errors(pe, le, p64, l64)) > 1e-4
+
+
+# ---- polish families (tests/weight_families.py make_polish; GPU leg: tests/test_gpu_polish_stress.py) ----------------
+POLISH_SHAPES = [{}, {"num_classes": 3}, {"num_classes": 7}, {"gru_layers": 2}]
+
+
+def test_polish_float64_restatement_is_pinned_by_the_reference_goldens(golden_dir):
+    """polish_predict_chunks_f64 against the accumulators the reference's own model class produced (float32 torch): the
+    default recipe at gain 3 and the confident head."""
+    import os
+    from pepper_amd import synthetic
+    for tag in ("g3", "confident"):
+        g = np.load(os.path.join(golden_dir, f"polish_{tag}.npz"))
+        sd = synthetic.polish_state_dict(seed=int(g["seed"]), gain=float(g["gain"]))
+        if "head_scale" in g.files:
+            sd["dense1.weight"] *= np.float32(g["head_scale"])
+            sd["dense1.bias"] *= np.float32(g["head_scale"])
+        acc64, counts = models_np.polish_predict_chunks_f64(sd, g["images"], 128)
+        assert np.abs(acc64 - g["acc"]).max() < 2e-5, tag
+        assert (counts[:, :50] == 1).all() and (counts[:, 950:] == 1).all() and (counts[:, 50:950] == 2).all()
+
+
+@pytest.mark.parametrize("family", wf.POLISH_FAMILIES)
+def test_polish_family_keeps_the_recurrence_conditioned(family):
+    """A family is a parity case only while the float32 restatement itself stays within 1e-5 of float64 on the test's own
+    chunks (measured distances: module docstring of weight_families)."""
+    case = wf.polish_case(family)
+    assert np.isfinite(case["acc32"]).all() and np.isfinite(case["acc64"]).all()
+    assert case["own"] <= 1e-5, (family, case["own"])
+    # each accumulated position is a sum of one or two softmax rows
+    assert np.abs(case["acc64"].sum(2) - case["counts"]).max() < 1e-12
+
+
+@pytest.mark.parametrize("shape", POLISH_SHAPES + [{"hidden": 256}], ids=str)
+def test_polish_shapes_stay_conditioned(shape):
+    n = 6 if shape.get("hidden") == 256 else wf.POLISH_CHUNKS
+    for family in ("default", "confident_head"):
+        assert wf.polish_case(family, n=n, **shape)["own"] <= 1e-5, (family, shape)
+
+
+def test_confident_head_reaches_the_trained_regime():
+    """phred 100 (t == 0 exactly) in the counts == 1 and in the counts == 2 region, and a spread of phred values between."""
+    case = wf.polish_case("confident_head")
+    edge = case["counts"] == 1
+    for acc in (case["acc32"], case["acc64"].astype(np.float32)):
+        _, phred, _, t = wf.polish_phred_from_acc(acc, case["counts"])
+        assert (phred[t == 0] == 100).all() and (phred[t > 0] < 100).all()
+        assert (t[edge] == 0).sum() > 100 and (t[~edge] == 0).sum() > 100
+        assert len(np.unique(phred)) >= 40
+    # a default-recipe head stays below phred 10: what every polish test saw before
+    assert wf.polish_phred_from_acc(wf.polish_case("default")["acc32"], case["counts"])[1].max() < 10
+
+
+def test_polish_near_tie_head_produces_near_ties():
+    case = wf.polish_case("near_tie_head")
+    top2 = np.sort(case["acc64"], axis=2)[:, :, -2:]
+    gap = top2[:, :, 1] - top2[:, :, 0]
+    assert gap.max() < 1e-3 and (gap > 0).all()
+    assert len(np.unique(case["acc64"].argmax(2))) > 1          # and no class wins everywhere
+
+
+@pytest.mark.parametrize("family", ["default"] + wf.POLISH_FAMILIES)
+def test_finalize_restated_in_float64_agrees_with_the_float32_formula(family):
+    """The expected phred of the GPU tests is floor(-10 log10(float64(t))) with t = f32(1 - f32(best / counts)); the
+    restatement of predict_distributed_cpu.py:83-90 takes log10 in float32.  The two agree except where ph is within 1e-4
+    of an integer, and such positions are at most 0.2 % of a call."""
+    case = wf.polish_case(family)
+    labels, phred, ph, t = wf.polish_phred_from_acc(case["acc32"], case["counts"])
+    values = case["acc32"].max(axis=2)
+    with np.errstate(divide="ignore"):
+        ph32 = -10.0 * np.log10((1.0 - values / case["counts"].astype(np.float32)).astype(np.float32))
+    ph32[np.isinf(ph32)] = 100
+    excused = (t > 0) & (np.abs(ph - np.round(ph)) < 1e-4)
+    assert excused.mean() <= 2e-3, excused.mean()
+    assert ((phred == ph32.astype(np.uint8)) | excused).all()
+    assert (labels == case["acc32"].argmax(2)).all()

@@ -3,7 +3,19 @@ recipe of pepper_amd.synthetic only scales ONE distribution; a trained checkpoin
 magnitude side by side, heavy tails and the odd large bias.  Each family starts from the PyTorch-default init and
 reshapes it; `near_tie_head` makes the three class scores almost equal so that tiny logit errors would flip calls.
 Also a numpy emulation of the product's arithmetic (every contraction as hi*hi + hi*lo + lo*hi on f16 halves) so the
-families can be judged on the CPU before a GPU sees them."""
+families can be judged on the CPU before a GPU sees them.
+
+Polish families (make_polish, POLISH_FAMILIES): the same idea for the bi-GRU polish model, plus the head of a trained
+checkpoint -- `confident_head` (dense1 x 40) puts phred between 1 and 100 with the accumulator at exactly 1.0 / 2.0 on
+about a tenth of the positions, `graded_head` (dense1.weight x 12) spreads phred over 1 .. 48.  The 1900-step recurrence
+with its hidden carry turns chaotic when the GRU matrices grow, so a family is a parity case only while the float32
+restatement itself stays within 1e-5 of the float64 one on the test's own chunks (polish_case: seed 70, 20 chunks of
+P-syn seed 2024).  Measured max |acc_f32 - acc_f64|:
+    default 1.5e-7   graded_head 1.2e-6   confident_head 4.1e-6   near_tie_head 7.9e-8   large_bias 2.1e-7
+    mixed_row_scales  top 0: 8.2e-8   0.5: 8.7e-8   1.0: 1.3e-7   1.2: 1.5e-7 (kept)   1.5: 2.3e-1   2.0: 4.2e-1
+    large_entries     rate 1e-4: 3.1e-7   2e-4: 3.2e-6   3e-4: 1.9e-6 (kept)   5e-4: 3.2e-5
+    confident_head at 3 classes 4.4e-6, 7 classes 3.8e-6, two GRU layers 2.5e-6, hidden size 256 (6 chunks) 4.2e-6
+so all six are parity cases (tests/test_weight_families_cpu.py holds each to 1e-5)."""
 import numpy as np
 
 from pepper_amd import synthetic
@@ -52,6 +64,93 @@ def make(name, seed):
     else:
         raise KeyError(name)
     return sd
+
+
+POLISH_FAMILIES = ["graded_head", "confident_head", "near_tie_head", "mixed_row_scales", "large_bias", "large_entries"]
+POLISH_MIXED_TOP = 1.2        # mixed_row_scales: per-row factors 10 ** U(-3, top) on the GRU matrices
+POLISH_SPRINKLE_RATE = 3e-4   # large_entries: share of GRU matrix entries set to +-50
+
+
+def make_polish(name, seed, top=None, rate=None, **shape_kw):
+    """Polish checkpoints (pepper_amd.synthetic.polish_state_dict(gain=1) reshaped); shape_kw: hidden, num_classes,
+    gru_layers.  `default` is the unchanged recipe."""
+    sd = synthetic.polish_state_dict(seed=seed, gain=1.0, **shape_kw)
+    rng = np.random.default_rng([seed, 98])
+    gru = [k for k, v in sd.items() if v.ndim == 2 and k.startswith("gru_")]
+    if name == "default":
+        pass
+    elif name == "graded_head":
+        sd["dense1.weight"] *= 12.0
+    elif name == "confident_head":
+        sd["dense1.weight"] *= 40.0
+        sd["dense1.bias"] *= 40.0
+    elif name == "near_tie_head":
+        w, b = sd["dense1.weight"], sd["dense1.bias"]
+        for c in range(1, w.shape[0]):
+            sign = 1.0 if c % 2 else -1.0
+            w[c] = w[0] * np.float32(1.0 + sign * c * 1e-4)
+            b[c] = b[0] + np.float32(sign * 1e-5)
+    elif name == "mixed_row_scales":
+        top = POLISH_MIXED_TOP if top is None else top
+        for k in gru:
+            sd[k] *= (10.0 ** rng.uniform(-3.0, top, size=(sd[k].shape[0], 1))).astype(np.float32)
+    elif name == "large_bias":
+        for k, v in sd.items():
+            if v.ndim == 1:
+                v *= 20.0
+    elif name == "large_entries":
+        rate = POLISH_SPRINKLE_RATE if rate is None else rate
+        for k in gru:
+            hit = rng.random(sd[k].shape) < rate
+            sd[k][hit] = rng.choice([-50.0, 50.0], size=int(hit.sum())).astype(np.float32)
+    else:
+        raise KeyError(name)
+    return sd
+
+
+def polish_stress_chunks(n, seed):
+    """n chunks of P-syn, one of them zero from position 300 on (the padded tail chunk_images produces)."""
+    x = synthetic.polish_chunks(n, seed=seed)
+    x[min(1, n - 1), 300:] = 0
+    return x
+
+
+POLISH_SEED, POLISH_CHUNK_SEED, POLISH_CHUNKS = 70, 2024, 20
+_POLISH_CASES = {}
+
+
+def polish_case(name, n=POLISH_CHUNKS, **shape_kw):
+    """One family (or `default`) at one model shape on the stress chunks, restated once per process in float64 and in
+    float32: dict(sd, x, acc64, counts, acc32, own) with own = max |acc32 - acc64|, the float32 restatement's own distance
+    from exact arithmetic.  Shared by the CPU checks and the GPU tests; callers leave the arrays unchanged."""
+    import warnings
+    from oracle import models_np
+    key = (name, n, tuple(sorted(shape_kw.items())))
+    if key not in _POLISH_CASES:
+        sd = make_polish(name, POLISH_SEED, **shape_kw)
+        x = polish_stress_chunks(n, POLISH_CHUNK_SEED)
+        H, L = shape_kw.get("hidden", synthetic.POLISH_HIDDEN), shape_kw.get("gru_layers", 1)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")          # exp overflow inside the float32 sigmoid of saturated gates
+            acc64, counts = models_np.polish_predict_chunks_f64(sd, x, H, gru_layers=L)
+            _, _, inter = models_np.polish_predict_chunks(sd, x, H, gru_layers=L, return_intermediates=True)
+        _POLISH_CASES[key] = dict(sd=sd, x=x, acc64=acc64, counts=counts, acc32=inter["acc"],
+                                  own=float(np.abs(inter["acc"] - acc64).max()))
+    return _POLISH_CASES[key]
+
+
+def polish_phred_from_acc(acc, counts):
+    """Labels, phred and t = f32(1 - f32(best / counts)) from a float32 accumulator, the finalize step restated in float64:
+    ph = -10 log10(t), 100 where t == 0, truncated to uint8.  -> (labels uint8, phred uint8, ph float64, t float32)."""
+    acc = np.asarray(acc, np.float32)
+    labels = acc.argmax(axis=2).astype(np.uint8)        # first maximum wins
+    best = acc.max(axis=2)
+    q = (best / np.asarray(counts, np.float32)).astype(np.float32)
+    t = (np.float32(1.0) - q).astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ph = -10.0 * np.log10(t.astype(np.float64))      # (NaN where t < 0: best > counts, which no softmax sum gives)
+    ph[t == 0] = 100.0
+    return labels, np.floor(np.where(t < 0, 0.0, ph)).astype(np.uint8), ph, t
 
 
 def stress_windows(n, seed):
