@@ -841,8 +841,8 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         switch (f.rec) {
         case FUSED_IN_H2:
             LAUNCH_TRY(m, "lstm_rec_h2_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
-                       pa::launch_lstm_rec_h2(H, nullptr, 0, static_cast<const int8_t*>(cur), r.K, bias_l,
-                                              r.w_cat_h2->p, y, 2 * H, (int)n, T, m->stream, s.small_rows));
+                       pa::launch_lstm_enc_h2(H, static_cast<const int8_t*>(cur), r.K, bias_l, r.w_cat_h2->p, y, 2 * H, (int)n, T,
+                                              m->stream, s.small_rows));
             break;
         case FUSED_IN_F32:
             LAUNCH_TRY(m, "lstm_rec_fused_in", 2.0 * n * T * (4.0 * H) * (H + r.K) * 2,
@@ -864,8 +864,7 @@ static int variant_forward_chunk(pa_variant_model* m, int a_kind, const void* im
         }
         case PLAIN_H2:
             LAUNCH_TRY(m, "lstm_rec_h2", 2.0 * n * T * (4.0 * H) * H * 2,
-                       pa::launch_lstm_rec_h2(H, m->xp->f(), NX, nullptr, 0, nullptr, r.w_hh_h2->p, y, 2 * H, (int)n,
-                                              T, m->stream, s.small_rows));
+                       pa::launch_lstm_seed_h2(H, m->xp->f(), NX, r.w_hh_h2->p, y, 2 * H, (int)n, T, m->stream, s.small_rows));
             break;
         case PLAIN_F32:
             LAUNCH_TRY(m, "lstm_rec", 2.0 * n * T * (4.0 * H) * H * 2,

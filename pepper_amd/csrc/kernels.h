@@ -49,19 +49,21 @@ hipError_t launch_gru_rec_fused(int H, const uint8_t* X, int F, int64_t x_bstrid
                                 const float* Wcat, const float* bhn, const float* h0, int ldh0, float* hn, int ldhn,
                                 float* Y, int ldy, int B, int T, hipStream_t stream);
 
-// rnn_h2.hip: the LSTM step loop on the f16 matrix pipe.  X == nullptr: Xp seeds the accumulators as in
-// launch_lstm_rec, weights packed by pack_rec_weights_h2 (wih = {nullptr, nullptr}, KX = 0: W_hh alone).  X != nullptr
-// selects the fused first layer (int8 rows [B, T, F], F <= 32, bias [2*4H]) on 16x16x32 tiles: weights packed with
-// pa_dec16::pack(whh, wih, H, 32, out, F, bias) of dec_frag16.h (the bias in column H + F when F < 32).
+// rnn_h2.hip: the LSTM step loops on the f16 matrix pipe (H = 256).  launch_lstm_seed_h2: Xp seeds the accumulators as in
+// launch_lstm_rec, weights packed by pack_rec_weights_h2 (wih = {nullptr, nullptr}, KX = 0: W_hh alone).
+// launch_lstm_enc_h2: the fused first layer (int8 rows X [B, T, F], 0 < F <= 32, bias [2*4H]) on 16x16x32 tiles: weights
+// packed with pa_dec16::pack(whh, wih, H, 32, out, F, bias) of dec_frag16.h (the bias in column H + F when F < 32).
 // Y receives the layer output in the h2 split format (ldy in 4-byte elements).
 void pack_rec_weights_h2(const float* const whh[2], const float* const wih[2], int G, int H, int F, int KX,
                          uint32_t* out, const float* const* bias = nullptr);   // bias: column H + F (fused layers, F < KX)
 size_t rec_weights_h2_words(int G, int H, int KX);
 int gru_fused_input_kx(int H, int F);   // 16 / 128: padded width of the uint8-input step loop; 0: projection as a GEMM
 // The weights, the bias and Xp are multiplied per gate row by the exp2 constants (see rnn_h2.hip).
-hipError_t launch_lstm_rec_h2(int H, const float* Xp, int ldx, const int8_t* X, int F, const float* bias,
-                              const void* Wp, void* Y, int ldy, int B, int T, hipStream_t stream,
-                              bool small = false);   // small: 32-row workgroups (small calls)
+// small: 32-row workgroups (small calls); the encoder has none for F = 32 and takes the 64-row ones
+hipError_t launch_lstm_seed_h2(int H, const float* Xp, int ldx, const void* Wp, void* Y, int ldy, int B, int T,
+                               hipStream_t stream, bool small = false);
+hipError_t launch_lstm_enc_h2(int H, const int8_t* X, int F, const float* bias, const void* Wp, void* Y, int ldy, int B, int T,
+                              hipStream_t stream, bool small = false);
 
 // The step loop of a call of at most 512 windows with a tile's hidden units split over eight workgroups that exchange h_t
 // through `exch` every step (rnn_h2.hip lstm_rec_h2_split_kernel); prescaled weights only.  *failed is set when a group

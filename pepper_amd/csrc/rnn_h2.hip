@@ -1,21 +1,26 @@
-// LSTM step loop on the f16 matrix pipe with split (h2) operands -- the fast form of
+// LSTM and GRU step loops on the f16 matrix pipe with split (h2) operands -- the fast forms of
 // rnn.hip:lstm_rec_kernel for the variant model's four H = 256 directions
-// (/root/reference/pepper_variant/modules/python/models/simple_model.py:51,54).
+// (pepper_variant/modules/python/models/simple_model.py:51,54 of the reference), and their GRU counterparts.
 //
 // Same decomposition and lockstep phase structure as the f32 kernel (workgroup = 64 batch rows x one
 // direction, wave u owns hidden units [32u, 32u+32) of all four gates and both row tiles, MFMA phase
 // | barrier | gate phase | barrier), but the contraction h_{t-1} W_hh^T (+ x_t W_ih^T when the input
-// projection is fused) runs as three v_mfma_f32_32x32x16_f16 per 16-wide k step on operands held as
+// projection is fused) runs as three f16 MFMAs per k step on operands held as
 // f16 hi/lo pairs (gemm_h2.hip describes the format and why it is as accurate as f32):
 //   * h lives in LDS in h2 form (32 bytes per 8 units: 16 B hi, 16 B lo); the gate phase rounds
-//     the new h to (hi, lo), neighbouring lanes swap one half through DPP so each lane still writes
-//     one dword per element;
+//     the new h to (hi, lo) and each lane writes its own pair with two 16-bit stores (h2_store16);
 //   * y is that LDS image copied out 16 bytes per lane during the MFMA phase, i.e. the layer output
 //     is ALREADY in the h2 format the next projection GEMM / linear_1 consumes -- no conversion pass;
-//   * W_hh (and W_ih for the fused first layer, whose int8 inputs are exact in the hi half) is packed
-//     on the host in per-lane fragment order [gate tile][k step][hi, lo][64 lanes][16 B], streamed
-//     from L2 through a 2-deep register ring.
-// Per step a wave issues 24 MFMAs x 32 cycles per k step instead of 128 x 64: the MFMA phase shrinks
+//   * W_hh (and W_ih for the fused layers; the first layer's int8 inputs are exact in the hi half) is packed
+//     on the host in per-lane fragment order, streamed from L2 through a register ring.
+// The LSTM has three step loops, each a kernel of its own:
+//   * lstm_seed_h2_kernel: accumulators seeded from Xp, the projection GEMM's output; v_mfma_f32_32x32x16_f16, weights
+//     in [gate tile][k step][hi, lo][64 lanes][16 B] order (pack_rec_weights_h2).  What small calls run;
+//   * lstm_enc_h2_kernel: the first layer with its int8 input contracted inside the loop, v_mfma_f32_16x16x32_f16;
+//   * lstm_dec_h2_kernel: the layers fed by an h2 layer output, contracted inside the loop, v_mfma_f32_16x16x32_f16
+//     (both in dec_frag16.h's fragment order).
+// lstm_rec_h2_split_kernel splits a tile's hidden units over workgroups for the smallest calls; the GRU loops follow.
+// Per step a wave of the 32x32x16 loop issues 24 MFMAs x 32 cycles per k step instead of 128 x 64: the MFMA phase shrinks
 // ~5x and the weight stream (1 MiB per step per workgroup, same bytes as f32) becomes the thing to
 // watch (~40 B/clk/CU of the ~64 B/clk/CU L2 path).
 #include <cstdlib>
@@ -26,6 +31,7 @@
 namespace {
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int MT = 64;
 
@@ -37,62 +43,106 @@ PA_DEV void decode_block(int bid, int& dir, int& btile) {
     btile = q * 4 + (xcd & 3);
 }
 
-// value of lane ^ 1 (quad_perm [1,0,3,2])
-
-
+// ------------------------------------------------------------------------------------------------
+// What the three LSTM step loops (H = 256, 8 waves) share.
 // The packed weights, the bias and Xp arrive pre-multiplied per gate row by -log2(e) (i, f, o) or
 // +2 log2(e) (g), so the accumulators ARE the exp2 arguments of sigmoid / tanh (api.hip build_rec_layer).
-// XG (decoder layers, whose input x_t is the previous layer's h2 output Xh [B*T, KX]): a step loop of its own,
-// lstm_dec_h2_body below; this kernel is only its entry.
-// KX = 32 (the fused int8 first layer) likewise: lstm_enc_h2_body below, on v_mfma_f32_16x16x32_f16 like the decoder's.  What
-// this kernel's own body still runs is the form seeded from Xp (KX = 0, whose Xp arrives in 32x32 C-fragment order); the
-// fused parts of it (x_load / x_store, BC, the two-term x steps) are what the encoder body restates on its own tiles.
-// SAUX: cache policy of the stream that passes through once -- the y stores (2 = nt: the lines are not kept in the XCD's
-// L2, which has to hold this direction's weight fragments that every workgroup re-reads every step; 0 = default policy,
-// what the forms seeded from Xp are launched with).  Measured r02 (16384 windows, device-resident pass): 2.566 -> 2.596 M
-// windows/s with nt on the once-through streams.
-// BC (fused int8 first layer with F < KX): the bias lives in column H + F of the packed weights and x carries a constant
-// 1.0 there, so the first MFMA of a step starts every accumulator from the inline constant 0: no bias loads and no 128
-// register moves per step in the gate phase, which is bound by VALU issue (two waves per SIMD, ~1300 instructions each).
-// MTILES (row tiles of 32 per workgroup; 2 = the 64-row workgroup everything above describes, 1 = the small-call schedule):
+// MTILES (row tiles of 32 per workgroup; 2 = the 64-row workgroup, 1 = the small-call schedule):
 // a step is one CU's affair -- 8 waves x KS k steps x 12 MTILES MFMAs of 32 cycles on 4 SIMDs, then the gate phase of
 // 16 MTILES elements per lane -- whatever the number of workgroups, so a call of a few hundred windows, which fills a small
 // part of the chip either way, takes half the time per step with 32-row workgroups (twice as many of them, each still
 // streaming the direction's weight fragments from L2).  Big calls keep 64 rows: half the weight stream per window.
-template <int MTILES>
-PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
-                             int B, int T, unsigned long long* __restrict__ dbg, const uint32_t* __restrict__ Xh, int ldxh);
-// The fused int8 first layer (KX = 32) has a step loop of its own as well, lstm_enc_h2_body below.
-template <int MTILES, bool BC>
-PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* __restrict__ bias, const uint32_t* __restrict__ Wp,
-                             uint32_t* __restrict__ Y, int ldy, int B, int T, unsigned long long* __restrict__ dbg);
 
-template <int H, int KX, bool XG = false, int SAUX = 0, bool BC = false, int MTILES = 2>
-__global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float* __restrict__ Xp, int ldx,
-                                                                     const int8_t* __restrict__ Xi, int F,
-                                                                     const float* __restrict__ bias,
-                                                                     const uint32_t* __restrict__ Wp,
-                                                                     uint32_t* __restrict__ Y, int ldy, int B, int T,
-                                                                     unsigned long long* __restrict__ dbg,
-                                                                     const uint32_t* __restrict__ Xh = nullptr, int ldxh = 0) {
-    if constexpr (XG) {
-        static_assert(H == 256 && KX == 512 && SAUX == 2 && !BC, "the fused decoder has one shape");
-        lstm_dec_h2_body<MTILES>(bias, Wp, Y, ldy, B, T, dbg, Xh, ldxh);
-        return;
-    }
-    if constexpr (!XG && KX == 32) {
-        static_assert(H == 256 && SAUX == 2, "the fused int8 encoder has one shape");
-        lstm_enc_h2_body<MTILES, BC>(Xi, F, bias, Wp, Y, ldy, B, T, dbg);
-        return;
-    }
-    constexpr int KT = H + KX, KS = KT / 16, KSH = H / 16, NT = H / 32, NW = H / 32;
-    constexpr int MTL = 32 * MTILES;             // rows of this workgroup
+// The dynamic LDS of a step loop, in the order it is carved: [32 MTILES rows][ROWD] the h2 image of [h | KXROW columns of x]
+// + 16 B pad, the c state (f32) [wave][16 MTILES][lane], then two ring slots of [rows][XRD] dwords (the decoder's x ring).
+// The kernels take their pointers from here and the launchers their size.  (The three layouts, named once: below.)
+// The helpers reach `lds` by name; the split and GRU kernels further down declare the same array again, locally.
+extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+template <int MTILES, int KXROW = 0, int XRD_ = 0>
+struct LstmLds {
     static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
-    constexpr int ROWB = KT * 4 + 16;            // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
-    constexpr int ROWD = ROWB / 4;               // in dwords
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, then c (f32)
-    static_assert(KS % 2 == 0, "the weight prefetch assumes an even number of k steps");
+    static constexpr int H = 256, NW = H / 32;
+    static constexpr int MTL = 32 * MTILES;              // rows of the workgroup
+    static constexpr int ROWB = (H + KXROW) * 4 + 16;    // bytes per row: h2 image + 16 pad (odd 16-B count)
+    static constexpr int ROWD = ROWB / 4;                // in dwords
     static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
+    static constexpr int CS = NW * MTILES * 16 * 64;     // dwords of c state
+    static constexpr int XRD = XRD_, XSLOT = MTL * XRD;  // dwords of a ring row and a ring slot
+    static constexpr int RING = MTL * ROWD + CS;         // where the ring starts
+    static constexpr size_t BYTES = (size_t)(RING + 2 * XSLOT) * 4;
+    static_assert(BYTES <= 160 * 1024, "a workgroup has one CU's 160 KB of LDS");
+    // the lane's c slots, [wave][m][r][lane]
+    PA_DEV static float* c_slots(int u, int lane) { return reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane; }
+    // h_{-1} = c_{-1} = 0 (the ring needs no zeros)
+    PA_DEV static void clear(int tid) {
+        for (int idx = tid; idx < RING; idx += blockDim.x) lds[idx] = 0u;
+    }
+};
+
+template <int MTILES> using SeedLds = LstmLds<MTILES>;          // lstm_seed_h2_kernel: h rows
+template <int MTILES> using EncLds = LstmLds<MTILES, 32>;       // lstm_enc_h2_kernel: [h | 32 x columns] rows
+template <int MTILES> using DecLds = LstmLds<MTILES, 0, 36>;    // lstm_dec_h2_kernel: h rows, ring rows of 128 B of x + 16 B pad
+
+// Gate phase of two elements of a lane: the exp2 arguments of i, f, g, o in, c (slots c[0] and c[64]) updated, the new h
+// pair out.  The plain arithmetic is written on 2-vectors so it can issue as packed f32 instructions (the matrix pipe is
+// idle in this phase).
+// (Starting a wave's gate math before the barrier, beside the other wave's MFMAs, was measured:
+// the VALU / transcendental issue slows that MFMA stream by about what it hides.  The phase is
+// transcendental-bound: 10 quarter-rate ops per element.)
+PA_DEV f32x2 lstm_gate_pair(f32x2 ai, f32x2 af, f32x2 ag, f32x2 ao, float* c) {
+    const f32x2 one = {1.0f, 1.0f};
+    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
+    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
+    const f32x2 ig = rcp(one + ex2(ai));
+    const f32x2 fg = rcp(one + ex2(af));
+    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
+    const f32x2 og = rcp(one + ex2(ao));
+    const f32x2 cold = {c[0], c[64]};
+    const f32x2 cn = fg * cold + ig * gg;
+    c[0] = cn.x;
+    c[64] = cn.y;
+    return og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
+}
+
+// y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is, 16 bytes per thread and pass.
+// AUX: cache policy of the stores, a stream that passes through once (2 = nt: the lines are not kept in the XCD's L2, which
+// has to hold this direction's weight fragments that every workgroup re-reads every step; 0 = default policy, what the loop
+// seeded from Xp is launched with).  Measured r02 (16384 windows, device-resident pass): 2.566 -> 2.596 M windows/s with
+// nt on the once-through streams.
+template <int ROWD, int MTL, int AUX>
+struct YCopy {
+    static constexpr int CPR = 256 / 4;            // 16-byte chunks per row
+    static constexpr int YROWS = 512 / CPR;        // rows per pass (8)
+    static constexpr int YC = MTL / YROWS;         // passes (8 or 4)
+    const uint32_t* src;
+    __amdgpu_buffer_rsrc_t rs;
+    unsigned off;
+    int T, ldy;
+    PA_DEV YCopy(uint32_t* Y, int ldy_, int b0, int T_, int dir, int tid) : T(T_), ldy(ldy_) {
+        const int row = tid / CPR, c = tid % CPR;
+        src = lds + row * ROWD + c * 4;
+        rs = __builtin_amdgcn_make_buffer_rsrc(Y + (size_t)b0 * T * ldy + dir * 256, 0, 0x7fffffff, 0x00020000);
+        off = ((unsigned)(row * T) * ldy + c * 4) * 4u;
+    }
+    PA_DEV u32x4 read(int j) const { return *reinterpret_cast<const u32x4*>(src + j * YROWS * ROWD); }
+    PA_DEV void write(int j, int tp, u32x4 v) const {      // pass j of time index tp
+        __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, AUX);
+    }
+};
+// (The passes after the last step stay a short loop in each kernel, and the helpers take no `lds` argument: either changes
+// the device code, profiles/lstm_step_loop_entries_isa.txt.)
+
+// ------------------------------------------------------------------------------------------------
+// The step loop seeded from Xp = x W_ih^T + b, the projection GEMM's output in 32x32 C-fragment order: v_mfma_f32_32x32x16_f16,
+// K = H, acc[row tile of 32][gate] (f32x16), a 2-deep register ring of whole k steps.  y goes out with the default cache policy.
+template <int MTILES>
+__global__ __launch_bounds__(512, 1) void lstm_seed_h2_kernel(const float* __restrict__ Xp, int ldx, const uint32_t* __restrict__ Wp,
+                                                              uint32_t* __restrict__ Y, int ldy, int B, int T,
+                                                              unsigned long long* __restrict__ dbg) {
+    using L = SeedLds<MTILES>;
+    constexpr int H = 256, KS = H / 16, NT = H / 32;
+    constexpr int MTL = L::MTL, ROWD = L::ROWD;
+    static_assert(KS % 2 == 0, "the weight prefetch assumes an even number of k steps");
 
     int dir, btile;
     decode_block(blockIdx.x, dir, btile);
@@ -102,16 +152,13 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
     const int tid = threadIdx.x, lane = tid & 63;
     const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, hf = lane >> 5;
-
-    float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][r][lane]
-    for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
+    float* cs = L::c_slots(u, lane);
+    L::clear(tid);
 
     f32x16 acc[MTILES][4];   // [row tile][gate]
 
-    const size_t urow = (size_t)b0 * T;
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<float*>(KX ? bias + dir * 4 * H + 32 * u : Xp + (size_t)(b0 >> 5) * T * (ldx >> 5) * 1024), 0,
-        0x7fffffff, 0x00020000);
+        const_cast<float*>(Xp + (size_t)(b0 >> 5) * T * (ldx >> 5) * 1024), 0, 0x7fffffff, 0x00020000);
     // fragment (g, s, hi/lo) of this wave lives at byte (((g*NT + u) * KS + s) * 2 + hl) * 1024 + lane * 16 of the direction's
     // block.  The wave's own term (u) is part of the descriptor's base, so that every fragment's scalar offset is a
     // compile-time constant the compiler re-materialises with one s_mov where it needs it: with `u` inside the offset the
@@ -119,60 +166,23 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
     // lanes and 314 v_readlane_b32 per time step in the K = 768 form.
     const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * NT) + u) * KS * 512), 0, 0x7fffffff, 0x00020000);
-    const unsigned xoff = KX ? li * 4u : lane * 16u;
+    const unsigned xoff = lane * 16u;
     const unsigned woff = lane * 16u;
 
-    // accumulator seed of (row tile m, register chunk qd) for step t: the unfused form starts from the precomputed input
-    // projection (identical to rnn.hip).  Fused forms (KX > 0) seed nothing: the first product into every accumulator starts from the inline constant 0 and the
-    // four biases of the lane's column are added in the gate phase (packed adds; with the bias column they are zero).
+    // accumulator seed of (row tile m, register chunk qd) for step t: the precomputed input projection (identical to rnn.hip)
     auto seed_chunk = [&](int m, int qd, int t) {
-        if (KX) return;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            {
-                const unsigned ct = (unsigned)(dir * (4 * NT) + g * NT + u);
-                const unsigned so = (((unsigned)(m * T + t) * (ldx >> 5) + ct) * 4u + qd) * 1024u;
-                const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff, so, 0));
-                acc[m][g][4 * qd] = v.x;
-                acc[m][g][4 * qd + 1] = v.y;
-                acc[m][g][4 * qd + 2] = v.z;
-                acc[m][g][4 * qd + 3] = v.w;
-            }
+            const unsigned ct = (unsigned)(dir * (4 * NT) + g * NT + u);
+            const unsigned so = (((unsigned)(m * T + t) * (ldx >> 5) + ct) * 4u + qd) * 1024u;
+            const f32x4 v = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff, so, 0));
+            acc[m][g][4 * qd] = v.x;
+            acc[m][g][4 * qd + 1] = v.y;
+            acc[m][g][4 * qd + 2] = v.z;
+            acc[m][g][4 * qd + 3] = v.w;
         }
     };
 
-    // fused only: x_t (int8, exact in f16) -> hi halves of LDS columns [H, H+KX); lo halves stay 0.
-    // One thread per pair of features: 64 rows x KX/2 pairs over 512 threads.
-    constexpr bool XI8 = KX > 0;
-    constexpr int XN = XI8 ? (MTL * KX / 2) / (NW * 64) : 1;
-    unsigned xv[XN];
-    auto x_load = [&](int t) {
-        if (XI8) {
-#pragma unroll
-            for (int k = 0; k < XN; ++k) {
-                const int e = tid + k * (NW * 64);
-                const int row = e / (KX / 2), f = (e % (KX / 2)) * 2;
-                int brow = b0 + row;
-                brow = brow < B ? brow : B - 1;
-                const int8_t* src = Xi + ((size_t)brow * T + t) * F;
-                const _Float16 one = BC ? (_Float16)1.0f : (_Float16)0.0f;     // the bias column's input
-                const _Float16 h0 = f < F ? (_Float16)(float)src[f] : (f == F ? one : (_Float16)0.0f);
-                const _Float16 h1 = f + 1 < F ? (_Float16)(float)src[f + 1] : (f + 1 == F ? one : (_Float16)0.0f);
-                xv[k] = (unsigned)__builtin_bit_cast(unsigned short, h0) |
-                        ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
-            }
-        }
-    };
-    auto x_store = [&]() {
-        if (XI8) {
-#pragma unroll
-            for (int k = 0; k < XN; ++k) {
-                const int e = tid + k * (NW * 64);
-                const int row = e / (KX / 2), f = (e % (KX / 2)) * 2;
-                lds[row * ROWD + ((H + f) >> 3) * 8 + ((f & 7) >> 1)] = xv[k];
-            }
-        }
-    };
     struct Frag { h8 b[4][2], a[MTILES][2]; };     // [gate][hi, lo], [row tile][hi, lo]
     const uint32_t* arow = lds + li * ROWD + hf * 8;
     auto load_b = [&](int s, Frag& fr) {
@@ -183,7 +193,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                 fr.b[g][hl] = __builtin_bit_cast(h8, __builtin_amdgcn_raw_buffer_load_b128(
                                                          wrs, woff, (unsigned)((g * NT * KS + s) * 2 + hl) * 1024u, 0));
     };
-    auto load_a = [&](int s, Frag& fr, int) {
+    auto load_a = [&](int s, Frag& fr) {
 #pragma unroll
         for (int m = 0; m < MTILES; ++m) {
             fr.a[m][0] = *reinterpret_cast<const h8*>(arow + m * 32 * ROWD + s * 16);
@@ -191,25 +201,13 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
         }
     };
 
-    // y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is
-    constexpr int CPR = H / 4;                                // 16-byte chunks per row
-    constexpr int YROWS = (NW * 64) / CPR;                    // rows per pass (8)
-    constexpr int YC = MTL / YROWS;                            // passes (8)
-    const int yc_row = tid / CPR, yc_c = tid % CPR;
-    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
-    const __amdgpu_buffer_rsrc_t ycrs =
-        __builtin_amdgcn_make_buffer_rsrc(Y + urow * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
-    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
-    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
-    auto yc_write = [&](int j, int tp, u32x4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, SAUX);
-    };
+    const YCopy<ROWD, MTL, 0> yc(Y, ldy, b0, T, dir, tid);
+    constexpr int YC = decltype(yc)::YC;
 
     // gate-phase h write: element (row, col = 32u + li) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2,
     // lo half 16 bytes later: two 16-bit stores from the lane's own pair (h2_store16).
     const int hcol = 32 * u + li;
     unsigned short* hl_dst = reinterpret_cast<unsigned short*>(lds + 4 * hf * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
-    const bool odd = li & 1;
 
     // The weights do not depend on the step: the B fragments of k step 0 are requested during the last
     // k step of the previous time step and fly under the gate phase (ring[0].b stays live across it).
@@ -221,8 +219,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
         for (int m = 0; m < MTILES; ++m)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) seed_chunk(m, qd, t0);
-        x_load(t0);
-        x_store();
         load_b(0, ring[0]);
     }
     __syncthreads();
@@ -233,28 +229,23 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
         if (stamp) dbg[(u * 80 + 2 * step) * 2] = __builtin_amdgcn_s_memtime();
         // ---------------- MFMA phase ----------------
         {
-            load_a(0, ring[0], t);
+            load_a(0, ring[0]);
             const int tp = step > 0 ? (dir ? t + 1 : t - 1) : t;   // time index of h_{s-1} (step 0: zeros, rewritten later)
             u32x4 ycv = {0, 0, 0, 0};
 #pragma unroll
             for (int s = 0; s < KS; ++s) {
                 const int p = s & 1;
-                if (s + 1 < KS) { load_b(s + 1, ring[p ^ 1]); load_a(s + 1, ring[p ^ 1], t); }
+                if (s + 1 < KS) { load_b(s + 1, ring[p ^ 1]); load_a(s + 1, ring[p ^ 1]); }
                 else load_b(0, ring[p ^ 1]);            // KS is even: ring[p ^ 1] == ring[0]
-                if (s >= 1 && s <= YC) yc_write(s - 1, tp, ycv);
-                if (s < YC) ycv = yc_read(s);
+                if (s >= 1 && s <= YC) yc.write(s - 1, tp, ycv);
+                if (s < YC) ycv = yc.read(s);
 #pragma unroll
-                for (int term = 0; term < 3; ++term) {
-                    // int8 summaries are exact in the hi half: their lo half is identically zero, so is lo(a) * hi(w)
-                    if (XI8 && s >= KSH && term == 0) continue;
-                    const bool fresh = KX && s == 0 && term == 0;       // accumulators start from the inline constant 0
+                for (int term = 0; term < 3; ++term)
 #pragma unroll
                     for (int g = 0; g < 4; ++g)
 #pragma unroll
                         for (int m = 0; m < MTILES; ++m)
-                            acc[m][g] = mfma_h(ring[p].a[m][term == 0 ? 1 : 0], ring[p].b[g][term == 1 ? 1 : 0],
-                                               fresh ? f32x16{} : acc[m][g]);
-                }
+                            acc[m][g] = mfma_h(ring[p].a[m][term == 0 ? 1 : 0], ring[p].b[g][term == 1 ? 1 : 0], acc[m][g]);
                 if (MTILES == 1 && s + 1 < KS) {
                     // 12 MFMAs per k step: 8 weight fragments, 2 A fragments, the y copy's read / write in the first steps
 #pragma unroll
@@ -313,70 +304,94 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        // the lane's four biases, re-read every step (in flight across the barrier) rather than held through the MFMA phase
-        float cb[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (KX && !BC) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-                cb[g] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xoff, (unsigned)(g * H) * 4u, 0));
-        }
         if (stamp) dbg[(u * 80 + 2 * step) * 2 + 1] = __builtin_amdgcn_s_memtime();
 
         lds_barrier();                    // every wave has finished reading h_{t-1}
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2] = __builtin_amdgcn_s_memtime();
 
         // ---------------- gate phase ----------------
-        // (Starting a wave's gate math before the barrier, beside the other wave's MFMAs, was measured:
-        // the VALU / transcendental issue slows that MFMA stream by about what it hides.  The phase is
-        // transcendental-bound: 10 quarter-rate ops per element.)
         const int tn = dir ? t - 1 : t + 1;
-        if (step + 1 < T) x_load(tn);
 #pragma unroll
         for (int m = 0; m < MTILES; ++m)
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) {
 #pragma unroll
                 for (int e = 0; e < 4; e += 2) {
-                    // two elements per pass: the plain arithmetic is written on 2-vectors so it can issue as
-                    // packed f32 instructions (the matrix pipe is idle in this phase)
                     const int r = 4 * qd + e;
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const f32x2 one = {1.0f, 1.0f};
-                    f32x2 ai = {acc[m][0][r], acc[m][0][r + 1]}, af = {acc[m][1][r], acc[m][1][r + 1]},
-                          ag = {acc[m][2][r], acc[m][2][r + 1]}, ao = {acc[m][3][r], acc[m][3][r + 1]};
-                    if (KX && !BC) { ai += cb[0]; af += cb[1]; ag += cb[2]; ao += cb[3]; }
-                    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
-                    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
-                    const f32x2 ig = rcp(one + ex2(ai));
-                    const f32x2 fg = rcp(one + ex2(af));
-                    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
-                    const f32x2 og = rcp(one + ex2(ao));
-                    const f32x2 cold = {cs[(m * 16 + r) * 64], cs[(m * 16 + r + 1) * 64]};
-                    const f32x2 cn = fg * cold + ig * gg;
-                    cs[(m * 16 + r) * 64] = cn.x;
-                    cs[(m * 16 + r + 1) * 64] = cn.y;
-                    const f32x2 hv2 = og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
+                    const f32x2 ai = {acc[m][0][r], acc[m][0][r + 1]}, af = {acc[m][1][r], acc[m][1][r + 1]},
+                                ag = {acc[m][2][r], acc[m][2][r + 1]}, ao = {acc[m][3][r], acc[m][3][r + 1]};
+                    const f32x2 hv2 = lstm_gate_pair(ai, af, ag, ao, cs + (m * 16 + r) * 64);
 #pragma unroll
-                    for (int k = 0; k < 2; ++k) {
-                        const float hv = k ? hv2.y : hv2.x;
-                        h2_store16(hl_dst + (32 * m + ((r + k) & 3) + 8 * ((r + k) >> 2)) * ROWD * 2, hv);
-                    }
+                    for (int k = 0; k < 2; ++k)
+                        h2_store16(hl_dst + (32 * m + ((r + k) & 3) + 8 * ((r + k) >> 2)) * ROWD * 2, k ? hv2.y : hv2.x);
                 }
                 if (step + 1 < T) seed_chunk(m, qd, tn);
             }
-        if (step + 1 < T) x_store();
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
-        lds_barrier();                    // h_t (and x_{t+1}) visible
+        lds_barrier();                    // h_t visible
     }
     {
         const int tl = dir ? 0 : T - 1;
 #pragma unroll
-        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
+        for (int j = 0; j < YC; ++j) yc.write(j, tl, yc.read(j));
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// The fused decoder's step loop: lstm_rec_h2_kernel's decomposition (workgroup = 64 or 32 batch rows x one direction, wave u
+// What the two 16x16x32 step loops below share.  Tiles: a wave's rows x 128 outputs are acc[row tile of 16][gate][column tile
+// of 16] (f32x4: lane l holds column l & 15 = lr, rows 4 (l >> 4) + r = 4 lq + r); i, f, g, o of one (row, unit) share lane and
+// register index, so the gate phase stays lane-local.
+
+// fragment (g, column tile c, k step s, hi/lo) of this wave: byte ((((g * 16 + 2u + c) * KS + s) * 2 + hl) * 1024 + lane * 16
+// of the direction's block (dec_frag16.h); the wave's own term is part of the descriptor's base (lstm_seed_h2_kernel says why)
+template <int KS>
+PA_DEV __amdgpu_buffer_rsrc_t frag16_rsrc(const uint32_t* Wp, int dir, int u) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * 16) + 2 * u) * KS * 512), 0, 0x7fffffff,
+                                             0x00020000);
+}
+// B fragment idx (in the order the MFMAs first need them) of k step s into stage gp of
+// b[stage = gate pair][gate of the pair][column tile][hi, lo]; woff = lane * 16
+template <int KS>
+PA_DEV void load_b16(h8 (&b)[2][2][2][2], __amdgpu_buffer_rsrc_t wrs, unsigned woff, int s, int gp, int idx) {
+    const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
+    b[gp][g2][c][hl] = __builtin_bit_cast(
+        h8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * KS + s) * 2 + hl) * 1024u, 0));
+}
+// the lane's eight biases [gate][column tile], re-read every step (in flight across the barrier) rather than held through the
+// MFMA phase
+PA_DEV __amdgpu_buffer_rsrc_t bias16_rsrc(const float* bias, int dir, int u) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias + dir * 4 * 256 + 32 * u), 0, 0x7fffffff, 0x00020000);
+}
+PA_DEV void load_bias16(float (&cb)[4][2], __amdgpu_buffer_rsrc_t brs, int lr) {
+#pragma unroll
+    for (int g = 0; g < 4; ++g)
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            cb[g][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, lr * 4u, (unsigned)(g * 256 + 16 * c) * 4u, 0));
+}
+// gate-phase h write: element (row, col) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2, lo half 16 bytes later
+// (h2_store16); the lane's element (m, c, r) is row 16m + 4 lq + r, col 32u + 16c + lr.  hcol = 32u + lr
+template <int ROWD>
+PA_DEV unsigned short* hl_dst16(int hcol, int lq) {
+    return reinterpret_cast<unsigned short*>(lds + 4 * lq * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
+}
+// the gate phase of one 16x16 tile on this (row, column) <-> (lane, register) map: the lane's four rows of i, f, g, o, the
+// tile's c slots and h destination.  ADD_BIAS: the accumulators still lack the lane's biases b4 = (b_i, b_f, b_g, b_o).
+// The accumulators come by value, not as acc[RT][4][2] by reference (profiles/lstm_step_loop_entries_isa.txt).
+template <int ROWD, bool ADD_BIAS>
+PA_DEV void gate_tile16(f32x4 i4, f32x4 f4, f32x4 g4, f32x4 o4, f32x4 b4, float* cs, unsigned short* dst) {
+#pragma unroll
+    for (int e = 0; e < 4; e += 2) {
+        f32x2 ai = {i4[e], i4[e + 1]}, af = {f4[e], f4[e + 1]}, ag = {g4[e], g4[e + 1]}, ao = {o4[e], o4[e + 1]};
+        if (ADD_BIAS) { ai += b4[0]; af += b4[1]; ag += b4[2]; ao += b4[3]; }
+        const f32x2 hv2 = lstm_gate_pair(ai, af, ag, ao, cs + e * 64);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) h2_store16(dst + (e + k) * ROWD * 2, k ? hv2.y : hv2.x);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The fused decoder's step loop: lstm_seed_h2_kernel's decomposition (workgroup = 64 or 32 batch rows x one direction, wave u
 // owns hidden units [32u, 32u+32) of all four gates, MFMA phase | barrier | gate phase | barrier), the same h2 row image in
 // LDS (so the same y), the same three-term product (lo.hi, hi.lo, hi.hi per k step, k ascending per accumulator) -- on
 // v_mfma_f32_16x16x32_f16.  The chip holds a higher clock on that shape (tools/microbench/mfma_shape.hip,
@@ -390,8 +405,6 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 // streams (x slab loads, y stores) carry the nt cache policy: the XCD's L2 has to keep this direction's 3 MB of weight
 // fragments, which every workgroup re-reads every step.
 //
-// Tiles: a wave's 64 x 128 outputs are acc[row tile of 16][gate][column tile of 16] (f32x4: lane l holds column l & 15, rows
-// 4 (l >> 4) + r); i, f, g, o of one (row, unit) share lane and register index, so the gate phase stays lane-local.
 // k steps: 32 wide, 8 for h and 16 for x.  A lane's A chunk is the 16-byte hi (then lo) slot at s * 128 + (l >> 4) * 32 of
 // its row; sixteen rows at odd 16-byte strides (65 slots per h row, 9 per ring row) keep ds_read_b128 conflict-free.
 // Registers: 128 accumulators, the A fragments of one k step (single-buffered: a row tile's are re-read for the next k step
@@ -403,7 +416,7 @@ __global__ __launch_bounds__(H / 32 * 64, 1) void lstm_rec_h2_kernel(const float
 // Ring schedule (iteration j = k step 8 + j): loaded into the one staging register early in the second phase of step j + 6
 // (93 MFMAs before it is needed), written to slot j & 1 at the end of the first phase of step j + 7, published by the barrier
 // that opens the second phase of that step, whose A re-reads are the first to touch it.  16 barriers per time step.
-// MTILES = 1 is the small-call schedule (32-row workgroups, lstm_rec_h2_kernel explains why); both come from this one
+// MTILES = 1 is the small-call schedule (32-row workgroups); both come from this one
 // template, so a row's chain of products and sums is the same in both.
 // what a k step does beside its MFMAs and its B loads: FRESH the first products start the accumulators; Y (Y2) a y copy pass
 // (and the last pass); XR the ring work: 0 nothing, 1 load the first iteration, 2 write the staged iteration, which this
@@ -415,14 +428,12 @@ struct DecStep {
 };
 
 template <int MTILES>
-PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
-                             int B, int T, unsigned long long* __restrict__ dbg, const uint32_t* __restrict__ Xh, int ldxh) {
-    constexpr int H = 256, KX = 512, KS = (H + KX) / 32, KSH = H / 32, NW = H / 32, SAUX = 2;
-    constexpr int MTL = 32 * MTILES, RT = 2 * MTILES;   // rows, row tiles of 16
-    static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
-    constexpr int ROWB = H * 4 + 16, ROWD = ROWB / 4;   // bytes per LDS row: h2 image of h + 16 pad (odd 16-B count)
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, c (f32), x ring
-    static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
+PA_DEV void lstm_dec_h2_body(const uint32_t* __restrict__ Xh, int ldxh, const float* __restrict__ bias,
+                             const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy, int B, int T,
+                             unsigned long long* __restrict__ dbg) {
+    using L = DecLds<MTILES>;
+    constexpr int H = 256, KX = 512, KS = (H + KX) / 32, KSH = H / 32, SAUX = 2;
+    constexpr int MTL = L::MTL, RT = 2 * MTILES, ROWD = L::ROWD, XRD = L::XRD, XSLOT = L::XSLOT;   // rows, row tiles of 16
 
     int dir, btile;
     decode_block(blockIdx.x, dir, btile);
@@ -432,21 +443,14 @@ PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __r
     const int tid = threadIdx.x, lane = tid & 63;
     const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
-
-    float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][column tile][r][lane]
-    for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
-    constexpr int XRD = 36, XSLOT = MTL * XRD;           // ring: 2 slots x [MTL rows][128 B of x + 16 B pad]
-    uint32_t* xring = lds + MTL * ROWD + NW * MTILES * 16 * 64;
+    float* cs = L::c_slots(u, lane);                     // [wave][m][column tile][r][lane]
+    L::clear(tid);
+    uint32_t* xring = lds + L::RING;                     // 2 slots x [MTL rows][XRD]
 
     f32x4 acc[RT][4][2];   // [row tile][gate][column tile]
 
-    const size_t urow = (size_t)b0 * T;
-    const __amdgpu_buffer_rsrc_t brs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias + dir * 4 * H + 32 * u), 0, 0x7fffffff, 0x00020000);
-    // fragment (g, column tile c, k step s, hi/lo) of this wave: byte ((((g * 16 + 2u + c) * KS + s) * 2 + hl) * 1024 + lane * 16
-    // of the direction's block (dec_frag16.h); the wave's own term is part of the descriptor's base
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * 16) + 2 * u) * KS * 512), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs = bias16_rsrc(bias, dir, u);
+    const __amdgpu_buffer_rsrc_t wrs = frag16_rsrc<KS>(Wp, dir, u);
     const unsigned woff = lane * 16u;
 
     // x staging: thread -> (row = tid / 8, 16-byte chunk tid % 8) of an iteration's MTL x 128 B slab.  With 32 rows only
@@ -471,34 +475,15 @@ PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __r
     h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
     const uint32_t* arow = lds + lr * ROWD + lq * 8;
     const uint32_t* xrow = xring + lr * XRD + lq * 8;
-    auto load_b = [&](int s, int gp, int idx) {      // idx: in the order the MFMAs first need them
-        const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
-        b[gp][g2][c][hl] = __builtin_bit_cast(
-            h8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * KS + s) * 2 + hl) * 1024u, 0));
-    };
+    auto load_b = [&](int s, int gp, int idx) { load_b16<KS>(b, wrs, woff, s, gp, idx); };
     auto load_a_h = [&](int s, int m, int hl) { a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * ROWD + s * 32 + hl * 4); };
     auto load_a_x = [&](int slot, int m, int hl) {
         a[m][hl] = *reinterpret_cast<const h8*>(xrow + slot * XSLOT + m * 16 * XRD + hl * 4);
     };
 
-    // y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is
-    constexpr int CPR = H / 4;                                // 16-byte chunks per row
-    constexpr int YROWS = (NW * 64) / CPR;                    // rows per pass (8)
-    constexpr int YC = MTL / YROWS;                           // passes (8 or 4): one per k step from step 0
-    const int yc_row = tid / CPR, yc_c = tid % CPR;
-    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
-    const __amdgpu_buffer_rsrc_t ycrs =
-        __builtin_amdgcn_make_buffer_rsrc(Y + urow * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
-    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
-    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
-    auto yc_write = [&](int j, int tp, u32x4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, SAUX);
-    };
-
-    // gate-phase h write: element (row, col) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2, lo half 16 bytes later
-    // (h2_store16); the lane's element (m, c, r) is row 16m + 4 lq + r, col 32u + 16c + lr
-    const int hcol = 32 * u + lr;
-    unsigned short* hl_dst = reinterpret_cast<unsigned short*>(lds + 4 * lq * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
+    const YCopy<ROWD, MTL, SAUX> yc(Y, ldy, b0, T, dir, tid);
+    constexpr int YC = decltype(yc)::YC;                        // passes (8 or 4): one per k step from step 0
+    unsigned short* hl_dst = hl_dst16<ROWD>(32 * u + lr, lq);
 
     // The weights do not depend on the step: the first stage of k step 0 is requested during the last k step of the
     // previous time step and flies under the gate phase (b[0] stays live across it).
@@ -538,12 +523,12 @@ PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __r
                             else load_a_x(slot, m, i % 12 == 9 ? 1 : 0);
                         }
                         if (C::Y && i == NM / 2 + 1) {
-                            if (gp == 0) ycv = yc_read(s);
-                            else yc_write(s, tp, ycv);
+                            if (gp == 0) ycv = yc.read(s);
+                            else yc.write(s, tp, ycv);
                         }
                         if (C::Y2 && i == NM / 2 + 4) {
-                            if (gp == 0) ycv2 = yc_read(YC - 1);
-                            else yc_write(YC - 1, tp, ycv2);
+                            if (gp == 0) ycv2 = yc.read(YC - 1);
+                            else yc.write(YC - 1, tp, ycv2);
                         }
                         if (C::XR == 2 && gp == 0 && i == NM - 1) xg_store(slot);
                         // (the last step of the ring has nothing left to load: it loads the last iteration again)
@@ -573,77 +558,52 @@ PA_DEV void lstm_dec_h2_body(const float* __restrict__ bias, const uint32_t* __r
 #pragma unroll 1
             for (int r = 0; r < once; ++r) kstep(KS - 1, DecStep<false, false, false, 0, 0>{});
         }
-        // the lane's eight biases, re-read every step (in flight across the barrier) rather than held through the MFMA phase
         float cb[4][2];
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-#pragma unroll
-            for (int c = 0; c < 2; ++c)
-                cb[g][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, lr * 4u, (unsigned)(g * H + 16 * c) * 4u, 0));
+        load_bias16(cb, brs, lr);
         if (stamp) dbg[(u * 80 + 2 * step) * 2 + 1] = __builtin_amdgcn_s_memtime();
 
         lds_barrier();                    // every wave has finished reading h_{t-1}
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2] = __builtin_amdgcn_s_memtime();
 
-        // ---------------- gate phase (lstm_rec_h2_kernel's, on this kernel's (row, column) <-> (lane, register) map) ----------------
+        // ---------------- gate phase ----------------
 #pragma unroll
         for (int m = 0; m < RT; ++m)
 #pragma unroll
             for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const f32x2 one = {1.0f, 1.0f};
-                    f32x2 ai = {acc[m][0][c][e], acc[m][0][c][e + 1]}, af = {acc[m][1][c][e], acc[m][1][c][e + 1]},
-                          ag = {acc[m][2][c][e], acc[m][2][c][e + 1]}, ao = {acc[m][3][c][e], acc[m][3][c][e + 1]};
-                    ai += cb[0][c]; af += cb[1][c]; ag += cb[2][c]; ao += cb[3][c];
-                    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
-                    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
-                    const f32x2 ig = rcp(one + ex2(ai));
-                    const f32x2 fg = rcp(one + ex2(af));
-                    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
-                    const f32x2 og = rcp(one + ex2(ao));
-                    const int ci = (m * 8 + c * 4 + e) * 64;
-                    const f32x2 cold = {cs[ci], cs[ci + 64]};
-                    const f32x2 cn = fg * cold + ig * gg;
-                    cs[ci] = cn.x;
-                    cs[ci + 64] = cn.y;
-                    const f32x2 hv2 = og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) h2_store16(hl_dst + (16 * m + e + k) * ROWD * 2 + c * 32, k ? hv2.y : hv2.x);
-                }
+                gate_tile16<ROWD, true>(acc[m][0][c], acc[m][1][c], acc[m][2][c], acc[m][3][c], f32x4{cb[0][c], cb[1][c], cb[2][c], cb[3][c]},
+                                        cs + (m * 8 + c * 4) * 64, hl_dst + 16 * m * ROWD * 2 + c * 32);
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
         lds_barrier();                    // h_t visible
     }
     {
         const int tl = dir ? 0 : T - 1;
 #pragma unroll
-        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
+        for (int j = 0; j < YC; ++j) yc.write(j, tl, yc.read(j));
     }
 }
 
 // ------------------------------------------------------------------------------------------------
 // The fused int8 encoder's step loop (KX = 32: the first layer, whose input x_t is int8 features Xi [B*T, F], F <= 32), the
-// sibling of lstm_dec_h2_body on v_mfma_f32_16x16x32_f16: same decomposition, same tiles (acc[row tile of 16][gate][column
-// tile of 16], lane l = column l & 15, rows 4 (l >> 4) + r), same B ring of two gate-pair stages, same single-buffered A
+// sibling of lstm_dec_h2_kernel on v_mfma_f32_16x16x32_f16: same decomposition, same tiles, same B ring of two gate-pair
+// stages, same single-buffered A
 // fragments re-read right after their last use, same lane-local gate phase, every memory instruction alone in an MFMA gap,
 // the k loop a loop over one-k-step bodies (profiles/mfma_shape_probe.txt, the `enc` rows, is the probe that preceded it).
 // What differs: x is no ring.  The LDS row is the h2 image of [h | x] (288 units + 16 B pad = 1168 B, 73 16-byte slots: odd);
 // the gate phase converts the next step's int8 row and stores it beside h (hi halves; the lo halves stay zero; with BC the
 // constant 1.0 in column H + F, where the packed weights hold the bias), so the x columns are the ninth k step of the same
 // row.  That step issues two terms per product (x_hi.w_lo, x_hi.w_hi): the lo half of an int8 value is identically zero.
-// Nine k steps of 32 per time step, k ascending per accumulator: eight over h (three terms), one over x (the first time
-// step: the x step alone, PA_ENC_SKIP0 below).  The first stage of k step 0 is requested during the x step of the previous time
-// step and flies under the gate phase.
+// Nine k steps of 32 per time step, k ascending per accumulator: eight over h (three terms), one over x.  At the first time
+// step h is all zeros -- the eight h k steps would add exact zeros to accumulators that start from +0 -- so that step runs
+// the x step alone, with fresh accumulators, and no y copy (what the copy would write there, zeros, is rewritten one step
+// later anyway): same bits as running them.  The first stage of k step 0 is requested during the x step of the previous
+// time step and flies under the gate phase.
+// BC (F < KX): the bias lives in column H + F of the packed weights and x carries a constant 1.0 there, so the first MFMA of
+// a step starts every accumulator from the inline constant 0 and the matrix pipe adds the bias: no bias loads and no 128
+// register moves per step in the gate phase, which is bound by VALU issue (two waves per SIMD, ~1300 instructions each).
+// Without BC (F = 32 leaves no column) the gate phase adds the lane's eight biases like the decoder's.
 // Weights: dec_frag16.h's order with nine k steps (pa_dec16::pack with the bias column).
 // what a k step does beside its MFMAs and its B loads: FRESH the first products start the accumulators; Y a y copy pass;
 // X the two-term x step; AN the next k step's A fragments: 0 none, 1 hi and lo of the h columns, 2 the hi half of the x columns
-// PA_ENC_SKIP0 (build switch, 1 unless a build defines it 0): at the first time step h is all zeros -- the eight h k steps
-// would add exact zeros to accumulators that start from +0 -- so that step runs the x step alone, with fresh accumulators,
-// and no y copy (what the copy would write there, zeros, is rewritten one step later anyway).  Same bits either way.
-#ifndef PA_ENC_SKIP0
-#define PA_ENC_SKIP0 1
-#endif
 template <bool FRESH_, bool Y_, bool X_, int AN_>
 struct EncStep {
     static constexpr bool FRESH = FRESH_, Y = Y_, X = X_;
@@ -654,11 +614,8 @@ template <int MTILES, bool BC>
 PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* __restrict__ bias, const uint32_t* __restrict__ Wp,
                              uint32_t* __restrict__ Y, int ldy, int B, int T, unsigned long long* __restrict__ dbg) {
     constexpr int H = 256, KX = 32, KS = (H + KX) / 32, KSH = H / 32, NW = H / 32, SAUX = 2;
-    constexpr int MTL = 32 * MTILES, RT = 2 * MTILES;   // rows, row tiles of 16
-    static_assert(MTILES == 1 || MTILES == 2, "32 or 64 rows per workgroup");
-    constexpr int ROWB = (H + KX) * 4 + 16, ROWD = ROWB / 4;   // bytes per LDS row: h2 image of [h | x] + 16 pad (odd 16-B count)
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTL][ROWD] h2 rows, then c (f32)
-    static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
+    using L = EncLds<MTILES>;
+    constexpr int MTL = L::MTL, RT = 2 * MTILES, ROWD = L::ROWD;   // rows, row tiles of 16
 
     int dir, btile;
     decode_block(blockIdx.x, dir, btile);
@@ -668,19 +625,13 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
     const int tid = threadIdx.x, lane = tid & 63;
     const int u = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lr = lane & 15, lq = lane >> 4;
-
-    float* cs = reinterpret_cast<float*>(lds + MTL * ROWD) + u * (MTILES * 16 * 64) + lane;     // [wave][m][column tile][r][lane]
-    for (int idx = tid; idx < MTL * ROWD + NW * MTILES * 16 * 64; idx += blockDim.x) lds[idx] = 0u;
+    float* cs = L::c_slots(u, lane);                     // [wave][m][column tile][r][lane]
+    L::clear(tid);
 
     f32x4 acc[RT][4][2];   // [row tile][gate][column tile]
 
-    const size_t urow = (size_t)b0 * T;
-    const __amdgpu_buffer_rsrc_t brs =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(bias + dir * 4 * H + 32 * u), 0, 0x7fffffff, 0x00020000);
-    // fragment (g, column tile c, k step s, hi/lo) of this wave: byte ((((g * 16 + 2u + c) * KS + s) * 2 + hl) * 1024 + lane * 16
-    // of the direction's block (dec_frag16.h); the wave's own term is part of the descriptor's base
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<uint32_t*>(Wp + ((size_t)dir * (4 * 16) + 2 * u) * KS * 512), 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t brs = bias16_rsrc(bias, dir, u);
+    const __amdgpu_buffer_rsrc_t wrs = frag16_rsrc<KS>(Wp, dir, u);
     const unsigned woff = lane * 16u;
 
     // x_t (int8, exact in f16) -> hi halves of LDS columns [H, H+KX); lo halves stay 0.
@@ -715,32 +666,13 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
     h8 a[RT][2];            // [row tile][hi, lo] of the current k step
     h8 b[2][2][2][2];       // [stage = gate pair][gate of the pair][column tile][hi, lo]
     const uint32_t* arow = lds + lr * ROWD + lq * 8;
-    auto load_b = [&](int s, int gp, int idx) {      // idx: in the order the MFMAs first need them
-        const int c = idx >> 2, hl = (idx >> 1) & 1, g2 = idx & 1;
-        b[gp][g2][c][hl] = __builtin_bit_cast(
-            h8, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, (unsigned)((((2 * gp + g2) * 16 + c) * KS + s) * 2 + hl) * 1024u, 0));
-    };
+    auto load_b = [&](int s, int gp, int idx) { load_b16<KS>(b, wrs, woff, s, gp, idx); };
     auto load_a = [&](int s, int m, int hl) { a[m][hl] = *reinterpret_cast<const h8*>(arow + m * 16 * ROWD + s * 32 + hl * 4); };
 
-    // y copy: the h part of the LDS rows (H * 4 bytes = H/4 16-byte chunks per row) -> Y, as is
-    constexpr int CPR = H / 4;                                // 16-byte chunks per row
-    constexpr int YROWS = (NW * 64) / CPR;                    // rows per pass (8)
-    constexpr int YC = MTL / YROWS;                           // passes (8 or 4): one per k step from step 0
+    const YCopy<ROWD, MTL, SAUX> yc(Y, ldy, b0, T, dir, tid);
+    constexpr int YC = decltype(yc)::YC;                        // passes (8 or 4): one per k step from step 0
     static_assert(YC <= KSH, "one y copy pass per h k step");
-    const int yc_row = tid / CPR, yc_c = tid % CPR;
-    const uint32_t* yc_src = lds + yc_row * ROWD + yc_c * 4;
-    const __amdgpu_buffer_rsrc_t ycrs =
-        __builtin_amdgcn_make_buffer_rsrc(Y + urow * ldy + dir * H, 0, 0x7fffffff, 0x00020000);
-    const unsigned yc_off = ((unsigned)(yc_row * T) * ldy + yc_c * 4) * 4u;
-    auto yc_read = [&](int j) { return *reinterpret_cast<const u32x4*>(yc_src + j * YROWS * ROWD); };
-    auto yc_write = [&](int j, int tp, u32x4 v) {
-        __builtin_amdgcn_raw_buffer_store_b128(v, ycrs, yc_off, ((unsigned)(j * YROWS * T + tp) * ldy) * 4u, SAUX);
-    };
-
-    // gate-phase h write: element (row, col) -> hi half at row*ROWB + (col/8)*32 + (col%8)*2, lo half 16 bytes later
-    // (h2_store16); the lane's element (m, c, r) is row 16m + 4 lq + r, col 32u + 16c + lr
-    const int hcol = 32 * u + lr;
-    unsigned short* hl_dst = reinterpret_cast<unsigned short*>(lds + 4 * lq * ROWD + (hcol >> 3) * 8 + ((hcol & 7) >> 1)) + (hcol & 1);
+    unsigned short* hl_dst = hl_dst16<ROWD>(32 * u + lr, lq);
 
     // The weights do not depend on the step: the first stage of k step 0 is requested during the x step of the previous time
     // step and flies under the gate phase (b[0] stays live across it).
@@ -749,7 +681,7 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
         x_load(dir ? T - 1 : 0);
         x_store();
 #pragma unroll
-        for (int i = 0; i < 8; ++i) load_b(PA_ENC_SKIP0 ? KS - 1 : 0, 0, i);   // the first time step starts at the x step
+        for (int i = 0; i < 8; ++i) load_b(KS - 1, 0, i);   // the first time step starts at the x step
     }
     __syncthreads();
 
@@ -787,8 +719,8 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
                         if (!C::X && gp == 1 && C::AN == 1 && i % 12 == 9) load_a(sn, m, 1);
                         if (!C::X && gp == 1 && C::AN != 0 && i % 12 == 11) load_a(sn, m, 0);
                         if (C::Y && i == NM / 2 + 1) {
-                            if (gp == 0) ycv = yc_read(s);
-                            else yc_write(s, tp, ycv);
+                            if (gp == 0) ycv = yc.read(s);
+                            else yc.write(s, tp, ycv);
                         }
                         __builtin_amdgcn_sched_barrier(0);
                     }
@@ -799,7 +731,7 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
             // One straight sequence of loops whatever the step (a branch around the bodies makes the compiler rename the
             // accumulators between its arms, and spill): at the first time step the h bodies make no trip and the x step is
             // the fresh one.
-            const int hrun = PA_ENC_SKIP0 && step == 0 ? 0 : once;
+            const int hrun = step == 0 ? 0 : once;
 #pragma unroll
             for (int i = 0; i < 2 * RT; ++i) load_a(0, i >> 1, i & 1);
             __builtin_amdgcn_sched_barrier(0);
@@ -815,60 +747,31 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
             for (int r = 0; r < hrun; ++r) kstep(KSH - 1, EncStep<false, (YC >= KSH), false, 2>{});
 #pragma unroll 1
             for (int r = 0; r < hrun; ++r) kstep(KS - 1, EncStep<false, false, true, 0>{});
-            if (PA_ENC_SKIP0) {
 #pragma unroll 1
-                for (int r = hrun; r < once; ++r) {
-                    // h_{-1} = 0: only the x step, on fresh accumulators
+            for (int r = hrun; r < once; ++r) {
+                // h_{-1} = 0: only the x step, on fresh accumulators
 #pragma unroll
-                    for (int m = 0; m < RT; ++m) load_a(KSH, m, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    kstep(KS - 1, EncStep<true, false, true, 0>{});
-                }
+                for (int m = 0; m < RT; ++m) load_a(KSH, m, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                kstep(KS - 1, EncStep<true, false, true, 0>{});
             }
         }
-        // !BC: the lane's eight biases, re-read every step (in flight across the barrier) rather than held through the MFMA phase
         float cb[4][2] = {};
-        if (!BC) {
-#pragma unroll
-            for (int g = 0; g < 4; ++g)
-#pragma unroll
-                for (int c = 0; c < 2; ++c)
-                    cb[g][c] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(brs, lr * 4u, (unsigned)(g * H + 16 * c) * 4u, 0));
-        }
+        if (!BC) load_bias16(cb, brs, lr);
         if (stamp) dbg[(u * 80 + 2 * step) * 2 + 1] = __builtin_amdgcn_s_memtime();
 
         lds_barrier();                    // every wave has finished reading h_{t-1} and x_t
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2] = __builtin_amdgcn_s_memtime();
 
-        // ---------------- gate phase (lstm_dec_h2_body's) ----------------
+        // ---------------- gate phase ----------------
         const int tn = dir ? t - 1 : t + 1;
         if (step + 1 < T) x_load(tn);
 #pragma unroll
         for (int m = 0; m < RT; ++m)
 #pragma unroll
             for (int c = 0; c < 2; ++c)
-#pragma unroll
-                for (int e = 0; e < 4; e += 2) {
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    const f32x2 one = {1.0f, 1.0f};
-                    f32x2 ai = {acc[m][0][c][e], acc[m][0][c][e + 1]}, af = {acc[m][1][c][e], acc[m][1][c][e + 1]},
-                          ag = {acc[m][2][c][e], acc[m][2][c][e + 1]}, ao = {acc[m][3][c][e], acc[m][3][c][e + 1]};
-                    if (!BC) { ai += cb[0][c]; af += cb[1][c]; ag += cb[2][c]; ao += cb[3][c]; }
-                    auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
-                    auto rcp = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v.x), __builtin_amdgcn_rcpf(v.y)}; };
-                    const f32x2 ig = rcp(one + ex2(ai));
-                    const f32x2 fg = rcp(one + ex2(af));
-                    const f32x2 gg = one - 2.0f * rcp(one + ex2(ag));
-                    const f32x2 og = rcp(one + ex2(ao));
-                    const int ci = (m * 8 + c * 4 + e) * 64;
-                    const f32x2 cold = {cs[ci], cs[ci + 64]};
-                    const f32x2 cn = fg * cold + ig * gg;
-                    cs[ci] = cn.x;
-                    cs[ci + 64] = cn.y;
-                    const f32x2 hv2 = og * (one - 2.0f * rcp(one + ex2(cn * 2.8853900817779268f)));
-#pragma unroll
-                    for (int k = 0; k < 2; ++k) h2_store16(hl_dst + (16 * m + e + k) * ROWD * 2 + c * 32, k ? hv2.y : hv2.x);
-                }
+                gate_tile16<ROWD, !BC>(acc[m][0][c], acc[m][1][c], acc[m][2][c], acc[m][3][c], f32x4{cb[0][c], cb[1][c], cb[2][c], cb[3][c]},
+                                       cs + (m * 8 + c * 4) * 64, hl_dst + 16 * m * ROWD * 2 + c * 32);
         if (step + 1 < T) x_store();
         if (stamp) dbg[(u * 80 + 2 * step + 1) * 2 + 1] = __builtin_amdgcn_s_memtime();
         lds_barrier();                    // h_t (and x_{t+1}) visible
@@ -876,8 +779,23 @@ PA_DEV void lstm_enc_h2_body(const int8_t* __restrict__ Xi, int F, const float* 
     {
         const int tl = dir ? 0 : T - 1;
 #pragma unroll
-        for (int j = 0; j < YC; ++j) yc_write(j, tl, yc_read(j));
+        for (int j = 0; j < YC; ++j) yc.write(j, tl, yc.read(j));
     }
+}
+
+// The two 16x16x32 kernels.  Their loops stay force-inlined functions under these entries: written straight into a kernel
+// the same text schedules the gate phase differently (profiles/lstm_step_loop_entries_isa.txt).
+template <int MTILES>
+__global__ __launch_bounds__(512, 1) void lstm_dec_h2_kernel(const uint32_t* __restrict__ Xh, int ldxh, const float* __restrict__ bias,
+                                                             const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
+                                                             int B, int T, unsigned long long* __restrict__ dbg) {
+    lstm_dec_h2_body<MTILES>(Xh, ldxh, bias, Wp, Y, ldy, B, T, dbg);
+}
+template <int MTILES, bool BC>
+__global__ __launch_bounds__(512, 1) void lstm_enc_h2_kernel(const int8_t* __restrict__ Xi, int F, const float* __restrict__ bias,
+                                                             const uint32_t* __restrict__ Wp, uint32_t* __restrict__ Y, int ldy,
+                                                             int B, int T, unsigned long long* __restrict__ dbg) {
+    lstm_enc_h2_body<MTILES, BC>(Xi, F, bias, Wp, Y, ldy, B, T, dbg);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -909,7 +827,7 @@ __global__ __launch_bounds__(256, 1) void lstm_rec_h2_split_kernel(const float* 
     static_assert(H == 256 && (NTW == 1 || NTW == 2), "eight members of 32 units or four of 64");
     constexpr int KS = H / 16, NT = H / 32, K = NT / NTW;
     constexpr int ROWB = H * 4 + 16, ROWD = ROWB / 4;
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];      // [32][ROWD] h2 rows | gate buffer [4][NTW][16][64] f32 | flag
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];      // (the array above) [32][ROWD] h2 rows | gate buffer [4][NTW][16][64] f32 | flag
     float* gbuf = reinterpret_cast<float*>(lds + 32 * ROWD);
     uint32_t* flag = lds + 32 * ROWD + 4 * NTW * 16 * 64;
 
@@ -942,7 +860,7 @@ __global__ __launch_bounds__(256, 1) void lstm_rec_h2_split_kernel(const float* 
                                                               wrs, lane * 16u,
                                                               (unsigned)(((w * NT + member * NTW + j) * KS + s) * 2 + hl) * 1024u, 0));
     }
-    // accumulator seeds: the projection's tile (row tile, t, column tile ct, register chunk qd), as lstm_rec_h2_kernel reads it
+    // accumulator seeds: the projection's tile (row tile, t, column tile ct, register chunk qd), as lstm_seed_h2_kernel reads it
     const __amdgpu_buffer_rsrc_t xrs = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<float*>(Xp + (size_t)btile * T * (ldx >> 5) * 1024), 0, 0x7fffffff, 0x00020000);
     const unsigned ct0 = (unsigned)(dir * (4 * NT) + w * NT + member * NTW);
@@ -982,7 +900,7 @@ __global__ __launch_bounds__(256, 1) void lstm_rec_h2_split_kernel(const float* 
 
     for (int step = 0; step < T; ++step) {
         const int t = dir ? T - 1 - step : step;
-        // ---- contraction h_{t-1} W_hh^T of this wave's gate (three products per k step, lstm_rec_h2_kernel's order) ----
+        // ---- contraction h_{t-1} W_hh^T of this wave's gate (three products per k step, lstm_seed_h2_kernel's order) ----
         {
             h8 a0 = *reinterpret_cast<const h8*>(arow), a1 = *reinterpret_cast<const h8*>(arow + 4);
 #pragma unroll
@@ -1080,8 +998,8 @@ __global__ __launch_bounds__(256, 1) void lstm_rec_h2_split_kernel(const float* 
 // (and, when the uint8 input projection is fused, so has the input half).  h is carried exactly in f32
 // registers for the z * h_{t-1} term and the final state hand-off; the LDS / y image is its h2 split.
 //   /root/reference/pepper/modules/python/models/simple_model.py:30,32
-// XG: the layer input is an h2 layer output Xh [B*T, KX] streamed through a two-slot LDS ring exactly as in
-// lstm_rec_h2_kernel (two k steps = 128 rows x 128 B per slot, two 16-byte chunks per thread per iteration).
+// XG: the layer input is an h2 layer output Xh [B*T, KX] streamed through a two-slot LDS ring like
+// lstm_dec_h2_kernel's (here two k steps = 128 rows x 128 B per slot, two 16-byte chunks per thread per iteration).
 // DENSE (with XG; the polish model's last decoder layer): the layer output never leaves the workgroup.  Its only
 // consumer is dense1 (2H -> C classes, /root/reference/pepper/modules/python/models/simple_model.py:34), so while step
 // s+1 contracts, the h_s rows still in LDS are multiplied with this direction's half of dense1's weights on
@@ -1089,7 +1007,7 @@ __global__ __launch_bounds__(256, 1) void lstm_rec_h2_split_kernel(const float* 
 // MFMAs per step), the four k-quarter partials are summed through an LDS scratch behind a barrier the x ring needs
 // anyway, and 5 x 128 floats per step go to P[dir][batch tile][t][class][128 rows] (2.5 KB instead of the 128 KB of y).
 // polish_combine_kernel (head.hip) adds the two directions and the bias, takes the softmax and overlap-adds it.
-// BC: as in lstm_rec_h2_kernel, for the fused uint8 first layer with F < KX = 16: b_r, b_z and the input half of the n
+// BC: as in lstm_enc_h2_kernel, for the fused uint8 first layer with F < KX = 16: b_r, b_z and the input half of the n
 // gate's bias come out of the matrix pipe (bias column of the packed weights x constant 1.0 input); b_hn is added in the
 // gate phase.  No fused form seeds an accumulator (see seed_chunk below).
 template <int H, int KX, bool XG = false, int SAUX = 0, bool DENSE = false, bool BC = false>
@@ -1113,7 +1031,7 @@ __global__ __launch_bounds__(512, 1) void gru_rec_h2_kernel(const float* __restr
     constexpr int ROWB = KL * 4 + 16, ROWD = ROWB / 4;
     constexpr int XRD = 36, XSLOT = MTG * XRD, NXI = XG ? KX / 32 : 0;
     static_assert(!XG || KSH >= 7, "ring schedule needs KSH >= 7");
-    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // [MTG][ROWD] h2 rows of [h | x] (+ x ring when XG)
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];   // (the array above) [MTG][ROWD] h2 rows of [h | x] (+ x ring when XG)
     static_assert((ROWB / 16) % 2 == 1, "row stride must be an odd number of 16-byte slots");
 
     int dir, btile;
@@ -1218,7 +1136,7 @@ __global__ __launch_bounds__(512, 1) void gru_rec_h2_kernel(const float* __restr
         const unsigned so = (((unsigned)(m * T + t) * (ldx >> 5) + ct) * 4u + qd) * 1024u;
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xrs, xoff, so, 0));
     };
-    // packed h2 word of one element (see lstm_rec_h2_kernel)
+    // packed h2 word of one element (common.h)
 
     // exact f32 h_{t-1} of this lane's 32 elements (the z * h term and the final state).  The forms that sit at the
     // 256-register limit of two waves per SIMD keep the last HL of them in a per-wave private LDS strip [HL][64 lanes]
@@ -1397,7 +1315,7 @@ __global__ __launch_bounds__(512, 1) void gru_rec_h2_kernel(const float* __restr
             for (int s = 0; s < KS; ++s) {
                 const int p = s & 1;
                 if (XG) {
-                    // x ring schedule (see lstm_rec_h2_kernel): iteration j = k steps (KSH + 2j, KSH + 2j + 1) is loaded at
+                    // x ring schedule: iteration j = k steps (KSH + 2j, KSH + 2j + 1) is loaded at
                     // step KSH - 7 + 2j (j = 0, 1: steps 0, 1), stored at step KSH - 3 + 2j, published by the barrier at the
                     // start of step KSH - 1 + 2j
                     if (s == 0) xg_load(0, t);
@@ -1492,7 +1410,7 @@ __global__ __launch_bounds__(512, 1) void gru_rec_h2_kernel(const float* __restr
 #pragma unroll
                 for (int e = 0; e < 4; e += 2) {
                     // two elements per pass on 2-vectors, so the plain arithmetic issues as packed f32 instructions (as in
-                    // lstm_rec_h2_kernel); h' = n + z (h - n)
+                    // lstm_gate_pair); h' = n + z (h - n)
                     const int r = 4 * qd + e;
                     typedef float f32x2 __attribute__((ext_vector_type(2)));
                     auto ex2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v.x), __builtin_amdgcn_exp2f(v.y)}; };
@@ -1724,8 +1642,8 @@ __global__ __launch_bounds__(256, 1) void gru_small_h2_kernel(const float* __res
     }
 }
 
-inline int rec_grid(int B) {
-    const int nbt = (B + MT - 1) / MT;
+inline int rec_grid(int B, int rows = MT) {      // workgroups of a step loop with `rows` rows each (decode_block)
+    const int nbt = (B + rows - 1) / rows;
     return 2 * ((nbt + 3) / 4) * 4;
 }
 
@@ -1788,21 +1706,16 @@ hipError_t launch_lstm_dec_h2(int H, const void* Xh, int ldxh, const float* bias
                               int T, hipStream_t stream, bool small) {
     if (B <= 0) return hipSuccess;
     if (H != 256 || (ldy & 7) || (ldxh & 7) || ldxh < 512) return hipErrorInvalidValue;
-    if (small) {
+    if (small)
         // 32-row workgroups (MTILES = 1): a row's MFMA chain and gate arithmetic are those of the 64-row workgroup, the tile
         // just holds half the rows.  Xh / Y must hold the rows up to the next multiple of 32 (the workspace pads to 64).
-        const int nbt = (B + 31) / 32, grid1 = 2 * ((nbt + 3) / 4) * 4;
-        const size_t lds1 = (size_t)32 * (256 * 4 + 16) + (size_t)8 * 16 * 64 * 4 + (size_t)2 * 32 * 36 * 4;   // h + c + x ring
-        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, true, 2, false, 1>), dim3(grid1), dim3(512), lds1, stream,
-                           (const float*)nullptr, 0, (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp),
-                           static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr, static_cast<const uint32_t*>(Xh), ldxh);
-        return hipGetLastError();
-    }
-    const size_t lds = (size_t)MT * (256 * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4 + (size_t)2 * MT * 36 * 4;   // h + c + x ring
-    const int grid = rec_grid(B);
-    hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 512, true, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0,
-                       (const int8_t*)nullptr, 0, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
-                       debug_buffer(), static_cast<const uint32_t*>(Xh), ldxh);
+        hipLaunchKernelGGL((lstm_dec_h2_kernel<1>), dim3(rec_grid(B, 32)), dim3(512), DecLds<1>::BYTES, stream,
+                           static_cast<const uint32_t*>(Xh), ldxh, bias, static_cast<const uint32_t*>(Wp),
+                           static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL((lstm_dec_h2_kernel<2>), dim3(rec_grid(B)), dim3(512), DecLds<2>::BYTES, stream,
+                           static_cast<const uint32_t*>(Xh), ldxh, bias, static_cast<const uint32_t*>(Wp),
+                           static_cast<uint32_t*>(Y), ldy, B, T, debug_buffer());
     return hipGetLastError();
 }
 
@@ -1858,46 +1771,37 @@ hipError_t launch_lstm_rec_h2_split(int H, const float* Xp, int ldx, const void*
     return hipGetLastError();
 }
 
-hipError_t launch_lstm_rec_h2(int H, const float* Xp, int ldx, const int8_t* X, int F, const float* bias,
-                              const void* Wp, void* Y, int ldy, int B, int T, hipStream_t stream, bool small) {
+// small: 32-row workgroups for small calls (see MTILES): twice the workgroups, half the time per step
+hipError_t launch_lstm_seed_h2(int H, const float* Xp, int ldx, const void* Wp, void* Y, int ldy, int B, int T,
+                               hipStream_t stream, bool small) {
     if (B <= 0) return hipSuccess;
     if (H != 256 || (ldy & 7)) return hipErrorInvalidValue;
-    const int grid = rec_grid(B);
-    if (small) {
-        // 32-row workgroups for small calls (see the kernel's MTILES): twice the workgroups, half the time per step
-        const int nbt = (B + 31) / 32, grid1 = 2 * ((nbt + 3) / 4) * 4;
-        if (X != nullptr && F > 0 && F < 32) {
-            const size_t lds = (size_t)32 * ((256 + 32) * 4 + 16) + (size_t)8 * 16 * 64 * 4;
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2, true, 1>), dim3(grid1), dim3(512), lds, stream,
-                               (const float*)nullptr, 0, X, F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y),
-                               ldy, B, T, (unsigned long long*)nullptr);
-            return hipGetLastError();
-        }
-        if (X == nullptr) {
-            const size_t lds = (size_t)32 * (256 * 4 + 16) + (size_t)8 * 16 * 64 * 4;
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0, false, 0, false, 1>), dim3(grid1), dim3(512), lds, stream, Xp, ldx,
-                               (const int8_t*)nullptr, 0, (const float*)nullptr, static_cast<const uint32_t*>(Wp),
-                               static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr);
-            return hipGetLastError();
-        }
-    }
-    if (X != nullptr) {
-        if (F <= 0 || F > 32) return hipErrorInvalidValue;
-        const size_t lds = (size_t)MT * ((256 + 32) * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4;
-        if (F < 32)
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2, true>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
-                               F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
-                               debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
-        else
-            hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 32, false, 2>), dim3(grid), dim3(512), lds, stream, (const float*)nullptr, 0, X,
-                               F, bias, static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T,
-                               debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr);
-    } else {
-        const size_t lds = (size_t)MT * (256 * 4 + 16) + (size_t)8 * 2 * 16 * 64 * 4;
-        hipLaunchKernelGGL((lstm_rec_h2_kernel<256, 0>), dim3(grid), dim3(512), lds, stream, Xp, ldx,
-                           (const int8_t*)nullptr, 0, (const float*)nullptr, static_cast<const uint32_t*>(Wp),
-                           static_cast<uint32_t*>(Y), ldy, B, T, debug_buffer());
-    }
+    if (small)
+        hipLaunchKernelGGL((lstm_seed_h2_kernel<1>), dim3(rec_grid(B, 32)), dim3(512), SeedLds<1>::BYTES, stream, Xp, ldx,
+                           static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T, (unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL((lstm_seed_h2_kernel<2>), dim3(rec_grid(B)), dim3(512), SeedLds<2>::BYTES, stream, Xp, ldx,
+                           static_cast<const uint32_t*>(Wp), static_cast<uint32_t*>(Y), ldy, B, T, debug_buffer());
+    return hipGetLastError();
+}
+
+hipError_t launch_lstm_enc_h2(int H, const int8_t* X, int F, const float* bias, const void* Wp, void* Y, int ldy, int B, int T,
+                              hipStream_t stream, bool small) {
+    if (B <= 0) return hipSuccess;
+    if (H != 256 || (ldy & 7) || F <= 0 || F > 32) return hipErrorInvalidValue;
+    const uint32_t* W = static_cast<const uint32_t*>(Wp);
+    uint32_t* y = static_cast<uint32_t*>(Y);
+    unsigned long long* dbg = debug_buffer() ? debug_buffer() + 8 * 80 * 2 : nullptr;
+    // F = 32 leaves no input column for the bias and has no 32-row form: a small call takes the 64-row one
+    if (F == 32)
+        hipLaunchKernelGGL((lstm_enc_h2_kernel<2, false>), dim3(rec_grid(B)), dim3(512), EncLds<2>::BYTES, stream, X, F, bias,
+                           W, y, ldy, B, T, dbg);
+    else if (small)
+        hipLaunchKernelGGL((lstm_enc_h2_kernel<1, true>), dim3(rec_grid(B, 32)), dim3(512), EncLds<1>::BYTES, stream, X, F,
+                           bias, W, y, ldy, B, T, (unsigned long long*)nullptr);
+    else
+        hipLaunchKernelGGL((lstm_enc_h2_kernel<2, true>), dim3(rec_grid(B)), dim3(512), EncLds<2>::BYTES, stream, X, F, bias,
+                           W, y, ldy, B, T, dbg);
     return hipGetLastError();
 }
 

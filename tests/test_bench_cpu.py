@@ -94,6 +94,8 @@ def test_profiler_names_map_to_the_labels_the_bench_line_uses():
     spec.loader.exec_module(pmc)
     b = _bench()
     want = {
+        "void pa::(anonymous namespace)::lstm_dec_h2_kernel<2>(unsigned int const*, int)": "lstm_dec_h2_fused",
+        "void pa::(anonymous namespace)::lstm_enc_h2_kernel<2, true>(signed char const*, int)": "lstm_rec_h2_fused_in",
         "void pa::(anonymous namespace)::lstm_rec_h2_kernel<256, 512, true, 2, false, 2>(float const*, int)": "lstm_dec_h2_fused",
         "void pa::(anonymous namespace)::lstm_rec_h2_kernel<256, 32, false, 2, true, 2>(float const*)": "lstm_rec_h2_fused_in",
         "void pa::(anonymous namespace)::gru_rec_h2_kernel<128, 256, true, 2, true, false>(float const*)": "gru_dec_h2_fused_dense",

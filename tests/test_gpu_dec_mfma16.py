@@ -1,4 +1,4 @@
-"""The fused LSTM decoder on 16x16x32 MFMAs (rnn_h2.hip lstm_dec_h2_body, weights in the order of csrc/dec_frag16.h).
+"""The fused LSTM decoder on 16x16x32 MFMAs (rnn_h2.hip lstm_dec_h2_kernel, weights in the order of csrc/dec_frag16.h).
 
 Every model here is created with PA_SMALL_BATCH=0, so the decoder layer runs the fused step loop at every call size, and with
 PA_UNIT_SPLIT=0, so the encoder in front of it is the same kernel in every model of this file.
@@ -9,7 +9,7 @@ PA_UNIT_SPLIT=0, so the encoder in front of it is the same kernel in every model
    Largest error measured (MI355X), parent commit (32x32x16 decoder) -> this kernel:
        default-scale  64-row 9.19e-08 -> 7.59e-08   32-row 9.48e-08 -> 8.89e-08
        gain-2         64-row 1.38e-06 -> 1.33e-06   32-row 1.85e-06 -> 1.85e-06
-2. Against the unchanged decoder seeded from Xp (lstm_rec_h2_kernel<256, 0>, selected by a large PA_SMALL_BATCH): the same
+2. Against the unchanged decoder seeded from Xp (lstm_seed_h2_kernel, selected by a large PA_SMALL_BATCH): the same
    three-term arithmetic on 32x32x16 tiles.  The parent's fused form differs from the seeded form by 5.96e-08 (default-scale)
    and 1.19e-06 (gain-2) on these inputs (largest probability difference); twice that is allowed -- only the summation order
    inside an instruction changed.  Measured with this kernel: 5.96e-08 and 1.01e-06.

@@ -1,4 +1,4 @@
-"""The fused int8 LSTM encoder on 16x16x32 MFMAs (rnn_h2.hip lstm_enc_h2_body, weights in the order of csrc/dec_frag16.h with the
+"""The fused int8 LSTM encoder on 16x16x32 MFMAs (rnn_h2.hip lstm_enc_h2_kernel, weights in the order of csrc/dec_frag16.h with the
 bias column).
 
 Every model here is created with PA_UNIT_SPLIT=0 and PA_SMALL_BATCH=0: the first layer of an int8 call is the fused encoder at
@@ -12,7 +12,7 @@ encoder on 64-row workgroups; batch-invariant mode with the default PA_SMALL_ROW
        default-scale  64-row 8.85e-08 -> 8.67e-08   32-row 8.59e-08 -> 9.03e-08
        gain-2         64-row 1.15e-06 -> 1.20e-06   32-row 1.60e-06 -> 1.59e-06
 2. Against the unfused path: the same windows as f32 through the device entry point, whose first layer is the projection GEMM
-   and the unchanged step loop seeded from Xp (lstm_rec_h2_kernel<256, 0>, 32x32x16 tiles).  The parent's fused encoder
+   and the unchanged step loop seeded from Xp (lstm_seed_h2_kernel, 32x32x16 tiles).  The parent's fused encoder
    differs from that path by 5.96e-08 (default-scale) and 8.94e-07 (gain-2) on these inputs (largest probability
    difference); twice that is allowed.  Measured with this kernel: 5.96e-08 and 8.94e-07.
 3. Batch-invariant mode: a 33-window call (32-row workgroups) and the first 33 rows of a 3073-window call (64-row workgroups)
@@ -176,7 +176,7 @@ def test_both_directions_and_the_int8_extremes(t_diff):
 
 
 def test_the_form_without_the_bias_column():
-    """32 image features leave no input column for the bias: lstm_rec_h2_kernel<256, 32, false, 2, false, 2> adds the four
+    """32 image features leave no input column for the bias: lstm_enc_h2_kernel<2, false> adds the four
     biases in the gate phase.  (The 32-row launch of a 32-feature model has no fused form and is not reached here.)"""
     sd = synthetic.variant_state_dict(seed=7, gain=1.0, image_features=32)
     rng = np.random.default_rng(714)

@@ -56,17 +56,19 @@ def test_no_vector_register_spills(tmp_path, source):
         # the instantiations the polish and variant models launch, by their mangled template arguments
         for needle in ("gru_rec_h2_kernelILi128ELi256ELb1ELi2ELb1E", "gru_rec_h2_kernelILi128ELi256ELb1ELi2ELb0E",
                        "gru_rec_h2_kernelILi128ELi16E", "gru_rec_h2_kernelILi128ELi128E",
-                       "lstm_rec_h2_kernelILi256ELi512ELb1ELi2E", "lstm_rec_h2_kernelILi256ELi32ELb0ELi2E"):
+                       "lstm_dec_h2_kernelILi2E", "lstm_enc_h2_kernelILi2ELb1E", "lstm_seed_h2_kernelILi2E"):
             assert any(needle in k for k in kernels), needle
 
 
 # Every step loop rnn_h2.hip compiles, by template arguments (bools as 0 / 1): a change that adds a form adds it here.
-#   lstm_rec_h2_kernel<H, KX, XG, SAUX, BC, MTILES>, gru_rec_h2_kernel<H, KX, XG, SAUX, DENSE, BC>
+#   lstm_dec_h2_kernel<MTILES>, lstm_enc_h2_kernel<MTILES, BC>, lstm_seed_h2_kernel<MTILES>,
+#   gru_rec_h2_kernel<H, KX, XG, SAUX, DENSE, BC>
+LSTM_LOOPS = ("lstm_dec_h2_kernel", "lstm_enc_h2_kernel", "lstm_seed_h2_kernel")
 STEP_LOOPS = {
-    ("lstm_rec_h2_kernel", (256, 512, 1, 2, 0, 2)), ("lstm_rec_h2_kernel", (256, 512, 1, 2, 0, 1)),
-    ("lstm_rec_h2_kernel", (256, 32, 0, 2, 1, 2)), ("lstm_rec_h2_kernel", (256, 32, 0, 2, 1, 1)),
-    ("lstm_rec_h2_kernel", (256, 32, 0, 2, 0, 2)),
-    ("lstm_rec_h2_kernel", (256, 0, 0, 0, 0, 2)), ("lstm_rec_h2_kernel", (256, 0, 0, 0, 0, 1)),
+    ("lstm_dec_h2_kernel", (2,)), ("lstm_dec_h2_kernel", (1,)),
+    ("lstm_enc_h2_kernel", (2, 1)), ("lstm_enc_h2_kernel", (1, 1)),
+    ("lstm_enc_h2_kernel", (2, 0)),
+    ("lstm_seed_h2_kernel", (2,)), ("lstm_seed_h2_kernel", (1,)),
     ("gru_rec_h2_kernel", (128, 16, 0, 2, 0, 1)), ("gru_rec_h2_kernel", (128, 16, 0, 2, 0, 0)),
     ("gru_rec_h2_kernel", (128, 128, 0, 0, 0, 0)), ("gru_rec_h2_kernel", (128, 0, 0, 0, 0, 0)),
     ("gru_rec_h2_kernel", (128, 256, 1, 2, 0, 0)), ("gru_rec_h2_kernel", (128, 256, 1, 2, 1, 0)),
@@ -89,15 +91,15 @@ def test_step_loops_keep_their_scalars_in_scalar_registers(tmp_path):
     the time loop (at most two reloads in the whole kernel: prologue / epilogue values)."""
     asm = _asm(tmp_path, "rnn_h2.hip")
     kernels = _kernels(asm)
-    step_loops = [k for k in kernels if any(n in k for n in ("lstm_rec_h2_kernel", "gru_rec_h2_kernel", "lstm_rec_h2_split_kernel",
-                                                               "gru_small_h2_kernel"))]
+    step_loops = [k for k in kernels if any(n in k for n in LSTM_LOOPS + ("gru_rec_h2_kernel", "lstm_rec_h2_split_kernel",
+                                                                          "gru_small_h2_kernel"))]
     assert sorted(_instantiation(k) for k in step_loops) == sorted(STEP_LOOPS)
     for name in step_loops:
         assert kernels[name][2] <= 2, (name, kernels[name])
         reloads = sum("v_readlane_b32" in ln for ln in _body(asm, name))
         # (the split loops and the fused heads use v_readlane for wave-uniform values on purpose: only the LSTM / GRU big loops
         # are held to the reload count)
-        if "lstm_rec_h2_kernel" in name:
+        if any(n in name for n in LSTM_LOOPS):
             assert reloads <= 2, (name, reloads)
 
 

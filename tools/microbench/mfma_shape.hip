@@ -1,5 +1,5 @@
 // Debug aid (not product): does the chip hold a higher clock on v_mfma_f32_16x16x32_f16 than on v_mfma_f32_32x32x16_f16
-// in the fused LSTM decoder's step loop (rnn_h2.hip: lstm_rec_h2_kernel<256, 512, XG>)?
+// in the fused LSTM decoder's step loop (rnn_h2.hip: lstm_dec_h2_kernel)?
 //   hipcc --offload-arch=gfx950 -O3 -o tools/microbench/mfma_shape tools/microbench/mfma_shape.hip && tools/microbench/mfma_shape
 //   (arguments: repetitions per launch [200], passes over the table [2], rows all | dec | enc | gemm; the encoder's rows and
 //   linear_1's GEMM rows are below -- the gemm rows run one pass over the k range per 50 repetitions)
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(512, 1) void k(int nrep, const uint32_t* __restrict
     }
 }
 
-// ---- the fused int8 ENCODER's traffic (lstm_rec_h2_kernel<256, 32, false, 2, true, 2>): K = 256 + 32, 18 k16 = 9 k32 steps,
+// ---- the fused int8 ENCODER's traffic (lstm_enc_h2_kernel<2, true>): K = 256 + 32, 18 k16 = 9 k32 steps,
 // one direction's fragments 1.125 MB re-read every time step, h2 rows of 1168 B ([h | x] + 16 pad).  The x steps (the last
 // two k16 steps / the last k32 step) are two-term: x is int8, exact in its hi half, so lo(x).hi(w) is not issued.
 //   S32: the form the encoder has today -- the 18 k16 steps of a time step unrolled, a 2-deep ring of whole k steps;

@@ -21,7 +21,9 @@ from collections import OrderedDict, defaultdict
 
 # kernel symbol prefix -> label bench.py's profiler uses
 LABELS = [
-    ("lstm_rec_h2_kernel<256, 512, true", "lstm_dec_h2_fused"),
+    ("lstm_dec_h2_kernel", "lstm_dec_h2_fused"),
+    ("lstm_enc_h2_kernel", "lstm_rec_h2_fused_in"),
+    ("lstm_rec_h2_kernel<256, 512, true", "lstm_dec_h2_fused"),      # their names in result databases from before the split
     ("lstm_rec_h2_kernel<256, 32, false", "lstm_rec_h2_fused_in"),
     ("gemm_h2_kernel", "gemm_h2_linear_1"),
     ("gemm_h2_k32_kernel", "gemm_h2_linear_1"),
