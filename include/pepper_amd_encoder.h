@@ -374,7 +374,8 @@ int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity);
  * The handle stays usable. */
 int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
 /* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
- * its tables (the quality buffer among them when the finish produced qualities, the edit records once pa_stitcher_edits ran). */
+ * its tables (the quality buffer among them when the finish produced qualities, the edit records once pa_stitcher_edits ran,
+ * and once pa_stitcher_fill ran its table of 4 bytes per position, the filled sequence and the filled qualities). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
 
 /* What the last finish changed against the draft (opt-in, not in the reference; pepper_amd/polish/Edits.py is the host twin and
@@ -400,11 +401,29 @@ typedef struct pa_stitch_edit {
  * One wait; the records stay on the device until pa_stitcher_take_edits, in a buffer allocated on first use and counted in
  * pa_stitcher_stats [5] from then on.  A later finish invalidates them.
  * PA_ERR_INVALID before any launch: no finish yet; the last finish gave no sequence (a bad label, a failure); draft_length <=
- * the largest piece_last; the finish had more than 65 535 pieces.  The handle stays usable. */
+ * the largest piece_last; the finish had more than 65 535 pieces; draft is NULL and no pa_stitcher_fill of a draft of
+ * draft_length letters ran since the finish.  The handle stays usable. */
 int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts /* [6] */);
 /* The records of the last pa_stitcher_edits (capacity >= *n_edits records).  PA_ERR_INVALID: pa_stitcher_edits has not run since
  * the last finish; capacity is short.  The handle stays usable. */
 int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity);
+
+/* Complete the consensus of the last finish with draft[0 .. draft_length), the whole contig of the draft (opt-in, not in the
+ * reference; Stitch.py filled_piece is the host twin).  The finish must have had ONE piece (every region in piece 0: the merge
+ * of the whole contig).  Every position of the draft without a slot -- in front of the piece's first position, behind its last,
+ * and in the runs inside -- gives draft[p] as it is passed (no case folding) with quality '!'; a position with a slot gives what
+ * it gave.  *filled_length letters; counts[0] runs filled (the two ends count when they are not empty), counts[1] letters filled.
+ * A finish without a kept row is filled with the whole draft.
+ * From then on, until the next finish, the handle speaks of the FILLED consensus: pa_stitcher_take and pa_stitcher_take_qualities
+ * copy it (capacity >= *filled_length), and pa_stitcher_edits gives its records -- `offset` counts its letters, and a GAP pair's
+ * offset is the first filled letter of its run.  Records made before the fill are dropped: pa_stitcher_edits has to run again.
+ * That call may pass draft = NULL with the same draft_length: it then reads the copy this call uploaded, so a contig's draft goes
+ * to the device once.
+ * One wait; one scan over the positions and one lane per position, the ends are copies on the device.
+ * PA_ERR_INVALID before any launch: no finish yet; the last finish gave no sequence; it had more than one piece; draft_length <=
+ * the piece's last position.  PA_ERR_UNSUPPORTED: the draft or the filled consensus has more than 2^32 - 1 letters.  The handle
+ * stays usable, and a refused call changes nothing. */
+int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* filled_length, int64_t* counts /* [2] */);
 
 /* ------------------------------------------------------------------------------------------
  * The candidate finder's selection ON THE DEVICE (opt-in: call_variant(..., fused_inference=True, device_selection=True);

@@ -143,6 +143,7 @@ SYMBOLS = [
     ("pa_stitcher_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_stitcher_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     ("pa_stitcher_take_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
+    ("pa_stitcher_fill", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     ("pa_selector_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_selector_destroy", None, [c_void_p]),
     ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
@@ -328,6 +329,16 @@ def polish_edits():
     """PEPPER_AMD_POLISH_EDITS=1: polish() writes <prefix>_pepper_polished.edits.tsv beside the FASTA: what the consensus changed
     against the draft (pepper_amd/polish/Edits.py).  Unset or any other value: the FASTA alone."""
     return os.environ.get(POLISH_EDITS_ENV, "0") == "1"
+
+
+POLISH_FILL_ENV = "PEPPER_AMD_POLISH_FILL"
+
+
+def polish_fill():
+    """PEPPER_AMD_POLISH_FILL=1: polish() writes a complete consensus -- every contig merged as one piece, the draft's own letters
+    where no prediction covered a position, and without a region the contigs no read landed on.  Unset or any other value: the
+    reference's stitch, which leaves such sequence out."""
+    return os.environ.get(POLISH_FILL_ENV, "0") == "1"
 
 
 def check(rc):

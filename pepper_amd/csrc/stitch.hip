@@ -27,6 +27,13 @@
 // gives 0 or 1 record, and the slot (p, 0) behind a run of uncovered positions carries the run's two GAP records in front of
 // its own: every run is closed by exactly one such slot.  Count (block sums), scan of the sums, write: the write pass scans
 // its block again instead of reading a per-slot prefix, so the only table this adds is the records themselves.
+//
+// Fill (pa_stitcher_fill; opt-in, not in the reference): the consensus of a finish with ONE piece, completed with the draft's own
+// letters where a position has no slot -- in front of the piece, behind it, and in the runs inside it.  One more exclusive scan,
+// over "the position has no slot" (the same reduce-then-scan), tells every position how many draft letters lie in front of it
+// inside the piece; the scanned word also counts, in its upper half, the positions that begin a run, so the one total that comes
+// back sizes the buffer and counts the runs.  Then one lane per POSITION writes what the position gives: its slots' letters at
+// lead + place + holes, or draft[p] (and '!') at lead + letters in front + holes.  The two ends are copies of the draft.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -237,6 +244,50 @@ struct LoadLetter {
     const uint8_t* p;
     PA_DEV uint64_t operator()(uint64_t i) const { return p[i] != 0; }
 };
+// low word: the position has no slot; high word: ... and the position in front of it has one, so a run begins here.  Scanned
+// into 32-bit outputs the low word alone survives; the 64-bit total carries both counts (each below 2^32: so are the positions).
+struct LoadHole {
+    const uint32_t* width;
+    PA_DEV uint64_t operator()(uint64_t i) const {
+        if (width[i] != 0) return 0;
+        return 1ull | ((uint64_t)(i > 0 && width[i - 1] != 0) << 32);
+    }
+};
+
+// ---------------------------------------------------------------- fill: the draft where no slot is ----
+// One lane per position of the one piece.  holes[p]: positions without a slot in front of p; draft: the draft from the piece's
+// first position on; lead: letters in front of the piece.  Consecutive lanes write consecutive letters wherever the widths are 1.
+// A position with many insert slots is walked by its one lane (at most 65 536 slots; the edit passes deal a lane per slot
+// because they bisect anyway, here the position's own tables give every address and a second bisection would cost every lane).
+template <bool QUAL>
+__global__ __launch_bounds__(ST_THREADS) void k_stitch_fill(const uint32_t* __restrict__ width, const uint32_t* __restrict__ slot_base,
+                                                            const uint32_t* __restrict__ holes, const uint8_t* __restrict__ letters,
+                                                            const uint32_t* __restrict__ place,
+                                                            const unsigned long long* __restrict__ slots,
+                                                            const uint8_t* __restrict__ draft, uint64_t n_positions, uint64_t n_slots,
+                                                            uint64_t n_letters, uint64_t lead, uint64_t n_out, uint8_t* __restrict__ out,
+                                                            uint8_t* __restrict__ qual) {
+    const uint64_t p = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (p >= n_positions) return;
+    const uint32_t w = width[p];
+    const uint64_t base = slot_base[p], shift = lead + holes[p];
+    if (w == 0) {                                        // (shares the base of the next position that has a slot)
+        const uint64_t at = shift + (base < n_slots ? (uint64_t)place[base] : n_letters);
+        if (at < n_out) {
+            out[at] = draft[p];
+            if (QUAL) qual[at] = (uint8_t)'!';
+        }
+        return;
+    }
+    for (uint64_t i = base; i < base + w && i < n_slots; ++i) {
+        const uint8_t letter = letters[i];
+        const uint64_t at = shift + place[i];
+        if (letter && at < n_out) {
+            out[at] = letter;
+            if (QUAL) qual[at] = (uint8_t)(33u + min(((uint32_t)slots[i] >> 8) & 0xFFu, ST_MAX_QUALITY));
+        }
+    }
+}
 
 // ---------------------------------------------------------------- edits against the draft ----
 struct EditTables {                                     // the last finish's tables, as the edit passes read them
@@ -250,8 +301,10 @@ struct EditTables {                                     // the last finish's tab
     const int64_t* letter_shift;                        // [n_pieces] take() offset of the piece's first letter - its table offset
     const uint16_t* take_index;                         // [n_pieces] the piece's place in take() order
     const uint8_t* draft;                               // draft[draft_lo .. draft_lo + draft_span)
+    const uint32_t* holes;                              // [n_positions] after a fill: positions without a slot in front (else null)
     uint64_t n_positions, n_slots;
     uint32_t n_pieces, draft_lo, draft_span, qualities;
+    uint32_t lead;                                      // after a fill: letters in front of the piece
 };
 
 struct SlotEdit {
@@ -371,7 +424,8 @@ __global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const u
         if (i0 + k >= t.n_slots) break;
         const SlotEdit& e = item[k];
         const uint32_t piece = t.take_index[e.piece];
-        const uint32_t letters_before = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[e.piece]);
+        uint32_t letters_before = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[e.piece]);
+        if (t.holes) letters_before += t.lead + t.holes[t.pbase[e.piece] + (e.position - t.pmin[e.piece])];      // (uniform)
         if (e.index == 0 && (uint64_t)(e.position - t.pmin[e.piece]) == 0) piece_start[e.piece] = run;
         if (e.gap) {
             const uint32_t close_at = e.position - 1;
@@ -379,8 +433,10 @@ __global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const u
             uint8_t d_open = lo < t.draft_span ? t.draft[lo] : (uint8_t)0, d_close = hi < t.draft_span ? t.draft[hi] : (uint8_t)0;
             if (d_open >= 'a' && d_open <= 'z') d_open = (uint8_t)(d_open - 32);
             if (d_close >= 'a' && d_close <= 'z') d_close = (uint8_t)(d_close - 32);
-            if (run < n_edits) out[run] = make_edit(e.open_at, letters_before, 0, piece, PA_EDIT_GAP_OPEN, d_open, 0, 0);
-            if (run + 1 < n_edits) out[run + 1] = make_edit(close_at, letters_before, 0, piece, PA_EDIT_GAP_CLOSE, d_close, 0, 0);
+            // after a fill the run's own letters are in the consensus, behind the pair's offset
+            const uint32_t run_at = t.holes ? letters_before - (close_at - e.open_at + 1) : letters_before;
+            if (run < n_edits) out[run] = make_edit(e.open_at, run_at, 0, piece, PA_EDIT_GAP_OPEN, d_open, 0, 0);
+            if (run + 1 < n_edits) out[run + 1] = make_edit(close_at, run_at, 0, piece, PA_EDIT_GAP_CLOSE, d_close, 0, 0);
             run += 2;
         }
         if (e.kind) {
@@ -447,6 +503,11 @@ struct pa_stitcher {
     Buffer f_desc, f_piece, f_width, f_base, f_slots, f_letters, f_place, f_out, f_qual, f_scan, f_words;
     // edits' staging (the draft span, the pieces' take() order) and its one table: the records
     Buffer e_draft, e_piece, e_records;
+    // fill's tables: the positions without a slot in front of every position, the filled sequence, the filled qualities
+    Buffer f_holes, f_fill, f_fillq;
+    bool filled = false;                                // pa_stitcher_fill ran on the last finish: take, take_qualities, edits speak of it
+    int64_t filled_length = 0, fill_lead = 0, fill_bytes = 0;      // fill_bytes: its share of last_scratch_bytes
+    int64_t draft_held = -1;                            // e_draft holds draft[0 .. draft_held) of that fill (-1: it does not)
     std::vector<PieceOut> pieces;                       // of the last finish, in output order
     int64_t sequence_length = 0;
     bool finished = false;                              // a finish has run: the three below speak of it
@@ -474,7 +535,7 @@ int no_memory(const char* what, uint64_t bytes) {
 std::vector<Buffer*> buffers_of(pa_stitcher* s) {
     return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
             &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words,
-            &s->e_draft, &s->e_piece, &s->e_records};
+            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq};
 }
 
 }  // namespace
@@ -637,6 +698,9 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     s->contig_qualities = s->have_qualities = false;
     s->have_sequence = s->have_edits = false;
     s->n_edits = 0;
+    s->filled = false;
+    s->filled_length = s->fill_lead = s->fill_bytes = 0;
+    s->draft_held = -1;
     s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
@@ -809,10 +873,16 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
 int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (capacity < s->sequence_length)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take: the sequence has " + std::to_string(s->sequence_length) + " letters, room for " +
+    const int64_t length = s->filled ? s->filled_length : s->sequence_length;
+    if (capacity < length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take: the sequence has " + std::to_string(length) + " letters, room for " +
                                                  std::to_string(capacity));
     ST_HIP(hipSetDevice(s->device));
+    if (s->filled) {
+        if (length > 0) ST_HIP(hipMemcpyAsync(dst, s->f_fill.p, (size_t)length, hipMemcpyDeviceToHost, s->stream));
+        ST_HIP(hipStreamSynchronize(s->stream));
+        return PA_OK;
+    }
     int64_t at = 0;
     for (const PieceOut& piece : s->pieces) {
         if (piece.length == 0) continue;
@@ -832,10 +902,16 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
                                                  ? "stitcher take qualities: the last finish gave no sequence (a label that is no base, or it failed)"
                                                  : "stitcher take qualities: the last finish produced none: a chunk of its contig was added "
                                                    "without qualities (pa_stitcher_add_qual on every chunk asks for them), or it failed early");
-    if (capacity < s->sequence_length)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: the sequence has " + std::to_string(s->sequence_length) +
+    const int64_t length = s->filled ? s->filled_length : s->sequence_length;
+    if (capacity < length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: the sequence has " + std::to_string(length) +
                                                  " letters, room for " + std::to_string(capacity));
     ST_HIP(hipSetDevice(s->device));
+    if (s->filled) {
+        if (length > 0) ST_HIP(hipMemcpyAsync(dst, s->f_fillq.p, (size_t)length, hipMemcpyDeviceToHost, s->stream));
+        ST_HIP(hipStreamSynchronize(s->stream));
+        return PA_OK;
+    }
     int64_t at = 0;
     for (const PieceOut& piece : s->pieces) {
         if (piece.length == 0) continue;
@@ -847,11 +923,13 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
 }
 
 int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
-    if (!s || !n_edits || !counts || draft_length < 0 || (draft_length > 0 && !draft))
-        return pa::set_error(PA_ERR_INVALID, "stitcher edits: null or negative argument");
+    if (!s || !n_edits || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher edits: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
     *n_edits = 0;
     for (int k = 0; k < 6; ++k) counts[k] = 0;
+    const bool held = !draft && s->filled && s->draft_held == draft_length;      // the draft the fill uploaded
+    if (draft_length > 0 && !draft && !held)
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: null draft (only after a pa_stitcher_fill of a draft of this length)");
     if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher edits: no contig has been finished");
     if (!s->have_sequence)
         return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish gave no sequence (a label that is no base, or it failed)");
@@ -898,7 +976,10 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
     ST_HIP(hipMemcpyAsync(d_shift, shift.data(), np * 8, hipMemcpyHostToDevice, s->stream));
     ST_HIP(hipMemcpyAsync(d_index, take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
     ST_HIP(hipMemsetAsync(d_start, 0, np * 8 + 6 * 8, s->stream));
-    ST_HIP(hipMemcpyAsync(s->e_draft.p, draft + lo, span, hipMemcpyHostToDevice, s->stream));
+    if (!held) {
+        ST_HIP(hipMemcpyAsync(s->e_draft.p, draft + lo, span, hipMemcpyHostToDevice, s->stream));
+        s->draft_held = -1;                             // (behind the fill's kernels on the stream; its whole draft is gone)
+    }
     // the piece words of the finish: [pmin u32 | pmax u32 | pbase u64 | ...] x n_pieces
     const uint8_t* pw = s->f_piece.as<uint8_t>();
     EditTables t;
@@ -911,7 +992,9 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
     t.pmin = (const uint32_t*)pw;
     t.letter_shift = d_shift;
     t.take_index = d_index;
-    t.draft = s->e_draft.as<uint8_t>();
+    t.draft = s->e_draft.as<uint8_t>() + (held ? lo : 0);
+    t.holes = s->filled ? s->f_holes.as<uint32_t>() : nullptr;
+    t.lead = (uint32_t)s->fill_lead;
     t.n_positions = (uint64_t)s->last_positions;
     t.n_slots = n_slots;
     t.n_pieces = (uint32_t)np;
@@ -940,6 +1023,85 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
     s->have_edits = true;
     *n_edits = (int64_t)total;
     for (int k = 0; k < 6; ++k) counts[k] = (int64_t)kinds[k];
+    return PA_OK;
+}
+
+int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* filled_length, int64_t* counts) {
+    if (!s || !filled_length || !counts || draft_length < 0 || (draft_length > 0 && !draft))
+        return pa::set_error(PA_ERR_INVALID, "stitcher fill: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    *filled_length = 0;
+    counts[0] = counts[1] = 0;
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher fill: no contig has been finished");
+    if (!s->have_sequence)
+        return pa::set_error(PA_ERR_INVALID, "stitcher fill: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (s->last_pieces > 1)
+        return pa::set_error(PA_ERR_INVALID, "stitcher fill: the last finish had " + std::to_string(s->last_pieces) +
+                                                 " pieces, a filled consensus is one piece");
+    const bool rows = !s->pieces.empty();
+    const int64_t first = rows ? s->pieces[0].first : draft_length, last = rows ? s->pieces[0].last : -1;
+    if (draft_length <= last)
+        return pa::set_error(PA_ERR_INVALID, "stitcher fill: the draft has " + std::to_string(draft_length) +
+                                                 " letters, the piece ends at position " + std::to_string(last));
+    if (draft_length > ST_MAX_POSITION)
+        return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher fill: the draft has " + std::to_string(draft_length) + " letters, an offset counts 2^32 - 1");
+    // asked again, or after edits: counted once, and the records of the consensus as it was are gone
+    s->last_scratch_bytes -= s->fill_bytes;
+    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
+    s->have_edits = s->filled = false;
+    s->n_edits = s->fill_bytes = s->filled_length = s->fill_lead = 0;
+    s->draft_held = -1;
+    ST_HIP(hipSetDevice(s->device));
+    const uint64_t n_positions = rows ? (uint64_t)s->last_positions : 0, n_slots = (uint64_t)s->last_slots;
+    const uint64_t n_letters = (uint64_t)s->sequence_length;
+    if (!s->e_draft.grow((size_t)draft_length + 1) || !s->f_holes.grow(n_positions * 4 + 4)) return no_memory("the draft", (uint64_t)draft_length);
+    if (draft_length > 0) ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
+    uint64_t word = 0;                                  // runs that begin inside the piece << 32 | positions without a slot
+    if (n_positions) {                                  // (f_scan is the width scan's scratch: sized for n_positions, free since)
+        const uint64_t* d_total = scan_exclusive<LoadHole, uint32_t>(s->stream, LoadHole{s->f_width.as<uint32_t>()}, n_positions,
+                                                                     s->f_holes.as<uint32_t>(), s->f_scan.as<uint64_t>());
+        ST_HIP(hipGetLastError());
+        ST_HIP(hipMemcpyAsync(&word, d_total, 8, hipMemcpyDeviceToHost, s->stream));
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));            // the one wait: the filled buffer's size
+    const uint64_t holes = word & 0xFFFFFFFFull, runs = word >> 32;
+    const uint64_t lead = (uint64_t)first, trail = rows ? (uint64_t)(draft_length - last - 1) : 0;
+    const uint64_t total = lead + n_letters + holes + trail;
+    if (total > 0xFFFFFFFFull)
+        return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher fill: the filled consensus has " + std::to_string(total) + " letters, an offset counts 2^32 - 1");
+    const bool qualities = s->have_qualities;
+    if (!s->f_fill.grow(total + 1) || (qualities && !s->f_fillq.grow(total + 1))) return no_memory("the filled sequence", total);
+    uint8_t* out = s->f_fill.as<uint8_t>();
+    uint8_t* qual = qualities ? s->f_fillq.as<uint8_t>() : nullptr;
+    const uint8_t* d_draft = s->e_draft.as<uint8_t>();
+    // the two ends are copies; everything below is left in flight: take, edits, a later finish and destroy are ordered behind it
+    if (lead) ST_HIP(hipMemcpyAsync(out, d_draft, lead, hipMemcpyDeviceToDevice, s->stream));
+    if (trail) ST_HIP(hipMemcpyAsync(out + (total - trail), d_draft + last + 1, trail, hipMemcpyDeviceToDevice, s->stream));
+    if (qual && lead) ST_HIP(hipMemsetAsync(qual, '!', lead, s->stream));
+    if (qual && trail) ST_HIP(hipMemsetAsync(qual + (total - trail), '!', trail, s->stream));
+    if (n_positions) {
+        const unsigned blocks = (unsigned)((n_positions + ST_THREADS - 1) / ST_THREADS);
+        if (qual)
+            k_stitch_fill<true><<<blocks, ST_THREADS, 0, s->stream>>>(s->f_width.as<uint32_t>(), s->f_base.as<uint32_t>(), s->f_holes.as<uint32_t>(),
+                                                                      s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
+                                                                      s->f_slots.as<unsigned long long>(), d_draft + first, n_positions, n_slots,
+                                                                      n_letters, lead, total, out, qual);
+        else
+            k_stitch_fill<false><<<blocks, ST_THREADS, 0, s->stream>>>(s->f_width.as<uint32_t>(), s->f_base.as<uint32_t>(), s->f_holes.as<uint32_t>(),
+                                                                       s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
+                                                                       s->f_slots.as<unsigned long long>(), d_draft + first, n_positions, n_slots,
+                                                                       n_letters, lead, total, out, nullptr);
+        ST_HIP(hipGetLastError());
+    }
+    s->fill_bytes = (int64_t)(n_positions * 4 + total * (qualities ? 2 : 1));
+    s->last_scratch_bytes += s->fill_bytes;
+    s->filled = true;
+    s->filled_length = (int64_t)total;
+    s->fill_lead = (int64_t)lead;
+    s->draft_held = draft_length;
+    *filled_length = (int64_t)total;
+    counts[0] = (int64_t)(runs + (lead > 0) + (trail > 0));
+    counts[1] = (int64_t)(lead + holes + trail);
     return PA_OK;
 }
 

@@ -9,6 +9,10 @@ qualities on (opt-in, not in the reference) byte for byte its FASTQ: the phred o
 plan() restates the loop order of the reference: regions sorted by name, then stably by (start, end), cut into pieces of
 max(2, int(n / threads) + 1) consecutive regions; inside a region the chunk ids in STRING order.  The device only needs, per
 row, its piece and a rank that grows along that loop: the last write of a key is the one with the largest rank.
+
+fill (opt-in, not in the reference; perform_stitch(..., fill=) is the host form): the contig is planned as ONE piece whatever
+`threads` is and pa_stitcher_fill completes the consensus on the device with the draft's letters where no row covered a position;
+the draft goes up once per contig, the edits read that copy.
 """
 import collections
 import contextlib
@@ -23,8 +27,8 @@ from pepper_amd import _lib, h5
 from pepper_amd.polish import Edits
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
-from pepper_amd.polish.perform_stitch import (_log, draft_lengths, fastq_path, get_file_paths_from_directory, natural_key,
-                                              write_fastq_record)
+from pepper_amd.polish.perform_stitch import (_log, check_fill, draft_lengths, fastq_path, get_file_paths_from_directory,
+                                              natural_key, write_fastq_record, write_unpolished)
 
 Plan = collections.namedtuple("Plan", "order piece rank n_pieces chunk_order")
 
@@ -90,6 +94,10 @@ class DeviceStitcher(object):
         self.last_edit_counts = None         # of the last edits(): records per kind, [0..5]
         # over every edits() of this handle; the seconds: the comparison with its copy back, and the text made of it
         self.edit_totals = {"records": 0, "bytes_returned": 0, "seconds_compare": 0.0, "seconds_text": 0.0}
+        self.last_fill_counts = None         # of the last finish(fill=): [runs filled, letters filled]
+        self.last_filled = False             # the last finish was one with fill
+        # over every finish(fill=) of this handle; the seconds: pa_stitcher_fill alone (the upload of the draft, the scan, the wait)
+        self.fill_totals = {"runs": 0, "letters": 0, "seconds": 0.0}
         handle = ctypes.c_void_p()
         _lib.check(self._lib.pa_stitcher_create(self.device, ctypes.c_void_p(stream) if stream else None, ctypes.byref(handle)))
         self._handle = handle
@@ -189,17 +197,29 @@ class DeviceStitcher(object):
             if phred_ptr is None:
                 self._plain.add(contig)
 
-    def finish(self, contig, threads, region_keys=None, qualities=False):
+    def finish(self, contig, threads, region_keys=None, qualities=False, fill=None):
         """The consensus of one contig as create_consensus_sequence(contig, region_keys, threads) returns it; region_keys
         default to the contig's regions in the order they first arrived.  KeyError(label): a surviving label that is no base.
         qualities: (sequence, quality) as create_consensus_sequence(..., qualities=True) returns them; PepperAmdError where an
-        add of the contig came without phred."""
+        add of the contig came without phred.
+        fill (str or bytes, the whole contig of the draft as its file stores it): the FILLED consensus, as
+        create_consensus_sequence(..., fill=) returns it -- one piece whatever `threads` is, the draft's letters where no row
+        covered a position, their qualities '!'; pieces() is then the one piece with the filled length, and edits() gives the
+        filled consensus' records."""
+        draft = None if fill is None else fill.encode() if isinstance(fill, str) else bytes(fill)
         with self._lock:
+            self.last_filled = draft is not None
             entry = self._contigs.get(contig)
             if entry is None:
+                self.last_pieces = []
+                if draft is not None:            # no row of the contig: the draft as it is
+                    self.last_fill_counts = [1 if draft else 0, len(draft)]
+                    self.fill_totals["runs"] += self.last_fill_counts[0]
+                    self.fill_totals["letters"] += len(draft)
+                    return (draft.decode(), "!" * len(draft)) if qualities else draft.decode()
                 return ("", "") if qualities else ""
             keys = list(region_keys) if region_keys is not None else list(entry[2])
-            p = plan(keys, threads)
+            p = plan(keys, 1 if draft is not None else threads)
             known = [i for i, k in enumerate(keys) if k in entry[1]]
             region = np.array([entry[1][keys[i]] for i in known], dtype=np.int32)
             piece = np.array([p.piece[i] for i in known], dtype=np.int32)
@@ -213,6 +233,15 @@ class DeviceStitcher(object):
             if bad.value:
                 raise KeyError(int(bad.value))
             self.last_pieces = list(zip(first.tolist(), last.tolist(), length.tolist()))
+            if draft is not None:
+                t0 = time.perf_counter()
+                counts = (ctypes.c_int64 * 2)()
+                _lib.check(self._lib.pa_stitcher_fill(self.handle, draft, len(draft), ctypes.byref(total), counts))
+                self.last_pieces = [(f, l, total.value) for f, l, _ in self.last_pieces if f != -1 and l != -1]
+                self.last_fill_counts = [int(v) for v in counts]
+                self.fill_totals["runs"] += self.last_fill_counts[0]
+                self.fill_totals["letters"] += self.last_fill_counts[1]
+                self.fill_totals["seconds"] += time.perf_counter() - t0
             buf = ctypes.create_string_buffer(max(1, total.value))
             _lib.check(self._lib.pa_stitcher_take(self.handle, buf, total.value))
             sequence = buf.raw[:total.value].decode()
@@ -232,12 +261,17 @@ class DeviceStitcher(object):
     def edits(self, draft_sequence):
         """After finish(): what the consensus changed against draft_sequence (str or bytes, the whole contig of the draft), as
         Edits.EDIT_DTYPE records in the order and with the bytes of Edits.records_numpy -- compared on the device, only the
-        records come back.  Pieces go with them as pieces()."""
+        records come back.  Pieces go with them as pieces().  After finish(fill=): the records of the filled consensus (the
+        draft is the one that filled, and is not uploaded again)."""
         draft = draft_sequence.encode() if isinstance(draft_sequence, str) else bytes(draft_sequence)
         with self._lock:
+            if self.last_filled and not self.last_pieces:            # the draft as it is: nothing was merged, no record
+                self.last_edit_counts = [0] * 6
+                return np.zeros(0, Edits.EDIT_DTYPE)
             t0 = time.perf_counter()
             n, counts = ctypes.c_int64(), (ctypes.c_int64 * 6)()
-            _lib.check(self._lib.pa_stitcher_edits(self.handle, draft, len(draft), ctypes.byref(n), counts))
+            held = self.last_filled                                  # pa_stitcher_fill ran: its copy of the draft is read
+            _lib.check(self._lib.pa_stitcher_edits(self.handle, None if held else draft, len(draft), ctypes.byref(n), counts))
             records = np.zeros(n.value, Edits.EDIT_DTYPE)
             _lib.check(self._lib.pa_stitcher_take_edits(self.handle, records.ctypes.data, n.value))
             self.last_edit_counts = [int(v) for v in counts]
@@ -246,13 +280,14 @@ class DeviceStitcher(object):
             self.edit_totals["seconds_compare"] += time.perf_counter() - t0
         return records
 
-    def _write_edits(self, edits_file, draft, lengths, contig):
-        """One contig's lines of the .edits.tsv, after its finish."""
+    def _write_edits(self, edits_file, draft, lengths, contig, stored=None):
+        """One contig's lines of the .edits.tsv, after its finish (stored: the draft the finish was filled with)."""
         if contig not in lengths:
             raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
-        records = self.edits(draft.get_reference_bytes(contig, 0, lengths[contig]))
+        records = self.edits(stored if stored is not None else draft.get_reference_bytes(contig, 0, lengths[contig]))
         t0 = time.perf_counter()
-        Edits.write_contig(edits_file, contig, records, self.pieces(), lengths[contig], self.has_qualities(contig))
+        Edits.write_contig(edits_file, contig, records, self.pieces(), lengths[contig], self.has_qualities(contig),
+                           filled=stored is not None)
         self.edit_totals["seconds_text"] += time.perf_counter() - t0
 
     def stats(self):
@@ -261,36 +296,38 @@ class DeviceStitcher(object):
         _lib.check(self._lib.pa_stitcher_stats(self.handle, out, 6))
         return dict(zip(("rows", "slab_bytes", "slots", "pieces", "positions", "table_bytes"), (int(v) for v in out)))
 
-    def write_fasta(self, output_prefix, threads, edits=None):
+    def write_fasta(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False):
         """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file).  edits: the
-        draft FASTA's path; <output_prefix>_pepper_polished.edits.tsv beside it (perform_stitch(..., edits=)'s file)."""
-        return self._write(output_prefix, threads, False, edits)
+        draft FASTA's path; <output_prefix>_pepper_polished.edits.tsv beside it (perform_stitch(..., edits=)'s file).
+        fill / unpolished_contigs: perform_stitch's -- the draft FASTA's path, every contig filled; and the draft's other
+        contigs written among them."""
+        return self._write(output_prefix, threads, False, edits, fill, unpolished_contigs)
 
-    def write_fastq(self, output_prefix, threads, edits=None):
+    def write_fastq(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False):
         """write_fasta's file, and beside it <output_prefix>_pepper_polished.fastq with the same records and their qualities
         (perform_stitch(..., qualities=True)'s two files), from one finish per contig.  -> the FASTQ's path."""
-        return self._write(output_prefix, threads, True, edits)
+        return self._write(output_prefix, threads, True, edits, fill, unpolished_contigs)
 
-    def _write(self, output_prefix, threads, qualities, edits):
+    def _write(self, output_prefix, threads, qualities, edits, fill=None, unpolished_contigs=False):
+        check_fill(edits, fill, unpolished_contigs)
         output_path = output_prefix + '_pepper_polished.fa'
         Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
         with contextlib.ExitStack() as files:
             fasta = files.enter_context(open(output_path, 'w'))
             fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
-            if edits is not None:
-                from pepper_amd.variant.fasta import FASTA_handler
-                lengths = draft_lengths(edits)
-                draft = FASTA_handler(edits)
-                files.callback(draft.close)
-                edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
-                edits_file.write(Edits.HEADER)
-            for contig in sorted(self.contigs(), key=natural_key):
+            draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill)
+            held = set(self.contigs())
+            for contig in sorted(held | set(lengths if unpolished_contigs else ()), key=natural_key):
+                if contig not in held:
+                    write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file)
+                    continue
+                stored = _stored_draft(draft, lengths, contig) if fill is not None else None
                 if qualities:
-                    sequence, quality = self.finish(contig, threads, qualities=True)
+                    sequence, quality = self.finish(contig, threads, qualities=True, fill=stored)
                 else:
-                    sequence = self.finish(contig, threads)
+                    sequence = self.finish(contig, threads, fill=stored)
                 if edits is not None:
-                    self._write_edits(edits_file, draft, lengths, contig)
+                    self._write_edits(edits_file, draft, lengths, contig, stored)
                 _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
                 if len(sequence) > 0:
                     fasta.write('>' + contig + "\n")
@@ -315,6 +352,30 @@ class DeviceStitcher(object):
             self.close()
         except Exception:
             pass
+
+
+def _open_draft(files, output_prefix, edits, fill):
+    """What a writer needs of the draft FASTA (the one that fills, else the one the edits are taken against): (handler, {contig:
+    length}, the open .edits.tsv with its header or None); (None, {}, None) without either."""
+    path = fill if fill is not None else edits
+    if path is None:
+        return None, {}, None
+    from pepper_amd.variant.fasta import FASTA_handler
+    lengths = draft_lengths(path)
+    draft = FASTA_handler(path)
+    files.callback(draft.close)
+    edits_file = None
+    if edits is not None:
+        edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
+        edits_file.write(Edits.HEADER)
+    return draft, lengths, edits_file
+
+
+def _stored_draft(draft, lengths, contig):
+    """The whole contig of the draft as the file stores it."""
+    if contig not in lengths:
+        raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+    return draft.get_reference_bytes(contig, 0, lengths[contig], stored_case=True)
 
 
 def _read_region(hdf5_file, prefix, qualities=False):
@@ -362,10 +423,12 @@ class _Held(object):
         self.keys, self.order, self.blocks = [], [], []
 
 
-def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False, edits=None):
-    """perform_stitch(hdf_file_path, output_path, threads, qualities, edits) with the merge on the device: the same files read,
-    the same FASTA (and FASTQ, and .edits.tsv) written.  stats: a dict that receives the handle's stats() after the last
-    contig."""
+def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False, edits=None, fill=None,
+                     unpolished_contigs=False):
+    """perform_stitch(hdf_file_path, output_path, threads, qualities, edits, fill, unpolished_contigs) with the merge on the
+    device: the same files read, the same FASTA (and FASTQ, and .edits.tsv) written.  stats: a dict that receives the handle's
+    stats() after the last contig (with fill: and `fill`, the handle's fill_totals)."""
+    check_fill(edits, fill, unpolished_contigs)
     read_phred = qualities or edits is not None         # the edit records carry the winners' phred
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
@@ -380,14 +443,11 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
         stitcher = files.enter_context(DeviceStitcher(device))
         fasta = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
-        if edits is not None:
-            from pepper_amd.variant.fasta import FASTA_handler
-            lengths = draft_lengths(edits)
-            draft = FASTA_handler(edits)
-            files.callback(draft.close)
-            edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
-            edits_file.write(Edits.HEADER)
-        for contig in sorted(all_contigs, key=natural_key):
+        draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill)
+        for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
+            if contig not in all_contigs:
+                write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file)
+                continue
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
             held = _Held(stitcher, contig)
@@ -405,12 +465,13 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                             held.take(key, at, *block)
                             at += len(block[0])
             held.flush()
+            stored = _stored_draft(draft, lengths, contig) if fill is not None else None
             if qualities:
-                sequence, quality = stitcher.finish(contig, threads, all_chunk_keys, qualities=True)
+                sequence, quality = stitcher.finish(contig, threads, all_chunk_keys, qualities=True, fill=stored)
             else:
-                sequence = stitcher.finish(contig, threads, all_chunk_keys)
+                sequence = stitcher.finish(contig, threads, all_chunk_keys, fill=stored)
             if edits is not None:
-                stitcher._write_edits(edits_file, draft, lengths, contig)
+                stitcher._write_edits(edits_file, draft, lengths, contig, stored)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
             if len(sequence) > 0:
                 fasta.write('>' + contig + "\n")
@@ -419,4 +480,6 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                     write_fastq_record(fastq, contig, sequence, quality)
         if stats is not None:
             stats.update(stitcher.stats())
+            if fill is not None:
+                stats["fill"] = dict(stitcher.fill_totals)
     return output_path

@@ -19,6 +19,13 @@ consensus: the record's own letter for SUB and INS, the letters in front of the 
 records_numpy() makes them from the numpy merge's sorted last-write arrays (Stitch.small_chunk_stitch_numpy); the device makes
 the same bytes from its tables (pa_stitcher_edits).  hunks() and write_edits() turn either into the text both forms write, and
 apply() replays the records over the draft: it gives back the consensus, which is the check that needs no twin.
+
+FILL (opt-in: polish(..., fill=True) / PEPPER_AMD_POLISH_FILL=1): the contig is merged as ONE piece and every position of the draft
+that has no slot gives the draft's own letter, so the consensus is complete.  The records keep their layout and kinds; `offset`
+counts letters of the FILLED consensus (the draft letters in front of the piece and the filled positions count), and a GAP pair's
+offset is the first filled letter of its run.  The one piece is (first, last, filled length).  filled_hunks(), write_contig(...,
+filled=True) and apply_filled() read such records: a run is a `filled` hunk with equal draft and polished intervals, and so are
+[0, first) and (last, draft_length); `uncovered` and `duplicated` cannot occur.
 """
 import numpy as np
 
@@ -28,7 +35,8 @@ EDIT_DTYPE = np.dtype([("position", "<u4"), ("offset", "<u4"), ("index", "<u2"),
 assert EDIT_DTYPE.itemsize == 16
 MAX_PIECES = 0xFFFF
 HEADER = "#contig\tdraft_start\tdraft_end\tpolished_start\tpolished_end\tkind\tdraft\tpolished\tmin_phred\n"
-HUNK_KINDS = ("sub", "ins", "del", "complex", "uncovered", "duplicated")
+HUNK_KINDS = ("sub", "ins", "del", "complex", "uncovered", "duplicated", "filled")
+SUMMARY_KEYS = ("sub", "ins", "del", "complex_draft", "complex_polished", "uncovered", "duplicated")
 _DECODE = np.frombuffer(b"\0ACGT", dtype=np.uint8)
 _UPPER = bytes(c - 32 if 97 <= c <= 122 else c for c in range(256))
 
@@ -44,11 +52,12 @@ def upper_bytes(draft):
     return np.frombuffer(bytes(draft).translate(_UPPER), dtype=np.uint8)
 
 
-def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece=0, offset=0):
+def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece=0, offset=0, filled=False):
     """The records of ONE piece.  positions / indices / labels: its keys after the merge -- sorted by (position, index), one
     entry per key, labels 0..4 -- and phred the winners' (None: the contig has no qualities, every record gets 0).  draft: the
     draft letters from draft_start on, covering [positions[0], positions[-1]].  piece / offset: the piece's place among the
-    contig's pieces and the letters in front of it."""
+    contig's pieces and the letters in front of it.  filled: the records of the filled consensus -- the contig's one piece; every
+    offset also counts the positions in front of the piece and the positions without a key in front of the record's own."""
     positions = np.asarray(positions, dtype=np.int64)
     if positions.size == 0:
         return np.zeros(0, EDIT_DTYPE)
@@ -61,6 +70,10 @@ def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece
                          (draft_start, draft_start + draft.size, positions[0], positions[-1]))
     is_letter = letters != 0
     before = offset + np.cumsum(is_letter) - is_letter               # letters in front of every key
+    first = np.ones(positions.size, dtype=bool)                      # the first key of every position
+    first[1:] = positions[1:] != positions[:-1]
+    if filled:                                                       # and the draft's letters: every position in front of the
+        before = before + positions - (np.cumsum(first) - 1)         # key's own that has no key (from position 0 on)
     at0, deeper = indices == 0, indices > 0
     d = draft[positions - draft_start]
     sub = at0 & is_letter & (letters != d)
@@ -70,9 +83,7 @@ def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece
     kind = np.where(sub, SUB, np.where(dele, DEL, INS))
     parts = [(positions[keep], before[keep], indices[keep], kind[keep], np.where(ins, 0, d)[keep], np.where(dele, 0, letters)[keep],
               phred[keep])]
-    # the first key of every position: a position whose keys start above index 0 has an empty slot (p, 0)
-    first = np.ones(positions.size, dtype=bool)
-    first[1:] = positions[1:] != positions[:-1]
+    # a position whose keys start above index 0 has an empty slot (p, 0)
     hole = first & deeper
     zeros = np.zeros(int(hole.sum()), np.int64)
     parts.append((positions[hole], before[hole], zeros, zeros + DEL, d[hole], zeros, zeros))
@@ -81,6 +92,8 @@ def records_numpy(positions, indices, labels, phred, draft, draft_start=0, piece
     run = np.flatnonzero(positions[heads][1:] - positions[heads][:-1] > 1)
     zeros = np.zeros(run.size, np.int64)
     open_at, close_at, lead = positions[heads][run] + 1, positions[heads][run + 1] - 1, before[heads][run + 1]
+    if filled:                                                        # the run's own letters lie behind its offset
+        lead = lead - (close_at - open_at + 1)
     parts.append((open_at, lead, zeros, zeros + GAP_OPEN, draft[open_at - draft_start], zeros, zeros))
     parts.append((close_at, lead, zeros, zeros + GAP_CLOSE, draft[close_at - draft_start], zeros, zeros))
     columns = [np.concatenate([p[k] for p in parts]) for k in range(7)]
@@ -104,9 +117,10 @@ def place(records, piece, offset):
     return records
 
 
-def _record_hunks(records, has_qualities):
+def _record_hunks(records, has_qualities, filled=False):
     """The hunks the records of ONE piece give, as columns: (draft_start, draft_end, polished_start, polished_end, kind, draft
-    text, polished text, min_phred), lists of equal length in record order."""
+    text, polished text, min_phred), lists of equal length in record order.  filled: a GAP pair is a `filled` hunk whose polished
+    interval is as long as its draft interval."""
     if records.size == 0:
         return tuple([] for _ in range(8))
     kind = records["kind"]
@@ -122,23 +136,26 @@ def _record_hunks(records, has_qualities):
     d0 = p + (kind == INS)
     d1 = np.where(gap, close_at + 1, p + 1)
     o1 = o + ((kind == SUB) | (kind == INS))
+    if filled:
+        o1 = np.where(gap, o + d1 - d0, o1)
     join = np.zeros(p.size, dtype=bool)
     join[1:] = ~gap[1:] & ~gap[:-1] & (d0[1:] == d1[:-1]) & (o[1:] == o1[:-1])
     starts = np.flatnonzero(~join)
     ends = np.append(starts[1:], p.size) - 1
     h_d0, h_d1, h_o0, h_o1, h_gap = d0[starts], d1[ends], o[starts], o1[ends], gap[starts]
     dn, on = h_d1 - h_d0, h_o1 - h_o0
-    names = np.array(HUNK_KINDS)[np.where(h_gap, 4, np.where(dn == on, 0, np.where(dn == 0, 1, np.where(on == 0, 2, 3))))]
+    names = np.array(HUNK_KINDS)[np.where(h_gap, 6 if filled else 4, np.where(dn == on, 0, np.where(dn == 0, 1, np.where(on == 0, 2, 3))))]
     # the letters: every SUB and DEL brings one draft letter, every SUB and INS one polished letter, so a hunk's texts are dn and
     # on letters of the two streams
     units = records[unit]
     draft_text = units["draft"][(kind == SUB) | (kind == DEL)].tobytes().decode()
     polished_text = units["letter"][(kind == SUB) | (kind == INS)].tobytes().decode()
-    da = np.cumsum(np.where(h_gap, 0, dn)) - np.where(h_gap, 0, dn)
-    oa = np.cumsum(np.where(h_gap, 0, on)) - np.where(h_gap, 0, on)
+    dn, on = np.where(h_gap, 0, dn), np.where(h_gap, 0, on)          # a run brings no letters of either stream
+    da = np.cumsum(dn) - dn
+    oa = np.cumsum(on) - on
     low = np.minimum.reduceat(units["phred"], starts)
-    texts_d = [draft_text[a:a + n] or "." for a, n in zip(da.tolist(), np.where(h_gap, 0, dn).tolist())]
-    texts_o = [polished_text[a:a + n] or "." for a, n in zip(oa.tolist(), np.where(h_gap, 0, on).tolist())]
+    texts_d = [draft_text[a:a + n] or "." for a, n in zip(da.tolist(), dn.tolist())]
+    texts_o = [polished_text[a:a + n] or "." for a, n in zip(oa.tolist(), on.tolist())]
     phreds = [str(q) if has_qualities and not g else "." for q, g in zip(low.tolist(), h_gap.tolist())]
     return (h_d0.tolist(), h_d1.tolist(), h_o0.tolist(), h_o1.tolist(), names.tolist(), texts_d, texts_o, phreds)
 
@@ -172,6 +189,32 @@ def _hunk_blocks(records, pieces, draft_length, has_qualities):
         yield [(0, draft_length, 0, 0, "uncovered", ".", ".", ".")]
 
 
+def _filled_blocks(records, pieces, draft_length, has_qualities):
+    """filled_hunks(), as _hunk_blocks gives hunks(): the leading run, the piece's hunks, the trailing run."""
+    records = np.asarray(records, dtype=EDIT_DTYPE)
+    if len(pieces) > 1 or (not pieces and records.size) or (records.size and records["piece"].any()):
+        raise ValueError("a filled consensus has one piece")
+    if not pieces:
+        if draft_length > 0:
+            yield [(0, draft_length, 0, draft_length, "filled", ".", ".", ".")]
+        return
+    first, last, length = pieces[0]
+    if last >= draft_length:
+        raise ValueError("the piece ends at position %d, the draft has %d letters" % (last, draft_length))
+    if first > 0:
+        yield [(0, first, 0, first, "filled", ".", ".", ".")]
+    yield list(zip(*_record_hunks(records, has_qualities, filled=True)))
+    if last + 1 < draft_length:
+        yield [(last + 1, draft_length, length - (draft_length - last - 1), length, "filled", ".", ".", ".")]
+
+
+def filled_hunks(records, pieces, draft_length, has_qualities):
+    """hunks() for the records of a FILLED consensus (pieces: its one piece, or none for a contig without a prediction): a
+    GAP_OPEN / GAP_CLOSE pair is one `filled` hunk whose polished interval holds the draft's letters, and from the piece bounds
+    come `filled` hunks for [0, first) and (last, draft_length)."""
+    return [hunk for block in _filled_blocks(records, pieces, draft_length, has_qualities) for hunk in block]
+
+
 def hunks(records, pieces, draft_length, has_qualities):
     """-> [(draft_start, draft_end, polished_start, polished_end, kind, draft, polished, min_phred)] in the consensus' order;
     0-based half-open coordinates, '.' for an empty column.  pieces: [(first, last, length)] in the order of the consensus.
@@ -185,11 +228,11 @@ def hunks(records, pieces, draft_length, has_qualities):
     return [hunk for block in _hunk_blocks(records, pieces, draft_length, has_qualities) for hunk in block]
 
 
-def summary(hunk_list, total=None):
-    """Bases per hunk kind: draft bases for sub / del / uncovered / duplicated, polished bases for ins, both for complex
-    (total: a summary to add to)."""
+def summary(hunk_list, total=None, filled=False):
+    """Bases per hunk kind: draft bases for sub / del / uncovered / duplicated / filled, polished bases for ins, both for complex
+    (total: a summary to add to; filled: a new summary has a `filled` count, behind the others)."""
     if total is None:
-        total = dict.fromkeys(("sub", "ins", "del", "complex_draft", "complex_polished", "uncovered", "duplicated"), 0)
+        total = dict.fromkeys(SUMMARY_KEYS + (("filled",) if filled else ()), 0)
     for d0, d1, o0, o1, kind, _, _, _ in hunk_list:
         if kind == "complex":
             total["complex_draft"] += d1 - d0
@@ -201,18 +244,24 @@ def summary(hunk_list, total=None):
     return total
 
 
-def write_edits(file, contig, hunk_list, draft_length, polished_length, blocks=False):
-    """One line per hunk, then the contig's summary line (blocks: hunk_list is an iterable of lists of hunks)."""
+def write_edits(file, contig, hunk_list, draft_length, polished_length, blocks=False, filled=False):
+    """One line per hunk, then the contig's summary line (blocks: hunk_list is an iterable of lists of hunks; filled: the
+    summary line ends with filled=<bases>)."""
     total = None
     for block in (hunk_list if blocks else [hunk_list]):
         file.writelines(contig + "\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%s\n" % hunk for hunk in block)
-        total = summary(block, total)
+        total = summary(block, total, filled)
     file.write("##contig=" + contig + "\tdraft_length=" + str(draft_length) + "\tpolished_length=" + str(polished_length) +
-               "".join("\t%s=%d" % kv for kv in (total or summary([])).items()) + "\n")
+               "".join("\t%s=%d" % kv for kv in (total or summary([], None, filled)).items()) + "\n")
 
 
-def write_contig(file, contig, records, pieces, draft_length, has_qualities):
-    """hunks() + write_edits(), piece by piece: what both stitch forms call per contig (pieces: [(first, last, length)])."""
+def write_contig(file, contig, records, pieces, draft_length, has_qualities, filled=False):
+    """hunks() + write_edits(), piece by piece: what both stitch forms call per contig (pieces: [(first, last, length)]).
+    filled: filled_hunks() instead; a contig without a piece is the whole draft."""
+    if filled:
+        write_edits(file, contig, _filled_blocks(records, pieces, draft_length, has_qualities), draft_length,
+                    pieces[0][2] if pieces else draft_length, blocks=True, filled=True)
+        return
     write_edits(file, contig, _hunk_blocks(records, pieces, draft_length, has_qualities), draft_length, sum(p[2] for p in pieces),
                 blocks=True)
 
@@ -239,3 +288,29 @@ def apply(draft_sequence, records, pieces):
         text = np.concatenate([letters[keep], mine["letter"][ins]])
         out.append(text[np.argsort(key, kind="stable")].tobytes().decode())
     return "".join(out)
+
+
+def apply_filled(draft_sequence, records, pieces):
+    """apply() for the records of a FILLED consensus: the whole contig again.  Inside the one piece a position gives its draft
+    letter upper-cased unless a DEL takes it or a SUB replaces it; a position of a GAP run, and every position in front of the
+    piece and behind it, gives its draft letter as the draft has it."""
+    records = np.asarray(records, dtype=EDIT_DTYPE)
+    raw = np.frombuffer(draft_sequence.encode() if isinstance(draft_sequence, str) else bytes(draft_sequence), dtype=np.uint8)
+    if not pieces:
+        return raw.tobytes().decode()
+    if len(pieces) > 1 or records["piece"].any():
+        raise ValueError("a filled consensus has one piece")
+    first, last, _length = pieces[0]
+    position = records["position"].astype(np.int64)
+    kind = records["kind"]
+    letters = upper_bytes(draft_sequence)[first:last + 1].copy()
+    keep = np.ones(letters.size, dtype=bool)
+    keep[position[kind == DEL] - first] = False
+    for a, b in zip(position[kind == GAP_OPEN], position[kind == GAP_CLOSE]):
+        letters[a - first:b - first + 1] = raw[a:b + 1]
+    letters[position[kind == SUB] - first] = records["letter"][kind == SUB]
+    ins = kind == INS
+    key = np.concatenate([(np.arange(first, last + 1, dtype=np.int64) << 16)[keep],
+                          (position[ins] << 16) | records["index"][ins].astype(np.int64)])
+    text = np.concatenate([letters[keep], records["letter"][ins]])
+    return (raw[:first].tobytes() + text[np.argsort(key, kind="stable")].tobytes() + raw[last + 1:].tobytes()).decode()

@@ -11,6 +11,9 @@ qualities=True (opt-in, not in the reference): the phred_score of the row that s
 comes out as Sanger text, chr(33 + min(phred, 93)); a winning gap gives neither a letter nor a quality.
 edits=<draft FASTA> (opt-in, not in the reference): every piece also gives the records of what it changed against the draft
 (pepper_amd/polish/Edits.py); a worker reads the span of the draft its piece covers from the file itself.
+fill=<draft FASTA> (opt-in, not in the reference): the contig is merged as ONE piece whatever `threads` is, and every position of
+the draft that has no key gives the draft's own letter (in the case the file stores it, quality '!'): the consensus is complete
+and does not depend on the thread count.  Edits taken with it are those of the filled consensus (Edits.py, FILL).
 Pinned: tests/golden/polish_stitch_ref.fa is the reference's own output on the same prediction arrays.
 """
 import concurrent.futures
@@ -31,14 +34,15 @@ def chunks(file_names, threads):
     return [file_names[i:i + threads] for i in range(0, len(file_names), threads)]
 
 
-def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None):
+def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None, fill=None):
     """One piece of the consensus.  The merge runs inside the I/O library (pa_h5_stitch_polish_regions: chunk rows straight
     from the mapped prediction files, each chunk merged into the tail of the piece; 3 k -> see DESIGN.md chunks/s);
     PEPPER_AMD_STITCH_NUMPY=1 keeps the numpy form below, which tests hold it to.  qualities: (first, last, sequence, quality),
     always through the numpy form (the library's merge carries no phred).  edits: the draft FASTA's path; the piece's edit
-    records (piece 0, offsets from the piece's first letter) follow as one more element, through the numpy form as well."""
-    if qualities or edits is not None:
-        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=qualities, edits=edits)
+    records (piece 0, offsets from the piece's first letter) follow as one more element, through the numpy form as well.
+    fill: the draft FASTA's path; the keys are the whole contig's and the piece comes out filled (numpy form)."""
+    if qualities or edits is not None or fill is not None:
+        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=qualities, edits=edits, fill=fill)
     if os.environ.get("PEPPER_AMD_STITCH_NUMPY") == "1":
         return small_chunk_stitch_numpy(contig, small_chunk_keys)
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
@@ -58,7 +62,51 @@ def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None):
             f.close()
 
 
-def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=None):
+def filled_piece(draft, first, positions, letters, quality):
+    """The filled consensus of a contig: draft (uint8, the whole contig as stored), the merged keys' positions and letters (0: no
+    letter), quality (the letters' Sanger bytes, or None) -> (sequence, quality or None) as uint8 arrays.  Every position of the
+    draft without a key gives draft[p] and '!'."""
+    last = int(positions[-1])
+    is_letter = letters != 0
+    slot = positions - first
+    covered = np.zeros(last - first + 1, dtype=bool)
+    covered[slot] = True
+    holes = np.cumsum(~covered) - ~covered                           # uncovered positions of the piece in front of every position
+    per_position = np.bincount(slot, weights=is_letter, minlength=covered.size).astype(np.int64)
+    letters_before = np.cumsum(per_position) - per_position
+    n_letters, n_holes, tail = int(is_letter.sum()), int((~covered).sum()), draft.size - last - 1
+    out = np.empty(first + n_letters + n_holes + tail, dtype=np.uint8)
+    out[:first] = draft[:first]
+    out[out.size - tail:] = draft[last + 1:]
+    at_letter = first + np.flatnonzero(is_letter) - np.cumsum(~is_letter)[is_letter] + holes[slot[is_letter]]
+    out[at_letter] = letters[is_letter]
+    empty = np.flatnonzero(~covered)
+    at_hole = first + letters_before[empty] + holes[empty]
+    out[at_hole] = draft[first + empty]
+    if quality is None:
+        return out, None
+    text = np.full(out.size, 33, dtype=np.uint8)
+    text[at_letter] = quality
+    return out, text
+
+
+def whole_draft(fill, contig):
+    """A contig of the draft as the filled consensus of no prediction: (sequence, quality) -- its letters as stored, all '!'."""
+    from pepper_amd.variant.fasta import FASTA_handler
+    draft = FASTA_handler(fill)
+    try:
+        length = draft.get_chromosome_sequence_length(contig)
+        if length < 0:
+            raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+        sequence = draft.get_reference_bytes(contig, 0, length, stored_case=True).decode()
+    finally:
+        draft.close()
+    return sequence, "!" * len(sequence)
+
+
+def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=None, fill=None):
+    if fill is not None and edits is not None and str(edits) != str(fill):
+        raise ValueError("with fill the edits are taken against the draft that fills: %s is not %s" % (edits, fill))
     want_qualities = qualities
     qualities = qualities or edits is not None          # the edit records carry the winners' phred
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
@@ -127,6 +175,25 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=No
         phred = np.concatenate(phred_parts)[order][last]
         if want_qualities:
             result += ((33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8).tobytes().decode(),)
+    if fill is not None:                  # the whole contig of the draft is read, and the records are those of the filled piece
+        from pepper_amd.variant.fasta import FASTA_handler
+        draft = FASTA_handler(fill)
+        try:
+            length = draft.get_chromosome_sequence_length(contig)
+            if length < 0:
+                raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+            if length <= result[1]:
+                raise ValueError("the draft FASTA %s has no letter at position %d of %s" % (fill, result[1], contig))
+            stored = np.frombuffer(draft.get_reference_bytes(contig, 0, length, stored_case=True), dtype=np.uint8)
+        finally:
+            draft.close()
+        text, quality = filled_piece(stored, result[0], positions[last], letters,
+                                     (33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8) if want_qualities else None)
+        result = result[:2] + (text.tobytes().decode(),) + ((quality.tobytes().decode(),) if want_qualities else ())
+        if edits is not None:
+            from pepper_amd.polish import Edits
+            result += (Edits.records_numpy(positions[last], indices[last], labels, np.minimum(phred, 255), stored, filled=True),)
+        return result
     if edits is not None:                 # only the span the piece covers is read from the draft
         from pepper_amd.variant.fasta import FASTA_handler
         draft = FASTA_handler(edits)
@@ -140,14 +207,29 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=No
     return result
 
 
-def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False, edits=None):
+def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False, edits=None, fill=None):
     """The consensus of one contig; qualities: (sequence, quality), the pieces' qualities concatenated as their letters are.
     edits (the draft FASTA's path): (sequence, quality or None, records, pieces) -- the contig's edit records and its pieces
-    [(first, last, length)], both in the order of the consensus (pepper_amd/polish/Edits.py)."""
+    [(first, last, length)], both in the order of the consensus (pepper_amd/polish/Edits.py).
+    fill (the draft FASTA's path): the same forms for the FILLED consensus -- every region of the contig in one piece, in the
+    order they are iterated here, and the draft's letters where no key is; `threads` does not shape it."""
     extra = (bool(qualities), edits) if edits is not None else (True,) if qualities else ()
     key_list = sorted(((file_name, contig, int(contig_start), int(contig_end))
                        for file_name, _, contig_start, contig_end in sorted(sequence_chunk_keys, key=lambda e: e[1])),
                       key=lambda e: (e[2], e[3]))
+    if fill is not None:
+        piece = small_chunk_stitch(contig, key_list, bool(qualities), edits, fill)
+        if piece[0] == -1 or piece[1] == -1:                      # no kept row: the draft as it is
+            sequence, quality = whole_draft(fill, contig)
+            piece, pieces = (-1, -1, sequence) + ((quality,) if qualities else ()), []
+            records = None
+        else:
+            pieces, records = [(piece[0], piece[1], len(piece[2]))], piece[-1]
+        if edits is not None:
+            from pepper_amd.polish import Edits
+            return (piece[2], piece[3] if qualities else None, records if records is not None else np.zeros(0, Edits.EDIT_DTYPE),
+                    pieces)
+        return (piece[2], piece[3]) if qualities else piece[2]
     file_chunks = chunks(key_list, max(MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING, int(len(key_list) / max(1, threads)) + 1))
     if threads <= 1 or len(file_chunks) <= 1:
         results = [small_chunk_stitch(contig, chunk, *extra) for chunk in file_chunks]

@@ -7,6 +7,9 @@ qualities=True (opt-in, not in the reference) also writes `<output_path>_pepper_
 phred of the prediction row that supplied each base, as Sanger text.
 edits=<draft FASTA> (opt-in, not in the reference) also writes `<output_path>_pepper_polished.edits.tsv`: what the consensus
 changed against the draft, hunk by hunk in both coordinate systems (pepper_amd/polish/Edits.py).
+fill=<draft FASTA> (opt-in, not in the reference): every contig is merged as one piece and the draft's own letters stand where no
+prediction covered a position, so the consensus is complete and does not depend on `threads`; unpolished_contigs=True also
+writes the contigs of the draft that have no prediction, unchanged, in natural order among the rest.
 """
 import contextlib
 import re
@@ -17,7 +20,7 @@ from os.path import isfile, join
 from pathlib import Path
 
 from pepper_amd import h5
-from pepper_amd.polish.Stitch import create_consensus_sequence
+from pepper_amd.polish.Stitch import create_consensus_sequence, whole_draft
 
 
 def natural_key(string_):
@@ -55,7 +58,31 @@ def draft_lengths(draft_fasta):
         handler.close()
 
 
-def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None):
+def check_fill(edits, fill, unpolished_contigs):
+    """What every stitch form asks of its fill arguments."""
+    if unpolished_contigs and fill is None:
+        raise ValueError("unpolished_contigs needs fill: the draft FASTA the contigs are taken from")
+    if fill is not None and edits is not None and str(edits) != str(fill):
+        raise ValueError("with fill the edits are taken against the draft that fills: %s is not %s" % (edits, fill))
+
+
+def write_unpolished(contig, fill, draft_length, fasta, fastq, edits_file):
+    """A contig of the draft without a prediction, as the filled consensus of nothing: its letters as stored, qualities '!',
+    one `filled` hunk."""
+    sequence, quality = whole_draft(fill, contig)
+    _log("NO PREDICTION FOR " + contig + ", DRAFT SEQUENCE LENGTH: " + str(len(sequence)) + ".")
+    if edits_file is not None:
+        from pepper_amd.polish import Edits
+        Edits.write_contig(edits_file, contig, [], [], draft_length, True, filled=True)
+    if len(sequence) > 0:
+        fasta.write('>' + contig + "\n")
+        fasta.write(sequence + "\n")
+        if fastq is not None:
+            write_fastq_record(fastq, contig, sequence, quality)
+
+
+def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None, fill=None, unpolished_contigs=False):
+    check_fill(edits, fill, unpolished_contigs)
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -69,12 +96,16 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
     with contextlib.ExitStack() as files:
         consensus_fasta_file = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
+        edits_file = None
         if edits is not None:
             from pepper_amd.polish import Edits
-            lengths = draft_lengths(edits)
             edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
             edits_file.write(Edits.HEADER)
-        for contig in sorted(all_contigs, key=natural_key):
+        lengths = draft_lengths(fill if fill is not None else edits) if edits is not None or fill is not None else {}
+        for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
+            if contig not in all_contigs:
+                write_unpolished(contig, fill, lengths[contig], consensus_fasta_file, fastq, edits_file)
+                continue
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
             for prediction_file in all_prediction_files:
@@ -83,16 +114,16 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
                         continue
                     # every region group with its contig_start / contig_end in one library call (names in sorted order)
                     all_chunk_keys.extend((prediction_file, name, start, end) for name, start, end in hdf5_file.list_polish_regions(contig))
+            if (edits is not None or fill is not None) and contig not in lengths:
+                raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
             if edits is not None:
-                if contig not in lengths:
-                    raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
                 consensus_sequence, quality, records, pieces = create_consensus_sequence(contig, all_chunk_keys, threads,
-                                                                                         qualities=qualities, edits=edits)
-                Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True)
+                                                                                         qualities=qualities, edits=edits, fill=fill)
+                Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None)
             elif qualities:
-                consensus_sequence, quality = create_consensus_sequence(contig, all_chunk_keys, threads, qualities=True)
+                consensus_sequence, quality = create_consensus_sequence(contig, all_chunk_keys, threads, qualities=True, fill=fill)
             else:
-                consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads)
+                consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads, fill=fill)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(consensus_sequence)) + ".")
             if consensus_sequence is not None and len(consensus_sequence) > 0:
                 consensus_fasta_file.write('>' + contig + "\n")

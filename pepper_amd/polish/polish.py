@@ -19,7 +19,7 @@ def _log(message):
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
            num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0, device_stitch=None,
-           keep_predictions=None, qualities=None, edits=None):
+           keep_predictions=None, qualities=None, edits=None, fill=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
@@ -33,7 +33,12 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     edits (default: PEPPER_AMD_POLISH_EDITS=1): step 3 also writes <output>_pepper_polished.edits.tsv, what the consensus changed
     against fasta_filepath hunk by hunk in both coordinate systems (pepper_amd/polish/Edits.py; not in the reference); in the
     fused device-stitch form the comparison runs on the device and the phred goes to the stitcher as with qualities
-    (stage_walls["device_stitch_edits"]: the records, the bytes that came back, the seconds of the comparison and of the text)."""
+    (stage_walls["device_stitch_edits"]: the records, the bytes that came back, the seconds of the comparison and of the text).
+    fill (default: PEPPER_AMD_POLISH_FILL=1): step 3 writes a COMPLETE consensus -- every contig merged as one piece, so the files
+    do not depend on `threads`, the letters of fasta_filepath (as stored, quality '!') where no prediction covered a position, and
+    without a region the contigs no prediction names, unchanged (perform_stitch(..., fill=, unpolished_contigs=); not in the
+    reference).  In the device forms the filling runs on the device (stage_walls["device_stitch_fill"] in the fused form: the runs
+    and letters filled, the seconds)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     if qualities is None:
@@ -42,6 +47,9 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     if edits is None:
         edits = _lib.polish_edits()
     draft_fasta = fasta_filepath if edits else None
+    if fill is None:
+        fill = _lib.polish_fill()
+    fill_kw = dict(fill=fasta_filepath, unpolished_contigs=region is None) if fill else {}
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
         if not os.path.isfile(path):
             raise FileNotFoundError("CAN NOT LOCATE " + what + " FILE: " + str(path))
@@ -90,11 +98,13 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         t2 = time.perf_counter()
     _log("STEP 3: RUNNING STITCH -> " + output_dir)
     if not device_stitch:
-        perform_stitch(prediction_output_directory, output_dir, threads, qualities=qualities, edits=draft_fasta)
+        perform_stitch(prediction_output_directory, output_dir, threads, qualities=qualities, edits=draft_fasta, **fill_kw)
     elif not fused_inference:
         from pepper_amd.polish.DeviceStitch import stitch_directory
         stitch_directory(prediction_output_directory, output_dir, threads, device=parse_device_ids(device_ids)[0], qualities=qualities,
-                         edits=draft_fasta)
+                         edits=draft_fasta, **fill_kw)
+    elif stitcher is None and fill:          # (no chunk was predicted: the draft's contigs as they are, or nothing of a region)
+        perform_stitch(prediction_output_directory, output_dir, threads, qualities=qualities, edits=draft_fasta, **fill_kw)
     elif stitcher is None:                   # (no chunk was predicted: perform_stitch over no files writes an empty FASTA)
         open(output_dir + '_pepper_polished.fa', 'w').close()
         if qualities:
@@ -106,13 +116,15 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     else:
         try:
             if qualities:
-                stitcher.write_fastq(output_dir, threads, edits=draft_fasta)
+                stitcher.write_fastq(output_dir, threads, edits=draft_fasta, **fill_kw)
             else:
-                stitcher.write_fasta(output_dir, threads, edits=draft_fasta)
+                stitcher.write_fasta(output_dir, threads, edits=draft_fasta, **fill_kw)
             if stage_walls is not None:
                 stage_walls["device_stitch_stats"] = stitcher.stats()
                 if edits:
                     stage_walls["device_stitch_edits"] = dict(stitcher.edit_totals)
+                if fill:
+                    stage_walls["device_stitch_fill"] = dict(stitcher.fill_totals)
         finally:
             stitcher.close()
     if stage_walls is not None:

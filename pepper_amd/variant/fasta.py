@@ -84,9 +84,9 @@ class FASTA_handler(object):
             return -1
         return self._index[chromosome_name][0]
 
-    def get_reference_bytes(self, region, start, stop):
+    def get_reference_bytes(self, region, start, stop, stored_case=False):
         """get_reference_sequence as upper-case bytes (what the encoders take; image generation fetches a whole group of
-        intervals with one call and slices it)."""
+        intervals with one call and slices it).  stored_case: the letters in the case the file stores them."""
         if region not in self._index:
             raise KeyError("CHROMOSOME NAME NOT PRESENT IN REFERENCE FASTA FILE: %s %d %d" % (region, start, stop))
         length, offset, line_bases, line_width = self._index[region]
@@ -98,7 +98,7 @@ class FASTA_handler(object):
         last = offset + ((stop - 1) // line_bases) * line_width + (stop - 1) % line_bases
         self._fh.seek(first)
         raw = self._fh.read(last - first + 1)
-        return raw.translate(_UPPER, b"\n\r")               # line ends out and upper case in one pass
+        return raw.translate(None if stored_case else _UPPER, b"\n\r")      # line ends out and upper case in one pass
 
     def get_reference_sequence(self, region, start, stop):
         return self.get_reference_bytes(region, start, stop).decode()

@@ -6,7 +6,11 @@ numpy merge with a phred column) and, with --device, stitch_directory(..., quali
 --edits runs the set with the edits on as well, against a seeded random draft (the labels are random too, so four slots in five
 are an edit: the record buffer's worst case, not a polished assembly's share) -- perform_stitch(..., edits=draft) on the host and,
 with --device, stitch_directory(..., edits=draft) -- and checks the two .edits.tsv files equal.
-    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits]"""
+--fill runs the set with fill on as well, against the same draft (the job's rows cover the draft but for its last 1 200 letters, so
+the filling is one trailing run) -- perform_stitch(..., fill=draft) on the host and, with --device, stitch_directory(..., fill=draft),
+checked against the host's FASTA -- and then, on one handle that holds the job's rows, times finish + take without fill beside
+finish + fill + take (one warm-up and three timed calls each; pa_stitcher_fill's own seconds beside them).
+    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits] [--fill]"""
 import argparse
 import json
 import os
@@ -23,6 +27,52 @@ from pepper_amd.polish.DataStorePredict import DataStore  # noqa: E402
 from pepper_amd.polish.perform_stitch import perform_stitch  # noqa: E402
 
 
+def device_fill_legs(pred, tmp, draft_fa, regions):
+    """stitch_directory with fill against the host's file, then finish + take beside finish + fill + take on one handle."""
+    import statistics
+
+    from pepper_amd import h5
+    from pepper_amd.polish.DeviceStitch import DeviceStitcher, _Held, _read_region, stitch_directory
+    from pepper_amd.polish.perform_stitch import get_file_paths_from_directory
+    runs = []
+    host = open(os.path.join(tmp, "outf1") + "_pepper_polished.fa", "rb").read()
+    for threads in (1, 8):
+        for repeat in range(2):
+            stats = {}
+            t0 = time.perf_counter()
+            out = stitch_directory(pred, os.path.join(tmp, "devf%d%d" % (threads, repeat)), threads, stats=stats, fill=draft_fa)
+            dt = time.perf_counter() - t0
+            runs.append({"merge": "device", "fill": True, "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
+                         "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                         "equals_host": open(out, "rb").read() == host, "stats": stats})
+    draft = open(draft_fa, "rb").read().split(b"\n")[1]
+    with DeviceStitcher(0) as st:
+        keys, held = [], _Held(st, "ctg0")
+        for prediction_file in get_file_paths_from_directory(pred):
+            with h5.File(prediction_file, 'r') as f:
+                for name, start, end in f.list_polish_regions("ctg0"):
+                    key, at = (prediction_file, name, start, end), 0
+                    keys.append(key)
+                    for block in _read_region(f, 'predictions/ctg0/ctg0-%d-%d' % (start, end)):
+                        held.take(key, at, *block)
+                        at += len(block[0])
+        held.flush()
+        legs = {}
+        for leg, kw in (("finish_take", {}), ("finish_fill_take", {"fill": draft})):
+            seconds = []
+            for repeat in range(4):                          # (the first call grows the handle's tables)
+                before = st.fill_totals["seconds"]
+                t0 = time.perf_counter()
+                sequence = st.finish("ctg0", 1, keys, **kw)
+                seconds.append((time.perf_counter() - t0, st.fill_totals["seconds"] - before))
+            legs[leg] = {"seconds": [round(s[0], 4) for s in seconds[1:]], "median": round(statistics.median(s[0] for s in seconds[1:]), 4),
+                         "fill_call_seconds": [round(s[1], 4) for s in seconds[1:]], "letters": len(sequence), "stats": st.stats()}
+        legs["ratio"] = round(legs["finish_fill_take"]["median"] / legs["finish_take"]["median"], 3)
+        legs["fill_counts"] = st.last_fill_counts
+        runs.append({"merge": "device", "fill": "one handle", **legs})
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=65536)
@@ -31,6 +81,7 @@ def main():
     ap.add_argument("--device", action="store_true", help="also run the set through the device stitch")
     ap.add_argument("--qualities", action="store_true", help="also run the set with qualities on (FASTQ beside the FASTA)")
     ap.add_argument("--edits", action="store_true", help="also run the set with the edits on (.edits.tsv beside the FASTA)")
+    ap.add_argument("--fill", action="store_true", help="also run the set with fill on (the draft where no row covered it)")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
@@ -73,12 +124,13 @@ def main():
                 runs.append({"merge": "numpy", "qualities": True, "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                              "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
-        if args.edits:
+        if args.edits or args.fill:
             os.environ["PEPPER_AMD_STITCH_NUMPY"] = "0"
             draft_fa = os.path.join(tmp, "draft.fa")
             with open(draft_fa, "w") as fh:                 # as long as the positions reach
                 fh.write(">ctg0\n" + np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(5).integers(0, 4, regions * 1000 + 2400)]
                          .tobytes().decode() + "\n")
+        if args.edits:
             for threads in (1, 8):
                 t0 = time.perf_counter()
                 out = perform_stitch(pred, os.path.join(tmp, "oute%d" % threads), threads, edits=draft_fa)
@@ -87,6 +139,13 @@ def main():
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                              "edits_tsv_bytes": os.path.getsize(out[:-len(".fa")] + ".edits.tsv"),
                              "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
+        if args.fill:
+            for threads in (1, 8):
+                t0 = time.perf_counter()
+                out = perform_stitch(pred, os.path.join(tmp, "outf%d" % threads), threads, fill=draft_fa)
+                dt = time.perf_counter() - t0
+                runs.append({"merge": "numpy", "fill": True, "threads": threads, "seconds": round(dt, 2),
+                             "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out)})
         if args.device:
             from pepper_amd.polish.DeviceStitch import stitch_directory
             host = {threads: open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read() for threads in (1, 8)}
@@ -123,6 +182,8 @@ def main():
                                  "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                                  "equals_host": open(out, "rb").read() == host[threads], "edits_tsv_equals_host": tsv == host_tsv,
                                  "edits_tsv_bytes": len(tsv), "stats": stats})
+            if args.fill:
+                runs.extend(device_fill_legs(pred, tmp, draft_fa, regions))
         from pepper_amd.hostinfo import usable_cpus
         print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
