@@ -233,6 +233,17 @@ int pa_encoder_pair_live(pa_encoder* e, uint8_t* keep, int64_t n);
 int pa_encoder_set_device_candidates(pa_encoder* e, int32_t on);
 int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host);
 
+/* Targets of the contig the next calls' regions lie on: n disjoint, ascending, non-touching half-open intervals
+ * [start[i], end[i]) in contig coordinates.  A position outside all of them carries no candidate (it fails the
+ * per-position pass as if outside candidate_region_start.._end); summary matrix and windows are unchanged.
+ * n == 0: no restriction (the state of a new handle).  The table is copied to the device in this call and holds for every
+ * later stage / run of the handle, pa_encoder_run_staged repeated included, until set again.  A table that is not of that
+ * form (start >= end, a negative start, an interval that does not begin behind the end of the one before it) is refused with
+ * PA_ERR_INVALID, pa_last_error names the interval's index, and the handle keeps the table it had.  With a table set,
+ * target_rows_kernel (csrc/encoder.hip) writes one verdict per matrix row in front of tile_count_kernel, which reads it in its
+ * per-position pass; without one it is not launched.  The polish encoder and the polish chain ignore the table. */
+int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const int64_t* end);
+
 /* Times of the last run in milliseconds, HIP events on the encoder's stream: [0] record kernels (segment_reads x 2 +
  * tile_offsets), [1] tile_count_kernel, [2] compact_votes_kernel + pack_results_kernel, [3] gather_windows_kernel; host clock:
  * [4] candidate enumeration, [5] the whole run, [6], [7] parts of [4]; packed form: [8] upload of arena + tables,

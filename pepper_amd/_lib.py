@@ -111,6 +111,7 @@ SYMBOLS = [
     ("pa_encoder_pair_live", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_encoder_set_device_candidates", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_encoder_candidate_calls", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    ("pa_encoder_set_targets", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     ("pa_encoder_last_timing", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_batch_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_get_results", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

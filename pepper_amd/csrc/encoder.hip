@@ -76,6 +76,7 @@ struct RegRec {                      // one region of the batch, as the kernels 
     int64_t ref_off;                 // first byte of its reference in d_ref
     int64_t row_base;                // first row of its matrix (multiple of 16: line-aligned tile stores)
     int64_t seq_base;                // first base of its reads in d_seq / d_qual
+    int64_t region_start;            // contig position of row 0 (target_rows_kernel)
     int32_t ref_len, L;              // L = region_end - region_start + 1; the matrix has L + 1 rows (row L stays zero)
     int32_t tile0, n_tiles;
     int32_t cand_lo, cand_hi;        // candidate_region_start / _end as rows (clamped into int32)
@@ -659,6 +660,51 @@ __global__ __launch_bounds__(1024) void tile_offsets_kernel(const int* __restric
     if (threadIdx.x == 0) tile_off[n_tiles] = carry;
 }
 
+// ---- targets (pa_encoder_set_targets) --------------------------------------------------------------------------------
+// One verdict per matrix row of the batch, laid out like `pass`: is the row's contig position inside one of the n disjoint,
+// ascending half-open intervals [t_start[i], t_end[i])?  One workgroup per tile, four rows per thread (row_base is a multiple
+// of 16 and a tile starts at a multiple of 512: every thread stores one aligned word).  The workgroup's stretch of the table
+// -- the intervals that can touch its 512 positions -- comes from two binary searches whose every operand is the same in all
+// lanes; a thread then searches that stretch (at most 257 intervals) for its first row and steps through its other three.
+constexpr int TRT = TP / 4;
+__global__ __launch_bounds__(TRT) void target_rows_kernel(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region,
+                                                          const int64_t* __restrict__ t_start, const int64_t* __restrict__ t_end,
+                                                          int64_t n, uint8_t* __restrict__ targets) {
+    const int tile = blockIdx.x;
+    const RegRec* reg = regions + tile_region[tile];
+    const int tile_lo = (tile - reg->tile0) * TP;
+    const int rows = (reg->L + 1 + 15) & ~15;      // the rows of `targets` that are this region's (region_pass)
+    const int64_t p0 = reg->region_start + tile_lo;
+    int64_t lo = 0, hi = n;                        // first interval that ends behind the tile's first position
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (t_end[mid] > p0) hi = mid; else lo = mid + 1;
+    }
+    const int64_t first = lo;
+    hi = n;                                        // first interval that starts behind the tile's last position
+    while (lo < hi) {
+        const int64_t mid = lo + ((hi - lo) >> 1);
+        if (t_start[mid] >= p0 + TP) hi = mid; else lo = mid + 1;
+    }
+    const int64_t last = lo;
+    const int r0 = tile_lo + 4 * (int)threadIdx.x;
+    if (r0 >= rows) return;
+    const int64_t p = reg->region_start + r0;
+    int64_t k = first;                             // first interval of the stretch that ends behind p
+    hi = last;
+    while (k < hi) {
+        const int64_t mid = k + ((hi - k) >> 1);
+        if (t_end[mid] > p) hi = mid; else k = mid + 1;
+    }
+    uint32_t word = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        while (k < last && t_end[k] <= p + j) ++k;
+        if (k < last && t_start[k] <= p + j) word |= 1u << (8 * j);
+    }
+    *reinterpret_cast<uint32_t*>(targets + reg->row_base + r0) = word;
+}
+
 // ---- the tile kernel -----------------------------------------------------------------------------------------------
 struct TileArgs {
     const ReadRec* reads; const RegRec* regions; const int32_t* tile_region;
@@ -666,6 +712,7 @@ struct TileArgs {
     const TileRec* recs; const int* tile_off; int rec_cap;
     int* mat; uint8_t* pass; SiteRec* sites; Vote* votes; Vote* votes_out; int vote_cap; int4* ovf; int ovf_cap; int* counters;
     int* region_counts;
+    const uint8_t* targets;   // verdicts of target_rows_kernel, one per row like `pass`; null: no targets set
     int debug;        // PA_TILE_DEBUG (profiling only, tools/tile_ablation.sh): parts of the kernel switched off
 };
 
@@ -1110,6 +1157,7 @@ __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileA
         const bool n = (double)n_ins / c >= reg.ins_thr;
         const bool d = (double)n_del / c >= reg.del_thr;
         passes = (s || n || d) && idx >= reg.cand_lo && idx <= reg.cand_hi && (double)cov >= reg.min_cov;
+        if (a.targets != nullptr) passes = passes && a.targets[reg.row_base + idx] != 0;
         a.pass[reg.row_base + idx] = passes ? 1 : 0;
         pass_s[tid] = passes ? 1 : 0;
         if (passes) {
@@ -1609,6 +1657,7 @@ struct pa_variant_batch {
     int64_t resident_bytes = 0;      // inflated bytes pa_encoder_inflate_bgzf left in d_arena (0: none)
     std::vector<int32_t> live;        // reads with a base inside each region (the reference's len(all_reads)) of the last run
     DBuf d_zero;                      // counters [CT_N] | per-region counts [2 n_regions] | tile_count [n_tiles] | tile_fill [n_tiles]: cleared per run
+    DBuf d_targets;                   // verdicts of target_rows_kernel for the staged batch's rows (pa_encoder_set_targets)
     DBuf d_tile_off, d_sorted, d_mat, d_pass, d_sites, d_votes, d_votes_out, d_sites_dense, d_votes_dense, d_ovf, d_cands, d_img32, d_img8;
     HBuf h_counts, h_sites, h_votes;
     // candidates enumerated on the device (pa_encoder_set_device_candidates): the rules of the staged regions, the per-site and
@@ -1758,6 +1807,7 @@ int region_pass(const pa_pileup& p, const pa_summary_params* q, const pa_summary
     if (p.region_end < p.region_start || p.region_end - p.region_start > (int64_t)1 << 28) return pa::set_error(PA_ERR_INVALID, "bad region");
     std::memset(&g, 0, sizeof(g));
     g.L = (int32_t)(p.region_end - p.region_start + 1);
+    g.region_start = p.region_start;
     if (!q) return PA_OK;
     if (q->feature_size < 26 || q->candidate_window_size < 2 || q->candidate_window_size > 254)
         return pa::set_error(PA_ERR_INVALID, "feature_size must be >= 26 and 2 <= candidate_window_size <= 254");
@@ -2186,6 +2236,14 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     ENC_ALLOC(b.d_ovf, (size_t)b.ovf_cap * sizeof(int4));
     ENC_ALLOC(b.d_pool, (size_t)b.pool_cap * POOL_SLOT);
     ENC_HIP(hipMemsetAsync(b.d_zero.p, 0, w.n_zero * 4, st));
+    const uint8_t* targets = nullptr;             // a table is set: the verdict of every row, in front of the timed kernels
+    if (e->n_targets > 0) {
+        ENC_ALLOC(b.d_targets, (size_t)b.total_rows + 64);
+        const int64_t* tab = e->d_target_table.as<int64_t>();
+        hipLaunchKernelGGL(target_rows_kernel, dim3((unsigned)b.n_tiles), dim3(TRT), 0, st, b.p_regions, b.p_tile_region, tab,
+                           tab + e->n_targets, e->n_targets, b.d_targets.as<uint8_t>());
+        targets = b.d_targets.as<uint8_t>();
+    }
     ENC_HIP(hipEventRecord(e->ev[0], st));
     const dim3 seg_grid((unsigned)((b.total_reads + 3) / 4));
     if (b.total_reads > 0)
@@ -2208,6 +2266,7 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     ta.ovf = b.d_ovf.as<int4>(); ta.ovf_cap = b.ovf_cap; ta.counters = w.counters; ta.region_counts = w.region_counts;
     static const int tile_debug = [] { const char* e = getenv("PA_TILE_DEBUG"); return e ? atoi(e) : 0; }();
     ta.debug = tile_debug;
+    ta.targets = targets;
     hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
     ENC_HIP(hipEventRecord(e->ev[2], st));
     hipLaunchKernelGGL(compact_votes_kernel, dim3((unsigned)std::min(2048, (w.vote_cap + 255) / 256)), dim3(256), 0, st, b.d_votes.as<Vote>(),
@@ -3009,6 +3068,28 @@ int pa_encoder_set_device_candidates(pa_encoder* e, int32_t on) {
     if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
     if (!e->variant) e->variant = new pa_variant_batch();
     e->variant->dev_cands = on != 0;
+    return PA_OK;
+}
+
+int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const int64_t* end) {
+    if (!e || n < 0 || (n > 0 && (!start || !end))) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (n > ((int64_t)1 << 28)) return pa::set_error(PA_ERR_INVALID, "targets: more than 2^28 intervals");
+    for (int64_t i = 0; i < n; ++i)                // (checked in full before anything of the handle changes)
+        if (start[i] < 0 || start[i] >= end[i] || (i > 0 && start[i] <= end[i - 1]))
+            return pa::set_error(PA_ERR_INVALID, "targets: interval " + std::to_string(i) +
+                                                     " is empty, negative, or not behind the end of the one before it");
+    if (n == 0) {
+        e->n_targets = 0;
+        return PA_OK;
+    }
+    ENC_HIP(hipSetDevice(e->device));
+    e->n_targets = 0;                              // (no table while the buffer may move)
+    ENC_ALLOC(e->d_target_table, (size_t)n * 16);
+    int64_t* tab = e->d_target_table.as<int64_t>();
+    ENC_HIP(hipMemcpyAsync(tab, start, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    ENC_HIP(hipMemcpyAsync(tab + n, end, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    e->n_targets = n;
     return PA_OK;
 }
 

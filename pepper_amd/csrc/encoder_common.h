@@ -165,6 +165,8 @@ struct pa_encoder {
     struct pa_realigner* realigner = nullptr;      // the polish image chain's re-aligner on this encoder's stream (made on first use)
     pa_sampler sampler;
     bool split_walk = false;                       // pa_encoder_set_split_slices: the record walk resolves CIGARs kept in the CG tag
+    int64_t n_targets = 0;                         // pa_encoder_set_targets: intervals of the table (0: no restriction) ...
+    pa_enc::DBuf d_target_table;                   // ... [start x n][end x n] on the device
     std::vector<int64_t> seq_off;                  // pa_encoder_set_seq_offsets: per packed read of the NEXT staging where its bases lie (-1: behind its operations)
 };
 

@@ -8,9 +8,11 @@ are injected objects with the reference's handler methods (`get_reads`, `get_ref
 htslib ingestion itself is out of scope here.  train_mode (truth-VCF labels)
 is not provided.
 """
+import contextlib
+
 import numpy as np
 
-from pepper_amd.variant import PEPPER_VARIANT
+from pepper_amd.variant import PEPPER_VARIANT, Targets
 from pepper_amd.variant.Options import ImageSizeOptions
 
 
@@ -78,9 +80,18 @@ class AlignmentSummarizer:
         if prepared is None:
             return None
         regional_summary, all_reads, args = prepared
-        if as_arrays:
-            return regional_summary.generate_summary_arrays(all_reads, *args)
-        return regional_summary.generate_summary(all_reads, *args)
+        with targets_of(bed_list, self.chromosome_name, getattr(options, "device", 0)):
+            if as_arrays:
+                return regional_summary.generate_summary_arrays(all_reads, *args)
+            return regional_summary.generate_summary(all_reads, *args)
+
+
+def targets_of(bed_list, chromosome_name, device):
+    """Around encoder calls of this thread on one contig: bed_list (options.region_bed as Targets.read_bed returns it; None:
+    no restriction, nothing is done) restricts their candidates to the contig's targets."""
+    if not bed_list:
+        return contextlib.nullcontext()
+    return PEPPER_VARIANT.thread_targets(Targets.table(bed_list, chromosome_name), device or 0)
 
 
 def create_summaries(prepared):

@@ -19,6 +19,7 @@ from datetime import datetime
 
 import numpy as np
 
+from pepper_amd.variant import Targets
 from pepper_amd.variant.AlignmentSummarizer import AlignmentSummarizer
 from pepper_amd.variant.DataStore import DataStore
 
@@ -184,7 +185,7 @@ class ImageGenerationUtils:
         intervals = [r for i, r in enumerate(all_intervals) if (i // run) % options.threads == process_id]
         if process_id == 0:
             _log("INFO: STARTING PROCESS: " + str(process_id) + " FOR " + str(len(intervals)) + " INTERVALS")
-        from pepper_amd.variant.AlignmentSummarizer import create_summaries
+        from pepper_amd.variant.AlignmentSummarizer import create_summaries, targets_of
         from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder, adjacent_run, merge_stats, worker_counters
         generators = {}
         stats = getattr(options, "stage_seconds", None)      # a dict the caller wants the stage times of this worker added to
@@ -194,9 +195,12 @@ class ImageGenerationUtils:
         # tables were built on the device (PEPPER_AMD_DEVICE_PACK=1) / on the host
         # ... and, in a fused run with device_selection, the encoder calls whose candidates were selected on the device (one
         # segment per call, pepper_amd/variant/fused.py: forward_select) / the calls and host-clipped groups selected the host way
+        # ... and, with options.region_bed (bed_list: its tables, Targets.read_bed), the encoder calls of either form that ran
+        # with a contig's targets set (the intervals the planner dropped are counted by generate_images)
         mine = {"sampled_on_device": 0, "host_form_intervals": 0, "long_cigar_reads_on_device": 0,
                 "encoder_calls": 0, "device_enumerated_calls": 0, "host_enumerated_calls": 0,
-                "device_packed_calls": 0, "host_packed_calls": 0, "device_selected_calls": 0, "host_selected_calls": 0}
+                "device_packed_calls": 0, "host_packed_calls": 0, "device_selected_calls": 0, "host_selected_calls": 0,
+                "target_calls": 0}
 
         def lap(key, t0):
             now = time.perf_counter()
@@ -243,7 +247,20 @@ class ImageGenerationUtils:
                     generators[chr_name] = ImageGenerator(chr_name, options.bam, options.fasta, wopts)
                 prepared.append(generators[chr_name].prepare(wopts, _start, _end))
             t0 = time.perf_counter()
-            for (chr_name, _start, _end), out in zip(group, create_summaries(prepared)):
+            if bed_list is None:
+                summaries = create_summaries(prepared)
+            else:
+                # one encoder call per run of one contig, with that contig's targets on this thread's handle for its duration
+                summaries, k0 = [], 0
+                while k0 < len(group):
+                    k1 = k0 + 1
+                    while k1 < len(group) and group[k1][0] == group[k0][0]:
+                        k1 += 1
+                    with targets_of(bed_list, group[k0][0], device):
+                        summaries += create_summaries(prepared[k0:k1])
+                    mine["target_calls"] += 1 if any(p is not None for p in prepared[k0:k1]) else 0
+                    k0 = k1
+            for (chr_name, _start, _end), out in zip(group, summaries):
                 if out is not None:
                     write(output_hdf_file, chr_name, _start, _end, out)
             if selecting:
@@ -329,6 +346,8 @@ class ImageGenerationUtils:
                     t0 = lap("fasta", t0)
                     # (the lean form of device_selection fetches no list and no image: outs are then the counts per interval)
                     fetch = keep_images or keep_predictions
+                    if bed_list is not None:             # (sent when the contig changes: a worker's groups are runs of one contig)
+                        enc.set_targets(Targets.table(bed_list, chr_name), chr_name)
                     try:
                         outs, live = enc.encode(regions, references, region_pairs, counts, params, [(s, e) for _, s, e in group],
                                                 ImageSizeOptions.CANDIDATE_WINDOW_SIZE, ImageSizeOptions.IMAGE_HEIGHT, resident=resident,
@@ -341,6 +360,7 @@ class ImageGenerationUtils:
                         continue
                     t0 = lap("encode", t0)
                     mine["encoder_calls"] += 1
+                    mine["target_calls"] += 1 if bed_list is not None else 0
                     mine["device_packed_calls" if (resident and enc.device_packed) else "host_packed_calls"] += 1
                     probs, at = None, 0
                     if selecting:
@@ -393,15 +413,27 @@ class ImageGenerationUtils:
         all_intervals, total_bases = ImageGenerationUtils.split_intervals(chr_list, fasta_handler, options.region_size)
         _log("INFO: TOTAL CONTIGS: " + str(len(chr_list)) + " TOTAL INTERVALS: " + str(len(all_intervals))
              + " TOTAL BASES: " + str(total_bases))
+        # options.region_bed: candidates only inside the BED's intervals (the reference parses the file and reads the list
+        # while training only).  The intervals stay on split_intervals' grid; one without a target position is never fetched
+        bed_list = None
+        region_bed = getattr(options, "region_bed", None)
+        if region_bed:
+            lengths = {name: fasta_handler.get_chromosome_sequence_length(name) for name in fasta_handler.get_chromosome_names()}
+            bed_list = Targets.read_bed(region_bed, lengths, log=_log)
+            all_intervals, dropped, dropped_bases = Targets.filter_intervals(all_intervals, bed_list)
+            _log("INFO: REGION BED: " + str(dropped) + " INTERVALS (" + str(dropped_bases) + " BASES) WITHOUT A TARGET DROPPED, "
+                 + str(len(all_intervals)) + " INTERVALS KEPT")
+            from pepper_amd.variant.PEPPER_VARIANT import merge_stats
+            merge_stats(getattr(options, "stage_seconds", None), {"target_intervals_dropped": dropped})
         # the reference forks options.threads processes; here they are threads of one process sharing the GPU: the
         # BAM reader, the encoder's host pass and libhdf5 run outside the GIL, each worker has its own BAM / FASTA
         # handles, encoder workspace and output file (interval i goes to worker i % threads, as in the reference)
         if options.threads <= 1:
-            ImageGenerationUtils.generate_image_and_save_to_file(options, all_intervals, None, 0)
+            ImageGenerationUtils.generate_image_and_save_to_file(options, all_intervals, bed_list, 0)
         else:
             from concurrent.futures import ThreadPoolExecutor
             with ThreadPoolExecutor(max_workers=options.threads) as pool:
-                futures = [pool.submit(ImageGenerationUtils.generate_image_and_save_to_file, options, all_intervals, None,
+                futures = [pool.submit(ImageGenerationUtils.generate_image_and_save_to_file, options, all_intervals, bed_list,
                                        process_id) for process_id in range(options.threads)]
                 for fut in futures:
                     fut.result()

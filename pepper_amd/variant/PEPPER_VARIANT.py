@@ -130,6 +130,27 @@ def candidate_calls(device=0):
     return dev.value, host.value
 
 
+def _send_targets(lib, enc, table):
+    """pa_encoder_set_targets: table = (starts, ends) of one contig, merged (pepper_amd/variant/Targets.py), or None: none."""
+    if table is None:
+        _lib.check(lib.pa_encoder_set_targets(enc, 0, None, None))
+        return
+    starts, ends = np.ascontiguousarray(table[0], np.int64), np.ascontiguousarray(table[1], np.int64)
+    _lib.check(lib.pa_encoder_set_targets(enc, len(starts), starts.ctypes.data, ends.ctypes.data))
+
+
+@contextlib.contextmanager
+def thread_targets(table, device=0):
+    """This thread's encoder on `device` -- what RegionalSummaryGenerator and generate_summary_arrays_batch run on -- restricted
+    to the targets of one contig for the calls inside, and unrestricted again behind them: the handle outlives the job."""
+    lib, enc = _encoder(device)
+    _send_targets(lib, enc, table)
+    try:
+        yield
+    finally:
+        _send_targets(lib, enc, None)
+
+
 def flatten_reads(reads):
     """type_read-like objects -> the flat arrays of pa_pileup."""
     n = len(reads)
@@ -320,7 +341,9 @@ class PackedEncoder(object):
             for k, enc in enumerate(cls._idle):
                 if (enc.device == device and enc.arena is not None and enc.arena.nbytes <= arena_bytes and enc.arena.nbytes >= min(arena_bytes, 16 << 20)
                         and (enc.stream is not None) == bool(torch_stream)):
-                    return cls._idle.pop(k)
+                    enc = cls._idle.pop(k)
+                    enc.set_targets(None)        # (whatever job had it last: its targets are not this one's)
+                    return enc
         size = arena_bytes
         while True:
             try:
@@ -367,6 +390,7 @@ class PackedEncoder(object):
         self.host_walk_spans = 0
         self._device_packed = False
         self.pack_handbacks = 0
+        self._targets_contig = None
 
     def close(self):
         if self.enc:
@@ -392,6 +416,15 @@ class PackedEncoder(object):
     def set_device_candidates(self, on):
         """Candidates of this handle's next runs enumerated on the device (pa_encoder_set_device_candidates)."""
         _lib.check(self.lib.pa_encoder_set_device_candidates(self.enc, 1 if on else 0))
+
+    def set_targets(self, table, contig=None):
+        """The targets of this handle's next runs (pa_encoder_set_targets): (starts, ends) of one contig, None: no restriction.
+        contig: the table's contig; a call that names the contig the handle already has sends nothing (a worker's groups are
+        runs of one contig)."""
+        if table is not None and contig is not None and contig == self._targets_contig:
+            return
+        _send_targets(self.lib, self.enc, table)
+        self._targets_contig = contig if table is not None else None
 
     def candidate_calls(self):
         """-> (runs enumerated on the device, runs handed back to the host) since this handle was created."""

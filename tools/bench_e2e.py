@@ -6,6 +6,8 @@
   python tools/bench_e2e.py call_variant_fused <dir> ...     the same with options.fused_inference (pepper_amd/variant/fused.py)
       --device-selection (also on call_variant, which then runs fused: the selection needs it): with options.device_selection, the lean form (pepper_amd/variant/DeviceSelect.py: no image file, no
       prediction file); --keep-files with it: keep_images and keep_predictions, the files written beside the device selection
+      --region-bed FILE (both call_variant forms): options.region_bed, candidates only inside the file's intervals
+      (tools/bench_variant_images.py beds <dir> writes two for a data set of the same size and seed)
   python tools/bench_e2e.py polish <dir> [draft_bases=64000000] [coverage=60] [runs=3]
   python tools/bench_e2e.py polish_fused <dir> ...           the same with fused_inference=True (pepper_amd/polish/fused.py)
       pepper_amd.polish.polish.polish (pepper polish, polish.py:94-117): BAM + draft + checkpoint -> images -> predictions -> FASTA
@@ -82,7 +84,7 @@ def median_run(runs, key="seconds"):
     return order[len(order) // 2]
 
 
-def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selection=False, keep_files=False):
+def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selection=False, keep_files=False, region_bed=None):
     from pepper_amd.hostinfo import usable_cpus
     from pepper_amd.variant.CallVariant import call_variant
     info = synth(work, bases, coverage)
@@ -104,7 +106,8 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selectio
             sample_name="SYN", allowed_multiallelics=4, snp_p_value=0.1, insert_p_value=0.25, delete_p_value=0.25, snp_p_value_in_lc=0.1,
             insert_p_value_in_lc=0.3, delete_p_value_in_lc=0.3, snp_q_cutoff=20, indel_q_cutoff=15, snp_q_cutoff_in_lc=20,
             indel_q_cutoff_in_lc=10, report_snp_above_freq=0, report_indel_above_freq=0, stage_walls=walls, stage_seconds=stages,
-            fused_inference=fused, device_selection=device_selection, keep_images=keep_files, keep_predictions=keep_files)
+            fused_inference=fused, device_selection=device_selection, keep_images=keep_files, keep_predictions=keep_files,
+            region_bed=region_bed)
         t0 = time.perf_counter()
         image_dir, pred_dir, totals = call_variant(options)
         dt = time.perf_counter() - t0
@@ -134,7 +137,7 @@ def call_variant_job(work, bases, coverage, n_runs, fused=False, device_selectio
             "image_stage_seconds_summed_over_workers": mid["image_stage_seconds_summed_over_workers"],
             "windows_per_s": round(mid["windows"] / mid["seconds"], 1),
             "candidates_per_s_in_find_candidates": round(mid["windows"] / max(1e-9, mid["stage_walls"]["find_candidates"]), 1),
-            "candidates_written": mid["candidates_written"], "threads": threads,
+            "candidates_written": mid["candidates_written"], "threads": threads, "region_bed": region_bed,
             "model": "seeded random init (gain 2), output layer leaned towards the reference class by %.2f so that ~2 %% of the windows are called" % bias,
             "data": "synthetic BAM %.0f Mb at %.0fx, %d records, %.2f GB (tools/synth_bam), seeded random-init checkpoint" % (
                 info["genome_bases"] / 1e6, info["coverage"], info["records"], info["bam_bytes"] / 1e9), "synth_seconds": info["seconds"]}
@@ -190,6 +193,13 @@ def polish_job(work, bases, coverage, n_runs, fused=False, device_stitch=None, q
 
 
 if __name__ == "__main__":
+    bed = None
+    if "--region-bed" in sys.argv:
+        at = sys.argv.index("--region-bed")
+        bed = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
+        if not sys.argv[1].startswith("call_variant"):
+            raise SystemExit("--region-bed: call_variant / call_variant_fused only")
     flags = {a for a in sys.argv[1:] if a.startswith("--")}
     sys.argv = [a for a in sys.argv if not a.startswith("--")]
     if flags - {"--device-selection", "--keep-files"}:
@@ -200,7 +210,7 @@ if __name__ == "__main__":
     n_runs = int(sys.argv[5]) if len(sys.argv) > 5 else 3
     if kind == "call_variant_fused" or (kind == "call_variant" and "--device-selection" in flags):      # (the selection needs the fused run)
         print(json.dumps(call_variant_job(work, bases, coverage, n_runs, fused=True, device_selection="--device-selection" in flags,
-                                          keep_files="--keep-files" in flags)))
+                                          keep_files="--keep-files" in flags, region_bed=bed)))
     elif kind.startswith("polish"):
         edits = True if kind.endswith("_edits") else None
         form = kind[:-len("_edits")] if edits else kind
@@ -209,4 +219,7 @@ if __name__ == "__main__":
         print(json.dumps(polish_job(work, bases, coverage, n_runs, fused="fused" in form,
                                     device_stitch=True if form.endswith("device_stitch") else None, qualities=qualities, edits=edits)))
     else:
-        print(json.dumps((call_variant_job if kind == "call_variant" else polish_job)(work, bases, coverage, n_runs)))
+        if kind == "call_variant":
+            print(json.dumps(call_variant_job(work, bases, coverage, n_runs, region_bed=bed)))
+        else:
+            print(json.dumps(polish_job(work, bases, coverage, n_runs)))

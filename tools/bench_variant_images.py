@@ -2,12 +2,17 @@
 through pepper_amd.variant.ImageGenerationUI.generate_images, the entry point of pepper_variant make_images / call_variant.
 
   python tools/bench_variant_images.py make_fast <dir> [genome_bases=64000000] [coverage=60] [seed] [level=1] [tags=0] [quals=0] [cg_ppm=0]    synthetic data set
-  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000] [downsample_rate=1.0]     GPU; one JSON line
+  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000] [downsample_rate=1.0] [--region-bed FILE]    GPU; one JSON line
+  python tools/bench_variant_images.py beds <dir> [fraction=0.02]     two BEDs for the data set: exons.bed, blocks.bed (their paths as JSON)
 
 `run` reports, per thread count, the wall time, Mb of reference per second, aligned bases per second and the stage times
 summed over the workers (bam_pack: inflate + header walk + slice copies; fasta; encode: upload + clip/decode + kernels +
 candidate enumeration + result copy; hdf5).  PEPPER_AMD_PACKED_READS=0 times the host-clipped form;
-PEPPER_AMD_DEVICE_CANDIDATES=1 the form whose candidates are enumerated on the device (the line says which it was)."""
+PEPPER_AMD_DEVICE_CANDIDATES=1 the form whose candidates are enumerated on the device (the line says which it was).
+--region-bed FILE: options.region_bed, candidates only inside the file's intervals (the rates stay per Mb of the WHOLE reference;
+the stage counts say how many intervals were dropped).  `beds` writes the two shapes a restriction comes in, each covering
+`fraction` of every contig: "exons", intervals of 200 bases spread evenly (every interval of the run keeps a target), and
+"blocks", four contiguous stretches per contig (most intervals of the run are dropped)."""
 import json
 import os
 import shutil
@@ -48,13 +53,34 @@ def make_fast(out, bases=64000000, coverage=60, seed=2027, level=1, tags=0, qual
     return info
 
 
-def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rate=1.0):
+def write_beds(data, fraction=0.02, exon=200, blocks=4):
+    """-> {"exons": path, "blocks": path}, each file covering `fraction` of every contig of the data set's FASTA."""
+    from pepper_amd.variant.fasta import FASTA_handler
+    fasta = FASTA_handler(os.path.join(data, "draft.fa"))
+    contigs = [(name, fasta.get_chromosome_sequence_length(name)) for name in fasta.get_chromosome_names()]
+    paths = {"exons": os.path.join(data, "exons.bed"), "blocks": os.path.join(data, "blocks.bed")}
+    with open(paths["exons"], "w") as fh:
+        for name, length in contigs:
+            n = max(1, int(length * fraction / exon))
+            for k in range(n):
+                start = max(0, int((k + 0.5) * length / n) - exon // 2)
+                fh.write("%s\t%d\t%d\n" % (name, start, min(length, start + exon)))
+    with open(paths["blocks"], "w") as fh:
+        for name, length in contigs:
+            size = max(1, int(length * fraction / blocks))
+            for k in range(blocks):
+                start = max(0, int((k + 0.5) * length / blocks) - size // 2)
+                fh.write("%s\t%d\t%d\n" % (name, start, min(length, start + size)))
+    return paths
+
+
+def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rate=1.0, region_bed=None):
     from pepper_amd.variant.ImageGenerationUI import ImageGenerationUtils
     info = json.load(open(os.path.join(data, "synth.json")))
     mb = info["genome_bases"] / 1e6
     if warm:      # library load, the workers' buffers grown to the size of the job's groups, the file in the page cache -- not part of the rate
         ImageGenerationUtils.generate_images(options(data, os.path.join(data, "vimages_warm"), thread_counts[0], region_size,
-                                                     downsample_rate=downsample_rate))
+                                                     downsample_rate=downsample_rate, region_bed=region_bed))
         shutil.rmtree(os.path.join(data, "vimages_warm"), ignore_errors=True)
     runs = []
     for threads in thread_counts:
@@ -63,7 +89,7 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rat
         stages = {}
         t0 = time.perf_counter()
         ImageGenerationUtils.generate_images(options(data, tmp, threads, region_size, stage_seconds=stages,
-                                                     downsample_rate=downsample_rate))
+                                                     downsample_rate=downsample_rate, region_bed=region_bed))
         dt = time.perf_counter() - t0
         size = sum(os.path.getsize(os.path.join(tmp, f)) for f in os.listdir(tmp))
         runs.append({"threads": threads, "seconds": round(dt, 3), "mb_reference_per_s": round(mb / dt, 2),
@@ -77,13 +103,21 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rat
                 (", NM/MD/RG tags" if info.get("aux_tags") else "") + (", run-length qualities" if "run-length" in info.get("quals", "") else ""),
                 region_size),
             "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0",
-            "device_candidates": os.environ.get("PEPPER_AMD_DEVICE_CANDIDATES", "0") == "1", "downsample_rate": downsample_rate, "runs": runs}
+            "device_candidates": os.environ.get("PEPPER_AMD_DEVICE_CANDIDATES", "0") == "1", "downsample_rate": downsample_rate,
+            "region_bed": region_bed, "runs": runs}
 
 
 if __name__ == "__main__":
+    bed = None
+    if "--region-bed" in sys.argv:
+        at = sys.argv.index("--region-bed")
+        bed = sys.argv[at + 1]
+        del sys.argv[at:at + 2]
     if sys.argv[1] == "make_fast":
         print(json.dumps(make_fast(sys.argv[2], *(float(a) for a in sys.argv[3:10]))))
+    elif sys.argv[1] == "beds":
+        print(json.dumps(write_beds(sys.argv[2], *(float(a) for a in sys.argv[3:4]))))
     else:
         counts = tuple(int(t) for t in sys.argv[3].split(",")) if len(sys.argv) > 3 else (16,)
         print(json.dumps(run(sys.argv[2], counts, int(sys.argv[4]) if len(sys.argv) > 4 else 100000,
-                             downsample_rate=float(sys.argv[5]) if len(sys.argv) > 5 else 1.0)))
+                             downsample_rate=float(sys.argv[5]) if len(sys.argv) > 5 else 1.0, region_bed=bed)))
