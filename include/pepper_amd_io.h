@@ -313,7 +313,11 @@ int pa_bam_pack_regions(pa_bam* b, const char* contig, int32_t n_regions, const 
  * After pa_encoder_set_split_slices the walk looks the CG tag up itself: state = 3, data_off = where the tag's operations
  * start, n_cigar / ref_len = their number / reference bases, and block_size = the distance from data_off BACK to the record's
  * bases (bases | qualities stay in the core: at data_off - block_size).  block_size of a state-3 header is therefore NOT the
- * record's size: it is the record's size in every other state.  State 2 then also covers a malformed auxiliary field. */
+ * record's size: it is the record's size in every other state.  State 2 then also covers a malformed auxiliary field.
+ * ref_len is summed in 64 bits and SATURATES at INT32_MAX (nine N operations of 2^28 - 1 bases are more than the field
+ * holds): pa_pack::read_end(pos, ref_len) then still lies beyond every region start a BAM can name (a reference has at most
+ * 2^31 - 1 bases), so pa_bam_pack_headers gives such a record the regions pa_bam_pack_inflated's 64-bit sum gives it.  A
+ * state-2 header has ref_len = 0. */
 #ifndef PA_RECORD_HEADER_DEFINED
 #define PA_RECORD_HEADER_DEFINED
 typedef struct {

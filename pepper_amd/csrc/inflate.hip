@@ -1101,7 +1101,7 @@ __global__ __launch_bounds__(256) void record_finish_kernel(const uint8_t* __res
     for (int j = (blockIdx.x & 15) * 4 + ((int)threadIdx.x >> 6); j < n; j += 64) {
     RecHdr h = slots[(size_t)i * cap + j];
     const int l_name = h.ref_len;
-    int ref = 0;
+    long long ref = 0;                             // (64 bits: nine N operations of 2^28 - 1 bases are more than an int holds)
     if (h.state == 0) {
         const uint8_t* cig = data + h.data_off;
         int n_ops = h.n_cigar;
@@ -1136,13 +1136,13 @@ __global__ __launch_bounds__(256) void record_finish_kernel(const uint8_t* __res
                 const int k = k0 + lane;
                 const uint32_t c = k < n_ops ? load32(cig + 4ll * k) : 5u;
                 const int op = (int)(c & 15u);
-                ref += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (int)(c >> 4) : 0;
+                ref += (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ? (long long)(c >> 4) : 0ll;
             }
             for (int o = 32; o > 0; o >>= 1) ref += __shfl_xor(ref, o, 64);
         }
     }
     if (lane == 0 && (long long)base[i] + j < out_cap) {
-        h.ref_len = ref;
+        h.ref_len = ref > 0x7fffffffll ? 0x7fffffff : (int32_t)ref;     // saturated: pa_record_header, include/pepper_amd_io.h
         out[base[i] + j] = h;
     }
     }

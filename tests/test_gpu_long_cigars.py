@@ -135,7 +135,7 @@ def test_a_count_above_16_bits_passes_through_the_tables(tmp_path, monkeypatch):
 def test_malformed_auxiliary_fields_fall_back_quietly(tmp_path, monkeypatch):
     """A Z string without its NUL, a B array longer than the record and an unknown type letter inside placeholder records:
     pack_device gives None or the host walk's tables, and raises nothing."""
-    from pepper_amd.variant.bam import BAM_handler
+    from pepper_amd.variant.bam import BAM_handler, PACKED_READ
     from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
     rng = np.random.default_rng(915)
     ref = pu.random_reference(rng, 20000)
@@ -150,8 +150,24 @@ def test_malformed_auxiliary_fields_fall_back_quietly(tmp_path, monkeypatch):
     for walk in ("1", "0"):
         monkeypatch.setenv("PEPPER_AMD_DEVICE_WALK", walk)
         enc = PackedEncoder(0, arena_bytes=16 << 20)
-        out = enc.pack_device(BAM_handler(bam), "ctg", [0, 5000], [5100, 19000], False, 0, long_cigars=True)
+        handler = BAM_handler(bam)
+        out = enc.pack_device(handler, "ctg", [0, 5000], [5100, 19000], False, 0, long_cigars=True)
         assert out is None or len(out) == 3
+        # the rung that served the call: the device's walk marks the three records (state 2), pack_headers refuses them (-6)
+        # and the host walks the span after all -- once; without the device's walk the host's walk is the first rung, not counted
+        assert out is not None and enc.host_walk_spans == (1 if walk == "1" else 0)
+        if walk == "1":
+            assert int((enc.headers["state"] == 2).sum()) == 3
+        # ... and its tables are pack_inflated's for the same span: the three records kept with their core CIGAR
+        n_done, region_pairs, counts = out
+        data, data_bytes, first, final = host_side._inflate_span(handler, "ctg", 0, 19000)
+        reads, pairs = np.zeros(4000, PACKED_READ), np.zeros(8000, np.int32)
+        want_done, want_rp, want_counts = handler.pack_inflated(data, data_bytes, first, final, "ctg", [0, 5000], [5100, 19000], False, 0,
+                                                                reads, pairs, long_cigars=True)
+        assert (n_done, counts[:2]) == (want_done, want_counts[:2]) and n_done == 2 and counts[0] > 25 and region_pairs.tolist() == want_rp.tolist()
+        assert enc.reads[:counts[0]].tobytes() == reads[:counts[0]].tobytes()
+        assert enc.pair_read[:counts[1]].tolist() == pairs[:counts[1]].tolist()
+        assert enc.seq_off is None and handler.split_offsets(counts[0])[1] == 0
         enc.close()
 
 

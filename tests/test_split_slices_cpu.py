@@ -10,7 +10,8 @@ import pytest
 
 import bam_utils as bu
 import pileup_utils as pu
-from pepper_amd.variant.bam import BAM_handler, BamError, PACKED_READ, RECORD_HEADER
+from record_walk_cases import split_headers          # (the restatement of the device's walk, tag walk included)
+from pepper_amd.variant.bam import BAM_handler, BamError, PACKED_READ
 
 AUX_EVERY_TYPE = (b"XAAq" + b"Xcc" + struct.pack("<b", -5) + b"XSS" + struct.pack("<H", 40000) + b"Xii" + struct.pack("<i", -70000) +
                   b"Xff" + struct.pack("<f", 1.5) + b"XBBc" + struct.pack("<I", 5) + bytes([1, 2, 3, 4, 5]) + b"XZZabc\0" +
@@ -44,57 +45,6 @@ def decode_split(arena, rd, seq_off):
     flags = int(rd["flags"])
     return dict(pos=int(rd["pos"]), cigar=[(int(w) & 15, int(w) >> 4) for w in words], seq="".join("=ACMGRSVTWYHKDBN"[c] for c in codes[:l_seq]),
                 qual=arena[q0:q0 + l_seq].tolist(), flag=flags & 0xffff, mapq=(flags >> 16) & 0xff)
-
-
-def _find_cg(aux):
-    """htslib's tag walk restated: -> (offset of the operations in aux, count) or None."""
-    size = {b"A": 1, b"c": 1, b"C": 1, b"s": 2, b"S": 2, b"i": 4, b"I": 4, b"f": 4, b"d": 8}
-    p = 0
-    while len(aux) - p >= 4:
-        tag, t = aux[p:p + 2], aux[p + 2:p + 3]
-        p += 3
-        if t in size:
-            p += size[t]
-        elif t in (b"Z", b"H"):
-            p = aux.index(b"\0", p) + 1
-        elif t == b"B":
-            sub, cnt = aux[p:p + 1], struct.unpack("<I", aux[p + 1:p + 5])[0]
-            if tag == b"CG" and sub in (b"I", b"i"):
-                return p + 5, cnt
-            p += 5 + cnt * size[sub]
-        else:
-            return None
-    return None
-
-
-def split_headers(data, data_bytes, first):
-    """The record headers of a span as the device's walk reports them after pa_encoder_set_split_slices: state 3 for a
-    placeholder with a usable CG tag (data_off / n_cigar / ref_len of the tag's operations, block_size = the distance back to
-    the bases), the core fields for everything else."""
-    out, at = [], int(first)
-    while at + 4 <= data_bytes:
-        bs = int.from_bytes(data[at:at + 4].tobytes(), "little")
-        if at + 4 + bs > data_bytes:
-            break
-        R = data[at + 4:at + 4 + bs].tobytes()
-        ref_id, pos = struct.unpack("<ii", R[:8])
-        l_name, mapq = R[8], R[9]
-        n_cig, flag, l_seq = struct.unpack("<HHI", R[12:20])
-        o_cig = 32 + l_name
-        o_seq = o_cig + 4 * n_cig
-        o_aux = o_seq + (l_seq + 1) // 2 + l_seq
-        state, data_off, last = 0, at + 4 + o_cig, bs
-        words = np.frombuffer(R[o_cig:o_seq], "<u4")
-        if n_cig >= 1 and (int(words[0]) & 15) == 4 and (int(words[0]) >> 4) == l_seq:
-            found = _find_cg(R[o_aux:])
-            if found is not None and n_cig <= found[1] < (1 << 29):
-                ops = o_aux + found[0]
-                words = np.frombuffer(R[ops:ops + 4 * found[1]], "<u4")
-                state, data_off, n_cig, last = 3, at + 4 + ops, found[1], ops - o_seq
-        ref_len = int(sum(int(w) >> 4 for w in words if (int(w) & 15) in (0, 2, 3, 7, 8)))
-        out.append((data_off, ref_id, pos, l_seq, n_cig, flag | mapq << 16, ref_len, state, last))
-        at += 4 + bs
-    return np.array(out, RECORD_HEADER)
 
 
 @pytest.fixture(scope="module")
