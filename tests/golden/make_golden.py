@@ -42,9 +42,13 @@ def variant_inputs(n):
 
 
 @torch.no_grad()
-def make_variant(tag, seed, gain, n=64):
+def make_variant(tag, seed, gain, n=64, head_scale=1.0):
+    """head_scale: output_layer_type (weight and bias) multiplied by it -- 12 on the gain-2 recipe gives the confident head
+    of a trained checkpoint (tests/weight_families.py confident_head): logits up to 20, probabilities up to 0.99999."""
     from pepper_variant.modules.python.models.simple_model import TransducerGRU
     sd = synthetic.variant_state_dict(seed=seed, gain=gain)
+    sd["output_layer_type.weight"] *= np.float32(head_scale)
+    sd["output_layer_type.bias"] *= np.float32(head_scale)
     model = TransducerGRU(image_features=26, gru_layers=1, hidden_size=128, num_classes=28,
                           num_classes_type=3, bidirectional=True)
     model.load_state_dict(to_torch(sd))
@@ -58,7 +62,7 @@ def make_variant(tag, seed, gain, n=64):
     # the same forward in float64: what a port must reproduce whatever CPU runs it (float32 results move with the CPU's
     # thread count and vector width, by up to a few 1e-6 at gain 3)
     probs64 = model.double()(xf.double(), False).numpy()
-    np.savez_compressed(os.path.join(OUT, f"variant_{tag}.npz"), seed=seed, gain=gain, images=x,
+    np.savez_compressed(os.path.join(OUT, f"variant_{tag}.npz"), seed=seed, gain=gain, head_scale=head_scale, images=x,
                         probs=probs, logits=logits, enc2=enc.numpy(), dec2=dec.numpy(), probs64=probs64)
     print(tag, "probs[4:7]", probs[4:7])
 
@@ -142,10 +146,15 @@ if __name__ == "__main__":
         torch.set_num_threads(8)
         make_polish("confident", seed=24, gain=1.0, n=2, head_scale=40)
         sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "variant_confident":
+        torch.set_num_threads(8)
+        make_variant("confident", seed=70, gain=2.0, head_scale=12)
+        sys.exit(0)
     torch.set_num_threads(8)
     make_variant("g1", seed=11, gain=1.0)
     make_variant("g3", seed=12, gain=3.0)
     make_variant_two_layer("l2", seed=13, gain=2.0)
+    make_variant("confident", seed=70, gain=2.0, head_scale=12)
     make_polish("g1", seed=21, gain=1.0)
     make_polish("g3", seed=22, gain=3.0)
     make_polish_two_layer("l2", seed=23, gain=2.0)

@@ -1,6 +1,7 @@
 """CPU leg of the weight-family stress test (tests/weight_families.py): the numpy emulation of the product's
 arithmetic -- every contraction as hi*hi + hi*lo + lo*hi on f16 halves of f32 operands -- against the float64
-restatement.  The GPU leg is tests/test_gpu_arith_modes.py::test_split_arithmetic_on_weight_families."""
+restatement.  The GPU legs are tests/test_gpu_arith_modes.py::test_split_arithmetic_on_weight_families (the unit-split
+form) and tests/test_gpu_variant_stress.py (every kernel form, with the head families)."""
 import warnings
 
 import numpy as np
@@ -38,6 +39,81 @@ def test_why_large_weights_leave_the_split_path():
         pe, le = wf.variant_forward_emulated(sd, x)
     assert max(wf.errors(p32, inter["logits"], p64, l64)) < 2e-5
     assert max(wf.errors(pe, le, p64, l64)) > 1e-4
+
+
+# ---- variant head families and shapes (GPU leg: tests/test_gpu_variant_stress.py) ------------------------------------
+VARIANT_SHAPES = [{}, {"gru_layers": 2}, {"image_features": 48, "window": 21}]
+
+
+@pytest.mark.parametrize("family", ["default", "default_gain2"] + wf.FAMILIES + wf.HEAD_FAMILIES)
+def test_variant_family_stays_conditioned(family):
+    """A family is a parity case only while the float32 restatement itself stays within 1e-5 of float64 on the probe
+    windows (measured distances: module docstring of weight_families)."""
+    case = wf.variant_case(family)
+    assert np.isfinite(case["p32"]).all() and np.isfinite(case["l64"]).all()
+    assert case["own"] <= 1e-5, (family, case["own"])
+    assert np.abs(case["p64"].sum(1) - 1).max() < 1e-12
+    # the probes begin with the int8 extremes
+    assert (case["x"][0] == 127).all() and (case["x"][1] == -128).all() and (case["x"][2] == 0).all()
+
+
+@pytest.mark.parametrize("shape", VARIANT_SHAPES[1:], ids=str)
+def test_variant_shapes_stay_conditioned(shape):
+    """confident_head keeps head x 12 at both shapes (two layers: 9.0e-6, 48 features x 21 rows: 3.7e-6)."""
+    for family in ("default", "confident_head"):
+        case = wf.variant_case(family, **shape)
+        assert case["x"].shape[1:] == (shape.get("window", 33), shape.get("image_features", 26))
+        assert case["own"] <= 1e-5, (family, shape, case["own"])
+    if "image_features" in shape:           # the columns past V-syn's 26 are not left zero
+        assert (wf.variant_case("default", **shape)["x"][3:, :, 26:] != 0).any()
+
+
+def test_variant_confident_head_reaches_the_trained_regime():
+    """All three classes called, logits past 10, a best probability above 0.9999 on one probe and below 0.5 on another
+    (96 probes: a draw of 64 has 0.57 as its least confident call); the gain-1 default -- what every family test saw
+    before -- calls at most two classes with every logit below 0.2."""
+    case = wf.variant_case("confident_head", n_probes=96)
+    best = case["p64"].max(axis=1)
+    assert len(np.unique(case["p64"].argmax(1))) == 3
+    assert np.abs(case["l64"]).max() > 10
+    assert best.max() > 0.9999 and best.min() < 0.5
+    # the 64 probes the GPU tests embed: all three classes as well, 0.57 to 0.99999
+    best = wf.variant_case("confident_head")["p64"].max(axis=1)
+    assert len(np.unique(wf.variant_case("confident_head")["p64"].argmax(1))) == 3 and best.max() > 0.9999 and best.min() < 0.6
+    flat = wf.variant_case("default", n_probes=96)
+    assert len(np.unique(flat["p64"].argmax(1))) <= 2 and np.abs(flat["l64"]).max() < 0.2
+
+
+@pytest.mark.parametrize("terms", [3, 1])
+@pytest.mark.parametrize("family", wf.HEAD_FAMILIES)
+def test_head_families_make_a_missing_term_visible(family, terms):
+    """The emulated product arithmetic (three terms) stays within 2e-5 of float64 on the head families; with the lo halves
+    dropped (hi*hi only) it is at least 10 x the 1e-4 bar away -- on mixed_row_scales that error is 2.9e-6 and would pass."""
+    case = wf.variant_case(family)
+    n = 12
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        pe, le = wf.variant_forward_emulated(case["sd"], case["x"][:n], terms=terms)
+    err = max(wf.errors(pe, le, case["p64"][:n], case["l64"][:n]))
+    if terms == 3:
+        assert err < 2e-5, (family, err)
+    else:
+        assert err >= 10 * 1e-4, (family, err)
+
+
+def test_variant_float64_restatement_is_pinned_by_the_reference_golden(golden_dir):
+    """variant_forward_f64 against what the reference's own model class produced on the confident head (float32 torch;
+    make_golden.py make_variant(head_scale=12)): within 2e-5, logits relative to their largest."""
+    import os
+    from pepper_amd import synthetic
+    g = np.load(os.path.join(golden_dir, "variant_confident.npz"))
+    sd = synthetic.variant_state_dict(seed=int(g["seed"]), gain=float(g["gain"]))
+    sd["output_layer_type.weight"] *= np.float32(g["head_scale"])
+    sd["output_layer_type.bias"] *= np.float32(g["head_scale"])
+    assert g["images"].dtype == np.int8 and g["images"].shape == (64, 33, 26)
+    assert np.abs(g["logits"]).max() > 10 and g["probs"].max() > 0.9999          # the fixture is in the confident regime
+    p64, l64 = models_np.variant_forward_f64(sd, g["images"])
+    assert max(wf.errors(g["probs"], g["logits"], p64, l64)) < 2e-5
 
 
 # ---- polish families (tests/weight_families.py make_polish; GPU leg: tests/test_gpu_polish_stress.py) ----------------
