@@ -244,11 +244,48 @@ int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_ho
  * per-position pass; without one it is not launched.  The polish encoder and the polish chain ignore the table. */
 int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const int64_t* end);
 
+/* Depth classes of the positions a run looked at (opt-in, not in the reference; pepper_amd/variant/Coverage.py is the host twin
+ * and writes the BED).  The depth of a position is what tile_count_kernel holds as its coverage when the per-position pass
+ * starts -- the reference's coverage_vector (region_summary.cpp:379, :454): aligned bases with quality >= min_snp_baseq and
+ * insert anchors rescued by the indel quality rule, of reads with mapping quality > 0, after the reservoir sample where one
+ * was drawn; deleted bases do not count -- the number `cov < min_coverage_threshold` refuses a site by.
+ * pa_encoder_set_depth_bins  n ascending lower bounds, lower[0] == 0 < lower[1] < ... , 1 <= n <= 8: bin k holds the depths in
+ *                     [lower[k], lower[k + 1]), the last bin is open above.  n == 0: off (the state of a new handle; every launch
+ *                     and every output byte is then as without the feature).  Holds for every variant form -- pa_encoder_
+ *                     generate_summary[_batch], pa_encoder_run_staged after pa_encoder_stage_batch, pa_encoder_stage_packed or
+ *                     pa_encoder_stage_packed_device, repeated runs included -- until set again.  n > 8, lower[0] != 0 or a bound
+ *                     not above the one before it: PA_ERR_INVALID, pa_last_error names the entry, the handle keeps what it had.
+ *                     With bins set tile_count_kernel (its <true> instance) stores every row's depth (int32, four bytes per row beside the 104 of the
+ *                     matrix: no saturation, any int32 bound is taken), and behind the run's other kernels, in the same submission
+ *                     and before its one wait, depth_runs_kernel (csrc/encoder.hip; one workgroup per 512-row tile, run twice around
+ *                     a scan of the tiles' counts) run-length encodes the bins of the rows of every region's candidate window
+ *                     [candidate_region_start, candidate_region_end] cut to the region: one 12-byte record per run stays on the
+ *                     device, 72 bytes of totals per region come back with the run's counters.
+ *                     With targets set (pa_encoder_set_targets) a position outside all of them has bin -1: its runs are
+ *                     reported like any other, the totals leave them out.  Candidates and images do not depend on the bins.
+ *                     Room for the records is one per 16 rows and four per tile (a sixteenth of the worst case, a run per
+ *                     row), or what an earlier run of the handle needed; a run with more is emitted a second time into a
+ *                     buffer of the scanned total after one more wait, and counted (pa_encoder_depth_calls): the answer is exact
+ *                     either way.  Debug: PEPPER_AMD_DEPTH_RUN_CAP=<records>, read by this call, replaces the first figure.
+ * pa_encoder_depth_runs  *n_runs = the runs of the last run (all regions, in region and position order; valid until the
+ *                     handle's next stage or run).  With any of region / start / end / bin given, capacity >= *n_runs entries
+ *                     are filled -- one download of the records, the ends derived here: region index, start and end (half-open)
+ *                     as contig positions, bin -- else PA_ERR_INVALID (nothing is truncated).  PA_ERR_INVALID too when the last
+ *                     run had no bins set.
+ * pa_encoder_depth_totals  per region r < n_regions of the last run: bases[8 r + k] positions of its window in bin k
+ *                     (on-target ones when targets are set), depth_sum[r] the sum of their depths; either may be NULL.
+ * pa_encoder_depth_calls  runs of this handle made with bins set / runs among them emitted twice (either may be NULL). */
+int pa_encoder_set_depth_bins(pa_encoder* e, int32_t n, const int32_t* lower);
+int pa_encoder_depth_runs(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* bin, int64_t* n_runs);
+int pa_encoder_depth_totals(pa_encoder* e, int32_t n_regions, int64_t* bases, int64_t* depth_sum);
+int pa_encoder_depth_calls(pa_encoder* e, int64_t* runs_with_bins, int64_t* overflows);
+
 /* Times of the last run in milliseconds, HIP events on the encoder's stream: [0] record kernels (segment_reads x 2 +
  * tile_offsets), [1] tile_count_kernel, [2] compact_votes_kernel + pack_results_kernel, [3] gather_windows_kernel; host clock:
  * [4] candidate enumeration, [5] the whole run, [6], [7] parts of [4]; packed form: [8] upload of arena + tables,
  * [9] unpack_clip_kernel; [12] the device enumeration (group_votes_kernel, enumerate_sites_kernel and the scans between them;
- * [4], [6], [7] are 0 for a run it served, [12] is 0 for every other run).  Sizes of the staged batch: [0] read bases, [1] matrix rows,
+ * [4], [6], [7] are 0 for a run it served, [12] is 0 for every other run); [13] the depth-class kernels (depth_runs_kernel twice and the
+ * scan between them, HIP events; 0 for a run without depth bins).  Sizes of the staged batch: [0] read bases, [1] matrix rows,
  * [2] reads, [3] CIGAR operations, [4] tiles, [5] regions. */
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n);
 int pa_encoder_batch_stats(pa_encoder* e, int64_t* out, int32_t n);

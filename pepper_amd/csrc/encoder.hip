@@ -713,6 +713,7 @@ struct TileArgs {
     int* mat; uint8_t* pass; SiteRec* sites; Vote* votes; Vote* votes_out; int vote_cap; int4* ovf; int ovf_cap; int* counters;
     int* region_counts;
     const uint8_t* targets;   // verdicts of target_rows_kernel, one per row like `pass`; null: no targets set
+    int32_t* depth;           // tile_count_kernel<true>: the row's coverage as the per-position pass sees it, one int32 per row like `pass`
     int debug;        // PA_TILE_DEBUG (profiling only, tools/tile_ablation.sh): parts of the kernel switched off
 };
 
@@ -743,6 +744,10 @@ __device__ unsigned long long g_enc_cycles[8];     // debug: shader-clock cycles
 #else
 #define ENC_LAP(k) do { } while (0)
 #endif
+// DEPTH (depth bins set, pa_encoder_set_depth_bins): the per-position pass also stores the row's coverage.  A template
+// parameter and not a test of a.depth: the instance every other run launches is then instruction for instruction the kernel
+// without the feature (with the test in it the register allocation moved and the kernel measured 6 % slower, switch off).
+template <bool DEPTH>
 __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileArgs a) {
     __shared__ int cnt[NCNT * TP];                 // [counter][row]; reused as the finished [row][26] tile for the store
     __shared__ char ref_s[TP];
@@ -1159,6 +1164,7 @@ __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileA
         passes = (s || n || d) && idx >= reg.cand_lo && idx <= reg.cand_hi && (double)cov >= reg.min_cov;
         if (a.targets != nullptr) passes = passes && a.targets[reg.row_base + idx] != 0;
         a.pass[reg.row_base + idx] = passes ? 1 : 0;
+        if (DEPTH) a.depth[reg.row_base + idx] = cov;
         pass_s[tid] = passes ? 1 : 0;
         if (passes) {
             site.region = region;
@@ -1217,6 +1223,91 @@ __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileA
     if (lane == 0)
         for (int k = 0; k < 8; ++k) atomicAdd(&g_enc_cycles[k], lap_acc[k]);
 #endif
+}
+
+// ---- depth classes (pa_encoder_set_depth_bins) ------------------------------------------------------------------------
+// The rows of every region's candidate window [cand_lo, cand_hi] (clamped to [0, L - 1]; row L is never reported), each in
+// the bin of the coverage tile_count_kernel stored for it, run-length encoded: one record per run, in region and row order.
+// One workgroup per tile, one thread per row, launched twice around tile_offsets_kernel.  EMIT = false counts the tile's run
+// heads and adds the tile's share of the region's totals (bases per bin, sum of depths: integers, so the order of the atomics
+// does not show); EMIT = true computes the same flags again and writes every head at the tile's scanned offset plus its rank
+// among the tile's heads.  A run's end is the next record's start in its region, or the window's end: the host derives it.
+// A row outside every target (targets != null) has the bin DEPTH_OFF_TARGET and adds nothing to the totals.
+constexpr int DEPTH_MAX_BINS = 8;
+constexpr int DEPTH_OFF_TARGET = 255;
+constexpr int DEPTH_TOTALS = DEPTH_MAX_BINS + 1;    // per region: bases of bin 0 .. 7, sum of depths
+struct DepthBins { int32_t n; int32_t lower[DEPTH_MAX_BINS]; };      // lower[0] == 0 < lower[1] < ...; bin k = [lower[k], lower[k + 1])
+struct DepthRun { int32_t region, row, bin; };
+
+__device__ __forceinline__ int depth_bin(const DepthBins& bins, int depth) {
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < DEPTH_MAX_BINS; ++j) k += (j < bins.n && depth >= bins.lower[j]) ? 1 : 0;
+    return k;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(TP) void depth_runs_kernel(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region,
+                                                        const int32_t* __restrict__ depth, const uint8_t* __restrict__ targets,
+                                                        DepthBins bins, int* __restrict__ tile_heads, const int* __restrict__ tile_off,
+                                                        unsigned long long* __restrict__ totals, DepthRun* __restrict__ runs, int run_cap) {
+    __shared__ uint8_t bin_s[TP];
+    __shared__ int wave_heads[TP / 64];
+    __shared__ int bases_s[DEPTH_MAX_BINS];
+    __shared__ unsigned long long sum_s;
+    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int region = tile_region[tile];
+    const RegRec* reg = regions + region;
+    const int lo = reg->cand_lo > 0 ? reg->cand_lo : 0;
+    const int hi = reg->cand_hi < reg->L - 1 ? reg->cand_hi : reg->L - 1;
+    const int tile_lo = (tile - reg->tile0) * TP;
+    const int idx = tile_lo + tid;
+    const bool in = idx >= lo && idx <= hi;          // (idx <= L - 1: a row tile_count_kernel stored a depth for)
+    if (!EMIT && tid < DEPTH_MAX_BINS) bases_s[tid] = 0;
+    if (!EMIT && tid == 0) sum_s = 0;
+    int d = 0, bin = DEPTH_OFF_TARGET;
+    bool on_target = false;
+    if (in) {
+        d = depth[reg->row_base + idx];
+        on_target = targets == nullptr || targets[reg->row_base + idx] != 0;
+        if (on_target) bin = depth_bin(bins, d);
+    }
+    bin_s[tid] = (uint8_t)bin;
+    __syncthreads();
+    bool head = false;
+    if (in) {
+        if (idx == lo) head = true;
+        else if (tid > 0) head = bin_s[tid - 1] != bin;
+        else {                                       // the previous row is the last one of the tile in front: read where that tile read it
+            const bool prev_on = targets == nullptr || targets[reg->row_base + idx - 1] != 0;
+            head = (prev_on ? depth_bin(bins, depth[reg->row_base + idx - 1]) : DEPTH_OFF_TARGET) != bin;
+        }
+    }
+    const unsigned long long hm = __ballot(head);
+    if (lane == 0) wave_heads[w] = __popcll(hm);
+    if (!EMIT) {
+        // the tile's share of the totals: per wave one LDS atomic per bin that occurs and one for the depths
+        for (int k = 0; k < bins.n; ++k) {
+            const unsigned long long m = __ballot(on_target && bin == k);
+            if (m && lane == 0) atomicAdd(&bases_s[k], __popcll(m));
+        }
+        const long long dsum = wave_inclusive_sum64(on_target ? (long long)d : 0);
+        if (lane == 63 && dsum) atomicAdd(&sum_s, (unsigned long long)dsum);
+    }
+    __syncthreads();
+    if (!EMIT) {
+        if (tid == 0) {
+            int n = 0;
+            for (int k = 0; k < TP / 64; ++k) n += wave_heads[k];
+            tile_heads[tile] = n;
+        }
+        if (tid < DEPTH_MAX_BINS && bases_s[tid]) atomicAdd(&totals[(size_t)region * DEPTH_TOTALS + tid], (unsigned long long)bases_s[tid]);
+        if (tid == DEPTH_MAX_BINS && sum_s) atomicAdd(&totals[(size_t)region * DEPTH_TOTALS + DEPTH_MAX_BINS], sum_s);
+    } else if (head) {
+        int slot = tile_off[tile] + __popcll(hm & ((1ull << lane) - 1ull));
+        for (int k = 0; k < w; ++k) slot += wave_heads[k];
+        if (slot < run_cap) runs[slot] = DepthRun{region, idx, bin};      // past the capacity: the host emits again with room
+    }
 }
 
 // votes of the sites that passed the thresholds, compacted for the host
@@ -1658,6 +1749,15 @@ struct pa_variant_batch {
     std::vector<int32_t> live;        // reads with a base inside each region (the reference's len(all_reads)) of the last run
     DBuf d_zero;                      // counters [CT_N] | per-region counts [2 n_regions] | tile_count [n_tiles] | tile_fill [n_tiles]: cleared per run
     DBuf d_targets;                   // verdicts of target_rows_kernel for the staged batch's rows (pa_encoder_set_targets)
+    // depth classes (pa_encoder_set_depth_bins): the coverage of every row, [totals x n_regions][heads x n_tiles] cleared per
+    // run, the scanned head counts, the run records; of the last run: was it made with bins, their number, its runs, and the
+    // handle's counters (runs made with bins / runs whose records outgrew the buffer and were emitted a second time)
+    DBuf d_depth, d_dzero, d_dscan, d_runs;
+    HBuf h_dtot;
+    int64_t run_cap = 0;
+    bool depth_on = false;
+    int depth_bins = 0;
+    int64_t n_runs = 0, depth_calls = 0, depth_overflows = 0;
     DBuf d_tile_off, d_sorted, d_mat, d_pass, d_sites, d_votes, d_votes_out, d_sites_dense, d_votes_dense, d_ovf, d_cands, d_img32, d_img8;
     HBuf h_counts, h_sites, h_votes;
     // candidates enumerated on the device (pa_encoder_set_device_candidates): the rules of the staged regions, the per-site and
@@ -1686,7 +1786,7 @@ struct pa_variant_batch {
     std::vector<int64_t> positions;
     std::vector<int32_t> depths, freqs;
     std::string names;
-    double ms[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void pa_variant_batch_free(pa_variant_batch* b) { delete b; }
@@ -1794,6 +1894,7 @@ const char* const BATCH_TOO_LARGE = "batch too large: more than 2^30 rows or 2^3
 // a staging call, accepted or refused, leaves no earlier batch staged: first thing in each of them
 void unstage(pa_encoder* e) {
     if (e && e->variant) e->variant->staged = false;
+    if (e && e->variant) e->variant->depth_on = false;      // (the depth runs of the last run speak of its regions)
 }
 
 struct RegionSums { int64_t rows = 0, ref = 0; int tiles = 0; };      // matrix rows, reference bytes and tiles of the regions so far
@@ -2267,7 +2368,13 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     static const int tile_debug = [] { const char* e = getenv("PA_TILE_DEBUG"); return e ? atoi(e) : 0; }();
     ta.debug = tile_debug;
     ta.targets = targets;
-    hipLaunchKernelGGL(tile_count_kernel, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    ta.depth = nullptr;                            // depth bins set: the tile kernel keeps every row's coverage for depth_runs_kernel
+    if (e->n_depth_bins > 0) {
+        ENC_ALLOC(b.d_depth, (size_t)b.total_rows * 4 + 64);
+        ta.depth = b.d_depth.as<int32_t>();
+    }
+    if (ta.depth != nullptr) hipLaunchKernelGGL(tile_count_kernel<true>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    else hipLaunchKernelGGL(tile_count_kernel<false>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
     ENC_HIP(hipEventRecord(e->ev[2], st));
     hipLaunchKernelGGL(compact_votes_kernel, dim3((unsigned)std::min(2048, (w.vote_cap + 255) / 256)), dim3(256), 0, st, b.d_votes.as<Vote>(),
                        w.counters, w.vote_cap, b.p_regions, b.d_pass.as<uint8_t>(), b.d_seq.as<char>(), b.p_ref, w.region_counts,
@@ -2277,6 +2384,74 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
                        b.d_seq.as<char>(), b.d_pool.as<char>(), b.pool_cap, w.counters);
     ENC_HIP(hipEventRecord(e->ev[3], st));
     ENC_HIP(hipGetLastError());
+    return PA_OK;
+}
+
+// The depth classes behind everything else of the submission (depth bins set): heads counted and totals summed per tile, the
+// head counts scanned, the runs emitted; the totals and the run count travel with the counters, before the run's one wait.
+// Room for the records: one run per 16 rows and four more per tile -- a sixteenth of the worst case of a run per row (real
+// coverage changes class a few times per kilobase) -- or what PEPPER_AMD_DEPTH_RUN_CAP named when the bins were set, or what an
+// earlier run of the handle needed; a run with more heads than that is emitted a second time (finish_depth_runs).
+void launch_depth_runs(pa_encoder* e, bool emit) {
+    pa_variant_batch& b = *e->variant;
+    DepthBins bins;
+    bins.n = b.depth_bins;
+    for (int k = 0; k < DEPTH_MAX_BINS; ++k) bins.lower[k] = e->depth_lower[k];
+    unsigned long long* totals = b.d_dzero.as<unsigned long long>();
+    int* heads = reinterpret_cast<int*>(totals + b.regs.size() * DEPTH_TOTALS);
+    const uint8_t* targets = e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr;
+    if (emit)
+        hipLaunchKernelGGL(depth_runs_kernel<true>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
+                           b.d_depth.as<int32_t>(), targets, bins, heads, b.d_dscan.as<int>(), totals, b.d_runs.as<DepthRun>(), (int)b.run_cap);
+    else
+        hipLaunchKernelGGL(depth_runs_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
+                           b.d_depth.as<int32_t>(), targets, bins, heads, b.d_dscan.as<int>(), totals, b.d_runs.as<DepthRun>(), (int)b.run_cap);
+}
+
+int submit_depth_runs(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    if (e->n_depth_bins <= 0) return PA_OK;
+    b.depth_bins = e->n_depth_bins;
+    const size_t n_tot = (size_t)w.n_regions * DEPTH_TOTALS;
+    const int64_t sized = e->depth_run_cap > 0 ? e->depth_run_cap : b.total_rows / 16 + 4 * (int64_t)b.n_tiles;
+    b.run_cap = std::min<int64_t>(std::max(b.run_cap, sized), 0x7ffffff0);
+    ENC_ALLOC(b.d_dzero, n_tot * 8 + (size_t)b.n_tiles * 4);
+    ENC_ALLOC(b.d_dscan, ((size_t)b.n_tiles + 1) * 4);
+    ENC_ALLOC(b.d_runs, (size_t)b.run_cap * sizeof(DepthRun));
+    if (!b.h_dtot.ensure((n_tot + 1) * 8)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_HIP(hipEventRecord(e->ev[12], st));
+    ENC_HIP(hipMemsetAsync(b.d_dzero.p, 0, n_tot * 8 + (size_t)b.n_tiles * 4, st));
+    launch_depth_runs(e, false);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st,
+                       reinterpret_cast<const int*>(b.d_dzero.as<unsigned long long>() + n_tot), b.n_tiles, b.d_dscan.as<int>());
+    launch_depth_runs(e, true);
+    ENC_HIP(hipEventRecord(e->ev[13], st));
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipMemcpyAsync(b.h_dtot.p, b.d_dzero.p, n_tot * 8, hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipMemcpyAsync(b.h_dtot.as<unsigned long long>() + n_tot, b.d_dscan.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
+    return PA_OK;
+}
+
+// after the run's wait: the run count, and the second emit of a run whose records outgrew the buffer (every overflow is
+// counted; the depths, the verdicts and the scanned offsets are where the first emit read them, so the records are exact)
+int finish_depth_runs(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    if (e->n_depth_bins <= 0) return PA_OK;
+    b.depth_calls += 1;
+    b.n_runs = *reinterpret_cast<const int*>(b.h_dtot.as<unsigned long long>() + (size_t)w.n_regions * DEPTH_TOTALS);
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e->ev[12], e->ev[13]); b.ms[13] = ms;     // depth_runs_kernel x 2 + tile_offsets_kernel
+    b.depth_on = true;
+    if (b.n_runs <= b.run_cap) return PA_OK;
+    b.depth_on = false;                            // (until the second emit is through)
+    b.depth_overflows += 1;
+    b.run_cap = b.n_runs;
+    ENC_ALLOC(b.d_runs, (size_t)b.run_cap * sizeof(DepthRun));
+    launch_depth_runs(e, true);
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    b.depth_on = true;
     return PA_OK;
 }
 
@@ -2484,8 +2659,14 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.region_n.assign((size_t)n_regions, 0);
     b.positions.clear(); b.depths.clear(); b.freqs.clear(); b.names.clear();
     b.dev_results = b.dev_lists = false;
+    b.depth_on = false;
+    b.n_runs = 0;
     for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
-    if (n_regions == 0) return PA_OK;
+    if (n_regions == 0) {
+        b.depth_on = e->n_depth_bins > 0;         // (no region: no run, no total)
+        b.depth_bins = e->n_depth_bins;
+        return PA_OK;
+    }
     const auto t_begin = std::chrono::steady_clock::now();
     RunShape w;
     int rc = size_workspaces(e, w);
@@ -2501,12 +2682,14 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.dev_results = false;
     b.dev_lists = false;
     b.ms[12] = 0;
+    b.ms[13] = 0;
     if (w.dev) ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
     int* host_counters = w.host_counters;
     bool on_device = false;           // this call's candidates were enumerated by the kernels
     for (int attempt = 0;; ++attempt) {       // one submission and one wait each; repeated with room when a buffer was too small
         rc = submit_counts(e, w);
         if (rc == PA_OK && w.dev) rc = submit_candidates(e, w);
+        if (rc == PA_OK) rc = submit_depth_runs(e, w);
         if (rc != PA_OK) return rc;
         ENC_HIP(hipMemcpyAsync(host_counters, w.counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
         ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2539,6 +2722,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         (void)hipEventElapsedTime(&ms, e->ev[7], e->ev[8]); b.ms[9] = ms;   // unpack_clip_kernel
     }
     rc = check_reports(e, w);
+    if (rc == PA_OK) rc = finish_depth_runs(e, w);
     if (rc == PA_OK) rc = on_device ? take_device_results(e, w, n_candidates) : enumerate_on_host(e, w, n_candidates);
     if (rc != PA_OK) return rc;
     b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();  // whole run, host clock
@@ -3093,6 +3277,70 @@ int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const
     return PA_OK;
 }
 
+int pa_encoder_set_depth_bins(pa_encoder* e, int32_t n, const int32_t* lower) {
+    if (!e || n < 0 || (n > 0 && !lower)) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (n > DEPTH_MAX_BINS) return pa::set_error(PA_ERR_INVALID, "depth bins: entry 8 is one more than the 8 bins a table may have");
+    for (int32_t k = 0; k < n; ++k)                // (checked in full before anything of the handle changes)
+        if (k == 0 ? lower[0] != 0 : lower[k] <= lower[k - 1])
+            return pa::set_error(PA_ERR_INVALID, "depth bins: entry " + std::to_string(k) +
+                                                     (k == 0 ? " must be 0" : " is not above the one before it"));
+    e->n_depth_bins = n;
+    for (int32_t k = 0; k < DEPTH_MAX_BINS; ++k) e->depth_lower[k] = k < n ? lower[k] : 0;
+    const char* cap = n > 0 ? getenv("PEPPER_AMD_DEPTH_RUN_CAP") : nullptr;     // (debug: tests/test_gpu_coverage.py makes a run overflow with it)
+    e->depth_run_cap = cap ? std::max<int64_t>(0, atoll(cap)) : 0;
+    return PA_OK;
+}
+
+int pa_encoder_depth_runs(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* bin, int64_t* n_runs) {
+    if (!e || capacity < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!e->variant || !e->variant->depth_on) return pa::set_error(PA_ERR_INVALID, "depth runs: the handle's last run had no depth bins set");
+    pa_variant_batch& b = *e->variant;
+    if (n_runs) *n_runs = b.n_runs;
+    if (!region && !start && !end && !bin) return PA_OK;
+    if (capacity < b.n_runs)
+        return pa::set_error(PA_ERR_INVALID, "depth runs: " + std::to_string(b.n_runs) + " runs, room for " + std::to_string(capacity));
+    if (b.n_runs == 0) return PA_OK;
+    ENC_HIP(hipSetDevice(e->device));
+    std::vector<DepthRun> runs((size_t)b.n_runs);
+    ENC_HIP(hipMemcpyAsync(runs.data(), b.d_runs.p, runs.size() * sizeof(DepthRun), hipMemcpyDeviceToHost, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < runs.size(); ++k) {
+        const DepthRun& r = runs[k];
+        if (r.region < 0 || r.region >= (int)b.regs.size() || (k > 0 && r.region < runs[k - 1].region))
+            return pa::set_error(PA_ERR_HIP, "depth runs: record " + std::to_string(k) + " names no region of the batch");
+        const RegHost& rh = b.regs[(size_t)r.region];
+        // a run ends where the next one of its region starts, the last one behind the window's last row
+        const int64_t window_end = std::min<int64_t>(rh.L - 1, rh.q.candidate_region_end - rh.p.region_start) + 1;
+        const int64_t stop = (k + 1 < runs.size() && runs[k + 1].region == r.region) ? runs[k + 1].row : window_end;
+        if (region) region[k] = r.region;
+        if (start) start[k] = rh.p.region_start + r.row;
+        if (end) end[k] = rh.p.region_start + stop;
+        if (bin) bin[k] = r.bin == DEPTH_OFF_TARGET ? -1 : r.bin;
+    }
+    return PA_OK;
+}
+
+int pa_encoder_depth_totals(pa_encoder* e, int32_t n_regions, int64_t* bases, int64_t* depth_sum) {
+    if (!e || n_regions < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!e->variant || !e->variant->depth_on) return pa::set_error(PA_ERR_INVALID, "depth totals: the handle's last run had no depth bins set");
+    pa_variant_batch& b = *e->variant;
+    if (n_regions > (int32_t)b.regs.size()) return pa::set_error(PA_ERR_INVALID, "depth totals: more regions than the last run had");
+    const unsigned long long* tot = b.h_dtot.as<unsigned long long>();
+    for (int32_t r = 0; r < n_regions; ++r) {
+        if (bases)
+            for (int k = 0; k < DEPTH_MAX_BINS; ++k) bases[(size_t)r * DEPTH_MAX_BINS + k] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + k];
+        if (depth_sum) depth_sum[r] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + DEPTH_MAX_BINS];
+    }
+    return PA_OK;
+}
+
+int pa_encoder_depth_calls(pa_encoder* e, int64_t* runs_with_bins, int64_t* overflows) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (runs_with_bins) *runs_with_bins = e->variant ? e->variant->depth_calls : 0;
+    if (overflows) *overflows = e->variant ? e->variant->depth_overflows : 0;
+    return PA_OK;
+}
+
 int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host) {
     if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
     if (on_device) *on_device = e->variant ? e->variant->dev_calls : 0;
@@ -3191,7 +3439,7 @@ const int8_t* pa_encoder_device_images(pa_encoder* e) {
 
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n) {
     if (!e || !ms || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 13) ? e->variant->ms[i] : 0.0;
+    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 14) ? e->variant->ms[i] : 0.0;
     return PA_OK;
 }
 

@@ -159,7 +159,7 @@ struct pa_encoder {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev[12] = {};
+    hipEvent_t ev[14] = {};                        // ([12], [13]: around the depth-run kernels)
     pa_variant_batch* variant = nullptr;
     pa_polish_batch* polish = nullptr;
     struct pa_realigner* realigner = nullptr;      // the polish image chain's re-aligner on this encoder's stream (made on first use)
@@ -167,6 +167,9 @@ struct pa_encoder {
     bool split_walk = false;                       // pa_encoder_set_split_slices: the record walk resolves CIGARs kept in the CG tag
     int64_t n_targets = 0;                         // pa_encoder_set_targets: intervals of the table (0: no restriction) ...
     pa_enc::DBuf d_target_table;                   // ... [start x n][end x n] on the device
+    int32_t n_depth_bins = 0;                      // pa_encoder_set_depth_bins: bins of the depth classes (0: the feature is off) ...
+    int32_t depth_lower[8] = {};                   // ... and their ascending lower bounds, depth_lower[0] == 0
+    int64_t depth_run_cap = 0;                     // ... PEPPER_AMD_DEPTH_RUN_CAP as that call read it (0: sized by the batch)
     std::vector<int64_t> seq_off;                  // pa_encoder_set_seq_offsets: per packed read of the NEXT staging where its bases lie (-1: behind its operations)
 };
 

@@ -50,6 +50,8 @@ def call_variant(options):
     _log("IMAGE OUTPUT: " + str(image_output_directory))
     _log("STEP 1/3 GENERATING IMAGES:")
     options.image_output_directory = image_output_directory
+    # (options.coverage_bed: image generation writes PEPPER_VARIANT_COVERAGE.bed beside the VCFs, not among the images)
+    options.coverage_output_directory = output_dir
     walls = getattr(options, "stage_walls", None)           # a dict the caller wants the three steps' wall times in
     precomputed = None
     t0 = time.perf_counter()

@@ -19,7 +19,7 @@ from datetime import datetime
 
 import numpy as np
 
-from pepper_amd.variant import Targets
+from pepper_amd.variant import Coverage, Targets
 from pepper_amd.variant.AlignmentSummarizer import AlignmentSummarizer
 from pepper_amd.variant.DataStore import DataStore
 
@@ -202,10 +202,55 @@ class ImageGenerationUtils:
                 "device_packed_calls": 0, "host_packed_calls": 0, "device_selected_calls": 0, "host_selected_calls": 0,
                 "target_calls": 0}
 
+        # ... and, with options.coverage_bed (track: the job's Coverage.CoverageTrack), the encoder calls of either form that
+        # ran with depth bins set, the depth runs they reported and the calls whose runs outgrew the device's buffer
+        track = getattr(options, "coverage_track", None)
+        if track is not None:
+            mine.update(coverage_calls=0, coverage_runs=0, coverage_overflows=0)
+
         def lap(key, t0):
             now = time.perf_counter()
             mine[key] = mine.get(key, 0.0) + now - t0
             return now
+
+        def collect_depth(depth, group):
+            """The depth runs and totals of the encoder call that covered `group` (depth: the PackedEncoder, or what
+            thread_depth_bins yields), interval by interval into the track."""
+            region, starts, ends, which = depth.depth_runs()
+            bases, sums = depth.depth_totals(len(group))
+            cut = np.searchsorted(region, np.arange(len(group) + 1))          # (the runs come in region order)
+            for r, (chr_name, _start, _end) in enumerate(group):
+                a, b = int(cut[r]), int(cut[r + 1])
+                track.add(chr_name, (_start, _end), (starts[a:b], ends[a:b], which[a:b]), (bases[r], sums[r]))
+            mine["coverage_runs"] += len(region)
+
+        def empty_depth(chr_name, _start, _end):
+            """An interval without a read is never encoded by the host-clipped form: every position of it has depth 0."""
+            on_target = None
+            if bed_list is not None:
+                on_target = Targets.contains(*Targets.table(bed_list, chr_name), np.arange(_start, _end + 1, dtype=np.int64))
+            zeros = np.zeros(_end - _start + 1, np.int64)
+            track.add(chr_name, (_start, _end), Coverage.runs_numpy(zeros, _start, track.bins, on_target),
+                      Coverage.totals_numpy(zeros, track.bins, on_target))
+
+        def summaries_of(prepared, group):
+            """create_summaries of one host-clipped call; with a track, under this thread's depth bins and collected."""
+            if track is None:
+                return create_summaries(prepared)
+            from pepper_amd.variant.PEPPER_VARIANT import thread_depth_bins
+            live = [g for g, p in zip(group, prepared) if p is not None]
+            with thread_depth_bins(track.bins, device) as depth:
+                before = depth.depth_calls()
+                outs = create_summaries(prepared)
+                if live:
+                    collect_depth(depth, live)
+                after = depth.depth_calls()
+            mine["coverage_calls"] += after[0] - before[0]
+            mine["coverage_overflows"] += after[1] - before[1]
+            for g, p in zip(group, prepared):
+                if p is None:
+                    empty_depth(*g)
+            return outs
 
         sink = getattr(options, "fused_sink", None)         # call_variant's fused form: predictions straight from the encoder's windows
         # ... with the selection on the device behind the model: segments instead of probabilities, and neither HDF5 file unless
@@ -248,7 +293,7 @@ class ImageGenerationUtils:
                 prepared.append(generators[chr_name].prepare(wopts, _start, _end))
             t0 = time.perf_counter()
             if bed_list is None:
-                summaries = create_summaries(prepared)
+                summaries = summaries_of(prepared, group)
             else:
                 # one encoder call per run of one contig, with that contig's targets on this thread's handle for its duration
                 summaries, k0 = [], 0
@@ -257,7 +302,7 @@ class ImageGenerationUtils:
                     while k1 < len(group) and group[k1][0] == group[k0][0]:
                         k1 += 1
                     with targets_of(bed_list, group[k0][0], device):
-                        summaries += create_summaries(prepared[k0:k1])
+                        summaries += summaries_of(prepared[k0:k1], group[k0:k1])
                     mine["target_calls"] += 1 if any(p is not None for p in prepared[k0:k1]) else 0
                     k0 = k1
             for (chr_name, _start, _end), out in zip(group, summaries):
@@ -318,6 +363,9 @@ class ImageGenerationUtils:
             # raises leaves its handle out of the pool
             with worker_counters(enc, mine, release_on_error=False, inflate_figures=True, candidates=True):
                 g0 = 0
+                if track is not None:
+                    enc.set_depth_bins(track.bins)
+                    depth_before = enc.depth_calls()
                 while g0 < len(intervals):
                     group = intervals[g0:adjacent_run(intervals, g0, batch, 2 * safe)]
                     chr_name = group[0][0]
@@ -358,6 +406,8 @@ class ImageGenerationUtils:
                         host_clipped(output_hdf_file, group)
                         g0 += n_done
                         continue
+                    if track is not None:
+                        collect_depth(enc, group)
                     t0 = lap("encode", t0)
                     mine["encoder_calls"] += 1
                     mine["target_calls"] += 1 if bed_list is not None else 0
@@ -398,6 +448,11 @@ class ImageGenerationUtils:
                         at += k
                     lap("hdf5", t0)
                     g0 += n_done
+                if track is not None:                # (the handle goes back to the pool without this job's bins)
+                    depth_after = enc.depth_calls()
+                    mine["coverage_calls"] += depth_after[0] - depth_before[0]
+                    mine["coverage_overflows"] += depth_after[1] - depth_before[1]
+                    enc.set_depth_bins(None)
             t_close = time.perf_counter()
         lap("close", t_close)
         merge_stats(stats, mine)
@@ -428,15 +483,31 @@ class ImageGenerationUtils:
         # the reference forks options.threads processes; here they are threads of one process sharing the GPU: the
         # BAM reader, the encoder's host pass and libhdf5 run outside the GIL, each worker has its own BAM / FASTA
         # handles, encoder workspace and output file (interval i goes to worker i % threads, as in the reference)
-        if options.threads <= 1:
-            ImageGenerationUtils.generate_image_and_save_to_file(options, all_intervals, bed_list, 0)
-        else:
-            from concurrent.futures import ThreadPoolExecutor
-            with ThreadPoolExecutor(max_workers=options.threads) as pool:
-                futures = [pool.submit(ImageGenerationUtils.generate_image_and_save_to_file, options, all_intervals, bed_list,
-                                       process_id) for process_id in range(options.threads)]
-                for fut in futures:
-                    fut.result()
+        # options.coverage_bed (or PEPPER_AMD_COVERAGE_BED=1): the depth classes of every position the run looks at, reported by
+        # the encoder beside its candidates and written as PEPPER_VARIANT_COVERAGE.bed (pepper_amd/variant/Coverage.py); the
+        # workers find the track on the options while they run
+        track = None
+        if getattr(options, "coverage_bed", None) or os.environ.get("PEPPER_AMD_COVERAGE_BED") == "1":
+            bins, labels = Coverage.parse_bins(getattr(options, "coverage_bins", None), options.min_coverage_threshold)
+            track = Coverage.CoverageTrack(fasta_handler.get_chromosome_names(), bins, labels)
+            options.coverage_track = track
+        try:
+            if options.threads <= 1:
+                ImageGenerationUtils.generate_image_and_save_to_file(options, all_intervals, bed_list, 0)
+            else:
+                from concurrent.futures import ThreadPoolExecutor
+                with ThreadPoolExecutor(max_workers=options.threads) as pool:
+                    futures = [pool.submit(ImageGenerationUtils.generate_image_and_save_to_file, options, all_intervals, bed_list,
+                                           process_id) for process_id in range(options.threads)]
+                    for fut in futures:
+                        fut.result()
+        finally:
+            if track is not None:
+                del options.coverage_track
+        if track is not None:
+            coverage_dir = getattr(options, "coverage_output_directory", None) or options.image_output_directory
+            runs = track.write(ImageGenerationUtils.handle_output_directory(coverage_dir) + Coverage.BED_NAME)
+            _log("INFO: " + track.log_line(runs))
         _log("INFO: FINISHED IMAGE GENERATION")
         secs = int(time.time() - start_time)
         _log("INFO: TOTAL ELAPSED TIME FOR GENERATING IMAGES: " + str(secs // 60) + " Min " + str(secs % 60) + " Sec")

@@ -151,6 +151,70 @@ def thread_targets(table, device=0):
         _send_targets(lib, enc, None)
 
 
+def _send_depth_bins(lib, enc, bins):
+    """pa_encoder_set_depth_bins: ascending lower bounds starting at 0 (pepper_amd/variant/Coverage.py parse_bins), None: off."""
+    if bins is None or len(bins) == 0:
+        _lib.check(lib.pa_encoder_set_depth_bins(enc, 0, None))
+        return
+    lower = np.ascontiguousarray(bins, np.int32)
+    _lib.check(lib.pa_encoder_set_depth_bins(enc, len(lower), lower.ctypes.data))
+
+
+def _depth_runs(lib, enc):
+    """pa_encoder_depth_runs -> (region int32, start int64, end int64, bin int32) of the handle's last run: every region's runs
+    in region and position order, contig coordinates, ends half-open, bin -1 outside the targets."""
+    n = ctypes.c_int64()
+    _lib.check(lib.pa_encoder_depth_runs(enc, 0, None, None, None, None, ctypes.byref(n)))
+    k = max(1, n.value)
+    region, start, end, which = np.zeros(k, np.int32), np.zeros(k, np.int64), np.zeros(k, np.int64), np.zeros(k, np.int32)
+    _lib.check(lib.pa_encoder_depth_runs(enc, k, region.ctypes.data, start.ctypes.data, end.ctypes.data, which.ctypes.data,
+                                         ctypes.byref(n)))
+    return region[:n.value], start[:n.value], end[:n.value], which[:n.value]
+
+
+def _depth_totals(lib, enc, n_regions):
+    """pa_encoder_depth_totals -> (bases int64 [n_regions, 8], sum of depths int64 [n_regions]) of the handle's last run."""
+    bases, sums = np.zeros((max(1, n_regions), 8), np.int64), np.zeros(max(1, n_regions), np.int64)
+    _lib.check(lib.pa_encoder_depth_totals(enc, n_regions, bases.ctypes.data, sums.ctypes.data))
+    return bases[:n_regions], sums[:n_regions]
+
+
+def _depth_calls(lib, enc):
+    made, overflows = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(lib.pa_encoder_depth_calls(enc, ctypes.byref(made), ctypes.byref(overflows)))
+    return made.value, overflows.value
+
+
+class _ThreadDepth(object):
+    """What thread_depth_bins yields: the depth runs, totals and counters of this thread's encoder, under the names
+    PackedEncoder gives them."""
+
+    def __init__(self, lib, enc):
+        self.lib, self.enc = lib, enc
+
+    def depth_runs(self):
+        return _depth_runs(self.lib, self.enc)
+
+    def depth_totals(self, n_regions):
+        return _depth_totals(self.lib, self.enc, n_regions)
+
+    def depth_calls(self):
+        return _depth_calls(self.lib, self.enc)
+
+
+@contextlib.contextmanager
+def thread_depth_bins(bins, device=0):
+    """This thread's encoder on `device` -- what RegionalSummaryGenerator and generate_summary_arrays_batch run on -- with depth
+    bins set for the calls inside (pa_encoder_set_depth_bins) and without them again behind: the handle outlives the job.
+    Yields an object whose depth_runs() / depth_totals(n_regions) / depth_calls() speak of that handle's last run."""
+    lib, enc = _encoder(device)
+    _send_depth_bins(lib, enc, bins)
+    try:
+        yield _ThreadDepth(lib, enc)
+    finally:
+        _send_depth_bins(lib, enc, None)
+
+
 def flatten_reads(reads):
     """type_read-like objects -> the flat arrays of pa_pileup."""
     n = len(reads)
@@ -260,6 +324,12 @@ class StagedBatch(object):
                     host_enumeration_ms=ms[4], run_ms=ms[5], host_bucket_ms=ms[6], host_bucket_and_threads_ms=ms[7],
                     upload_ms=ms[8], unpack_clip_ms=ms[9], device_enumeration_ms=ms[12])
 
+    def depth_runs_ms(self):
+        """Event time of the depth-class kernels of the last run (pa_encoder_last_timing [13]; 0 without depth bins)."""
+        ms = np.zeros(14, np.float64)
+        _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 14))
+        return float(ms[13])
+
     def stats(self):
         v = np.zeros(6, np.int64)
         _lib.check(self.lib.pa_encoder_batch_stats(self.enc, v.ctypes.data, 6))
@@ -343,6 +413,7 @@ class PackedEncoder(object):
                         and (enc.stream is not None) == bool(torch_stream)):
                     enc = cls._idle.pop(k)
                     enc.set_targets(None)        # (whatever job had it last: its targets are not this one's)
+                    enc.set_depth_bins(None)     # (... nor its depth bins)
                     return enc
         size = arena_bytes
         while True:
@@ -425,6 +496,22 @@ class PackedEncoder(object):
             return
         _send_targets(self.lib, self.enc, table)
         self._targets_contig = contig if table is not None else None
+
+    def set_depth_bins(self, bins):
+        """Depth classes of this handle's next runs (pa_encoder_set_depth_bins): ascending lower bounds starting at 0, None: off."""
+        _send_depth_bins(self.lib, self.enc, bins)
+
+    def depth_runs(self):
+        """-> (region, start, end, bin) of the last run's depth runs (pa_encoder_depth_runs)."""
+        return _depth_runs(self.lib, self.enc)
+
+    def depth_totals(self, n_regions):
+        """-> (bases per bin [n_regions, 8], sum of depths [n_regions]) of the last run (pa_encoder_depth_totals)."""
+        return _depth_totals(self.lib, self.enc, n_regions)
+
+    def depth_calls(self):
+        """-> (runs made with depth bins set, runs among them whose records were emitted twice) since this handle was created."""
+        return _depth_calls(self.lib, self.enc)
 
     def candidate_calls(self):
         """-> (runs enumerated on the device, runs handed back to the host) since this handle was created."""
