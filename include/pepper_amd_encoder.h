@@ -423,7 +423,8 @@ int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity);
 int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
 /* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
  * its tables (the quality buffer among them when the finish produced qualities, the edit records once pa_stitcher_edits ran,
- * and once pa_stitcher_fill ran its table of 4 bytes per position, the filled sequence and the filled qualities). */
+ * once pa_stitcher_fill ran its table of 4 bytes per position, the filled sequence and the filled qualities, and once
+ * pa_stitcher_gate ran its withheld records). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
 
 /* What the last finish changed against the draft (opt-in, not in the reference; pepper_amd/polish/Edits.py is the host twin and
@@ -449,8 +450,8 @@ typedef struct pa_stitch_edit {
  * One wait; the records stay on the device until pa_stitcher_take_edits, in a buffer allocated on first use and counted in
  * pa_stitcher_stats [5] from then on.  A later finish invalidates them.
  * PA_ERR_INVALID before any launch: no finish yet; the last finish gave no sequence (a bad label, a failure); draft_length <=
- * the largest piece_last; the finish had more than 65 535 pieces; draft is NULL and no pa_stitcher_fill of a draft of
- * draft_length letters ran since the finish.  The handle stays usable. */
+ * the largest piece_last; the finish had more than 65 535 pieces; draft is NULL and neither a pa_stitcher_fill nor a
+ * pa_stitcher_gate of a draft of draft_length letters ran since the finish.  The handle stays usable. */
 int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts /* [6] */);
 /* The records of the last pa_stitcher_edits (capacity >= *n_edits records).  PA_ERR_INVALID: pa_stitcher_edits has not run since
  * the last finish; capacity is short.  The handle stays usable. */
@@ -472,6 +473,33 @@ int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity
  * the piece's last position.  PA_ERR_UNSUPPORTED: the draft or the filled consensus has more than 2^32 - 1 letters.  The handle
  * stays usable, and a refused call changes nothing. */
 int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* filled_length, int64_t* counts /* [2] */);
+
+/* Apply only the edits the model is sure of (opt-in, not in the reference; Stitch.py gate_numpy is the host twin).  Runs after a
+ * finish with any number of pieces and BEFORE pa_stitcher_fill and pa_stitcher_edits, over the winners of the merge (so the result
+ * does not depend on how the rows were chunked or in which order they were added); draft[0 .. draft_length) is the whole contig.
+ * With d = upper(draft[p]) and the winner's raw phred (0 for a slot without a writer):
+ *   slot (p, 0), d in ACGT, the winner is a base other than d (SUB) or a gap / no writer (DEL), phred < min_phred:
+ *       WITHHELD -- the slot emits d, upper-cased, with phred 0 (quality '!')
+ *   slot (p, i > 0), the winner is a base (INS), phred < min_phred:   WITHHELD -- the slot emits nothing
+ *   everything else -- phred >= min_phred, a winner equal to d, a gap in an insert slot, and EVERY slot (p, 0) whose draft letter
+ *   is not one of ACGT -- stays as the model decided it.
+ * A withheld slot's letter and winner word are rewritten (phred byte 0, the label of what it emits), the letters are scanned and
+ * emitted again: piece_length [n_pieces of the finish] and *sequence_length are those of the gated consensus, and from then on,
+ * until the next finish, pa_stitcher_take, _take_qualities, _fill, _edits and _stats speak of it -- the edit records are exactly the
+ * applied edits.  A following pa_stitcher_fill or pa_stitcher_edits may pass draft = NULL with the same draft_length and read the
+ * copy this call uploaded.  counts: withheld in all, SUB, DEL, INS.  One wait.  The handle keeps its rows: a second finish of the
+ * contig gives the ungated tables again.
+ * The withheld records (pa_stitcher_take_withheld; capacity >= counts[0]) are pa_stitch_edit-shaped and ordered as the edit records
+ * are: kind SUB / DEL / INS, letter the model's (0 for DEL), draft d (0 for INS), phred the winner's, offset the place of the kept
+ * draft letter (SUB, DEL) or the letters in front of the slot (INS) in the consensus the handle speaks of when they are taken: the
+ * gated one, and after a pa_stitcher_fill the filled one.  They stay on the device until taken; pa_stitcher_stats [5] grows by 16
+ * bytes per record, and by the letters the sequence gained or lost (its quality buffer).
+ * PA_ERR_INVALID before any launch, the handle stays usable and nothing changes: no finish yet; the finish gave no sequence; a chunk
+ * of the contig was added without qualities; draft_length <= the largest piece_last; min_phred outside 1..255; a gate or a fill
+ * already ran since the finish; the finish had more than 65 535 pieces; take_withheld without a gate, or with short capacity. */
+int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, int32_t min_phred, int64_t* piece_length,
+                     int64_t* sequence_length, int64_t* counts /* [4] */);
+int pa_stitcher_take_withheld(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity);
 
 /* ------------------------------------------------------------------------------------------
  * The candidate finder's selection ON THE DEVICE (opt-in: call_variant(..., fused_inference=True, device_selection=True);

@@ -149,6 +149,8 @@ SYMBOLS = [
     ("pa_stitcher_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     ("pa_stitcher_take_edits", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_stitcher_fill", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_stitcher_gate", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_stitcher_take_withheld", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_selector_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_selector_destroy", None, [c_void_p]),
     ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
@@ -344,6 +346,33 @@ def polish_fill():
     where no prediction covered a position, and without a region the contigs no read landed on.  Unset or any other value: the
     reference's stitch, which leaves such sequence out."""
     return os.environ.get(POLISH_FILL_ENV, "0") == "1"
+
+
+POLISH_MIN_QUALITY_ENV = "PEPPER_AMD_POLISH_MIN_QUALITY"
+
+
+def min_quality_value(min_quality):
+    """What every stitch form makes of its min_quality argument: None or 0 -> None (off), an integer 1..255 -> itself, anything
+    else ValueError."""
+    if min_quality is None:
+        return None
+    if isinstance(min_quality, bool) or int(min_quality) != min_quality or not 0 <= min_quality <= 255:
+        raise ValueError("min_quality is an integer from 1 to 255 (0 or None: off), not %r" % (min_quality,))
+    return int(min_quality) or None
+
+
+def polish_min_quality():
+    """PEPPER_AMD_POLISH_MIN_QUALITY=Q (1..255): polish() applies only the edits against the draft whose winning prediction has
+    phred >= Q and keeps the draft's letter elsewhere (pepper_amd/polish/Stitch.py gate_numpy; <prefix>_pepper_polished.withheld.tsv
+    lists what it kept back).  Unset, empty or 0: every label the model emits is applied.  Anything else: ValueError."""
+    text = os.environ.get(POLISH_MIN_QUALITY_ENV, "").strip()
+    if not text:
+        return None
+    try:
+        value = int(text)
+    except ValueError:
+        raise ValueError(POLISH_MIN_QUALITY_ENV + " is an integer from 1 to 255 (0 or unset: off), not %r" % text)
+    return min_quality_value(value)
 
 
 def check(rc):

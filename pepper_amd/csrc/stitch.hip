@@ -34,6 +34,13 @@
 // inside the piece; the scanned word also counts, in its upper half, the positions that begin a run, so the one total that comes
 // back sizes the buffer and counts the runs.  Then one lane per POSITION writes what the position gives: its slots' letters at
 // lead + place + holes, or draft[p] (and '!') at lead + letters in front + holes.  The two ends are copies of the draft.
+//
+// Gate (pa_stitcher_gate, pa_stitcher_take_withheld; opt-in, not in the reference): only the edits against the draft whose winner
+// has a phred of at least min_phred are applied; the others are withheld -- the slot emits the draft's letter (SUB, DEL) or nothing
+// (INS) with phred 0 -- and listed.  Runs behind a finish, in front of fill and edits.  One lane per slot, twice: the first pass
+// decides from the winner word and the draft, rewrites letters[] and counts; the letters are scanned again; the second pass
+// decides once more (the words still hold the model's labels), places the records (count, scan, write) and rewrites the words, so
+// emit, fill and edits read consistent tables without knowing about the gate.  A lane touches only its own slot.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -325,7 +332,9 @@ template <class T, class K> PA_DEV uint64_t last_at_most(const T* __restrict__ v
     return lo;
 }
 
-PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) {
+// letter: what the slot emits (the edit passes read letters[s]; the gate passes decode the winner word, which still holds the
+// model's label while letters[] is being rewritten); RUNS: also look for the run of uncovered positions the slot closes
+template <bool RUNS> PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s, uint8_t letter) {
     SlotEdit e;
     // zero-width positions share the base of the next covered one: the LAST position whose base is <= s owns the slot
     const uint64_t gp = last_at_most(t.slot_base, t.n_positions, (uint32_t)s);
@@ -333,7 +342,7 @@ PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) {
     const uint64_t row0 = t.pbase[e.piece];
     e.position = t.pmin[e.piece] + (uint32_t)(gp - row0);
     e.index = (uint32_t)s - t.slot_base[gp];
-    e.letter = t.letters[s];
+    e.letter = letter;
     e.draft = 0;
     e.kind = 0;
     e.gap = false;
@@ -348,13 +357,15 @@ PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) {
     e.draft = d;
     if (!e.letter) e.kind = PA_EDIT_DEL;
     else if (e.letter != d) e.kind = PA_EDIT_SUB;
-    if (gp > row0 && t.width[gp - 1] == 0) {            // the piece's first position has a slot, so slot s - 1 is the piece's too
+    if (RUNS && gp > row0 && t.width[gp - 1] == 0) {    // the piece's first position has a slot, so slot s - 1 is the piece's too
         const uint64_t before = last_at_most(t.slot_base, t.n_positions, (uint32_t)(s - 1));
         e.gap = true;
         e.open_at = e.position - (uint32_t)(gp - before) + 1;
     }
     return e;
 }
+
+PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) { return classify_slot<true>(t, s, t.letters[s]); }
 
 // sums[b] = records of slots [b * B, (b + 1) * B) (a workgroup past the end writes 0); kinds[k] += records of kind k
 __global__ __launch_bounds__(ST_THREADS) void k_edit_count(EditTables t, uint64_t* __restrict__ sums,
@@ -449,6 +460,126 @@ __global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const u
     }
 }
 
+// ---------------------------------------------------------------- gate: withhold the edits below a phred ----
+// What one slot decides, read off the winner word the finish left (the model's label and raw phred) and the draft.  The word is
+// read, not letters[]: the first pass rewrites letters[] while the second still has to find the model's letter.
+struct SlotGate {
+    SlotEdit e;                                         // the edit the winner makes against the draft (kind 0: none)
+    bool withheld;
+    uint8_t phred;                                      // the winner's raw phred (0: no writer)
+    uint8_t emits;                                      // what a withheld slot emits: the draft letter, nothing (0) for an INS
+};
+
+PA_DEV uint8_t word_letter(unsigned long long word) {
+    const uint32_t label = (uint32_t)word & 0xFFu;
+    return label >= 1 && label <= 4 ? (uint8_t)((0x54474341u >> (8 * (label - 1))) & 0xFFu) : (uint8_t)0;
+}
+PA_DEV uint32_t base_code(uint8_t d) { return d == 'A' ? 1u : d == 'C' ? 2u : d == 'G' ? 3u : d == 'T' ? 4u : 0u; }
+
+// withheld: an edit whose phred is below min_phred; a SUB or DEL only where the draft letter is a base (the gate has no letter to
+// keep elsewhere, and the model's decision stands)
+PA_DEV SlotGate gate_slot(const EditTables& t, uint64_t s, uint32_t min_phred) {
+    SlotGate g;
+    const unsigned long long word = t.slots[s];
+    g.e = classify_slot<false>(t, s, word_letter(word));
+    g.phred = (uint8_t)((word >> 8) & 0xFFu);
+    g.withheld = g.e.kind != 0 && g.phred < min_phred && (g.e.kind == PA_EDIT_INS || base_code(g.e.draft) != 0);
+    g.emits = g.e.kind == PA_EDIT_INS ? (uint8_t)0 : g.e.draft;
+    return g;
+}
+
+// first pass: letters[i] of every withheld slot becomes what it emits now; sums[b] = withheld slots of [b * B, (b + 1) * B) (a
+// workgroup past the end writes 0); kinds[k] += withheld edits of kind k.  A lane writes the letter of its own slots only.
+__global__ __launch_bounds__(ST_THREADS) void k_gate_mark(EditTables t, uint32_t min_phred, uint8_t* letters,
+                                                          uint64_t* __restrict__ sums, unsigned long long* __restrict__ kinds) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    __shared__ uint64_t s_kind[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    uint64_t v = 0, packed = 0;                         // packed: SUB | DEL << 16 | INS << 32 (a workgroup has <= 1024 each)
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        if (i0 + k >= t.n_slots) break;
+        const SlotGate g = gate_slot(t, i0 + k, min_phred);
+        if (!g.withheld) continue;
+        letters[i0 + k] = g.emits;
+        v += 1;
+        packed += 1ull << (16 * (g.e.kind - 1));
+    }
+    for (int d = 32; d; d >>= 1)
+        packed += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(packed >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)packed, d);
+    if ((threadIdx.x & 63) == 0) s_kind[threadIdx.x >> 6] = packed;
+    uint64_t total;
+    (void)block_scan(v, s_wave, &total);               // (its barrier also publishes s_kind)
+    if (threadIdx.x == 0) {
+        sums[blockIdx.x] = total;
+        uint64_t all = 0;
+        for (int w = 0; w < ST_THREADS / 64; ++w) all += s_kind[w];
+        const unsigned long long sub = all & 0xFFFFu, del = (all >> 16) & 0xFFFFu, ins = (all >> 32) & 0xFFFFu;
+        if (sub) atomicAdd(&kinds[PA_EDIT_SUB], sub);     // one atomic per workgroup and kind; integer sums do not depend on the order
+        if (del) atomicAdd(&kinds[PA_EDIT_DEL], del);
+        if (ins) atomicAdd(&kinds[PA_EDIT_INS], ins);
+    }
+}
+
+// second pass, after the letters were scanned again (t.place is the gated place): the record of a withheld slot goes to
+// out[offset[b] + withheld slots of the block in front of it], and its winner word loses its phred and takes the label of what it
+// emits, so that emit, fill and edits read tables that agree with letters[].  piece_start[p] = where the records of piece p begin.
+__global__ __launch_bounds__(ST_THREADS) void k_gate_write(EditTables t, uint32_t min_phred, const uint64_t* __restrict__ offset,
+                                                           uint64_t n_records, pa_stitch_edit* __restrict__ out,
+                                                           uint64_t* __restrict__ piece_start, unsigned long long* slots) {
+    __shared__ uint64_t s_wave[ST_THREADS / 64];
+    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
+    SlotGate item[ST_ITEMS];
+    uint64_t v = 0;
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        item[k].withheld = false;
+        if (i0 + k < t.n_slots) item[k] = gate_slot(t, i0 + k, min_phred);
+        v += item[k].withheld;
+    }
+    uint64_t total;
+    uint64_t run = block_scan(v, s_wave, &total) - v + offset[blockIdx.x];
+    for (int k = 0; k < ST_ITEMS; ++k) {
+        if (i0 + k >= t.n_slots) break;
+        const SlotGate& g = item[k];
+        if (g.e.index == 0 && g.e.position == t.pmin[g.e.piece]) piece_start[g.e.piece] = run;
+        if (!g.withheld) continue;
+        const uint32_t at = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[g.e.piece]);
+        if (run < n_records)
+            out[run] = make_edit(g.e.position, at, g.e.index, t.take_index[g.e.piece], g.e.kind, g.e.draft,
+                                 g.e.kind == PA_EDIT_DEL ? (uint8_t)0 : g.e.letter, g.phred);
+        slots[i0 + k] = (slots[i0 + k] & ~0xFFFFull) | base_code(g.emits);
+        run += 1;
+    }
+}
+
+// the withheld records of a gated finish that was filled afterwards: their offsets count the filled consensus, as the edit
+// records' do (one piece: the row of a position is position - first)
+__global__ void k_gate_filled_offsets(pa_stitch_edit* __restrict__ records, uint64_t n, const uint32_t* __restrict__ holes,
+                                      uint64_t n_positions, uint32_t first, uint32_t lead) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t row = (uint64_t)(records[i].position - first);
+    if (row < n_positions) records[i].offset += lead + holes[row];
+}
+
+// letter_shift[p] (take() offset of a piece's first letter - its table offset) of the gated pieces, before the host knows their
+// lengths: the pieces with rows walked in take() order by one lane (a finish has a handful of pieces).  start[p] as
+// k_stitch_bounds left it, ST_AT_END where a piece has no slot behind it.
+constexpr uint64_t ST_AT_END = ~0ull;
+__global__ void k_gate_shift(const uint16_t* __restrict__ order, uint32_t n_taken, const uint64_t* __restrict__ start, uint32_t n_pieces,
+                             const uint64_t* __restrict__ n_letters, int64_t* __restrict__ shift) {
+    if (blockIdx.x != 0 || threadIdx.x != 0) return;
+    const uint64_t end = *n_letters;
+    uint64_t at = 0;
+    for (uint32_t k = 0; k < n_taken; ++k) {
+        const uint32_t p = order[k];
+        if (p >= n_pieces) continue;
+        const uint64_t from = start[p] == ST_AT_END ? end : start[p];
+        const uint64_t to = p + 1 < n_pieces && start[p + 1] != ST_AT_END ? start[p + 1] : end;
+        shift[p] = (int64_t)at - (int64_t)from;
+        at += to - from;
+    }
+}
+
 struct Buffer {
     void* p = nullptr;
     size_t cap = 0;
@@ -507,7 +638,12 @@ struct pa_stitcher {
     Buffer f_holes, f_fill, f_fillq;
     bool filled = false;                                // pa_stitcher_fill ran on the last finish: take, take_qualities, edits speak of it
     int64_t filled_length = 0, fill_lead = 0, fill_bytes = 0;      // fill_bytes: its share of last_scratch_bytes
-    int64_t draft_held = -1;                            // e_draft holds draft[0 .. draft_held) of that fill (-1: it does not)
+    int64_t draft_held = -1;                            // e_draft holds draft[0 .. draft_held) of that fill or gate (-1: it does not)
+    // gate's staging (per piece: letter shift, where its records begin, its take() place; the counts) and the withheld records
+    Buffer g_piece, g_records;
+    bool gated = false;                                 // pa_stitcher_gate ran on the last finish: every later call speaks of the gated tables
+    bool withheld_filled = false;                       // ... and the records' offsets already count the fill that followed
+    int64_t n_withheld = 0;
     std::vector<PieceOut> pieces;                       // of the last finish, in output order
     int64_t sequence_length = 0;
     bool finished = false;                              // a finish has run: the three below speak of it
@@ -535,7 +671,33 @@ int no_memory(const char* what, uint64_t bytes) {
 std::vector<Buffer*> buffers_of(pa_stitcher* s) {
     return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
             &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words,
-            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq};
+            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq, &s->g_piece, &s->g_records};
+}
+
+// Records the write passes left piece after piece in TABLE order (start[p]: where those of table piece p begin, on the device)
+// -> dst, piece after piece as take() goes
+int take_records(pa_stitcher* s, const uint64_t* d_start, const pa_stitch_edit* records, int64_t n, pa_stitch_edit* dst, const char* what) {
+    const size_t np = (size_t)s->last_pieces;
+    std::vector<uint64_t> start(np);
+    ST_HIP(hipMemcpyAsync(start.data(), d_start, np * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    // in the buffer the pieces lie in table order: a piece's records end where those of the next piece with rows begin
+    std::vector<std::pair<int, uint64_t>> table;
+    for (const PieceOut& piece : s->pieces) table.push_back({piece.piece, start[(size_t)piece.piece]});
+    std::sort(table.begin(), table.end());
+    std::vector<uint64_t> end_of(np, 0);
+    for (size_t k = 0; k < table.size(); ++k) end_of[(size_t)table[k].first] = k + 1 < table.size() ? table[k + 1].second : (uint64_t)n;
+    int64_t at = 0;
+    for (const PieceOut& piece : s->pieces) {
+        const uint64_t begin = start[(size_t)piece.piece], end = end_of[(size_t)piece.piece];
+        if (begin > end || end > (uint64_t)n || at + (int64_t)(end - begin) > n)
+            return pa::set_error(PA_ERR_HIP, std::string(what) + ": a piece's records lie outside the buffer");
+        if (end == begin) continue;
+        ST_HIP(hipMemcpyAsync(dst + at, records + begin, (size_t)(end - begin) * sizeof(pa_stitch_edit), hipMemcpyDeviceToHost, s->stream));
+        at += (int64_t)(end - begin);
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
 }
 
 }  // namespace
@@ -701,6 +863,8 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     s->filled = false;
     s->filled_length = s->fill_lead = s->fill_bytes = 0;
     s->draft_held = -1;
+    s->gated = s->withheld_filled = false;
+    s->n_withheld = 0;
     s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
@@ -927,9 +1091,9 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
     std::lock_guard<std::mutex> guard(s->lock);
     *n_edits = 0;
     for (int k = 0; k < 6; ++k) counts[k] = 0;
-    const bool held = !draft && s->filled && s->draft_held == draft_length;      // the draft the fill uploaded
+    const bool held = !draft && (s->filled || s->gated) && s->draft_held == draft_length;      // the draft a fill or a gate uploaded
     if (draft_length > 0 && !draft && !held)
-        return pa::set_error(PA_ERR_INVALID, "stitcher edits: null draft (only after a pa_stitcher_fill of a draft of this length)");
+        return pa::set_error(PA_ERR_INVALID, "stitcher edits: null draft (only after a pa_stitcher_fill or pa_stitcher_gate of a draft of this length)");
     if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher edits: no contig has been finished");
     if (!s->have_sequence)
         return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish gave no sequence (a label that is no base, or it failed)");
@@ -1027,11 +1191,13 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
 }
 
 int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* filled_length, int64_t* counts) {
-    if (!s || !filled_length || !counts || draft_length < 0 || (draft_length > 0 && !draft))
-        return pa::set_error(PA_ERR_INVALID, "stitcher fill: null or negative argument");
+    if (!s || !filled_length || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher fill: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
     *filled_length = 0;
     counts[0] = counts[1] = 0;
+    const bool held = !draft && s->gated && s->draft_held == draft_length;      // the draft the gate uploaded
+    if (draft_length > 0 && !draft && !held)
+        return pa::set_error(PA_ERR_INVALID, "stitcher fill: null draft (only after a pa_stitcher_gate of a draft of this length)");
     if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher fill: no contig has been finished");
     if (!s->have_sequence)
         return pa::set_error(PA_ERR_INVALID, "stitcher fill: the last finish gave no sequence (a label that is no base, or it failed)");
@@ -1050,12 +1216,12 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
     if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
     s->have_edits = s->filled = false;
     s->n_edits = s->fill_bytes = s->filled_length = s->fill_lead = 0;
-    s->draft_held = -1;
+    if (!held) s->draft_held = -1;
     ST_HIP(hipSetDevice(s->device));
     const uint64_t n_positions = rows ? (uint64_t)s->last_positions : 0, n_slots = (uint64_t)s->last_slots;
     const uint64_t n_letters = (uint64_t)s->sequence_length;
     if (!s->e_draft.grow((size_t)draft_length + 1) || !s->f_holes.grow(n_positions * 4 + 4)) return no_memory("the draft", (uint64_t)draft_length);
-    if (draft_length > 0) ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
+    if (draft_length > 0 && !held) ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
     uint64_t word = 0;                                  // runs that begin inside the piece << 32 | positions without a slot
     if (n_positions) {                                  // (f_scan is the width scan's scratch: sized for n_positions, free since)
         const uint64_t* d_total = scan_exclusive<LoadHole, uint32_t>(s->stream, LoadHole{s->f_width.as<uint32_t>()}, n_positions,
@@ -1114,29 +1280,184 @@ int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity
                                                  std::to_string(capacity));
     if (s->n_edits == 0) return PA_OK;
     ST_HIP(hipSetDevice(s->device));
-    // where every piece's records begin (table order; the write pass left them), then piece after piece as take() goes
+    // where every piece's records begin (table order; the write pass left them)
     const size_t np = (size_t)s->last_pieces;
-    std::vector<uint64_t> start(np);
-    ST_HIP(hipMemcpyAsync(start.data(), s->e_piece.as<uint8_t>() + np * 8, np * 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipStreamSynchronize(s->stream));
-    // in the buffer the pieces lie in table order: a piece's records end where those of the next piece with rows begin
-    std::vector<std::pair<int, uint64_t>> table;
-    for (const PieceOut& piece : s->pieces) table.push_back({piece.piece, start[(size_t)piece.piece]});
-    std::sort(table.begin(), table.end());
-    std::vector<uint64_t> end_of(np, 0);
-    for (size_t k = 0; k < table.size(); ++k) end_of[(size_t)table[k].first] = k + 1 < table.size() ? table[k + 1].second : (uint64_t)s->n_edits;
-    int64_t at = 0;
-    for (const PieceOut& piece : s->pieces) {
-        const uint64_t begin = start[(size_t)piece.piece], end = end_of[(size_t)piece.piece];
-        if (begin > end || end > (uint64_t)s->n_edits || at + (int64_t)(end - begin) > s->n_edits)
-            return pa::set_error(PA_ERR_HIP, "stitcher take edits: a piece's records lie outside the buffer");
-        if (end == begin) continue;
-        ST_HIP(hipMemcpyAsync(dst + at, s->e_records.as<pa_stitch_edit>() + begin, (size_t)(end - begin) * sizeof(pa_stitch_edit),
-                              hipMemcpyDeviceToHost, s->stream));
-        at += (int64_t)(end - begin);
+    return take_records(s, (const uint64_t*)(s->e_piece.as<uint8_t>() + np * 8), s->e_records.as<pa_stitch_edit>(), s->n_edits, dst,
+                        "stitcher take edits");
+}
+
+int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, int32_t min_phred, int64_t* piece_length,
+                     int64_t* sequence_length, int64_t* counts) {
+    if (!s || !sequence_length || !counts || draft_length < 0 || (draft_length > 0 && !draft))
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher gate: no contig has been finished");
+    if (!s->have_sequence)
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (!s->contig_qualities)
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: a chunk of the contig was added without qualities (pa_stitcher_add_qual on "
+                                             "every chunk gives the gate its phred)");
+    if (min_phred < 1 || min_phred > 255)
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: min_phred " + std::to_string(min_phred) + " is outside 1..255");
+    if (s->gated || s->filled)
+        return pa::set_error(PA_ERR_INVALID, std::string("stitcher gate: a ") + (s->gated ? "gate" : "fill") +
+                                                 " already ran since the finish (the gate comes first, once)");
+    if (s->last_pieces > 0xFFFF)
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: the last finish had " + std::to_string(s->last_pieces) +
+                                                 " pieces, a record names 65535");
+    if (s->last_pieces > 0 && !piece_length) return pa::set_error(PA_ERR_INVALID, "stitcher gate: null piece_length");
+    int64_t hi = -1;
+    for (const PieceOut& piece : s->pieces) hi = std::max(hi, piece.last);
+    if (draft_length <= hi)
+        return pa::set_error(PA_ERR_INVALID, "stitcher gate: the draft has " + std::to_string(draft_length) +
+                                                 " letters, a piece ends at position " + std::to_string(hi));
+    if (draft_length > ST_MAX_POSITION)
+        return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher gate: the draft has " + std::to_string(draft_length) + " letters, an offset counts 2^32 - 1");
+    const size_t np = (size_t)s->last_pieces;
+    const uint64_t n_slots = (uint64_t)s->last_slots, n_positions = (uint64_t)s->last_positions;
+    const uint64_t blocks = scan_blocks(n_slots), sum_words = scan_scratch_words(n_slots);
+    const size_t off_start = np * 8, off_kinds = off_start + np * 8, off_index = off_kinds + 4 * 8, off_order = off_index + np * 2,
+                 piece_bytes = off_order + np * 2;
+    ST_HIP(hipSetDevice(s->device));
+    // (f_scan is the width scan's scratch, free since the finish: here it takes the block sums, sized for the slots)
+    if (!s->e_draft.grow((size_t)draft_length + 1) || !s->g_piece.grow(piece_bytes + 8) || !s->f_scan.grow(sum_words * 8))
+        return no_memory("the draft", (uint64_t)draft_length);
+    // records of the ungated consensus are gone
+    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
+    s->have_edits = false;
+    s->n_edits = 0;
+    s->draft_held = -1;
+    for (int k = 0; k < 4; ++k) counts[k] = 0;
+    if (draft_length > 0) ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
+    if (s->pieces.empty() || n_slots == 0) {            // nothing was merged: nothing to withhold
+        ST_HIP(hipStreamSynchronize(s->stream));
+        s->draft_held = draft_length;
+        s->gated = true;
+        s->withheld_filled = false;
+        s->n_withheld = 0;
+        for (size_t p = 0; p < np; ++p) piece_length[p] = 0;
+        *sequence_length = s->sequence_length;
+        return PA_OK;
     }
-    ST_HIP(hipStreamSynchronize(s->stream));
+    uint8_t* gw = s->g_piece.as<uint8_t>();
+    int64_t* d_shift = (int64_t*)gw;
+    uint64_t* d_rec_start = (uint64_t*)(gw + off_start);
+    unsigned long long* d_kinds = (unsigned long long*)(gw + off_kinds);
+    uint16_t* d_index = (uint16_t*)(gw + off_index);
+    uint16_t* d_order = (uint16_t*)(gw + off_order);
+    // the pieces' take() order is the finish's: (first, last) do not move
+    std::vector<uint16_t> take_index(np, 0), order(s->pieces.size(), 0);
+    for (size_t k = 0; k < s->pieces.size(); ++k) {
+        take_index[(size_t)s->pieces[k].piece] = (uint16_t)k;
+        order[k] = (uint16_t)s->pieces[k].piece;
+    }
+    ST_HIP(hipMemcpyAsync(d_index, take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(d_order, order.data(), order.size() * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(d_shift, 0, np * 8 + np * 8 + 4 * 8, s->stream));
+    // the piece words of the finish: [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces
+    uint8_t* pw = s->f_piece.as<uint8_t>();
+    const size_t off_pbase = (np * 8 + 7) / 8 * 8;
+    uint64_t* d_pbase = (uint64_t*)(pw + off_pbase);
+    uint64_t* d_start = (uint64_t*)(pw + off_pbase + np * 8);
+    EditTables t;
+    t.slot_base = s->f_base.as<uint32_t>();
+    t.width = s->f_width.as<uint32_t>();
+    t.slots = s->f_slots.as<unsigned long long>();
+    t.letters = s->f_letters.as<uint8_t>();
+    t.place = s->f_place.as<uint32_t>();
+    t.pbase = d_pbase;
+    t.pmin = (const uint32_t*)pw;
+    t.letter_shift = d_shift;
+    t.take_index = d_index;
+    t.draft = s->e_draft.as<uint8_t>();
+    t.holes = nullptr;
+    t.lead = 0;
+    t.n_positions = n_positions;
+    t.n_slots = n_slots;
+    t.n_pieces = (uint32_t)np;
+    t.draft_lo = 0;
+    t.draft_span = (uint32_t)draft_length;
+    t.qualities = 1u;
+    // 1. decide every slot, rewrite its letter, count; 2. the letters' places again, the pieces' starts; 3. scan of the counts
+    uint64_t* sums = s->f_scan.as<uint64_t>();
+    k_gate_mark<<<(unsigned)(blocks + 1), ST_THREADS, 0, s->stream>>>(t, (uint32_t)min_phred, s->f_letters.as<uint8_t>(), sums, d_kinds);
+    ST_HIP(hipGetLastError());
+    const uint64_t* d_letters_total = scan_exclusive<LoadLetter, uint32_t>(s->stream, LoadLetter{s->f_letters.as<uint8_t>()}, n_slots,
+                                                                           s->f_place.as<uint32_t>(), s->f_words.as<uint64_t>());
+    ST_HIP(hipGetLastError());
+    k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(d_pbase, (int)np, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
+                                                                     n_positions, n_slots, ST_AT_END, d_start);      // (the end: not known yet)
+    ST_HIP(hipGetLastError());
+    k_gate_shift<<<1, 64, 0, s->stream>>>(d_order, (uint32_t)order.size(), d_start, (uint32_t)np, d_letters_total, d_shift);
+    ST_HIP(hipGetLastError());
+    scan_sums(s->stream, sums, blocks + 1, sums + blocks + 1);
+    ST_HIP(hipGetLastError());
+    uint64_t n_letters = 0, total = 0, kinds[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> start(np + 1);
+    ST_HIP(hipMemcpyAsync(&n_letters, d_letters_total, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(&total, sums + blocks, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(kinds, d_kinds, 4 * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(start.data(), d_start, np * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));            // the one wait: the sizes of the sequence and of the record buffer
+    // from here on the tables are the gated ones whatever happens: letters[] and place[] are rewritten
+    const int64_t letters_before = s->sequence_length;
+    s->gated = true;
+    s->withheld_filled = false;
+    s->n_withheld = 0;
+    s->have_sequence = false;                           // (until the winner words and the sequence agree with them again)
+    if (!s->f_out.grow(n_letters + 1) || !s->f_qual.grow(n_letters + 1)) return no_memory("the sequence", n_letters);
+    if (total > 0 && !s->g_records.grow(total * sizeof(pa_stitch_edit))) return no_memory("the withheld records", total * sizeof(pa_stitch_edit));
+    for (size_t p = 0; p < np; ++p)
+        if (start[p] == ST_AT_END) start[p] = n_letters;
+    start[np] = n_letters;
+    for (size_t p = 0; p < np; ++p) piece_length[p] = 0;
+    for (PieceOut& piece : s->pieces) {                 // (those with kept rows; their order by (first, last) stands)
+        piece.offset = (int64_t)start[(size_t)piece.piece];
+        piece.length = (int64_t)(start[(size_t)piece.piece + 1] - start[(size_t)piece.piece]);
+        piece_length[piece.piece] = piece.length;
+    }
+    // 4. the records and the winner words, 5. the letters; left in flight: every later call is ordered behind them on the stream
+    if (total > 0) {                                    // (nothing withheld: every table and the sequence are as they were)
+        k_gate_write<<<(unsigned)blocks, ST_THREADS, 0, s->stream>>>(t, (uint32_t)min_phred, sums, total, s->g_records.as<pa_stitch_edit>(),
+                                                                    d_rec_start, s->f_slots.as<unsigned long long>());
+        ST_HIP(hipGetLastError());
+        const unsigned slot_blocks = (unsigned)((n_slots + ST_THREADS - 1) / ST_THREADS);
+        k_stitch_emit<true><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
+                                                                       s->f_slots.as<unsigned long long>(), n_slots, n_letters,
+                                                                       s->f_out.as<uint8_t>(), s->f_qual.as<uint8_t>());
+        ST_HIP(hipGetLastError());
+    }
+    s->last_scratch_bytes += (int64_t)(total * sizeof(pa_stitch_edit)) + ((int64_t)n_letters - letters_before);
+    s->sequence_length = (int64_t)n_letters;
+    s->n_withheld = (int64_t)total;
+    s->draft_held = draft_length;
+    s->have_sequence = true;
+    *sequence_length = (int64_t)n_letters;
+    counts[0] = (int64_t)total;
+    for (int k = 1; k < 4; ++k) counts[k] = (int64_t)kinds[k];
     return PA_OK;
+}
+
+int pa_stitcher_take_withheld(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity) {
+    if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (!s->gated || !s->have_sequence)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: pa_stitcher_gate has not run since the last finish");
+    if (capacity < s->n_withheld)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: there are " + std::to_string(s->n_withheld) + " records, room for " +
+                                                 std::to_string(capacity));
+    if (s->n_withheld == 0) return PA_OK;
+    ST_HIP(hipSetDevice(s->device));
+    if (s->filled && !s->withheld_filled) {             // a fill came behind the gate: the offsets count its letters, once
+        k_gate_filled_offsets<<<(unsigned)((s->n_withheld + 255) / 256), 256, 0, s->stream>>>(
+            s->g_records.as<pa_stitch_edit>(), (uint64_t)s->n_withheld, s->f_holes.as<uint32_t>(), (uint64_t)s->last_positions,
+            (uint32_t)s->pieces[0].first, (uint32_t)s->fill_lead);
+        ST_HIP(hipGetLastError());
+        s->withheld_filled = true;
+    }
+    const size_t np = (size_t)s->last_pieces;
+    return take_records(s, (const uint64_t*)(s->g_piece.as<uint8_t>() + np * 8), s->g_records.as<pa_stitch_edit>(), s->n_withheld, dst,
+                        "stitcher take withheld");
 }
 
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n) {

@@ -13,6 +13,10 @@ row, its piece and a rank that grows along that loop: the last write of a key is
 fill (opt-in, not in the reference; perform_stitch(..., fill=) is the host form): the contig is planned as ONE piece whatever
 `threads` is and pa_stitcher_fill completes the consensus on the device with the draft's letters where no row covered a position;
 the draft goes up once per contig, the edits read that copy.
+
+min_quality (opt-in, not in the reference; perform_stitch(..., min_quality=, draft=) is the host form): pa_stitcher_gate runs between
+the finish and the fill, over the winners on the device -- the edits whose phred is below it are withheld, the draft's letter
+stands -- and the withheld records come back for the .withheld.tsv; the draft the gate uploaded serves the fill and the edits.
 """
 import collections
 import contextlib
@@ -27,8 +31,8 @@ from pepper_amd import _lib, h5
 from pepper_amd.polish import Edits
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
-from pepper_amd.polish.perform_stitch import (_log, check_fill, draft_lengths, fastq_path, get_file_paths_from_directory,
-                                              natural_key, write_fastq_record, write_unpolished)
+from pepper_amd.polish.perform_stitch import (GateLog, _log, check_fill, check_gate, draft_lengths, fastq_path,
+                                              get_file_paths_from_directory, natural_key, write_fastq_record, write_unpolished)
 
 Plan = collections.namedtuple("Plan", "order piece rank n_pieces chunk_order")
 
@@ -98,6 +102,11 @@ class DeviceStitcher(object):
         self.last_filled = False             # the last finish was one with fill
         # over every finish(fill=) of this handle; the seconds: pa_stitcher_fill alone (the upload of the draft, the scan, the wait)
         self.fill_totals = {"runs": 0, "letters": 0, "seconds": 0.0}
+        self.last_gate_counts = None         # of the last finish(min_quality=): withheld edits [in all, SUB, DEL, INS]
+        self.last_gated = False              # the last finish was one with min_quality
+        self._withheld = None                # its withheld records, once withheld() took them
+        # over every finish(min_quality=) of this handle; the seconds: pa_stitcher_gate and the records' copy back
+        self.gate_totals = {"withheld": 0, "sub": 0, "del": 0, "ins": 0, "bytes_returned": 0, "seconds": 0.0}
         handle = ctypes.c_void_p()
         _lib.check(self._lib.pa_stitcher_create(self.device, ctypes.c_void_p(stream) if stream else None, ctypes.byref(handle)))
         self._handle = handle
@@ -197,7 +206,7 @@ class DeviceStitcher(object):
             if phred_ptr is None:
                 self._plain.add(contig)
 
-    def finish(self, contig, threads, region_keys=None, qualities=False, fill=None):
+    def finish(self, contig, threads, region_keys=None, qualities=False, fill=None, min_quality=None, draft=None):
         """The consensus of one contig as create_consensus_sequence(contig, region_keys, threads) returns it; region_keys
         default to the contig's regions in the order they first arrived.  KeyError(label): a surviving label that is no base.
         qualities: (sequence, quality) as create_consensus_sequence(..., qualities=True) returns them; PepperAmdError where an
@@ -205,10 +214,25 @@ class DeviceStitcher(object):
         fill (str or bytes, the whole contig of the draft as its file stores it): the FILLED consensus, as
         create_consensus_sequence(..., fill=) returns it -- one piece whatever `threads` is, the draft's letters where no row
         covered a position, their qualities '!'; pieces() is then the one piece with the filled length, and edits() gives the
-        filled consensus' records."""
+        filled consensus' records.
+        min_quality (1..255; None or 0: off) with draft (str or bytes, the whole contig of the draft; default: `fill`): the GATED
+        consensus, as create_consensus_sequence(..., min_quality=, draft=) returns it -- the edits against the draft whose winner
+        has a phred below min_quality are withheld (pa_stitcher_gate, before the fill); withheld() gives their records,
+        last_gate_counts their numbers, and edits() the applied edits.  Every add of the contig must have come with phred."""
+        min_quality = _lib.min_quality_value(min_quality)
+        if min_quality and draft is None:
+            draft = fill
+        if min_quality and draft is None:
+            raise ValueError("min_quality needs the draft: the whole contig the edits are measured against")
+        gate_draft = None if not min_quality else draft.encode() if isinstance(draft, str) else bytes(draft)
         draft = None if fill is None else fill.encode() if isinstance(fill, str) else bytes(fill)
+        if gate_draft is not None and draft is not None and gate_draft != draft:
+            raise ValueError("with min_quality the draft is the one that fills")
         with self._lock:
             self.last_filled = draft is not None
+            self.last_gated = gate_draft is not None
+            self._withheld = np.zeros(0, Edits.EDIT_DTYPE) if self.last_gated else None
+            self.last_gate_counts = [0, 0, 0, 0] if self.last_gated else None
             entry = self._contigs.get(contig)
             if entry is None:
                 self.last_pieces = []
@@ -232,11 +256,23 @@ class DeviceStitcher(object):
                                                     length.ctypes.data, ctypes.byref(total), ctypes.byref(bad)))
             if bad.value:
                 raise KeyError(int(bad.value))
+            if gate_draft is not None:
+                t0 = time.perf_counter()
+                counts = (ctypes.c_int64 * 4)()
+                _lib.check(self._lib.pa_stitcher_gate(self.handle, gate_draft, len(gate_draft), min_quality, length.ctypes.data,
+                                                      ctypes.byref(total), counts))
+                self.last_gate_counts = [int(v) for v in counts]
+                self._withheld = None                                # (on the device until withheld() asks)
+                for name, v in zip(("withheld", "sub", "del", "ins"), self.last_gate_counts):
+                    self.gate_totals[name] += v
+                self.gate_totals["seconds"] += time.perf_counter() - t0
             self.last_pieces = list(zip(first.tolist(), last.tolist(), length.tolist()))
             if draft is not None:
                 t0 = time.perf_counter()
                 counts = (ctypes.c_int64 * 2)()
-                _lib.check(self._lib.pa_stitcher_fill(self.handle, draft, len(draft), ctypes.byref(total), counts))
+                # (after a gate the draft is on the device already)
+                _lib.check(self._lib.pa_stitcher_fill(self.handle, None if gate_draft is not None else draft, len(draft),
+                                                      ctypes.byref(total), counts))
                 self.last_pieces = [(f, l, total.value) for f, l, _ in self.last_pieces if f != -1 and l != -1]
                 self.last_fill_counts = [int(v) for v in counts]
                 self.fill_totals["runs"] += self.last_fill_counts[0]
@@ -249,6 +285,32 @@ class DeviceStitcher(object):
                 return sequence
             _lib.check(self._lib.pa_stitcher_take_qualities(self.handle, buf, total.value))
             return sequence, buf.raw[:total.value].decode()
+
+    def withheld(self):
+        """After finish(min_quality=): the edits the gate kept back, as Edits.EDIT_DTYPE records in the order and with the bytes
+        of Stitch.gate_numpy (through create_consensus_sequence); after finish(fill=, min_quality=) their offsets count the
+        filled consensus."""
+        with self._lock:
+            if not self.last_gated:
+                raise _lib.PepperAmdError("the last finish had no min_quality")
+            if self._withheld is None:
+                t0 = time.perf_counter()
+                records = np.zeros(self.last_gate_counts[0], Edits.EDIT_DTYPE)
+                _lib.check(self._lib.pa_stitcher_take_withheld(self.handle, records.ctypes.data, len(records)))
+                self._withheld = records
+                self.gate_totals["bytes_returned"] += records.nbytes
+                self.gate_totals["seconds"] += time.perf_counter() - t0
+            return self._withheld
+
+    def applied_counts(self, draft_length):
+        """After finish(min_quality=): the applied edits [SUB, DEL, INS], counted on the device against the draft the gate left
+        there; no record comes back."""
+        with self._lock:
+            if not self.last_pieces or all(p[0] == -1 for p in self.last_pieces):
+                return [0, 0, 0]
+            n, counts = ctypes.c_int64(), (ctypes.c_int64 * 6)()
+            _lib.check(self._lib.pa_stitcher_edits(self.handle, None, draft_length, ctypes.byref(n), counts))
+            return [int(v) for v in counts[1:4]]
 
     def has_qualities(self, contig):
         """Every add of the contig came with phred."""
@@ -270,7 +332,7 @@ class DeviceStitcher(object):
                 return np.zeros(0, Edits.EDIT_DTYPE)
             t0 = time.perf_counter()
             n, counts = ctypes.c_int64(), (ctypes.c_int64 * 6)()
-            held = self.last_filled                                  # pa_stitcher_fill ran: its copy of the draft is read
+            held = self.last_filled or (self.last_gated and bool(self.last_pieces))      # a fill or a gate left its copy of the draft
             _lib.check(self._lib.pa_stitcher_edits(self.handle, None if held else draft, len(draft), ctypes.byref(n), counts))
             records = np.zeros(n.value, Edits.EDIT_DTYPE)
             _lib.check(self._lib.pa_stitcher_take_edits(self.handle, records.ctypes.data, n.value))
@@ -280,15 +342,36 @@ class DeviceStitcher(object):
             self.edit_totals["seconds_compare"] += time.perf_counter() - t0
         return records
 
-    def _write_edits(self, edits_file, draft, lengths, contig, stored=None):
-        """One contig's lines of the .edits.tsv, after its finish (stored: the draft the finish was filled with)."""
+    def _write_edits(self, edits_file, draft, lengths, contig, stored=None, filled=None, withheld=None):
+        """One contig's lines of the .edits.tsv, after its finish (stored: the draft the finish was filled or gated with; filled:
+        it was filled, default: whenever stored is given; withheld: Edits.write_edits')."""
         if contig not in lengths:
             raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
         records = self.edits(stored if stored is not None else draft.get_reference_bytes(contig, 0, lengths[contig]))
         t0 = time.perf_counter()
         Edits.write_contig(edits_file, contig, records, self.pieces(), lengths[contig], self.has_qualities(contig),
-                           filled=stored is not None)
+                           filled=stored is not None if filled is None else filled, withheld=withheld)
         self.edit_totals["seconds_text"] += time.perf_counter() - t0
+
+    def _finish_and_write(self, contig, threads, keys, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill, min_quality,
+                          gate):
+        """One held contig of a writer: its finish (filled, gated) and its records in every file that is open."""
+        stored = _stored_draft(draft, lengths, contig) if fill is not None or min_quality else None
+        result = self.finish(contig, threads, keys, qualities=qualities, fill=stored if fill is not None else None,
+                             min_quality=min_quality, draft=stored if min_quality else None)
+        sequence, quality = result if qualities else (result, None)
+        withheld = self.withheld() if min_quality else None
+        if edits is not None:
+            self._write_edits(edits_file, draft, lengths, contig, stored, filled=fill is not None,
+                              withheld=None if withheld is None else len(withheld))
+        if min_quality:
+            gate.contig(contig, withheld, self.last_edit_counts[1:4] if edits is not None else self.applied_counts(lengths[contig]))
+        _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
+        if len(sequence) > 0:
+            fasta.write('>' + contig + "\n")
+            fasta.write(sequence + "\n")
+            if qualities:
+                write_fastq_record(fastq, contig, sequence, quality)
 
     def stats(self):
         """{'rows', 'slab_bytes'} held, and of the last finish {'slots', 'pieces', 'positions', 'table_bytes'}"""
@@ -296,44 +379,38 @@ class DeviceStitcher(object):
         _lib.check(self._lib.pa_stitcher_stats(self.handle, out, 6))
         return dict(zip(("rows", "slab_bytes", "slots", "pieces", "positions", "table_bytes"), (int(v) for v in out)))
 
-    def write_fasta(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False):
+    def write_fasta(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None):
         """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file).  edits: the
         draft FASTA's path; <output_prefix>_pepper_polished.edits.tsv beside it (perform_stitch(..., edits=)'s file).
         fill / unpolished_contigs: perform_stitch's -- the draft FASTA's path, every contig filled; and the draft's other
-        contigs written among them."""
-        return self._write(output_prefix, threads, False, edits, fill, unpolished_contigs)
+        contigs written among them.  min_quality / draft: perform_stitch's -- the gate and the draft FASTA's path; also writes
+        <output_prefix>_pepper_polished.withheld.tsv."""
+        return self._write(output_prefix, threads, False, edits, fill, unpolished_contigs, min_quality, draft)
 
-    def write_fastq(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False):
+    def write_fastq(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None):
         """write_fasta's file, and beside it <output_prefix>_pepper_polished.fastq with the same records and their qualities
         (perform_stitch(..., qualities=True)'s two files), from one finish per contig.  -> the FASTQ's path."""
-        return self._write(output_prefix, threads, True, edits, fill, unpolished_contigs)
+        return self._write(output_prefix, threads, True, edits, fill, unpolished_contigs, min_quality, draft)
 
-    def _write(self, output_prefix, threads, qualities, edits, fill=None, unpolished_contigs=False):
+    def _write(self, output_prefix, threads, qualities, edits, fill=None, unpolished_contigs=False, min_quality=None, gate_draft=None):
         check_fill(edits, fill, unpolished_contigs)
+        min_quality = check_gate(min_quality, gate_draft, edits, fill)
         output_path = output_prefix + '_pepper_polished.fa'
         Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
         with contextlib.ExitStack() as files:
             fasta = files.enter_context(open(output_path, 'w'))
             fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
-            draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill)
+            draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill, gate_draft if min_quality else None)
+            gate = GateLog(files, output_prefix) if min_quality else None
             held = set(self.contigs())
             for contig in sorted(held | set(lengths if unpolished_contigs else ()), key=natural_key):
                 if contig not in held:
-                    write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file)
+                    write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file, gated=gate is not None)
                     continue
-                stored = _stored_draft(draft, lengths, contig) if fill is not None else None
-                if qualities:
-                    sequence, quality = self.finish(contig, threads, qualities=True, fill=stored)
-                else:
-                    sequence = self.finish(contig, threads, fill=stored)
-                if edits is not None:
-                    self._write_edits(edits_file, draft, lengths, contig, stored)
-                _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
-                if len(sequence) > 0:
-                    fasta.write('>' + contig + "\n")
-                    fasta.write(sequence + "\n")
-                    if qualities:
-                        write_fastq_record(fastq, contig, sequence, quality)
+                self._finish_and_write(contig, threads, None, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill,
+                                       min_quality, gate)
+            if gate is not None:
+                gate.log(min_quality)
         return fastq_path(output_prefix) if qualities else output_path
 
     def close(self):
@@ -354,10 +431,11 @@ class DeviceStitcher(object):
             pass
 
 
-def _open_draft(files, output_prefix, edits, fill):
-    """What a writer needs of the draft FASTA (the one that fills, else the one the edits are taken against): (handler, {contig:
-    length}, the open .edits.tsv with its header or None); (None, {}, None) without either."""
-    path = fill if fill is not None else edits
+def _open_draft(files, output_prefix, edits, fill, gate_draft=None):
+    """What a writer needs of the draft FASTA (the one that fills, else the one the edits are taken against, else the one the
+    gate measures against): (handler, {contig: length}, the open .edits.tsv with its header or None); (None, {}, None) without
+    any."""
+    path = fill if fill is not None else edits if edits is not None else gate_draft
     if path is None:
         return None, {}, None
     from pepper_amd.variant.fasta import FASTA_handler
@@ -424,12 +502,15 @@ class _Held(object):
 
 
 def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False, edits=None, fill=None,
-                     unpolished_contigs=False):
+                     unpolished_contigs=False, min_quality=None, draft=None):
     """perform_stitch(hdf_file_path, output_path, threads, qualities, edits, fill, unpolished_contigs) with the merge on the
     device: the same files read, the same FASTA (and FASTQ, and .edits.tsv) written.  stats: a dict that receives the handle's
-    stats() after the last contig (with fill: and `fill`, the handle's fill_totals)."""
+    stats() after the last contig (with fill: and `fill`, the handle's fill_totals; with min_quality: and `gate`, its gate_totals).
+    min_quality / draft: perform_stitch's gate, on the device; the same .withheld.tsv."""
     check_fill(edits, fill, unpolished_contigs)
-    read_phred = qualities or edits is not None         # the edit records carry the winners' phred
+    min_quality = check_gate(min_quality, draft, edits, fill)
+    gate_draft = draft
+    read_phred = qualities or edits is not None or bool(min_quality)      # the edit records and the gate read the winners' phred
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -443,10 +524,11 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
         stitcher = files.enter_context(DeviceStitcher(device))
         fasta = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
-        draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill)
+        draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill, gate_draft if min_quality else None)
+        gate = GateLog(files, output_prefix) if min_quality else None
         for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
             if contig not in all_contigs:
-                write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file)
+                write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file, gated=gate is not None)
                 continue
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -465,21 +547,14 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                             held.take(key, at, *block)
                             at += len(block[0])
             held.flush()
-            stored = _stored_draft(draft, lengths, contig) if fill is not None else None
-            if qualities:
-                sequence, quality = stitcher.finish(contig, threads, all_chunk_keys, qualities=True, fill=stored)
-            else:
-                sequence = stitcher.finish(contig, threads, all_chunk_keys, fill=stored)
-            if edits is not None:
-                stitcher._write_edits(edits_file, draft, lengths, contig, stored)
-            _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
-            if len(sequence) > 0:
-                fasta.write('>' + contig + "\n")
-                fasta.write(sequence + "\n")
-                if qualities:
-                    write_fastq_record(fastq, contig, sequence, quality)
+            stitcher._finish_and_write(contig, threads, all_chunk_keys, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill,
+                                       min_quality, gate)
+        if gate is not None:
+            gate.log(min_quality)
         if stats is not None:
             stats.update(stitcher.stats())
             if fill is not None:
                 stats["fill"] = dict(stitcher.fill_totals)
+            if min_quality:
+                stats["gate"] = dict(stitcher.gate_totals)
     return output_path

@@ -26,6 +26,12 @@ counts letters of the FILLED consensus (the draft letters in front of the piece 
 offset is the first filled letter of its run.  The one piece is (first, last, filled length).  filled_hunks(), write_contig(...,
 filled=True) and apply_filled() read such records: a run is a `filled` hunk with equal draft and polished intervals, and so are
 [0, first) and (last, draft_length); `uncovered` and `duplicated` cannot occur.
+
+GATE (opt-in: polish(..., min_quality=Q) / PEPPER_AMD_POLISH_MIN_QUALITY=Q): the SUB / DEL / INS edits whose winner has a phred
+below Q are withheld before anything here reads the merge (Stitch.gate_numpy, pa_stitcher_gate), so the records are exactly the
+applied edits.  The withheld ones come as records of the same layout -- letter the model's, offset the place of the kept draft
+letter (SUB, DEL) or the letters in front of the slot (INS) -- which write_withheld() prints, one line each, into
+<prefix>_pepper_polished.withheld.tsv; the summary line of the .edits.tsv then ends with withheld=<n>.
 """
 import numpy as np
 
@@ -43,6 +49,29 @@ _UPPER = bytes(c - 32 if 97 <= c <= 122 else c for c in range(256))
 
 def edits_path(output_prefix):
     return output_prefix + '_pepper_polished.edits.tsv'
+
+
+WITHHELD_HEADER = "#contig\tdraft_position\tinsert_index\tkind\tdraft\tmodel\tphred\tpolished_offset\n"
+_WITHHELD_KINDS = {SUB: "sub", DEL: "del", INS: "ins"}
+
+
+def withheld_path(output_prefix):
+    return output_prefix + '_pepper_polished.withheld.tsv'
+
+
+def write_withheld(file, contig, records):
+    """One line per edit the min_quality gate kept back (Stitch.gate_numpy / pa_stitcher_gate), in the records' order: contig,
+    draft position (0-based), insert index, kind, the draft's letter ('-' for ins), the model's letter ('-' for del), the winner's
+    phred, and the offset in the polished contig -- of the kept draft letter for sub and del, of the letter behind the slot for ins."""
+    records = np.asarray(records, dtype=EDIT_DTYPE)
+    file.writelines("%s\t%d\t%d\t%s\t%s\t%s\t%d\t%d\n" % (contig, p, i, _WITHHELD_KINDS[k], chr(d) if d else "-", chr(c) if c else "-", q, o)
+                    for p, o, i, _, k, d, c, q in records.tolist())
+
+
+def kind_counts(records):
+    """[SUB, DEL, INS] records."""
+    kind = np.asarray(records, dtype=EDIT_DTYPE)["kind"]
+    return [int((kind == k).sum()) for k in (SUB, DEL, INS)]
 
 
 def upper_bytes(draft):
@@ -244,26 +273,28 @@ def summary(hunk_list, total=None, filled=False):
     return total
 
 
-def write_edits(file, contig, hunk_list, draft_length, polished_length, blocks=False, filled=False):
+def write_edits(file, contig, hunk_list, draft_length, polished_length, blocks=False, filled=False, withheld=None):
     """One line per hunk, then the contig's summary line (blocks: hunk_list is an iterable of lists of hunks; filled: the
-    summary line ends with filled=<bases>)."""
+    summary line ends with filled=<bases>; withheld: the run has a min_quality gate, and the line ends with withheld=<edits the
+    gate kept back>)."""
     total = None
     for block in (hunk_list if blocks else [hunk_list]):
         file.writelines(contig + "\t%d\t%d\t%d\t%d\t%s\t%s\t%s\t%s\n" % hunk for hunk in block)
         total = summary(block, total, filled)
     file.write("##contig=" + contig + "\tdraft_length=" + str(draft_length) + "\tpolished_length=" + str(polished_length) +
-               "".join("\t%s=%d" % kv for kv in (total or summary([], None, filled)).items()) + "\n")
+               "".join("\t%s=%d" % kv for kv in (total or summary([], None, filled)).items()) +
+               ("" if withheld is None else "\twithheld=%d" % withheld) + "\n")
 
 
-def write_contig(file, contig, records, pieces, draft_length, has_qualities, filled=False):
+def write_contig(file, contig, records, pieces, draft_length, has_qualities, filled=False, withheld=None):
     """hunks() + write_edits(), piece by piece: what both stitch forms call per contig (pieces: [(first, last, length)]).
-    filled: filled_hunks() instead; a contig without a piece is the whole draft."""
+    filled: filled_hunks() instead; a contig without a piece is the whole draft.  withheld: write_edits'."""
     if filled:
         write_edits(file, contig, _filled_blocks(records, pieces, draft_length, has_qualities), draft_length,
-                    pieces[0][2] if pieces else draft_length, blocks=True, filled=True)
+                    pieces[0][2] if pieces else draft_length, blocks=True, filled=True, withheld=withheld)
         return
     write_edits(file, contig, _hunk_blocks(records, pieces, draft_length, has_qualities), draft_length, sum(p[2] for p in pieces),
-                blocks=True)
+                blocks=True, withheld=withheld)
 
 
 def apply(draft_sequence, records, pieces):

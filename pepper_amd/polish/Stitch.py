@@ -34,15 +34,18 @@ def chunks(file_names, threads):
     return [file_names[i:i + threads] for i in range(0, len(file_names), threads)]
 
 
-def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None, fill=None):
+def small_chunk_stitch(contig, small_chunk_keys, qualities=False, edits=None, fill=None, min_quality=None, draft=None):
     """One piece of the consensus.  The merge runs inside the I/O library (pa_h5_stitch_polish_regions: chunk rows straight
     from the mapped prediction files, each chunk merged into the tail of the piece; 3 k -> see DESIGN.md chunks/s);
     PEPPER_AMD_STITCH_NUMPY=1 keeps the numpy form below, which tests hold it to.  qualities: (first, last, sequence, quality),
     always through the numpy form (the library's merge carries no phred).  edits: the draft FASTA's path; the piece's edit
     records (piece 0, offsets from the piece's first letter) follow as one more element, through the numpy form as well.
-    fill: the draft FASTA's path; the keys are the whole contig's and the piece comes out filled (numpy form)."""
-    if qualities or edits is not None or fill is not None:
-        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=qualities, edits=edits, fill=fill)
+    fill: the draft FASTA's path; the keys are the whole contig's and the piece comes out filled (numpy form).
+    min_quality / draft: the gate (gate_numpy) over the piece's winners, against the draft FASTA `draft`; the withheld records
+    follow as the last element (numpy form)."""
+    if qualities or edits is not None or fill is not None or min_quality:
+        return small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=qualities, edits=edits, fill=fill, min_quality=min_quality,
+                                        draft=draft)
     if os.environ.get("PEPPER_AMD_STITCH_NUMPY") == "1":
         return small_chunk_stitch_numpy(contig, small_chunk_keys)
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
@@ -104,15 +107,119 @@ def whole_draft(fill, contig):
     return sequence, "!" * len(sequence)
 
 
-def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=None, fill=None):
+_CODE = np.zeros(256, dtype=np.int64)
+_CODE[np.frombuffer(b"ACGT", dtype=np.uint8)] = (1, 2, 3, 4)
+
+
+def with_empty_slots(positions, indices, labels, phred):
+    """The merge's winners -- sorted by (position, index), one entry per key -- with the slots (p, 0) that have no writer beside
+    insert slots put in as label 0, phred 0: the tables the gate works on.  (Such a slot is a DEL; the consensus and the edit
+    records are the same with it or without.)"""
+    positions, indices = np.asarray(positions, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    labels, phred = np.asarray(labels, dtype=np.int64), np.asarray(phred, dtype=np.int64)
+    first = np.ones(positions.size, dtype=bool)
+    first[1:] = positions[1:] != positions[:-1]
+    hole = np.flatnonzero(first & (indices > 0))
+    if hole.size == 0:
+        return positions, indices, labels, phred
+    return (np.insert(positions, hole, positions[hole]), np.insert(indices, hole, 0), np.insert(labels, hole, 0),
+            np.insert(phred, hole, 0))
+
+
+def gate_numpy(positions, indices, labels, phred, draft, min_quality, draft_start=0, filled=False):
+    """min_quality polish, the host twin of pa_stitcher_gate: apply only the edits the model is sure of.  positions / indices /
+    labels / phred: the winners of ONE piece's merge with its empty slots (with_empty_slots); draft: the draft's letters from
+    draft_start on (any case); min_quality 1..255.  -> (labels, phred, withheld records).
+
+        slot (p, 0), d = upper(draft[p]) in ACGT, the winner is a base other than d (SUB) or a gap / no writer (DEL), and its
+        phred < min_quality: WITHHELD -- the slot gets d's label and phred 0
+        slot (p, i > 0), the winner is a base (INS), phred < min_quality: WITHHELD -- the slot gets the gap's label and phred 0
+        every other slot is untouched: phred >= min_quality, a winner equal to d, a gap in an insert slot, and every slot (p, 0)
+        whose draft letter is outside ACGT (there is no letter to keep: the model's decision stands)
+
+    The records (Edits.EDIT_DTYPE, piece 0) are ordered as the keys are: kind SUB / DEL / INS, letter the model's (0 for DEL),
+    draft d (0 for INS), phred the winner's, offset the place of the kept draft letter (SUB, DEL) or the letters in front of the
+    slot (INS) in the gated piece; filled: in the filled consensus, as Edits.records_numpy(..., filled=True) counts."""
+    from pepper_amd.polish import Edits
+    positions, indices = np.asarray(positions, dtype=np.int64), np.asarray(indices, dtype=np.int64)
+    labels, phred = np.asarray(labels, dtype=np.int64), np.asarray(phred, dtype=np.int64)
+    if positions.size == 0:
+        return labels, phred, np.zeros(0, Edits.EDIT_DTYPE)
+    d = Edits.upper_bytes(draft)[positions - draft_start]
+    code = _CODE[d]
+    letters = _DECODE[labels]
+    is_letter, at0, low = letters != 0, indices == 0, phred < min_quality
+    sub = at0 & is_letter & (letters != d) & (code != 0) & low
+    dele = at0 & ~is_letter & (code != 0) & low
+    ins = ~at0 & is_letter & low
+    held = sub | dele | ins
+    gated = np.where(sub | dele, code, np.where(ins, 0, labels))
+    emits = gated != 0
+    before = np.cumsum(emits) - emits                                # gated letters in front of every key
+    if filled:
+        first = np.ones(positions.size, dtype=bool)
+        first[1:] = positions[1:] != positions[:-1]
+        before = before + positions - (np.cumsum(first) - 1)
+    out = np.zeros(int(held.sum()), Edits.EDIT_DTYPE)
+    out["position"], out["offset"], out["index"] = positions[held], before[held], indices[held]
+    out["kind"] = np.where(sub, Edits.SUB, np.where(dele, Edits.DEL, Edits.INS))[held]
+    out["draft"], out["letter"], out["phred"] = np.where(ins, 0, d)[held], letters[held], phred[held]
+    return gated, np.where(held, 0, phred), out
+
+
+def _contig_of(draft_fasta, contig, last):
+    """The whole contig of the draft as the file stores it (uint8); it must reach position `last`."""
+    from pepper_amd.variant.fasta import FASTA_handler
+    draft = FASTA_handler(draft_fasta)
+    try:
+        length = draft.get_chromosome_sequence_length(contig)
+        if length < 0:
+            raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
+        if length <= last:
+            raise ValueError("the draft FASTA %s has no letter at position %d of %s" % (draft_fasta, last, contig))
+        return np.frombuffer(draft.get_reference_bytes(contig, 0, length, stored_case=True), dtype=np.uint8)
+    finally:
+        draft.close()
+
+
+def _gated_piece(contig, positions, indices, labels, phred, want_qualities, edits, fill, min_quality, draft):
+    """small_chunk_stitch_numpy's result for a piece whose winners (sorted keys, labels 0..4, raw phred) go through the gate:
+    (first, last, sequence[, quality][, edit records], withheld records).  The whole contig of the draft is read once and serves
+    the gate, the fill and the edits."""
+    from pepper_amd.polish import Edits
+    stored = _contig_of(draft, contig, int(positions[-1]))
+    filled = fill is not None
+    positions, indices, labels, phred = with_empty_slots(positions, indices, labels, np.minimum(phred, 255))
+    labels, phred, withheld = gate_numpy(positions, indices, labels, phred, stored, min_quality, filled=filled)
+    letters = _DECODE[labels]
+    quality = (33 + np.minimum(phred[letters != 0], MAX_QUALITY)).astype(np.uint8)
+    if filled:
+        text, quality = filled_piece(stored, int(positions[0]), positions, letters, quality)
+    else:
+        text = letters[letters != 0]
+    result = (int(positions[0]), int(positions[-1]), text.tobytes().decode())
+    if want_qualities:
+        result += (quality.tobytes().decode(),)
+    if edits is not None:
+        result += (Edits.records_numpy(positions, indices, labels, phred, stored, filled=filled),)
+    return result + (withheld,)
+
+
+def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=None, fill=None, min_quality=None, draft=None):
     if fill is not None and edits is not None and str(edits) != str(fill):
         raise ValueError("with fill the edits are taken against the draft that fills: %s is not %s" % (edits, fill))
+    if min_quality:
+        if draft is None or any(other is not None and str(other) != str(draft) for other in (edits, fill)):
+            raise ValueError("min_quality needs the draft FASTA, the one that fills and the edits are taken against")
     want_qualities = qualities
-    qualities = qualities or edits is not None          # the edit records carry the winners' phred
+    qualities = qualities or edits is not None or bool(min_quality)      # the edit records and the gate read the winners' phred
     buffer_positions = ImageSizeOptions.MIN_IMAGE_OVERLAP * 2
     nothing = (-1, -1, '', '') if want_qualities else (-1, -1, '')
-    if edits is not None:
+    if edits is not None or min_quality:
         from pepper_amd.polish import Edits
+    if edits is not None:
+        nothing += (np.zeros(0, Edits.EDIT_DTYPE),)
+    if min_quality:                       # (the withheld records: one more element, the last)
         nothing += (np.zeros(0, Edits.EDIT_DTYPE),)
     names = ('position', 'index', 'bases', 'phred_score') if qualities else ('position', 'index', 'bases')
     pos_parts, idx_parts, base_parts, phred_parts = [], [], [], []
@@ -168,6 +275,9 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=No
     labels = bases[last]
     if labels.size and (labels.min() < 0 or labels.max() > 4):
         raise KeyError(int(labels[(labels < 0) | (labels > 4)][0]))      # label_decoder[...] in the reference
+    if min_quality:                       # the gate works on the winners; everything below reads what it leaves
+        return _gated_piece(contig, positions[last], indices[last], labels, np.concatenate(phred_parts)[order][last], want_qualities,
+                            edits, fill, min_quality, draft)
     letters = _DECODE[labels]
     sequence = letters[letters != 0].tobytes().decode()
     result = (int(positions[0]), int(positions[-1]), sequence)
@@ -207,12 +317,60 @@ def small_chunk_stitch_numpy(contig, small_chunk_keys, qualities=False, edits=No
     return result
 
 
-def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False, edits=None, fill=None):
+def _gated_consensus(contig, sequence_chunk_keys, threads, qualities, edits, fill, min_quality, draft):
+    """create_consensus_sequence(..., min_quality=, draft=): the same plan -- one piece with fill, else pieces of consecutive regions
+    -- every piece through the numpy merge and the gate."""
+    from pepper_amd.polish import Edits
+    key_list = sorted(((file_name, contig, int(contig_start), int(contig_end))
+                       for file_name, _, contig_start, contig_end in sorted(sequence_chunk_keys, key=lambda e: e[1])),
+                      key=lambda e: (e[2], e[3]))
+    extra = (bool(qualities), edits, fill, min_quality, draft)
+    if fill is not None:
+        file_chunks = [key_list]
+    else:
+        file_chunks = chunks(key_list, max(MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING, int(len(key_list) / max(1, threads)) + 1))
+    if threads <= 1 or len(file_chunks) <= 1:
+        results = [small_chunk_stitch(contig, chunk, *extra) for chunk in file_chunks]
+    else:
+        with concurrent.futures.ProcessPoolExecutor(max_workers=threads) as executor:
+            results = [f.result() for f in [executor.submit(small_chunk_stitch, contig, chunk, *extra) for chunk in file_chunks]]
+    pieces = sorted((r for r in results if r[0] != -1 and r[1] != -1), key=lambda e: (e[0], e[1]))
+    empty = np.zeros(0, Edits.EDIT_DTYPE)
+    if fill is not None and not pieces:                               # no kept row: the draft as it is
+        sequence, quality = whole_draft(fill, contig)
+        records, withheld, bounds = empty, empty, []
+    else:
+        sequence = ''.join(piece[2] for piece in pieces)
+        quality = ''.join(piece[3] for piece in pieces) if qualities else None
+        records, withheld, at = [empty], [empty], 0
+        for k, piece in enumerate(pieces):
+            withheld.append(Edits.place(piece[-1], k, at))
+            if edits is not None:
+                records.append(Edits.place(piece[-2], k, at))
+            at += len(piece[2])
+        records, withheld = np.concatenate(records), np.concatenate(withheld)
+        bounds = [(piece[0], piece[1], len(piece[2])) for piece in pieces]
+    if edits is not None:
+        return sequence, quality if qualities else None, records, bounds, withheld
+    if qualities:
+        return sequence, quality, withheld
+    return sequence, withheld
+
+
+def create_consensus_sequence(contig, sequence_chunk_keys, threads, qualities=False, edits=None, fill=None, min_quality=None,
+                              draft=None):
     """The consensus of one contig; qualities: (sequence, quality), the pieces' qualities concatenated as their letters are.
     edits (the draft FASTA's path): (sequence, quality or None, records, pieces) -- the contig's edit records and its pieces
     [(first, last, length)], both in the order of the consensus (pepper_amd/polish/Edits.py).
     fill (the draft FASTA's path): the same forms for the FILLED consensus -- every region of the contig in one piece, in the
-    order they are iterated here, and the draft's letters where no key is; `threads` does not shape it."""
+    order they are iterated here, and the draft's letters where no key is; `threads` does not shape it.
+    min_quality (1..255; None or 0: off) with draft (the draft FASTA's path): every piece's winners go through gate_numpy first, and
+    the contig's withheld records (piece and offset as the edit records have them) follow the form asked for as one more element
+    -- a bare sequence becomes (sequence, withheld)."""
+    from pepper_amd import _lib
+    min_quality = _lib.min_quality_value(min_quality)
+    if min_quality:
+        return _gated_consensus(contig, sequence_chunk_keys, threads, qualities, edits, fill, min_quality, draft)
     extra = (bool(qualities), edits) if edits is not None else (True,) if qualities else ()
     key_list = sorted(((file_name, contig, int(contig_start), int(contig_end))
                        for file_name, _, contig_start, contig_end in sorted(sequence_chunk_keys, key=lambda e: e[1])),

@@ -10,6 +10,9 @@ changed against the draft, hunk by hunk in both coordinate systems (pepper_amd/p
 fill=<draft FASTA> (opt-in, not in the reference): every contig is merged as one piece and the draft's own letters stand where no
 prediction covered a position, so the consensus is complete and does not depend on `threads`; unpolished_contigs=True also
 writes the contigs of the draft that have no prediction, unchanged, in natural order among the rest.
+min_quality=Q with draft=<draft FASTA> (opt-in, not in the reference): only the edits whose winning prediction has phred >= Q are
+applied, the draft's letter stands elsewhere (pepper_amd/polish/Stitch.py gate_numpy); also writes
+`<output_path>_pepper_polished.withheld.tsv`, the edits kept back.
 """
 import contextlib
 import re
@@ -66,14 +69,48 @@ def check_fill(edits, fill, unpolished_contigs):
         raise ValueError("with fill the edits are taken against the draft that fills: %s is not %s" % (edits, fill))
 
 
-def write_unpolished(contig, fill, draft_length, fasta, fastq, edits_file):
+def check_gate(min_quality, draft, edits, fill):
+    """What every stitch form asks of its gate arguments -> min_quality as an integer 1..255, or None (off)."""
+    from pepper_amd import _lib
+    min_quality = _lib.min_quality_value(min_quality)
+    if min_quality is None:
+        return None
+    if draft is None:
+        raise ValueError("min_quality needs draft: the draft FASTA the edits are measured against")
+    for other, what in ((edits, "the edits are taken against"), (fill, "fills")):
+        if other is not None and str(other) != str(draft):
+            raise ValueError("with min_quality the draft is the one that %s: %s is not %s" % (what, other, draft))
+    return min_quality
+
+
+class GateLog(object):
+    """The withheld.tsv of a gated run and its one INFO line: the applied and the withheld edits by kind, over every contig."""
+
+    def __init__(self, files, output_prefix):
+        from pepper_amd.polish import Edits
+        self.file = files.enter_context(open(Edits.withheld_path(output_prefix), 'w'))
+        self.file.write(Edits.WITHHELD_HEADER)
+        self.applied, self.withheld = [0, 0, 0], [0, 0, 0]
+
+    def contig(self, contig, withheld, applied_counts):
+        from pepper_amd.polish import Edits
+        Edits.write_withheld(self.file, contig, withheld)
+        self.applied = [a + b for a, b in zip(self.applied, applied_counts)]
+        self.withheld = [a + b for a, b in zip(self.withheld, Edits.kind_counts(withheld))]
+
+    def log(self, min_quality):
+        _log("MIN QUALITY %d: APPLIED sub=%d del=%d ins=%d, WITHHELD sub=%d del=%d ins=%d." %
+             ((min_quality,) + tuple(self.applied) + tuple(self.withheld)))
+
+
+def write_unpolished(contig, fill, draft_length, fasta, fastq, edits_file, gated=False):
     """A contig of the draft without a prediction, as the filled consensus of nothing: its letters as stored, qualities '!',
-    one `filled` hunk."""
+    one `filled` hunk (gated: the run has a min_quality gate; the summary line says withheld=0)."""
     sequence, quality = whole_draft(fill, contig)
     _log("NO PREDICTION FOR " + contig + ", DRAFT SEQUENCE LENGTH: " + str(len(sequence)) + ".")
     if edits_file is not None:
         from pepper_amd.polish import Edits
-        Edits.write_contig(edits_file, contig, [], [], draft_length, True, filled=True)
+        Edits.write_contig(edits_file, contig, [], [], draft_length, True, filled=True, withheld=0 if gated else None)
     if len(sequence) > 0:
         fasta.write('>' + contig + "\n")
         fasta.write(sequence + "\n")
@@ -81,8 +118,10 @@ def write_unpolished(contig, fill, draft_length, fasta, fastq, edits_file):
             write_fastq_record(fastq, contig, sequence, quality)
 
 
-def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None, fill=None, unpolished_contigs=False):
+def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None, fill=None, unpolished_contigs=False,
+                   min_quality=None, draft=None):
     check_fill(edits, fill, unpolished_contigs)
+    min_quality = check_gate(min_quality, draft, edits, fill)
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -97,14 +136,17 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
         consensus_fasta_file = files.enter_context(open(output_path, 'w'))
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
         edits_file = None
-        if edits is not None:
+        if edits is not None or min_quality:
             from pepper_amd.polish import Edits
+        if edits is not None:
             edits_file = files.enter_context(open(Edits.edits_path(output_prefix), 'w'))
             edits_file.write(Edits.HEADER)
-        lengths = draft_lengths(fill if fill is not None else edits) if edits is not None or fill is not None else {}
+        gate = GateLog(files, output_prefix) if min_quality else None
+        draft_path = draft if min_quality else fill if fill is not None else edits
+        lengths = draft_lengths(draft_path) if draft_path is not None else {}
         for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
             if contig not in all_contigs:
-                write_unpolished(contig, fill, lengths[contig], consensus_fasta_file, fastq, edits_file)
+                write_unpolished(contig, fill, lengths[contig], consensus_fasta_file, fastq, edits_file, gated=gate is not None)
                 continue
             _log("PROCESSING CONTIG: " + contig)
             all_chunk_keys = []
@@ -114,9 +156,16 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
                         continue
                     # every region group with its contig_start / contig_end in one library call (names in sorted order)
                     all_chunk_keys.extend((prediction_file, name, start, end) for name, start, end in hdf5_file.list_polish_regions(contig))
-            if (edits is not None or fill is not None) and contig not in lengths:
+            if draft_path is not None and contig not in lengths:
                 raise KeyError("CONTIG NOT PRESENT IN THE DRAFT FASTA: " + contig)
-            if edits is not None:
+            if gate is not None:              # (the records are always made: their kinds are the applied edits the run logs)
+                consensus_sequence, quality, records, pieces, withheld = create_consensus_sequence(
+                    contig, all_chunk_keys, threads, qualities=qualities, edits=draft, fill=fill, min_quality=min_quality, draft=draft)
+                gate.contig(contig, withheld, Edits.kind_counts(records))
+                if edits is not None:
+                    Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None,
+                                       withheld=len(withheld))
+            elif edits is not None:
                 consensus_sequence, quality, records, pieces = create_consensus_sequence(contig, all_chunk_keys, threads,
                                                                                          qualities=qualities, edits=edits, fill=fill)
                 Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None)
@@ -130,4 +179,6 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
                 consensus_fasta_file.write(consensus_sequence + "\n")
                 if qualities:
                     write_fastq_record(fastq, contig, consensus_sequence, quality)
+        if gate is not None:
+            gate.log(min_quality)
     return output_path

@@ -19,7 +19,7 @@ def _log(message):
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
            num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0, device_stitch=None,
-           keep_predictions=None, qualities=None, edits=None, fill=None):
+           keep_predictions=None, qualities=None, edits=None, fill=None, min_quality=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
@@ -38,7 +38,13 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     do not depend on `threads`, the letters of fasta_filepath (as stored, quality '!') where no prediction covered a position, and
     without a region the contigs no prediction names, unchanged (perform_stitch(..., fill=, unpolished_contigs=); not in the
     reference).  In the device forms the filling runs on the device (stage_walls["device_stitch_fill"] in the fused form: the runs
-    and letters filled, the seconds)."""
+    and letters filled, the seconds).
+    min_quality (default: PEPPER_AMD_POLISH_MIN_QUALITY; an integer 1..255, 0 or None: off): step 3 applies only the edits against
+    fasta_filepath whose winning prediction has phred >= min_quality -- a substitution or deletion below it keeps the draft's
+    letter (upper-cased, quality '!'), an insertion below it is left out; positions whose draft letter is not ACGT are the model's
+    (pepper_amd/polish/Stitch.py gate_numpy; not in the reference) -- and writes <output>_pepper_polished.withheld.tsv, the edits it
+    kept back.  In the device forms the gate runs on the device (stage_walls["device_stitch_gate"] in the fused form: the edits
+    withheld by kind, the bytes that came back, the seconds)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     if qualities is None:
@@ -50,6 +56,9 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     if fill is None:
         fill = _lib.polish_fill()
     fill_kw = dict(fill=fasta_filepath, unpolished_contigs=region is None) if fill else {}
+    min_quality = _lib.min_quality_value(_lib.polish_min_quality() if min_quality is None else min_quality)
+    if min_quality:
+        fill_kw.update(min_quality=min_quality, draft=fasta_filepath)
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
         if not os.path.isfile(path):
             raise FileNotFoundError("CAN NOT LOCATE " + what + " FILE: " + str(path))
@@ -80,7 +89,7 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         _log("STEP 1+2: GENERATING IMAGES AND RUNNING INFERENCE (FUSED) -> " + prediction_output_directory)
         sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant, device_stitch=device_stitch,
                               keep_predictions=bool(keep_predictions) or not device_stitch,
-                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities or bool(edits))
+                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities or bool(edits) or bool(min_quality))
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
                         stats=image_stats, downsample_rate=downsample_rate)
@@ -113,6 +122,10 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
             from pepper_amd.polish import Edits
             with open(Edits.edits_path(output_dir), 'w') as edits_file:
                 edits_file.write(Edits.HEADER)
+        if min_quality:                      # (nothing to gate: the header alone, as perform_stitch over no files writes it)
+            from pepper_amd.polish import Edits
+            with open(Edits.withheld_path(output_dir), 'w') as withheld_file:
+                withheld_file.write(Edits.WITHHELD_HEADER)
     else:
         try:
             if qualities:
@@ -125,6 +138,8 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
                     stage_walls["device_stitch_edits"] = dict(stitcher.edit_totals)
                 if fill:
                     stage_walls["device_stitch_fill"] = dict(stitcher.fill_totals)
+                if min_quality:
+                    stage_walls["device_stitch_gate"] = dict(stitcher.gate_totals)
         finally:
             stitcher.close()
     if stage_walls is not None:

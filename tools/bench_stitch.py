@@ -10,7 +10,13 @@ with --device, stitch_directory(..., edits=draft) -- and checks the two .edits.t
 the filling is one trailing run) -- perform_stitch(..., fill=draft) on the host and, with --device, stitch_directory(..., fill=draft),
 checked against the host's FASTA -- and then, on one handle that holds the job's rows, times finish + take without fill beside
 finish + fill + take (one warm-up and three timed calls each; pa_stitcher_fill's own seconds beside them).
-    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits] [--fill]"""
+--min-quality Q runs the set with the gate on as well, against the same draft (random labels: four slots in five are an edit, and
+with phred uniform in 0..100 a share Q / 101 of them is withheld) -- perform_stitch(..., min_quality=Q, draft=draft) on the host
+and, with --device, stitch_directory(..., min_quality=Q, draft=draft), FASTA and .withheld.tsv checked against the host's -- and
+then, on one handle that holds the job's rows with their phred, times finish + take beside finish + gate + take (+ the withheld
+records' copy back), one warm-up and three timed calls each.
+    python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits] [--fill]
+                                 [--min-quality Q]"""
 import argparse
 import json
 import os
@@ -73,6 +79,56 @@ def device_fill_legs(pred, tmp, draft_fa, regions):
     return runs
 
 
+def device_gate_legs(pred, tmp, draft_fa, regions, q):
+    """stitch_directory with the gate against the host's files, then finish + take beside finish + gate + take on one handle."""
+    import statistics
+
+    from pepper_amd import h5
+    from pepper_amd.polish.DeviceStitch import DeviceStitcher, _Held, _read_region, stitch_directory
+    from pepper_amd.polish.perform_stitch import get_file_paths_from_directory
+    runs = []
+    for threads in (1, 8):
+        host = [open(os.path.join(tmp, "outg%d" % threads) + suffix, "rb").read() for suffix in ("_pepper_polished.fa", "_pepper_polished.withheld.tsv")]
+        for repeat in range(2):
+            stats = {}
+            t0 = time.perf_counter()
+            out = stitch_directory(pred, os.path.join(tmp, "devg%d%d" % (threads, repeat)), threads, stats=stats, min_quality=q, draft=draft_fa)
+            dt = time.perf_counter() - t0
+            runs.append({"merge": "device", "min_quality": q, "threads": threads, "repeat": repeat, "seconds": round(dt, 2),
+                         "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                         "equals_host": open(out, "rb").read() == host[0],
+                         "withheld_tsv_equals_host": open(out[:-len(".fa")] + ".withheld.tsv", "rb").read() == host[1], "stats": stats})
+    draft = open(draft_fa, "rb").read().split(b"\n")[1]
+    with DeviceStitcher(0) as st:
+        keys, held = [], _Held(st, "ctg0")
+        for prediction_file in get_file_paths_from_directory(pred):
+            with h5.File(prediction_file, 'r') as f:
+                for name, start, end in f.list_polish_regions("ctg0"):
+                    key, at = (prediction_file, name, start, end), 0
+                    keys.append(key)
+                    for block in _read_region(f, 'predictions/ctg0/ctg0-%d-%d' % (start, end), True):
+                        held.take(key, at, *block)
+                        at += len(block[0])
+        held.flush()
+        legs = {}
+        for leg, kw in (("finish_take", {}), ("finish_gate_take", {"min_quality": q, "draft": draft}),
+                        ("finish_gate_take_withheld", {"min_quality": q, "draft": draft})):
+            seconds = []
+            for repeat in range(4):                          # (the first call grows the handle's tables)
+                before = st.gate_totals["seconds"]
+                t0 = time.perf_counter()
+                sequence = st.finish("ctg0", 8, keys, **kw)
+                if leg.endswith("withheld"):
+                    st.withheld()
+                seconds.append((time.perf_counter() - t0, st.gate_totals["seconds"] - before))
+            legs[leg] = {"seconds": [round(s[0], 4) for s in seconds[1:]], "median": round(statistics.median(s[0] for s in seconds[1:]), 4),
+                         "gate_call_seconds": [round(s[1], 4) for s in seconds[1:]], "letters": len(sequence), "stats": st.stats()}
+        legs["ratio"] = round(legs["finish_gate_take"]["median"] / legs["finish_take"]["median"], 3)
+        legs["gate_counts"] = st.last_gate_counts
+        runs.append({"merge": "device", "min_quality": "one handle", **legs})
+    return runs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=65536)
@@ -82,6 +138,7 @@ def main():
     ap.add_argument("--qualities", action="store_true", help="also run the set with qualities on (FASTQ beside the FASTA)")
     ap.add_argument("--edits", action="store_true", help="also run the set with the edits on (.edits.tsv beside the FASTA)")
     ap.add_argument("--fill", action="store_true", help="also run the set with fill on (the draft where no row covered it)")
+    ap.add_argument("--min-quality", type=int, default=0, help="also run the set with the gate on (only the edits with phred >= Q)")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
@@ -124,7 +181,7 @@ def main():
                 runs.append({"merge": "numpy", "qualities": True, "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                              "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
-        if args.edits or args.fill:
+        if args.edits or args.fill or args.min_quality:
             os.environ["PEPPER_AMD_STITCH_NUMPY"] = "0"
             draft_fa = os.path.join(tmp, "draft.fa")
             with open(draft_fa, "w") as fh:                 # as long as the positions reach
@@ -146,6 +203,14 @@ def main():
                 dt = time.perf_counter() - t0
                 runs.append({"merge": "numpy", "fill": True, "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out)})
+        if args.min_quality:
+            for threads in (1, 8):
+                t0 = time.perf_counter()
+                out = perform_stitch(pred, os.path.join(tmp, "outg%d" % threads), threads, min_quality=args.min_quality, draft=draft_fa)
+                dt = time.perf_counter() - t0
+                runs.append({"merge": "numpy", "min_quality": args.min_quality, "threads": threads, "seconds": round(dt, 2),
+                             "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
+                             "withheld_tsv_bytes": os.path.getsize(out[:-len(".fa")] + ".withheld.tsv")})
         if args.device:
             from pepper_amd.polish.DeviceStitch import stitch_directory
             host = {threads: open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read() for threads in (1, 8)}
@@ -184,6 +249,8 @@ def main():
                                  "edits_tsv_bytes": len(tsv), "stats": stats})
             if args.fill:
                 runs.extend(device_fill_legs(pred, tmp, draft_fa, regions))
+            if args.min_quality:
+                runs.extend(device_gate_legs(pred, tmp, draft_fa, regions, args.min_quality))
         from pepper_amd.hostinfo import usable_cpus
         print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
