@@ -424,7 +424,8 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity);
 /* out[0] rows held, [1] bytes of slabs, and of the last finish: [2] slots, [3] pieces, [4] positions spanned, [5] bytes of
  * its tables (the quality buffer among them when the finish produced qualities, the edit records once pa_stitcher_edits ran,
  * once pa_stitcher_fill ran its table of 4 bytes per position, the filled sequence and the filled qualities, and once
- * pa_stitcher_gate ran its withheld records). */
+ * pa_stitcher_gate ran its withheld records, and once pa_stitcher_variants ran its tables -- 4 bytes per edit record, 69 per
+ * hunk -- and its records). */
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n);
 
 /* What the last finish changed against the draft (opt-in, not in the reference; pepper_amd/polish/Edits.py is the host twin and
@@ -500,6 +501,51 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
 int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, int32_t min_phred, int64_t* piece_length,
                      int64_t* sequence_length, int64_t* counts /* [4] */);
 int pa_stitcher_take_withheld(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity);
+
+/* What the FILLED consensus changed against the draft as normalised variant records, one per hunk (opt-in, not in the reference;
+ * pepper_amd/polish/Variants.py states the rule, records_numpy there is the host twin and lines() writes the VCF text).  Runs
+ * after pa_stitcher_fill (and after pa_stitcher_gate where there is one); draft = NULL reads the copy the fill uploaded.  Where the
+ * edit records of the filled consensus are not there yet the call makes them as pa_stitcher_edits does (they can be taken).
+ *
+ * THE RULE.  The units are runs of SUB / DEL / INS edit records: a record joins its predecessor when its draft interval and its
+ * consensus interval begin where the predecessor's end (SUB [p, p+1) [o, o+1); DEL [p, p+1) [o, o); INS [p+1, p+1) [o, o+1)); GAP
+ * records join nothing and give nothing.  Hunk i: the draft interval [a0, b0), the letters ALT0 = consensus[o0, o1), q = the
+ * minimum phred of its records.  With d = the draft upper-cased:
+ *   1. Trim: while both alleles are non-empty and end in the same letter drop it from both, then the same for the first letter:
+ *      (a, b, alt).  Both empty: a no-op, no record, counted.  Both non-empty: REF = d[a, b), ALT = alt, at position a.
+ *   2. A pure indel (one allele empty) moves left while a - 2 >= bound and d[a-1] == d[b-1] (deletion) or d[a-1] == alt[-1]
+ *      (insertion, which rotates: alt = d[a-1] + alt[:-1]); then REF = d[a-1, b), ALT = d[a-1] + alt, at position a - 1.
+ *      bound = the UNTRIMMED b0 of the hunk in front, 0 for the first.
+ *   3. link_0: hunk 0 is a pure indel with a == 0; link_j: hunk j is a pure indel with a_j == b_(j-1) + 1 (both trimmed).  F = the
+ *      first j whose link is false.  Hunks i < F are anchored on the right and not moved: REF = d[a, b+1), ALT = alt + d[b], at
+ *      position a; one with b == draft_length has no letter on either side: no record, counted as unanchored.  Hunk F > 0 takes
+ *      bound = b_(F-1) + 1.
+ * A record carries no letters:  REF = draft[position, position + ref_len);  ALT = draft[position, position + lead), then
+ * consensus[offset, offset + alt_len - lead - tail), then for tail = 1 draft[position + ref_len - 1].  A moved insertion of n letters
+ * has lead = 1 + min(shift, n), a deletion lead 1, a right-anchored record lead 0 and tail 1, every other record lead 0 and tail 0.
+ * Records in hunk order (ascending position, REF intervals disjoint).  Two runs over the same input leave the same bytes. */
+enum { PA_VARIANT_SUB = 1, PA_VARIANT_INS = 2, PA_VARIANT_DEL = 3, PA_VARIANT_COMPLEX = 4 };
+typedef struct pa_stitch_variant {
+    uint32_t position;   /* of the draft, 0-based: where REF begins */
+    uint32_t ref_len;
+    uint32_t alt_len;
+    uint32_t lead;       /* letters of ALT that are the draft's, from `position` on */
+    uint32_t offset;     /* of the filled consensus: where the hunk's trimmed letters begin */
+    uint32_t shift;      /* places a pure indel moved left */
+    uint8_t phred;       /* the minimum over the hunk's edit records; 0 for a contig without qualities */
+    uint8_t kind;        /* PA_VARIANT_*, of the trimmed hunk */
+    uint8_t tail;        /* 1: anchored on the right, ALT ends in draft[position + ref_len - 1] */
+    uint8_t pad;         /* 0 */
+    uint32_t reserved;   /* 0 */
+} pa_stitch_variant;     /* 32 bytes */
+/* *n_variants records; counts: records, no-ops, unanchored, hunks moved, places moved in all.  One wait for the hunks, one for the
+ * records; the records stay on the device until pa_stitcher_take_variants, in buffers counted in pa_stitcher_stats [5] from then on.
+ * A later finish, gate or fill invalidates them.
+ * PA_ERR_INVALID before any launch, the handle stays usable: no finish yet; the last finish gave no sequence; no pa_stitcher_fill
+ * since the finish; draft_length is not the fill's; draft is NULL and the fill's copy is gone (a pa_stitcher_edits with a draft of
+ * its own replaced it); take_variants without a run since the last finish, or with short capacity. */
+int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_variants, int64_t* counts /* [5] */);
+int pa_stitcher_take_variants(pa_stitcher* s, pa_stitch_variant* dst, int64_t capacity);
 
 /* ------------------------------------------------------------------------------------------
  * The candidate finder's selection ON THE DEVICE (opt-in: call_variant(..., fused_inference=True, device_selection=True);

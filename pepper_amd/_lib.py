@@ -151,6 +151,8 @@ SYMBOLS = [
     ("pa_stitcher_fill", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
     ("pa_stitcher_gate", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, ctypes.POINTER(c_int64), c_void_p]),
     ("pa_stitcher_take_withheld", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
+    ("pa_stitcher_variants", ctypes.c_int, [c_void_p, c_void_p, c_int64, ctypes.POINTER(c_int64), c_void_p]),
+    ("pa_stitcher_take_variants", ctypes.c_int, [c_void_p, c_void_p, c_int64]),
     ("pa_selector_create", ctypes.c_int, [c_int32, c_void_p, ctypes.POINTER(c_void_p)]),
     ("pa_selector_destroy", None, [c_void_p]),
     ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
@@ -346,6 +348,16 @@ def polish_fill():
     where no prediction covered a position, and without a region the contigs no read landed on.  Unset or any other value: the
     reference's stitch, which leaves such sequence out."""
     return os.environ.get(POLISH_FILL_ENV, "0") == "1"
+
+
+POLISH_VCF_ENV = "PEPPER_AMD_POLISH_VCF"
+
+
+def polish_vcf():
+    """PEPPER_AMD_POLISH_VCF=1: polish() writes <prefix>_pepper_polished.vcf.gz and its .tbi beside the FASTA: what the filled
+    consensus changed against the draft, trimmed and left-aligned (pepper_amd/polish/Variants.py); needs fill.  Unset or any other
+    value: no VCF."""
+    return os.environ.get(POLISH_VCF_ENV, "0") == "1"
 
 
 POLISH_MIN_QUALITY_ENV = "PEPPER_AMD_POLISH_MIN_QUALITY"

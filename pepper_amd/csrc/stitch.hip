@@ -41,6 +41,14 @@
 // decides from the winner word and the draft, rewrites letters[] and counts; the letters are scanned again; the second pass
 // decides once more (the words still hold the model's labels), places the records (count, scan, write) and rewrites the words, so
 // emit, fill and edits read consistent tables without knowing about the gate.  A lane touches only its own slot.
+//
+// Variants (pa_stitcher_variants, pa_stitcher_take_variants; opt-in, not in the reference): the edit records of the FILLED consensus
+// grouped into hunks, trimmed and left-aligned against the draft (the rule: the header, at the call).  Runs behind fill on what is
+// resident: the draft, the filled consensus, the sorted records.  Hunk heads are decided inside a scan's load from a record and the
+// one in front of it; a lane per record writes the hunks' ranges, a lane per hunk trims, a WAVE per hunk left-aligns -- one
+// comparison per lane and a ballot for the first mismatch, 64 places per step, where a lane per hunk would walk a satellite
+// repeat alone -- and a scan of "the hunk gives a record" compacts in hunk order.  A hunk reads its neighbour's trimmed and untrimmed
+// ends, never its result; integer minima and sums only.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -580,6 +588,188 @@ __global__ void k_gate_shift(const uint16_t* __restrict__ order, uint32_t n_take
     }
 }
 
+// ---------------------------------------------------------------- variants: the hunks of the filled consensus, normalised ----
+// (the rule: include/pepper_amd_encoder.h at pa_stitcher_variants; pepper_amd/polish/Variants.py records_numpy is the twin)
+struct VarTables {
+    const pa_stitch_edit* records;                      // of the filled consensus: one piece, keys in order
+    const uint8_t* draft;                               // the whole contig as stored (compared upper-cased)
+    const uint8_t* cons;                                // the filled consensus
+    uint64_t n_records, draft_length, cons_length;
+};
+
+struct HunkWork {                                       // one hunk between the passes
+    uint32_t first, last;                               // its records
+    uint32_t q;                                         // the minimum of their phred
+    uint32_t a, b, s, t;                                // trimmed: draft [a, b), consensus [s, t)
+    uint32_t b0;                                        // the untrimmed end of its draft interval
+};
+
+PA_DEV uint8_t upper_letter(uint8_t c) { return c >= 'a' && c <= 'z' ? (uint8_t)(c - 32) : c; }
+PA_DEV bool is_edit(const pa_stitch_edit& r) { return r.kind >= PA_EDIT_SUB && r.kind <= PA_EDIT_INS; }
+PA_DEV uint32_t edit_d0(const pa_stitch_edit& r) { return r.position + (r.kind == PA_EDIT_INS); }
+PA_DEV uint32_t edit_o1(const pa_stitch_edit& r) { return r.offset + (r.kind == PA_EDIT_SUB || r.kind == PA_EDIT_INS); }
+// record i begins a hunk: an edit that does not continue the record in front of it in both coordinate systems
+PA_DEV bool hunk_head(const pa_stitch_edit* __restrict__ rec, uint64_t i) {
+    const pa_stitch_edit r = rec[i];
+    if (!is_edit(r)) return false;
+    if (i == 0) return true;
+    const pa_stitch_edit q = rec[i - 1];
+    return !(is_edit(q) && edit_d0(r) == q.position + 1 && r.offset == edit_o1(q));
+}
+struct LoadHead {
+    const pa_stitch_edit* rec;
+    PA_DEV uint64_t operator()(uint64_t i) const { return hunk_head(rec, i); }
+};
+
+// One lane per record.  before[i] = hunk heads in front of record i (the scan), so an edit lies in hunk before[i] + head - 1;
+// the head and the last record of a hunk write its range, every record lowers its phred (an integer minimum: order-free).
+__global__ __launch_bounds__(ST_THREADS) void k_var_ranges(const pa_stitch_edit* __restrict__ rec, uint64_t n,
+                                                           const uint32_t* __restrict__ before, HunkWork* __restrict__ hunks,
+                                                           uint64_t n_hunks) {
+    const uint64_t i = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const pa_stitch_edit r = rec[i];
+    if (!is_edit(r)) return;
+    const bool head = hunk_head(rec, i);
+    const uint64_t h = (uint64_t)before[i] + (head ? 1 : 0) - 1;      // (the first edit is a head: never before[i] = 0 without one)
+    if (h >= n_hunks) return;
+    if (head) hunks[h].first = (uint32_t)i;
+    if (i + 1 == n || !is_edit(rec[i + 1]) || hunk_head(rec, i + 1)) hunks[h].last = (uint32_t)i;
+    atomicMin(&hunks[h].q, (uint32_t)r.phred);
+}
+
+// One lane per hunk: step 1 of the rule.  The loops are as long as the letters a complex hunk shares with the draft at its ends
+// (a hunk is a handful of records; the long walk, the left-alignment, has a wave per hunk below).
+__global__ __launch_bounds__(ST_THREADS) void k_var_trim(VarTables t, HunkWork* __restrict__ hunks, uint64_t n_hunks) {
+    const uint64_t h = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (h >= n_hunks) return;
+    HunkWork w = hunks[h];
+    if (w.first >= t.n_records || w.last >= t.n_records) return;
+    const pa_stitch_edit f = t.records[w.first], l = t.records[w.last];
+    uint32_t a = edit_d0(f), b = l.position + 1, s = f.offset, e = edit_o1(l);
+    w.b0 = b;
+    while (b > a && e > s && b <= t.draft_length && e <= t.cons_length && upper_letter(t.draft[b - 1]) == t.cons[e - 1]) {
+        --b;
+        --e;
+    }
+    while (b > a && e > s && a < t.draft_length && s < t.cons_length && upper_letter(t.draft[a]) == t.cons[s]) {
+        ++a;
+        ++s;
+    }
+    w.a = a;
+    w.b = b;
+    w.s = s;
+    w.t = e;
+    hunks[h] = w;
+}
+
+PA_DEV bool pure_indel(const HunkWork& w) { return (w.b == w.a) != (w.t == w.s); }
+
+// One lane per hunk: step 3's F, the first hunk that is not linked to the contig's start (an integer minimum: order-free)
+__global__ __launch_bounds__(ST_THREADS) void k_var_link(const HunkWork* __restrict__ hunks, uint64_t n_hunks, uint32_t* __restrict__ first_unlinked) {
+    const uint64_t h = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (h >= n_hunks) return;
+    const HunkWork w = hunks[h];
+    const bool link = pure_indel(w) && w.a == (h == 0 ? 0u : hunks[h - 1].b + 1u);
+    if (!link) atomicMin(first_unlinked, (uint32_t)h);
+}
+
+// One WAVE per hunk: steps 2 and 3.  A pure indel of n letters moves left while V[x] == V[x + n] for x = a - 1, a - 2, ... down
+// to bound + 1, V the draft (deletion) or draft[0, a) + alt (insertion): lane l compares place k + l + 1, a ballot finds the
+// first mismatch, 64 places per step; consecutive lanes read consecutive bytes.  Lane 0 writes the record of hunk h to tmp[h]
+// and whether it is one to emit[h]; the counts go through the workgroup's LDS, one atomic per workgroup and count (integer sums).
+__global__ __launch_bounds__(ST_THREADS) void k_var_align(VarTables t, const HunkWork* __restrict__ hunks, uint64_t n_hunks,
+                                                          const uint32_t* __restrict__ first_unlinked, uint32_t qualities,
+                                                          pa_stitch_variant* __restrict__ tmp, uint8_t* __restrict__ emit,
+                                                          unsigned long long* __restrict__ counts) {
+    __shared__ unsigned long long s_count[4];           // no-ops, unanchored, moved, places moved
+    if (threadIdx.x < 4) s_count[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t lane = threadIdx.x & 63;
+    const uint64_t h = (uint64_t)blockIdx.x * (ST_THREADS / 64) + (threadIdx.x >> 6);
+    if (h < n_hunks) {                                   // (uniform for the wave)
+        const HunkWork w = hunks[h];
+        const uint64_t F = *first_unlinked;
+        const uint32_t rn = w.b - w.a, an = w.t - w.s;
+        uint32_t position = w.a, ref_len = rn, alt_len = an, lead = 0, k = 0, kind = rn == an ? PA_VARIANT_SUB : PA_VARIANT_COMPLEX;
+        bool keep = true, tail = false, noop = false, unanchored = false;
+        if (rn == 0 && an == 0) {
+            keep = false;
+            noop = true;
+        } else if (rn == 0 || an == 0) {
+            const bool del = rn > 0;
+            kind = del ? PA_VARIANT_DEL : PA_VARIANT_INS;
+            ref_len = rn + 1;
+            alt_len = an + 1;
+            if (h < F) {                                 // anchored on the right
+                tail = true;
+                if (w.b >= t.draft_length) {
+                    keep = false;
+                    unanchored = true;
+                }
+            } else {
+                const uint32_t bound = h == 0 ? 0u : h == F ? hunks[h - 1].b + 1u : hunks[h - 1].b0;
+                const uint32_t n = del ? rn : an;
+                const uint32_t room = w.a > bound ? w.a - 1u - bound : 0u;      // places it may move at most (a - 1 >= bound by the rule)
+                while (k < room) {
+                    const uint32_t j = k + lane + 1;
+                    bool same = false;
+                    if (j <= room) {
+                        const uint64_t x = w.a - j, y = x + n;
+                        if (!del && y >= w.a) {
+                            const uint64_t c = (uint64_t)w.s + (y - w.a);
+                            same = x < t.draft_length && c < t.cons_length && upper_letter(t.draft[x]) == t.cons[c];
+                        } else {
+                            same = y < t.draft_length && upper_letter(t.draft[x]) == upper_letter(t.draft[y]);
+                        }
+                    }
+                    const unsigned long long miss = __ballot(!same);
+                    if (miss) {
+                        k += (uint32_t)__ffsll((long long)miss) - 1u;
+                        break;
+                    }
+                    k += 64;
+                }
+                position = w.a - k - 1u;
+                lead = del ? 1u : 1u + min(k, an);
+            }
+        }
+        if (lane == 0) {
+            pa_stitch_variant v;
+            v.position = position;
+            v.ref_len = ref_len;
+            v.alt_len = alt_len;
+            v.lead = lead;
+            v.offset = w.s;
+            v.shift = k;
+            v.phred = qualities ? (uint8_t)min(w.q, 255u) : (uint8_t)0;
+            v.kind = (uint8_t)kind;
+            v.tail = tail ? 1 : 0;
+            v.pad = 0;
+            v.reserved = 0;
+            tmp[h] = v;
+            emit[h] = keep ? 1 : 0;
+            if (noop) atomicAdd(&s_count[0], 1ull);
+            if (unanchored) atomicAdd(&s_count[1], 1ull);
+            if (k) {
+                atomicAdd(&s_count[2], 1ull);
+                atomicAdd(&s_count[3], (unsigned long long)k);
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 4 && s_count[threadIdx.x]) atomicAdd(&counts[1 + threadIdx.x], s_count[threadIdx.x]);
+}
+
+// the records that are ones, in hunk order: place[h] = records in front of hunk h (the scan of emit)
+__global__ __launch_bounds__(ST_THREADS) void k_var_compact(const pa_stitch_variant* __restrict__ tmp, const uint8_t* __restrict__ emit,
+                                                            const uint32_t* __restrict__ place, uint64_t n_hunks, uint64_t n_out,
+                                                            pa_stitch_variant* __restrict__ out) {
+    const uint64_t h = (uint64_t)blockIdx.x * ST_THREADS + threadIdx.x;
+    if (h >= n_hunks || !emit[h]) return;
+    if (place[h] < n_out) out[place[h]] = tmp[h];
+}
+
 struct Buffer {
     void* p = nullptr;
     size_t cap = 0;
@@ -644,7 +834,13 @@ struct pa_stitcher {
     bool gated = false;                                 // pa_stitcher_gate ran on the last finish: every later call speaks of the gated tables
     bool withheld_filled = false;                       // ... and the records' offsets already count the fill that followed
     int64_t n_withheld = 0;
-    std::vector<PieceOut> pieces;                       // of the last finish, in output order
+    // variants' tables: hunk heads in front of every edit record, the hunks, their records before and after the compaction, the
+    // flags and places of the compaction, scan scratch, the counts
+    Buffer v_before, v_hunks, v_tmp, v_emit, v_place, v_out, v_scan, v_words;
+    bool have_variants = false;                         // pa_stitcher_variants ran on the last fill
+    int64_t n_variants = 0, variant_bytes = 0;          // variant_bytes: its share of last_scratch_bytes
+    int64_t fill_draft_length = -1;                     // the draft_length of the last fill
+    std::vector<PieceOut> pieces;                      // of the last finish, in output order
     int64_t sequence_length = 0;
     bool finished = false;                              // a finish has run: the three below speak of it
     bool contig_qualities = false;                      // every chunk of its contig came with qualities
@@ -671,7 +867,8 @@ int no_memory(const char* what, uint64_t bytes) {
 std::vector<Buffer*> buffers_of(pa_stitcher* s) {
     return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
             &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words,
-            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq, &s->g_piece, &s->g_records};
+            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq, &s->g_piece, &s->g_records,
+            &s->v_before, &s->v_hunks, &s->v_tmp, &s->v_emit, &s->v_place, &s->v_out, &s->v_scan, &s->v_words};
 }
 
 // Records the write passes left piece after piece in TABLE order (start[p]: where those of table piece p begin, on the device)
@@ -865,6 +1062,9 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     s->draft_held = -1;
     s->gated = s->withheld_filled = false;
     s->n_withheld = 0;
+    s->have_variants = false;
+    s->n_variants = s->variant_bytes = 0;
+    s->fill_draft_length = -1;
     s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
@@ -1086,9 +1286,8 @@ int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
     return PA_OK;
 }
 
-int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
-    if (!s || !n_edits || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher edits: null or negative argument");
-    std::lock_guard<std::mutex> guard(s->lock);
+// pa_stitcher_edits under the handle's lock (pa_stitcher_variants makes the records it lacks through it)
+static int edits_locked(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
     *n_edits = 0;
     for (int k = 0; k < 6; ++k) counts[k] = 0;
     const bool held = !draft && (s->filled || s->gated) && s->draft_held == draft_length;      // the draft a fill or a gate uploaded
@@ -1190,6 +1389,12 @@ int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, i
     return PA_OK;
 }
 
+int pa_stitcher_edits(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
+    if (!s || !n_edits || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher edits: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    return edits_locked(s, draft, draft_length, n_edits, counts);
+}
+
 int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* filled_length, int64_t* counts) {
     if (!s || !filled_length || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher fill: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
@@ -1216,6 +1421,10 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
     if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
     s->have_edits = s->filled = false;
     s->n_edits = s->fill_bytes = s->filled_length = s->fill_lead = 0;
+    s->last_scratch_bytes -= s->variant_bytes;          // (and the variants of the consensus as it was)
+    s->have_variants = false;
+    s->n_variants = s->variant_bytes = 0;
+    s->fill_draft_length = -1;
     if (!held) s->draft_held = -1;
     ST_HIP(hipSetDevice(s->device));
     const uint64_t n_positions = rows ? (uint64_t)s->last_positions : 0, n_slots = (uint64_t)s->last_slots;
@@ -1265,6 +1474,7 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
     s->filled_length = (int64_t)total;
     s->fill_lead = (int64_t)lead;
     s->draft_held = draft_length;
+    s->fill_draft_length = draft_length;
     *filled_length = (int64_t)total;
     counts[0] = (int64_t)(runs + (lead > 0) + (trail > 0));
     counts[1] = (int64_t)(lead + holes + trail);
@@ -1458,6 +1668,130 @@ int pa_stitcher_take_withheld(pa_stitcher* s, pa_stitch_edit* dst, int64_t capac
     const size_t np = (size_t)s->last_pieces;
     return take_records(s, (const uint64_t*)(s->g_piece.as<uint8_t>() + np * 8), s->g_records.as<pa_stitch_edit>(), s->n_withheld, dst,
                         "stitcher take withheld");
+}
+
+int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_variants, int64_t* counts) {
+    if (!s || !n_variants || !counts || draft_length < 0) return pa::set_error(PA_ERR_INVALID, "stitcher variants: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    *n_variants = 0;
+    for (int k = 0; k < 5; ++k) counts[k] = 0;
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher variants: no contig has been finished");
+    if (!s->have_sequence)
+        return pa::set_error(PA_ERR_INVALID, "stitcher variants: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (!s->filled)
+        return pa::set_error(PA_ERR_INVALID, "stitcher variants: pa_stitcher_fill has not run since the last finish (the records describe "
+                                             "the one complete consensus of the contig)");
+    if (draft_length != s->fill_draft_length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher variants: the draft has " + std::to_string(draft_length) + " letters, the fill's had " +
+                                                 std::to_string(s->fill_draft_length));
+    if (!draft && draft_length > 0 && s->draft_held != draft_length)
+        return pa::set_error(PA_ERR_INVALID, "stitcher variants: null draft, and the copy the fill uploaded is gone (a pa_stitcher_edits "
+                                             "with a draft of its own replaced it)");
+    ST_HIP(hipSetDevice(s->device));
+    s->last_scratch_bytes -= s->variant_bytes;          // asked again: counted once
+    s->have_variants = false;
+    s->n_variants = s->variant_bytes = 0;
+    if (draft && draft_length > 0) {
+        if (!s->e_draft.grow((size_t)draft_length + 1)) return no_memory("the draft", (uint64_t)draft_length);
+        ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
+        ST_HIP(hipStreamSynchronize(s->stream));        // the caller's draft is free again
+        s->draft_held = draft_length;
+    }
+    if (!s->have_edits) {                               // the one comparison there is: the records of the filled consensus
+        int64_t n_edits = 0, kinds[6];
+        const int rc = edits_locked(s, nullptr, draft_length, &n_edits, kinds);
+        if (rc != PA_OK) return rc;
+    }
+    const uint64_t n = (uint64_t)s->n_edits;
+    if (n == 0) {
+        s->have_variants = true;
+        return PA_OK;
+    }
+    VarTables t;
+    t.records = s->e_records.as<pa_stitch_edit>();
+    t.draft = s->e_draft.as<uint8_t>();
+    t.cons = s->f_fill.as<uint8_t>();
+    t.n_records = n;
+    t.draft_length = (uint64_t)draft_length;
+    t.cons_length = (uint64_t)s->filled_length;
+    // 1. the hunks: heads by the joining rule, scanned
+    if (!s->v_before.grow(n * 4) || !s->v_scan.grow(std::max(scan_scratch_words(n), (uint64_t)1) * 8) || !s->v_words.grow(64))
+        return no_memory("the hunk heads", n * 4);
+    const uint64_t* d_heads = scan_exclusive<LoadHead, uint32_t>(s->stream, LoadHead{t.records}, n, s->v_before.as<uint32_t>(),
+                                                                 s->v_scan.as<uint64_t>());
+    ST_HIP(hipGetLastError());
+    uint64_t n_hunks = 0;
+    ST_HIP(hipMemcpyAsync(&n_hunks, d_heads, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));            // the first wait: the size of the hunk tables
+    int64_t bytes = (int64_t)(n * 4);
+    if (n_hunks == 0) {                                  // GAP records alone
+        s->variant_bytes = bytes;
+        s->last_scratch_bytes += bytes;
+        s->have_variants = true;
+        return PA_OK;
+    }
+    if (n_hunks > 0xFFFFFFFEull) return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher variants: more than 2^32 - 2 hunks");
+    if (!s->v_hunks.grow(n_hunks * sizeof(HunkWork)) || !s->v_tmp.grow(n_hunks * sizeof(pa_stitch_variant)) || !s->v_emit.grow(n_hunks) ||
+        !s->v_place.grow(n_hunks * 4) || !s->v_scan.grow(std::max(scan_scratch_words(std::max(n, n_hunks)), (uint64_t)1) * 8))
+        return no_memory("the hunk tables", n_hunks * (sizeof(HunkWork) + sizeof(pa_stitch_variant) + 5));
+    bytes += (int64_t)(n_hunks * (sizeof(HunkWork) + sizeof(pa_stitch_variant) + 5));
+    HunkWork* hunks = s->v_hunks.as<HunkWork>();
+    unsigned long long* d_counts = s->v_words.as<unsigned long long>();      // [5] counts, then F
+    uint32_t* d_first_unlinked = (uint32_t*)(d_counts + 5);
+    const uint32_t all_linked = (uint32_t)n_hunks;
+    ST_HIP(hipMemsetAsync(hunks, 0xFF, n_hunks * sizeof(HunkWork), s->stream));
+    ST_HIP(hipMemsetAsync(d_counts, 0, 5 * 8, s->stream));
+    ST_HIP(hipMemcpyAsync(d_first_unlinked, &all_linked, 4, hipMemcpyHostToDevice, s->stream));
+    const unsigned record_blocks = (unsigned)((n + ST_THREADS - 1) / ST_THREADS), hunk_blocks = (unsigned)((n_hunks + ST_THREADS - 1) / ST_THREADS);
+    const unsigned wave_blocks = (unsigned)((n_hunks + ST_THREADS / 64 - 1) / (ST_THREADS / 64));
+    k_var_ranges<<<record_blocks, ST_THREADS, 0, s->stream>>>(t.records, n, s->v_before.as<uint32_t>(), hunks, n_hunks);
+    ST_HIP(hipGetLastError());
+    // 2. trim, the contig's start, left-alignment
+    k_var_trim<<<hunk_blocks, ST_THREADS, 0, s->stream>>>(t, hunks, n_hunks);
+    ST_HIP(hipGetLastError());
+    k_var_link<<<hunk_blocks, ST_THREADS, 0, s->stream>>>(hunks, n_hunks, d_first_unlinked);
+    ST_HIP(hipGetLastError());
+    k_var_align<<<wave_blocks, ST_THREADS, 0, s->stream>>>(t, hunks, n_hunks, d_first_unlinked, s->contig_qualities ? 1u : 0u,
+                                                           s->v_tmp.as<pa_stitch_variant>(), s->v_emit.as<uint8_t>(), d_counts);
+    ST_HIP(hipGetLastError());
+    // 3. compaction in hunk order
+    const uint64_t* d_kept = scan_exclusive<LoadLetter, uint32_t>(s->stream, LoadLetter{s->v_emit.as<uint8_t>()}, n_hunks,
+                                                                 s->v_place.as<uint32_t>(), s->v_scan.as<uint64_t>());
+    ST_HIP(hipGetLastError());
+    uint64_t kept = 0, host_counts[5] = {0, 0, 0, 0, 0};
+    ST_HIP(hipMemcpyAsync(&kept, d_kept, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(host_counts, d_counts, 5 * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));            // the second wait: the size of the record buffer
+    if (kept > 0) {
+        if (!s->v_out.grow(kept * sizeof(pa_stitch_variant))) return no_memory("the variant records", kept * sizeof(pa_stitch_variant));
+        // left in flight: take_variants, a later finish and destroy are ordered behind it on the handle's stream
+        k_var_compact<<<hunk_blocks, ST_THREADS, 0, s->stream>>>(s->v_tmp.as<pa_stitch_variant>(), s->v_emit.as<uint8_t>(),
+                                                                 s->v_place.as<uint32_t>(), n_hunks, kept, s->v_out.as<pa_stitch_variant>());
+        ST_HIP(hipGetLastError());
+    }
+    bytes += (int64_t)(kept * sizeof(pa_stitch_variant));
+    s->variant_bytes = bytes;
+    s->last_scratch_bytes += bytes;
+    s->n_variants = (int64_t)kept;
+    s->have_variants = true;
+    *n_variants = (int64_t)kept;
+    counts[0] = (int64_t)kept;
+    for (int k = 1; k < 5; ++k) counts[k] = (int64_t)host_counts[k];
+    return PA_OK;
+}
+
+int pa_stitcher_take_variants(pa_stitcher* s, pa_stitch_variant* dst, int64_t capacity) {
+    if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take variants: null or negative argument");
+    std::lock_guard<std::mutex> guard(s->lock);
+    if (!s->have_variants) return pa::set_error(PA_ERR_INVALID, "stitcher take variants: pa_stitcher_variants has not run since the last finish");
+    if (capacity < s->n_variants)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take variants: there are " + std::to_string(s->n_variants) + " records, room for " +
+                                                 std::to_string(capacity));
+    if (s->n_variants == 0) return PA_OK;
+    ST_HIP(hipSetDevice(s->device));
+    ST_HIP(hipMemcpyAsync(dst, s->v_out.p, (size_t)s->n_variants * sizeof(pa_stitch_variant), hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
 }
 
 int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n) {

@@ -17,6 +17,10 @@ the draft goes up once per contig, the edits read that copy.
 min_quality (opt-in, not in the reference; perform_stitch(..., min_quality=, draft=) is the host form): pa_stitcher_gate runs between
 the finish and the fill, over the winners on the device -- the edits whose phred is below it are withheld, the draft's letter
 stands -- and the withheld records come back for the .withheld.tsv; the draft the gate uploaded serves the fill and the edits.
+
+vcf (opt-in, with fill, not in the reference; perform_stitch(..., fill=, vcf=) is the host form): pa_stitcher_variants groups the
+edit records of the filled consensus into hunks, trims and left-aligns them against the draft on the device, and 32 bytes per
+record come back; pepper_amd/polish/Variants.py states the rule and writes the .vcf.gz from them.
 """
 import collections
 import contextlib
@@ -28,7 +32,7 @@ from pathlib import Path
 import numpy as np
 
 from pepper_amd import _lib, h5
-from pepper_amd.polish import Edits
+from pepper_amd.polish import Edits, Variants
 from pepper_amd.polish.Options import ImageSizeOptions
 from pepper_amd.polish.Stitch import MIN_SEQUENCE_REQUIRED_FOR_MULTITHREADING
 from pepper_amd.polish.perform_stitch import (GateLog, _log, check_fill, check_gate, draft_lengths, fastq_path,
@@ -107,6 +111,10 @@ class DeviceStitcher(object):
         self._withheld = None                # its withheld records, once withheld() took them
         # over every finish(min_quality=) of this handle; the seconds: pa_stitcher_gate and the records' copy back
         self.gate_totals = {"withheld": 0, "sub": 0, "del": 0, "ins": 0, "bytes_returned": 0, "seconds": 0.0}
+        self.last_variant_counts = None      # of the last variants(): [records, no-ops, unanchored, shifted, letters shifted]
+        # over every variants() of this handle; the seconds: pa_stitcher_variants with its copy back, and the text made of it
+        self.variant_totals = {"records": 0, "noops": 0, "unanchored": 0, "shifted": 0, "bytes_returned": 0, "seconds_device": 0.0,
+                               "seconds_text": 0.0}
         handle = ctypes.c_void_p()
         _lib.check(self._lib.pa_stitcher_create(self.device, ctypes.c_void_p(stream) if stream else None, ctypes.byref(handle)))
         self._handle = handle
@@ -342,6 +350,38 @@ class DeviceStitcher(object):
             self.edit_totals["seconds_compare"] += time.perf_counter() - t0
         return records
 
+    def variants(self, draft_sequence):
+        """After finish(fill=): the hunks of the filled consensus trimmed and left-aligned against draft_sequence (str or bytes,
+        the whole contig of the draft -- the one that filled, which is not uploaded again), as Variants.VARIANT_DTYPE records
+        with the bytes of Variants.records_numpy; normalised on the device (pa_stitcher_variants), only the records come back.
+        last_variant_counts: [records, no-ops, unanchored, shifted, letters shifted]."""
+        from pepper_amd.polish import Variants
+        draft = draft_sequence.encode() if isinstance(draft_sequence, str) else bytes(draft_sequence)
+        with self._lock:
+            if not self.last_filled:
+                raise _lib.PepperAmdError("the last finish had no fill: the variants describe the filled consensus")
+            if not self.last_pieces:                                 # the draft as it is: nothing was merged, no record
+                self.last_variant_counts = [0] * 5
+                return np.zeros(0, Variants.VARIANT_DTYPE)
+            t0 = time.perf_counter()
+            n, counts = ctypes.c_int64(), (ctypes.c_int64 * 5)()
+            _lib.check(self._lib.pa_stitcher_variants(self.handle, None, len(draft), ctypes.byref(n), counts))
+            records = np.zeros(n.value, Variants.VARIANT_DTYPE)
+            _lib.check(self._lib.pa_stitcher_take_variants(self.handle, records.ctypes.data, n.value))
+            self.last_variant_counts = [int(v) for v in counts]
+            for name, v in zip(("records", "noops", "unanchored", "shifted"), self.last_variant_counts):
+                self.variant_totals[name] += v
+            self.variant_totals["bytes_returned"] += records.nbytes
+            self.variant_totals["seconds_device"] += time.perf_counter() - t0
+        return records
+
+    def _write_variants(self, vcf_file, contig, stored, sequence):
+        """One contig's records of the .vcf.gz, after its filled finish (stored: the draft it was filled with)."""
+        records = self.variants(stored)
+        t0 = time.perf_counter()
+        vcf_file.contig(contig, records, self.last_variant_counts, stored, sequence, self.has_qualities(contig))
+        self.variant_totals["seconds_text"] += time.perf_counter() - t0
+
     def _write_edits(self, edits_file, draft, lengths, contig, stored=None, filled=None, withheld=None):
         """One contig's lines of the .edits.tsv, after its finish (stored: the draft the finish was filled or gated with; filled:
         it was filled, default: whenever stored is given; withheld: Edits.write_edits')."""
@@ -354,7 +394,7 @@ class DeviceStitcher(object):
         self.edit_totals["seconds_text"] += time.perf_counter() - t0
 
     def _finish_and_write(self, contig, threads, keys, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill, min_quality,
-                          gate):
+                          gate, vcf_file=None):
         """One held contig of a writer: its finish (filled, gated) and its records in every file that is open."""
         stored = _stored_draft(draft, lengths, contig) if fill is not None or min_quality else None
         result = self.finish(contig, threads, keys, qualities=qualities, fill=stored if fill is not None else None,
@@ -366,6 +406,8 @@ class DeviceStitcher(object):
                               withheld=None if withheld is None else len(withheld))
         if min_quality:
             gate.contig(contig, withheld, self.last_edit_counts[1:4] if edits is not None else self.applied_counts(lengths[contig]))
+        if vcf_file is not None:              # (behind the edits: it reads their records where they are)
+            self._write_variants(vcf_file, contig, stored, sequence)
         _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(sequence)) + ".")
         if len(sequence) > 0:
             fasta.write('>' + contig + "\n")
@@ -379,21 +421,26 @@ class DeviceStitcher(object):
         _lib.check(self._lib.pa_stitcher_stats(self.handle, out, 6))
         return dict(zip(("rows", "slab_bytes", "slots", "pieces", "positions", "table_bytes"), (int(v) for v in out)))
 
-    def write_fasta(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None):
+    def write_fasta(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None,
+                    vcf=None):
         """Every contig held, in natural order, to <output_prefix>_pepper_polished.fa (perform_stitch's file).  edits: the
         draft FASTA's path; <output_prefix>_pepper_polished.edits.tsv beside it (perform_stitch(..., edits=)'s file).
         fill / unpolished_contigs: perform_stitch's -- the draft FASTA's path, every contig filled; and the draft's other
         contigs written among them.  min_quality / draft: perform_stitch's -- the gate and the draft FASTA's path; also writes
-        <output_prefix>_pepper_polished.withheld.tsv."""
-        return self._write(output_prefix, threads, False, edits, fill, unpolished_contigs, min_quality, draft)
+        <output_prefix>_pepper_polished.withheld.tsv.  vcf: perform_stitch's -- the draft FASTA's path (the one that fills); also
+        writes <output_prefix>_pepper_polished.vcf.gz and .tbi, normalised on the device (variants())."""
+        return self._write(output_prefix, threads, False, edits, fill, unpolished_contigs, min_quality, draft, vcf)
 
-    def write_fastq(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None):
+    def write_fastq(self, output_prefix, threads, edits=None, fill=None, unpolished_contigs=False, min_quality=None, draft=None,
+                    vcf=None):
         """write_fasta's file, and beside it <output_prefix>_pepper_polished.fastq with the same records and their qualities
         (perform_stitch(..., qualities=True)'s two files), from one finish per contig.  -> the FASTQ's path."""
-        return self._write(output_prefix, threads, True, edits, fill, unpolished_contigs, min_quality, draft)
+        return self._write(output_prefix, threads, True, edits, fill, unpolished_contigs, min_quality, draft, vcf)
 
-    def _write(self, output_prefix, threads, qualities, edits, fill=None, unpolished_contigs=False, min_quality=None, gate_draft=None):
+    def _write(self, output_prefix, threads, qualities, edits, fill=None, unpolished_contigs=False, min_quality=None, gate_draft=None,
+               vcf=None):
         check_fill(edits, fill, unpolished_contigs)
+        Variants.check_vcf(vcf, fill)
         min_quality = check_gate(min_quality, gate_draft, edits, fill)
         output_path = output_prefix + '_pepper_polished.fa'
         Path(output_path).resolve().parents[0].mkdir(parents=True, exist_ok=True)
@@ -402,13 +449,14 @@ class DeviceStitcher(object):
             fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
             draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill, gate_draft if min_quality else None)
             gate = GateLog(files, output_prefix) if min_quality else None
+            vcf_file = Variants.VcfOutput(files, output_prefix, lengths) if vcf is not None else None
             held = set(self.contigs())
             for contig in sorted(held | set(lengths if unpolished_contigs else ()), key=natural_key):
                 if contig not in held:
                     write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file, gated=gate is not None)
                     continue
                 self._finish_and_write(contig, threads, None, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill,
-                                       min_quality, gate)
+                                       min_quality, gate, vcf_file)
             if gate is not None:
                 gate.log(min_quality)
         return fastq_path(output_prefix) if qualities else output_path
@@ -502,15 +550,18 @@ class _Held(object):
 
 
 def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, qualities=False, edits=None, fill=None,
-                     unpolished_contigs=False, min_quality=None, draft=None):
+                     unpolished_contigs=False, min_quality=None, draft=None, vcf=None):
     """perform_stitch(hdf_file_path, output_path, threads, qualities, edits, fill, unpolished_contigs) with the merge on the
     device: the same files read, the same FASTA (and FASTQ, and .edits.tsv) written.  stats: a dict that receives the handle's
     stats() after the last contig (with fill: and `fill`, the handle's fill_totals; with min_quality: and `gate`, its gate_totals).
-    min_quality / draft: perform_stitch's gate, on the device; the same .withheld.tsv."""
+    min_quality / draft: perform_stitch's gate, on the device; the same .withheld.tsv.  vcf: perform_stitch's, normalised on the
+    device; the same .vcf.gz (stats then also receives `variants`, the handle's variant_totals)."""
     check_fill(edits, fill, unpolished_contigs)
+    Variants.check_vcf(vcf, fill)
     min_quality = check_gate(min_quality, draft, edits, fill)
     gate_draft = draft
-    read_phred = qualities or edits is not None or bool(min_quality)      # the edit records and the gate read the winners' phred
+    # the edit records, the gate and the variants read the winners' phred
+    read_phred = qualities or edits is not None or bool(min_quality) or vcf is not None
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
     for prediction_file in all_prediction_files:
@@ -526,6 +577,7 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
         fastq = files.enter_context(open(fastq_path(output_prefix), 'w')) if qualities else None
         draft, lengths, edits_file = _open_draft(files, output_prefix, edits, fill, gate_draft if min_quality else None)
         gate = GateLog(files, output_prefix) if min_quality else None
+        vcf_file = Variants.VcfOutput(files, output_prefix, lengths) if vcf is not None else None
         for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
             if contig not in all_contigs:
                 write_unpolished(contig, fill, lengths[contig], fasta, fastq, edits_file, gated=gate is not None)
@@ -548,7 +600,7 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                             at += len(block[0])
             held.flush()
             stitcher._finish_and_write(contig, threads, all_chunk_keys, qualities, fasta, fastq, edits_file, draft, lengths, edits, fill,
-                                       min_quality, gate)
+                                       min_quality, gate, vcf_file)
         if gate is not None:
             gate.log(min_quality)
         if stats is not None:
@@ -557,4 +609,6 @@ def stitch_directory(hdf_file_path, output_path, threads, device=0, stats=None, 
                 stats["fill"] = dict(stitcher.fill_totals)
             if min_quality:
                 stats["gate"] = dict(stitcher.gate_totals)
+            if vcf is not None:
+                stats["variants"] = dict(stitcher.variant_totals)
     return output_path

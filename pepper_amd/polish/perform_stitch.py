@@ -13,6 +13,8 @@ writes the contigs of the draft that have no prediction, unchanged, in natural o
 min_quality=Q with draft=<draft FASTA> (opt-in, not in the reference): only the edits whose winning prediction has phred >= Q are
 applied, the draft's letter stands elsewhere (pepper_amd/polish/Stitch.py gate_numpy); also writes
 `<output_path>_pepper_polished.withheld.tsv`, the edits kept back.
+vcf=<draft FASTA> with fill (opt-in, not in the reference) also writes `<output_path>_pepper_polished.vcf.gz` and its `.tbi`: the
+hunks of the filled consensus trimmed and left-aligned against the draft (pepper_amd/polish/Variants.py).
 """
 import contextlib
 import re
@@ -119,8 +121,10 @@ def write_unpolished(contig, fill, draft_length, fasta, fastq, edits_file, gated
 
 
 def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=None, fill=None, unpolished_contigs=False,
-                   min_quality=None, draft=None):
+                   min_quality=None, draft=None, vcf=None):
+    from pepper_amd.polish import Variants
     check_fill(edits, fill, unpolished_contigs)
+    Variants.check_vcf(vcf, fill)
     min_quality = check_gate(min_quality, draft, edits, fill)
     all_prediction_files = get_file_paths_from_directory(hdf_file_path)
     all_contigs = set()
@@ -144,6 +148,7 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
         gate = GateLog(files, output_prefix) if min_quality else None
         draft_path = draft if min_quality else fill if fill is not None else edits
         lengths = draft_lengths(draft_path) if draft_path is not None else {}
+        vcf_file = Variants.VcfOutput(files, output_prefix, lengths) if vcf is not None else None
         for contig in sorted(all_contigs | set(lengths if unpolished_contigs else ()), key=natural_key):
             if contig not in all_contigs:
                 write_unpolished(contig, fill, lengths[contig], consensus_fasta_file, fastq, edits_file, gated=gate is not None)
@@ -165,14 +170,19 @@ def perform_stitch(hdf_file_path, output_path, threads, qualities=False, edits=N
                 if edits is not None:
                     Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None,
                                        withheld=len(withheld))
-            elif edits is not None:
-                consensus_sequence, quality, records, pieces = create_consensus_sequence(contig, all_chunk_keys, threads,
-                                                                                         qualities=qualities, edits=edits, fill=fill)
-                Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None)
+            elif edits is not None or vcf is not None:  # (the VCF is made of the filled consensus' edit records)
+                consensus_sequence, quality, records, pieces = create_consensus_sequence(
+                    contig, all_chunk_keys, threads, qualities=qualities, edits=edits if edits is not None else vcf, fill=fill)
+                if edits is not None:
+                    Edits.write_contig(edits_file, contig, records, pieces, lengths[contig], True, filled=fill is not None)
             elif qualities:
                 consensus_sequence, quality = create_consensus_sequence(contig, all_chunk_keys, threads, qualities=True, fill=fill)
             else:
                 consensus_sequence = create_consensus_sequence(contig, all_chunk_keys, threads, fill=fill)
+            if vcf_file is not None:
+                stored = whole_draft(fill, contig)[0]
+                vcf_file.contig(contig, *Variants.records_numpy(records, stored, consensus_sequence, True), stored, consensus_sequence,
+                                True)
             _log("FINISHED PROCESSING " + contig + ", POLISHED SEQUENCE LENGTH: " + str(len(consensus_sequence)) + ".")
             if consensus_sequence is not None and len(consensus_sequence) > 0:
                 consensus_fasta_file.write('>' + contig + "\n")

@@ -19,7 +19,7 @@ def _log(message):
 
 def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_path, batch_size, gpu_mode, device_ids,
            num_workers, stage_walls=None, fused_inference=None, batch_invariant=None, downsample_rate=1.0, device_stitch=None,
-           keep_predictions=None, qualities=None, edits=None, fill=None, min_quality=None):
+           keep_predictions=None, qualities=None, edits=None, fill=None, min_quality=None, vcf=None):
     """The reference's ten arguments; stage_walls: a dict that receives the three steps' wall times; fused_inference (default:
     PEPPER_AMD_FUSED_POLISH=1): the image workers hand their chunks to the model on the device instead of call_consensus reading
     the image files back (pepper_amd/polish/fused.py); both stores are still written.  batch_invariant (default:
@@ -44,7 +44,13 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     letter (upper-cased, quality '!'), an insertion below it is left out; positions whose draft letter is not ACGT are the model's
     (pepper_amd/polish/Stitch.py gate_numpy; not in the reference) -- and writes <output>_pepper_polished.withheld.tsv, the edits it
     kept back.  In the device forms the gate runs on the device (stage_walls["device_stitch_gate"] in the fused form: the edits
-    withheld by kind, the bytes that came back, the seconds)."""
+    withheld by kind, the bytes that came back, the seconds).
+    vcf (default: PEPPER_AMD_POLISH_VCF=1; needs fill, ValueError before any work without it): step 3 also writes
+    <output>_pepper_polished.vcf.gz and its .tbi -- one record per hunk of the filled consensus, trimmed and left-aligned against
+    fasta_filepath, QUAL and GQ the lowest phred of the hunk, so that replaying the records over the draft gives the FASTA
+    (pepper_amd/polish/Variants.py; not in the reference).  With min_quality it holds exactly the applied edits.  In the device
+    forms the hunks are normalised on the device (stage_walls["device_stitch_vcf"] in the fused form: the records, no-ops,
+    unanchored and shifted hunks, the bytes that came back, the seconds of the device call and of the text)."""
     from pepper_amd import _lib
     batch_invariant = _lib.batch_invariant_default(batch_invariant)
     if qualities is None:
@@ -59,6 +65,12 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
     min_quality = _lib.min_quality_value(_lib.polish_min_quality() if min_quality is None else min_quality)
     if min_quality:
         fill_kw.update(min_quality=min_quality, draft=fasta_filepath)
+    if vcf is None:
+        vcf = _lib.polish_vcf()
+    if vcf:
+        if not fill:
+            raise ValueError("vcf needs fill: the records describe one complete consensus per contig")
+        fill_kw.update(vcf=fasta_filepath)
     for path, what in ((bam_filepath, "BAM"), (fasta_filepath, "FASTA"), (model_path, "MODEL")):
         if not os.path.isfile(path):
             raise FileNotFoundError("CAN NOT LOCATE " + what + " FILE: " + str(path))
@@ -89,7 +101,7 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
         _log("STEP 1+2: GENERATING IMAGES AND RUNNING INFERENCE (FUSED) -> " + prediction_output_directory)
         sink = FusedConsensus(model_path, prediction_output_directory, batch_invariant=batch_invariant, device_stitch=device_stitch,
                               keep_predictions=bool(keep_predictions) or not device_stitch,
-                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities or bool(edits) or bool(min_quality))
+                              stitch_device=parse_device_ids(device_ids)[0], qualities=qualities or bool(edits) or bool(min_quality) or bool(vcf))
         try:
             make_images(bam_filepath, fasta_filepath, region, image_output_directory, threads, device_ids=device_ids, fused=sink,
                         stats=image_stats, downsample_rate=downsample_rate)
@@ -140,6 +152,8 @@ def polish(bam_filepath, fasta_filepath, output_path, threads, region, model_pat
                     stage_walls["device_stitch_fill"] = dict(stitcher.fill_totals)
                 if min_quality:
                     stage_walls["device_stitch_gate"] = dict(stitcher.gate_totals)
+                if vcf:
+                    stage_walls["device_stitch_vcf"] = dict(stitcher.variant_totals)
         finally:
             stitcher.close()
     if stage_walls is not None:

@@ -15,8 +15,12 @@ with phred uniform in 0..100 a share Q / 101 of them is withheld) -- perform_sti
 and, with --device, stitch_directory(..., min_quality=Q, draft=draft), FASTA and .withheld.tsv checked against the host's -- and
 then, on one handle that holds the job's rows with their phred, times finish + take beside finish + gate + take (+ the withheld
 records' copy back), one warm-up and three timed calls each.
+--vcf (with --device) holds the job's rows with their phred on one handle, fills once against the same draft, and times three
+things on the same edit records, one warm-up and three timed calls each: the edit comparison with its copy back
+(pa_stitcher_edits + take), the variant normalisation with its copy back (pa_stitcher_variants + take) and the numpy twin
+(Variants.records_numpy); the device's records are checked against the twin's bytes.
     python tools/bench_stitch.py [--chunks 65536] [--files 4] [--dir /dev/shm] [--device] [--qualities] [--edits] [--fill]
-                                 [--min-quality Q]"""
+                                 [--min-quality Q] [--vcf]"""
 import argparse
 import json
 import os
@@ -129,6 +133,45 @@ def device_gate_legs(pred, tmp, draft_fa, regions, q):
     return runs
 
 
+def device_vcf_legs(pred, draft_fa):
+    """On one handle that holds the job's rows with their phred, after one filled finish: the edit comparison with its copy back,
+    pa_stitcher_variants with its copy back (the edit records are there), and the numpy twin on the same records; one warm-up
+    and three timed calls each.  The device's records are checked against the twin's bytes."""
+    import statistics
+
+    from pepper_amd import h5
+    from pepper_amd.polish import Variants
+    from pepper_amd.polish.DeviceStitch import DeviceStitcher, _Held, _read_region
+    from pepper_amd.polish.perform_stitch import get_file_paths_from_directory
+    draft = open(draft_fa, "rb").read().split(b"\n")[1]
+    with DeviceStitcher(0) as st:
+        keys, held = [], _Held(st, "ctg0")
+        for prediction_file in get_file_paths_from_directory(pred):
+            with h5.File(prediction_file, 'r') as f:
+                for name, start, end in f.list_polish_regions("ctg0"):
+                    key, at = (prediction_file, name, start, end), 0
+                    keys.append(key)
+                    for block in _read_region(f, 'predictions/ctg0/ctg0-%d-%d' % (start, end), True):
+                        held.take(key, at, *block)
+                        at += len(block[0])
+        held.flush()
+        sequence = st.finish("ctg0", 1, keys, fill=draft)
+        legs, results = {}, {}
+        for leg, call in (("edits_take", lambda: st.edits(draft)), ("variants_take", lambda: st.variants(draft)),
+                          ("twin", lambda: Variants.records_numpy(results["edits_take"], draft, sequence, True))):
+            seconds = []
+            for repeat in range(4):                          # (the first call grows the handle's tables)
+                t0 = time.perf_counter()
+                results[leg] = call()
+                seconds.append(time.perf_counter() - t0)
+            legs[leg] = {"seconds": [round(s, 4) for s in seconds[1:]], "median": round(statistics.median(seconds[1:]), 4)}
+        legs["edit_records"], legs["variant_counts"] = len(results["edits_take"]), st.last_variant_counts
+        legs["equals_twin"] = results["variants_take"].tobytes() == results["twin"][0].tobytes() and \
+            st.last_variant_counts == results["twin"][1]
+        legs["letters"], legs["stats"] = len(sequence), st.stats()
+    return [{"merge": "device", "vcf": "one handle", **legs}]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--chunks", type=int, default=65536)
@@ -139,6 +182,7 @@ def main():
     ap.add_argument("--edits", action="store_true", help="also run the set with the edits on (.edits.tsv beside the FASTA)")
     ap.add_argument("--fill", action="store_true", help="also run the set with fill on (the draft where no row covered it)")
     ap.add_argument("--min-quality", type=int, default=0, help="also run the set with the gate on (only the edits with phred >= Q)")
+    ap.add_argument("--vcf", action="store_true", help="with --device: time the variant normalisation beside the edit comparison and the twin")
     args = ap.parse_args()
     tmp = tempfile.mkdtemp(dir=args.dir)
     try:
@@ -181,7 +225,7 @@ def main():
                 runs.append({"merge": "numpy", "qualities": True, "threads": threads, "seconds": round(dt, 2),
                              "chunks_per_s": round(2 * regions / dt), "bases": os.path.getsize(out),
                              "equals_fasta": open(out, "rb").read() == open(os.path.join(tmp, "out0%d" % threads) + "_pepper_polished.fa", "rb").read()})
-        if args.edits or args.fill or args.min_quality:
+        if args.edits or args.fill or args.min_quality or args.vcf:
             os.environ["PEPPER_AMD_STITCH_NUMPY"] = "0"
             draft_fa = os.path.join(tmp, "draft.fa")
             with open(draft_fa, "w") as fh:                 # as long as the positions reach
@@ -251,6 +295,8 @@ def main():
                 runs.extend(device_fill_legs(pred, tmp, draft_fa, regions))
             if args.min_quality:
                 runs.extend(device_gate_legs(pred, tmp, draft_fa, regions, args.min_quality))
+            if args.vcf:
+                runs.extend(device_vcf_legs(pred, draft_fa))
         from pepper_amd.hostinfo import usable_cpus
         print(json.dumps({"metric": "perform_stitch: prediction HDF5 -> FASTA (host" + (" and device" if args.device else "") + ")", "chunks": 2 * regions, "files": args.files,
                           "usable_cpus": usable_cpus(), "runs": runs}))
