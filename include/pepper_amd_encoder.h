@@ -320,7 +320,8 @@ int pa_polish_encoder_generate_summary_batch(pa_encoder* e, int32_t n_regions, c
                                              const int64_t* start_pos, const int64_t* end_pos, int64_t* n_rows);
 /* The two halves of the call above (stage = validate + upload, run = the kernels; may be repeated: what bench.py times with the
  * pileups resident in HBM), and the sizes of the staged batch / last run: [0] read bases, [1] output rows, [2] reads, [3] CIGAR
- * operations, [4] tiles, [5] regions. */
+ * operations, [4] tiles, [5] regions, [6] the launch sets the last run took: 1 where the first sizes of the record and
+ * insert-slot buffers held, 2 or 3 where the run was repeated with room (0 before any run). */
 int pa_polish_encoder_stage_batch(pa_encoder* e, int32_t n_regions, const pa_pileup* pileups, const int64_t* start_pos,
                                   const int64_t* end_pos);
 int pa_polish_encoder_run_staged(pa_encoder* e, int64_t* n_rows);

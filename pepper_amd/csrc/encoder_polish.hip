@@ -413,6 +413,7 @@ struct pa_polish_batch {
     int64_t total_bases = 0, total_ops = 0, total_reads = 0, total_rows = 0, total_out = 0, total_positions = 0;
     int n_tiles = 0, rec_cap = 0;
     int64_t ins_cap = 0;                     // insert slots the output buffers hold (grows with what the handle has seen)
+    int runs = 0;                            // launch sets the last call took: 1 = the buffers' first sizes held
     bool staged = false;
     DBuf d_seq, d_cig_op, d_cig_len, d_meta, d_zero, d_tile_off, d_sorted, d_ins_base, d_totals,
         d_bases, d_ins_counts, d_coverage, d_pixels, d_positions;
@@ -559,6 +560,7 @@ int polish_run(pa_encoder* e, int64_t* n_rows) {
     hipStream_t st = e->stream;
     const int n_regions = (int)b.regs.size();
     b.total_out = 0;
+    b.runs = 0;
     if (n_regions == 0) return PA_OK;
     const char* dm = b.d_meta.as<char>();
     const ReadRec* d_reads = b.x_reads ? b.x_reads : reinterpret_cast<const ReadRec*>(dm + b.o_reads);
@@ -587,6 +589,7 @@ int polish_run(pa_encoder* e, int64_t* n_rows) {
     int* tile_fill = tile_count + b.n_tiles;
     int* back = b.h_back.as<int>();            // [PC_N] counters | records | totals per region
     for (int attempt = 0;; ++attempt) {
+        b.runs = attempt + 1;
         const int64_t out_cap = b.total_positions + b.ins_cap;
         ENC_ALLOC(b.d_sorted, (size_t)b.rec_cap * sizeof(TileRec));
         ENC_ALLOC(b.d_ins_counts, (size_t)(b.ins_cap + 1) * PROW * 4);
@@ -802,9 +805,9 @@ int pa_polish_encoder_run_staged(pa_encoder* e, int64_t* n_rows) { return polish
 int pa_polish_encoder_batch_stats(pa_encoder* e, int64_t* out, int32_t n) {
     if (!e || !out || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
     const pa_polish_batch* b = e->polish;
-    const int64_t v[6] = {b ? b->total_bases : 0, b ? b->total_out : 0, b ? b->total_reads : 0, b ? b->total_ops : 0,
-                          b ? (int64_t)b->n_tiles : 0, b ? (int64_t)b->regs.size() : 0};
-    for (int i = 0; i < n; ++i) out[i] = i < 6 ? v[i] : 0;
+    const int64_t v[7] = {b ? b->total_bases : 0, b ? b->total_out : 0, b ? b->total_reads : 0, b ? b->total_ops : 0,
+                          b ? (int64_t)b->n_tiles : 0, b ? (int64_t)b->regs.size() : 0, b ? (int64_t)b->runs : 0};
+    for (int i = 0; i < n; ++i) out[i] = i < 7 ? v[i] : 0;
     return PA_OK;
 }
 

@@ -128,9 +128,10 @@ class StagedSummaries(object):
         return dict(records_ms=ms[0], tile_ms=ms[1], insert_rows_ms=ms[2])
 
     def stats(self):
-        v = np.zeros(6, np.int64)
-        _lib.check(self.lib.pa_polish_encoder_batch_stats(self.enc, v.ctypes.data, 6))
-        return dict(bases=int(v[0]), rows=int(v[1]), reads=int(v[2]), cigar_ops=int(v[3]), tiles=int(v[4]), regions=int(v[5]))
+        v = np.zeros(7, np.int64)
+        _lib.check(self.lib.pa_polish_encoder_batch_stats(self.enc, v.ctypes.data, 7))
+        return dict(bases=int(v[0]), rows=int(v[1]), reads=int(v[2]), cigar_ops=int(v[3]), tiles=int(v[4]), regions=int(v[5]),
+                    runs=int(v[6]))
 
     def results(self):
         total = int(self.rows[:self.n].sum())
