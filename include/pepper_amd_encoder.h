@@ -255,7 +255,7 @@ int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const
  *                     generate_summary[_batch], pa_encoder_run_staged after pa_encoder_stage_batch, pa_encoder_stage_packed or
  *                     pa_encoder_stage_packed_device, repeated runs included -- until set again.  n > 8, lower[0] != 0 or a bound
  *                     not above the one before it: PA_ERR_INVALID, pa_last_error names the entry, the handle keeps what it had.
- *                     With bins set tile_count_kernel (its <true> instance) stores every row's depth (int32, four bytes per row beside the 104 of the
+ *                     With bins set tile_count_kernel (its TILE_DEPTH instance) stores every row's depth (int32, four bytes per row beside the 104 of the
  *                     matrix: no saturation, any int32 bound is taken), and behind the run's other kernels, in the same submission
  *                     and before its one wait, depth_runs_kernel (csrc/encoder.hip; one workgroup per 512-row tile, run twice around
  *                     a scan of the tiles' counts) run-length encodes the bins of the rows of every region's candidate window
@@ -280,12 +280,53 @@ int pa_encoder_depth_runs(pa_encoder* e, int64_t capacity, int32_t* region, int6
 int pa_encoder_depth_totals(pa_encoder* e, int32_t n_regions, int64_t* bases, int64_t* depth_sum);
 int pa_encoder_depth_calls(pa_encoder* e, int64_t* runs_with_bins, int64_t* overflows);
 
+/* Reference blocks of the positions a run looked at (opt-in, not in the reference; pepper_amd/variant/RefConfidence.py states the
+ * rule and builds the table, pepper_amd/variant/Gvcf.py writes the gVCF).  Per position, from tile_count_kernel's counters
+ * before the int8 clamp and the sign flip (F / R: forward / reverse slot of a symbol): cov the coverage above, ref_col = F + R
+ * of the reference letter (0 where it is not one of ACGT), ins = F + R of the insert anchor, star = F + R of `*`;
+ * n_ref = max(0, ref_col - ins), n_alt = max(0, cov - ref_col) + min(ins, ref_col) + star; with n = n_ref + n_alt > 100 both are
+ * rescaled in 64-bit integers, n_ref' = (100 n_ref + n - 1) / n, n_alt' = 100 - n_ref'.  GQ = table[n_ref][n_alt], 0 where the
+ * reference letter is not one of ACGT: a read-count model (DeepVariant's reference confidence), not the network's output.
+ * pa_encoder_set_ref_confidence  table: table_side x table_side uint8, row n_ref, column n_alt (HOST pointer, copied to the
+ *                     device by this call); table_side must be 101.  lower: n_bands ascending lower bounds of GQ,
+ *                     lower[0] == 0 < lower[1] < ... <= 255, 1 <= n_bands <= 8: band k holds the GQs in [lower[k], lower[k + 1]),
+ *                     the last band is open above.  n_bands == 0: off (the state of a new handle; every launch and every
+ *                     output byte is then as without the feature; table and lower are not read).  Holds for every variant form
+ *                     -- pa_encoder_generate_summary[_batch], pa_encoder_run_staged after any staging call, repeated runs
+ *                     included -- until set again.  Malformed: a side other than 101, more than 8 bands, lower[0] != 0, a bound
+ *                     not above the one before it or above 255, table[0][0] != 0, an entry below the one of one reference read
+ *                     less or above the one of one other read less -- PA_ERR_INVALID, pa_last_error names the entry, the
+ *                     handle keeps what it had.
+ *                     With a table set tile_count_kernel (its third instance; it serves the depth bins too when both are set)
+ *                     stores every row's depth (int32, no saturation) and GQ (one byte), and behind the run's other kernels, in
+ *                     the same submission and before its one wait, ref_blocks_kernel (csrc/encoder.hip; one workgroup per
+ *                     512-row tile, run twice around a scan of the tiles' counts) run-length encodes the bands of the rows of
+ *                     every region's candidate window cut to the region, with the smallest depth and the smallest GQ of each
+ *                     run: one 20-byte record per run and tile stays on the device, their count comes back with the run's
+ *                     counters.  A run that crosses a tile border (every 512 rows of a region) is reported as one record per
+ *                     tile: touching records of equal band are the caller's to merge, taking the minima (RefConfidence.py
+ *                     merge_blocks).  With targets set a position outside all of them has band -1 and is reported like any
+ *                     other.  Candidates and images do not depend on the table.
+ *                     Room for the records is sized as for the depth runs, or by what an earlier run of the handle needed; a
+ *                     run with more is emitted a second time after one more wait, exact, and counted (pa_encoder_ref_calls).
+ *                     Debug: PEPPER_AMD_REF_BLOCK_CAP=<records>, read by this call, replaces the first figure.
+ * pa_encoder_ref_blocks  *n_blocks = the records of the last run (all regions, in region and position order; valid until the
+ *                     handle's next stage or run).  With any output array given, capacity >= *n_blocks entries are filled --
+ *                     region index, start and end (half-open) as contig positions, band, smallest depth, smallest GQ -- else
+ *                     PA_ERR_INVALID (nothing is truncated).  PA_ERR_INVALID too when the last run had no table set.
+ * pa_encoder_ref_calls  runs of this handle made with a table set / runs among them emitted twice (either may be NULL). */
+int pa_encoder_set_ref_confidence(pa_encoder* e, const uint8_t* table, int32_t table_side, int32_t n_bands, const int32_t* lower);
+int pa_encoder_ref_blocks(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* band, int32_t* min_dp,
+                          int32_t* min_gq, int64_t* n_blocks);
+int pa_encoder_ref_calls(pa_encoder* e, int64_t* runs, int64_t* overflows);
+
 /* Times of the last run in milliseconds, HIP events on the encoder's stream: [0] record kernels (segment_reads x 2 +
  * tile_offsets), [1] tile_count_kernel, [2] compact_votes_kernel + pack_results_kernel, [3] gather_windows_kernel; host clock:
  * [4] candidate enumeration, [5] the whole run, [6], [7] parts of [4]; packed form: [8] upload of arena + tables,
  * [9] unpack_clip_kernel; [12] the device enumeration (group_votes_kernel, enumerate_sites_kernel and the scans between them;
  * [4], [6], [7] are 0 for a run it served, [12] is 0 for every other run); [13] the depth-class kernels (depth_runs_kernel twice and the
- * scan between them, HIP events; 0 for a run without depth bins).  Sizes of the staged batch: [0] read bases, [1] matrix rows,
+ * scan between them, HIP events; 0 for a run without depth bins); [14] the reference-block kernels (ref_blocks_kernel twice and
+ * the scan between them, HIP events; 0 for a run without a reference-confidence table).  Sizes of the staged batch: [0] read bases, [1] matrix rows,
  * [2] reads, [3] CIGAR operations, [4] tiles, [5] regions. */
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n);
 int pa_encoder_batch_stats(pa_encoder* e, int64_t* out, int32_t n);

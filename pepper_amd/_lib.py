@@ -116,6 +116,10 @@ SYMBOLS = [
     ("pa_encoder_depth_runs", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_int64)]),
     ("pa_encoder_depth_totals", ctypes.c_int, [c_void_p, c_int32, c_void_p, c_void_p]),
     ("pa_encoder_depth_calls", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
+    ("pa_encoder_set_ref_confidence", ctypes.c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
+    ("pa_encoder_ref_blocks", ctypes.c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             ctypes.POINTER(c_int64)]),
+    ("pa_encoder_ref_calls", ctypes.c_int, [c_void_p, ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]),
     ("pa_encoder_last_timing", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_batch_stats", ctypes.c_int, [c_void_p, c_void_p, c_int32]),
     ("pa_encoder_get_results", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -715,6 +715,8 @@ struct TileArgs {
     const uint8_t* targets;   // verdicts of target_rows_kernel, one per row like `pass`; null: no targets set
     int32_t* depth;           // tile_count_kernel<true>: the row's coverage as the per-position pass sees it, one int32 per row like `pass`
     int debug;        // PA_TILE_DEBUG (profiling only, tools/tile_ablation.sh): parts of the kernel switched off
+    uint8_t* gq;              // tile_count_kernel<TILE_REFCONF>: the row's reference-confidence GQ, one byte per row like `pass` ...
+    const uint8_t* gq_table;  // ... looked up in the host's REFCONF_SIDE x REFCONF_SIDE table [n_ref][n_alt] (pa_encoder_set_ref_confidence)
 };
 
 __device__ __forceinline__ uint64_t allele_prefix(const char* bytes, uint32_t off, uint32_t len) {
@@ -744,10 +746,15 @@ __device__ unsigned long long g_enc_cycles[8];     // debug: shader-clock cycles
 #else
 #define ENC_LAP(k) do { } while (0)
 #endif
-// DEPTH (depth bins set, pa_encoder_set_depth_bins): the per-position pass also stores the row's coverage.  A template
-// parameter and not a test of a.depth: the instance every other run launches is then instruction for instruction the kernel
-// without the feature (with the test in it the register allocation moved and the kernel measured 6 % slower, switch off).
-template <bool DEPTH>
+// FORM: what the per-position pass keeps beside the matrix row.  TILE_PLAIN nothing; TILE_DEPTH (depth bins set,
+// pa_encoder_set_depth_bins) the row's coverage; TILE_REFCONF (a reference-confidence table set, pa_encoder_set_ref_confidence,
+// with or without depth bins) the coverage and the row's GQ byte: the evidence of variant/RefConfidence.py from the counters
+// before the int8 clamp, rescaled to 100 and looked up -- no transcendental runs here.  A template parameter and not a test of
+// a.depth / a.gq: the instance every other run launches is then instruction for instruction the kernel without the feature
+// (with the test in it the register allocation moved and the kernel measured 6 % slower, switch off).
+enum { TILE_PLAIN = 0, TILE_DEPTH = 1, TILE_REFCONF = 2 };
+constexpr int REFCONF_SIDE = 101;                  // the table's side: counts 0 .. 100 after the rescale
+template <int FORM>
 __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileArgs a) {
     __shared__ int cnt[NCNT * TP];                 // [counter][row]; reused as the finished [row][26] tile for the store
     __shared__ char ref_s[TP];
@@ -1164,7 +1171,24 @@ __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileA
         passes = (s || n || d) && idx >= reg.cand_lo && idx <= reg.cand_hi && (double)cov >= reg.min_cov;
         if (a.targets != nullptr) passes = passes && a.targets[reg.row_base + idx] != 0;
         a.pass[reg.row_base + idx] = passes ? 1 : 0;
-        if (DEPTH) a.depth[reg.row_base + idx] = cov;
+        if (FORM != TILE_PLAIN) a.depth[reg.row_base + idx] = cov;
+        if (FORM == TILE_REFCONF) {
+            // reads that show the reference letter and open no insert behind it speak for the reference; other letters, insert
+            // anchors and deleted bases (not part of cov) against it.  vals[] hold the negated, still unclamped counters.
+            const int code = vals[0];              // 1 .. 4: A C G T, 5: anything else
+            int ref_col = 0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) ref_col = code == s + 1 ? -(vals[8 + s] + vals[19 + s]) : ref_col;
+            const int ins = -(vals[12] + vals[23]), star = -(vals[14] + vals[25]);
+            int n_ref = max(0, ref_col - ins);
+            int n_alt = max(0, cov - ref_col) + min(ins, ref_col) + star;
+            const long long n = (long long)n_ref + n_alt;
+            if (n > REFCONF_SIDE - 1) {
+                n_ref = (int)((100ll * n_ref + n - 1) / n);
+                n_alt = 100 - n_ref;
+            }
+            a.gq[reg.row_base + idx] = code <= 4 ? a.gq_table[n_ref * REFCONF_SIDE + n_alt] : (uint8_t)0;
+        }
         pass_s[tid] = passes ? 1 : 0;
         if (passes) {
             site.region = region;
@@ -1307,6 +1331,80 @@ __global__ __launch_bounds__(TP) void depth_runs_kernel(const RegRec* __restrict
         int slot = tile_off[tile] + __popcll(hm & ((1ull << lane) - 1ull));
         for (int k = 0; k < w; ++k) slot += wave_heads[k];
         if (slot < run_cap) runs[slot] = DepthRun{region, idx, bin};      // past the capacity: the host emits again with room
+    }
+}
+
+// ---- reference blocks (pa_encoder_set_ref_confidence) -------------------------------------------------------------------
+// The rows of every region's candidate window, as above, each in the band of the GQ byte tile_count_kernel<TILE_REFCONF> stored
+// for it, run-length encoded with the smallest coverage and the smallest GQ of each run: one record per run and tile, in
+// region and row order.  One workgroup per tile, one thread per row, launched twice around tile_offsets_kernel.  A tile's
+// first row inside the window is always a head -- a run that crosses a tile border is one record per tile, and the host
+// (variant/RefConfidence.py merge_blocks, BlockTrack) joins touching records of equal band with their minima -- so every row
+// of the window belongs to a head of its own tile and the minima are taken in LDS: atomicMin on the slot of the head's rank
+// among the tile's heads (a minimum does not depend on the order; no global atomic on the way to the output).
+// A row outside every target (targets != null) has the band DEPTH_OFF_TARGET.
+constexpr int REFCONF_MAX_BANDS = 8;
+struct RefBands { int32_t n; int32_t lower[REFCONF_MAX_BANDS]; };    // lower[0] == 0 < lower[1] < ...; band k = GQ in [lower[k], lower[k + 1])
+struct RefBlock { int32_t region, row, band, min_dp, min_gq; };
+
+__device__ __forceinline__ int ref_band(const RefBands& bands, int gq) {
+    int k = 0;
+#pragma unroll
+    for (int j = 1; j < REFCONF_MAX_BANDS; ++j) k += (j < bands.n && gq >= bands.lower[j]) ? 1 : 0;
+    return k;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(TP) void ref_blocks_kernel(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region,
+                                                        const int32_t* __restrict__ depth, const uint8_t* __restrict__ gq,
+                                                        const uint8_t* __restrict__ targets, RefBands bands,
+                                                        int* __restrict__ tile_heads, const int* __restrict__ tile_off,
+                                                        RefBlock* __restrict__ blocks, int block_cap) {
+    __shared__ uint8_t band_s[TP];
+    __shared__ int wave_heads[TP / 64];
+    __shared__ int min_dp_s[TP], min_gq_s[TP];       // per head of the tile, by rank (at most one head per row)
+    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int region = tile_region[tile];
+    const RegRec* reg = regions + region;
+    const int lo = reg->cand_lo > 0 ? reg->cand_lo : 0;
+    const int hi = reg->cand_hi < reg->L - 1 ? reg->cand_hi : reg->L - 1;
+    const int idx = (tile - reg->tile0) * TP + tid;
+    const bool in = idx >= lo && idx <= hi;          // (idx <= L - 1: a row tile_count_kernel stored a depth and a GQ for)
+    int d = 0, q = 0, band = DEPTH_OFF_TARGET;
+    if (in) {
+        d = depth[reg->row_base + idx];
+        q = gq[reg->row_base + idx];
+        if (targets == nullptr || targets[reg->row_base + idx] != 0) band = ref_band(bands, q);
+    }
+    band_s[tid] = (uint8_t)band;
+    if (EMIT) {
+        min_dp_s[tid] = 0x7fffffff;
+        min_gq_s[tid] = 0x7fffffff;
+    }
+    __syncthreads();
+    const bool head = in && (idx == lo || tid == 0 || band_s[tid - 1] != band);
+    const unsigned long long hm = __ballot(head);
+    if (lane == 0) wave_heads[w] = __popcll(hm);
+    __syncthreads();
+    if (!EMIT) {
+        if (tid == 0) {
+            int n = 0;
+            for (int k = 0; k < TP / 64; ++k) n += wave_heads[k];
+            tile_heads[tile] = n;
+        }
+        return;
+    }
+    // the rank of this row's run among the tile's heads: heads at or before it, less one (>= 0 for every row of the window)
+    int rank = __popcll(hm & ((2ull << lane) - 1ull)) - 1;
+    for (int k = 0; k < w; ++k) rank += wave_heads[k];
+    if (in) {
+        atomicMin(&min_dp_s[rank], d);
+        atomicMin(&min_gq_s[rank], q);
+    }
+    __syncthreads();
+    if (head) {
+        const int slot = tile_off[tile] + rank;
+        if (slot < block_cap) blocks[slot] = RefBlock{region, idx, band, min_dp_s[rank], min_gq_s[rank]};   // past the capacity: emitted again with room
     }
 }
 
@@ -1758,6 +1856,14 @@ struct pa_variant_batch {
     bool depth_on = false;
     int depth_bins = 0;
     int64_t n_runs = 0, depth_calls = 0, depth_overflows = 0;
+    // reference blocks (pa_encoder_set_ref_confidence): the GQ byte of every row, the tiles' head counts and their scan, the
+    // block records; of the last run: was it made with a table, its records, and the handle's counters as for the depth runs
+    DBuf d_gq, d_bheads, d_bscan, d_blocks;
+    HBuf h_bcount;
+    int64_t block_cap = 0;
+    bool ref_on = false;
+    int ref_bands = 0;
+    int64_t n_blocks = 0, ref_calls = 0, ref_overflows = 0;
     DBuf d_tile_off, d_sorted, d_mat, d_pass, d_sites, d_votes, d_votes_out, d_sites_dense, d_votes_dense, d_ovf, d_cands, d_img32, d_img8;
     HBuf h_counts, h_sites, h_votes;
     // candidates enumerated on the device (pa_encoder_set_device_candidates): the rules of the staged regions, the per-site and
@@ -1786,7 +1892,7 @@ struct pa_variant_batch {
     std::vector<int64_t> positions;
     std::vector<int32_t> depths, freqs;
     std::string names;
-    double ms[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double ms[15] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 void pa_variant_batch_free(pa_variant_batch* b) { delete b; }
@@ -1895,6 +2001,7 @@ const char* const BATCH_TOO_LARGE = "batch too large: more than 2^30 rows or 2^3
 void unstage(pa_encoder* e) {
     if (e && e->variant) e->variant->staged = false;
     if (e && e->variant) e->variant->depth_on = false;      // (the depth runs of the last run speak of its regions)
+    if (e && e->variant) e->variant->ref_on = false;        // (... and so do its reference blocks)
 }
 
 struct RegionSums { int64_t rows = 0, ref = 0; int tiles = 0; };      // matrix rows, reference bytes and tiles of the regions so far
@@ -2369,12 +2476,20 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     ta.debug = tile_debug;
     ta.targets = targets;
     ta.depth = nullptr;                            // depth bins set: the tile kernel keeps every row's coverage for depth_runs_kernel
-    if (e->n_depth_bins > 0) {
+    ta.gq = nullptr;                               // a reference-confidence table set: the coverage and the GQ byte for ref_blocks_kernel
+    ta.gq_table = nullptr;
+    if (e->n_depth_bins > 0 || e->n_ref_bands > 0) {
         ENC_ALLOC(b.d_depth, (size_t)b.total_rows * 4 + 64);
         ta.depth = b.d_depth.as<int32_t>();
     }
-    if (ta.depth != nullptr) hipLaunchKernelGGL(tile_count_kernel<true>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
-    else hipLaunchKernelGGL(tile_count_kernel<false>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    if (e->n_ref_bands > 0) {
+        ENC_ALLOC(b.d_gq, (size_t)b.total_rows + 64);
+        ta.gq = b.d_gq.as<uint8_t>();
+        ta.gq_table = e->d_gq_table.as<uint8_t>();
+    }
+    if (ta.gq != nullptr) hipLaunchKernelGGL(tile_count_kernel<TILE_REFCONF>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    else if (ta.depth != nullptr) hipLaunchKernelGGL(tile_count_kernel<TILE_DEPTH>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
+    else hipLaunchKernelGGL(tile_count_kernel<TILE_PLAIN>, dim3((unsigned)b.n_tiles), dim3(NT), 0, st, ta);
     ENC_HIP(hipEventRecord(e->ev[2], st));
     hipLaunchKernelGGL(compact_votes_kernel, dim3((unsigned)std::min(2048, (w.vote_cap + 255) / 256)), dim3(256), 0, st, b.d_votes.as<Vote>(),
                        w.counters, w.vote_cap, b.p_regions, b.d_pass.as<uint8_t>(), b.d_seq.as<char>(), b.p_ref, w.region_counts,
@@ -2452,6 +2567,70 @@ int finish_depth_runs(pa_encoder* e, const RunShape& w) {
     ENC_HIP(hipGetLastError());
     ENC_HIP(hipStreamSynchronize(e->stream));
     b.depth_on = true;
+    return PA_OK;
+}
+
+// The reference blocks behind the depth classes, in the same submission (a reference-confidence table set): heads counted per
+// tile, the counts scanned, the blocks emitted with their minima; the block count travels to the host before the run's one
+// wait.  Room as for the depth runs: a record per 16 rows and four per tile, or PEPPER_AMD_REF_BLOCK_CAP as
+// pa_encoder_set_ref_confidence read it, or what an earlier run of the handle needed; more heads: finish_ref_blocks.
+void launch_ref_blocks(pa_encoder* e, bool emit) {
+    pa_variant_batch& b = *e->variant;
+    RefBands bands;
+    bands.n = b.ref_bands;
+    for (int k = 0; k < REFCONF_MAX_BANDS; ++k) bands.lower[k] = e->ref_lower[k];
+    const uint8_t* targets = e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr;
+    if (emit)
+        hipLaunchKernelGGL(ref_blocks_kernel<true>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
+                           b.d_depth.as<int32_t>(), b.d_gq.as<uint8_t>(), targets, bands, b.d_bheads.as<int>(), b.d_bscan.as<int>(),
+                           b.d_blocks.as<RefBlock>(), (int)b.block_cap);
+    else
+        hipLaunchKernelGGL(ref_blocks_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
+                           b.d_depth.as<int32_t>(), b.d_gq.as<uint8_t>(), targets, bands, b.d_bheads.as<int>(), b.d_bscan.as<int>(),
+                           b.d_blocks.as<RefBlock>(), (int)b.block_cap);
+}
+
+int submit_ref_blocks(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    hipStream_t st = e->stream;
+    (void)w;
+    if (e->n_ref_bands <= 0) return PA_OK;
+    b.ref_bands = e->n_ref_bands;
+    const int64_t sized = e->ref_block_cap > 0 ? e->ref_block_cap : b.total_rows / 16 + 4 * (int64_t)b.n_tiles;
+    b.block_cap = std::min<int64_t>(std::max(b.block_cap, sized), 0x7ffffff0);
+    ENC_ALLOC(b.d_bheads, (size_t)b.n_tiles * 4);            // (every tile writes its count: nothing to clear)
+    ENC_ALLOC(b.d_bscan, ((size_t)b.n_tiles + 1) * 4);
+    ENC_ALLOC(b.d_blocks, (size_t)b.block_cap * sizeof(RefBlock));
+    if (!b.h_bcount.ensure(8)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_HIP(hipEventRecord(e->ev[14], st));
+    launch_ref_blocks(e, false);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, b.d_bheads.as<int>(), b.n_tiles, b.d_bscan.as<int>());
+    launch_ref_blocks(e, true);
+    ENC_HIP(hipEventRecord(e->ev[15], st));
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipMemcpyAsync(b.h_bcount.p, b.d_bscan.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
+    return PA_OK;
+}
+
+// after the run's wait: the block count, and the second emit of a run whose records outgrew the buffer (counted; depths, GQ
+// bytes, verdicts and scanned offsets are where the first emit read them, so the records are exact)
+int finish_ref_blocks(pa_encoder* e) {
+    pa_variant_batch& b = *e->variant;
+    if (e->n_ref_bands <= 0) return PA_OK;
+    b.ref_calls += 1;
+    b.n_blocks = *b.h_bcount.as<int>();
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, e->ev[14], e->ev[15]); b.ms[14] = ms;     // ref_blocks_kernel x 2 + tile_offsets_kernel
+    b.ref_on = true;
+    if (b.n_blocks <= b.block_cap) return PA_OK;
+    b.ref_on = false;                              // (until the second emit is through)
+    b.ref_overflows += 1;
+    b.block_cap = b.n_blocks;
+    ENC_ALLOC(b.d_blocks, (size_t)b.block_cap * sizeof(RefBlock));
+    launch_ref_blocks(e, true);
+    ENC_HIP(hipGetLastError());
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    b.ref_on = true;
     return PA_OK;
 }
 
@@ -2661,10 +2840,14 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.dev_results = b.dev_lists = false;
     b.depth_on = false;
     b.n_runs = 0;
+    b.ref_on = false;
+    b.n_blocks = 0;
     for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
     if (n_regions == 0) {
         b.depth_on = e->n_depth_bins > 0;         // (no region: no run, no total)
         b.depth_bins = e->n_depth_bins;
+        b.ref_on = e->n_ref_bands > 0;
+        b.ref_bands = e->n_ref_bands;
         return PA_OK;
     }
     const auto t_begin = std::chrono::steady_clock::now();
@@ -2683,6 +2866,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.dev_lists = false;
     b.ms[12] = 0;
     b.ms[13] = 0;
+    b.ms[14] = 0;
     if (w.dev) ENC_HIP(hipMemcpyAsync(b.d_rules.p, b.h_rules.p, (size_t)n_regions * sizeof(pa_cand::Rule), hipMemcpyHostToDevice, st));
     int* host_counters = w.host_counters;
     bool on_device = false;           // this call's candidates were enumerated by the kernels
@@ -2690,6 +2874,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         rc = submit_counts(e, w);
         if (rc == PA_OK && w.dev) rc = submit_candidates(e, w);
         if (rc == PA_OK) rc = submit_depth_runs(e, w);
+        if (rc == PA_OK) rc = submit_ref_blocks(e, w);
         if (rc != PA_OK) return rc;
         ENC_HIP(hipMemcpyAsync(host_counters, w.counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
         ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2723,6 +2908,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     }
     rc = check_reports(e, w);
     if (rc == PA_OK) rc = finish_depth_runs(e, w);
+    if (rc == PA_OK) rc = finish_ref_blocks(e);
     if (rc == PA_OK) rc = on_device ? take_device_results(e, w, n_candidates) : enumerate_on_host(e, w, n_candidates);
     if (rc != PA_OK) return rc;
     b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();  // whole run, host clock
@@ -3341,6 +3527,85 @@ int pa_encoder_depth_calls(pa_encoder* e, int64_t* runs_with_bins, int64_t* over
     return PA_OK;
 }
 
+int pa_encoder_set_ref_confidence(pa_encoder* e, const uint8_t* table, int32_t table_side, int32_t n_bands, const int32_t* lower) {
+    if (!e || n_bands < 0 || (n_bands > 0 && (!lower || !table))) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (n_bands == 0) {
+        e->n_ref_bands = 0;
+        e->ref_block_cap = 0;
+        return PA_OK;
+    }
+    // (checked in full before anything of the handle changes)
+    if (table_side != REFCONF_SIDE)
+        return pa::set_error(PA_ERR_INVALID, "reference confidence: a table of side " + std::to_string(table_side) + ", not " +
+                                                 std::to_string(REFCONF_SIDE));
+    if (n_bands > REFCONF_MAX_BANDS)
+        return pa::set_error(PA_ERR_INVALID, "reference confidence: band 8 is one more than the 8 bands a table may have");
+    for (int32_t k = 0; k < n_bands; ++k)
+        if (k == 0 ? lower[0] != 0 : (lower[k] <= lower[k - 1] || lower[k] > 255))
+            return pa::set_error(PA_ERR_INVALID, "reference confidence: band " + std::to_string(k) +
+                                                     (k == 0 ? " must start at 0" : lower[k] > 255 ? " is above 255, the largest GQ a table holds"
+                                                                                                   : " is not above the one before it"));
+    if (table[0] != 0) return pa::set_error(PA_ERR_INVALID, "reference confidence: table entry (0, 0) must be 0: no read, no confidence");
+    // more reference reads never lower the confidence, more other reads never raise it
+    for (int r = 0; r < REFCONF_SIDE; ++r)
+        for (int a = 0; a < REFCONF_SIDE; ++a) {
+            const int v = table[r * REFCONF_SIDE + a];
+            if ((r > 0 && v < table[(r - 1) * REFCONF_SIDE + a]) || (a > 0 && v > table[r * REFCONF_SIDE + a - 1]))
+                return pa::set_error(PA_ERR_INVALID, "reference confidence: table entry (" + std::to_string(r) + ", " + std::to_string(a) +
+                                                         ") is not monotone: GQ rises with n_ref and falls with n_alt");
+        }
+    ENC_HIP(hipSetDevice(e->device));
+    ENC_HIP(hipStreamSynchronize(e->stream));      // (no run of the handle reads the table while it changes)
+    ENC_ALLOC(e->d_gq_table, (size_t)REFCONF_SIDE * REFCONF_SIDE);
+    ENC_HIP(hipMemcpyAsync(e->d_gq_table.p, table, (size_t)REFCONF_SIDE * REFCONF_SIDE, hipMemcpyHostToDevice, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    e->n_ref_bands = n_bands;
+    for (int32_t k = 0; k < REFCONF_MAX_BANDS; ++k) e->ref_lower[k] = k < n_bands ? lower[k] : 0;
+    const char* cap = getenv("PEPPER_AMD_REF_BLOCK_CAP");      // (debug: tests/test_gpu_refconf.py makes a run overflow with it)
+    e->ref_block_cap = cap ? std::max<int64_t>(0, atoll(cap)) : 0;
+    return PA_OK;
+}
+
+int pa_encoder_ref_blocks(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* band, int32_t* min_dp,
+                          int32_t* min_gq, int64_t* n_blocks) {
+    if (!e || capacity < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
+    if (!e->variant || !e->variant->ref_on)
+        return pa::set_error(PA_ERR_INVALID, "reference blocks: the handle's last run had no reference-confidence table set");
+    pa_variant_batch& b = *e->variant;
+    if (n_blocks) *n_blocks = b.n_blocks;
+    if (!region && !start && !end && !band && !min_dp && !min_gq) return PA_OK;
+    if (capacity < b.n_blocks)
+        return pa::set_error(PA_ERR_INVALID, "reference blocks: " + std::to_string(b.n_blocks) + " blocks, room for " + std::to_string(capacity));
+    if (b.n_blocks == 0) return PA_OK;
+    ENC_HIP(hipSetDevice(e->device));
+    std::vector<RefBlock> blocks((size_t)b.n_blocks);
+    ENC_HIP(hipMemcpyAsync(blocks.data(), b.d_blocks.p, blocks.size() * sizeof(RefBlock), hipMemcpyDeviceToHost, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < blocks.size(); ++k) {
+        const RefBlock& r = blocks[k];
+        if (r.region < 0 || r.region >= (int)b.regs.size() || (k > 0 && r.region < blocks[k - 1].region))
+            return pa::set_error(PA_ERR_HIP, "reference blocks: record " + std::to_string(k) + " names no region of the batch");
+        const RegHost& rh = b.regs[(size_t)r.region];
+        // a block ends where the next one of its region starts, the last one behind the window's last row
+        const int64_t window_end = std::min<int64_t>(rh.L - 1, rh.q.candidate_region_end - rh.p.region_start) + 1;
+        const int64_t stop = (k + 1 < blocks.size() && blocks[k + 1].region == r.region) ? blocks[k + 1].row : window_end;
+        if (region) region[k] = r.region;
+        if (start) start[k] = rh.p.region_start + r.row;
+        if (end) end[k] = rh.p.region_start + stop;
+        if (band) band[k] = r.band == DEPTH_OFF_TARGET ? -1 : r.band;
+        if (min_dp) min_dp[k] = r.min_dp;
+        if (min_gq) min_gq[k] = r.min_gq;
+    }
+    return PA_OK;
+}
+
+int pa_encoder_ref_calls(pa_encoder* e, int64_t* runs, int64_t* overflows) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (runs) *runs = e->variant ? e->variant->ref_calls : 0;
+    if (overflows) *overflows = e->variant ? e->variant->ref_overflows : 0;
+    return PA_OK;
+}
+
 int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host) {
     if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
     if (on_device) *on_device = e->variant ? e->variant->dev_calls : 0;
@@ -3439,7 +3704,7 @@ const int8_t* pa_encoder_device_images(pa_encoder* e) {
 
 int pa_encoder_last_timing(pa_encoder* e, double* ms, int32_t n) {
     if (!e || !ms || n < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 14) ? e->variant->ms[i] : 0.0;
+    for (int i = 0; i < n; ++i) ms[i] = (e->variant && i < 15) ? e->variant->ms[i] : 0.0;
     return PA_OK;
 }
 

@@ -159,7 +159,7 @@ struct pa_encoder {
     int device = 0;
     hipStream_t stream = nullptr;
     bool own_stream = false;
-    hipEvent_t ev[14] = {};                        // ([12], [13]: around the depth-run kernels)
+    hipEvent_t ev[16] = {};                        // ([12], [13]: around the depth-run kernels; [14], [15]: around the reference-block kernels)
     pa_variant_batch* variant = nullptr;
     pa_polish_batch* polish = nullptr;
     struct pa_realigner* realigner = nullptr;      // the polish image chain's re-aligner on this encoder's stream (made on first use)
@@ -170,6 +170,10 @@ struct pa_encoder {
     int32_t n_depth_bins = 0;                      // pa_encoder_set_depth_bins: bins of the depth classes (0: the feature is off) ...
     int32_t depth_lower[8] = {};                   // ... and their ascending lower bounds, depth_lower[0] == 0
     int64_t depth_run_cap = 0;                     // ... PEPPER_AMD_DEPTH_RUN_CAP as that call read it (0: sized by the batch)
+    int32_t n_ref_bands = 0;                       // pa_encoder_set_ref_confidence: bands of the reference blocks (0: the feature is off) ...
+    int32_t ref_lower[8] = {};                     // ... their ascending lower bounds of GQ, ref_lower[0] == 0 ...
+    pa_enc::DBuf d_gq_table;                       // ... the 101 x 101 uint8 table [n_ref][n_alt] -> GQ on the device ...
+    int64_t ref_block_cap = 0;                     // ... PEPPER_AMD_REF_BLOCK_CAP as that call read it (0: sized by the batch)
     std::vector<int64_t> seq_off;                  // pa_encoder_set_seq_offsets: per packed read of the NEXT staging where its bases lie (-1: behind its operations)
 };
 

@@ -52,6 +52,10 @@ def call_variant(options):
     options.image_output_directory = image_output_directory
     # (options.coverage_bed: image generation writes PEPPER_VARIANT_COVERAGE.bed beside the VCFs, not among the images)
     options.coverage_output_directory = output_dir
+    # (options.gvcf: image generation hands the run's reference blocks over here; the gVCF is written behind step 3.  The
+    # hook is taken off the options again before anything pickles them for another process)
+    gvcf_tracks = []
+    options.gvcf_take = gvcf_tracks.append
     walls = getattr(options, "stage_walls", None)           # a dict the caller wants the three steps' wall times in
     precomputed = None
     t0 = time.perf_counter()
@@ -78,6 +82,7 @@ def call_variant(options):
         try:
             ImageGenerationUtils.generate_images(options)
         finally:
+            del options.gvcf_take
             sink, options.fused_sink = options.fused_sink, None
             # (an image worker that raised: the predictions written so far are withdrawn, not published under the final name)
             sink.close(failed=sys.exc_info()[0] is not None)
@@ -96,7 +101,10 @@ def call_variant(options):
                 _log("INFO: FUSED: " + str(len(sink.segments)) + " OF " + str(sink.batch_no) + " BATCHES SELECTED AHEAD OF STEP 3")
         t1 = t2 = time.perf_counter()
     else:
-        ImageGenerationUtils.generate_images(options)
+        try:
+            ImageGenerationUtils.generate_images(options)
+        finally:
+            del options.gvcf_take
         t1 = time.perf_counter()
 
         _log("STEP 2/3 RUNNING INFERENCE")
@@ -108,6 +116,14 @@ def call_variant(options):
     _log("OUTPUT: " + str(candidate_output_directory))
     totals = process_candidates(options, prediction_output_directory, candidate_output_directory,
                                 precomputed=precomputed if fused else None, segments=segments)
+    if gvcf_tracks:
+        from pepper_amd.variant import Gvcf
+        from pepper_amd.variant.fasta import FASTA_handler
+        t3 = time.perf_counter()
+        Gvcf.write_gvcf(candidate_output_directory + "PEPPER_VARIANT_FULL.vcf.gz", candidate_output_directory + Gvcf.GVCF_NAME,
+                        gvcf_tracks[0], FASTA_handler(options.fasta), log=_log)
+        if walls is not None:
+            walls["gvcf"] = time.perf_counter() - t3
     if walls is not None:
         walls.update(make_images=t1 - t0, run_inference=t2 - t1, find_candidates=time.perf_counter() - t2)
 

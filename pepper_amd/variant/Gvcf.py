@@ -1,0 +1,114 @@
+"""The gVCF of a call_variant run (options.gvcf): the records of PEPPER_VARIANT_FULL.vcf.gz and, between them, blocks of
+non-variant positions with a reference-confidence GQ and a MIN_DP.
+
+The blocks are what the encoder reported while it made the images (pepper_amd/variant/RefConfidence.py: a read-count model,
+not the network's output); the records are read back from the finished FULL file, so whichever of the three record-writing
+paths made it, this module does not touch it.  Every record is copied verbatim; no <NON_REF> allele is added to it (its
+Number=A fields would need a value for that allele).  Blocks are cut around the records' REF spans: a piece keeps the minima
+of the block it was cut from, which are then lower bounds for it.
+
+A block line:  CHROM POS . <ref base> <NON_REF> . . END=<end> GT:GQ:MIN_DP 0/0:<min GQ>:<min DP>  (./. where MIN_DP is 0).
+Contigs in FASTA order, positions ascending."""
+import gzip
+
+from pepper_amd.variant.bgzf import BgzfWriter, TabixBuilder
+
+GVCF_NAME = "PEPPER_VARIANT_FULL.g.vcf.gz"
+EXTRA_HEADER = ('##ALT=<ID=NON_REF,Description="Represents any possible alternative allele at this location">\n'
+                '##INFO=<ID=END,Number=1,Type=Integer,Description="End position (for use with symbolic alleles)">\n'
+                '##FORMAT=<ID=MIN_DP,Number=1,Type=Integer,Description="Minimum depth of the positions of a reference block">\n')
+
+
+def read_vcf(path):
+    """A (BGZF or gzip) VCF -> (header text up to and without the #CHROM line, the #CHROM line, [(contig, pos0, len(REF), line)])
+    in file order, lines as bytes with their newline."""
+    meta, columns, records = [], b"", []
+    with gzip.open(path, "rb") as fh:
+        for line in fh:
+            if line.startswith(b"##"):
+                meta.append(line)
+            elif line.startswith(b"#"):
+                columns = line
+            elif line.strip():
+                fields = line.split(b"\t", 4)
+                records.append((fields[0].decode(), int(fields[1]) - 1, len(fields[3]), line if line.endswith(b"\n") else line + b"\n"))
+    return b"".join(meta).decode(), columns.decode(), records
+
+
+def header_text(meta, columns):
+    present = set(meta.splitlines())
+    extra = "".join(line + "\n" for line in EXTRA_HEADER.splitlines() if line not in present)
+    return meta + extra + columns
+
+
+def block_line(contig, start, end, ref_base, min_dp, min_gq):
+    """start, end: 0-based, half-open -> the line, bytes."""
+    genotype = "0/0" if min_dp > 0 else "./."
+    return ("%s\t%d\t.\t%s\t<NON_REF>\t.\t.\tEND=%d\tGT:GQ:MIN_DP\t%s:%d:%d\n"
+            % (contig, start + 1, ref_base, end, genotype, min_gq, min_dp)).encode()
+
+
+def compose(contigs, blocks, records, ref_base):
+    """contigs: names in FASTA order; blocks: [(contig, start, end, band, min_dp, min_gq)], 0-based half-open, disjoint (what
+    RefConfidence.BlockTrack.finish returns); records: what read_vcf returns; ref_base(contig, pos0) -> the reference letter.
+    -> [(contig, start, end, line, is_record)] in output order: per contig the records in position order (equal positions in
+    file order) and the pieces of the blocks that no record's REF span covers."""
+    order = {name: k for k, name in enumerate(contigs)}
+    for contig, _pos, _n, _line in records:
+        if contig not in order:
+            raise ValueError("gvcf: the record's contig %r is not in the FASTA" % (contig,))
+    per_contig_records = {}
+    for k, (contig, pos, n, line) in enumerate(records):
+        per_contig_records.setdefault(contig, []).append((pos, k, n, line))
+    per_contig_blocks = {}
+    for block in blocks:
+        per_contig_blocks.setdefault(block[0], []).append(block)
+    out = []
+    for contig in contigs:
+        recs = sorted(per_contig_records.get(contig, []))
+        spans = []                                   # the union of the records' REF spans, ascending and disjoint
+        for pos, _k, n, _line in recs:
+            if spans and pos <= spans[-1][1]:
+                spans[-1][1] = max(spans[-1][1], pos + n)
+            else:
+                spans.append([pos, pos + n])
+        entries = [(pos, 1, k, contig, pos, pos + n, line) for pos, k, n, line in recs]
+        at = 0
+        for _c, start, end, _band, min_dp, min_gq in sorted(per_contig_blocks.get(contig, []), key=lambda b: b[1]):
+            while at < len(spans) and spans[at][1] <= start:
+                at += 1
+            cursor, k = start, at
+            while cursor < end:
+                if k < len(spans) and spans[k][0] <= cursor:
+                    cursor = max(cursor, spans[k][1])
+                    k += 1
+                    continue
+                stop = min(end, spans[k][0]) if k < len(spans) else end
+                entries.append((cursor, 0, 0, contig, cursor, stop, block_line(contig, cursor, stop, ref_base(contig, cursor), min_dp, min_gq)))
+                cursor = stop
+        entries.sort(key=lambda e: e[:3])
+        out += [(c, s, e, line, bool(is_record)) for _p, is_record, _k, c, s, e, line in entries]
+    return out
+
+
+def write_gvcf(full_vcf_path, out_path, track, fasta_handler, log=None):
+    """PEPPER_VARIANT_FULL.vcf.gz and the run's block track -> out_path and out_path + '.tbi'; -> (records, block lines)."""
+    meta, columns, records = read_vcf(full_vcf_path)
+    blocks = track.finish()
+
+    def ref_base(contig, pos):
+        return fasta_handler.get_reference_bytes(contig, pos, pos + 1).decode() or "N"
+
+    entries = compose(track.contigs, blocks, records, ref_base)
+    out, index = BgzfWriter(out_path, deferred=True), TabixBuilder()
+    out.write(header_text(meta, columns))
+    for contig, start, end, line, _is_record in entries:
+        vbeg = out.tell()
+        out.write(line)
+        index.add(contig, start, end, vbeg, out.tell())
+    out.close()
+    index.write(out_path + ".tbi", resolve=out.resolve)
+    n_blocks = sum(1 for e in entries if not e[4])
+    if log is not None:
+        log("INFO: GVCF: " + str(len(records)) + " RECORDS AND " + str(n_blocks) + " REFERENCE BLOCKS WRITTEN TO " + out_path)
+    return len(records), n_blocks

@@ -19,7 +19,7 @@ from datetime import datetime
 
 import numpy as np
 
-from pepper_amd.variant import Coverage, Targets
+from pepper_amd.variant import Coverage, RefConfidence, Targets
 from pepper_amd.variant.AlignmentSummarizer import AlignmentSummarizer
 from pepper_amd.variant.DataStore import DataStore
 
@@ -208,6 +208,13 @@ class ImageGenerationUtils:
         if track is not None:
             mine.update(coverage_calls=0, coverage_runs=0, coverage_overflows=0)
 
+        # ... and, with options.gvcf (gtrack: the job's RefConfidence.BlockTrack), the encoder calls of either form that ran with
+        # a reference-confidence table set, the block records they reported, the calls whose records outgrew the device's
+        # buffer and the event time of the block kernels
+        gtrack = getattr(options, "gvcf_track", None)
+        if gtrack is not None:
+            mine.update(gvcf_calls=0, gvcf_records=0, gvcf_overflows=0, gvcf_kernel_ms=0.0)
+
         def lap(key, t0):
             now = time.perf_counter()
             mine[key] = mine.get(key, 0.0) + now - t0
@@ -233,23 +240,55 @@ class ImageGenerationUtils:
             track.add(chr_name, (_start, _end), Coverage.runs_numpy(zeros, _start, track.bins, on_target),
                       Coverage.totals_numpy(zeros, track.bins, on_target))
 
+        def collect_blocks(source, group):
+            """The reference blocks of the encoder call that covered `group` (source: the PackedEncoder, or what
+            thread_ref_confidence yields), interval by interval into the gVCF's track (which merges the records of a run that
+            crossed a tile border)."""
+            region, starts, ends, band, min_dp, min_gq = source.ref_blocks()
+            cut = np.searchsorted(region, np.arange(len(group) + 1))          # (the records come in region order)
+            for r, (chr_name, _start, _end) in enumerate(group):
+                a, b = int(cut[r]), int(cut[r + 1])
+                gtrack.add(chr_name, (_start, _end), (starts[a:b], ends[a:b], band[a:b], min_dp[a:b], min_gq[a:b]))
+            mine["gvcf_records"] += len(region)
+            mine["gvcf_kernel_ms"] += source.ref_blocks_ms()
+
+        def empty_blocks(chr_name, _start, _end):
+            """An interval without a read is never encoded by the host-clipped form: depth 0 and GQ 0 at every position."""
+            on_target = None
+            if bed_list is not None:
+                on_target = Targets.contains(*Targets.table(bed_list, chr_name), np.arange(_start, _end + 1, dtype=np.int64))
+            gtrack.add_empty(chr_name, (_start, _end), on_target)
+
         def summaries_of(prepared, group):
-            """create_summaries of one host-clipped call; with a track, under this thread's depth bins and collected."""
-            if track is None:
+            """create_summaries of one host-clipped call; with a track, under this thread's depth bins and collected, with a
+            gVCF track under this thread's reference-confidence table likewise."""
+            if track is None and gtrack is None:
                 return create_summaries(prepared)
-            from pepper_amd.variant.PEPPER_VARIANT import thread_depth_bins
+            from pepper_amd.variant.PEPPER_VARIANT import thread_depth_bins, thread_ref_confidence
             live = [g for g, p in zip(group, prepared) if p is not None]
-            with thread_depth_bins(track.bins, device) as depth:
-                before = depth.depth_calls()
+            with contextlib.ExitStack() as stack:
+                depth = stack.enter_context(thread_depth_bins(track.bins, device)) if track is not None else None
+                conf = stack.enter_context(thread_ref_confidence(gtrack.table, gtrack.bands, device)) if gtrack is not None else None
+                before = depth.depth_calls() if depth is not None else None
+                conf_before = conf.ref_calls() if conf is not None else None
                 outs = create_summaries(prepared)
-                if live:
+                if live and depth is not None:
                     collect_depth(depth, live)
-                after = depth.depth_calls()
-            mine["coverage_calls"] += after[0] - before[0]
-            mine["coverage_overflows"] += after[1] - before[1]
+                if live and conf is not None:
+                    collect_blocks(conf, live)
+                if depth is not None:
+                    after = depth.depth_calls()
+                    mine["coverage_calls"] += after[0] - before[0]
+                    mine["coverage_overflows"] += after[1] - before[1]
+                if conf is not None:
+                    conf_after = conf.ref_calls()
+                    mine["gvcf_calls"] += conf_after[0] - conf_before[0]
+                    mine["gvcf_overflows"] += conf_after[1] - conf_before[1]
             for g, p in zip(group, prepared):
-                if p is None:
+                if p is None and track is not None:
                     empty_depth(*g)
+                if p is None and gtrack is not None:
+                    empty_blocks(*g)
             return outs
 
         sink = getattr(options, "fused_sink", None)         # call_variant's fused form: predictions straight from the encoder's windows
@@ -366,6 +405,9 @@ class ImageGenerationUtils:
                 if track is not None:
                     enc.set_depth_bins(track.bins)
                     depth_before = enc.depth_calls()
+                if gtrack is not None:
+                    enc.set_ref_confidence(gtrack.table, gtrack.bands)
+                    conf_before = enc.ref_calls()
                 while g0 < len(intervals):
                     group = intervals[g0:adjacent_run(intervals, g0, batch, 2 * safe)]
                     chr_name = group[0][0]
@@ -408,6 +450,8 @@ class ImageGenerationUtils:
                         continue
                     if track is not None:
                         collect_depth(enc, group)
+                    if gtrack is not None:
+                        collect_blocks(enc, group)
                     t0 = lap("encode", t0)
                     mine["encoder_calls"] += 1
                     mine["target_calls"] += 1 if bed_list is not None else 0
@@ -453,6 +497,11 @@ class ImageGenerationUtils:
                     mine["coverage_calls"] += depth_after[0] - depth_before[0]
                     mine["coverage_overflows"] += depth_after[1] - depth_before[1]
                     enc.set_depth_bins(None)
+                if gtrack is not None:               # (... nor this job's reference-confidence table)
+                    conf_after = enc.ref_calls()
+                    mine["gvcf_calls"] += conf_after[0] - conf_before[0]
+                    mine["gvcf_overflows"] += conf_after[1] - conf_before[1]
+                    enc.set_ref_confidence(None, None)
             t_close = time.perf_counter()
         lap("close", t_close)
         merge_stats(stats, mine)
@@ -491,6 +540,16 @@ class ImageGenerationUtils:
             bins, labels = Coverage.parse_bins(getattr(options, "coverage_bins", None), options.min_coverage_threshold)
             track = Coverage.CoverageTrack(fasta_handler.get_chromosome_names(), bins, labels)
             options.coverage_track = track
+        # options.gvcf (or PEPPER_AMD_GVCF=1): the reference blocks of every position the run looks at, reported by the encoder
+        # beside its candidates (pepper_amd/variant/RefConfidence.py); the workers find the track on the options while they
+        # run, call_variant finds it there afterwards and writes the gVCF behind step 3 (pepper_amd/variant/Gvcf.py)
+        gtrack = None
+        if getattr(options, "gvcf", None) or os.environ.get("PEPPER_AMD_GVCF") == "1":
+            rate = getattr(options, "gvcf_error_rate", None)
+            table = RefConfidence.build_table(RefConfidence.DEFAULT_ERROR_RATE if rate is None else rate)
+            gtrack = RefConfidence.BlockTrack(fasta_handler.get_chromosome_names(), RefConfidence.parse_bands(getattr(options, "gvcf_bands", None)),
+                                              table)
+            options.gvcf_track = gtrack
         try:
             if options.threads <= 1:
                 ImageGenerationUtils.generate_image_and_save_to_file(options, all_intervals, bed_list, 0)
@@ -504,10 +563,17 @@ class ImageGenerationUtils:
         finally:
             if track is not None:
                 del options.coverage_track
+            if gtrack is not None:
+                del options.gvcf_track
         if track is not None:
             coverage_dir = getattr(options, "coverage_output_directory", None) or options.image_output_directory
             runs = track.write(ImageGenerationUtils.handle_output_directory(coverage_dir) + Coverage.BED_NAME)
             _log("INFO: " + track.log_line(runs))
+        if gtrack is not None:
+            _log("INFO: " + gtrack.log_line())
+            take = getattr(options, "gvcf_take", None)       # call_variant's: it writes the gVCF behind step 3
+            if take is not None:
+                take(gtrack)
         _log("INFO: FINISHED IMAGE GENERATION")
         secs = int(time.time() - start_time)
         _log("INFO: TOTAL ELAPSED TIME FOR GENERATING IMAGES: " + str(secs // 60) + " Min " + str(secs % 60) + " Sec")

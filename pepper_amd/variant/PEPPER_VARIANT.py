@@ -215,6 +215,75 @@ def thread_depth_bins(bins, device=0):
         _send_depth_bins(lib, enc, None)
 
 
+def _send_ref_confidence(lib, enc, table, bands):
+    """pa_encoder_set_ref_confidence: the 101 x 101 uint8 table of pepper_amd/variant/RefConfidence.py build_table and ascending
+    lower bounds of GQ starting at 0 (parse_bands); bands None: off."""
+    if bands is None or len(bands) == 0:
+        _lib.check(lib.pa_encoder_set_ref_confidence(enc, None, 0, 0, None))
+        return
+    table = np.ascontiguousarray(table, np.uint8)
+    if table.ndim != 2 or table.shape[0] != table.shape[1]:
+        raise ValueError("reference confidence: the table must be square, not %r" % (table.shape,))
+    lower = np.ascontiguousarray(bands, np.int32)
+    _lib.check(lib.pa_encoder_set_ref_confidence(enc, table.ctypes.data, table.shape[0], len(lower), lower.ctypes.data))
+
+
+def _ref_blocks(lib, enc):
+    """pa_encoder_ref_blocks -> (region int32, start int64, end int64, band int32, min_dp int32, min_gq int32) of the handle's
+    last run: every region's records in region and position order, contig coordinates, ends half-open, band -1 outside the
+    targets; a run that crosses a tile border comes as one record per tile (RefConfidence.merge_blocks joins them)."""
+    n = ctypes.c_int64()
+    _lib.check(lib.pa_encoder_ref_blocks(enc, 0, None, None, None, None, None, None, ctypes.byref(n)))
+    k = max(1, n.value)
+    region, start, end = np.zeros(k, np.int32), np.zeros(k, np.int64), np.zeros(k, np.int64)
+    band, min_dp, min_gq = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
+    _lib.check(lib.pa_encoder_ref_blocks(enc, k, region.ctypes.data, start.ctypes.data, end.ctypes.data, band.ctypes.data,
+                                         min_dp.ctypes.data, min_gq.ctypes.data, ctypes.byref(n)))
+    return tuple(v[:n.value] for v in (region, start, end, band, min_dp, min_gq))
+
+
+def _ref_calls(lib, enc):
+    made, overflows = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(lib.pa_encoder_ref_calls(enc, ctypes.byref(made), ctypes.byref(overflows)))
+    return made.value, overflows.value
+
+
+def _ref_blocks_ms(lib, enc):
+    ms = np.zeros(15, np.float64)
+    _lib.check(lib.pa_encoder_last_timing(enc, ms.ctypes.data, 15))
+    return float(ms[14])
+
+
+class _ThreadRefConfidence(object):
+    """What thread_ref_confidence yields: the reference blocks and counters of this thread's encoder, under the names
+    PackedEncoder gives them."""
+
+    def __init__(self, lib, enc):
+        self.lib, self.enc = lib, enc
+
+    def ref_blocks(self):
+        return _ref_blocks(self.lib, self.enc)
+
+    def ref_calls(self):
+        return _ref_calls(self.lib, self.enc)
+
+    def ref_blocks_ms(self):
+        return _ref_blocks_ms(self.lib, self.enc)
+
+
+@contextlib.contextmanager
+def thread_ref_confidence(table, bands, device=0):
+    """This thread's encoder on `device` with a reference-confidence table set for the calls inside
+    (pa_encoder_set_ref_confidence) and without it again behind: the handle outlives the job.  Yields an object whose
+    ref_blocks() / ref_calls() / ref_blocks_ms() speak of that handle's last run."""
+    lib, enc = _encoder(device)
+    _send_ref_confidence(lib, enc, table, bands)
+    try:
+        yield _ThreadRefConfidence(lib, enc)
+    finally:
+        _send_ref_confidence(lib, enc, None, None)
+
+
 def flatten_reads(reads):
     """type_read-like objects -> the flat arrays of pa_pileup."""
     n = len(reads)
@@ -330,6 +399,10 @@ class StagedBatch(object):
         _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 14))
         return float(ms[13])
 
+    def ref_blocks_ms(self):
+        """Event time of the reference-block kernels of the last run (pa_encoder_last_timing [14]; 0 without a table)."""
+        return _ref_blocks_ms(self.lib, self.enc)
+
     def stats(self):
         v = np.zeros(6, np.int64)
         _lib.check(self.lib.pa_encoder_batch_stats(self.enc, v.ctypes.data, 6))
@@ -414,6 +487,7 @@ class PackedEncoder(object):
                     enc = cls._idle.pop(k)
                     enc.set_targets(None)        # (whatever job had it last: its targets are not this one's)
                     enc.set_depth_bins(None)     # (... nor its depth bins)
+                    enc.set_ref_confidence(None, None)       # (... nor its reference-confidence table)
                     return enc
         size = arena_bytes
         while True:
@@ -512,6 +586,23 @@ class PackedEncoder(object):
     def depth_calls(self):
         """-> (runs made with depth bins set, runs among them whose records were emitted twice) since this handle was created."""
         return _depth_calls(self.lib, self.enc)
+
+    def set_ref_confidence(self, table, bands):
+        """Reference blocks of this handle's next runs (pa_encoder_set_ref_confidence): RefConfidence.build_table's table and
+        ascending lower bounds of GQ starting at 0; bands None: off."""
+        _send_ref_confidence(self.lib, self.enc, table, bands)
+
+    def ref_blocks(self):
+        """-> (region, start, end, band, min_dp, min_gq) of the last run's reference blocks (pa_encoder_ref_blocks)."""
+        return _ref_blocks(self.lib, self.enc)
+
+    def ref_calls(self):
+        """-> (runs made with a table set, runs among them whose records were emitted twice) since this handle was created."""
+        return _ref_calls(self.lib, self.enc)
+
+    def ref_blocks_ms(self):
+        """Event time of the reference-block kernels of the last run (pa_encoder_last_timing [14]; 0 without a table)."""
+        return _ref_blocks_ms(self.lib, self.enc)
 
     def candidate_calls(self):
         """-> (runs enumerated on the device, runs handed back to the host) since this handle was created."""

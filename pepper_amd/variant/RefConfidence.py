@@ -1,0 +1,226 @@
+"""Reference confidence of the positions a run looked at (options.gvcf): the non-variant blocks of the gVCF.
+
+A position without a record in the VCF may be one where the reads agree with the reference, or one where nothing could be
+seen.  The encoder holds what tells them apart once per run: with a reference-confidence table set
+(pa_encoder_set_ref_confidence) tile_count_kernel turns the counters of every position into a GQ byte and ref_blocks_kernel
+(pepper_amd/csrc/encoder.hip) run-length encodes the GQ bands of every candidate window, with the smallest depth and the
+smallest GQ of each run.  This module states the rule once, in numpy, builds the table the device looks up, and collects the
+workers' blocks (BlockTrack); pepper_amd/variant/Gvcf.py writes the file.
+
+Evidence of a position, from the tile kernel's counters before the int8 clamp (F[s] / R[s]: forward / reverse slot of symbol s):
+    cov      the coverage, the number the depth track reports (pepper_amd/variant/Coverage.py)
+    ref_col  F + R of the reference letter, 0 where the reference base is not one of ACGT
+    ins      F + R of the insert anchor,  star  F + R of `*`
+    n_ref = max(0, ref_col - ins),  n_alt = max(0, cov - ref_col) + min(ins, ref_col) + star
+Reads that show the reference letter and open no insert behind it speak for the reference; other letters, insert anchors and
+deleted bases (which are not part of cov) against it.  With n = n_ref + n_alt > 100 both are rescaled as DeepVariant does,
+n_ref' = (100 n_ref + n - 1) // n, n_alt' = 100 - n_ref'.
+
+GQ is DeepVariant's published reference-confidence model with its defaults: the log10 likelihoods of hom-ref, het and hom-alt
+under a per-read error rate p, normalised, GQ = floor(min(max_gq, -10 log10(1 - P(hom-ref)))).  It is a model of read counts
+and not the network's output, and nobody has calibrated p for nanopore reads here: it is a parameter (options.gvcf_error_rate).
+"""
+import math
+import threading
+
+import numpy as np
+
+MAX_BANDS = 8
+OFF_TARGET = -1                      # the band of a position outside every target (pa_encoder_set_targets): never written
+TABLE_SIDE = 101                     # counts 0 .. 100 after the rescale
+RESCALE_TO = 100
+DEFAULT_ERROR_RATE = 0.001
+DEFAULT_MAX_GQ = 50
+DEFAULT_BANDS = (0, 1, 10, 20, 30, 40, 50)
+
+
+def _log10_sum(*terms):
+    top = max(terms)
+    return top + math.log10(sum(10.0 ** (t - top) for t in terms))
+
+
+def gq_value(n_ref, n_alt, p=DEFAULT_ERROR_RATE, max_gq=DEFAULT_MAX_GQ):
+    """The GQ of n_ref reads for the reference and n_alt against it (after the rescale), in f64.  (0, 0) -> 0."""
+    if n_ref == 0 and n_alt == 0:
+        return 0
+    hom_ref = n_ref * math.log10(1.0 - p) + n_alt * math.log10(p)
+    het = -(n_ref + n_alt) * math.log10(2.0)
+    hom_alt = n_ref * math.log10(p) + n_alt * math.log10(1.0 - p)
+    # log10(1 - P(hom-ref)) as the log-sum of the other two terms over the log-sum of all three: no subtraction from 1
+    log_not_ref = _log10_sum(het, hom_alt) - _log10_sum(hom_ref, het, hom_alt)
+    return int(math.floor(min(float(max_gq), -10.0 * log_not_ref)))
+
+
+def build_table(p=DEFAULT_ERROR_RATE, max_gq=DEFAULT_MAX_GQ):
+    """-> uint8 [101, 101], row n_ref, column n_alt: what the device looks up.  ValueError: p outside (0, 0.5), max_gq outside
+    [0, 255]."""
+    p = float(p)
+    if not (0.0 < p < 0.5):
+        raise ValueError("reference confidence: error rate %r is not inside (0, 0.5)" % (p,))
+    if not (0 <= int(max_gq) <= 255) or int(max_gq) != max_gq:
+        raise ValueError("reference confidence: max_gq %r is not an integer in [0, 255]" % (max_gq,))
+    table = np.zeros((TABLE_SIDE, TABLE_SIDE), np.uint8)
+    for r in range(TABLE_SIDE):
+        for a in range(TABLE_SIDE):
+            table[r, a] = max(0, gq_value(r, a, p, int(max_gq)))
+    return table
+
+
+def parse_bands(bands=None):
+    """-> int32 lower bounds of GQ.  bands: None (DEFAULT_BANDS), a sequence of integers or their text "0,1,10,20".  ValueError,
+    naming the entry: more than 8 bands, none at all, a first bound that is not 0, a bound that is not above the one before it,
+    not an integer or above 255."""
+    if bands is None or (isinstance(bands, str) and bands.strip() == ""):
+        return np.array(DEFAULT_BANDS, np.int32)
+    fields = [f.strip() for f in bands.split(",")] if isinstance(bands, str) else list(bands)
+    if len(fields) == 0:
+        raise ValueError("gvcf bands: no band")
+    if len(fields) > MAX_BANDS:
+        raise ValueError("gvcf bands: entry %d is one more than the %d bands a table may have" % (MAX_BANDS, MAX_BANDS))
+    bounds = []
+    for k, field in enumerate(fields):
+        try:
+            if isinstance(field, (float, np.floating)) and float(field) != int(field):
+                raise ValueError
+            value = int(field)
+        except (TypeError, ValueError):
+            raise ValueError("gvcf bands: entry %d (%r) is not an integer" % (k, field)) from None
+        if k == 0 and value != 0:
+            raise ValueError("gvcf bands: entry 0 must be 0, not %d" % value)
+        if k > 0 and value <= bounds[-1]:
+            raise ValueError("gvcf bands: entry %d (%d) is not above the one before it (%d)" % (k, value, bounds[-1]))
+        if value > 255:
+            raise ValueError("gvcf bands: entry %d (%d) is above 255, the largest GQ a table holds" % (k, value))
+        bounds.append(value)
+    return np.array(bounds, np.int32)
+
+
+def band_labels(bands):
+    bounds = [int(b) for b in bands]
+    return ["GQ %d-%d" % (lo, hi - 1) for lo, hi in zip(bounds, bounds[1:])] + ["GQ %d+" % bounds[-1]]
+
+
+def evidence(cov, ref_col, ins, star):
+    """-> (n_ref, n_alt), int64, before the rescale."""
+    cov, ref_col, ins, star = (np.asarray(v, np.int64) for v in (cov, ref_col, ins, star))
+    n_ref = np.maximum(0, ref_col - ins)
+    n_alt = np.maximum(0, cov - ref_col) + np.minimum(ins, ref_col) + star
+    return n_ref, n_alt
+
+
+def rescale(n_ref, n_alt):
+    """Counts whose sum is above 100 brought to a sum of 100, in 64-bit integers, rounding n_ref up."""
+    n_ref, n_alt = np.asarray(n_ref, np.int64), np.asarray(n_alt, np.int64)
+    n = n_ref + n_alt
+    big = n > RESCALE_TO
+    safe = np.where(big, n, 1)
+    scaled = (RESCALE_TO * n_ref + safe - 1) // safe
+    return np.where(big, scaled, n_ref), np.where(big, RESCALE_TO - scaled, n_alt)
+
+
+def gq_numpy(cov, ref_col, ins, star, ref_is_acgt, table):
+    """The GQ byte of every position: the evidence, rescaled, looked up; 0 where the reference base is not one of ACGT."""
+    n_ref, n_alt = rescale(*evidence(cov, ref_col, ins, star))
+    gq = np.asarray(table, np.uint8)[n_ref, n_alt].astype(np.int32)
+    return np.where(np.asarray(ref_is_acgt, bool), gq, 0).astype(np.int32)
+
+
+def blocks_numpy(cov, gq, first_position, bands, on_target=None):
+    """The rule of ref_blocks_kernel without its tile borders: cov[i], gq[i] speak of position first_position + i ->
+    (starts, ends, band, min_dp, min_gq) of the maximal runs of equal band, ends half-open, each with the smallest cov and the
+    smallest gq of its positions.  on_target (bool per position; None: all): a position outside has the band OFF_TARGET."""
+    cov, gq = np.asarray(cov, np.int64), np.asarray(gq, np.int64)
+    which = (np.searchsorted(np.asarray(bands, np.int64), gq, side="right") - 1).astype(np.int32)
+    if on_target is not None:
+        which = np.where(np.asarray(on_target, bool), which, np.int32(OFF_TARGET)).astype(np.int32)
+    n = len(which)
+    if n == 0:
+        return (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32))
+    heads = np.flatnonzero(np.concatenate([[True], which[1:] != which[:-1]]))
+    starts = heads.astype(np.int64) + int(first_position)
+    ends = np.concatenate([heads[1:], [n]]).astype(np.int64) + int(first_position)
+    return (starts, ends, which[heads], np.minimum.reduceat(cov, heads).astype(np.int32),
+            np.minimum.reduceat(gq, heads).astype(np.int32))
+
+
+def merge_blocks(region, starts, ends, band, min_dp, min_gq):
+    """Touching records of one region and equal band joined, with the smaller of their minima: what the device reports one
+    record per tile for.  Records in region and position order -> the same six arrays, shorter."""
+    out = []
+    for rec in zip(*(np.asarray(v).tolist() for v in (region, starts, ends, band, min_dp, min_gq))):
+        if out and out[-1][0] == rec[0] and out[-1][2] == rec[1] and out[-1][3] == rec[3]:
+            last = out[-1]
+            out[-1] = (last[0], last[1], rec[2], last[3], min(last[4], rec[4]), min(last[5], rec[5]))
+        else:
+            out.append(rec)
+    cols = list(zip(*out)) if out else [[]] * 6
+    return tuple(np.array(c, t) for c, t in zip(cols, (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32)))
+
+
+class BlockTrack(object):
+    """The blocks of a whole job, collected from its workers in any order (add) and finished once.
+
+    contigs: the FASTA's contig names in its order; bands: what parse_bands returned; table: what build_table returned."""
+
+    def __init__(self, contigs, bands, table):
+        self.contigs = list(contigs)
+        self.order = {name: k for k, name in enumerate(self.contigs)}
+        self.bands = np.asarray(bands, np.int32)
+        self.table = np.ascontiguousarray(table, np.uint8)
+        self._lock = threading.Lock()
+        self._pieces = []
+
+    def add(self, contig, interval, blocks):
+        """One interval of the planner: interval = (pos_start, pos_end), both inclusive; blocks = (starts, ends, band, min_dp,
+        min_gq) of its window in contig coordinates, ascending."""
+        if contig not in self.order:
+            raise ValueError("block track: contig %r is not in the FASTA" % (contig,))
+        cols = [np.array(v, t) for v, t in zip(blocks, (np.int64, np.int64, np.int32, np.int32, np.int32))]
+        if len(set(len(c) for c in cols)) != 1:
+            raise ValueError("block track: blocks of unequal lengths")
+        with self._lock:
+            self._pieces.append((self.order[contig], int(interval[0]), int(interval[1]), contig) + tuple(cols))
+
+    def add_empty(self, contig, interval, on_target=None):
+        """An interval no encoder call covered because no read lies in it: depth 0 and GQ 0 at every position."""
+        zeros = np.zeros(int(interval[1]) - int(interval[0]) + 1, np.int64)
+        self.add(contig, interval, blocks_numpy(zeros, zeros, int(interval[0]), self.bands, on_target))
+
+    def finish_arrays(self):
+        """-> (contig index int64, start, end, band, min_dp, min_gq) of the finished blocks, in FASTA order, ends half-open: the
+        pieces ordered by contig and start; the position two consecutive intervals share belongs to the one that starts there
+        -- the earlier interval's blocks are cut at the next interval's start (a cut block keeps its minima: they are then
+        lower bounds) and dropped when nothing is left; off-target blocks dropped; touching blocks of equal band merged with
+        their minima.  Whole-array work: a job has a block every few positions where the reads are noisy."""
+        with self._lock:
+            pieces = sorted(self._pieces, key=lambda p: p[:3])
+        cols = [[], [], [], [], [], []]
+        for k, (rank, _s, _e, _contig, starts, ends, band, min_dp, min_gq) in enumerate(pieces):
+            if k + 1 < len(pieces) and pieces[k + 1][0] == pieces[k][0]:
+                ends = np.minimum(ends, pieces[k + 1][1])          # the next interval of the contig owns everything from its start
+            for col, v in zip(cols, (np.full(len(starts), rank, np.int64), starts, ends, band, min_dp, min_gq)):
+                col.append(v)
+        if not cols[0]:
+            return tuple(np.zeros(0, t) for t in (np.int64, np.int64, np.int64, np.int32, np.int32, np.int32))
+        rank, starts, ends, band, min_dp, min_gq = (np.concatenate(c) for c in cols)
+        keep = (starts < ends) & (band != OFF_TARGET)
+        rank, starts, ends, band, min_dp, min_gq = (v[keep] for v in (rank, starts, ends, band, min_dp, min_gq))
+        if len(rank) == 0:
+            return rank, starts, ends, band, min_dp, min_gq
+        joins = (rank[1:] == rank[:-1]) & (starts[1:] == ends[:-1]) & (band[1:] == band[:-1])
+        heads = np.flatnonzero(np.concatenate([[True], ~joins]))
+        last = np.concatenate([heads[1:], [len(rank)]]) - 1
+        return (rank[heads], starts[heads], ends[last], band[heads], np.minimum.reduceat(min_dp, heads), np.minimum.reduceat(min_gq, heads))
+
+    def finish(self):
+        """finish_arrays as [(contig, start, end, band, min_dp, min_gq)]."""
+        rank, starts, ends, band, min_dp, min_gq = self.finish_arrays()
+        names = [self.contigs[k] for k in rank.tolist()]
+        return list(zip(names, starts.tolist(), ends.tolist(), band.tolist(), min_dp.tolist(), min_gq.tolist()))
+
+    def log_line(self, arrays=None):
+        _rank, starts, ends, band, _dp, _gq = self.finish_arrays() if arrays is None else arrays
+        bases = np.bincount(band, weights=(ends - starts).astype(np.float64), minlength=len(self.bands)).astype(np.int64).tolist()
+        total = sum(bases)
+        parts = ["%s %d (%.4f)" % (label, n, n / total if total else 0.0) for label, n in zip(band_labels(self.bands), bases)]
+        return "GVCF: " + str(total) + " BASES IN " + str(len(band)) + " BLOCKS BEFORE THE RECORDS ARE CUT OUT: " + ", ".join(parts)

@@ -2,7 +2,7 @@
 through pepper_amd.variant.ImageGenerationUI.generate_images, the entry point of pepper_variant make_images / call_variant.
 
   python tools/bench_variant_images.py make_fast <dir> [genome_bases=64000000] [coverage=60] [seed] [level=1] [tags=0] [quals=0] [cg_ppm=0]    synthetic data set
-  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000] [downsample_rate=1.0] [--region-bed FILE]    GPU; one JSON line
+  python tools/bench_variant_images.py run <dir> [threads,threads,...] [region_size=100000] [downsample_rate=1.0] [--region-bed FILE] [--gvcf]    GPU; one JSON line
   python tools/bench_variant_images.py beds <dir> [fraction=0.02]     two BEDs for the data set: exons.bed, blocks.bed (their paths as JSON)
 
 `run` reports, per thread count, the wall time, Mb of reference per second, aligned bases per second and the stage times
@@ -12,7 +12,9 @@ PEPPER_AMD_DEVICE_CANDIDATES=1 the form whose candidates are enumerated on the d
 --region-bed FILE: options.region_bed, candidates only inside the file's intervals (the rates stay per Mb of the WHOLE reference;
 the stage counts say how many intervals were dropped).  `beds` writes the two shapes a restriction comes in, each covering
 `fraction` of every contig: "exons", intervals of 200 bases spread evenly (every interval of the run keeps a target), and
-"blocks", four contiguous stretches per contig (most intervals of the run are dropped)."""
+"blocks", four contiguous stretches per contig (most intervals of the run are dropped).
+--gvcf: options.gvcf, the encoder also reports the reference blocks of every position (make_images collects them and writes no
+file); the stage counts then hold gvcf_kernel_ms, the event time of the block kernels summed over the encoder calls."""
 import json
 import os
 import shutil
@@ -74,13 +76,13 @@ def write_beds(data, fraction=0.02, exon=200, blocks=4):
     return paths
 
 
-def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rate=1.0, region_bed=None):
+def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rate=1.0, region_bed=None, gvcf=False):
     from pepper_amd.variant.ImageGenerationUI import ImageGenerationUtils
     info = json.load(open(os.path.join(data, "synth.json")))
     mb = info["genome_bases"] / 1e6
     if warm:      # library load, the workers' buffers grown to the size of the job's groups, the file in the page cache -- not part of the rate
         ImageGenerationUtils.generate_images(options(data, os.path.join(data, "vimages_warm"), thread_counts[0], region_size,
-                                                     downsample_rate=downsample_rate, region_bed=region_bed))
+                                                     downsample_rate=downsample_rate, region_bed=region_bed, gvcf=gvcf))
         shutil.rmtree(os.path.join(data, "vimages_warm"), ignore_errors=True)
     runs = []
     for threads in thread_counts:
@@ -89,7 +91,7 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rat
         stages = {}
         t0 = time.perf_counter()
         ImageGenerationUtils.generate_images(options(data, tmp, threads, region_size, stage_seconds=stages,
-                                                     downsample_rate=downsample_rate, region_bed=region_bed))
+                                                     downsample_rate=downsample_rate, region_bed=region_bed, gvcf=gvcf))
         dt = time.perf_counter() - t0
         size = sum(os.path.getsize(os.path.join(tmp, f)) for f in os.listdir(tmp))
         runs.append({"threads": threads, "seconds": round(dt, 3), "mb_reference_per_s": round(mb / dt, 2),
@@ -104,7 +106,7 @@ def run(data, thread_counts=(16,), region_size=100000, warm=True, downsample_rat
                 region_size),
             "packed_reads": os.environ.get("PEPPER_AMD_PACKED_READS", "1") != "0",
             "device_candidates": os.environ.get("PEPPER_AMD_DEVICE_CANDIDATES", "0") == "1", "downsample_rate": downsample_rate,
-            "region_bed": region_bed, "runs": runs}
+            "region_bed": region_bed, "gvcf": gvcf, "runs": runs}
 
 
 if __name__ == "__main__":
@@ -113,6 +115,9 @@ if __name__ == "__main__":
         at = sys.argv.index("--region-bed")
         bed = sys.argv[at + 1]
         del sys.argv[at:at + 2]
+    gvcf = "--gvcf" in sys.argv
+    if gvcf:
+        sys.argv.remove("--gvcf")
     if sys.argv[1] == "make_fast":
         print(json.dumps(make_fast(sys.argv[2], *(float(a) for a in sys.argv[3:10]))))
     elif sys.argv[1] == "beds":
@@ -120,4 +125,4 @@ if __name__ == "__main__":
     else:
         counts = tuple(int(t) for t in sys.argv[3].split(",")) if len(sys.argv) > 3 else (16,)
         print(json.dumps(run(sys.argv[2], counts, int(sys.argv[4]) if len(sys.argv) > 4 else 100000,
-                             downsample_rate=float(sys.argv[5]) if len(sys.argv) > 5 else 1.0, region_bed=bed)))
+                             downsample_rate=float(sys.argv[5]) if len(sys.argv) > 5 else 1.0, region_bed=bed, gvcf=gvcf)))
