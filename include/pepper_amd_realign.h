@@ -13,6 +13,15 @@
  * and its pinning against the reference's own SSW build are oracle/ssw_oracle.cpp, tests/test_realign_oracle.py).
  * Reads arrive as flat arrays (type_read.pos, concatenated type_read.sequence), as for pepper_amd_encoder.h.
  * Return codes and pa_last_error() are those of pepper_amd.h.
+ *
+ * Limits (a call that holds a read beyond one of them fails as a whole with PA_ERR_INVALID; nothing is launched for it):
+ *   - a read has at most 4 000 bases (the score pass packs row indices into 14-bit fields: 4 m < 16 384);
+ *   - the banded trace-back keeps its rows in LDS: with n2 = the window bases and m2 = the read bases the alignment spans
+ *     (ref_end - ref_begin + 1, query_end - query_begin + 1), 13 n2 + m2 + 128 <= 153 600.  Every alignment with
+ *     n2 <= 11 497 fits, so a 4 000-base read may lose up to 7 497 window bases to deletions; beyond that the call fails
+ *     with "alignment too long for the band stage".  Below 3 072 reads per call the band stage runs three wavefronts per
+ *     read while 37 n2 + m2 + 224 <= 153 600 holds for every read of a round (n2 <= 4 037 at m2 = 4 000) and one
+ *     wavefront per read otherwise; the results do not depend on which (tests/test_gpu_realign_cases.py).
  */
 #ifndef PEPPER_AMD_REALIGN_H
 #define PEPPER_AMD_REALIGN_H

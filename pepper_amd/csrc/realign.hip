@@ -898,6 +898,8 @@ __global__ __launch_bounds__(64 * BAND_WAVES) void band_kernel(Job* __restrict__
     }
 }
 
+constexpr size_t BAND_LDS_LIMIT = 150 * 1024;      // LDS a band launch may ask for (a CU has 160 KiB)
+
 // wavefronts per read of the band stage: three widths at once for a call that does not fill the chip on its own, one after the
 // other beyond that (PA_BAND_WAVES overrides)
 // slots per row of the direction bytes a read gets first: half width <= 64 for three wavefronts per read; <= 128 for one (its one
@@ -1436,26 +1438,36 @@ __global__ __launch_bounds__(256) void apply_alignment_kernel(const Job* __restr
 }
 
 // the band rounds laid out by the host over r->jobs (states ST_BAND / ST_WIDER pending): round 0 with rows of at most 129 slots,
-// later rounds with full rows; dj holds the table on the device before and after
-int band_rounds_host(pa_realigner* r, Job* dj, const int8_t* dref, const int8_t* dseq, int32_t n_reads, int first_round, int aux, int nw) {
+// later rounds with full rows; dj holds the table on the device before and after.  A round whose rows do not fit three
+// wavefronts' band arrays in LDS (full rows from n2 = 4 064 on at m2 = 4 000) is laid out and launched with one wavefront per
+// read: the same result, the narrowest width that reaches the score wins either way.  What one wavefront cannot hold is the limit
+// include/pepper_amd_realign.h states.
+int band_rounds_host(pa_realigner* r, Job* dj, const int8_t* dref, const int8_t* dseq, int32_t n_reads, int first_round, int aux, int call_nw) {
     for (int round = first_round; round < 3; ++round) {
         int64_t dir_total = 0;
-        int cap = 0, pending = 0;
-        for (Job& J : r->jobs) {
-            if (J.state == ST_WIDER) J.state = ST_BAND;
-            if (J.state != ST_BAND) continue;
-            const int n2 = J.ref_end - J.ref_begin + 1, m2 = J.read_end - J.read_begin + 1;
-            J.dir_width = round == 0 ? std::min(n2, first_band_width(nw)) : n2;
-            if (round == 0 && std::min(2 * J.bw + 1, n2) > J.dir_width) J.dir_width = n2;   // first band already wider
-            J.dir_off = dir_total;
-            dir_total += (int64_t)m2 * J.dir_width * nw + 2ll * (n2 + m2 + 2);
-            const int bw_cap = J.dir_width >= n2 ? INT32_MAX / 4 : (J.dir_width - 1) / 2;
-            cap = std::max(cap, (int)std::min<int64_t>(2 * (int64_t)bw_cap + 3, n2 + 2) + 2);
-            ++pending;
+        int cap = 0, pending = 0, nw = call_nw;
+        size_t lds = 0;
+        for (;;) {
+            dir_total = 0;
+            cap = pending = 0;
+            for (Job& J : r->jobs) {
+                if (J.state == ST_WIDER) J.state = ST_BAND;
+                if (J.state != ST_BAND) continue;
+                const int n2 = J.ref_end - J.ref_begin + 1, m2 = J.read_end - J.read_begin + 1;
+                J.dir_width = round == 0 ? std::min(n2, first_band_width(nw)) : n2;
+                if (round == 0 && std::min(2 * J.bw + 1, n2) > J.dir_width) J.dir_width = n2;   // first band already wider
+                J.dir_off = dir_total;
+                dir_total += (int64_t)m2 * J.dir_width * nw + 2ll * (n2 + m2 + 2);
+                const int bw_cap = J.dir_width >= n2 ? INT32_MAX / 4 : (J.dir_width - 1) / 2;
+                cap = std::max(cap, (int)std::min<int64_t>(2 * (int64_t)bw_cap + 3, n2 + 2) + 2);
+                ++pending;
+            }
+            lds = (size_t)cap * 12 * nw + (size_t)aux + 64;
+            if (lds <= BAND_LDS_LIMIT || nw == 1) break;
+            nw = 1;
         }
         if (!pending) break;
-        const size_t lds = (size_t)cap * 12 * nw + (size_t)aux + 64;
-        if (lds > 150 * 1024) return pa::set_error(PA_ERR_INVALID, "alignment too long for the band stage");
+        if (lds > BAND_LDS_LIMIT) return pa::set_error(PA_ERR_INVALID, "alignment too long for the band stage");
         RA_ALLOC(r->d_dir, (size_t)std::max<int64_t>(dir_total, 1));
         RA_HIP(hipMemcpyAsync(dj, r->jobs.data(), sizeof(Job) * (size_t)n_reads, hipMemcpyHostToDevice, r->stream));
         RA_HIP(hipEventRecord(r->ev[2], r->stream));
@@ -1579,7 +1591,7 @@ int pa_ra::align_device(pa_realigner* r, const char* window_text, int64_t window
     {
         const int cap = std::min(2 * ((first_width - 1) / 2) + 3, max_wl + 2) + 2;
         const size_t lds = (size_t)cap * 12 * nw + (size_t)aux + 64;
-        if (lds > 150 * 1024) return pa::set_error(PA_ERR_INVALID, "alignment too long for the band stage");
+        if (lds > BAND_LDS_LIMIT) return pa::set_error(PA_ERR_INVALID, "alignment too long for the band stage");
         RA_HIP(hipEventRecord(r->ev[2], st));
         RA_HIP(launch_band(st, nw, n_reads, lds, dj, dref, dseq, static_cast<uint8_t*>(r->d_dir.p), static_cast<uint32_t*>(r->d_ops.p), d_opsctr, cap));
         RA_HIP(hipEventRecord(r->ev[3], st));
