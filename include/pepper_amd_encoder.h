@@ -649,6 +649,21 @@ int pa_selector_limits(int64_t* out, int32_t n);
 int pa_selector_run(pa_selector* s, const pa_candidate_rules* rules, int64_t n, const int64_t* position, const int32_t* depth,
                     const int32_t* support, const float* prediction, const char* names, int64_t name_bytes, int32_t n_regions,
                     const pa_selector_region* regions, int32_t on_device, pa_selection* summary);
+/* The ploidy of the contig the selector's next runs are about (options.haploid_contigs / par_regions_bed;
+ * pepper_amd/variant/Ploidy.py).  A call's rows are one contig.  haploid_contig 0 (with n_par 0, NULL, NULL): every row diploid,
+ * the state of a new selector.  Otherwise position p is haploid unless par_start[k] <= p < par_end[k] for some k: n_par
+ * intervals, 0-based and half-open, ascending and disjoint (HOST pointers; uploaded to the selector's device here, not per run:
+ * set it again only when the contig changes).  At a haploid row pa_selector_run and pa_encoder_select_candidates decide from
+ * the primed triple,
+ *     s   = (double)p0 + (double)p2
+ *     p0' = (float)((double)p0 / s),  p1' = 0.0f,  p2' = (float)((double)p2 / s)     if s != 0
+ *     p0' = 0.5f,                     p1' = 0.0f,  p2' = 0.5f                         if s == 0
+ * exactly where they read the model's: the genotype (first maximum: 0 or 2), non_alt = max(p1', p2') against p_value[_in_lc],
+ * the deletion swap.  A NaN in the triple still sets PA_SELECT_NAN; the frequency admission, the low-complexity flag and the
+ * letter / name checks do not see the ploidy.  flags bit 3 is set on the haploid rows that are kept.  The compacted prediction
+ * stays the MODEL's triple: pa_candidates_select_format_ploidy primes it again from flags bit 3.  A run stays one submission and
+ * one wait.  PA_ERR_INVALID: intervals without a haploid contig, or a table that is not ascending and disjoint. */
+int pa_selector_set_ploidy(pa_selector* s, int32_t haploid_contig, int64_t n_par, const int64_t* par_start, const int64_t* par_end);
 /* The m kept rows of the last run in row order (HOST pointers, any may be NULL): their row numbers, flags, reference letters
  * and low-complexity flags, the compacted fields, the kept names back to back and where each begins (name_offsets[m] = the
  * kept name bytes).  One wait.  PA_ERR_INVALID: no run, or its status was not 0. */

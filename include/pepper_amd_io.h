@@ -119,6 +119,23 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
                                     const uint8_t* reference_base, const uint8_t* in_repeat, const char* alleles,
                                     const int64_t* allele_offsets, int32_t separator_bytes, int32_t* kept_row, int32_t* ref_len,
                                     uint8_t* flags, char* lines, int64_t lines_cap, int64_t* line_offsets);
+/* pa_candidates_select_format with a ploidy per row (options.haploid_contigs; pepper_amd/variant/Ploidy.py).  haploid: one byte
+ * per row, non-zero where the row's position is haploid; NULL: every row diploid, byte for byte the function above.  prediction
+ * holds the MODEL's triples; at a haploid row the function primes them itself,
+ *     s   = (double)p0 + (double)p2
+ *     p0' = (float)((double)p0 / s),  p1' = 0.0f,  p2' = (float)((double)p2 / s)     if s != 0
+ *     p0' = 0.5f,                     p1' = 0.0f,  p2' = 0.5f                         if s == 0
+ * (the IEEE double quotient: this library is built without a fast-math or reciprocal flag) and the genotype (first maximum: 0
+ * or 2), non_alt = max(p1', p2') against p_value[_in_lc], the deletion swap, GQ / QUAL, the AP field and the QUAL cutoff read
+ * the primed triple where they read the model's.  A NaN in the triple returns -2 as above.  The frequency admission, the
+ * low-complexity flag and the letter / name checks do not see the ploidy.  A haploid row's GT is "0" (refCall) or "1"; flags
+ * bit 3 is set on the haploid rows that are kept. */
+int64_t pa_candidates_select_format_ploidy(const pa_candidate_rules* rules, const char* contig, int64_t n, const int64_t* position,
+                                           const int64_t* depth, const int64_t* support, const float* prediction,
+                                           const uint8_t* reference_base, const uint8_t* in_repeat, const char* alleles,
+                                           const int64_t* allele_offsets, int32_t separator_bytes, int32_t* kept_row,
+                                           int32_t* ref_len, uint8_t* flags, char* lines, int64_t lines_cap, int64_t* line_offsets,
+                                           const uint8_t* haploid);
 
 /* One piece of a contig's consensus, as pepper Stitch.py:36-94 (small_chunk_stitch) builds it: the chunks of the given region
  * groups ("predictions/<contig>/<contig>-<start>-<end>", NUL-separated, each in files[file_of_region[r]]; chunk ids in string

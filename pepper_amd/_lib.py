@@ -162,6 +162,7 @@ SYMBOLS = [
     ("pa_selector_limits", ctypes.c_int, [c_void_p, c_int32]),
     ("pa_selector_run", ctypes.c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
                                        c_void_p, c_int32, c_void_p]),
+    ("pa_selector_set_ploidy", ctypes.c_int, [c_void_p, c_int32, c_int64, c_void_p, c_void_p]),
     ("pa_selector_take", ctypes.c_int, [c_void_p] * 11),
     ("pa_encoder_select_candidates", ctypes.c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     # include/pepper_amd_realign.h

@@ -85,6 +85,17 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
                                     const uint8_t* reference_base, const uint8_t* in_repeat, const char* alleles,
                                     const int64_t* allele_offsets, int32_t separator_bytes, int32_t* kept_row, int32_t* ref_len,
                                     uint8_t* flags, char* lines, int64_t lines_cap, int64_t* line_offsets) {
+    return pa_candidates_select_format_ploidy(rules, contig, n, position, depth, support, prediction, reference_base, in_repeat,
+                                              alleles, allele_offsets, separator_bytes, kept_row, ref_len, flags, lines, lines_cap,
+                                              line_offsets, nullptr);
+}
+
+int64_t pa_candidates_select_format_ploidy(const pa_candidate_rules* rules, const char* contig, int64_t n, const int64_t* position,
+                                           const int64_t* depth, const int64_t* support, const float* prediction,
+                                           const uint8_t* reference_base, const uint8_t* in_repeat, const char* alleles,
+                                           const int64_t* allele_offsets, int32_t separator_bytes, int32_t* kept_row,
+                                           int32_t* ref_len, uint8_t* flags, char* lines, int64_t lines_cap, int64_t* line_offsets,
+                                           const uint8_t* haploid) {
     if (!rules || !contig || n < 0 ||
         (n > 0 && (!position || !depth || !support || !prediction || !reference_base || !in_repeat || !alleles ||
                    !allele_offsets || !kept_row || !ref_len || !flags || !lines || !line_offsets))) {
@@ -92,6 +103,7 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
         return -1;
     }
     static const char* const GT_TEXT[3] = {"0/0", "0/1", "1/1"};
+    static const char* const GT_TEXT_HAPLOID[3] = {"0", "0", "1"};     // (a primed triple's first maximum is 0 or 2)
     static const char FORMAT[] = "GT:AP:GQ:DP:AD:VAF:REP";
     const size_t contig_len = std::strlen(contig);
     int64_t m = 0;
@@ -114,8 +126,22 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
         // division by zero there, so the batch goes to the caller's Python path, which raises it
         if (depth[i] == 0) return -2;
         if (kind < 0 || kind > 2) continue;
-        const float p0 = prediction[3 * i], p1 = prediction[3 * i + 1], p2 = prediction[3 * i + 2];
+        float p0 = prediction[3 * i], p1 = prediction[3 * i + 1], p2 = prediction[3 * i + 2];
         if (std::isnan(p0) || std::isnan(p1) || std::isnan(p2)) return -2;     // numpy's argmax / maximum rules for NaN: the caller's Python path
+        const bool hap = haploid && haploid[i];
+        if (hap) {
+            // a haploid position (Ploidy.py): the mass on HET is dropped and the rest renormalised -- the IEEE double quotient,
+            // rounded to float32 -- and everything below reads the primed triple
+            const double s = (double)p0 + (double)p2;
+            p1 = 0.0f;
+            if (s == 0) {
+                p0 = p2 = 0.5f;
+            } else {
+                const float q0 = (float)((double)p0 / s), q2 = (float)((double)p2 / s);
+                p0 = q0;
+                p2 = q2;
+            }
+        }
         const int g = (p1 > p0) ? ((p2 > p1) ? 2 : 1) : ((p2 > p0) ? 2 : 0);   // first maximum
         const double pv = g == 0 ? p0 : (g == 1 ? p1 : p2);
         const double non_alt = p1 > p2 ? p1 : p2;
@@ -160,7 +186,7 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
         w = put_str(w, "\t.\t", 3);
         w = put_str(w, FORMAT, sizeof FORMAT - 1);
         *w++ = '\t';
-        w = put_str(w, GT_TEXT[g], 3);
+        w = hap ? put_str(w, GT_TEXT_HAPLOID[g], 1) : put_str(w, GT_TEXT[g], 3);
         *w++ = ':';
         w = put_str(w, num, (size_t)std::snprintf(num, sizeof num, "%g", non_alt));
         *w++ = ':';
@@ -179,7 +205,7 @@ int64_t pa_candidates_select_format(const pa_candidate_rules* rules, const char*
         *w++ = '\n';
         kept_row[m] = (int32_t)i;
         ref_len[m] = (int32_t)rlen;
-        flags[m] = (uint8_t)((is_snp ? 1 : 0) | ((g == 0 || (double)qual <= cutoff) ? 2 : 0) | (swap ? 4 : 0) | (g << 4));
+        flags[m] = (uint8_t)((is_snp ? 1 : 0) | ((g == 0 || (double)qual <= cutoff) ? 2 : 0) | (swap ? 4 : 0) | (hap ? 8 : 0) | (g << 4));
         ++m;
         line_offsets[m] = w - lines;
     }

@@ -18,6 +18,11 @@
 //
 // No fast-math flag is given to this file: the f64 division is the correctly rounded IEEE quotient the host computes, and
 // the comparisons are exact.
+//
+// Ploidy (pa_selector_set_ploidy; pepper_amd/variant/Ploidy.py): with a haploid contig set, decide looks a row's position up in
+// the contig's sorted PAR table, primes the triple of a haploid row (HET dropped, the rest renormalised by the same f64 quotient)
+// and decides from the primed one; flags bit 3 says so.  compact still copies the MODEL's triple: the host formatter primes
+// again from it and bit 3, so its flags remain an independent check of the device's.  No launch and no wait is added.
 #include "../../include/pepper_amd.h"
 #include "../../include/pepper_amd_encoder.h"
 
@@ -87,6 +92,11 @@ struct DecideArgs {
     uint8_t* rep;
     uint64_t* block_total;            // kept rows << 32 | kept name bytes
     uint32_t* status;
+    // the ploidy of the call's one contig (pa_selector_set_ploidy): haploid 0 -> every row diploid, the table is not read
+    int32_t haploid;
+    int64_t n_par;
+    const int64_t* par_start;         // [n_par] ascending, disjoint: the stretches that stay diploid
+    const int64_t* par_end;
 };
 
 __global__ __launch_bounds__(ST_THREADS) void k_select_decide(DecideArgs a) {
@@ -149,10 +159,33 @@ __global__ __launch_bounds__(ST_THREADS) void k_select_decide(DecideArgs a) {
             if (depth == 0) {
                 status |= PA_SELECT_ZERO_DEPTH;
             } else if (kind >= 0 && kind <= 2) {
-                const float p0 = a.pred[3 * i], p1 = a.pred[3 * i + 1], p2 = a.pred[3 * i + 2];
+                float p0 = a.pred[3 * i], p1 = a.pred[3 * i + 1], p2 = a.pred[3 * i + 2];
                 if (p0 != p0 || p1 != p1 || p2 != p2) {
                     status |= PA_SELECT_NAN;
                 } else {
+                    bool hap = false;
+                    if (a.haploid) {                     // (uniform)
+                        // haploid unless a PAR interval holds p: the last interval that starts at or before p
+                        int64_t lo = 0;
+                        for (int64_t hi = a.n_par; lo < hi;) {
+                            const int64_t mid = (lo + hi) >> 1;
+                            if (a.par_start[mid] <= p) lo = mid + 1; else hi = mid;
+                        }
+                        hap = !(lo > 0 && p < a.par_end[lo - 1]);
+                        if (hap) {
+                            // the primed triple (Ploidy.py; candidates.cpp restates it too): the rules below read it, the
+                            // compaction copies the model's
+                            const double s = (double)p0 + (double)p2;
+                            p1 = 0.0f;
+                            if (s == 0) {
+                                p0 = p2 = 0.5f;
+                            } else {
+                                const float q0 = (float)((double)p0 / s), q2 = (float)((double)p2 / s);
+                                p0 = q0;
+                                p2 = q2;
+                            }
+                        }
+                    }
                     const int g = (p1 > p0) ? ((p2 > p1) ? 2 : 1) : ((p2 > p0) ? 2 : 0);   // first maximum
                     const double non_alt = p1 > p2 ? p1 : p2;
                     const bool by_probability = non_alt >= (rep ? a.rules.p_value_in_lc[kind] : a.rules.p_value[kind]);
@@ -164,7 +197,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_select_decide(DecideArgs a) {
                     if (admitted) {
                         const bool swap = kind == 2 && by_probability;
                         const bool is_snp = code_len - 1 <= 1;      // max(len(REF), len(ALT)) == 1, swapped or not
-                        flags = (uint8_t)((is_snp ? 1 : 0) | (swap ? 4 : 0) | (g << 4));
+                        flags = (uint8_t)((is_snp ? 1 : 0) | (swap ? 4 : 0) | (hap ? 8 : 0) | (g << 4));
                         keep_len = (uint32_t)code_len + 1;
                     }
                 }
@@ -296,6 +329,10 @@ struct pa_selector {
     bool have = false;                // a run has finished: the two below speak of it
     int64_t kept = 0, kept_bytes = 0;
     int32_t status = 0;
+    // the ploidy table of the contig the runs are about (pa_selector_set_ploidy): uploaded on set, read by every run
+    Buffer t_par;                     // n_par starts, then n_par ends
+    int32_t haploid = 0;
+    int64_t n_par = 0;
 };
 
 namespace {
@@ -309,7 +346,7 @@ namespace {
 std::vector<Buffer*> buffers_of(pa_selector* s) {
     return {&s->u_pos, &s->u_depth, &s->u_support, &s->u_pred, &s->u_names, &s->u_ref, &s->t_regions, &s->t_nuls, &s->t_start, &s->t_scan,
             &s->t_keep, &s->t_flags, &s->t_letter, &s->t_rep, &s->t_block, &s->t_bscan, &s->t_words, &s->o_row, &s->o_flags, &s->o_letter,
-            &s->o_rep, &s->o_pos, &s->o_depth, &s->o_support, &s->o_pred, &s->o_names, &s->o_name_off};
+            &s->o_rep, &s->o_pos, &s->o_depth, &s->o_support, &s->o_pred, &s->o_names, &s->o_name_off, &s->t_par};
 }
 
 // One run over arrays that are all in the memory of the selector's device (`regions`: host table, device references).  The
@@ -351,6 +388,8 @@ int select_device(pa_selector* s, const pa_candidate_rules* rules, int64_t n, co
         d.n_regions = (int)regions.size(); d.keep_len = s->t_keep.as<uint8_t>(); d.flags = s->t_flags.as<uint8_t>();
         d.letter = s->t_letter.as<uint8_t>(); d.rep = s->t_rep.as<uint8_t>(); d.block_total = s->t_block.as<uint64_t>();
         d.status = d_status;
+        d.haploid = s->haploid; d.n_par = s->haploid ? s->n_par : 0;
+        d.par_start = s->t_par.as<int64_t>(); d.par_end = s->t_par.as<int64_t>() + d.n_par;
         k_select_decide<<<(unsigned)nb, ST_THREADS, 0, st>>>(d);
         SEL_HIP(hipGetLastError());
     }
@@ -486,6 +525,35 @@ int pa_selector_run(pa_selector* s, const pa_candidate_rules* rules, int64_t n, 
     for (int32_t r = 0; r < n_regions; ++r)
         table[(size_t)r] = SelRegion{regions[r].first_row, regions[r].reference_start, regions[r].reference_len, regions[r].reference};
     return select_device(s, rules, n, position, depth, support, prediction, names, name_bytes, table, summary);
+}
+
+int pa_selector_set_ploidy(pa_selector* s, int32_t haploid_contig, int64_t n_par, const int64_t* par_start, const int64_t* par_end) {
+    if (!s || n_par < 0 || (n_par > 0 && (!par_start || !par_end)))
+        return pa::set_error(PA_ERR_INVALID, "selector set ploidy: null or negative argument");
+    if (!haploid_contig && n_par > 0)
+        return pa::set_error(PA_ERR_INVALID, "selector set ploidy: PAR intervals on a contig that is not haploid");
+    for (int64_t k = 0; k < n_par; ++k)
+        if (par_start[k] < 0 || par_end[k] <= par_start[k] || (k > 0 && par_start[k] < par_end[k - 1]))
+            return pa::set_error(PA_ERR_INVALID, "selector set ploidy: interval " + std::to_string(k) + " is empty, negative or not behind "
+                                                     "the one before it");
+    std::lock_guard<std::mutex> guard(s->lock);
+    SEL_HIP(hipSetDevice(s->device));
+    s->haploid = 0;                   // (a failed upload leaves the selector diploid, not with half a table)
+    s->n_par = 0;
+    if (haploid_contig && n_par > 0) {
+        const size_t bytes = (size_t)n_par * 8;
+        if (!s->t_par.grow(2 * bytes + 8)) {
+            (void)hipGetLastError();
+            return pa::set_error(PA_ERR_HIP, "selector set ploidy: no device memory for " + std::to_string(n_par) + " intervals");
+        }
+        // behind the runs already on the stream, and complete before the caller's arrays may go away
+        SEL_HIP(hipMemcpyAsync(s->t_par.p, par_start, bytes, hipMemcpyHostToDevice, s->stream));
+        SEL_HIP(hipMemcpyAsync(s->t_par.as<uint8_t>() + bytes, par_end, bytes, hipMemcpyHostToDevice, s->stream));
+        SEL_HIP(hipStreamSynchronize(s->stream));
+        s->n_par = n_par;
+    }
+    s->haploid = haploid_contig ? 1 : 0;
+    return PA_OK;
 }
 
 int pa_selector_take(pa_selector* s, int32_t* row, uint8_t* flags, uint8_t* letter, uint8_t* in_repeat, int64_t* position,

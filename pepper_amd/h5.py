@@ -53,6 +53,8 @@ SYMBOLS = [
     ("pa_candidates_reference_flags", ctypes.c_int, [c_char_p, c_int64, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
     ("pa_candidates_select_format", c_int64, [c_void_p, c_char_p, c_int64] + [c_void_p] * 8 + [c_int32, c_void_p, c_void_p, c_void_p,
                                                                                             c_void_p, c_int64, c_void_p]),
+    ("pa_candidates_select_format_ploidy", c_int64, [c_void_p, c_char_p, c_int64] + [c_void_p] * 8 +
+     [c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
     ("pa_h5_builder_open", ctypes.c_int, [c_char_p, ctypes.POINTER(c_void_p)]),
     ("pa_h5_builder_write_polish_predictions", ctypes.c_int, [c_void_p, c_int32, c_int32, c_void_p, c_int32] + [c_void_p] * 9),
     ("pa_h5_builder_write", ctypes.c_int, [c_void_p, c_char_p, c_int32, c_int32, P64, c_void_p]),

@@ -36,6 +36,11 @@ def call_variant(options):
     if options.num_workers < 0:
         raise ValueError("ERROR: num_workers NEEDS TO BE >=0.")
 
+    # options.haploid_contigs / options.par_regions_bed (pepper_amd/variant/Ploidy.py): read once, before any work, so that a
+    # contig name the FASTA does not have stops the run here instead of calling it diploid
+    from pepper_amd.variant import Ploidy
+    Ploidy.of(options)
+
     timestr = time.strftime("%m%d%Y_%H%M%S")
     # batch-invariant mode (options.batch_invariant, default PEPPER_AMD_BATCH_INVARIANT): resolved once here, the options object
     # carries it to every handle of the run -- three-step or fused, the lanes' second handle, every process of device_ids
@@ -121,7 +126,7 @@ def call_variant(options):
         from pepper_amd.variant.fasta import FASTA_handler
         t3 = time.perf_counter()
         Gvcf.write_gvcf(candidate_output_directory + "PEPPER_VARIANT_FULL.vcf.gz", candidate_output_directory + Gvcf.GVCF_NAME,
-                        gvcf_tracks[0], FASTA_handler(options.fasta), log=_log)
+                        gvcf_tracks[0], FASTA_handler(options.fasta), log=_log, ploidy=Ploidy.of(options))
         if walls is not None:
             walls["gvcf"] = time.perf_counter() - t3
     if walls is not None:

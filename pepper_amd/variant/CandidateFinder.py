@@ -21,6 +21,7 @@ from collections import defaultdict
 import numpy as np
 
 from pepper_amd import h5
+from pepper_amd.variant import Ploidy
 from pepper_amd.variant.fasta import FASTA_handler
 
 _BASES = frozenset("ACGT")
@@ -143,10 +144,12 @@ def _in_repeat_many(window, contig, positions):
     return [chr(c) if c else "" for c in letters.tolist()], flags.tolist()
 
 
-def _select_site(options, contig, position, depth, alleles, supports, prediction, reference_base, in_repeat):
-    """One site -> (margin tuple or None, re-genotyping tuple or None)."""
+def _select_site(options, contig, position, depth, alleles, supports, prediction, reference_base, in_repeat, haploid=False):
+    """One site -> (margin tuple or None, re-genotyping tuple or None).  haploid: the position is haploid and `prediction` is
+    the primed triple (Ploidy.prime_batch): its first maximum is 0 or 2, and the tuples carry a genotype of ONE number -- [0] or
+    [1] -- which is how VCFWriter.candidate_list_to_variant tells the site's ploidy."""
     predicted_genotype = max(range(len(prediction)), key=prediction.__getitem__)      # first maximum, as numpy.argmax
-    genotype = ([0, 0], [0, 1], [1, 1])[predicted_genotype]
+    genotype = (([0], [1], [1]) if haploid else ([0, 0], [0, 1], [1, 1]))[predicted_genotype]
     prediction_value = prediction[predicted_genotype]
     non_alt_prediction = max(prediction[1], prediction[2])
 
@@ -199,6 +202,7 @@ def _select_site(options, contig, position, depth, alleles, supports, prediction
 
 def small_chunk_stitch(options, file_chunks):
     fasta_handler = _fasta(options)
+    ploidy = Ploidy.of(options, fasta_handler)
     selected_candidate_list_margin = []
     selected_candidate_list_deepvariant = []
     for file_name, batch_key in file_chunks:
@@ -231,6 +235,11 @@ def small_chunk_stitch(options, file_chunks):
                 ref_bases[k] = base
                 in_repeats[k] = flag
         depth_list = np.asarray(depths).reshape(n).tolist()
+        haploid = [False] * n
+        if ploidy is not None:
+            # options.haploid_contigs: the rows at haploid positions read the primed triple from here on
+            base_predictions, mask = Ploidy.prime_batch(ploidy, names, pos, base_predictions.reshape(n, -1))
+            haploid = mask.tolist()
         prediction_rows = base_predictions.reshape(n, -1).tolist()           # float32 values as Python floats
         position_list = pos.tolist()
         for i in range(n):
@@ -240,7 +249,7 @@ def small_chunk_stitch(options, file_chunks):
             alleles = _parse_list_field(candidates[i])
             supports = [int(x) for x in _parse_list_field(candidate_frequencies[i])]
             margin, calling = _select_site(options, names[i], position_list[i], int(depth_list[i]), alleles, supports,
-                                           prediction_rows[i], reference_base, in_repeats[i])
+                                           prediction_rows[i], reference_base, in_repeats[i], haploid=haploid[i])
             if margin is not None:
                 selected_candidate_list_margin.append(margin)
             if calling is not None:

@@ -23,7 +23,7 @@ def _is_tensor(x):
 
 class Taken(object):
     """The kept rows of one run (numpy, row order): row int32 [m] (numbers in the run's lists), flags uint8 [m] (bit 0 SNP, bit 2
-    swapped, bits 4-5 genotype), letter / in_repeat uint8 [m], position / depth / support int64 [m], prediction float32 [m, 3],
+    swapped, bit 3 haploid, bits 4-5 genotype), letter / in_repeat uint8 [m], position / depth / support int64 [m], prediction float32 [m, 3],
     names (bytes: m NUL-terminated strings) and name_offsets int64 [m + 1]."""
 
     __slots__ = ("row", "flags", "letter", "in_repeat", "position", "depth", "support", "prediction", "names", "name_offsets")
@@ -71,6 +71,21 @@ class DeviceSelector(object):
         out = (ctypes.c_int64 * 5)()
         _lib.check(_lib.load().pa_selector_limits(out, 5))
         return dict(zip(("rows_per_workgroup", "scan_block", "max_name", "scan_level", "max_rows"), [int(v) for v in out]))
+
+    def set_ploidy(self, haploid, par_starts=None, par_ends=None):
+        """The ploidy of the contig the next runs are about (pa_selector_set_ploidy; Ploidy.table gives the three).  haploid
+        false: every row diploid, as a new selector.  The table is uploaded here; a call with the table the selector already
+        holds does nothing."""
+        starts = np.ascontiguousarray(par_starts if haploid and par_starts is not None else [], np.int64)
+        ends = np.ascontiguousarray(par_ends if haploid and par_ends is not None else [], np.int64)
+        key = (bool(haploid), starts.tobytes(), ends.tobytes())
+        if key == getattr(self, "_ploidy_key", (False, b"", b"")):
+            return
+        self._ploidy_key = None                                  # (a failed set leaves the handle diploid)
+        _lib.check(self.lib.pa_selector_set_ploidy(self.handle, 1 if haploid else 0, len(starts),
+                                                   ctypes.c_void_p(starts.ctypes.data if len(starts) else 0),
+                                                   ctypes.c_void_p(ends.ctypes.data if len(ends) else 0)))
+        self._ploidy_key = key
 
     def run(self, rules, position, depth, support, prediction, names, regions):
         """One call's rows.  Either every array is numpy / bytes (uploaded) or every array is a torch tensor on the selector's
@@ -151,14 +166,16 @@ def segment(rules, contig, taken):
     offsets = np.empty(m + 1, np.int64)
     cap = len(taken.names) + m * (len(first) + 200)
     lines = np.empty(cap, np.uint8)
-    kept = io.pa_candidates_select_format(
+    # (flags bit 3: the rows the device decided as haploid.  The prediction is the model's triple: the library primes it again)
+    haploid = np.ascontiguousarray((taken.flags >> 3) & 1)
+    kept = io.pa_candidates_select_format_ploidy(
         ctypes.byref(rules), first, m, taken.position.ctypes.data, taken.depth.ctypes.data, taken.support.ctypes.data,
         taken.prediction.ctypes.data, taken.letter.ctypes.data, taken.in_repeat.ctypes.data, taken.names,
         taken.name_offsets.ctypes.data, 1, row.ctypes.data, ref_len.ctypes.data, flags.ctypes.data,
-        ctypes.c_void_p(lines.ctypes.data), cap, offsets.ctypes.data)
+        ctypes.c_void_p(lines.ctypes.data), cap, offsets.ctypes.data, haploid.ctypes.data if haploid.any() else None)
     if kept == -1:
         raise h5.H5Error(io.pa_h5_last_error().decode())
-    if kept != m or (flags & 0x35 != taken.flags).any():
+    if kept != m or (flags & 0x3d != taken.flags).any():
         raise RuntimeError("device selection kept %d rows of a call and pa_candidates_select_format keeps %d of them (or their flags "
                            "differ): the device and the host disagree" % (m, kept))
     cut = offsets.tolist()

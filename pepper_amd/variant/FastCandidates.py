@@ -23,12 +23,16 @@ import os
 import numpy as np
 
 from pepper_amd import h5
+from pepper_amd.variant import Ploidy
 from pepper_amd.variant.CandidateFinder import (_BASES, _fasta, _in_repeat_many, _parse_list_field, _ReferenceWindow,
                                                 _select_site)
 from pepper_amd.variant.VcfWriter import _F32, VCFWriter
 
 _FORMAT = "GT:AP:GQ:DP:AD:VAF:REP"
 _GT_TEXT = ("0/0", "0/1", "1/1")
+_GT_TEXT_HAPLOID = ("0", "0", "1")              # (a primed triple's first maximum is 0 or 2: Ploidy.py)
+_GT_LIST = ([0, 0], [0, 1], [1, 1])
+_GT_LIST_HAPLOID = ([0], [1], [1])
 
 
 def _g(value):
@@ -43,7 +47,7 @@ def _f32(value):
 class _Columns(object):
     """Selected allele records, one list per field (the fields of the calling tuple of _select_site)."""
 
-    __slots__ = ("contig", "pos", "ref", "alt", "gt", "depth", "support", "pv", "p0", "p1", "p2", "non_alt", "rep")
+    __slots__ = ("contig", "pos", "ref", "alt", "gt", "depth", "support", "pv", "p0", "p1", "p2", "non_alt", "rep", "hap")
 
     def __init__(self):
         for name in self.__slots__:
@@ -53,10 +57,11 @@ class _Columns(object):
         return len(self.pos)
 
     def record(self, i):
-        """The calling tuple CandidateFinder._select_site would have built for row i."""
+        """The calling tuple CandidateFinder._select_site would have built for row i (hap: a haploid row, whose triple is the
+        primed one and whose genotype is one number)."""
         prediction = [self.p0[i], self.p1[i], self.p2[i]]
         return (self.contig[i], self.pos[i], self.pos[i] + len(self.ref[i]), self.ref[i], [self.alt[i]],
-                ([0, 0], [0, 1], [1, 1])[self.gt[i]], self.depth[i], [self.support[i]], self.pv[i], prediction,
+                (_GT_LIST_HAPLOID if self.hap[i] else _GT_LIST)[self.gt[i]], self.depth[i], [self.support[i]], self.pv[i], prediction,
                 [self.non_alt[i]], self.rep[i])
 
 
@@ -93,6 +98,12 @@ def _select_batch(options, fasta_handler, file_name, batch_key, cols, leftovers)
     predictions = predictions.reshape(n, -1)
     if predictions.shape[1] != 3:
         raise ValueError("base_prediction of %s/%s has %d classes, expected 3" % (file_name, batch_key, predictions.shape[1]))
+    # options.haploid_contigs: the rows at haploid positions read the primed triple from here on (hap: which rows)
+    ploidy = Ploidy.of(options, fasta_handler)
+    hap = [False] * n
+    if ploidy is not None:
+        predictions, mask = Ploidy.prime_batch(ploidy, names[0] if one_contig else names, pos, predictions)
+        hap = mask.tolist()
     gt = predictions.argmax(axis=1)                                        # first maximum, as the per-site code
     pv = predictions[np.arange(n), gt].tolist()
     non_alt = np.maximum(predictions[:, 1], predictions[:, 2]).tolist()
@@ -120,13 +131,13 @@ def _select_batch(options, fasta_handler, file_name, batch_key, cols, leftovers)
                 continue
             _, calling = _select_site(options, names[i], pos[i], int(depth[i]), _parse_list_field(candidates[i]),
                                       [int(x) for x in _parse_list_field(candidate_frequencies[i])],
-                                      [p0[i], p1[i], p2[i]], rb, in_repeats[i])
+                                      [p0[i], p1[i], p2[i]], rb, in_repeats[i], haploid=hap[i])
             if calling is not None:
                 leftovers.append(calling)
         return
     bases = _BASES
     c_contig, c_pos, c_ref, c_alt, c_gt, c_depth, c_support = cols.contig, cols.pos, cols.ref, cols.alt, cols.gt, cols.depth, cols.support
-    c_pv, c_p0, c_p1, c_p2, c_non_alt, c_rep = cols.pv, cols.p0, cols.p1, cols.p2, cols.non_alt, cols.rep
+    c_pv, c_p0, c_p1, c_p2, c_non_alt, c_rep, c_hap = cols.pv, cols.p0, cols.p1, cols.p2, cols.non_alt, cols.rep, cols.hap
     for i in range(n):
         rb = ref_bases[i]
         if rb not in bases:                       # (one upper-cased character or "")
@@ -162,6 +173,7 @@ def _select_batch(options, fasta_handler, file_name, batch_key, cols, leftovers)
         c_p2.append(p2[i])
         c_non_alt.append(na)
         c_rep.append(rep)
+        c_hap.append(hap[i])
 
 
 def _format_single(options, cols, rows):
@@ -181,7 +193,8 @@ def _format_single(options, cols, rows):
         cutoff = (snp_cut_lc if rep else snp_cut) if is_snp else (indel_cut_lc if rep else indel_cut)
         depth, support = cols.depth[i], cols.support[i]
         line = "%s\t%d\t.\t%s\t%s\t%d\t%s\t.\t%s\t%s:%s:%d:%d:%d:%s:%s\n" % (
-            cols.contig[i], cols.pos[i] + 1, ref, alt, qual, "refCall" if g == 0 else "PASS", _FORMAT, _GT_TEXT[g],
+            cols.contig[i], cols.pos[i] + 1, ref, alt, qual, "refCall" if g == 0 else "PASS", _FORMAT,
+            (_GT_TEXT_HAPLOID if cols.hap[i] else _GT_TEXT)[g],
             _g(cols.non_alt[i]), qual, depth, support, _g(_f32(round(support / max(1, depth), 3))), "1" if rep else "0")
         ref_lens.append(len(ref))
         lines.append(line.encode())
@@ -195,7 +208,9 @@ def _plain_options(options):
     names = ("allowed_multiallelics", "snp_q_cutoff", "snp_q_cutoff_in_lc", "indel_q_cutoff", "indel_q_cutoff_in_lc",
              "snp_p_value", "snp_p_value_in_lc", "insert_p_value", "insert_p_value_in_lc", "delete_p_value", "delete_p_value_in_lc",
              "report_snp_above_freq", "report_indel_above_freq", "fasta")
-    return SimpleNamespace(**{n: getattr(options, n) for n in names})
+    # ploidy: options.haploid_contigs / par_regions_bed resolved here (Ploidy.of), so that a spawned worker neither reads the
+    # BED again nor depends on the caller's environment; None when the run has none
+    return SimpleNamespace(ploidy=Ploidy.of(options), **{n: getattr(options, n) for n in names})
 
 
 class _Rules(ctypes.Structure):      # pa_candidate_rules (include/pepper_amd_io.h)
@@ -236,9 +251,10 @@ class _Segment(object):
         allele = blob[starts[i] + 1:starts[i + 1] - 1].decode()
         base = chr(letters[i])
         ref, alt = (allele, base) if flags[k] & 4 else (base, allele)
-        p = [float(x) for x in pred[i]]
+        hap = bool(flags[k] & 8)                 # a haploid row: the library decided from the primed triple, `pred` is the model's
+        p = [float(x) for x in (Ploidy.prime(pred[i])[0] if hap else pred[i])]
         g = int(flags[k]) >> 4
-        return (self.contig, int(pos[i]), int(pos[i]) + len(ref), ref, [alt], ([0, 0], [0, 1], [1, 1])[g], int(depth[i]),
+        return (self.contig, int(pos[i]), int(pos[i]) + len(ref), ref, [alt], (_GT_LIST_HAPLOID if hap else _GT_LIST)[g], int(depth[i]),
                 [int(support[i])], p[g], p, [max(p[1], p[2])], bool(rep[i]))
 
     def pair(self, k):
@@ -302,10 +318,18 @@ def _native_batch_open(options, rules, fasta_handler, file_name, batch_key, file
     return native_batch_arrays(options, rules, fasta_handler, first, n, positions, depths, freq, pred, blob, file_name + "/" + batch_key)
 
 
-def native_batch_arrays(options, rules, fasta_handler, first, n, positions, depths, freq, pred, blob, where="(memory)"):
+_FROM_OPTIONS = object()
+
+
+def native_batch_arrays(options, rules, fasta_handler, first, n, positions, depths, freq, pred, blob, where="(memory)",
+                        ploidy=_FROM_OPTIONS):
     """Selection + record text of ONE prediction batch from its arrays (what _native_batch_open reads from a file; the fused
     call_variant hands over a batch as it writes it): first = the batch's one contig name (bytes), blob = its n candidate strings,
-    each followed by a NUL.  -> _Segment, or None when the batch needs the per-row Python path."""
+    each followed by a NUL.  ploidy: the run's Ploidy or None (left out: Ploidy.of(options)); with one, the rows at haploid
+    positions are marked for pa_candidates_select_format_ploidy, which primes their triples itself.
+    -> _Segment, or None when the batch needs the per-row Python path."""
+    if ploidy is _FROM_OPTIONS:
+        ploidy = Ploidy.of(options, fasta_handler)
     file_name, batch_key = where, ""
     text = np.frombuffer(blob, np.uint8)
     ends = np.flatnonzero(text == 0)
@@ -334,10 +358,14 @@ def native_batch_arrays(options, rules, fasta_handler, first, n, positions, dept
     offsets = np.empty(n + 1, np.int64)
     cap = len(blob) + n * (len(first) + 200)
     lines = np.empty(cap, np.uint8)                       # (not zero-filled, and only the written part is copied out)
-    m = h5.load().pa_candidates_select_format(
+    haploid = None
+    if ploidy is not None and contig in ploidy.contigs:
+        haploid = np.ascontiguousarray(ploidy.is_haploid(contig, pos), np.uint8)
+    m = h5.load().pa_candidates_select_format_ploidy(
         ctypes.byref(rules), first, n, pos.ctypes.data, depth.ctypes.data, support.ctypes.data, pred.ctypes.data,
         letters.ctypes.data, rep.ctypes.data, blob, starts.ctypes.data, 1, row.ctypes.data, ref_len.ctypes.data,
-        flags.ctypes.data, ctypes.c_void_p(lines.ctypes.data), cap, offsets.ctypes.data)
+        flags.ctypes.data, ctypes.c_void_p(lines.ctypes.data), cap, offsets.ctypes.data,
+        None if haploid is None else haploid.ctypes.data)          # (NULL: every row diploid, pa_candidates_select_format itself)
     if m == -2:
         return None
     if m < 0:

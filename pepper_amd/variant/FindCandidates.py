@@ -46,9 +46,14 @@ def candidate_finder(options, input_dir, output_path, precomputed=None, segments
     factory = getattr(options, "fasta_handler_factory", None)
 
     def writer():
+        from pepper_amd.variant import Ploidy
+        handler = factory(options.fasta) if factory is not None else None
+        # (options.haploid_contigs / par_regions_bed: resolved against the FASTA here at the latest, so that a name it does not
+        # have stops the run before a file is opened; the header of the five files says what was asked for)
+        ploidy = Ploidy.of(options, handler)
         return VCFWriter([], options.fasta, options.sample_name, output_path, "PEPPER_VARIANT_FULL",
                          "PEPPER_VARIANT_OUTPUT_PEPPER", "PEPPER_VARIANT_OUTPUT_VARIANT_CALLING",
-                         fasta_handler=factory(options.fasta) if factory is not None else None)
+                         fasta_handler=handler, ploidy=ploidy)
     if segments is not None:
         from pepper_amd.variant import FastCandidates
         vcf_file_full = writer()

@@ -8,7 +8,10 @@ Number=A fields would need a value for that allele).  Blocks are cut around the 
 of the block it was cut from, which are then lower bounds for it.
 
 A block line:  CHROM POS . <ref base> <NON_REF> . . END=<end> GT:GQ:MIN_DP 0/0:<min GQ>:<min DP>  (./. where MIN_DP is 0).
+With options.haploid_contigs (pepper_amd/variant/Ploidy.py) the pieces are also cut where the ploidy changes and a haploid piece
+writes GT 0 (. where MIN_DP is 0); its GQ stays the diploid read-count value, a lower bound (RefConfidence.py).
 Contigs in FASTA order, positions ascending."""
+import bisect
 import gzip
 
 from pepper_amd.variant.bgzf import BgzfWriter, TabixBuilder
@@ -41,18 +44,24 @@ def header_text(meta, columns):
     return meta + extra + columns
 
 
-def block_line(contig, start, end, ref_base, min_dp, min_gq):
-    """start, end: 0-based, half-open -> the line, bytes."""
-    genotype = "0/0" if min_dp > 0 else "./."
+def block_line(contig, start, end, ref_base, min_dp, min_gq, haploid=False):
+    """start, end: 0-based, half-open -> the line, bytes.  haploid: the piece lies where the run calls haploid
+    (options.haploid_contigs): GT 0 (. where MIN_DP is 0); the GQ stays the read-count model's diploid value, a lower bound."""
+    if haploid:
+        genotype = "0" if min_dp > 0 else "."
+    else:
+        genotype = "0/0" if min_dp > 0 else "./."
     return ("%s\t%d\t.\t%s\t<NON_REF>\t.\t.\tEND=%d\tGT:GQ:MIN_DP\t%s:%d:%d\n"
             % (contig, start + 1, ref_base, end, genotype, min_gq, min_dp)).encode()
 
 
-def compose(contigs, blocks, records, ref_base):
+def compose(contigs, blocks, records, ref_base, ploidy=None):
     """contigs: names in FASTA order; blocks: [(contig, start, end, band, min_dp, min_gq)], 0-based half-open, disjoint (what
     RefConfidence.BlockTrack.finish returns); records: what read_vcf returns; ref_base(contig, pos0) -> the reference letter.
     -> [(contig, start, end, line, is_record)] in output order: per contig the records in position order (equal positions in
-    file order) and the pieces of the blocks that no record's REF span covers."""
+    file order) and the pieces of the blocks that no record's REF span covers.
+    ploidy: the run's Ploidy (options.haploid_contigs) or None; with one, a piece is additionally cut wherever the ploidy
+    changes (the edges of the PAR intervals of a haploid contig), and a haploid piece writes GT 0 instead of 0/0."""
     order = {name: k for k, name in enumerate(contigs)}
     for contig, _pos, _n, _line in records:
         if contig not in order:
@@ -73,6 +82,7 @@ def compose(contigs, blocks, records, ref_base):
             else:
                 spans.append([pos, pos + n])
         entries = [(pos, 1, k, contig, pos, pos + n, line) for pos, k, n, line in recs]
+        edges = ploidy.boundaries(contig) if ploidy is not None and contig in ploidy.contigs else None
         at = 0
         for _c, start, end, _band, min_dp, min_gq in sorted(per_contig_blocks.get(contig, []), key=lambda b: b[1]):
             while at < len(spans) and spans[at][1] <= start:
@@ -84,22 +94,30 @@ def compose(contigs, blocks, records, ref_base):
                     k += 1
                     continue
                 stop = min(end, spans[k][0]) if k < len(spans) else end
-                entries.append((cursor, 0, 0, contig, cursor, stop, block_line(contig, cursor, stop, ref_base(contig, cursor), min_dp, min_gq)))
+                haploid = False
+                if edges is not None:
+                    nxt = bisect.bisect_right(edges, cursor)             # the first ploidy boundary behind the cursor
+                    if nxt < len(edges):
+                        stop = min(stop, edges[nxt])
+                    haploid = bool(ploidy.is_haploid(contig, [cursor])[0])
+                entries.append((cursor, 0, 0, contig, cursor, stop,
+                                block_line(contig, cursor, stop, ref_base(contig, cursor), min_dp, min_gq, haploid)))
                 cursor = stop
         entries.sort(key=lambda e: e[:3])
         out += [(c, s, e, line, bool(is_record)) for _p, is_record, _k, c, s, e, line in entries]
     return out
 
 
-def write_gvcf(full_vcf_path, out_path, track, fasta_handler, log=None):
-    """PEPPER_VARIANT_FULL.vcf.gz and the run's block track -> out_path and out_path + '.tbi'; -> (records, block lines)."""
+def write_gvcf(full_vcf_path, out_path, track, fasta_handler, log=None, ploidy=None):
+    """PEPPER_VARIANT_FULL.vcf.gz and the run's block track -> out_path and out_path + '.tbi'; -> (records, block lines).
+    ploidy: the run's Ploidy or None (compose)."""
     meta, columns, records = read_vcf(full_vcf_path)
     blocks = track.finish()
 
     def ref_base(contig, pos):
         return fasta_handler.get_reference_bytes(contig, pos, pos + 1).decode() or "N"
 
-    entries = compose(track.contigs, blocks, records, ref_base)
+    entries = compose(track.contigs, blocks, records, ref_base, ploidy=ploidy)
     out, index = BgzfWriter(out_path, deferred=True), TabixBuilder()
     out.write(header_text(meta, columns))
     for contig, start, end, line, _is_record in entries:

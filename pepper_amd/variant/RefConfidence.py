@@ -19,6 +19,10 @@ n_ref' = (100 n_ref + n - 1) // n, n_alt' = 100 - n_ref'.
 GQ is DeepVariant's published reference-confidence model with its defaults: the log10 likelihoods of hom-ref, het and hom-alt
 under a per-read error rate p, normalised, GQ = floor(min(max_gq, -10 log10(1 - P(hom-ref)))).  It is a model of read counts
 and not the network's output, and nobody has calibrated p for nanopore reads here: it is a parameter (options.gvcf_error_rate).
+
+With options.haploid_contigs (pepper_amd/variant/Ploidy.py) the blocks of a haploid stretch keep this DIPLOID GQ: there is no
+haploid table.  Dropping the het hypothesis removes a term from the normaliser and leaves the hom-ref term as it is, so it can
+only raise P(hom-ref): the diploid GQ is a lower bound of the haploid one.  Gvcf.py writes such a block with GT 0.
 """
 import math
 import threading

@@ -27,14 +27,13 @@ def _merge(pairs):
     return np.array(starts, np.int64), np.array(ends, np.int64)
 
 
-def read_bed(path, contig_lengths, log=None):
-    """-> {contig: (starts int64[n], ends int64[n])}, merged; only contigs that keep at least one target.
+def parse_bed(path, contig_lengths):
+    """-> ({contig: [(start, end)]} unmerged, the number of intervals on contigs that contig_lengths does not have).
 
-    contig_lengths: {contig: length} of the FASTA.  Fields are split on any whitespace; blank lines and lines starting with
-    `#`, `track` or `browser` are skipped; start and end are base-10 integers with 0 <= start <= end; start == end is empty
-    and ignored; ends beyond the contig are clamped; contigs the FASTA does not have are ignored (log, if given, gets one line
-    that counts them).  A malformed line raises ValueError with the file and the 1-based line number, and so does a file
-    that leaves no target at all."""
+    contig_lengths: {contig: length}.  Fields are split on any whitespace; blank lines and lines starting with `#`, `track` or
+    `browser` are skipped; start and end are base-10 integers with 0 <= start <= end; start == end is empty and ignored; ends
+    beyond the contig are clamped; contigs without a length are counted and ignored.  A malformed line raises ValueError with
+    the file and the 1-based line number.  (Shared with Ploidy.parse: the PAR BED has the same syntax.)"""
     per_contig, unknown = {}, 0
     with open(path, "r") as fh:
         for number, line in enumerate(fh, 1):
@@ -60,6 +59,16 @@ def read_bed(path, contig_lengths, log=None):
             end = min(end, int(length))
             if start < end:
                 per_contig.setdefault(fields[0], []).append((start, end))
+    return per_contig, unknown
+
+
+def read_bed(path, contig_lengths, log=None):
+    """-> {contig: (starts int64[n], ends int64[n])}, merged; only contigs that keep at least one target.
+
+    contig_lengths: {contig: length} of the FASTA.  The syntax is parse_bed's; contigs the FASTA does not have are ignored (log,
+    if given, gets one line that counts them).  A malformed line raises ValueError with the file and the 1-based line number,
+    and so does a file that leaves no target at all."""
+    per_contig, unknown = parse_bed(path, contig_lengths)
     if unknown and log is not None:
         log("INFO: REGION BED: " + str(unknown) + " INTERVALS ON CONTIGS THE FASTA DOES NOT HAVE ARE IGNORED")
     if not per_contig:

@@ -41,7 +41,8 @@ def _picklable_options(options):
     """The option fields the formatter reads, as a plain namespace (the caller's object may hold handles / factories)."""
     from types import SimpleNamespace
     names = ("allowed_multiallelics", "snp_q_cutoff", "snp_q_cutoff_in_lc", "indel_q_cutoff", "indel_q_cutoff_in_lc")
-    return SimpleNamespace(**{n: getattr(options, n) for n in names})
+    # (the formatter reads a site's ploidy off its tuples; `ploidy` rides along for whoever selects with these options)
+    return SimpleNamespace(ploidy=getattr(options, "ploidy", None), **{n: getattr(options, n) for n in names})
 
 
 class _VcfFile(object):
@@ -79,8 +80,9 @@ class _VcfFile(object):
 
 class VCFWriter:
     def __init__(self, all_contigs, reference_file_path, sample_name, output_dir, filename_full, filename_pepper,
-                 filename_variant_calling, fasta_handler=None):
+                 filename_variant_calling, fasta_handler=None, ploidy=None):
         self.fasta_handler = fasta_handler if fasta_handler is not None else FASTA_handler(reference_file_path)
+        self.ploidy = ploidy               # the run's Ploidy (options.haploid_contigs) or None: one header line says so
         contigs = self.fasta_handler.get_chromosome_names()
         self.contigs = contigs
         self.vcf_header = self.get_vcf_header(sample_name, contigs)
@@ -157,7 +159,12 @@ class VCFWriter:
                 genotype_hp1.append(i + 1)
                 genotype_hp2.append(i + 1)
 
-        if 0 < len(genotype_hp1) + len(genotype_hp2) <= 2:
+        if candidates and len(candidates[0][5]) == 1:
+            # a haploid site (options.haploid_contigs; a site is one position, so it has one ploidy: its records carry a genotype
+            # of one number and the primed triple): the called allele is the first record, in the order above, whose genotype is
+            # 2, written as one number -- never 1/2 -- and none means 0.  Every other field is what the loop above computed
+            gt = [genotype_hp2[0]] if genotype_hp2 else [0]
+        elif 0 < len(genotype_hp1) + len(genotype_hp2) <= 2:
             gt = genotype_hp1 + genotype_hp2
             if len(gt) == 1:
                 gt = [0, gt[0]]
@@ -204,10 +211,11 @@ class VCFWriter:
                 cutoff = options.indel_q_cutoff_in_lc if site_in_repeat else options.indel_q_cutoff
             failed_variant = qual <= cutoff
             # everything not confidently genotyped goes to the re-genotyping set (:178-182)
-            selected_for_variant_calling = genotype == [0, 0] or failed_variant
+            hom_ref = genotype == [0, 0] or genotype == [0]      # (a haploid 0 routes like [0, 0])
+            selected_for_variant_calling = hom_ref or failed_variant
             vafs = [round(ad / max(1, depth), 3) for ad in variant_allele_support]
             rep = "1" if site_in_repeat else "0"
-            record = VCFWriter._record(contig, ref_start, alleles, qual, 'refCall' if genotype == [0, 0] else 'PASS',
+            record = VCFWriter._record(contig, ref_start, alleles, qual, 'refCall' if hom_ref else 'PASS',
                                        genotype, non_alt_predictions, qual, depth, variant_allele_support, vafs, rep)
             out.append((record, is_snp, selected_for_variant_calling))
         return out
@@ -271,6 +279,8 @@ class VCFWriter:
             '##FORMAT=<ID=GQ,Number=1,Type=Float,Description="Genotype Quality">',
             '##FORMAT=<ID=REP,Number=1,Type=String,Description="If set to 1 then variant site is considered to be ina LowCompexity repeat region">',
         ]
+        if getattr(self, "ploidy", None) is not None:
+            lines.insert(6, self.ploidy.header_line())           # behind the FILTER lines
         for sq in self.fasta_handler.get_chromosome_names():
             if sq not in contigs:
                 continue

@@ -45,6 +45,10 @@ class FusedPredictor(object):
         self.keep_predictions = not self.device_selection or bool(getattr(options, "keep_predictions", False))
         self.device_segments = []
         self.rules = None
+        # options.haploid_contigs / par_regions_bed (Ploidy.py; None: every call diploid): the device selection is told the
+        # call's contig's table before each run, the host selection is handed it
+        from pepper_amd.variant import Ploidy
+        self.ploidy = Ploidy.of(options)
         self.output_filepath = output_filepath
         self.host_files = 0
         # (the append-only writer: ~9 000 batch groups per 256 Mb cost the writer thread 0.3 ms each through libhdf5)
@@ -171,6 +175,8 @@ class FusedPredictor(object):
                     selector = getattr(model, "_selector", None)
                     if selector is None:                 # one selector per model handle, on the handle's stream
                         selector = model._selector = DeviceSelect.DeviceSelector(device, model._stream)
+                    if self.ploidy is not None:          # (uploaded only when the table differs from the one the selector holds)
+                        selector.set_ploidy(*self.ploidy.table(contig.decode() if isinstance(contig, bytes) else contig))
                     status, _, _ = selector.run_encoder(enc.enc, self.rules, probs)
                     if status == 0:
                         taken = selector.take()
@@ -206,7 +212,8 @@ class FusedPredictor(object):
         probs = np.ascontiguousarray(probs, np.float32).reshape(n, -1)
         seg = None
         if self.rules is not None:
-            seg = FastCandidates.native_batch_arrays(self.options, self.rules, fasta_handler, first, n, positions, depths, freqs, probs, blob)
+            seg = FastCandidates.native_batch_arrays(self.options, self.rules, fasta_handler, first, n, positions, depths, freqs, probs, blob,
+                                                     ploidy=self.ploidy)
         if seg is None:
             with self.timer_lock:
                 self.host_files += 1
@@ -305,7 +312,7 @@ class FusedPredictor(object):
                     continue
                 first = bytes(contigs[0])
                 seg = FastCandidates.native_batch_arrays(options, rules, fasta_handler, first, len(positions), positions, depths, freqs,
-                                                         probs, blob, self.filename + "/" + key)
+                                                         probs, blob, self.filename + "/" + key, ploidy=self.ploidy)
                 if seg is not None:
                     self.segments[(self.filename, key)] = seg
                 with self.timer_lock:
