@@ -244,7 +244,13 @@ int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_ho
  * per-position pass; without one it is not launched.  The polish encoder and the polish chain ignore the table. */
 int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const int64_t* end);
 
-/* Depth classes of the positions a run looked at (opt-in, not in the reference; pepper_amd/variant/Coverage.py is the host twin
+/* Two per-position tracks, depth classes and reference blocks (below), share one scheme in csrc/encoder.hip: the rows of every
+ * region's candidate window classified by at most 8 ascending lower bounds (ClassBounds / class_of), the classes run-length
+ * encoded per 512-row tile in a COUNT and an EMIT launch around tile_offsets_kernel (track_row, note_heads, head_rank), the
+ * records sized, re-emitted on overflow and counted by submit_track / finish_track over a RunTrack of the batch, and fetched
+ * with the ends derived by fetch_track.  What differs is said with each: where a run may begin, and what a record carries.
+ *
+ * Depth classes of the positions a run looked at (opt-in, not in the reference; pepper_amd/variant/Coverage.py is the host twin
  * and writes the BED).  The depth of a position is what tile_count_kernel holds as its coverage when the per-position pass
  * starts -- the reference's coverage_vector (region_summary.cpp:379, :454): aligned bases with quality >= min_snp_baseq and
  * insert anchors rescued by the indel quality rule, of reads with mapping quality > 0, after the reservoir sample where one

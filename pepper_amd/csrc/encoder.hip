@@ -1249,66 +1249,99 @@ __global__ __launch_bounds__(NT, PA_TILE_MIN_WAVES) void tile_count_kernel(TileA
 #endif
 }
 
-// ---- depth classes (pa_encoder_set_depth_bins) ------------------------------------------------------------------------
+// ---- per-position tracks: depth classes (pa_encoder_set_depth_bins), reference blocks (pa_encoder_set_ref_confidence) ----
 // The rows of every region's candidate window [cand_lo, cand_hi] (clamped to [0, L - 1]; row L is never reported), each in
-// the bin of the coverage tile_count_kernel stored for it, run-length encoded: one record per run, in region and row order.
-// One workgroup per tile, one thread per row, launched twice around tile_offsets_kernel.  EMIT = false counts the tile's run
-// heads and adds the tile's share of the region's totals (bases per bin, sum of depths: integers, so the order of the atomics
-// does not show); EMIT = true computes the same flags again and writes every head at the tile's scanned offset plus its rank
-// among the tile's heads.  A run's end is the next record's start in its region, or the window's end: the host derives it.
-// A row outside every target (targets != null) has the bin DEPTH_OFF_TARGET and adds nothing to the totals.
-constexpr int DEPTH_MAX_BINS = 8;
-constexpr int DEPTH_OFF_TARGET = 255;
-constexpr int DEPTH_TOTALS = DEPTH_MAX_BINS + 1;    // per region: bases of bin 0 .. 7, sum of depths
-struct DepthBins { int32_t n; int32_t lower[DEPTH_MAX_BINS]; };      // lower[0] == 0 < lower[1] < ...; bin k = [lower[k], lower[k + 1])
-struct DepthRun { int32_t region, row, bin; };
+// the class of a value tile_count_kernel stored for it -- the depth track: the bin of the coverage; the reference-block track:
+// the band of the GQ byte --, run-length encoded: one record per run head, in region and row order.  One workgroup per tile,
+// one thread per row, launched twice around tile_offsets_kernel.  EMIT = false counts the tile's heads; EMIT = true computes
+// the same flags again and writes every head at the tile's scanned offset plus its rank among the tile's heads.  A run's end
+// is the next record's start in its region, or the window's end: the host derives it (fetch_track).  A row outside every
+// target (targets != null) has the class TRACK_OFF_TARGET.  The two kernels share everything but what makes a head at a
+// tile's first row and what a record carries beside its class: each says so where it decides.
+constexpr int TRACK_CLASSES = 8;
+constexpr int TRACK_OFF_TARGET = 255;
+struct ClassBounds { int32_t n; int32_t lower[TRACK_CLASSES]; };     // lower[0] == 0 < lower[1] < ...; class k = [lower[k], lower[k + 1])
 
-__device__ __forceinline__ int depth_bin(const DepthBins& bins, int depth) {
+__device__ __forceinline__ int class_of(const ClassBounds& bounds, int value) {
     int k = 0;
 #pragma unroll
-    for (int j = 1; j < DEPTH_MAX_BINS; ++j) k += (j < bins.n && depth >= bins.lower[j]) ? 1 : 0;
+    for (int j = 1; j < TRACK_CLASSES; ++j) k += (j < bounds.n && value >= bounds.lower[j]) ? 1 : 0;
     return k;
 }
+
+// the row of this thread: its region, the window's first row, the row in the region and in the batch, is it inside the window
+struct TrackRow { int region, lo, idx; int64_t at; bool in; };
+__device__ __forceinline__ TrackRow track_row(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region) {
+    TrackRow r;
+    r.region = tile_region[blockIdx.x];
+    const RegRec* reg = regions + r.region;
+    r.lo = reg->cand_lo > 0 ? reg->cand_lo : 0;
+    const int hi = reg->cand_hi < reg->L - 1 ? reg->cand_hi : reg->L - 1;
+    r.idx = ((int)blockIdx.x - reg->tile0) * TP + (int)threadIdx.x;
+    r.at = reg->row_base + r.idx;
+    r.in = r.idx >= r.lo && r.idx <= hi;             // (idx <= L - 1: a row tile_count_kernel stored its values for)
+    return r;
+}
+__device__ __forceinline__ bool row_on_target(const uint8_t* __restrict__ targets, int64_t at) { return targets == nullptr || targets[at] != 0; }
+
+// the heads of a wave as a mask, their number where the tile's other waves read it behind the next barrier
+__device__ __forceinline__ unsigned long long note_heads(bool head, int* wave_heads) {
+    const unsigned long long hm = __ballot(head);
+    if ((threadIdx.x & 63) == 0) wave_heads[threadIdx.x >> 6] = __popcll(hm);
+    return hm;
+}
+// EMIT = false: the tile's head count for tile_offsets_kernel
+__device__ __forceinline__ void store_tile_heads(const int* wave_heads, int* __restrict__ tile_heads) {
+    if (threadIdx.x == 0) {
+        int n = 0;
+        for (int k = 0; k < TP / 64; ++k) n += wave_heads[k];
+        tile_heads[blockIdx.x] = n;
+    }
+}
+// the rank of this row's run among the tile's heads: heads at or before the row, less one (a head's own rank; its record's
+// slot is the tile's scanned offset plus it)
+__device__ __forceinline__ int head_rank(unsigned long long hm, const int* wave_heads) {
+    int rank = __popcll(hm & ((2ull << (threadIdx.x & 63)) - 1ull)) - 1;
+    for (int k = 0; k < (int)(threadIdx.x >> 6); ++k) rank += wave_heads[k];
+    return rank;
+}
+
+// The depth track.  The count pass also adds the tile's share of the region's totals (bases per bin, sum of depths: integers,
+// so the order of the atomics does not show); a row outside every target adds nothing to them.
+constexpr int DEPTH_TOTALS = TRACK_CLASSES + 1;     // per region: bases of bin 0 .. 7, sum of depths
+struct DepthRun { int32_t region, row, bin; };
 
 template <bool EMIT>
 __global__ __launch_bounds__(TP) void depth_runs_kernel(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region,
                                                         const int32_t* __restrict__ depth, const uint8_t* __restrict__ targets,
-                                                        DepthBins bins, int* __restrict__ tile_heads, const int* __restrict__ tile_off,
+                                                        ClassBounds bins, int* __restrict__ tile_heads, const int* __restrict__ tile_off,
                                                         unsigned long long* __restrict__ totals, DepthRun* __restrict__ runs, int run_cap) {
     __shared__ uint8_t bin_s[TP];
     __shared__ int wave_heads[TP / 64];
-    __shared__ int bases_s[DEPTH_MAX_BINS];
+    __shared__ int bases_s[TRACK_CLASSES];
     __shared__ unsigned long long sum_s;
-    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int region = tile_region[tile];
-    const RegRec* reg = regions + region;
-    const int lo = reg->cand_lo > 0 ? reg->cand_lo : 0;
-    const int hi = reg->cand_hi < reg->L - 1 ? reg->cand_hi : reg->L - 1;
-    const int tile_lo = (tile - reg->tile0) * TP;
-    const int idx = tile_lo + tid;
-    const bool in = idx >= lo && idx <= hi;          // (idx <= L - 1: a row tile_count_kernel stored a depth for)
-    if (!EMIT && tid < DEPTH_MAX_BINS) bases_s[tid] = 0;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const TrackRow r = track_row(regions, tile_region);
+    if (!EMIT && tid < TRACK_CLASSES) bases_s[tid] = 0;
     if (!EMIT && tid == 0) sum_s = 0;
-    int d = 0, bin = DEPTH_OFF_TARGET;
+    int d = 0, bin = TRACK_OFF_TARGET;
     bool on_target = false;
-    if (in) {
-        d = depth[reg->row_base + idx];
-        on_target = targets == nullptr || targets[reg->row_base + idx] != 0;
-        if (on_target) bin = depth_bin(bins, d);
+    if (r.in) {
+        d = depth[r.at];
+        on_target = row_on_target(targets, r.at);
+        if (on_target) bin = class_of(bins, d);
     }
     bin_s[tid] = (uint8_t)bin;
     __syncthreads();
+    // A run is ONE record, whatever tiles it crosses: a tile's first row looks back across the border, at the row in front
+    // as the tile in front read it.
     bool head = false;
-    if (in) {
-        if (idx == lo) head = true;
+    if (r.in) {
+        if (r.idx == r.lo) head = true;
         else if (tid > 0) head = bin_s[tid - 1] != bin;
-        else {                                       // the previous row is the last one of the tile in front: read where that tile read it
-            const bool prev_on = targets == nullptr || targets[reg->row_base + idx - 1] != 0;
-            head = (prev_on ? depth_bin(bins, depth[reg->row_base + idx - 1]) : DEPTH_OFF_TARGET) != bin;
-        }
+        else head = (row_on_target(targets, r.at - 1) ? class_of(bins, depth[r.at - 1]) : TRACK_OFF_TARGET) != bin;
     }
-    const unsigned long long hm = __ballot(head);
-    if (lane == 0) wave_heads[w] = __popcll(hm);
+    const unsigned long long hm = note_heads(head, wave_heads);
     if (!EMIT) {
         // the tile's share of the totals: per wave one LDS atomic per bin that occurs and one for the depths
         for (int k = 0; k < bins.n; ++k) {
@@ -1320,61 +1353,34 @@ __global__ __launch_bounds__(TP) void depth_runs_kernel(const RegRec* __restrict
     }
     __syncthreads();
     if (!EMIT) {
-        if (tid == 0) {
-            int n = 0;
-            for (int k = 0; k < TP / 64; ++k) n += wave_heads[k];
-            tile_heads[tile] = n;
-        }
-        if (tid < DEPTH_MAX_BINS && bases_s[tid]) atomicAdd(&totals[(size_t)region * DEPTH_TOTALS + tid], (unsigned long long)bases_s[tid]);
-        if (tid == DEPTH_MAX_BINS && sum_s) atomicAdd(&totals[(size_t)region * DEPTH_TOTALS + DEPTH_MAX_BINS], sum_s);
+        store_tile_heads(wave_heads, tile_heads);
+        if (tid < TRACK_CLASSES && bases_s[tid]) atomicAdd(&totals[(size_t)r.region * DEPTH_TOTALS + tid], (unsigned long long)bases_s[tid]);
+        if (tid == TRACK_CLASSES && sum_s) atomicAdd(&totals[(size_t)r.region * DEPTH_TOTALS + TRACK_CLASSES], sum_s);
     } else if (head) {
-        int slot = tile_off[tile] + __popcll(hm & ((1ull << lane) - 1ull));
-        for (int k = 0; k < w; ++k) slot += wave_heads[k];
-        if (slot < run_cap) runs[slot] = DepthRun{region, idx, bin};      // past the capacity: the host emits again with room
+        const int slot = tile_off[blockIdx.x] + head_rank(hm, wave_heads);
+        if (slot < run_cap) runs[slot] = DepthRun{r.region, r.idx, bin};      // past the capacity: the host emits again with room
     }
 }
 
-// ---- reference blocks (pa_encoder_set_ref_confidence) -------------------------------------------------------------------
-// The rows of every region's candidate window, as above, each in the band of the GQ byte tile_count_kernel<TILE_REFCONF> stored
-// for it, run-length encoded with the smallest coverage and the smallest GQ of each run: one record per run and tile, in
-// region and row order.  One workgroup per tile, one thread per row, launched twice around tile_offsets_kernel.  A tile's
-// first row inside the window is always a head -- a run that crosses a tile border is one record per tile, and the host
-// (variant/RefConfidence.py merge_blocks, BlockTrack) joins touching records of equal band with their minima -- so every row
-// of the window belongs to a head of its own tile and the minima are taken in LDS: atomicMin on the slot of the head's rank
-// among the tile's heads (a minimum does not depend on the order; no global atomic on the way to the output).
-// A row outside every target (targets != null) has the band DEPTH_OFF_TARGET.
-constexpr int REFCONF_MAX_BANDS = 8;
-struct RefBands { int32_t n; int32_t lower[REFCONF_MAX_BANDS]; };    // lower[0] == 0 < lower[1] < ...; band k = GQ in [lower[k], lower[k + 1])
+// The reference-block track: every record carries the smallest coverage and the smallest GQ of its rows.
 struct RefBlock { int32_t region, row, band, min_dp, min_gq; };
-
-__device__ __forceinline__ int ref_band(const RefBands& bands, int gq) {
-    int k = 0;
-#pragma unroll
-    for (int j = 1; j < REFCONF_MAX_BANDS; ++j) k += (j < bands.n && gq >= bands.lower[j]) ? 1 : 0;
-    return k;
-}
 
 template <bool EMIT>
 __global__ __launch_bounds__(TP) void ref_blocks_kernel(const RegRec* __restrict__ regions, const int32_t* __restrict__ tile_region,
                                                         const int32_t* __restrict__ depth, const uint8_t* __restrict__ gq,
-                                                        const uint8_t* __restrict__ targets, RefBands bands,
+                                                        const uint8_t* __restrict__ targets, ClassBounds bands,
                                                         int* __restrict__ tile_heads, const int* __restrict__ tile_off,
                                                         RefBlock* __restrict__ blocks, int block_cap) {
     __shared__ uint8_t band_s[TP];
     __shared__ int wave_heads[TP / 64];
     __shared__ int min_dp_s[TP], min_gq_s[TP];       // per head of the tile, by rank (at most one head per row)
-    const int tile = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int region = tile_region[tile];
-    const RegRec* reg = regions + region;
-    const int lo = reg->cand_lo > 0 ? reg->cand_lo : 0;
-    const int hi = reg->cand_hi < reg->L - 1 ? reg->cand_hi : reg->L - 1;
-    const int idx = (tile - reg->tile0) * TP + tid;
-    const bool in = idx >= lo && idx <= hi;          // (idx <= L - 1: a row tile_count_kernel stored a depth and a GQ for)
-    int d = 0, q = 0, band = DEPTH_OFF_TARGET;
-    if (in) {
-        d = depth[reg->row_base + idx];
-        q = gq[reg->row_base + idx];
-        if (targets == nullptr || targets[reg->row_base + idx] != 0) band = ref_band(bands, q);
+    const int tid = threadIdx.x;
+    const TrackRow r = track_row(regions, tile_region);
+    int d = 0, q = 0, band = TRACK_OFF_TARGET;
+    if (r.in) {
+        d = depth[r.at];
+        q = gq[r.at];
+        if (row_on_target(targets, r.at)) band = class_of(bands, q);
     }
     band_s[tid] = (uint8_t)band;
     if (EMIT) {
@@ -1382,29 +1388,26 @@ __global__ __launch_bounds__(TP) void ref_blocks_kernel(const RegRec* __restrict
         min_gq_s[tid] = 0x7fffffff;
     }
     __syncthreads();
-    const bool head = in && (idx == lo || tid == 0 || band_s[tid - 1] != band);
-    const unsigned long long hm = __ballot(head);
-    if (lane == 0) wave_heads[w] = __popcll(hm);
+    // A run is one record PER TILE: a tile's first row inside the window is always a head, and the host joins touching records
+    // of equal band with their minima (variant/RefConfidence.py merge_blocks, BlockTrack).  So every row of the window belongs
+    // to a head of its own tile, and the minima are taken in LDS: atomicMin on the slot of the head's rank among the tile's
+    // heads (a minimum does not depend on the order; no global atomic on the way to the output).
+    const bool head = r.in && (r.idx == r.lo || tid == 0 || band_s[tid - 1] != band);
+    const unsigned long long hm = note_heads(head, wave_heads);
     __syncthreads();
     if (!EMIT) {
-        if (tid == 0) {
-            int n = 0;
-            for (int k = 0; k < TP / 64; ++k) n += wave_heads[k];
-            tile_heads[tile] = n;
-        }
+        store_tile_heads(wave_heads, tile_heads);
         return;
     }
-    // the rank of this row's run among the tile's heads: heads at or before it, less one (>= 0 for every row of the window)
-    int rank = __popcll(hm & ((2ull << lane) - 1ull)) - 1;
-    for (int k = 0; k < w; ++k) rank += wave_heads[k];
-    if (in) {
+    const int rank = head_rank(hm, wave_heads);      // (>= 0 for every row of the window)
+    if (r.in) {
         atomicMin(&min_dp_s[rank], d);
         atomicMin(&min_gq_s[rank], q);
     }
     __syncthreads();
     if (head) {
-        const int slot = tile_off[tile] + rank;
-        if (slot < block_cap) blocks[slot] = RefBlock{region, idx, band, min_dp_s[rank], min_gq_s[rank]};   // past the capacity: emitted again with room
+        const int slot = tile_off[blockIdx.x] + rank;
+        if (slot < block_cap) blocks[slot] = RefBlock{r.region, r.idx, band, min_dp_s[rank], min_gq_s[rank]};   // past the capacity: emitted again with room
     }
 }
 
@@ -1847,23 +1850,22 @@ struct pa_variant_batch {
     std::vector<int32_t> live;        // reads with a base inside each region (the reference's len(all_reads)) of the last run
     DBuf d_zero;                      // counters [CT_N] | per-region counts [2 n_regions] | tile_count [n_tiles] | tile_fill [n_tiles]: cleared per run
     DBuf d_targets;                   // verdicts of target_rows_kernel for the staged batch's rows (pa_encoder_set_targets)
-    // depth classes (pa_encoder_set_depth_bins): the coverage of every row, [totals x n_regions][heads x n_tiles] cleared per
-    // run, the scanned head counts, the run records; of the last run: was it made with bins, their number, its runs, and the
-    // handle's counters (runs made with bins / runs whose records outgrew the buffer and were emitted a second time)
-    DBuf d_depth, d_dzero, d_dscan, d_runs;
+    // The per-position tracks: depth classes (pa_encoder_set_depth_bins) and reference blocks (pa_encoder_set_ref_confidence).
+    // What tile_count_kernel keeps for them, the coverage and the GQ byte of every row; per track the tiles' head counts (every
+    // tile writes its own: nothing to clear), their scan, the records and the record count as the host gets it; of the last
+    // run: was it made with the track's setting, its classes, its records; and the handle's counters (runs made with the
+    // setting / runs whose records outgrew the buffer and were emitted a second time).  The depth track alone has totals:
+    // [DEPTH_TOTALS x n_regions], cleared per run, and their host copy.
+    struct RunTrack {
+        DBuf d_heads, d_scan, d_recs;
+        HBuf h_count;
+        int64_t cap = 0, n = 0, calls = 0, overflows = 0;
+        int classes = 0;
+        bool on = false;
+    };
+    DBuf d_depth, d_gq, d_dtot;
     HBuf h_dtot;
-    int64_t run_cap = 0;
-    bool depth_on = false;
-    int depth_bins = 0;
-    int64_t n_runs = 0, depth_calls = 0, depth_overflows = 0;
-    // reference blocks (pa_encoder_set_ref_confidence): the GQ byte of every row, the tiles' head counts and their scan, the
-    // block records; of the last run: was it made with a table, its records, and the handle's counters as for the depth runs
-    DBuf d_gq, d_bheads, d_bscan, d_blocks;
-    HBuf h_bcount;
-    int64_t block_cap = 0;
-    bool ref_on = false;
-    int ref_bands = 0;
-    int64_t n_blocks = 0, ref_calls = 0, ref_overflows = 0;
+    RunTrack depth, blocks;
     DBuf d_tile_off, d_sorted, d_mat, d_pass, d_sites, d_votes, d_votes_out, d_sites_dense, d_votes_dense, d_ovf, d_cands, d_img32, d_img8;
     HBuf h_counts, h_sites, h_votes;
     // candidates enumerated on the device (pa_encoder_set_device_candidates): the rules of the staged regions, the per-site and
@@ -2000,8 +2002,7 @@ const char* const BATCH_TOO_LARGE = "batch too large: more than 2^30 rows or 2^3
 // a staging call, accepted or refused, leaves no earlier batch staged: first thing in each of them
 void unstage(pa_encoder* e) {
     if (e && e->variant) e->variant->staged = false;
-    if (e && e->variant) e->variant->depth_on = false;      // (the depth runs of the last run speak of its regions)
-    if (e && e->variant) e->variant->ref_on = false;        // (... and so do its reference blocks)
+    if (e && e->variant) e->variant->depth.on = e->variant->blocks.on = false;      // (the last run's records speak of its regions)
 }
 
 struct RegionSums { int64_t rows = 0, ref = 0; int tiles = 0; };      // matrix rows, reference bytes and tiles of the regions so far
@@ -2478,11 +2479,11 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     ta.depth = nullptr;                            // depth bins set: the tile kernel keeps every row's coverage for depth_runs_kernel
     ta.gq = nullptr;                               // a reference-confidence table set: the coverage and the GQ byte for ref_blocks_kernel
     ta.gq_table = nullptr;
-    if (e->n_depth_bins > 0 || e->n_ref_bands > 0) {
+    if (e->depth_bins.n > 0 || e->ref_bands.n > 0) {
         ENC_ALLOC(b.d_depth, (size_t)b.total_rows * 4 + 64);
         ta.depth = b.d_depth.as<int32_t>();
     }
-    if (e->n_ref_bands > 0) {
+    if (e->ref_bands.n > 0) {
         ENC_ALLOC(b.d_gq, (size_t)b.total_rows + 64);
         ta.gq = b.d_gq.as<uint8_t>();
         ta.gq_table = e->d_gq_table.as<uint8_t>();
@@ -2502,135 +2503,137 @@ int submit_counts(pa_encoder* e, const RunShape& w) {
     return PA_OK;
 }
 
-// The depth classes behind everything else of the submission (depth bins set): heads counted and totals summed per tile, the
-// head counts scanned, the runs emitted; the totals and the run count travel with the counters, before the run's one wait.
-// Room for the records: one run per 16 rows and four more per tile -- a sixteenth of the worst case of a run per row (real
-// coverage changes class a few times per kilobase) -- or what PEPPER_AMD_DEPTH_RUN_CAP named when the bins were set, or what an
-// earlier run of the handle needed; a run with more heads than that is emitted a second time (finish_depth_runs).
+// ---- the per-position tracks behind everything else of the submission: the depth classes, then the reference blocks ---------
+using RunTrack = pa_variant_batch::RunTrack;
+struct TrackSlots { int ev, ms; size_t rec_bytes; };     // events ev, ev + 1 around the track's kernels, their time in ms[ms]; a record
+constexpr TrackSlots DEPTH_SLOTS{12, 13, sizeof(DepthRun)}, BLOCK_SLOTS{14, 14, sizeof(RefBlock)};
+
+ClassBounds track_bounds(const RunTrack& t, const pa_track_setting& set) {
+    ClassBounds bounds;
+    bounds.n = t.classes;
+    for (int k = 0; k < TRACK_CLASSES; ++k) bounds.lower[k] = set.lower[k];
+    return bounds;
+}
+
+// the count pass (first the totals cleared: a failure shows at the submission's hipGetLastError) or the emit pass of each track
 void launch_depth_runs(pa_encoder* e, bool emit) {
     pa_variant_batch& b = *e->variant;
-    DepthBins bins;
-    bins.n = b.depth_bins;
-    for (int k = 0; k < DEPTH_MAX_BINS; ++k) bins.lower[k] = e->depth_lower[k];
-    unsigned long long* totals = b.d_dzero.as<unsigned long long>();
-    int* heads = reinterpret_cast<int*>(totals + b.regs.size() * DEPTH_TOTALS);
-    const uint8_t* targets = e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr;
-    if (emit)
-        hipLaunchKernelGGL(depth_runs_kernel<true>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
-                           b.d_depth.as<int32_t>(), targets, bins, heads, b.d_dscan.as<int>(), totals, b.d_runs.as<DepthRun>(), (int)b.run_cap);
-    else
-        hipLaunchKernelGGL(depth_runs_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
-                           b.d_depth.as<int32_t>(), targets, bins, heads, b.d_dscan.as<int>(), totals, b.d_runs.as<DepthRun>(), (int)b.run_cap);
+    if (!emit) (void)hipMemsetAsync(b.d_dtot.p, 0, b.regs.size() * DEPTH_TOTALS * 8, e->stream);
+    hipLaunchKernelGGL(emit ? depth_runs_kernel<true> : depth_runs_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream,
+                       b.p_regions, b.p_tile_region, b.d_depth.as<int32_t>(), e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr,
+                       track_bounds(b.depth, e->depth_bins), b.depth.d_heads.as<int>(), b.depth.d_scan.as<int>(),
+                       b.d_dtot.as<unsigned long long>(), b.depth.d_recs.as<DepthRun>(), (int)b.depth.cap);
 }
-
-int submit_depth_runs(pa_encoder* e, const RunShape& w) {
-    pa_variant_batch& b = *e->variant;
-    hipStream_t st = e->stream;
-    if (e->n_depth_bins <= 0) return PA_OK;
-    b.depth_bins = e->n_depth_bins;
-    const size_t n_tot = (size_t)w.n_regions * DEPTH_TOTALS;
-    const int64_t sized = e->depth_run_cap > 0 ? e->depth_run_cap : b.total_rows / 16 + 4 * (int64_t)b.n_tiles;
-    b.run_cap = std::min<int64_t>(std::max(b.run_cap, sized), 0x7ffffff0);
-    ENC_ALLOC(b.d_dzero, n_tot * 8 + (size_t)b.n_tiles * 4);
-    ENC_ALLOC(b.d_dscan, ((size_t)b.n_tiles + 1) * 4);
-    ENC_ALLOC(b.d_runs, (size_t)b.run_cap * sizeof(DepthRun));
-    if (!b.h_dtot.ensure((n_tot + 1) * 8)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
-    ENC_HIP(hipEventRecord(e->ev[12], st));
-    ENC_HIP(hipMemsetAsync(b.d_dzero.p, 0, n_tot * 8 + (size_t)b.n_tiles * 4, st));
-    launch_depth_runs(e, false);
-    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st,
-                       reinterpret_cast<const int*>(b.d_dzero.as<unsigned long long>() + n_tot), b.n_tiles, b.d_dscan.as<int>());
-    launch_depth_runs(e, true);
-    ENC_HIP(hipEventRecord(e->ev[13], st));
-    ENC_HIP(hipGetLastError());
-    ENC_HIP(hipMemcpyAsync(b.h_dtot.p, b.d_dzero.p, n_tot * 8, hipMemcpyDeviceToHost, st));
-    ENC_HIP(hipMemcpyAsync(b.h_dtot.as<unsigned long long>() + n_tot, b.d_dscan.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
-    return PA_OK;
-}
-
-// after the run's wait: the run count, and the second emit of a run whose records outgrew the buffer (every overflow is
-// counted; the depths, the verdicts and the scanned offsets are where the first emit read them, so the records are exact)
-int finish_depth_runs(pa_encoder* e, const RunShape& w) {
-    pa_variant_batch& b = *e->variant;
-    if (e->n_depth_bins <= 0) return PA_OK;
-    b.depth_calls += 1;
-    b.n_runs = *reinterpret_cast<const int*>(b.h_dtot.as<unsigned long long>() + (size_t)w.n_regions * DEPTH_TOTALS);
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, e->ev[12], e->ev[13]); b.ms[13] = ms;     // depth_runs_kernel x 2 + tile_offsets_kernel
-    b.depth_on = true;
-    if (b.n_runs <= b.run_cap) return PA_OK;
-    b.depth_on = false;                            // (until the second emit is through)
-    b.depth_overflows += 1;
-    b.run_cap = b.n_runs;
-    ENC_ALLOC(b.d_runs, (size_t)b.run_cap * sizeof(DepthRun));
-    launch_depth_runs(e, true);
-    ENC_HIP(hipGetLastError());
-    ENC_HIP(hipStreamSynchronize(e->stream));
-    b.depth_on = true;
-    return PA_OK;
-}
-
-// The reference blocks behind the depth classes, in the same submission (a reference-confidence table set): heads counted per
-// tile, the counts scanned, the blocks emitted with their minima; the block count travels to the host before the run's one
-// wait.  Room as for the depth runs: a record per 16 rows and four per tile, or PEPPER_AMD_REF_BLOCK_CAP as
-// pa_encoder_set_ref_confidence read it, or what an earlier run of the handle needed; more heads: finish_ref_blocks.
 void launch_ref_blocks(pa_encoder* e, bool emit) {
     pa_variant_batch& b = *e->variant;
-    RefBands bands;
-    bands.n = b.ref_bands;
-    for (int k = 0; k < REFCONF_MAX_BANDS; ++k) bands.lower[k] = e->ref_lower[k];
-    const uint8_t* targets = e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr;
-    if (emit)
-        hipLaunchKernelGGL(ref_blocks_kernel<true>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
-                           b.d_depth.as<int32_t>(), b.d_gq.as<uint8_t>(), targets, bands, b.d_bheads.as<int>(), b.d_bscan.as<int>(),
-                           b.d_blocks.as<RefBlock>(), (int)b.block_cap);
-    else
-        hipLaunchKernelGGL(ref_blocks_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream, b.p_regions, b.p_tile_region,
-                           b.d_depth.as<int32_t>(), b.d_gq.as<uint8_t>(), targets, bands, b.d_bheads.as<int>(), b.d_bscan.as<int>(),
-                           b.d_blocks.as<RefBlock>(), (int)b.block_cap);
+    hipLaunchKernelGGL(emit ? ref_blocks_kernel<true> : ref_blocks_kernel<false>, dim3((unsigned)b.n_tiles), dim3(TP), 0, e->stream,
+                       b.p_regions, b.p_tile_region, b.d_depth.as<int32_t>(), b.d_gq.as<uint8_t>(),
+                       e->n_targets > 0 ? b.d_targets.as<uint8_t>() : nullptr, track_bounds(b.blocks, e->ref_bands),
+                       b.blocks.d_heads.as<int>(), b.blocks.d_scan.as<int>(), b.blocks.d_recs.as<RefBlock>(), (int)b.blocks.cap);
 }
 
-int submit_ref_blocks(pa_encoder* e, const RunShape& w) {
+// A track that is set: heads counted per tile, the counts scanned, the records emitted; the record count travels to the host
+// before the run's one wait.  Room for the records: one per 16 rows and four more per tile -- a sixteenth of the worst case of
+// a record per row (real coverage changes class a few times per kilobase) -- or the debug capacity the setting call read from
+// the environment, or what an earlier run of the handle needed; a run with more heads than that is emitted a second time
+// (finish_track).
+int submit_track(pa_encoder* e, RunTrack& t, const pa_track_setting& set, const TrackSlots& slots, void (*launch)(pa_encoder*, bool)) {
     pa_variant_batch& b = *e->variant;
     hipStream_t st = e->stream;
-    (void)w;
-    if (e->n_ref_bands <= 0) return PA_OK;
-    b.ref_bands = e->n_ref_bands;
-    const int64_t sized = e->ref_block_cap > 0 ? e->ref_block_cap : b.total_rows / 16 + 4 * (int64_t)b.n_tiles;
-    b.block_cap = std::min<int64_t>(std::max(b.block_cap, sized), 0x7ffffff0);
-    ENC_ALLOC(b.d_bheads, (size_t)b.n_tiles * 4);            // (every tile writes its count: nothing to clear)
-    ENC_ALLOC(b.d_bscan, ((size_t)b.n_tiles + 1) * 4);
-    ENC_ALLOC(b.d_blocks, (size_t)b.block_cap * sizeof(RefBlock));
-    if (!b.h_bcount.ensure(8)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
-    ENC_HIP(hipEventRecord(e->ev[14], st));
-    launch_ref_blocks(e, false);
-    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, b.d_bheads.as<int>(), b.n_tiles, b.d_bscan.as<int>());
-    launch_ref_blocks(e, true);
-    ENC_HIP(hipEventRecord(e->ev[15], st));
+    t.classes = set.n;
+    const int64_t sized = set.cap > 0 ? set.cap : b.total_rows / 16 + 4 * (int64_t)b.n_tiles;
+    t.cap = std::min<int64_t>(std::max(t.cap, sized), 0x7ffffff0);
+    ENC_ALLOC(t.d_heads, (size_t)b.n_tiles * 4);             // (every tile writes its count: nothing to clear)
+    ENC_ALLOC(t.d_scan, ((size_t)b.n_tiles + 1) * 4);
+    ENC_ALLOC(t.d_recs, (size_t)t.cap * slots.rec_bytes);
+    if (!t.h_count.ensure(8)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+    ENC_HIP(hipEventRecord(e->ev[slots.ev], st));
+    launch(e, false);
+    hipLaunchKernelGGL(tile_offsets_kernel, dim3(1), dim3(1024), 0, st, t.d_heads.as<int>(), b.n_tiles, t.d_scan.as<int>());
+    launch(e, true);
+    ENC_HIP(hipEventRecord(e->ev[slots.ev + 1], st));
     ENC_HIP(hipGetLastError());
-    ENC_HIP(hipMemcpyAsync(b.h_bcount.p, b.d_bscan.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
+    ENC_HIP(hipMemcpyAsync(t.h_count.p, t.d_scan.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
     return PA_OK;
 }
 
-// after the run's wait: the block count, and the second emit of a run whose records outgrew the buffer (counted; depths, GQ
-// bytes, verdicts and scanned offsets are where the first emit read them, so the records are exact)
-int finish_ref_blocks(pa_encoder* e) {
-    pa_variant_batch& b = *e->variant;
-    if (e->n_ref_bands <= 0) return PA_OK;
-    b.ref_calls += 1;
-    b.n_blocks = *b.h_bcount.as<int>();
+// after the run's wait: the record count, and the second emit of a run whose records outgrew the buffer (every overflow is
+// counted; the rows' values, the verdicts and the scanned offsets are where the first emit read them, so the records are exact)
+int finish_track(pa_encoder* e, RunTrack& t, const TrackSlots& slots, void (*launch)(pa_encoder*, bool)) {
+    t.calls += 1;
+    t.n = *t.h_count.as<int>();
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, e->ev[14], e->ev[15]); b.ms[14] = ms;     // ref_blocks_kernel x 2 + tile_offsets_kernel
-    b.ref_on = true;
-    if (b.n_blocks <= b.block_cap) return PA_OK;
-    b.ref_on = false;                              // (until the second emit is through)
-    b.ref_overflows += 1;
-    b.block_cap = b.n_blocks;
-    ENC_ALLOC(b.d_blocks, (size_t)b.block_cap * sizeof(RefBlock));
-    launch_ref_blocks(e, true);
+    (void)hipEventElapsedTime(&ms, e->ev[slots.ev], e->ev[slots.ev + 1]); e->variant->ms[slots.ms] = ms;     // the track's kernel x 2 + tile_offsets_kernel
+    t.on = true;
+    if (t.n <= t.cap) return PA_OK;
+    t.on = false;                                  // (until the second emit is through)
+    t.overflows += 1;
+    t.cap = t.n;
+    ENC_ALLOC(t.d_recs, (size_t)t.cap * slots.rec_bytes);
+    launch(e, true);
     ENC_HIP(hipGetLastError());
     ENC_HIP(hipStreamSynchronize(e->stream));
-    b.ref_on = true;
+    t.on = true;
+    return PA_OK;
+}
+
+int submit_tracks(pa_encoder* e, const RunShape& w) {
+    pa_variant_batch& b = *e->variant;
+    if (e->depth_bins.n > 0) {
+        const size_t tot_bytes = (size_t)w.n_regions * DEPTH_TOTALS * 8;
+        ENC_ALLOC(b.d_dtot, tot_bytes);
+        if (!b.h_dtot.ensure(tot_bytes)) return pa::set_error(PA_ERR_HIP, "hipHostMalloc failed");
+        const int rc = submit_track(e, b.depth, e->depth_bins, DEPTH_SLOTS, launch_depth_runs);
+        if (rc != PA_OK) return rc;
+        ENC_HIP(hipMemcpyAsync(b.h_dtot.p, b.d_dtot.p, tot_bytes, hipMemcpyDeviceToHost, e->stream));
+    }
+    return e->ref_bands.n > 0 ? submit_track(e, b.blocks, e->ref_bands, BLOCK_SLOTS, launch_ref_blocks) : PA_OK;
+}
+
+int finish_tracks(pa_encoder* e) {
+    pa_variant_batch& b = *e->variant;
+    const int rc = e->depth_bins.n > 0 ? finish_track(e, b.depth, DEPTH_SLOTS, launch_depth_runs) : PA_OK;
+    return rc == PA_OK && e->ref_bands.n > 0 ? finish_track(e, b.blocks, BLOCK_SLOTS, launch_ref_blocks) : rc;
+}
+
+// The records of the last run's track into the caller's columns (null: not wanted; `wanted`: one of them is not null): region,
+// start and end for every track, `rest(k, record)` for the columns of this one.  what / noun: how the messages begin and what
+// they call a record.
+inline int32_t reported_class(int cls) { return cls == TRACK_OFF_TARGET ? -1 : cls; }
+
+template <typename Rec, typename Rest>
+int fetch_track(pa_encoder* e, const RunTrack& t, const char* what, const char* noun, bool wanted, int64_t capacity, int32_t* region,
+                int64_t* start, int64_t* end, int64_t* n_out, Rest rest) {
+    const pa_variant_batch& b = *e->variant;
+    if (n_out) *n_out = t.n;
+    if (!wanted) return PA_OK;
+    if (capacity < t.n)
+        return pa::set_error(PA_ERR_INVALID, std::string(what) + ": " + std::to_string(t.n) + " " + noun + ", room for " + std::to_string(capacity));
+    if (t.n == 0) return PA_OK;
+    ENC_HIP(hipSetDevice(e->device));
+    std::vector<Rec> recs((size_t)t.n);
+    ENC_HIP(hipMemcpyAsync(recs.data(), t.d_recs.p, recs.size() * sizeof(Rec), hipMemcpyDeviceToHost, e->stream));
+    ENC_HIP(hipStreamSynchronize(e->stream));
+    for (size_t k = 0; k < recs.size(); ++k) {
+        const Rec& r = recs[k];
+        if (r.region < 0 || r.region >= (int)b.regs.size() || (k > 0 && r.region < recs[k - 1].region))
+            return pa::set_error(PA_ERR_HIP, std::string(what) + ": record " + std::to_string(k) + " names no region of the batch");
+        const RegHost& rh = b.regs[(size_t)r.region];
+        // a record ends where the next one of its region starts, the last one behind the window's last row
+        const int64_t window_end = std::min<int64_t>(rh.L - 1, rh.q.candidate_region_end - rh.p.region_start) + 1;
+        const int64_t stop = (k + 1 < recs.size() && recs[k + 1].region == r.region) ? recs[k + 1].row : window_end;
+        if (region) region[k] = r.region;
+        if (start) start[k] = rh.p.region_start + r.row;
+        if (end) end[k] = rh.p.region_start + stop;
+        rest(k, r);
+    }
+    return PA_OK;
+}
+
+int track_calls(pa_encoder* e, RunTrack pa_variant_batch::*track, int64_t* runs, int64_t* overflows) {
+    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
+    if (runs) *runs = e->variant ? (e->variant->*track).calls : 0;
+    if (overflows) *overflows = e->variant ? (e->variant->*track).overflows : 0;
     return PA_OK;
 }
 
@@ -2838,16 +2841,11 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     b.region_n.assign((size_t)n_regions, 0);
     b.positions.clear(); b.depths.clear(); b.freqs.clear(); b.names.clear();
     b.dev_results = b.dev_lists = false;
-    b.depth_on = false;
-    b.n_runs = 0;
-    b.ref_on = false;
-    b.n_blocks = 0;
+    for (RunTrack* t : {&b.depth, &b.blocks}) { t->on = false; t->n = 0; }
     for (int k = 0; k < 8; ++k) b.ms[k] = 0;          // ([8], [9] belong to the staging of this batch)
     if (n_regions == 0) {
-        b.depth_on = e->n_depth_bins > 0;         // (no region: no run, no total)
-        b.depth_bins = e->n_depth_bins;
-        b.ref_on = e->n_ref_bands > 0;
-        b.ref_bands = e->n_ref_bands;
+        b.depth.on = (b.depth.classes = e->depth_bins.n) > 0;       // (no region: no record, no total)
+        b.blocks.on = (b.blocks.classes = e->ref_bands.n) > 0;
         return PA_OK;
     }
     const auto t_begin = std::chrono::steady_clock::now();
@@ -2873,8 +2871,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
     for (int attempt = 0;; ++attempt) {       // one submission and one wait each; repeated with room when a buffer was too small
         rc = submit_counts(e, w);
         if (rc == PA_OK && w.dev) rc = submit_candidates(e, w);
-        if (rc == PA_OK) rc = submit_depth_runs(e, w);
-        if (rc == PA_OK) rc = submit_ref_blocks(e, w);
+        if (rc == PA_OK) rc = submit_tracks(e, w);
         if (rc != PA_OK) return rc;
         ENC_HIP(hipMemcpyAsync(host_counters, w.counters, ((size_t)CT_N + 2 * (size_t)n_regions) * 4, hipMemcpyDeviceToHost, st));
         ENC_HIP(hipMemcpyAsync(host_counters + CT_N + 2 * n_regions, b.d_tile_off.as<int>() + b.n_tiles, sizeof(int), hipMemcpyDeviceToHost, st));
@@ -2907,8 +2904,7 @@ int run_staged(pa_encoder* e, int64_t* n_candidates) {
         (void)hipEventElapsedTime(&ms, e->ev[7], e->ev[8]); b.ms[9] = ms;   // unpack_clip_kernel
     }
     rc = check_reports(e, w);
-    if (rc == PA_OK) rc = finish_depth_runs(e, w);
-    if (rc == PA_OK) rc = finish_ref_blocks(e);
+    if (rc == PA_OK) rc = finish_tracks(e);
     if (rc == PA_OK) rc = on_device ? take_device_results(e, w, n_candidates) : enumerate_on_host(e, w, n_candidates);
     if (rc != PA_OK) return rc;
     b.ms[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();  // whole run, host clock
@@ -3465,80 +3461,52 @@ int pa_encoder_set_targets(pa_encoder* e, int64_t n, const int64_t* start, const
 
 int pa_encoder_set_depth_bins(pa_encoder* e, int32_t n, const int32_t* lower) {
     if (!e || n < 0 || (n > 0 && !lower)) return pa::set_error(PA_ERR_INVALID, "null argument");
-    if (n > DEPTH_MAX_BINS) return pa::set_error(PA_ERR_INVALID, "depth bins: entry 8 is one more than the 8 bins a table may have");
+    if (n > TRACK_CLASSES) return pa::set_error(PA_ERR_INVALID, "depth bins: entry 8 is one more than the 8 bins a table may have");
     for (int32_t k = 0; k < n; ++k)                // (checked in full before anything of the handle changes)
         if (k == 0 ? lower[0] != 0 : lower[k] <= lower[k - 1])
             return pa::set_error(PA_ERR_INVALID, "depth bins: entry " + std::to_string(k) +
                                                      (k == 0 ? " must be 0" : " is not above the one before it"));
-    e->n_depth_bins = n;
-    for (int32_t k = 0; k < DEPTH_MAX_BINS; ++k) e->depth_lower[k] = k < n ? lower[k] : 0;
-    const char* cap = n > 0 ? getenv("PEPPER_AMD_DEPTH_RUN_CAP") : nullptr;     // (debug: tests/test_gpu_coverage.py makes a run overflow with it)
-    e->depth_run_cap = cap ? std::max<int64_t>(0, atoll(cap)) : 0;
+    e->depth_bins.set(n, lower, "PEPPER_AMD_DEPTH_RUN_CAP");     // (the capacity is for debugging: tests/test_gpu_coverage.py makes a run overflow with it)
     return PA_OK;
 }
 
 int pa_encoder_depth_runs(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* bin, int64_t* n_runs) {
     if (!e || capacity < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    if (!e->variant || !e->variant->depth_on) return pa::set_error(PA_ERR_INVALID, "depth runs: the handle's last run had no depth bins set");
-    pa_variant_batch& b = *e->variant;
-    if (n_runs) *n_runs = b.n_runs;
-    if (!region && !start && !end && !bin) return PA_OK;
-    if (capacity < b.n_runs)
-        return pa::set_error(PA_ERR_INVALID, "depth runs: " + std::to_string(b.n_runs) + " runs, room for " + std::to_string(capacity));
-    if (b.n_runs == 0) return PA_OK;
-    ENC_HIP(hipSetDevice(e->device));
-    std::vector<DepthRun> runs((size_t)b.n_runs);
-    ENC_HIP(hipMemcpyAsync(runs.data(), b.d_runs.p, runs.size() * sizeof(DepthRun), hipMemcpyDeviceToHost, e->stream));
-    ENC_HIP(hipStreamSynchronize(e->stream));
-    for (size_t k = 0; k < runs.size(); ++k) {
-        const DepthRun& r = runs[k];
-        if (r.region < 0 || r.region >= (int)b.regs.size() || (k > 0 && r.region < runs[k - 1].region))
-            return pa::set_error(PA_ERR_HIP, "depth runs: record " + std::to_string(k) + " names no region of the batch");
-        const RegHost& rh = b.regs[(size_t)r.region];
-        // a run ends where the next one of its region starts, the last one behind the window's last row
-        const int64_t window_end = std::min<int64_t>(rh.L - 1, rh.q.candidate_region_end - rh.p.region_start) + 1;
-        const int64_t stop = (k + 1 < runs.size() && runs[k + 1].region == r.region) ? runs[k + 1].row : window_end;
-        if (region) region[k] = r.region;
-        if (start) start[k] = rh.p.region_start + r.row;
-        if (end) end[k] = rh.p.region_start + stop;
-        if (bin) bin[k] = r.bin == DEPTH_OFF_TARGET ? -1 : r.bin;
-    }
-    return PA_OK;
+    if (!e->variant || !e->variant->depth.on) return pa::set_error(PA_ERR_INVALID, "depth runs: the handle's last run had no depth bins set");
+    return fetch_track<DepthRun>(e, e->variant->depth, "depth runs", "runs", region || start || end || bin, capacity, region, start, end, n_runs,
+                                 [&](size_t k, const DepthRun& r) { if (bin) bin[k] = reported_class(r.bin); });
 }
 
 int pa_encoder_depth_totals(pa_encoder* e, int32_t n_regions, int64_t* bases, int64_t* depth_sum) {
     if (!e || n_regions < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    if (!e->variant || !e->variant->depth_on) return pa::set_error(PA_ERR_INVALID, "depth totals: the handle's last run had no depth bins set");
+    if (!e->variant || !e->variant->depth.on) return pa::set_error(PA_ERR_INVALID, "depth totals: the handle's last run had no depth bins set");
     pa_variant_batch& b = *e->variant;
     if (n_regions > (int32_t)b.regs.size()) return pa::set_error(PA_ERR_INVALID, "depth totals: more regions than the last run had");
     const unsigned long long* tot = b.h_dtot.as<unsigned long long>();
     for (int32_t r = 0; r < n_regions; ++r) {
         if (bases)
-            for (int k = 0; k < DEPTH_MAX_BINS; ++k) bases[(size_t)r * DEPTH_MAX_BINS + k] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + k];
-        if (depth_sum) depth_sum[r] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + DEPTH_MAX_BINS];
+            for (int k = 0; k < TRACK_CLASSES; ++k) bases[(size_t)r * TRACK_CLASSES + k] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + k];
+        if (depth_sum) depth_sum[r] = (int64_t)tot[(size_t)r * DEPTH_TOTALS + TRACK_CLASSES];
     }
     return PA_OK;
 }
 
 int pa_encoder_depth_calls(pa_encoder* e, int64_t* runs_with_bins, int64_t* overflows) {
-    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
-    if (runs_with_bins) *runs_with_bins = e->variant ? e->variant->depth_calls : 0;
-    if (overflows) *overflows = e->variant ? e->variant->depth_overflows : 0;
-    return PA_OK;
+    return track_calls(e, &pa_variant_batch::depth, runs_with_bins, overflows);
 }
 
 int pa_encoder_set_ref_confidence(pa_encoder* e, const uint8_t* table, int32_t table_side, int32_t n_bands, const int32_t* lower) {
     if (!e || n_bands < 0 || (n_bands > 0 && (!lower || !table))) return pa::set_error(PA_ERR_INVALID, "null argument");
     if (n_bands == 0) {
-        e->n_ref_bands = 0;
-        e->ref_block_cap = 0;
+        e->ref_bands.n = 0;
+        e->ref_bands.cap = 0;
         return PA_OK;
     }
     // (checked in full before anything of the handle changes)
     if (table_side != REFCONF_SIDE)
         return pa::set_error(PA_ERR_INVALID, "reference confidence: a table of side " + std::to_string(table_side) + ", not " +
                                                  std::to_string(REFCONF_SIDE));
-    if (n_bands > REFCONF_MAX_BANDS)
+    if (n_bands > TRACK_CLASSES)
         return pa::set_error(PA_ERR_INVALID, "reference confidence: band 8 is one more than the 8 bands a table may have");
     for (int32_t k = 0; k < n_bands; ++k)
         if (k == 0 ? lower[0] != 0 : (lower[k] <= lower[k - 1] || lower[k] > 255))
@@ -3559,51 +3527,25 @@ int pa_encoder_set_ref_confidence(pa_encoder* e, const uint8_t* table, int32_t t
     ENC_ALLOC(e->d_gq_table, (size_t)REFCONF_SIDE * REFCONF_SIDE);
     ENC_HIP(hipMemcpyAsync(e->d_gq_table.p, table, (size_t)REFCONF_SIDE * REFCONF_SIDE, hipMemcpyHostToDevice, e->stream));
     ENC_HIP(hipStreamSynchronize(e->stream));
-    e->n_ref_bands = n_bands;
-    for (int32_t k = 0; k < REFCONF_MAX_BANDS; ++k) e->ref_lower[k] = k < n_bands ? lower[k] : 0;
-    const char* cap = getenv("PEPPER_AMD_REF_BLOCK_CAP");      // (debug: tests/test_gpu_refconf.py makes a run overflow with it)
-    e->ref_block_cap = cap ? std::max<int64_t>(0, atoll(cap)) : 0;
+    e->ref_bands.set(n_bands, lower, "PEPPER_AMD_REF_BLOCK_CAP");     // (the capacity is for debugging: tests/test_gpu_refconf.py makes a run overflow with it)
     return PA_OK;
 }
 
 int pa_encoder_ref_blocks(pa_encoder* e, int64_t capacity, int32_t* region, int64_t* start, int64_t* end, int32_t* band, int32_t* min_dp,
                           int32_t* min_gq, int64_t* n_blocks) {
     if (!e || capacity < 0) return pa::set_error(PA_ERR_INVALID, "null argument");
-    if (!e->variant || !e->variant->ref_on)
+    if (!e->variant || !e->variant->blocks.on)
         return pa::set_error(PA_ERR_INVALID, "reference blocks: the handle's last run had no reference-confidence table set");
-    pa_variant_batch& b = *e->variant;
-    if (n_blocks) *n_blocks = b.n_blocks;
-    if (!region && !start && !end && !band && !min_dp && !min_gq) return PA_OK;
-    if (capacity < b.n_blocks)
-        return pa::set_error(PA_ERR_INVALID, "reference blocks: " + std::to_string(b.n_blocks) + " blocks, room for " + std::to_string(capacity));
-    if (b.n_blocks == 0) return PA_OK;
-    ENC_HIP(hipSetDevice(e->device));
-    std::vector<RefBlock> blocks((size_t)b.n_blocks);
-    ENC_HIP(hipMemcpyAsync(blocks.data(), b.d_blocks.p, blocks.size() * sizeof(RefBlock), hipMemcpyDeviceToHost, e->stream));
-    ENC_HIP(hipStreamSynchronize(e->stream));
-    for (size_t k = 0; k < blocks.size(); ++k) {
-        const RefBlock& r = blocks[k];
-        if (r.region < 0 || r.region >= (int)b.regs.size() || (k > 0 && r.region < blocks[k - 1].region))
-            return pa::set_error(PA_ERR_HIP, "reference blocks: record " + std::to_string(k) + " names no region of the batch");
-        const RegHost& rh = b.regs[(size_t)r.region];
-        // a block ends where the next one of its region starts, the last one behind the window's last row
-        const int64_t window_end = std::min<int64_t>(rh.L - 1, rh.q.candidate_region_end - rh.p.region_start) + 1;
-        const int64_t stop = (k + 1 < blocks.size() && blocks[k + 1].region == r.region) ? blocks[k + 1].row : window_end;
-        if (region) region[k] = r.region;
-        if (start) start[k] = rh.p.region_start + r.row;
-        if (end) end[k] = rh.p.region_start + stop;
-        if (band) band[k] = r.band == DEPTH_OFF_TARGET ? -1 : r.band;
-        if (min_dp) min_dp[k] = r.min_dp;
-        if (min_gq) min_gq[k] = r.min_gq;
-    }
-    return PA_OK;
+    return fetch_track<RefBlock>(e, e->variant->blocks, "reference blocks", "blocks", region || start || end || band || min_dp || min_gq,
+                                 capacity, region, start, end, n_blocks, [&](size_t k, const RefBlock& r) {
+                                     if (band) band[k] = reported_class(r.band);
+                                     if (min_dp) min_dp[k] = r.min_dp;
+                                     if (min_gq) min_gq[k] = r.min_gq;
+                                 });
 }
 
 int pa_encoder_ref_calls(pa_encoder* e, int64_t* runs, int64_t* overflows) {
-    if (!e) return pa::set_error(PA_ERR_INVALID, "null encoder");
-    if (runs) *runs = e->variant ? e->variant->ref_calls : 0;
-    if (overflows) *overflows = e->variant ? e->variant->ref_overflows : 0;
-    return PA_OK;
+    return track_calls(e, &pa_variant_batch::blocks, runs, overflows);
 }
 
 int pa_encoder_candidate_calls(pa_encoder* e, int64_t* on_device, int64_t* on_host) {

@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <string>
@@ -152,6 +153,19 @@ struct pa_sampler {
     pa_enc::HBuf h_tab;
 };
 
+// The setting of a per-position track of the variant encoder (encoder.hip: depth classes, reference blocks).
+struct pa_track_setting {
+    int32_t n = 0;                   // classes (0: the track is off) ...
+    int32_t lower[8] = {};           // ... and their ascending lower bounds, lower[0] == 0
+    int64_t cap = 0;                 // the track's debug capacity from the environment, as the setting call read it (0: sized by the batch)
+    void set(int32_t n_classes, const int32_t* bounds, const char* cap_env) {
+        n = n_classes;
+        for (int32_t k = 0; k < 8; ++k) lower[k] = k < n ? bounds[k] : 0;
+        const char* text = n > 0 ? getenv(cap_env) : nullptr;
+        cap = text ? std::max<int64_t>(0, atoll(text)) : 0;
+    }
+};
+
 struct pa_variant_batch;     // encoder.hip
 struct pa_polish_batch;      // encoder_polish.hip
 
@@ -167,13 +181,9 @@ struct pa_encoder {
     bool split_walk = false;                       // pa_encoder_set_split_slices: the record walk resolves CIGARs kept in the CG tag
     int64_t n_targets = 0;                         // pa_encoder_set_targets: intervals of the table (0: no restriction) ...
     pa_enc::DBuf d_target_table;                   // ... [start x n][end x n] on the device
-    int32_t n_depth_bins = 0;                      // pa_encoder_set_depth_bins: bins of the depth classes (0: the feature is off) ...
-    int32_t depth_lower[8] = {};                   // ... and their ascending lower bounds, depth_lower[0] == 0
-    int64_t depth_run_cap = 0;                     // ... PEPPER_AMD_DEPTH_RUN_CAP as that call read it (0: sized by the batch)
-    int32_t n_ref_bands = 0;                       // pa_encoder_set_ref_confidence: bands of the reference blocks (0: the feature is off) ...
-    int32_t ref_lower[8] = {};                     // ... their ascending lower bounds of GQ, ref_lower[0] == 0 ...
-    pa_enc::DBuf d_gq_table;                       // ... the 101 x 101 uint8 table [n_ref][n_alt] -> GQ on the device ...
-    int64_t ref_block_cap = 0;                     // ... PEPPER_AMD_REF_BLOCK_CAP as that call read it (0: sized by the batch)
+    pa_track_setting depth_bins;                   // pa_encoder_set_depth_bins: the bins of the depth classes (cap: PEPPER_AMD_DEPTH_RUN_CAP)
+    pa_track_setting ref_bands;                    // pa_encoder_set_ref_confidence: the GQ bands of the reference blocks (cap: PEPPER_AMD_REF_BLOCK_CAP) ...
+    pa_enc::DBuf d_gq_table;                       // ... and the 101 x 101 uint8 table [n_ref][n_alt] -> GQ on the device
     std::vector<int64_t> seq_off;                  // pa_encoder_set_seq_offsets: per packed read of the NEXT staging where its bases lie (-1: behind its operations)
 };
 

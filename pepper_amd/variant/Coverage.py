@@ -13,12 +13,13 @@ is open above.  `runs_numpy` is the device's rule in numpy; `CoverageTrack` coll
 PEPPER_VARIANT_COVERAGE.bed: contig, start, end (0-based, half-open), label.
 """
 import math
-import threading
 
 import numpy as np
 
-MAX_BINS = 8
-OFF_TARGET = -1                      # the bin of a position outside every target (pa_encoder_set_targets): never written
+from pepper_amd.variant import RunTracks
+from pepper_amd.variant.RunTracks import OFF_TARGET        # the bin of a position outside every target: never written
+
+MAX_BINS = RunTracks.MAX_CLASSES
 BED_NAME = "PEPPER_VARIANT_COVERAGE.bed"
 
 
@@ -42,26 +43,7 @@ def parse_bins(bins=None, min_coverage_threshold=None):
             raise ValueError("coverage bins: neither bins nor min_coverage_threshold given")
         bounds, labels = default_bins(min_coverage_threshold)
         return np.array(bounds, np.int32), labels
-    fields = [f.strip() for f in bins.split(",")] if isinstance(bins, str) else list(bins)
-    if len(fields) == 0:
-        raise ValueError("coverage bins: no bin")
-    if len(fields) > MAX_BINS:
-        raise ValueError("coverage bins: entry %d is one more than the %d bins a table may have" % (MAX_BINS, MAX_BINS))
-    bounds = []
-    for k, field in enumerate(fields):
-        try:
-            if isinstance(field, (float, np.floating)) and float(field) != int(field):
-                raise ValueError
-            value = int(field)
-        except (TypeError, ValueError):
-            raise ValueError("coverage bins: entry %d (%r) is not an integer" % (k, field)) from None
-        if k == 0 and value != 0:
-            raise ValueError("coverage bins: entry 0 must be 0, not %d" % value)
-        if k > 0 and value <= bounds[-1]:
-            raise ValueError("coverage bins: entry %d (%d) is not above the one before it (%d)" % (k, value, bounds[-1]))
-        if value >= 1 << 31:
-            raise ValueError("coverage bins: entry %d (%d) does not fit 31 bits" % (k, value))
-        bounds.append(value)
+    bounds = RunTracks.parse_bounds(bins, "coverage bins", "bin", lambda v: "does not fit 31 bits" if v >= 1 << 31 else None).tolist()
     labels = ["%d:%d" % (lo, hi) for lo, hi in zip(bounds, bounds[1:])] + ["%d:inf" % bounds[-1]]
     return np.array(bounds, np.int32), labels
 
@@ -70,77 +52,41 @@ def runs_numpy(depths, first_position, bins, on_target=None):
     """The rule of depth_runs_kernel: depths[i] is the depth of position first_position + i -> (starts, ends, bins) of the
     maximal runs of equal bin, int64 / int64 / int32, ends half-open.  on_target (bool per position; None: all): a position
     outside has the bin OFF_TARGET, and its runs are reported like any other."""
-    depths = np.asarray(depths, np.int64)
-    bounds = np.asarray(bins, np.int64)
-    which = (np.searchsorted(bounds, depths, side="right") - 1).astype(np.int32)
-    if on_target is not None:
-        which = np.where(np.asarray(on_target, bool), which, np.int32(OFF_TARGET)).astype(np.int32)
-    n = len(which)
-    if n == 0:
-        return np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32)
-    heads = np.flatnonzero(np.concatenate([[True], which[1:] != which[:-1]]))
-    starts = heads.astype(np.int64) + int(first_position)
-    ends = np.concatenate([heads[1:], [n]]).astype(np.int64) + int(first_position)
-    return starts, ends, which[heads]
+    return RunTracks.class_runs(depths, first_position, bins, on_target)
 
 
 def totals_numpy(depths, bins, on_target=None):
     """-> (bases per bin int64 [8], sum of depths): what pa_encoder_depth_totals reports for a region with these depths."""
     depths = np.asarray(depths, np.int64)
     keep = np.ones(len(depths), bool) if on_target is None else np.asarray(on_target, bool)
-    which = np.searchsorted(np.asarray(bins, np.int64), depths[keep], side="right") - 1
+    which = RunTracks.classes_of(depths[keep], bins)
     return np.bincount(which, minlength=MAX_BINS).astype(np.int64)[:MAX_BINS], int(depths[keep].sum())
 
 
-class CoverageTrack(object):
-    """The runs of a whole job, collected from its workers in any order (add) and finished once (finish / write).
+class CoverageTrack(RunTracks.RunTrack):
+    """The runs of a whole job, collected from its workers in any order (add) and finished once (finish / write): finish ->
+    [(contig, start, end, bin)] in FASTA order.
 
     contigs: the FASTA's contig names in its order; bins, labels: what parse_bins returned."""
+    what = "coverage track"
 
     def __init__(self, contigs, bins, labels):
-        self.order = {name: k for k, name in enumerate(contigs)}
+        super().__init__(contigs)
         self.bins = np.asarray(bins, np.int32)
         self.labels = list(labels)
         if len(self.labels) != len(self.bins):
             raise ValueError("coverage track: one label per bin")
-        self._lock = threading.Lock()
-        self._pieces = []
         self.depth_sum = 0
         self.depth_bases = 0
 
     def add(self, contig, interval, runs, totals=None):
         """One interval of the planner: interval = (pos_start, pos_end), both inclusive; runs = (starts, ends, bins) of its
         window in contig coordinates, ascending; totals = (bases per bin, sum of depths) or None."""
-        if contig not in self.order:
-            raise ValueError("coverage track: contig %r is not in the FASTA" % (contig,))
-        starts, ends, which = (np.array(v, dtype) for v, dtype in zip(runs, (np.int64, np.int64, np.int32)))
-        if not (len(starts) == len(ends) == len(which)):
-            raise ValueError("coverage track: runs of unequal lengths")
-        with self._lock:
-            self._pieces.append((self.order[contig], int(interval[0]), int(interval[1]), contig, starts, ends, which))
-            if totals is not None:
+        super().add(contig, interval, runs)
+        if totals is not None:
+            with self._lock:
                 self.depth_bases += int(np.asarray(totals[0], np.int64).sum())
                 self.depth_sum += int(totals[1])
-
-    def finish(self):
-        """-> [(contig, start, end, bin)] in FASTA order: the pieces ordered by contig and start; the position two consecutive
-        intervals of split_intervals share (pos_end of one == pos_start of the next) belongs to the one that starts there -- the
-        earlier interval's runs are cut at the next interval's start and dropped when nothing is left; off-target runs dropped;
-        touching runs of equal bin merged."""
-        with self._lock:
-            pieces = sorted(self._pieces, key=lambda p: p[:3])
-        out = []
-        for k, (_rank, _s, _e, contig, starts, ends, which) in enumerate(pieces):
-            if k + 1 < len(pieces) and pieces[k + 1][0] == pieces[k][0]:
-                ends = np.minimum(ends, pieces[k + 1][1])          # the next interval of the contig owns everything from its start
-            for s, e, b in zip(starts.tolist(), ends.tolist(), which.tolist()):
-                if s >= e or b == OFF_TARGET:
-                    continue
-                if out and out[-1][0] == contig and out[-1][2] == s and out[-1][3] == b:
-                    out[-1] = (contig, out[-1][1], e, b)
-                else:
-                    out.append((contig, s, e, b))
-        return out
 
     def write(self, path):
         """The BED -> the finished runs."""

@@ -220,44 +220,43 @@ class ImageGenerationUtils:
             mine[key] = mine.get(key, 0.0) + now - t0
             return now
 
-        def collect_depth(depth, group):
-            """The depth runs and totals of the encoder call that covered `group` (depth: the PackedEncoder, or what
-            thread_depth_bins yields), interval by interval into the track."""
-            region, starts, ends, which = depth.depth_runs()
-            bases, sums = depth.depth_totals(len(group))
-            cut = np.searchsorted(region, np.arange(len(group) + 1))          # (the runs come in region order)
-            for r, (chr_name, _start, _end) in enumerate(group):
-                a, b = int(cut[r]), int(cut[r + 1])
-                track.add(chr_name, (_start, _end), (starts[a:b], ends[a:b], which[a:b]), (bases[r], sums[r]))
-            mine["coverage_runs"] += len(region)
-
-        def empty_depth(chr_name, _start, _end):
-            """An interval without a read is never encoded by the host-clipped form: every position of it has depth 0."""
-            on_target = None
-            if bed_list is not None:
-                on_target = Targets.contains(*Targets.table(bed_list, chr_name), np.arange(_start, _end + 1, dtype=np.int64))
-            zeros = np.zeros(_end - _start + 1, np.int64)
-            track.add(chr_name, (_start, _end), Coverage.runs_numpy(zeros, _start, track.bins, on_target),
-                      Coverage.totals_numpy(zeros, track.bins, on_target))
-
-        def collect_blocks(source, group):
-            """The reference blocks of the encoder call that covered `group` (source: the PackedEncoder, or what
-            thread_ref_confidence yields), interval by interval into the gVCF's track (which merges the records of a run that
-            crossed a tile border)."""
-            region, starts, ends, band, min_dp, min_gq = source.ref_blocks()
+        def collect(source, group, into, fetch):
+            """The records of the encoder call that covered `group`, interval by interval into a track -> their number.  source:
+            the PackedEncoder, or what thread_depth_bins / thread_ref_confidence yield; fetch(source, n) -> (the records, their
+            region first, and None or the (bases, sums) of the n intervals)."""
+            (region, *cols), totals = fetch(source, len(group))
             cut = np.searchsorted(region, np.arange(len(group) + 1))          # (the records come in region order)
             for r, (chr_name, _start, _end) in enumerate(group):
                 a, b = int(cut[r]), int(cut[r + 1])
-                gtrack.add(chr_name, (_start, _end), (starts[a:b], ends[a:b], band[a:b], min_dp[a:b], min_gq[a:b]))
-            mine["gvcf_records"] += len(region)
+                into.add(chr_name, (_start, _end), tuple(c[a:b] for c in cols), *([] if totals is None else [(totals[0][r], totals[1][r])]))
+            return len(region)
+
+        def collect_depth(source, group):
+            mine["coverage_runs"] += collect(source, group, track, lambda s, n: (s.depth_runs(), s.depth_totals(n)))
+
+        def collect_blocks(source, group):
+            """(the gVCF's track merges the records of a run that crossed a tile border)"""
+            mine["gvcf_records"] += collect(source, group, gtrack, lambda s, n: (s.ref_blocks(), None))
             mine["gvcf_kernel_ms"] += source.ref_blocks_ms()
 
-        def empty_blocks(chr_name, _start, _end):
-            """An interval without a read is never encoded by the host-clipped form: depth 0 and GQ 0 at every position."""
-            on_target = None
-            if bed_list is not None:
-                on_target = Targets.contains(*Targets.table(bed_list, chr_name), np.arange(_start, _end + 1, dtype=np.int64))
-            gtrack.add_empty(chr_name, (_start, _end), on_target)
+        def empty_on_target(chr_name, _start, _end):
+            """An interval without a read is never encoded by the host-clipped form: every position of it has depth 0 and GQ 0.
+            -> which of them lie inside a target (None: no BED, all)."""
+            if bed_list is None:
+                return None
+            return Targets.contains(*Targets.table(bed_list, chr_name), np.arange(_start, _end + 1, dtype=np.int64))
+
+        @contextlib.contextmanager
+        def counting(prefix, calls, switch_off=None):
+            """While the block runs: the encoder calls made with a track's setting and those among them whose records outgrew
+            the buffer (calls() -> both, since the handle was created) into `mine`; behind it the setting off the handle."""
+            before = calls()
+            yield
+            after = calls()
+            mine[prefix + "_calls"] += after[0] - before[0]
+            mine[prefix + "_overflows"] += after[1] - before[1]
+            if switch_off is not None:
+                switch_off()
 
         def summaries_of(prepared, group):
             """create_summaries of one host-clipped call; with a track, under this thread's depth bins and collected, with a
@@ -267,28 +266,24 @@ class ImageGenerationUtils:
             from pepper_amd.variant.PEPPER_VARIANT import thread_depth_bins, thread_ref_confidence
             live = [g for g, p in zip(group, prepared) if p is not None]
             with contextlib.ExitStack() as stack:
-                depth = stack.enter_context(thread_depth_bins(track.bins, device)) if track is not None else None
-                conf = stack.enter_context(thread_ref_confidence(gtrack.table, gtrack.bands, device)) if gtrack is not None else None
-                before = depth.depth_calls() if depth is not None else None
-                conf_before = conf.ref_calls() if conf is not None else None
+                if track is not None:
+                    depth = stack.enter_context(thread_depth_bins(track.bins, device))
+                    stack.enter_context(counting("coverage", depth.depth_calls))
+                if gtrack is not None:
+                    conf = stack.enter_context(thread_ref_confidence(gtrack.table, gtrack.bands, device))
+                    stack.enter_context(counting("gvcf", conf.ref_calls))
                 outs = create_summaries(prepared)
-                if live and depth is not None:
+                if live and track is not None:
                     collect_depth(depth, live)
-                if live and conf is not None:
+                if live and gtrack is not None:
                     collect_blocks(conf, live)
-                if depth is not None:
-                    after = depth.depth_calls()
-                    mine["coverage_calls"] += after[0] - before[0]
-                    mine["coverage_overflows"] += after[1] - before[1]
-                if conf is not None:
-                    conf_after = conf.ref_calls()
-                    mine["gvcf_calls"] += conf_after[0] - conf_before[0]
-                    mine["gvcf_overflows"] += conf_after[1] - conf_before[1]
-            for g, p in zip(group, prepared):
+            for (chr_name, _start, _end), p in zip(group, prepared):
                 if p is None and track is not None:
-                    empty_depth(*g)
+                    zeros, on_target = np.zeros(_end - _start + 1, np.int64), empty_on_target(chr_name, _start, _end)
+                    track.add(chr_name, (_start, _end), Coverage.runs_numpy(zeros, _start, track.bins, on_target),
+                              Coverage.totals_numpy(zeros, track.bins, on_target))
                 if p is None and gtrack is not None:
-                    empty_blocks(*g)
+                    gtrack.add_empty(chr_name, (_start, _end), empty_on_target(chr_name, _start, _end))
             return outs
 
         sink = getattr(options, "fused_sink", None)         # call_variant's fused form: predictions straight from the encoder's windows
@@ -400,14 +395,15 @@ class ImageGenerationUtils:
             # what the encoder counts while this worker runs goes into `mine`; candidates enumerated between the count kernels
             # and the window gather where PEPPER_AMD_DEVICE_CANDIDATES=1 (pa_encoder_set_device_candidates).  A worker that
             # raises leaves its handle out of the pool
-            with worker_counters(enc, mine, release_on_error=False, inflate_figures=True, candidates=True):
+            # The job's bins and reference-confidence table on the handle while this worker runs: it goes back to the pool without them
+            with worker_counters(enc, mine, release_on_error=False, inflate_figures=True, candidates=True), contextlib.ExitStack() as stack:
                 g0 = 0
                 if track is not None:
                     enc.set_depth_bins(track.bins)
-                    depth_before = enc.depth_calls()
+                    stack.enter_context(counting("coverage", enc.depth_calls, lambda: enc.set_depth_bins(None)))
                 if gtrack is not None:
                     enc.set_ref_confidence(gtrack.table, gtrack.bands)
-                    conf_before = enc.ref_calls()
+                    stack.enter_context(counting("gvcf", enc.ref_calls, lambda: enc.set_ref_confidence(None, None)))
                 while g0 < len(intervals):
                     group = intervals[g0:adjacent_run(intervals, g0, batch, 2 * safe)]
                     chr_name = group[0][0]
@@ -492,16 +488,6 @@ class ImageGenerationUtils:
                         at += k
                     lap("hdf5", t0)
                     g0 += n_done
-                if track is not None:                # (the handle goes back to the pool without this job's bins)
-                    depth_after = enc.depth_calls()
-                    mine["coverage_calls"] += depth_after[0] - depth_before[0]
-                    mine["coverage_overflows"] += depth_after[1] - depth_before[1]
-                    enc.set_depth_bins(None)
-                if gtrack is not None:               # (... nor this job's reference-confidence table)
-                    conf_after = enc.ref_calls()
-                    mine["gvcf_calls"] += conf_after[0] - conf_before[0]
-                    mine["gvcf_overflows"] += conf_after[1] - conf_before[1]
-                    enc.set_ref_confidence(None, None)
             t_close = time.perf_counter()
         lap("close", t_close)
         merge_stats(stats, mine)

@@ -125,9 +125,7 @@ def set_device_candidates(on, device=0):
 def candidate_calls(device=0):
     """-> (calls enumerated on the device, calls handed back to the host) of this thread's encoder on `device`."""
     lib, enc = _encoder(device)
-    dev, host = ctypes.c_int64(), ctypes.c_int64()
-    _lib.check(lib.pa_encoder_candidate_calls(enc, ctypes.byref(dev), ctypes.byref(host)))
-    return dev.value, host.value
+    return _calls_pair(lib.pa_encoder_candidate_calls, enc)
 
 
 def _send_targets(lib, enc, table):
@@ -160,61 +158,6 @@ def _send_depth_bins(lib, enc, bins):
     _lib.check(lib.pa_encoder_set_depth_bins(enc, len(lower), lower.ctypes.data))
 
 
-def _depth_runs(lib, enc):
-    """pa_encoder_depth_runs -> (region int32, start int64, end int64, bin int32) of the handle's last run: every region's runs
-    in region and position order, contig coordinates, ends half-open, bin -1 outside the targets."""
-    n = ctypes.c_int64()
-    _lib.check(lib.pa_encoder_depth_runs(enc, 0, None, None, None, None, ctypes.byref(n)))
-    k = max(1, n.value)
-    region, start, end, which = np.zeros(k, np.int32), np.zeros(k, np.int64), np.zeros(k, np.int64), np.zeros(k, np.int32)
-    _lib.check(lib.pa_encoder_depth_runs(enc, k, region.ctypes.data, start.ctypes.data, end.ctypes.data, which.ctypes.data,
-                                         ctypes.byref(n)))
-    return region[:n.value], start[:n.value], end[:n.value], which[:n.value]
-
-
-def _depth_totals(lib, enc, n_regions):
-    """pa_encoder_depth_totals -> (bases int64 [n_regions, 8], sum of depths int64 [n_regions]) of the handle's last run."""
-    bases, sums = np.zeros((max(1, n_regions), 8), np.int64), np.zeros(max(1, n_regions), np.int64)
-    _lib.check(lib.pa_encoder_depth_totals(enc, n_regions, bases.ctypes.data, sums.ctypes.data))
-    return bases[:n_regions], sums[:n_regions]
-
-
-def _depth_calls(lib, enc):
-    made, overflows = ctypes.c_int64(), ctypes.c_int64()
-    _lib.check(lib.pa_encoder_depth_calls(enc, ctypes.byref(made), ctypes.byref(overflows)))
-    return made.value, overflows.value
-
-
-class _ThreadDepth(object):
-    """What thread_depth_bins yields: the depth runs, totals and counters of this thread's encoder, under the names
-    PackedEncoder gives them."""
-
-    def __init__(self, lib, enc):
-        self.lib, self.enc = lib, enc
-
-    def depth_runs(self):
-        return _depth_runs(self.lib, self.enc)
-
-    def depth_totals(self, n_regions):
-        return _depth_totals(self.lib, self.enc, n_regions)
-
-    def depth_calls(self):
-        return _depth_calls(self.lib, self.enc)
-
-
-@contextlib.contextmanager
-def thread_depth_bins(bins, device=0):
-    """This thread's encoder on `device` -- what RegionalSummaryGenerator and generate_summary_arrays_batch run on -- with depth
-    bins set for the calls inside (pa_encoder_set_depth_bins) and without them again behind: the handle outlives the job.
-    Yields an object whose depth_runs() / depth_totals(n_regions) / depth_calls() speak of that handle's last run."""
-    lib, enc = _encoder(device)
-    _send_depth_bins(lib, enc, bins)
-    try:
-        yield _ThreadDepth(lib, enc)
-    finally:
-        _send_depth_bins(lib, enc, None)
-
-
 def _send_ref_confidence(lib, enc, table, bands):
     """pa_encoder_set_ref_confidence: the 101 x 101 uint8 table of pepper_amd/variant/RefConfidence.py build_table and ascending
     lower bounds of GQ starting at 0 (parse_bands); bands None: off."""
@@ -228,60 +171,87 @@ def _send_ref_confidence(lib, enc, table, bands):
     _lib.check(lib.pa_encoder_set_ref_confidence(enc, table.ctypes.data, table.shape[0], len(lower), lower.ctypes.data))
 
 
-def _ref_blocks(lib, enc):
-    """pa_encoder_ref_blocks -> (region int32, start int64, end int64, band int32, min_dp int32, min_gq int32) of the handle's
-    last run: every region's records in region and position order, contig coordinates, ends half-open, band -1 outside the
-    targets; a run that crosses a tile border comes as one record per tile (RefConfidence.merge_blocks joins them)."""
+def _fetch_records(fetch, enc, dtypes):
+    """The records of the handle's last run from pa_encoder_depth_runs / pa_encoder_ref_blocks: asked for their number, then
+    fetched into one array per column."""
     n = ctypes.c_int64()
-    _lib.check(lib.pa_encoder_ref_blocks(enc, 0, None, None, None, None, None, None, ctypes.byref(n)))
-    k = max(1, n.value)
-    region, start, end = np.zeros(k, np.int32), np.zeros(k, np.int64), np.zeros(k, np.int64)
-    band, min_dp, min_gq = np.zeros(k, np.int32), np.zeros(k, np.int32), np.zeros(k, np.int32)
-    _lib.check(lib.pa_encoder_ref_blocks(enc, k, region.ctypes.data, start.ctypes.data, end.ctypes.data, band.ctypes.data,
-                                         min_dp.ctypes.data, min_gq.ctypes.data, ctypes.byref(n)))
-    return tuple(v[:n.value] for v in (region, start, end, band, min_dp, min_gq))
+    _lib.check(fetch(enc, 0, *([None] * len(dtypes)), ctypes.byref(n)))
+    cols = [np.zeros(max(1, n.value), t) for t in dtypes]
+    _lib.check(fetch(enc, len(cols[0]), *(c.ctypes.data for c in cols), ctypes.byref(n)))
+    return tuple(c[:n.value] for c in cols)
 
 
-def _ref_calls(lib, enc):
-    made, overflows = ctypes.c_int64(), ctypes.c_int64()
-    _lib.check(lib.pa_encoder_ref_calls(enc, ctypes.byref(made), ctypes.byref(overflows)))
-    return made.value, overflows.value
+def _calls_pair(calls, enc):
+    """The two counters of pa_encoder_depth_calls, pa_encoder_ref_calls and their like."""
+    first, second = ctypes.c_int64(), ctypes.c_int64()
+    _lib.check(calls(enc, ctypes.byref(first), ctypes.byref(second)))
+    return first.value, second.value
 
 
-def _ref_blocks_ms(lib, enc):
-    ms = np.zeros(15, np.float64)
-    _lib.check(lib.pa_encoder_last_timing(enc, ms.ctypes.data, 15))
-    return float(ms[14])
+class _TrackReads(object):
+    """What a holder of an encoder handle (self.lib, self.enc) can ask about the per-position tracks of the handle's last run."""
+
+    def depth_runs(self):
+        """pa_encoder_depth_runs -> (region int32, start int64, end int64, bin int32): every region's runs in region and
+        position order, contig coordinates, ends half-open, bin -1 outside the targets."""
+        return _fetch_records(self.lib.pa_encoder_depth_runs, self.enc, (np.int32, np.int64, np.int64, np.int32))
+
+    def depth_totals(self, n_regions):
+        """pa_encoder_depth_totals -> (bases per bin int64 [n_regions, 8], sum of depths int64 [n_regions])."""
+        bases, sums = np.zeros((max(1, n_regions), 8), np.int64), np.zeros(max(1, n_regions), np.int64)
+        _lib.check(self.lib.pa_encoder_depth_totals(self.enc, n_regions, bases.ctypes.data, sums.ctypes.data))
+        return bases[:n_regions], sums[:n_regions]
+
+    def depth_calls(self):
+        """-> (runs made with depth bins set, runs among them whose records were emitted twice) since the handle was created."""
+        return _calls_pair(self.lib.pa_encoder_depth_calls, self.enc)
+
+    def ref_blocks(self):
+        """pa_encoder_ref_blocks -> (region int32, start int64, end int64, band int32, min_dp int32, min_gq int32): every
+        region's records in region and position order, contig coordinates, ends half-open, band -1 outside the targets; a run
+        that crosses a tile border comes as one record per tile (RefConfidence.merge_blocks joins them)."""
+        return _fetch_records(self.lib.pa_encoder_ref_blocks, self.enc, (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32))
+
+    def ref_calls(self):
+        """-> (runs made with a table set, runs among them whose records were emitted twice) since the handle was created."""
+        return _calls_pair(self.lib.pa_encoder_ref_calls, self.enc)
+
+    def ref_blocks_ms(self):
+        """Event time of the reference-block kernels of the last run (pa_encoder_last_timing [14]; 0 without a table)."""
+        ms = np.zeros(15, np.float64)
+        _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 15))
+        return float(ms[14])
 
 
-class _ThreadRefConfidence(object):
-    """What thread_ref_confidence yields: the reference blocks and counters of this thread's encoder, under the names
-    PackedEncoder gives them."""
+class _ThreadTracks(_TrackReads):
+    """What thread_depth_bins and thread_ref_confidence yield: this thread's encoder, under the names PackedEncoder gives."""
 
     def __init__(self, lib, enc):
         self.lib, self.enc = lib, enc
 
-    def ref_blocks(self):
-        return _ref_blocks(self.lib, self.enc)
-
-    def ref_calls(self):
-        return _ref_calls(self.lib, self.enc)
-
-    def ref_blocks_ms(self):
-        return _ref_blocks_ms(self.lib, self.enc)
-
 
 @contextlib.contextmanager
-def thread_ref_confidence(table, bands, device=0):
-    """This thread's encoder on `device` with a reference-confidence table set for the calls inside
-    (pa_encoder_set_ref_confidence) and without it again behind: the handle outlives the job.  Yields an object whose
-    ref_blocks() / ref_calls() / ref_blocks_ms() speak of that handle's last run."""
+def _thread_track(send, device, *setting):
+    """This thread's encoder on `device` -- what RegionalSummaryGenerator and generate_summary_arrays_batch run on -- with a
+    track's setting sent for the calls inside and taken back behind them: the handle outlives the job."""
     lib, enc = _encoder(device)
-    _send_ref_confidence(lib, enc, table, bands)
+    send(lib, enc, *setting)
     try:
-        yield _ThreadRefConfidence(lib, enc)
+        yield _ThreadTracks(lib, enc)
     finally:
-        _send_ref_confidence(lib, enc, None, None)
+        send(lib, enc, *([None] * len(setting)))
+
+
+def thread_depth_bins(bins, device=0):
+    """Depth bins (pa_encoder_set_depth_bins) on this thread's encoder for the calls inside.  Yields an object whose
+    depth_runs() / depth_totals(n_regions) / depth_calls() speak of that handle's last run."""
+    return _thread_track(_send_depth_bins, device, bins)
+
+
+def thread_ref_confidence(table, bands, device=0):
+    """A reference-confidence table (pa_encoder_set_ref_confidence) on this thread's encoder for the calls inside.  Yields an
+    object whose ref_blocks() / ref_calls() / ref_blocks_ms() speak of that handle's last run."""
+    return _thread_track(_send_ref_confidence, device, table, bands)
 
 
 def flatten_reads(reads):
@@ -357,7 +327,7 @@ def _pileup_struct(gen, flat, keep):
                    flat["cigar_offset"].ctypes.data, flat["cigar_op"].ctypes.data, flat["cigar_len"].ctypes.data)
 
 
-class StagedBatch(object):
+class StagedBatch(_TrackReads):
     """A batch of regions uploaded once (pa_encoder_stage_batch) and encoded any number of times
     (pa_encoder_run_staged): what bench.py times with the inputs resident in HBM."""
 
@@ -398,10 +368,6 @@ class StagedBatch(object):
         ms = np.zeros(14, np.float64)
         _lib.check(self.lib.pa_encoder_last_timing(self.enc, ms.ctypes.data, 14))
         return float(ms[13])
-
-    def ref_blocks_ms(self):
-        """Event time of the reference-block kernels of the last run (pa_encoder_last_timing [14]; 0 without a table)."""
-        return _ref_blocks_ms(self.lib, self.enc)
 
     def stats(self):
         v = np.zeros(6, np.int64)
@@ -462,7 +428,7 @@ def _lap(laps, key, t0):
     return now
 
 
-class PackedEncoder(object):
+class PackedEncoder(_TrackReads):
     """The packed form of a batch (pa_encoder_stage_packed): the reads of a run of regions as pa_bam_pack_regions leaves them
     in this object's page-locked arena -- CIGAR words, 4-bit bases, qualities, once per read -- clipped to each region and
     decoded by the device.  One object per worker thread: it owns its encoder handle (stream, workspace, arena)."""
@@ -575,46 +541,20 @@ class PackedEncoder(object):
         """Depth classes of this handle's next runs (pa_encoder_set_depth_bins): ascending lower bounds starting at 0, None: off."""
         _send_depth_bins(self.lib, self.enc, bins)
 
-    def depth_runs(self):
-        """-> (region, start, end, bin) of the last run's depth runs (pa_encoder_depth_runs)."""
-        return _depth_runs(self.lib, self.enc)
-
-    def depth_totals(self, n_regions):
-        """-> (bases per bin [n_regions, 8], sum of depths [n_regions]) of the last run (pa_encoder_depth_totals)."""
-        return _depth_totals(self.lib, self.enc, n_regions)
-
-    def depth_calls(self):
-        """-> (runs made with depth bins set, runs among them whose records were emitted twice) since this handle was created."""
-        return _depth_calls(self.lib, self.enc)
-
     def set_ref_confidence(self, table, bands):
         """Reference blocks of this handle's next runs (pa_encoder_set_ref_confidence): RefConfidence.build_table's table and
         ascending lower bounds of GQ starting at 0; bands None: off."""
         _send_ref_confidence(self.lib, self.enc, table, bands)
 
-    def ref_blocks(self):
-        """-> (region, start, end, band, min_dp, min_gq) of the last run's reference blocks (pa_encoder_ref_blocks)."""
-        return _ref_blocks(self.lib, self.enc)
-
-    def ref_calls(self):
-        """-> (runs made with a table set, runs among them whose records were emitted twice) since this handle was created."""
-        return _ref_calls(self.lib, self.enc)
-
-    def ref_blocks_ms(self):
-        """Event time of the reference-block kernels of the last run (pa_encoder_last_timing [14]; 0 without a table)."""
-        return _ref_blocks_ms(self.lib, self.enc)
+    # depth_runs / depth_totals / depth_calls / ref_blocks / ref_calls / ref_blocks_ms of the last run: _TrackReads
 
     def candidate_calls(self):
         """-> (runs enumerated on the device, runs handed back to the host) since this handle was created."""
-        dev, host = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self.lib.pa_encoder_candidate_calls(self.enc, ctypes.byref(dev), ctypes.byref(host)))
-        return dev.value, host.value
+        return _calls_pair(self.lib.pa_encoder_candidate_calls, self.enc)
 
     def pack_calls(self):
         """-> (calls packed on the device, calls the device handed back) since this handle was created (pa_encoder_pack_calls)."""
-        dev, back = ctypes.c_int64(), ctypes.c_int64()
-        _lib.check(self.lib.pa_encoder_pack_calls(self.enc, ctypes.byref(dev), ctypes.byref(back)))
-        return dev.value, back.value
+        return _calls_pair(self.lib.pa_encoder_pack_calls, self.enc)
 
     def packed_tables(self, n_reads, n_pairs):
         """-> (reads, pair_read, seq_off): the tables the last device pack built, copied out (pa_encoder_packed_tables)."""

@@ -25,12 +25,13 @@ haploid table.  Dropping the het hypothesis removes a term from the normaliser a
 only raise P(hom-ref): the diploid GQ is a lower bound of the haploid one.  Gvcf.py writes such a block with GT 0.
 """
 import math
-import threading
 
 import numpy as np
 
-MAX_BANDS = 8
-OFF_TARGET = -1                      # the band of a position outside every target (pa_encoder_set_targets): never written
+from pepper_amd.variant import RunTracks
+from pepper_amd.variant.RunTracks import OFF_TARGET        # the band of a position outside every target: never written
+
+MAX_BANDS = RunTracks.MAX_CLASSES
 TABLE_SIDE = 101                     # counts 0 .. 100 after the rescale
 RESCALE_TO = 100
 DEFAULT_ERROR_RATE = 0.001
@@ -76,27 +77,8 @@ def parse_bands(bands=None):
     not an integer or above 255."""
     if bands is None or (isinstance(bands, str) and bands.strip() == ""):
         return np.array(DEFAULT_BANDS, np.int32)
-    fields = [f.strip() for f in bands.split(",")] if isinstance(bands, str) else list(bands)
-    if len(fields) == 0:
-        raise ValueError("gvcf bands: no band")
-    if len(fields) > MAX_BANDS:
-        raise ValueError("gvcf bands: entry %d is one more than the %d bands a table may have" % (MAX_BANDS, MAX_BANDS))
-    bounds = []
-    for k, field in enumerate(fields):
-        try:
-            if isinstance(field, (float, np.floating)) and float(field) != int(field):
-                raise ValueError
-            value = int(field)
-        except (TypeError, ValueError):
-            raise ValueError("gvcf bands: entry %d (%r) is not an integer" % (k, field)) from None
-        if k == 0 and value != 0:
-            raise ValueError("gvcf bands: entry 0 must be 0, not %d" % value)
-        if k > 0 and value <= bounds[-1]:
-            raise ValueError("gvcf bands: entry %d (%d) is not above the one before it (%d)" % (k, value, bounds[-1]))
-        if value > 255:
-            raise ValueError("gvcf bands: entry %d (%d) is above 255, the largest GQ a table holds" % (k, value))
-        bounds.append(value)
-    return np.array(bounds, np.int32)
+    return RunTracks.parse_bounds(bands, "gvcf bands", "band",
+                                  lambda v: "is above 255, the largest GQ a table holds" if v > 255 else None)
 
 
 def band_labels(bands):
@@ -133,94 +115,33 @@ def blocks_numpy(cov, gq, first_position, bands, on_target=None):
     """The rule of ref_blocks_kernel without its tile borders: cov[i], gq[i] speak of position first_position + i ->
     (starts, ends, band, min_dp, min_gq) of the maximal runs of equal band, ends half-open, each with the smallest cov and the
     smallest gq of its positions.  on_target (bool per position; None: all): a position outside has the band OFF_TARGET."""
-    cov, gq = np.asarray(cov, np.int64), np.asarray(gq, np.int64)
-    which = (np.searchsorted(np.asarray(bands, np.int64), gq, side="right") - 1).astype(np.int32)
-    if on_target is not None:
-        which = np.where(np.asarray(on_target, bool), which, np.int32(OFF_TARGET)).astype(np.int32)
-    n = len(which)
-    if n == 0:
-        return (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros(0, np.int32), np.zeros(0, np.int32), np.zeros(0, np.int32))
-    heads = np.flatnonzero(np.concatenate([[True], which[1:] != which[:-1]]))
-    starts = heads.astype(np.int64) + int(first_position)
-    ends = np.concatenate([heads[1:], [n]]).astype(np.int64) + int(first_position)
-    return (starts, ends, which[heads], np.minimum.reduceat(cov, heads).astype(np.int32),
-            np.minimum.reduceat(gq, heads).astype(np.int32))
+    return RunTracks.class_runs(gq, first_position, bands, on_target, minimise=(cov, gq))
 
 
 def merge_blocks(region, starts, ends, band, min_dp, min_gq):
     """Touching records of one region and equal band joined, with the smaller of their minima: what the device reports one
     record per tile for.  Records in region and position order -> the same six arrays, shorter."""
-    out = []
-    for rec in zip(*(np.asarray(v).tolist() for v in (region, starts, ends, band, min_dp, min_gq))):
-        if out and out[-1][0] == rec[0] and out[-1][2] == rec[1] and out[-1][3] == rec[3]:
-            last = out[-1]
-            out[-1] = (last[0], last[1], rec[2], last[3], min(last[4], rec[4]), min(last[5], rec[5]))
-        else:
-            out.append(rec)
-    cols = list(zip(*out)) if out else [[]] * 6
-    return tuple(np.array(c, t) for c, t in zip(cols, (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32)))
+    types = (np.int32, np.int64, np.int64, np.int32, np.int32, np.int32)
+    cols = RunTracks.merge_touching(*(np.asarray(v, t) for v, t in zip((region, starts, ends, band, min_dp, min_gq), types)))
+    return tuple(np.asarray(c, t) for c, t in zip(cols, types))
 
 
-class BlockTrack(object):
-    """The blocks of a whole job, collected from its workers in any order (add) and finished once.
+class BlockTrack(RunTracks.RunTrack):
+    """The blocks of a whole job, collected from its workers in any order (add: blocks = (starts, ends, band, min_dp, min_gq))
+    and finished once (finish_arrays; finish -> [(contig, start, end, band, min_dp, min_gq)]).
 
     contigs: the FASTA's contig names in its order; bands: what parse_bands returned; table: what build_table returned."""
+    what, noun, columns = "block track", "blocks", (np.int32, np.int32, np.int32)
 
     def __init__(self, contigs, bands, table):
-        self.contigs = list(contigs)
-        self.order = {name: k for k, name in enumerate(self.contigs)}
+        super().__init__(contigs)
         self.bands = np.asarray(bands, np.int32)
         self.table = np.ascontiguousarray(table, np.uint8)
-        self._lock = threading.Lock()
-        self._pieces = []
-
-    def add(self, contig, interval, blocks):
-        """One interval of the planner: interval = (pos_start, pos_end), both inclusive; blocks = (starts, ends, band, min_dp,
-        min_gq) of its window in contig coordinates, ascending."""
-        if contig not in self.order:
-            raise ValueError("block track: contig %r is not in the FASTA" % (contig,))
-        cols = [np.array(v, t) for v, t in zip(blocks, (np.int64, np.int64, np.int32, np.int32, np.int32))]
-        if len(set(len(c) for c in cols)) != 1:
-            raise ValueError("block track: blocks of unequal lengths")
-        with self._lock:
-            self._pieces.append((self.order[contig], int(interval[0]), int(interval[1]), contig) + tuple(cols))
 
     def add_empty(self, contig, interval, on_target=None):
         """An interval no encoder call covered because no read lies in it: depth 0 and GQ 0 at every position."""
         zeros = np.zeros(int(interval[1]) - int(interval[0]) + 1, np.int64)
         self.add(contig, interval, blocks_numpy(zeros, zeros, int(interval[0]), self.bands, on_target))
-
-    def finish_arrays(self):
-        """-> (contig index int64, start, end, band, min_dp, min_gq) of the finished blocks, in FASTA order, ends half-open: the
-        pieces ordered by contig and start; the position two consecutive intervals share belongs to the one that starts there
-        -- the earlier interval's blocks are cut at the next interval's start (a cut block keeps its minima: they are then
-        lower bounds) and dropped when nothing is left; off-target blocks dropped; touching blocks of equal band merged with
-        their minima.  Whole-array work: a job has a block every few positions where the reads are noisy."""
-        with self._lock:
-            pieces = sorted(self._pieces, key=lambda p: p[:3])
-        cols = [[], [], [], [], [], []]
-        for k, (rank, _s, _e, _contig, starts, ends, band, min_dp, min_gq) in enumerate(pieces):
-            if k + 1 < len(pieces) and pieces[k + 1][0] == pieces[k][0]:
-                ends = np.minimum(ends, pieces[k + 1][1])          # the next interval of the contig owns everything from its start
-            for col, v in zip(cols, (np.full(len(starts), rank, np.int64), starts, ends, band, min_dp, min_gq)):
-                col.append(v)
-        if not cols[0]:
-            return tuple(np.zeros(0, t) for t in (np.int64, np.int64, np.int64, np.int32, np.int32, np.int32))
-        rank, starts, ends, band, min_dp, min_gq = (np.concatenate(c) for c in cols)
-        keep = (starts < ends) & (band != OFF_TARGET)
-        rank, starts, ends, band, min_dp, min_gq = (v[keep] for v in (rank, starts, ends, band, min_dp, min_gq))
-        if len(rank) == 0:
-            return rank, starts, ends, band, min_dp, min_gq
-        joins = (rank[1:] == rank[:-1]) & (starts[1:] == ends[:-1]) & (band[1:] == band[:-1])
-        heads = np.flatnonzero(np.concatenate([[True], ~joins]))
-        last = np.concatenate([heads[1:], [len(rank)]]) - 1
-        return (rank[heads], starts[heads], ends[last], band[heads], np.minimum.reduceat(min_dp, heads), np.minimum.reduceat(min_gq, heads))
-
-    def finish(self):
-        """finish_arrays as [(contig, start, end, band, min_dp, min_gq)]."""
-        rank, starts, ends, band, min_dp, min_gq = self.finish_arrays()
-        names = [self.contigs[k] for k in rank.tolist()]
-        return list(zip(names, starts.tolist(), ends.tolist(), band.tolist(), min_dp.tolist(), min_gq.tolist()))
 
     def log_line(self, arrays=None):
         _rank, starts, ends, band, _dp, _gq = self.finish_arrays() if arrays is None else arrays

@@ -347,6 +347,40 @@ def test_a_run_that_overflows_its_buffer_is_exact_and_counted(job, plain, monkey
         form.close()
 
 
+def test_a_class_that_holds_across_a_tile_border_with_both_tracks_on(tmp_path):
+    """One region of 520 rows, three reads over rows 500 - 519, depth bins and a table set for one run: depth 3 (bin 2) and
+    GQ 9 (band 1) on both sides of row 512.  Here the two tracks' head rules differ: the depth track looks back across the
+    border -- exactly one run over it --, the block track starts a record with every tile -- exactly two, touching on row
+    512, of equal band, each with the numpy rule's minima over its own rows."""
+    from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
+    from pepper_amd.variant.bam import BAM_handler
+    a, b = OFF + 1000, OFF + 1519
+    ref = pu.random_reference(np.random.default_rng(9108), cov.SPAN)
+    reads = [cov._read(ref, 1500, [(pu.OP_M, 20)], "r%d" % j, reverse=j % 2 == 1) for j in range(3)]
+    bam = str(tmp_path / "border.bam")
+    bu.write_bam(bam, [("ctg", cov.CONTIG_LEN)], {0: reads}, flush_every=7)
+    ev = evidence_numpy(reads, ref[1000:1520], a, b, cov.MIN_SNP_Q, cov.MIN_INDEL_Q, 1)
+    gq = RefConfidence.gq_numpy(*ev, TABLE)
+    want_runs = [(0,) + rec for rec in zip(*(c.tolist() for c in Coverage.runs_numpy(ev[0], a, cov.BINS)))]
+    want_blocks = [(0,) + rec for lo, hi in ((0, 512), (512, 520))
+                   for rec in zip(*(c.tolist() for c in RefConfidence.blocks_numpy(ev[0][lo:hi], gq[lo:hi], a + lo, BANDS)))]
+    assert want_runs == [(0, a, a + 500, 0), (0, a + 500, a + 520, 2)]
+    assert want_blocks == [(0, a, a + 500, 0, 0, 0), (0, a + 500, a + 512, 1, 3, 9), (0, a + 512, a + 520, 1, 3, 9)]
+    enc = PackedEncoder(0, arena_bytes=16 << 20)
+    try:
+        n_done, region_pairs, counts = enc.pack(BAM_handler(bam), "ctg", [a], [b], False, 1)
+        assert n_done == 1
+        enc.set_depth_bins(cov.BINS)
+        enc.set_ref_confidence(TABLE, BANDS)
+        enc.encode([(a, b)], [ref[1000:1520]], region_pairs, counts, cov.PARAMS, [(a, b)])
+        runs = list(zip(*(c.tolist() for c in enc.depth_runs())))
+        blocks = list(zip(*(c.tolist() for c in enc.ref_blocks())))
+    finally:
+        enc.close()
+    assert runs == want_runs
+    assert blocks == want_blocks
+
+
 def test_a_pooled_handle_does_not_carry_the_table_over(job):
     from pepper_amd import _lib
     from pepper_amd.variant.PEPPER_VARIANT import PackedEncoder
