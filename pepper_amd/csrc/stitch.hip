@@ -373,19 +373,93 @@ template <bool RUNS> PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t
     return e;
 }
 
-PA_DEV SlotEdit classify_slot(const EditTables& t, uint64_t s) { return classify_slot<true>(t, s, t.letters[s]); }
+PA_DEV pa_stitch_edit make_edit(uint32_t position, uint32_t offset, uint32_t index, uint32_t piece, uint32_t kind, uint8_t draft,
+                                uint8_t letter, uint8_t phred) {
+    pa_stitch_edit r;
+    r.position = position;
+    r.offset = offset;
+    r.index = (uint16_t)index;
+    r.piece = (uint16_t)piece;
+    r.kind = (uint8_t)kind;
+    r.draft = draft;
+    r.letter = letter;
+    r.phred = phred;
+    return r;
+}
 
-// sums[b] = records of slots [b * B, (b + 1) * B) (a workgroup past the end writes 0); kinds[k] += records of kind k
-__global__ __launch_bounds__(ST_THREADS) void k_edit_count(EditTables t, uint64_t* __restrict__ sums,
-                                                           unsigned long long* __restrict__ kinds) {
+PA_DEV uint8_t word_letter(unsigned long long word) {
+    const uint32_t label = (uint32_t)word & 0xFFu;
+    return label >= 1 && label <= 4 ? (uint8_t)((0x54474341u >> (8 * (label - 1))) & 0xFFu) : (uint8_t)0;
+}
+PA_DEV uint32_t base_code(uint8_t d) { return d == 'A' ? 1u : d == 'C' ? 2u : d == 'G' ? 3u : d == 'T' ? 4u : 0u; }
+
+// ---------------------------------------------------------------- the record passes: a rule, a count pass, a write pass ----
+// A rule says what one slot yields -- slot(): a SlotEdit whose kind is 0 where the slot has no record of its own -- how many
+// records that is, and what the slot's lane does beside the counting (counted) and beside the writing (written: only for a slot
+// with a record of its own).  The two passes below do everything else, once.
+
+// the edits of the consensus against the draft: 0 or 1 record per slot, and in front of it the GAP pair of the run it closes
+struct EditRule {
+    PA_DEV SlotEdit slot(const EditTables& t, uint64_t s) const { return classify_slot<true>(t, s, t.letters[s]); }
+    PA_DEV static uint32_t records(const SlotEdit& e) { return (e.kind != 0) + (e.gap ? 2u : 0u); }
+    PA_DEV void counted(uint64_t, const SlotEdit&) const {}
+    // the run's two records go to out[run], out[run + 1]; letters_before: of the closing slot
+    PA_DEV uint32_t write_run(const EditTables& t, const SlotEdit& e, uint32_t letters_before, uint32_t piece, uint64_t run,
+                              uint64_t n_records, pa_stitch_edit* __restrict__ out) const {
+        if (!e.gap) return 0;
+        const uint32_t close_at = e.position - 1;
+        const uint32_t lo = e.open_at - t.draft_lo, hi = close_at - t.draft_lo;
+        uint8_t d_open = lo < t.draft_span ? t.draft[lo] : (uint8_t)0, d_close = hi < t.draft_span ? t.draft[hi] : (uint8_t)0;
+        if (d_open >= 'a' && d_open <= 'z') d_open = (uint8_t)(d_open - 32);
+        if (d_close >= 'a' && d_close <= 'z') d_close = (uint8_t)(d_close - 32);
+        // after a fill the run's own letters are in the consensus, behind the pair's offset
+        const uint32_t run_at = t.holes ? letters_before - (close_at - e.open_at + 1) : letters_before;
+        if (run < n_records) out[run] = make_edit(e.open_at, run_at, 0, piece, PA_EDIT_GAP_OPEN, d_open, 0, 0);
+        if (run + 1 < n_records) out[run + 1] = make_edit(close_at, run_at, 0, piece, PA_EDIT_GAP_CLOSE, d_close, 0, 0);
+        return 2;
+    }
+    PA_DEV void written(uint64_t, const SlotEdit&) const {}
+};
+
+// the gate: the edit the winner makes against the draft where it is WITHHELD -- its phred is below min_phred; a SUB or DEL only
+// where the draft letter is a base (the gate has no letter to keep elsewhere, and the model's decision stands).  Read off the
+// winner word the finish left (the model's label and raw phred), not letters[]: the count pass rewrites letters[] while the write
+// pass still has to find the model's letter.  A lane touches only its own slot.
+struct GateRule {
+    uint32_t min_phred;
+    uint8_t* letters;                                   // count pass: a withheld slot's letter becomes what it emits now
+    unsigned long long* slots;                          // write pass: its winner word loses its phred and takes that letter's label,
+                                                        // so that emit, fill and edits read tables that agree with letters[]
+    PA_DEV SlotEdit slot(const EditTables& t, uint64_t s) const {
+        const unsigned long long word = t.slots[s];
+        SlotEdit e = classify_slot<false>(t, s, word_letter(word));
+        const uint32_t phred = (uint32_t)(word >> 8) & 0xFFu;      // (0: no writer)
+        if (!(phred < min_phred && (e.kind == PA_EDIT_INS || base_code(e.draft) != 0))) e.kind = 0;
+        return e;
+    }
+    PA_DEV static uint32_t records(const SlotEdit& e) { return e.kind != 0; }
+    // what a withheld slot emits: the draft letter, nothing (0) for an INS
+    PA_DEV static uint8_t emits(const SlotEdit& e) { return e.kind == PA_EDIT_INS ? (uint8_t)0 : e.draft; }
+    PA_DEV void counted(uint64_t s, const SlotEdit& e) const {
+        if (e.kind) letters[s] = emits(e);
+    }
+    PA_DEV uint32_t write_run(const EditTables&, const SlotEdit&, uint32_t, uint32_t, uint64_t, uint64_t, pa_stitch_edit*) const { return 0; }
+    PA_DEV void written(uint64_t s, const SlotEdit& e) const { slots[s] = (slots[s] & ~0xFFFFull) | base_code(emits(e)); }
+};
+
+// count pass: sums[b] = records of slots [b * B, (b + 1) * B) (a workgroup past the end writes 0); kinds[k] += records of kind k
+template <class Rule>
+__global__ __launch_bounds__(ST_THREADS) void k_record_count(EditTables t, Rule rule, uint64_t* __restrict__ sums,
+                                                             unsigned long long* __restrict__ kinds) {
     __shared__ uint64_t s_wave[ST_THREADS / 64];
     __shared__ uint64_t s_kind[ST_THREADS / 64];
     const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
     uint64_t v = 0, packed = 0;                         // packed: SUB | DEL << 16 | INS << 32 | gaps << 48 (a workgroup has <= 1024 each)
     for (int k = 0; k < ST_ITEMS; ++k) {
         if (i0 + k >= t.n_slots) break;
-        const SlotEdit e = classify_slot(t, i0 + k);
-        v += (e.kind != 0) + (e.gap ? 2 : 0);
+        const SlotEdit e = rule.slot(t, i0 + k);
+        rule.counted(i0 + k, e);
+        v += Rule::records(e);
         if (e.kind) packed += 1ull << (16 * (e.kind - 1));
         if (e.gap) packed += 1ull << 48;
     }
@@ -409,24 +483,13 @@ __global__ __launch_bounds__(ST_THREADS) void k_edit_count(EditTables t, uint64_
     }
 }
 
-PA_DEV pa_stitch_edit make_edit(uint32_t position, uint32_t offset, uint32_t index, uint32_t piece, uint32_t kind, uint8_t draft,
-                                uint8_t letter, uint8_t phred) {
-    pa_stitch_edit r;
-    r.position = position;
-    r.offset = offset;
-    r.index = (uint16_t)index;
-    r.piece = (uint16_t)piece;
-    r.kind = (uint8_t)kind;
-    r.draft = draft;
-    r.letter = letter;
-    r.phred = phred;
-    return r;
-}
-
-// the records of slot i go to out[offset[b] + records of the block's slots in front of i ..): k_scan_down's walk with the
-// classification in place of a load.  piece_start[p] = where the records of piece p begin.
-__global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const uint64_t* __restrict__ offset, uint64_t n_edits,
-                                                           pa_stitch_edit* __restrict__ out, uint64_t* __restrict__ piece_start) {
+// write pass (the gate's: after the letters were scanned again, t.place is the gated place): the records of slot i go to
+// out[offset[b] + records of the block's slots in front of i ..): k_scan_down's walk with the rule in place of a load.
+// piece_start[p] = where the records of piece p begin.
+template <class Rule>
+__global__ __launch_bounds__(ST_THREADS) void k_record_write(EditTables t, Rule rule, const uint64_t* __restrict__ offset,
+                                                             uint64_t n_records, pa_stitch_edit* __restrict__ out,
+                                                             uint64_t* __restrict__ piece_start) {
     __shared__ uint64_t s_wave[ST_THREADS / 64];
     const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
     SlotEdit item[ST_ITEMS];
@@ -434,131 +497,32 @@ __global__ __launch_bounds__(ST_THREADS) void k_edit_write(EditTables t, const u
     for (int k = 0; k < ST_ITEMS; ++k) {
         item[k].kind = 0;
         item[k].gap = false;
-        if (i0 + k < t.n_slots) item[k] = classify_slot(t, i0 + k);
-        v += (item[k].kind != 0) + (item[k].gap ? 2 : 0);
+        if (i0 + k < t.n_slots) item[k] = rule.slot(t, i0 + k);
+        v += Rule::records(item[k]);
     }
     uint64_t total;
     uint64_t run = block_scan(v, s_wave, &total) - v + offset[blockIdx.x];
     for (int k = 0; k < ST_ITEMS; ++k) {
         if (i0 + k >= t.n_slots) break;
         const SlotEdit& e = item[k];
+        if (e.index == 0 && e.position == t.pmin[e.piece]) piece_start[e.piece] = run;
+        if (Rule::records(e) == 0) continue;
         const uint32_t piece = t.take_index[e.piece];
         uint32_t letters_before = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[e.piece]);
         if (t.holes) letters_before += t.lead + t.holes[t.pbase[e.piece] + (e.position - t.pmin[e.piece])];      // (uniform)
-        if (e.index == 0 && (uint64_t)(e.position - t.pmin[e.piece]) == 0) piece_start[e.piece] = run;
-        if (e.gap) {
-            const uint32_t close_at = e.position - 1;
-            const uint32_t lo = e.open_at - t.draft_lo, hi = close_at - t.draft_lo;
-            uint8_t d_open = lo < t.draft_span ? t.draft[lo] : (uint8_t)0, d_close = hi < t.draft_span ? t.draft[hi] : (uint8_t)0;
-            if (d_open >= 'a' && d_open <= 'z') d_open = (uint8_t)(d_open - 32);
-            if (d_close >= 'a' && d_close <= 'z') d_close = (uint8_t)(d_close - 32);
-            // after a fill the run's own letters are in the consensus, behind the pair's offset
-            const uint32_t run_at = t.holes ? letters_before - (close_at - e.open_at + 1) : letters_before;
-            if (run < n_edits) out[run] = make_edit(e.open_at, run_at, 0, piece, PA_EDIT_GAP_OPEN, d_open, 0, 0);
-            if (run + 1 < n_edits) out[run + 1] = make_edit(close_at, run_at, 0, piece, PA_EDIT_GAP_CLOSE, d_close, 0, 0);
-            run += 2;
-        }
+        run += rule.write_run(t, e, letters_before, piece, run, n_records, out);
         if (e.kind) {
-            const uint8_t phred = t.qualities ? (uint8_t)(((uint32_t)t.slots[i0 + k] >> 8) & 0xFFu) : (uint8_t)0;
-            if (run < n_edits)
+            const uint8_t phred = t.qualities ? (uint8_t)(((uint32_t)t.slots[i0 + k] >> 8) & 0xFFu) : (uint8_t)0;      // (the raw one)
+            if (run < n_records)
                 out[run] = make_edit(e.position, letters_before, e.index, piece, e.kind, e.draft, e.kind == PA_EDIT_DEL ? (uint8_t)0 : e.letter,
                                      phred);
+            rule.written(i0 + k, e);
             run += 1;
         }
     }
 }
 
-// ---------------------------------------------------------------- gate: withhold the edits below a phred ----
-// What one slot decides, read off the winner word the finish left (the model's label and raw phred) and the draft.  The word is
-// read, not letters[]: the first pass rewrites letters[] while the second still has to find the model's letter.
-struct SlotGate {
-    SlotEdit e;                                         // the edit the winner makes against the draft (kind 0: none)
-    bool withheld;
-    uint8_t phred;                                      // the winner's raw phred (0: no writer)
-    uint8_t emits;                                      // what a withheld slot emits: the draft letter, nothing (0) for an INS
-};
-
-PA_DEV uint8_t word_letter(unsigned long long word) {
-    const uint32_t label = (uint32_t)word & 0xFFu;
-    return label >= 1 && label <= 4 ? (uint8_t)((0x54474341u >> (8 * (label - 1))) & 0xFFu) : (uint8_t)0;
-}
-PA_DEV uint32_t base_code(uint8_t d) { return d == 'A' ? 1u : d == 'C' ? 2u : d == 'G' ? 3u : d == 'T' ? 4u : 0u; }
-
-// withheld: an edit whose phred is below min_phred; a SUB or DEL only where the draft letter is a base (the gate has no letter to
-// keep elsewhere, and the model's decision stands)
-PA_DEV SlotGate gate_slot(const EditTables& t, uint64_t s, uint32_t min_phred) {
-    SlotGate g;
-    const unsigned long long word = t.slots[s];
-    g.e = classify_slot<false>(t, s, word_letter(word));
-    g.phred = (uint8_t)((word >> 8) & 0xFFu);
-    g.withheld = g.e.kind != 0 && g.phred < min_phred && (g.e.kind == PA_EDIT_INS || base_code(g.e.draft) != 0);
-    g.emits = g.e.kind == PA_EDIT_INS ? (uint8_t)0 : g.e.draft;
-    return g;
-}
-
-// first pass: letters[i] of every withheld slot becomes what it emits now; sums[b] = withheld slots of [b * B, (b + 1) * B) (a
-// workgroup past the end writes 0); kinds[k] += withheld edits of kind k.  A lane writes the letter of its own slots only.
-__global__ __launch_bounds__(ST_THREADS) void k_gate_mark(EditTables t, uint32_t min_phred, uint8_t* letters,
-                                                          uint64_t* __restrict__ sums, unsigned long long* __restrict__ kinds) {
-    __shared__ uint64_t s_wave[ST_THREADS / 64];
-    __shared__ uint64_t s_kind[ST_THREADS / 64];
-    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
-    uint64_t v = 0, packed = 0;                         // packed: SUB | DEL << 16 | INS << 32 (a workgroup has <= 1024 each)
-    for (int k = 0; k < ST_ITEMS; ++k) {
-        if (i0 + k >= t.n_slots) break;
-        const SlotGate g = gate_slot(t, i0 + k, min_phred);
-        if (!g.withheld) continue;
-        letters[i0 + k] = g.emits;
-        v += 1;
-        packed += 1ull << (16 * (g.e.kind - 1));
-    }
-    for (int d = 32; d; d >>= 1)
-        packed += ((uint64_t)(uint32_t)__shfl_xor((int)(uint32_t)(packed >> 32), d) << 32) | (uint32_t)__shfl_xor((int)(uint32_t)packed, d);
-    if ((threadIdx.x & 63) == 0) s_kind[threadIdx.x >> 6] = packed;
-    uint64_t total;
-    (void)block_scan(v, s_wave, &total);               // (its barrier also publishes s_kind)
-    if (threadIdx.x == 0) {
-        sums[blockIdx.x] = total;
-        uint64_t all = 0;
-        for (int w = 0; w < ST_THREADS / 64; ++w) all += s_kind[w];
-        const unsigned long long sub = all & 0xFFFFu, del = (all >> 16) & 0xFFFFu, ins = (all >> 32) & 0xFFFFu;
-        if (sub) atomicAdd(&kinds[PA_EDIT_SUB], sub);     // one atomic per workgroup and kind; integer sums do not depend on the order
-        if (del) atomicAdd(&kinds[PA_EDIT_DEL], del);
-        if (ins) atomicAdd(&kinds[PA_EDIT_INS], ins);
-    }
-}
-
-// second pass, after the letters were scanned again (t.place is the gated place): the record of a withheld slot goes to
-// out[offset[b] + withheld slots of the block in front of it], and its winner word loses its phred and takes the label of what it
-// emits, so that emit, fill and edits read tables that agree with letters[].  piece_start[p] = where the records of piece p begin.
-__global__ __launch_bounds__(ST_THREADS) void k_gate_write(EditTables t, uint32_t min_phred, const uint64_t* __restrict__ offset,
-                                                           uint64_t n_records, pa_stitch_edit* __restrict__ out,
-                                                           uint64_t* __restrict__ piece_start, unsigned long long* slots) {
-    __shared__ uint64_t s_wave[ST_THREADS / 64];
-    const uint64_t i0 = (uint64_t)blockIdx.x * ST_B + (uint64_t)threadIdx.x * ST_ITEMS;
-    SlotGate item[ST_ITEMS];
-    uint64_t v = 0;
-    for (int k = 0; k < ST_ITEMS; ++k) {
-        item[k].withheld = false;
-        if (i0 + k < t.n_slots) item[k] = gate_slot(t, i0 + k, min_phred);
-        v += item[k].withheld;
-    }
-    uint64_t total;
-    uint64_t run = block_scan(v, s_wave, &total) - v + offset[blockIdx.x];
-    for (int k = 0; k < ST_ITEMS; ++k) {
-        if (i0 + k >= t.n_slots) break;
-        const SlotGate& g = item[k];
-        if (g.e.index == 0 && g.e.position == t.pmin[g.e.piece]) piece_start[g.e.piece] = run;
-        if (!g.withheld) continue;
-        const uint32_t at = (uint32_t)((int64_t)t.place[i0 + k] + t.letter_shift[g.e.piece]);
-        if (run < n_records)
-            out[run] = make_edit(g.e.position, at, g.e.index, t.take_index[g.e.piece], g.e.kind, g.e.draft,
-                                 g.e.kind == PA_EDIT_DEL ? (uint8_t)0 : g.e.letter, g.phred);
-        slots[i0 + k] = (slots[i0 + k] & ~0xFFFFull) | base_code(g.emits);
-        run += 1;
-    }
-}
-
+// ---------------------------------------------------------------- gate: what it runs beside the record passes ----
 // the withheld records of a gated finish that was filled afterwards: their offsets count the filled consensus, as the edit
 // records' do (one piece: the row of a position is position - first)
 __global__ void k_gate_filled_offsets(pa_stitch_edit* __restrict__ records, uint64_t n, const uint32_t* __restrict__ holes,
@@ -783,12 +747,43 @@ struct Buffer {
         cap = want;
         return true;
     }
-    void release() {
+    Buffer() = default;
+    Buffer(const Buffer&) = delete;
+    Buffer& operator=(const Buffer&) = delete;
+    ~Buffer() {                                         // (with the handle: pa_stitcher_destroy has set the device and waited)
         if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
     }
     template <class T> T* as() const { return (T*)p; }
+};
+
+// The finish's piece words (f_piece): [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces, then fault, bad label
+struct PieceWords {
+    uint8_t* base;
+    size_t np;
+    static size_t at_pbase(size_t np) { return (np * 8 + 7) / 8 * 8; }
+    static size_t bytes(size_t np) { return at_pbase(np) + np * 16 + 16; }
+    uint32_t* pmin() const { return (uint32_t*)base; }
+    uint32_t* pmax() const { return (uint32_t*)(base + np * 4); }
+    uint64_t* pbase() const { return (uint64_t*)(base + at_pbase(np)); }
+    uint64_t* letter_start() const { return pbase() + np; }
+    uint32_t* flags() const { return (uint32_t*)(letter_start() + np); }      // [2]: a row outside its tables, the largest bad label
+};
+
+// The record passes' per-piece block (e_piece, g_piece): what the host says per piece (table order) -- what turns a table letter
+// offset into a take() offset, its place in take() order -- and the device's answers: where a piece's records begin, the records
+// per kind.  [letter_shift i64 | start u64] x n_pieces, kinds u64 x 6, [take_index u16 | order u16] x n_pieces
+struct RecordWords {
+    uint8_t* base;
+    size_t np;
+    static size_t bytes(size_t np) { return np * 20 + 6 * 8; }
+    int64_t* letter_shift() const { return (int64_t*)base; }
+    uint64_t* start() const { return (uint64_t*)base + np; }
+    unsigned long long* kinds() const { return (unsigned long long*)(start() + np); }
+    uint16_t* take_index() const { return (uint16_t*)(kinds() + 6); }
+    uint16_t* order() const { return take_index() + np; }      // the gate's: the pieces with rows as take() goes
+    // what a caller zeroes in one piece: start and kinds; with letter_shift in front of them where the device writes that too
+    size_t answer_bytes() const { return np * 8 + 6 * 8; }
+    size_t device_bytes() const { return np * 8 + answer_bytes(); }
 };
 
 struct ChunkRec {
@@ -803,6 +798,25 @@ struct ChunkRec {
 struct PieceOut {
     int64_t first, last, offset, length;
     int piece;
+};
+
+// What the calls behind a finish make of its tables.  A product is live from the call that made it until a call that drops it.
+enum Product { EDITS, FILL, WITHHELD, VARIANTS, N_PRODUCTS };
+struct ProductState {
+    bool live = false;
+    int64_t count = 0;                                  // its records (FILL: its letters)
+    int64_t bytes = 0;                                  // its share of the table bytes pa_stitcher_stats reports
+};
+// The one invalidation rule: what a call drops when it starts its work (its own product, to be made anew, among them).  A gate
+// changes the consensus the edits describe; a fill changes it again, and the variants are the filled consensus' own; the withheld
+// records outlive a fill (their offsets are moved once: withheld_filled).
+enum Call { CALL_FINISH, CALL_GATE, CALL_FILL, CALL_EDITS, CALL_VARIANTS };
+constexpr unsigned DROPS[] = {
+    /* finish   */ 1u << EDITS | 1u << FILL | 1u << WITHHELD | 1u << VARIANTS,
+    /* gate     */ 1u << EDITS,
+    /* fill     */ 1u << EDITS | 1u << FILL | 1u << VARIANTS,
+    /* edits    */ 1u << EDITS,
+    /* variants */ 1u << VARIANTS,
 };
 
 }  // namespace
@@ -826,29 +840,47 @@ struct pa_stitcher {
     Buffer e_draft, e_piece, e_records;
     // fill's tables: the positions without a slot in front of every position, the filled sequence, the filled qualities
     Buffer f_holes, f_fill, f_fillq;
-    bool filled = false;                                // pa_stitcher_fill ran on the last finish: take, take_qualities, edits speak of it
-    int64_t filled_length = 0, fill_lead = 0, fill_bytes = 0;      // fill_bytes: its share of last_scratch_bytes
-    int64_t draft_held = -1;                            // e_draft holds draft[0 .. draft_held) of that fill or gate (-1: it does not)
     // gate's staging (per piece: letter shift, where its records begin, its take() place; the counts) and the withheld records
     Buffer g_piece, g_records;
-    bool gated = false;                                 // pa_stitcher_gate ran on the last finish: every later call speaks of the gated tables
-    bool withheld_filled = false;                       // ... and the records' offsets already count the fill that followed
-    int64_t n_withheld = 0;
     // variants' tables: hunk heads in front of every edit record, the hunks, their records before and after the compaction, the
     // flags and places of the compaction, scan scratch, the counts
     Buffer v_before, v_hunks, v_tmp, v_emit, v_place, v_out, v_scan, v_words;
-    bool have_variants = false;                         // pa_stitcher_variants ran on the last fill
-    int64_t n_variants = 0, variant_bytes = 0;          // variant_bytes: its share of last_scratch_bytes
-    int64_t fill_draft_length = -1;                     // the draft_length of the last fill
+    // what is live since the last finish.  EDITS: pa_stitcher_edits ran on the tables as they are.  FILL: pa_stitcher_fill ran --
+    // take, take_qualities, edits speak of the filled consensus.  WITHHELD: pa_stitcher_gate ran -- every later call speaks of the
+    // gated tables.  VARIANTS: pa_stitcher_variants ran on that fill.
+    ProductState product[N_PRODUCTS];
+    int64_t fill_lead = 0;                              // of the live fill: letters in front of the piece
+    int64_t fill_draft_length = -1;                     // ... and the draft_length it was given
+    bool withheld_filled = false;                       // the withheld records' offsets already count the fill that followed
+    int64_t draft_held = -1;                            // e_draft holds draft[0 .. draft_held) of a fill, gate or variants (-1: it does not)
     std::vector<PieceOut> pieces;                      // of the last finish, in output order
     int64_t sequence_length = 0;
     bool finished = false;                              // a finish has run: the three below speak of it
     bool contig_qualities = false;                      // every chunk of its contig came with qualities
     bool have_qualities = false;                        // ... and it got as far as the emit: f_qual holds them
-    int64_t last_slots = 0, last_pieces = 0, last_positions = 0, last_scratch_bytes = 0;
+    int64_t last_slots = 0, last_pieces = 0, last_positions = 0;
+    int64_t base_bytes = 0;                             // the finish's own table bytes (a gate moves them by the letters it moves)
     bool have_sequence = false;                         // the last finish ran to its end: its tables are whole
-    bool have_edits = false;                            // pa_stitcher_edits ran on them
-    int64_t n_edits = 0;
+
+    bool live(Product p) const { return product[p].live; }
+    void make(Product p, int64_t count, int64_t bytes) { product[p] = ProductState{true, count, bytes}; }
+    void drop(Product p) {
+        product[p] = ProductState();
+        if (p == FILL) {
+            fill_lead = 0;
+            fill_draft_length = -1;
+        }
+        if (p == WITHHELD) withheld_filled = false;
+    }
+    void begin(Call call) {
+        for (int p = 0; p < N_PRODUCTS; ++p)
+            if (DROPS[call] >> p & 1u) drop((Product)p);
+    }
+    int64_t table_bytes() const {
+        int64_t bytes = base_bytes;
+        for (const ProductState& p : product) bytes += p.bytes;      // (a dropped product has none)
+        return bytes;
+    }
 };
 
 namespace {
@@ -864,11 +896,81 @@ int no_memory(const char* what, uint64_t bytes) {
     return pa::set_error(PA_ERR_HIP, std::string("stitcher: no device memory for ") + what + " (" + std::to_string(bytes) + " bytes)");
 }
 
-std::vector<Buffer*> buffers_of(pa_stitcher* s) {
-    return {&s->a_pos, &s->a_idx, &s->a_lab, &s->a_phr, &s->a_drop, &s->a_kept, &s->a_refused, &s->a_dst, &s->f_desc, &s->f_piece,
-            &s->f_width, &s->f_base, &s->f_slots, &s->f_letters, &s->f_place, &s->f_out, &s->f_qual, &s->f_scan, &s->f_words,
-            &s->e_draft, &s->e_piece, &s->e_records, &s->f_holes, &s->f_fill, &s->f_fillq, &s->g_piece, &s->g_records,
-            &s->v_before, &s->v_hunks, &s->v_tmp, &s->v_emit, &s->v_place, &s->v_out, &s->v_scan, &s->v_words};
+// the refusals of every call that reads the last finish's tables, in the caller's name (whole: they are there to be read)
+int needs_finish(const pa_stitcher* s, const char* who, bool whole) {
+    if (!s->finished) return pa::set_error(PA_ERR_INVALID, std::string(who) + ": no contig has been finished");
+    if (!whole) return pa::set_error(PA_ERR_INVALID, std::string(who) + ": the last finish gave no sequence (a label that is no base, or it failed)");
+    return PA_OK;
+}
+
+// kernel<true> where there is a `qual` to write, else kernel<false>; `qual` is the kernels' last argument
+template <class Kernel, class... Args>
+void launch_qual(Kernel with, Kernel without, unsigned blocks, hipStream_t stream, uint8_t* qual, Args... args) {
+    (qual ? with : without)<<<blocks, ST_THREADS, 0, stream>>>(args..., qual);
+}
+
+// pa_stitcher_take / pa_stitcher_take_qualities: the filled buffer as it lies, else the pieces in order
+int take_letters(pa_stitcher* s, const Buffer& filled, const Buffer& pieces, char* dst, int64_t capacity, const char* who) {
+    const int64_t length = s->live(FILL) ? s->product[FILL].count : s->sequence_length;
+    if (capacity < length)
+        return pa::set_error(PA_ERR_INVALID, std::string(who) + ": the sequence has " + std::to_string(length) + " letters, room for " +
+                                                 std::to_string(capacity));
+    ST_HIP(hipSetDevice(s->device));
+    if (s->live(FILL)) {
+        if (length > 0) ST_HIP(hipMemcpyAsync(dst, filled.p, (size_t)length, hipMemcpyDeviceToHost, s->stream));
+        ST_HIP(hipStreamSynchronize(s->stream));
+        return PA_OK;
+    }
+    int64_t at = 0;
+    for (const PieceOut& piece : s->pieces) {
+        if (piece.length == 0) continue;
+        ST_HIP(hipMemcpyAsync(dst + at, pieces.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
+        at += piece.length;
+    }
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
+}
+
+// The last finish's tables as the record passes read them, with the per-piece block `w`; the draft window (none), the fill's holes
+// and lead (none) are the caller's to set
+EditTables tables_of(const pa_stitcher* s, const RecordWords& w) {
+    const PieceWords pw{s->f_piece.as<uint8_t>(), w.np};
+    EditTables t;
+    t.slot_base = s->f_base.as<uint32_t>();
+    t.width = s->f_width.as<uint32_t>();
+    t.slots = s->f_slots.as<unsigned long long>();
+    t.letters = s->f_letters.as<uint8_t>();
+    t.place = s->f_place.as<uint32_t>();
+    t.pbase = pw.pbase();
+    t.pmin = pw.pmin();
+    t.letter_shift = w.letter_shift();
+    t.take_index = w.take_index();
+    t.draft = nullptr;
+    t.holes = nullptr;
+    t.n_positions = (uint64_t)s->last_positions;
+    t.n_slots = (uint64_t)s->last_slots;
+    t.n_pieces = (uint32_t)w.np;
+    t.draft_lo = t.draft_span = t.lead = 0;
+    t.qualities = s->contig_qualities ? 1u : 0u;
+    return t;
+}
+
+// The count pass of `rule` into the block sums, the scan of the sums, and the total and the kinds read behind ONE wait.  `between`
+// queues what the caller has to run behind the count pass and read behind the same wait.
+template <class Rule, class Between>
+int count_records(pa_stitcher* s, const EditTables& t, const Rule& rule, uint64_t* sums, unsigned long long* d_kinds, Between between,
+                  uint64_t* total, uint64_t* kinds) {
+    const uint64_t blocks = scan_blocks(t.n_slots);
+    k_record_count<Rule><<<(unsigned)(blocks + 1), ST_THREADS, 0, s->stream>>>(t, rule, sums, d_kinds);
+    ST_HIP(hipGetLastError());
+    const int rc = between();
+    if (rc != PA_OK) return rc;
+    scan_sums(s->stream, sums, blocks + 1, sums + blocks + 1);
+    ST_HIP(hipGetLastError());
+    ST_HIP(hipMemcpyAsync(total, sums + blocks, 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(kinds, d_kinds, 6 * 8, hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipStreamSynchronize(s->stream));
+    return PA_OK;
 }
 
 // Records the write passes left piece after piece in TABLE order (start[p]: where those of table piece p begin, on the device)
@@ -934,10 +1036,9 @@ void pa_stitcher_destroy(pa_stitcher* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
     (void)hipStreamSynchronize(s->stream);
-    for (Buffer* b : buffers_of(s)) b->release();
     for (uint64_t* slab : s->slabs) (void)hipFree(slab);
     if (s->own_stream) (void)hipStreamDestroy(s->stream);
-    delete s;
+    delete s;                                           // (its Buffers free themselves)
 }
 
 }  // extern "C"
@@ -1055,17 +1156,10 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     s->sequence_length = 0;
     s->finished = true;
     s->contig_qualities = s->have_qualities = false;
-    s->have_sequence = s->have_edits = false;
-    s->n_edits = 0;
-    s->filled = false;
-    s->filled_length = s->fill_lead = s->fill_bytes = 0;
+    s->have_sequence = false;
+    s->begin(CALL_FINISH);
     s->draft_held = -1;
-    s->gated = s->withheld_filled = false;
-    s->n_withheld = 0;
-    s->have_variants = false;
-    s->n_variants = s->variant_bytes = 0;
-    s->fill_draft_length = -1;
-    s->last_slots = s->last_positions = s->last_scratch_bytes = 0;
+    s->last_slots = s->last_positions = s->base_bytes = 0;
     s->last_pieces = n_pieces;
     for (int32_t p = 0; p < n_pieces; ++p) {
         piece_first[p] = piece_last[p] = -1;
@@ -1114,18 +1208,12 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
         return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher finish: the contig keeps " + std::to_string(rank_base) +
                                                      " rows, the scatter word ranks 2^48 - 1");
     s->contig_qualities = qualities;
-    // piece words on the device: [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces, then fault, bad label
     const size_t np = (size_t)n_pieces;
-    const size_t off_pmax = np * 4, off_pbase = (np * 8 + 7) / 8 * 8, off_start = off_pbase + np * 8, off_flags = off_start + np * 8;
-    if (!s->f_desc.grow(n_desc * sizeof(ChunkDesc)) || !s->f_piece.grow(off_flags + 16))
+    if (!s->f_desc.grow(n_desc * sizeof(ChunkDesc)) || !s->f_piece.grow(PieceWords::bytes(np)))
         return no_memory("the chunk table", n_desc * sizeof(ChunkDesc));
-    uint8_t* pw = s->f_piece.as<uint8_t>();
-    uint32_t* d_pmin = (uint32_t*)pw;
-    uint32_t* d_pmax = (uint32_t*)(pw + off_pmax);
-    uint64_t* d_pbase = (uint64_t*)(pw + off_pbase);
-    uint64_t* d_start = (uint64_t*)(pw + off_start);
-    uint32_t* d_fault = (uint32_t*)(pw + off_flags);
-    uint32_t* d_bad = d_fault + 1;
+    const PieceWords pw{s->f_piece.as<uint8_t>(), np};
+    uint32_t *d_pmin = pw.pmin(), *d_pmax = pw.pmax(), *d_fault = pw.flags(), *d_bad = pw.flags() + 1;
+    uint64_t *d_pbase = pw.pbase(), *d_start = pw.letter_start();
     ST_HIP(hipMemcpyAsync(s->f_desc.p, desc.data(), n_desc * sizeof(ChunkDesc), hipMemcpyHostToDevice, s->stream));
     ST_HIP(hipMemsetAsync(d_pmin, 0xFF, np * 4, s->stream));
     ST_HIP(hipMemsetAsync(d_pmax, 0, np * 4, s->stream));
@@ -1171,7 +1259,7 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     const uint64_t letter_words = std::max(scan_scratch_words(n_slots), (uint64_t)1);
     if (!s->f_slots.grow(n_slots * 8) || !s->f_letters.grow(n_slots) || !s->f_place.grow(n_slots * 4) || !s->f_words.grow(letter_words * 8))
         return no_memory("the slot table", n_slots * 13);
-    s->last_scratch_bytes = (int64_t)(n_positions * 8 + n_slots * 13 + (scan_words + letter_words) * 8 + n_desc * sizeof(ChunkDesc));
+    s->base_bytes = (int64_t)(n_positions * 8 + n_slots * 13 + (scan_words + letter_words) * 8 + n_desc * sizeof(ChunkDesc));
     ST_HIP(hipMemsetAsync(s->f_slots.p, 0, n_slots * 8, s->stream));
     k_stitch_scatter<<<(unsigned)n_desc, ST_THREADS, 0, s->stream>>>(s->f_desc.as<ChunkDesc>(), d_pmin, d_pbase, s->f_base.as<uint32_t>(),
                                                                       s->f_slots.as<unsigned long long>(), n_positions, n_slots, d_fault);
@@ -1198,17 +1286,12 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
     if (!s->f_out.grow(n_letters + 1)) return no_memory("the sequence", n_letters);
     if (qualities) {
         if (!s->f_qual.grow(n_letters + 1)) return no_memory("the qualities", n_letters);
-        s->last_scratch_bytes += (int64_t)n_letters;
+        s->base_bytes += (int64_t)n_letters;
     }
     if (slot_blocks) {
-        if (qualities)
-            k_stitch_emit<true><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
-                                                                           s->f_slots.as<unsigned long long>(), n_slots, n_letters,
-                                                                           s->f_out.as<uint8_t>(), s->f_qual.as<uint8_t>());
-        else
-            k_stitch_emit<false><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
-                                                                            s->f_slots.as<unsigned long long>(), n_slots, n_letters,
-                                                                            s->f_out.as<uint8_t>(), nullptr);
+        launch_qual(k_stitch_emit<true>, k_stitch_emit<false>, slot_blocks, s->stream, qualities ? s->f_qual.as<uint8_t>() : nullptr,
+                    s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(), s->f_slots.as<unsigned long long>(), n_slots, n_letters,
+                    s->f_out.as<uint8_t>());
         ST_HIP(hipGetLastError());
     }
     k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(d_pbase, n_pieces, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
@@ -1237,65 +1320,27 @@ int pa_stitcher_finish(pa_stitcher* s, int32_t contig, int32_t n_regions, const 
 int pa_stitcher_take(pa_stitcher* s, char* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    const int64_t length = s->filled ? s->filled_length : s->sequence_length;
-    if (capacity < length)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take: the sequence has " + std::to_string(length) + " letters, room for " +
-                                                 std::to_string(capacity));
-    ST_HIP(hipSetDevice(s->device));
-    if (s->filled) {
-        if (length > 0) ST_HIP(hipMemcpyAsync(dst, s->f_fill.p, (size_t)length, hipMemcpyDeviceToHost, s->stream));
-        ST_HIP(hipStreamSynchronize(s->stream));
-        return PA_OK;
-    }
-    int64_t at = 0;
-    for (const PieceOut& piece : s->pieces) {
-        if (piece.length == 0) continue;
-        ST_HIP(hipMemcpyAsync(dst + at, s->f_out.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
-        at += piece.length;
-    }
-    ST_HIP(hipStreamSynchronize(s->stream));
-    return PA_OK;
+    return take_letters(s, s->f_fill, s->f_out, dst, capacity, "stitcher take");
 }
 
 int pa_stitcher_take_qualities(pa_stitcher* s, char* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: no contig has been finished");
+    if (const int rc = needs_finish(s, "stitcher take qualities", s->have_qualities || !s->contig_qualities)) return rc;
     if (!s->have_qualities)
-        return pa::set_error(PA_ERR_INVALID, s->contig_qualities
-                                                 ? "stitcher take qualities: the last finish gave no sequence (a label that is no base, or it failed)"
-                                                 : "stitcher take qualities: the last finish produced none: a chunk of its contig was added "
-                                                   "without qualities (pa_stitcher_add_qual on every chunk asks for them), or it failed early");
-    const int64_t length = s->filled ? s->filled_length : s->sequence_length;
-    if (capacity < length)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: the sequence has " + std::to_string(length) +
-                                                 " letters, room for " + std::to_string(capacity));
-    ST_HIP(hipSetDevice(s->device));
-    if (s->filled) {
-        if (length > 0) ST_HIP(hipMemcpyAsync(dst, s->f_fillq.p, (size_t)length, hipMemcpyDeviceToHost, s->stream));
-        ST_HIP(hipStreamSynchronize(s->stream));
-        return PA_OK;
-    }
-    int64_t at = 0;
-    for (const PieceOut& piece : s->pieces) {
-        if (piece.length == 0) continue;
-        ST_HIP(hipMemcpyAsync(dst + at, s->f_qual.as<uint8_t>() + piece.offset, (size_t)piece.length, hipMemcpyDeviceToHost, s->stream));
-        at += piece.length;
-    }
-    ST_HIP(hipStreamSynchronize(s->stream));
-    return PA_OK;
+        return pa::set_error(PA_ERR_INVALID, "stitcher take qualities: the last finish produced none: a chunk of its contig was added "
+                                             "without qualities (pa_stitcher_add_qual on every chunk asks for them), or it failed early");
+    return take_letters(s, s->f_fillq, s->f_qual, dst, capacity, "stitcher take qualities");
 }
 
 // pa_stitcher_edits under the handle's lock (pa_stitcher_variants makes the records it lacks through it)
 static int edits_locked(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_edits, int64_t* counts) {
     *n_edits = 0;
     for (int k = 0; k < 6; ++k) counts[k] = 0;
-    const bool held = !draft && (s->filled || s->gated) && s->draft_held == draft_length;      // the draft a fill or a gate uploaded
+    const bool held = !draft && (s->live(FILL) || s->live(WITHHELD)) && s->draft_held == draft_length;      // the draft a fill or a gate uploaded
     if (draft_length > 0 && !draft && !held)
         return pa::set_error(PA_ERR_INVALID, "stitcher edits: null draft (only after a pa_stitcher_fill or pa_stitcher_gate of a draft of this length)");
-    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher edits: no contig has been finished");
-    if (!s->have_sequence)
-        return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (const int rc = needs_finish(s, "stitcher edits", s->have_sequence)) return rc;
     if (s->last_pieces > 0xFFFF)
         return pa::set_error(PA_ERR_INVALID, "stitcher edits: the last finish had " + std::to_string(s->last_pieces) +
                                                  " pieces, a record names 65535");
@@ -1307,13 +1352,10 @@ static int edits_locked(pa_stitcher* s, const char* draft, int64_t draft_length,
     if (draft_length <= hi)
         return pa::set_error(PA_ERR_INVALID, "stitcher edits: the draft has " + std::to_string(draft_length) +
                                                  " letters, a piece ends at position " + std::to_string(hi));
-    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);      // asked again: counted once
-    s->have_edits = false;
-    s->n_edits = 0;
+    s->begin(CALL_EDITS);
     const size_t np = (size_t)s->last_pieces;
-    const uint64_t n_slots = (uint64_t)s->last_slots;
-    if (s->pieces.empty() || n_slots == 0) {            // nothing was merged: no record
-        s->have_edits = true;
+    if (s->pieces.empty() || s->last_slots == 0) {      // nothing was merged: no record
+        s->make(EDITS, 0, 0);
         return PA_OK;
     }
     ST_HIP(hipSetDevice(s->device));
@@ -1328,62 +1370,37 @@ static int edits_locked(pa_stitcher* s, const char* draft, int64_t draft_length,
         take_index[(size_t)piece.piece] = (uint16_t)k;
         at += piece.length;
     }
-    const size_t off_start = np * 8, off_kinds = off_start + np * 8, off_index = off_kinds + 6 * 8, piece_bytes = off_index + np * 2;
     const size_t span = (size_t)(hi - lo + 1);
-    if (!s->e_piece.grow(piece_bytes) || !s->e_draft.grow(span)) return no_memory("the draft", span);
-    uint8_t* ew = s->e_piece.as<uint8_t>();
-    int64_t* d_shift = (int64_t*)ew;
-    uint64_t* d_start = (uint64_t*)(ew + off_start);
-    unsigned long long* d_kinds = (unsigned long long*)(ew + off_kinds);
-    uint16_t* d_index = (uint16_t*)(ew + off_index);
-    ST_HIP(hipMemcpyAsync(d_shift, shift.data(), np * 8, hipMemcpyHostToDevice, s->stream));
-    ST_HIP(hipMemcpyAsync(d_index, take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
-    ST_HIP(hipMemsetAsync(d_start, 0, np * 8 + 6 * 8, s->stream));
+    if (!s->e_piece.grow(RecordWords::bytes(np)) || !s->e_draft.grow(span)) return no_memory("the draft", span);
+    const RecordWords w{s->e_piece.as<uint8_t>(), np};
+    ST_HIP(hipMemcpyAsync(w.letter_shift(), shift.data(), np * 8, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(w.take_index(), take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(w.start(), 0, w.answer_bytes(), s->stream));
     if (!held) {
         ST_HIP(hipMemcpyAsync(s->e_draft.p, draft + lo, span, hipMemcpyHostToDevice, s->stream));
         s->draft_held = -1;                             // (behind the fill's kernels on the stream; its whole draft is gone)
     }
-    // the piece words of the finish: [pmin u32 | pmax u32 | pbase u64 | ...] x n_pieces
-    const uint8_t* pw = s->f_piece.as<uint8_t>();
-    EditTables t;
-    t.slot_base = s->f_base.as<uint32_t>();
-    t.width = s->f_width.as<uint32_t>();
-    t.slots = s->f_slots.as<unsigned long long>();
-    t.letters = s->f_letters.as<uint8_t>();
-    t.place = s->f_place.as<uint32_t>();
-    t.pbase = (const uint64_t*)(pw + (np * 8 + 7) / 8 * 8);
-    t.pmin = (const uint32_t*)pw;
-    t.letter_shift = d_shift;
-    t.take_index = d_index;
+    EditTables t = tables_of(s, w);
     t.draft = s->e_draft.as<uint8_t>() + (held ? lo : 0);
-    t.holes = s->filled ? s->f_holes.as<uint32_t>() : nullptr;
-    t.lead = (uint32_t)s->fill_lead;
-    t.n_positions = (uint64_t)s->last_positions;
-    t.n_slots = n_slots;
-    t.n_pieces = (uint32_t)np;
     t.draft_lo = (uint32_t)lo;
     t.draft_span = (uint32_t)span;
-    t.qualities = s->contig_qualities ? 1u : 0u;
-    // count per block (f_words is the letter scan's scratch: sized for n_slots elements, free since the finish), scan the sums
-    const uint64_t blocks = scan_blocks(n_slots);
+    if (s->live(FILL)) {
+        t.holes = s->f_holes.as<uint32_t>();
+        t.lead = (uint32_t)s->fill_lead;
+    }
+    // count per block (f_words is the letter scan's scratch: sized for n_slots elements, free since the finish), scan the sums;
+    // the one wait: the record buffer's size
     uint64_t* sums = s->f_words.as<uint64_t>();
-    k_edit_count<<<(unsigned)(blocks + 1), ST_THREADS, 0, s->stream>>>(t, sums, d_kinds);
-    ST_HIP(hipGetLastError());
-    scan_sums(s->stream, sums, blocks + 1, sums + blocks + 1);
-    ST_HIP(hipGetLastError());
     uint64_t total = 0, kinds[6] = {0, 0, 0, 0, 0, 0};
-    ST_HIP(hipMemcpyAsync(&total, sums + blocks, 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipMemcpyAsync(kinds, d_kinds, 6 * 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipStreamSynchronize(s->stream));            // the one wait: the record buffer's size
+    if (const int rc = count_records(s, t, EditRule(), sums, w.kinds(), [] { return PA_OK; }, &total, kinds)) return rc;
     if (total > 0) {
         if (!s->e_records.grow(total * sizeof(pa_stitch_edit))) return no_memory("the edit records", total * sizeof(pa_stitch_edit));
         // the write is left in flight: take_edits, a later finish and destroy are ordered behind it on the handle's stream
-        k_edit_write<<<(unsigned)blocks, ST_THREADS, 0, s->stream>>>(t, sums, total, s->e_records.as<pa_stitch_edit>(), d_start);
+        k_record_write<EditRule><<<(unsigned)scan_blocks(t.n_slots), ST_THREADS, 0, s->stream>>>(t, EditRule(), sums, total,
+                                                                                                 s->e_records.as<pa_stitch_edit>(), w.start());
         ST_HIP(hipGetLastError());
     }
-    s->last_scratch_bytes += (int64_t)(total * sizeof(pa_stitch_edit));
-    s->n_edits = (int64_t)total;
-    s->have_edits = true;
+    s->make(EDITS, (int64_t)total, (int64_t)(total * sizeof(pa_stitch_edit)));
     *n_edits = (int64_t)total;
     for (int k = 0; k < 6; ++k) counts[k] = (int64_t)kinds[k];
     return PA_OK;
@@ -1400,12 +1417,10 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
     std::lock_guard<std::mutex> guard(s->lock);
     *filled_length = 0;
     counts[0] = counts[1] = 0;
-    const bool held = !draft && s->gated && s->draft_held == draft_length;      // the draft the gate uploaded
+    const bool held = !draft && s->live(WITHHELD) && s->draft_held == draft_length;      // the draft the gate uploaded
     if (draft_length > 0 && !draft && !held)
         return pa::set_error(PA_ERR_INVALID, "stitcher fill: null draft (only after a pa_stitcher_gate of a draft of this length)");
-    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher fill: no contig has been finished");
-    if (!s->have_sequence)
-        return pa::set_error(PA_ERR_INVALID, "stitcher fill: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (const int rc = needs_finish(s, "stitcher fill", s->have_sequence)) return rc;
     if (s->last_pieces > 1)
         return pa::set_error(PA_ERR_INVALID, "stitcher fill: the last finish had " + std::to_string(s->last_pieces) +
                                                  " pieces, a filled consensus is one piece");
@@ -1416,15 +1431,7 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
                                                  " letters, the piece ends at position " + std::to_string(last));
     if (draft_length > ST_MAX_POSITION)
         return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher fill: the draft has " + std::to_string(draft_length) + " letters, an offset counts 2^32 - 1");
-    // asked again, or after edits: counted once, and the records of the consensus as it was are gone
-    s->last_scratch_bytes -= s->fill_bytes;
-    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
-    s->have_edits = s->filled = false;
-    s->n_edits = s->fill_bytes = s->filled_length = s->fill_lead = 0;
-    s->last_scratch_bytes -= s->variant_bytes;          // (and the variants of the consensus as it was)
-    s->have_variants = false;
-    s->n_variants = s->variant_bytes = 0;
-    s->fill_draft_length = -1;
+    s->begin(CALL_FILL);                                // (asked again: counted once)
     if (!held) s->draft_held = -1;
     ST_HIP(hipSetDevice(s->device));
     const uint64_t n_positions = rows ? (uint64_t)s->last_positions : 0, n_slots = (uint64_t)s->last_slots;
@@ -1456,22 +1463,12 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
     if (qual && trail) ST_HIP(hipMemsetAsync(qual + (total - trail), '!', trail, s->stream));
     if (n_positions) {
         const unsigned blocks = (unsigned)((n_positions + ST_THREADS - 1) / ST_THREADS);
-        if (qual)
-            k_stitch_fill<true><<<blocks, ST_THREADS, 0, s->stream>>>(s->f_width.as<uint32_t>(), s->f_base.as<uint32_t>(), s->f_holes.as<uint32_t>(),
-                                                                      s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
-                                                                      s->f_slots.as<unsigned long long>(), d_draft + first, n_positions, n_slots,
-                                                                      n_letters, lead, total, out, qual);
-        else
-            k_stitch_fill<false><<<blocks, ST_THREADS, 0, s->stream>>>(s->f_width.as<uint32_t>(), s->f_base.as<uint32_t>(), s->f_holes.as<uint32_t>(),
-                                                                       s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
-                                                                       s->f_slots.as<unsigned long long>(), d_draft + first, n_positions, n_slots,
-                                                                       n_letters, lead, total, out, nullptr);
+        launch_qual(k_stitch_fill<true>, k_stitch_fill<false>, blocks, s->stream, qual, s->f_width.as<uint32_t>(), s->f_base.as<uint32_t>(),
+                    s->f_holes.as<uint32_t>(), s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(), s->f_slots.as<unsigned long long>(),
+                    d_draft + first, n_positions, n_slots, n_letters, lead, total, out);
         ST_HIP(hipGetLastError());
     }
-    s->fill_bytes = (int64_t)(n_positions * 4 + total * (qualities ? 2 : 1));
-    s->last_scratch_bytes += s->fill_bytes;
-    s->filled = true;
-    s->filled_length = (int64_t)total;
+    s->make(FILL, (int64_t)total, (int64_t)(n_positions * 4 + total * (qualities ? 2 : 1)));
     s->fill_lead = (int64_t)lead;
     s->draft_held = draft_length;
     s->fill_draft_length = draft_length;
@@ -1484,16 +1481,15 @@ int pa_stitcher_fill(pa_stitcher* s, const char* draft, int64_t draft_length, in
 int pa_stitcher_take_edits(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take edits: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (!s->have_edits) return pa::set_error(PA_ERR_INVALID, "stitcher take edits: pa_stitcher_edits has not run since the last finish");
-    if (capacity < s->n_edits)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take edits: there are " + std::to_string(s->n_edits) + " records, room for " +
+    const int64_t n_edits = s->product[EDITS].count;
+    if (!s->live(EDITS)) return pa::set_error(PA_ERR_INVALID, "stitcher take edits: pa_stitcher_edits has not run since the last finish");
+    if (capacity < n_edits)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take edits: there are " + std::to_string(n_edits) + " records, room for " +
                                                  std::to_string(capacity));
-    if (s->n_edits == 0) return PA_OK;
+    if (n_edits == 0) return PA_OK;
     ST_HIP(hipSetDevice(s->device));
-    // where every piece's records begin (table order; the write pass left them)
-    const size_t np = (size_t)s->last_pieces;
-    return take_records(s, (const uint64_t*)(s->e_piece.as<uint8_t>() + np * 8), s->e_records.as<pa_stitch_edit>(), s->n_edits, dst,
-                        "stitcher take edits");
+    return take_records(s, RecordWords{s->e_piece.as<uint8_t>(), (size_t)s->last_pieces}.start(), s->e_records.as<pa_stitch_edit>(), n_edits,
+                        dst, "stitcher take edits");
 }
 
 int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, int32_t min_phred, int64_t* piece_length,
@@ -1501,16 +1497,14 @@ int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, in
     if (!s || !sequence_length || !counts || draft_length < 0 || (draft_length > 0 && !draft))
         return pa::set_error(PA_ERR_INVALID, "stitcher gate: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher gate: no contig has been finished");
-    if (!s->have_sequence)
-        return pa::set_error(PA_ERR_INVALID, "stitcher gate: the last finish gave no sequence (a label that is no base, or it failed)");
+    if (const int rc = needs_finish(s, "stitcher gate", s->have_sequence)) return rc;
     if (!s->contig_qualities)
         return pa::set_error(PA_ERR_INVALID, "stitcher gate: a chunk of the contig was added without qualities (pa_stitcher_add_qual on "
                                              "every chunk gives the gate its phred)");
     if (min_phred < 1 || min_phred > 255)
         return pa::set_error(PA_ERR_INVALID, "stitcher gate: min_phred " + std::to_string(min_phred) + " is outside 1..255");
-    if (s->gated || s->filled)
-        return pa::set_error(PA_ERR_INVALID, std::string("stitcher gate: a ") + (s->gated ? "gate" : "fill") +
+    if (s->live(WITHHELD) || s->live(FILL))
+        return pa::set_error(PA_ERR_INVALID, std::string("stitcher gate: a ") + (s->live(WITHHELD) ? "gate" : "fill") +
                                                  " already ran since the finish (the gate comes first, once)");
     if (s->last_pieces > 0xFFFF)
         return pa::set_error(PA_ERR_INVALID, "stitcher gate: the last finish had " + std::to_string(s->last_pieces) +
@@ -1525,95 +1519,59 @@ int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, in
         return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher gate: the draft has " + std::to_string(draft_length) + " letters, an offset counts 2^32 - 1");
     const size_t np = (size_t)s->last_pieces;
     const uint64_t n_slots = (uint64_t)s->last_slots, n_positions = (uint64_t)s->last_positions;
-    const uint64_t blocks = scan_blocks(n_slots), sum_words = scan_scratch_words(n_slots);
-    const size_t off_start = np * 8, off_kinds = off_start + np * 8, off_index = off_kinds + 4 * 8, off_order = off_index + np * 2,
-                 piece_bytes = off_order + np * 2;
     ST_HIP(hipSetDevice(s->device));
     // (f_scan is the width scan's scratch, free since the finish: here it takes the block sums, sized for the slots)
-    if (!s->e_draft.grow((size_t)draft_length + 1) || !s->g_piece.grow(piece_bytes + 8) || !s->f_scan.grow(sum_words * 8))
+    if (!s->e_draft.grow((size_t)draft_length + 1) || !s->g_piece.grow(RecordWords::bytes(np)) ||
+        !s->f_scan.grow(scan_scratch_words(n_slots) * 8))
         return no_memory("the draft", (uint64_t)draft_length);
-    // records of the ungated consensus are gone
-    if (s->have_edits) s->last_scratch_bytes -= s->n_edits * (int64_t)sizeof(pa_stitch_edit);
-    s->have_edits = false;
-    s->n_edits = 0;
+    s->begin(CALL_GATE);                                // records of the ungated consensus are gone
     s->draft_held = -1;
     for (int k = 0; k < 4; ++k) counts[k] = 0;
     if (draft_length > 0) ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
     if (s->pieces.empty() || n_slots == 0) {            // nothing was merged: nothing to withhold
         ST_HIP(hipStreamSynchronize(s->stream));
         s->draft_held = draft_length;
-        s->gated = true;
-        s->withheld_filled = false;
-        s->n_withheld = 0;
+        s->make(WITHHELD, 0, 0);
         for (size_t p = 0; p < np; ++p) piece_length[p] = 0;
         *sequence_length = s->sequence_length;
         return PA_OK;
     }
-    uint8_t* gw = s->g_piece.as<uint8_t>();
-    int64_t* d_shift = (int64_t*)gw;
-    uint64_t* d_rec_start = (uint64_t*)(gw + off_start);
-    unsigned long long* d_kinds = (unsigned long long*)(gw + off_kinds);
-    uint16_t* d_index = (uint16_t*)(gw + off_index);
-    uint16_t* d_order = (uint16_t*)(gw + off_order);
+    const RecordWords w{s->g_piece.as<uint8_t>(), np};
+    const PieceWords pw{s->f_piece.as<uint8_t>(), np};
     // the pieces' take() order is the finish's: (first, last) do not move
     std::vector<uint16_t> take_index(np, 0), order(s->pieces.size(), 0);
     for (size_t k = 0; k < s->pieces.size(); ++k) {
         take_index[(size_t)s->pieces[k].piece] = (uint16_t)k;
         order[k] = (uint16_t)s->pieces[k].piece;
     }
-    ST_HIP(hipMemcpyAsync(d_index, take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
-    ST_HIP(hipMemcpyAsync(d_order, order.data(), order.size() * 2, hipMemcpyHostToDevice, s->stream));
-    ST_HIP(hipMemsetAsync(d_shift, 0, np * 8 + np * 8 + 4 * 8, s->stream));
-    // the piece words of the finish: [pmin u32 | pmax u32 | pbase u64 | letter_start u64] x n_pieces
-    uint8_t* pw = s->f_piece.as<uint8_t>();
-    const size_t off_pbase = (np * 8 + 7) / 8 * 8;
-    uint64_t* d_pbase = (uint64_t*)(pw + off_pbase);
-    uint64_t* d_start = (uint64_t*)(pw + off_pbase + np * 8);
-    EditTables t;
-    t.slot_base = s->f_base.as<uint32_t>();
-    t.width = s->f_width.as<uint32_t>();
-    t.slots = s->f_slots.as<unsigned long long>();
-    t.letters = s->f_letters.as<uint8_t>();
-    t.place = s->f_place.as<uint32_t>();
-    t.pbase = d_pbase;
-    t.pmin = (const uint32_t*)pw;
-    t.letter_shift = d_shift;
-    t.take_index = d_index;
+    ST_HIP(hipMemcpyAsync(w.take_index(), take_index.data(), np * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemcpyAsync(w.order(), order.data(), order.size() * 2, hipMemcpyHostToDevice, s->stream));
+    ST_HIP(hipMemsetAsync(w.letter_shift(), 0, w.device_bytes(), s->stream));      // (k_gate_shift writes the shifts)
+    EditTables t = tables_of(s, w);
     t.draft = s->e_draft.as<uint8_t>();
-    t.holes = nullptr;
-    t.lead = 0;
-    t.n_positions = n_positions;
-    t.n_slots = n_slots;
-    t.n_pieces = (uint32_t)np;
-    t.draft_lo = 0;
     t.draft_span = (uint32_t)draft_length;
-    t.qualities = 1u;
-    // 1. decide every slot, rewrite its letter, count; 2. the letters' places again, the pieces' starts; 3. scan of the counts
+    const GateRule rule{(uint32_t)min_phred, s->f_letters.as<uint8_t>(), s->f_slots.as<unsigned long long>()};
+    // 1. decide every slot, rewrite its letter, count; 2. the letters' places again, the pieces' starts; 3. scan of the counts;
+    // the one wait: the sizes of the sequence and of the record buffer
     uint64_t* sums = s->f_scan.as<uint64_t>();
-    k_gate_mark<<<(unsigned)(blocks + 1), ST_THREADS, 0, s->stream>>>(t, (uint32_t)min_phred, s->f_letters.as<uint8_t>(), sums, d_kinds);
-    ST_HIP(hipGetLastError());
-    const uint64_t* d_letters_total = scan_exclusive<LoadLetter, uint32_t>(s->stream, LoadLetter{s->f_letters.as<uint8_t>()}, n_slots,
-                                                                           s->f_place.as<uint32_t>(), s->f_words.as<uint64_t>());
-    ST_HIP(hipGetLastError());
-    k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(d_pbase, (int)np, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
-                                                                     n_positions, n_slots, ST_AT_END, d_start);      // (the end: not known yet)
-    ST_HIP(hipGetLastError());
-    k_gate_shift<<<1, 64, 0, s->stream>>>(d_order, (uint32_t)order.size(), d_start, (uint32_t)np, d_letters_total, d_shift);
-    ST_HIP(hipGetLastError());
-    scan_sums(s->stream, sums, blocks + 1, sums + blocks + 1);
-    ST_HIP(hipGetLastError());
-    uint64_t n_letters = 0, total = 0, kinds[4] = {0, 0, 0, 0};
+    uint64_t n_letters = 0, total = 0, kinds[6] = {0, 0, 0, 0, 0, 0};
     std::vector<uint64_t> start(np + 1);
-    ST_HIP(hipMemcpyAsync(&n_letters, d_letters_total, 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipMemcpyAsync(&total, sums + blocks, 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipMemcpyAsync(kinds, d_kinds, 4 * 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipMemcpyAsync(start.data(), d_start, np * 8, hipMemcpyDeviceToHost, s->stream));
-    ST_HIP(hipStreamSynchronize(s->stream));            // the one wait: the sizes of the sequence and of the record buffer
+    const auto places_again = [&]() -> int {
+        const uint64_t* d_letters_total = scan_exclusive<LoadLetter, uint32_t>(s->stream, LoadLetter{s->f_letters.as<uint8_t>()}, n_slots,
+                                                                               s->f_place.as<uint32_t>(), s->f_words.as<uint64_t>());
+        ST_HIP(hipGetLastError());
+        k_stitch_bounds<<<(unsigned)((np + 63) / 64), 64, 0, s->stream>>>(pw.pbase(), (int)np, s->f_base.as<uint32_t>(), s->f_place.as<uint32_t>(),
+                                                                         n_positions, n_slots, ST_AT_END, pw.letter_start());      // (the end: not known yet)
+        ST_HIP(hipGetLastError());
+        k_gate_shift<<<1, 64, 0, s->stream>>>(w.order(), (uint32_t)order.size(), pw.letter_start(), (uint32_t)np, d_letters_total, w.letter_shift());
+        ST_HIP(hipGetLastError());
+        ST_HIP(hipMemcpyAsync(&n_letters, d_letters_total, 8, hipMemcpyDeviceToHost, s->stream));
+        ST_HIP(hipMemcpyAsync(start.data(), pw.letter_start(), np * 8, hipMemcpyDeviceToHost, s->stream));
+        return PA_OK;
+    };
+    if (const int rc = count_records(s, t, rule, sums, w.kinds(), places_again, &total, kinds)) return rc;
     // from here on the tables are the gated ones whatever happens: letters[] and place[] are rewritten
-    const int64_t letters_before = s->sequence_length;
-    s->gated = true;
-    s->withheld_filled = false;
-    s->n_withheld = 0;
+    s->make(WITHHELD, 0, 0);
     s->have_sequence = false;                           // (until the winner words and the sequence agree with them again)
     if (!s->f_out.grow(n_letters + 1) || !s->f_qual.grow(n_letters + 1)) return no_memory("the sequence", n_letters);
     if (total > 0 && !s->g_records.grow(total * sizeof(pa_stitch_edit))) return no_memory("the withheld records", total * sizeof(pa_stitch_edit));
@@ -1628,18 +1586,17 @@ int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, in
     }
     // 4. the records and the winner words, 5. the letters; left in flight: every later call is ordered behind them on the stream
     if (total > 0) {                                    // (nothing withheld: every table and the sequence are as they were)
-        k_gate_write<<<(unsigned)blocks, ST_THREADS, 0, s->stream>>>(t, (uint32_t)min_phred, sums, total, s->g_records.as<pa_stitch_edit>(),
-                                                                    d_rec_start, s->f_slots.as<unsigned long long>());
+        k_record_write<GateRule><<<(unsigned)scan_blocks(n_slots), ST_THREADS, 0, s->stream>>>(t, rule, sums, total,
+                                                                                               s->g_records.as<pa_stitch_edit>(), w.start());
         ST_HIP(hipGetLastError());
-        const unsigned slot_blocks = (unsigned)((n_slots + ST_THREADS - 1) / ST_THREADS);
-        k_stitch_emit<true><<<slot_blocks, ST_THREADS, 0, s->stream>>>(s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(),
-                                                                       s->f_slots.as<unsigned long long>(), n_slots, n_letters,
-                                                                       s->f_out.as<uint8_t>(), s->f_qual.as<uint8_t>());
+        launch_qual(k_stitch_emit<true>, k_stitch_emit<false>, (unsigned)((n_slots + ST_THREADS - 1) / ST_THREADS), s->stream,
+                    s->f_qual.as<uint8_t>(), s->f_letters.as<uint8_t>(), s->f_place.as<uint32_t>(), s->f_slots.as<unsigned long long>(),
+                    n_slots, n_letters, s->f_out.as<uint8_t>());
         ST_HIP(hipGetLastError());
     }
-    s->last_scratch_bytes += (int64_t)(total * sizeof(pa_stitch_edit)) + ((int64_t)n_letters - letters_before);
+    s->make(WITHHELD, (int64_t)total, (int64_t)(total * sizeof(pa_stitch_edit)));
+    s->base_bytes += (int64_t)n_letters - s->sequence_length;      // (the quality buffer follows the sequence's length)
     s->sequence_length = (int64_t)n_letters;
-    s->n_withheld = (int64_t)total;
     s->draft_held = draft_length;
     s->have_sequence = true;
     *sequence_length = (int64_t)n_letters;
@@ -1651,23 +1608,23 @@ int pa_stitcher_gate(pa_stitcher* s, const char* draft, int64_t draft_length, in
 int pa_stitcher_take_withheld(pa_stitcher* s, pa_stitch_edit* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (!s->gated || !s->have_sequence)
+    const int64_t n_withheld = s->product[WITHHELD].count;
+    if (!s->live(WITHHELD) || !s->have_sequence)
         return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: pa_stitcher_gate has not run since the last finish");
-    if (capacity < s->n_withheld)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: there are " + std::to_string(s->n_withheld) + " records, room for " +
+    if (capacity < n_withheld)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take withheld: there are " + std::to_string(n_withheld) + " records, room for " +
                                                  std::to_string(capacity));
-    if (s->n_withheld == 0) return PA_OK;
+    if (n_withheld == 0) return PA_OK;
     ST_HIP(hipSetDevice(s->device));
-    if (s->filled && !s->withheld_filled) {             // a fill came behind the gate: the offsets count its letters, once
-        k_gate_filled_offsets<<<(unsigned)((s->n_withheld + 255) / 256), 256, 0, s->stream>>>(
-            s->g_records.as<pa_stitch_edit>(), (uint64_t)s->n_withheld, s->f_holes.as<uint32_t>(), (uint64_t)s->last_positions,
+    if (s->live(FILL) && !s->withheld_filled) {         // a fill came behind the gate: the offsets count its letters, once
+        k_gate_filled_offsets<<<(unsigned)((n_withheld + 255) / 256), 256, 0, s->stream>>>(
+            s->g_records.as<pa_stitch_edit>(), (uint64_t)n_withheld, s->f_holes.as<uint32_t>(), (uint64_t)s->last_positions,
             (uint32_t)s->pieces[0].first, (uint32_t)s->fill_lead);
         ST_HIP(hipGetLastError());
         s->withheld_filled = true;
     }
-    const size_t np = (size_t)s->last_pieces;
-    return take_records(s, (const uint64_t*)(s->g_piece.as<uint8_t>() + np * 8), s->g_records.as<pa_stitch_edit>(), s->n_withheld, dst,
-                        "stitcher take withheld");
+    return take_records(s, RecordWords{s->g_piece.as<uint8_t>(), (size_t)s->last_pieces}.start(), s->g_records.as<pa_stitch_edit>(),
+                        n_withheld, dst, "stitcher take withheld");
 }
 
 int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length, int64_t* n_variants, int64_t* counts) {
@@ -1675,10 +1632,8 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
     std::lock_guard<std::mutex> guard(s->lock);
     *n_variants = 0;
     for (int k = 0; k < 5; ++k) counts[k] = 0;
-    if (!s->finished) return pa::set_error(PA_ERR_INVALID, "stitcher variants: no contig has been finished");
-    if (!s->have_sequence)
-        return pa::set_error(PA_ERR_INVALID, "stitcher variants: the last finish gave no sequence (a label that is no base, or it failed)");
-    if (!s->filled)
+    if (const int rc = needs_finish(s, "stitcher variants", s->have_sequence)) return rc;
+    if (!s->live(FILL))
         return pa::set_error(PA_ERR_INVALID, "stitcher variants: pa_stitcher_fill has not run since the last finish (the records describe "
                                              "the one complete consensus of the contig)");
     if (draft_length != s->fill_draft_length)
@@ -1688,23 +1643,21 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
         return pa::set_error(PA_ERR_INVALID, "stitcher variants: null draft, and the copy the fill uploaded is gone (a pa_stitcher_edits "
                                              "with a draft of its own replaced it)");
     ST_HIP(hipSetDevice(s->device));
-    s->last_scratch_bytes -= s->variant_bytes;          // asked again: counted once
-    s->have_variants = false;
-    s->n_variants = s->variant_bytes = 0;
+    s->begin(CALL_VARIANTS);                            // (asked again: counted once)
     if (draft && draft_length > 0) {
         if (!s->e_draft.grow((size_t)draft_length + 1)) return no_memory("the draft", (uint64_t)draft_length);
         ST_HIP(hipMemcpyAsync(s->e_draft.p, draft, (size_t)draft_length, hipMemcpyHostToDevice, s->stream));
         ST_HIP(hipStreamSynchronize(s->stream));        // the caller's draft is free again
         s->draft_held = draft_length;
     }
-    if (!s->have_edits) {                               // the one comparison there is: the records of the filled consensus
+    if (!s->live(EDITS)) {                              // the one comparison there is: the records of the filled consensus
         int64_t n_edits = 0, kinds[6];
         const int rc = edits_locked(s, nullptr, draft_length, &n_edits, kinds);
         if (rc != PA_OK) return rc;
     }
-    const uint64_t n = (uint64_t)s->n_edits;
+    const uint64_t n = (uint64_t)s->product[EDITS].count;
     if (n == 0) {
-        s->have_variants = true;
+        s->make(VARIANTS, 0, 0);
         return PA_OK;
     }
     VarTables t;
@@ -1713,7 +1666,7 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
     t.cons = s->f_fill.as<uint8_t>();
     t.n_records = n;
     t.draft_length = (uint64_t)draft_length;
-    t.cons_length = (uint64_t)s->filled_length;
+    t.cons_length = (uint64_t)s->product[FILL].count;
     // 1. the hunks: heads by the joining rule, scanned
     if (!s->v_before.grow(n * 4) || !s->v_scan.grow(std::max(scan_scratch_words(n), (uint64_t)1) * 8) || !s->v_words.grow(64))
         return no_memory("the hunk heads", n * 4);
@@ -1725,9 +1678,7 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
     ST_HIP(hipStreamSynchronize(s->stream));            // the first wait: the size of the hunk tables
     int64_t bytes = (int64_t)(n * 4);
     if (n_hunks == 0) {                                  // GAP records alone
-        s->variant_bytes = bytes;
-        s->last_scratch_bytes += bytes;
-        s->have_variants = true;
+        s->make(VARIANTS, 0, bytes);
         return PA_OK;
     }
     if (n_hunks > 0xFFFFFFFEull) return pa::set_error(PA_ERR_UNSUPPORTED, "stitcher variants: more than 2^32 - 2 hunks");
@@ -1770,10 +1721,7 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
         ST_HIP(hipGetLastError());
     }
     bytes += (int64_t)(kept * sizeof(pa_stitch_variant));
-    s->variant_bytes = bytes;
-    s->last_scratch_bytes += bytes;
-    s->n_variants = (int64_t)kept;
-    s->have_variants = true;
+    s->make(VARIANTS, (int64_t)kept, bytes);
     *n_variants = (int64_t)kept;
     counts[0] = (int64_t)kept;
     for (int k = 1; k < 5; ++k) counts[k] = (int64_t)host_counts[k];
@@ -1783,13 +1731,14 @@ int pa_stitcher_variants(pa_stitcher* s, const char* draft, int64_t draft_length
 int pa_stitcher_take_variants(pa_stitcher* s, pa_stitch_variant* dst, int64_t capacity) {
     if (!s || capacity < 0 || (capacity > 0 && !dst)) return pa::set_error(PA_ERR_INVALID, "stitcher take variants: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
-    if (!s->have_variants) return pa::set_error(PA_ERR_INVALID, "stitcher take variants: pa_stitcher_variants has not run since the last finish");
-    if (capacity < s->n_variants)
-        return pa::set_error(PA_ERR_INVALID, "stitcher take variants: there are " + std::to_string(s->n_variants) + " records, room for " +
+    const int64_t n_variants = s->product[VARIANTS].count;
+    if (!s->live(VARIANTS)) return pa::set_error(PA_ERR_INVALID, "stitcher take variants: pa_stitcher_variants has not run since the last finish");
+    if (capacity < n_variants)
+        return pa::set_error(PA_ERR_INVALID, "stitcher take variants: there are " + std::to_string(n_variants) + " records, room for " +
                                                  std::to_string(capacity));
-    if (s->n_variants == 0) return PA_OK;
+    if (n_variants == 0) return PA_OK;
     ST_HIP(hipSetDevice(s->device));
-    ST_HIP(hipMemcpyAsync(dst, s->v_out.p, (size_t)s->n_variants * sizeof(pa_stitch_variant), hipMemcpyDeviceToHost, s->stream));
+    ST_HIP(hipMemcpyAsync(dst, s->v_out.p, (size_t)n_variants * sizeof(pa_stitch_variant), hipMemcpyDeviceToHost, s->stream));
     ST_HIP(hipStreamSynchronize(s->stream));
     return PA_OK;
 }
@@ -1798,7 +1747,7 @@ int pa_stitcher_stats(pa_stitcher* s, int64_t* out, int32_t n) {
     if (!s || !out || n < 0) return pa::set_error(PA_ERR_INVALID, "stitcher stats: null or negative argument");
     std::lock_guard<std::mutex> guard(s->lock);
     const int64_t v[6] = {s->rows_held, (int64_t)s->slabs.size() * ST_SLAB_ROWS * 8, s->last_slots, s->last_pieces, s->last_positions,
-                          s->last_scratch_bytes};
+                          s->table_bytes()};
     for (int32_t i = 0; i < n; ++i) out[i] = i < 6 ? v[i] : 0;
     return PA_OK;
 }

@@ -301,14 +301,24 @@ class DeviceStitcher(object):
         with self._lock:
             if not self.last_gated:
                 raise _lib.PepperAmdError("the last finish had no min_quality")
-            if self._withheld is None:
-                t0 = time.perf_counter()
-                records = np.zeros(self.last_gate_counts[0], Edits.EDIT_DTYPE)
-                _lib.check(self._lib.pa_stitcher_take_withheld(self.handle, records.ctypes.data, len(records)))
-                self._withheld = records
-                self.gate_totals["bytes_returned"] += records.nbytes
-                self.gate_totals["seconds"] += time.perf_counter() - t0
+            if self._withheld is None:                               # (the gate made them and said how many)
+                self._withheld, _ = self._records(None, self.last_gate_counts[0], self._lib.pa_stitcher_take_withheld, Edits.EDIT_DTYPE,
+                                                  self.gate_totals, "seconds")
             return self._withheld
+
+    def _records(self, make, n_counts, take, dtype, totals, seconds):
+        """Under the lock: make(n, counts), the call that makes the records and counts them (None: they are made, n_counts of
+        them); a buffer of that many; `take`; totals["bytes_returned"] and totals[seconds] grow.  -> (records, counts or None)"""
+        t0 = time.perf_counter()
+        n, counts = ctypes.c_int64(n_counts), None
+        if make is not None:
+            counts = (ctypes.c_int64 * n_counts)()
+            _lib.check(make(ctypes.byref(n), counts))
+        records = np.zeros(n.value, dtype)
+        _lib.check(take(self.handle, records.ctypes.data, n.value))
+        totals["bytes_returned"] += records.nbytes
+        totals[seconds] += time.perf_counter() - t0
+        return records, None if counts is None else [int(v) for v in counts]
 
     def applied_counts(self, draft_length):
         """After finish(min_quality=): the applied edits [SUB, DEL, INS], counted on the device against the draft the gate left
@@ -338,16 +348,11 @@ class DeviceStitcher(object):
             if self.last_filled and not self.last_pieces:            # the draft as it is: nothing was merged, no record
                 self.last_edit_counts = [0] * 6
                 return np.zeros(0, Edits.EDIT_DTYPE)
-            t0 = time.perf_counter()
-            n, counts = ctypes.c_int64(), (ctypes.c_int64 * 6)()
             held = self.last_filled or (self.last_gated and bool(self.last_pieces))      # a fill or a gate left its copy of the draft
-            _lib.check(self._lib.pa_stitcher_edits(self.handle, None if held else draft, len(draft), ctypes.byref(n), counts))
-            records = np.zeros(n.value, Edits.EDIT_DTYPE)
-            _lib.check(self._lib.pa_stitcher_take_edits(self.handle, records.ctypes.data, n.value))
-            self.last_edit_counts = [int(v) for v in counts]
-            self.edit_totals["records"] += n.value
-            self.edit_totals["bytes_returned"] += n.value * Edits.EDIT_DTYPE.itemsize
-            self.edit_totals["seconds_compare"] += time.perf_counter() - t0
+            make = lambda n, counts: self._lib.pa_stitcher_edits(self.handle, None if held else draft, len(draft), n, counts)
+            records, self.last_edit_counts = self._records(make, 6, self._lib.pa_stitcher_take_edits, Edits.EDIT_DTYPE, self.edit_totals,
+                                                           "seconds_compare")
+            self.edit_totals["records"] += len(records)
         return records
 
     def variants(self, draft_sequence):
@@ -363,16 +368,11 @@ class DeviceStitcher(object):
             if not self.last_pieces:                                 # the draft as it is: nothing was merged, no record
                 self.last_variant_counts = [0] * 5
                 return np.zeros(0, Variants.VARIANT_DTYPE)
-            t0 = time.perf_counter()
-            n, counts = ctypes.c_int64(), (ctypes.c_int64 * 5)()
-            _lib.check(self._lib.pa_stitcher_variants(self.handle, None, len(draft), ctypes.byref(n), counts))
-            records = np.zeros(n.value, Variants.VARIANT_DTYPE)
-            _lib.check(self._lib.pa_stitcher_take_variants(self.handle, records.ctypes.data, n.value))
-            self.last_variant_counts = [int(v) for v in counts]
+            make = lambda n, counts: self._lib.pa_stitcher_variants(self.handle, None, len(draft), n, counts)
+            records, self.last_variant_counts = self._records(make, 5, self._lib.pa_stitcher_take_variants, Variants.VARIANT_DTYPE,
+                                                              self.variant_totals, "seconds_device")
             for name, v in zip(("records", "noops", "unanchored", "shifted"), self.last_variant_counts):
                 self.variant_totals[name] += v
-            self.variant_totals["bytes_returned"] += records.nbytes
-            self.variant_totals["seconds_device"] += time.perf_counter() - t0
         return records
 
     def _write_variants(self, vcf_file, contig, stored, sequence):
