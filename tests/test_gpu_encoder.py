@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import pileup_utils as pu
+import variant_encoder_cases as vc
 from test_encoder_oracle import CASES, PRESET_CASES, _case, preset_case
 
 pytestmark = pytest.mark.gpu
@@ -251,8 +252,24 @@ def test_encoder_object_interface_and_edges():
     assert [o.position for o in objs] == want["positions"].tolist()
     assert np.array_equal(np.array([o.image_matrix for o in objs]), want["images"])
     assert objs[0].contig == "chr20" and objs[0].candidate_frequency == [int(want["candidate_frequency"][0])]
-    # windows of candidates within 16 rows of the region edges are zero padded
-    assert want["positions"].min() < 5016 or want["positions"].max() > 5784 or True
+    # windows of candidates within 16 rows of the region edges are zero padded: tests/variant_encoder_cases.py region_edges / snp
+    # has a SNP candidate on rows 0, 1, 15, 16, 17, L - 18, L - 17, L - 16, L - 2 and L - 1 of a region of L = 100 rows.  Window
+    # row w of a candidate on row r shows row r - 16 + w; every row inside the region holds its reference code, row L is all zero
+    case = vc.region_edges()["snp"]
+    n_rows = case[1] - case[0] + 1
+    edge = _product(vc.pileup(case), vc.params(case))
+    _check(edge, pu.run_variant(oracle, vc.pileup(case), vc.params(case)))
+    rows = (edge["positions"] - case[0]).tolist()
+    assert rows == list(vc.EDGE_SITES) and min(rows) == 0 and max(rows) == n_rows - 1
+    for r, img in zip(rows, edge["images_int32"]):
+        if r < 16:
+            assert not img[:16 - r].any() and img[16 - r].any(), r             # rows 0 .. 15 - r lie in front of the region
+        else:
+            assert img[0].any(), r
+        if r >= n_rows - 16:
+            assert img[n_rows - 1 - r + 16].any() and not img[n_rows - r + 16:].any(), r    # row L and everything behind it
+        else:
+            assert img[32].any(), r
     # empty pileup
     empty = pu.FlatPileup(5000, 5800, ref, [])
     assert _product(empty, params)["candidates"] == []
